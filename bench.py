@@ -19,7 +19,10 @@ timed step contains the RCCL exchange of sylber_amd/dist.py::ShardedSegmenter.ru
 waveform blocks over xGMI, every rank encodes + segments its block, root gathers hidden states, segment tables,
 counts and pooled features; the gather of step i travels under the compute of step i+1.  The resident-shard
 figure (no data-path collective) is reported next to it as ``resident_shards``.  ``--no-exchange`` swaps the two.
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0; ``ms_per_step`` is the wall time of the K timed steps divided by K.
+
+``--dump-outputs DIR`` writes what the path behind ``value`` computed in its last timed step, as rank 0 holds it, to DIR/<name>.npy
+(dump_outputs below).  Inputs and weights are seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import hashlib
@@ -31,11 +34,6 @@ import time
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
-# ROCm multiplexes a process's HIP streams onto GPU_MAX_HW_QUEUES hardware queues (default 4), and streams that share a queue run
-# strictly one after the other (sylber_amd/streams.py).  The N > 1 step keeps two engine streams, two side streams and RCCL's own
-# stream busy: with 4 queues RCCL's gather would share one with a compute stream and hold its kernels back.  Must be set before
-# HIP initialises; harmless at N = 1 (measured: 4.87 vs 4.87 ms).
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 
 CLIP_SAMPLES = 160000
 CLIP_SECONDS = 10.0
@@ -116,15 +114,78 @@ def parse_args():
                     help="skip the one-rank RCCL self-test child of `other_configs` (the N > 1 code path on this one GPU)")
     ap.add_argument("--agreement-clips", type=int, default=0,
                     help="also report bf16-vs-fp32 segment agreement on this many synthetic clips (fp32 parity mode as truth)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step (rank 0) as DIR/<name>.npy: "
+                         "hidden_states, segments, segment_counts, segment_features (float32 / float64, all finite: table slots past an "
+                         "utterance's count hold -1, feature rows there and frames past a ragged clip's end hold 0); at most 64 MB in all, "
+                         "beyond that a fixed seeded sample of rows (indices in DIR/<name>_rows.npy)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
+
+
+DUMP_BYTES = 64 * 10 ** 6          # everything --dump-outputs writes, .npy headers included
+DUMP_SEED = 0
+
+
+def host_outputs(hidden, seg, nseg, feats, valid_frames=None) -> dict:
+    """the four device tensors of one step as the host arrays a caller would read.  Rows that are not part of the output get fixed,
+    finite values instead of stale buffer contents: table slots past an utterance's segment count hold -1 (no frame index), pooled
+    feature rows there hold 0 (the reference zero-pads its avg_fts the same way, sylber.py:238-241), and so do the frames past a
+    ragged clip's end; segment_counts says which rows are real"""
+    import numpy as np
+    out = {"hidden_states": hidden.float().cpu().numpy().copy()}          # (copies: the masking below must not reach the tensors)
+    if valid_frames is not None:
+        for i, n in enumerate(valid_frames):
+            out["hidden_states"][i, n:] = 0.0
+    if seg is not None:
+        counts = nseg.cpu().numpy().astype(np.int64)
+        out["segments"] = seg.cpu().numpy().astype(np.float64)
+        out["segment_counts"] = counts.astype(np.float64)
+        out["segment_features"] = feats.float().cpu().numpy().copy()
+        for i, n in enumerate(counts):
+            out["segments"][i, n:] = -1.0
+            out["segment_features"][i, n:] = 0.0
+    return out
+
+
+def dump_outputs(out_dir: str, arrays: dict, budget: int = DUMP_BYTES) -> dict:
+    """writes every array as out_dir/<name>.npy (float32 stays float32, anything else becomes float64) within `budget` bytes.
+    Small arrays are written whole; an array larger than its share of what is left keeps a fixed, seeded sample of the rows of
+    its last axis, in ascending order, and the flat row indices go to out_dir/<name>_rows.npy.  The sample depends on the array's
+    shape alone, so runs with the same arguments write the same rows.  Returns {name: shape written}."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    header = 128                                           # a .npy header of these shapes
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float32 if v.dtype == np.float32 else np.float64) for k, v in arrays.items()}
+    left, n_left, written = budget, len(arrays), {}
+    for name in sorted(arrays, key=lambda k: (arrays[k].nbytes, k)):       # smallest first: what they leave goes to the larger ones
+        a = arrays[name]
+        share = left // n_left - 2 * header
+        if a.nbytes > share:
+            rows = a.reshape(-1, a.shape[-1] if a.ndim > 1 else 1)
+            k = max(0, share // (rows.shape[1] * rows.itemsize + 8))
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(len(rows), size=k, replace=False))
+            np.save(os.path.join(out_dir, name + "_rows.npy"), idx.astype(np.float64))
+            left -= os.path.getsize(os.path.join(out_dir, name + "_rows.npy"))
+            a = rows[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        left -= os.path.getsize(os.path.join(out_dir, name + ".npy"))
+        n_left -= 1
+        written[name] = list(a.shape)
+    assert left >= 0, "--dump-outputs overran its budget"
+    return written
 
 
 def maybe_spawn(args):
-    """`python bench.py --gpus N` without a launcher: become N ranks."""
+    """`python bench.py --gpus N` without a launcher: run N ranks as children and exit with their status.  The GPUs are
+    counted in a short-lived child, so that this parent never opens a device."""
     if args.gpus <= 1 or "WORLD_SIZE" in os.environ:
         return
-    import torch
-    have = torch.cuda.device_count()
+    import subprocess
+    r = subprocess.run([sys.executable, "-c", "import torch; print(torch.cuda.device_count())"], capture_output=True, text=True)
+    have = int(r.stdout.strip()) if r.returncode == 0 and r.stdout.strip().isdigit() else 0
     if have < args.gpus:
         sys.stderr.write("bench.py: --gpus %d requested but only %d GPU(s) are visible to PyTorch-ROCm; refusing to "
                          "oversubscribe (one rank per GPU)\n" % (args.gpus, have))
@@ -136,7 +197,9 @@ def maybe_spawn(args):
     os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(args.gpus),
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
-    os.execv(sys.executable, cmd)
+    sys.stdout.flush()
+    rc = subprocess.run(cmd).returncode
+    sys.exit(rc if rc >= 0 else 128 - rc)
 
 
 def gemm_flops_per_forward(B: int, n_samples: int = CLIP_SAMPLES) -> dict:
@@ -640,6 +703,8 @@ def main():
         host_issue["s"], host_issue["n"] = time.perf_counter() - t_issue0, n
         return evs
 
+    last_exchange = {}                                   # --dump-outputs: the result the loop yielded last (rank 0)
+
     def _exchange_loop(src, n, evs):
         for _o in sharded.run_stream(src, None, max_segments=min(T_frames, 192), ingest=args.ingest,
                                      host_shards=[host_shard] * n if host_shard is not None else None, gather=gather_mode["m"],
@@ -647,6 +712,8 @@ def main():
             ev = torch.cuda.Event(enable_timing=True)
             ev.record(torch.cuda.current_stream(dev))
             evs.append(ev)
+            if args.dump_outputs and rank == 0:
+                last_exchange["out"] = _o
 
     ex_txt = ("root scatter over RCCL in every step, results left on their ranks (gather=none)" if args.gather == "none" else
               "root scatter + gather over RCCL in every step (run_stream: gather(i) overlapped with compute(i+1))"
@@ -705,6 +772,22 @@ def main():
     want_exchange = world > 1 or selftest                      # --no-exchange only swaps which figure is `value`
     r_elapsed, r_med = timed(resident_steps)
     r_per_rank = per_rank.get("last")
+    # --dump-outputs: the last timed step's results, copied to the host once the timed region has ended (the closing barrier has
+    # drained every stream); the path whose figure becomes `value` is written at the end
+    dumps = {}
+
+    def write_dump(path):
+        info = {"dir": args.dump_outputs, "path": path, "steps": args.steps}
+        try:
+            info["arrays"] = dump_outputs(args.dump_outputs, dumps[path])
+        except Exception as e:  # noqa: BLE001 - the measurement stays valid; the line says why the dump is missing
+            info["error"] = "%s: %s" % (type(e).__name__, e)
+        return info
+
+    if args.dump_outputs and rank == 0:
+        hidden_, seg_out_ = bufs[(state["i"] - 1) % NSETS]
+        dumps["resident"] = host_outputs(hidden_, *(seg_out_ if not args.skip_segment else (None, None, None)),
+                                         valid_frames=None if lengths is None else [enc.num_frames(n) for n in lengths])
     x_info = None
     total_audio = world * valid_seconds * args.steps           # (ragged: rank 0's draw stands for every rank)
     elapsed, med_ms = r_elapsed, r_med
@@ -725,6 +808,8 @@ def main():
                     fb = build_line(total_audio / xe, xe, xm, True)
                     fb["resident_shards"] = {"value": round(total_audio / r_elapsed, 1), "unit": "audio-sec/s", "ms_per_step": round(1e3 * r_elapsed / args.steps, 3)}
                     fb["results_left_sharded"] = {"error": "did not finish within the watchdog's %d s; rank 0 was in: %s" % (args.exchange_timeout, sharded.phase)}
+                    if "exchange" in dumps:
+                        fb["dump_outputs"] = write_dump("exchange")
                     sys.stdout.flush()
                     print(json.dumps(fb), flush=True)
                     os._exit(0)
@@ -734,6 +819,8 @@ def main():
                 w = rccl_warnings()
                 if w:
                     fb["exchange_error"] += "; RCCL: " + w
+                if "resident" in dumps:
+                    fb["dump_outputs"] = write_dump("resident")
                 sys.stdout.flush()
                 print(json.dumps(fb), flush=True)
             os._exit(0)
@@ -747,6 +834,8 @@ def main():
             ms0_ = torch.cuda.memory_stats(dev)
             x_elapsed, x_med = timed(exchange_steps, warmup=0)
             ms1_ = torch.cuda.memory_stats(dev)
+            if last_exchange.get("out") is not None:         # (before the pass below reuses the ring that holds it)
+                dumps["exchange"] = host_outputs(*last_exchange.pop("out"))
             st_ = sharded.stats
             x_info = {"per_rank_ms_per_step": per_rank.get("last"),
                       "root_wait_ms_per_step": round(1e3 * st_["wait_s"] / max(st_["steps"], 1), 3),
@@ -1053,6 +1142,8 @@ def main():
             line["other_configs"] = other
         if args.skip_segment:
             line["invalid"] = "--skip-segment: boundary detection left out of the timed steps (A/B measurement only)"
+        if args.dump_outputs:
+            line["dump_outputs"] = write_dump("exchange" if exchange_first else "resident")
     if world > 1 or selftest:
         dist.barrier()
         dist.destroy_process_group()

@@ -1,6 +1,6 @@
 """HIP streams that really run concurrently.
 
-ROCm multiplexes a process's HIP streams onto a handful of hardware queues (GPU_MAX_HW_QUEUES, 4 by default); two streams that
+ROCm multiplexes a process's HIP streams onto a handful of hardware queues (four by default; the HIP runtime's GPU_MAX_HW_QUEUES); two streams that
 land on the SAME hardware queue execute strictly one after the other, whatever the program's dependencies say.  Which streams
 share a queue depends on the order in which the process first used its streams (measured on MI355X / ROCm 7.2,
 tools/stream_queue_probe.py: of ten pool streams, {0,7} {1,6,null} {2,5,9} {3,4,8} serialise).  A two-batches-in-flight

@@ -83,3 +83,62 @@ def test_exchange_rehearsal_child_failure_is_reported_not_raised():
     import bench
     r = bench.exchange_rehearsal(timeout_s=300)
     assert set(r) == {"error"} and "self-test child" in r["error"]
+
+
+def test_steps_must_be_at_least_one():
+    r = run("--steps", "0")
+    assert r.returncode == 2 and "--steps" in r.stderr
+    assert "{" not in r.stdout
+
+
+def test_dump_outputs_fits_the_budget_with_a_fixed_sample(tmp_path):
+    """--dump-outputs on the default workload's four arrays (98 MB): at most 64 MB in all, small arrays whole, the large ones a
+    seeded sample of rows that depends on the shapes alone, so that two runs write the same rows"""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    rng = np.random.default_rng(5)
+    B, T = 32, 499
+    arrays = {"hidden_states": rng.standard_normal((B, T, 768), dtype=np.float32),
+              "segments": rng.integers(0, T, (B, T, 2)).astype(np.float64),
+              "segment_counts": rng.integers(0, T, B).astype(np.float64),
+              "segment_features": rng.standard_normal((B, T, 768), dtype=np.float32)}
+    shapes = bench.dump_outputs(str(tmp_path / "a"), arrays)
+    files = sorted((tmp_path / "a").iterdir())
+    assert sum(f.stat().st_size for f in files) <= bench.DUMP_BYTES
+    assert shapes["segments"] == [B, T, 2] and shapes["segment_counts"] == [B]
+    assert {f.name for f in files} == {"hidden_states.npy", "hidden_states_rows.npy", "segments.npy", "segment_counts.npy",
+                                       "segment_features.npy", "segment_features_rows.npy"}
+    for f in files:
+        assert np.load(f).dtype in (np.float32, np.float64), f.name
+    for name in ("hidden_states", "segment_features"):
+        got, rows = np.load(tmp_path / "a" / (name + ".npy")), np.load(tmp_path / "a" / (name + "_rows.npy"))
+        assert got.dtype == np.float32 and len(got) == len(rows) > 8000 and np.all(np.diff(rows) > 0)
+        assert np.array_equal(got, arrays[name].reshape(-1, 768)[rows.astype(np.int64)])
+    assert np.array_equal(np.load(tmp_path / "a" / "segments.npy"), arrays["segments"])
+    bench.dump_outputs(str(tmp_path / "b"), {k: v + 1 for k, v in arrays.items()})
+    for name in ("hidden_states_rows", "segment_features_rows"):
+        assert np.array_equal(np.load(tmp_path / "a" / (name + ".npy")), np.load(tmp_path / "b" / (name + ".npy")))
+    bench.dump_outputs(str(tmp_path / "c"), {"x": np.arange(10, dtype=np.int32)})
+    x = np.load(tmp_path / "c" / "x.npy")
+    assert x.dtype == np.float64 and np.array_equal(x, np.arange(10)) and not (tmp_path / "c" / "x_rows.npy").exists()
+
+
+def test_host_outputs_mark_rows_outside_the_output():
+    """table slots past an utterance's count are -1, feature rows there and frames past a ragged clip's end are 0: finite, fixed values
+    (not stale buffer contents)"""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    hidden, feats = torch.randn(2, 5, 768), torch.randn(2, 5, 768)
+    seg = torch.arange(20, dtype=torch.int64).reshape(2, 5, 2)
+    out = bench.host_outputs(hidden, seg, torch.tensor([2, 0], dtype=torch.int32), feats, valid_frames=[5, 3])
+    assert out["hidden_states"].dtype == np.float32 and out["segments"].dtype == np.float64
+    assert np.array_equal(out["hidden_states"][0], hidden[0].numpy()) and np.array_equal(out["hidden_states"][1, :3], hidden[1, :3].numpy())
+    assert (out["hidden_states"][1, 3:] == 0).all()
+    assert all(np.isfinite(a).all() for a in out.values())
+    assert np.array_equal(out["segments"][0, :2], seg[0, :2].numpy()) and (out["segments"][0, 2:] == -1).all()
+    assert (out["segments"][1] == -1).all() and (out["segment_features"][1] == 0).all()
+    assert np.array_equal(out["segment_features"][0, :2], feats[0, :2].numpy()) and (out["segment_features"][0, 2:] == 0).all()
+    assert np.array_equal(out["segment_counts"], [2.0, 0.0])

@@ -187,15 +187,23 @@ def test_watchdog_line_is_complete_and_names_the_phase():
     assert any(w in err for w in ("scatter", "gather", "compute", "idle")), err
 
 
+def _hw_queues() -> int:
+    """hardware queues HIP gives this process per device: GPU_MAX_HW_QUEUES, the runtime's default 4 when unset"""
+    return int(os.environ.get("GPU_MAX_HW_QUEUES", "4"))
+
+
 def test_pipeline_streams_are_on_different_hardware_queues():
     """sylber_amd/streams.py: the streams the two-batches-in-flight pipelines use must run kernels concurrently (HIP streams that
     share a hardware queue run one after the other, whatever the program's dependencies say)"""
     import torch
     from sylber_amd.streams import concurrent_streams, serialised
+    q = _hw_queues()
     st = concurrent_streams(4, "cuda:0")
     assert len(st) == 4 and len({s.cuda_stream for s in st}) == 4
     assert not serialised(st[0], st[1])                      # the two compute streams
-    assert sum(serialised(st[i], st[j]) for i in range(4) for j in range(i + 1, 4)) <= 1   # (4 hardware queues by default)
+    # four streams on q queues share at least `forced` pairs (none with the default 4 queues); the probe may miss one more
+    forced = sum(c * (c - 1) // 2 for c in (4 // q + (i < 4 % q) for i in range(q))) if q < 4 else 0
+    assert sum(serialised(st[i], st[j]) for i in range(4) for j in range(i + 1, 4)) <= forced + 1
     assert serialised(st[0], st[0])                          # the probe itself: one stream against itself is serial
 
 
@@ -206,13 +214,14 @@ def test_concurrent_streams_are_leased_not_shared():
     import torch
     from sylber_amd import streams as S
     S._LEASES.clear()                                        # (earlier tests of this process hold leases they never return)
-    a = S.concurrent_streams(2, "cuda")
-    b = S.concurrent_streams(2, "cuda:0")
+    n = min(2, _hw_queues() // 2)                            # two owners, together no more streams than hardware queues (2 each by default)
+    a = S.concurrent_streams(n, "cuda")
+    b = S.concurrent_streams(n, "cuda:0")
     ids = lambda st: {int(x.cuda_stream) for x in st}
-    assert len(ids(a)) == 2 and len(ids(b)) == 2
+    assert n >= 1 and len(ids(a)) == n and len(ids(b)) == n
     assert not (ids(a) & ids(b)), "two owners were handed the same streams while unused independent ones existed"
     S.release_streams(a)
-    c = S.concurrent_streams(2, "cuda:0")
+    c = S.concurrent_streams(n, "cuda:0")
     assert ids(c) == ids(a), "released streams go out again before anything is shared"
     S.release_streams(b)
     S.release_streams(c)

@@ -63,19 +63,14 @@ def test_edge_cases_shapes():
     assert np.array_equal(r, np.array([[0, 1]]))
 
 
-@pytest.mark.reference
-def test_oracle_vs_live_reference():
-    import sys
-    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(__file__)), "tools"))
-    import ref_shim
-    if not ref_shim.available():
-        pytest.skip("reference checkout not present")
-    _, seg_utils, _ = ref_shim.load()
-    import warnings
-    warnings.simplefilter("ignore")
-    for seed in range(40):
-        T = [5, 77, 300][seed % 3]
-        st = syllable_states(T, 9000 + seed, mode=["normal", "edge", "long"][seed % 3])
-        r = seg_utils.get_segment(st, 2.6, 0.8)
+def test_oracle_vs_reference_seeded_states(golden_dir):
+    """the reference's own get_segment on 40 seeded state sequences, stored by tools/gen_golden_seeded_segment.py"""
+    g = np.load(os.path.join(golden_dir, "segment_seeded.npz"))
+    off = g["offsets"]
+    assert len(g["seed"]) == 40
+    for i in range(len(g["seed"])):
+        st = syllable_states(int(g["T"][i]), int(g["seed"][i]), mode=str(g["mode"][i]))
+        assert st.astype(np.float64).sum() == g["state_sum"][i], i   # the inputs the reference saw
         o = segment_oracle.get_segment(st, 2.6, 0.8)
-        assert r.shape == o.shape and np.array_equal(r, o)
+        exp = g["segments"][off[i]:off[i + 1]]
+        assert o.dtype == np.int64 and np.array_equal(o, exp), i

@@ -3,7 +3,6 @@ step's hidden states, segment tables, counts and pooled features compared bit fo
 (LDS-DMA hazards, stream ordering, workspace aliasing) would show up as a mismatch.   python tools/soak.py [steps] [precision] [clips = 32]
 (24 clips: FFN1 / conv5 on the 192-row tile 46; 4 clips: the eight-wave small tiles)"""
 import os, sys, time
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from sylber_amd import HubertEncoderHIP
