@@ -262,6 +262,45 @@ int sylber_set_graph_mode(sylber_t h, int32_t enable);
 /* bytes of device workspace currently held by the handle */
 int64_t sylber_workspace_bytes(sylber_t h);
 
+/* ---- resynthesis decoder (sylber/model/flowmatching.py:474-824: Regressor + ConditionalFlowMatcherWrapperRegressor.sample) ----
+ * The sylber_resynthesis.yaml geometry only: dim 512, depth 8, 8 heads x 64, dim_cond_emb 256, dim_in_proj 64, 16 register
+ * tokens, conv kernel 31, ff_mult 4 (FF inner 1365), dim_out 14.  HOST pointers to fp32 tensors in the layout of the
+ * Regressor's state_dict(); `precision`: SYLBER_BF16 (default), SYLBER_FP16 (the same launches on IEEE-half operands) or
+ * SYLBER_FP32 (parity mode: exact-fp32 GEMMs and attention). */
+#define SYLBER_CFM_DEPTH 8
+typedef struct {
+    const float *attn_gamma_w, *attn_gamma_b, *attn_beta_w, *attn_beta_b;  /* layers.i.2: AdaptiveRMSNorm to_gamma / to_beta [512,2048], [512] */
+    const float *q_gamma, *k_gamma;                                        /* layers.i.3.{q,k}_norm.gamma [8,1,64] */
+    const float *qkv_w, *out_w;                                            /* layers.i.3.to_qkv [1536,512], to_out [512,512] (no bias) */
+    const float *ff_gamma_w, *ff_gamma_b, *ff_beta_w, *ff_beta_b;          /* layers.i.4 */
+    const float *ff1_w, *ff1_b, *ff2_w, *ff2_b;                            /* layers.i.5.0 [2730,512] (value | gate), 5.3 [512,1365] */
+} SylberCfmLayer;
+typedef struct {
+    const float *proj_in_w, *proj_in_b;             /* [64,14], [64] */
+    const float *time_freq, *time_w, *time_b;       /* sinu_pos_emb.0.weights [256], sinu_pos_emb.1 [2048,512], [2048] */
+    const float *to_embed_w, *to_embed_b;           /* [512, 384] over [proj_in(y), cond_emb, proj_in(cond)], [512] */
+    const float *conv_w, *conv_b;                   /* conv_embed.dw_conv1d.0 [512,1,31], [512] */
+    const float *register_tokens;                   /* transformer.register_tokens [16,512] */
+    const float *rotary_inv_freq;                   /* transformer.rotary_emb.inv_freq [32] */
+    SylberCfmLayer layers[SYLBER_CFM_DEPTH];
+    const float *final_gamma;                       /* transformer.final_norm.gamma [512] */
+    const float *to_pred_w;                         /* [14,512] (no bias) */
+} SylberCfmWeights;
+typedef struct sylber_cfm* sylber_cfm_t;
+int sylber_cfm_create(const SylberCfmWeights* w, int device, int precision, sylber_cfm_t* out);
+void sylber_cfm_destroy(sylber_cfm_t h);
+/* bytes of caller-owned device workspace for a [B, T] call of sylber_cfm_sample / sylber_cfm_eval (-1 on error) */
+int64_t sylber_cfm_workspace_bytes(sylber_cfm_t h, int32_t B, int32_t T);
+/* art_dev [B,T,14] fp32 = sample(cond_emb_dev [B,T,256] fp32) with torchdiffeq's fixed-grid midpoint rule on
+ * t = linspace(0, 1, steps) (steps 1..65; 1 returns y0), starting from y0_dev [B,T,14] (nullable: zeros), then
+ * channel 12 divided by pitch_amp.  No mask: every row's frames 0..T-1 are ordinary frames (upstream's behaviour).
+ * Enqueued on `stream`; no host synchronisation. */
+int sylber_cfm_sample(sylber_cfm_t h, const float* cond_emb_dev, int32_t B, int32_t T, int32_t steps, const float* y0_dev,
+                      float pitch_amp, float* art_dev, void* workspace_dev, void* stream);
+/* one velocity evaluation v_dev [B,T,14] = Regressor(x_dev [B,T,14], t, cond_emb_dev) (test aid: localises errors) */
+int sylber_cfm_eval(sylber_cfm_t h, const float* x_dev, float t, const float* cond_emb_dev, int32_t B, int32_t T, float* v_dev,
+                    void* workspace_dev, void* stream);
+
 /* ---- single-op entry points (unit parity tests; same kernels the forward path launches) ------ */
 /* C[M,N] (fp32) = A[M,K] (fp32, cast to bf16) x W[N,K]^T (fp32, cast to bf16) + bias[N] (nullable); act: 0 none,
  * 1 gelu (the bf16 path's polynomial), 2 gelu (erf); precision: SYLBER_BF16 or SYLBER_FP8 (K % 128 == 0);

@@ -32,6 +32,23 @@ class SylberMlpWeights(ctypes.Structure):
                 ("hidden", SylberMlpHidden * 4), ("out_w", c_float_p), ("out_b", c_float_p)]
 
 
+CFM_DEPTH = 8
+
+
+class SylberCfmLayer(ctypes.Structure):
+    """mirror of SylberCfmLayer in include/sylber_hip.h"""
+    _fields_ = [(n, c_float_p) for n in (
+        "attn_gamma_w", "attn_gamma_b", "attn_beta_w", "attn_beta_b", "q_gamma", "k_gamma", "qkv_w", "out_w",
+        "ff_gamma_w", "ff_gamma_b", "ff_beta_w", "ff_beta_b", "ff1_w", "ff1_b", "ff2_w", "ff2_b")]
+
+
+class SylberCfmWeights(ctypes.Structure):
+    """mirror of SylberCfmWeights in include/sylber_hip.h"""
+    _fields_ = [(n, c_float_p) for n in ("proj_in_w", "proj_in_b", "time_freq", "time_w", "time_b", "to_embed_w", "to_embed_b",
+                                         "conv_w", "conv_b", "register_tokens", "rotary_inv_freq")] + \
+               [("layers", SylberCfmLayer * CFM_DEPTH), ("final_gamma", c_float_p), ("to_pred_w", c_float_p)]
+
+
 class SylberWeights(ctypes.Structure):
     _fields_ = [("num_layers", c_int32), ("conv_w", c_float_p * 7), ("gn_w", c_float_p), ("gn_b", c_float_p),
                 ("fp_ln_w", c_float_p), ("fp_ln_b", c_float_p), ("fp_w", c_float_p), ("fp_b", c_float_p),
@@ -78,6 +95,11 @@ EXPORTS = {
     "sylber_condition": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_float, c_void_p,
                                  c_void_p, c_void_p, c_void_p]),
     "sylber_condition_features": (c_int, [c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p]),
+    "sylber_cfm_create": (c_int, [POINTER(SylberCfmWeights), c_int, c_int, POINTER(c_void_p)]),
+    "sylber_cfm_destroy": (None, [c_void_p]),
+    "sylber_cfm_workspace_bytes": (c_int64, [c_void_p, c_int32, c_int32]),
+    "sylber_cfm_sample": (c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_float, c_void_p, c_void_p, c_void_p]),
+    "sylber_cfm_eval": (c_int, [c_void_p, c_void_p, c_float, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
     "sylber_op_attention": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32,
                                     c_int32, c_void_p]),
 }

@@ -1,0 +1,328 @@
+"""``SegmentSynthesis.resynthesize`` on the MI355X (sylber/model/segment_synthesis.py:57-146): HuBERT hidden states
+(``HubertEncoderHIP``) -> segmentation (``HubertEncoderHIP.segment``) -> segment-mean conditioning (``SegmentConditioner``)
+-> the flow-matching decoder (``CfmDecoder``, csrc/cfm.hip: sylber/model/flowmatching.py:474-824) -> the 14-channel
+articulatory trajectory ``art``.
+
+The decoder only exists at the sylber_resynthesis.yaml geometry; any other raises ``ValueError``.  Training (``forward``,
+the loss, the ``Thresholder`` updates), the torchode path and classifier-free guidance (``cond_scale != 1``) are not here:
+upstream's ``resynthesize`` uses none of them."""
+from __future__ import annotations
+
+import ctypes
+from pathlib import Path
+from typing import Dict, Optional
+
+import numpy as np
+import torch
+
+from . import _lib
+from .downstream import SegmentConditioner
+from .segmenter import HubertEncoderHIP
+from .weights import (CFM_CONV_K, CFM_DEPTH, CFM_DIM, CFM_DIM_COND_EMB, CFM_DIM_HEAD, CFM_DIM_IN_PROJ, CFM_DIM_OUT, CFM_FF_INNER,
+                      CFM_FF_MULT, CFM_HEADS, CFM_REGISTERS, CFM_TIME_HIDDEN)
+
+PRECISIONS = {"bf16": 0, "fp32": 1, "fp16": 3}        # include/sylber_hip.h SYLBER_BF16 / SYLBER_FP32 / SYLBER_FP16
+
+# sylber_configs/sylber_resynthesis.yaml
+DEFAULT_INPUT_CONFIGS = {"output_dim": 256, "hidden_dims": [512, 512], "dropout": 0.05}
+DEFAULT_REGRESSOR_CONFIGS = {"depth": 8, "sigma": 0.0, "dim_head": 64, "heads": 8, "dim": 512, "dim_in_proj": 64, "dim_cond_emb": 256}
+DEFAULT_THRESHOLDER_CONFIGS = {"signal_mean": 6.10, "signal_var": 0.87, "noise_mean": 0.3879, "noise_var": 0.6819}
+
+# the Regressor's constructor arguments the decoder is built for, with flowmatching.py's defaults where the yaml is silent
+_GEOMETRY = {"dim": CFM_DIM, "depth": CFM_DEPTH, "heads": CFM_HEADS, "dim_head": CFM_DIM_HEAD, "dim_in_proj": CFM_DIM_IN_PROJ,
+             "dim_cond_emb": CFM_DIM_COND_EMB, "dim_out": CFM_DIM_OUT, "num_register_tokens": CFM_REGISTERS,
+             "conv_pos_embed_kernel_size": CFM_CONV_K, "ff_mult": CFM_FF_MULT, "time_hidden_dim": CFM_TIME_HIDDEN}
+_NOT_SUPPORTED = {"use_gateloop_layers": False, "conv_pos_embed_groups": None, "attn_qk_norm": True, "condition_on_text": True}
+
+
+def regressor_shapes() -> Dict[str, tuple]:
+    """tensor shapes of ``Regressor.state_dict()`` the decoder reads, at the supported geometry"""
+    D, HD, TH, FI = CFM_DIM, CFM_HEADS * CFM_DIM_HEAD, CFM_TIME_HIDDEN, CFM_FF_INNER
+    s = {"proj_in.weight": (CFM_DIM_IN_PROJ, CFM_DIM_OUT), "proj_in.bias": (CFM_DIM_IN_PROJ,),
+         "sinu_pos_emb.0.weights": (D // 2,), "sinu_pos_emb.1.weight": (TH, D), "sinu_pos_emb.1.bias": (TH,),
+         "to_embed.weight": (D, 2 * CFM_DIM_IN_PROJ + CFM_DIM_COND_EMB), "to_embed.bias": (D,),
+         "conv_embed.dw_conv1d.0.weight": (D, 1, CFM_CONV_K), "conv_embed.dw_conv1d.0.bias": (D,),
+         "transformer.register_tokens": (CFM_REGISTERS, D), "transformer.rotary_emb.inv_freq": (CFM_DIM_HEAD // 2,),
+         "transformer.final_norm.gamma": (D,), "to_pred.weight": (CFM_DIM_OUT, D)}
+    for i in range(CFM_DEPTH):
+        p = "transformer.layers.%d." % i
+        for n in (2, 4):
+            s[p + "%d.to_gamma.weight" % n] = s[p + "%d.to_beta.weight" % n] = (D, TH)
+            s[p + "%d.to_gamma.bias" % n] = s[p + "%d.to_beta.bias" % n] = (D,)
+        s[p + "3.q_norm.gamma"] = s[p + "3.k_norm.gamma"] = (CFM_HEADS, 1, CFM_DIM_HEAD)
+        s[p + "3.to_qkv.weight"] = (3 * HD, D)
+        s[p + "3.to_out.weight"] = (D, HD)
+        s[p + "5.0.weight"] = (2 * FI, D)
+        s[p + "5.0.bias"] = (2 * FI,)
+        s[p + "5.3.weight"] = (D, FI)
+        s[p + "5.3.bias"] = (D,)
+    return s
+
+
+def check_regressor_configs(cfg: Optional[dict]) -> None:
+    """``ValueError`` unless ``regressor_configs`` describes the geometry the decoder is built for"""
+    cfg = dict(cfg or {})
+    for k, v in cfg.items():
+        if k in _GEOMETRY and int(v) != _GEOMETRY[k]:
+            raise ValueError("regressor_configs[%r] = %r: the HIP decoder is built for %s = %d only (sylber_resynthesis.yaml)"
+                             % (k, v, k, _GEOMETRY[k]))
+        if k in _NOT_SUPPORTED and v != _NOT_SUPPORTED[k]:
+            raise ValueError("regressor_configs[%r] = %r is not supported by the HIP decoder" % (k, v))
+    if "dim" in cfg and "time_hidden_dim" not in cfg and int(cfg["dim"]) * 4 != CFM_TIME_HIDDEN:
+        raise ValueError("time_hidden_dim must be %d" % CFM_TIME_HIDDEN)
+
+
+def _strip(sd: Dict[str, torch.Tensor], prefix: str) -> Dict[str, torch.Tensor]:
+    return {k[len(prefix):]: v for k, v in sd.items() if k.startswith(prefix)}
+
+
+def unwrap_checkpoint(ckpt) -> Dict[str, torch.Tensor]:
+    """path (``torch.load``) or dict; a Lightning ``{"state_dict": {"net.<key>": ...}}`` wrapper is unwrapped to the keys of
+    ``SegmentSynthesis.state_dict()``"""
+    if isinstance(ckpt, (str, Path)):
+        ckpt = torch.load(str(ckpt), map_location="cpu")
+    if not isinstance(ckpt, dict):
+        raise TypeError("model_ckpt must be a path or a state dict")
+    if "state_dict" in ckpt and isinstance(ckpt["state_dict"], dict):
+        ckpt = ckpt["state_dict"]
+    if any(k.startswith("net.") for k in ckpt):
+        ckpt = _strip(ckpt, "net.")
+    return ckpt
+
+
+def regressor_state_dict(sd: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+    """the ``Regressor`` keys out of a ``SegmentSynthesis`` state dict (``regressor.*``, or its duplicate
+    ``cfm_wrapper.regressor.*``), or ``sd`` itself when it already is one.  Checks every tensor the decoder reads:
+    ``KeyError`` naming a missing one, ``ValueError`` for a foreign shape."""
+    reg = _strip(sd, "regressor.")
+    if not reg:
+        reg = _strip(sd, "cfm_wrapper.regressor.")
+    if not reg:
+        reg = sd
+    for name, shape in regressor_shapes().items():
+        if name not in reg:
+            raise KeyError("checkpoint is missing regressor tensor %s" % name)
+        if tuple(reg[name].shape) != shape:
+            raise ValueError("regressor tensor %s has shape %s, expected %s: the HIP decoder is built for the sylber_resynthesis.yaml "
+                             "geometry only" % (name, tuple(reg[name].shape), shape))
+    return reg
+
+
+def threshold_from_stats(signal_mean, signal_var, noise_mean, noise_var, eta: float = 1.0) -> float:
+    """``Thresholder.get_threshold()`` (sylber/utils/segment_utils.py:27-52) on the host in torch fp32, in the reference's order of
+    operations: the crossing point of the two Gaussians N(mu_S, var_S) and N(mu_N, var_N) (+1e-8 on both variances)."""
+    f = lambda v: torch.as_tensor(v, dtype=torch.float32).reshape(1)       # noqa: E731
+    mu_s, mu_n = f(signal_mean), f(noise_mean)
+    sd_s, sd_n = (f(signal_var) + 1e-8) ** .5, (f(noise_var) + 1e-8) ** .5
+    vs, vn = sd_s ** 2, sd_n ** 2
+    qa = vs - vn
+    qb = -2 * vs * mu_n + 2 * vn * mu_s
+    qc = vs * mu_n ** 2 - vn * mu_s ** 2 - 2 * vn * vs * (np.log(eta) + torch.log(sd_s / sd_n))
+    if qa != 0:
+        disc = qb ** 2 - 4 * qa * qc
+        if disc > 0:
+            return float(((-qb + ((mu_s > mu_n) * 1.0) * torch.sqrt(disc)) / (2 * qa)).item())
+        if disc == 0:
+            return float((-qb / (2 * qa)).item())
+        raise ValueError("thresholder statistics have no crossing point (negative discriminant)")
+    if qb != 0:
+        return float((-qc / qb).item())
+    raise ValueError("thresholder statistics are degenerate (equal variances and means)")
+
+
+def _as_f32(t) -> torch.Tensor:
+    return t.detach().to("cpu", torch.float32).contiguous()
+
+
+class CfmDecoder:
+    """The resynthesis decoder behind ``sylber_cfm_*`` (include/sylber_hip.h): ``sample`` = ``cfm_wrapper.sample``,
+    ``eval`` = one ``Regressor`` evaluation.  ``state_dict``: ``Regressor.state_dict()`` keys (or a ``SegmentSynthesis``
+    dict, see ``regressor_state_dict``)."""
+
+    def __init__(self, state_dict: Dict[str, torch.Tensor], device="cuda", precision: str = "bf16"):
+        self.lib = _lib.load()
+        if not torch.cuda.is_available():
+            raise _lib.SylberHipError("no MI355X visible to PyTorch-ROCm; the HIP path has no CPU fallback")
+        if precision not in PRECISIONS:
+            raise ValueError("precision must be one of %s" % sorted(PRECISIONS))
+        sd = regressor_state_dict(state_dict)
+        keep = []
+
+        def ptr(name):
+            t = _as_f32(sd[name])
+            keep.append(t)
+            return ctypes.cast(t.data_ptr(), _lib.c_float_p)
+
+        w = _lib.SylberCfmWeights()
+        w.proj_in_w, w.proj_in_b = ptr("proj_in.weight"), ptr("proj_in.bias")
+        w.time_freq, w.time_w, w.time_b = ptr("sinu_pos_emb.0.weights"), ptr("sinu_pos_emb.1.weight"), ptr("sinu_pos_emb.1.bias")
+        w.to_embed_w, w.to_embed_b = ptr("to_embed.weight"), ptr("to_embed.bias")
+        w.conv_w, w.conv_b = ptr("conv_embed.dw_conv1d.0.weight"), ptr("conv_embed.dw_conv1d.0.bias")
+        w.register_tokens = ptr("transformer.register_tokens")
+        w.rotary_inv_freq = ptr("transformer.rotary_emb.inv_freq")
+        for i in range(CFM_DEPTH):
+            p = "transformer.layers.%d." % i
+            L = w.layers[i]
+            L.attn_gamma_w, L.attn_gamma_b = ptr(p + "2.to_gamma.weight"), ptr(p + "2.to_gamma.bias")
+            L.attn_beta_w, L.attn_beta_b = ptr(p + "2.to_beta.weight"), ptr(p + "2.to_beta.bias")
+            L.q_gamma, L.k_gamma = ptr(p + "3.q_norm.gamma"), ptr(p + "3.k_norm.gamma")
+            L.qkv_w, L.out_w = ptr(p + "3.to_qkv.weight"), ptr(p + "3.to_out.weight")
+            L.ff_gamma_w, L.ff_gamma_b = ptr(p + "4.to_gamma.weight"), ptr(p + "4.to_gamma.bias")
+            L.ff_beta_w, L.ff_beta_b = ptr(p + "4.to_beta.weight"), ptr(p + "4.to_beta.bias")
+            L.ff1_w, L.ff1_b = ptr(p + "5.0.weight"), ptr(p + "5.0.bias")
+            L.ff2_w, L.ff2_b = ptr(p + "5.3.weight"), ptr(p + "5.3.bias")
+        w.final_gamma = ptr("transformer.final_norm.gamma")
+        w.to_pred_w = ptr("to_pred.weight")
+        self.device = torch.device(device if device != "cuda" else "cuda:%d" % torch.cuda.current_device())
+        self.precision = precision
+        self.handle = ctypes.c_void_p()
+        _lib.check(self.lib.sylber_cfm_create(ctypes.byref(w), self.device.index or 0, PRECISIONS[precision], ctypes.byref(self.handle)),
+                   "sylber_cfm_create")
+        del keep
+
+    def __del__(self):
+        h = getattr(self, "handle", None)
+        if h:
+            self.lib.sylber_cfm_destroy(h)
+            self.handle = None
+
+    def _cond(self, cond_emb: torch.Tensor) -> torch.Tensor:
+        if cond_emb.dim() != 3 or cond_emb.shape[-1] != CFM_DIM_COND_EMB:
+            raise ValueError("cond_emb must be [B, T, %d], got %s" % (CFM_DIM_COND_EMB, tuple(cond_emb.shape)))
+        if cond_emb.shape[0] < 1 or cond_emb.shape[1] < 1:
+            raise ValueError("cond_emb must have B >= 1 and T >= 1, got %s" % (tuple(cond_emb.shape),))
+        return cond_emb.to(self.device, torch.float32).contiguous()
+
+    def _state(self, y: Optional[torch.Tensor], cond: torch.Tensor, name: str) -> Optional[torch.Tensor]:
+        if y is None:
+            return None
+        B, T, _ = cond.shape
+        if tuple(y.shape) != (B, T, CFM_DIM_OUT):
+            raise ValueError("%s must be [%d, %d, %d], got %s" % (name, B, T, CFM_DIM_OUT, tuple(y.shape)))
+        return y.to(self.device, torch.float32).contiguous()
+
+    def _workspace(self, B: int, T: int) -> torch.Tensor:
+        n = int(self.lib.sylber_cfm_workspace_bytes(self.handle, B, T))
+        if n < 0:
+            _lib.check(1, "sylber_cfm_workspace_bytes")
+        return torch.empty(n, dtype=torch.uint8, device=self.device)
+
+    def sample(self, cond_emb: torch.Tensor, steps: int = 5, y0: Optional[torch.Tensor] = None, pitch_amp: float = 1.0) -> torch.Tensor:
+        """``cfm_wrapper.sample(cond_emb=..., steps=...)`` from ``y0`` (None: zeros, i.e. ``rand_scale = 0``), then channel 12
+        divided by ``pitch_amp`` -> ``[B, T, 14]`` fp32 on the device.  Enqueued on the current stream."""
+        if isinstance(steps, bool) or int(steps) != steps or not 1 <= int(steps) <= 65:
+            raise ValueError("steps must be an integer in 1..65, got %r" % (steps,))
+        cond = self._cond(cond_emb)
+        y0 = self._state(y0, cond, "y0")
+        B, T, _ = cond.shape
+        art = torch.empty(B, T, CFM_DIM_OUT, dtype=torch.float32, device=self.device)
+        ws = self._workspace(B, T)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.sylber_cfm_sample(self.handle, ctypes.c_void_p(cond.data_ptr()), B, T, int(steps),
+                                                  ctypes.c_void_p(y0.data_ptr()) if y0 is not None else None,
+                                                  ctypes.c_float(float(pitch_amp)), ctypes.c_void_p(art.data_ptr()),
+                                                  ctypes.c_void_p(ws.data_ptr()),
+                                                  ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)),
+                       "sylber_cfm_sample")
+        return art
+
+    def eval(self, x: torch.Tensor, t: float, cond_emb: torch.Tensor) -> torch.Tensor:
+        """one velocity evaluation of the ``Regressor`` at state ``x [B, T, 14]`` and time ``t``"""
+        cond = self._cond(cond_emb)
+        x = self._state(x, cond, "x")
+        B, T, _ = cond.shape
+        v = torch.empty(B, T, CFM_DIM_OUT, dtype=torch.float32, device=self.device)
+        ws = self._workspace(B, T)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.sylber_cfm_eval(self.handle, ctypes.c_void_p(x.data_ptr()), ctypes.c_float(float(t)),
+                                                ctypes.c_void_p(cond.data_ptr()), B, T, ctypes.c_void_p(v.data_ptr()),
+                                                ctypes.c_void_p(ws.data_ptr()),
+                                                ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)),
+                       "sylber_cfm_eval")
+        return v
+
+
+class SegmentSynthesis:
+    """Same constructor and ``resynthesize`` contract as the reference's ``SegmentSynthesis``
+    (sylber/model/segment_synthesis.py:57-146), inference only.  ``model_ckpt``: a path or a state dict with the keys of
+    ``SegmentSynthesis.state_dict()`` (``speech_model.*``, ``input_model.mlp.*``, ``regressor.*`` / ``cfm_wrapper.regressor.*``,
+    ``thresholder.*``), optionally inside a Lightning ``{"state_dict": {"net.<key>": ...}}`` wrapper.  ``precision``:
+    "bf16" (default), "fp16" or "fp32" (parity mode), for the encoder and the decoder alike."""
+
+    def __init__(self, model_ckpt=None, speech_upstream="facebook/hubert-base-ls960", encoding_layer=9, input_configs=None,
+                 regressor_configs=None, thresholder_configs=None, pitch_amp=5, quantizer=None, device="cuda", precision="bf16",
+                 **kwargs):
+        if "cuda" not in str(device):
+            raise _lib.SylberHipError("sylber_amd.SegmentSynthesis runs on the MI355X only (device=%r)" % (device,))
+        if precision not in PRECISIONS:
+            raise ValueError("precision must be one of %s" % sorted(PRECISIONS))
+        self.input_configs = dict(DEFAULT_INPUT_CONFIGS if input_configs is None else input_configs)
+        self.regressor_configs = dict(DEFAULT_REGRESSOR_CONFIGS if regressor_configs is None else regressor_configs)
+        self.thresholder_configs = dict(DEFAULT_THRESHOLDER_CONFIGS if thresholder_configs is None else thresholder_configs)
+        check_regressor_configs(self.regressor_configs)
+        if int(self.input_configs.get("output_dim", CFM_DIM_COND_EMB)) != CFM_DIM_COND_EMB:
+            raise ValueError("input_configs['output_dim'] must equal the decoder's dim_cond_emb (%d)" % CFM_DIM_COND_EMB)
+        if model_ckpt is None:
+            raise ValueError("model_ckpt is required (a path or a SegmentSynthesis state dict)")
+        sd = unwrap_checkpoint(model_ckpt)
+        self.pitch_amp = pitch_amp
+        self.encoding_layer = encoding_layer
+        self.speech_upstream = speech_upstream
+        speech = _strip(sd, "speech_model.")
+        if not speech:
+            raise KeyError("checkpoint is missing the speech_model.* tensors")
+        mlp = _strip(sd, "input_model.")
+        if not mlp:
+            raise KeyError("checkpoint is missing the input_model.* tensors")
+        self.decoder = CfmDecoder(sd, device=device, precision=precision)     # checks the regressor tensors first (cheapest to fail)
+        self.speech_model = HubertEncoderHIP(speech, num_layers=encoding_layer, device=device, precision=precision)
+        self.input_model = SegmentConditioner(mlp, device=device)
+        self.device = self.speech_model.device
+        self.quantizer = quantizer                     # a KMQuantizer (or None), passed to SegmentConditioner
+        thr = _strip(sd, "thresholder.")
+        if "threshold" in thr:
+            self._threshold = float(thr["threshold"].reshape(-1)[0])
+        elif all(k in thr for k in ("signal_mean", "signal_var", "noise_mean", "noise_var")):
+            self._threshold = threshold_from_stats(thr["signal_mean"], thr["signal_var"], thr["noise_mean"], thr["noise_var"])
+        else:
+            c = self.thresholder_configs
+            self._threshold = threshold_from_stats(c["signal_mean"], c["signal_var"], c["noise_mean"], c["noise_var"])
+
+    def get_threshold(self) -> float:
+        """``thresholder.get_threshold()``: the checkpoint's thresholder statistics, else ``thresholder_configs``'"""
+        return self._threshold
+
+    def resynthesize(self, input_values=None, attention_mask=None, features=None, steps=5, rand_scale=0.0, merge_threshold=0.8,
+                     normthreshold=None, prosody_steps=None, prosody_rand_scale=None, y0=None):
+        """-> ``(art [B, T, 14] fp32 on the device, segments)`` with channel 12 divided by ``pitch_amp``; ``segments`` is a list of
+        int64 ``[n, 2]`` arrays (``np.array([])`` for none), or None on the ``features=`` branch.  ``rand_scale > 0`` starts the
+        sampler from ``randn_like(cond) * rand_scale`` on the device; ``y0=`` supplies that start explicitly (tests).
+        ``prosody_*`` are accepted and ignored, as upstream."""
+        dev = self.device
+        if features is None:
+            if input_values is None:
+                raise ValueError("pass input_values or features")
+            x = torch.as_tensor(input_values).to(dev, torch.float32)
+            if x.dim() == 1:
+                x = x[None]
+            x = x.contiguous()
+            lengths = None if attention_mask is None else [int(v) for v in torch.as_tensor(attention_mask).sum(-1).tolist()]
+            hidden = self.speech_model.forward(x, lengths)
+            if normthreshold is None:
+                normthreshold = self.get_threshold()
+            seg, nseg, feats = self.speech_model.segment(hidden, normthreshold, merge_threshold)
+            cond, _ = self.input_model(hidden, seg, nseg, feats, normthreshold, quantizer=self.quantizer)
+            nseg_h = nseg.cpu().numpy()
+            nmax = max(int(nseg_h.max()), 1)
+            seg_h = seg[:, :nmax].cpu().numpy()
+            segments = [seg_h[i, : int(nseg_h[i])].copy() if nseg_h[i] > 0 else np.array([]) for i in range(len(nseg_h))]
+        else:
+            feats = torch.as_tensor(features).to(dev, torch.float32).contiguous()
+            if feats.dim() != 3:
+                raise ValueError("features must be [B, T, 768]")
+            cond = self.input_model.from_features(feats)
+            segments = None
+        if y0 is None and rand_scale:
+            y0 = torch.randn(cond.shape[0], cond.shape[1], CFM_DIM_OUT, device=dev) * rand_scale
+        art = self.decoder.sample(cond, steps=steps, y0=y0, pitch_amp=self.pitch_amp)
+        return art, segments

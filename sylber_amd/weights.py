@@ -162,3 +162,72 @@ def synthetic_mlp_state_dict(seed: int = 0, input_dim: int = HIDDEN, output_dim:
     sd["mlp.%d.weight" % (2 * len(hidden_dims))] = randn(output_dim, d_in, std=1.0 / math.sqrt(d_in))
     sd["mlp.%d.bias" % (2 * len(hidden_dims))] = randn(output_dim, std=0.1)
     return sd
+
+
+# ---- the resynthesis decoder (flow-matching Regressor, sylber_configs/sylber_resynthesis.yaml geometry) ----------------------
+CFM_DIM, CFM_DEPTH, CFM_HEADS, CFM_DIM_HEAD = 512, 8, 8, 64
+CFM_DIM_IN_PROJ, CFM_DIM_COND_EMB, CFM_DIM_OUT = 64, 256, 14
+CFM_REGISTERS, CFM_CONV_K, CFM_FF_MULT = 16, 31, 4
+CFM_FF_INNER = int(CFM_DIM * CFM_FF_MULT * 2 / 3)      # 1365 (FeedForward, flowmatching.py)
+CFM_TIME_HIDDEN = CFM_DIM * 4                           # 2048
+CFM_ROTARY_THETA = 50000
+
+
+def synthetic_regressor_state_dict(seed: int = 0) -> Dict[str, torch.Tensor]:
+    """Seeded weights of the flow-matching ``Regressor`` (sylber/model/flowmatching.py:474-688) in the key layout of its
+    ``state_dict()``, at the sylber_resynthesis.yaml geometry (dim 512, depth 8, 8 x 64 heads, dim_cond_emb 256,
+    dim_in_proj 64, 16 register tokens, conv kernel 31, ff_mult 4).  CPU torch generator, so every machine builds the same
+    tensors.
+
+    The scaling is chosen to look like a TRAINED decoder rather than the reference's initialisation:
+      * residual output projections (attention ``to_out``, FF out) at 0.3 / sqrt(fan_in): each block adds a fraction of the
+        residual stream instead of doubling it;
+      * q / k ``MultiheadRMSNorm`` gains around 0.3: with the Attend scale of 10 on top of the norm-8 q and k the reference's
+        unit gains give attention logits of 370-410, where any 16-bit rounding of the operands changes which key wins (a
+        chaotic decoder); at 0.3 the logits stay in the 30s;
+      * AdaRMSNorm ``to_gamma`` / ``to_beta`` with nonzero weights and gains around 1, so that the time conditioning is
+        exercised (the reference initialises them to the identity, which would leave that path untested);
+      * ``to_embed`` bias at std 1 (a residual stream of norm ~20 even where the conditioning is zero): at 0.1, the
+        silence-masked and zero-padded frames carry a residual of norm ~3 that the RMSNorms blow up, and the sampler's
+        Lipschitz constant there is ~200 -- a 1e-5 change of the input moves the 5-step sample by 0.4 relative RMS, so no
+        two implementations (or summation orders) agree.  At std 1 both kinds of frames sit near 0.5-0.7;
+      * everything else at 1 / sqrt(fan_in), biases at 0.05-0.1, learned sinusoidal frequencies and register tokens at
+        std 1 as in the reference."""
+    g = torch.Generator().manual_seed(20_000 + seed)
+
+    def randn(*shape, std=1.0):
+        return torch.randn(*shape, generator=g, dtype=torch.float32) * std
+
+    D, TH, FI, HD = CFM_DIM, CFM_TIME_HIDDEN, CFM_FF_INNER, CFM_HEADS * CFM_DIM_HEAD
+    sd: Dict[str, torch.Tensor] = {}
+    sd["proj_in.weight"] = randn(CFM_DIM_IN_PROJ, CFM_DIM_OUT, std=1.0 / math.sqrt(CFM_DIM_OUT))
+    sd["proj_in.bias"] = randn(CFM_DIM_IN_PROJ, std=0.1)
+    sd["sinu_pos_emb.0.weights"] = randn(D // 2)
+    sd["sinu_pos_emb.1.weight"] = randn(TH, D, std=1.0 / math.sqrt(D))
+    sd["sinu_pos_emb.1.bias"] = randn(TH, std=0.1)
+    sd["to_cond_emb.weight"] = randn(501, CFM_DIM_COND_EMB)          # unused at inference (cond_emb is passed in)
+    sd["to_embed.weight"] = randn(D, 2 * CFM_DIM_IN_PROJ + CFM_DIM_COND_EMB, std=1.0 / math.sqrt(2 * CFM_DIM_IN_PROJ + CFM_DIM_COND_EMB))
+    sd["to_embed.bias"] = randn(D, std=1.0)
+    sd["null_cond"] = torch.zeros(D)
+    sd["conv_embed.dw_conv1d.0.weight"] = randn(D, 1, CFM_CONV_K, std=1.0 / math.sqrt(CFM_CONV_K))
+    sd["conv_embed.dw_conv1d.0.bias"] = randn(D, std=0.1)
+    sd["transformer.register_tokens"] = randn(CFM_REGISTERS, D)
+    sd["transformer.rotary_emb.inv_freq"] = 1.0 / (CFM_ROTARY_THETA ** (torch.arange(0, CFM_DIM_HEAD, 2).float() / CFM_DIM_HEAD))
+    for i in range(CFM_DEPTH):
+        p = "transformer.layers.%d." % i
+        for n in (2, 4):
+            sd[p + "%d.to_gamma.weight" % n] = randn(D, TH, std=0.3 / math.sqrt(TH))
+            sd[p + "%d.to_gamma.bias" % n] = 1.0 + randn(D, std=0.1)
+            sd[p + "%d.to_beta.weight" % n] = randn(D, TH, std=0.1 / math.sqrt(TH))
+            sd[p + "%d.to_beta.bias" % n] = randn(D, std=0.05)
+        sd[p + "3.q_norm.gamma"] = 0.3 * (1.0 + randn(CFM_HEADS, 1, CFM_DIM_HEAD, std=0.1))
+        sd[p + "3.k_norm.gamma"] = 0.3 * (1.0 + randn(CFM_HEADS, 1, CFM_DIM_HEAD, std=0.1))
+        sd[p + "3.to_qkv.weight"] = randn(3 * HD, D, std=1.0 / math.sqrt(D))
+        sd[p + "3.to_out.weight"] = randn(D, HD, std=0.3 / math.sqrt(HD))
+        sd[p + "5.0.weight"] = randn(2 * FI, D, std=1.0 / math.sqrt(D))
+        sd[p + "5.0.bias"] = randn(2 * FI, std=0.05)
+        sd[p + "5.3.weight"] = randn(D, FI, std=0.3 / math.sqrt(FI))
+        sd[p + "5.3.bias"] = randn(D, std=0.05)
+    sd["transformer.final_norm.gamma"] = 1.0 + randn(D, std=0.1)
+    sd["to_pred.weight"] = randn(CFM_DIM_OUT, D, std=1.0 / math.sqrt(D))
+    return sd
