@@ -110,6 +110,13 @@ int sylber_forward(sylber_t h, const float* wav_dev, const int32_t* lengths_host
  */
 int sylber_segment(sylber_t h, const float* hidden_dev, int32_t B, int32_t T, int32_t D, float norm_thr,
                    float merge_thr, int64_t* seg_dev, int32_t* nseg_dev, float* feat_dev, void* stream);
+/* batch-invariant sibling of sylber_segment: row b is segmented and pooled as if it had exactly frames_host[b] frames
+ * (get_segment(states[:frames_host[b]])): frames at or past that count are never read, a run of speech frames ends there as at the
+ * end of an array, and every table entry lies in [0, frames_host[b]).  frames_host [B] in [1, T], read before the call returns (the
+ * counts travel as kernel arguments).  Buffers and pitch (T) as sylber_segment.  Wide path only: refused under
+ * SYLBER_OPT_SEGMENT = -1. */
+int sylber_segment_frames(sylber_t h, const float* hidden_dev, const int32_t* frames_host, int32_t B, int32_t T, int32_t D,
+                          float norm_thr, float merge_thr, int64_t* seg_dev, int32_t* nseg_dev, float* feat_dev, void* stream);
 
 /* ---- file ingest on the device (replaces sylber.py:83-86) -------------------
  *   wav, sr = torchaudio.load(file); if sr != 16000: wav = torchaudio.transforms.Resample(sr, 16000)(wav);
@@ -229,9 +236,16 @@ int sylber_condition(sylber_mlp_t m, const float* hidden_dev, const int64_t* seg
  *   SYLBER_OPT_FP16_AUDIT              1: (re)start the fp16 headroom audit -- from now on every forward of a SYLBER_FP16 / SYLBER_MIXED16 handle scans each
  *                                      16-bit activation buffer right behind its producer and accumulates, per stage, the number of values AT the
  *                                      format's saturation value (+-65504: the fp16 modes clamp on conversion, they never produce infinities) and the
- *                                      largest magnitude seen; read with sylber_get_fp16_audit.  0 (default): off, nothing is launched. */
+ *                                      largest magnitude seen; read with sylber_get_fp16_audit.  0 (default): off, nothing is launched.
+ *   SYLBER_OPT_PER_UTTERANCE           1: batch-invariant encoder -- conv0's GroupNorm statistics of row b are taken over that row's own conv0 frames
+ *                                      (lengths_host[b] - 10) / 5 + 1 instead of the padded length, so hidden[b, :T_b] (T_b = sylber_num_frames(
+ *                                      lengths_host[b])) is bit-identical to a forward of that clip alone in every precision (SYLBER_FP8 with
+ *                                      SYLBER_OPT_FP8_ATTENTION = -1: its fp8 attention core is chosen by batch shape).  Frames at or past T_b hold
+ *                                      whatever the forward computes there; segment with sylber_segment_frames.  Works in graph mode (the counts
+ *                                      are uploaded before every replay).  0 (default): the reference's statistics over the padded time axis. */
 enum { SYLBER_OPT_GEMM_TILE = 1, SYLBER_OPT_ATTN_QUERIES_PER_WAVE = 2, SYLBER_OPT_GEMM_PERSISTENT = 3, SYLBER_OPT_FUSE_OUTPROJ_LN = 4,
-       SYLBER_OPT_CONV0_VALU = 5, SYLBER_OPT_RESLN_PREFETCH = 6, SYLBER_OPT_FP8_ATTENTION = 7, SYLBER_OPT_GEMM_TAIL = 8, SYLBER_OPT_SEGMENT = 9, SYLBER_OPT_FP16_AUDIT = 10, SYLBER_OPT_GEMM_H192 = 11, SYLBER_OPT_GEMM_MODEL = 12, SYLBER_OPT_GEMM_MFMA16 = 13 };
+       SYLBER_OPT_CONV0_VALU = 5, SYLBER_OPT_RESLN_PREFETCH = 6, SYLBER_OPT_FP8_ATTENTION = 7, SYLBER_OPT_GEMM_TAIL = 8, SYLBER_OPT_SEGMENT = 9, SYLBER_OPT_FP16_AUDIT = 10, SYLBER_OPT_GEMM_H192 = 11, SYLBER_OPT_GEMM_MODEL = 12, SYLBER_OPT_GEMM_MFMA16 = 13,
+       SYLBER_OPT_PER_UTTERANCE = 14 };
 int sylber_set_option(sylber_t h, int32_t key, int32_t value);
 /* the audit's counters since SYLBER_OPT_FP16_AUDIT was last set (synchronises the device): names[i] (static strings: conv0 .. conv6, ln512,
  * proj_xpad, layernorm, q, k, v, context, ffn1), saturated[i] values clamped at +-65504, max_abs[i] largest magnitude; returns the number of
@@ -297,6 +311,11 @@ int64_t sylber_cfm_workspace_bytes(sylber_cfm_t h, int32_t B, int32_t T);
  * Enqueued on `stream`; no host synchronisation. */
 int sylber_cfm_sample(sylber_cfm_t h, const float* cond_emb_dev, int32_t B, int32_t T, int32_t steps, const float* y0_dev,
                       float pitch_amp, float* art_dev, void* workspace_dev, void* stream);
+/* batch-invariant sibling of sylber_cfm_sample: row b is sampled as a [1, frames_host[b]] call samples it -- the depthwise conv treats
+ * frames at or past frames_host[b] as its zero padding, attention sees the 16 register tokens and the row's own frames only, and
+ * art_dev[b, t] = 0 for t >= frames_host[b].  frames_host [B] in [1, T], read before the call returns.  Same workspace size. */
+int sylber_cfm_sample_frames(sylber_cfm_t h, const float* cond_emb_dev, const int32_t* frames_host, int32_t B, int32_t T, int32_t steps,
+                             const float* y0_dev, float pitch_amp, float* art_dev, void* workspace_dev, void* stream);
 /* one velocity evaluation v_dev [B,T,14] = Regressor(x_dev [B,T,14], t, cond_emb_dev) (test aid: localises errors) */
 int sylber_cfm_eval(sylber_cfm_t h, const float* x_dev, float t, const float* cond_emb_dev, int32_t B, int32_t T, float* v_dev,
                     void* workspace_dev, void* stream);

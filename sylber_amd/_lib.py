@@ -66,6 +66,8 @@ EXPORTS = {
     "sylber_forward": (c_int, [c_void_p, c_void_p, POINTER(c_int32), c_int32, c_int32, c_void_p, c_void_p]),
     "sylber_segment": (c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_float, c_float, c_void_p, c_void_p,
                                c_void_p, c_void_p]),
+    "sylber_segment_frames": (c_int, [c_void_p, c_void_p, POINTER(c_int32), c_int32, c_int32, c_int32, c_float, c_float, c_void_p,
+                                      c_void_p, c_void_p, c_void_p]),
     "sylber_set_stop_stage": (c_int, [c_void_p, c_int32]),
     "sylber_set_profiling": (c_int, [c_void_p, c_int32]),
     "sylber_set_graph_mode": (c_int, [c_void_p, c_int32]),
@@ -99,6 +101,8 @@ EXPORTS = {
     "sylber_cfm_destroy": (None, [c_void_p]),
     "sylber_cfm_workspace_bytes": (c_int64, [c_void_p, c_int32, c_int32]),
     "sylber_cfm_sample": (c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_float, c_void_p, c_void_p, c_void_p]),
+    "sylber_cfm_sample_frames": (c_int, [c_void_p, c_void_p, POINTER(c_int32), c_int32, c_int32, c_int32, c_void_p, c_float, c_void_p,
+                                         c_void_p, c_void_p]),
     "sylber_cfm_eval": (c_int, [c_void_p, c_void_p, c_float, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
     "sylber_op_attention": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32,
                                     c_int32, c_void_p]),
@@ -112,6 +116,7 @@ DEV_EXPORTS = {
     "sylber_debug_poison_workspace": (c_int, [c_void_p, c_int32]),
 }
 OPT_GEMM_TILE, OPT_ATTN_QUERIES_PER_WAVE, OPT_GEMM_PERSISTENT = 1, 2, 3
+OPT_FP8_ATTENTION, OPT_SEGMENT, OPT_PER_UTTERANCE = 7, 9, 14
 
 _LIB = None
 

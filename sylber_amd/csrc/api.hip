@@ -97,6 +97,7 @@ struct sylber_ctx {
     int opt_gemm_tail = 0;                                         // row split of multi-round GEMM launches: 0 auto, -1 never, k + 1 = tail tile id k
     int opt_attn8 = 0;                                             // SYLBER_FP8: attention core on MXFP8 operands (0 / 1 on, -1 off)
     int opt_resln_pre = 0;                                         // residual prefetch of the out-proj / FFN2 K loops: 0 default, -1 off, 1..3 columns
+    int opt_per_utt = 0;                                           // 1: conv0 GroupNorm statistics over each utterance's own frames (batch-invariant mode)
     bool graph_mode = false;
     std::vector<GraphEntry> graphs; unsigned long long graph_clock = 0;
     // profiling
@@ -313,6 +314,7 @@ extern "C" int sylber_set_option(sylber_t c, int32_t key, int32_t value) {
         case SYLBER_OPT_GEMM_H192: c->opt_gemm_h192 = value < 0 ? -1 : 0; break;
         case SYLBER_OPT_GEMM_MFMA16: c->opt_gemm_mfma16 = value < 0 ? -1 : 0; break;
         case SYLBER_OPT_GEMM_TAIL: c->opt_gemm_tail = value < 0 ? -1 : (value > 0 ? value + 1 : 0); break;   // k > 0: tail tile id k (stored id + 1)
+        case SYLBER_OPT_PER_UTTERANCE: c->opt_per_utt = value == 1 ? 1 : 0; break;
         default: syl_set_error("sylber_set_option", "unknown option key"); return 1;
     }
     if (c->graph_mode) { for (auto& g : c->graphs) if (g.exec) hipGraphExecDestroy(g.exec); c->graphs.clear(); }   // captured launches are stale
@@ -333,7 +335,7 @@ extern "C" int64_t sylber_workspace_bytes(sylber_t c) { return c ? (int64_t)(c->
 struct Plan {
     int B, Lmax, L[7], T, Tp, Tpv, R[7];
     size_t o_bufA, o_bufB, o_ln512, o_xf32, o_xpad, o_pre, o_stats, o_hbf16, o_q, o_k, o_vt, o_ctx, o_ffn, o_part, o_ss, o_valid,
-        total;
+        o_rows, total;
     int nchunk;
     bool zero_all = false;        // fp32 parity plan: its own offsets, zero everything on a layout change
     // SYLBER_SPLIT16: every 16-bit buffer holds two half planes; element offsets of the lo planes (0 otherwise)
@@ -384,6 +386,7 @@ static void make_plan(int B, int Lmax, Plan& p, int planes = 1) {
     p.o_part = take((size_t)B * p.nchunk * 65 * 8);
     p.o_ss = take((size_t)B * 512 * 2 * 4);
     p.o_valid = take((size_t)B * 4);
+    p.o_rows = take((size_t)B * 4);
     p.total = off;
 }
 
@@ -423,6 +426,22 @@ static int ensure_workspace(sylber_ctx* c, const Plan& p, hipStream_t s) {
 struct ValidPack { int v[64]; };
 __global__ void set_valid_kernel(int* __restrict__ dst, ValidPack p, int n) {
     if ((int)threadIdx.x < n) dst[threadIdx.x] = p.v[threadIdx.x];
+}
+int launch_upload_ints(int* dst, const int32_t* vals_host, int n, int add, hipStream_t s) {
+    for (int b0 = 0; b0 < n; b0 += 64) {
+        ValidPack pk;
+        const int k = n - b0 < 64 ? n - b0 : 64;
+        for (int i = 0; i < k; ++i) pk.v[i] = vals_host[b0 + i] + add;
+        hipLaunchKernelGGL(set_valid_kernel, dim3(1), dim3(64), 0, s, dst + b0, pk, k);
+    }
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+// SYLBER_OPT_PER_UTTERANCE: conv0 frames of every utterance's own length, (n_b - 10) / 5 + 1 (lengths already checked by upload_valid)
+static int upload_conv0_rows(int* rows_dev, const int32_t* lengths_host, int B, int Lmax, hipStream_t s) {
+    std::vector<int32_t> l0(B);
+    for (int b = 0; b < B; ++b) l0[b] = ((lengths_host ? lengths_host[b] : Lmax) - CK[0]) / CS[0] + 1;
+    return launch_upload_ints(rows_dev, l0.data(), B, 0, s);
 }
 static int upload_valid(int* valid_dev, const int32_t* lengths_host, int B, int Lmax, hipStream_t s) {
     for (int b0 = 0; b0 < B; b0 += 64) {
@@ -535,11 +554,12 @@ static int forward_launch(sylber_ctx* c, const Plan& p, const float* wav_dev, fl
     bf16_t* q = (bf16_t*)(w + p.o_q); bf16_t* k = (bf16_t*)(w + p.o_k); bf16_t* vt = (bf16_t*)(w + p.o_vt);
     bf16_t* ctx = (bf16_t*)(w + p.o_ctx); bf16_t* ffn = (bf16_t*)(w + p.o_ffn);
     double* part = (double*)(w + p.o_part); float* ss = (float*)(w + p.o_ss); int* valid = (int*)(w + p.o_valid);
+    const int* rows0 = c->opt_per_utt ? (const int*)(w + p.o_rows) : nullptr;    // per-utterance GroupNorm statistics (nullptr: padded L0)
     const int M = B * p.Tp;
 
     // ---- conv layer 0 + GroupNorm + GELU
-    RUN("conv0_stats", launch_conv0_stats(wav_dev, B, Lmax, p.L[0], part, p.nchunk, s));
-    RUN("conv0_finalize", launch_conv0_finalize(part, p.nchunk, c->conv0_w, c->gn_w, c->gn_b, B, p.L[0], ss, s));
+    RUN("conv0_stats", launch_conv0_stats(wav_dev, B, Lmax, p.L[0], part, p.nchunk, s, rows0));
+    RUN("conv0_finalize", launch_conv0_finalize(part, p.nchunk, c->conv0_w, c->gn_w, c->gn_b, B, p.L[0], ss, s, rows0));
     const bool split = c->precision == SYLBER_SPLIT16;      // hi / lo half planes, erf GELU (fp32-grade decisions)
     RUN("conv0_gn_gelu", launch_conv0_gn_gelu(wav_dev, B, Lmax, p.L[0], p.R[0], c->conv0_w, ss, bufA, 0, s, c->fmt_conv, p.lo_bufA, c->opt_conv0_valu));
     const bool aud_c = c->opt_audit16 && c->fmt_conv == FMT_F16, aud_e = c->opt_audit16 && c->fmt == FMT_F16;   // (the audit launches are never captured: graph mode is refused with it)
@@ -727,6 +747,8 @@ extern "C" int sylber_forward(sylber_t c, const float* wav_dev, const int32_t* l
     int* valid = (int*)(c->ws + p.o_valid);
     // valid frames per utterance (TP:664-689): conv-length formula of the number of valid samples
     if (upload_valid(valid, lengths_host, B, Lmax, s)) return 1;
+    // (before any capture or replay: a replayed graph reads this call's counts)
+    if (c->opt_per_utt && upload_conv0_rows((int*)(c->ws + p.o_rows), lengths_host, B, Lmax, s)) return 1;
     if (!c->graph_mode || c->profiling || c->opt_audit16 || s == nullptr) return forward_launch(c, p, wav_dev, hidden_dev, s);
     GraphEntry* e = nullptr;
     for (auto& g : c->graphs)
@@ -774,7 +796,7 @@ static int forward_f32(sylber_ctx* c, const float* wav_dev, const int32_t* lengt
     const size_t o_ln = take(M * 512 * 4), o_x = take(M * 768 * 4), o_xpad = take((size_t)B * (p.Tp + 128) * 768 * 4);
     const size_t o_pre = take(M * 768 * 4), o_h = take(M * 768 * 4), o_qkv = take(M * 2304 * 4), o_ctx = take(M * 768 * 4);
     const size_t o_ffn = take(M * 3072 * 4), o_part = take((size_t)B * p.nchunk * 65 * 8), o_ss = take((size_t)B * 512 * 2 * 4);
-    const size_t o_valid = take((size_t)B * 4);
+    const size_t o_valid = take((size_t)B * 4), o_rows = take((size_t)B * 4);
     Plan q = p; q.total = off; q.zero_all = true;
     if (ensure_workspace(c, q, s)) return 1;
     char* w = c->ws;
@@ -783,8 +805,13 @@ static int forward_f32(sylber_ctx* c, const float* wav_dev, const int32_t* lengt
     float* qkv = (float*)(w + o_qkv); float* ctx = (float*)(w + o_ctx); float* ffn = (float*)(w + o_ffn);
     double* part = (double*)(w + o_part); float* ss = (float*)(w + o_ss); int* valid = (int*)(w + o_valid);
     if (upload_valid(valid, lengths_host, B, Lmax, s)) return 1;
-    RUN("conv0_stats", launch_conv0_stats(wav_dev, B, Lmax, p.L[0], part, p.nchunk, s));
-    RUN("conv0_finalize", launch_conv0_finalize(part, p.nchunk, c->conv0_w, c->gn_w, c->gn_b, B, p.L[0], ss, s));
+    int* rows0 = nullptr;
+    if (c->opt_per_utt) {
+        rows0 = (int*)(w + o_rows);
+        if (upload_conv0_rows(rows0, lengths_host, B, Lmax, s)) return 1;
+    }
+    RUN("conv0_stats", launch_conv0_stats(wav_dev, B, Lmax, p.L[0], part, p.nchunk, s, rows0));
+    RUN("conv0_finalize", launch_conv0_finalize(part, p.nchunk, c->conv0_w, c->gn_w, c->gn_b, B, p.L[0], ss, s, rows0));
     RUN("conv0_gn_gelu", launch_conv0_gn_gelu(wav_dev, B, Lmax, p.L[0], p.R[0], c->conv0_w, ss, bufA, 1, s));
     float* src = bufA; float* dst = bufB;
     for (int i = 1; i < 7; ++i) {
@@ -847,13 +874,16 @@ static int forward_f32(sylber_ctx* c, const float* wav_dev, const int32_t* lengt
     return 0;
 }
 
-extern "C" int sylber_segment(sylber_t c, const float* hidden_dev, int32_t B, int32_t T, int32_t D, float norm_thr,
-                              float merge_thr, int64_t* seg_dev, int32_t* nseg_dev, float* feat_dev, void* stream) {
-    if (!c || !hidden_dev || !seg_dev || !nseg_dev) { syl_set_error("sylber_segment", "null argument"); return 1; }
+// frames_host: nullptr (sylber_segment) or each row's own frame count (sylber_segment_frames), which travels to the device as kernel
+// arguments into the slots behind the wide path's slab
+static int segment_call(const char* what, sylber_t c, const float* hidden_dev, const int32_t* frames_host, int32_t B, int32_t T, int32_t D,
+                        float norm_thr, float merge_thr, int64_t* seg_dev, int32_t* nseg_dev, float* feat_dev, void* stream) {
+    if (!c || !hidden_dev || !seg_dev || !nseg_dev) { syl_set_error(what, "null argument"); return 1; }
     hipStream_t s = (hipStream_t)stream;
     GUARD_DEVICE(c->device);
     // per-utterance slab of the wide path (frame norms, slot table, bookkeeping of long runs; grow-only)
-    const size_t need = segment_scratch_floats(B, T, D);
+    const size_t slabs = segment_scratch_floats(B, T, D);
+    const size_t need = slabs + (frames_host ? (((size_t)B + 63) & ~(size_t)63) : 0);
     if (need > c->seg_scratch_floats) {
         HIP_TRY(hipStreamSynchronize(s));
         if (c->seg_scratch) HIP_TRY(hipFree(c->seg_scratch));
@@ -861,8 +891,30 @@ extern "C" int sylber_segment(sylber_t c, const float* hidden_dev, int32_t B, in
         HIP_TRY(hipMalloc((void**)&c->seg_scratch, need * 4));
         c->seg_scratch_floats = need;
     }
+    int* frames_dev = nullptr;
+    if (frames_host) {
+        frames_dev = (int*)(c->seg_scratch + slabs);
+        if (launch_upload_ints(frames_dev, frames_host, B, 0, s)) return 1;
+    }
     ProfScope ps(c, s, "segment");
-    return launch_segment(hidden_dev, B, T, D, norm_thr, merge_thr, seg_dev, nseg_dev, feat_dev, c->seg_scratch, s, c->opt_segment);
+    return launch_segment(hidden_dev, B, T, D, norm_thr, merge_thr, seg_dev, nseg_dev, feat_dev, c->seg_scratch, s, c->opt_segment, frames_dev);
+}
+
+extern "C" int sylber_segment(sylber_t c, const float* hidden_dev, int32_t B, int32_t T, int32_t D, float norm_thr,
+                              float merge_thr, int64_t* seg_dev, int32_t* nseg_dev, float* feat_dev, void* stream) {
+    return segment_call("sylber_segment", c, hidden_dev, nullptr, B, T, D, norm_thr, merge_thr, seg_dev, nseg_dev, feat_dev, stream);
+}
+
+extern "C" int sylber_segment_frames(sylber_t c, const float* hidden_dev, const int32_t* frames_host, int32_t B, int32_t T, int32_t D,
+                                     float norm_thr, float merge_thr, int64_t* seg_dev, int32_t* nseg_dev, float* feat_dev, void* stream) {
+    if (!frames_host) { syl_set_error("sylber_segment_frames", "null argument"); return 1; }
+    if (c && c->opt_segment < 0) {
+        syl_set_error("sylber_segment_frames", "not available with SYLBER_OPT_SEGMENT = -1 (the one-workgroup-per-utterance kernel has no per-row bound)");
+        return 1;
+    }
+    for (int b = 0; b < B; ++b)
+        if (frames_host[b] < 1 || frames_host[b] > T) { syl_set_error("sylber_segment_frames", "frames must be in [1, T]"); return 1; }
+    return segment_call("sylber_segment_frames", c, hidden_dev, frames_host, B, T, D, norm_thr, merge_thr, seg_dev, nseg_dev, feat_dev, stream);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -4,7 +4,8 @@
 //
 // One evaluation (rows of a batch element: 16 register rows, then the Tmax frames, padded to Tp = round_up(16 + Tmax, 32)):
 //   cfm_embed      xe = cond part (one GEMM per sample call, to_embed's bias and proj_in's folded in) + (to_embed o proj_in) y
-//   cfm_conv       x  = [registers; gelu(dwconv31(xe)) + xe; zero rows]          (no mask: padded frames are ordinary frames)
+//   cfm_conv       x  = [registers; gelu(dwconv31(xe)) + xe; zero rows]          (no mask: padded frames are ordinary frames, unless
+//                                                                                 sylber_cfm_sample_frames bounds each row: see below)
 //   per layer      h  = AdaRMSNorm(x)                     cfm_adanorm  (16-bit operand out; fp32 in the parity mode)
 //                  qkv = h Wqkv^T                         GEMM, fp32 out
 //                  q, k, V^T = per-head RMSNorm, rotary   cfm_qkprep   (q pre-scaled for the attention kernel)
@@ -17,6 +18,9 @@
 //   cfm_final      v = to_pred(RMSNorm(x)) of the frame rows, fused with the midpoint update of the sampler state
 // The time conditioning (sinusoidal embedding -> Linear -> SiLU -> 16 gamma / beta vectors) depends on t only: all the times
 // of one sample call are computed up front in fp32 (cfm_time_hidden, cfm_time_gb).
+// sylber_cfm_sample_frames: row b has its own frame count Tb (the workspace's `valid` slots hold 16 + Tb).  cfm_conv treats frames at
+// or past Tb as the zero padding at the end and writes zero rows there, attention masks keys at or past 16 + Tb, and cfm_final writes
+// 0 to the output frames at or past Tb: every other launch is row-local, so row b computes what a [1, Tb] call computes.
 #include "kernels.h"
 #include "../../include/sylber_hip.h"
 #include <cmath>
@@ -62,7 +66,7 @@ struct sylber_cfm {
 // ---- workspace layout ----------------------------------------------------------------------------------------------
 struct CfmLayout {
     int B, T, L, Tp, Tpv; long M;
-    size_t o_cond, o_condx, o_xe, o_x, o_h, o_qkv, o_qkvf, o_q, o_k, o_vt, o_ctx, o_ff, o_g, o_temb, o_gb, o_y, o_total;
+    size_t o_cond, o_condx, o_xe, o_x, o_h, o_qkv, o_qkvf, o_q, o_k, o_vt, o_ctx, o_ff, o_g, o_temb, o_gb, o_y, o_valid, o_total;
 };
 static CfmLayout cfm_layout(int precision, int B, int T) {
     CfmLayout l;
@@ -93,6 +97,7 @@ static CfmLayout cfm_layout(int precision, int B, int T) {
     l.o_temb = take((size_t)CFM_MAX_TIMES * CFM_TH * 4);
     l.o_gb = take((size_t)CFM_MAX_TIMES * CFM_NORMS * 2 * CFM_D * 4);
     l.o_y = take((size_t)B * T * CFM_OUT * 4);
+    l.o_valid = take((size_t)B * 4);                         // sylber_cfm_sample_frames: 16 + Tb per row
     l.o_total = o;
     return l;
 }
@@ -166,19 +171,20 @@ __global__ __launch_bounds__(256) void cfm_embed(const float* __restrict__ condx
 // x rows of batch element b: [registers (16); gelu(depthwise conv31(xe) + bias) + xe (T frames, zero padded at both ends);
 // zero rows up to Tp]
 __global__ __launch_bounds__(256) void cfm_conv(const float* __restrict__ xe, const float* __restrict__ w, const float* __restrict__ bias,
-                                                const float* __restrict__ reg, float* __restrict__ x, int T, int Tp) {
+                                                const float* __restrict__ reg, float* __restrict__ x, int T, int Tp, const int* __restrict__ valid) {
     const int r = blockIdx.x, b = blockIdx.y;
+    const int Tb = valid ? valid[b] - CFM_REG : T;           // the row's own frames (T is the row pitch of xe)
     float* dst = x + ((size_t)b * Tp + r) * CFM_D;
     for (int c = threadIdx.x; c < CFM_D; c += 256) {
         float v;
         if (r < CFM_REG) v = reg[r * CFM_D + c];
-        else if (r < CFM_REG + T) {
+        else if (r < CFM_REG + Tb) {
             const int t = r - CFM_REG;
             const float* src = xe + (size_t)b * T * CFM_D + c;
             float acc = bias[c];
             for (int k = 0; k < CFM_KW; ++k) {
                 const int tt = t + k - CFM_KW / 2;
-                if (tt >= 0 && tt < T) acc = fmaf(w[c * CFM_KW + k], src[(size_t)tt * CFM_D], acc);
+                if (tt >= 0 && tt < Tb) acc = fmaf(w[c * CFM_KW + k], src[(size_t)tt * CFM_D], acc);
             }
             v = cfm_gelu(acc) + src[(size_t)t * CFM_D];
         } else v = 0.f;
@@ -263,11 +269,15 @@ __global__ __launch_bounds__(256) void cfm_geglu(const float* __restrict__ ff, v
 // (y and out may alias: each element is read and written by the same lane)
 __global__ __launch_bounds__(256) void cfm_final(const float* __restrict__ x, const float* __restrict__ gamma, const float* __restrict__ wp,
                                                  const float* y, float* out, int B, int T, int Tp, int mode,
-                                                 float dt, int last, float pitch_amp) {
+                                                 float dt, int last, float pitch_amp, const int* __restrict__ valid) {
     const long fr = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
     if (fr >= (long)B * T) return;
     const int b = (int)(fr / T), t = (int)(fr % T);
+    if (valid && t >= valid[b] - CFM_REG) {                  // past the row's own frames: 0 (wave-uniform)
+        if (lane < CFM_OUT) out[(size_t)fr * CFM_OUT + lane] = 0.f;
+        return;
+    }
     const float* xr = x + ((size_t)b * Tp + CFM_REG + t) * CFM_D;
     float v[8], ss = 0.f;
 #pragma unroll
@@ -298,9 +308,15 @@ __global__ __launch_bounds__(256) void cfm_final(const float* __restrict__ x, co
 }
 
 // steps == 1 (and y0 handling): art = y0 (or zeros), channel 12 / pitch_amp when `scale`
-__global__ void cfm_init_state(const float* __restrict__ y0, float* __restrict__ art, size_t n, int scale, float pitch_amp) {
+// valid (nullable): frames t >= valid[b] - 16 of row b (T frames per row) start at, and keep, 0
+__global__ void cfm_init_state(const float* __restrict__ y0, float* __restrict__ art, size_t n, int scale, float pitch_amp,
+                               const int* __restrict__ valid, int T) {
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
         float v = y0 ? y0[i] : 0.f;
+        if (valid) {
+            const size_t fr = i / CFM_OUT;
+            if ((int)(fr % T) >= valid[fr / T] - CFM_REG) v = 0.f;
+        }
         if (scale && i % CFM_OUT == 12) v = __fdiv_rn(v, pitch_amp);
         art[i] = v;
     }
@@ -335,9 +351,9 @@ static void cfm_linspace(int steps, std::vector<float>& t) {
 }
 
 // one evaluation of the decoder at yin (fp32 [B, T, 14]) and time index ti; writes per `mode` (see cfm_final) with the
-// update's base state ybase
+// update's base state ybase.  valid: nullptr (every row T frames) or the workspace's per-row 16 + Tb (sylber_cfm_sample_frames)
 static int cfm_evaluate(const sylber_cfm* h, const CfmLayout& l, char* ws, int ti, const float* yin, const float* ybase, float* out, int mode, float dt,
-                        int last, float pitch_amp, hipStream_t s) {
+                        int last, float pitch_amp, hipStream_t s, const int* valid = nullptr) {
     const bool f32 = h->precision == SYLBER_FP32;
     const int B = l.B, T = l.T;
     float* xe = (float*)(ws + l.o_xe); float* x = (float*)(ws + l.o_x); void* hb = ws + l.o_h;
@@ -347,7 +363,7 @@ static int cfm_evaluate(const sylber_cfm* h, const CfmLayout& l, char* ws, int t
     const dim3 rows4((unsigned)((l.M + 3) / 4));
     hipLaunchKernelGGL(cfm_embed, dim3(B * T), dim3(256), 0, s, (const float*)(ws + l.o_condx), yin, h->wy, xe);
     CFM_RUN("embed", 0);
-    hipLaunchKernelGGL(cfm_conv, dim3(l.Tp, B), dim3(256), 0, s, xe, h->conv_w, h->conv_b, h->reg, x, T, l.Tp);
+    hipLaunchKernelGGL(cfm_conv, dim3(l.Tp, B), dim3(256), 0, s, xe, h->conv_w, h->conv_b, h->reg, x, T, l.Tp, valid);
     CFM_RUN("conv", 0);
     auto norm = [&](int n) {
         const float* ga = gb + (size_t)n * 2 * CFM_D;
@@ -365,13 +381,13 @@ static int cfm_evaluate(const sylber_cfm* h, const CfmLayout& l, char* ws, int t
             float* qkvf = (float*)(ws + l.o_qkvf);
             hipLaunchKernelGGL((cfm_qkprep<FMT_BF16, true>), gq, dim3(256), 0, s, qkv, qg, kg, h->inv_freq, nullptr, nullptr, nullptr, qkvf, l.L, l.Tp, l.Tpv);
             CFM_RUN("qkprep", 0);
-            CFM_RUN("attention", launch_attention_f32(qkvf, qkvf + SYL_HIDDEN, qkvf + 2 * SYL_HIDDEN, nullptr, (float*)ctx, B, l.L, l.Tp, s));
+            CFM_RUN("attention", launch_attention_f32(qkvf, qkvf + SYL_HIDDEN, qkvf + 2 * SYL_HIDDEN, valid, (float*)ctx, B, l.L, l.Tp, s));
         } else {
             bf16_t* q = (bf16_t*)(ws + l.o_q); bf16_t* k = (bf16_t*)(ws + l.o_k); bf16_t* vt = (bf16_t*)(ws + l.o_vt);
             if (h->fmt == FMT_F16) hipLaunchKernelGGL((cfm_qkprep<FMT_F16, false>), gq, dim3(256), 0, s, qkv, qg, kg, h->inv_freq, q, k, vt, nullptr, l.L, l.Tp, l.Tpv);
             else hipLaunchKernelGGL((cfm_qkprep<FMT_BF16, false>), gq, dim3(256), 0, s, qkv, qg, kg, h->inv_freq, q, k, vt, nullptr, l.L, l.Tp, l.Tpv);
             CFM_RUN("qkprep", 0);
-            CFM_RUN("attention", launch_attention(q, k, vt, nullptr, (bf16_t*)ctx, B, l.L, l.Tp, l.Tpv, 0, s, h->fmt));
+            CFM_RUN("attention", launch_attention(q, k, vt, valid, (bf16_t*)ctx, B, l.L, l.Tp, l.Tpv, 0, s, h->fmt));
         }
         CFM_RUN("out", cfm_gemm(h, ctx, SYL_HIDDEN, h->wo[li], M, CFM_D, CFM_D, nullptr, x, CFM_D, true, s));
         norm(2 * li + 1);
@@ -384,14 +400,14 @@ static int cfm_evaluate(const sylber_cfm* h, const CfmLayout& l, char* ws, int t
         CFM_RUN("ff2", cfm_gemm(h, g, CFM_FIP, h->w2[li], M, CFM_D, CFM_FIP, h->b2 + (size_t)li * CFM_D, x, CFM_D, true, s));
     }
     hipLaunchKernelGGL(cfm_final, dim3((unsigned)(((long)B * T + 3) / 4)), dim3(256), 0, s, x, h->fin_g, h->pred_w, ybase, out, B, T, l.Tp, mode,
-                       dt, last, pitch_amp);
+                       dt, last, pitch_amp, valid);
     CFM_RUN("final", 0);
     return 0;
 }
 
 // per call: clear the workspace, the conditioning GEMM (once), the time conditioning of every time of the call
 static int cfm_prepare(const sylber_cfm* h, const CfmLayout& l, char* ws, const float* cond_dev, const float* times, int ntimes, hipStream_t s) {
-    HIP_TRY(hipMemsetAsync(ws, 0, l.o_total, s));
+    HIP_TRY(hipMemsetAsync(ws, 0, l.o_valid, s));          // (everything but the per-row counts, the last region: written before this)
     const size_t n = (size_t)l.B * l.T * CFM_COND;
     void* cb = ws + l.o_cond;
     if (h->precision == SYLBER_FP32) HIP_TRY(hipMemcpyAsync(cb, cond_dev, n * 4, hipMemcpyDeviceToDevice, s));
@@ -538,16 +554,27 @@ static int cfm_check(const char* what, sylber_cfm_t h, const float* cond, int B,
     return 0;
 }
 
-extern "C" int sylber_cfm_sample(sylber_cfm_t h, const float* cond_emb_dev, int32_t B, int32_t T, int32_t steps, const float* y0_dev,
-                                 float pitch_amp, float* art_dev, void* workspace_dev, void* stream) {
-    if (cfm_check("sylber_cfm_sample", h, cond_emb_dev, B, T, art_dev, workspace_dev)) return 1;
-    if (steps < 1 || 2 * (steps - 1) > CFM_MAX_TIMES) { syl_set_error("sylber_cfm_sample", "steps must be in 1..65"); return 1; }
-    if (!(pitch_amp != 0.0f) || !std::isfinite(pitch_amp)) { syl_set_error("sylber_cfm_sample", "pitch_amp must be finite and nonzero"); return 1; }
+// frames_host: nullptr (sylber_cfm_sample) or each row's own frame count (sylber_cfm_sample_frames)
+static int cfm_sample(const char* what, sylber_cfm_t h, const float* cond_emb_dev, const int32_t* frames_host, int32_t B, int32_t T, int32_t steps,
+                      const float* y0_dev, float pitch_amp, float* art_dev, void* workspace_dev, void* stream) {
+    if (cfm_check(what, h, cond_emb_dev, B, T, art_dev, workspace_dev)) return 1;
+    if (steps < 1 || 2 * (steps - 1) > CFM_MAX_TIMES) { syl_set_error(what, "steps must be in 1..65"); return 1; }
+    if (!(pitch_amp != 0.0f) || !std::isfinite(pitch_amp)) { syl_set_error(what, "pitch_amp must be finite and nonzero"); return 1; }
+    if (frames_host)
+        for (int b = 0; b < B; ++b)
+            if (frames_host[b] < 1 || frames_host[b] > T) { syl_set_error(what, "frames must be in [1, T]"); return 1; }
     DevGuardC dg(h->device);
     hipStream_t s = (hipStream_t)stream;
     const size_t n = (size_t)B * T * CFM_OUT;
+    const CfmLayout l = cfm_layout(h->precision, B, T);
+    char* ws = (char*)workspace_dev;
+    int* valid = nullptr;
+    if (frames_host) {
+        valid = (int*)(ws + l.o_valid);
+        if (launch_upload_ints(valid, frames_host, B, CFM_REG, s)) return 1;
+    }
     // art is the sampler state; steps == 1 is a one-point grid (the state is y0) and scales channel 12 right away
-    hipLaunchKernelGGL(cfm_init_state, dim3(256), dim3(256), 0, s, y0_dev, art_dev, n, steps == 1 ? 1 : 0, pitch_amp);
+    hipLaunchKernelGGL(cfm_init_state, dim3(256), dim3(256), 0, s, y0_dev, art_dev, n, steps == 1 ? 1 : 0, pitch_amp, valid, T);
     HIP_TRY(hipGetLastError());
     if (steps == 1) return 0;
     std::vector<float> t;
@@ -558,16 +585,25 @@ extern "C" int sylber_cfm_sample(sylber_cfm_t h, const float* cond_emb_dev, int3
         const float dt = t[i + 1] - t[i], half = 0.5f * dt;
         times.push_back(t[i]); times.push_back(t[i] + half); dts.push_back(dt);
     }
-    const CfmLayout l = cfm_layout(h->precision, B, T);
-    char* ws = (char*)workspace_dev;
     if (cfm_prepare(h, l, ws, cond_emb_dev, times.data(), (int)times.size(), s)) return 1;
     float* ymid = (float*)(ws + l.o_y);
     for (int i = 0; i + 1 < steps; ++i) {
         const float dt = dts[i], half = 0.5f * dt;
-        if (cfm_evaluate(h, l, ws, 2 * i, art_dev, art_dev, ymid, 1, half, 0, pitch_amp, s)) return 1;
-        if (cfm_evaluate(h, l, ws, 2 * i + 1, ymid, art_dev, art_dev, 2, dt, i + 2 == steps, pitch_amp, s)) return 1;
+        if (cfm_evaluate(h, l, ws, 2 * i, art_dev, art_dev, ymid, 1, half, 0, pitch_amp, s, valid)) return 1;
+        if (cfm_evaluate(h, l, ws, 2 * i + 1, ymid, art_dev, art_dev, 2, dt, i + 2 == steps, pitch_amp, s, valid)) return 1;
     }
     return 0;
+}
+
+extern "C" int sylber_cfm_sample(sylber_cfm_t h, const float* cond_emb_dev, int32_t B, int32_t T, int32_t steps, const float* y0_dev,
+                                 float pitch_amp, float* art_dev, void* workspace_dev, void* stream) {
+    return cfm_sample("sylber_cfm_sample", h, cond_emb_dev, nullptr, B, T, steps, y0_dev, pitch_amp, art_dev, workspace_dev, stream);
+}
+
+extern "C" int sylber_cfm_sample_frames(sylber_cfm_t h, const float* cond_emb_dev, const int32_t* frames_host, int32_t B, int32_t T,
+                                        int32_t steps, const float* y0_dev, float pitch_amp, float* art_dev, void* workspace_dev, void* stream) {
+    if (!frames_host) { syl_set_error("sylber_cfm_sample_frames", "null argument"); return 1; }
+    return cfm_sample("sylber_cfm_sample_frames", h, cond_emb_dev, frames_host, B, T, steps, y0_dev, pitch_amp, art_dev, workspace_dev, stream);
 }
 
 extern "C" int sylber_cfm_eval(sylber_cfm_t h, const float* x_dev, float t, const float* cond_emb_dev, int32_t B, int32_t T, float* v_dev,

@@ -19,10 +19,18 @@
 #define C0_ROWS 256  // conv0 output rows per workgroup
 
 // ---------------------------------------------------------------------------------------------------
+// rows: optional per-utterance conv0 frame counts (SYLBER_OPT_PER_UTTERANCE), nullptr = every row has the padded L0.  A row with
+// its own count n is chunked exactly as a call whose padded length is n would chunk it (ceil(n / 2048) chunks of ceil(n / nchunk_n)
+// frames), so its fp64 sums happen in the same order whatever the batch's L0 is; chunks past its own are written as exact zeros.
 __global__ __launch_bounds__(256) void conv0_stats_kernel(const float* __restrict__ wav, int Lmax, int L0, int chunk,
-                                                          double* __restrict__ partials, int nchunk) {
+                                                          double* __restrict__ partials, int nchunk, const int* __restrict__ rows) {
     const int b = blockIdx.y, ck = blockIdx.x;
     const float* x = wav + (size_t)b * Lmax;
+    if (rows) {
+        L0 = rows[b];
+        const int nck = (L0 + 2047) / 2048;
+        chunk = (L0 + nck - 1) / nck;
+    }
     const int l0 = ck * chunk;
     const int l1 = min(L0, l0 + chunk);
     double acc[NSTAT];
@@ -59,12 +67,17 @@ __global__ __launch_bounds__(256) void conv0_stats_kernel(const float* __restric
 __global__ __launch_bounds__(512) void conv0_finalize_kernel(const double* __restrict__ partials, int nchunk,
                                                              const float* __restrict__ w0, const float* __restrict__ gn_w,
                                                              const float* __restrict__ gn_b, int L0,
-                                                             float* __restrict__ scale_shift) {
+                                                             float* __restrict__ scale_shift, const int* __restrict__ rows) {
     __shared__ double st[NSTAT];
     const int b = blockIdx.x, c = threadIdx.x;
+    const int pitch = nchunk;                       // partials of utterance b: [b * pitch, b * pitch + nchunk)
+    if (rows) {                                     // the row's own frames and chunks (see conv0_stats_kernel)
+        L0 = rows[b];
+        nchunk = (L0 + 2047) / 2048;
+    }
     if (c < NSTAT) {
         double s = 0.0;
-        for (int k = 0; k < nchunk; ++k) s += partials[((size_t)b * nchunk + k) * NSTAT + c];
+        for (int k = 0; k < nchunk; ++k) s += partials[((size_t)b * pitch + k) * NSTAT + c];
         st[c] = s;
     }
     __syncthreads();
@@ -287,15 +300,15 @@ __global__ __launch_bounds__(256, 2) void conv0_mfma_kernel(const float* __restr
     }
 }
 
-int launch_conv0_stats(const float* wav, int B, int Lmax, int L0, double* partials, int nchunk, hipStream_t s) {
+int launch_conv0_stats(const float* wav, int B, int Lmax, int L0, double* partials, int nchunk, hipStream_t s, const int* rows) {
     const int chunk = (L0 + nchunk - 1) / nchunk;
-    hipLaunchKernelGGL(conv0_stats_kernel, dim3(nchunk, B), dim3(256), 0, s, wav, Lmax, L0, chunk, partials, nchunk);
+    hipLaunchKernelGGL(conv0_stats_kernel, dim3(nchunk, B), dim3(256), 0, s, wav, Lmax, L0, chunk, partials, nchunk, rows);
     HIP_TRY(hipGetLastError());
     return 0;
 }
 int launch_conv0_finalize(const double* partials, int nchunk, const float* w0, const float* gn_w, const float* gn_b, int B,
-                          int L0, float* scale_shift, hipStream_t s) {
-    hipLaunchKernelGGL(conv0_finalize_kernel, dim3(B), dim3(512), 0, s, partials, nchunk, w0, gn_w, gn_b, L0, scale_shift);
+                          int L0, float* scale_shift, hipStream_t s, const int* rows) {
+    hipLaunchKernelGGL(conv0_finalize_kernel, dim3(B), dim3(512), 0, s, partials, nchunk, w0, gn_w, gn_b, L0, scale_shift, rows);
     HIP_TRY(hipGetLastError());
     return 0;
 }

@@ -111,9 +111,11 @@ int launch_gemm_f32(const GemmArgsF32& a, hipStream_t s);
 // ------------------------------------------------------------------------------------------------
 // conv frontend layer 0: Conv1d(1->512,k10,s5) + GroupNorm(per (b,c) over time) + GELU, channels-last out
 // ------------------------------------------------------------------------------------------------
-int launch_conv0_stats(const float* wav, int B, int Lmax, int L0, double* partials, int nchunk, hipStream_t s);
+// rows (device, [B], nullable): per-utterance conv0 frame counts for the GroupNorm statistics (SYLBER_OPT_PER_UTTERANCE);
+// nullptr = every utterance over the padded L0 (the reference's behaviour)
+int launch_conv0_stats(const float* wav, int B, int Lmax, int L0, double* partials, int nchunk, hipStream_t s, const int* rows = nullptr);
 int launch_conv0_finalize(const double* partials, int nchunk, const float* w0, const float* gn_w, const float* gn_b,
-                          int B, int L0, float* scale_shift, hipStream_t s);
+                          int B, int L0, float* scale_shift, hipStream_t s, const int* rows = nullptr);
 // out: [B][R0][512] (bf16 or f32); rows l >= L0 are written as zeros
 // fmt FMT_SPLIT: erf GELU, hi halves at out, lo halves at out + out_lo (element offset)
 int launch_conv0_gn_gelu(const float* wav, int B, int Lmax, int L0, int R0, const float* w0,
@@ -174,11 +176,16 @@ int launch_posconv_f32(const float* xpad, const float* w, const float* bias, con
 // segmentation (get_segment + mean-pool), numpy-f32 bit-exact
 // ------------------------------------------------------------------------------------------------
 // mode 0: wide (frame norms, one workgroup per run of speech frames, compaction, pooling: all CUs); -1: one workgroup per utterance
+// frames (device, [B], nullable): row b is segmented and pooled over its first frames[b] frames only (1 <= frames[b] <= T; the row
+// pitch stays T); nullptr = T frames for every row.  Wide path only: mode -1 with frames is refused.
 int launch_segment(const float* hidden, int B, int T, int D, float norm_thr, float merge_thr, int64_t* seg, int* nseg,
-                   float* feat, float* scratch, hipStream_t s, int mode = 0);
+                   float* feat, float* scratch, hipStream_t s, int mode = 0, const int* frames = nullptr);
 size_t segment_scratch_floats(int B, int T, int D);
 
 // misc elementwise
+// dst[i] = vals_host[i] + add for i < n, stream-ordered: the values travel as kernel arguments (no pageable copy, nothing
+// to keep alive, capturable into a hipGraph)
+int launch_upload_ints(int* dst, const int32_t* vals_host, int n, int add, hipStream_t s);
 int launch_f32_to_bf16(const float* in, bf16_t* out, size_t n, hipStream_t s);
 int launch_f32_to_split16(const float* in, bf16_t* out, long lo_off, size_t n, hipStream_t s);   // hi plane at out, lo plane at out + lo_off
 int launch_bf16_to_f32_rows(const bf16_t* in, long ld_in, float* out, int B, int Tp, int T, int D, hipStream_t s, int fmt = 0, long in_lo = 0);

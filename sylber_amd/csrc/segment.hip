@@ -387,7 +387,8 @@ __global__ __launch_bounds__(256) void segment_norms_kernel(const float* __restr
 
 template <bool GS>
 __global__ __launch_bounds__(256) void segment_runs_kernel(const float* __restrict__ hidden, int T, float norm_thr, float merge_thr,
-                                                           float* __restrict__ scratch, size_t slab, int list_cap) {
+                                                           float* __restrict__ scratch, size_t slab, int list_cap,
+                                                           const int* __restrict__ frames) {
     extern __shared__ __attribute__((aligned(16))) float lds_f[];
     float* ca_s = lds_f;                       // [768]
     float* cb_s = ca_s + SEG_D;                // [768]
@@ -400,15 +401,18 @@ __global__ __launch_bounds__(256) void segment_runs_kernel(const float* __restri
     const float* g_npw = sl + T;
     int* g_slot = (int*)(sl + 2 * (size_t)T);  // [(T+1)][2]
     int* g_live = g_slot + 2 * ((size_t)T + 1);
+    // the utterance's own end (sylber_segment_frames): frames at or past Tb do not exist for the scan, a run ends at Tb as at the end of
+    // an array.  T stays the row pitch of `hidden` and the slab.
+    const int Tb = frames ? frames[b] : T;
 
     // ---- which runs are mine: run r (in frame order) belongs to workgroup r % G
     if (tid < 16) sh_i[tid] = 0;
     __syncthreads();
     int running = 0;
-    for (int c0 = 0; c0 < T; c0 += 256) {
+    for (int c0 = 0; c0 < Tb; c0 += 256) {
         const int i = c0 + tid;
-        const bool sp = i < T && g_nsq[i] >= norm_thr;
-        const bool pv = i > 0 && i < T && g_nsq[i - 1] >= norm_thr;
+        const bool sp = i < Tb && g_nsq[i] >= norm_thr;
+        const bool pv = i > 0 && i < Tb && g_nsq[i - 1] >= norm_thr;
         const bool st = sp && !pv;
         const unsigned long long bal = __builtin_amdgcn_ballot_w64(st);
         if (lane == 0) sh_i[4 + wave] = __builtin_popcountll(bal);
@@ -428,18 +432,18 @@ __global__ __launch_bounds__(256) void segment_runs_kernel(const float* __restri
     for (int jr = 0; jr < mine; ++jr) {
         __syncthreads();                                     // the previous run's LDS is free
         const int base = mystart[jr];
-        // ---- the run's end: the first non-speech frame behind its start, or T
-        if (tid == 0) sh_i[8] = T;
+        // ---- the run's end: the first non-speech frame behind its start, or Tb
+        if (tid == 0) sh_i[8] = Tb;
         __syncthreads();
-        for (int c0 = base + 1; c0 < T; c0 += 256) {
+        for (int c0 = base + 1; c0 < Tb; c0 += 256) {
             const int i = c0 + tid;
-            const bool ns = i < T && !(g_nsq[i] >= norm_thr);
+            const bool ns = i < Tb && !(g_nsq[i] >= norm_thr);
             const unsigned long long bal = __builtin_amdgcn_ballot_w64(ns);
             if (bal != 0ull && lane == 0) atomicMin(&sh_i[8], c0 + wave * 64 + (int)__builtin_ctzll(bal));
             __syncthreads();
             const int e = sh_i[8];
             __syncthreads();
-            if (e < T) break;
+            if (e < Tb) break;
         }
         const int end = sh_i[8];
         const int len = end - base;
@@ -605,16 +609,17 @@ __global__ __launch_bounds__(256) void segment_runs_kernel(const float* __restri
 
 // live slots in slot order = the reference's table (np.array(segments) without the merged indices, segment_utils.py:130-131)
 __global__ __launch_bounds__(256) void segment_compact_kernel(int T, const float* __restrict__ scratch, size_t slab, int64_t* __restrict__ seg_out,
-                                                              int* __restrict__ nseg_out) {
+                                                              int* __restrict__ nseg_out, const int* __restrict__ frames) {
     __shared__ int cnt_s[4];
     const int b = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const float* sl = scratch + (size_t)b * slab;
     const int* g_slot = (const int*)(sl + 2 * (size_t)T);
     const int* g_live = g_slot + 2 * ((size_t)T + 1);
+    const int Tb = frames ? frames[b] : T;                   // (slots at or past the row's own end were never written by this call)
     int running = 0;
-    for (int c0 = 0; c0 < T; c0 += 256) {
+    for (int c0 = 0; c0 < Tb; c0 += 256) {
         const int i = c0 + tid;
-        const bool lv = i < T && g_live[i] != 0;
+        const bool lv = i < Tb && g_live[i] != 0;
         const unsigned long long bal = __builtin_amdgcn_ballot_w64(lv);
         if (lane == 0) cnt_s[wave] = __builtin_popcountll(bal);
         __syncthreads();
@@ -659,9 +664,10 @@ size_t segment_scratch_floats(int B, int T, int D) {
 
 // mode 0: the wide path (norms / runs / compaction / pooling on all CUs); mode -1: one workgroup per utterance (rounds 1-5; A/B and bitwise reference)
 int launch_segment(const float* hidden, int B, int T, int D, float norm_thr, float merge_thr, int64_t* seg, int* nseg,
-                   float* feat, float* scratch, hipStream_t s, int mode) {
+                   float* feat, float* scratch, hipStream_t s, int mode, const int* frames) {
     if (D != SEG_D) { syl_set_error("launch_segment", "feature dim must be 768"); return 1; }
     if (T < 1) { syl_set_error("launch_segment", "T must be >= 1"); return 1; }
+    if (frames && mode < 0) { syl_set_error("launch_segment", "per-row frame counts need the wide path (SYLBER_OPT_SEGMENT = 0)"); return 1; }
     if (mode >= 0) {
         if (!scratch) { syl_set_error("launch_segment", "the wide path needs its scratch slab (segment_scratch_floats)"); return 1; }
         const size_t slab = seg_wide_slab_floats(T);
@@ -675,10 +681,10 @@ int launch_segment(const float* hidden, int B, int T, int D, float norm_thr, flo
             static PerDeviceOnce once;
             if (once.need()) HIP_TRY(hipFuncSetAttribute((const void*)segment_runs_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         }
-        hipLaunchKernelGGL(segment_runs_kernel<false>, dim3(G, B), dim3(256), lds_l, s, hidden, T, norm_thr, merge_thr, scratch, slab, list_cap);
+        hipLaunchKernelGGL(segment_runs_kernel<false>, dim3(G, B), dim3(256), lds_l, s, hidden, T, norm_thr, merge_thr, scratch, slab, list_cap, frames);
         if (T > SEG_LCAP)
-            hipLaunchKernelGGL(segment_runs_kernel<true>, dim3(G, B), dim3(256), lds_g, s, hidden, T, norm_thr, merge_thr, scratch, slab, list_cap);
-        hipLaunchKernelGGL(segment_compact_kernel, dim3(B), dim3(256), 0, s, T, scratch, slab, seg, nseg);
+            hipLaunchKernelGGL(segment_runs_kernel<true>, dim3(G, B), dim3(256), lds_g, s, hidden, T, norm_thr, merge_thr, scratch, slab, list_cap, frames);
+        hipLaunchKernelGGL(segment_compact_kernel, dim3(B), dim3(256), 0, s, T, scratch, slab, seg, nseg, frames);
         if (feat) {
             int PX = (T + 15) / 16; PX = PX < 1 ? 1 : (PX > 64 ? 64 : PX);
             hipLaunchKernelGGL(segment_pool_kernel, dim3(PX, B), dim3(256), 0, s, hidden, T, seg, nseg, feat);

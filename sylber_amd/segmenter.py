@@ -249,28 +249,48 @@ class HubertEncoderHIP:
         _lib.check(self.lib.sylber_set_graph_mode(self.handle, 1 if enable else 0), "sylber_set_graph_mode")
         self._graph_stream = torch.cuda.Stream(device=self.device) if enable else None
 
+    def set_per_utterance(self, enable: bool = True) -> None:
+        """batch-invariant encoder (include/sylber_hip.h SYLBER_OPT_PER_UTTERANCE): conv0's GroupNorm statistics of every row over its
+        own length, so ``forward(...)[b, :T_b]`` is bit-identical to a forward of that clip alone"""
+        self.set_option(_lib.OPT_PER_UTTERANCE, 1 if enable else 0)
+
+    def frame_counts(self, lengths: Sequence[int]) -> List[int]:
+        """frames of each row's own length (``num_frames`` per row)"""
+        return [self.num_frames(int(n)) for n in lengths]
+
     def segment(self, hidden: torch.Tensor, norm_threshold: float, merge_threshold: float, with_features: bool = True,
-                out=None):
+                out=None, frames: Optional[Sequence[int]] = None):
         """hidden: [B, T, 768] float32 device.  Returns (segments [B,T,2] int64, nseg [B] int32, feats [B,T,768]).
         Runs on the CURRENT torch stream; it touches no encoder workspace, so a caller may run it on a side
         stream concurrently with the next batch's forward; it uses the handle's own scratch slab (frame norms, slot table), so the
-        segment calls of one handle must be ordered on one stream."""
+        segment calls of one handle must be ordered on one stream.
+        ``frames``: each row's own frame count (``sylber_segment_frames``): row b is segmented and pooled as ``hidden[b, :frames[b]]``
+        alone would be, frames past it are never read.  Counts outside ``[1, T]`` raise ValueError."""
         assert hidden.is_cuda and hidden.dtype == torch.float32 and hidden.is_contiguous()
         B, T, D = hidden.shape
+        farr = None
+        if frames is not None:
+            fl = [int(f) for f in frames]
+            if len(fl) != B:
+                raise ValueError("frames must have one count per row (%d), got %d" % (B, len(fl)))
+            if any(f < 1 or f > T for f in fl):
+                raise ValueError("frame counts must be in [1, %d], got %s" % (T, fl))
+            farr = (ctypes.c_int32 * B)(*fl)
         if out is not None:
             seg, nseg, feats = out
         else:
             seg = torch.empty(B, T, 2, dtype=torch.int64, device=hidden.device)
             nseg = torch.empty(B, dtype=torch.int32, device=hidden.device)
             feats = torch.empty(B, T, D, dtype=torch.float32, device=hidden.device) if with_features else None
+        args = (B, T, D, ctypes.c_float(float(np.float32(norm_threshold))), ctypes.c_float(float(np.float32(merge_threshold))),
+                ctypes.c_void_p(seg.data_ptr()), ctypes.c_void_p(nseg.data_ptr()),
+                ctypes.c_void_p(feats.data_ptr()) if feats is not None else None, _stream_ptr(hidden.device))
         with torch.cuda.device(hidden.device):
-            st = self.lib.sylber_segment(self.handle, ctypes.c_void_p(hidden.data_ptr()), B, T, D,
-                                         ctypes.c_float(float(np.float32(norm_threshold))),
-                                         ctypes.c_float(float(np.float32(merge_threshold))),
-                                         ctypes.c_void_p(seg.data_ptr()), ctypes.c_void_p(nseg.data_ptr()),
-                                         ctypes.c_void_p(feats.data_ptr()) if feats is not None else None,
-                                         _stream_ptr(hidden.device))
-        _lib.check(st, "sylber_segment")
+            if farr is None:
+                st = self.lib.sylber_segment(self.handle, ctypes.c_void_p(hidden.data_ptr()), *args)
+            else:
+                st = self.lib.sylber_segment_frames(self.handle, ctypes.c_void_p(hidden.data_ptr()), farr, *args)
+        _lib.check(st, "sylber_segment" if farr is None else "sylber_segment_frames")
         return seg, nseg, feats
 
     def set_profiling(self, on: bool) -> None:
@@ -323,6 +343,11 @@ class Segmenter:
         # two handles, as bench.py's pipeline runs, one column is: profiles/r04_resln_prefetch.md).  Bit-identical either way.
         self._resln_prefetch = int(kwargs.get("resln_prefetch", 3))
         self.speech_model.set_option(6, self._resln_prefetch)
+        # batch-invariant mode (off by default): every clip of a batch gets exactly the results it gets alone -- GroupNorm statistics
+        # over its own length (SYLBER_OPT_PER_UTTERANCE), segmentation over its own frames (sylber_segment_frames), hidden states cut to them
+        self.batch_invariant = bool(kwargs.get("batch_invariant", False))
+        if self.batch_invariant:
+            self.speech_model.set_per_utterance(True)
         self.norm_threshold = norm_threshold
         self.merge_threshold = merge_threshold
         # where __call__'s numpy results live: "pinned" (default) = views of leased page-locked blocks, at most
@@ -484,22 +509,28 @@ class Segmenter:
         return slot["buf"][:n].view(*shape), slot
 
     def segment(self, input_values=None, features=None, attention_mask=None, mergethreshold=None, normthreshold=None,
-                **kwargs):
+                frames=None, **kwargs):
         """Tensor-native sibling of ``__call__`` with the signature of the reference's ``Sylber.segment``
         (sylber/model/sylber.py:208-247): a padded ``[B, N]`` waveform batch (+ 0/1 ``attention_mask``) or
         precomputed ``features [B, T, 768]`` in, ``(features, segments, avg_fts)`` out — ``segments`` a list of
         int64 ``[n, 2]`` arrays, ``avg_fts`` the segment means zero-padded to ``[B, max(n, 1), 768]`` on the
-        device (an utterance without segments contributes one zero row, sylber.py:238-241)."""
+        device (an utterance without segments contributes one zero row, sylber.py:238-241).
+        With ``batch_invariant=True`` every row of the waveform branch is segmented over its own frames (from ``attention_mask``) and
+        ``features`` past them are zeroed.  ``frames=`` gives the features branch each row's frame count (default: all ``T``)."""
         dev = self.speech_model.device
         if features is None:
             x = input_values.to(dev, torch.float32).contiguous()
             lengths = None if attention_mask is None else [int(v) for v in attention_mask.sum(-1).tolist()]
             features = self.speech_model.forward(x, lengths)
+            if self.batch_invariant:
+                frames = self.speech_model.frame_counts(lengths if lengths is not None else [x.shape[1]] * x.shape[0])
+                for b, f in enumerate(frames):
+                    features[b, f:] = 0.0
         else:
             features = features.to(dev, torch.float32).contiguous()
         nt = self.norm_threshold if normthreshold is None else normthreshold
         mt = self.merge_threshold if mergethreshold is None else mergethreshold
-        seg, nseg, feats = self.speech_model.segment(features, nt, mt)
+        seg, nseg, feats = self.speech_model.segment(features, nt, mt, frames=frames)
         nseg_h = nseg.cpu().numpy()
         nmax = max(int(nseg_h.max()), 1)
         seg_h = seg[:, :nmax].cpu().numpy()
@@ -523,7 +554,8 @@ class Segmenter:
         parts = self._split_plan(batch_wavs) if (is_batch and tr is None and gtr is None) else None
         if parts is not None:
             return self._call_in_parts(parts, in_second)
-        hidden, _ = self.encode_batch(batch_wavs)
+        hidden, lengths = self.encode_batch(batch_wavs)
+        frames = self.speech_model.frame_counts(lengths) if self.batch_invariant else None
         gmark("forward done")
         mark("padded, H2D and forward issued")
         # D2H (sylber.py:122-138's .cpu().numpy()) into ONE leased page-locked block (PinnedOutputPool: persistent blocks, no
@@ -560,7 +592,8 @@ class Segmenter:
                 blk[:B * T * D * 4].view(torch.float32).view(B, T, D).copy_(hidden, non_blocking=True)
                 gmark("hidden states D2H done", copy_s)
             hidden.record_stream(copy_s)
-        seg, nseg, feats = self.speech_model.segment(hidden, self.norm_threshold, self.merge_threshold, with_features=want_f)
+        seg, nseg, feats = self.speech_model.segment(hidden, self.norm_threshold, self.merge_threshold, with_features=want_f,
+                                                     frames=frames)
         gmark("boundary detection done")
         nseg_pin = self._nseg_pinned(B)
         nseg_pin.copy_(nseg, non_blocking=True)
@@ -605,7 +638,8 @@ class Segmenter:
                 # (a view of the leased block, like hidden_states; a scratch block is reused by the next call, so its rows are copied)
                 o["segment_features"] = (feats_h[i, :n] if handed else feats_h[i, :n].copy()) if n > 0 else np.array([])
             if want_h:
-                o["hidden_states"] = hidden_h[i] if handed else hidden_h[i].copy()
+                hb = hidden_h[i] if frames is None else hidden_h[i, :frames[i]]
+                o["hidden_states"] = hb if handed else hb.copy()
             outputs.append(o)
         mark("dicts built")
         return outputs if is_batch else outputs[0]
@@ -732,7 +766,8 @@ class Segmenter:
                 hidden = self.speech_model.forward(batch, lengths, out=flat(d, "hid", B_ * T_ * 768, torch.float32).view(B_, T_, 768))
                 out = (flat(d, "seg", B_ * T_ * 2, torch.int64).view(B_, T_, 2), flat(d, "nseg", B_, torch.int32),
                        flat(d, "feat", B_ * T_ * 768, torch.float32).view(B_, T_, 768) if want_f else None)
-                seg, nseg, feats = self.speech_model.segment(hidden, self.norm_threshold, self.merge_threshold, out=out)
+                frames = self.speech_model.frame_counts(lengths) if self.batch_invariant else None
+                seg, nseg, feats = self.speech_model.segment(hidden, self.norm_threshold, self.merge_threshold, out=out, frames=frames)
             tr = self.__dict__.get("_trace")                  # tools/api_stream_timeline.py: (label, host time[, event]) marks
             done = torch.cuda.Event(enable_timing=tr is not None)
             done.record(cur)
@@ -769,7 +804,7 @@ class Segmenter:
                 out_ev.record(d2h)
             d["in_free"], d["out_free"] = done, out_ev
             t.update(dict(shape=(B, T, D), kcap=kcap, offs=(o_cnt, o_seg, o_feat), owner=owner, handed=handed, out_ev=out_ev,
-                          dev=(seg, feats)))
+                          dev=(seg, feats), frames=frames))
             t.pop("batch")
             return t
 
@@ -811,7 +846,8 @@ class Segmenter:
                 if want_f:
                     o["segment_features"] = (feats_h[i, :n].copy() if tcopy else feats_h[i, :n]) if n > 0 else np.array([])
                 if want_h:
-                    o["hidden_states"] = hidden_h[i] if handed else hidden_h[i].copy()
+                    hb = hidden_h[i] if t["frames"] is None else hidden_h[i, :t["frames"][i]]
+                    o["hidden_states"] = hb if handed else hb.copy()
                 outputs.append(o)
             return outputs[0] if t["single"] else outputs
 

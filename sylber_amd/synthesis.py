@@ -10,7 +10,7 @@ from __future__ import annotations
 
 import ctypes
 from pathlib import Path
-from typing import Dict, Optional
+from typing import Dict, Optional, Sequence
 
 import numpy as np
 import torch
@@ -207,23 +207,34 @@ class CfmDecoder:
             _lib.check(1, "sylber_cfm_workspace_bytes")
         return torch.empty(n, dtype=torch.uint8, device=self.device)
 
-    def sample(self, cond_emb: torch.Tensor, steps: int = 5, y0: Optional[torch.Tensor] = None, pitch_amp: float = 1.0) -> torch.Tensor:
+    def sample(self, cond_emb: torch.Tensor, steps: int = 5, y0: Optional[torch.Tensor] = None, pitch_amp: float = 1.0,
+               frames: Optional[Sequence[int]] = None) -> torch.Tensor:
         """``cfm_wrapper.sample(cond_emb=..., steps=...)`` from ``y0`` (None: zeros, i.e. ``rand_scale = 0``), then channel 12
-        divided by ``pitch_amp`` -> ``[B, T, 14]`` fp32 on the device.  Enqueued on the current stream."""
+        divided by ``pitch_amp`` -> ``[B, T, 14]`` fp32 on the device.  Enqueued on the current stream.
+        ``frames``: each row's own frame count (``sylber_cfm_sample_frames``): row b is sampled as ``cond_emb[b:b+1, :frames[b]]``
+        alone would be, and ``art[b, frames[b]:]`` is 0.  Counts outside ``[1, T]`` raise ValueError."""
         if isinstance(steps, bool) or int(steps) != steps or not 1 <= int(steps) <= 65:
             raise ValueError("steps must be an integer in 1..65, got %r" % (steps,))
         cond = self._cond(cond_emb)
         y0 = self._state(y0, cond, "y0")
         B, T, _ = cond.shape
+        farr = None
+        if frames is not None:
+            fl = [int(f) for f in frames]
+            if len(fl) != B or any(f < 1 or f > T for f in fl):
+                raise ValueError("frames must hold %d counts in [1, %d], got %s" % (B, T, fl))
+            farr = (ctypes.c_int32 * B)(*fl)
         art = torch.empty(B, T, CFM_DIM_OUT, dtype=torch.float32, device=self.device)
         ws = self._workspace(B, T)
+        tail = (int(steps), ctypes.c_void_p(y0.data_ptr()) if y0 is not None else None, ctypes.c_float(float(pitch_amp)),
+                ctypes.c_void_p(art.data_ptr()), ctypes.c_void_p(ws.data_ptr()),
+                ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream))
         with torch.cuda.device(self.device):
-            _lib.check(self.lib.sylber_cfm_sample(self.handle, ctypes.c_void_p(cond.data_ptr()), B, T, int(steps),
-                                                  ctypes.c_void_p(y0.data_ptr()) if y0 is not None else None,
-                                                  ctypes.c_float(float(pitch_amp)), ctypes.c_void_p(art.data_ptr()),
-                                                  ctypes.c_void_p(ws.data_ptr()),
-                                                  ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)),
-                       "sylber_cfm_sample")
+            if farr is None:
+                _lib.check(self.lib.sylber_cfm_sample(self.handle, ctypes.c_void_p(cond.data_ptr()), B, T, *tail), "sylber_cfm_sample")
+            else:
+                _lib.check(self.lib.sylber_cfm_sample_frames(self.handle, ctypes.c_void_p(cond.data_ptr()), farr, B, T, *tail),
+                           "sylber_cfm_sample_frames")
         return art
 
     def eval(self, x: torch.Tensor, t: float, cond_emb: torch.Tensor) -> torch.Tensor:
@@ -276,6 +287,10 @@ class SegmentSynthesis:
             raise KeyError("checkpoint is missing the input_model.* tensors")
         self.decoder = CfmDecoder(sd, device=device, precision=precision)     # checks the regressor tensors first (cheapest to fail)
         self.speech_model = HubertEncoderHIP(speech, num_layers=encoding_layer, device=device, precision=precision)
+        # batch-invariant mode (off by default): each row of a padded batch is resynthesized exactly as it is alone
+        self.batch_invariant = bool(kwargs.get("batch_invariant", False))
+        if self.batch_invariant:
+            self.speech_model.set_per_utterance(True)
         self.input_model = SegmentConditioner(mlp, device=device)
         self.device = self.speech_model.device
         self.quantizer = quantizer                     # a KMQuantizer (or None), passed to SegmentConditioner
@@ -293,11 +308,14 @@ class SegmentSynthesis:
         return self._threshold
 
     def resynthesize(self, input_values=None, attention_mask=None, features=None, steps=5, rand_scale=0.0, merge_threshold=0.8,
-                     normthreshold=None, prosody_steps=None, prosody_rand_scale=None, y0=None):
+                     normthreshold=None, prosody_steps=None, prosody_rand_scale=None, y0=None, frames=None):
         """-> ``(art [B, T, 14] fp32 on the device, segments)`` with channel 12 divided by ``pitch_amp``; ``segments`` is a list of
         int64 ``[n, 2]`` arrays (``np.array([])`` for none), or None on the ``features=`` branch.  ``rand_scale > 0`` starts the
         sampler from ``randn_like(cond) * rand_scale`` on the device; ``y0=`` supplies that start explicitly (tests).
-        ``prosody_*`` are accepted and ignored, as upstream."""
+        ``prosody_*`` are accepted and ignored, as upstream.
+        With ``batch_invariant=True``, row b of ``art[:, :T_b]`` (``T_b`` from ``attention_mask``) and its segments are bit-identical
+        to the clip resynthesized alone, and ``art[b, T_b:]`` is 0.  ``frames=`` gives the ``features=`` branch each row's frame count
+        (default: every row ``T`` frames)."""
         dev = self.device
         if features is None:
             if input_values is None:
@@ -308,9 +326,11 @@ class SegmentSynthesis:
             x = x.contiguous()
             lengths = None if attention_mask is None else [int(v) for v in torch.as_tensor(attention_mask).sum(-1).tolist()]
             hidden = self.speech_model.forward(x, lengths)
+            frames = (self.speech_model.frame_counts(lengths if lengths is not None else [x.shape[1]] * x.shape[0])
+                      if self.batch_invariant else None)
             if normthreshold is None:
                 normthreshold = self.get_threshold()
-            seg, nseg, feats = self.speech_model.segment(hidden, normthreshold, merge_threshold)
+            seg, nseg, feats = self.speech_model.segment(hidden, normthreshold, merge_threshold, frames=frames)
             cond, _ = self.input_model(hidden, seg, nseg, feats, normthreshold, quantizer=self.quantizer)
             nseg_h = nseg.cpu().numpy()
             nmax = max(int(nseg_h.max()), 1)
@@ -324,5 +344,5 @@ class SegmentSynthesis:
             segments = None
         if y0 is None and rand_scale:
             y0 = torch.randn(cond.shape[0], cond.shape[1], CFM_DIM_OUT, device=dev) * rand_scale
-        art = self.decoder.sample(cond, steps=steps, y0=y0, pitch_amp=self.pitch_amp)
+        art = self.decoder.sample(cond, steps=steps, y0=y0, pitch_amp=self.pitch_amp, frames=frames)
         return art, segments
