@@ -153,6 +153,16 @@ int sylber_km_assign(const float* feats_dev, int32_t n, const float* centroids_d
 /* KMQuantizer.decode (quantizer.py:127-133): out[r] = centroids[clip(idx[r], 0)] */
 int sylber_km_decode(const int32_t* idx_dev, int32_t n, const float* centroids_dev, int32_t K, int32_t D, float* out_dev, void* stream);
 
+/* ResidualKMQuantizer.get_indices (quantizer.py:137-160): stage 1 = sylber_km_assign(c1, normalize 0) into idx_dev[r][0], then
+ * r = x - c1[max(idx1, 0)] (one fp32 subtract per element, token - z_q) assigned against c2 into idx_dev[r][1].
+ *   idx_dev [n, 2] int32; workspace_dev: sylber_km_residual_workspace_floats(n, K1, K2, D) floats */
+int64_t sylber_km_residual_workspace_floats(int32_t n, int32_t K1, int32_t K2, int32_t D);
+int sylber_km_assign_residual(const float* feats_dev, int32_t n, const float* c1_dev, int32_t K1, const float* c2_dev, int32_t K2,
+                              int32_t D, int32_t* idx_dev, float* workspace_dev, void* stream);
+/* ResidualKMQuantizer.decode (quantizer.py:174-178): out[r] = c1[max(idx[r][0], 0)] + c2[max(idx[r][1], 0)] (z_q1 + z_q2) */
+int sylber_km_decode_residual(const int32_t* idx_dev, int32_t n, const float* c1_dev, int32_t K1, const float* c2_dev, int32_t K2,
+                              int32_t D, float* out_dev, void* stream);
+
 /* N3: front half of SegmentSynthesis.resynthesize (sylber/model/segment_synthesis.py:103-140): segment means broadcast
  * back to their frames -> `MLP` conditioner (Linear -> RFF -> ... -> Linear, segment_synthesis.py:17-53) -> frames with
  * hidden-state norm < norm_thr zeroed.  HOST pointers to fp32 tensors in nn.Linear / nn.LayerNorm layout. */
@@ -176,6 +186,27 @@ int64_t sylber_condition_workspace_floats(sylber_mlp_t m, int32_t B, int32_t S);
 int sylber_condition(sylber_mlp_t m, const float* hidden_dev, const int64_t* seg_dev, const int32_t* nseg_dev, const float* feat_dev,
                      int32_t B, int32_t T, int32_t S, float norm_thr, float* avg_hidden_dev, float* cond_dev, float* workspace_dev,
                      void* stream);
+
+/* syllable units -> conditioning input: the fused form of
+ *   sylber_condition_features(expand_feature(decode(units), durations))   (flowmatching.py:873-882, segment_synthesis.py:135-140)
+ * with the MLP run once per unit instead of once per frame; the result is bitwise the same.
+ *   c1_dev [K1, input_dim], c2_dev [K2, input_dim] or NULL (one codebook); units_dev [B, S, ncb] int32 (ncb = 2 with c2, else 1),
+ *   ids in [-1, K) (-1 reads as 0, KMQuantizer.decode's clip); spans_dev [B, S, 2] int32: unit j of row b covers frames
+ *   [start, end), 0 <= start < end <= T, start >= the previous unit's end; nunits_dev [B] in [0, S]; frames_dev [B] in [1, T] or
+ *   NULL (every row T frames).  cond_dev [B, T, output_dim]: frame t of row b takes the MLP row of the unit whose span holds it,
+ *   0 where none does, where t >= frames[b], or where the unit's decoded row has sqrt(sum x^2) < 1e-4.
+ *   All device pointers.  The tables are checked on the device before anything else runs (the call synchronises `stream` once);
+ *   a bad entry returns an error naming the call.  workspace_dev: sylber_condition_units_workspace_floats(m, B, S) floats */
+int64_t sylber_condition_units_workspace_floats(sylber_mlp_t m, int32_t B, int32_t S);
+int sylber_condition_units(sylber_mlp_t m, const float* c1_dev, int32_t K1, const float* c2_dev, int32_t K2, const int32_t* units_dev,
+                           const int32_t* spans_dev, const int32_t* nunits_dev, const int32_t* frames_dev, int32_t B, int32_t T, int32_t S,
+                           float* cond_dev, float* workspace_dev, void* stream);
+/* expand_feature(avg_fts, durations) (flowmatching.py:873-882) on the device: row b of out_dev [B, T, D] is feats_dev[b, 0] repeated
+ * durations[b, 0, 0] times, then durations[b, 0, 1] zero rows, then unit 1 ...  durations_dev [B, S, 2] int32 >= 0; every row must
+ * sum to T (upstream's torch.stack refuses ragged rows), else an error.  Synchronises `stream` once (the check);
+ * workspace_dev: B * S + 1 int32 */
+int sylber_expand_units(const float* feats_dev, const int32_t* durations_dev, int32_t B, int32_t S, int32_t D, int32_t T, float* out_dev,
+                        int32_t* workspace_dev, void* stream);
 
 /* ---- per-handle options ------------------------------------------------------------------------ */
 /* Tuning / test overrides, scoped to ONE handle (nothing process-global).  SYLBER_OPT_GEMM_TILE: value < 0 restores the

@@ -2,5 +2,8 @@
 (reference API: sylber/__init__.py:1 exports ``Segmenter``) and of ``SegmentSynthesis.resynthesize``."""
 from .segmenter import Segmenter, HubertEncoderHIP  # noqa: F401
 from .synthesis import SegmentSynthesis  # noqa: F401
+from .downstream import (KMQuantizer, ResidualKMQuantizer, expand_feature, load_km_quantizer,  # noqa: F401
+                         load_residualkm_quantizer)
 
-__all__ = ["Segmenter", "HubertEncoderHIP", "SegmentSynthesis"]
+__all__ = ["Segmenter", "HubertEncoderHIP", "SegmentSynthesis", "KMQuantizer", "ResidualKMQuantizer", "expand_feature",
+           "load_km_quantizer", "load_residualkm_quantizer"]

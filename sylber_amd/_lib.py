@@ -91,12 +91,19 @@ EXPORTS = {
     "sylber_km_workspace_floats": (c_int64, [c_int32, c_int32, c_int32]),
     "sylber_km_assign": (c_int, [c_void_p, c_int32, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
     "sylber_km_decode": (c_int, [c_void_p, c_int32, c_void_p, c_int32, c_int32, c_void_p, c_void_p]),
+    "sylber_km_residual_workspace_floats": (c_int64, [c_int32, c_int32, c_int32, c_int32]),
+    "sylber_km_assign_residual": (c_int, [c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
+    "sylber_km_decode_residual": (c_int, [c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_int32, c_int32, c_void_p, c_void_p]),
     "sylber_mlp_create": (c_int, [POINTER(SylberMlpWeights), c_int, POINTER(c_void_p)]),
     "sylber_mlp_destroy": (None, [c_void_p]),
     "sylber_condition_workspace_floats": (c_int64, [c_void_p, c_int32, c_int32]),
     "sylber_condition": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_float, c_void_p,
                                  c_void_p, c_void_p, c_void_p]),
     "sylber_condition_features": (c_int, [c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p]),
+    "sylber_condition_units_workspace_floats": (c_int64, [c_void_p, c_int32, c_int32]),
+    "sylber_condition_units": (c_int, [c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_int32,
+                                       c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
+    "sylber_expand_units": (c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
     "sylber_cfm_create": (c_int, [POINTER(SylberCfmWeights), c_int, c_int, POINTER(c_void_p)]),
     "sylber_cfm_destroy": (None, [c_void_p]),
     "sylber_cfm_workspace_bytes": (c_int64, [c_void_p, c_int32, c_int32]),

@@ -11,6 +11,7 @@
 #include "kernels.h"
 #include "../../include/sylber_hip.h"
 #include <cstring>
+#include <string>
 #include <vector>
 
 // ---- N4 ---------------------------------------------------------------------------------------------------------
@@ -37,7 +38,7 @@ __global__ __launch_bounds__(256) void km_sqnorm_kernel(const float* __restrict_
 // idx[r] = argmin_c (||c||^2 - 2 x.c)  (the ||x||^2 term and the square root of cdist are monotone / constant per
 // row); ties -> the smallest index, like argmax over -cdist returns the first maximum
 __global__ __launch_bounds__(256) void km_argmin_kernel(const float* __restrict__ dots, long ld, const float* __restrict__ cn,
-                                                        int32_t* __restrict__ idx, int n, int K) {
+                                                        int32_t* __restrict__ idx, int istride, int n, int K) {
     __shared__ float bv[4]; __shared__ int bi[4];
     const int r = blockIdx.x;
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -55,7 +56,7 @@ __global__ __launch_bounds__(256) void km_argmin_kernel(const float* __restrict_
     __syncthreads();
     if (threadIdx.x == 0) {
         for (int w = 1; w < 4; ++w) if (bv[w] < best || (bv[w] == best && bi[w] < besti)) { best = bv[w]; besti = bi[w]; }
-        idx[r] = besti;
+        idx[(size_t)r * istride] = besti;
     }
 }
 
@@ -64,11 +65,9 @@ extern "C" int64_t sylber_km_workspace_floats(int32_t n, int32_t K, int32_t D) {
     return (int64_t)n * ((K + 3) & ~3) + (int64_t)n * D + ((K + 3) & ~3) + 64;
 }
 
-extern "C" int sylber_km_assign(const float* feats_dev, int32_t n, const float* centroids_dev, int32_t K, int32_t D, int32_t normalize,
-                                int32_t* idx_dev, float* workspace_dev, void* stream) {
-    hipStream_t s = (hipStream_t)stream;
-    if (!feats_dev || !centroids_dev || !idx_dev || !workspace_dev) { syl_set_error("sylber_km_assign", "null argument"); return 1; }
-    if (n < 1 || K < 1 || D < 16 || D % 16) { syl_set_error("sylber_km_assign", "need n, K >= 1 and D a multiple of 16"); return 1; }
+// idx_dev[r * istride] = nearest centroid of row r (istride 2: one column of the residual quantizer's [n, 2] table)
+static int km_assign_impl(const char* what, const float* feats_dev, int32_t n, const float* centroids_dev, int32_t K, int32_t D,
+                          int32_t normalize, int32_t* idx_dev, int istride, float* workspace_dev, hipStream_t s) {
     const int Kp = (K + 3) & ~3;
     float* dots = workspace_dev;                         // [n][Kp]
     float* xn = dots + (size_t)n * Kp;                   // [n][D] (normalised copy)
@@ -90,11 +89,18 @@ extern "C" int sylber_km_assign(const float* feats_dev, int32_t n, const float* 
         GemmArgsF32 t = g;
         t.W = centroids_dev + (size_t)(K - 4 < 0 ? 0 : K - 4) * D; t.N = 4; t.out0 = dots + (K - 4 < 0 ? 0 : K - 4);
         if (K >= 4) { if (launch_gemm_f32(t, s)) return 1; }
-        else { syl_set_error("sylber_km_assign", "K < 4 with K % 4 != 0 is not supported"); return 1; }
+        else { syl_set_error(what, "K < 4 with K % 4 != 0 is not supported"); return 1; }
     } else if (launch_gemm_f32(g, s)) return 1;
-    hipLaunchKernelGGL(km_argmin_kernel, dim3(n), dim3(256), 0, s, dots, (long)Kp, cn, idx_dev, n, K);
+    hipLaunchKernelGGL(km_argmin_kernel, dim3(n), dim3(256), 0, s, dots, (long)Kp, cn, idx_dev, istride, n, K);
     HIP_TRY(hipGetLastError());
     return 0;
+}
+
+extern "C" int sylber_km_assign(const float* feats_dev, int32_t n, const float* centroids_dev, int32_t K, int32_t D, int32_t normalize,
+                                int32_t* idx_dev, float* workspace_dev, void* stream) {
+    if (!feats_dev || !centroids_dev || !idx_dev || !workspace_dev) { syl_set_error("sylber_km_assign", "null argument"); return 1; }
+    if (n < 1 || K < 1 || D < 16 || D % 16) { syl_set_error("sylber_km_assign", "need n, K >= 1 and D a multiple of 16"); return 1; }
+    return km_assign_impl("sylber_km_assign", feats_dev, n, centroids_dev, K, D, normalize, idx_dev, 1, workspace_dev, (hipStream_t)stream);
 }
 
 // KMQuantizer.decode (quantizer.py:127-133): rows of the codebook; negative indices are clipped to 0
@@ -107,6 +113,54 @@ __global__ __launch_bounds__(256) void km_decode_kernel(const int32_t* __restric
 extern "C" int sylber_km_decode(const int32_t* idx_dev, int32_t n, const float* centroids_dev, int32_t K, int32_t D, float* out_dev, void* stream) {
     if (!idx_dev || !centroids_dev || !out_dev || n < 1 || K < 1 || D < 1) { syl_set_error("sylber_km_decode", "bad argument"); return 1; }
     hipLaunchKernelGGL(km_decode_kernel, dim3(n), dim3(256), 0, (hipStream_t)stream, idx_dev, centroids_dev, out_dev, n, K, D);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// ResidualKMQuantizer (quantizer.py:137-180): stage 1 is KMQuantizer(centroids).get_indices (never normalised: upstream
+// builds both stages without `normalize`), stage 2 assigns token - decode(stage 1) against the second codebook
+// r = x - c1[max(idx1, 0)]: one fp32 subtract per element (token - z_q); idx1 is column 0 of the [n, 2] table
+__global__ __launch_bounds__(256) void km_residual_kernel(const float* __restrict__ x, const int32_t* __restrict__ idx, const float* __restrict__ c,
+                                                          float* __restrict__ r, int n, int K, int D) {
+    const int row = blockIdx.x;
+    int i = idx[(size_t)row * 2]; i = i < 0 ? 0 : (i >= K ? K - 1 : i);
+    for (int j = threadIdx.x; j < D; j += 256) r[(size_t)row * D + j] = x[(size_t)row * D + j] - c[(size_t)i * D + j];
+}
+
+extern "C" int64_t sylber_km_residual_workspace_floats(int32_t n, int32_t K1, int32_t K2, int32_t D) {
+    if (n < 1 || K1 < 1 || K2 < 1 || D < 1) return -1;
+    return sylber_km_workspace_floats(n, K1 > K2 ? K1 : K2, D) + (int64_t)n * D + 64;
+}
+
+extern "C" int sylber_km_assign_residual(const float* feats_dev, int32_t n, const float* c1_dev, int32_t K1, const float* c2_dev, int32_t K2,
+                                         int32_t D, int32_t* idx_dev, float* workspace_dev, void* stream) {
+    static const char* what = "sylber_km_assign_residual";
+    hipStream_t s = (hipStream_t)stream;
+    if (!feats_dev || !c1_dev || !c2_dev || !idx_dev || !workspace_dev) { syl_set_error(what, "null argument"); return 1; }
+    if (n < 1 || K1 < 1 || K2 < 1 || D < 16 || D % 16) { syl_set_error(what, "need n, K1, K2 >= 1 and D a multiple of 16"); return 1; }
+    float* ws = workspace_dev;                                            // sylber_km_workspace_floats(n, max K, D): shared by both stages
+    float* r = ws + (sylber_km_workspace_floats(n, K1 > K2 ? K1 : K2, D) + 63) / 64 * 64;   // [n][D] residual
+    if (km_assign_impl(what, feats_dev, n, c1_dev, K1, D, 0, idx_dev, 2, ws, s)) return 1;
+    hipLaunchKernelGGL(km_residual_kernel, dim3(n), dim3(256), 0, s, feats_dev, idx_dev, c1_dev, r, n, K1, D);
+    HIP_TRY(hipGetLastError());
+    return km_assign_impl(what, r, n, c2_dev, K2, D, 0, idx_dev + 1, 2, ws, s);
+}
+
+// ResidualKMQuantizer.decode (quantizer.py:174-178): z_q1 + z_q2 = c1[max(i1, 0)] + c2[max(i2, 0)], added in that order
+__global__ __launch_bounds__(256) void km_decode_residual_kernel(const int32_t* __restrict__ idx, const float* __restrict__ c1, int K1,
+                                                                 const float* __restrict__ c2, int K2, float* __restrict__ out, int n, int D) {
+    const int r = blockIdx.x;
+    int i1 = idx[(size_t)r * 2], i2 = idx[(size_t)r * 2 + 1];
+    i1 = i1 < 0 ? 0 : (i1 >= K1 ? K1 - 1 : i1);
+    i2 = i2 < 0 ? 0 : (i2 >= K2 ? K2 - 1 : i2);
+    for (int j = threadIdx.x; j < D; j += 256) out[(size_t)r * D + j] = c1[(size_t)i1 * D + j] + c2[(size_t)i2 * D + j];
+}
+extern "C" int sylber_km_decode_residual(const int32_t* idx_dev, int32_t n, const float* c1_dev, int32_t K1, const float* c2_dev, int32_t K2,
+                                         int32_t D, float* out_dev, void* stream) {
+    if (!idx_dev || !c1_dev || !c2_dev || !out_dev || n < 1 || K1 < 1 || K2 < 1 || D < 1) {
+        syl_set_error("sylber_km_decode_residual", "bad argument"); return 1;
+    }
+    hipLaunchKernelGGL(km_decode_residual_kernel, dim3(n), dim3(256), 0, (hipStream_t)stream, idx_dev, c1_dev, K1, c2_dev, K2, out_dev, n, D);
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -297,6 +351,190 @@ extern "C" int sylber_condition_features(sylber_mlp_t m, const float* features_d
     if (run_mlp(m, features_dev, R, ha, hb, hc, yo, s)) return 1;
     hipLaunchKernelGGL(cond_mask_rows_kernel, dim3((unsigned)(((long)R + 3) / 4)), dim3(256), 0, s, features_dev, yo, (long)R, m->input_dim,
                        m->output_dim, cond_dev);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// ---- syllable units -> conditioning (the unit half of the speech <-> units loop) --------------------------------------
+// Upstream turns units back into frames with expand_feature(avg_fts, durations) (flowmatching.py:873-882) and feeds the
+// result to resynthesize(features=...) (segment_synthesis.py:135-140), which runs the MLP on every frame.  All frames of a
+// unit carry the same row, so sylber_condition_units runs the MLP once per unit (B*S + 1 rows) and expands afterwards.
+// Every MLP row is computed as in a B*T-row launch (launch_gemm_f32 picks no tile by M, the LayerNorm is row-local) and the
+// silence decision uses cond_mask_rows_kernel's arithmetic on the same decoded row, so `cond` is bitwise the features path's.
+
+enum { UNITS_BAD_COUNT = 1, UNITS_BAD_FRAMES = 2, UNITS_BAD_ID = 4, UNITS_BAD_SPAN = 8, UNITS_BAD_DURATION = 16, UNITS_BAD_SUM = 32 };
+
+static int units_report(const char* what, const int32_t* flag_dev, hipStream_t s) {
+    int32_t flag = 0;
+    HIP_TRY(hipMemcpyAsync(&flag, flag_dev, sizeof(flag), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (!flag) return 0;
+    std::string msg;
+    if (flag & UNITS_BAD_COUNT) msg += "unit counts must be in [0, S]; ";
+    if (flag & UNITS_BAD_FRAMES) msg += "frame counts must be in [1, T]; ";
+    if (flag & UNITS_BAD_ID) msg += "unit ids must be in [-1, K) of their codebook; ";
+    if (flag & UNITS_BAD_SPAN) msg += "spans must satisfy 0 <= start < end <= T and start >= the previous unit's end; ";
+    if (flag & UNITS_BAD_DURATION) msg += "durations must be >= 0; ";
+    if (flag & UNITS_BAD_SUM) msg += "every row's durations must sum to T (upstream's torch.stack refuses ragged rows); ";
+    msg.resize(msg.size() - 2);
+    syl_set_error(what, msg.c_str());
+    return 1;
+}
+
+// one block (64 lanes) per utterance: every table entry a later kernel reads is checked here first
+__global__ __launch_bounds__(64) void units_check_kernel(const int32_t* __restrict__ units, int ncb, int K1, int K2,
+                                                         const int32_t* __restrict__ spans, const int32_t* __restrict__ nunits,
+                                                         const int32_t* __restrict__ frames, int T, int S, int32_t* __restrict__ flag) {
+    const int b = blockIdx.x;
+    int bad = 0;
+    const int n = nunits[b];
+    if (n < 0 || n > S) bad |= UNITS_BAD_COUNT;
+    if (frames && (frames[b] < 1 || frames[b] > T)) bad |= UNITS_BAD_FRAMES;
+    const int nn = n < 0 ? 0 : (n > S ? S : n);
+    for (int j = threadIdx.x; j < nn; j += 64) {
+        const size_t u = (size_t)b * S + j;
+        const int i1 = units[u * ncb];
+        if (i1 < -1 || i1 >= K1) bad |= UNITS_BAD_ID;
+        if (ncb > 1) { const int i2 = units[u * ncb + 1]; if (i2 < -1 || i2 >= K2) bad |= UNITS_BAD_ID; }
+        const int s0 = spans[u * 2], s1 = spans[u * 2 + 1];
+        if (s0 < 0 || s1 <= s0 || s1 > T) bad |= UNITS_BAD_SPAN;
+        if (j > 0 && s0 < spans[(u - 1) * 2 + 1]) bad |= UNITS_BAD_SPAN;
+    }
+    if (bad) atomicOr(flag, bad);
+}
+
+// one wave per row: row (b, j < nunits[b]) = c1[i1] (+ c2[i2]) with ids < 0 read as 0 (KMQuantizer.decode's clip), other
+// rows and the trailing row B*S zero; keep[r] = !(sqrt(sum x^2) < 1e-4) in cond_mask_rows_kernel's order of operations
+__global__ __launch_bounds__(256) void units_gather_kernel(const int32_t* __restrict__ units, int ncb, const float* __restrict__ c1, int K1,
+                                                           const float* __restrict__ c2, int K2, const int32_t* __restrict__ nunits,
+                                                           int B, int S, int D, float* __restrict__ rows, int32_t* __restrict__ keep) {
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int r = blockIdx.x * 4 + wave;
+    if (r > B * S) return;
+    const bool real = r < B * S;
+    const int b = real ? r / S : 0, j = real ? r - b * S : 0;
+    const bool ok = real && j < nunits[b];
+    int i1 = ok ? units[(size_t)r * ncb] : 0, i2 = ok && c2 ? units[(size_t)r * ncb + 1] : 0;
+    i1 = i1 < 0 ? 0 : (i1 >= K1 ? K1 - 1 : i1);
+    i2 = i2 < 0 ? 0 : (i2 >= K2 ? K2 - 1 : i2);
+    float s = 0.f;
+    for (int c = lane; c < D; c += 64) {
+        float v = 0.f;
+        if (ok) v = c2 ? c1[(size_t)i1 * D + c] + c2[(size_t)i2 * D + c] : c1[(size_t)i1 * D + c];
+        rows[(size_t)r * D + c] = v;
+        s = fmaf(v, v, s);
+    }
+    s = wave_sum(s);
+    if (lane == 0) keep[r] = ok && !(sqrtf(s) < 1e-4f);
+}
+
+// one wave per frame: the MLP row of the LAST unit whose span holds the frame; 0 where no span does, past frames[b], or
+// where the unit's decoded row is silent
+__global__ __launch_bounds__(256) void units_expand_cond_kernel(const int32_t* __restrict__ spans, const int32_t* __restrict__ nunits,
+                                                                const int32_t* __restrict__ frames, const int32_t* __restrict__ keep,
+                                                                const float* __restrict__ mlp_rows, int B, int T, int S, int OD,
+                                                                float* __restrict__ cond_out) {
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const long f = (long)blockIdx.x * 4 + wave;
+    if (f >= (long)B * T) return;
+    const int b = (int)(f / T), t = (int)(f - (long)b * T);
+    int n = nunits[b]; n = n < 0 ? 0 : (n > S ? S : n);
+    int j = -1;
+    for (int q = lane; q < n; q += 64) {
+        const int s0 = spans[((size_t)b * S + q) * 2], s1 = spans[((size_t)b * S + q) * 2 + 1];
+        if (t >= s0 && t < s1) j = q;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { const int oj = __shfl_xor(j, o, 64); j = oj > j ? oj : j; }
+    const bool live = j >= 0 && (!frames || t < frames[b]) && keep[b * S + (j >= 0 ? j : 0)];
+    const float* src = mlp_rows + (size_t)(b * S + (j >= 0 ? j : 0)) * OD;
+    for (int c = lane; c < OD; c += 64) cond_out[(size_t)f * OD + c] = live ? src[c] : 0.f;
+}
+
+extern "C" int64_t sylber_condition_units_workspace_floats(sylber_mlp_t m, int32_t B, int32_t S) {
+    const int64_t base = sylber_condition_workspace_floats(m, B, S);
+    if (base < 0) return -1;
+    return base + (int64_t)B * S + 1 + 64;
+}
+
+extern "C" int sylber_condition_units(sylber_mlp_t m, const float* c1_dev, int32_t K1, const float* c2_dev, int32_t K2, const int32_t* units_dev,
+                                      const int32_t* spans_dev, const int32_t* nunits_dev, const int32_t* frames_dev, int32_t B, int32_t T,
+                                      int32_t S, float* cond_dev, float* workspace_dev, void* stream) {
+    static const char* what = "sylber_condition_units";
+    hipStream_t s = (hipStream_t)stream;
+    if (!m || !c1_dev || !units_dev || !spans_dev || !nunits_dev || !cond_dev || !workspace_dev) { syl_set_error(what, "null argument"); return 1; }
+    if (B < 1 || T < 1 || S < 1 || K1 < 1 || (c2_dev && K2 < 1)) { syl_set_error(what, "need B, T, S, K1 >= 1 (and K2 >= 1 with a second codebook)"); return 1; }
+    DevGuard dg(m->device);
+    const int D = m->input_dim, R = B * S + 1, MD = mlp_maxdim(m), ncb = c2_dev ? 2 : 1;
+    float* x0 = workspace_dev;
+    float* ha = x0 + (size_t)R * D; float* hb = ha + (size_t)R * MD; float* hc = hb + (size_t)R * MD;
+    float* yo = hc + (size_t)R * MD;
+    int32_t* keep = (int32_t*)(yo + (size_t)R * m->output_dim);
+    int32_t* flag = keep + R;
+    HIP_TRY(hipMemsetAsync(flag, 0, sizeof(int32_t), s));
+    hipLaunchKernelGGL(units_check_kernel, dim3(B), dim3(64), 0, s, units_dev, ncb, K1, K2, spans_dev, nunits_dev, frames_dev, T, S, flag);
+    HIP_TRY(hipGetLastError());
+    if (units_report(what, flag, s)) return 1;
+    hipLaunchKernelGGL(units_gather_kernel, dim3((R + 3) / 4), dim3(256), 0, s, units_dev, ncb, c1_dev, K1, c2_dev, K2, nunits_dev, B, S, D,
+                       x0, keep);
+    HIP_TRY(hipGetLastError());
+    if (run_mlp(m, x0, R, ha, hb, hc, yo, s)) return 1;
+    const long frames = (long)B * T;
+    hipLaunchKernelGGL(units_expand_cond_kernel, dim3((unsigned)((frames + 3) / 4)), dim3(256), 0, s, spans_dev, nunits_dev, frames_dev, keep, yo,
+                       B, T, S, m->output_dim, cond_dev);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// expand_feature (flowmatching.py:873-882): row b is [feat_0]*d00 + [0]*d01 + [feat_1]*d10 + [0]*d11 + ...; starts[b*S + j]
+// = the first frame of unit j, and every row must sum to T (upstream's torch.stack of the per-row results)
+__global__ __launch_bounds__(64) void expand_check_kernel(const int32_t* __restrict__ dur, int S, int T, int32_t* __restrict__ starts,
+                                                          int32_t* __restrict__ flag) {
+    if (threadIdx.x) return;
+    const int b = blockIdx.x;
+    long cum = 0;
+    int bad = 0;
+    for (int j = 0; j < S; ++j) {
+        const int d0 = dur[((size_t)b * S + j) * 2], d1 = dur[((size_t)b * S + j) * 2 + 1];
+        if (d0 < 0 || d1 < 0) bad |= UNITS_BAD_DURATION;
+        starts[(size_t)b * S + j] = (int32_t)(cum < 0 ? 0 : (cum > T ? T : cum));
+        cum += (long)(d0 > 0 ? d0 : 0) + (d1 > 0 ? d1 : 0);
+    }
+    if (cum != T) bad |= UNITS_BAD_SUM;
+    if (bad) atomicOr(flag, bad);
+}
+__global__ __launch_bounds__(256) void expand_units_kernel(const float* __restrict__ feats, const int32_t* __restrict__ dur,
+                                                           const int32_t* __restrict__ starts, int B, int S, int D, int T, float* __restrict__ out) {
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const long f = (long)blockIdx.x * 4 + wave;
+    if (f >= (long)B * T) return;
+    const int b = (int)(f / T), t = (int)(f - (long)b * T);
+    int j = -1;
+    for (int q = lane; q < S; q += 64) {
+        const int s0 = starts[(size_t)b * S + q];
+        if (t >= s0 && t < s0 + dur[((size_t)b * S + q) * 2]) j = q;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { const int oj = __shfl_xor(j, o, 64); j = oj > j ? oj : j; }
+    const float* src = feats + ((size_t)b * S + (j >= 0 ? j : 0)) * D;
+    for (int c = lane; c < D; c += 64) out[(size_t)f * D + c] = j >= 0 ? src[c] : 0.f;
+}
+
+extern "C" int sylber_expand_units(const float* feats_dev, const int32_t* durations_dev, int32_t B, int32_t S, int32_t D, int32_t T,
+                                   float* out_dev, int32_t* workspace_dev, void* stream) {
+    static const char* what = "sylber_expand_units";
+    hipStream_t s = (hipStream_t)stream;
+    if (!feats_dev || !durations_dev || !out_dev || !workspace_dev) { syl_set_error(what, "null argument"); return 1; }
+    if (B < 1 || S < 1 || D < 1 || T < 1) { syl_set_error(what, "need B, S, D, T >= 1"); return 1; }
+    int32_t* starts = workspace_dev;
+    int32_t* flag = starts + (size_t)B * S;
+    HIP_TRY(hipMemsetAsync(flag, 0, sizeof(int32_t), s));
+    hipLaunchKernelGGL(expand_check_kernel, dim3(B), dim3(64), 0, s, durations_dev, S, T, starts, flag);
+    HIP_TRY(hipGetLastError());
+    if (units_report(what, flag, s)) return 1;
+    const long frames = (long)B * T;
+    hipLaunchKernelGGL(expand_units_kernel, dim3((unsigned)((frames + 3) / 4)), dim3(256), 0, s, feats_dev, durations_dev, starts, B, S, D, T,
+                       out_dev);
     HIP_TRY(hipGetLastError());
     return 0;
 }

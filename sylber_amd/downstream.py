@@ -2,6 +2,8 @@
 device-resident outputs of ``HubertEncoderHIP.segment`` through the C-ABI (csrc/downstream.hip):
 
 * ``KMQuantizer`` — sylber/model/quantizer.py:86-135: ``get_indices`` (nearest centroid) and ``decode``;
+* ``ResidualKMQuantizer`` — quantizer.py:137-180: two-stage k-means, ``indices [..., 2]``, ``decode`` = ``z_q1 + z_q2``;
+* ``expand_feature`` — sylber/model/flowmatching.py:873-882: unit features laid out over frames by ``durations``;
 * ``SegmentConditioner`` — the front half of ``SegmentSynthesis.resynthesize`` (sylber/model/segment_synthesis.py:
   103-140): segment means broadcast back to frames -> ``MLP`` conditioner -> silence mask."""
 from __future__ import annotations
@@ -70,6 +72,104 @@ class KMQuantizer:
         return {"indices": idx, "quantize": self.decode(idx), "non_quantized": token}
 
 
+class ResidualKMQuantizer:
+    """``ResidualKMQuantizer(centroids, centroids2, normalize=False)`` (quantizer.py:137-180): stage 1 assigns the token against
+    ``centroids``, stage 2 assigns ``token - decode(stage 1)`` against ``centroids2``; ``indices`` are ``[..., 2]`` and ``decode``
+    returns ``z_q1 + z_q2``.  ``normalize`` is accepted and ignored, as upstream (whose constructor builds both stages as
+    ``KMQuantizer(c)`` without it).  ``centroids`` / ``centroids2``: ``.npy`` paths or arrays / tensors ``[K, 768]``."""
+
+    def __init__(self, centroids, centroids2, normalize: bool = False, device="cuda"):
+        self.km = KMQuantizer(centroids, device=device)
+        self.km2 = KMQuantizer(centroids2, device=device)
+        if self.km.centroids.shape[1] != self.km2.centroids.shape[1]:
+            raise ValueError("the two codebooks must have the same width")
+        self.lib, self.device = self.km.lib, self.km.device
+        self.normalize = normalize
+
+    @property
+    def codebooks(self):
+        return (self.km.centroids, self.km2.centroids)
+
+    def get_indices(self, token: torch.Tensor) -> torch.Tensor:
+        """token ``[..., D]`` -> int64 indices ``[..., 2]`` (stage-1 id, stage-2 id of the residual)"""
+        lead = tuple(token.shape[:-1])
+        x = token.reshape(-1, token.shape[-1]).to(self.device, torch.float32).contiguous()
+        n, D = x.shape
+        (c1, c2), K1, K2 = self.codebooks, self.km.centroids.shape[0], self.km2.centroids.shape[0]
+        idx = torch.empty(n, 2, dtype=torch.int32, device=self.device)
+        ws = torch.empty(int(self.lib.sylber_km_residual_workspace_floats(n, K1, K2, D)), dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.sylber_km_assign_residual(_vp(x), n, _vp(c1), K1, _vp(c2), K2, D, _vp(idx), _vp(ws), _stream(self.device)),
+                       "sylber_km_assign_residual")
+        return idx.to(torch.int64).reshape(lead + (2,))
+
+    def decode(self, indices: torch.Tensor) -> torch.Tensor:
+        """indices ``[..., 2]`` -> ``c1[i1] + c2[i2]`` ``[..., D]`` (negative indices clipped to 0)"""
+        if indices.shape[-1] != 2:
+            raise ValueError("ResidualKMQuantizer.decode takes indices [..., 2], got %s" % (tuple(indices.shape),))
+        lead = tuple(indices.shape[:-1])
+        flat = indices.reshape(-1, 2).to(self.device, torch.int32).contiguous()
+        (c1, c2), K1, K2 = self.codebooks, self.km.centroids.shape[0], self.km2.centroids.shape[0]
+        D = c1.shape[1]
+        out = torch.empty(flat.shape[0], D, dtype=torch.float32, device=self.device)
+        if flat.shape[0]:
+            with torch.cuda.device(self.device):
+                _lib.check(self.lib.sylber_km_decode_residual(_vp(flat), flat.shape[0], _vp(c1), K1, _vp(c2), K2, D, _vp(out),
+                                                              _stream(self.device)), "sylber_km_decode_residual")
+        return out.reshape(lead + (D,))
+
+    def __call__(self, token: torch.Tensor) -> Dict[str, torch.Tensor]:
+        idx = self.get_indices(token)
+        return {"indices": idx, "quantize": self.decode(idx), "non_quantized": token}
+
+
+def load_km_quantizer(centroids, normalize: bool = False, device="cuda") -> KMQuantizer:
+    """quantizer.py:79-80"""
+    return KMQuantizer(centroids, normalize=normalize, device=device)
+
+
+def load_residualkm_quantizer(centroids, centroids2, normalize: bool = False, device="cuda") -> ResidualKMQuantizer:
+    """quantizer.py:82-83 (``normalize`` is ignored there too)"""
+    return ResidualKMQuantizer(centroids, centroids2, normalize=normalize, device=device)
+
+
+def quantizer_codebooks(quantizer) -> Sequence[torch.Tensor]:
+    """the codebooks whose rows ``quantizer.decode`` sums: one for a ``KMQuantizer``, two for a ``ResidualKMQuantizer``"""
+    books = getattr(quantizer, "codebooks", None)
+    if books is None:
+        books = (quantizer.centroids,)
+    return tuple(books)
+
+
+def expand_feature(avg_fts: torch.Tensor, durations) -> torch.Tensor:
+    """``expand_feature(avg_fts, durations)`` (flowmatching.py:873-882) on the device: ``avg_fts [B, S, D]``, ``durations
+    [B, S, 2]`` = (frames of the unit, zero frames after it) -> ``[B, T, D]``, every row laid out as
+    ``[feat_0] * d00 + [0] * d01 + [feat_1] * d10 + ...``.  Rows whose durations do not sum to the same T raise ValueError
+    (upstream's ``torch.stack`` refuses them too)."""
+    lib = _lib.load()
+    x = torch.as_tensor(avg_fts)
+    dev = x.device if x.is_cuda else torch.device("cuda:%d" % torch.cuda.current_device())
+    x = x.to(dev, torch.float32).contiguous()
+    d = torch.as_tensor(durations)
+    if x.dim() != 3 or tuple(d.shape) != (x.shape[0], x.shape[1], 2):
+        raise ValueError("expand_feature takes avg_fts [B, S, D] and durations [B, S, 2], got %s and %s"
+                         % (tuple(x.shape), tuple(d.shape)))
+    dh = d.detach().to("cpu", torch.int64)
+    if (dh < 0).any():
+        raise ValueError("durations must be >= 0")
+    sums = dh.sum(dim=(1, 2)).tolist()
+    if len(set(sums)) != 1 or sums[0] < 1:
+        raise ValueError("every row's durations must sum to the same T >= 1, got %s" % sums)
+    B, S, D = x.shape
+    T = int(sums[0])
+    out = torch.empty(B, T, D, dtype=torch.float32, device=dev)
+    dd = dh.to(torch.int32).to(dev).contiguous()
+    ws = torch.empty(B * S + 1, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib.sylber_expand_units(_vp(x), _vp(dd), B, S, D, T, _vp(out), _vp(ws), _stream(dev)), "sylber_expand_units")
+    return out
+
+
 class SegmentConditioner:
     """``MLP(input_dim, output_dim, hidden_dims)`` of segment_synthesis.py:35-53 + the frame broadcast / silence mask
     of ``resynthesize``.  ``state_dict`` uses the keys of the reference module (``mlp.0.weight`` ...; an
@@ -113,12 +213,12 @@ class SegmentConditioner:
             self.handle = None
 
     def __call__(self, hidden: torch.Tensor, seg: torch.Tensor, nseg: torch.Tensor, feats: torch.Tensor, normthreshold: float,
-                 max_segments: Optional[int] = None, quantizer: Optional["KMQuantizer"] = None):
+                 max_segments: Optional[int] = None, quantizer=None):
         """hidden ``[B,T,768]``, (seg, nseg, feats) as returned by ``HubertEncoderHIP.segment`` -> ``(input [B,T,out],
         averaged_target_hidden_states [B,T,768])`` — the tensors named so at segment_synthesis.py:115,138-139.
         ``quantizer``: the optional substitution inside the averaging loop (segment_synthesis.py:121-125): every segment
         mean is replaced by its nearest codebook entry (``get_indices`` -> ``get_output_from_indices``) before it is
-        broadcast to its frames and fed to the MLP."""
+        broadcast to its frames and fed to the MLP; a ``KMQuantizer`` or a ``ResidualKMQuantizer`` (the sum of both codebooks)."""
         B, T, D = hidden.shape
         if D != self.input_dim:
             raise ValueError("hidden dim %d != MLP input dim %d" % (D, self.input_dim))
@@ -155,3 +255,34 @@ class SegmentConditioner:
             _lib.check(self.lib.sylber_condition_features(self.handle, _vp(x), rows, _vp(cond), _vp(ws), _stream(self.device)),
                        "sylber_condition_features")
         return cond.reshape(lead + (self.output_dim,))
+
+    def from_units(self, codebooks: Sequence[torch.Tensor], units: torch.Tensor, spans: torch.Tensor, nunits: torch.Tensor, T: int,
+                   frames: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """``sylber_condition_units``: the conditioning input of syllable units -> ``[B, T, out]``, bitwise
+        ``from_features(expand_feature(decode(units), durations))``.  ``codebooks``: one or two ``[K, 768]`` fp32 device tensors
+        (decode sums them); ``units [B, S, len(codebooks)]``, ``spans [B, S, 2]`` (frames [start, end) of each unit), ``nunits [B]``,
+        ``frames [B]`` (optional): int32 device tensors.  Bad ids, spans or counts raise ``SylberHipError``."""
+        if not 1 <= len(codebooks) <= 2:
+            raise ValueError("one or two codebooks")
+        c1 = codebooks[0]
+        c2 = codebooks[1] if len(codebooks) > 1 else None
+        i32 = lambda t: torch.as_tensor(t).to(self.device, torch.int32).contiguous()   # noqa: E731
+        units, spans, nunits = i32(units), i32(spans), i32(nunits)
+        frames = i32(frames) if frames is not None else None
+        if units.dim() != 3:
+            raise ValueError("units must be [B, S, ncb]")
+        B, S, ncb = units.shape
+        if ncb != len(codebooks) or tuple(spans.shape) != (B, S, 2) or tuple(nunits.shape) != (B,):
+            raise ValueError("units [B, S, %d], spans [B, S, 2] and nunits [B] expected, got %s, %s, %s"
+                             % (len(codebooks), tuple(units.shape), tuple(spans.shape), tuple(nunits.shape)))
+        for c in codebooks:
+            if c.dim() != 2 or c.shape[1] != self.input_dim:
+                raise ValueError("codebooks must be [K, %d]" % self.input_dim)
+        cond = torch.empty(B, int(T), self.output_dim, dtype=torch.float32, device=self.device)
+        ws = torch.empty(int(self.lib.sylber_condition_units_workspace_floats(self.handle, B, S)), dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.sylber_condition_units(self.handle, _vp(c1), c1.shape[0], _vp(c2) if c2 is not None else None,
+                                                       c2.shape[0] if c2 is not None else 0, _vp(units), _vp(spans), _vp(nunits),
+                                                       _vp(frames) if frames is not None else None, B, int(T), S, _vp(cond), _vp(ws),
+                                                       _stream(self.device)), "sylber_condition_units")
+        return cond

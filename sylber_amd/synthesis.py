@@ -10,13 +10,13 @@ from __future__ import annotations
 
 import ctypes
 from pathlib import Path
-from typing import Dict, Optional, Sequence
+from typing import Dict, List, Optional, Sequence
 
 import numpy as np
 import torch
 
 from . import _lib
-from .downstream import SegmentConditioner
+from .downstream import KMQuantizer, ResidualKMQuantizer, SegmentConditioner, quantizer_codebooks
 from .segmenter import HubertEncoderHIP
 from .weights import (CFM_CONV_K, CFM_DEPTH, CFM_DIM, CFM_DIM_COND_EMB, CFM_DIM_HEAD, CFM_DIM_IN_PROJ, CFM_DIM_OUT, CFM_FF_INNER,
                       CFM_FF_MULT, CFM_HEADS, CFM_REGISTERS, CFM_TIME_HIDDEN)
@@ -258,7 +258,10 @@ class SegmentSynthesis:
     (sylber/model/segment_synthesis.py:57-146), inference only.  ``model_ckpt``: a path or a state dict with the keys of
     ``SegmentSynthesis.state_dict()`` (``speech_model.*``, ``input_model.mlp.*``, ``regressor.*`` / ``cfm_wrapper.regressor.*``,
     ``thresholder.*``), optionally inside a Lightning ``{"state_dict": {"net.<key>": ...}}`` wrapper.  ``precision``:
-    "bf16" (default), "fp16" or "fp32" (parity mode), for the encoder and the decoder alike."""
+    "bf16" (default), "fp16" or "fp32" (parity mode), for the encoder and the decoder alike.
+    ``quantizer``: None, a ``KMQuantizer`` / ``ResidualKMQuantizer``, or a ``.npy`` codebook path; with a path,
+    ``residual_quantizer`` (a second ``.npy`` path) makes it a ``ResidualKMQuantizer`` and ``normalize_embed`` is the
+    ``KMQuantizer``'s ``normalize`` (what upstream's constructor, segment_synthesis.py:93-99, means to do)."""
 
     def __init__(self, model_ckpt=None, speech_upstream="facebook/hubert-base-ls960", encoding_layer=9, input_configs=None,
                  regressor_configs=None, thresholder_configs=None, pitch_amp=5, quantizer=None, device="cuda", precision="bf16",
@@ -293,7 +296,15 @@ class SegmentSynthesis:
             self.speech_model.set_per_utterance(True)
         self.input_model = SegmentConditioner(mlp, device=device)
         self.device = self.speech_model.device
-        self.quantizer = quantizer                     # a KMQuantizer (or None), passed to SegmentConditioner
+        residual = kwargs.get("residual_quantizer")
+        if isinstance(quantizer, (str, Path)):
+            if residual is not None:
+                quantizer = ResidualKMQuantizer(str(quantizer), str(residual), device=self.device)
+            else:
+                quantizer = KMQuantizer(str(quantizer), normalize=bool(kwargs.get("normalize_embed", False)), device=self.device)
+        elif residual is not None:
+            raise ValueError("residual_quantizer is a codebook path that goes with a quantizer path; pass a ResidualKMQuantizer instead")
+        self.quantizer = quantizer                     # KMQuantizer / ResidualKMQuantizer (or None), passed to SegmentConditioner
         thr = _strip(sd, "thresholder.")
         if "threshold" in thr:
             self._threshold = float(thr["threshold"].reshape(-1)[0])
@@ -346,3 +357,99 @@ class SegmentSynthesis:
             y0 = torch.randn(cond.shape[0], cond.shape[1], CFM_DIM_OUT, device=dev) * rand_scale
         art = self.decoder.sample(cond, steps=steps, y0=y0, pitch_amp=self.pitch_amp, frames=frames)
         return art, segments
+
+    def tokenize(self, input_values, attention_mask=None, merge_threshold=0.8, normthreshold=None) -> List[dict]:
+        """speech -> syllable units: one dict per clip with ``units`` int64 ``[n, ncb]`` (the quantizer's ids of the clip's segment
+        means: ncb = 1 for a ``KMQuantizer``, 2 for a ``ResidualKMQuantizer``), ``segments`` int64 ``[n, 2]`` (the table
+        ``resynthesize`` returns; ``[0, 2]`` for none) and ``frames`` (the clip's own frame count).  Everything up to the ids runs on the
+        device; slots past a clip's segment count are zeroed there.  ``synthesize_units(tokenize(wav))`` is bitwise
+        ``resynthesize(wav)`` with ``batch_invariant=True``.  ``ValueError`` without a quantizer."""
+        if self.quantizer is None:
+            raise ValueError("tokenize needs a quantizer (SegmentSynthesis(quantizer=...))")
+        dev = self.device
+        x = torch.as_tensor(input_values).to(dev, torch.float32)
+        if x.dim() == 1:
+            x = x[None]
+        x = x.contiguous()
+        lengths = None if attention_mask is None else [int(v) for v in torch.as_tensor(attention_mask).sum(-1).tolist()]
+        hidden = self.speech_model.forward(x, lengths)
+        frames = self.speech_model.frame_counts(lengths if lengths is not None else [x.shape[1]] * x.shape[0])
+        if normthreshold is None:
+            normthreshold = self.get_threshold()
+        seg, nseg, feats = self.speech_model.segment(hidden, normthreshold, merge_threshold, frames=frames if self.batch_invariant else None)
+        S = min(max(int(nseg.max().item()), 1), hidden.shape[1])
+        keep = torch.arange(S, device=dev)[None, :] < nseg[:, None].to(torch.int64)
+        head = torch.where(keep[:, :, None], feats[:, :S], torch.zeros((), device=dev)).contiguous()
+        ids = self.quantizer.get_indices(head).cpu().numpy()
+        seg_h = seg[:, :S].cpu().numpy()
+        nseg_h = nseg.cpu().numpy()
+        return [{"units": ids[b, :int(n)].astype(np.int64), "segments": seg_h[b, :int(n)].astype(np.int64).reshape(-1, 2),
+                 "frames": int(frames[b])} for b, n in enumerate(nseg_h)]
+
+    def synthesize_units(self, units, segments=None, frames=None, steps=5, rand_scale=0.0, y0=None, nunits=None) -> torch.Tensor:
+        """syllable units -> ``art [B, T, 14]`` fp32 on the device (channel 12 divided by ``pitch_amp``): each unit's decoded codebook
+        row (the sum of the quantizer's codebooks) conditions the frames of its segment, frames outside every segment and units whose
+        decoded row has norm < 1e-4 get a zero conditioning row, and the decoder samples row b over its own ``frames[b]`` frames
+        (``art[b, frames[b]:]`` is 0, as in batch-invariant mode).  ``T = max(frames)``.
+        Bitwise ``resynthesize(features=expand_feature(decode(units), durations), frames=frames)``, with the conditioning MLP run once
+        per unit instead of once per frame.
+        ``units``: the list ``tokenize`` returns; or a list of per-clip int arrays ``[n_b, ncb]`` with ``segments`` a list of ``[n_b, 2]``
+        frame spans; or a padded ``[B, S, ncb]`` tensor with ``segments [B, S, 2]`` and ``nunits [B]``.  ``frames`` defaults to each
+        clip's last segment end (1 for a clip without units)."""
+        if self.quantizer is None:
+            raise ValueError("synthesize_units needs a quantizer (SegmentSynthesis(quantizer=...))")
+        books = quantizer_codebooks(self.quantizer)
+        ncb = len(books)
+        if isinstance(units, (list, tuple)):
+            if units and isinstance(units[0], dict):
+                if segments is not None:
+                    raise ValueError("segments come with tokenize()'s dicts; do not pass them again")
+                if frames is None:
+                    frames = [int(u["frames"]) for u in units]
+                units, segments = [u["units"] for u in units], [u["segments"] for u in units]
+            if segments is None or len(segments) != len(units) or not units:
+                raise ValueError("pass one segment table per clip")
+            ul = [np.asarray(u.cpu() if torch.is_tensor(u) else u, dtype=np.int64) for u in units]
+            for u in ul:
+                if not (u.ndim == 2 and u.shape[-1] == ncb) and not (u.ndim == 1 and ncb == 1):
+                    raise ValueError("this quantizer decodes %d id(s) per unit: units must be [n, %d], got %s" % (ncb, ncb, u.shape))
+            ul = [u.reshape(-1, ncb) for u in ul]
+            sl = [np.asarray(s.cpu() if torch.is_tensor(s) else s, dtype=np.int64).reshape(-1, 2) for s in segments]
+            if any(len(u) != len(s) for u, s in zip(ul, sl)):
+                raise ValueError("each clip needs one segment per unit, got %s units and %s segments"
+                                 % ([len(u) for u in ul], [len(s) for s in sl]))
+            B, S = len(ul), max(1, max(len(u) for u in ul))
+            U = np.zeros((B, S, ncb), np.int64)
+            P = np.zeros((B, S, 2), np.int64)
+            for b, (u, s) in enumerate(zip(ul, sl)):
+                U[b, :len(u)], P[b, :len(s)] = u, s
+            counts = [len(u) for u in ul]
+        else:
+            if segments is None or nunits is None:
+                raise ValueError("a padded units tensor needs segments [B, S, 2] and nunits [B]")
+            U = torch.as_tensor(units).cpu().numpy().astype(np.int64)
+            P = torch.as_tensor(segments).cpu().numpy().astype(np.int64)
+            counts = [int(n) for n in torch.as_tensor(nunits).reshape(-1).tolist()]
+            if U.ndim != 3 or U.shape[-1] != ncb or P.shape != U.shape[:2] + (2,) or len(counts) != U.shape[0]:
+                raise ValueError("units [B, S, %d], segments [B, S, 2] and nunits [B] expected, got %s, %s, %d counts"
+                                 % (ncb, U.shape, P.shape, len(counts)))
+            B, S = U.shape[0], max(U.shape[1], 1)
+        if U.shape[-1] != ncb:
+            raise ValueError("this quantizer decodes %d id(s) per unit, got %d" % (ncb, U.shape[-1]))
+        if frames is None:
+            frames = [int(P[b, counts[b] - 1, 1]) if 0 < counts[b] <= P.shape[1] else 1 for b in range(B)]
+        frames = [int(f) for f in frames]
+        if len(frames) != B or min(frames) < 1:
+            raise ValueError("frames must hold %d counts >= 1, got %s" % (B, frames))
+        T = max(frames)
+        for arr, name in ((U, "unit ids"), (P, "spans")):
+            if arr.size and (arr.min() < -2 ** 31 or arr.max() >= 2 ** 31):
+                raise ValueError("%s do not fit int32" % name)
+        dev = self.device
+        i32 = lambda a: torch.from_numpy(np.ascontiguousarray(np.asarray(a, np.int32))).to(dev)   # noqa: E731
+        if U.shape[1] == 0:
+            U, P = np.zeros((B, 1, ncb), np.int64), np.zeros((B, 1, 2), np.int64)
+        cond = self.input_model.from_units(books, i32(U), i32(P), i32(counts), T, frames=i32(frames))
+        if y0 is None and rand_scale:
+            y0 = torch.randn(cond.shape[0], cond.shape[1], CFM_DIM_OUT, device=dev) * rand_scale
+        return self.decoder.sample(cond, steps=steps, y0=y0, pitch_amp=self.pitch_amp, frames=frames)
