@@ -17,11 +17,10 @@ import os
 
 from typing import List, Optional, Sequence
 
-import numpy as np
 import torch
 import torch.distributed as dist
 
-FRAME_RATE = 50
+from .segmenter import _result_dicts
 
 
 class ShardedSegmenter:
@@ -624,11 +623,4 @@ class ShardedSegmenter:
         if self.rank != 0:
             return None
         hidden, seg, nseg, feats = (t.cpu().numpy() for t in out)
-        res = []
-        for i in range(hidden.shape[0]):
-            n = int(nseg[i])
-            segments = seg[i, :n].copy() if n > 0 else np.array([])
-            res.append({"segments": segments * 1.0 / FRAME_RATE if in_second else segments,
-                        "segment_features": feats[i, :n].copy() if n > 0 else np.array([]),
-                        "hidden_states": hidden[i]})
-        return res
+        return _result_dicts(nseg, seg, feats, hidden, in_second=in_second, handed=True)

@@ -4,6 +4,7 @@ include/sylber_hip.h.  Host code stays Python on PyTorch-ROCm (device memory, st
 from __future__ import annotations
 
 import ctypes
+import math
 import os
 import collections
 import threading
@@ -75,7 +76,7 @@ class PinnedOutputPool:
         # same thread while it holds the (non-reentrant) lock, when a collection frees owner arrays caught in a reference
         # cycle -- so the release path takes no lock: deque.append is atomic, and lease() drains the deque under the lock
         self._returned = collections.deque()
-        self._alloc = alloc or (lambda cap: torch.empty(cap, dtype=torch.uint8, pin_memory=True))   # (tests inject pageable memory)
+        self._alloc = alloc or _pinned            # (tests inject pageable memory)
         self.allocations = 0                      # page-locking events so far (tests / bench: must stop growing)
 
     def _release(self, blk: torch.Tensor) -> None:
@@ -129,6 +130,97 @@ class PinnedOutputPool:
         owner = blk.numpy()
         weakref.finalize(owner, self._release, blk)
         return owner, blk
+
+
+def _pinned(nbytes: int) -> torch.Tensor:
+    return torch.empty(nbytes, dtype=torch.uint8, pin_memory=True)
+
+
+def _pad_rows(stage_np: np.ndarray, rows, lengths, lo: int, hi: int) -> None:
+    """rows [lo, hi) of a batch into the host staging view, zero padded to its width (numpy's copy releases the GIL)"""
+    for i in range(lo, hi):
+        src = rows[i].detach()
+        stage_np[i, : lengths[i]] = (src if src.dtype == torch.float32 else src.to(torch.float32)).numpy()
+        stage_np[i, lengths[i]:] = 0.0
+
+
+class _BlockLayout:
+    """Byte layout of the host block one batch's results land in: [hidden states | tables | pooled features | counts], every part
+    256-byte aligned, ``kcap`` segment slots per utterance.  The views work on the torch uint8 block (the D2H copies' targets) and
+    on its numpy owner (what the caller gets)."""
+
+    _TORCH = {np.float32: (torch.float32, 4), np.int32: (torch.int32, 4), np.int64: (torch.int64, 8)}
+
+    def __init__(self, B: int, T: int, D: int, kcap: int, with_hidden: bool, with_feats: bool):
+        def al(n):
+            return (n + 255) & ~255
+        self.B, self.T, self.D, self.kcap = B, T, D, kcap
+        self.with_hidden, self.with_feats = with_hidden, with_feats
+        self.o_seg = al(B * T * D * 4) if with_hidden else 0
+        self.o_feat = self.o_seg + al(B * kcap * 2 * 8)
+        self.o_cnt = self.o_feat + (al(B * kcap * D * 4) if with_feats else 0)
+        self.nbytes = self.o_cnt + al(B * 4)
+
+    @classmethod
+    def _view(cls, buf, off: int, dtype, shape):
+        tdt, size = cls._TORCH[dtype]
+        n = math.prod(shape) * size
+        if torch.is_tensor(buf):
+            return buf[off:off + n].view(tdt).view(shape)
+        return buf[off:off + n].view(dtype).reshape(shape)
+
+    def hidden(self, buf):
+        return self._view(buf, 0, np.float32, (self.B, self.T, self.D)) if self.with_hidden else None
+
+    def counts(self, buf):
+        return self._view(buf, self.o_cnt, np.int32, (self.B,))
+
+    def tables(self, buf, k: Optional[int] = None):
+        """(segments [B, k, 2] int64, pooled features [B, k, D] float32 or None), packed at the start of their parts (k <= kcap)"""
+        k = self.kcap if k is None else k
+        return (self._view(buf, self.o_seg, np.int64, (self.B, k, 2)),
+                self._view(buf, self.o_feat, np.float32, (self.B, k, self.D)) if self.with_feats else None)
+
+
+def _fetch_tables(seg: torch.Tensor, feats: Optional[torch.Tensor], k: int, alloc=_pinned):
+    """The tables of a batch with more segments than its block has slots: the first ``k`` slots of the device tables (and pooled
+    features) into a private block of their own, on the current stream.  -> their numpy views, valid once that stream is synchronised."""
+    B, T = seg.shape[:2]
+    lay = _BlockLayout(B, T, feats.shape[2] if feats is not None else 0, k, False, feats is not None)
+    blk = alloc(lay.nbytes)
+    seg_d, feat_d = lay.tables(blk)
+    seg_d.copy_(seg[:, :k], non_blocking=True)
+    if feat_d is not None:
+        feat_d.copy_(feats[:, :k], non_blocking=True)
+    return lay.tables(blk.numpy())
+
+
+def _segment_list(seg_h: np.ndarray, nseg_h: np.ndarray) -> List[np.ndarray]:
+    """host tables [B, k, 2] + counts [B] -> one int64 [n, 2] array per utterance (``np.array([])`` for none, sylber.py:134)"""
+    return [seg_h[i, :int(n)].copy() if n > 0 else np.array([]) for i, n in enumerate(nseg_h)]
+
+
+def _result_dicts(nseg_h, seg_h, feats_h=None, hidden_h=None, frames=None, in_second=True, handed=False) -> List[dict]:
+    """The reference's per-utterance dicts (sylber.py:128-138) from host results: counts [B], tables [B, k, 2], optional pooled
+    features [B, k, D] and hidden states [B, T, D] (cut to ``frames[i]`` frames when given).  ``handed``: the arrays belong to the
+    caller (a leased or fresh block), so features and hidden states are returned as views of them; otherwise they are copied out."""
+    outputs = []
+    for i, segments in enumerate(_segment_list(seg_h, nseg_h)):
+        n = len(segments)
+        o = {"segments": segments * 1.0 / FRAME_RATE if in_second else segments}
+        if feats_h is not None:
+            o["segment_features"] = (feats_h[i, :n] if handed else feats_h[i, :n].copy()) if n > 0 else np.array([])
+        if hidden_h is not None:
+            hb = hidden_h[i] if frames is None else hidden_h[i, :frames[i]]
+            o["hidden_states"] = hb if handed else hb.copy()
+        outputs.append(o)
+    return outputs
+
+
+def _tables_to_host(seg: torch.Tensor, nseg: torch.Tensor):
+    """-> (counts [B] int32, the first max(max(counts), 1) slots of the tables [B, k, 2] int64) on the host"""
+    nseg_h = nseg.cpu().numpy()
+    return nseg_h, seg[:, :max(int(nseg_h.max()), 1)].cpu().numpy()
 
 
 class HubertEncoderHIP:
@@ -293,6 +385,20 @@ class HubertEncoderHIP:
         _lib.check(st, "sylber_segment" if farr is None else "sylber_segment_frames")
         return seg, nseg, feats
 
+    def segment_batch(self, input_values, attention_mask, norm_threshold: float, merge_threshold: float, per_row: bool):
+        """A padded waveform batch ``[B, N]`` (or one ``[N]`` clip) and its optional 0/1 ``attention_mask`` -> forward, each row's own
+        frame count, segmentation (``per_row``: over each row's own frames, batch-invariant mode), and the counts plus the first
+        ``max(max(nseg), 1)`` table slots on the host.  Returns ``(hidden, frames, seg, nseg, feats, nseg_h, seg_h)``."""
+        x = torch.as_tensor(input_values).to(self.device, torch.float32)
+        if x.dim() == 1:
+            x = x[None]
+        x = x.contiguous()
+        lengths = None if attention_mask is None else [int(v) for v in torch.as_tensor(attention_mask).sum(-1).tolist()]
+        hidden = self.forward(x, lengths)
+        frames = self.frame_counts(lengths if lengths is not None else [x.shape[1]] * x.shape[0])
+        seg, nseg, feats = self.segment(hidden, norm_threshold, merge_threshold, frames=frames if per_row else None)
+        return (hidden, frames, seg, nseg, feats) + _tables_to_host(seg, nseg)
+
     def set_profiling(self, on: bool) -> None:
         self.lib.sylber_set_profiling(self.handle, 1 if on else 0)
 
@@ -356,13 +462,6 @@ class Segmenter:
         self.output_memory = kwargs.get("output_memory", "pinned")
         if self.output_memory not in ("pinned", "pageable"):
             raise ValueError("output_memory must be 'pinned' or 'pageable'")
-        # Round 6 (measured, OFF by default): `call_split = n >= 2` cuts a large batch of host tensors into n sub-batches that go through the machinery of
-        # ``stream`` inside the one synchronous call (upload of part 2 under the forward of part 1, download of part 1 under the forward of part 2; every
-        # part padded to the WHOLE batch's longest clip, so the call returns exactly the unsplit call's bits).  It is SLOWER on every shape tried
-        # (32 x 10 s: 7.4 -> 8.2 ms with two parts, 9.7 with three; 16 x 10 s 4.5 -> 5.5; 8 x 60 s equal): a half batch's forward is not half a forward, and
-        # the download of one part runs as a shader copy beside the 160-KiB-LDS GEMM workgroups of the other part's forward (tools/api_split_ab.py).
-        self._call_split = max(0, int(kwargs.get("call_split", 0)))
-        # (a split call leases one page-locked block per part: `max_pinned_batches` counts blocks)
         self.out_pool = PinnedOutputPool(max_leased=int(kwargs.get("max_pinned_batches", 4)))
         # host padding of tensor inputs (encode_batch).  tools/pad_probe.py on the 256-cpu boxes: the 20 MB copy of a 32 x 10 s batch into the
         # page-locked staging buffer takes 0.49 ms on one thread, 0.36-0.44 on two, MORE on four / eight / sixteen (0.58 / 0.93 / 1.25: waking
@@ -371,7 +470,6 @@ class Segmenter:
         self._fill_groups = max(1, int(kwargs.get("host_pad_groups", 8)))       # row groups the padding + H2D of a batch is cut into (H2D of group g under the padding of g + 1)
         self._kcap_seen = 128                                                    # segment slots per utterance the next block is sized for
         self._kcap_recent = collections.deque(maxlen=16)                         # per-batch maxima of the last 16 batches (sizing decays with them)
-        self._overlap_d2h = bool(kwargs.get("overlap_d2h", True))               # hidden-state D2H under the segmenter (A/B switch)
         # which keys of the reference's dict (sylber.py:134-138) a call returns.  Default = all three, the reference's contract.  A caller
         # that consumes only the tables / pooled features (tokenisation, the resynthesis front half) can drop "hidden_states": that skips
         # the 49 MB device-to-host copy of a 32 x 10 s batch (0.87 ms of a 7.9 ms call) and its page-locked block (round 6)
@@ -447,11 +545,6 @@ class Segmenter:
             batch = torch.empty(len(rows), lmax, dtype=torch.float32, device=dev)
             mark("  device batch allocated")
 
-            def fill(lo, hi):
-                for i in range(lo, hi):
-                    src = rows[i].detach()
-                    stage_np[i, : lengths[i]] = (src if src.dtype == torch.float32 else src.to(torch.float32)).numpy()
-                    stage_np[i, lengths[i]:] = 0.0
             # round 4: the 20 MB host copy of a 32 x 10 s batch is 0.47 ms on one thread, 0.26 ms on two, slower again on four or eight
             # (probed on the 256-cpu boxes).  Row groups are padded by a small
             # private thread pool (numpy's copy releases the GIL) and each group crosses PCIe as soon as it is padded, so the
@@ -461,11 +554,11 @@ class Segmenter:
             # START when the padding is over (tools/api_timeline.py: H2D done 1.25 ms into the call against 0.26 + 0.37 of work)
             ngrp = min(self._fill_groups, max(1, nrow // 4)) if nrow * lmax >= (1 << 20) else 1
             if ngrp <= 1:
-                fill(0, nrow)
+                _pad_rows(stage_np, rows, lengths, 0, nrow)
                 batch.copy_(stage, non_blocking=True)
             else:
                 bounds = [(g * nrow // ngrp, (g + 1) * nrow // ngrp) for g in range(ngrp)]
-                futs = [self._fill_pool().submit(fill, lo, hi) for lo, hi in bounds]
+                futs = [self._fill_pool().submit(_pad_rows, stage_np, rows, lengths, lo, hi) for lo, hi in bounds]
                 for (lo, hi), f in zip(bounds, futs):
                     f.result()
                     batch[lo:hi].copy_(stage[lo:hi], non_blocking=True)
@@ -518,26 +611,22 @@ class Segmenter:
         With ``batch_invariant=True`` every row of the waveform branch is segmented over its own frames (from ``attention_mask``) and
         ``features`` past them are zeroed.  ``frames=`` gives the features branch each row's frame count (default: all ``T``)."""
         dev = self.speech_model.device
+        nt = self.norm_threshold if normthreshold is None else normthreshold
+        mt = self.merge_threshold if mergethreshold is None else mergethreshold
         if features is None:
-            x = input_values.to(dev, torch.float32).contiguous()
-            lengths = None if attention_mask is None else [int(v) for v in attention_mask.sum(-1).tolist()]
-            features = self.speech_model.forward(x, lengths)
+            features, frames, seg, nseg, feats, nseg_h, seg_h = self.speech_model.segment_batch(input_values, attention_mask, nt, mt,
+                                                                                                self.batch_invariant)
             if self.batch_invariant:
-                frames = self.speech_model.frame_counts(lengths if lengths is not None else [x.shape[1]] * x.shape[0])
                 for b, f in enumerate(frames):
                     features[b, f:] = 0.0
         else:
             features = features.to(dev, torch.float32).contiguous()
-        nt = self.norm_threshold if normthreshold is None else normthreshold
-        mt = self.merge_threshold if mergethreshold is None else mergethreshold
-        seg, nseg, feats = self.speech_model.segment(features, nt, mt, frames=frames)
-        nseg_h = nseg.cpu().numpy()
-        nmax = max(int(nseg_h.max()), 1)
-        seg_h = seg[:, :nmax].cpu().numpy()
-        segments = [seg_h[i, : int(nseg_h[i])].copy() if nseg_h[i] > 0 else np.array([]) for i in range(len(nseg_h))]
+            seg, nseg, feats = self.speech_model.segment(features, nt, mt, frames=frames)
+            nseg_h, seg_h = _tables_to_host(seg, nseg)
+        nmax = seg_h.shape[1]
         keep = torch.arange(nmax, device=dev)[None, :] < nseg[:, None]
         avg_fts = torch.where(keep[:, :, None], feats[:, :nmax], torch.zeros((), device=dev))
-        return features, segments, avg_fts
+        return features, _segment_list(seg_h, nseg_h), avg_fts
 
     def __call__(self, wav_file=None, wav=None, in_second=True):
         tr = self.__dict__.get("_trace")                     # tools/api_timeline.py: list of (label, host time) marks
@@ -551,9 +640,6 @@ class Segmenter:
         mark("enter")
         gmark("enter")
         batch_wavs, is_batch = self._collect(wav_file, wav)
-        parts = self._split_plan(batch_wavs) if (is_batch and tr is None and gtr is None) else None
-        if parts is not None:
-            return self._call_in_parts(parts, in_second)
         hidden, lengths = self.encode_batch(batch_wavs)
         frames = self.speech_model.frame_counts(lengths) if self.batch_invariant else None
         gmark("forward done")
@@ -568,118 +654,46 @@ class Segmenter:
         dev = hidden.device
         cur = torch.cuda.current_stream(dev)
         B, T, D = hidden.shape
-
-        def al(n):
-            return (n + 255) & ~255
-        want_h, want_f = self._want_hidden, self._want_feats
-        hid_bytes = al(B * T * D * 4) if want_h else 0
-
-        def sizes(kc):
-            return hid_bytes, hid_bytes + al(B * kc * 2 * 8), hid_bytes + al(B * kc * 2 * 8) + (al(B * kc * D * 4) if want_f else 0)
-        kcap = min(T, self._kcap_seen)
-        o_seg, o_feat, need = sizes(kcap)
-        lease = self.out_pool.lease(need) if self.output_memory == "pinned" else None
-        handed = lease is not None
-        owner, blk = lease if handed else self._scratch_block(need)
+        lay = _BlockLayout(B, T, D, min(T, self._kcap_seen), self._want_hidden, self._want_feats)
+        owner, blk, handed = self._out_block(lay.nbytes, "call")
         copy_s = self.__dict__.get("_copy_stream")
         if copy_s is None or copy_s.device != dev:
             copy_s = self._copy_stream = torch.cuda.Stream(device=dev)
         fwd_done = self.__dict__.setdefault("_ev_fwd", torch.cuda.Event())
         fwd_done.record(cur)
-        if self._overlap_d2h and want_h:
+        if lay.with_hidden:
             with torch.cuda.stream(copy_s):
                 copy_s.wait_event(fwd_done)
-                blk[:B * T * D * 4].view(torch.float32).view(B, T, D).copy_(hidden, non_blocking=True)
+                lay.hidden(blk).copy_(hidden, non_blocking=True)
                 gmark("hidden states D2H done", copy_s)
             hidden.record_stream(copy_s)
-        seg, nseg, feats = self.speech_model.segment(hidden, self.norm_threshold, self.merge_threshold, with_features=want_f,
+        seg, nseg, feats = self.speech_model.segment(hidden, self.norm_threshold, self.merge_threshold, with_features=lay.with_feats,
                                                      frames=frames)
         gmark("boundary detection done")
-        nseg_pin = self._nseg_pinned(B)
-        nseg_pin.copy_(nseg, non_blocking=True)
+        lay.counts(blk).copy_(nseg, non_blocking=True)
         counted = self.__dict__.setdefault("_ev_counts", torch.cuda.Event())
         counted.record(cur)
         mark("lease, segmenter issued")
         counted.synchronize()                                # the counts are on the host
         mark("counts on the host (forward + boundary detection done)")
-        nseg_h = nseg_pin.numpy().copy()
-        nmax = int(nseg_h.max()) if len(nseg_h) else 0
-        k = max(nmax, 1)
-        towner, tblk = owner, blk
+        nseg_h = lay.counts(owner).copy()
+        k = max(int(nseg_h.max()), 1)
         self._note_segments(k)
-        if k > kcap:                                         # more segments than the recent batches had: the tables get their own block
-            kcap = min(T, (k + 63) & ~63)
-            t_seg, t_feat, t_need = al(0), al(B * kcap * 2 * 8), al(B * kcap * 2 * 8) + (al(B * kcap * D * 4) if want_f else 0)
-            tl = self.out_pool.lease(t_need) if handed else None
-            if tl is not None:
-                towner, tblk = tl
-            else:                                            # pageable mode, or the pool is exhausted: a private pinned bounce block
-                pb = torch.empty(t_need, dtype=torch.uint8, pin_memory=True)
-                towner, tblk = pb.numpy(), pb
-            o_seg, o_feat = t_seg, t_feat
-        if not self._overlap_d2h and want_h:
-            blk[:B * T * D * 4].view(torch.float32).view(B, T, D).copy_(hidden, non_blocking=True)
-        tblk[o_seg:o_seg + B * k * 2 * 8].view(torch.int64).view(B, k, 2).copy_(seg[:, :k], non_blocking=True)
-        if want_f:
-            tblk[o_feat:o_feat + B * k * D * 4].view(torch.float32).view(B, k, D).copy_(feats[:, :k], non_blocking=True)
+        if k > lay.kcap:                                     # more segments than the recent batches had: the tables get their own block
+            seg_h, feats_h = _fetch_tables(seg, feats, k)
+        else:
+            seg_d, feat_d = lay.tables(blk, k)
+            seg_d.copy_(seg[:, :k], non_blocking=True)
+            if feat_d is not None:
+                feat_d.copy_(feats[:, :k], non_blocking=True)
+            seg_h, feats_h = lay.tables(owner, k)
         gmark("tables D2H done")
         cur.wait_stream(copy_s)
         cur.synchronize()
         mark("all D2H done")
-        hidden_h = owner[:B * T * D * 4].view(np.float32).reshape(B, T, D) if want_h else None
-        seg_h = towner[o_seg:o_seg + B * k * 2 * 8].view(np.int64).reshape(B, k, 2)
-        feats_h = towner[o_feat:o_feat + B * k * D * 4].view(np.float32).reshape(B, k, D) if want_f else None
-        outputs = []
-        for i in range(B):
-            n = int(nseg_h[i])
-            segments = seg_h[i, :n].copy() if n > 0 else np.array([])
-            o = {"segments": segments * 1.0 / FRAME_RATE if in_second else segments}
-            if want_f:
-                # (a view of the leased block, like hidden_states; a scratch block is reused by the next call, so its rows are copied)
-                o["segment_features"] = (feats_h[i, :n] if handed else feats_h[i, :n].copy()) if n > 0 else np.array([])
-            if want_h:
-                hb = hidden_h[i] if frames is None else hidden_h[i, :frames[i]]
-                o["hidden_states"] = hb if handed else hb.copy()
-            outputs.append(o)
+        outputs = _result_dicts(nseg_h, seg_h, feats_h, lay.hidden(owner), frames, in_second, handed)
         mark("dicts built")
         return outputs if is_batch else outputs[0]
-
-    # -- one synchronous call on a large host batch, pipelined over sub-batches (round 6) -----------------
-    def _split_plan(self, batch_wavs):
-        """sub-batches (lists of the caller's tensors, in order) or None: only host batches large enough that a part still fills the chip
-        (at least 8 rows and ~65 s of padded audio per part)"""
-        n = self._call_split
-        if n < 2 or len(batch_wavs) < 2:
-            return None
-        rows, lmax = 0, 0
-        for w in batch_wavs:
-            if not torch.is_tensor(w) or w.dim() != 2 or w.is_cuda:
-                return None
-            rows += int(w.shape[0])
-            lmax = max(lmax, int(w.shape[1]))
-        n = min(n, rows // 8, (rows * lmax) >> 20)
-        if n < 2:
-            return None
-        parts, cur, acc, k = [], [], 0, 1
-        for w in batch_wavs:
-            cur.append(w)
-            acc += int(w.shape[0])
-            if acc * n >= rows * k and k < n:
-                parts.append(cur)
-                cur, k = [], k + 1
-        if cur:
-            parts.append(cur)
-        return parts if len(parts) >= 2 else None
-
-    def _call_in_parts(self, parts, in_second):
-        self._force_lmax = max(int(w.shape[1]) for p in parts for w in p)
-        outputs = []
-        try:
-            for res in self.stream(parts, in_second=in_second):
-                outputs.extend(res)
-        finally:
-            self._force_lmax = 0
-        return outputs
 
     # -- a stream of batches: the PCIe-inclusive path at (nearly) the resident rate -----------------------
     def stream(self, batches, in_second=True):
@@ -720,22 +734,16 @@ class Segmenter:
             rows, lengths = self._rows(batch_wavs if isinstance(batch_wavs, (list, tuple)) else [batch_wavs])
             if any(r.is_cuda for r in rows):
                 raise ValueError("Segmenter.stream takes host tensors (device batches have nothing to overlap: use __call__)")
-            lmax = max(max(lengths), int(self.__dict__.get("_force_lmax") or 0))      # (a split __call__ pads every part to the whole batch's max)
+            lmax = max(lengths)
             stage, slot = self._stage_buffer((len(rows), lmax))
             stage_np = stage.numpy()
-
-            def fill(lo, hi):
-                for i in range(lo, hi):
-                    src = rows[i].detach()
-                    stage_np[i, : lengths[i]] = (src if src.dtype == torch.float32 else src.to(torch.float32)).numpy()
-                    stage_np[i, lengths[i]:] = 0.0
             n = len(rows)
             if self._fill_threads > 1 and n >= 16:
-                fut = self._fill_pool().submit(fill, 0, n // 2)
-                fill(n // 2, n)
+                fut = self._fill_pool().submit(_pad_rows, stage_np, rows, lengths, 0, n // 2)
+                _pad_rows(stage_np, rows, lengths, n // 2, n)
                 fut.result()
             else:
-                fill(0, n)
+                _pad_rows(stage_np, rows, lengths, 0, n)
             tr = self.__dict__.get("_trace")
             if tr is not None:
                 tr.append(("padded", time.perf_counter()))
@@ -774,37 +782,22 @@ class Segmenter:
             if tr is not None:
                 tr.append(("compute issued", time.perf_counter(), done))
             B, T, D = hidden.shape
-
-            def al(n):
-                return (n + 255) & ~255
-            kcap = min(T, self._kcap_seen)
-            o_cnt = al(B * T * D * 4) if want_h else 0
-            o_seg = o_cnt + al(B * 4)
-            o_feat = o_seg + al(B * kcap * 2 * 8)
-            need = o_feat + (al(B * kcap * D * 4) if want_f else 0)
-            lease = self.out_pool.lease(need) if self.output_memory == "pinned" else None
-            handed = lease is not None
-            if handed:
-                owner, blk = lease
-            else:                                         # pageable mode / pool exhausted: one private bounce block per in-flight slot (three)
-                ring = self.__dict__.setdefault("_stream_scratch", [None] * 8)
-                if ring[slot_id] is None or ring[slot_id].numel() < need:
-                    ring[slot_id] = torch.empty((need + (1 << 20) - 1) >> 20 << 20, dtype=torch.uint8, pin_memory=True)
-                blk = ring[slot_id]
-                owner = blk.numpy()
+            lay = _BlockLayout(B, T, D, min(T, self._kcap_seen), want_h, want_f)
+            # (pageable mode / pool exhausted: one private bounce block per in-flight slot, three)
+            owner, blk, handed = self._out_block(lay.nbytes, slot_id)
             with torch.cuda.stream(d2h):
                 d2h.wait_event(done)
                 if want_h:
-                    blk[:B * T * D * 4].view(torch.float32).view(B, T, D).copy_(hidden, non_blocking=True)
-                blk[o_cnt:o_cnt + B * 4].view(torch.int32).copy_(nseg, non_blocking=True)
-                blk[o_seg:o_seg + B * kcap * 2 * 8].view(torch.int64).view(B, kcap, 2).copy_(seg[:, :kcap], non_blocking=True)
+                    lay.hidden(blk).copy_(hidden, non_blocking=True)
+                lay.counts(blk).copy_(nseg, non_blocking=True)
+                seg_d, feat_d = lay.tables(blk)
+                seg_d.copy_(seg[:, :lay.kcap], non_blocking=True)
                 if want_f:
-                    blk[o_feat:o_feat + B * kcap * D * 4].view(torch.float32).view(B, kcap, D).copy_(feats[:, :kcap], non_blocking=True)
+                    feat_d.copy_(feats[:, :lay.kcap], non_blocking=True)
                 out_ev = torch.cuda.Event()
                 out_ev.record(d2h)
             d["in_free"], d["out_free"] = done, out_ev
-            t.update(dict(shape=(B, T, D), kcap=kcap, offs=(o_cnt, o_seg, o_feat), owner=owner, handed=handed, out_ev=out_ev,
-                          dev=(seg, feats), frames=frames))
+            t.update(dict(layout=lay, owner=owner, handed=handed, out_ev=out_ev, dev=(seg, feats), frames=frames))
             t.pop("batch")
             return t
 
@@ -815,40 +808,17 @@ class Segmenter:
             t["out_ev"].synchronize()
             if tr is not None:
                 tr.append(("results on the host", time.perf_counter()))
-            B, T, D = t["shape"]
-            o_cnt, o_seg, o_feat = t["offs"]
-            owner, handed, kslots = t["owner"], t["handed"], t["kcap"]
-            nseg_h = owner[o_cnt:o_cnt + B * 4].view(np.int32).copy()
-            k = max(int(nseg_h.max()) if B else 0, 1)
-            towner = owner
+            lay, owner = t["layout"], t["owner"]
+            nseg_h = lay.counts(owner).copy()
+            k = max(int(nseg_h.max()), 1)
             self._note_segments(k)
-            if k > kslots:                                # more segments than the recent batches had: fetch the tables again (rare)
-                seg, feats = t["dev"]
-                kslots = min(T, (k + 63) & ~63)
-                o_seg, o_feat = 0, (B * kslots * 2 * 8 + 255) & ~255
-                pb = torch.empty(o_feat + (B * kslots * D * 4 if want_f else 0), dtype=torch.uint8, pin_memory=True)
-                pb[o_seg:o_seg + B * kslots * 2 * 8].view(torch.int64).view(B, kslots, 2).copy_(seg[:, :kslots], non_blocking=True)
-                if want_f:
-                    pb[o_feat:o_feat + B * kslots * D * 4].view(torch.float32).view(B, kslots, D).copy_(feats[:, :kslots], non_blocking=True)
+            seg, feats = t.pop("dev")
+            if k > lay.kcap:                              # more segments than the recent batches had: fetch the tables again (rare)
+                seg_h, feats_h = _fetch_tables(seg, feats, k)
                 torch.cuda.current_stream(dev).synchronize()
-                towner, tcopy = pb.numpy(), False
             else:
-                tcopy = not handed
-            t.pop("dev")
-            hidden_h = owner[:B * T * D * 4].view(np.float32).reshape(B, T, D) if want_h else None
-            seg_h = towner[o_seg:o_seg + B * kslots * 2 * 8].view(np.int64).reshape(B, kslots, 2)
-            feats_h = towner[o_feat:o_feat + B * kslots * D * 4].view(np.float32).reshape(B, kslots, D) if want_f else None
-            outputs = []
-            for i in range(B):
-                n = int(nseg_h[i])
-                segments = seg_h[i, :n].copy() if n > 0 else np.array([])
-                o = {"segments": segments * 1.0 / FRAME_RATE if in_second else segments}
-                if want_f:
-                    o["segment_features"] = (feats_h[i, :n].copy() if tcopy else feats_h[i, :n]) if n > 0 else np.array([])
-                if want_h:
-                    hb = hidden_h[i] if t["frames"] is None else hidden_h[i, :t["frames"][i]]
-                    o["hidden_states"] = hb if handed else hb.copy()
-                outputs.append(o)
+                seg_h, feats_h = lay.tables(owner)
+            outputs = _result_dicts(nseg_h, seg_h, feats_h, lay.hidden(owner), t["frames"], in_second, t["handed"])
             return outputs[0] if t["single"] else outputs
 
         try:
@@ -904,17 +874,14 @@ class Segmenter:
         self._kcap_recent.append(int(k))
         self._kcap_seen = max(128, (max(self._kcap_recent) + 63) & ~63)
 
-    def _nseg_pinned(self, B: int) -> torch.Tensor:
-        buf = self.__dict__.get("_nseg_pin")
-        if buf is None or buf.numel() < B:
-            buf = torch.empty(max(B, 64), dtype=torch.int32, pin_memory=True)
-            self._nseg_pin = buf
-        return buf[:B]
-
-    def _scratch_block(self, nbytes: int):
-        """one private pinned block for the pageable-output mode (results are COPIED out of it, so it is reused)"""
-        blk = self.__dict__.get("_scratch_pin")
+    def _out_block(self, nbytes: int, slot):
+        """-> (numpy owner, block tensor, handed): a leased pool block in "pinned" mode while the pool has one to give (handed to the
+        caller with the results), else private scratch block ``slot``, reused by the next batch with that slot (results are copied out)"""
+        lease = self.out_pool.lease(nbytes) if self.output_memory == "pinned" else None
+        if lease is not None:
+            return lease[0], lease[1], True
+        scratch = self.__dict__.setdefault("_scratch_blocks", {})
+        blk = scratch.get(slot)
         if blk is None or blk.numel() < nbytes:
-            blk = torch.empty((nbytes + (1 << 20) - 1) >> 20 << 20, dtype=torch.uint8, pin_memory=True)
-            self._scratch_pin = blk
-        return blk.numpy(), blk
+            blk = scratch[slot] = _pinned((nbytes + (1 << 20) - 1) >> 20 << 20)
+        return blk.numpy(), blk, False

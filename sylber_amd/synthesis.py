@@ -17,7 +17,7 @@ import torch
 
 from . import _lib
 from .downstream import KMQuantizer, ResidualKMQuantizer, SegmentConditioner, quantizer_codebooks
-from .segmenter import HubertEncoderHIP
+from .segmenter import HubertEncoderHIP, _segment_list
 from .weights import (CFM_CONV_K, CFM_DEPTH, CFM_DIM, CFM_DIM_COND_EMB, CFM_DIM_HEAD, CFM_DIM_IN_PROJ, CFM_DIM_OUT, CFM_FF_INNER,
                       CFM_FF_MULT, CFM_HEADS, CFM_REGISTERS, CFM_TIME_HIDDEN)
 
@@ -331,22 +331,14 @@ class SegmentSynthesis:
         if features is None:
             if input_values is None:
                 raise ValueError("pass input_values or features")
-            x = torch.as_tensor(input_values).to(dev, torch.float32)
-            if x.dim() == 1:
-                x = x[None]
-            x = x.contiguous()
-            lengths = None if attention_mask is None else [int(v) for v in torch.as_tensor(attention_mask).sum(-1).tolist()]
-            hidden = self.speech_model.forward(x, lengths)
-            frames = (self.speech_model.frame_counts(lengths if lengths is not None else [x.shape[1]] * x.shape[0])
-                      if self.batch_invariant else None)
             if normthreshold is None:
                 normthreshold = self.get_threshold()
-            seg, nseg, feats = self.speech_model.segment(hidden, normthreshold, merge_threshold, frames=frames)
+            hidden, frames, seg, nseg, feats, nseg_h, seg_h = self.speech_model.segment_batch(input_values, attention_mask, normthreshold,
+                                                                                              merge_threshold, self.batch_invariant)
+            if not self.batch_invariant:
+                frames = None
             cond, _ = self.input_model(hidden, seg, nseg, feats, normthreshold, quantizer=self.quantizer)
-            nseg_h = nseg.cpu().numpy()
-            nmax = max(int(nseg_h.max()), 1)
-            seg_h = seg[:, :nmax].cpu().numpy()
-            segments = [seg_h[i, : int(nseg_h[i])].copy() if nseg_h[i] > 0 else np.array([]) for i in range(len(nseg_h))]
+            segments = _segment_list(seg_h, nseg_h)
         else:
             feats = torch.as_tensor(features).to(dev, torch.float32).contiguous()
             if feats.dim() != 3:
@@ -367,22 +359,14 @@ class SegmentSynthesis:
         if self.quantizer is None:
             raise ValueError("tokenize needs a quantizer (SegmentSynthesis(quantizer=...))")
         dev = self.device
-        x = torch.as_tensor(input_values).to(dev, torch.float32)
-        if x.dim() == 1:
-            x = x[None]
-        x = x.contiguous()
-        lengths = None if attention_mask is None else [int(v) for v in torch.as_tensor(attention_mask).sum(-1).tolist()]
-        hidden = self.speech_model.forward(x, lengths)
-        frames = self.speech_model.frame_counts(lengths if lengths is not None else [x.shape[1]] * x.shape[0])
         if normthreshold is None:
             normthreshold = self.get_threshold()
-        seg, nseg, feats = self.speech_model.segment(hidden, normthreshold, merge_threshold, frames=frames if self.batch_invariant else None)
-        S = min(max(int(nseg.max().item()), 1), hidden.shape[1])
+        _, frames, _, nseg, feats, nseg_h, seg_h = self.speech_model.segment_batch(input_values, attention_mask, normthreshold,
+                                                                                   merge_threshold, self.batch_invariant)
+        S = seg_h.shape[1]
         keep = torch.arange(S, device=dev)[None, :] < nseg[:, None].to(torch.int64)
         head = torch.where(keep[:, :, None], feats[:, :S], torch.zeros((), device=dev)).contiguous()
         ids = self.quantizer.get_indices(head).cpu().numpy()
-        seg_h = seg[:, :S].cpu().numpy()
-        nseg_h = nseg.cpu().numpy()
         return [{"units": ids[b, :int(n)].astype(np.int64), "segments": seg_h[b, :int(n)].astype(np.int64).reshape(-1, 2),
                  "frames": int(frames[b])} for b, n in enumerate(nseg_h)]
 

@@ -273,8 +273,9 @@ def test_ragged_serving_loop_is_history_independent(sd):
 
 def test_stream_of_batches_equals_calls(sd):
     """Segmenter.stream (padding + H2D of batch i + 1 and D2H + slicing of batch i - 1 under batch i's forward) yields, batch by batch,
-    the bits of the synchronous __call__: ragged batches of changing size, a single-tensor item, both output modes, a batch with
-    more segments than any before it (the tables' second fetch), and a consumer that keeps every result"""
+    the bits of the synchronous __call__: ragged batches of changing size, a single-tensor item, a large ragged batch with a [2, N]
+    item (two rows; row groups padded on the pool threads), both output modes, a batch with more segments than any before it (the
+    tables' second fetch), and a consumer that keeps every result"""
     from sylber_amd import Segmenter
     rng = np.random.default_rng(21)
     batches = []
@@ -282,9 +283,14 @@ def test_stream_of_batches_equals_calls(sd):
         nb = int(rng.integers(1, 7))
         batches.append([syllable_wave(int(rng.integers(6000, 60000)), 900 + 10 * j + i) for i in range(nb)])
     batches.insert(3, syllable_wave(30000, 77))                               # a bare tensor: one dict, not a list
+    big = [syllable_wave(int(rng.integers(100000, 128000)), 500 + i) for i in range(20)]
+    big.insert(5, torch.cat([syllable_wave(120000, 601), syllable_wave(120000, 602)], 0))      # [2, N]: two rows of the batch
+    big[11] = syllable_wave(131072, 603)                                                         # the batch max
+    batches.insert(5, big)
     batches.append([syllable_wave(200000, 78 + i) for i in range(3)])          # long clips: many segments
     ref_seg = Segmenter(model_ckpt=sd)
     ref = [ref_seg(wav=b, in_second=False) for b in batches]
+    assert len(ref[5]) == 22 and all(o["hidden_states"].shape == ref[5][0]["hidden_states"].shape for o in ref[5])
     for mode in ("pinned", "pageable"):
         S = Segmenter(model_ckpt=sd, output_memory=mode, max_pinned_batches=3)
         S._kcap_seen = 16                                                     # force the overflow path early
@@ -306,45 +312,6 @@ def test_stream_of_batches_equals_calls(sd):
     assert list(Segmenter(model_ckpt=sd).stream([])) == []
     sec = list(Segmenter(model_ckpt=sd).stream(batches[:2], in_second=True))
     assert all(np.array_equal(a["segments"], b["segments"] / 50.0) for a, b in zip(sec[0], ref[0]))
-
-
-def test_call_split_returns_the_unsplit_call(sd):
-    """round 6 (an option, off by default: measured slower, tools/api_split_ab.py): `call_split = n` cuts a large host batch into n sub-batches pipelined
-    INSIDE one synchronous __call__ (upload of part 2 under the forward of part 1, download of part 1 under the forward of part 2).  Every part is padded to the whole batch's longest clip (sylber.py:93-118 pads to
-    the batch max and returns the padded frames) and an utterance's results do not depend on the batch it is computed in, so the call returns the
-    bits of the unsplit call: ragged lengths, a stereo item (two rows), 2 / 3 / 4 parts, both output memories, the opt-in output subset; small
-    batches, device tensors and a single tensor are not split"""
-    from sylber_amd import Segmenter
-    rng = np.random.default_rng(33)
-    wavs = [syllable_wave(int(rng.integers(100000, 128000)), 500 + i) for i in range(23)]
-    wavs.insert(5, torch.cat([syllable_wave(120000, 601), syllable_wave(120000, 602)], 0))      # [2, N]: two rows of the batch
-    wavs[11] = syllable_wave(131072, 603)                                                         # the batch max
-    ref_seg = Segmenter(model_ckpt=sd, call_split=0)
-    assert ref_seg._split_plan(wavs) is None
-    ref = ref_seg(wav=wavs, in_second=False)
-    assert len(ref) == 25 and all(o["hidden_states"].shape == ref[0]["hidden_states"].shape for o in ref)
-    for n, mode in ((2, "pinned"), (3, "pinned"), (4, "pageable")):
-        S = Segmenter(model_ckpt=sd, call_split=n, output_memory=mode)
-        plan = S._split_plan(wavs)
-        assert plan is not None and len(plan) == min(n, 3) and sum(len(p) for p in plan) == len(wavs)      # (25 rows: at most 3 parts of 8+ rows)
-        for _ in range(2):
-            got = S(wav=wavs, in_second=False)
-            assert len(got) == len(ref)
-            for g, e in zip(got, ref):
-                _check_contract(g, False)
-                assert np.array_equal(g["hidden_states"], e["hidden_states"]) and np.array_equal(g["segments"], e["segments"])
-                assert np.array_equal(g["segment_features"], e["segment_features"], equal_nan=True)
-        sec = S(wav=wavs, in_second=True)
-        assert all(np.array_equal(a["segments"], b["segments"] / 50.0) for a, b in zip(sec, ref))
-    S = Segmenter(model_ckpt=sd, call_split=2, outputs=("segments", "segment_features"))
-    got = S(wav=wavs, in_second=False)
-    assert all(set(g) == {"segments", "segment_features"} and np.array_equal(g["segments"], e["segments"]) and
-               np.array_equal(g["segment_features"], e["segment_features"], equal_nan=True) for g, e in zip(got, ref))
-    # not split: few rows, little audio, device tensors, a bare tensor
-    assert S._split_plan(wavs[:6]) is None and S._split_plan([w[:, :8000] for w in wavs]) is None
-    assert S._split_plan([w.cuda() for w in wavs]) is None
-    one = S(wav=wavs[0], in_second=False)
-    assert isinstance(one, dict) and np.array_equal(one["segments"], Segmenter(model_ckpt=sd, call_split=0)(wav=wavs[0], in_second=False)["segments"])
 
 
 def test_outputs_opt_in_skips_hidden_states(sd):
