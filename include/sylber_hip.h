@@ -163,6 +163,37 @@ int sylber_km_assign_residual(const float* feats_dev, int32_t n, const float* c1
 int sylber_km_decode_residual(const int32_t* idx_dev, int32_t n, const float* c1_dev, int32_t K1, const float* c2_dev, int32_t K2,
                               int32_t D, float* out_dev, void* stream);
 
+/* Learned quantizer (sylber/model/quantizer.py:6-77, 182-257: `load_quantizer` / `Quantizer`), eval, exact fp32.  The host
+ * (sylber_amd/quantizer.py) chains: sylber_lq_norm (input norm / padding) -> sylber_ffenc -> sylber_lq_norm (output norm, blank rows)
+ * -> sylber_rvq_assign for the art window and the pitch window -> sylber_lq_norm of the quantized rows.  All data pointers are device
+ * pointers; `ld*` are row strides in elements.
+ *
+ * _unit_norm / _unit_norm_sep (quantizer.py:33-44) and the blank mask: y[r, c] = x[r, c] / sqrt(sum x[r, range]^2 + 1e-5) for c < D
+ *   (normalize != 0; else a copy), the ranges [0, split) and [split, D) when 0 < split < D, else [0, D); y[r, D..Dy) = 0; the whole
+ *   row 0 where the row of blank_dev (width D_blank, nullable) has no positive sum of squares.  In place needs ldx == ldy. */
+int sylber_lq_norm(const float* x_dev, int64_t ldx, int32_t n, int32_t D, int32_t split, int32_t normalize, const float* blank_dev,
+                   int64_t ld_blank, int32_t D_blank, float* y_dev, int64_t ldy, int32_t Dy, void* stream);
+/* FFEncoder.forward (quantizer.py:15-31) on the exact-fp32 GEMM, one launch per Linear in upstream's order.  dims (host) [num_hidden + 2]:
+ * the input width, the hidden widths, the output width, each padded to a multiple of 16; weights (host array of device pointers)
+ * [2 * (3 * num_hidden + 1)]: (W, b) of mlp.{2i}, mlp.{2i+1}.0, mlp.{2i+1}.3 per hidden width, then of mlp.{2H}, each W [out][in] and
+ * b [out] zero-padded to the padded widths.  x_dev [n][dims[0]], y_dev [n][dims[H+1]].
+ *   workspace_dev: sylber_ffenc_workspace_floats(n, num_hidden, dims) floats */
+int64_t sylber_ffenc_workspace_floats(int32_t n, int32_t num_hidden, const int32_t* dims);
+int sylber_ffenc(const float* x_dev, int32_t n, int32_t num_hidden, const int32_t* dims, const float* const* weights, float* y_dev,
+                 float* workspace_dev, void* stream);
+/* Residual VQ of one group (GroupedResidualVQ, groups = 1, Euclidean codebooks), eval.  codebooks_dev [Q][Kp][Dp] with Kp = K rounded
+ * up to 4 and Dp = D rounded up to 16, the padding zero; sqnorms_dev [Q][Kp] = ||row||^2, written once by sylber_rvq_prepare.
+ * assign: r = x; per stage q: i_q = argmin_k ||r - E_q[k]|| (the arg-min of sylber_km_assign: ||e||^2 - 2 r.e, ties to the smallest k)
+ *   into idx_dev[row * ld_idx + q], z += E_q[i_q] (z_dev nullable), r -= E_q[i_q].  x_dev / z_dev: windows of width D, strides ldx / ldz.
+ *   workspace_dev: sylber_rvq_workspace_floats(n, K, D) floats.
+ * decode: z = sum_q E_q[clamp(idx[row * ld_idx + q], 0, K - 1)] in stage order, the sums of assign bit for bit. */
+int sylber_rvq_prepare(const float* codebooks_dev, int32_t Q, int32_t K, int32_t D, float* sqnorms_dev, void* stream);
+int64_t sylber_rvq_workspace_floats(int32_t n, int32_t K, int32_t D);
+int sylber_rvq_assign(const float* x_dev, int64_t ldx, int32_t n, int32_t D, const float* codebooks_dev, const float* sqnorms_dev, int32_t Q,
+                      int32_t K, int32_t* idx_dev, int64_t ld_idx, float* z_dev, int64_t ldz, float* workspace_dev, void* stream);
+int sylber_rvq_decode(const int32_t* idx_dev, int64_t ld_idx, int32_t n, const float* codebooks_dev, int32_t Q, int32_t K, int32_t D,
+                      float* z_dev, int64_t ldz, void* stream);
+
 /* N3: front half of SegmentSynthesis.resynthesize (sylber/model/segment_synthesis.py:103-140): segment means broadcast
  * back to their frames -> `MLP` conditioner (Linear -> RFF -> ... -> Linear, segment_synthesis.py:17-53) -> frames with
  * hidden-state norm < norm_thr zeroed.  HOST pointers to fp32 tensors in nn.Linear / nn.LayerNorm layout. */

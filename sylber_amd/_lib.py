@@ -94,6 +94,15 @@ EXPORTS = {
     "sylber_km_residual_workspace_floats": (c_int64, [c_int32, c_int32, c_int32, c_int32]),
     "sylber_km_assign_residual": (c_int, [c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
     "sylber_km_decode_residual": (c_int, [c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_int32, c_int32, c_void_p, c_void_p]),
+    "sylber_lq_norm": (c_int, [c_void_p, c_int64, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int64, c_int32, c_void_p, c_int64,
+                               c_int32, c_void_p]),
+    "sylber_ffenc_workspace_floats": (c_int64, [c_int32, c_int32, POINTER(c_int32)]),
+    "sylber_ffenc": (c_int, [c_void_p, c_int32, c_int32, POINTER(c_int32), POINTER(c_void_p), c_void_p, c_void_p, c_void_p]),
+    "sylber_rvq_prepare": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
+    "sylber_rvq_workspace_floats": (c_int64, [c_int32, c_int32, c_int32]),
+    "sylber_rvq_assign": (c_int, [c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_int64, c_void_p,
+                                  c_int64, c_void_p, c_void_p]),
+    "sylber_rvq_decode": (c_int, [c_void_p, c_int64, c_int32, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_int64, c_void_p]),
     "sylber_mlp_create": (c_int, [POINTER(SylberMlpWeights), c_int, POINTER(c_void_p)]),
     "sylber_mlp_destroy": (None, [c_void_p]),
     "sylber_condition_workspace_floats": (c_int64, [c_void_p, c_int32, c_int32]),

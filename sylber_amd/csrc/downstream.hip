@@ -65,6 +65,29 @@ extern "C" int64_t sylber_km_workspace_floats(int32_t n, int32_t K, int32_t D) {
     return (int64_t)n * ((K + 3) & ~3) + (int64_t)n * D + ((K + 3) & ~3) + 64;
 }
 
+// idx[r * istride] = argmin over the first K rows of cb of (||c||^2 - 2 x.c), given cn = ||c||^2: x . c on the exact-fp32 MFMA
+// GEMM over the first Kc >= K rows of cb (row stride D), then km_argmin_kernel.  The GEMM's N must be a multiple of 4: with
+// Kc % 4 != 0 the last (Kp - Kc) columns re-read row Kc-1.  dots: [n][Kp] floats, Kp = Kc rounded up to 4.  x: row stride ldx.
+// The one arg-min rule of the library: the k-means quantizers and the residual VQ of the learned quantizer both end here.
+static int km_nearest(const char* what, const float* x, long ldx, int n, const float* cb, int Kc, int K, int D, const float* cn,
+                      int32_t* idx_dev, int istride, float* dots, hipStream_t s) {
+    const int Kp = (Kc + 3) & ~3;
+    GemmArgsF32 g = {};
+    g.X = x; g.ldx = ldx; g.W = cb; g.M = n; g.N = Kc; g.K = D; g.out0 = dots; g.ld0 = Kp;
+    if (Kc % 4) {
+        // run the aligned part on the GEMM and leave the ragged tail to a second, 4-wide launch over the last 4 rows
+        g.N = Kc & ~3;
+        if (g.N > 0 && launch_gemm_f32(g, s)) return 1;
+        GemmArgsF32 t = g;
+        t.W = cb + (size_t)(Kc - 4 < 0 ? 0 : Kc - 4) * D; t.N = 4; t.out0 = dots + (Kc - 4 < 0 ? 0 : Kc - 4);
+        if (Kc >= 4) { if (launch_gemm_f32(t, s)) return 1; }
+        else { syl_set_error(what, "K < 4 with K % 4 != 0 is not supported"); return 1; }
+    } else if (launch_gemm_f32(g, s)) return 1;
+    hipLaunchKernelGGL(km_argmin_kernel, dim3(n), dim3(256), 0, s, dots, (long)Kp, cn, idx_dev, istride, n, K);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
 // idx_dev[r * istride] = nearest centroid of row r (istride 2: one column of the residual quantizer's [n, 2] table)
 static int km_assign_impl(const char* what, const float* feats_dev, int32_t n, const float* centroids_dev, int32_t K, int32_t D,
                           int32_t normalize, int32_t* idx_dev, int istride, float* workspace_dev, hipStream_t s) {
@@ -79,21 +102,7 @@ static int km_assign_impl(const char* what, const float* feats_dev, int32_t n, c
     }
     hipLaunchKernelGGL(km_sqnorm_kernel, dim3((K + 3) / 4), dim3(256), 0, s, centroids_dev, cn, K, D);
     HIP_TRY(hipGetLastError());
-    // x . c on the exact-fp32 MFMA GEMM; N must be a multiple of 4: the last (Kp - K) columns re-read centroid K-1
-    GemmArgsF32 g = {};
-    g.X = x; g.ldx = D; g.W = centroids_dev; g.M = n; g.N = K; g.K = D; g.out0 = dots; g.ld0 = Kp;
-    if (K % 4) {
-        // run the aligned part on the GEMM and leave the ragged tail to a second, 4-wide launch over the last 4 rows
-        g.N = K & ~3;
-        if (g.N > 0 && launch_gemm_f32(g, s)) return 1;
-        GemmArgsF32 t = g;
-        t.W = centroids_dev + (size_t)(K - 4 < 0 ? 0 : K - 4) * D; t.N = 4; t.out0 = dots + (K - 4 < 0 ? 0 : K - 4);
-        if (K >= 4) { if (launch_gemm_f32(t, s)) return 1; }
-        else { syl_set_error(what, "K < 4 with K % 4 != 0 is not supported"); return 1; }
-    } else if (launch_gemm_f32(g, s)) return 1;
-    hipLaunchKernelGGL(km_argmin_kernel, dim3(n), dim3(256), 0, s, dots, (long)Kp, cn, idx_dev, istride, n, K);
-    HIP_TRY(hipGetLastError());
-    return 0;
+    return km_nearest(what, x, D, n, centroids_dev, K, K, D, cn, idx_dev, istride, dots, s);
 }
 
 extern "C" int sylber_km_assign(const float* feats_dev, int32_t n, const float* centroids_dev, int32_t K, int32_t D, int32_t normalize,
@@ -161,6 +170,194 @@ extern "C" int sylber_km_decode_residual(const int32_t* idx_dev, int32_t n, cons
         syl_set_error("sylber_km_decode_residual", "bad argument"); return 1;
     }
     hipLaunchKernelGGL(km_decode_residual_kernel, dim3(n), dim3(256), 0, (hipStream_t)stream, idx_dev, c1_dev, K1, c2_dev, K2, out_dev, n, D);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// ---- learned quantizer (sylber/model/quantizer.py:6-77, 182-257: FFEncoder + two GroupedResidualVQ stacks) --------------------
+// Exact fp32 like the k-means path: the encoder's Linears on the f32 MFMA GEMM (one launch per Linear, upstream's order), the
+// unit norms in one kernel, the residual VQ on km_nearest (the arg-min rule above) plus a residual-update kernel per stage.
+// Widths that are not multiples of 16 are zero-padded: the caller pads weights and codebooks once at load, the kernels pad the
+// activations; a zero column adds fmaf(0, 0, acc) = acc to every chain, so the padded contractions are the unpadded ones.
+
+// _unit_norm / _unit_norm_sep (quantizer.py:33-44) and the blank mask of Quantizer.forward (:217, :228-229), one wave per row:
+//   y[r, c] = x[r, c] / sqrt(sum_{c' in range(c)} x[r, c']^2 + 1e-5)  for c < D (normalize; else a plain copy), the ranges being
+//   [0, split) and [split, D) for 0 < split < D and [0, D) otherwise; y[r, c] = 0 for D <= c < Dy (padding);
+//   the whole row 0 where !(sum_c blank[r, c]^2 > 0) (blank != nullptr: the token as it entered forward).
+// Each range's sum is a lane-strided fmaf chain plus the wave's butterfly: a fixed order per row, whatever n is.  In place is allowed
+// (x == y, ldx == ldy): every lane reads an element before it writes it, and the sums are complete before any write.
+__global__ __launch_bounds__(256) void lq_norm_kernel(const float* x, long ldx, int n, int D, int split, int normalize,
+                                                      const float* __restrict__ blank, long ldb, int Db, float* y, long ldy, int Dy) {
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int r = blockIdx.x * 4 + wave;
+    if (r >= n) return;
+    const float* xr = x + (size_t)r * ldx;
+    float* yr = y + (size_t)r * ldy;
+    bool zero = false;
+    if (blank) {
+        float b = 0.f;
+        for (int c = lane; c < Db; c += 64) { const float v = blank[(size_t)r * ldb + c]; b = fmaf(v, v, b); }
+        b = wave_sum(b);
+        zero = !(b > 0.f);
+    }
+    const int sp = (split > 0 && split < D) ? split : D;
+    float n0 = 1.f, n1 = 1.f;
+    if (normalize) {
+        float s0 = 0.f, s1 = 0.f;
+        for (int c = lane; c < sp; c += 64) { const float v = xr[c]; s0 = fmaf(v, v, s0); }
+        for (int c = sp + lane; c < D; c += 64) { const float v = xr[c]; s1 = fmaf(v, v, s1); }
+        s0 = wave_sum(s0); s1 = wave_sum(s1);
+        n0 = sqrtf(s0 + 1e-5f); n1 = sqrtf(s1 + 1e-5f);
+    }
+    for (int c = lane; c < Dy; c += 64) {
+        float v = 0.f;
+        if (c < D && !zero) { v = xr[c]; if (normalize) v = v / (c < sp ? n0 : n1); }
+        yr[c] = v;
+    }
+}
+
+extern "C" int sylber_lq_norm(const float* x_dev, int64_t ldx, int32_t n, int32_t D, int32_t split, int32_t normalize, const float* blank_dev,
+                              int64_t ld_blank, int32_t D_blank, float* y_dev, int64_t ldy, int32_t Dy, void* stream) {
+    static const char* what = "sylber_lq_norm";
+    if (!x_dev || !y_dev) { syl_set_error(what, "null argument"); return 1; }
+    if (n < 0 || D < 1 || Dy < D || ldx < D || ldy < Dy || (blank_dev && (D_blank < 1 || ld_blank < D_blank))) {
+        syl_set_error(what, "need n >= 0, D >= 1, Dy >= D, ldx >= D, ldy >= Dy (and ld_blank >= D_blank >= 1 with a blank source)"); return 1;
+    }
+    if (x_dev == y_dev && ldx != ldy) { syl_set_error(what, "in place needs ldx == ldy"); return 1; }
+    if (n == 0) return 0;
+    hipLaunchKernelGGL(lq_norm_kernel, dim3((n + 3) / 4), dim3(256), 0, (hipStream_t)stream, x_dev, (long)ldx, n, D, split, normalize,
+                       blank_dev, (long)ld_blank, D_blank, y_dev, (long)ldy, Dy);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+static int64_t ffenc_maxdim(int32_t num_hidden, const int32_t* dims) {
+    int64_t m = 0;
+    for (int i = 0; i < num_hidden; ++i) m = dims[i + 1] > m ? dims[i + 1] : m;
+    return m;
+}
+extern "C" int64_t sylber_ffenc_workspace_floats(int32_t n, int32_t num_hidden, const int32_t* dims) {
+    if (n < 1 || num_hidden < 0 || !dims) return -1;
+    return 2 * (int64_t)n * ffenc_maxdim(num_hidden, dims) + 64;
+}
+
+// FFEncoder.forward (quantizer.py:15-31): per hidden dim h, Linear(in, h) -> Linear(h, h) -> ReLU -> Linear(h, h) (the FeedForward;
+// Dropout is the identity in eval), then Linear(in, out).  One GEMM launch per Linear with the bias (and the ReLU) in the epilogue,
+// ping-ponging between two [n][max h] buffers of the workspace.
+extern "C" int sylber_ffenc(const float* x_dev, int32_t n, int32_t num_hidden, const int32_t* dims, const float* const* weights, float* y_dev,
+                            float* workspace_dev, void* stream) {
+    static const char* what = "sylber_ffenc";
+    hipStream_t s = (hipStream_t)stream;
+    if (!x_dev || !dims || !weights || !y_dev || !workspace_dev) { syl_set_error(what, "null argument"); return 1; }
+    if (n < 1 || num_hidden < 0) { syl_set_error(what, "need n >= 1 and num_hidden >= 0"); return 1; }
+    for (int i = 0; i < num_hidden + 2; ++i)
+        if (dims[i] < 16 || dims[i] % 16) { syl_set_error(what, "every (padded) width must be a positive multiple of 16"); return 1; }
+    for (int i = 0; i < 2 * (3 * num_hidden + 1); ++i)
+        if (!weights[i]) { syl_set_error(what, "missing weight or bias"); return 1; }
+    float* buf[2] = {workspace_dev, workspace_dev + (size_t)n * ffenc_maxdim(num_hidden, dims)};
+    const float* cur = x_dev;
+    int in = dims[0], w = 0, pp = 0;
+    auto linear = [&](int out, int act, float* dst) {
+        GemmArgsF32 g = {};
+        g.X = cur; g.ldx = in; g.W = weights[w]; g.M = n; g.N = out; g.K = in; g.bias = weights[w + 1]; g.act = act; g.out0 = dst; g.ld0 = out;
+        w += 2; cur = dst; in = out;
+        return launch_gemm_f32(g, s);
+    };
+    for (int i = 0; i < num_hidden; ++i) {
+        const int h = dims[i + 1];
+        if (linear(h, 0, buf[pp])) return 1;                  // mlp.{2i}: Linear(in, h)
+        pp ^= 1;
+        if (linear(h, ACTF_RELU, buf[pp])) return 1;          // mlp.{2i+1}.0 + ReLU
+        pp ^= 1;
+        if (linear(h, 0, buf[pp])) return 1;                  // mlp.{2i+1}.3
+        pp ^= 1;
+    }
+    return linear(dims[num_hidden + 1], 0, y_dev);             // mlp.{2H}: Linear(in, out)
+}
+
+// ||E_q[k]||^2 of every codebook row, once at load: codebooks [Q][Kp][Dp] (Kp = K rounded up to 4, Dp = D rounded up to 16, the
+// padding zero), out [Q][Kp].  The same lane-strided chain as km_sqnorm_kernel (which it is): zero columns add nothing.
+extern "C" int sylber_rvq_prepare(const float* codebooks_dev, int32_t Q, int32_t K, int32_t D, float* sqnorms_dev, void* stream) {
+    if (!codebooks_dev || !sqnorms_dev || Q < 1 || K < 1 || D < 1) { syl_set_error("sylber_rvq_prepare", "bad argument"); return 1; }
+    const int Kp = (K + 3) & ~3, Dp = (D + 15) & ~15, rows = Q * Kp;
+    hipLaunchKernelGGL(km_sqnorm_kernel, dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, codebooks_dev, sqnorms_dev, rows, Dp);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+extern "C" int64_t sylber_rvq_workspace_floats(int32_t n, int32_t K, int32_t D) {
+    if (n < 1 || K < 1 || D < 1) return -1;
+    return (int64_t)n * ((K + 3) & ~3) + (int64_t)n * ((D + 15) & ~15) + 64;
+}
+
+// one residual stage, one wave per row: i = idx[r * ld_idx] (already in [0, K) from the arg-min; clamped all the same), then
+// r -= E_q[i] over the Dp padded columns (update_r; 0 - 0 keeps the padding 0) and z = (first ? 0 : z) + E_q[i] over D columns
+// (z != nullptr): quantized_out = quantized_out + quantized, residual = residual - quantized, in stage order.
+__global__ __launch_bounds__(256) void rvq_update_kernel(const int32_t* __restrict__ idx, long ld_idx, const float* __restrict__ E, int K, int D,
+                                                         int Dp, float* __restrict__ res, int update_r, float* __restrict__ z, long ldz, int first, int n) {
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int r = blockIdx.x * 4 + wave;
+    if (r >= n) return;
+    int i = idx[(size_t)r * ld_idx]; i = i < 0 ? 0 : (i >= K ? K - 1 : i);
+    const float* e = E + (size_t)i * Dp;
+    if (update_r) for (int c = lane; c < Dp; c += 64) res[(size_t)r * Dp + c] = res[(size_t)r * Dp + c] - e[c];
+    if (z) for (int c = lane; c < D; c += 64) z[(size_t)r * ldz + c] = (first ? 0.f : z[(size_t)r * ldz + c]) + e[c];
+}
+
+// ResidualVQ of one group, eval (the GroupedResidualVQ restatement): r = x; for q: i_q = argmin_k ||r - E_q[k]|| (ties: smallest k),
+// z += E_q[i_q], r -= E_q[i_q].  x: rows of width D at stride ldx (a column window of the normalised encoder output), idx: column q at
+// idx_dev[row * ld_idx + q], z: optional window of width D at stride ldz.  The residual lives in the workspace, zero-padded to Dp.
+extern "C" int sylber_rvq_assign(const float* x_dev, int64_t ldx, int32_t n, int32_t D, const float* codebooks_dev, const float* sqnorms_dev,
+                                 int32_t Q, int32_t K, int32_t* idx_dev, int64_t ld_idx, float* z_dev, int64_t ldz, float* workspace_dev,
+                                 void* stream) {
+    static const char* what = "sylber_rvq_assign";
+    hipStream_t s = (hipStream_t)stream;
+    if (!x_dev || !codebooks_dev || !sqnorms_dev || !idx_dev || !workspace_dev) { syl_set_error(what, "null argument"); return 1; }
+    if (n < 1 || D < 1 || Q < 1 || K < 1 || ldx < D || ld_idx < Q || (z_dev && ldz < D)) {
+        syl_set_error(what, "need n, D, Q, K >= 1, ldx >= D, ld_idx >= Q and ldz >= D"); return 1;
+    }
+    const int Kp = (K + 3) & ~3, Dp = (D + 15) & ~15;
+    float* dots = workspace_dev;                              // [n][Kp]
+    float* res = dots + (size_t)n * Kp;                       // [n][Dp] (16-byte aligned: Kp % 4 == 0)
+    hipLaunchKernelGGL(lq_norm_kernel, dim3((n + 3) / 4), dim3(256), 0, s, x_dev, (long)ldx, n, D, 0, 0, (const float*)nullptr, 0L, 0,
+                       res, (long)Dp, Dp);
+    HIP_TRY(hipGetLastError());
+    for (int q = 0; q < Q; ++q) {
+        const float* E = codebooks_dev + (size_t)q * Kp * Dp;
+        if (km_nearest(what, res, Dp, n, E, Kp, K, Dp, sqnorms_dev + (size_t)q * Kp, idx_dev + q, (int)ld_idx, dots, s)) return 1;
+        const int update_r = q + 1 < Q;                         // the last stage's residual is never read
+        if (!update_r && !z_dev) break;
+        hipLaunchKernelGGL(rvq_update_kernel, dim3((n + 3) / 4), dim3(256), 0, s, idx_dev + q, (long)ld_idx, E, K, D, Dp, res, update_r,
+                           z_dev, (long)ldz, q == 0 ? 1 : 0, n);
+        HIP_TRY(hipGetLastError());
+    }
+    return 0;
+}
+
+// get_output_from_indices of the same stack: z = sum_q E_q[clamp(i_q, 0, K-1)] in stage order (from 0, as the assignment's z),
+// one wave per row.  Negative ids are upstream's clip(0); ids >= K clamp to K-1 (upstream would index out of range).
+__global__ __launch_bounds__(256) void rvq_decode_kernel(const int32_t* __restrict__ idx, long ld_idx, const float* __restrict__ cb, int Q, int K,
+                                                         int Kp, int D, int Dp, float* __restrict__ z, long ldz, int n) {
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int r = blockIdx.x * 4 + wave;
+    if (r >= n) return;
+    for (int c = lane; c < D; c += 64) {
+        float acc = 0.f;
+        for (int q = 0; q < Q; ++q) {
+            int i = idx[(size_t)r * ld_idx + q]; i = i < 0 ? 0 : (i >= K ? K - 1 : i);
+            acc = acc + cb[((size_t)q * Kp + i) * Dp + c];
+        }
+        z[(size_t)r * ldz + c] = acc;
+    }
+}
+extern "C" int sylber_rvq_decode(const int32_t* idx_dev, int64_t ld_idx, int32_t n, const float* codebooks_dev, int32_t Q, int32_t K, int32_t D,
+                                 float* z_dev, int64_t ldz, void* stream) {
+    if (!idx_dev || !codebooks_dev || !z_dev || n < 0 || Q < 1 || K < 1 || D < 1 || ld_idx < Q || ldz < D) {
+        syl_set_error("sylber_rvq_decode", "bad argument"); return 1;
+    }
+    if (n == 0) return 0;
+    hipLaunchKernelGGL(rvq_decode_kernel, dim3((n + 3) / 4), dim3(256), 0, (hipStream_t)stream, idx_dev, (long)ld_idx, codebooks_dev, Q, K,
+                       (K + 3) & ~3, D, (D + 15) & ~15, z_dev, (long)ldz, n);
     HIP_TRY(hipGetLastError());
     return 0;
 }

@@ -133,8 +133,17 @@ def load_residualkm_quantizer(centroids, centroids2, normalize: bool = False, de
     return ResidualKMQuantizer(centroids, centroids2, normalize=normalize, device=device)
 
 
+LEARNED_QUANTIZER_NO_FEATURES = (
+    "a learned Quantizer decodes to its [..., output_dim] art / pitch embedding, not to the 768-d segment feature the conditioning "
+    "MLP reads; it can tokenize, but not condition resynthesis (use a KMQuantizer / ResidualKMQuantizer for that)")
+
+
 def quantizer_codebooks(quantizer) -> Sequence[torch.Tensor]:
-    """the codebooks whose rows ``quantizer.decode`` sums: one for a ``KMQuantizer``, two for a ``ResidualKMQuantizer``"""
+    """the codebooks whose rows ``quantizer.decode`` sums: one for a ``KMQuantizer``, two for a ``ResidualKMQuantizer``.  A learned
+    ``Quantizer`` is refused: its decode is an art / pitch embedding of ``output_dim`` columns, not a 768-d feature row."""
+    from .quantizer import Quantizer
+    if isinstance(quantizer, Quantizer):
+        raise ValueError(LEARNED_QUANTIZER_NO_FEATURES)
     books = getattr(quantizer, "codebooks", None)
     if books is None:
         books = (quantizer.centroids,)

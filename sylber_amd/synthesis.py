@@ -16,7 +16,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from .downstream import KMQuantizer, ResidualKMQuantizer, SegmentConditioner, quantizer_codebooks
+from .downstream import LEARNED_QUANTIZER_NO_FEATURES, KMQuantizer, ResidualKMQuantizer, SegmentConditioner, quantizer_codebooks
+from .quantizer import Quantizer
 from .segmenter import HubertEncoderHIP, _segment_list
 from .weights import (CFM_CONV_K, CFM_DEPTH, CFM_DIM, CFM_DIM_COND_EMB, CFM_DIM_HEAD, CFM_DIM_IN_PROJ, CFM_DIM_OUT, CFM_FF_INNER,
                       CFM_FF_MULT, CFM_HEADS, CFM_REGISTERS, CFM_TIME_HIDDEN)
@@ -259,7 +260,8 @@ class SegmentSynthesis:
     ``SegmentSynthesis.state_dict()`` (``speech_model.*``, ``input_model.mlp.*``, ``regressor.*`` / ``cfm_wrapper.regressor.*``,
     ``thresholder.*``), optionally inside a Lightning ``{"state_dict": {"net.<key>": ...}}`` wrapper.  ``precision``:
     "bf16" (default), "fp16" or "fp32" (parity mode), for the encoder and the decoder alike.
-    ``quantizer``: None, a ``KMQuantizer`` / ``ResidualKMQuantizer``, or a ``.npy`` codebook path; with a path,
+    ``quantizer``: None, a ``KMQuantizer`` / ``ResidualKMQuantizer``, a learned ``Quantizer`` (``tokenize`` only: its decode is
+    not a feature row, so ``resynthesize`` / ``synthesize_units`` refuse it), or a ``.npy`` codebook path; with a path,
     ``residual_quantizer`` (a second ``.npy`` path) makes it a ``ResidualKMQuantizer`` and ``normalize_embed`` is the
     ``KMQuantizer``'s ``normalize`` (what upstream's constructor, segment_synthesis.py:93-99, means to do)."""
 
@@ -331,6 +333,8 @@ class SegmentSynthesis:
         if features is None:
             if input_values is None:
                 raise ValueError("pass input_values or features")
+            if isinstance(self.quantizer, Quantizer):
+                raise ValueError(LEARNED_QUANTIZER_NO_FEATURES)
             if normthreshold is None:
                 normthreshold = self.get_threshold()
             hidden, frames, seg, nseg, feats, nseg_h, seg_h = self.speech_model.segment_batch(input_values, attention_mask, normthreshold,
@@ -352,7 +356,7 @@ class SegmentSynthesis:
 
     def tokenize(self, input_values, attention_mask=None, merge_threshold=0.8, normthreshold=None) -> List[dict]:
         """speech -> syllable units: one dict per clip with ``units`` int64 ``[n, ncb]`` (the quantizer's ids of the clip's segment
-        means: ncb = 1 for a ``KMQuantizer``, 2 for a ``ResidualKMQuantizer``), ``segments`` int64 ``[n, 2]`` (the table
+        means: ncb = 1 for a ``KMQuantizer``, 2 for a ``ResidualKMQuantizer``, Qa + Qp for a learned ``Quantizer``), ``segments`` int64 ``[n, 2]`` (the table
         ``resynthesize`` returns; ``[0, 2]`` for none) and ``frames`` (the clip's own frame count).  Everything up to the ids runs on the
         device; slots past a clip's segment count are zeroed there.  ``synthesize_units(tokenize(wav))`` is bitwise
         ``resynthesize(wav)`` with ``batch_invariant=True``.  ``ValueError`` without a quantizer."""
@@ -382,6 +386,8 @@ class SegmentSynthesis:
         clip's last segment end (1 for a clip without units)."""
         if self.quantizer is None:
             raise ValueError("synthesize_units needs a quantizer (SegmentSynthesis(quantizer=...))")
+        if isinstance(self.quantizer, Quantizer):
+            raise ValueError(LEARNED_QUANTIZER_NO_FEATURES)
         books = quantizer_codebooks(self.quantizer)
         ncb = len(books)
         if isinstance(units, (list, tuple)):

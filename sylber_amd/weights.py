@@ -231,3 +231,52 @@ def synthetic_regressor_state_dict(seed: int = 0) -> Dict[str, torch.Tensor]:
     sd["transformer.final_norm.gamma"] = 1.0 + randn(D, std=0.1)
     sd["to_pred.weight"] = randn(CFM_DIM_OUT, D, std=1.0 / math.sqrt(D))
     return sd
+
+
+# ---- the learned quantizer (sylber/model/quantizer.py:182-257) ------------------------------------------------------------------
+def synthetic_quantizer_state_dict(config: dict, seed: int = 0, bias_std: float = 0.01) -> Dict[str, torch.Tensor]:
+    """Seeded weights of upstream's ``Quantizer(**config)`` in the key layout of its ``state_dict()``: ``encoder.mlp.*`` and
+    ``{art,pitch}_vq.rvqs.0.layers.{q}._codebook.embed`` ``[1, K, d]`` (with the ``initted`` / ``cluster_size`` / ``embed_avg``
+    buffers a trained checkpoint carries).  Codebooks that make near-ties rare: stage 0 holds the (normalised, if the config says
+    so) encoder outputs of random tokens, computed here in float64; later stages are random rows at a smaller scale each."""
+    from .quantizer import _encoder_layers, check_quantizer_config
+    geom = check_quantizer_config(config["encoder_configs"], config["art_vq_configs"], config["pitch_vq_configs"],
+                                  config.get("pitch_emb_dim", 8))
+    g = torch.Generator().manual_seed(20_000 + seed)
+
+    def randn(*shape, std=1.0):
+        return torch.randn(*shape, generator=g, dtype=torch.float64) * std
+
+    sd: Dict[str, torch.Tensor] = {}
+    layers = []
+    for name, out_f, in_f in _encoder_layers(geom):
+        w, b = randn(out_f, in_f, std=1.0 / math.sqrt(in_f)), randn(out_f, std=bias_std)
+        sd[name + ".weight"], sd[name + ".bias"] = w.float(), b.float()
+        layers.append((name, w, b))
+
+    def unit(x):
+        return x / torch.sqrt((x ** 2).sum(-1, keepdim=True) + 1e-5)
+
+    A, p = geom["A"], geom["p"]
+    Kmax = max(geom["art"]["codebook_size"], geom["pitch"]["codebook_size"])
+    x = randn(Kmax, geom["input_dim"])
+    if config.get("unit_norm_encoder_input", True):
+        x = unit(x)
+    for name, w, b in layers:
+        x = x @ w.T + b
+        if name.endswith(".0"):
+            x = torch.relu(x)
+    if config.get("unit_norm_encoder_output", True):
+        x = torch.cat([unit(x[:, :A]), unit(x[:, A:])], 1) if config.get("separate_norm", True) else unit(x)
+    for st, cols in (("art_vq", x[:, :A]), ("pitch_vq", x[:, A:])):
+        vc = geom["art" if st == "art_vq" else "pitch"]
+        K, d = vc["codebook_size"], vc["dim"]
+        scale = float(torch.sqrt((cols[:K] ** 2).sum(-1).mean()))
+        for q in range(vc["num_quantizers"]):
+            e = cols[:K] + randn(K, d, std=0.05 * scale / math.sqrt(d)) if q == 0 else randn(K, d, std=scale * 0.4 ** q / math.sqrt(d))
+            pre = "%s.rvqs.0.layers.%d._codebook." % (st, q)
+            sd[pre + "embed"] = e.float()[None]
+            sd[pre + "initted"] = torch.tensor([True])
+            sd[pre + "cluster_size"] = torch.ones(1, K)
+            sd[pre + "embed_avg"] = e.float()[None].clone()
+    return sd
