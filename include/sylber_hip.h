@@ -118,6 +118,32 @@ int sylber_segment(sylber_t h, const float* hidden_dev, int32_t B, int32_t T, in
 int sylber_segment_frames(sylber_t h, const float* hidden_dev, const int32_t* frames_host, int32_t B, int32_t T, int32_t D,
                           float norm_thr, float merge_thr, int64_t* seg_dev, int32_t* nseg_dev, float* feat_dev, void* stream);
 
+/* ---- packed variable-length batches ------------------------------------------------------------
+ * A ragged batch without padding to its longest clip: clip b gets a slot of frames at frame offset offsets[b], the slots follow each
+ * other, and the whole batch runs as one pseudo-utterance of offsets[B] frames.  Per clip the results are bit-identical to
+ * sylber_forward with SYLBER_OPT_PER_UTTERANCE = 1 (and to that clip alone) and to sylber_segment_frames.  Host only, no GPU:
+ *   samples_host [B] samples per clip, each >= 400 (one frame)
+ *   offsets      [B + 1] out: slot b = frames [offsets[b], offsets[b + 1]), offsets[0] = 0, offsets[B] = the batch's total frames.  A slot
+ *                holds every conv layer's valid rows of a call of the clip's own length, rounded up to a multiple of 64 frames (whole
+ *                attention key tiles), so it is 1 to 65 frames longer than frames[b]
+ *   frames       [B] out: sylber_num_frames(samples_host[b])
+ * Fails (status 1) on B < 1, a clip below 400 samples, or a batch whose waveform (320 x offsets[B] samples) exceeds 2^31 - 1 samples. */
+int sylber_packed_layout(const int32_t* samples_host, int32_t B, int32_t* offsets, int32_t* frames);
+/* (1) for a packed batch.  wav_dev: 320 x offsets[B] fp32 samples, clip b's samples_host[b] samples from sample 320 x offsets[b], zeros
+ * to the end of its slot.  hidden_dev [offsets[B], 768] fp32: clip b's hidden states are rows [offsets[b], offsets[b] + frames[b]); the
+ * rows behind them hold whatever the forward computes there.  SYLBER_BF16 and SYLBER_FP16 only; refused in graph mode, with a stop
+ * stage, SYLBER_OPT_CONV0_VALU or SYLBER_OPT_ATTN_QUERIES_PER_WAVE set.  The slot tables travel as kernel arguments (no host copy);
+ * samples_host is read before the call returns.  Same workspace and stream rules as sylber_forward. */
+int sylber_forward_packed(sylber_t h, const float* wav_dev, const int32_t* samples_host, int32_t B, float* hidden_dev, void* stream);
+/* (2)+(3) for a packed batch: clip b is segmented and pooled as sylber_segment_frames segments hidden[offsets[b] : offsets[b] + frames[b]]
+ * alone.  Tables relative to the clip's first frame, kcap = max frames[b] slots per clip: seg_dev [B, kcap, 2], nseg_dev [B], feat_dev
+ * [B, kcap, 768] or NULL.  Refused under SYLBER_OPT_SEGMENT = -1. */
+int sylber_segment_packed(sylber_t h, const float* hidden_dev, const int32_t* samples_host, int32_t B, float norm_thr, float merge_thr,
+                          int64_t* seg_dev, int32_t* nseg_dev, float* feat_dev, void* stream);
+/* each clip's own hidden states of a packed batch, back to back: out_dev [sum frames[b], 768] fp32 (clip b from row frames[0] + ... +
+ * frames[b - 1]), from sylber_forward_packed's hidden_dev.  No handle, stream-ordered; one device-to-host copy then fetches them all. */
+int sylber_packed_gather(const float* hidden_dev, const int32_t* samples_host, int32_t B, float* out_dev, void* stream);
+
 /* ---- file ingest on the device (replaces sylber.py:83-86) -------------------
  *   wav, sr = torchaudio.load(file); if sr != 16000: wav = torchaudio.transforms.Resample(sr, 16000)(wav);
  *   wav = (wav - wav.mean()) / wav.std()

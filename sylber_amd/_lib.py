@@ -120,6 +120,11 @@ EXPORTS = {
     "sylber_cfm_sample_frames": (c_int, [c_void_p, c_void_p, POINTER(c_int32), c_int32, c_int32, c_int32, c_void_p, c_float, c_void_p,
                                          c_void_p, c_void_p]),
     "sylber_cfm_eval": (c_int, [c_void_p, c_void_p, c_float, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
+    "sylber_packed_layout": (c_int, [POINTER(c_int32), c_int32, POINTER(c_int32), POINTER(c_int32)]),
+    "sylber_forward_packed": (c_int, [c_void_p, c_void_p, POINTER(c_int32), c_int32, c_void_p, c_void_p]),
+    "sylber_packed_gather": (c_int, [c_void_p, POINTER(c_int32), c_int32, c_void_p, c_void_p]),
+    "sylber_segment_packed": (c_int, [c_void_p, c_void_p, POINTER(c_int32), c_int32, c_float, c_float, c_void_p, c_void_p, c_void_p,
+                                      c_void_p]),
     "sylber_op_attention": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32,
                                     c_int32, c_void_p]),
 }
@@ -132,6 +137,7 @@ DEV_EXPORTS = {
     "sylber_debug_poison_workspace": (c_int, [c_void_p, c_int32]),
 }
 OPT_GEMM_TILE, OPT_ATTN_QUERIES_PER_WAVE, OPT_GEMM_PERSISTENT = 1, 2, 3
+OPT_CONV0_VALU = 5
 OPT_FP8_ATTENTION, OPT_SEGMENT, OPT_PER_UTTERANCE = 7, 9, 14
 
 _LIB = None

@@ -42,7 +42,7 @@ extern "C" int32_t sylber_num_frames(int32_t n) {
 // frame pitch per utterance of the internal activation buffers: enough rows for every conv layer's valid outputs at
 // its 2^(6-i) rows-per-frame pitch, rounded up to 32 (a 32-row MFMA block then never straddles two utterances, and
 // 32 x 10 s = 16384 rows is a whole number of 256-row tiles)
-static int padded_frames(int Lmax) {
+static int frames_needed(int Lmax) {
     int n = Lmax, tp = 0;
     for (int i = 0; i < 7; ++i) {
         n = (n - CK[i]) / CS[i] + 1;
@@ -50,9 +50,29 @@ static int padded_frames(int Lmax) {
         const int need = (n + f - 1) / f;
         tp = need > tp ? need : tp;
     }
-    return (tp + 31) & ~31;
+    return tp;
 }
+static int padded_frames(int Lmax) { return (frames_needed(Lmax) + 31) & ~31; }
 extern "C" int32_t sylber_padded_frames(int32_t n_samples) { return n_samples < 400 ? 0 : padded_frames(n_samples); }
+
+// packed batches: clip b's slot holds every conv layer's valid rows of a call of its own length (frames_needed, which can exceed its
+// frame count by one or two), rounded up to whole 64-key attention tiles; the slots follow each other from frame 0
+#define SYL_SLOT_ALIGN 64
+extern "C" int sylber_packed_layout(const int32_t* samples_host, int32_t B, int32_t* offsets, int32_t* frames) {
+    if (!samples_host || !offsets || !frames || B < 1) { syl_set_error("sylber_packed_layout", "need B >= 1 and non-null arrays"); return 1; }
+    // the waveform offsets (SYL_SLOT_SAMPLES x frame offset) and the conv1 GEMM's rows (64 x frames) are 32-bit in the kernels
+    const long long cap = (long long)INT32_MAX / SYL_SLOT_SAMPLES;
+    long long off = 0;
+    for (int b = 0; b < B; ++b) {
+        if (samples_host[b] < 400) { syl_set_error("sylber_packed_layout", "every clip needs at least 400 samples (one frame)"); return 1; }
+        offsets[b] = (int32_t)off;
+        frames[b] = sylber_num_frames(samples_host[b]);
+        off += (frames_needed(samples_host[b]) + SYL_SLOT_ALIGN - 1) & ~(SYL_SLOT_ALIGN - 1);
+        if (off > cap) { syl_set_error("sylber_packed_layout", "the packed batch is too long (more than 2^31 waveform samples)"); return 1; }
+    }
+    offsets[B] = (int32_t)off;
+    return 0;
+}
 
 struct LayerDev {
     bf16_t *wqkv, *wo, *w1, *w2;
@@ -335,21 +355,17 @@ extern "C" int64_t sylber_workspace_bytes(sylber_t c) { return c ? (int64_t)(c->
 struct Plan {
     int B, Lmax, L[7], T, Tp, Tpv, R[7];
     size_t o_bufA, o_bufB, o_ln512, o_xf32, o_xpad, o_pre, o_stats, o_hbf16, o_q, o_k, o_vt, o_ctx, o_ffn, o_part, o_ss, o_valid,
-        o_rows, total;
+        o_rows, o_pk, total;
     int nchunk;
     bool zero_all = false;        // fp32 parity plan: its own offsets, zero everything on a layout change
     // SYLBER_SPLIT16: every 16-bit buffer holds two half planes; element offsets of the lo planes (0 otherwise)
     long lo_bufA = 0, lo_bufB = 0, lo_ln512 = 0, lo_xpad = 0, lo_hbf = 0, lo_qk = 0, lo_vt = 0, lo_ctx = 0, lo_ffn = 0;
 };
 
-static void make_plan(int B, int Lmax, Plan& p, int planes = 1) {
-    p.B = B; p.Lmax = Lmax;
-    int n = Lmax;
-    for (int i = 0; i < 7; ++i) { n = (n - CK[i]) / CS[i] + 1; p.L[i] = n; }
-    p.T = p.L[6];
-    p.Tp = padded_frames(Lmax);
-    p.Tpv = (p.Tp + 63) & ~63;
-    for (int i = 0; i < 7; ++i) p.R[i] = p.Tp << (6 - i);
+// the workspace offsets of a plan whose geometry (B, Tp, Tpv, R, L[0]) is set: nb = utterances of the per-utterance tables (GroupNorm
+// partials, scale / shift, valid, rows), ntab = ints of a packed batch's slot tables (0: none)
+static void plan_buffers(Plan& p, int planes, int nb, int ntab) {
+    const int B = p.B;
     size_t off = 0;
     auto take = [&](size_t bytes) { size_t o = off; off = (off + bytes + 255) & ~(size_t)255; return o; };
     const size_t M = (size_t)B * p.Tp;
@@ -383,11 +399,36 @@ static void make_plan(int B, int Lmax, Plan& p, int planes = 1) {
         if (off - attn_begin < need) take(need - (off - attn_begin));
     }
     p.nchunk = (p.L[0] + 2047) / 2048;
-    p.o_part = take((size_t)B * p.nchunk * 65 * 8);
-    p.o_ss = take((size_t)B * 512 * 2 * 4);
-    p.o_valid = take((size_t)B * 4);
-    p.o_rows = take((size_t)B * 4);
+    p.o_part = take((size_t)nb * p.nchunk * 65 * 8);
+    p.o_ss = take((size_t)nb * 512 * 2 * 4);
+    p.o_valid = take((size_t)nb * 4);
+    p.o_rows = take((size_t)nb * 4);
+    p.o_pk = ntab > 0 ? take((size_t)ntab * 4) : 0;
     p.total = off;
+}
+
+static void make_plan(int B, int Lmax, Plan& p, int planes = 1) {
+    p.B = B; p.Lmax = Lmax;
+    int n = Lmax;
+    for (int i = 0; i < 7; ++i) { n = (n - CK[i]) / CS[i] + 1; p.L[i] = n; }
+    p.T = p.L[6];
+    p.Tp = padded_frames(Lmax);
+    p.Tpv = (p.Tp + 63) & ~63;
+    for (int i = 0; i < 7; ++i) p.R[i] = p.Tp << (6 - i);
+    plan_buffers(p, planes, B, 0);
+}
+
+// a packed batch (sylber_forward_packed): ONE pseudo-utterance of Ptot frames (a multiple of 64) holding `nclip` slots.  B = 1 and
+// T = Tp = Tpv = Ptot for every launch that sees the whole batch; Lmax = -Ptot is the layout key of ensure_workspace (never a padded
+// layout's).  L[i] = the longest clip's (nmax samples) valid rows of layer i: L[0] sizes the GroupNorm partials, each clip's own
+// counts live in the slot tables.
+static void make_plan_packed(int nclip, int Ptot, int nmax, Plan& p) {
+    p.B = 1; p.Lmax = -Ptot;
+    int n = nmax;
+    for (int i = 0; i < 7; ++i) { n = (n - CK[i]) / CS[i] + 1; p.L[i] = n; }
+    p.T = p.Tp = p.Tpv = Ptot;
+    for (int i = 0; i < 7; ++i) p.R[i] = p.Tp << (6 - i);
+    plan_buffers(p, 1, nclip, 3 * nclip + 2);
 }
 
 static int ensure_workspace(sylber_ctx* c, const Plan& p, hipStream_t s) {
@@ -542,9 +583,15 @@ extern "C" int sylber_get_profile(sylber_t c, const char** names, float* ms, int
 static int forward_f32(sylber_ctx* c, const float* wav_dev, const int32_t* lengths_host, int B, int Lmax, float* hidden_dev,
                        hipStream_t s);
 
+// a packed batch (sylber_forward_packed): its slot tables on the device (Plan::o_pk) and the host-side sizes of its launches
+struct PackedCall {
+    int nclip, total_samples, slot_max, tail_max, total_qb;
+    const int *slot, *frames, *qb, *rows0;     // [nclip + 1], [nclip], [nclip + 1], [nclip]; slot / frames / qb contiguous (attention)
+};
+
 // every kernel launch of the bf16 / fp8 forward, in stream order; nothing else (no allocation, copy or synchronisation),
-// so the sequence can be replayed from a captured hipGraph
-static int forward_launch(sylber_ctx* c, const Plan& p, const float* wav_dev, float* hidden_dev, hipStream_t s) {
+// so the sequence can be replayed from a captured hipGraph.  pk: a packed batch (bf16 / fp16), nullptr for the padded one
+static int forward_launch(sylber_ctx* c, const Plan& p, const float* wav_dev, float* hidden_dev, hipStream_t s, const PackedCall* pk = nullptr) {
     const int B = p.B, Lmax = p.Lmax;
     char* w = c->ws;
     bf16_t* bufA = (bf16_t*)(w + p.o_bufA); bf16_t* bufB = (bf16_t*)(w + p.o_bufB);
@@ -558,10 +605,16 @@ static int forward_launch(sylber_ctx* c, const Plan& p, const float* wav_dev, fl
     const int M = B * p.Tp;
 
     // ---- conv layer 0 + GroupNorm + GELU
+    const bool split = c->precision == SYLBER_SPLIT16;      // hi / lo half planes, erf GELU (fp32-grade decisions)
+    if (pk) {                                               // per slot: each utterance's own statistics, rows and waveform offset
+        RUN("conv0_stats", launch_conv0_stats(wav_dev, pk->nclip, 0, p.L[0], part, p.nchunk, s, pk->rows0, pk->slot));
+        RUN("conv0_finalize", launch_conv0_finalize(part, p.nchunk, c->conv0_w, c->gn_w, c->gn_b, pk->nclip, p.L[0], ss, s, pk->rows0));
+        RUN("conv0_gn_gelu", launch_conv0_packed(wav_dev, pk->nclip, pk->total_samples, pk->slot_max, pk->rows0, pk->slot, c->conv0_w, ss, bufA, c->fmt_conv, s));
+    } else {
     RUN("conv0_stats", launch_conv0_stats(wav_dev, B, Lmax, p.L[0], part, p.nchunk, s, rows0));
     RUN("conv0_finalize", launch_conv0_finalize(part, p.nchunk, c->conv0_w, c->gn_w, c->gn_b, B, p.L[0], ss, s, rows0));
-    const bool split = c->precision == SYLBER_SPLIT16;      // hi / lo half planes, erf GELU (fp32-grade decisions)
     RUN("conv0_gn_gelu", launch_conv0_gn_gelu(wav_dev, B, Lmax, p.L[0], p.R[0], c->conv0_w, ss, bufA, 0, s, c->fmt_conv, p.lo_bufA, c->opt_conv0_valu));
+    }
     const bool aud_c = c->opt_audit16 && c->fmt_conv == FMT_F16, aud_e = c->opt_audit16 && c->fmt == FMT_F16;   // (the audit launches are never captured: graph mode is refused with it)
     if (aud_c && audit16(c, AUD_CONV0, bufA, (long)B * p.R[0], 512, 512, s)) return 1;
     // ---- conv layers 1..6 as implicit GEMM (ping-pong)
@@ -598,9 +651,13 @@ static int forward_launch(sylber_ctx* c, const Plan& p, const float* wav_dev, fl
         g.out0 = xf32; g.ld0 = 768; g.out1 = xpad; g.Tp = p.Tp; g.T = p.T; g.valid = valid; g.xpad_rows = p.Tp + 128; g.fmt = c->fmt;
         g.x_lo = p.lo_ln512; g.w_lo = (long)768 * 512; g.out_lo = p.lo_xpad;
         RUN("gemm_proj", launch_gemm_bf16(EPI_PROJ, g, s));
+        // packed: the projection sees one utterance; the frames behind each clip's own end are zeroed here instead (what valid[b] does)
+        if (pk) RUN("zero_slot_tails", launch_zero_slot_tails(xf32, xpad, pk->slot, pk->frames, pk->nclip, pk->tail_max, s));
         if (aud_e && (audit16(c, AUD_LN512, ln512, M, 512, 512, s) || audit16(c, AUD_XPAD, xpad, (long)B * (p.Tp + 128), 768, 768, s))) return 1;
     }
     // ---- positional conv + residual, encoder LayerNorm
+    if (pk) RUN("posconv", launch_posconv_packed(xpad, c->pos_w, c->pos_b, xf32, pre, pk->nclip, pk->slot_max, pk->slot, pk->frames, s, c->fmt));
+    else
     RUN("posconv", launch_posconv(xpad, c->pos_w, c->pos_b, xf32, pre, B, p.Tp, split ? 2 : 1, s, c->fmt, p.lo_xpad, (long)16 * 128 * 64 * 56));
     // SYLBER_FP8: the FFN runs on MXFP8 operands; the LayerNorm in front of it then emits e4m3 + E8M0 block scales
     // instead of bf16 (into the same buffer), and FFN1 leaves its GELU output as MXFP8 for FFN2
@@ -671,6 +728,8 @@ static int forward_launch(sylber_ctx* c, const Plan& p, const float* wav_dev, fl
             o.X8 = ctx8; o.ldx8 = 768; o.XS = ctx8s; o.xs_rows = Mp; o.W8 = d.woq; o.WS = d.wos; o.ws_rows = 768;
             RUN("gemm_out", launch_gemm_mxfp8(EPI_F32_RESLN, o, s));
         } else {
+        if (pk) RUN("attention", launch_attention_packed(q, k, vt, pk->slot, pk->nclip, pk->total_qb, ctx, p.Tp, s, c->fmt));
+        else
         RUN("attention", launch_attention(q, k, vt, valid, ctx, B, p.T, p.Tp, p.Tpv, c->opt_attn_qw, s, c->fmt, p.lo_qk, p.lo_vt, p.lo_ctx));
         if (aud_e && audit16(c, AUD_CTX, ctx, M, 768, 768, s)) return 1;
         GemmArgs o = {};
@@ -782,6 +841,83 @@ extern "C" int sylber_forward(sylber_t c, const float* wav_dev, const int32_t* l
     return 0;
 }
 
+// Packed batch: B clips of samples_host[b] samples, clip b at sample SYL_SLOT_SAMPLES x offsets[b] of wav_dev (sylber_packed_layout), zero
+// to the end of its slot; the whole batch runs as ONE utterance of offsets[B] frames, and only the GroupNorm statistics, conv0, the
+// zeroing of the frames behind each clip's end, the pos-conv and the attention read the slot tables.  hidden_dev [offsets[B]][768].
+extern "C" int sylber_forward_packed(sylber_t c, const float* wav_dev, const int32_t* samples_host, int32_t B, float* hidden_dev, void* stream) {
+    if (!c || !wav_dev || !samples_host || !hidden_dev) { syl_set_error("sylber_forward_packed", "null argument"); return 1; }
+    if (c->precision != SYLBER_BF16 && c->precision != SYLBER_FP16) {
+        syl_set_error("sylber_forward_packed", "packed batches run in the bf16 and fp16 precisions only"); return 1;
+    }
+    if (c->graph_mode) { syl_set_error("sylber_forward_packed", "not available in graph mode (sylber_set_graph_mode)"); return 1; }
+    if (c->stop_stage != 0 || c->opt_conv0_valu != 0 || c->opt_attn_qw != 0) {
+        syl_set_error("sylber_forward_packed", "not available with a stop stage, SYLBER_OPT_CONV0_VALU or SYLBER_OPT_ATTN_QUERIES_PER_WAVE"); return 1;
+    }
+    std::vector<int32_t> off(B > 0 ? B + 1 : 1), fr(B > 0 ? B : 1);
+    if (sylber_packed_layout(samples_host, B, off.data(), fr.data())) return 1;
+    const int Ptot = off[B];
+    std::vector<int32_t> tab(3 * (size_t)B + 2), rows0(B);
+    int slot_max = 0, tail_max = 0, nmax = 0;
+    tab[2 * B + 1] = 0;
+    for (int b = 0; b < B; ++b) {
+        const int sl = off[b + 1] - off[b];
+        slot_max = sl > slot_max ? sl : slot_max;
+        tail_max = sl - fr[b] > tail_max ? sl - fr[b] : tail_max;
+        rows0[b] = (samples_host[b] - CK[0]) / CS[0] + 1;
+        nmax = samples_host[b] > nmax ? samples_host[b] : nmax;
+        tab[B + 1 + b] = fr[b];
+        tab[2 * B + 2 + b] = tab[2 * B + 1 + b] + (fr[b] + 127) / 128;
+    }
+    for (int b = 0; b <= B; ++b) tab[b] = off[b];
+    hipStream_t s = (hipStream_t)stream;
+    GUARD_DEVICE(c->device);
+    Plan p;
+    make_plan_packed(B, Ptot, nmax, p);
+    char* ws_before = c->ws;
+    if (ensure_workspace(c, p, s)) return 1;
+    if (c->ws != ws_before) graphs_clear(c);
+    int* pkd = (int*)(c->ws + p.o_pk);
+    int* rows_d = (int*)(c->ws + p.o_rows);
+    const int32_t one = Ptot;                           // the projection's valid[0]: no frame of the pseudo-utterance is padding to it
+    if (launch_upload_ints(pkd, tab.data(), 3 * B + 2, 0, s) || launch_upload_ints(rows_d, rows0.data(), B, 0, s) ||
+        launch_upload_ints((int*)(c->ws + p.o_valid), &one, 1, 0, s)) return 1;
+    PackedCall pc = {B, SYL_SLOT_SAMPLES * Ptot, slot_max, tail_max, tab[3 * B + 1], pkd, pkd + B + 1, pkd + 2 * B + 1, rows_d};
+    return forward_launch(c, p, wav_dev, hidden_dev, s, &pc);
+}
+
+// each clip's own rows of a packed forward's hidden states, back to back: one device-to-host copy instead of one per clip.  Up to 64
+// clips per launch, their source row, destination row and frame count as kernel arguments; grid (row blocks, clips), one wave per row
+struct GatherPack { int src[64], dst[64], n[64]; };
+__global__ __launch_bounds__(256) void packed_gather_kernel(const float* __restrict__ in, float* __restrict__ out, GatherPack g) {
+    const int b = blockIdx.y, lane = threadIdx.x & 63;
+    for (int r = blockIdx.x * 4 + (threadIdx.x >> 6); r < g.n[b]; r += gridDim.x * 4) {
+        const float4* s = (const float4*)(in + ((size_t)g.src[b] + r) * SYL_HIDDEN);
+        float4* d = (float4*)(out + ((size_t)g.dst[b] + r) * SYL_HIDDEN);
+#pragma unroll
+        for (int i = 0; i < 3; ++i) d[lane + 64 * i] = s[lane + 64 * i];
+    }
+}
+extern "C" int sylber_packed_gather(const float* hidden_dev, const int32_t* samples_host, int32_t B, float* out_dev, void* stream) {
+    if (!hidden_dev || !samples_host || !out_dev) { syl_set_error("sylber_packed_gather", "null argument"); return 1; }
+    std::vector<int32_t> off(B > 0 ? B + 1 : 1), fr(B > 0 ? B : 1);
+    if (sylber_packed_layout(samples_host, B, off.data(), fr.data())) return 1;
+    int dst = 0;
+    for (int b0 = 0; b0 < B; b0 += 64) {
+        GatherPack g;
+        const int k = B - b0 < 64 ? B - b0 : 64;
+        int nmax = 1;
+        for (int i = 0; i < k; ++i) {
+            g.src[i] = off[b0 + i]; g.dst[i] = dst; g.n[i] = fr[b0 + i];
+            dst += fr[b0 + i];
+            nmax = fr[b0 + i] > nmax ? fr[b0 + i] : nmax;
+        }
+        const int gx = (nmax + 15) / 16;               // ~4 rows per wave
+        hipLaunchKernelGGL(packed_gather_kernel, dim3(gx, k), dim3(256), 0, (hipStream_t)stream, hidden_dev, out_dev, g);
+    }
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
 // ------------------------------------------------------------------------------------------------
 // fp32 parity mode: same sequence, every tensor fp32, own workspace plan
 static int forward_f32(sylber_ctx* c, const float* wav_dev, const int32_t* lengths_host, int B, int Lmax, float* hidden_dev,
@@ -876,14 +1012,16 @@ static int forward_f32(sylber_ctx* c, const float* wav_dev, const int32_t* lengt
 
 // frames_host: nullptr (sylber_segment) or each row's own frame count (sylber_segment_frames), which travels to the device as kernel
 // arguments into the slots behind the wide path's slab
+// row0_host (sylber_segment_packed, needs frames_host): row b's first frame is hidden row row0_host[b]
 static int segment_call(const char* what, sylber_t c, const float* hidden_dev, const int32_t* frames_host, int32_t B, int32_t T, int32_t D,
-                        float norm_thr, float merge_thr, int64_t* seg_dev, int32_t* nseg_dev, float* feat_dev, void* stream) {
+                        float norm_thr, float merge_thr, int64_t* seg_dev, int32_t* nseg_dev, float* feat_dev, void* stream,
+                        const int32_t* row0_host = nullptr) {
     if (!c || !hidden_dev || !seg_dev || !nseg_dev) { syl_set_error(what, "null argument"); return 1; }
     hipStream_t s = (hipStream_t)stream;
     GUARD_DEVICE(c->device);
     // per-utterance slab of the wide path (frame norms, slot table, bookkeeping of long runs; grow-only)
     const size_t slabs = segment_scratch_floats(B, T, D);
-    const size_t need = slabs + (frames_host ? (((size_t)B + 63) & ~(size_t)63) : 0);
+    const size_t need = slabs + (frames_host ? (((size_t)B + 63) & ~(size_t)63) * (row0_host ? 2 : 1) : 0);
     if (need > c->seg_scratch_floats) {
         HIP_TRY(hipStreamSynchronize(s));
         if (c->seg_scratch) HIP_TRY(hipFree(c->seg_scratch));
@@ -892,12 +1030,18 @@ static int segment_call(const char* what, sylber_t c, const float* hidden_dev, c
         c->seg_scratch_floats = need;
     }
     int* frames_dev = nullptr;
+    int* row0_dev = nullptr;
     if (frames_host) {
         frames_dev = (int*)(c->seg_scratch + slabs);
         if (launch_upload_ints(frames_dev, frames_host, B, 0, s)) return 1;
     }
+    if (row0_host) {
+        row0_dev = frames_dev + (((size_t)B + 63) & ~(size_t)63);
+        if (launch_upload_ints(row0_dev, row0_host, B, 0, s)) return 1;
+    }
     ProfScope ps(c, s, "segment");
-    return launch_segment(hidden_dev, B, T, D, norm_thr, merge_thr, seg_dev, nseg_dev, feat_dev, c->seg_scratch, s, c->opt_segment, frames_dev);
+    return launch_segment(hidden_dev, B, T, D, norm_thr, merge_thr, seg_dev, nseg_dev, feat_dev, c->seg_scratch, s, c->opt_segment, frames_dev,
+                          row0_dev);
 }
 
 extern "C" int sylber_segment(sylber_t c, const float* hidden_dev, int32_t B, int32_t T, int32_t D, float norm_thr,
@@ -915,6 +1059,23 @@ extern "C" int sylber_segment_frames(sylber_t c, const float* hidden_dev, const 
     for (int b = 0; b < B; ++b)
         if (frames_host[b] < 1 || frames_host[b] > T) { syl_set_error("sylber_segment_frames", "frames must be in [1, T]"); return 1; }
     return segment_call("sylber_segment_frames", c, hidden_dev, frames_host, B, T, D, norm_thr, merge_thr, seg_dev, nseg_dev, feat_dev, stream);
+}
+
+// boundary detection of a packed batch (sylber_forward_packed's hidden states): clip b is segmented and pooled as its own frames
+// hidden[offsets[b], offsets[b] + frames[b]) alone; tables relative to the clip's start, kcap = max frames[b] slots per clip
+extern "C" int sylber_segment_packed(sylber_t c, const float* hidden_dev, const int32_t* samples_host, int32_t B, float norm_thr, float merge_thr,
+                                     int64_t* seg_dev, int32_t* nseg_dev, float* feat_dev, void* stream) {
+    if (!samples_host) { syl_set_error("sylber_segment_packed", "null argument"); return 1; }
+    if (c && c->opt_segment < 0) {
+        syl_set_error("sylber_segment_packed", "not available with SYLBER_OPT_SEGMENT = -1 (the one-workgroup-per-utterance kernel has no per-row bound)");
+        return 1;
+    }
+    std::vector<int32_t> off(B > 0 ? B + 1 : 1), fr(B > 0 ? B : 1);
+    if (sylber_packed_layout(samples_host, B, off.data(), fr.data())) return 1;
+    int kcap = 0;
+    for (int b = 0; b < B; ++b) kcap = fr[b] > kcap ? fr[b] : kcap;
+    return segment_call("sylber_segment_packed", c, hidden_dev, fr.data(), B, kcap, SYL_HIDDEN, norm_thr, merge_thr, seg_dev, nseg_dev, feat_dev,
+                        stream, off.data());
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -529,27 +529,56 @@ __device__ __forceinline__ i32x4a_t rsrc_words_a(const void* base) {
 }
 
 #define ATA_SLOT 16384
-template <bool F8, int FMT, int VAR = 0>
+// PK (packed layout, launch_attention_packed): q / k [H][Tp][64] and V^T [H][64][Tpv] of ONE pseudo-utterance of Tp = Tpv frames that
+// holds `nclip` utterances in slots; pk = [slot offsets (nclip + 1) | frames (nclip) | prefix of 128-query blocks (nclip + 1)].  Workgroup
+// -> (utterance, head, query block) through the prefix table; Q, K and V^T are based at the utterance's slot, the key bound is its own
+// frame count, and the context rows [frames, slot end) are written as zeros.  The generated key loop sees the same operands as for a
+// lone utterance: its frames' keys in tiles of 64 from the slot start (slots are multiples of 64 frames), V^T's row pitch Tpv.
+template <bool F8, int FMT, int VAR = 0, bool PK = false>
 __global__ __launch_bounds__(256, 3) void attention_asm_kernel(const bf16_t* __restrict__ Q, const bf16_t* __restrict__ K,
                                                                const bf16_t* __restrict__ Vt, const int* __restrict__ valid,
                                                                bf16_t* __restrict__ ctx, int T, int Tp, int Tpv,
-                                                               uint8_t* __restrict__ ctx_scale, long scale_rows) {
+                                                               uint8_t* __restrict__ ctx_scale, long scale_rows,
+                                                               const int* __restrict__ pk, int nclip) {
     static_assert(FMT == FMT_BF16 || FMT == FMT_F16, "16-bit single-plane formats");
     __shared__ __attribute__((aligned(1024))) char smem[3 * ATA_SLOT];
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const int nqb = (T + 127) / 128;
     const int vid = xcd_remap(blockIdx.x, gridDim.x);
-    const int b = vid / (nqb * SYL_HEADS);
-    const int head = (vid / nqb) % SYL_HEADS;
-    const int q0 = (vid % nqb) * 128 + wave * 32;
+    int b, head, q0, nvalid;
+    const bf16_t *Qb, *Kb, *Vb;
+    if constexpr (PK) {
+        const int* qbp = pk + 2 * nclip + 1;
+        const int blk = vid / SYL_HEADS;               // (utterance b owns workgroups [12 qbp[b], 12 qbp[b + 1]))
+        int lo = 0, hi = nclip - 1;                    // the last b with qbp[b] <= blk
+        while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (qbp[mid] <= blk) lo = mid; else hi = mid - 1; }
+        b = __builtin_amdgcn_readfirstlane(lo);
+        const int nqb = qbp[b + 1] - qbp[b], local = vid - SYL_HEADS * qbp[b];
+        head = local / nqb;
+        q0 = (local % nqb) * 128 + wave * 32;
+        const int s0 = pk[b];
+        nvalid = __builtin_amdgcn_readfirstlane(pk[nclip + 1 + b]);
+        T = nvalid;
+        const size_t hb = (size_t)head * Tp + s0;      // this utterance's first row in head `head`
+        Qb = Q + hb * 64;
+        Kb = K + hb * 64;
+        Vb = Vt + (size_t)head * 64 * Tpv + s0;
+        ctx += (size_t)s0 * SYL_HIDDEN;
+        Tp = pk[b + 1] - s0;                           // from here on: the slot's frames (query clamp, zeroed context rows)
+        b = 0;
+    } else {
+        const int nqb = (T + 127) / 128;
+        b = vid / (nqb * SYL_HEADS);
+        head = (vid / nqb) % SYL_HEADS;
+        q0 = (vid % nqb) * 128 + wave * 32;
+        nvalid = valid ? valid[b] : T;
+        nvalid = nvalid < T ? nvalid : T;
+        nvalid = __builtin_amdgcn_readfirstlane(nvalid);
+        const size_t bh = (size_t)b * SYL_HEADS + head;
+        Qb = Q + bh * Tp * 64;
+        Kb = K + bh * Tp * 64;
+        Vb = Vt + bh * 64 * Tpv;
+    }
     const int ql = lane & 31, h = lane >> 5;
-    int nvalid = valid ? valid[b] : T;
-    nvalid = nvalid < T ? nvalid : T;
-    nvalid = __builtin_amdgcn_readfirstlane(nvalid);
-    const size_t bh = (size_t)b * SYL_HEADS + head;
-    const bf16_t* Qb = Q + bh * Tp * 64;
-    const bf16_t* Kb = K + bh * Tp * 64;
-    const bf16_t* Vb = Vt + bh * 64 * Tpv;
     f32x16_t oacc[2];
     float lsum = 0.f;
     const int nt = __builtin_amdgcn_readfirstlane((nvalid + 63) / 64);
@@ -643,7 +672,7 @@ static int launch_attention_any(const bf16_t* q, const bf16_t* k, const bf16_t* 
 #ifdef SYLBER_GEMM_ASM_EXPERIMENTS
     if (force_qw >= 101 && force_qw <= 109) {       // knock-out variants of the key loop (timing only, results wrong): tools/attn_bench.py
         const dim3 grid_a(((T + 127) / 128) * SYL_HEADS * B);
-#define ATA_VAR(N) case 100 + N: hipLaunchKernelGGL((attention_asm_kernel<false, FMT_BF16, N>), grid_a, dim3(256), 0, s, q, k, vt, valid, c, T, Tp, Tpv, nullptr, 0L); break;
+#define ATA_VAR(N) case 100 + N: hipLaunchKernelGGL((attention_asm_kernel<false, FMT_BF16, N>), grid_a, dim3(256), 0, s, q, k, vt, valid, c, T, Tp, Tpv, nullptr, 0L, nullptr, 0); break;
         switch (force_qw) { ATA_VAR(1) ATA_VAR(2) ATA_VAR(3) ATA_VAR(4) ATA_VAR(5) ATA_VAR(6) ATA_VAR(7) ATA_VAR(8) ATA_VAR(9) }
 #undef ATA_VAR
         HIP_TRY(hipGetLastError());
@@ -654,9 +683,9 @@ static int launch_attention_any(const bf16_t* q, const bf16_t* k, const bf16_t* 
         // default since round 5: the hand-scheduled key loop (attention_asm_kernel); 32 / 64 queries per wave select the
         // compiler-scheduled kernels, kept as its reference
         const dim3 grid_a(((T + 127) / 128) * SYL_HEADS * B);
-        if (ctx_scale) hipLaunchKernelGGL((attention_asm_kernel<true, FMT_BF16>), grid_a, dim3(256), 0, s, q, k, vt, valid, c, T, Tp, Tpv, ctx_scale, scale_rows);
-        else if (fmt == FMT_F16) hipLaunchKernelGGL((attention_asm_kernel<false, FMT_F16>), grid_a, dim3(256), 0, s, q, k, vt, valid, c, T, Tp, Tpv, nullptr, 0L);
-        else hipLaunchKernelGGL((attention_asm_kernel<false, FMT_BF16>), grid_a, dim3(256), 0, s, q, k, vt, valid, c, T, Tp, Tpv, nullptr, 0L);
+        if (ctx_scale) hipLaunchKernelGGL((attention_asm_kernel<true, FMT_BF16>), grid_a, dim3(256), 0, s, q, k, vt, valid, c, T, Tp, Tpv, ctx_scale, scale_rows, nullptr, 0);
+        else if (fmt == FMT_F16) hipLaunchKernelGGL((attention_asm_kernel<false, FMT_F16>), grid_a, dim3(256), 0, s, q, k, vt, valid, c, T, Tp, Tpv, nullptr, 0L, nullptr, 0);
+        else hipLaunchKernelGGL((attention_asm_kernel<false, FMT_BF16>), grid_a, dim3(256), 0, s, q, k, vt, valid, c, T, Tp, Tpv, nullptr, 0L, nullptr, 0);
         HIP_TRY(hipGetLastError());
         return 0;
     }
@@ -679,6 +708,18 @@ static int launch_attention_any(const bf16_t* q, const bf16_t* k, const bf16_t* 
         if (qw == 2) hipLaunchKernelGGL((attention_bf16_kernel<2, false>), grid, dim3(256), AT_LDS, s, q, k, vt, valid, c, T, Tp, Tpv, nullptr, 0L, 0L, 0L, 0L);
         else hipLaunchKernelGGL((attention_bf16_kernel<1, false>), grid, dim3(256), AT_LDS, s, q, k, vt, valid, c, T, Tp, Tpv, nullptr, 0L, 0L, 0L, 0L);
     }
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// packed layout (see attention_asm_kernel's PK): total_qb = the sum of every utterance's ceil(frames / 128); bf16 / fp16
+int launch_attention_packed(const bf16_t* q, const bf16_t* k, const bf16_t* vt, const int* pk, int nclip, int total_qb, bf16_t* ctx,
+                            int Ptot, hipStream_t s, int fmt) {
+    if (Ptot % 64 != 0) { syl_set_error("launch_attention_packed", "slots must be whole 64-key tiles"); return 1; }
+    const dim3 grid(total_qb * SYL_HEADS);
+    if (fmt == FMT_F16) hipLaunchKernelGGL((attention_asm_kernel<false, FMT_F16, 0, true>), grid, dim3(256), 0, s, q, k, vt, nullptr, ctx, 0, Ptot, Ptot, nullptr, 0L, pk, nclip);
+    else if (fmt == FMT_BF16) hipLaunchKernelGGL((attention_asm_kernel<false, FMT_BF16, 0, true>), grid, dim3(256), 0, s, q, k, vt, nullptr, ctx, 0, Ptot, Ptot, nullptr, 0L, pk, nclip);
+    else { syl_set_error("launch_attention_packed", "bf16 / fp16 only"); return 1; }
     HIP_TRY(hipGetLastError());
     return 0;
 }

@@ -12,6 +12,7 @@ typedef unsigned short u16x4_t __attribute__((ext_vector_type(4)));
 
 #define SYL_HIDDEN 768
 #define SYL_CONV 512
+#define SYL_SLOT_SAMPLES 320    // waveform samples per frame of a packed batch's slot (the conv stack's total stride)
 #define SYL_HEADS 12
 #define SYL_HDIM 64
 #define SYL_FFN 3072

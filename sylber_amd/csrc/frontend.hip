@@ -22,10 +22,12 @@
 // rows: optional per-utterance conv0 frame counts (SYLBER_OPT_PER_UTTERANCE), nullptr = every row has the padded L0.  A row with
 // its own count n is chunked exactly as a call whose padded length is n would chunk it (ceil(n / 2048) chunks of ceil(n / nchunk_n)
 // frames), so its fp64 sums happen in the same order whatever the batch's L0 is; chunks past its own are written as exact zeros.
+// slot: optional packed layout (sylber_forward_packed, needs rows): utterance b's waveform starts at sample 320 * slot[b], not at b * Lmax.
 __global__ __launch_bounds__(256) void conv0_stats_kernel(const float* __restrict__ wav, int Lmax, int L0, int chunk,
-                                                          double* __restrict__ partials, int nchunk, const int* __restrict__ rows) {
+                                                          double* __restrict__ partials, int nchunk, const int* __restrict__ rows,
+                                                          const int* __restrict__ slot) {
     const int b = blockIdx.y, ck = blockIdx.x;
-    const float* x = wav + (size_t)b * Lmax;
+    const float* x = wav + (slot ? (size_t)SYL_SLOT_SAMPLES * slot[b] : (size_t)b * Lmax);
     if (rows) {
         L0 = rows[b];
         const int nck = (L0 + 2047) / 2048;
@@ -200,10 +202,13 @@ __global__ __launch_bounds__(256) void conv0_gn_gelu_kernel(const float* __restr
 #define C0M_LDS (C0M_WFR + 512 * 4 + (C0_ROWS * 5 + 16) * 4 + 4 * C0M_STG)
 // NOSTORE (experiments build, SYLBER_OPT_CONV0_VALU = 2): the rows are produced into the LDS staging region and never leave it --
 // the cost of conv0 as a PRODUCER inside another kernel (profiles/r05_conv0_fusion.md); results wrong by construction
+// rows / slot (packed layout, sylber_forward_packed; nullptr otherwise): utterance b has its own conv0 frames rows[b] and a slot of
+// R0_b = 64 (slot[b + 1] - slot[b]) rows at row 64 slot[b], its waveform at sample 320 slot[b]; Lmax is then the packed buffer's total
+// samples.  The last rows of a slot read up to the first samples of the next slot: they are at or past rows[b] and written as zeros.
 template <int FMT, bool NOSTORE = false>
 __global__ __launch_bounds__(256, 2) void conv0_mfma_kernel(const float* __restrict__ wav, int Lmax, int L0, int R0,
                                                             const float* __restrict__ w0, const float* __restrict__ scale_shift,
-                                                            bf16_t* __restrict__ out) {
+                                                            bf16_t* __restrict__ out, const int* __restrict__ rows, const int* __restrict__ slot) {
     extern __shared__ __attribute__((aligned(256))) char smem[];
     char* wfr = smem;
     float* shf = (float*)(smem + C0M_WFR);
@@ -212,6 +217,15 @@ __global__ __launch_bounds__(256, 2) void conv0_mfma_kernel(const float* __restr
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     char* stg = smem + C0M_WFR + 512 * 4 + (C0_ROWS * 5 + 16) * 4 + wave * C0M_STG;
     const float* x = wav + (size_t)b * Lmax;
+    size_t obase = (size_t)b * R0;                    // first output row of this utterance
+    if (slot) {
+        const int s0 = slot[b];
+        x = wav + (size_t)SYL_SLOT_SAMPLES * s0;
+        Lmax -= SYL_SLOT_SAMPLES * s0;                // samples from the slot's start to the end of the packed buffer
+        L0 = rows[b];
+        R0 = 64 * (slot[b + 1] - s0);
+        obase = (size_t)64 * s0;
+    }
     // weight fragments of this utterance: entry (blk, ln): channel c = 32 blk + (ln & 31), taps k = 8 (ln >> 5) .. + 7
     for (int e = tid; e < 16 * 64; e += 256) {
         const int blk = e >> 6, ln = e & 63;
@@ -293,16 +307,16 @@ __global__ __launch_bounds__(256, 2) void conv0_mfma_kernel(const float* __restr
                 const u32x4_t v = *(const u32x4_t*)(stg + r * (256 + 16) + ch * 16);
                 const int l = l0 + r;
                 if constexpr (NOSTORE) { if (v.x == 0x7fc1dead && l < 0) out[0] = (bf16_t)v.y; }      // (keeps the staging reads alive)
-                else if (l < R0) __builtin_nontemporal_store(v, (u32x4_t*)(out + ((size_t)b * R0 + l) * SYL_CONV + q4 * 128 + ch * 8));
+                else if (l < R0) __builtin_nontemporal_store(v, (u32x4_t*)(out + (obase + l) * SYL_CONV + q4 * 128 + ch * 8));
             }
         }
     }
     }
 }
 
-int launch_conv0_stats(const float* wav, int B, int Lmax, int L0, double* partials, int nchunk, hipStream_t s, const int* rows) {
+int launch_conv0_stats(const float* wav, int B, int Lmax, int L0, double* partials, int nchunk, hipStream_t s, const int* rows, const int* slot) {
     const int chunk = (L0 + nchunk - 1) / nchunk;
-    hipLaunchKernelGGL(conv0_stats_kernel, dim3(nchunk, B), dim3(256), 0, s, wav, Lmax, L0, chunk, partials, nchunk, rows);
+    hipLaunchKernelGGL(conv0_stats_kernel, dim3(nchunk, B), dim3(256), 0, s, wav, Lmax, L0, chunk, partials, nchunk, rows, slot);
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -338,12 +352,56 @@ int launch_conv0_gn_gelu(const float* wav, int B, int Lmax, int L0, int R0, cons
         if (valu16 == 2) {
             static PerDeviceOnce once2;
             if (once2.need()) HIP_TRY(hipFuncSetAttribute((const void*)conv0_mfma_kernel<FMT_BF16, true>, hipFuncAttributeMaxDynamicSharedMemorySize, C0M_LDS));
-            hipLaunchKernelGGL((conv0_mfma_kernel<FMT_BF16, true>), pgrid, dim3(256), C0M_LDS, s, wav, Lmax, L0, R0, w0, scale_shift, (bf16_t*)out);
+            hipLaunchKernelGGL((conv0_mfma_kernel<FMT_BF16, true>), pgrid, dim3(256), C0M_LDS, s, wav, Lmax, L0, R0, w0, scale_shift, (bf16_t*)out, nullptr, nullptr);
         } else
 #endif
-        if (fmt == FMT_F16) hipLaunchKernelGGL((conv0_mfma_kernel<FMT_F16>), pgrid, dim3(256), C0M_LDS, s, wav, Lmax, L0, R0, w0, scale_shift, (bf16_t*)out);
-        else hipLaunchKernelGGL((conv0_mfma_kernel<FMT_BF16>), pgrid, dim3(256), C0M_LDS, s, wav, Lmax, L0, R0, w0, scale_shift, (bf16_t*)out);
+        if (fmt == FMT_F16) hipLaunchKernelGGL((conv0_mfma_kernel<FMT_F16>), pgrid, dim3(256), C0M_LDS, s, wav, Lmax, L0, R0, w0, scale_shift, (bf16_t*)out, nullptr, nullptr);
+        else hipLaunchKernelGGL((conv0_mfma_kernel<FMT_BF16>), pgrid, dim3(256), C0M_LDS, s, wav, Lmax, L0, R0, w0, scale_shift, (bf16_t*)out, nullptr, nullptr);
     }
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// packed layout (sylber_forward_packed): the MFMA kernel above per slot, grid y = utterance; workgroups past a short slot's rows exit
+int launch_conv0_packed(const float* wav, int B, int total_samples, int slot_max, const int* rows, const int* slot, const float* w0,
+                        const float* scale_shift, bf16_t* out, int fmt, hipStream_t s) {
+    if (fmt != FMT_F16 && fmt != FMT_BF16) { syl_set_error("launch_conv0_packed", "bf16 / fp16 only"); return 1; }
+    static PerDeviceOnce once;
+    if (once.need()) {
+        HIP_TRY(hipFuncSetAttribute((const void*)conv0_mfma_kernel<FMT_BF16>, hipFuncAttributeMaxDynamicSharedMemorySize, C0M_LDS));
+        HIP_TRY(hipFuncSetAttribute((const void*)conv0_mfma_kernel<FMT_F16>, hipFuncAttributeMaxDynamicSharedMemorySize, C0M_LDS));
+    }
+    const int nblk = (64 * slot_max + C0_ROWS - 1) / C0_ROWS;
+    int gx = (1024 + B - 1) / B;
+    gx = gx < 1 ? 1 : (gx > nblk ? nblk : gx);
+    const dim3 pgrid(gx, B);
+    if (fmt == FMT_F16) hipLaunchKernelGGL((conv0_mfma_kernel<FMT_F16>), pgrid, dim3(256), C0M_LDS, s, wav, total_samples, 0, 0, w0, scale_shift, out, rows, slot);
+    else hipLaunchKernelGGL((conv0_mfma_kernel<FMT_BF16>), pgrid, dim3(256), C0M_LDS, s, wav, total_samples, 0, 0, w0, scale_shift, out, rows, slot);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// packed layout: frames [slot[b] + frames[b], slot[b + 1]) of the fp32 residual x [rows][768] and of the 16-bit pos-conv input
+// (row 64 + frame of xpad) become +0 -- stores, not a product, so a non-finite value there cannot survive.  Grid (row blocks, B).
+__global__ __launch_bounds__(256) void zero_slot_tails_kernel(float* __restrict__ x, bf16_t* __restrict__ xpad, const int* __restrict__ slot,
+                                                              const int* __restrict__ frames) {
+    const int b = blockIdx.y;
+    const int r0 = slot[b] + frames[b], r1 = slot[b + 1];
+    for (int r = r0 + blockIdx.x * 4 + (threadIdx.x >> 6); r < r1; r += gridDim.x * 4) {
+        const int lane = threadIdx.x & 63;
+        float4* xr = (float4*)(x + (size_t)r * SYL_HIDDEN);
+        uint2* pr = (uint2*)(xpad + (size_t)(r + 64) * SYL_HIDDEN);
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            xr[lane + 64 * i] = make_float4(0.f, 0.f, 0.f, 0.f);
+            pr[lane + 64 * i] = make_uint2(0u, 0u);
+        }
+    }
+}
+int launch_zero_slot_tails(float* x, bf16_t* xpad, const int* slot, const int* frames, int B, int tail_max, hipStream_t s) {
+    int gx = (tail_max + 3) / 4;
+    gx = gx < 1 ? 1 : (gx > 16 ? 16 : gx);
+    hipLaunchKernelGGL(zero_slot_tails_kernel, dim3(gx, B), dim3(256), 0, s, x, xpad, slot, frames);
     HIP_TRY(hipGetLastError());
     return 0;
 }

@@ -113,13 +113,29 @@ int launch_gemm_f32(const GemmArgsF32& a, hipStream_t s);
 // ------------------------------------------------------------------------------------------------
 // rows (device, [B], nullable): per-utterance conv0 frame counts for the GroupNorm statistics (SYLBER_OPT_PER_UTTERANCE);
 // nullptr = every utterance over the padded L0 (the reference's behaviour)
-int launch_conv0_stats(const float* wav, int B, int Lmax, int L0, double* partials, int nchunk, hipStream_t s, const int* rows = nullptr);
+// slot (device, [B + 1], nullable, needs rows): packed layout -- utterance b's waveform starts at sample SYL_SLOT_SAMPLES x slot[b]
+int launch_conv0_stats(const float* wav, int B, int Lmax, int L0, double* partials, int nchunk, hipStream_t s, const int* rows = nullptr,
+                       const int* slot = nullptr);
 int launch_conv0_finalize(const double* partials, int nchunk, const float* w0, const float* gn_w, const float* gn_b,
                           int B, int L0, float* scale_shift, hipStream_t s, const int* rows = nullptr);
 // out: [B][R0][512] (bf16 or f32); rows l >= L0 are written as zeros
 // fmt FMT_SPLIT: erf GELU, hi halves at out, lo halves at out + out_lo (element offset)
 int launch_conv0_gn_gelu(const float* wav, int B, int Lmax, int L0, int R0, const float* w0,
                          const float* scale_shift, void* out, int out_f32, hipStream_t s, int fmt = 0, long out_lo = 0, int valu16 = 0);   // valu16: 16-bit modes on the VALU kernel (A/B)
+// Packed batches (sylber_forward_packed): B utterances in slots of one pseudo-utterance.  slot [B + 1] = frame offsets (prefix of the
+// slot sizes, multiples of 64), frames [B] = each utterance's own frame count, rows [B] = its own conv0 frames; device tables.
+// conv0 + GroupNorm + GELU per slot: out rows [64 slot[b], 64 slot[b + 1]); rows at or past rows[b] are zeros (bf16 / fp16)
+int launch_conv0_packed(const float* wav, int B, int total_samples, int slot_max, const int* rows, const int* slot, const float* w0,
+                        const float* scale_shift, bf16_t* out, int fmt, hipStream_t s);
+// frames [slot[b] + frames[b], slot[b + 1]) of the fp32 residual x [rows][768] and of xpad (row 64 + frame) become +0; tail_max = the
+// longest such tail
+int launch_zero_slot_tails(float* x, bf16_t* xpad, const int* slot, const int* frames, int B, int tail_max, hipStream_t s);
+// pos-conv per slot: frames outside [0, frames[b]) of utterance b read as zeros; out / x_f32 [slot[B]][768]
+int launch_posconv_packed(const bf16_t* xpad, const bf16_t* wpk, const float* bias, const float* x_f32, float* out, int B, int slot_max,
+                          const int* slot, const int* frames, hipStream_t s, int fmt);
+// attention per slot: pk = [slot (B + 1) | frames (B) | prefix of ceil(frames / 128) (B + 1)], Ptot = slot[B] (a multiple of 64)
+int launch_attention_packed(const bf16_t* q, const bf16_t* k, const bf16_t* vt, const int* pk, int nclip, int total_qb, bf16_t* ctx,
+                            int Ptot, hipStream_t s, int fmt);
 
 // ------------------------------------------------------------------------------------------------
 // LayerNorm over the last dim (512 or 768), eps 1e-5, one wave per row
@@ -179,7 +195,9 @@ int launch_posconv_f32(const float* xpad, const float* w, const float* bias, con
 // frames (device, [B], nullable): row b is segmented and pooled over its first frames[b] frames only (1 <= frames[b] <= T; the row
 // pitch stays T); nullptr = T frames for every row.  Wide path only: mode -1 with frames is refused.
 int launch_segment(const float* hidden, int B, int T, int D, float norm_thr, float merge_thr, int64_t* seg, int* nseg,
-                   float* feat, float* scratch, hipStream_t s, int mode = 0, const int* frames = nullptr);
+                   float* feat, float* scratch, hipStream_t s, int mode = 0, const int* frames = nullptr, const int* row0 = nullptr);
+// row0 (device, [B], nullable, needs frames): row b's frame t is hidden row row0[b] + t (packed layout; T is then only the pitch of the
+// outputs and of the slab, >= every frames[b])
 size_t segment_scratch_floats(int B, int T, int D);
 
 // misc elementwise

@@ -33,7 +33,8 @@ __device__ __forceinline__ void glds16p(__amdgpu_buffer_rsrc_t rs, int voff, int
 template <int ACT, int FMT>
 __global__ __launch_bounds__(512, 4) void posconv_bf16_kernel(const bf16_t* __restrict__ xpad, const bf16_t* __restrict__ wpk,
                                                               const float* __restrict__ bias, const float* __restrict__ x_f32,
-                                                              float* __restrict__ out, int Tp, long x_lo, long w_lo) {
+                                                              float* __restrict__ out, int Tp, long x_lo, long w_lo,
+                                                              const int* __restrict__ slot, const int* __restrict__ frames) {
     extern __shared__ __attribute__((aligned(256))) char smem[];
     char* xwin = smem;
     char* wring = smem + PC_XWIN;
@@ -41,6 +42,14 @@ __global__ __launch_bounds__(512, 4) void posconv_bf16_kernel(const bf16_t* __re
     const int ql = lane & 31, h = lane >> 5;
     const int t0 = blockIdx.x * PC_BM, g = blockIdx.y, b = blockIdx.z;
     const int rows_per_b = Tp + 128;
+    // packed layout (sylber_forward_packed; slot / frames nullptr otherwise): utterance b owns frames [slot[b], slot[b + 1]) of ONE
+    // xpad pseudo-utterance (64 halo rows in front); frames outside [0, frames[b]) of it are loaded as zeros, exactly what a lone
+    // utterance's halo and zeroed tail hold, so a neighbour's frames never enter its window
+    int s0 = 0, Tb = 0, Tpb = Tp;
+    if (slot) {
+        s0 = slot[b]; Tb = frames[b]; Tpb = slot[b + 1] - s0;
+        if (t0 >= Tpb) return;                         // (uniform: the whole workgroup)
+    }
 
     f32x16_t acc[2];
 #pragma unroll
@@ -54,14 +63,20 @@ __global__ __launch_bounds__(512, 4) void posconv_bf16_kernel(const bf16_t* __re
     if (pass > 0) __syncthreads();                     // the previous pass's window and ring reads are done
     // ---- stage the x window: rows t0 .. t0+382 of xpad[b], channels g*48 .. +47
     {
-        const bf16_t* xb = xpad + (pass == 1 ? x_lo : 0L) + (size_t)b * rows_per_b * SYL_HIDDEN + g * SYL_POSC;
+        const bf16_t* xb = xpad + (pass == 1 ? x_lo : 0L) + (slot ? (size_t)s0 : (size_t)b * rows_per_b) * SYL_HIDDEN + g * SYL_POSC;
 #pragma unroll
         for (int i = 0; i < 5; ++i) {
             const int idx = tid + 512 * i;         // 384 rows x 6 16-byte chunks = 2304 (4.5 per thread)
             if (idx < 384 * 6) {
                 const int r = idx / 6, ch = idx - r * 6;
-                int row = t0 + r; row = row < rows_per_b ? row : rows_per_b - 1;
-                const uint4 v = *(const uint4*)(xb + (size_t)row * SYL_HIDDEN + ch * 8);
+                uint4 v;
+                if (slot) {
+                    const int f = t0 + r - 64;         // frame of the utterance this window row holds
+                    v = (f >= 0 && f < Tb) ? *(const uint4*)(xb + (size_t)(f + 64) * SYL_HIDDEN + ch * 8) : make_uint4(0u, 0u, 0u, 0u);
+                } else {
+                    int row = t0 + r; row = row < rows_per_b ? row : rows_per_b - 1;
+                    v = *(const uint4*)(xb + (size_t)row * SYL_HIDDEN + ch * 8);
+                }
                 *(uint4*)(xwin + r * PC_XROW + ch * 16) = v;
             }
         }
@@ -105,8 +120,8 @@ __global__ __launch_bounds__(512, 4) void posconv_bf16_kernel(const bf16_t* __re
     }   // pass
     // ---- epilogue: out = x + gelu(conv + bias); lane owns frame t, runs of 4 output channels
     const int t = t0 + wave * 32 + ql;
-    if (t < Tp) {
-        const size_t m = (size_t)b * Tp + t;
+    if (t < Tpb) {
+        const size_t m = slot ? (size_t)s0 + t : (size_t)b * Tp + t;
 #pragma unroll
         for (int nf = 0; nf < 2; ++nf)
 #pragma unroll
@@ -126,9 +141,7 @@ __global__ __launch_bounds__(512, 4) void posconv_bf16_kernel(const bf16_t* __re
     }
 }
 
-int launch_posconv(const bf16_t* xpad, const bf16_t* wpk, const float* bias, const float* x_f32, float* out, int B, int Tp,
-                   int act, hipStream_t s, int fmt, long x_lo, long w_lo) {
-    dim3 grid((Tp + PC_BM - 1) / PC_BM, SYL_POSG, B);
+static int posconv_attrs() {
     static PerDeviceOnce attr_once;
     if (attr_once.need()) {
         HIP_TRY(hipFuncSetAttribute((const void*)posconv_bf16_kernel<1, FMT_BF16>, hipFuncAttributeMaxDynamicSharedMemorySize, PC_LDS));
@@ -136,15 +149,35 @@ int launch_posconv(const bf16_t* xpad, const bf16_t* wpk, const float* bias, con
         HIP_TRY(hipFuncSetAttribute((const void*)posconv_bf16_kernel<1, FMT_F16>, hipFuncAttributeMaxDynamicSharedMemorySize, PC_LDS));
         HIP_TRY(hipFuncSetAttribute((const void*)posconv_bf16_kernel<2, FMT_SPLIT>, hipFuncAttributeMaxDynamicSharedMemorySize, PC_LDS));
     }
+    return 0;
+}
+
+int launch_posconv(const bf16_t* xpad, const bf16_t* wpk, const float* bias, const float* x_f32, float* out, int B, int Tp,
+                   int act, hipStream_t s, int fmt, long x_lo, long w_lo) {
+    dim3 grid((Tp + PC_BM - 1) / PC_BM, SYL_POSG, B);
+    if (posconv_attrs()) return 1;
     if (fmt == FMT_SPLIT) {
-        hipLaunchKernelGGL((posconv_bf16_kernel<2, FMT_SPLIT>), grid, dim3(512), PC_LDS, s, xpad, wpk, bias, x_f32, out, Tp, x_lo, w_lo);
+        hipLaunchKernelGGL((posconv_bf16_kernel<2, FMT_SPLIT>), grid, dim3(512), PC_LDS, s, xpad, wpk, bias, x_f32, out, Tp, x_lo, w_lo, nullptr, nullptr);
         HIP_TRY(hipGetLastError());
         return 0;
     }
     if (fmt == FMT_F16 && act == 2) { syl_set_error("launch_posconv", "the erf GELU (act 2) has no fp16 instantiation"); return 1; }
-    if (fmt == FMT_F16) hipLaunchKernelGGL((posconv_bf16_kernel<1, FMT_F16>), grid, dim3(512), PC_LDS, s, xpad, wpk, bias, x_f32, out, Tp, 0L, 0L);
-    else if (act == 2) hipLaunchKernelGGL((posconv_bf16_kernel<2, FMT_BF16>), grid, dim3(512), PC_LDS, s, xpad, wpk, bias, x_f32, out, Tp, 0L, 0L);
-    else hipLaunchKernelGGL((posconv_bf16_kernel<1, FMT_BF16>), grid, dim3(512), PC_LDS, s, xpad, wpk, bias, x_f32, out, Tp, 0L, 0L);
+    if (fmt == FMT_F16) hipLaunchKernelGGL((posconv_bf16_kernel<1, FMT_F16>), grid, dim3(512), PC_LDS, s, xpad, wpk, bias, x_f32, out, Tp, 0L, 0L, nullptr, nullptr);
+    else if (act == 2) hipLaunchKernelGGL((posconv_bf16_kernel<2, FMT_BF16>), grid, dim3(512), PC_LDS, s, xpad, wpk, bias, x_f32, out, Tp, 0L, 0L, nullptr, nullptr);
+    else hipLaunchKernelGGL((posconv_bf16_kernel<1, FMT_BF16>), grid, dim3(512), PC_LDS, s, xpad, wpk, bias, x_f32, out, Tp, 0L, 0L, nullptr, nullptr);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// packed layout (sylber_forward_packed): B utterances in slots of one xpad pseudo-utterance of slot[B] frames; grid z = utterance,
+// x = 256-frame blocks of the longest slot (blocks past a shorter slot exit); 16-bit single-plane formats
+int launch_posconv_packed(const bf16_t* xpad, const bf16_t* wpk, const float* bias, const float* x_f32, float* out, int B, int slot_max,
+                          const int* slot, const int* frames, hipStream_t s, int fmt) {
+    if (fmt != FMT_BF16 && fmt != FMT_F16) { syl_set_error("launch_posconv_packed", "bf16 / fp16 only"); return 1; }
+    if (posconv_attrs()) return 1;
+    dim3 grid((slot_max + PC_BM - 1) / PC_BM, SYL_POSG, B);
+    if (fmt == FMT_F16) hipLaunchKernelGGL((posconv_bf16_kernel<1, FMT_F16>), grid, dim3(512), PC_LDS, s, xpad, wpk, bias, x_f32, out, 0, 0L, 0L, slot, frames);
+    else hipLaunchKernelGGL((posconv_bf16_kernel<1, FMT_BF16>), grid, dim3(512), PC_LDS, s, xpad, wpk, bias, x_f32, out, 0, 0L, 0L, slot, frames);
     HIP_TRY(hipGetLastError());
     return 0;
 }

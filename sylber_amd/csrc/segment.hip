@@ -354,7 +354,10 @@ __global__ __launch_bounds__(256) void segment_kernel(const float* __restrict__ 
 // mid [(T+1) x 2], merged [T+1]
 __host__ __device__ inline size_t seg_wide_slab_floats(int T) { return (5 * (size_t)T + 6 * ((size_t)T + 1) + 63) & ~(size_t)63; }
 
-__global__ __launch_bounds__(256) void segment_norms_kernel(const float* __restrict__ hidden, int B, int T, float* __restrict__ scratch, size_t slab) {
+// row0 (packed layout, sylber_segment_packed; nullptr otherwise): utterance b's frame t is row row0[b] + t of `hidden` instead of b T + t,
+// and only its first frames[b] rows exist (the norms of t >= frames[b] are taken from its last frame: they are never read)
+__global__ __launch_bounds__(256) void segment_norms_kernel(const float* __restrict__ hidden, int B, int T, float* __restrict__ scratch, size_t slab,
+                                                            const int* __restrict__ row0, const int* __restrict__ frames) {
     __shared__ float ss_s[64];
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const long rows = (long)B * T, r0 = (long)blockIdx.x * 64 + wave * 16;
@@ -362,7 +365,12 @@ __global__ __launch_bounds__(256) void segment_norms_kernel(const float* __restr
     for (int q = 0; q < 4; ++q) {
         float x[4][12];
 #pragma unroll
-        for (int r = 0; r < 4; ++r) { const long g = r0 + 4 * q + r; load_pw(hidden + (size_t)(g < rows ? g : rows - 1) * SEG_D, lane, x[r]); }
+        for (int r = 0; r < 4; ++r) {
+            long g = r0 + 4 * q + r;
+            g = g < rows ? g : rows - 1;
+            if (row0) { const int b = (int)(g / T), t = (int)(g % T); g = (long)row0[b] + (t < frames[b] ? t : frames[b] - 1); }
+            load_pw(hidden + (size_t)g * SEG_D, lane, x[r]);
+        }
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const float ss = pw_dot(x[r], x[r]) + 1e-8f;
@@ -388,14 +396,14 @@ __global__ __launch_bounds__(256) void segment_norms_kernel(const float* __restr
 template <bool GS>
 __global__ __launch_bounds__(256) void segment_runs_kernel(const float* __restrict__ hidden, int T, float norm_thr, float merge_thr,
                                                            float* __restrict__ scratch, size_t slab, int list_cap,
-                                                           const int* __restrict__ frames) {
+                                                           const int* __restrict__ frames, const int* __restrict__ row0) {
     extern __shared__ __attribute__((aligned(16))) float lds_f[];
     float* ca_s = lds_f;                       // [768]
     float* cb_s = ca_s + SEG_D;                // [768]
     int* sh_i = (int*)(cb_s + SEG_D);          // [16]
     int* mystart = sh_i + 16;                  // [list_cap]
     const int b = blockIdx.y, rx = blockIdx.x, G = gridDim.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const float* states = hidden + (size_t)b * T * SEG_D;
+    const float* states = hidden + (row0 ? (size_t)row0[b] : (size_t)b * T) * SEG_D;
     float* sl = scratch + (size_t)b * slab;
     const float* g_nsq = sl;
     const float* g_npw = sl + T;
@@ -404,6 +412,7 @@ __global__ __launch_bounds__(256) void segment_runs_kernel(const float* __restri
     // the utterance's own end (sylber_segment_frames): frames at or past Tb do not exist for the scan, a run ends at Tb as at the end of
     // an array.  T stays the row pitch of `hidden` and the slab.
     const int Tb = frames ? frames[b] : T;
+    const int Tl = row0 ? Tb : T;              // rows of `states` that may be read (prefetch clamp)
 
     // ---- which runs are mine: run r (in frame order) belongs to workgroup r % G
     if (tid < 16) sh_i[tid] = 0;
@@ -479,7 +488,7 @@ __global__ __launch_bounds__(256) void segment_runs_kernel(const float* __restri
             float g0[4][12], g1[4][12];
             auto ldg = [&](int i, float (&g)[4][12]) {
 #pragma unroll
-                for (int r = 0; r < 4; ++r) load_pw(states + (size_t)(i + r < T ? i + r : T - 1) * SEG_D, lane, g[r]);
+                for (int r = 0; r < 4; ++r) load_pw(states + (size_t)(i + r < Tl ? i + r : Tl - 1) * SEG_D, lane, g[r]);
             };
             ldg(base, g0);
             for (int i0 = base; i0 < end; i0 += 4) {
@@ -639,9 +648,9 @@ __global__ __launch_bounds__(256) void segment_compact_kernel(int T, const float
 
 // states[s:e].mean(0) per segment (sylber.py:133): one wave per segment, the utterance's segments spread over gridDim.x workgroups
 __global__ __launch_bounds__(256) void segment_pool_kernel(const float* __restrict__ hidden, int T, const int64_t* __restrict__ seg_out,
-                                                           const int* __restrict__ nseg_out, float* __restrict__ feat_out) {
+                                                           const int* __restrict__ nseg_out, float* __restrict__ feat_out, const int* __restrict__ row0) {
     const int b = blockIdx.y, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const float* states = hidden + (size_t)b * T * SEG_D;
+    const float* states = hidden + (row0 ? (size_t)row0[b] : (size_t)b * T) * SEG_D;
     const int n = nseg_out[b];
     for (int k = blockIdx.x * 4 + wave; k < n; k += gridDim.x * 4) {
         const int s = (int)seg_out[((size_t)b * T + k) * 2], e = (int)seg_out[((size_t)b * T + k) * 2 + 1];
@@ -664,7 +673,8 @@ size_t segment_scratch_floats(int B, int T, int D) {
 
 // mode 0: the wide path (norms / runs / compaction / pooling on all CUs); mode -1: one workgroup per utterance (rounds 1-5; A/B and bitwise reference)
 int launch_segment(const float* hidden, int B, int T, int D, float norm_thr, float merge_thr, int64_t* seg, int* nseg,
-                   float* feat, float* scratch, hipStream_t s, int mode, const int* frames) {
+                   float* feat, float* scratch, hipStream_t s, int mode, const int* frames, const int* row0) {
+    if (row0 && !frames) { syl_set_error("launch_segment", "row offsets need per-row frame counts"); return 1; }
     if (D != SEG_D) { syl_set_error("launch_segment", "feature dim must be 768"); return 1; }
     if (T < 1) { syl_set_error("launch_segment", "T must be >= 1"); return 1; }
     if (frames && mode < 0) { syl_set_error("launch_segment", "per-row frame counts need the wide path (SYLBER_OPT_SEGMENT = 0)"); return 1; }
@@ -672,7 +682,7 @@ int launch_segment(const float* hidden, int B, int T, int D, float norm_thr, flo
         if (!scratch) { syl_set_error("launch_segment", "the wide path needs its scratch slab (segment_scratch_floats)"); return 1; }
         const size_t slab = seg_wide_slab_floats(T);
         const long rows = (long)B * T;
-        hipLaunchKernelGGL(segment_norms_kernel, dim3((unsigned)((rows + 63) / 64)), dim3(256), 0, s, hidden, B, T, scratch, slab);
+        hipLaunchKernelGGL(segment_norms_kernel, dim3((unsigned)((rows + 63) / 64)), dim3(256), 0, s, hidden, B, T, scratch, slab, row0, frames);
         int G = (T + 7) / 8; G = G < 8 ? 8 : (G > 128 ? 128 : G);
         const int list_cap = ((T + 1) / 2 + G - 1) / G + 1;
         const size_t lds_l = ((size_t)2 * SEG_D + 16 + list_cap + 5 * SEG_LCAP + 5 * (SEG_LCAP + 1)) * 4;
@@ -681,13 +691,13 @@ int launch_segment(const float* hidden, int B, int T, int D, float norm_thr, flo
             static PerDeviceOnce once;
             if (once.need()) HIP_TRY(hipFuncSetAttribute((const void*)segment_runs_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         }
-        hipLaunchKernelGGL(segment_runs_kernel<false>, dim3(G, B), dim3(256), lds_l, s, hidden, T, norm_thr, merge_thr, scratch, slab, list_cap, frames);
+        hipLaunchKernelGGL(segment_runs_kernel<false>, dim3(G, B), dim3(256), lds_l, s, hidden, T, norm_thr, merge_thr, scratch, slab, list_cap, frames, row0);
         if (T > SEG_LCAP)
-            hipLaunchKernelGGL(segment_runs_kernel<true>, dim3(G, B), dim3(256), lds_g, s, hidden, T, norm_thr, merge_thr, scratch, slab, list_cap, frames);
+            hipLaunchKernelGGL(segment_runs_kernel<true>, dim3(G, B), dim3(256), lds_g, s, hidden, T, norm_thr, merge_thr, scratch, slab, list_cap, frames, row0);
         hipLaunchKernelGGL(segment_compact_kernel, dim3(B), dim3(256), 0, s, T, scratch, slab, seg, nseg, frames);
         if (feat) {
             int PX = (T + 15) / 16; PX = PX < 1 ? 1 : (PX > 64 ? 64 : PX);
-            hipLaunchKernelGGL(segment_pool_kernel, dim3(PX, B), dim3(256), 0, s, hidden, T, seg, nseg, feat);
+            hipLaunchKernelGGL(segment_pool_kernel, dim3(PX, B), dim3(256), 0, s, hidden, T, seg, nseg, feat, row0);
         }
         HIP_TRY(hipGetLastError());
         return 0;

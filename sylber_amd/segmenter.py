@@ -21,6 +21,8 @@ from .ingest import ingest_file
 from .weights import (NUM_LAYERS, expected_shapes, fold_pos_conv_weight, normalize_keys, synthetic_state_dict)
 
 FRAME_RATE = 50  # sylber.py:132
+SLOT_SAMPLES = 320  # waveform samples per frame of a packed batch's slot (the conv stack's total stride)
+PACKED_PRECISIONS = ("bf16", "fp16")
 
 
 def _ptr(t: torch.Tensor):
@@ -144,6 +146,34 @@ def _pad_rows(stage_np: np.ndarray, rows, lengths, lo: int, hi: int) -> None:
         stage_np[i, lengths[i]:] = 0.0
 
 
+def packed_layout(lengths: Sequence[int]):
+    """The slots of a packed batch (``sylber_packed_layout``; host only, no GPU): per-clip sample counts -> ``(offsets, frames)``, int32
+    arrays of B + 1 slot offsets in frames (``offsets[-1]`` = the batch's total frames) and of each clip's own frame count.  Clip b's
+    waveform goes to sample ``SLOT_SAMPLES * offsets[b]`` of the packed buffer, its hidden states come back as rows
+    ``[offsets[b], offsets[b] + frames[b])``.  ValueError for an empty batch, a clip below 400 samples or a batch too long for 32-bit offsets."""
+    lib = _lib.load()
+    n = [int(x) for x in lengths]
+    B = len(n)
+    if B < 1:
+        raise ValueError("a packed batch needs at least one clip")
+    if any(x < 400 or x > 2 ** 31 - 1 for x in n):
+        raise ValueError("every clip of a packed batch needs 400 .. 2^31 - 1 samples, got %s" % n)
+    off, fr = (ctypes.c_int32 * (B + 1))(), (ctypes.c_int32 * B)()
+    if lib.sylber_packed_layout((ctypes.c_int32 * B)(*n), B, off, fr) != 0:
+        raise ValueError(lib.sylber_last_error().decode())
+    return np.frombuffer(off, dtype=np.int32).copy(), np.frombuffer(fr, dtype=np.int32).copy()
+
+
+def _stage_packed(stage_np: np.ndarray, rows, lengths, offsets, lo: int, hi: int) -> None:
+    """clips [lo, hi) of a batch into the flat host staging view of a packed batch: clip i at sample ``SLOT_SAMPLES * offsets[i]``, zeros
+    to the end of its slot (numpy's copy releases the GIL)"""
+    for i in range(lo, hi):
+        a, e = SLOT_SAMPLES * int(offsets[i]), SLOT_SAMPLES * int(offsets[i + 1])
+        src = rows[i].detach()
+        stage_np[a:a + lengths[i]] = (src if src.dtype == torch.float32 else src.to(torch.float32)).numpy()
+        stage_np[a + lengths[i]:e] = 0.0
+
+
 class _BlockLayout:
     """Byte layout of the host block one batch's results land in: [hidden states | tables | pooled features | counts], every part
     256-byte aligned, ``kcap`` segment slots per utterance.  The views work on the torch uint8 block (the D2H copies' targets) and
@@ -151,12 +181,16 @@ class _BlockLayout:
 
     _TORCH = {np.float32: (torch.float32, 4), np.int32: (torch.int32, 4), np.int64: (torch.int64, 8)}
 
-    def __init__(self, B: int, T: int, D: int, kcap: int, with_hidden: bool, with_feats: bool):
+    def __init__(self, B: int, T: int, D: int, kcap: int, with_hidden: bool, with_feats: bool, frames: Optional[Sequence[int]] = None):
         def al(n):
             return (n + 255) & ~255
         self.B, self.T, self.D, self.kcap = B, T, D, kcap
         self.with_hidden, self.with_feats = with_hidden, with_feats
-        self.o_seg = al(B * T * D * 4) if with_hidden else 0
+        # frames (packed batches): the hidden part holds only each clip's own frames, back to back ([sum(frames), D])
+        self.frames = None if frames is None else [int(f) for f in frames]
+        self.starts = None if frames is None else np.concatenate([[0], np.cumsum(self.frames)]).astype(np.int64)
+        hrows = B * T if frames is None else int(self.starts[-1])
+        self.o_seg = al(hrows * D * 4) if with_hidden else 0
         self.o_feat = self.o_seg + al(B * kcap * 2 * 8)
         self.o_cnt = self.o_feat + (al(B * kcap * D * 4) if with_feats else 0)
         self.nbytes = self.o_cnt + al(B * 4)
@@ -170,7 +204,16 @@ class _BlockLayout:
         return buf[off:off + n].view(dtype).reshape(shape)
 
     def hidden(self, buf):
-        return self._view(buf, 0, np.float32, (self.B, self.T, self.D)) if self.with_hidden else None
+        if not self.with_hidden:
+            return None
+        if self.frames is not None:
+            return self._view(buf, 0, np.float32, (int(self.starts[-1]), self.D))
+        return self._view(buf, 0, np.float32, (self.B, self.T, self.D))
+
+    def clip_hidden(self, buf):
+        """packed layout: one [frames[b], D] view per clip"""
+        h = self.hidden(buf)
+        return None if h is None else [h[self.starts[b]:self.starts[b + 1]] for b in range(self.B)]
 
     def counts(self, buf):
         return self._view(buf, self.o_cnt, np.int32, (self.B,))
@@ -235,6 +278,8 @@ class HubertEncoderHIP:
             raise _lib.SylberHipError("no MI355X visible to PyTorch-ROCm; the HIP path has no CPU fallback")
         self.device = torch.device(device if device != "cuda" else "cuda:%d" % torch.cuda.current_device())
         self.num_layers = num_layers
+        self.precision = precision
+        self._opts = {}
         sd = normalize_keys(state_dict)
         shapes = expected_shapes(num_layers)
         keep = {}
@@ -299,6 +344,7 @@ class HubertEncoderHIP:
     def set_option(self, key: int, value: int) -> None:
         """per-handle tuning / test override (include/sylber_hip.h SYLBER_OPT_*; value < 0 = automatic)"""
         _lib.check(self.lib.sylber_set_option(self.handle, int(key), int(value)), "sylber_set_option")
+        self._opts[int(key)] = int(value)
 
     def forward(self, wav: torch.Tensor, lengths: Optional[Sequence[int]] = None, stop_stage: int = 0,
                 out: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -340,6 +386,93 @@ class HubertEncoderHIP:
         input buffer so that the key repeats."""
         _lib.check(self.lib.sylber_set_graph_mode(self.handle, 1 if enable else 0), "sylber_set_graph_mode")
         self._graph_stream = torch.cuda.Stream(device=self.device) if enable else None
+
+    def _check_packed(self, what: str) -> None:
+        """ValueError, before any launch, for what the packed path does not cover"""
+        if self.precision not in PACKED_PRECISIONS:
+            raise ValueError("%s: packed batches run in precision %s only (this encoder: %r)" % (what, " / ".join(map(repr, PACKED_PRECISIONS)),
+                                                                                                   self.precision))
+        if getattr(self, "_graph_stream", None) is not None:
+            raise ValueError("%s: packed batches do not run in graph mode (set_graph_mode(False))" % what)
+        if self._opts.get(_lib.OPT_SEGMENT, 0) < 0:
+            raise ValueError("%s: packed boundary detection needs the wide segmenter (SYLBER_OPT_SEGMENT = 0, not -1)" % what)
+        # exactly the settings sylber_forward_packed refuses: sylber_set_option stores a non-zero queries-per-wave state only for the
+        # values 32 and 64 (any other value selects the automatic kernel), and a non-zero conv0 switch for every value > 0
+        if (self._opts.get(_lib.OPT_ATTN_QUERIES_PER_WAVE, 0) in (32, 64) or self._opts.get(_lib.OPT_CONV0_VALU, 0) > 0):
+            raise ValueError("%s: packed batches need SYLBER_OPT_ATTN_QUERIES_PER_WAVE and SYLBER_OPT_CONV0_VALU at their defaults" % what)
+
+    def forward_packed_raw(self, wav: torch.Tensor, lengths: Sequence[int], out: Optional[torch.Tensor] = None, layout=None) -> torch.Tensor:
+        """A staged packed batch (``packed_layout``): wav [SLOT_SAMPLES * offsets[-1]] float32 on this device, clip b at sample
+        ``SLOT_SAMPLES * offsets[b]``, zeros to the end of its slot; lengths = the clips' sample counts.  Returns the hidden states
+        [offsets[-1], 768] float32 (device): clip b's are rows [offsets[b], offsets[b] + frames[b]), bit-identical to a forward of it alone.
+        ``layout``: ``packed_layout(lengths)`` when the caller has it already."""
+        self._check_packed("forward_packed")
+        n = [int(x) for x in lengths]
+        offsets, _ = packed_layout(n) if layout is None else layout
+        P = int(offsets[-1])
+        assert wav.is_cuda and wav.dtype == torch.float32 and wav.is_contiguous() and wav.numel() == SLOT_SAMPLES * P
+        if out is None:
+            out = torch.empty(P, 768, dtype=torch.float32, device=wav.device)
+        assert out.is_contiguous() and out.numel() >= P * 768
+        with torch.cuda.device(wav.device):
+            st = self.lib.sylber_forward_packed(self.handle, ctypes.c_void_p(wav.data_ptr()), (ctypes.c_int32 * len(n))(*n), len(n),
+                                                ctypes.c_void_p(out.data_ptr()), _stream_ptr(wav.device))
+        _lib.check(st, "sylber_forward_packed")
+        return out
+
+    def forward_packed(self, wavs: Sequence[torch.Tensor]):
+        """Clips of different lengths (1-D tensors, host or device) as ONE packed batch, no padding to the longest: each gets a slot of its
+        own frames rounded up to 64 (``packed_layout``).  Returns ``(hidden [offsets[-1], 768] device, offsets [B + 1], frames [B])``;
+        clip b's hidden states are ``hidden[offsets[b]:offsets[b] + frames[b]]``, bit-identical to a forward of that clip alone."""
+        self._check_packed("forward_packed")
+        rows = [torch.as_tensor(w).reshape(-1) for w in wavs]
+        lengths = [int(r.numel()) for r in rows]
+        offsets, frames = packed_layout(lengths)
+        wav = torch.zeros(SLOT_SAMPLES * int(offsets[-1]), dtype=torch.float32, device=self.device)
+        for i, r in enumerate(rows):
+            a = SLOT_SAMPLES * int(offsets[i])
+            wav[a:a + lengths[i]] = r.to(self.device, torch.float32)
+        return self.forward_packed_raw(wav, lengths), offsets, frames
+
+    def segment_packed(self, hidden: torch.Tensor, lengths: Sequence[int], norm_threshold: float, merge_threshold: float,
+                       with_features: bool = True, out=None, layout=None):
+        """Boundary detection of a packed batch (``sylber_segment_packed``): hidden [offsets[-1], 768] of ``forward_packed``, lengths = the
+        clips' sample counts.  Clip b is segmented and pooled as its own frames alone.  Returns (segments [B, kcap, 2] int64 relative to
+        the clip's start, nseg [B] int32, feats [B, kcap, 768] or None), kcap = max(frames).  Same stream rules as ``segment``."""
+        self._check_packed("segment_packed")
+        n = [int(x) for x in lengths]
+        offsets, frames = packed_layout(n) if layout is None else layout
+        assert hidden.is_cuda and hidden.dtype == torch.float32 and hidden.is_contiguous() and hidden.numel() >= int(offsets[-1]) * 768
+        B, K, D = len(n), int(frames.max()), 768
+        if out is not None:
+            seg, nseg, feats = out
+        else:
+            seg = torch.empty(B, K, 2, dtype=torch.int64, device=hidden.device)
+            nseg = torch.empty(B, dtype=torch.int32, device=hidden.device)
+            feats = torch.empty(B, K, D, dtype=torch.float32, device=hidden.device) if with_features else None
+        with torch.cuda.device(hidden.device):
+            st = self.lib.sylber_segment_packed(self.handle, ctypes.c_void_p(hidden.data_ptr()), (ctypes.c_int32 * B)(*n), B,
+                                                ctypes.c_float(float(np.float32(norm_threshold))),
+                                                ctypes.c_float(float(np.float32(merge_threshold))),
+                                                ctypes.c_void_p(seg.data_ptr()), ctypes.c_void_p(nseg.data_ptr()),
+                                                ctypes.c_void_p(feats.data_ptr()) if feats is not None else None, _stream_ptr(hidden.device))
+        _lib.check(st, "sylber_segment_packed")
+        return seg, nseg, feats
+
+    def gather_packed(self, hidden: torch.Tensor, lengths: Sequence[int], out: Optional[torch.Tensor] = None, layout=None) -> torch.Tensor:
+        """each clip's own rows of a packed forward's hidden states, back to back (``sylber_packed_gather``): [sum(frames), 768] on the
+        device, on the current stream -- one device-to-host copy then fetches exactly the clips' frames"""
+        n = [int(x) for x in lengths]
+        _, frames = packed_layout(n) if layout is None else layout
+        rows = int(frames.sum())
+        if out is None:
+            out = torch.empty(rows, 768, dtype=torch.float32, device=hidden.device)
+        assert hidden.is_cuda and hidden.is_contiguous() and out.is_contiguous() and out.numel() >= rows * 768
+        with torch.cuda.device(hidden.device):
+            st = self.lib.sylber_packed_gather(ctypes.c_void_p(hidden.data_ptr()), (ctypes.c_int32 * len(n))(*n), len(n),
+                                               ctypes.c_void_p(out.data_ptr()), _stream_ptr(hidden.device))
+        _lib.check(st, "sylber_packed_gather")
+        return out[:rows]
 
     def set_per_utterance(self, enable: bool = True) -> None:
         """batch-invariant encoder (include/sylber_hip.h SYLBER_OPT_PER_UTTERANCE): conv0's GroupNorm statistics of every row over its
@@ -438,6 +571,11 @@ class Segmenter:
                  encoding_layer=9, merge_threshold=0.8, norm_threshold=2.6, device="cuda", **kwargs):
         self.encoding_layer = encoding_layer
         self.enc_dim = 768
+        # packed batches (off by default): a ragged batch runs without padding to its longest clip -- each clip in a slot of its own
+        # frames rounded up to 64 (packed_layout) -- with batch_invariant=True's results, bit for bit (bf16 and fp16 only)
+        self.packed = bool(kwargs.get("packed", False))
+        if self.packed and kwargs.get("precision", "bf16") not in PACKED_PRECISIONS:
+            raise ValueError("packed=True supports precision %s only (got %r)" % (" / ".join(map(repr, PACKED_PRECISIONS)), kwargs.get("precision")))
         state_dict = self._load_state_dict(model_ckpt, encoding_layer)
         if "cuda" not in str(device):
             raise _lib.SylberHipError("sylber_amd.Segmenter runs on the MI355X only (device=%r)" % (device,))
@@ -451,7 +589,7 @@ class Segmenter:
         self.speech_model.set_option(6, self._resln_prefetch)
         # batch-invariant mode (off by default): every clip of a batch gets exactly the results it gets alone -- GroupNorm statistics
         # over its own length (SYLBER_OPT_PER_UTTERANCE), segmentation over its own frames (sylber_segment_frames), hidden states cut to them
-        self.batch_invariant = bool(kwargs.get("batch_invariant", False))
+        self.batch_invariant = bool(kwargs.get("batch_invariant", False)) or self.packed
         if self.batch_invariant:
             self.speech_model.set_per_utterance(True)
         self.norm_threshold = norm_threshold
@@ -576,6 +714,40 @@ class Segmenter:
         hidden = self.speech_model.forward(batch, lengths)
         return hidden, lengths
 
+    def _encode_packed(self, batch_wavs: Sequence[torch.Tensor]):
+        """packed=True's encode_batch: every clip staged at its slot (``packed_layout``), not into rows of the longest clip, and one
+        packed forward.  Returns the device hidden states [offsets[-1], 768], the clips' sample counts, offsets and frame counts."""
+        rows, lengths = self._rows(batch_wavs)
+        sm = self.speech_model
+        sm._check_packed("Segmenter(packed=True)")
+        offsets, frames = packed_layout(lengths)
+        n = SLOT_SAMPLES * int(offsets[-1])
+        dev = sm.device
+        if all(not r.is_cuda for r in rows):
+            # host inputs: staged in the pinned buffer and uploaded by row groups, as encode_batch does
+            stage, slot = self._stage_buffer((n,))
+            stage_np = stage.numpy()
+            batch = torch.empty(n, dtype=torch.float32, device=dev)
+            nrow = len(rows)
+            ngrp = min(self._fill_groups, max(1, nrow // 4)) if n >= (1 << 20) else 1
+            if ngrp <= 1:
+                _stage_packed(stage_np, rows, lengths, offsets, 0, nrow)
+                batch.copy_(stage, non_blocking=True)
+            else:
+                bounds = [(g * nrow // ngrp, (g + 1) * nrow // ngrp) for g in range(ngrp)]
+                futs = [self._fill_pool().submit(_stage_packed, stage_np, rows, lengths, offsets, lo, hi) for lo, hi in bounds]
+                for (lo, hi), f in zip(bounds, futs):
+                    f.result()
+                    a, e = SLOT_SAMPLES * int(offsets[lo]), SLOT_SAMPLES * int(offsets[hi])
+                    batch[a:e].copy_(stage[a:e], non_blocking=True)
+            slot["event"].record(torch.cuda.current_stream(dev))
+        else:
+            batch = torch.zeros(n, dtype=torch.float32, device=dev)
+            for i, r in enumerate(rows):
+                a = SLOT_SAMPLES * int(offsets[i])
+                batch[a:a + lengths[i]] = r.to(dev, torch.float32, non_blocking=True)
+        return sm.forward_packed_raw(batch, lengths, layout=(offsets, frames)), lengths, offsets, frames
+
     def _fill_pool(self):
         pool = self.__dict__.get("_fill_executor")
         if pool is None:
@@ -640,8 +812,12 @@ class Segmenter:
         mark("enter")
         gmark("enter")
         batch_wavs, is_batch = self._collect(wav_file, wav)
-        hidden, lengths = self.encode_batch(batch_wavs)
-        frames = self.speech_model.frame_counts(lengths) if self.batch_invariant else None
+        offsets = None
+        if self.packed:
+            hidden, lengths, offsets, frames = self._encode_packed(batch_wavs)
+        else:
+            hidden, lengths = self.encode_batch(batch_wavs)
+            frames = self.speech_model.frame_counts(lengths) if self.batch_invariant else None
         gmark("forward done")
         mark("padded, H2D and forward issued")
         # D2H (sylber.py:122-138's .cpu().numpy()) into ONE leased page-locked block (PinnedOutputPool: persistent blocks, no
@@ -653,22 +829,33 @@ class Segmenter:
         # tables (rare, and the sizes repeat from then on).
         dev = hidden.device
         cur = torch.cuda.current_stream(dev)
-        B, T, D = hidden.shape
-        lay = _BlockLayout(B, T, D, min(T, self._kcap_seen), self._want_hidden, self._want_feats)
+        if offsets is not None:                              # packed: only the clips' own frames leave the device
+            B, T, D = len(lengths), int(frames.max()), hidden.shape[1]
+            lay = _BlockLayout(B, T, D, min(T, self._kcap_seen), self._want_hidden, self._want_feats, frames=frames)
+        else:
+            B, T, D = hidden.shape
+            lay = _BlockLayout(B, T, D, min(T, self._kcap_seen), self._want_hidden, self._want_feats)
         owner, blk, handed = self._out_block(lay.nbytes, "call")
         copy_s = self.__dict__.get("_copy_stream")
         if copy_s is None or copy_s.device != dev:
             copy_s = self._copy_stream = torch.cuda.Stream(device=dev)
+        src = hidden
+        if offsets is not None and lay.with_hidden:         # packed: the clips' own rows gathered back to back, then one copy
+            src = self.speech_model.gather_packed(hidden, lengths, layout=(offsets, frames))
         fwd_done = self.__dict__.setdefault("_ev_fwd", torch.cuda.Event())
         fwd_done.record(cur)
         if lay.with_hidden:
             with torch.cuda.stream(copy_s):
                 copy_s.wait_event(fwd_done)
-                lay.hidden(blk).copy_(hidden, non_blocking=True)
+                lay.hidden(blk).copy_(src, non_blocking=True)
                 gmark("hidden states D2H done", copy_s)
-            hidden.record_stream(copy_s)
-        seg, nseg, feats = self.speech_model.segment(hidden, self.norm_threshold, self.merge_threshold, with_features=lay.with_feats,
-                                                     frames=frames)
+            src.record_stream(copy_s)
+        if offsets is not None:
+            seg, nseg, feats = self.speech_model.segment_packed(hidden, lengths, self.norm_threshold, self.merge_threshold,
+                                                                with_features=lay.with_feats, layout=(offsets, frames))
+        else:
+            seg, nseg, feats = self.speech_model.segment(hidden, self.norm_threshold, self.merge_threshold, with_features=lay.with_feats,
+                                                         frames=frames)
         gmark("boundary detection done")
         lay.counts(blk).copy_(nseg, non_blocking=True)
         counted = self.__dict__.setdefault("_ev_counts", torch.cuda.Event())
@@ -691,7 +878,10 @@ class Segmenter:
         cur.wait_stream(copy_s)
         cur.synchronize()
         mark("all D2H done")
-        outputs = _result_dicts(nseg_h, seg_h, feats_h, lay.hidden(owner), frames, in_second, handed)
+        if offsets is not None:
+            outputs = _result_dicts(nseg_h, seg_h, feats_h, lay.clip_hidden(owner), None, in_second, handed)
+        else:
+            outputs = _result_dicts(nseg_h, seg_h, feats_h, lay.hidden(owner), frames, in_second, handed)
         mark("dicts built")
         return outputs if is_batch else outputs[0]
 
@@ -735,15 +925,23 @@ class Segmenter:
             if any(r.is_cuda for r in rows):
                 raise ValueError("Segmenter.stream takes host tensors (device batches have nothing to overlap: use __call__)")
             lmax = max(lengths)
-            stage, slot = self._stage_buffer((len(rows), lmax))
-            stage_np = stage.numpy()
             n = len(rows)
+            offsets = frames = None
+            if self.packed:                                   # each clip at its slot, zeros to the slot's end
+                self.speech_model._check_packed("Segmenter.stream(packed=True)")
+                offsets, frames = packed_layout(lengths)
+                stage, slot = self._stage_buffer((SLOT_SAMPLES * int(offsets[-1]),))
+                fill, fargs = _stage_packed, (lengths, offsets)
+            else:
+                stage, slot = self._stage_buffer((len(rows), lmax))
+                fill, fargs = _pad_rows, (lengths,)
+            stage_np = stage.numpy()
             if self._fill_threads > 1 and n >= 16:
-                fut = self._fill_pool().submit(_pad_rows, stage_np, rows, lengths, 0, n // 2)
-                _pad_rows(stage_np, rows, lengths, n // 2, n)
+                fut = self._fill_pool().submit(fill, stage_np, rows, *fargs, 0, n // 2)
+                fill(stage_np, rows, *fargs, n // 2, n)
                 fut.result()
             else:
-                _pad_rows(stage_np, rows, lengths, 0, n)
+                fill(stage_np, rows, *fargs, 0, n)
             tr = self.__dict__.get("_trace")
             if tr is not None:
                 tr.append(("padded", time.perf_counter()))
@@ -755,34 +953,54 @@ class Segmenter:
             with torch.cuda.stream(h2d):
                 if d["in_free"] is not None:
                     h2d.wait_event(d["in_free"])
-                batch = flat(d, "in", n * lmax, torch.float32).view(n, lmax)
+                batch = flat(d, "in", stage.numel(), torch.float32).view(stage.shape)
                 batch.copy_(stage, non_blocking=True)
                 slot["event"].record(h2d)
                 ev = torch.cuda.Event()
                 ev.record(h2d)
-            return {"batch": batch, "lengths": lengths, "uploaded": ev, "single": not isinstance(batch_wavs, (list, tuple)), "set": d}
+            return {"batch": batch, "lengths": lengths, "uploaded": ev, "single": not isinstance(batch_wavs, (list, tuple)), "set": d,
+                    "offsets": offsets, "pframes": frames}
 
         def issue_compute(t, slot_id):
             batch, lengths, d = t["batch"], t["lengths"], t["set"]
             cur.wait_event(t["uploaded"])
             if d["out_free"] is not None:
                 cur.wait_event(d["out_free"])             # the copies of the batch that last used this set have left
-            B_, T_ = batch.shape[0], self.speech_model.num_frames(batch.shape[1])
+            offsets = t["offsets"]
+            if offsets is not None:                           # packed: B clips in offsets[-1] frames, tables of max(frames) slots
+                B_, T_, P_ = len(lengths), int(t["pframes"].max()), int(offsets[-1])
+            else:
+                B_, T_ = batch.shape[0], self.speech_model.num_frames(batch.shape[1])
             # forward + boundary detection run on `cur`, the stream that was current when the generator STARTED, whatever the
             # caller's current stream is at this resumption: `done` below is recorded on the stream the work was issued to
             with torch.cuda.stream(cur):
-                hidden = self.speech_model.forward(batch, lengths, out=flat(d, "hid", B_ * T_ * 768, torch.float32).view(B_, T_, 768))
                 out = (flat(d, "seg", B_ * T_ * 2, torch.int64).view(B_, T_, 2), flat(d, "nseg", B_, torch.int32),
                        flat(d, "feat", B_ * T_ * 768, torch.float32).view(B_, T_, 768) if want_f else None)
-                frames = self.speech_model.frame_counts(lengths) if self.batch_invariant else None
-                seg, nseg, feats = self.speech_model.segment(hidden, self.norm_threshold, self.merge_threshold, out=out, frames=frames)
+                if offsets is not None:
+                    frames = t["pframes"]
+                    hidden = self.speech_model.forward_packed_raw(batch, lengths, out=flat(d, "hid", P_ * 768, torch.float32).view(P_, 768),
+                                                                  layout=(offsets, frames))
+                    seg, nseg, feats = self.speech_model.segment_packed(hidden, lengths, self.norm_threshold, self.merge_threshold, out=out,
+                                                                        layout=(offsets, frames))
+                    if want_h:                        # the clips' own rows back to back: one D2H copy below
+                        nh = int(frames.sum())
+                        hidden = self.speech_model.gather_packed(hidden, lengths, out=flat(d, "cmp", nh * 768, torch.float32).view(nh, 768),
+                                                                 layout=(offsets, frames))
+                else:
+                    hidden = self.speech_model.forward(batch, lengths, out=flat(d, "hid", B_ * T_ * 768, torch.float32).view(B_, T_, 768))
+                    frames = self.speech_model.frame_counts(lengths) if self.batch_invariant else None
+                    seg, nseg, feats = self.speech_model.segment(hidden, self.norm_threshold, self.merge_threshold, out=out, frames=frames)
             tr = self.__dict__.get("_trace")                  # tools/api_stream_timeline.py: (label, host time[, event]) marks
             done = torch.cuda.Event(enable_timing=tr is not None)
             done.record(cur)
             if tr is not None:
                 tr.append(("compute issued", time.perf_counter(), done))
-            B, T, D = hidden.shape
-            lay = _BlockLayout(B, T, D, min(T, self._kcap_seen), want_h, want_f)
+            if offsets is not None:
+                B, T, D = B_, T_, 768
+                lay = _BlockLayout(B, T, D, min(T, self._kcap_seen), want_h, want_f, frames=frames)
+            else:
+                B, T, D = hidden.shape
+                lay = _BlockLayout(B, T, D, min(T, self._kcap_seen), want_h, want_f)
             # (pageable mode / pool exhausted: one private bounce block per in-flight slot, three)
             owner, blk, handed = self._out_block(lay.nbytes, slot_id)
             with torch.cuda.stream(d2h):
@@ -818,7 +1036,10 @@ class Segmenter:
                 torch.cuda.current_stream(dev).synchronize()
             else:
                 seg_h, feats_h = lay.tables(owner)
-            outputs = _result_dicts(nseg_h, seg_h, feats_h, lay.hidden(owner), t["frames"], in_second, t["handed"])
+            if lay.frames is not None:
+                outputs = _result_dicts(nseg_h, seg_h, feats_h, lay.clip_hidden(owner), None, in_second, t["handed"])
+            else:
+                outputs = _result_dicts(nseg_h, seg_h, feats_h, lay.hidden(owner), t["frames"], in_second, t["handed"])
             return outputs[0] if t["single"] else outputs
 
         try:
