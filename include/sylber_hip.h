@@ -258,6 +258,22 @@ int64_t sylber_condition_units_workspace_floats(sylber_mlp_t m, int32_t B, int32
 int sylber_condition_units(sylber_mlp_t m, const float* c1_dev, int32_t K1, const float* c2_dev, int32_t K2, const int32_t* units_dev,
                            const int32_t* spans_dev, const int32_t* nunits_dev, const int32_t* frames_dev, int32_t B, int32_t T, int32_t S,
                            float* cond_dev, float* workspace_dev, void* stream);
+/* packed batches: the conditioning of each clip's own frames, back to back -- clip b's frame t is row F_b + t of cond_dev
+ * [sum frames_host, output_dim] (F_b = frames_host[0] + ... + frames_host[b - 1]), the layout sylber_cfm_sample_packed reads.  Every row
+ * is bitwise the padded call's (sylber_condition / sylber_condition_units with frames_dev) for the same clip.  frames_host [B] >= 1 and
+ * offsets_host [B + 1] (sylber_packed_layout) are read before the call returns.  workspace_dev:
+ * sylber_condition_packed_workspace_floats(m, B, S) floats (for both calls). */
+int64_t sylber_condition_packed_workspace_floats(sylber_mlp_t m, int32_t B, int32_t S);
+/* hidden_dev [offsets[B], D]: sylber_forward_packed's rows, clip b's frame t at row offsets_host[b] + t; seg_dev [B, K, 2], nseg_dev [B],
+ * feat_dev [B, K, D]: sylber_segment_packed's tables (K = their pitch, max frames <= K); S: segment slots per clip run through the MLP
+ * (max nseg <= S <= K); avg_hidden_dev [sum frames, D] (nullable) and cond_dev [sum frames, output_dim] as sylber_condition's, per frame */
+int sylber_condition_packed(sylber_mlp_t m, const float* hidden_dev, const int32_t* offsets_host, const int32_t* frames_host, int32_t B,
+                            const int64_t* seg_dev, const int32_t* nseg_dev, const float* feat_dev, int32_t K, int32_t S, float norm_thr,
+                            float* avg_hidden_dev, float* cond_dev, float* workspace_dev, void* stream);
+/* sylber_condition_units with frames_dev = frames_host and T = max frames_host (the same table checks), cond_dev [sum frames, output_dim] */
+int sylber_condition_units_packed(sylber_mlp_t m, const float* c1_dev, int32_t K1, const float* c2_dev, int32_t K2, const int32_t* units_dev,
+                                  const int32_t* spans_dev, const int32_t* nunits_dev, const int32_t* frames_host, int32_t B, int32_t S,
+                                  float* cond_dev, float* workspace_dev, void* stream);
 /* expand_feature(avg_fts, durations) (flowmatching.py:873-882) on the device: row b of out_dev [B, T, D] is feats_dev[b, 0] repeated
  * durations[b, 0, 0] times, then durations[b, 0, 1] zero rows, then unit 1 ...  durations_dev [B, S, 2] int32 >= 0; every row must
  * sum to T (upstream's torch.stack refuses ragged rows), else an error.  Synchronises `stream` once (the check);
@@ -404,6 +420,19 @@ int sylber_cfm_sample(sylber_cfm_t h, const float* cond_emb_dev, int32_t B, int3
  * art_dev[b, t] = 0 for t >= frames_host[b].  frames_host [B] in [1, T], read before the call returns.  Same workspace size. */
 int sylber_cfm_sample_frames(sylber_cfm_t h, const float* cond_emb_dev, const int32_t* frames_host, int32_t B, int32_t T, int32_t steps,
                              const float* y0_dev, float pitch_amp, float* art_dev, void* workspace_dev, void* stream);
+/* packed batches: no padding to the longest clip.  Clip b (frames_host[b] >= 1 frames) gets a decoder slot of round_up(16 + frames_host[b], 64)
+ * rows -- 16 register rows, its frames, zero rows -- and the slots follow each other: slot b = rows [slot_offsets[b], slot_offsets[b + 1]).
+ * The multiple of 64 keeps every attention key tile inside its own slot.  Host only, no GPU; fails (status 1) on B < 1, a count below 1
+ * or slots totalling 2^24 rows or more.  slot_offsets: [B + 1] out. */
+int sylber_cfm_packed_layout(const int32_t* frames_host, int32_t B, int32_t* slot_offsets);
+/* bytes of caller-owned device workspace for a sylber_cfm_sample_packed call (-1 on error) */
+int64_t sylber_cfm_workspace_bytes_packed(sylber_cfm_t h, const int32_t* frames_host, int32_t B);
+/* sylber_cfm_sample_frames of a packed batch: cond_dev [sum frames, 256], y0_dev (nullable) and art_dev [sum frames, 14] hold each clip's
+ * frames back to back (clip b from row frames_host[0] + ... + frames_host[b - 1]).  Clip b's art is bit-identical to sylber_cfm_sample_frames'
+ * row b (and to the clip alone).  SYLBER_BF16 and SYLBER_FP16 handles only; a count below 1, B < 1, steps outside 1..65 and an fp32
+ * handle return status 1 before any launch.  frames_host is read before the call returns. */
+int sylber_cfm_sample_packed(sylber_cfm_t h, const float* cond_dev, const int32_t* frames_host, int32_t B, int32_t steps, const float* y0_dev,
+                             float pitch_amp, float* art_dev, void* workspace_dev, void* stream);
 /* one velocity evaluation v_dev [B,T,14] = Regressor(x_dev [B,T,14], t, cond_emb_dev) (test aid: localises errors) */
 int sylber_cfm_eval(sylber_cfm_t h, const float* x_dev, float t, const float* cond_emb_dev, int32_t B, int32_t T, float* v_dev,
                     void* workspace_dev, void* stream);

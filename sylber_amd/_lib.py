@@ -125,6 +125,15 @@ EXPORTS = {
     "sylber_packed_gather": (c_int, [c_void_p, POINTER(c_int32), c_int32, c_void_p, c_void_p]),
     "sylber_segment_packed": (c_int, [c_void_p, c_void_p, POINTER(c_int32), c_int32, c_float, c_float, c_void_p, c_void_p, c_void_p,
                                       c_void_p]),
+    "sylber_cfm_packed_layout": (c_int, [POINTER(c_int32), c_int32, POINTER(c_int32)]),
+    "sylber_cfm_workspace_bytes_packed": (c_int64, [c_void_p, POINTER(c_int32), c_int32]),
+    "sylber_cfm_sample_packed": (c_int, [c_void_p, c_void_p, POINTER(c_int32), c_int32, c_int32, c_void_p, c_float, c_void_p, c_void_p,
+                                         c_void_p]),
+    "sylber_condition_packed_workspace_floats": (c_int64, [c_void_p, c_int32, c_int32]),
+    "sylber_condition_packed": (c_int, [c_void_p, c_void_p, POINTER(c_int32), POINTER(c_int32), c_int32, c_void_p, c_void_p, c_void_p,
+                                        c_int32, c_int32, c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "sylber_condition_units_packed": (c_int, [c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_void_p,
+                                              POINTER(c_int32), c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
     "sylber_op_attention": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32,
                                     c_int32, c_void_p]),
 }

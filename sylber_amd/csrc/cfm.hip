@@ -21,6 +21,13 @@
 // sylber_cfm_sample_frames: row b has its own frame count Tb (the workspace's `valid` slots hold 16 + Tb).  cfm_conv treats frames at
 // or past Tb as the zero padding at the end and writes zero rows there, attention masks keys at or past 16 + Tb, and cfm_final writes
 // 0 to the output frames at or past Tb: every other launch is row-local, so row b computes what a [1, Tb] call computes.
+// sylber_cfm_sample_packed: no padding to the longest clip.  The x-side buffers (x, h, qkv, ctx, ff, g, q / k / V^T) hold ONE
+// pseudo-utterance of Ptot rows: clip b owns the slot [slot[b], slot[b + 1]) of round_up(16 + Tb, 64) rows (registers, its frames, zero
+// rows).  The frame-side buffers (cond, xe, the sampler state, art) hold the clips' frames back to back: clip b is rows [F_b, F_b + Tb).
+// The slot table (CfmLayout::o_valid, cfm_packed_table) is read by cfm_conv, cfm_qkprep (rotary positions from the slot start), the
+// packed attention (keys in 64-tiles from the slot start, context rows [16 + Tb, slot end) zeroed) and cfm_final; every other launch is
+// row-local and runs unchanged on M = Ptot (the GEMMs' per-row bits depend neither on M nor on the tile), so clip b computes what a
+// [1, Tb] call computes.
 #include "kernels.h"
 #include "../../include/sylber_hip.h"
 #include <cmath>
@@ -66,18 +73,22 @@ struct sylber_cfm {
 // ---- workspace layout ----------------------------------------------------------------------------------------------
 struct CfmLayout {
     int B, T, L, Tp, Tpv; long M;
+    long NF;                      // frame rows of cond / xe / the sampler state: B * T, or sum Tb (packed)
+    int nclip = 0;                // packed: the clips (B = 1 and Tp = Tpv = M = Ptot for every x-side launch); 0: padded
+    int total_qb = 0;             // packed: sum of ceil((16 + Tb) / 128), the attention's query blocks
     size_t o_cond, o_condx, o_xe, o_x, o_h, o_qkv, o_qkvf, o_q, o_k, o_vt, o_ctx, o_ff, o_g, o_temb, o_gb, o_y, o_valid, o_total;
 };
-static CfmLayout cfm_layout(int precision, int B, int T) {
-    CfmLayout l;
-    l.B = B; l.T = T; l.L = CFM_REG + T; l.Tp = (l.L + 31) & ~31; l.Tpv = (l.Tp + 63) & ~63; l.M = (long)B * l.Tp;
+// x-side geometry set by the callers below; ntab: ints of the per-clip tables (the last region, never cleared by cfm_prepare)
+static void cfm_layout_buffers(int precision, CfmLayout& l, size_t ntab) {
+    const int B = l.B;
     const size_t e = precision == SYLBER_FP32 ? 4 : 2;      // bytes of one GEMM operand element
     const size_t Ms = (size_t)l.M + CFM_SLACK;
     size_t o = 0;
     auto take = [&](size_t bytes) { size_t r = o; o = (o + bytes + 255) & ~(size_t)255; return r; };
-    l.o_cond = take(((size_t)B * T + CFM_SLACK) * CFM_COND * e);
-    l.o_condx = take((size_t)B * T * CFM_D * 4);
-    l.o_xe = take((size_t)B * T * CFM_D * 4);
+    const size_t NF = (size_t)l.NF;
+    l.o_cond = take((NF + CFM_SLACK) * CFM_COND * e);
+    l.o_condx = take(NF * CFM_D * 4);
+    l.o_xe = take(NF * CFM_D * 4);
     l.o_x = take(Ms * CFM_D * 4);
     l.o_h = take(Ms * CFM_D * e);
     l.o_qkv = take(Ms * 3 * CFM_D * 4);
@@ -96,9 +107,47 @@ static CfmLayout cfm_layout(int precision, int B, int T) {
     l.o_g = take(Ms * CFM_FIP * e);
     l.o_temb = take((size_t)CFM_MAX_TIMES * CFM_TH * 4);
     l.o_gb = take((size_t)CFM_MAX_TIMES * CFM_NORMS * 2 * CFM_D * 4);
-    l.o_y = take((size_t)B * T * CFM_OUT * 4);
-    l.o_valid = take((size_t)B * 4);                         // sylber_cfm_sample_frames: 16 + Tb per row
+    l.o_y = take(NF * CFM_OUT * 4);
+    l.o_valid = take(ntab * 4);                              // sylber_cfm_sample_frames: 16 + Tb per row; packed: cfm_packed_table
     l.o_total = o;
+}
+static CfmLayout cfm_layout(int precision, int B, int T) {
+    CfmLayout l;
+    l.B = B; l.T = T; l.L = CFM_REG + T; l.Tp = (l.L + 31) & ~31; l.Tpv = (l.Tp + 63) & ~63; l.M = (long)B * l.Tp; l.NF = (long)B * T;
+    cfm_layout_buffers(precision, l, (size_t)B);
+    return l;
+}
+
+// packed slots: slot[b + 1] - slot[b] = round_up(16 + Tb, 64) rows.  The 64 is what the packed attention needs: its key tiles start at
+// the slot start, so the last tile of a clip ends inside its own slot and never multiplies a neighbour's V.
+static bool cfm_slots(const int32_t* frames, int B, std::vector<int32_t>& slot, long& nf) {
+    slot.assign((size_t)B + 1, 0);
+    long off = 0; nf = 0;
+    for (int b = 0; b < B; ++b) {
+        if (frames[b] < 1) return false;
+        slot[b] = (int32_t)off;
+        off += ((long)CFM_REG + frames[b] + 63) & ~63L;
+        nf += frames[b];
+        if (off >= (1l << 24)) return false;                 // rows of the pseudo-utterance are int in every launch
+    }
+    slot[B] = (int32_t)off;
+    return true;
+}
+// the device table of a packed call: [slot offsets (B + 1) | 16 + Tb (B) | prefix of ceil((16 + Tb) / 128) (B + 1) | frame prefix F (B + 1)];
+// the first 3B + 2 entries are launch_attention_packed's pk
+static void cfm_packed_table(const int32_t* frames, int B, const std::vector<int32_t>& slot, std::vector<int32_t>& tab) {
+    tab.assign(4 * (size_t)B + 3, 0);
+    for (int b = 0; b <= B; ++b) tab[b] = slot[b];
+    for (int b = 0; b < B; ++b) {
+        tab[B + 1 + b] = CFM_REG + frames[b];
+        tab[2 * B + 2 + b] = tab[2 * B + 1 + b] + (CFM_REG + frames[b] + 127) / 128;
+        tab[3 * B + 3 + b] = tab[3 * B + 2 + b] + frames[b];
+    }
+}
+static CfmLayout cfm_layout_packed(int precision, int nclip, int Ptot, long NF) {
+    CfmLayout l;
+    l.B = 1; l.T = 0; l.L = l.Tp = l.Tpv = Ptot; l.M = Ptot; l.NF = NF; l.nclip = nclip;
+    cfm_layout_buffers(precision, l, 4 * (size_t)nclip + 3);
     return l;
 }
 
@@ -168,19 +217,37 @@ __global__ __launch_bounds__(256) void cfm_embed(const float* __restrict__ condx
     }
 }
 
+// packed calls: the clip whose entry of the ascending table tab[0 .. n) is the last one <= v (tab[0] == 0 <= v)
+__device__ __forceinline__ int cfm_clip_of(const int* __restrict__ tab, int n, long v) {
+    int lo = 0, hi = n - 1;
+    while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (tab[mid] <= v) lo = mid; else hi = mid - 1; }
+    return lo;
+}
+
 // x rows of batch element b: [registers (16); gelu(depthwise conv31(xe) + bias) + xe (T frames, zero padded at both ends);
 // zero rows up to Tp]
+// pk (packed, grid (Ptot, 1)): row blockIdx.x of the pseudo-utterance is row r of clip b's slot; the clip's frames are xe rows F_b ..
 __global__ __launch_bounds__(256) void cfm_conv(const float* __restrict__ xe, const float* __restrict__ w, const float* __restrict__ bias,
-                                                const float* __restrict__ reg, float* __restrict__ x, int T, int Tp, const int* __restrict__ valid) {
-    const int r = blockIdx.x, b = blockIdx.y;
-    const int Tb = valid ? valid[b] - CFM_REG : T;           // the row's own frames (T is the row pitch of xe)
-    float* dst = x + ((size_t)b * Tp + r) * CFM_D;
+                                                const float* __restrict__ reg, float* __restrict__ x, int T, int Tp, const int* __restrict__ valid,
+                                                const int* __restrict__ pk, int nclip) {
+    int r = blockIdx.x, b = blockIdx.y, Tb;
+    size_t f0;                                               // xe row of the clip's frame 0
+    if (pk) {
+        b = cfm_clip_of(pk, nclip, r);
+        r -= pk[b];
+        Tb = pk[nclip + 1 + b] - CFM_REG;
+        f0 = (size_t)pk[3 * nclip + 2 + b];
+    } else {
+        Tb = valid ? valid[b] - CFM_REG : T;                 // the row's own frames (T is the row pitch of xe)
+        f0 = (size_t)b * T;
+    }
+    float* dst = x + (pk ? (size_t)blockIdx.x : (size_t)b * Tp + r) * CFM_D;
     for (int c = threadIdx.x; c < CFM_D; c += 256) {
         float v;
         if (r < CFM_REG) v = reg[r * CFM_D + c];
         else if (r < CFM_REG + Tb) {
             const int t = r - CFM_REG;
-            const float* src = xe + (size_t)b * T * CFM_D + c;
+            const float* src = xe + f0 * CFM_D + c;
             float acc = bias[c];
             for (int k = 0; k < CFM_KW; ++k) {
                 const int tt = t + k - CFM_KW / 2;
@@ -220,10 +287,13 @@ __global__ __launch_bounds__(256) void cfm_adanorm(const float* __restrict__ x, 
 //   16-bit modes: q, k -> [B, 12, Tp, 64], v -> V^T [B, 12, 64, Tpv] with the key axis' bits 2 and 3 swapped (attention.hip);
 //                 q carries 10 * log2(e) (the 16-bit kernels take scores in log2 units)
 //   fp32 mode:    the fused [M, 2304] buffer of the fp32 attention, q carrying 80 (that kernel applies the exact 1/8 itself)
+//   pk (packed, B = 1, Tp = Tpv = Ptot): positions count from the row's slot start; slot starts are multiples of 64, so the key-axis
+//                 bit swap of the pseudo-utterance's row is the swap within the clip's own 64-key tile
 template <int FMT, bool F32>
 __global__ __launch_bounds__(256) void cfm_qkprep(const float* __restrict__ qkv, const float* __restrict__ qg, const float* __restrict__ kg,
                                                   const float* __restrict__ inv_freq, bf16_t* __restrict__ q16, bf16_t* __restrict__ k16,
-                                                  bf16_t* __restrict__ vt16, float* __restrict__ qkvf, int L, int Tp, int Tpv) {
+                                                  bf16_t* __restrict__ vt16, float* __restrict__ qkvf, int L, int Tp, int Tpv,
+                                                  const int* __restrict__ pk, int nclip) {
     const int r = blockIdx.x, b = blockIdx.y, head = blockIdx.z * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     const size_t row = (size_t)b * Tp + r;
     const float* src = qkv + row * 3 * CFM_D + head * 64 + lane;
@@ -231,7 +301,8 @@ __global__ __launch_bounds__(256) void cfm_qkprep(const float* __restrict__ qkv,
     const float qn = 1.0f / fmaxf(sqrtf(wave_sum(q * q)), 1e-12f), kn = 1.0f / fmaxf(sqrtf(wave_sum(k * k)), 1e-12f);
     q = (q * qn) * qg[head * 64 + lane] * 8.0f;
     k = (k * kn) * kg[head * 64 + lane] * 8.0f;
-    const float pos = r < CFM_REG ? -10000.0f : (float)(r - CFM_REG);
+    const int rs = pk ? r - pk[cfm_clip_of(pk, nclip, r)] : r;     // row within its slot
+    const float pos = rs < CFM_REG ? -10000.0f : (float)(rs - CFM_REG);
     const float ang = __fmul_rn(pos, inv_freq[lane & 31]);
     const float cs = cosf(ang), sn = sinf(ang);
     const float qo = __shfl_xor(q, 32, 64), ko = __shfl_xor(k, 32, 64);
@@ -267,18 +338,27 @@ __global__ __launch_bounds__(256) void cfm_geglu(const float* __restrict__ ff, v
 // final RMSNorm + to_pred of the frame rows, fused with the sampler: one wave per frame.
 //   mode 0: out = v;  mode 1: ymid = y + v * hdt;  mode 2: y = y + dt * v (in place), channel 12 / pitch_amp when `last`
 // (y and out may alias: each element is read and written by the same lane)
+// pk (packed, B = the clips): frame fr of the state is frame t = fr - F_b of clip b, x row slot[b] + 16 + t
 __global__ __launch_bounds__(256) void cfm_final(const float* __restrict__ x, const float* __restrict__ gamma, const float* __restrict__ wp,
-                                                 const float* y, float* out, int B, int T, int Tp, int mode,
-                                                 float dt, int last, float pitch_amp, const int* __restrict__ valid) {
+                                                 const float* y, float* out, long NF, int B, int T, int Tp, int mode,
+                                                 float dt, int last, float pitch_amp, const int* __restrict__ valid, const int* __restrict__ pk) {
     const long fr = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
-    if (fr >= (long)B * T) return;
-    const int b = (int)(fr / T), t = (int)(fr % T);
-    if (valid && t >= valid[b] - CFM_REG) {                  // past the row's own frames: 0 (wave-uniform)
-        if (lane < CFM_OUT) out[(size_t)fr * CFM_OUT + lane] = 0.f;
-        return;
+    if (fr >= NF) return;
+    size_t xrow;
+    if (pk) {
+        const int* F = pk + 3 * B + 2;
+        const int b = cfm_clip_of(F, B, fr);
+        xrow = (size_t)pk[b] + CFM_REG + (size_t)(fr - F[b]);
+    } else {
+        const int b = (int)(fr / T), t = (int)(fr % T);
+        if (valid && t >= valid[b] - CFM_REG) {              // past the row's own frames: 0 (wave-uniform)
+            if (lane < CFM_OUT) out[(size_t)fr * CFM_OUT + lane] = 0.f;
+            return;
+        }
+        xrow = (size_t)b * Tp + CFM_REG + t;
     }
-    const float* xr = x + ((size_t)b * Tp + CFM_REG + t) * CFM_D;
+    const float* xr = x + xrow * CFM_D;
     float v[8], ss = 0.f;
 #pragma unroll
     for (int j = 0; j < 8; ++j) { v[j] = xr[j * 64 + lane]; ss = fmaf(v[j], v[j], ss); }
@@ -351,19 +431,21 @@ static void cfm_linspace(int steps, std::vector<float>& t) {
 }
 
 // one evaluation of the decoder at yin (fp32 [B, T, 14]) and time index ti; writes per `mode` (see cfm_final) with the
-// update's base state ybase.  valid: nullptr (every row T frames) or the workspace's per-row 16 + Tb (sylber_cfm_sample_frames)
+// update's base state ybase.  valid: nullptr (every row T frames) or the workspace's per-row 16 + Tb (sylber_cfm_sample_frames);
+// a packed layout (l.nclip > 0) reads its table from the workspace instead (16-bit modes only)
 static int cfm_evaluate(const sylber_cfm* h, const CfmLayout& l, char* ws, int ti, const float* yin, const float* ybase, float* out, int mode, float dt,
                         int last, float pitch_amp, hipStream_t s, const int* valid = nullptr) {
     const bool f32 = h->precision == SYLBER_FP32;
-    const int B = l.B, T = l.T;
+    const int B = l.B, T = l.T, nclip = l.nclip;
+    const int* pk = nclip ? (const int*)(ws + l.o_valid) : nullptr;
     float* xe = (float*)(ws + l.o_xe); float* x = (float*)(ws + l.o_x); void* hb = ws + l.o_h;
     float* qkv = (float*)(ws + l.o_qkv); void* ctx = ws + l.o_ctx; float* ff = (float*)(ws + l.o_ff); void* g = ws + l.o_g;
     const float* gb = (const float*)(ws + l.o_gb) + (size_t)ti * CFM_NORMS * 2 * CFM_D;
     const int M = (int)l.M;
     const dim3 rows4((unsigned)((l.M + 3) / 4));
-    hipLaunchKernelGGL(cfm_embed, dim3(B * T), dim3(256), 0, s, (const float*)(ws + l.o_condx), yin, h->wy, xe);
+    hipLaunchKernelGGL(cfm_embed, dim3((unsigned)l.NF), dim3(256), 0, s, (const float*)(ws + l.o_condx), yin, h->wy, xe);
     CFM_RUN("embed", 0);
-    hipLaunchKernelGGL(cfm_conv, dim3(l.Tp, B), dim3(256), 0, s, xe, h->conv_w, h->conv_b, h->reg, x, T, l.Tp, valid);
+    hipLaunchKernelGGL(cfm_conv, dim3(l.Tp, B), dim3(256), 0, s, xe, h->conv_w, h->conv_b, h->reg, x, T, l.Tp, valid, pk, nclip);
     CFM_RUN("conv", 0);
     auto norm = [&](int n) {
         const float* ga = gb + (size_t)n * 2 * CFM_D;
@@ -379,15 +461,18 @@ static int cfm_evaluate(const sylber_cfm* h, const CfmLayout& l, char* ws, int t
         const dim3 gq(l.L, B, 2);
         if (f32) {
             float* qkvf = (float*)(ws + l.o_qkvf);
-            hipLaunchKernelGGL((cfm_qkprep<FMT_BF16, true>), gq, dim3(256), 0, s, qkv, qg, kg, h->inv_freq, nullptr, nullptr, nullptr, qkvf, l.L, l.Tp, l.Tpv);
+            hipLaunchKernelGGL((cfm_qkprep<FMT_BF16, true>), gq, dim3(256), 0, s, qkv, qg, kg, h->inv_freq, nullptr, nullptr, nullptr, qkvf, l.L, l.Tp, l.Tpv,
+                               nullptr, 0);
             CFM_RUN("qkprep", 0);
             CFM_RUN("attention", launch_attention_f32(qkvf, qkvf + SYL_HIDDEN, qkvf + 2 * SYL_HIDDEN, valid, (float*)ctx, B, l.L, l.Tp, s));
         } else {
             bf16_t* q = (bf16_t*)(ws + l.o_q); bf16_t* k = (bf16_t*)(ws + l.o_k); bf16_t* vt = (bf16_t*)(ws + l.o_vt);
-            if (h->fmt == FMT_F16) hipLaunchKernelGGL((cfm_qkprep<FMT_F16, false>), gq, dim3(256), 0, s, qkv, qg, kg, h->inv_freq, q, k, vt, nullptr, l.L, l.Tp, l.Tpv);
-            else hipLaunchKernelGGL((cfm_qkprep<FMT_BF16, false>), gq, dim3(256), 0, s, qkv, qg, kg, h->inv_freq, q, k, vt, nullptr, l.L, l.Tp, l.Tpv);
+            if (h->fmt == FMT_F16) hipLaunchKernelGGL((cfm_qkprep<FMT_F16, false>), gq, dim3(256), 0, s, qkv, qg, kg, h->inv_freq, q, k, vt, nullptr, l.L, l.Tp, l.Tpv,
+                                                      pk, nclip);
+            else hipLaunchKernelGGL((cfm_qkprep<FMT_BF16, false>), gq, dim3(256), 0, s, qkv, qg, kg, h->inv_freq, q, k, vt, nullptr, l.L, l.Tp, l.Tpv, pk, nclip);
             CFM_RUN("qkprep", 0);
-            CFM_RUN("attention", launch_attention(q, k, vt, valid, (bf16_t*)ctx, B, l.L, l.Tp, l.Tpv, 0, s, h->fmt));
+            if (pk) CFM_RUN("attention", launch_attention_packed(q, k, vt, pk, nclip, l.total_qb, (bf16_t*)ctx, l.Tp, s, h->fmt));
+            else CFM_RUN("attention", launch_attention(q, k, vt, valid, (bf16_t*)ctx, B, l.L, l.Tp, l.Tpv, 0, s, h->fmt));
         }
         CFM_RUN("out", cfm_gemm(h, ctx, SYL_HIDDEN, h->wo[li], M, CFM_D, CFM_D, nullptr, x, CFM_D, true, s));
         norm(2 * li + 1);
@@ -399,8 +484,8 @@ static int cfm_evaluate(const sylber_cfm* h, const CfmLayout& l, char* ws, int t
         CFM_RUN("geglu", 0);
         CFM_RUN("ff2", cfm_gemm(h, g, CFM_FIP, h->w2[li], M, CFM_D, CFM_FIP, h->b2 + (size_t)li * CFM_D, x, CFM_D, true, s));
     }
-    hipLaunchKernelGGL(cfm_final, dim3((unsigned)(((long)B * T + 3) / 4)), dim3(256), 0, s, x, h->fin_g, h->pred_w, ybase, out, B, T, l.Tp, mode,
-                       dt, last, pitch_amp, valid);
+    hipLaunchKernelGGL(cfm_final, dim3((unsigned)((l.NF + 3) / 4)), dim3(256), 0, s, x, h->fin_g, h->pred_w, ybase, out, l.NF, nclip ? nclip : B, T,
+                       l.Tp, mode, dt, last, pitch_amp, valid, pk);
     CFM_RUN("final", 0);
     return 0;
 }
@@ -408,13 +493,13 @@ static int cfm_evaluate(const sylber_cfm* h, const CfmLayout& l, char* ws, int t
 // per call: clear the workspace, the conditioning GEMM (once), the time conditioning of every time of the call
 static int cfm_prepare(const sylber_cfm* h, const CfmLayout& l, char* ws, const float* cond_dev, const float* times, int ntimes, hipStream_t s) {
     HIP_TRY(hipMemsetAsync(ws, 0, l.o_valid, s));          // (everything but the per-row counts, the last region: written before this)
-    const size_t n = (size_t)l.B * l.T * CFM_COND;
+    const size_t n = (size_t)l.NF * CFM_COND;
     void* cb = ws + l.o_cond;
     if (h->precision == SYLBER_FP32) HIP_TRY(hipMemcpyAsync(cb, cond_dev, n * 4, hipMemcpyDeviceToDevice, s));
     else if (h->fmt == FMT_F16) hipLaunchKernelGGL(cfm_convert<FMT_F16>, dim3(1024), dim3(256), 0, s, cond_dev, (bf16_t*)cb, n);
     else hipLaunchKernelGGL(cfm_convert<FMT_BF16>, dim3(1024), dim3(256), 0, s, cond_dev, (bf16_t*)cb, n);
     CFM_RUN("convert", 0);
-    CFM_RUN("cond", cfm_gemm(h, cb, CFM_COND, h->wc, l.B * l.T, CFM_D, CFM_COND, h->by, (float*)(ws + l.o_condx), CFM_D, false, s));
+    CFM_RUN("cond", cfm_gemm(h, cb, CFM_COND, h->wc, (int)l.NF, CFM_D, CFM_COND, h->by, (float*)(ws + l.o_condx), CFM_D, false, s));
     CfmTimes ts = {};
     for (int i = 0; i < ntimes; ++i) ts.t[i] = times[i];
     float* temb = (float*)(ws + l.o_temb);
@@ -555,6 +640,9 @@ static int cfm_check(const char* what, sylber_cfm_t h, const float* cond, int B,
 }
 
 // frames_host: nullptr (sylber_cfm_sample) or each row's own frame count (sylber_cfm_sample_frames)
+static int cfm_steps(const sylber_cfm* h, const CfmLayout& l, char* ws, const float* cond_emb_dev, int steps, const float* y0_dev, float pitch_amp,
+                     float* art_dev, size_t n, int T, const int* valid, hipStream_t s);
+
 static int cfm_sample(const char* what, sylber_cfm_t h, const float* cond_emb_dev, const int32_t* frames_host, int32_t B, int32_t T, int32_t steps,
                       const float* y0_dev, float pitch_amp, float* art_dev, void* workspace_dev, void* stream) {
     if (cfm_check(what, h, cond_emb_dev, B, T, art_dev, workspace_dev)) return 1;
@@ -573,6 +661,12 @@ static int cfm_sample(const char* what, sylber_cfm_t h, const float* cond_emb_de
         valid = (int*)(ws + l.o_valid);
         if (launch_upload_ints(valid, frames_host, B, CFM_REG, s)) return 1;
     }
+    return cfm_steps(h, l, ws, cond_emb_dev, steps, y0_dev, pitch_amp, art_dev, n, T, valid, s);
+}
+
+// the sampler over a prepared layout: art (n = NF * 14 floats) is the state; valid / T: cfm_init_state's masking (padded rows)
+static int cfm_steps(const sylber_cfm* h, const CfmLayout& l, char* ws, const float* cond_emb_dev, int steps, const float* y0_dev, float pitch_amp,
+                     float* art_dev, size_t n, int T, const int* valid, hipStream_t s) {
     // art is the sampler state; steps == 1 is a one-point grid (the state is y0) and scales channel 12 right away
     hipLaunchKernelGGL(cfm_init_state, dim3(256), dim3(256), 0, s, y0_dev, art_dev, n, steps == 1 ? 1 : 0, pitch_amp, valid, T);
     HIP_TRY(hipGetLastError());
@@ -604,6 +698,56 @@ extern "C" int sylber_cfm_sample_frames(sylber_cfm_t h, const float* cond_emb_de
                                         int32_t steps, const float* y0_dev, float pitch_amp, float* art_dev, void* workspace_dev, void* stream) {
     if (!frames_host) { syl_set_error("sylber_cfm_sample_frames", "null argument"); return 1; }
     return cfm_sample("sylber_cfm_sample_frames", h, cond_emb_dev, frames_host, B, T, steps, y0_dev, pitch_amp, art_dev, workspace_dev, stream);
+}
+
+// ---- packed batches ----------------------------------------------------------------------------------------------------
+extern "C" int sylber_cfm_packed_layout(const int32_t* frames_host, int32_t B, int32_t* slot_offsets) {
+    if (!frames_host || !slot_offsets || B < 1) { syl_set_error("sylber_cfm_packed_layout", "need B >= 1 and non-null arrays"); return 1; }
+    std::vector<int32_t> slot;
+    long nf = 0;
+    if (!cfm_slots(frames_host, B, slot, nf)) {
+        syl_set_error("sylber_cfm_packed_layout", "every clip needs >= 1 frame, and the slots must total fewer than 2^24 rows"); return 1;
+    }
+    std::copy(slot.begin(), slot.end(), slot_offsets);
+    return 0;
+}
+
+// the checks every packed entry point makes before it touches the device
+static bool cfm_packed_check(const char* what, sylber_cfm_t h, const int32_t* frames_host, int B, std::vector<int32_t>& slot, long& nf) {
+    if (!h || !frames_host) { syl_set_error(what, "null argument"); return false; }
+    if (B < 1) { syl_set_error(what, "need B >= 1"); return false; }
+    if (h->precision != SYLBER_BF16 && h->precision != SYLBER_FP16) {
+        syl_set_error(what, "packed batches run in the bf16 and fp16 precisions only"); return false;
+    }
+    if (!cfm_slots(frames_host, B, slot, nf)) { syl_set_error(what, "every clip needs >= 1 frame, and the slots must total fewer than 2^24 rows"); return false; }
+    return true;
+}
+
+extern "C" int64_t sylber_cfm_workspace_bytes_packed(sylber_cfm_t h, const int32_t* frames_host, int32_t B) {
+    std::vector<int32_t> slot;
+    long nf = 0;
+    if (!cfm_packed_check("sylber_cfm_workspace_bytes_packed", h, frames_host, B, slot, nf)) return -1;
+    return (int64_t)cfm_layout_packed(h->precision, B, slot[B], nf).o_total;
+}
+
+extern "C" int sylber_cfm_sample_packed(sylber_cfm_t h, const float* cond_dev, const int32_t* frames_host, int32_t B, int32_t steps,
+                                        const float* y0_dev, float pitch_amp, float* art_dev, void* workspace_dev, void* stream) {
+    static const char* what = "sylber_cfm_sample_packed";
+    std::vector<int32_t> slot;
+    long nf = 0;
+    if (!cfm_packed_check(what, h, frames_host, B, slot, nf)) return 1;
+    if (!cond_dev || !art_dev || !workspace_dev) { syl_set_error(what, "null argument"); return 1; }
+    if (steps < 1 || 2 * (steps - 1) > CFM_MAX_TIMES) { syl_set_error(what, "steps must be in 1..65"); return 1; }
+    if (!(pitch_amp != 0.0f) || !std::isfinite(pitch_amp)) { syl_set_error(what, "pitch_amp must be finite and nonzero"); return 1; }
+    std::vector<int32_t> tab;
+    cfm_packed_table(frames_host, B, slot, tab);
+    DevGuardC dg(h->device);
+    hipStream_t s = (hipStream_t)stream;
+    CfmLayout l = cfm_layout_packed(h->precision, B, slot[B], nf);
+    l.total_qb = tab[3 * (size_t)B + 1];
+    char* ws = (char*)workspace_dev;
+    if (launch_upload_ints((int*)(ws + l.o_valid), tab.data(), (int)tab.size(), 0, s)) return 1;
+    return cfm_steps(h, l, ws, cond_dev, steps, y0_dev, pitch_amp, art_dev, (size_t)nf * CFM_OUT, 1, nullptr, s);
 }
 
 extern "C" int sylber_cfm_eval(sylber_cfm_t h, const float* x_dev, float t, const float* cond_emb_dev, int32_t B, int32_t T, float* v_dev,

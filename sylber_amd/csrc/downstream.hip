@@ -446,17 +446,36 @@ __global__ __launch_bounds__(256) void cond_gather_kernel(const float* __restric
     for (int c = threadIdx.x; c < D; c += 256) rows[(size_t)r * D + c] = ok ? feat[((size_t)b * T + j) * D + c] : 0.f;
 }
 
+// packed batches (sylber_condition_packed / sylber_condition_units_packed): output frame f is frame t = f - F[b] of clip b, where
+// pk = [F (B + 1): frame prefix | frames (B) | encoder row of each clip's frame 0 (B)] and b is the last clip with F[b] <= f
+__device__ __forceinline__ int cond_clip_of(const int* __restrict__ F, int B, long f) {
+    int lo = 0, hi = B - 1;
+    while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (F[mid] <= f) lo = mid; else hi = mid - 1; }
+    return lo;
+}
+
 // one wave per frame: its segment (the LAST one containing it, like the sequential slice assignment at :126), the
 // hidden-state norm ((h**2).sum(-1)+1e-8)**.5 (:110), and the masked conditioning row (:138-139)
+// T: the pitch of seg / feat (and of hidden and the outputs when pk is null); pk: the packed tables (frames back to back, nf of them)
 __global__ __launch_bounds__(256) void cond_scatter_kernel(const float* __restrict__ hidden, const int64_t* __restrict__ seg,
                                                            const int32_t* __restrict__ nseg, const float* __restrict__ feat,
                                                            const float* __restrict__ mlp_rows, int B, int T, int S, int D, int OD, float thr,
-                                                           float* __restrict__ avg_out, float* __restrict__ cond_out) {
+                                                           float* __restrict__ avg_out, float* __restrict__ cond_out,
+                                                           const int* __restrict__ pk, long nf) {
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const long f = (long)blockIdx.x * 4 + wave;
-    if (f >= (long)B * T) return;
-    const int b = (int)(f / T), t = (int)(f - (long)b * T);
-    const float* h = hidden + (size_t)f * D;
+    if (f >= nf) return;
+    int b, t;
+    size_t hrow;
+    if (pk) {
+        b = cond_clip_of(pk, B, f);
+        t = (int)(f - pk[b]);
+        hrow = (size_t)pk[2 * B + 1 + b] + t;
+    } else {
+        b = (int)(f / T); t = (int)(f - (long)b * T);
+        hrow = (size_t)f;
+    }
+    const float* h = hidden + hrow * D;
     float s = 0.f;
     for (int c = lane; c < D; c += 64) s = fmaf(h[c], h[c], s);
     s = wave_sum(s);
@@ -516,7 +535,7 @@ extern "C" int sylber_condition(sylber_mlp_t m, const float* hidden_dev, const i
     if (run_mlp(m, x0, R, ha, hb, hc, yo, s)) return 1;
     const long frames = (long)B * T;
     hipLaunchKernelGGL(cond_scatter_kernel, dim3((unsigned)((frames + 3) / 4)), dim3(256), 0, s, hidden_dev, seg_dev, nseg_dev, feat_dev, yo, B, T, S, D,
-                       m->output_dim, norm_thr, avg_hidden_dev, cond_dev);
+                       m->output_dim, norm_thr, avg_hidden_dev, cond_dev, nullptr, frames);
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -626,15 +645,17 @@ __global__ __launch_bounds__(256) void units_gather_kernel(const int32_t* __rest
 }
 
 // one wave per frame: the MLP row of the LAST unit whose span holds the frame; 0 where no span does, past frames[b], or
-// where the unit's decoded row is silent
+// where the unit's decoded row is silent.  pk (packed): the clips' frames back to back, nf of them (cond_clip_of)
 __global__ __launch_bounds__(256) void units_expand_cond_kernel(const int32_t* __restrict__ spans, const int32_t* __restrict__ nunits,
                                                                 const int32_t* __restrict__ frames, const int32_t* __restrict__ keep,
                                                                 const float* __restrict__ mlp_rows, int B, int T, int S, int OD,
-                                                                float* __restrict__ cond_out) {
+                                                                float* __restrict__ cond_out, const int* __restrict__ pk, long nf) {
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const long f = (long)blockIdx.x * 4 + wave;
-    if (f >= (long)B * T) return;
-    const int b = (int)(f / T), t = (int)(f - (long)b * T);
+    if (f >= nf) return;
+    int b, t;
+    if (pk) { b = cond_clip_of(pk, B, f); t = (int)(f - pk[b]); }
+    else { b = (int)(f / T); t = (int)(f - (long)b * T); }
     int n = nunits[b]; n = n < 0 ? 0 : (n > S ? S : n);
     int j = -1;
     for (int q = lane; q < n; q += 64) {
@@ -678,7 +699,102 @@ extern "C" int sylber_condition_units(sylber_mlp_t m, const float* c1_dev, int32
     if (run_mlp(m, x0, R, ha, hb, hc, yo, s)) return 1;
     const long frames = (long)B * T;
     hipLaunchKernelGGL(units_expand_cond_kernel, dim3((unsigned)((frames + 3) / 4)), dim3(256), 0, s, spans_dev, nunits_dev, frames_dev, keep, yo,
-                       B, T, S, m->output_dim, cond_dev);
+                       B, T, S, m->output_dim, cond_dev, nullptr, frames);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// ---- packed batches: the conditioning of each clip's own frames, back to back --------------------------------------------
+// Clip b's frame t is output row F_b + t (F_b = frames[0] + ... + frames[b - 1]), so the decoder's packed call reads `cond` as it is.
+// The MLP rows and the per-frame decisions are the padded calls' (cond_gather_kernel / units_gather_kernel and run_mlp see the same
+// B * S + 1 rows); only the frame -> (clip, t) map of the scatter differs, so each row is bitwise the batch-invariant call's.
+extern "C" int64_t sylber_condition_packed_workspace_floats(sylber_mlp_t m, int32_t B, int32_t S) {
+    const int64_t base = sylber_condition_units_workspace_floats(m, B, S);
+    if (base < 0) return -1;
+    return base + 3 * (int64_t)B + 1 + 64;
+}
+
+// the host checks of both packed calls and the upload of their table (at the end of the workspace); nf: the frames in all
+static int cond_packed_table(const char* what, sylber_mlp_t m, const int32_t* frames_host, const int32_t* offsets_host, int B, int S,
+                             float* workspace_dev, int** pk_dev, long& nf, int& fmax, hipStream_t s) {
+    std::vector<int32_t> tab(3 * (size_t)B + 1, 0);
+    nf = 0; fmax = 0;
+    for (int b = 0; b < B; ++b) {
+        const int fb = frames_host[b];
+        if (fb < 1) { syl_set_error(what, "every clip needs >= 1 frame"); return 1; }
+        if (offsets_host && (offsets_host[b] < 0 || (long)offsets_host[b] + fb > offsets_host[b + 1])) {
+            syl_set_error(what, "clip b's frames must lie inside [offsets[b], offsets[b + 1])"); return 1;
+        }
+        tab[b] = (int32_t)nf;
+        tab[B + 1 + b] = fb;
+        tab[2 * B + 1 + b] = offsets_host ? offsets_host[b] : 0;
+        nf += fb;
+        fmax = fb > fmax ? fb : fmax;
+        if (nf >= (1l << 31)) { syl_set_error(what, "too many frames"); return 1; }
+    }
+    tab[B] = (int32_t)nf;
+    *pk_dev = (int*)(workspace_dev + sylber_condition_units_workspace_floats(m, B, S));
+    return launch_upload_ints(*pk_dev, tab.data(), (int)tab.size(), 0, s);
+}
+
+extern "C" int sylber_condition_packed(sylber_mlp_t m, const float* hidden_dev, const int32_t* offsets_host, const int32_t* frames_host, int32_t B,
+                                       const int64_t* seg_dev, const int32_t* nseg_dev, const float* feat_dev, int32_t K, int32_t S, float norm_thr,
+                                       float* avg_hidden_dev, float* cond_dev, float* workspace_dev, void* stream) {
+    static const char* what = "sylber_condition_packed";
+    hipStream_t s = (hipStream_t)stream;
+    if (!m || !hidden_dev || !offsets_host || !frames_host || !seg_dev || !nseg_dev || !feat_dev || !cond_dev || !workspace_dev) {
+        syl_set_error(what, "null argument"); return 1;
+    }
+    if (B < 1 || K < 1 || S < 1 || S > K) { syl_set_error(what, "need B, K >= 1 and 1 <= S <= K"); return 1; }
+    for (int b = 0; b < B; ++b)
+        if (frames_host[b] > K) { syl_set_error(what, "frame counts must be <= K (the tables' pitch)"); return 1; }
+    DevGuard dg(m->device);
+    int* pk = nullptr;
+    long nf = 0;
+    int fmax = 0;
+    if (cond_packed_table(what, m, frames_host, offsets_host, B, S, workspace_dev, &pk, nf, fmax, s)) return 1;
+    const int D = m->input_dim, R = B * S + 1, MD = mlp_maxdim(m);
+    float* x0 = workspace_dev;
+    float* ha = x0 + (size_t)R * D; float* hb = ha + (size_t)R * MD; float* hc = hb + (size_t)R * MD;
+    float* yo = hc + (size_t)R * MD;
+    hipLaunchKernelGGL(cond_gather_kernel, dim3(R), dim3(256), 0, s, feat_dev, nseg_dev, x0, B, K, S, D);
+    HIP_TRY(hipGetLastError());
+    if (run_mlp(m, x0, R, ha, hb, hc, yo, s)) return 1;
+    hipLaunchKernelGGL(cond_scatter_kernel, dim3((unsigned)((nf + 3) / 4)), dim3(256), 0, s, hidden_dev, seg_dev, nseg_dev, feat_dev, yo, B, K, S, D,
+                       m->output_dim, norm_thr, avg_hidden_dev, cond_dev, pk, nf);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+extern "C" int sylber_condition_units_packed(sylber_mlp_t m, const float* c1_dev, int32_t K1, const float* c2_dev, int32_t K2, const int32_t* units_dev,
+                                             const int32_t* spans_dev, const int32_t* nunits_dev, const int32_t* frames_host, int32_t B, int32_t S,
+                                             float* cond_dev, float* workspace_dev, void* stream) {
+    static const char* what = "sylber_condition_units_packed";
+    hipStream_t s = (hipStream_t)stream;
+    if (!m || !c1_dev || !units_dev || !spans_dev || !nunits_dev || !frames_host || !cond_dev || !workspace_dev) { syl_set_error(what, "null argument"); return 1; }
+    if (B < 1 || S < 1 || K1 < 1 || (c2_dev && K2 < 1)) { syl_set_error(what, "need B, S, K1 >= 1 (and K2 >= 1 with a second codebook)"); return 1; }
+    DevGuard dg(m->device);
+    int* pk = nullptr;
+    long nf = 0;
+    int T = 0;                                               // the padded call's T: spans are checked against the longest clip
+    if (cond_packed_table(what, m, frames_host, nullptr, B, S, workspace_dev, &pk, nf, T, s)) return 1;
+    const int D = m->input_dim, R = B * S + 1, MD = mlp_maxdim(m), ncb = c2_dev ? 2 : 1;
+    float* x0 = workspace_dev;
+    float* ha = x0 + (size_t)R * D; float* hb = ha + (size_t)R * MD; float* hc = hb + (size_t)R * MD;
+    float* yo = hc + (size_t)R * MD;
+    int32_t* keep = (int32_t*)(yo + (size_t)R * m->output_dim);
+    int32_t* flag = keep + R;
+    const int32_t* frames_dev = pk + B + 1;
+    HIP_TRY(hipMemsetAsync(flag, 0, sizeof(int32_t), s));
+    hipLaunchKernelGGL(units_check_kernel, dim3(B), dim3(64), 0, s, units_dev, ncb, K1, K2, spans_dev, nunits_dev, frames_dev, T, S, flag);
+    HIP_TRY(hipGetLastError());
+    if (units_report(what, flag, s)) return 1;
+    hipLaunchKernelGGL(units_gather_kernel, dim3((R + 3) / 4), dim3(256), 0, s, units_dev, ncb, c1_dev, K1, c2_dev, K2, nunits_dev, B, S, D,
+                       x0, keep);
+    HIP_TRY(hipGetLastError());
+    if (run_mlp(m, x0, R, ha, hb, hc, yo, s)) return 1;
+    hipLaunchKernelGGL(units_expand_cond_kernel, dim3((unsigned)((nf + 3) / 4)), dim3(256), 0, s, spans_dev, nunits_dev, frames_dev, keep, yo,
+                       B, T, S, m->output_dim, cond_dev, pk, nf);
     HIP_TRY(hipGetLastError());
     return 0;
 }

@@ -249,6 +249,35 @@ class SegmentConditioner:
                                                  _stream(self.device)), "sylber_condition")
         return cond, avg
 
+    def packed(self, hidden: torch.Tensor, offsets: Sequence[int], frames: Sequence[int], seg: torch.Tensor, nseg: torch.Tensor,
+               feats: torch.Tensor, normthreshold: float, max_segments: Optional[int] = None, quantizer=None) -> torch.Tensor:
+        """``__call__`` for a packed batch (``sylber_condition_packed``): hidden ``[offsets[-1], 768]`` of ``forward_packed`` (clip b's frame t
+        at row ``offsets[b] + t``), (seg, nseg, feats) of ``segment_packed`` (``[B, K, ...]``, relative to each clip's start) ->
+        the conditioning input ``[sum frames, out]`` of each clip's own frames, back to back: row for row what ``__call__`` computes
+        for the clip's frames in batch-invariant mode (the same silence mask and quantizer substitution)."""
+        B, K, D = feats.shape
+        fl = [int(f) for f in frames]
+        ol = [int(o) for o in offsets]
+        if D != self.input_dim:
+            raise ValueError("feature dim %d != MLP input dim %d" % (D, self.input_dim))
+        if len(fl) != B or len(ol) != B + 1:
+            raise ValueError("need %d frame counts and %d offsets, got %d and %d" % (B, B + 1, len(fl), len(ol)))
+        S = int(max_segments) if max_segments is not None else max(1, int(nseg.max().item()))
+        S = min(max(S, 1), K)
+        if quantizer is not None:
+            head = torch.nan_to_num(feats[:, :S].contiguous())
+            q = quantizer.decode(quantizer.get_indices(head))
+            feats = feats.clone()
+            feats[:, :S] = q
+        cond = torch.empty(sum(fl), self.output_dim, dtype=torch.float32, device=self.device)
+        ws = torch.empty(int(self.lib.sylber_condition_packed_workspace_floats(self.handle, B, S)), dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.sylber_condition_packed(self.handle, _vp(hidden), (ctypes.c_int32 * (B + 1))(*ol), (ctypes.c_int32 * B)(*fl), B,
+                                                        _vp(seg), _vp(nseg), _vp(feats.contiguous()), K, S,
+                                                        ctypes.c_float(float(np.float32(normthreshold))), None, _vp(cond), _vp(ws),
+                                                        _stream(self.device)), "sylber_condition_packed")
+        return cond
+
     def from_features(self, features: torch.Tensor) -> torch.Tensor:
         """the ``features is not None`` branch of ``resynthesize`` (segment_synthesis.py:135-140): ``features [B,T,768]``
         (already averaged / decoded by the caller) -> ``input [B,T,out]`` = MLP(features) with the frames whose
@@ -265,10 +294,12 @@ class SegmentConditioner:
                        "sylber_condition_features")
         return cond.reshape(lead + (self.output_dim,))
 
-    def from_units(self, codebooks: Sequence[torch.Tensor], units: torch.Tensor, spans: torch.Tensor, nunits: torch.Tensor, T: int,
+    def from_units(self, codebooks: Sequence[torch.Tensor], units: torch.Tensor, spans: torch.Tensor, nunits: torch.Tensor, T: Optional[int],
                    frames: Optional[torch.Tensor] = None) -> torch.Tensor:
         """``sylber_condition_units``: the conditioning input of syllable units -> ``[B, T, out]``, bitwise
-        ``from_features(expand_feature(decode(units), durations))``.  ``codebooks``: one or two ``[K, 768]`` fp32 device tensors
+        ``from_features(expand_feature(decode(units), durations))``.  ``T=None`` with ``frames``: a packed batch
+        (``sylber_condition_units_packed``) -> ``[sum frames, out]``, each clip's own frames back to back, row for row the padded call's
+        with ``T = max(frames)``.  ``codebooks``: one or two ``[K, 768]`` fp32 device tensors
         (decode sums them); ``units [B, S, len(codebooks)]``, ``spans [B, S, 2]`` (frames [start, end) of each unit), ``nunits [B]``,
         ``frames [B]`` (optional): int32 device tensors.  Bad ids, spans or counts raise ``SylberHipError``."""
         if not 1 <= len(codebooks) <= 2:
@@ -287,6 +318,20 @@ class SegmentConditioner:
         for c in codebooks:
             if c.dim() != 2 or c.shape[1] != self.input_dim:
                 raise ValueError("codebooks must be [K, %d]" % self.input_dim)
+        if T is None:                      # packed: each clip's own frames, back to back
+            if frames is None:
+                raise ValueError("a packed call (T=None) needs frames")
+            fl = [int(f) for f in frames.cpu().tolist()]
+            if len(fl) != B:
+                raise ValueError("need %d frame counts, got %d" % (B, len(fl)))
+            cond = torch.empty(sum(fl), self.output_dim, dtype=torch.float32, device=self.device)
+            ws = torch.empty(int(self.lib.sylber_condition_packed_workspace_floats(self.handle, B, S)), dtype=torch.float32, device=self.device)
+            with torch.cuda.device(self.device):
+                _lib.check(self.lib.sylber_condition_units_packed(self.handle, _vp(c1), c1.shape[0], _vp(c2) if c2 is not None else None,
+                                                                  c2.shape[0] if c2 is not None else 0, _vp(units), _vp(spans), _vp(nunits),
+                                                                  (ctypes.c_int32 * B)(*fl), B, S, _vp(cond), _vp(ws), _stream(self.device)),
+                           "sylber_condition_units_packed")
+            return cond
         cond = torch.empty(B, int(T), self.output_dim, dtype=torch.float32, device=self.device)
         ws = torch.empty(int(self.lib.sylber_condition_units_workspace_floats(self.handle, B, S)), dtype=torch.float32, device=self.device)
         with torch.cuda.device(self.device):

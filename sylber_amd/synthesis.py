@@ -18,7 +18,7 @@ import torch
 from . import _lib
 from .downstream import LEARNED_QUANTIZER_NO_FEATURES, KMQuantizer, ResidualKMQuantizer, SegmentConditioner, quantizer_codebooks
 from .quantizer import Quantizer
-from .segmenter import HubertEncoderHIP, _segment_list
+from .segmenter import PACKED_PRECISIONS, HubertEncoderHIP, _segment_list, _tables_to_host
 from .weights import (CFM_CONV_K, CFM_DEPTH, CFM_DIM, CFM_DIM_COND_EMB, CFM_DIM_HEAD, CFM_DIM_IN_PROJ, CFM_DIM_OUT, CFM_FF_INNER,
                       CFM_FF_MULT, CFM_HEADS, CFM_REGISTERS, CFM_TIME_HIDDEN)
 
@@ -131,6 +131,33 @@ def threshold_from_stats(signal_mean, signal_var, noise_mean, noise_var, eta: fl
     raise ValueError("thresholder statistics are degenerate (equal variances and means)")
 
 
+def cfm_packed_layout(frames: Sequence[int]) -> np.ndarray:
+    """The decoder slots of a packed batch (``sylber_cfm_packed_layout``; host only, no GPU): per-clip frame counts -> int32 ``[B + 1]``
+    slot offsets.  Clip b's slot holds ``round_up(16 + frames[b], 64)`` rows: its 16 register rows, its frames and zero rows.
+    ValueError for an empty batch, a count below 1 or slots totalling 2^24 rows or more."""
+    lib = _lib.load()
+    fl = [int(f) for f in frames]
+    if not fl:
+        raise ValueError("a packed batch needs at least one clip")
+    if any(f < 1 or f > 2 ** 31 - 1 for f in fl):
+        raise ValueError("every clip of a packed batch needs 1 .. 2^31 - 1 frames, got %s" % fl)
+    off = (ctypes.c_int32 * (len(fl) + 1))()
+    if lib.sylber_cfm_packed_layout((ctypes.c_int32 * len(fl))(*fl), len(fl), off) != 0:
+        raise ValueError(lib.sylber_last_error().decode())
+    return np.frombuffer(off, dtype=np.int32).copy()
+
+
+def _frame_starts(frames: Sequence[int]) -> np.ndarray:
+    """[B + 1] prefix sums: clip b's frames are rows [starts[b], starts[b + 1]) of a back-to-back [sum frames, ...] tensor"""
+    return np.concatenate([[0], np.cumsum(np.asarray(frames, np.int64))]).astype(np.int64)
+
+
+def _padded_rows(frames: Sequence[int], T: int, device) -> torch.Tensor:
+    """the flat row b * T + t of every clip frame (b, t < frames[b]) of a padded [B, T, ...] tensor, in back-to-back order"""
+    idx = np.concatenate([b * T + np.arange(int(f), dtype=np.int64) for b, f in enumerate(frames)])
+    return torch.from_numpy(idx).to(device)
+
+
 def _as_f32(t) -> torch.Tensor:
     return t.detach().to("cpu", torch.float32).contiguous()
 
@@ -238,6 +265,54 @@ class CfmDecoder:
                            "sylber_cfm_sample_frames")
         return art
 
+    def sample_packed(self, conds, steps: int = 5, y0: Optional[torch.Tensor] = None, pitch_amp: float = 1.0):
+        """A ragged batch without padding to its longest clip (``sylber_cfm_sample_packed``, bf16 / fp16).  ``conds``: a list of
+        ``[T_b, 256]`` tensors, or ``(packed [sum T_b, 256], frames)``.  ``y0``: ``[sum T_b, 14]`` in the same order, or None (zeros).
+        Returns ``(art [sum T_b, 14] fp32 on the device, starts)``: clip b is ``art[starts[b]:starts[b + 1]]``, bit-identical to
+        ``sample(cond, frames=...)``'s row b and to the clip sampled alone.  ValueError before any launch for an fp32 decoder, bad counts
+        or shapes."""
+        if self.precision not in PACKED_PRECISIONS:
+            raise ValueError("sample_packed: packed batches run in precision %s only (this decoder: %r)"
+                             % (" / ".join(map(repr, PACKED_PRECISIONS)), self.precision))
+        if isinstance(steps, bool) or int(steps) != steps or not 1 <= int(steps) <= 65:
+            raise ValueError("steps must be an integer in 1..65, got %r" % (steps,))
+        if isinstance(conds, tuple) and len(conds) == 2 and torch.is_tensor(conds[0]):
+            cond, frames = conds
+            fl = [int(f) for f in frames]
+        else:
+            parts = list(conds)
+            if not parts:
+                raise ValueError("a packed batch needs at least one clip")
+            for c in parts:
+                if c.dim() != 2 or c.shape[-1] != CFM_DIM_COND_EMB:
+                    raise ValueError("each clip's cond must be [T_b, %d], got %s" % (CFM_DIM_COND_EMB, tuple(c.shape)))
+            fl = [int(c.shape[0]) for c in parts]
+            cond = torch.cat([c.to(self.device, torch.float32) for c in parts]) if all(f > 0 for f in fl) else None
+        if not fl or any(f < 1 for f in fl):
+            raise ValueError("every clip needs >= 1 frame, got %s" % fl)
+        B, NF = len(fl), sum(fl)
+        if cond is None or cond.dim() != 2 or tuple(cond.shape) != (NF, CFM_DIM_COND_EMB):
+            raise ValueError("packed cond must be [sum T_b = %d, %d], got %s" % (NF, CFM_DIM_COND_EMB, None if cond is None else tuple(cond.shape)))
+        cond = cond.to(self.device, torch.float32).contiguous()
+        if y0 is not None:
+            if tuple(y0.shape) != (NF, CFM_DIM_OUT):
+                raise ValueError("y0 must be [%d, %d], got %s" % (NF, CFM_DIM_OUT, tuple(y0.shape)))
+            y0 = y0.to(self.device, torch.float32).contiguous()
+        farr = (ctypes.c_int32 * B)(*fl)
+        n = int(self.lib.sylber_cfm_workspace_bytes_packed(self.handle, farr, B))
+        if n < 0:
+            raise ValueError(self.lib.sylber_last_error().decode())
+        ws = torch.empty(n, dtype=torch.uint8, device=self.device)
+        art = torch.empty(NF, CFM_DIM_OUT, dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.sylber_cfm_sample_packed(self.handle, ctypes.c_void_p(cond.data_ptr()), farr, B, int(steps),
+                                                         ctypes.c_void_p(y0.data_ptr()) if y0 is not None else None,
+                                                         ctypes.c_float(float(pitch_amp)), ctypes.c_void_p(art.data_ptr()),
+                                                         ctypes.c_void_p(ws.data_ptr()),
+                                                         ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)),
+                       "sylber_cfm_sample_packed")
+        return art, _frame_starts(fl)
+
     def eval(self, x: torch.Tensor, t: float, cond_emb: torch.Tensor) -> torch.Tensor:
         """one velocity evaluation of the ``Regressor`` at state ``x [B, T, 14]`` and time ``t``"""
         cond = self._cond(cond_emb)
@@ -263,7 +338,9 @@ class SegmentSynthesis:
     ``quantizer``: None, a ``KMQuantizer`` / ``ResidualKMQuantizer``, a learned ``Quantizer`` (``tokenize`` only: its decode is
     not a feature row, so ``resynthesize`` / ``synthesize_units`` refuse it), or a ``.npy`` codebook path; with a path,
     ``residual_quantizer`` (a second ``.npy`` path) makes it a ``ResidualKMQuantizer`` and ``normalize_embed`` is the
-    ``KMQuantizer``'s ``normalize`` (what upstream's constructor, segment_synthesis.py:93-99, means to do)."""
+    ``KMQuantizer``'s ``normalize`` (what upstream's constructor, segment_synthesis.py:93-99, means to do).
+    ``packed=True`` (bf16 / fp16): ragged batches run without padding to the longest clip in the encoder, the conditioning and the
+    decoder, with ``batch_invariant=True``'s results bit for bit (it implies that mode)."""
 
     def __init__(self, model_ckpt=None, speech_upstream="facebook/hubert-base-ls960", encoding_layer=9, input_configs=None,
                  regressor_configs=None, thresholder_configs=None, pitch_amp=5, quantizer=None, device="cuda", precision="bf16",
@@ -272,6 +349,9 @@ class SegmentSynthesis:
             raise _lib.SylberHipError("sylber_amd.SegmentSynthesis runs on the MI355X only (device=%r)" % (device,))
         if precision not in PRECISIONS:
             raise ValueError("precision must be one of %s" % sorted(PRECISIONS))
+        self.packed = bool(kwargs.get("packed", False))
+        if self.packed and precision not in PACKED_PRECISIONS:
+            raise ValueError("packed=True supports precision %s only (got %r)" % (" / ".join(map(repr, PACKED_PRECISIONS)), precision))
         self.input_configs = dict(DEFAULT_INPUT_CONFIGS if input_configs is None else input_configs)
         self.regressor_configs = dict(DEFAULT_REGRESSOR_CONFIGS if regressor_configs is None else regressor_configs)
         self.thresholder_configs = dict(DEFAULT_THRESHOLDER_CONFIGS if thresholder_configs is None else thresholder_configs)
@@ -293,7 +373,8 @@ class SegmentSynthesis:
         self.decoder = CfmDecoder(sd, device=device, precision=precision)     # checks the regressor tensors first (cheapest to fail)
         self.speech_model = HubertEncoderHIP(speech, num_layers=encoding_layer, device=device, precision=precision)
         # batch-invariant mode (off by default): each row of a padded batch is resynthesized exactly as it is alone
-        self.batch_invariant = bool(kwargs.get("batch_invariant", False))
+        # packed batches (off by default) keep batch-invariant mode's results, so they imply it
+        self.batch_invariant = bool(kwargs.get("batch_invariant", False)) or self.packed
         if self.batch_invariant:
             self.speech_model.set_per_utterance(True)
         self.input_model = SegmentConditioner(mlp, device=device)
@@ -328,8 +409,13 @@ class SegmentSynthesis:
         ``prosody_*`` are accepted and ignored, as upstream.
         With ``batch_invariant=True``, row b of ``art[:, :T_b]`` (``T_b`` from ``attention_mask``) and its segments are bit-identical
         to the clip resynthesized alone, and ``art[b, T_b:]`` is 0.  ``frames=`` gives the ``features=`` branch each row's frame count
-        (default: every row ``T`` frames)."""
+        (default: every row ``T`` frames).
+        With ``packed=True`` the results are batch-invariant mode's, bit for bit; ``input_values`` may also be a list of 1-D clips (then
+        ``T`` is the longest clip's frame count)."""
         dev = self.device
+        if self.packed:
+            return self._resynthesize_packed(input_values, attention_mask, features, steps, rand_scale, merge_threshold, normthreshold, y0,
+                                             frames)
         if features is None:
             if input_values is None:
                 raise ValueError("pass input_values or features")
@@ -354,6 +440,83 @@ class SegmentSynthesis:
         art = self.decoder.sample(cond, steps=steps, y0=y0, pitch_amp=self.pitch_amp, frames=frames)
         return art, segments
 
+    # ---- packed batches ----------------------------------------------------------------------------------------------------
+    def _clips(self, input_values, attention_mask):
+        """-> (1-D clips, T of the padded result or None): a list of clips, one clip, or a padded [B, N] batch cut by its mask"""
+        if isinstance(input_values, (list, tuple)):
+            if attention_mask is not None:
+                raise ValueError("a list of clips carries its own lengths; do not pass attention_mask")
+            clips = [torch.as_tensor(c).reshape(-1) for c in input_values]
+            if not clips:
+                raise ValueError("a packed batch needs at least one clip")
+            return clips, None
+        x = torch.as_tensor(input_values)
+        if x.dim() == 1:
+            x = x[None]
+        if x.dim() != 2:
+            raise ValueError("input_values must be [B, N], [N] or a list of 1-D clips")
+        B, N = x.shape
+        lengths = [N] * B if attention_mask is None else [int(v) for v in torch.as_tensor(attention_mask).sum(-1).reshape(-1).tolist()]
+        if len(lengths) != B:
+            raise ValueError("attention_mask must have one row per clip")
+        return [x[b, :lengths[b]] for b in range(B)], self.speech_model.num_frames(N)
+
+    def _encode_packed(self, input_values, attention_mask, normthreshold, merge_threshold):
+        """encoder and boundary detection of a packed batch -> (hidden, offsets, frames, seg, nseg, feats, nseg_h, seg_h, T)"""
+        sm = self.speech_model
+        sm._check_packed("SegmentSynthesis(packed=True)")
+        clips, T = self._clips(input_values, attention_mask)
+        hidden, offsets, frames = sm.forward_packed(clips)
+        lengths = [int(c.numel()) for c in clips]
+        seg, nseg, feats = sm.segment_packed(hidden, lengths, normthreshold, merge_threshold, layout=(offsets, frames))
+        nseg_h, seg_h = _tables_to_host(seg, nseg)
+        return hidden, offsets, frames, seg, nseg, feats, nseg_h, seg_h, (T if T is not None else int(frames.max()))
+
+    def _sample_packed(self, cond: torch.Tensor, frames, T: int, steps, rand_scale, y0) -> torch.Tensor:
+        """the decoder over each clip's own frames (cond [sum frames, 256]) -> padded art [B, T, 14], zeros past each clip's frames.
+        rand_scale / a padded y0 [B, T, 14]: the batch-invariant call's start state, each clip's rows taken from it."""
+        dev = self.device
+        fl = [int(f) for f in frames]
+        B = len(fl)
+        idx = _padded_rows(fl, T, dev)
+        if y0 is None and rand_scale:
+            y0 = torch.randn(B, T, CFM_DIM_OUT, device=dev) * rand_scale
+        if y0 is not None:
+            y0 = torch.as_tensor(y0).to(dev, torch.float32)
+            if tuple(y0.shape) != (B, T, CFM_DIM_OUT):
+                raise ValueError("y0 must be [%d, %d, %d], got %s" % (B, T, CFM_DIM_OUT, tuple(y0.shape)))
+            y0 = y0.reshape(B * T, CFM_DIM_OUT).index_select(0, idx)
+        art_p, _ = self.decoder.sample_packed((cond, fl), steps=steps, y0=y0, pitch_amp=self.pitch_amp)
+        art = torch.zeros(B, T, CFM_DIM_OUT, dtype=torch.float32, device=dev)
+        art.view(B * T, CFM_DIM_OUT).index_copy_(0, idx, art_p)
+        return art
+
+    def _resynthesize_packed(self, input_values, attention_mask, features, steps, rand_scale, merge_threshold, normthreshold, y0, frames):
+        dev = self.device
+        if features is None:
+            if input_values is None:
+                raise ValueError("pass input_values or features")
+            if isinstance(self.quantizer, Quantizer):
+                raise ValueError(LEARNED_QUANTIZER_NO_FEATURES)
+            if normthreshold is None:
+                normthreshold = self.get_threshold()
+            hidden, offsets, fr, seg, nseg, feats, nseg_h, seg_h, T = self._encode_packed(input_values, attention_mask, normthreshold,
+                                                                                          merge_threshold)
+            cond = self.input_model.packed(hidden, offsets, fr, seg, nseg, feats, normthreshold, quantizer=self.quantizer)
+            return self._sample_packed(cond, fr, T, steps, rand_scale, y0), _segment_list(seg_h, nseg_h)
+        feats = torch.as_tensor(features).to(dev, torch.float32).contiguous()
+        if feats.dim() != 3:
+            raise ValueError("features must be [B, T, 768]")
+        B, T, D = feats.shape
+        fl = [T] * B if frames is None else [int(f) for f in frames]
+        if len(fl) != B or any(f < 1 or f > T for f in fl):
+            raise ValueError("frames must hold %d counts in [1, %d], got %s" % (B, T, fl))
+        if D != self.input_model.input_dim:
+            raise ValueError("feature dim %d != MLP input dim %d" % (D, self.input_model.input_dim))
+        rows = feats.reshape(B * T, D).index_select(0, _padded_rows(fl, T, dev))
+        cond = self.input_model.from_features(rows)
+        return self._sample_packed(cond, fl, T, steps, rand_scale, y0), None
+
     def tokenize(self, input_values, attention_mask=None, merge_threshold=0.8, normthreshold=None) -> List[dict]:
         """speech -> syllable units: one dict per clip with ``units`` int64 ``[n, ncb]`` (the quantizer's ids of the clip's segment
         means: ncb = 1 for a ``KMQuantizer``, 2 for a ``ResidualKMQuantizer``, Qa + Qp for a learned ``Quantizer``), ``segments`` int64 ``[n, 2]`` (the table
@@ -365,8 +528,11 @@ class SegmentSynthesis:
         dev = self.device
         if normthreshold is None:
             normthreshold = self.get_threshold()
-        _, frames, _, nseg, feats, nseg_h, seg_h = self.speech_model.segment_batch(input_values, attention_mask, normthreshold,
-                                                                                   merge_threshold, self.batch_invariant)
+        if self.packed:
+            _, _, frames, _, nseg, feats, nseg_h, seg_h, _ = self._encode_packed(input_values, attention_mask, normthreshold, merge_threshold)
+        else:
+            _, frames, _, nseg, feats, nseg_h, seg_h = self.speech_model.segment_batch(input_values, attention_mask, normthreshold,
+                                                                                       merge_threshold, self.batch_invariant)
         S = seg_h.shape[1]
         keep = torch.arange(S, device=dev)[None, :] < nseg[:, None].to(torch.int64)
         head = torch.where(keep[:, :, None], feats[:, :S], torch.zeros((), device=dev)).contiguous()
@@ -439,6 +605,9 @@ class SegmentSynthesis:
         i32 = lambda a: torch.from_numpy(np.ascontiguousarray(np.asarray(a, np.int32))).to(dev)   # noqa: E731
         if U.shape[1] == 0:
             U, P = np.zeros((B, 1, ncb), np.int64), np.zeros((B, 1, 2), np.int64)
+        if self.packed:
+            cond = self.input_model.from_units(books, i32(U), i32(P), i32(counts), None, frames=i32(frames))
+            return self._sample_packed(cond, frames, T, steps, rand_scale, y0)
         cond = self.input_model.from_units(books, i32(U), i32(P), i32(counts), T, frames=i32(frames))
         if y0 is None and rand_scale:
             y0 = torch.randn(cond.shape[0], cond.shape[1], CFM_DIM_OUT, device=dev) * rand_scale
