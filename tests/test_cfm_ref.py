@@ -155,3 +155,61 @@ def test_golden_regenerates_from_the_reference(golden, sd):
     assert np.array_equal(inp["cond"].numpy(), golden["cond"]) and np.array_equal(inp["y0"].numpy(), golden["y0"])
     out = G.sample_with(w, inp["cond"], 2, inp["y0"]).numpy()
     assert rel_rms(out, golden["s2_y0"]) <= 1e-6           # (bit-identical on the machine that wrote it; CPU kernels may differ elsewhere)
+
+
+# ---- the float64 path (tests/test_gpu_decoder_ref.py's reference) ---------------------------------------------------------------
+def test_float64_path_matches_reference_golden(golden, sd):
+    """the restatement in float64 (``to_f64``; the time grid and the rotary angles stay fp32, as upstream computes them) against the
+    fp32 golden: within fp32 noise.  Measured 1.2e-6 (eval), 1.0e-6 / 5.2e-7 (steps 2 / 5), 6.0e-7 (ragged)."""
+    sd64 = R.to_f64(sd)
+    cond, y0 = torch.from_numpy(golden["cond"]).double(), torch.from_numpy(golden["y0"]).double()
+    v = R.evaluate(sd64, torch.from_numpy(golden["x"]).double(), float(golden["eval_t0_time"]), cond)
+    assert v.dtype == torch.float64 and rel_rms(v.numpy(), golden["eval_t0"]) <= 1e-5
+    for steps in (2, 5):
+        out = R.sample(sd64, cond, steps, y0)
+        assert out.dtype == torch.float64 and rel_rms(out.numpy(), golden["s%d_y0" % steps]) <= 1e-5, steps
+    out = R.sample(sd64, cond, 5)                                           # y0 = None: the zero start is float64 too
+    assert out.dtype == torch.float64 and rel_rms(out.numpy(), golden["s5_zero"]) <= 1e-5
+    out = R.sample(sd64, torch.from_numpy(golden["rag_cond"]).double(), 5)
+    assert rel_rms(out.numpy(), golden["ragged"]) <= 1e-5
+
+
+def test_float64_path_is_more_than_fp32_noise_away_from_fp32(golden, sd):
+    """the float64 path really runs in float64: not bit-equal to the fp32 path, but within fp32 noise of it"""
+    cond = torch.from_numpy(golden["cond"])
+    a = R.sample(sd, cond, 2).numpy()
+    b = R.sample(R.to_f64(sd), cond.double(), 2).numpy()
+    assert not np.array_equal(a.astype(np.float64), b)
+    assert rel_rms(a, b) <= 1e-5
+
+
+@pytest.mark.parametrize("T", [1, 15])
+def test_float64_path_short_clips_are_sane(sd, T):
+    """below 31 frames the conv's 31-tap window pads both ends at once: finite, the right shape, O(1) velocities, and frame t of a
+    padded batch row is not the lone clip's (padded frames are ordinary frames)"""
+    g = torch.Generator().manual_seed(T)
+    cond = torch.randn(1, T, 256, generator=g, dtype=torch.float64)
+    y0 = torch.randn(1, T, 14, generator=g, dtype=torch.float64)
+    sd64 = R.to_f64(sd)
+    v = R.evaluate(sd64, y0, 0.25, cond)
+    out = R.sample(sd64, cond, 3, y0, pitch_amp=5)
+    for a in (v, out):
+        assert a.shape == (1, T, 14) and a.dtype == torch.float64 and torch.isfinite(a).all()
+        assert 1e-2 < a.pow(2).mean().sqrt().item() < 1e2
+    # fp32 agrees within fp32 noise
+    assert rel_rms(R.evaluate(sd, y0.float(), 0.25, cond.float()).numpy(), v.numpy()) <= 1e-5
+
+
+@pytest.mark.parametrize("prec", ["bf16", "fp16"])
+def test_round16_reference_rounds_where_the_kernels_round(sd, prec):
+    """round16= changes the result by about the format's rounding (bf16 ~1e-2, fp16 ~1e-3 relative RMS at the synthetic weights'
+    logit scale) and leaves the default path alone"""
+    g = torch.Generator().manual_seed(3)
+    cond = torch.randn(1, 40, 256, generator=g, dtype=torch.float64)
+    x = torch.randn(1, 40, 14, generator=g, dtype=torch.float64)
+    sd64 = R.to_f64(sd)
+    exact = R.evaluate(sd64, x, 0.25, cond).numpy()
+    r = rel_rms(R.evaluate(sd64, x, 0.25, cond, round16=prec).numpy(), exact)
+    lo, hi = {"bf16": (2e-3, 3e-2), "fp16": (2e-4, 4e-3)}[prec]
+    assert lo < r < hi, r
+    assert np.array_equal(R.evaluate(sd64, x, 0.25, cond, round16=None).numpy(), exact)

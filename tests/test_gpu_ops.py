@@ -413,3 +413,72 @@ def test_tail_split_is_bitwise(lib, tail):
         _lib.check(lib.sylber_op_conv3(_p(xd), ctypes.c_void_p(wc.data_ptr()), _p(y), R, M, t, None), "op_conv3")
         outs.append(y)
     assert torch.equal(outs[0], outs[1]) and torch.equal(outs[0], outs[2]), ("conv3", tail)
+
+
+def _unit_rows(g, n, dirs, spread):
+    """n unit vectors in 64 dims near +-one of `dirs` (spread: the noise's weight), so that scores reach the extremes"""
+    pick = torch.randint(0, dirs.shape[0], (n,), generator=g)
+    sign = torch.where(torch.rand(n, generator=g) < 0.5, -1.0, 1.0)
+    u = dirs[pick] * sign[:, None] + spread * torch.randn(n, 64, generator=g)
+    return u / u.norm(dim=-1, keepdim=True)
+
+
+@pytest.mark.parametrize("qw", [0, 1, 2])
+@pytest.mark.parametrize("T,v2", [(17, 9), (80, 41), (316, 227), (515, 300), (3015, 1500)])
+def test_attention_decoder_logit_scale(lib, T, v2, qw):
+    """The decoder's attention at a trained checkpoint's logit scale (q / k RMSNorm gamma 1): 12 heads with 8..11 all zero, q / k unit
+    per head times 8, q times the decoder's 10 (op_attention's SYL_Q_SCALE then gives log2 units), so scores reach +-923 in log2
+    units.  Two rows of 2: all T keys, and `v2` keys (ending mid-tile).  Planted: in row 0 / head 0 query 3 meets +100 in the first
+    tile, +923 mid-way and -900 in the last tile (the running maximum jumps by ~800); in row 1 / head 1 query 5 scores ~-900 on every
+    valid key and +923 on masked keys right behind the bound and in a later tile.  Reference: float64 base-2 softmax on the same
+    bf16-rounded, pre-scaled operands.  Bound: per-row max |err| 3e-2 (as test_attention: P and the output are bf16); the zero heads'
+    context exactly 0.  Measured on an MI355X: max |score| 867 .. 924, worst row 2.4e-3 .. 6.5e-3 x max|v|
+    (3.0e-2 absolute, T = 3015, qw = 1)."""
+    from sylber_amd import _lib
+    B = 2
+    g = torch.Generator().manual_seed(T + 7 * qw)
+    dirs = torch.randn(4, 64, generator=g)
+    dirs = dirs / dirs.norm(dim=-1, keepdim=True)
+    q = torch.zeros(B, T, 12, 64)
+    k = torch.zeros(B, T, 12, 64)
+    v = torch.zeros(B, T, 12, 64)
+    for b in range(B):
+        for h in range(8):
+            q[b, :, h] = _unit_rows(g, T, dirs, 0.3)
+            k[b, :, h] = _unit_rows(g, T, dirs, 0.3)
+            v[b, :, h] = torch.randn(T, 64, generator=g)
+    u = dirs[0]
+    if T >= 70:                                                    # row 0, head 0, query 3: max jumps between tiles
+        q[0, 3, 0] = u
+        w = torch.randn(64, 64, generator=g)
+        w = torch.nn.functional.normalize(w - (w @ u)[:, None] * u, dim=-1)    # unit, orthogonal to u
+        k[0, :64, 0] = 0.11 * u + (1 - 0.11 ** 2) ** 0.5 * w
+        k[0, T // 2, 0] = u
+        k[0, T - 2, 0] = -u
+    q[1, 5, 1] = u                                                  # row 1, head 1, query 5: valid keys far below masked keys
+    k[1, :v2, 1] = torch.nn.functional.normalize(-u + 0.05 * torch.randn(v2, 64, generator=g), dim=-1)
+    k[1, v2:, 1] = u
+    q, k = q * 640.0, k * 8.0             # the decoder's q / k: 8 gamma q^, 8 gamma k^; q also carries the 10 and op_attention's 1/8
+    qd, kd, vdev = (t.reshape(B, T, 768).cuda() for t in (q, k, v))
+    vd = torch.tensor([T, v2], dtype=torch.int32).cuda()
+    o = torch.full((B, T, 768), float("nan"), device="cuda")
+    _lib.check(lib.sylber_op_attention(_p(qd), _p(kd), _p(vdev), _p(vd), _p(o), B, T, 0, 32 * qw, None), "op_attention")
+    o = o.cpu().double().view(B, T, 12, 64)
+    assert torch.isfinite(o).all()
+    assert not o[:, :, 8:].any()                                    # the zero heads: exactly 0
+    qs = _bf(q * Q_SCALE).double()                                  # log2 units, as the kernel sees them
+    kb, vb = _bf(k).double(), _bf(v).double()
+    worst, worst_rel, smax = 0.0, 0.0, 0.0
+    for b in range(B):
+        n = [T, v2][b]
+        for h in range(8):
+            s = qs[b, :, h] @ kb[b, :n, h].T
+            smax = max(smax, s.abs().max().item())
+            p = torch.exp2(s - s.max(-1, keepdim=True).values)
+            ref = (p / p.sum(-1, keepdim=True)) @ vb[b, :n, h]
+            err = (o[b, :, h] - ref).abs().max(-1).values           # per query row
+            vmax = vb[b, :n, h].abs().max().item()                   # the context's scale: a convex combination of these rows
+            worst, worst_rel = max(worst, err.max().item()), max(worst_rel, err.max().item() / vmax)
+            assert err.max().item() <= 1e-2 * vmax, (b, h, err.argmax().item(), err.max().item(), vmax)
+    print("MEAS attention T=%d qw=%d max|score| %.0f worst row err %.3e (%.2e x max|v|)" % (T, qw, smax, worst, worst_rel))
+    assert smax > 850
