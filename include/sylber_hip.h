@@ -189,6 +189,34 @@ int sylber_km_assign_residual(const float* feats_dev, int32_t n, const float* c1
 int sylber_km_decode_residual(const int32_t* idx_dev, int32_t n, const float* c1_dev, int32_t K1, const float* c2_dev, int32_t K2,
                               int32_t D, float* out_dev, void* stream);
 
+/* Fitting k-means unit codebooks (sylber_amd/kmeans.py: fit_kmeans and the quantizers it returns).  Device pointers, exact fp32
+ * contractions, results independent of the launch geometry.
+ * sylber_km_normalize: y[r] = x[r] / sqrt(sum x[r]^2 + 1e-8) * 6, the arithmetic of sylber_km_assign's normalize (y may not alias x).
+ * sylber_kmeans_assign: idx_dev[r] = argmin_k fmaf(-2, x_r . c_k, ||c_k||^2), ties to the smallest k -- the bits of sylber_km_assign
+ *   for every K >= 1 -- without materialising the [n, K] dot matrix.  Optional outputs (nullable): dmin_dev [n] the minimum itself,
+ *   inertia_dev (one double) = sum_r max(0, ||x_r||^2 + dmin[r]) summed in fp64 in a fixed order, changed_dev (one int64) = rows whose
+ *   label differs from prev_idx_dev [n].  x_dev [n, D], c_dev [K, D] fp32, D % 16 == 0;
+ *   workspace_dev: sylber_kmeans_assign_workspace_floats(n, K, D) floats (O(n + K)).
+ * sylber_kmeans_update: counts_dev[k] = rows with idx_dev == k; for every k with counts > 0, c_dev[k] = fp32(fp64 sum of its rows /
+ *   count), the sum taken over the rows in ascending order in pieces of 512 rows, the pieces added left to right; clusters without
+ *   rows keep c_dev[k].  order_dev [n] int64: the row indices grouped by label in ascending label order, ascending within a label
+ *   (a stable sort of idx_dev).  workspace_dev: sylber_kmeans_update_workspace_bytes(n, K, D) bytes.
+ * sylber_kmeans_seed: k-means++ (one candidate per step) over x_dev [n, D], D % 4 == 0, with u_dev [K] fp64 uniforms in [0, 1):
+ *   chosen[0] = floor(u[0] n); after each center, dist[r] = min(dist[r], sum_j (x_rj - c_j)^2) (fmaf chain in ascending j), and the
+ *   next center is the first r whose fp64 prefix sum of dist (256-row block sums, each the last element of an inclusive in-block
+ *   scan, prefixed across blocks) exceeds u[j] * total.  chosen_dev [K] int32.  Asynchronous: status_dev (one int32) is 0 when done,
+ *   1 when the rows have fewer than K distinct values (total == 0).  workspace_dev: sylber_kmeans_seed_workspace_floats(n) floats. */
+int sylber_km_normalize(const float* x_dev, int32_t n, int32_t D, float* y_dev, void* stream);
+int64_t sylber_kmeans_assign_workspace_floats(int32_t n, int32_t K, int32_t D);
+int sylber_kmeans_assign(const float* x_dev, int32_t n, const float* c_dev, int32_t K, int32_t D, int32_t* idx_dev, float* dmin_dev,
+                         double* inertia_dev, const int32_t* prev_idx_dev, int64_t* changed_dev, float* workspace_dev, void* stream);
+int64_t sylber_kmeans_update_workspace_bytes(int32_t n, int32_t K, int32_t D);
+int sylber_kmeans_update(const float* x_dev, int32_t n, int32_t D, const int32_t* idx_dev, const int64_t* order_dev, int32_t K,
+                         float* c_dev, int32_t* counts_dev, void* workspace_dev, void* stream);
+int64_t sylber_kmeans_seed_workspace_floats(int32_t n);
+int sylber_kmeans_seed(const float* x_dev, int32_t n, int32_t D, int32_t K, const double* u_dev, int32_t* chosen_dev,
+                       int32_t* status_dev, float* workspace_dev, void* stream);
+
 /* Learned quantizer (sylber/model/quantizer.py:6-77, 182-257: `load_quantizer` / `Quantizer`), eval, exact fp32.  The host
  * (sylber_amd/quantizer.py) chains: sylber_lq_norm (input norm / padding) -> sylber_ffenc -> sylber_lq_norm (output norm, blank rows)
  * -> sylber_rvq_assign for the art window and the pitch window -> sylber_lq_norm of the quantized rows.  All data pointers are device

@@ -94,6 +94,14 @@ EXPORTS = {
     "sylber_km_residual_workspace_floats": (c_int64, [c_int32, c_int32, c_int32, c_int32]),
     "sylber_km_assign_residual": (c_int, [c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
     "sylber_km_decode_residual": (c_int, [c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_int32, c_int32, c_void_p, c_void_p]),
+    "sylber_km_normalize": (c_int, [c_void_p, c_int32, c_int32, c_void_p, c_void_p]),
+    "sylber_kmeans_assign_workspace_floats": (c_int64, [c_int32, c_int32, c_int32]),
+    "sylber_kmeans_assign": (c_int, [c_void_p, c_int32, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                     c_void_p, c_void_p]),
+    "sylber_kmeans_update_workspace_bytes": (c_int64, [c_int32, c_int32, c_int32]),
+    "sylber_kmeans_update": (c_int, [c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "sylber_kmeans_seed_workspace_floats": (c_int64, [c_int32]),
+    "sylber_kmeans_seed": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "sylber_lq_norm": (c_int, [c_void_p, c_int64, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int64, c_int32, c_void_p, c_int64,
                                c_int32, c_void_p]),
     "sylber_ffenc_workspace_floats": (c_int64, [c_int32, c_int32, POINTER(c_int32)]),

@@ -60,6 +60,19 @@ __global__ __launch_bounds__(256) void km_argmin_kernel(const float* __restrict_
     }
 }
 
+// the same two kernels for the k-means fit (kmeans.hip): fitting on normalised rows and scoring against the squared norms with the
+// quantizers' own arithmetic is what makes a fitted KMQuantizer map its training rows to the fit's labels bit for bit
+int launch_km_normalize(const float* x, float* y, int n, int D, hipStream_t s) {
+    hipLaunchKernelGGL(km_normalize_kernel, dim3((n + 3) / 4), dim3(256), 0, s, x, y, n, D);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+int launch_km_sqnorm(const float* c, float* out, int K, int D, hipStream_t s) {
+    hipLaunchKernelGGL(km_sqnorm_kernel, dim3((K + 3) / 4), dim3(256), 0, s, c, out, K, D);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
 extern "C" int64_t sylber_km_workspace_floats(int32_t n, int32_t K, int32_t D) {
     if (n < 1 || K < 1 || D < 1) return -1;
     return (int64_t)n * ((K + 3) & ~3) + (int64_t)n * D + ((K + 3) & ~3) + 64;

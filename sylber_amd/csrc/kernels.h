@@ -107,6 +107,9 @@ struct GemmArgsF32 {
     int tiled;                        // 1: the LDS-DMA 128x128 kernel (forward of the parity mode; K % 32 == 0); 0: the simple 64x64 one
 };
 int launch_gemm_f32(const GemmArgsF32& a, hipStream_t s);
+// downstream.hip: km_normalize_kernel (x / sqrt(sum x^2 + 1e-8) * 6 per row) and km_sqnorm_kernel (fmaf sum of squares per row)
+int launch_km_normalize(const float* x, float* y, int n, int D, hipStream_t s);
+int launch_km_sqnorm(const float* c, float* out, int K, int D, hipStream_t s);
 
 // ------------------------------------------------------------------------------------------------
 // conv frontend layer 0: Conv1d(1->512,k10,s5) + GroupNorm(per (b,c) over time) + GELU, channels-last out
