@@ -217,6 +217,31 @@ int64_t sylber_kmeans_seed_workspace_floats(int32_t n);
 int sylber_kmeans_seed(const float* x_dev, int32_t n, int32_t D, int32_t K, const double* u_dev, int32_t* chosen_dev,
                        int32_t* status_dev, float* workspace_dev, void* stream);
 
+/* Exact k-nearest-neighbour search (sylber_amd/search.py: SyllableIndex).  Device pointers, exact fp32, results independent of the
+ * launch geometry, the split count and how the queries are chunked.
+ * sylber_knn_search: for each query row i of q_dev [n, D] the k best database rows j of db_dev [N, D] (D % 16 == 0, N < 2^31,
+ *   1 <= k <= 128) under the score s(i, j) = fmaf(-2, q_i . x_j, c_j), the dot product the exact-fp32 contraction of
+ *   sylber_kmeans_assign (ascending k, one rounding per product).  metric SYLBER_KNN_L2: c_j = db_norm_dev[j] (sylber_knn_row_norms);
+ *   SYLBER_KNN_IP: c_j = 0 (db_norm_dev ignored; cosine = IP on sylber_knn_unit_rows).  Each list is ordered by (s, j) ascending: the
+ *   smaller score, then the smaller j.  A candidate with a NaN score is never returned; with q_group_dev [n] and db_group_dev [N]
+ *   (int32, both or neither) a candidate with db_group[j] == q_group[i] is skipped.  Rows with fewer than k admissible candidates
+ *   end in idx -1 / score +inf.  Reported scores: L2 max(0, ||q_i||^2 + s) with ||q_i||^2 as sylber_knn_row_norms (fp32; for k = 1
+ *   idx is sylber_kmeans_assign's label and the score max(0, ||q||^2 + dmin)); IP the dot product -s / 2, exact.  score_dev [n, k]
+ *   fp32, idx_dev [n, k] int64.  splits: database splits S (0 = automatic: enough workgroups to cover the chip; any other value is
+ *   clamped to [1, ceil(N / 128)]).  workspace_dev: sylber_knn_workspace_bytes(n, N, D, k, splits) bytes, O(n S k); no [n, N] buffer.
+ * sylber_knn_splits: the S that a call with these n, N and splits uses.
+ * sylber_knn_row_norms: out[r] = sum_c x[r][c]^2, the fmaf chain of sylber_kmeans_assign's norms (lane c % 64 over ascending c, then
+ *   the wave butterfly).
+ * sylber_knn_unit_rows: y[r] = x[r] / sqrtf(that sum), rows whose sum is 0 stay 0 (y may not alias x). */
+enum { SYLBER_KNN_L2 = 0, SYLBER_KNN_IP = 1 };
+int32_t sylber_knn_splits(int32_t n, int32_t N, int32_t splits);
+int64_t sylber_knn_workspace_bytes(int32_t n, int32_t N, int32_t D, int32_t k, int32_t splits);
+int sylber_knn_row_norms(const float* x_dev, int32_t n, int32_t D, float* out_dev, void* stream);
+int sylber_knn_unit_rows(const float* x_dev, int32_t n, int32_t D, float* y_dev, void* stream);
+int sylber_knn_search(const float* q_dev, int32_t n, const float* db_dev, int32_t N, int32_t D, const float* db_norm_dev, int32_t metric,
+                      int32_t k, const int32_t* q_group_dev, const int32_t* db_group_dev, int32_t splits, float* score_dev,
+                      int64_t* idx_dev, void* workspace_dev, void* stream);
+
 /* Learned quantizer (sylber/model/quantizer.py:6-77, 182-257: `load_quantizer` / `Quantizer`), eval, exact fp32.  The host
  * (sylber_amd/quantizer.py) chains: sylber_lq_norm (input norm / padding) -> sylber_ffenc -> sylber_lq_norm (output norm, blank rows)
  * -> sylber_rvq_assign for the art window and the pitch window -> sylber_lq_norm of the quantized rows.  All data pointers are device

@@ -102,6 +102,12 @@ EXPORTS = {
     "sylber_kmeans_update": (c_int, [c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
     "sylber_kmeans_seed_workspace_floats": (c_int64, [c_int32]),
     "sylber_kmeans_seed": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "sylber_knn_splits": (c_int32, [c_int32, c_int32, c_int32]),
+    "sylber_knn_workspace_bytes": (c_int64, [c_int32, c_int32, c_int32, c_int32, c_int32]),
+    "sylber_knn_row_norms": (c_int, [c_void_p, c_int32, c_int32, c_void_p, c_void_p]),
+    "sylber_knn_unit_rows": (c_int, [c_void_p, c_int32, c_int32, c_void_p, c_void_p]),
+    "sylber_knn_search": (c_int, [c_void_p, c_int32, c_void_p, c_int32, c_int32, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_int32,
+                                  c_void_p, c_void_p, c_void_p, c_void_p]),
     "sylber_lq_norm": (c_int, [c_void_p, c_int64, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int64, c_int32, c_void_p, c_int64,
                                c_int32, c_void_p]),
     "sylber_ffenc_workspace_floats": (c_int64, [c_int32, c_int32, POINTER(c_int32)]),

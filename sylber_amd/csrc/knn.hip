@@ -1,0 +1,344 @@
+// Exact k-nearest-neighbour search over a database of syllable embeddings (sylber_amd/search.py: SyllableIndex).
+//   * knn_search_kernel: the exact-fp32 MFMA contraction of km_fused_assign_kernel (kmeans.hip) -- same operand roles, same k-pair
+//     order, so a score's bits do not depend on where it is computed -- with a running per-row top-k in the epilogue instead of the
+//     arg-min.  The grid is (query blocks) x S database splits; each split writes a sorted partial list per query row.
+//   * knn_merge_kernel: pairwise merges of the S partial lists, ceil(log2 S) rounds;  knn_finish_kernel: reported values and -1 / +inf
+//     padding.
+// Every list is ordered by (s, j), smaller score first, then smaller index.  That order is strict and total over the admissible
+// candidates, so the top-k set and its order are unique: the result does not depend on the order in which candidates are inserted,
+// hence not on the split count, the launch geometry or the query chunking.  A NaN score never passes km_better and never enters.
+#include "kernels.h"
+#include "../../include/sylber_hip.h"
+#include <climits>
+
+// contraction geometry of km_fused_assign_kernel: 128 query rows x 128 database rows per tile, K step 16, LDS rows [0 2 .. 14 | 1 3 .. 15]
+constexpr int KN_BM = 128, KN_BN = 128, KN_BK = 16, KN_LD = 20;
+constexpr int KN_STRIP = 32, KN_SP = 132;                 // epilogue strip: 32 query rows x 128 scores, row stride 132 floats
+constexpr int KN_STAGE = 2 * KN_BM * KN_LD;               // floats of the operand staging; the strip (32 x 132) aliases it
+constexpr int KN_KMAX = 128;
+constexpr int KN_TARGET_BLOCKS = 512;                     // automatic splits: (query blocks) x S >= 2 workgroups per CU
+constexpr int KN_MIN_TILES = 4;                           // ... but no split shorter than 4 database tiles
+
+__device__ __forceinline__ bool kn_better(float v, int i, float bv, int bi) { return v < bv || (v == bv && i < bi); }   // km_better
+
+static size_t kn_lds_bytes(int k) { return (size_t)(KN_STAGE + 2 * KN_BN + 4) * 4 + (size_t)KN_BM * k * 8; }
+
+// one wave inserts candidate (v, j) into the sorted list (ls, li)[0..k) if it is better than the k-th entry
+__device__ __forceinline__ void kn_insert(float* ls, int* li, int k, int lane, float v, int j) {
+    if (!kn_better(v, j, ls[k - 1], li[k - 1])) return;
+    // position = entries better than (v, j)
+    int p = 0;
+#pragma unroll
+    for (int h = 0; h < KN_KMAX / 64; ++h) {
+        const int q = lane + 64 * h;
+        const bool b = q < k && kn_better(ls[q], li[q], v, j);
+        p += __popcll(__ballot(b));
+    }
+    // shift [p, k - 1) up by one: all reads, then all writes (a wave's LDS operations complete in order)
+    float sv[KN_KMAX / 64];
+    int si[KN_KMAX / 64];
+#pragma unroll
+    for (int h = 0; h < KN_KMAX / 64; ++h) {
+        const int q = lane + 64 * h;
+        if (q >= p && q < k - 1) { sv[h] = ls[q]; si[h] = li[q]; }
+    }
+#pragma unroll
+    for (int h = 0; h < KN_KMAX / 64; ++h) {
+        const int q = lane + 64 * h;
+        if (q >= p && q < k - 1) { ls[q + 1] = sv[h]; li[q + 1] = si[h]; }
+    }
+    if (lane == 0) { ls[p] = v; li[p] = j; }
+}
+
+// grid (ceil(n / 128), S).  Split sp walks database tiles [sp * tiles / S, (sp + 1) * tiles / S).  cn: ||x_j||^2 (L2) or null (inner
+// product: c_j = 0).  Writes the sorted top-k of each valid query row over its tiles to ps / pi [n][S][k]; entries that did not fill
+// stay (+inf, INT_MAX).
+__global__ __launch_bounds__(256) void knn_search_kernel(const float* __restrict__ q, int n, const float* __restrict__ x, int N, int D,
+                                                         const float* __restrict__ cn, int k, const int32_t* __restrict__ qgrp,
+                                                         const int32_t* __restrict__ xgrp, int S, float* __restrict__ ps,
+                                                         int32_t* __restrict__ pi) {
+    extern __shared__ __attribute__((aligned(16))) float kn_smem[];
+    float* xs = kn_smem;                                   // staging of the query rows (the "x" of km_fused_assign)
+    float* cs = kn_smem + KN_BM * KN_LD;                   // staging of the database rows (its "c")
+    float* strip = kn_smem;                                // epilogue strip, aliasing the staging
+    float* cns = kn_smem + KN_STAGE;
+    int* cgs = (int*)(cns + KN_BN);
+    int* flags = cgs + KN_BN;                              // [4]: strip s holds a candidate that passes its row's threshold
+    float* ls = (float*)(flags + 4);                       // [128][k] sorted scores
+    int* li = (int*)(ls + KN_BM * k);                      // [128][k] their database indices
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int wm = wave >> 1, wn = wave & 1;
+    const int m0 = blockIdx.x * KN_BM, sp = blockIdx.y;
+    const int tiles = (N + KN_BN - 1) / KN_BN;
+    const int tlo = (int)((int64_t)sp * tiles / S), thi = (int)((int64_t)(sp + 1) * tiles / S);
+    for (int e = tid; e < KN_BM * k; e += 256) { ls[e] = INFINITY; li[e] = INT_MAX; }
+    const int sr = tid >> 1, sh = (tid & 1) * 8;
+    int xm = m0 + sr; xm = xm < n ? xm : n - 1;
+    const float* qrow = q + (size_t)xm * D + sh;
+    float* xdst = xs + sr * KN_LD + (sh >> 1);
+    float* cdst = cs + sr * KN_LD + (sh >> 1);
+    const int frow = lane & 31, fh = lane >> 5;
+    const int ksteps = D / KN_BK, T = ksteps * (thi - tlo);
+    int qg[2] = {0, 0};
+    if (qgrp) {
+#pragma unroll
+        for (int fm = 0; fm < 2; ++fm) { const int r = m0 + wm * 64 + fm * 32 + frow; qg[fm] = qgrp[r < n ? r : n - 1]; }
+    }
+
+    f32x16_t acc[2][2];
+    float4 xa, xb, ca, cb;
+    auto fetch = [&](int t) {
+        const int tile = tlo + t / ksteps, k0 = (t % ksteps) * KN_BK;
+        int cr = tile * KN_BN + sr; cr = cr < N ? cr : N - 1;
+        const float* crow = x + (size_t)cr * D + sh + k0;
+        xa = *(const float4*)(qrow + k0); xb = *(const float4*)(qrow + k0 + 4);
+        ca = *(const float4*)crow; cb = *(const float4*)(crow + 4);
+    };
+    if (T > 0) fetch(0);
+    for (int t = 0; t < T; ++t) {
+        const int tile = tlo + t / ksteps, ks = t % ksteps, n0 = tile * KN_BN;
+        if (ks == 0) {
+#pragma unroll
+            for (int i = 0; i < 2; ++i)
+#pragma unroll
+                for (int j = 0; j < 2; ++j)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+        }
+        __syncthreads();                                   // previous fragments, strip, cns / cgs and flags are all read
+        *(float4*)xdst = make_float4(xa.x, xa.z, xb.x, xb.z);
+        *(float4*)(xdst + 8) = make_float4(xa.y, xa.w, xb.y, xb.w);
+        *(float4*)cdst = make_float4(ca.x, ca.z, cb.x, cb.z);
+        *(float4*)(cdst + 8) = make_float4(ca.y, ca.w, cb.y, cb.w);
+        if (ks == 0 && tid < KN_BN) {
+            const int j = n0 + tid;
+            cns[tid] = (cn && j < N) ? cn[j] : 0.f;
+            cgs[tid] = (xgrp && j < N) ? xgrp[j] : 0;
+            if (tid < 4) flags[tid] = 0;
+        }
+        __syncthreads();
+        if (t + 1 < T) fetch(t + 1);
+        f32x4_t xf[2][2], cf[2][2];
+#pragma unroll
+        for (int f = 0; f < 2; ++f) {
+            const float* xp = xs + (wm * 64 + f * 32 + frow) * KN_LD + fh * 8;
+            const float* cp = cs + (wn * 64 + f * 32 + frow) * KN_LD + fh * 8;
+            xf[f][0] = *(const f32x4_t*)xp; xf[f][1] = *(const f32x4_t*)(xp + 4);
+            cf[f][0] = *(const f32x4_t*)cp; cf[f][1] = *(const f32x4_t*)(cp + 4);
+        }
+#pragma unroll
+        for (int i = 0; i < 8; ++i)
+#pragma unroll
+            for (int fm = 0; fm < 2; ++fm)
+#pragma unroll
+                for (int fn = 0; fn < 2; ++fn)
+                    acc[fm][fn] = __builtin_amdgcn_mfma_f32_32x32x2f32(cf[fn][i >> 2][i & 3], xf[fm][i >> 2][i & 3], acc[fm][fn], 0, 0, 0);
+        if (ks != ksteps - 1) continue;
+        // epilogue: lane holds query row wm*64 + fm*32 + frow against database rows n0 + wn*64 + fn*32 + 8g + 4fh + e.  Scores become
+        // s = fmaf(-2, dot, c_j); inadmissible ones (past N, same group, past n) become NaN.  Test against the row's k-th entry.
+        bool pass[2] = {false, false};
+#pragma unroll
+        for (int fm = 0; fm < 2; ++fm) {
+            const int rl = wm * 64 + fm * 32 + frow;
+            const float tv = ls[rl * k + k - 1];
+            const int ti = li[rl * k + k - 1];
+            const bool rowok = m0 + rl < n;
+#pragma unroll
+            for (int fn = 0; fn < 2; ++fn)
+#pragma unroll
+                for (int g = 0; g < 4; ++g)
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        const int cl = wn * 64 + fn * 32 + 8 * g + 4 * fh + e;
+                        float s = fmaf(-2.0f, acc[fm][fn][4 * g + e], cns[cl]);
+                        if (!rowok || n0 + cl >= N || (xgrp && cgs[cl] == qg[fm])) s = __builtin_nanf("");
+                        acc[fm][fn][4 * g + e] = s;
+                        pass[fm] = pass[fm] || kn_better(s, n0 + cl, tv, ti);
+                    }
+        }
+        if (pass[0]) flags[wm * 2 + 0] = 1;
+        if (pass[1]) flags[wm * 2 + 1] = 1;
+        __syncthreads();                                   // flags complete; every wave is past its fragment reads (strip may alias)
+        const int fl = flags[0] | (flags[1] << 1) | (flags[2] << 2) | (flags[3] << 3);
+        for (int st = 0; st < 4; ++st) {
+            if (!((fl >> st) & 1)) continue;               // block-uniform
+            if (wm == (st >> 1)) {
+                const int fm = st & 1;
+#pragma unroll
+                for (int fn = 0; fn < 2; ++fn)
+#pragma unroll
+                    for (int g = 0; g < 4; ++g)
+                        *(float4*)(strip + frow * KN_SP + wn * 64 + fn * 32 + 8 * g + 4 * fh) =
+                            make_float4(acc[fm][fn][4 * g], acc[fm][fn][4 * g + 1], acc[fm][fn][4 * g + 2], acc[fm][fn][4 * g + 3]);
+            }
+            __syncthreads();
+            // each wave takes rows wave, wave + 4, ... of the strip: the survivors of a row go into its list one at a time
+            for (int rr = wave; rr < KN_STRIP; rr += 4) {
+                const int rl = st * KN_STRIP + rr;
+                if (m0 + rl >= n) break;
+                float* lsr = ls + rl * k;
+                int* lir = li + rl * k;
+                const float tv = lsr[k - 1];
+                const int ti = lir[k - 1];
+                const float v0 = strip[rr * KN_SP + lane], v1 = strip[rr * KN_SP + 64 + lane];
+                uint64_t b0 = __ballot(kn_better(v0, n0 + lane, tv, ti));
+                uint64_t b1 = __ballot(kn_better(v1, n0 + 64 + lane, tv, ti));
+                while (b0) {
+                    const int c = __ffsll((unsigned long long)b0) - 1;
+                    b0 &= b0 - 1;
+                    kn_insert(lsr, lir, k, lane, strip[rr * KN_SP + c], n0 + c);
+                }
+                while (b1) {
+                    const int c = __ffsll((unsigned long long)b1) - 1;
+                    b1 &= b1 - 1;
+                    kn_insert(lsr, lir, k, lane, strip[rr * KN_SP + 64 + c], n0 + 64 + c);
+                }
+            }
+            __syncthreads();                               // the strip is read before the next strip (or the staging) overwrites it
+        }
+    }
+    __syncthreads();
+    for (int rl = wave; rl < KN_BM; rl += 4) {
+        if (m0 + rl >= n) break;
+        const size_t o = ((size_t)(m0 + rl) * S + sp) * k;
+        for (int e = lane; e < k; e += 64) { ps[o + e] = ls[rl * k + e]; pi[o + e] = li[rl * k + e]; }
+    }
+}
+
+// one wave per (row, pair): lists 2p and 2p + 1 of row r (m lists of k per row in src) -> list p of row r (ceil(m / 2) per row in
+// dst).  An element's rank in the merged list is its position plus the number of entries of the other list before it (A's elements go
+// before B's equal ones: only the (+inf, INT_MAX) fillers can be equal), so every output slot < k is written exactly once.
+__global__ __launch_bounds__(64) void knn_merge_kernel(const float* __restrict__ ss, const int32_t* __restrict__ si, int m, int k,
+                                                       float* __restrict__ ds, int32_t* __restrict__ di) {
+    const int r = blockIdx.x, p = blockIdx.y, lane = threadIdx.x;
+    const int mo = (m + 1) / 2;
+    const float* as = ss + ((size_t)r * m + 2 * p) * k;
+    const int32_t* ai = si + ((size_t)r * m + 2 * p) * k;
+    float* os = ds + ((size_t)r * mo + p) * k;
+    int32_t* oi = di + ((size_t)r * mo + p) * k;
+    if (2 * p + 1 >= m) {
+        for (int e = lane; e < k; e += 64) { os[e] = as[e]; oi[e] = ai[e]; }
+        return;
+    }
+    const float* bs = as + k;
+    const int32_t* bi = ai + k;
+    for (int e = lane; e < k; e += 64) {
+        {   // A[e]: + #{B strictly better}
+            const float v = as[e]; const int j = ai[e];
+            int lo = 0, hi = k;
+            while (lo < hi) { const int mid = (lo + hi) >> 1; if (kn_better(bs[mid], bi[mid], v, j)) lo = mid + 1; else hi = mid; }
+            if (e + lo < k) { os[e + lo] = v; oi[e + lo] = j; }
+        }
+        {   // B[e]: + #{A not worse}
+            const float v = bs[e]; const int j = bi[e];
+            int lo = 0, hi = k;
+            while (lo < hi) { const int mid = (lo + hi) >> 1; if (!kn_better(v, j, as[mid], ai[mid])) lo = mid + 1; else hi = mid; }
+            if (e + lo < k) { os[e + lo] = v; oi[e + lo] = j; }
+        }
+    }
+}
+
+// reported values: L2 max(0, ||q||^2 + s), inner product -s / 2 (as 0 - s / 2, so that s = 0 reports +0); fillers -> (+inf, -1)
+__global__ __launch_bounds__(256) void knn_finish_kernel(const float* __restrict__ ls, const int32_t* __restrict__ li, int n, int k,
+                                                         const float* __restrict__ qsq, float* __restrict__ score, int64_t* __restrict__ idx) {
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= (int64_t)n * k) return;
+    const int j = li[e];
+    const float s = ls[e];
+    if (j == INT_MAX) { score[e] = INFINITY; idx[e] = -1; return; }
+    score[e] = qsq ? fmaxf(0.f, qsq[e / k] + s) : 0.f - 0.5f * s;
+    idx[e] = j;
+}
+
+// y[r] = x[r] / sqrt(sum x[r]^2) (the sum an fmaf chain per lane in ascending column steps of 64, then the wave butterfly), 0 rows stay 0
+__global__ __launch_bounds__(256) void knn_unit_rows_kernel(const float* __restrict__ x, float* __restrict__ y, int n, int D) {
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int r = blockIdx.x * 4 + wave;
+    if (r >= n) return;
+    float s = 0.f;
+    for (int c = lane; c < D; c += 64) { const float v = x[(size_t)r * D + c]; s = fmaf(v, v, s); }
+    s = wave_sum(s);
+    const float nrm = sqrtf(s);
+    for (int c = lane; c < D; c += 64) y[(size_t)r * D + c] = s > 0.f ? x[(size_t)r * D + c] / nrm : 0.f;
+}
+
+static int kn_splits(int32_t n, int32_t N, int32_t splits) {
+    const int64_t nb = ((int64_t)n + KN_BM - 1) / KN_BM, tiles = ((int64_t)N + KN_BN - 1) / KN_BN;
+    int64_t S = splits;
+    if (S <= 0) {
+        S = (KN_TARGET_BLOCKS + nb - 1) / nb;
+        const int64_t cap = tiles / KN_MIN_TILES;
+        S = S < cap ? S : cap;
+    }
+    S = S < tiles ? S : tiles;
+    S = S < 65535 ? S : 65535;
+    return (int)(S < 1 ? 1 : S);
+}
+
+static int64_t kn_al(int64_t bytes) { return (bytes + 255) / 256 * 256; }
+
+extern "C" int32_t sylber_knn_splits(int32_t n, int32_t N, int32_t splits) {
+    if (n < 1 || N < 1) return -1;
+    return kn_splits(n, N, splits);
+}
+
+extern "C" int64_t sylber_knn_workspace_bytes(int32_t n, int32_t N, int32_t D, int32_t k, int32_t splits) {
+    if (n < 1 || N < 1 || D < 1 || k < 1 || k > KN_KMAX) return -1;
+    const int64_t S = kn_splits(n, N, splits), S2 = (S + 1) / 2;
+    // ||q||^2 [n] | scores [n][S][k] | indices [n][S][k] | scores [n][ceil(S/2)][k] | indices [n][ceil(S/2)][k]
+    return kn_al((int64_t)n * 4) + 2 * kn_al((int64_t)n * S * k * 4) + 2 * kn_al((int64_t)n * S2 * k * 4);
+}
+
+extern "C" int sylber_knn_row_norms(const float* x_dev, int32_t n, int32_t D, float* out_dev, void* stream) {
+    if (!x_dev || !out_dev || n < 1 || D < 1) { syl_set_error("sylber_knn_row_norms", "bad argument"); return 1; }
+    return launch_km_sqnorm(x_dev, out_dev, n, D, (hipStream_t)stream);
+}
+
+extern "C" int sylber_knn_unit_rows(const float* x_dev, int32_t n, int32_t D, float* y_dev, void* stream) {
+    if (!x_dev || !y_dev || n < 1 || D < 1) { syl_set_error("sylber_knn_unit_rows", "bad argument"); return 1; }
+    hipLaunchKernelGGL(knn_unit_rows_kernel, dim3((n + 3) / 4), dim3(256), 0, (hipStream_t)stream, x_dev, y_dev, n, D);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+extern "C" int sylber_knn_search(const float* q_dev, int32_t n, const float* db_dev, int32_t N, int32_t D, const float* db_norm_dev,
+                                 int32_t metric, int32_t k, const int32_t* q_group_dev, const int32_t* db_group_dev, int32_t splits,
+                                 float* score_dev, int64_t* idx_dev, void* workspace_dev, void* stream) {
+    static const char* what = "sylber_knn_search";
+    hipStream_t s = (hipStream_t)stream;
+    if (!q_dev || !db_dev || !score_dev || !idx_dev || !workspace_dev) { syl_set_error(what, "null argument"); return 1; }
+    if (n < 1 || N < 1 || D < 16 || D % 16) { syl_set_error(what, "need n, N >= 1 and D a multiple of 16"); return 1; }
+    if (k < 1 || k > KN_KMAX) { syl_set_error(what, "need 1 <= k <= 128"); return 1; }
+    if (metric != SYLBER_KNN_L2 && metric != SYLBER_KNN_IP) { syl_set_error(what, "unknown metric"); return 1; }
+    if (metric == SYLBER_KNN_L2 && !db_norm_dev) { syl_set_error(what, "the L2 metric needs db_norm_dev"); return 1; }
+    if (!q_group_dev != !db_group_dev) { syl_set_error(what, "q_group_dev and db_group_dev go together"); return 1; }
+    const int S = kn_splits(n, N, splits), S2 = (S + 1) / 2;
+    char* w = (char*)workspace_dev;
+    float* qsq = (float*)w;
+    w += kn_al((int64_t)n * 4);
+    float* s0 = (float*)w; w += kn_al((int64_t)n * S * k * 4);
+    int32_t* i0 = (int32_t*)w; w += kn_al((int64_t)n * S * k * 4);
+    float* s1 = (float*)w; w += kn_al((int64_t)n * S2 * k * 4);
+    int32_t* i1 = (int32_t*)w;
+    if (metric == SYLBER_KNN_L2 && launch_km_sqnorm(q_dev, qsq, n, D, s)) return 1;
+    const size_t lds = kn_lds_bytes(k);
+    static PerDeviceOnce once;
+    if (once.need()) HIP_TRY(hipFuncSetAttribute((const void*)knn_search_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kn_lds_bytes(KN_KMAX)));
+    const unsigned nb = (unsigned)((n + KN_BM - 1) / KN_BM);
+    hipLaunchKernelGGL(knn_search_kernel, dim3(nb, (unsigned)S), dim3(256), lds, s, q_dev, n, db_dev, N, D,
+                       metric == SYLBER_KNN_L2 ? db_norm_dev : nullptr, k, q_group_dev, db_group_dev, S, s0, i0);
+    HIP_TRY(hipGetLastError());
+    float* cs = s0; int32_t* ci = i0;
+    float* os = s1; int32_t* oi = i1;
+    for (int m = S; m > 1; m = (m + 1) / 2) {
+        hipLaunchKernelGGL(knn_merge_kernel, dim3((unsigned)n, (unsigned)((m + 1) / 2)), dim3(64), 0, s, cs, ci, m, k, os, oi);
+        HIP_TRY(hipGetLastError());
+        float* ts = cs; cs = os; os = ts;
+        int32_t* ti = ci; ci = oi; oi = ti;
+    }
+    const int64_t tot = (int64_t)n * k;
+    hipLaunchKernelGGL(knn_finish_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, cs, ci, n, k,
+                       metric == SYLBER_KNN_L2 ? qsq : nullptr, score_dev, idx_dev);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
