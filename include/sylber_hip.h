@@ -242,6 +242,29 @@ int sylber_knn_search(const float* q_dev, int32_t n, const float* db_dev, int32_
                       int32_t k, const int32_t* q_group_dev, const int32_t* db_group_dev, int32_t splits, float* score_dev,
                       int64_t* idx_dev, void* workspace_dev, void* stream);
 
+/* Inverted-file search (sylber_amd/search.py: IVFSyllableIndex): sylber_knn_search restricted, per query, to the rows of the lists it
+ * probes.  The rows lie list by list in rows_dev (list l = positions list_offsets[l] .. list_offsets[l + 1], ascending original id
+ * within a list); row_id_dev [N] maps a position to the row's original id, row_norm_dev / row_group_dev are in position order too.
+ * sylber_ivf_work_items (host only, no GPU): the work items of one call.  pair_counts_host [nlist]: how many (query, probe slot)
+ *   pairs probe each list; list_offsets_host [nlist + 1].  One item per (probed list, block of up to 128 of its pairs, cut of at
+ *   most T of its 128-row tiles), in list order, 8 int32 each: {list, pair_begin, pair_count, row_lo, row_hi, cut, last, tile_begin};
+ *   pair_begin indexes the pairs grouped by list, [row_lo, row_hi) are positions, last marks a list's final cut.  item_tiles: T
+ *   (0 = automatic; raised where a list would need more than 16 cuts).  A probed empty list gets one item without rows.  Returns the
+ *   number of items (-1: bad argument, or more than capacity); writes them when items_host is non-null and *cuts_out = the largest
+ *   number of cuts of any probed list.
+ * sylber_ivf_search: q_dev [n, D]; pair_dev [n * nprobe] int32: the flat indices (query * nprobe + slot) of the probe table grouped
+ *   by list (a stable sort of the table by list id), every index exactly once; items_dev [n_items][8] as above for these pairs.
+ *   Each pair's partial top-k lists (one per cut) hold (s, original id) with s = fmaf(-2, q . x, c) exactly as sylber_knn_search;
+ *   the nprobe * cuts lists of a query are merged and reported as sylber_knn_search does (order (s, id), NaN never returned, group
+ *   exclusion, -1 / +inf padding).  workspace_dev: sylber_ivf_workspace_bytes(n, nprobe, k, cuts) bytes, O(n nprobe cuts k). */
+int32_t sylber_ivf_work_items(const int32_t* pair_counts_host, const int32_t* list_offsets_host, int32_t nlist, int32_t item_tiles,
+                              int32_t* items_host, int32_t capacity, int32_t* cuts_out);
+int64_t sylber_ivf_workspace_bytes(int32_t n, int32_t nprobe, int32_t k, int32_t cuts);
+int sylber_ivf_search(const float* q_dev, int32_t n, int32_t D, int32_t nprobe, const int32_t* pair_dev, const int32_t* items_dev,
+                      int32_t n_items, int32_t cuts, const float* rows_dev, const int32_t* row_id_dev, const float* row_norm_dev,
+                      int32_t metric, int32_t k, const int32_t* q_group_dev, const int32_t* row_group_dev, float* score_dev,
+                      int64_t* idx_dev, void* workspace_dev, void* stream);
+
 /* Learned quantizer (sylber/model/quantizer.py:6-77, 182-257: `load_quantizer` / `Quantizer`), eval, exact fp32.  The host
  * (sylber_amd/quantizer.py) chains: sylber_lq_norm (input norm / padding) -> sylber_ffenc -> sylber_lq_norm (output norm, blank rows)
  * -> sylber_rvq_assign for the art window and the pitch window -> sylber_lq_norm of the quantized rows.  All data pointers are device

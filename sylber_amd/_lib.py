@@ -108,6 +108,10 @@ EXPORTS = {
     "sylber_knn_unit_rows": (c_int, [c_void_p, c_int32, c_int32, c_void_p, c_void_p]),
     "sylber_knn_search": (c_int, [c_void_p, c_int32, c_void_p, c_int32, c_int32, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_int32,
                                   c_void_p, c_void_p, c_void_p, c_void_p]),
+    "sylber_ivf_work_items": (c_int32, [POINTER(c_int32), POINTER(c_int32), c_int32, c_int32, POINTER(c_int32), c_int32, POINTER(c_int32)]),
+    "sylber_ivf_workspace_bytes": (c_int64, [c_int32, c_int32, c_int32, c_int32]),
+    "sylber_ivf_search": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p,
+                                  c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "sylber_lq_norm": (c_int, [c_void_p, c_int64, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int64, c_int32, c_void_p, c_int64,
                                c_int32, c_void_p]),
     "sylber_ffenc_workspace_floats": (c_int64, [c_int32, c_int32, POINTER(c_int32)]),

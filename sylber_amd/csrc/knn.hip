@@ -2,6 +2,7 @@
 //   * knn_search_kernel: the exact-fp32 MFMA contraction of km_fused_assign_kernel (kmeans.hip) -- same operand roles, same k-pair
 //     order, so a score's bits do not depend on where it is computed -- with a running per-row top-k in the epilogue instead of the
 //     arg-min.  The grid is (query blocks) x S database splits; each split writes a sorted partial list per query row.
+//   * ivf_scan_kernel (IVFSyllableIndex): the same contraction over the ragged lists of an inverted file, for gathered query rows.
 //   * knn_merge_kernel: pairwise merges of the S partial lists, ceil(log2 S) rounds;  knn_finish_kernel: reported values and -1 / +inf
 //     padding.
 // Every list is ordered by (s, j), smaller score first, then smaller index.  That order is strict and total over the admissible
@@ -262,6 +263,183 @@ __global__ __launch_bounds__(256) void knn_unit_rows_kernel(const float* __restr
     for (int c = lane; c < D; c += 64) y[(size_t)r * D + c] = s > 0.f ? x[(size_t)r * D + c] / nrm : 0.f;
 }
 
+// ---- inverted-file scan (sylber_amd/search.py: IVFSyllableIndex) ---------------------------------------------------------------------
+// The database rows lie list by list (rows [row_lo, row_hi) of a work item belong to ONE list); rid maps a position to the row's
+// original id, which is the id that orders, is reported and breaks ties.  A work item is 8 int32:
+//   {list, pair_begin, pair_count <= 128, row_lo, row_hi, cut, last, tile_begin}
+// It gathers the queries pair[pair_begin + r] / nprobe of its up to 128 (query, probe slot) pairs into the operand tile, walks the
+// 128-row tiles of [row_lo, row_hi) with knn_search_kernel's contraction (same operand roles and k-pair order: same score bits) and
+// writes each pair's sorted top-k to partial list (pair * C + cut) of ps / pi [n * nprobe][C][k].  The item with last != 0 also
+// writes the fillers of the lists cut + 1 .. C - 1 of its pairs, so every partial list is written by exactly one item whatever the
+// workspace held.  Positions >= row_hi (the next list, or the end of the database) are never read and never become candidates.
+constexpr int IV_ITEM = 8;
+constexpr int IV_ITEM_TILES = 16;                         // automatic: at most 16 tiles (2 048 rows) of a list per work item ...
+constexpr int IV_TARGET_ITEMS = 512;                      // ... fewer while the launch has fewer than two work items per CU ...
+constexpr int IV_MIN_TILES = 2;                           // ... but not below 2 tiles
+constexpr int IV_MAX_CUTS = 16;                           // and never more than 16 cuts of one list (bounds the partial lists)
+
+__global__ __launch_bounds__(256) void ivf_scan_kernel(const float* __restrict__ q, const int32_t* __restrict__ items,
+                                                       const int32_t* __restrict__ pair, int nprobe, const float* __restrict__ x, int D,
+                                                       const int32_t* __restrict__ rid, const float* __restrict__ cn, int k,
+                                                       const int32_t* __restrict__ qgrp, const int32_t* __restrict__ xgrp, int C,
+                                                       float* __restrict__ ps, int32_t* __restrict__ pi) {
+    extern __shared__ __attribute__((aligned(16))) float kn_smem[];
+    float* xs = kn_smem;
+    float* cs = kn_smem + KN_BM * KN_LD;
+    float* strip = kn_smem;
+    float* cns = kn_smem + KN_STAGE;
+    int* cgs = (int*)(cns + KN_BN);
+    int* cids = cgs + KN_BN;                               // original ids of the tile's rows (INT_MAX behind the end)
+    int* prs = cids + KN_BN;                               // the item's pairs
+    int* flags = prs + KN_BM;
+    float* ls = (float*)(flags + 4);
+    int* li = (int*)(ls + KN_BM * k);
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int wm = wave >> 1, wn = wave & 1;
+    const int32_t* it = items + (size_t)blockIdx.x * IV_ITEM;
+    const int pbeg = it[1], cnt = it[2], rlo = it[3], rhi = it[4], cut = it[5], last = it[6];
+    const int tiles = (rhi - rlo + KN_BN - 1) / KN_BN;
+    for (int e = tid; e < KN_BM * k; e += 256) { ls[e] = INFINITY; li[e] = INT_MAX; }
+    if (tid < KN_BM) prs[tid] = pair[pbeg + (tid < cnt ? tid : cnt - 1)];
+    const int sr = tid >> 1, sh = (tid & 1) * 8;
+    const int xm = pair[pbeg + (sr < cnt ? sr : cnt - 1)] / nprobe;
+    const float* qrow = q + (size_t)xm * D + sh;
+    float* xdst = xs + sr * KN_LD + (sh >> 1);
+    float* cdst = cs + sr * KN_LD + (sh >> 1);
+    const int frow = lane & 31, fh = lane >> 5;
+    const int ksteps = D / KN_BK, T = ksteps * tiles;
+    int qg[2] = {0, 0};
+    bool live[2];                                          // wave-uniform: this wave's 32-row half holds a pair of the item
+#pragma unroll
+    for (int fm = 0; fm < 2; ++fm) {
+        live[fm] = wm * 64 + fm * 32 < cnt;
+        if (qgrp) { const int r = wm * 64 + fm * 32 + frow; qg[fm] = qgrp[pair[pbeg + (r < cnt ? r : cnt - 1)] / nprobe]; }
+    }
+
+    f32x16_t acc[2][2];
+    float4 xa, xb, ca, cb;
+    auto fetch = [&](int t) {
+        const int tile = t / ksteps, k0 = (t % ksteps) * KN_BK;
+        int cr = rlo + tile * KN_BN + sr; cr = cr < rhi ? cr : rhi - 1;
+        const float* crow = x + (size_t)cr * D + sh + k0;
+        xa = *(const float4*)(qrow + k0); xb = *(const float4*)(qrow + k0 + 4);
+        ca = *(const float4*)crow; cb = *(const float4*)(crow + 4);
+    };
+    if (T > 0) fetch(0);
+    for (int t = 0; t < T; ++t) {
+        const int tile = t / ksteps, ks = t % ksteps, n0 = rlo + tile * KN_BN;
+        if (ks == 0) {
+#pragma unroll
+            for (int i = 0; i < 2; ++i)
+#pragma unroll
+                for (int j = 0; j < 2; ++j)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+        }
+        __syncthreads();
+        *(float4*)xdst = make_float4(xa.x, xa.z, xb.x, xb.z);
+        *(float4*)(xdst + 8) = make_float4(xa.y, xa.w, xb.y, xb.w);
+        *(float4*)cdst = make_float4(ca.x, ca.z, cb.x, cb.z);
+        *(float4*)(cdst + 8) = make_float4(ca.y, ca.w, cb.y, cb.w);
+        if (ks == 0 && tid < KN_BN) {
+            const int j = n0 + tid;
+            cns[tid] = (cn && j < rhi) ? cn[j] : 0.f;
+            cgs[tid] = (xgrp && j < rhi) ? xgrp[j] : 0;
+            cids[tid] = j < rhi ? rid[j] : INT_MAX;
+            if (tid < 4) flags[tid] = 0;
+        }
+        __syncthreads();
+        if (t + 1 < T) fetch(t + 1);
+        f32x4_t xf[2][2], cf[2][2];
+#pragma unroll
+        for (int f = 0; f < 2; ++f) {
+            const float* xp = xs + (wm * 64 + f * 32 + frow) * KN_LD + fh * 8;
+            const float* cp = cs + (wn * 64 + f * 32 + frow) * KN_LD + fh * 8;
+            xf[f][0] = *(const f32x4_t*)xp; xf[f][1] = *(const f32x4_t*)(xp + 4);
+            cf[f][0] = *(const f32x4_t*)cp; cf[f][1] = *(const f32x4_t*)(cp + 4);
+        }
+        // a half without pairs skips its MFMAs: its scores are masked below whatever they are
+#pragma unroll
+        for (int fm = 0; fm < 2; ++fm) {
+            if (!live[fm]) continue;
+#pragma unroll
+            for (int i = 0; i < 8; ++i)
+#pragma unroll
+                for (int fn = 0; fn < 2; ++fn)
+                    acc[fm][fn] = __builtin_amdgcn_mfma_f32_32x32x2f32(cf[fn][i >> 2][i & 3], xf[fm][i >> 2][i & 3], acc[fm][fn], 0, 0, 0);
+        }
+        if (ks != ksteps - 1) continue;
+        bool pass[2] = {false, false};
+#pragma unroll
+        for (int fm = 0; fm < 2; ++fm) {
+            const int rl = wm * 64 + fm * 32 + frow;
+            const float tv = ls[rl * k + k - 1];
+            const int ti = li[rl * k + k - 1];
+            const bool rowok = rl < cnt;
+#pragma unroll
+            for (int fn = 0; fn < 2; ++fn)
+#pragma unroll
+                for (int g = 0; g < 4; ++g)
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        const int cl = wn * 64 + fn * 32 + 8 * g + 4 * fh + e;
+                        float s = fmaf(-2.0f, acc[fm][fn][4 * g + e], cns[cl]);
+                        if (!rowok || n0 + cl >= rhi || (xgrp && cgs[cl] == qg[fm])) s = __builtin_nanf("");
+                        acc[fm][fn][4 * g + e] = s;
+                        pass[fm] = pass[fm] || kn_better(s, cids[cl], tv, ti);
+                    }
+        }
+        if (pass[0]) flags[wm * 2 + 0] = 1;
+        if (pass[1]) flags[wm * 2 + 1] = 1;
+        __syncthreads();
+        const int fl = flags[0] | (flags[1] << 1) | (flags[2] << 2) | (flags[3] << 3);
+        for (int st = 0; st < 4; ++st) {
+            if (!((fl >> st) & 1)) continue;               // block-uniform
+            if (wm == (st >> 1)) {
+                const int fm = st & 1;
+#pragma unroll
+                for (int fn = 0; fn < 2; ++fn)
+#pragma unroll
+                    for (int g = 0; g < 4; ++g)
+                        *(float4*)(strip + frow * KN_SP + wn * 64 + fn * 32 + 8 * g + 4 * fh) =
+                            make_float4(acc[fm][fn][4 * g], acc[fm][fn][4 * g + 1], acc[fm][fn][4 * g + 2], acc[fm][fn][4 * g + 3]);
+            }
+            __syncthreads();
+            for (int rr = wave; rr < KN_STRIP; rr += 4) {
+                const int rl = st * KN_STRIP + rr;
+                if (rl >= cnt) break;
+                float* lsr = ls + rl * k;
+                int* lir = li + rl * k;
+                const float tv = lsr[k - 1];
+                const int ti = lir[k - 1];
+                const float v0 = strip[rr * KN_SP + lane], v1 = strip[rr * KN_SP + 64 + lane];
+                uint64_t b0 = __ballot(kn_better(v0, cids[lane], tv, ti));
+                uint64_t b1 = __ballot(kn_better(v1, cids[64 + lane], tv, ti));
+                while (b0) {
+                    const int c = __ffsll((unsigned long long)b0) - 1;
+                    b0 &= b0 - 1;
+                    kn_insert(lsr, lir, k, lane, strip[rr * KN_SP + c], cids[c]);
+                }
+                while (b1) {
+                    const int c = __ffsll((unsigned long long)b1) - 1;
+                    b1 &= b1 - 1;
+                    kn_insert(lsr, lir, k, lane, strip[rr * KN_SP + 64 + c], cids[64 + c]);
+                }
+            }
+            __syncthreads();
+        }
+    }
+    __syncthreads();
+    for (int rl = wave; rl < cnt; rl += 4) {
+        const size_t o = ((size_t)prs[rl] * C + cut) * k;
+        for (int e = lane; e < k; e += 64) { ps[o + e] = ls[rl * k + e]; pi[o + e] = li[rl * k + e]; }
+        if (last)
+            for (int e = lane; e < (C - 1 - cut) * k; e += 64) { ps[o + k + e] = INFINITY; pi[o + k + e] = INT_MAX; }
+    }
+}
+
+static size_t iv_lds_bytes(int k) { return (size_t)(KN_STAGE + 4 * KN_BN + 4) * 4 + (size_t)KN_BM * k * 8; }
+
 static int kn_splits(int32_t n, int32_t N, int32_t splits) {
     const int64_t nb = ((int64_t)n + KN_BM - 1) / KN_BM, tiles = ((int64_t)N + KN_BN - 1) / KN_BN;
     int64_t S = splits;
@@ -331,6 +509,106 @@ extern "C" int sylber_knn_search(const float* q_dev, int32_t n, const float* db_
     float* cs = s0; int32_t* ci = i0;
     float* os = s1; int32_t* oi = i1;
     for (int m = S; m > 1; m = (m + 1) / 2) {
+        hipLaunchKernelGGL(knn_merge_kernel, dim3((unsigned)n, (unsigned)((m + 1) / 2)), dim3(64), 0, s, cs, ci, m, k, os, oi);
+        HIP_TRY(hipGetLastError());
+        float* ts = cs; cs = os; os = ts;
+        int32_t* ti = ci; ci = oi; oi = ti;
+    }
+    const int64_t tot = (int64_t)n * k;
+    hipLaunchKernelGGL(knn_finish_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, cs, ci, n, k,
+                       metric == SYLBER_KNN_L2 ? qsq : nullptr, score_dev, idx_dev);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// Host only.  One work item per (probed list, block of up to 128 of its pairs, cut of its tiles); see ivf_scan_kernel.
+extern "C" int32_t sylber_ivf_work_items(const int32_t* pair_counts_host, const int32_t* list_offsets_host, int32_t nlist, int32_t item_tiles,
+                                         int32_t* items_host, int32_t capacity, int32_t* cuts_out) {
+    if (!pair_counts_host || !list_offsets_host || nlist < 1 || item_tiles < 0) return -1;
+    int64_t W0 = 0, TT = 0, maxt = 0;
+    for (int l = 0; l < nlist; ++l) {
+        const int64_t pc = pair_counts_host[l], sz = (int64_t)list_offsets_host[l + 1] - list_offsets_host[l];
+        if (pc < 0 || sz < 0) return -1;
+        if (!pc) continue;
+        const int64_t tiles = (sz + KN_BN - 1) / KN_BN, qb = (pc + KN_BM - 1) / KN_BM;
+        W0 += qb; TT += qb * (tiles > 1 ? tiles : 1);
+        maxt = tiles > maxt ? tiles : maxt;
+    }
+    int64_t T = item_tiles;
+    if (T <= 0) {
+        T = IV_ITEM_TILES;
+        if (W0 < IV_TARGET_ITEMS) {
+            const int64_t t = (TT + IV_TARGET_ITEMS - 1) / IV_TARGET_ITEMS;
+            T = t < IV_MIN_TILES ? IV_MIN_TILES : (t < IV_ITEM_TILES ? t : IV_ITEM_TILES);
+        }
+    }
+    const int64_t floorT = (maxt + IV_MAX_CUTS - 1) / IV_MAX_CUTS;
+    T = T < floorT ? floorT : T;
+    int64_t W = 0, C = 1, pb = 0;
+    for (int l = 0; l < nlist; ++l) {
+        const int64_t pc = pair_counts_host[l];
+        if (!pc) continue;
+        const int64_t lo = list_offsets_host[l], hi = list_offsets_host[l + 1];
+        const int64_t tiles = (hi - lo + KN_BN - 1) / KN_BN, cuts = tiles > T ? (tiles + T - 1) / T : 1;
+        C = cuts > C ? cuts : C;
+        for (int64_t b = 0; b < pc; b += KN_BM)
+            for (int64_t c = 0; c < cuts; ++c, ++W) {
+                if (!items_host) continue;
+                if (W >= capacity) return -1;
+                const int64_t t0 = c * T, t1 = (c + 1) * T < tiles ? (c + 1) * T : tiles;
+                const int64_t r0 = lo + t0 * KN_BN, r1 = lo + t1 * KN_BN < hi ? lo + t1 * KN_BN : hi;
+                int32_t* it = items_host + W * IV_ITEM;
+                it[0] = l; it[1] = (int32_t)(pb + b); it[2] = (int32_t)(pc - b < KN_BM ? pc - b : KN_BM);
+                it[3] = (int32_t)r0; it[4] = (int32_t)(r1 > r0 ? r1 : r0); it[5] = (int32_t)c; it[6] = c == cuts - 1; it[7] = (int32_t)t0;
+            }
+        pb += pc;
+    }
+    if (W > INT32_MAX) return -1;
+    if (cuts_out) *cuts_out = (int32_t)C;
+    return (int32_t)W;
+}
+
+extern "C" int64_t sylber_ivf_workspace_bytes(int32_t n, int32_t nprobe, int32_t k, int32_t cuts) {
+    if (n < 1 || nprobe < 1 || nprobe > KN_KMAX || k < 1 || k > KN_KMAX || cuts < 1) return -1;
+    const int64_t M = (int64_t)nprobe * cuts, M2 = (M + 1) / 2;
+    // ||q||^2 [n] | scores [n][M][k] | ids [n][M][k] | scores [n][ceil(M/2)][k] | ids [n][ceil(M/2)][k]
+    return kn_al((int64_t)n * 4) + 2 * kn_al((int64_t)n * M * k * 4) + 2 * kn_al((int64_t)n * M2 * k * 4);
+}
+
+extern "C" int sylber_ivf_search(const float* q_dev, int32_t n, int32_t D, int32_t nprobe, const int32_t* pair_dev,
+                                 const int32_t* items_dev, int32_t n_items, int32_t cuts, const float* rows_dev,
+                                 const int32_t* row_id_dev, const float* row_norm_dev, int32_t metric, int32_t k,
+                                 const int32_t* q_group_dev, const int32_t* row_group_dev, float* score_dev, int64_t* idx_dev,
+                                 void* workspace_dev, void* stream) {
+    static const char* what = "sylber_ivf_search";
+    hipStream_t s = (hipStream_t)stream;
+    if (!q_dev || !pair_dev || !items_dev || !rows_dev || !row_id_dev || !score_dev || !idx_dev || !workspace_dev) {
+        syl_set_error(what, "null argument"); return 1;
+    }
+    if (n < 1 || n_items < 1 || D < 16 || D % 16) { syl_set_error(what, "need n, n_items >= 1 and D a multiple of 16"); return 1; }
+    if (nprobe < 1 || nprobe > KN_KMAX || cuts < 1 || cuts > IV_MAX_CUTS) { syl_set_error(what, "need 1 <= nprobe <= 128 and 1 <= cuts <= 16"); return 1; }
+    if ((int64_t)n * nprobe * cuts > INT32_MAX / 2) { syl_set_error(what, "n x nprobe x cuts is too large: use smaller query chunks"); return 1; }
+    if (k < 1 || k > KN_KMAX) { syl_set_error(what, "need 1 <= k <= 128"); return 1; }
+    if (metric != SYLBER_KNN_L2 && metric != SYLBER_KNN_IP) { syl_set_error(what, "unknown metric"); return 1; }
+    if (metric == SYLBER_KNN_L2 && !row_norm_dev) { syl_set_error(what, "the L2 metric needs row_norm_dev"); return 1; }
+    if (!q_group_dev != !row_group_dev) { syl_set_error(what, "q_group_dev and row_group_dev go together"); return 1; }
+    const int64_t M = (int64_t)nprobe * cuts, M2 = (M + 1) / 2;
+    char* w = (char*)workspace_dev;
+    float* qsq = (float*)w;
+    w += kn_al((int64_t)n * 4);
+    float* s0 = (float*)w; w += kn_al((int64_t)n * M * k * 4);
+    int32_t* i0 = (int32_t*)w; w += kn_al((int64_t)n * M * k * 4);
+    float* s1 = (float*)w; w += kn_al((int64_t)n * M2 * k * 4);
+    int32_t* i1 = (int32_t*)w;
+    if (metric == SYLBER_KNN_L2 && launch_km_sqnorm(q_dev, qsq, n, D, s)) return 1;
+    static PerDeviceOnce once;
+    if (once.need()) HIP_TRY(hipFuncSetAttribute((const void*)ivf_scan_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)iv_lds_bytes(KN_KMAX)));
+    hipLaunchKernelGGL(ivf_scan_kernel, dim3((unsigned)n_items), dim3(256), iv_lds_bytes(k), s, q_dev, items_dev, pair_dev, nprobe, rows_dev, D,
+                       row_id_dev, metric == SYLBER_KNN_L2 ? row_norm_dev : nullptr, k, q_group_dev, row_group_dev, cuts, s0, i0);
+    HIP_TRY(hipGetLastError());
+    float* cs = s0; int32_t* ci = i0;
+    float* os = s1; int32_t* oi = i1;
+    for (int m = (int)M; m > 1; m = (m + 1) / 2) {
         hipLaunchKernelGGL(knn_merge_kernel, dim3((unsigned)n, (unsigned)((m + 1) / 2)), dim3(64), 0, s, cs, ci, m, k, os, oi);
         HIP_TRY(hipGetLastError());
         float* ts = cs; cs = os; os = ts;

@@ -13,6 +13,7 @@ Contract (tests/knn_ref.py restates it in numpy)::
 """
 from __future__ import annotations
 
+import ctypes
 from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -24,6 +25,7 @@ from .kmeans import _device, _stream, _vp
 METRICS = {"l2": 0, "cosine": 1}        # SYLBER_KNN_L2, SYLBER_KNN_IP (cosine = inner product on unit rows)
 MAX_K = 128
 DEFAULT_QUERY_CHUNK = 8192
+MAX_NPROBE = 128
 
 
 def _rows(a, what: str) -> torch.Tensor:
@@ -238,3 +240,223 @@ class SyllableIndex:
         self.dim, self._x, self._c = D, xd, c
         self._g = torch.from_numpy(np.ascontiguousarray(g, np.int32)).to(self.device)
         self._prov = np.asarray(prov, np.float64).reshape(m, 4)
+
+
+class IVFSyllableIndex:
+    """An inverted file over a ``SyllableIndex``: the rows are clustered into ``nlist`` lists once (``fit_kmeans``), and a search scans,
+    per query, only the ``nprobe`` lists whose centroids are nearest (csrc/knn.hip, ``sylber_ivf_search``).  The result is the exact
+    search's restricted to the rows of the probed lists, bit for bit (tests/ivf_ref.py restates the composition)::
+
+        list of row j      = sylber_kmeans_assign(rows, centroids)[j]      (squared L2 for both metrics; unit rows for "cosine";
+                                                                            a row with NaN is in no list)
+        lists of query i   = the ids of SyllableIndex(centroids, metric="l2").search(q_i, nprobe)
+        result of query i  = SyllableIndex.search's order (s, original id), reported values, exclusion and padding over those rows
+
+    Build one with ``IVFSyllableIndex.build``.  ``ivf.index`` is the source ``SyllableIndex`` (rows in id order; ``add`` appends to
+    it); the lists hold a second copy of the rows, laid out list by list."""
+
+    def __init__(self, index: SyllableIndex, centroids: torch.Tensor, labels: torch.Tensor):
+        self.index = index
+        self.centroids = centroids
+        self._coarse = SyllableIndex(centroids, metric="l2", device=index.device)
+        self._labels = labels                   # [N] int32 on the device, -1 = in no list
+        self.last_search = None
+        self._layout()
+
+    # ---- building -------------------------------------------------------------------------------------------------------------------
+    @classmethod
+    def build(cls, source, nlist: Optional[int] = None, *, centroids=None, seed: int = 0, max_iter: int = 25,
+              train_rows: Optional[int] = None, tol: float = 1e-4, groups=None, metric: str = "l2", device="cuda") -> "IVFSyllableIndex":
+        """``source``: a ``SyllableIndex`` (kept as ``ivf.index``, not copied) or ``[N, D]`` features (then ``groups``, ``metric`` and
+        ``device`` make the index).  The centroids are ``fit_kmeans(rows, nlist, seed=, max_iter=, tol=, init_rows=train_rows)`` on the
+        stored rows, or ``centroids [nlist, D]`` as given (finite).  ``ValueError`` for ``nlist < 1``, ``nlist > N`` or an empty index."""
+        from .kmeans import fit_kmeans
+        index = source if isinstance(source, SyllableIndex) else SyllableIndex(source, metric=metric, groups=groups, device=device)
+        N = len(index)
+        if N == 0:
+            raise ValueError("the index is empty")
+        if centroids is None:
+            if nlist is None or isinstance(nlist, bool) or int(nlist) != nlist or nlist < 1:
+                raise ValueError("nlist must be an integer >= 1, got %r" % (nlist,))
+            if nlist > N:
+                raise ValueError("nlist = %d > %d rows" % (nlist, N))
+            C = fit_kmeans(index._x, int(nlist), seed=seed, max_iter=max_iter, tol=tol, init_rows=train_rows, device=index.device).centroids
+        else:
+            c = _rows(centroids, "centroids")
+            if nlist is not None and c.shape[0] != nlist:
+                raise ValueError("centroids has %d rows, nlist = %r" % (c.shape[0], nlist))
+            if c.shape[0] < 1 or c.shape[0] > N:
+                raise ValueError("nlist = %d must be in [1, %d rows]" % (c.shape[0], N))
+            if c.shape[1] != index.dim:
+                raise ValueError("centroids: expected D = %d, got %d" % (index.dim, c.shape[1]))
+            C = c.to(index.device, torch.float32).contiguous().clone()
+            if not bool(torch.isfinite(C).all()):
+                raise ValueError("centroids hold non-finite values")
+        return cls(index, C, cls._assign(index._x, C))
+
+    @staticmethod
+    def _assign(x: torch.Tensor, C: torch.Tensor) -> torch.Tensor:
+        from .kmeans import assign
+        lab = assign(x, C)[0]
+        return torch.where((lab >= 0) & (lab < C.shape[0]), lab, torch.full_like(lab, -1))      # a NaN row has no nearest centroid
+
+    def _layout(self) -> None:
+        """the counting sort of the rows into lists (plumbing): positions, offsets and the list-ordered copies"""
+        idx, nlist = self.index, self.nlist
+        key = torch.where(self._labels < 0, torch.full_like(self._labels, nlist), self._labels).to(torch.int64)
+        order = torch.sort(key, stable=True).indices                    # by list, ascending id within a list; unlisted rows last
+        sizes = torch.bincount(key, minlength=nlist + 1)[:nlist]
+        order = order[:int(sizes.sum())]
+        self.list_sizes = sizes
+        off = np.zeros(nlist + 2, np.int64)
+        off[1:nlist + 1] = np.cumsum(sizes.cpu().numpy())
+        off[nlist + 1] = off[nlist]                                      # a virtual empty list for probe slots without a list
+        self._off_host = off.astype(np.int32)
+        self._rid = order.to(torch.int32)
+        self._rows = idx._x.index_select(0, order)
+        self._rc = idx._c.index_select(0, order) if idx._c is not None else None
+        self._rg = idx._g.index_select(0, order)
+        self._sizes_host = np.diff(off[:nlist + 1])
+
+    def add(self, features, groups=None) -> range:
+        """append rows to ``ivf.index``, assign them to the existing centroids (no retraining) and re-lay the lists out; the result
+        equals ``build`` from all the rows with ``centroids=`` these"""
+        ids = self.index.add(features, groups=groups)
+        if len(ids):
+            self._labels = torch.cat([self._labels, self._assign(self.index._x[ids.start:ids.stop], self.centroids)])
+            self._layout()
+        return ids
+
+    # ---- views ----------------------------------------------------------------------------------------------------------------------
+    def __len__(self) -> int:
+        return len(self.index)
+
+    @property
+    def nlist(self) -> int:
+        return int(self.centroids.shape[0])
+
+    @property
+    def metric(self) -> str:
+        return self.index.metric
+
+    @property
+    def labels(self) -> torch.Tensor:
+        """``[N]`` int64: the list of every row (-1 for a row in no list)"""
+        return self._labels.to(torch.int64)
+
+    def list_ids(self, l: int) -> torch.Tensor:
+        """the row ids of list ``l``, ascending"""
+        return self._rid[int(self._off_host[l]):int(self._off_host[l + 1])].to(torch.int64)
+
+    def provenance(self, ids):
+        return self.index.provenance(ids)
+
+    # ---- search ---------------------------------------------------------------------------------------------------------------------
+    def probe(self, queries, nprobe: int) -> torch.Tensor:
+        """``[n, nprobe]`` int64: the lists a search of these queries scans, nearest centroid first (-1 where a query is NaN)"""
+        self._check_nprobe(nprobe)
+        q = _rows(queries, "queries")
+        if q.shape[1] != self.index.dim:
+            raise ValueError("queries: expected D = %d, got %d" % (self.index.dim, q.shape[1]))
+        return self._coarse.search(self.index._prep(q), int(nprobe))[1]
+
+    def _check_nprobe(self, nprobe) -> None:
+        hi = min(self.nlist, MAX_NPROBE)
+        if isinstance(nprobe, bool) or int(nprobe) != nprobe or not 1 <= int(nprobe) <= hi:
+            raise ValueError("nprobe must be an integer in [1, min(nlist, %d) = %d], got %r" % (MAX_NPROBE, hi, nprobe))
+
+    def search(self, queries, k: int, nprobe: int, *, groups=None, exclude_same_group: bool = False,
+               query_chunk: int = DEFAULT_QUERY_CHUNK, item_tiles: int = 0, _workspace_fill=None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """as ``SyllableIndex.search`` over the rows of each query's ``nprobe`` nearest lists -> ``(scores fp32 [n, k], ids int64
+        [n, k])`` on the device, ids those of ``ivf.index``.  ``query_chunk`` bounds the workspace and the pair tables;
+        ``item_tiles`` (0 = automatic) is a test hook that cuts lists into work items of that many 128-row tiles.  Neither changes
+        the result.  ``ivf.last_search`` = ``{"pairs", "fraction", "items", "workspace_bytes"}`` of the call."""
+        idx = self.index
+        if isinstance(k, bool) or int(k) != k or not 1 <= int(k) <= MAX_K:
+            raise ValueError("k must be an integer in [1, %d], got %r" % (MAX_K, k))
+        k = int(k)
+        self._check_nprobe(nprobe)
+        nprobe = int(nprobe)
+        if len(idx) == 0:
+            raise ValueError("the index is empty")
+        q = _rows(queries, "queries")
+        n, D = q.shape
+        if D != idx.dim:
+            raise ValueError("queries: expected D = %d, got %d" % (idx.dim, D))
+        qg = None
+        if exclude_same_group:
+            if groups is None:
+                raise ValueError("exclude_same_group needs the queries' groups")
+            qg = torch.from_numpy(_groups(groups, n, "groups")).to(idx.device)
+        elif groups is not None:
+            _groups(groups, n, "groups")
+        if int(item_tiles) < 0 or int(query_chunk) < 1:
+            raise ValueError("item_tiles must be >= 0 and query_chunk >= 1")
+        dev = idx.device
+        scores = torch.empty((n, k), dtype=torch.float32, device=dev)
+        ids = torch.empty((n, k), dtype=torch.int64, device=dev)
+        self.last_search = {"pairs": 0, "fraction": 0.0, "items": 0, "workspace_bytes": 0}
+        if n == 0:
+            return scores, ids
+        lib = _lib.load()
+        qd = idx._prep(q)
+        nlist = self.nlist
+        step = min(n, int(query_chunk), max(1, 2 ** 25 // nprobe))     # n x nprobe x cuts (<= 16) stays below 2^30
+        metric = METRICS[idx.metric]
+        i32p = ctypes.POINTER(ctypes.c_int32)
+        off_p = self._off_host.ctypes.data_as(i32p)
+        pairs_scanned = 0
+        with torch.cuda.device(dev):
+            for r0 in range(0, n, step):
+                m = min(step, n - r0)
+                qc = qd[r0:r0 + m]
+                # the coarse step and the grouping of the (query, slot) pairs by list: plumbing
+                probe = self._coarse.search(qc, nprobe)[1].reshape(-1)
+                key = torch.where(probe < 0, torch.full_like(probe, nlist), probe)
+                pair = torch.sort(key, stable=True).indices.to(torch.int32)
+                counts = np.ascontiguousarray(torch.bincount(key, minlength=nlist + 1).cpu().numpy().astype(np.int32))
+                cnt_p = counts.ctypes.data_as(i32p)
+                cuts = ctypes.c_int32(0)
+                W = int(lib.sylber_ivf_work_items(cnt_p, off_p, nlist + 1, int(item_tiles), None, 0, ctypes.byref(cuts)))
+                items = np.empty((max(W, 1), 8), np.int32)
+                if W < 1 or int(lib.sylber_ivf_work_items(cnt_p, off_p, nlist + 1, int(item_tiles), items.ctypes.data_as(i32p), W,
+                                                          ctypes.byref(cuts))) != W:
+                    raise _lib.SylberHipError("sylber_ivf_work_items failed")
+                items_d = torch.from_numpy(items).to(dev)
+                nbytes = int(lib.sylber_ivf_workspace_bytes(m, nprobe, k, cuts.value))
+                ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+                if _workspace_fill is not None:
+                    ws.fill_(_workspace_fill)
+                _lib.check(lib.sylber_ivf_search(_vp(qc), m, D, nprobe, _vp(pair), _vp(items_d), W, cuts.value, _vp(self._rows), _vp(self._rid),
+                                                 _vp(self._rc), metric, k, _vp(qg[r0:r0 + m] if qg is not None else None),
+                                                 _vp(self._rg if qg is not None else None), _vp(scores[r0:r0 + m]), _vp(ids[r0:r0 + m]),
+                                                 _vp(ws), _stream(dev)), "sylber_ivf_search")
+                pairs_scanned += int((counts[:nlist].astype(np.int64) * self._sizes_host).sum())
+                self.last_search["items"] += W
+                self.last_search["workspace_bytes"] = max(self.last_search["workspace_bytes"], nbytes + pair.numel() * 4 + items.nbytes)
+        self.last_search["pairs"] = pairs_scanned
+        self.last_search["fraction"] = pairs_scanned / (float(n) * len(idx))
+        return scores, ids
+
+    # ---- persistence ----------------------------------------------------------------------------------------------------------------
+    def save(self, path: str) -> None:
+        """``.npz``: the source index's rows, groups, provenance and metric, the centroids and every row's list.  Loading neither
+        retrains nor reassigns, so a round trip searches bit for bit the same."""
+        i = self.index
+        np.savez(path, metric=np.array(i.metric), features=i._x.cpu().numpy(), groups=i._g.cpu().numpy(), provenance=i._prov,
+                 span_int=np.array(i._span_dtype is np.int64), centroids=self.centroids.cpu().numpy(), labels=self._labels.cpu().numpy())
+
+    @classmethod
+    def load(cls, path: str, device="cuda") -> "IVFSyllableIndex":
+        z = np.load(path, allow_pickle=False)
+        if "centroids" not in z.files or "labels" not in z.files:
+            raise ValueError("%s is not a saved IVFSyllableIndex" % path)
+        idx = SyllableIndex(metric=str(z["metric"]), device=device)
+        idx._load_rows(z["features"], z["groups"], z["provenance"])
+        if bool(z["span_int"]):
+            idx._span_dtype = np.int64
+        C = torch.from_numpy(np.ascontiguousarray(z["centroids"], np.float32)).to(idx.device)
+        labels = torch.from_numpy(np.ascontiguousarray(z["labels"], np.int32)).to(idx.device)
+        if labels.shape != (len(idx),) or C.dim() != 2 or C.shape[1] != idx.dim:
+            raise ValueError("%s: centroids / labels do not match the rows" % path)
+        return cls(idx, C, labels)
