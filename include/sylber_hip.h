@@ -265,6 +265,52 @@ int sylber_ivf_search(const float* q_dev, int32_t n, int32_t D, int32_t nprobe, 
                       int32_t metric, int32_t k, const int32_t* q_group_dev, const int32_t* row_group_dev, float* score_dev,
                       int64_t* idx_dev, void* workspace_dev, void* stream);
 
+/* Phrase search (sylber_amd/search.py: SyllableIndex.search_phrases): query-by-example subsequence DTW of syllable sequences
+ * (phrases, 1 <= m <= 64 rows) against every sequence of the database (runs of consecutive rows, at most 65 536 rows each).
+ * Local cost of phrase row i against database row j, in fp32, from the score s = fmaf(-2, q_i . x_j, c_j) of sylber_knn_search
+ * (same contraction, same bits):
+ *   SYLBER_KNN_L2: d = max(0, ||q_i||^2 + s) with ||q_i||^2 as sylber_knn_row_norms, i.e. exactly the score sylber_knn_search reports;
+ *   SYLBER_KNN_IP (cosine: phrase rows made unit rows as for sylber_knn_search): d = max(0, 1 - (-s / 2)) (the halving is exact, the
+ *   subtraction rounds once);  a NaN d (a NaN row on either side) counts as +inf.
+ * Subsequence DTW of a phrase of m rows against a sequence with columns j = 0 .. L - 1 (the phrase is consumed whole, its span in the
+ * sequence is free), all additions in fp32, one per cell:
+ *   A[0][j] = d[0][j]                                   start[0][j] = j
+ *   A[i][j] = d[i][j] + min(A[i-1][j-1], A[i-1][j], A[i][j-1])      (terms outside the sequence are +inf)
+ *             on equal values the predecessor is taken in that order: diagonal, then (i-1, j), then (i, j-1);
+ *             start[i][j] = start of the predecessor taken
+ *   cost = min_j A[m-1][j], the smallest such j on ties = end;   span = (row of start[m-1][end], row of end + 1)
+ * A sequence whose cost is +inf is never returned.  Each phrase's list is ordered by (cost, sequence number) ascending, the strict
+ * order sylber_knn_search uses; lists with fewer than k admissible sequences end in cost +inf, sequence -1, span (-1, -1).  Because
+ * fp32 + and min in a fixed cell order are deterministic, the result is unique: it does not depend on the split of the database, the
+ * packing or chunking of phrases, stale workspace contents, or whether the index came from one add or many.  m > L is legal
+ * (vertical steps).  No normalisation by path length.
+ * sylber_dtw_plan (host only, no GPU): seq_offsets_host [n_seq + 1] (first 0, ascending, last N: sequence s = rows offsets[s] ..
+ *   offsets[s + 1]), phrase_len_host [n_phrases].  Packs the phrases, in order, into query blocks of 128 rows -- a phrase lies inside
+ *   one 64-row half of one block; a block holds at most min(128, 4096 / k) phrases, fewer with block_phrases > 0 -- and cuts the
+ *   database at sequence starts only: cut c begins at the first sequence start at or after row c N / C' (C' = splits, or automatic
+ *   with splits = 0: enough workgroups to cover the chip, about 4 tiles of 128 rows or more each; at most 65 535), equal boundaries
+ *   collapsing.  Returns the number of cuts C; writes cut_rows_host [C + 1] (cut c = rows cut_rows[c] .. cut_rows[c + 1]; needs
+ *   cut_capacity >= C + 1) and phrase_row_host [n_phrases] (block * 128 + first row in the block) where non-null, *blocks_out and
+ *   *block_phrases_out (the cap used).  Errors: -1 bad argument or capacity, -2 a phrase length outside [1, 64], -3 a sequence
+ *   longer than 65 536 rows, -4 malformed offsets.
+ * sylber_dtw_search: q_dev [n_blocks * 128, D] the phrase rows as packed by the plan (padding rows zero; unit rows for cosine);
+ *   row_meta_dev [n_blocks * 128] int32: -1 for padding, else (row within its phrase) | (last row of its phrase) << 7 | (slot of its
+ *   phrase in the block) << 8; slot_phrase_dev [n_blocks * 128]: the phrase number of each slot of each block, -1 behind the last;
+ *   block_rows_dev [n_blocks]: rows in use; block_phrases: the largest number of slots of any block.  seq_id_dev [N]: the sequence
+ *   of every row; cut_rows_dev [cuts + 1].  With phrase_group_dev [n_phrases] and seq_group_dev [n_seq] (both or neither) a sequence
+ *   whose group equals the phrase's is skipped.  cost_dev [n_phrases, k] fp32, seq_dev [n_phrases, k] int64, span_dev
+ *   [n_phrases, k, 2] int64 (first row, one past the last row).  At most one match per sequence: its best one.  workspace_dev:
+ *   sylber_dtw_workspace_bytes(n_blocks, n_phrases, k, cuts) bytes, O(P C k); no [rows, N] buffer. */
+int32_t sylber_dtw_plan(const int32_t* seq_offsets_host, int32_t n_seq, const int32_t* phrase_len_host, int32_t n_phrases, int32_t k,
+                        int32_t splits, int32_t block_phrases, int32_t* cut_rows_host, int32_t cut_capacity, int32_t* phrase_row_host,
+                        int32_t* blocks_out, int32_t* block_phrases_out);
+int64_t sylber_dtw_workspace_bytes(int32_t n_blocks, int32_t n_phrases, int32_t k, int32_t cuts);
+int sylber_dtw_search(const float* q_dev, int32_t n_blocks, const int32_t* row_meta_dev, const int32_t* slot_phrase_dev,
+                      const int32_t* block_rows_dev, int32_t n_phrases, int32_t block_phrases, const float* db_dev, int32_t N, int32_t D,
+                      const float* db_norm_dev, int32_t metric, int32_t k, const int32_t* seq_id_dev, const int32_t* cut_rows_dev,
+                      int32_t cuts, const int32_t* phrase_group_dev, const int32_t* seq_group_dev, float* cost_dev, int64_t* seq_dev,
+                      int64_t* span_dev, void* workspace_dev, void* stream);
+
 /* Learned quantizer (sylber/model/quantizer.py:6-77, 182-257: `load_quantizer` / `Quantizer`), eval, exact fp32.  The host
  * (sylber_amd/quantizer.py) chains: sylber_lq_norm (input norm / padding) -> sylber_ffenc -> sylber_lq_norm (output norm, blank rows)
  * -> sylber_rvq_assign for the art window and the pitch window -> sylber_lq_norm of the quantized rows.  All data pointers are device

@@ -10,46 +10,14 @@
 // hence not on the split count, the launch geometry or the query chunking.  A NaN score never passes km_better and never enters.
 #include "kernels.h"
 #include "../../include/sylber_hip.h"
-#include <climits>
+#include "knn_tile.h"
 
-// contraction geometry of km_fused_assign_kernel: 128 query rows x 128 database rows per tile, K step 16, LDS rows [0 2 .. 14 | 1 3 .. 15]
-constexpr int KN_BM = 128, KN_BN = 128, KN_BK = 16, KN_LD = 20;
-constexpr int KN_STRIP = 32, KN_SP = 132;                 // epilogue strip: 32 query rows x 128 scores, row stride 132 floats
-constexpr int KN_STAGE = 2 * KN_BM * KN_LD;               // floats of the operand staging; the strip (32 x 132) aliases it
-constexpr int KN_KMAX = 128;
+// contraction geometry, kn_better, kn_stage / kn_mma (one K step) and kn_insert: knn_tile.h, shared with dtw.hip
+constexpr int KN_STRIP = 32, KN_SP = 132;                 // epilogue strip: 32 query rows x 128 scores, row stride 132 floats; aliases the staging
 constexpr int KN_TARGET_BLOCKS = 512;                     // automatic splits: (query blocks) x S >= 2 workgroups per CU
 constexpr int KN_MIN_TILES = 4;                           // ... but no split shorter than 4 database tiles
 
-__device__ __forceinline__ bool kn_better(float v, int i, float bv, int bi) { return v < bv || (v == bv && i < bi); }   // km_better
-
 static size_t kn_lds_bytes(int k) { return (size_t)(KN_STAGE + 2 * KN_BN + 4) * 4 + (size_t)KN_BM * k * 8; }
-
-// one wave inserts candidate (v, j) into the sorted list (ls, li)[0..k) if it is better than the k-th entry
-__device__ __forceinline__ void kn_insert(float* ls, int* li, int k, int lane, float v, int j) {
-    if (!kn_better(v, j, ls[k - 1], li[k - 1])) return;
-    // position = entries better than (v, j)
-    int p = 0;
-#pragma unroll
-    for (int h = 0; h < KN_KMAX / 64; ++h) {
-        const int q = lane + 64 * h;
-        const bool b = q < k && kn_better(ls[q], li[q], v, j);
-        p += __popcll(__ballot(b));
-    }
-    // shift [p, k - 1) up by one: all reads, then all writes (a wave's LDS operations complete in order)
-    float sv[KN_KMAX / 64];
-    int si[KN_KMAX / 64];
-#pragma unroll
-    for (int h = 0; h < KN_KMAX / 64; ++h) {
-        const int q = lane + 64 * h;
-        if (q >= p && q < k - 1) { sv[h] = ls[q]; si[h] = li[q]; }
-    }
-#pragma unroll
-    for (int h = 0; h < KN_KMAX / 64; ++h) {
-        const int q = lane + 64 * h;
-        if (q >= p && q < k - 1) { ls[q + 1] = sv[h]; li[q + 1] = si[h]; }
-    }
-    if (lane == 0) { ls[p] = v; li[p] = j; }
-}
 
 // grid (ceil(n / 128), S).  Split sp walks database tiles [sp * tiles / S, (sp + 1) * tiles / S).  cn: ||x_j||^2 (L2) or null (inner
 // product: c_j = 0).  Writes the sorted top-k of each valid query row over its tiles to ps / pi [n][S][k]; entries that did not fill
@@ -98,19 +66,9 @@ __global__ __launch_bounds__(256) void knn_search_kernel(const float* __restrict
     if (T > 0) fetch(0);
     for (int t = 0; t < T; ++t) {
         const int tile = tlo + t / ksteps, ks = t % ksteps, n0 = tile * KN_BN;
-        if (ks == 0) {
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int j = 0; j < 2; ++j)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-        }
+        if (ks == 0) kn_zero(acc);
         __syncthreads();                                   // previous fragments, strip, cns / cgs and flags are all read
-        *(float4*)xdst = make_float4(xa.x, xa.z, xb.x, xb.z);
-        *(float4*)(xdst + 8) = make_float4(xa.y, xa.w, xb.y, xb.w);
-        *(float4*)cdst = make_float4(ca.x, ca.z, cb.x, cb.z);
-        *(float4*)(cdst + 8) = make_float4(ca.y, ca.w, cb.y, cb.w);
+        kn_stage(xdst, cdst, xa, xb, ca, cb);
         if (ks == 0 && tid < KN_BN) {
             const int j = n0 + tid;
             cns[tid] = (cn && j < N) ? cn[j] : 0.f;
@@ -119,21 +77,7 @@ __global__ __launch_bounds__(256) void knn_search_kernel(const float* __restrict
         }
         __syncthreads();
         if (t + 1 < T) fetch(t + 1);
-        f32x4_t xf[2][2], cf[2][2];
-#pragma unroll
-        for (int f = 0; f < 2; ++f) {
-            const float* xp = xs + (wm * 64 + f * 32 + frow) * KN_LD + fh * 8;
-            const float* cp = cs + (wn * 64 + f * 32 + frow) * KN_LD + fh * 8;
-            xf[f][0] = *(const f32x4_t*)xp; xf[f][1] = *(const f32x4_t*)(xp + 4);
-            cf[f][0] = *(const f32x4_t*)cp; cf[f][1] = *(const f32x4_t*)(cp + 4);
-        }
-#pragma unroll
-        for (int i = 0; i < 8; ++i)
-#pragma unroll
-            for (int fm = 0; fm < 2; ++fm)
-#pragma unroll
-                for (int fn = 0; fn < 2; ++fn)
-                    acc[fm][fn] = __builtin_amdgcn_mfma_f32_32x32x2f32(cf[fn][i >> 2][i & 3], xf[fm][i >> 2][i & 3], acc[fm][fn], 0, 0, 0);
+        kn_mma(xs, cs, wm, wn, frow, fh, acc, true, true);
         if (ks != ksteps - 1) continue;
         // epilogue: lane holds query row wm*64 + fm*32 + frow against database rows n0 + wn*64 + fn*32 + 8g + 4fh + e.  Scores become
         // s = fmaf(-2, dot, c_j); inadmissible ones (past N, same group, past n) become NaN.  Test against the row's k-th entry.
@@ -328,19 +272,9 @@ __global__ __launch_bounds__(256) void ivf_scan_kernel(const float* __restrict__
     if (T > 0) fetch(0);
     for (int t = 0; t < T; ++t) {
         const int tile = t / ksteps, ks = t % ksteps, n0 = rlo + tile * KN_BN;
-        if (ks == 0) {
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int j = 0; j < 2; ++j)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-        }
+        if (ks == 0) kn_zero(acc);
         __syncthreads();
-        *(float4*)xdst = make_float4(xa.x, xa.z, xb.x, xb.z);
-        *(float4*)(xdst + 8) = make_float4(xa.y, xa.w, xb.y, xb.w);
-        *(float4*)cdst = make_float4(ca.x, ca.z, cb.x, cb.z);
-        *(float4*)(cdst + 8) = make_float4(ca.y, ca.w, cb.y, cb.w);
+        kn_stage(xdst, cdst, xa, xb, ca, cb);
         if (ks == 0 && tid < KN_BN) {
             const int j = n0 + tid;
             cns[tid] = (cn && j < rhi) ? cn[j] : 0.f;
@@ -350,24 +284,8 @@ __global__ __launch_bounds__(256) void ivf_scan_kernel(const float* __restrict__
         }
         __syncthreads();
         if (t + 1 < T) fetch(t + 1);
-        f32x4_t xf[2][2], cf[2][2];
-#pragma unroll
-        for (int f = 0; f < 2; ++f) {
-            const float* xp = xs + (wm * 64 + f * 32 + frow) * KN_LD + fh * 8;
-            const float* cp = cs + (wn * 64 + f * 32 + frow) * KN_LD + fh * 8;
-            xf[f][0] = *(const f32x4_t*)xp; xf[f][1] = *(const f32x4_t*)(xp + 4);
-            cf[f][0] = *(const f32x4_t*)cp; cf[f][1] = *(const f32x4_t*)(cp + 4);
-        }
         // a half without pairs skips its MFMAs: its scores are masked below whatever they are
-#pragma unroll
-        for (int fm = 0; fm < 2; ++fm) {
-            if (!live[fm]) continue;
-#pragma unroll
-            for (int i = 0; i < 8; ++i)
-#pragma unroll
-                for (int fn = 0; fn < 2; ++fn)
-                    acc[fm][fn] = __builtin_amdgcn_mfma_f32_32x32x2f32(cf[fn][i >> 2][i & 3], xf[fm][i >> 2][i & 3], acc[fm][fn], 0, 0, 0);
-        }
+        kn_mma(xs, cs, wm, wn, frow, fh, acc, live[0], live[1]);
         if (ks != ksteps - 1) continue;
         bool pass[2] = {false, false};
 #pragma unroll

@@ -10,6 +10,10 @@ Contract (tests/knn_ref.py restates it in numpy)::
     each list ordered by (s, j) ascending: the better score first, then the smaller id; NaN scores never returned;
     with exclude_same_group, candidates whose group equals the query's are skipped;
     rows with fewer than k admissible candidates are padded with id -1 and score +inf.
+
+``SyllableIndex.search_phrases`` searches for a *sequence* of syllables: subsequence DTW of each phrase against every sequence (by
+default: clip) of the index, in the epilogue of the same contraction (csrc/dtw.hip, ``sylber_dtw_search``); its contract is in the
+method's docstring, restated in numpy in tests/dtw_ref.py.
 """
 from __future__ import annotations
 
@@ -26,6 +30,9 @@ METRICS = {"l2": 0, "cosine": 1}        # SYLBER_KNN_L2, SYLBER_KNN_IP (cosine =
 MAX_K = 128
 DEFAULT_QUERY_CHUNK = 8192
 MAX_NPROBE = 128
+MAX_PHRASE_ROWS = 64            # DT_MAX_M of csrc/dtw.hip: one wave holds a phrase
+MAX_SEQUENCE_ROWS = 65536       # DT_MAX_SEQ: the DP along one sequence is serial
+DEFAULT_PHRASE_CHUNK = 4096
 
 
 def _rows(a, what: str) -> torch.Tensor:
@@ -70,6 +77,7 @@ class SyllableIndex:
         self._g = None              # [N] int32 groups on the device
         self._prov = None           # [N, 4] int64/float provenance (clip, segment, start, end), or None
         self._span_dtype = np.float64
+        self._seq_cache = None      # (N, default sequence offsets)
         if features is not None:
             self.add(features, groups=groups)
 
@@ -206,6 +214,170 @@ class SyllableIndex:
                                                  int(splits), _vp(scores[r0:r0 + m]), _vp(ids[r0:r0 + m]), _vp(ws), _stream(self.device)),
                            "sylber_knn_search")
         return scores, ids
+
+    # ---- phrase search --------------------------------------------------------------------------------------------------------------
+    def sequence_offsets(self) -> np.ndarray:
+        """int64 ``[S + 1]``: the default sequences of ``search_phrases``, sequence ``s`` = rows ``offsets[s] : offsets[s + 1]``: the
+        maximal runs of consecutive rows with equal group, numbered in row order (``from_outputs``: one per non-empty clip)"""
+        N = len(self)
+        if self._seq_cache is None or self._seq_cache[0] != N:
+            if N == 0:
+                off = np.zeros(1, np.int64)
+            else:
+                g = self._g.cpu().numpy()
+                off = np.concatenate([[0], np.nonzero(g[1:] != g[:-1])[0] + 1, [N]]).astype(np.int64)
+            self._seq_cache = (N, off)
+        return self._seq_cache[1].copy()
+
+    def _sequences(self, sequences) -> np.ndarray:
+        N = len(self)
+        if sequences is None:
+            off = self.sequence_offsets()
+        else:
+            a = np.asarray(sequences.detach().cpu().numpy() if torch.is_tensor(sequences) else sequences)
+            if a.ndim != 1 or a.size < 2 or a.dtype.kind not in "iu":
+                raise ValueError("sequences must be integer offsets [S + 1]")
+            off = a.astype(np.int64)
+            if off[0] != 0 or off[-1] != N or np.any(np.diff(off) < 1):
+                raise ValueError("sequences must ascend from 0 to %d rows without an empty sequence" % N)
+        longest = int(np.diff(off).max())
+        if longest > MAX_SEQUENCE_ROWS:
+            raise ValueError("a sequence has %d rows, more than %d: cut it with sequences=" % (longest, MAX_SEQUENCE_ROWS))
+        return off
+
+    def search_phrases(self, phrases, k: int, *, lengths=None, groups=None, exclude_same_group: bool = False, sequences=None,
+                       splits: int = 0, phrase_chunk: int = DEFAULT_PHRASE_CHUNK, block_phrases: int = 0,
+                       _workspace_fill=None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """query-by-example search of syllable *sequences*: the k best sequences of the index for each phrase, by subsequence DTW
+        -> ``(costs fp32 [P, k], seqs int64 [P, k], spans int64 [P, k, 2])`` on the device; a span is (first row id, one past the last
+        row id) of the match, so ``provenance`` works on it.  At most one match per sequence: its best one.  ``phrases``: a list of
+        ``[m_p, D]`` arrays / tensors (host or device), or one ``[sum m_p, D]`` array with ``lengths=[m_0, m_1, ...]``; ``1 <= m_p <= 64``.
+
+        Sequences: by default ``sequence_offsets()``; ``sequences=`` takes explicit offsets ``[S + 1]`` (ascending, first 0, last N, no
+        empty sequence; at most 65 536 rows each).  A sequence's group, for ``exclude_same_group`` (``groups [P]``), is the group of
+        its first row.
+
+        Local cost of phrase row i against database row j, in fp32, from the score ``s = fmaf(-2, q_i . x_j, c_j)`` of ``search``
+        (same contraction, same bits):
+
+        * ``"l2"``: ``d = max(0, ||q_i||^2 + s)``, i.e. exactly the score ``search`` reports;
+        * ``"cosine"``: phrase rows are made unit rows as ``search`` does; ``d = max(0, 1 - (-s / 2))`` (the halving is exact, the
+          subtraction rounds once);
+        * a NaN ``d`` (a NaN row on either side) counts as ``+inf``.
+
+        Subsequence DTW of a phrase of m rows against a sequence with columns j = 0 .. L - 1 (the phrase is consumed whole, its span
+        in the sequence is free), all additions in fp32, one per cell::
+
+            A[0][j] = d[0][j]                                   start[0][j] = j
+            A[i][j] = d[i][j] + min(A[i-1][j-1], A[i-1][j], A[i][j-1])      (terms outside the sequence are +inf)
+                      on equal values the predecessor is taken in that order: diagonal, then (i-1, j), then (i, j-1);
+                      start[i][j] = start of the predecessor taken
+            cost = min_j A[m-1][j], the smallest such j on ties = end;   span = (row of start[m-1][end], row of end + 1)
+
+        A sequence whose cost is ``+inf`` is never returned.  Each phrase's list is ordered by (cost, sequence number) ascending, the
+        strict order ``search`` uses; lists with fewer than k admissible sequences end in cost ``+inf``, sequence -1, span (-1, -1).
+        Because fp32 ``+`` and ``min`` in a fixed cell order are deterministic, the result is unique: it does not depend on the split
+        of the database, the packing or chunking of phrases, stale workspace contents, or whether the index came from one ``add`` or
+        many.  ``m > L`` is legal (vertical steps).  No normalisation by path length: divide by ``m`` if you want it.
+
+        Test hooks, none of which changes the result: ``splits`` (0 = automatic) asks for that many cuts of the database (cuts fall
+        on sequence starts only), ``phrase_chunk`` bounds the phrases per launch (and so the workspace), ``block_phrases`` (0 =
+        automatic) the phrases packed into one 128-row query block."""
+        if isinstance(k, bool) or int(k) != k or not 1 <= int(k) <= MAX_K:
+            raise ValueError("k must be an integer in [1, %d], got %r" % (MAX_K, k))
+        k = int(k)
+        N = len(self)
+        if N == 0:
+            raise ValueError("the index is empty")
+        if lengths is None:
+            if torch.is_tensor(phrases) or isinstance(phrases, np.ndarray):
+                raise ValueError("phrases given as one [sum m, D] array need lengths=")
+            parts = [_rows(p, "phrases[%d]" % i) for i, p in enumerate(phrases)]
+            lens = np.array([p.shape[0] for p in parts], np.int64)
+            for p in parts:
+                if p.shape[1] != self.dim:
+                    raise ValueError("phrases: expected D = %d, got %d" % (self.dim, p.shape[1]))
+            q = torch.cat([p.to(self.device, torch.float32) for p in parts]) if parts else torch.zeros((0, self.dim), device=self.device)
+        else:
+            q = _rows(phrases, "phrases")
+            if q.shape[1] != self.dim:
+                raise ValueError("phrases: expected D = %d, got %d" % (self.dim, q.shape[1]))
+            lens = np.asarray(lengths.detach().cpu().numpy() if torch.is_tensor(lengths) else lengths)
+            if lens.ndim != 1 or (lens.size and lens.dtype.kind not in "iu"):
+                raise ValueError("lengths must be a 1-D sequence of integers")
+            lens = lens.astype(np.int64)
+            if int(lens.sum()) != q.shape[0]:
+                raise ValueError("lengths sum to %d, phrases has %d rows" % (int(lens.sum()), q.shape[0]))
+        P = int(lens.size)
+        if P and (lens.min() < 1 or lens.max() > MAX_PHRASE_ROWS):
+            raise ValueError("a phrase has between 1 and %d rows, got lengths from %d to %d" % (MAX_PHRASE_ROWS, lens.min(), lens.max()))
+        pg = None
+        if exclude_same_group:
+            if groups is None:
+                raise ValueError("exclude_same_group needs the phrases' groups")
+            pg = _groups(groups, P, "groups")
+        elif groups is not None:
+            _groups(groups, P, "groups")
+        if int(splits) < 0 or int(phrase_chunk) < 1 or int(block_phrases) < 0:
+            raise ValueError("splits and block_phrases must be >= 0 and phrase_chunk >= 1")
+        off = self._sequences(sequences)
+        dev = self.device
+        costs = torch.empty((P, k), dtype=torch.float32, device=dev)
+        seqs = torch.empty((P, k), dtype=torch.int64, device=dev)
+        spans = torch.empty((P, k, 2), dtype=torch.int64, device=dev)
+        if P == 0:
+            return costs, seqs, spans
+        lib = _lib.load()
+        qd = self._prep(q)
+        S = off.size - 1
+        off32 = np.ascontiguousarray(off, np.int32)
+        # plumbing: the sequence of every row and (for the exclusion) the group of every sequence
+        off_d = torch.from_numpy(off).to(dev)
+        seq_id = torch.repeat_interleave(torch.arange(S, dtype=torch.int32, device=dev), off_d[1:] - off_d[:-1])
+        seq_grp = self._g.index_select(0, off_d[:-1]) if pg is not None else None
+        i32p = ctypes.POINTER(ctypes.c_int32)
+        metric = METRICS[self.metric]
+        row0 = np.concatenate([[0], np.cumsum(lens)])
+        step = int(phrase_chunk)
+        with torch.cuda.device(dev):
+            for p0 in range(0, P, step):
+                p1 = min(P, p0 + step)
+                Pc = p1 - p0
+                ln = np.ascontiguousarray(lens[p0:p1], np.int32)
+                nb, ph = ctypes.c_int32(0), ctypes.c_int32(0)
+                place = np.empty(Pc, np.int32)
+                args = (off32.ctypes.data_as(i32p), S, ln.ctypes.data_as(i32p), Pc, k, int(splits), int(block_phrases))
+                C = int(lib.sylber_dtw_plan(*args, None, 0, place.ctypes.data_as(i32p), ctypes.byref(nb), ctypes.byref(ph)))
+                cut_rows = np.empty(max(C, 1) + 1, np.int32)
+                if C < 1 or int(lib.sylber_dtw_plan(*args, cut_rows.ctypes.data_as(i32p), C + 1, None, None, None)) != C:
+                    raise _lib.SylberHipError("sylber_dtw_plan failed (%d)" % C)
+                nb = nb.value
+                # the packed layout of the chunk's rows (plumbing): where each row goes, what it is, which phrase owns each slot
+                R = int(ln.sum())
+                first = np.repeat(place.astype(np.int64), ln)
+                local = np.arange(R) - np.repeat(np.cumsum(ln) - ln, ln)
+                blk = place // 128
+                slot = np.arange(Pc) - np.searchsorted(blk, blk, side="left")
+                meta = np.full(nb * 128, -1, np.int32)
+                meta[first + local] = local | ((local == np.repeat(ln, ln) - 1).astype(np.int64) << 7) | (np.repeat(slot, ln) << 8)
+                slot_phrase = np.full(nb * 128, -1, np.int32)
+                slot_phrase[blk.astype(np.int64) * 128 + slot] = np.arange(Pc)
+                block_rows = np.zeros(nb, np.int32)
+                np.maximum.at(block_rows, blk, place % 128 + ln)
+                qp = torch.zeros((nb * 128, self.dim), dtype=torch.float32, device=dev)
+                qp[torch.from_numpy(first + local).to(dev)] = qd[int(row0[p0]):int(row0[p1])]
+                nbytes = int(lib.sylber_dtw_workspace_bytes(nb, Pc, k, C))
+                ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+                if _workspace_fill is not None:
+                    ws.fill_(_workspace_fill)
+                meta_d, sp_d, br_d = (torch.from_numpy(a).to(dev) for a in (meta, slot_phrase, block_rows))
+                cut_d = torch.from_numpy(cut_rows).to(dev)
+                pg_d = torch.from_numpy(np.ascontiguousarray(pg[p0:p1])).to(dev) if pg is not None else None
+                _lib.check(lib.sylber_dtw_search(_vp(qp), nb, _vp(meta_d), _vp(sp_d), _vp(br_d), Pc, int(slot.max()) + 1, _vp(self._x), N,
+                                                 self.dim, _vp(self._c), metric, k, _vp(seq_id), _vp(cut_d), C, _vp(pg_d), _vp(seq_grp),
+                                                 _vp(costs[p0:p1]), _vp(seqs[p0:p1]), _vp(spans[p0:p1]), _vp(ws), _stream(dev)),
+                           "sylber_dtw_search")
+        return costs, seqs, spans
 
     # ---- persistence ----------------------------------------------------------------------------------------------------------------
     def save(self, path: str) -> None:

@@ -1,0 +1,75 @@
+"""Phrase search on one MI355X (csrc/dtw.hip, ``SyllableIndex.search_phrases``), seeded random data on the device, D = 768, L2.
+
+N database rows in sequences of 20 to 60 rows; phrases of m rows, P of them so that the query rows total ``rows``; k = 10.  The
+yardstick is ``SyllableIndex.search`` of the same index with the same number of query rows in the same run: the same contraction
+without the dynamic programme.  For every (rows, m): median milliseconds of the whole call (host clock around calls that end in a
+device synchronise, after a warm-up call), the spread (min .. max) of the timed calls, TFLOP/s on 2 rows N D, and the ratio
+yardstick time / phrase-search time.  Prints one JSON line (rows also go to stderr as they finish).
+
+    python tools/phrase_bench.py [--iters 5] [--N 4194304] [--rows 128,1024,8192] [--ms 2,8,32] [--k 10]"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def timed(fn, iters):
+    fn()
+    torch.cuda.synchronize()
+    out = []
+    for _ in range(iters):
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        out.append((time.perf_counter() - t0) * 1e3)
+    return statistics.median(out), min(out), max(out)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--iters", type=int, default=5)
+    ap.add_argument("--N", type=int, default=4194304)
+    ap.add_argument("--rows", default="128,1024,8192")
+    ap.add_argument("--ms", default="2,8,32")
+    ap.add_argument("--k", type=int, default=10)
+    args = ap.parse_args()
+    from sylber_amd import SyllableIndex
+    dev = torch.device("cuda:0")
+    torch.cuda.set_device(dev)
+    g = torch.Generator(device=dev).manual_seed(0)
+    rng = np.random.default_rng(0)
+    D, N, k = 768, args.N, args.k
+    lens = rng.integers(20, 61, N // 20 + 1)
+    lens = lens[:int(np.searchsorted(np.cumsum(lens), N)) + 1]
+    lens[-1] -= int(lens.sum()) - N
+    lens = lens[lens > 0]
+    groups = np.repeat(np.arange(lens.size), lens).astype(np.int32)
+    idx = SyllableIndex(torch.randn(N, D, device=dev, generator=g), metric="l2", groups=groups, device=dev)
+    idx.sequence_offsets()
+    out = []
+    for rows in [int(v) for v in args.rows.split(",")]:
+        q = idx.features[torch.randint(0, N - rows, (1,), device=dev, generator=g).item():][:rows] + 0.5 * torch.randn(rows, D, device=dev, generator=g)
+        fl = 2.0 * rows * N * D
+        t_knn, lo, hi = timed(lambda: idx.search(q, k), args.iters)
+        base = {"rows": rows, "N": N, "sequences": int(lens.size), "k": k, "search_ms": round(t_knn, 2), "search_ms_min_max": [round(lo, 2), round(hi, 2)],
+                "search_tflops": round(fl / t_knn / 1e9, 1)}
+        for m in [int(v) for v in args.ms.split(",")]:
+            P = rows // m
+            t, lo, hi = timed(lambda: idx.search_phrases(q[:P * m], k, lengths=[m] * P), args.iters)
+            row = dict(base, m=m, phrases=P, phrase_ms=round(t, 2), phrase_ms_min_max=[round(lo, 2), round(hi, 2)],
+                       phrase_tflops=round(2.0 * P * m * N * D / t / 1e9, 1), search_over_phrase=round(t_knn / t, 3))
+            print(json.dumps(row), file=sys.stderr, flush=True)
+            out.append(row)
+    print(json.dumps({"D": D, "metric": "l2", "iters": args.iters, "rows": out}))
+
+
+if __name__ == "__main__":
+    main()
