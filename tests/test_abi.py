@@ -34,7 +34,7 @@ def test_header_symbols_are_exported(lib):
 
 def test_no_process_global_tuning_state():
     """tuning overrides are per handle (sylber_set_option) or per call: the old process-global force switches are gone"""
-    for f in ("gemm_bf16.hip", "gemm_mxfp8.hip", "attention.hip", "api.hip"):
+    for f in ("gemm_bf16.hip", "gemm_mxfp8.hip", "attention.hip", "api.hip", "forward.hip", "ops.hip", "ctx.h"):
         src = open(os.path.join(ROOT, "sylber_amd", "csrc", f)).read()
         assert "force_cfg" not in src and "g_force" not in src and "xpad_rows &" not in src, f
 
