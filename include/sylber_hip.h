@@ -242,6 +242,30 @@ int sylber_knn_search(const float* q_dev, int32_t n, const float* db_dev, int32_
                       int32_t k, const int32_t* q_group_dev, const int32_t* db_group_dev, int32_t splits, float* score_dev,
                       int64_t* idx_dev, void* workspace_dev, void* stream);
 
+/* Two-stage search (sylber_amd/search.py: SyllableIndex.search_refined): a 16-bit MFMA scan picks m candidates per query, the exact
+ * score of sylber_knn_search re-ranks them.  The result is sylber_knn_search restricted to the candidates; with m >= N it is
+ * sylber_knn_search bit for bit.
+ * sylber_knn16_pack: out16_dev [n, D] = the fp32 rows x_dev [n, D] (D % 16 == 0) rounded to nearest even to IEEE half
+ *   (SYLBER_KNN16_FP16) or bfloat16 (SYLBER_KNN16_BF16); NaN stays NaN.  fp16 saturates at +-65504, and *sat_count_dev (int32 on the
+ *   device, may be null; the caller zeroes it) grows by the number of FINITE values beyond +-65504.
+ * sylber_knn16_scan: candidates of query i = the m best database rows (1 <= m <= 128) under the strict order (t, j) of the coarse
+ *   score t(i, j) = fmaf(-2, dot16(q16_i, x16_j), c_j): dot16 the fp32-accumulated sum of the exact 16-bit products in the one
+ *   fixed order of the kernel's MFMA chain (ascending K), c_j = db_norm_dev[j] (the fp32 norms of sylber_knn_search) or 0 when
+ *   db_norm_dev is null.  NaN t and (with both group arrays) rows of the query's group are not admissible.  cand_dev [n, m] int32,
+ *   best first, padded with -1: bitwise independent of splits, of how the queries are chunked and of what the workspace held.
+ *   workspace_dev: sylber_knn16_workspace_bytes(n, N, D, m, splits) bytes; splits as sylber_knn_search.
+ * sylber_knn_rerank: for each candidate j of cand_dev [n, m] (-1 = none) the score s = fmaf(-2, q_i . x_j, c_j) with the bits of
+ *   sylber_knn_search (the ascending fmaf chain from 0); NaN s dropped; ordered by (s, j), the best k (1 <= k <= m) reported as
+ *   sylber_knn_search reports them (L2 max(0, ||q_i||^2 + s), IP -s / 2, padding idx -1 / score +inf). */
+enum { SYLBER_KNN16_FP16 = 0, SYLBER_KNN16_BF16 = 1 };
+int sylber_knn16_pack(const float* x_dev, int32_t n, int32_t D, int32_t storage, void* out16_dev, int32_t* sat_count_dev, void* stream);
+int64_t sylber_knn16_workspace_bytes(int32_t n, int32_t N, int32_t D, int32_t m, int32_t splits);
+int sylber_knn16_scan(const void* q16_dev, int32_t n, const void* db16_dev, int32_t N, int32_t D, const float* db_norm_dev,
+                      int32_t storage, int32_t m, const int32_t* q_group_dev, const int32_t* db_group_dev, int32_t splits,
+                      int32_t* cand_dev, void* workspace_dev, void* stream);
+int sylber_knn_rerank(const float* q_dev, int32_t n, const float* db_dev, int32_t N, int32_t D, const float* db_norm_dev, int32_t metric,
+                      const int32_t* cand_dev, int32_t m, int32_t k, float* score_dev, int64_t* idx_dev, void* stream);
+
 /* Inverted-file search (sylber_amd/search.py: IVFSyllableIndex): sylber_knn_search restricted, per query, to the rows of the lists it
  * probes.  The rows lie list by list in rows_dev (list l = positions list_offsets[l] .. list_offsets[l + 1], ascending original id
  * within a list); row_id_dev [N] maps a position to the row's original id, row_norm_dev / row_group_dev are in position order too.

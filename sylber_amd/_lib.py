@@ -108,6 +108,12 @@ EXPORTS = {
     "sylber_knn_unit_rows": (c_int, [c_void_p, c_int32, c_int32, c_void_p, c_void_p]),
     "sylber_knn_search": (c_int, [c_void_p, c_int32, c_void_p, c_int32, c_int32, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_int32,
                                   c_void_p, c_void_p, c_void_p, c_void_p]),
+    "sylber_knn16_pack": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
+    "sylber_knn16_workspace_bytes": (c_int64, [c_int32, c_int32, c_int32, c_int32, c_int32]),
+    "sylber_knn16_scan": (c_int, [c_void_p, c_int32, c_void_p, c_int32, c_int32, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_int32,
+                                  c_void_p, c_void_p, c_void_p]),
+    "sylber_knn_rerank": (c_int, [c_void_p, c_int32, c_void_p, c_int32, c_int32, c_void_p, c_int32, c_void_p, c_int32, c_int32, c_void_p,
+                                  c_void_p, c_void_p]),
     "sylber_ivf_work_items": (c_int32, [POINTER(c_int32), POINTER(c_int32), c_int32, c_int32, POINTER(c_int32), c_int32, POINTER(c_int32)]),
     "sylber_ivf_workspace_bytes": (c_int64, [c_int32, c_int32, c_int32, c_int32]),
     "sylber_ivf_search": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p,

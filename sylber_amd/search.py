@@ -33,6 +33,8 @@ MAX_NPROBE = 128
 MAX_PHRASE_ROWS = 64            # DT_MAX_M of csrc/dtw.hip: one wave holds a phrase
 MAX_SEQUENCE_ROWS = 65536       # DT_MAX_SEQ: the DP along one sequence is serial
 DEFAULT_PHRASE_CHUNK = 4096
+STORAGES = {"fp16": (0, torch.float16), "bf16": (1, torch.bfloat16)}     # SYLBER_KNN16_FP16 / _BF16: the planes of search_refined
+MAX_CANDIDATES = 128            # k * refine of search_refined: the LDS top-list of the scan beside a 128-row query block
 
 
 def _rows(a, what: str) -> torch.Tensor:
@@ -58,6 +60,15 @@ def _groups(g, n: int, what: str) -> np.ndarray:
     return a.astype(np.int32)
 
 
+def _chunked_workspace_bytes(size_fn, n: int, step: int, *rest) -> int:
+    """the workspace that serves every chunk of n queries taken ``step`` at a time: with automatic splits a shorter last chunk gets
+    MORE splits than a full one and can need more bytes, so the buffer is the larger of the two sizes"""
+    need = int(size_fn(step, *rest))
+    if n % step:
+        need = max(need, int(size_fn(n % step, *rest)))
+    return need
+
+
 class SyllableIndex:
     """A device-resident database of syllable embeddings with exact k-NN search.
 
@@ -78,6 +89,7 @@ class SyllableIndex:
         self._prov = None           # [N, 4] int64/float provenance (clip, segment, start, end), or None
         self._span_dtype = np.float64
         self._seq_cache = None      # (N, default sequence offsets)
+        self._planes = {}           # storage -> [N, D] 16-bit copy of _x for search_refined, built on first use
         if features is not None:
             self.add(features, groups=groups)
 
@@ -127,6 +139,9 @@ class SyllableIndex:
             with torch.cuda.device(self.device):
                 _lib.check(lib.sylber_knn_row_norms(_vp(xd), m, D, _vp(c), _stream(self.device)), "sylber_knn_row_norms")
         prov = np.full((m, 4), -1.0) if _prov is None else np.asarray(_prov, np.float64).reshape(m, 4)
+        more = {st: self._pack16(xd, st, refuse=True) for st in self._planes}      # raises before anything is appended
+        for st, h in more.items():
+            self._planes[st] = torch.cat([self._planes[st], h])
         if self._x is None:
             self.dim, self._x, self._c, self._g, self._prov = D, xd, c, gd, prov
         else:
@@ -204,7 +219,8 @@ class SyllableIndex:
         qd = self._prep(q)
         N = len(self)
         step = min(n, int(query_chunk))
-        ws = torch.empty(int(lib.sylber_knn_workspace_bytes(step, N, D, k, int(splits))), dtype=torch.uint8, device=self.device)
+        ws = torch.empty(_chunked_workspace_bytes(lib.sylber_knn_workspace_bytes, n, step, N, D, k, int(splits)), dtype=torch.uint8,
+                         device=self.device)
         metric = METRICS[self.metric]
         with torch.cuda.device(self.device):
             for r0 in range(0, n, step):
@@ -214,6 +230,102 @@ class SyllableIndex:
                                                  int(splits), _vp(scores[r0:r0 + m]), _vp(ids[r0:r0 + m]), _vp(ws), _stream(self.device)),
                            "sylber_knn_search")
         return scores, ids
+
+    # ---- two-stage search ------------------------------------------------------------------------------------------------------------
+    def _pack16(self, x: torch.Tensor, storage: str, refuse: bool) -> torch.Tensor:
+        """fp32 rows on the device -> their 16-bit rows (csrc/knn16.hip); ``refuse``: a finite value that fp16 cannot hold is an error"""
+        code, dtype = STORAGES[storage]
+        lib = _lib.load()
+        out = torch.empty(x.shape, dtype=dtype, device=self.device)
+        if x.shape[0] == 0:
+            return out
+        sat = torch.zeros(1, dtype=torch.int32, device=self.device) if refuse and storage == "fp16" else None
+        with torch.cuda.device(self.device):
+            _lib.check(lib.sylber_knn16_pack(_vp(x), x.shape[0], x.shape[1], code, _vp(out), _vp(sat), _stream(self.device)),
+                       "sylber_knn16_pack")
+        if sat is not None and int(sat.item()):
+            raise ValueError('%d stored values lie beyond +-65504, the range of storage="fp16": use storage="bf16"' % int(sat.item()))
+        return out
+
+    def half_rows(self, storage: str = "fp16") -> torch.Tensor:
+        """the ``[N, D]`` 16-bit plane of the stored rows that ``search_refined(storage=...)`` scans (``torch.float16`` or
+        ``torch.bfloat16``, round to nearest even), built on first use and extended by ``add``; ``2 N D`` bytes.  ``"fp16"`` raises
+        ``ValueError`` if a finite stored value lies beyond +-65504."""
+        if storage not in STORAGES:
+            raise ValueError("storage must be 'fp16' or 'bf16', got %r" % (storage,))
+        if len(self) == 0:
+            raise ValueError("the index is empty")
+        if storage not in self._planes:
+            self._planes[storage] = self._pack16(self._x, storage, refuse=True)
+        return self._planes[storage]
+
+    def search_refined(self, queries, k: int, refine: int = 4, storage: str = "fp16", groups=None, exclude_same_group: bool = False,
+                       splits: int = 0, query_chunk: int = DEFAULT_QUERY_CHUNK, return_candidates: bool = False):
+        """two-stage ``search``: a 16-bit MFMA scan of ``half_rows(storage)`` picks ``m = k * refine`` candidates per query, the exact
+        fp32 score re-ranks only those -> ``(scores, ids)`` shaped, typed, ordered, padded and reported exactly as ``search``'s
+        (plus ``cand`` int64 ``[n, m]`` with ``return_candidates=True``: the stage-1 ids in stage-1 order, padded with -1).
+
+        Stage 1: ``q~ = round16(q)``, ``x~ = round16(x)`` (round to nearest even, NaN stays NaN, fp16 saturates at +-65504; queries
+        are never refused), ``t(i, j) = fmaf(-2, dot16(q~_i, x~_j), c_j)`` with ``c_j`` the index's fp32 ``||x_j||^2`` (``"l2"``) or
+        0 (``"cosine"``) and ``dot16`` the fp32-accumulated sum of the exact 16-bit products in the one fixed order of the kernel's
+        MFMA chain.  The candidates of query i are the m best admissible rows under ``(t, j)``; NaN ``t`` and same-group rows are
+        not admissible.  Stage 2: the exact ``s = fmaf(-2, q_i . x_j, c_j)`` of ``search``, bit for bit, for each candidate; order
+        ``(s, id)``, keep k.
+
+        So the result is ``search`` restricted to the candidate set -- every returned score is a real ``search`` score -- and with
+        ``m >= N`` it *is* ``search``, bit for bit.  The only approximation is which rows get re-ranked; ``refine`` controls it.
+        ``cand``, scores and ids do not depend on ``splits``, ``query_chunk``, how the index was built or stale workspace contents.
+        ``1 <= k <= 128``, integer ``refine >= 1``, ``k * refine <= 128``."""
+        if isinstance(k, bool) or int(k) != k or not 1 <= int(k) <= MAX_K:
+            raise ValueError("k must be an integer in [1, %d], got %r" % (MAX_K, k))
+        k = int(k)
+        if isinstance(refine, bool) or int(refine) != refine or int(refine) < 1:
+            raise ValueError("refine must be an integer >= 1, got %r" % (refine,))
+        m = k * int(refine)
+        if m > MAX_CANDIDATES:
+            raise ValueError("k * refine = %d candidates per query, more than %d" % (m, MAX_CANDIDATES))
+        if storage not in STORAGES:
+            raise ValueError("storage must be 'fp16' or 'bf16', got %r" % (storage,))
+        if len(self) == 0:
+            raise ValueError("the index is empty")
+        q = _rows(queries, "queries")
+        n, D = q.shape
+        if D != self.dim:
+            raise ValueError("queries: expected D = %d, got %d" % (self.dim, D))
+        qg = None
+        if exclude_same_group:
+            if groups is None:
+                raise ValueError("exclude_same_group needs the queries' groups")
+            qg = torch.from_numpy(_groups(groups, n, "groups")).to(self.device)
+        elif groups is not None:
+            _groups(groups, n, "groups")
+        if int(splits) < 0 or int(query_chunk) < 1:
+            raise ValueError("splits must be >= 0 and query_chunk >= 1")
+        scores = torch.empty((n, k), dtype=torch.float32, device=self.device)
+        ids = torch.empty((n, k), dtype=torch.int64, device=self.device)
+        cand = torch.empty((n, m), dtype=torch.int32, device=self.device)
+        if n == 0:
+            return (scores, ids, cand.to(torch.int64)) if return_candidates else (scores, ids)
+        x16 = self.half_rows(storage)
+        lib = _lib.load()
+        qd = self._prep(q)
+        q16 = self._pack16(qd, storage, refuse=False)
+        N = len(self)
+        step = min(n, int(query_chunk))
+        ws = torch.empty(_chunked_workspace_bytes(lib.sylber_knn16_workspace_bytes, n, step, N, D, m, int(splits)), dtype=torch.uint8,
+                         device=self.device)
+        metric, code = METRICS[self.metric], STORAGES[storage][0]
+        xg = self._g if qg is not None else None
+        with torch.cuda.device(self.device):
+            st = _stream(self.device)
+            for r0 in range(0, n, step):
+                r1 = min(n, r0 + step)
+                _lib.check(lib.sylber_knn16_scan(_vp(q16[r0:r1]), r1 - r0, _vp(x16), N, D, _vp(self._c), code, m,
+                                                 _vp(qg[r0:r1] if qg is not None else None), _vp(xg), int(splits), _vp(cand[r0:r1]), _vp(ws),
+                                                 st), "sylber_knn16_scan")
+                _lib.check(lib.sylber_knn_rerank(_vp(qd[r0:r1]), r1 - r0, _vp(self._x), N, D, _vp(self._c), metric, _vp(cand[r0:r1]), m, k,
+                                                 _vp(scores[r0:r1]), _vp(ids[r0:r1]), st), "sylber_knn_rerank")
+        return (scores, ids, cand.to(torch.int64)) if return_candidates else (scores, ids)
 
     # ---- phrase search --------------------------------------------------------------------------------------------------------------
     def sequence_offsets(self) -> np.ndarray:
