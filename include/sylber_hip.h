@@ -513,7 +513,15 @@ int sylber_condition_features(sylber_mlp_t m, const float* features_dev, int32_t
 /* ---- introspection used by parity tests and the benchmark ------------------------------------ */
 /* run sylber_forward only up to a stage: 0 = all, 1 = conv stack, 2 = +projection/pos-conv/LN,
  * 3 + l = through encoder layer l.  The stage output is written to hidden_dev in place of the final
- * hidden states: stage 1 -> [B,T,512] conv features, otherwise [B,T,768]. */
+ * hidden states: stage 1 -> [B,T,512] conv features, otherwise [B,T,768].
+ * Negative stages are taps inside the front half (the same launches as every forward, then a copy; never captured into a graph,
+ * not available to sylber_forward_packed), all fp32:
+ *   SYLBER_TAP_CONV0    conv layer 0 alone (GroupNorm + GELU applied): [B, R0, 512] with R0 = 64 * sylber_padded_frames(Lmax), every
+ *                       row of the 16-bit buffer widened exactly (hi + lo for SYLBER_SPLIT16); rows at or past (Lmax - 10) / 5 + 1 are +0
+ *   SYLBER_TAP_PROJ     the projected residual stream x, frames at or past an utterance's valid count zeroed: [B, T, 768]
+ *   SYLBER_TAP_POSCONV  x + GELU(pos-conv(x)), the input of the encoder LayerNorm: [B, T, 768]
+ * Any other negative stage is refused. */
+enum { SYLBER_TAP_CONV0 = -1, SYLBER_TAP_PROJ = -2, SYLBER_TAP_POSCONV = -3 };
 int sylber_set_stop_stage(sylber_t h, int32_t stage);
 /* per-kernel device time of the last forward, measured with HIP events on the launch stream.
  * names/ms arrays of capacity cap; returns the number of entries (<=cap) or <0 on error. */

@@ -27,6 +27,10 @@ int sylber_debug_gemm_trace(int32_t M, int32_t N, int32_t K, int32_t ldx, int32_
 /* test aid: fill the handle's activation workspace with `byte` (0xFF = NaN patterns) and force the next forward to redo the zeroing it
  * does after a batch-shape change; results must not change (tests/test_gpu_encoder.py) */
 int sylber_debug_poison_workspace(sylber_t h, int32_t byte);
+/* test aid: conv0's GroupNorm scale / shift table of the handle's last forward (padded or packed) of B utterances, copied to
+ * out_host [B][512][2]: (a, b) per channel with a = gamma / sqrt(var + 1e-5), b = beta - mean * a; synchronises the device
+ * (tests/test_gpu_frontend.py checks it against float64) */
+int sylber_debug_conv0_scale_shift(sylber_t h, int32_t B, float* out_host);
 /* average ms of one launch of the attention core (12 heads x 64, B utterances of T frames, no key mask) on pseudo-random packed
  * operands; precision: SYLBER_BF16 (bf16 operands) or SYLBER_FP8 (MXFP8 q / k / V^T, e4m3 P) */
 int sylber_debug_attention_bench(int32_t B, int32_t T, int32_t precision, int32_t iters, float* ms_out);

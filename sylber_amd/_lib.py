@@ -174,10 +174,13 @@ DEV_EXPORTS = {
     "sylber_debug_gemm_trace": (c_int, [c_int32] * 6 + [POINTER(ctypes.c_uint64), POINTER(c_float)]),
     "sylber_debug_attention_bench": (c_int, [c_int32] * 4 + [POINTER(c_float)]),
     "sylber_debug_poison_workspace": (c_int, [c_void_p, c_int32]),
+    "sylber_debug_conv0_scale_shift": (c_int, [c_void_p, c_int32, c_void_p]),
 }
 OPT_GEMM_TILE, OPT_ATTN_QUERIES_PER_WAVE, OPT_GEMM_PERSISTENT = 1, 2, 3
 OPT_CONV0_VALU = 5
 OPT_FP8_ATTENTION, OPT_SEGMENT, OPT_PER_UTTERANCE = 7, 9, 14
+# negative stop stages of sylber_set_stop_stage: taps inside the front half (include/sylber_hip.h SYLBER_TAP_*)
+TAP_CONV0, TAP_PROJ, TAP_POSCONV = -1, -2, -3
 
 _LIB = None
 

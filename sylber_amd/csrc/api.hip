@@ -186,7 +186,12 @@ extern "C" void sylber_destroy(sylber_t c) {
     delete c;
 }
 
-extern "C" int sylber_set_stop_stage(sylber_t c, int32_t stage) { if (!c) return 1; c->stop_stage = stage; return 0; }
+extern "C" int sylber_set_stop_stage(sylber_t c, int32_t stage) {
+    if (!c) return 1;
+    if (stage < SYLBER_TAP_POSCONV) { syl_set_error("sylber_set_stop_stage", "unknown tap (negative stages: -1 conv0, -2 projection, -3 pos-conv)"); return 1; }
+    c->stop_stage = stage;
+    return 0;
+}
 extern "C" int sylber_set_option(sylber_t c, int32_t key, int32_t value) {
     if (!c) { syl_set_error("sylber_set_option", "null handle"); return 1; }
     switch (key) {

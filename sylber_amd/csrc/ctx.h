@@ -63,6 +63,7 @@ struct sylber_ctx {
     int ws_B = 0, ws_Lmax = 0;
     float* seg_scratch = nullptr; size_t seg_scratch_floats = 0;
     int stop_stage = 0;
+    const float* dbg_ss = nullptr; int dbg_ss_B = 0;               // conv0's GroupNorm scale / shift table of the last forward (sylber_debug_conv0_scale_shift)
     int opt_gemm_cfg = 0, opt_attn_qw = 0, opt_gemm_persist = 0;   // sylber_set_option (0 = automatic)
     int opt_fuse_ln = 0;                                           // out-projection + LayerNorm in one launch: 0 auto, 1 always, -1 never
     int opt_conv0_valu = 0;                                        // 1: conv0 of the 16-bit modes on the VALU kernel (A/B switch)

@@ -322,9 +322,20 @@ struct PackedCall {
     const int *slot, *frames, *qb, *rows0;     // [nclip + 1], [nclip], [nclip + 1], [nclip]; slot / frames / qb contiguous (attention)
 };
 
+// the taps in front of the encoder LayerNorm (SYLBER_TAP_PROJ / SYLBER_TAP_POSCONV): frames [0, T) of every utterance of an fp32
+// [B][Tp][768] workspace tensor, compacted to [B][T][768].  Copies, so a tap call is never captured into a graph (sylber_forward).
+static int copy_frames_f32(const float* src, float* dst, int B, int Tp, int T, hipStream_t s) {
+    for (int b = 0; b < B; ++b)
+        HIP_TRY(hipMemcpyAsync(dst + (size_t)b * T * SYL_HIDDEN, src + (size_t)b * Tp * SYL_HIDDEN, (size_t)T * SYL_HIDDEN * 4,
+                               hipMemcpyDeviceToDevice, s));
+    return 0;
+}
+
 // every kernel launch of the bf16 / fp16 / mixed16 / split16 / fp8 forward, in stream order; nothing else (no allocation, copy or
 // synchronisation), so the sequence can be replayed from a captured hipGraph.  pk: a packed batch (bf16 / fp16), nullptr for the padded
 // one; only conv0, the zeroing of the slot tails, the pos-conv and the attention read its tables.
+// The one exception: with a negative stop stage (a tap) run() ends in device-to-device copies (copy_frames_f32); sylber_forward never
+// captures such a call and sylber_forward_packed refuses it.
 struct Forward {
     sylber_ctx* c; const Plan& p; const float* wav_dev; float* hidden_dev; hipStream_t s; const PackedCall* pk;
     const Ws<bf16_t> w; const WsF8 w8;
@@ -503,12 +514,20 @@ struct Forward {
     }
 
     int run() {
-        if (conv0() || conv_stack()) return 1;
+        if (conv0()) return 1;
+        if (c->stop_stage == SYLBER_TAP_CONV0) {        // every row of the 16-bit buffer, rows [L0, R0) included, widened exactly
+            RUN("copy_out", launch_bf16_to_f32_rows(w.bufA, 512, hidden_dev, B, p.R[0], p.R[0], 512, s, c->fmt_conv, p.lo_bufA));
+            return 0;
+        }
+        if (conv_stack()) return 1;
         if (c->stop_stage == 1) {
             RUN("copy_out", launch_bf16_to_f32_rows(feats, 512, hidden_dev, B, p.Tp, p.T, 512, s, c->fmt_conv, feats_lo));
             return 0;
         }
-        if (projection() || posconv()) return 1;
+        if (projection()) return 1;
+        if (c->stop_stage == SYLBER_TAP_PROJ) return copy_frames_f32(w.xf32, hidden_dev, B, p.Tp, p.T, s);
+        if (posconv()) return 1;
+        if (c->stop_stage == SYLBER_TAP_POSCONV) return copy_frames_f32(w.pre, hidden_dev, B, p.Tp, p.T, s);
         RUN("layernorm", layernorm(c->enc_ln_w, c->enc_ln_b, c->stop_stage == 2));
         if (c->stop_stage == 2) return 0;
         res_g = c->enc_ln_w; res_b = c->enc_ln_b;
@@ -599,7 +618,12 @@ struct ForwardF32 {
     }
 
     int run() {
-        if (conv0() || conv_stack()) return 1;
+        if (conv0()) return 1;
+        if (c->stop_stage == SYLBER_TAP_CONV0) {
+            HIP_TRY(hipMemcpyAsync(hidden_dev, w.bufA, (size_t)B * p.R[0] * 512 * 4, hipMemcpyDeviceToDevice, s));
+            return 0;
+        }
+        if (conv_stack()) return 1;
         if (c->stop_stage == 1) {
             for (int b = 0; b < B; ++b)
                 HIP_TRY(hipMemcpyAsync(hidden_dev + (size_t)b * p.T * 512, feats + (size_t)b * p.Tp * 512, (size_t)p.T * 512 * 4,
@@ -607,7 +631,9 @@ struct ForwardF32 {
             return 0;
         }
         if (projection()) return 1;
+        if (c->stop_stage == SYLBER_TAP_PROJ) return copy_frames_f32(w.xf32, hidden_dev, B, p.Tp, p.T, s);
         RUN("posconv_f32", launch_posconv_f32(w.xpad, c->pos_w32, c->pos_b, w.xf32, w.pre, B, p.Tp, s));
+        if (c->stop_stage == SYLBER_TAP_POSCONV) return copy_frames_f32(w.pre, hidden_dev, B, p.Tp, p.T, s);
         RUN("layernorm", layernorm(c->enc_ln_w, c->enc_ln_b, c->stop_stage == 2));
         if (c->stop_stage == 2) return 0;
         for (int l = 0; l < c->num_layers; ++l) {
@@ -673,8 +699,10 @@ extern "C" int sylber_forward(sylber_t c, const float* wav_dev, const int32_t* l
     const bool f32 = c->precision == SYLBER_FP32;
     const Plan p = f32 ? make_plan_f32(B, Lmax) : make_plan(B, Lmax, c->precision == SYLBER_SPLIT16 ? 2 : 1);
     if (begin_call(c, p, {{p.o_valid, valid.data(), B}, {p.o_rows, c->opt_per_utt ? rows0.data() : nullptr, B}}, s)) return 1;
+    c->dbg_ss = (const float*)(c->ws + p.o_ss); c->dbg_ss_B = B;      // sylber_debug_conv0_scale_shift
     if (f32) return ForwardF32(c, p, wav_dev, hidden_dev, s).run();
-    if (!c->graph_mode || c->profiling || c->opt_audit16 || s == nullptr) return Forward(c, p, wav_dev, hidden_dev, s, nullptr).run();
+    // a tap (negative stop stage) copies workspace tensors out: always eager, never captured
+    if (!c->graph_mode || c->profiling || c->opt_audit16 || s == nullptr || c->stop_stage < 0) return Forward(c, p, wav_dev, hidden_dev, s, nullptr).run();
     return forward_graph(c, p, wav_dev, hidden_dev, s);
 }
 
@@ -712,6 +740,7 @@ extern "C" int sylber_forward_packed(sylber_t c, const float* wav_dev, const int
     const int32_t one = Ptot;                           // the projection's valid[0]: no frame of the pseudo-utterance is padding to it
     if (begin_call(c, p, {{p.o_pk, tab.data(), 3 * B + 2}, {p.o_rows, rows0.data(), B}, {p.o_valid, &one, 1}}, s)) return 1;
     const int* pkd = (const int*)(c->ws + p.o_pk);
+    c->dbg_ss = (const float*)(c->ws + p.o_ss); c->dbg_ss_B = B;
     const PackedCall pc = {B, SYL_SLOT_SAMPLES * Ptot, slot_max, tail_max, tab[3 * B + 1], pkd, pkd + B + 1, pkd + 2 * B + 1, (const int*)(c->ws + p.o_rows)};
     return Forward(c, p, wav_dev, hidden_dev, s, &pc).run();
 }

@@ -274,6 +274,17 @@ extern "C" int sylber_debug_poison_workspace(sylber_t c, int32_t byte) {
     return 0;
 }
 
+// test aid: conv0's GroupNorm table of the handle's last forward, [B][512][2] = (a_c, b_c) with a = gamma / sqrt(var + eps) and
+// b = beta - mean a (conv0_finalize_kernel), copied to the host.  It lives in the workspace and is overwritten by the next forward.
+extern "C" int sylber_debug_conv0_scale_shift(sylber_t c, int32_t B, float* out_host) {
+    if (!c || !out_host) { syl_set_error("sylber_debug_conv0_scale_shift", "null argument"); return 1; }
+    if (!c->dbg_ss || !c->ws || B < 1 || B != c->dbg_ss_B) { syl_set_error("sylber_debug_conv0_scale_shift", "B must be the batch size of the handle's last forward"); return 1; }
+    GUARD_DEVICE(c->device);
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(out_host, c->dbg_ss, (size_t)B * SYL_CONV * 2 * sizeof(float), hipMemcpyDeviceToHost));
+    return 0;
+}
+
 // kernel-only timing of the attention core on random packed operands (development aid): precision SYLBER_BF16 or SYLBER_FP8
 extern "C" int sylber_debug_attention_bench(int32_t B, int32_t T, int32_t precision, int32_t iters, float* ms_out) {
     const int Tp = (T + 31) & ~31, Tpv = (Tp + 63) & ~63;

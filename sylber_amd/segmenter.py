@@ -348,17 +348,26 @@ class HubertEncoderHIP:
 
     def forward(self, wav: torch.Tensor, lengths: Optional[Sequence[int]] = None, stop_stage: int = 0,
                 out: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """wav: [B, Lmax] float32 on this device, zero padded.  Returns [B, T, 768] float32 (device)."""
+        """wav: [B, Lmax] float32 on this device, zero padded.  Returns [B, T, 768] float32 (device).
+
+        ``stop_stage`` (include/sylber_hip.h sylber_set_stop_stage): 1 returns the conv features [B, T, 512], 2 / 3 + l the stream after
+        the encoder LayerNorm / layer l.  Negative values are the taps of the front half: ``_lib.TAP_CONV0`` conv layer 0 alone,
+        [B, 64 * padded_frames(Lmax), 512] (every row of its buffer); ``_lib.TAP_PROJ`` the projected residual stream and
+        ``_lib.TAP_POSCONV`` the encoder LayerNorm's input, both [B, T, 768]."""
         assert wav.is_cuda and wav.dtype == torch.float32 and wav.dim() == 2 and wav.is_contiguous()
         B, Lmax = wav.shape
         T = self.num_frames(Lmax)
-        width = 512 if stop_stage == 1 else 768
+        if stop_stage == _lib.TAP_CONV0:
+            shape = (B, 64 * self.padded_frames(Lmax), 512)
+        else:
+            shape = (B, T, 512 if stop_stage == 1 else 768)
         if out is None:
-            out = torch.empty(B, T, width, dtype=torch.float32, device=wav.device)
+            out = torch.empty(*shape, dtype=torch.float32, device=wav.device)
+        assert out.numel() >= shape[0] * shape[1] * shape[2]
         larr = None
         if lengths is not None:
             larr = (ctypes.c_int32 * B)(*[int(x) for x in lengths])
-        self.lib.sylber_set_stop_stage(self.handle, int(stop_stage))
+        _lib.check(self.lib.sylber_set_stop_stage(self.handle, int(stop_stage)), "sylber_set_stop_stage")
         cur = torch.cuda.current_stream(wav.device)
         use = cur
         if getattr(self, "_graph_stream", None) is not None and cur.cuda_stream == 0:
@@ -372,6 +381,13 @@ class HubertEncoderHIP:
             cur.wait_stream(use)
         self.lib.sylber_set_stop_stage(self.handle, 0)
         _lib.check(st, "sylber_forward")
+        return out
+
+    def conv0_scale_shift(self, B: int) -> np.ndarray:
+        """test aid: conv0's GroupNorm table of the last forward (of B utterances), [B, 512, 2] float32 = (scale, shift) per channel"""
+        out = np.empty((int(B), 512, 2), dtype=np.float32)
+        _lib.check(self.lib.sylber_debug_conv0_scale_shift(self.handle, int(B), out.ctypes.data_as(ctypes.c_void_p)),
+                   "sylber_debug_conv0_scale_shift")
         return out
 
     def set_batches_in_flight(self, n: int) -> None:

@@ -32,6 +32,21 @@ def test_header_symbols_are_exported(lib):
         assert hasattr(lib, name), name
 
 
+def test_front_half_taps_are_declared_on_both_sides(lib):
+    """the negative stop stages (taps inside the front half) carry the same ids in the header and in the ctypes binding, and the debug
+    getter of conv0's GroupNorm table is a development aid, not part of the drop-in ABI"""
+    from sylber_amd import _lib
+    hdr = open(os.path.join(ROOT, "include", "sylber_hip.h")).read()
+    ids = {k: int(v) for k, v in re.findall(r"\b(SYLBER_TAP_[A-Z0-9]+)\s*=\s*(-?\d+)", hdr)}
+    assert ids == {"SYLBER_TAP_CONV0": _lib.TAP_CONV0, "SYLBER_TAP_PROJ": _lib.TAP_PROJ, "SYLBER_TAP_POSCONV": _lib.TAP_POSCONV}
+    assert sorted(ids.values()) == [-3, -2, -1]
+    assert "sylber_debug_conv0_scale_shift" in _lib.DEV_EXPORTS and "sylber_debug_conv0_scale_shift" not in _lib.EXPORTS
+    dev = open(os.path.join(ROOT, "include", "sylber_hip_dev.h")).read()
+    assert re.search(r"int\s+sylber_debug_conv0_scale_shift\s*\(\s*sylber_t\s+h\s*,\s*int32_t\s+B\s*,\s*float\s*\*\s*out_host\s*\)", dev)
+    # host-only behaviour: a null handle is refused by both entry points (no device is touched)
+    assert lib.sylber_set_stop_stage(None, -1) != 0 and lib.sylber_debug_conv0_scale_shift(None, 1, None) != 0
+
+
 def test_no_process_global_tuning_state():
     """tuning overrides are per handle (sylber_set_option) or per call: the old process-global force switches are gone"""
     for f in ("gemm_bf16.hip", "gemm_mxfp8.hip", "attention.hip", "api.hip", "forward.hip", "ops.hip", "ctx.h"):
