@@ -266,6 +266,31 @@ int sylber_knn16_scan(const void* q16_dev, int32_t n, const void* db16_dev, int3
 int sylber_knn_rerank(const float* q_dev, int32_t n, const float* db_dev, int32_t N, int32_t D, const float* db_norm_dev, int32_t metric,
                       const int32_t* cand_dev, int32_t m, int32_t k, float* score_dev, int64_t* idx_dev, void* stream);
 
+/* Product-quantized search (sylber_amd/pq.py: PQSyllableIndex): a row of D floats is stored as M bytes (1 <= M <= 64, D % M == 0,
+ * dsub = D / M a multiple of 16), byte m the nearest of the 256 centroids cb_dev [M, 256, dsub] of sub-space m (columns
+ * [m dsub, (m + 1) dsub)); cnorm_dev [M, 256] = sylber_knn_row_norms of the centroids.
+ * sylber_pq_encode: code_dev [n, M] = for every m the label sylber_kmeans_assign gives the sub-row against codebook m, bit for bit:
+ *   argmin_c fmaf(-2, x . c, ||c||^2), the dot product the ascending fmaf chain from 0, ties to the smaller c; all M sub-spaces in one
+ *   launch.  A sub-row without a comparable distance (it holds a NaN) gets code 0, and bad_dev [n] is 1 for such a row, else 0.
+ * sylber_pq_decode: out_dev [n, D] = the centroids the codes name.
+ * sylber_pq_lut: lut_dev [n, M, 256], lut[i][m][c] = fmaf(-2, q_i[sub-row m] . cb[m][c], cm), the same chain; cm = cnorm[m][c]
+ *   (SYLBER_KNN_L2) or 0 (SYLBER_KNN_IP: cnorm_dev may be null).
+ * sylber_pq_scan: t(i, j) = ((lut[i][0][code[j][0]] + lut[i][1][code[j][1]]) + ...) + lut[i][M-1][code[j][M-1]], fp32 adds in ascending
+ *   m.  The candidates of query i are the m best admissible rows under the strict order (t, j): t_dev / cand_dev [n, m], best first,
+ *   padded with (+inf, -1).  A NaN t, a row with bad_dev[j] != 0 (bad_dev may be null: no mask) and, with both group arrays, a row
+ *   of the query's group are not admissible.  Bitwise independent of splits (0 = automatic), of how the queries are chunked or
+ *   share workgroups, and of what the workspace held.  workspace_dev: sylber_pq_workspace_bytes(n, N, M, m, splits) bytes; code_dev
+ *   16-byte aligned. */
+int sylber_pq_encode(const float* x_dev, int32_t n, int32_t D, const float* cb_dev, const float* cnorm_dev, int32_t M, uint8_t* code_dev,
+                     uint8_t* bad_dev, void* stream);
+int sylber_pq_decode(const uint8_t* code_dev, int32_t n, const float* cb_dev, int32_t M, int32_t D, float* out_dev, void* stream);
+int sylber_pq_lut(const float* q_dev, int32_t n, int32_t D, const float* cb_dev, const float* cnorm_dev, int32_t M, int32_t metric,
+                  float* lut_dev, void* stream);
+int64_t sylber_pq_workspace_bytes(int32_t n, int32_t N, int32_t M, int32_t m, int32_t splits);
+int sylber_pq_scan(const float* lut_dev, int32_t n, const uint8_t* code_dev, const uint8_t* bad_dev, int32_t N, int32_t M, int32_t m,
+                   const int32_t* q_group_dev, const int32_t* db_group_dev, int32_t splits, float* t_dev, int32_t* cand_dev,
+                   void* workspace_dev, void* stream);
+
 /* Inverted-file search (sylber_amd/search.py: IVFSyllableIndex): sylber_knn_search restricted, per query, to the rows of the lists it
  * probes.  The rows lie list by list in rows_dev (list l = positions list_offsets[l] .. list_offsets[l + 1], ascending original id
  * within a list); row_id_dev [N] maps a position to the row's original id, row_norm_dev / row_group_dev are in position order too.

@@ -114,6 +114,12 @@ EXPORTS = {
                                   c_void_p, c_void_p, c_void_p]),
     "sylber_knn_rerank": (c_int, [c_void_p, c_int32, c_void_p, c_int32, c_int32, c_void_p, c_int32, c_void_p, c_int32, c_int32, c_void_p,
                                   c_void_p, c_void_p]),
+    "sylber_pq_encode": (c_int, [c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p]),
+    "sylber_pq_decode": (c_int, [c_void_p, c_int32, c_void_p, c_int32, c_int32, c_void_p, c_void_p]),
+    "sylber_pq_lut": (c_int, [c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p]),
+    "sylber_pq_workspace_bytes": (c_int64, [c_int32, c_int32, c_int32, c_int32, c_int32]),
+    "sylber_pq_scan": (c_int, [c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_int32, c_void_p,
+                               c_void_p, c_void_p, c_void_p]),
     "sylber_ivf_work_items": (c_int32, [POINTER(c_int32), POINTER(c_int32), c_int32, c_int32, POINTER(c_int32), c_int32, POINTER(c_int32)]),
     "sylber_ivf_workspace_bytes": (c_int64, [c_int32, c_int32, c_int32, c_int32]),
     "sylber_ivf_search": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p,

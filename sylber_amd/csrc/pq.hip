@@ -1,0 +1,361 @@
+// Product-quantized syllable search (sylber_amd/pq.py: PQSyllableIndex): a row of D floats is stored as M bytes, byte m the nearest of
+// the 256 centroids of sub-space m (columns [m dsub, (m + 1) dsub), dsub = D / M); a query scores a row by M look-ups in its own
+// [M, 256] table of partial scores (asymmetric distance computation).
+//   * pq_encode_kernel: code[j][m] = argmin_c fmaf(-2, x_j[slice m] . C[m][c], ||C[m][c]||^2), the dot product an explicit ascending fmaf
+//     chain from 0 -- the chain v_mfma_f32_32x32x2_f32 performs in km_fused_assign_kernel (kmeans.hip), so the codes are
+//     sylber_kmeans_assign's labels of the sliced rows, bit for bit -- ties to the smaller c.  One launch walks all M sub-spaces of a
+//     block of rows.  A sub-row without any comparable distance (a NaN in it) gets code 0 and marks its row in the byte mask.
+//   * pq_lut_kernel: lut[i][m][c] = fmaf(-2, q_i[slice m] . C[m][c], cnorm[m][c] or 0), the same chain.
+//   * pq_scan_kernel: a workgroup holds the tables of QB queries in LDS (M KiB each) and walks one split of the code rows, a lane per
+//     row: t = the fp32 sum of the row's M table entries in ascending m, one order for every row, split and block, so t's bits are a
+//     function of (query, row) alone.  Rows that beat a query's current worst go through an LDS strip into that query's sorted top
+//     list (kn_insert); the per-split lists are merged with knn_lists.h.  The table gather is a random 4-byte LDS read inside a 1 KiB
+//     region: bank conflicts of a few ways are part of the algorithm (any layout that avoids them changes the add order).
+//   * pq_decode_kernel: out[j][slice m] = C[m][code[j][m]].
+#include "kernels.h"
+#include "../../include/sylber_hip.h"
+#include "knn_tile.h"
+#include "knn_lists.h"
+
+constexpr int PQ_KSUB = 256;                               // centroids per sub-space: one byte per code
+constexpr int PQ_MAX_M = 64;
+constexpr int PQ_T = 1024;                                 // threads of a scan workgroup = code rows of a tile: four waves per SIMD keep
+                                                           // the 4-byte LDS gathers in flight
+constexpr int PQ_LDS = 160 * 1024;                         // LDS of a CU; one workgroup takes as many tables as fit
+constexpr int PQ_LDS_FIXED = 256;                          // flags and query groups
+constexpr int PQ_TARGET_BLOCKS = 512, PQ_MIN_TILES = 4;    // automatic splits: about this many workgroups, at least these tiles each
+constexpr int PE_R = 32;                                   // rows of an encode workgroup
+
+static bool pq_geometry(int D, int M) { return M >= 1 && M <= PQ_MAX_M && D >= 16 && D % M == 0 && (D / M) % 16 == 0; }
+
+// ---- encode ----------------------------------------------------------------------------------------------------------------------
+// grid ceil(n / 32): thread c owns centroid c of the current sub-space and carries 32 rows' chains; the rows' 16 values of a K step
+// are staged in LDS and read as broadcasts.
+__global__ __launch_bounds__(256) void pq_encode_kernel(const float* __restrict__ x, int n, int D, const float* __restrict__ cb,
+                                                        const float* __restrict__ cnorm, int M, uint8_t* __restrict__ code,
+                                                        uint8_t* __restrict__ bad) {
+    __shared__ __attribute__((aligned(16))) float xs[PE_R][16];
+    __shared__ float rv[4][PE_R];
+    __shared__ int ri[4][PE_R];
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int r0 = blockIdx.x * PE_R, dsub = D / M;
+    int xr = r0 + (tid >> 2); xr = xr < n ? xr : n - 1;
+    const float* xsrc = x + (size_t)xr * D + (tid & 3) * 4;
+    int isbad = 0;                                         // thread r < 32: row r0 + r has a sub-row without a code
+    for (int m = 0; m < M; ++m) {
+        const float* crow = cb + ((size_t)m * PQ_KSUB + tid) * dsub;
+        float acc[PE_R];
+#pragma unroll
+        for (int r = 0; r < PE_R; ++r) acc[r] = 0.f;
+        for (int k0 = 0; k0 < dsub; k0 += 16) {
+            __syncthreads();                               // the previous step's xs (and the previous sub-space's rv / ri) are read
+            if (tid < PE_R * 4) *(float4*)&xs[tid >> 2][(tid & 3) * 4] = *(const float4*)(xsrc + m * dsub + k0);
+            float cv[16];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const float4 c4 = *(const float4*)(crow + k0 + 4 * e);
+                cv[4 * e] = c4.x; cv[4 * e + 1] = c4.y; cv[4 * e + 2] = c4.z; cv[4 * e + 3] = c4.w;
+            }
+            __syncthreads();
+#pragma unroll
+            for (int r = 0; r < PE_R; ++r) {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const float4 x4 = *(const float4*)&xs[r][4 * e];
+                    acc[r] = __builtin_fmaf(x4.x, cv[4 * e], acc[r]);
+                    acc[r] = __builtin_fmaf(x4.y, cv[4 * e + 1], acc[r]);
+                    acc[r] = __builtin_fmaf(x4.z, cv[4 * e + 2], acc[r]);
+                    acc[r] = __builtin_fmaf(x4.w, cv[4 * e + 3], acc[r]);
+                }
+            }
+        }
+        const float cn = cnorm[m * PQ_KSUB + tid];
+#pragma unroll
+        for (int r = 0; r < PE_R; ++r) {
+            const float d = __builtin_fmaf(-2.0f, acc[r], cn);
+            float bv = d == d ? d : INFINITY;              // a NaN distance never wins (km_better never takes it)
+            int bi = d == d ? tid : INT_MAX;
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) {
+                const float ov = __shfl_xor(bv, o, 64);
+                const int oi = __shfl_xor(bi, o, 64);
+                if (kn_better(ov, oi, bv, bi)) { bv = ov; bi = oi; }
+            }
+            if (lane == 0) { rv[wave][r] = bv; ri[wave][r] = bi; }
+        }
+        __syncthreads();
+        if (tid < PE_R && r0 + tid < n) {
+            float bv = rv[0][tid]; int bi = ri[0][tid];
+#pragma unroll
+            for (int w = 1; w < 4; ++w) if (kn_better(rv[w][tid], ri[w][tid], bv, bi)) { bv = rv[w][tid]; bi = ri[w][tid]; }
+            if (bi == INT_MAX) { bi = 0; isbad = 1; }
+            code[(size_t)(r0 + tid) * M + m] = (uint8_t)bi;
+        }
+    }
+    if (tid < PE_R && r0 + tid < n) bad[r0 + tid] = (uint8_t)isbad;
+}
+
+// ---- decode ----------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void pq_decode_kernel(const uint8_t* __restrict__ code, int64_t quads, const float* __restrict__ cb, int M,
+                                                        int D, float* __restrict__ out) {
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;     // one float4 of the output
+    if (e >= quads) return;
+    const int dsub = D / M, dq = D / 4;
+    const int64_t j = e / dq;
+    const int col = (int)(e - j * dq) * 4, m = col / dsub;
+    const int c = code[j * M + m];
+    *(float4*)(out + j * D + col) = *(const float4*)(cb + ((size_t)m * PQ_KSUB + c) * dsub + (col - m * dsub));
+}
+
+// ---- table -----------------------------------------------------------------------------------------------------------------------
+// grid n x M: workgroup (i, m), thread c.  cnorm null: the inner-product table.
+__global__ __launch_bounds__(256) void pq_lut_kernel(const float* __restrict__ q, int D, const float* __restrict__ cb,
+                                                     const float* __restrict__ cnorm, int M, float* __restrict__ lut) {
+    const int64_t b = blockIdx.x;
+    const int64_t i = b / M;
+    const int m = (int)(b - i * M), c = threadIdx.x, dsub = D / M;
+    const float* qr = q + i * D + (size_t)m * dsub;
+    const float* cr = cb + ((size_t)m * PQ_KSUB + c) * dsub;
+    float dot = 0.f;
+    for (int k = 0; k < dsub; k += 4) {
+        const float4 a = *(const float4*)(qr + k), v = *(const float4*)(cr + k);
+        dot = __builtin_fmaf(a.x, v.x, dot);
+        dot = __builtin_fmaf(a.y, v.y, dot);
+        dot = __builtin_fmaf(a.z, v.z, dot);
+        dot = __builtin_fmaf(a.w, v.w, dot);
+    }
+    lut[b * PQ_KSUB + c] = __builtin_fmaf(-2.0f, dot, cnorm ? cnorm[m * PQ_KSUB + c] : 0.f);
+}
+
+// ---- scan ------------------------------------------------------------------------------------------------------------------------
+// the queries of a workgroup: the most tables that fit beside their strips and top lists
+static size_t pq_lds_per_query(int M, int m) { return (size_t)M * PQ_KSUB * 4 + (size_t)PQ_T * 4 + (size_t)m * 8; }
+static int pq_block_queries(int M, int m) {
+    const int fit = (int)((PQ_LDS - PQ_LDS_FIXED) / pq_lds_per_query(M, m));
+    for (int qb : {8, 6, 4, 3, 2}) if (fit >= qb) return qb;
+    return 1;
+}
+static int pq_scan_splits(int64_t n, int64_t N, int QB, int64_t splits) {
+    const int64_t nb = (n + QB - 1) / QB, tiles = (N + PQ_T - 1) / PQ_T;
+    int64_t S = splits;
+    if (S <= 0) {
+        S = (PQ_TARGET_BLOCKS + nb - 1) / nb;
+        const int64_t cap = tiles / PQ_MIN_TILES;
+        S = S < cap ? S : cap;
+    }
+    S = S < tiles ? S : tiles;
+    S = S < 65535 ? S : 65535;
+    return (int)(S < 1 ? 1 : S);
+}
+
+template <int VEC> __device__ __forceinline__ void pq_load(const uint8_t* p, uint32_t (&w)[4]) { w[0] = *p; }
+template <> __device__ __forceinline__ void pq_load<4>(const uint8_t* p, uint32_t (&w)[4]) { w[0] = *(const uint32_t*)p; }
+template <> __device__ __forceinline__ void pq_load<16>(const uint8_t* p, uint32_t (&w)[4]) {
+    const uint4 v = *(const uint4*)p;
+    w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
+}
+
+// grid (ceil(n / QB), S): split sp walks the tiles [sp * tiles / S, (sp + 1) * tiles / S) of PQ_T code rows.  VEC bytes of a code row
+// per load (VEC divides M; 16 where M % 16 == 0).  Writes the sorted best m of every valid query over its tiles to ps / pi [n][S][m];
+// entries that did not fill stay (+inf, INT_MAX).
+template <int QB, int VEC>
+__global__ __launch_bounds__(PQ_T) void pq_scan_kernel(const float* __restrict__ lut, int n, const uint8_t* __restrict__ code,
+                                                       const uint8_t* __restrict__ bad, int N, int M, int m,
+                                                       const int32_t* __restrict__ qgrp, const int32_t* __restrict__ xgrp, int S,
+                                                       float* __restrict__ ps, int32_t* __restrict__ pi) {
+    extern __shared__ __attribute__((aligned(16))) float pq_smem[];
+    const int tsz = M * PQ_KSUB;
+    float* tab = pq_smem;                                  // [QB][M][256] the queries' tables
+    float* strip = tab + QB * tsz;                         // [QB][PQ_T] a tile's scores of a flagged query (NaN = not admissible)
+    float* ls = strip + QB * PQ_T;                         // [QB][m] sorted scores
+    int* li = (int*)(ls + QB * m);                         // [QB][m] their rows
+    int* flags = li + QB * m;                              // [2][QB] by tile parity: the tile may hold a candidate of query q
+    int* qgs = flags + 2 * QB;                             // [QB] the queries' groups
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int q0 = blockIdx.x * QB, sp = blockIdx.y;
+    const int nq = n - q0 < QB ? n - q0 : QB;
+    const int tiles = (N + PQ_T - 1) / PQ_T;
+    const int tlo = (int)((int64_t)sp * tiles / S), thi = (int)((int64_t)(sp + 1) * tiles / S);
+#pragma unroll
+    for (int q = 0; q < QB; ++q) {                         // queries past n copy the last one: they gather, but never flag
+        const float* src = lut + (size_t)(q < nq ? q0 + q : n - 1) * tsz;
+        for (int e = tid * 4; e < tsz; e += PQ_T * 4) *(float4*)(tab + q * tsz + e) = *(const float4*)(src + e);
+    }
+    for (int e = tid; e < QB * m; e += PQ_T) { ls[e] = INFINITY; li[e] = INT_MAX; }
+    if (tid < 2 * QB) flags[tid] = 0;
+    if (tid < QB) qgs[tid] = qgrp ? qgrp[tid < nq ? q0 + tid : n - 1] : 0;
+    __syncthreads();
+    for (int tile = tlo; tile < thi; ++tile) {
+        const int base = tile * PQ_T, row = base + tid;
+        const int r = row < N ? row : N - 1;
+        const uint8_t* cr = code + (size_t)r * M;
+        float t[QB];
+#pragma unroll
+        for (int q = 0; q < QB; ++q) t[q] = -0.0f;         // -0 + v = v for every v, -0 included: the sum starts at its first entry
+        for (int mb = 0; mb < M; mb += VEC) {
+            uint32_t w[4];
+            pq_load<VEC>(cr + mb, w);
+#pragma unroll
+            for (int b = 0; b < VEC; ++b) {
+                const float* tp = tab + (mb + b) * PQ_KSUB + ((w[b >> 2] >> (8 * (b & 3))) & 255u);
+#pragma unroll
+                for (int q = 0; q < QB; ++q) t[q] += tp[q * tsz];
+            }
+        }
+        const bool live = row < N && !(bad && bad[r]);
+        const int g = xgrp ? xgrp[r] : 0;
+        int* fl_w = flags + (tile & 1) * QB;
+#pragma unroll
+        for (int q = 0; q < QB; ++q) {
+            const bool adm = live && q < nq && !(xgrp && g == qgs[q]);
+            t[q] = adm ? t[q] : __builtin_nanf("");
+            if (t[q] <= ls[q * m + m - 1]) fl_w[q] = 1;    // a superset of the exact (t, row) test; NaN never passes
+        }
+        __syncthreads();
+        int fl = 0;
+#pragma unroll
+        for (int q = 0; q < QB; ++q) fl |= fl_w[q] << q;   // block-uniform; the next tile flags the other parity
+        if (!fl) continue;
+#pragma unroll
+        for (int q = 0; q < QB; ++q) if ((fl >> q) & 1) strip[q * PQ_T + tid] = t[q];
+        __syncthreads();
+        if (tid < QB) fl_w[tid] = 0;
+        if (wave < QB && ((fl >> wave) & 1)) {             // wave q puts the survivors of query q into its list one at a time
+            float* lsr = ls + wave * m;
+            int* lir = li + wave * m;
+            const float* sq = strip + wave * PQ_T;
+            for (int h = 0; h < PQ_T / 64; ++h) {
+                uint64_t bal = __ballot(kn_better(sq[h * 64 + lane], base + h * 64 + lane, lsr[m - 1], lir[m - 1]));
+                while (bal) {
+                    const int c = __ffsll((unsigned long long)bal) - 1;
+                    bal &= bal - 1;
+                    kn_insert(lsr, lir, m, lane, sq[h * 64 + c], base + h * 64 + c);
+                }
+            }
+        }
+        __syncthreads();                                   // the lists are complete before the next tile reads its thresholds
+    }
+    __syncthreads();
+    for (int q = 0; q < nq; ++q) {
+        const size_t o = ((size_t)(q0 + q) * S + sp) * m;
+        for (int e = tid; e < m; e += PQ_T) { ps[o + e] = ls[q * m + e]; pi[o + e] = li[q * m + e]; }
+    }
+}
+
+// the merged lists as candidates: the (+inf, INT_MAX) fillers become (+inf, -1)
+__global__ __launch_bounds__(256) void pq_cand_kernel(const float* __restrict__ ls, const int32_t* __restrict__ li, int64_t tot,
+                                                      float* __restrict__ t, int32_t* __restrict__ cand) {
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= tot) return;
+    const int j = li[e];
+    t[e] = j == INT_MAX ? INFINITY : ls[e];
+    cand[e] = j == INT_MAX ? -1 : j;
+}
+
+template <int QB, int VEC>
+static int pq_launch_scan(const float* lut, int n, const uint8_t* code, const uint8_t* bad, int N, int M, int m, const int32_t* qg,
+                          const int32_t* xg, int S, float* ps, int32_t* pi, hipStream_t s) {
+    static PerDeviceOnce once;
+    if (once.need())
+        HIP_TRY(hipFuncSetAttribute((const void*)pq_scan_kernel<QB, VEC>, hipFuncAttributeMaxDynamicSharedMemorySize, PQ_LDS));
+    const size_t lds = QB * pq_lds_per_query(M, m) + PQ_LDS_FIXED;
+    hipLaunchKernelGGL((pq_scan_kernel<QB, VEC>), dim3((unsigned)((n + QB - 1) / QB), (unsigned)S), dim3(PQ_T), lds, s, lut, n, code, bad, N, M,
+                       m, qg, xg, S, ps, pi);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+template <int QB, typename... A> static int pq_launch_scan_vec(int M, A... a) {
+    if (M % 16 == 0) return pq_launch_scan<QB, 16>(a...);
+    if (M % 4 == 0) return pq_launch_scan<QB, 4>(a...);
+    return pq_launch_scan<QB, 1>(a...);
+}
+
+static int64_t pq_al(int64_t bytes) { return (bytes + 255) / 256 * 256; }
+
+extern "C" int sylber_pq_encode(const float* x_dev, int32_t n, int32_t D, const float* cb_dev, const float* cnorm_dev, int32_t M,
+                                uint8_t* code_dev, uint8_t* bad_dev, void* stream) {
+    static const char* what = "sylber_pq_encode";
+    if (!x_dev || !cb_dev || !cnorm_dev || !code_dev || !bad_dev) { syl_set_error(what, "null argument"); return 1; }
+    if (n < 1) { syl_set_error(what, "need n >= 1"); return 1; }
+    if (!pq_geometry(D, M)) { syl_set_error(what, "need 1 <= M <= 64, D % M == 0 and (D / M) % 16 == 0"); return 1; }
+    hipLaunchKernelGGL(pq_encode_kernel, dim3((unsigned)((n + PE_R - 1) / PE_R)), dim3(256), 0, (hipStream_t)stream, x_dev, n, D, cb_dev,
+                       cnorm_dev, M, code_dev, bad_dev);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+extern "C" int sylber_pq_decode(const uint8_t* code_dev, int32_t n, const float* cb_dev, int32_t M, int32_t D, float* out_dev, void* stream) {
+    static const char* what = "sylber_pq_decode";
+    if (!code_dev || !cb_dev || !out_dev) { syl_set_error(what, "null argument"); return 1; }
+    if (n < 1) { syl_set_error(what, "need n >= 1"); return 1; }
+    if (!pq_geometry(D, M)) { syl_set_error(what, "need 1 <= M <= 64, D % M == 0 and (D / M) % 16 == 0"); return 1; }
+    const int64_t quads = (int64_t)n * D / 4, blocks = (quads + 255) / 256;
+    if (blocks > INT32_MAX) { syl_set_error(what, "n x D is too large: decode in pieces"); return 1; }
+    hipLaunchKernelGGL(pq_decode_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, code_dev, quads, cb_dev, M, D, out_dev);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+extern "C" int sylber_pq_lut(const float* q_dev, int32_t n, int32_t D, const float* cb_dev, const float* cnorm_dev, int32_t M, int32_t metric,
+                             float* lut_dev, void* stream) {
+    static const char* what = "sylber_pq_lut";
+    if (!q_dev || !cb_dev || !lut_dev) { syl_set_error(what, "null argument"); return 1; }
+    if (n < 1) { syl_set_error(what, "need n >= 1"); return 1; }
+    if (!pq_geometry(D, M)) { syl_set_error(what, "need 1 <= M <= 64, D % M == 0 and (D / M) % 16 == 0"); return 1; }
+    if (metric != SYLBER_KNN_L2 && metric != SYLBER_KNN_IP) { syl_set_error(what, "unknown metric"); return 1; }
+    if (metric == SYLBER_KNN_L2 && !cnorm_dev) { syl_set_error(what, "the L2 metric needs cnorm_dev"); return 1; }
+    if ((int64_t)n * M > INT32_MAX) { syl_set_error(what, "n x M is too large: use smaller query chunks"); return 1; }
+    hipLaunchKernelGGL(pq_lut_kernel, dim3((unsigned)((int64_t)n * M)), dim3(PQ_KSUB), 0, (hipStream_t)stream, q_dev, D, cb_dev,
+                       metric == SYLBER_KNN_L2 ? cnorm_dev : nullptr, M, lut_dev);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+extern "C" int64_t sylber_pq_workspace_bytes(int32_t n, int32_t N, int32_t M, int32_t m, int32_t splits) {
+    if (n < 1 || N < 1 || M < 1 || M > PQ_MAX_M || m < 1 || m > KN_KMAX) return -1;
+    const int64_t S = pq_scan_splits(n, N, pq_block_queries(M, m), splits), S2 = (S + 1) / 2;
+    // scores [n][S][m] | rows [n][S][m] | scores [n][ceil(S/2)][m] | rows [n][ceil(S/2)][m]
+    return 2 * pq_al((int64_t)n * S * m * 4) + 2 * pq_al((int64_t)n * S2 * m * 4);
+}
+
+extern "C" int sylber_pq_scan(const float* lut_dev, int32_t n, const uint8_t* code_dev, const uint8_t* bad_dev, int32_t N, int32_t M, int32_t m,
+                              const int32_t* q_group_dev, const int32_t* db_group_dev, int32_t splits, float* t_dev, int32_t* cand_dev,
+                              void* workspace_dev, void* stream) {
+    static const char* what = "sylber_pq_scan";
+    hipStream_t s = (hipStream_t)stream;
+    if (!lut_dev || !code_dev || !t_dev || !cand_dev || !workspace_dev) { syl_set_error(what, "null argument"); return 1; }
+    if (n < 1 || N < 1) { syl_set_error(what, "need n, N >= 1"); return 1; }
+    if (M < 1 || M > PQ_MAX_M) { syl_set_error(what, "need 1 <= M <= 64"); return 1; }
+    if (m < 1 || m > KN_KMAX) { syl_set_error(what, "need 1 <= m <= 128"); return 1; }
+    if (!q_group_dev != !db_group_dev) { syl_set_error(what, "q_group_dev and db_group_dev go together"); return 1; }
+    const int QB = pq_block_queries(M, m);
+    const int S = pq_scan_splits(n, N, QB, splits), S2 = (S + 1) / 2;
+    char* w = (char*)workspace_dev;
+    float* s0 = (float*)w; w += pq_al((int64_t)n * S * m * 4);
+    int32_t* i0 = (int32_t*)w; w += pq_al((int64_t)n * S * m * 4);
+    float* s1 = (float*)w; w += pq_al((int64_t)n * S2 * m * 4);
+    int32_t* i1 = (int32_t*)w;
+    int rc = 1;
+    switch (QB) {
+        case 8: rc = pq_launch_scan_vec<8>(M, lut_dev, n, code_dev, bad_dev, N, M, m, q_group_dev, db_group_dev, S, s0, i0, s); break;
+        case 6: rc = pq_launch_scan_vec<6>(M, lut_dev, n, code_dev, bad_dev, N, M, m, q_group_dev, db_group_dev, S, s0, i0, s); break;
+        case 4: rc = pq_launch_scan_vec<4>(M, lut_dev, n, code_dev, bad_dev, N, M, m, q_group_dev, db_group_dev, S, s0, i0, s); break;
+        case 3: rc = pq_launch_scan_vec<3>(M, lut_dev, n, code_dev, bad_dev, N, M, m, q_group_dev, db_group_dev, S, s0, i0, s); break;
+        case 2: rc = pq_launch_scan_vec<2>(M, lut_dev, n, code_dev, bad_dev, N, M, m, q_group_dev, db_group_dev, S, s0, i0, s); break;
+        default: rc = pq_launch_scan_vec<1>(M, lut_dev, n, code_dev, bad_dev, N, M, m, q_group_dev, db_group_dev, S, s0, i0, s); break;
+    }
+    if (rc) return rc;
+    float* cs = s0; int32_t* ci = i0;
+    float* os = s1; int32_t* oi = i1;
+    for (int l = S; l > 1; l = (l + 1) / 2) {
+        hipLaunchKernelGGL(knn_merge_kernel, dim3((unsigned)n, (unsigned)((l + 1) / 2)), dim3(64), 0, s, cs, ci, l, m, os, oi);
+        HIP_TRY(hipGetLastError());
+        float* ts = cs; cs = os; os = ts;
+        int32_t* ti = ci; ci = oi; oi = ti;
+    }
+    const int64_t tot = (int64_t)n * m;
+    hipLaunchKernelGGL(pq_cand_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, cs, ci, tot, t_dev, cand_dev);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
