@@ -545,8 +545,20 @@ int sylber_condition_features(sylber_mlp_t m, const float* features_dev, int32_t
  *                       row of the 16-bit buffer widened exactly (hi + lo for SYLBER_SPLIT16); rows at or past (Lmax - 10) / 5 + 1 are +0
  *   SYLBER_TAP_PROJ     the projected residual stream x, frames at or past an utterance's valid count zeroed: [B, T, 768]
  *   SYLBER_TAP_POSCONV  x + GELU(pos-conv(x)), the input of the encoder LayerNorm: [B, T, 768]
- * Any other negative stage is refused. */
+ * Taps inside encoder layer l: stage SYLBER_TAP_LAYER(l, k) = -(8 (l + 1) + k) ends the forward after one launch of the layer and returns
+ * frames [0, T) of every utterance as fp32 [B, T, W]; 16-bit buffers are widened exactly (hi + lo for SYLBER_SPLIT16):
+ *   k = SYLBER_LTAP_QKV       after the q / k / v projection: q | k | v in natural order (head-major q / k and the key-permuted V^T
+ *                             gathered back), q as stored, i.e. pre-scaled by log2(e) / 8 in the 16-bit modes            W = 2304
+ *       SYLBER_LTAP_CTX       after the attention: the context                                                           W = 768
+ *       SYLBER_LTAP_ATTN_SUM  after the out-projection: bias + residual added, the input of LayerNorm 1                  W = 768
+ *       SYLBER_LTAP_LN1       after LayerNorm 1: the FFN's operand                                                       W = 768
+ *       SYLBER_LTAP_FFN1      after FFN1 (GELU applied)                                                                  W = 3072
+ *       SYLBER_LTAP_FFN2_SUM  after FFN2: bias + residual added, the input of LayerNorm 2 (whose output is stage 3 + l)  W = 768
+ *   Refused for l >= num_layers, for the SYLBER_FP8 precision and (like every stop stage) by sylber_forward_packed.
+ * Any other negative stage (-4 .. -7, k = 6, 7) is refused. */
 enum { SYLBER_TAP_CONV0 = -1, SYLBER_TAP_PROJ = -2, SYLBER_TAP_POSCONV = -3 };
+enum { SYLBER_LTAP_QKV = 0, SYLBER_LTAP_CTX = 1, SYLBER_LTAP_ATTN_SUM = 2, SYLBER_LTAP_LN1 = 3, SYLBER_LTAP_FFN1 = 4, SYLBER_LTAP_FFN2_SUM = 5 };
+#define SYLBER_TAP_LAYER(l, k) (-(8 * ((l) + 1) + (k)))
 int sylber_set_stop_stage(sylber_t h, int32_t stage);
 /* per-kernel device time of the last forward, measured with HIP events on the launch stream.
  * names/ms arrays of capacity cap; returns the number of entries (<=cap) or <0 on error. */

@@ -183,10 +183,19 @@ DEV_EXPORTS = {
     "sylber_debug_conv0_scale_shift": (c_int, [c_void_p, c_int32, c_void_p]),
 }
 OPT_GEMM_TILE, OPT_ATTN_QUERIES_PER_WAVE, OPT_GEMM_PERSISTENT = 1, 2, 3
-OPT_CONV0_VALU = 5
+OPT_FUSE_OUTPROJ_LN, OPT_CONV0_VALU = 4, 5
 OPT_FP8_ATTENTION, OPT_SEGMENT, OPT_PER_UTTERANCE = 7, 9, 14
 # negative stop stages of sylber_set_stop_stage: taps inside the front half (include/sylber_hip.h SYLBER_TAP_*)
 TAP_CONV0, TAP_PROJ, TAP_POSCONV = -1, -2, -3
+# taps inside encoder layer l (SYLBER_TAP_LAYER / SYLBER_LTAP_*): the forward ends after launch k of the layer
+LTAP_QKV, LTAP_CTX, LTAP_ATTN_SUM, LTAP_LN1, LTAP_FFN1, LTAP_FFN2_SUM = 0, 1, 2, 3, 4, 5
+LTAP_WIDTH = {LTAP_QKV: 2304, LTAP_CTX: 768, LTAP_ATTN_SUM: 768, LTAP_LN1: 768, LTAP_FFN1: 3072, LTAP_FFN2_SUM: 768}
+
+
+def TAP_LAYER(l: int, k: int) -> int:
+    """the stop stage of tap k (LTAP_*) of encoder layer l"""
+    return -(8 * (int(l) + 1) + int(k))
+
 
 _LIB = None
 

@@ -188,7 +188,15 @@ extern "C" void sylber_destroy(sylber_t c) {
 
 extern "C" int sylber_set_stop_stage(sylber_t c, int32_t stage) {
     if (!c) return 1;
-    if (stage < SYLBER_TAP_POSCONV) { syl_set_error("sylber_set_stop_stage", "unknown tap (negative stages: -1 conv0, -2 projection, -3 pos-conv)"); return 1; }
+    if (stage < SYLBER_TAP_POSCONV) {
+        // SYLBER_TAP_LAYER(l, k) = -(8 (l + 1) + k)
+        const int n = -stage, l = n / 8 - 1, k = n % 8;
+        if (l < 0 || k > SYLBER_LTAP_FFN2_SUM) {
+            syl_set_error("sylber_set_stop_stage", "unknown tap (negative stages: -1 conv0, -2 projection, -3 pos-conv, -(8 (l + 1) + k) tap k = 0..5 of layer l)"); return 1;
+        }
+        if (l >= c->num_layers) { syl_set_error("sylber_set_stop_stage", "layer tap: the handle has no such layer"); return 1; }
+        if (c->precision == SYLBER_FP8) { syl_set_error("sylber_set_stop_stage", "layer taps are not available in the fp8 precision"); return 1; }
+    }
     c->stop_stage = stage;
     return 0;
 }

@@ -324,18 +324,23 @@ struct PackedCall {
 
 // the taps in front of the encoder LayerNorm (SYLBER_TAP_PROJ / SYLBER_TAP_POSCONV): frames [0, T) of every utterance of an fp32
 // [B][Tp][768] workspace tensor, compacted to [B][T][768].  Copies, so a tap call is never captured into a graph (sylber_forward).
-static int copy_frames_f32(const float* src, float* dst, int B, int Tp, int T, hipStream_t s) {
+static int copy_frames_f32(const float* src, float* dst, int B, int Tp, int T, hipStream_t s, int W = SYL_HIDDEN) {
     for (int b = 0; b < B; ++b)
-        HIP_TRY(hipMemcpyAsync(dst + (size_t)b * T * SYL_HIDDEN, src + (size_t)b * Tp * SYL_HIDDEN, (size_t)T * SYL_HIDDEN * 4,
-                               hipMemcpyDeviceToDevice, s));
+        HIP_TRY(hipMemcpyAsync(dst + (size_t)b * T * W, src + (size_t)b * Tp * W, (size_t)T * W * 4, hipMemcpyDeviceToDevice, s));
     return 0;
 }
+
+// the taps inside an encoder layer (SYLBER_TAP_LAYER(l, k) = -(8 (l + 1) + k)): the layer and the launch a call stops behind
+struct LayerTap {
+    int l = -1, k = -1;
+    explicit LayerTap(int stop_stage) { if (stop_stage <= -8) { l = -stop_stage / 8 - 1; k = -stop_stage % 8; } }
+};
 
 // every kernel launch of the bf16 / fp16 / mixed16 / split16 / fp8 forward, in stream order; nothing else (no allocation, copy or
 // synchronisation), so the sequence can be replayed from a captured hipGraph.  pk: a packed batch (bf16 / fp16), nullptr for the padded
 // one; only conv0, the zeroing of the slot tails, the pos-conv and the attention read its tables.
-// The one exception: with a negative stop stage (a tap) run() ends in device-to-device copies (copy_frames_f32); sylber_forward never
-// captures such a call and sylber_forward_packed refuses it.
+// The one exception: with a negative stop stage (a tap) run() ends in device-to-device copies (copy_frames_f32) or a widening copy
+// kernel; sylber_forward never captures such a call and sylber_forward_packed refuses it.
 struct Forward {
     sylber_ctx* c; const Plan& p; const float* wav_dev; float* hidden_dev; hipStream_t s; const PackedCall* pk;
     const Ws<bf16_t> w; const WsF8 w8;
@@ -347,11 +352,13 @@ struct Forward {
     // the residual of every block is the previous LayerNorm's output; it is re-derived in the GEMM epilogue from
     // the pre-LN sum still sitting in `pre` (updated in place) + that LayerNorm's row statistics and affine
     const float *res_g = nullptr, *res_b = nullptr;
+    const LayerTap tap;                                 // a tap inside a layer: layer16 sets `tapped` once it has copied it out
+    bool tapped = false;
 
     Forward(sylber_ctx* c_, const Plan& p_, const float* wav, float* hidden, hipStream_t s_, const PackedCall* pk_)
         : c(c_), p(p_), wav_dev(wav), hidden_dev(hidden), s(s_), pk(pk_), w(c_->ws, p_), w8(w, p_), B(p_.B), M(p_.B * p_.Tp),
           split(c_->precision == SYLBER_SPLIT16), f8(c_->precision == SYLBER_FP8),
-          aud_c(c_->opt_audit16 && c_->fmt_conv == FMT_F16), aud_e(c_->opt_audit16 && c_->fmt == FMT_F16) {}
+          aud_c(c_->opt_audit16 && c_->fmt_conv == FMT_F16), aud_e(c_->opt_audit16 && c_->fmt == FMT_F16), tap(c_->stop_stage) {}
 
     // conv layer 0 + GroupNorm + GELU
     int conv0() {
@@ -444,8 +451,16 @@ struct Forward {
         return 0;
     }
 
-    // one post-LN encoder layer on 16-bit operands
-    int layer16(const LayerDev& d, bool last) {
+    // a layer tap: frames [0, T) of a 16-bit workspace buffer [B][Tp][W], widened exactly, or of the fp32 pre-LayerNorm sums
+    int tap_rows16(const bf16_t* buf, long lo, int W) {
+        tapped = true;
+        RUN("copy_out", launch_bf16_to_f32_rows(buf, W, hidden_dev, B, p.Tp, p.T, W, s, c->fmt, lo));
+        return 0;
+    }
+    int tap_pre() { tapped = true; return copy_frames_f32(w.pre, hidden_dev, B, p.Tp, p.T, s); }
+
+    // one post-LN encoder layer on 16-bit operands; tk: the layer tap to stop behind (-1: none)
+    int layer16(const LayerDev& d, bool last, int tk) {
         // one launch for q, k and v (N = 2304): the q / k thirds leave head-major, the v third transposed (EPI_QK)
         GemmArgs g = linear(w.h, p.lo_hbf, d.wqkv, d.bqkv, 2304, 768);
         g.out0 = w.q; g.out1 = w.k; g.out2 = w.vt; g.Tp = p.Tp; g.Tpv = p.Tpv; g.T = p.T; g.out_lo = p.lo_qk; g.out2_lo = p.lo_vt;
@@ -454,9 +469,15 @@ struct Forward {
         AUDIT(aud_e, AUD_Q, w.q, M, 768, 768);
         AUDIT(aud_e, AUD_K, w.k, M, 768, 768);
         AUDIT(aud_e, AUD_V, w.vt, (long)B * 768, p.Tp, p.Tpv);
+        if (tk == SYLBER_LTAP_QKV) {
+            tapped = true;
+            RUN("copy_out", launch_tap_qkv(w.q, w.k, w.vt, hidden_dev, B, p.T, p.Tp, p.Tpv, s, c->fmt, p.lo_qk, p.lo_vt));
+            return 0;
+        }
         if (pk) RUN("attention", launch_attention_packed(w.q, w.k, w.vt, pk->slot, pk->nclip, pk->total_qb, w.ctx, p.Tp, s, c->fmt));
         else RUN("attention", launch_attention(w.q, w.k, w.vt, w.valid, w.ctx, B, p.T, p.Tp, p.Tpv, c->opt_attn_qw, s, c->fmt, p.lo_qk, p.lo_vt, p.lo_ctx));
         AUDIT(aud_e, AUD_CTX, w.ctx, M, 768, 768);
+        if (tk == SYLBER_LTAP_CTX) return tap_rows16(w.ctx, p.lo_ctx, 768);
         GemmArgs o = linear(w.ctx, p.lo_ctx, d.wo, d.bo, 768, 768);
         residual(o, res_g, res_b);
         tune_from_options(c, o);
@@ -464,19 +485,24 @@ struct Forward {
         o.out1 = w.h; o.ln_stats_out = w.stats; o.ln_gamma_out = d.ln1w; o.ln_beta_out = d.ln1b;
         if (!split && c->opt_fuse_ln > 0 && gemm_rowln_applicable(o)) {      // measured: faster as a pair, slower with two batches in flight
             RUN("gemm_out_ln", launch_gemm_rowln(o, s));
+            if (tk == SYLBER_LTAP_ATTN_SUM) return tap_pre();
         } else {
             RUN("gemm_out", launch_gemm_bf16(EPI_F32_RESLN, o, s));
+            if (tk == SYLBER_LTAP_ATTN_SUM) return tap_pre();
             RUN("layernorm", layernorm(d.ln1w, d.ln1b, false));
         }
+        if (tk == SYLBER_LTAP_LN1) return tap_rows16(w.h, p.lo_hbf, 768);
         GemmArgs f1 = linear(w.h, p.lo_hbf, d.w1, d.b1, 3072, 768);
         f1.act = split ? ACT_GELU_ERF7 : ACT_GELU_FAST; f1.out0 = w.ffn; f1.ld0 = 3072; f1.out_lo = p.lo_ffn;
         tune_from_options(c, f1);
         RUN("gemm_ffn1", launch_gemm_bf16(EPI_BF16, f1, s));
         AUDIT(aud_e, AUD_FFN1, w.ffn, M, 3072, 3072);
+        if (tk == SYLBER_LTAP_FFN1) return tap_rows16(w.ffn, p.lo_ffn, 3072);
         GemmArgs f2 = linear(w.ffn, p.lo_ffn, d.w2, d.b2, 768, 3072);
         residual(f2, d.ln1w, d.ln1b);
         tune_from_options(c, f2);
         RUN("gemm_ffn2", launch_gemm_bf16(EPI_F32_RESLN, f2, s));
+        if (tk == SYLBER_LTAP_FFN2_SUM) return tap_pre();
         RUN("layernorm", layernorm(d.ln2w, d.ln2b, last));
         return 0;
     }
@@ -534,8 +560,8 @@ struct Forward {
         for (int l = 0; l < c->num_layers; ++l) {
             const LayerDev& d = c->L[l];
             const bool last = (l == c->num_layers - 1) || (c->stop_stage == 3 + l);
-            if (f8 ? layer8(d, last) : layer16(d, last)) return 1;
-            if (last) break;
+            if (f8 ? layer8(d, last) : layer16(d, last, l == tap.l ? tap.k : -1)) return 1;
+            if (last || tapped) break;
             res_g = d.ln2w; res_b = d.ln2b;
         }
         return 0;
@@ -548,9 +574,11 @@ struct ForwardF32 {
     const Ws<float> w;
     const int B, M;
     const float* feats = nullptr;                       // the conv stack's output [B*Tp][512]
+    const LayerTap tap;                                 // a tap inside a layer: layer() sets `tapped` once it has copied it out
+    bool tapped = false;
 
     ForwardF32(sylber_ctx* c_, const Plan& p_, const float* wav, float* hidden, hipStream_t s_)
-        : c(c_), p(p_), wav_dev(wav), hidden_dev(hidden), s(s_), w(c_->ws, p_), B(p_.B), M(p_.B * p_.Tp) {}
+        : c(c_), p(p_), wav_dev(wav), hidden_dev(hidden), s(s_), w(c_->ws, p_), B(p_.B), M(p_.B * p_.Tp), tap(c_->stop_stage) {}
 
     int conv0() {
         const int* rows0 = c->opt_per_utt ? w.rows : nullptr;
@@ -599,20 +627,30 @@ struct ForwardF32 {
         return launch_layernorm(a, s);
     }
 
+    // a layer tap: frames [0, T) of an fp32 workspace tensor [B][Tp][W] (q | k | v are stored in natural order, q unscaled)
+    int tap_rows(const float* buf, int W) { tapped = true; return copy_frames_f32(buf, hidden_dev, B, p.Tp, p.T, s, W); }
+
     int layer(int l, bool last) {
         const LayerDev& d = c->L[l];
+        const int tk = l == tap.l ? tap.k : -1;         // the layer tap to stop behind (-1: none)
         RUN("gemm_f32", launch_gemm_f32(linear(w.h, c->L32[l].wqkv, d.bqkv, w.q, 2304, 768), s));
+        if (tk == SYLBER_LTAP_QKV) return tap_rows(w.q, 2304);
         RUN("attention_f32", launch_attention_f32(w.q, w.q + 768, w.q + 1536, w.valid, w.ctx, B, p.T, p.Tp, s));
+        if (tk == SYLBER_LTAP_CTX) return tap_rows(w.ctx, 768);
         GemmArgsF32 o = linear(w.ctx, c->L32[l].wo, d.bo, w.pre, 768, 768);
         o.res = w.h; o.ldres = 768;
         RUN("gemm_f32", launch_gemm_f32(o, s));
+        if (tk == SYLBER_LTAP_ATTN_SUM) return tap_rows(w.pre, 768);
         RUN("layernorm", layernorm(d.ln1w, d.ln1b, false));
+        if (tk == SYLBER_LTAP_LN1) return tap_rows(w.h, 768);
         GemmArgsF32 f1 = linear(w.h, c->L32[l].w1, d.b1, w.ffn, 3072, 768);
         f1.act = 1;
         RUN("gemm_f32", launch_gemm_f32(f1, s));
+        if (tk == SYLBER_LTAP_FFN1) return tap_rows(w.ffn, 3072);
         GemmArgsF32 f2 = linear(w.ffn, c->L32[l].w2, d.b2, w.pre, 768, 3072);
         f2.res = w.h; f2.ldres = 768;
         RUN("gemm_f32", launch_gemm_f32(f2, s));
+        if (tk == SYLBER_LTAP_FFN2_SUM) return tap_rows(w.pre, 768);
         RUN("layernorm", layernorm(d.ln2w, d.ln2b, last));
         return 0;
     }
@@ -639,7 +677,7 @@ struct ForwardF32 {
         for (int l = 0; l < c->num_layers; ++l) {
             const bool last = (l == c->num_layers - 1) || (c->stop_stage == 3 + l);
             if (layer(l, last)) return 1;
-            if (last) break;
+            if (last || tapped) break;
         }
         return 0;
     }

@@ -162,6 +162,37 @@ __global__ void pack_qkv_kernel(const float* __restrict__ q, const float* __rest
     }
 }
 
+// The layer tap SYLBER_LTAP_QKV (forward.hip): what EPI_QK left in the workspace, back in natural order and widened exactly.  q / k
+// [B][12][Tp][64] head-major, V^T [B][12][64][Tpv] with bits 2 and 3 of the key index swapped (attention.hip) -> out [B][T][2304] =
+// q | k | v of frames [0, T); FMT_SPLIT adds the lo planes lo_qk / lo_vt elements on.  pos < Tp: the swap stays inside a 16-key group
+// and Tp is a multiple of 32.
+__global__ __launch_bounds__(256) void tap_qkv_kernel(const bf16_t* __restrict__ q, const bf16_t* __restrict__ k, const bf16_t* __restrict__ vt,
+                                                      float* __restrict__ out, int T, int Tp, int Tpv, int fmt, long lo_qk, long lo_vt) {
+    const int b = blockIdx.y, t = blockIdx.x;
+    const int pos = (t & ~12) | ((t & 4) << 1) | ((t & 8) >> 1);
+    float* dst = out + ((size_t)b * T + t) * (3 * SYL_HIDDEN);
+    for (int c = threadIdx.x; c < SYL_HIDDEN; c += 256) {
+        const int head = c >> 6, d = c & 63;
+        const size_t hm = (((size_t)b * SYL_HEADS + head) * Tp + t) * 64 + d;
+        const size_t vi = (((size_t)b * SYL_HEADS + head) * 64 + d) * Tpv + pos;
+        if (fmt == FMT_SPLIT) {
+            dst[c] = H16<FMT_F16>::up(q[hm]) + H16<FMT_F16>::up(q[lo_qk + hm]);
+            dst[SYL_HIDDEN + c] = H16<FMT_F16>::up(k[hm]) + H16<FMT_F16>::up(k[lo_qk + hm]);
+            dst[2 * SYL_HIDDEN + c] = H16<FMT_F16>::up(vt[vi]) + H16<FMT_F16>::up(vt[lo_vt + vi]);
+        } else if (fmt == FMT_F16) {
+            dst[c] = H16<FMT_F16>::up(q[hm]); dst[SYL_HIDDEN + c] = H16<FMT_F16>::up(k[hm]); dst[2 * SYL_HIDDEN + c] = H16<FMT_F16>::up(vt[vi]);
+        } else {
+            dst[c] = bf2f(q[hm]); dst[SYL_HIDDEN + c] = bf2f(k[hm]); dst[2 * SYL_HIDDEN + c] = bf2f(vt[vi]);
+        }
+    }
+}
+int launch_tap_qkv(const bf16_t* q, const bf16_t* k, const bf16_t* vt, float* out, int B, int T, int Tp, int Tpv, hipStream_t s, int fmt, long lo_qk, long lo_vt) {
+    if (T < 1 || T > Tp || Tp % 32 != 0 || Tpv < Tp) { syl_set_error("launch_tap_qkv", "need 1 <= T <= Tp, Tp % 32 == 0, Tpv >= Tp"); return 1; }
+    hipLaunchKernelGGL(tap_qkv_kernel, dim3(T, B), dim3(256), 0, s, q, k, vt, out, T, Tp, Tpv, fmt, lo_qk, lo_vt);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
 // q,k [B,T,768] f32 -> MXFP8 head-major q (x0.125), k: e4m3 [B,H,Tp,64] + one E8M0 scale per 32 features [B,H,Tp,2].
 // One 32-lane group per (token, head, 32-feature block).
 __global__ void pack_qk_f8_kernel(const float* __restrict__ q, const float* __restrict__ k, uint8_t* __restrict__ q8, uint8_t* __restrict__ qs,

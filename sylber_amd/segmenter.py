@@ -353,12 +353,15 @@ class HubertEncoderHIP:
         ``stop_stage`` (include/sylber_hip.h sylber_set_stop_stage): 1 returns the conv features [B, T, 512], 2 / 3 + l the stream after
         the encoder LayerNorm / layer l.  Negative values are the taps of the front half: ``_lib.TAP_CONV0`` conv layer 0 alone,
         [B, 64 * padded_frames(Lmax), 512] (every row of its buffer); ``_lib.TAP_PROJ`` the projected residual stream and
-        ``_lib.TAP_POSCONV`` the encoder LayerNorm's input, both [B, T, 768]."""
+        ``_lib.TAP_POSCONV`` the encoder LayerNorm's input, both [B, T, 768].  ``_lib.TAP_LAYER(l, k)`` is tap k (``_lib.LTAP_*``)
+        inside encoder layer l: [B, T, _lib.LTAP_WIDTH[k]] (2304 = q | k | v, 3072 for FFN1, else 768)."""
         assert wav.is_cuda and wav.dtype == torch.float32 and wav.dim() == 2 and wav.is_contiguous()
         B, Lmax = wav.shape
         T = self.num_frames(Lmax)
         if stop_stage == _lib.TAP_CONV0:
             shape = (B, 64 * self.padded_frames(Lmax), 512)
+        elif stop_stage <= -8:
+            shape = (B, T, _lib.LTAP_WIDTH.get(-stop_stage % 8, 768))       # (an unknown k is refused by the library below)
         else:
             shape = (B, T, 512 if stop_stage == 1 else 768)
         if out is None:

@@ -40,6 +40,13 @@ def test_front_half_taps_are_declared_on_both_sides(lib):
     ids = {k: int(v) for k, v in re.findall(r"\b(SYLBER_TAP_[A-Z0-9]+)\s*=\s*(-?\d+)", hdr)}
     assert ids == {"SYLBER_TAP_CONV0": _lib.TAP_CONV0, "SYLBER_TAP_PROJ": _lib.TAP_PROJ, "SYLBER_TAP_POSCONV": _lib.TAP_POSCONV}
     assert sorted(ids.values()) == [-3, -2, -1]
+    # the taps inside an encoder layer: SYLBER_TAP_LAYER(l, k) = -(8 (l + 1) + k) with the k names of SYLBER_LTAP_*
+    ltap = {k: int(v) for k, v in re.findall(r"\b(SYLBER_LTAP_[A-Z0-9_]+)\s*=\s*(\d+)", hdr)}
+    assert ltap == {"SYLBER_LTAP_QKV": _lib.LTAP_QKV, "SYLBER_LTAP_CTX": _lib.LTAP_CTX, "SYLBER_LTAP_ATTN_SUM": _lib.LTAP_ATTN_SUM,
+                    "SYLBER_LTAP_LN1": _lib.LTAP_LN1, "SYLBER_LTAP_FFN1": _lib.LTAP_FFN1, "SYLBER_LTAP_FFN2_SUM": _lib.LTAP_FFN2_SUM}
+    assert sorted(ltap.values()) == list(range(6)) and sorted(_lib.LTAP_WIDTH) == list(range(6))
+    assert re.search(r"#define\s+SYLBER_TAP_LAYER\(l,\s*k\)\s+\(-\(8\s*\*\s*\(\(l\)\s*\+\s*1\)\s*\+\s*\(k\)\)\)", hdr)
+    assert _lib.TAP_LAYER(0, 0) == -8 and _lib.TAP_LAYER(1, 5) == -21
     assert "sylber_debug_conv0_scale_shift" in _lib.DEV_EXPORTS and "sylber_debug_conv0_scale_shift" not in _lib.EXPORTS
     dev = open(os.path.join(ROOT, "include", "sylber_hip_dev.h")).read()
     assert re.search(r"int\s+sylber_debug_conv0_scale_shift\s*\(\s*sylber_t\s+h\s*,\s*int32_t\s+B\s*,\s*float\s*\*\s*out_host\s*\)", dev)
