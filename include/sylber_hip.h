@@ -314,6 +314,25 @@ int sylber_ivf_search(const float* q_dev, int32_t n, int32_t D, int32_t nprobe, 
                       int32_t metric, int32_t k, const int32_t* q_group_dev, const int32_t* row_group_dev, float* score_dev,
                       int64_t* idx_dev, void* workspace_dev, void* stream);
 
+/* Compressed inverted-file search (sylber_amd/pq.py: IVFPQSyllableIndex): sylber_pq_scan restricted, per query, to the rows of the
+ * lists it probes.  The codes lie list by list in code_dev [N_listed, M] (list l = positions list_offsets_dev[l] ..
+ * list_offsets_dev[l + 1], ascending original id within a list; 16-byte aligned); row_id_dev [N_listed] maps a position to the row's
+ * original id; bad_dev (may be null: no mask) and row_group_dev are in position order too.  The codes are those of the rows
+ * themselves (sylber_pq_encode), not of residuals, so lut_dev [n, M, 256] is sylber_pq_lut's table: one per query for all its lists.
+ * sylber_ivfpq_scan: probe_dev [n, nprobe] int32 names the lists of each query (1 <= nprobe <= 128; an entry outside [0, nlist) names
+ *   none).  t(i, j) is sylber_pq_scan's sum.  The candidates of query i are the m best (1 <= m <= 128) admissible rows of its lists
+ *   under the strict order (t, original id): t_dev / cand_dev [n, m] (original ids), best first, padded with (+inf, -1).  A NaN t, a
+ *   masked row and, with both group arrays, a row of the query's group are not admissible.  With every list probed the result is
+ *   sylber_pq_scan's on the same rows, bit for bit.  Bitwise independent of splits (0 = automatic: about 512 workgroups, at most
+ *   nprobe per query), of how the queries are chunked and of what the workspace held.  No host work: one workgroup per (query, split
+ *   of its probe slots) reads the lists' bounds on the device.  workspace_dev: sylber_ivfpq_workspace_bytes(n, nprobe, m, splits)
+ *   bytes (-1 for arguments that sylber_ivfpq_scan refuses). */
+int64_t sylber_ivfpq_workspace_bytes(int32_t n, int32_t nprobe, int32_t m, int32_t splits);
+int sylber_ivfpq_scan(const float* lut_dev, int32_t n, const int32_t* probe_dev, int32_t nprobe, const int32_t* list_offsets_dev,
+                      int32_t nlist, const uint8_t* code_dev, const uint8_t* bad_dev, const int32_t* row_id_dev, int32_t N_listed, int32_t M,
+                      int32_t m, const int32_t* q_group_dev, const int32_t* row_group_dev, int32_t splits, float* t_dev, int32_t* cand_dev,
+                      void* workspace_dev, void* stream);
+
 /* Phrase search (sylber_amd/search.py: SyllableIndex.search_phrases): query-by-example subsequence DTW of syllable sequences
  * (phrases, 1 <= m <= 64 rows) against every sequence of the database (runs of consecutive rows, at most 65 536 rows each).
  * Local cost of phrase row i against database row j, in fp32, from the score s = fmaf(-2, q_i . x_j, c_j) of sylber_knn_search

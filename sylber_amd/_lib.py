@@ -124,6 +124,9 @@ EXPORTS = {
     "sylber_ivf_workspace_bytes": (c_int64, [c_int32, c_int32, c_int32, c_int32]),
     "sylber_ivf_search": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p,
                                   c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "sylber_ivfpq_workspace_bytes": (c_int64, [c_int32, c_int32, c_int32, c_int32]),
+    "sylber_ivfpq_scan": (c_int, [c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_int32,
+                                  c_int32, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
     "sylber_dtw_plan": (c_int32, [POINTER(c_int32), c_int32, POINTER(c_int32), c_int32, c_int32, c_int32, c_int32, POINTER(c_int32), c_int32,
                                   POINTER(c_int32), POINTER(c_int32), POINTER(c_int32)]),
     "sylber_dtw_workspace_bytes": (c_int64, [c_int32, c_int32, c_int32, c_int32]),

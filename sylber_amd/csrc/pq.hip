@@ -12,6 +12,8 @@
 //     list (kn_insert); the per-split lists are merged with knn_lists.h.  The table gather is a random 4-byte LDS read inside a 1 KiB
 //     region: bank conflicts of a few ways are part of the algorithm (any layout that avoids them changes the add order).
 //   * pq_decode_kernel: out[j][slice m] = C[m][code[j][m]].
+//   * ivfpq_scan_kernel (IVFPQSyllableIndex): the same t over the codes of the lists a query probes only; a workgroup holds ONE query's
+//     table and walks the lists of one split of the query's probe slots; the order is (t, original id).
 #include "kernels.h"
 #include "../../include/sylber_hip.h"
 #include "knn_tile.h"
@@ -355,6 +357,172 @@ extern "C" int sylber_pq_scan(const float* lut_dev, int32_t n, const uint8_t* co
         int32_t* ti = ci; ci = oi; oi = ti;
     }
     const int64_t tot = (int64_t)n * m;
+    hipLaunchKernelGGL(pq_cand_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, cs, ci, tot, t_dev, cand_dev);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// ---- scan of the probed lists (IVF-PQ) -------------------------------------------------------------------------------------------
+// One workgroup per (query, split of its probe slots): a table is fetched once per split, whatever lists the query probes, and the
+// codes of lists that many queries probe come from L2 / Infinity Cache.
+constexpr int IPQ_T = 512;                                 // threads = code rows of a tile.  LDS of a workgroup: the table (M KiB) + two
+                                                           // strips (4 KiB) + the top list (8 m <= 1 KiB) + 16 bytes: 53 KiB at M = 48,
+                                                           // three workgroups per CU (159 KiB of 160) = 24 waves, six per SIMD for
+                                                           // the 4-byte gathers; 69 KiB at M = 64 (two workgroups, four waves per SIMD);
+                                                           // from M <= 35 on the 32 waves of a CU allow four workgroups
+constexpr int IPQ_LDS_FIXED = 16;                          // the two tile flags
+constexpr int IPQ_MAX_NPROBE = 128;
+
+static size_t ipq_lds_bytes(int M, int m) { return (size_t)M * PQ_KSUB * 4 + (size_t)IPQ_T * 8 + (size_t)m * 8 + IPQ_LDS_FIXED; }
+static int ipq_splits(int64_t n, int nprobe, int splits) {
+    int64_t S = splits > 0 ? splits : (PQ_TARGET_BLOCKS + n - 1) / n;
+    S = S < nprobe ? S : nprobe;
+    return (int)(S < 1 ? 1 : S);
+}
+
+// grid (n, S): split sp of query i walks the lists of its probe slots [sp * nprobe / S, (sp + 1) * nprobe / S), a list at a time in
+// tiles of IPQ_T positions (a slot < 0 or without rows costs nothing).  code / bad / rid / xgrp are in position order (list by list,
+// ascending original id within a list).  Writes the sorted best m (t, original id) of the split to ps / pi [n][S][m]; entries that
+// did not fill stay (+inf, INT_MAX).
+template <int VEC>
+__global__ __launch_bounds__(IPQ_T) void ivfpq_scan_kernel(const float* __restrict__ lut, const int32_t* __restrict__ probe, int nprobe,
+                                                          const int32_t* __restrict__ off, int nlist, const uint8_t* __restrict__ code,
+                                                          const uint8_t* __restrict__ bad, const int32_t* __restrict__ rid, int NL, int M,
+                                                          int m, const int32_t* __restrict__ qgrp, const int32_t* __restrict__ xgrp, int S,
+                                                          float* __restrict__ ps, int32_t* __restrict__ pi) {
+    extern __shared__ __attribute__((aligned(16))) float ipq_smem[];
+    const int tsz = M * PQ_KSUB;
+    float* tab = ipq_smem;                                 // [M][256] the query's table
+    float* strip = tab + tsz;                              // [IPQ_T] a flagged tile's scores (NaN = no candidate)
+    int* sid = (int*)(strip + IPQ_T);                      // [IPQ_T] their original ids
+    float* ls = (float*)(sid + IPQ_T);                     // [m] sorted scores
+    int* li = (int*)(ls + m);                              // [m] their original ids
+    int* flags = li + m;                                   // [2] by tile parity: the tile may hold a candidate
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int i = blockIdx.x, sp = blockIdx.y;
+    const int slo = (int)((int64_t)sp * nprobe / S), shi = (int)((int64_t)(sp + 1) * nprobe / S);
+    const float* src = lut + (size_t)i * tsz;
+    for (int e = tid * 4; e < tsz; e += IPQ_T * 4) *(float4*)(tab + e) = *(const float4*)(src + e);
+    for (int e = tid; e < m; e += IPQ_T) { ls[e] = INFINITY; li[e] = INT_MAX; }
+    if (tid < 2) flags[tid] = 0;
+    const int qg = qgrp ? qgrp[i] : 0;
+    __syncthreads();
+    int par = 0;
+    for (int slot = slo; slot < shi; ++slot) {
+        const int l = probe[(size_t)i * nprobe + slot];    // block-uniform
+        if (l < 0 || l >= nlist) continue;
+        const int lo = off[l], hi = off[l + 1];
+        if (lo < 0 || hi > NL || lo >= hi) continue;
+        for (int base = lo; base < hi; base += IPQ_T, par ^= 1) {
+            const int pos = base + tid;
+            const int r = pos < hi ? pos : hi - 1;
+            const uint8_t* cr = code + (size_t)r * M;
+            float t = -0.0f;                               // -0 + v = v for every v, -0 included: the sum starts at its first entry
+            for (int mb = 0; mb < M; mb += VEC) {
+                uint32_t w[4];
+                pq_load<VEC>(cr + mb, w);
+#pragma unroll
+                for (int b = 0; b < VEC; ++b) t += tab[(mb + b) * PQ_KSUB + ((w[b >> 2] >> (8 * (b & 3))) & 255u)];
+            }
+            // The order is (t, ORIGINAL id): positions ascend with the id inside a list, not across lists.  The id -- with the mask
+            // and the group -- is fetched for the rows that pass the threshold only: a superset of the exact (t, id) test (NaN
+            // never passes) that few rows pass once the list has filled, where a fetch for every row would add 9 bytes to the M
+            // bytes of each code row.
+            bool pass = pos < hi && t <= ls[m - 1];
+            int id = 0;
+            if (pass) {
+                pass = !(bad && bad[r]) && !(xgrp && xgrp[r] == qg);
+                if (pass) id = rid[r];
+            }
+            if (pass) flags[par] = 1;
+            __syncthreads();
+            if (!flags[par]) continue;                     // block-uniform; the next tile flags the other parity
+            strip[tid] = pass ? t : __builtin_nanf("");
+            sid[tid] = id;
+            __syncthreads();
+            if (tid == 0) flags[par] = 0;
+            if (wave == 0) {                               // one wave puts the survivors into the list one at a time
+                for (int h = 0; h < IPQ_T / 64; ++h) {
+                    uint64_t bal = __ballot(kn_better(strip[h * 64 + lane], sid[h * 64 + lane], ls[m - 1], li[m - 1]));
+                    while (bal) {
+                        const int c = __ffsll((unsigned long long)bal) - 1;
+                        bal &= bal - 1;
+                        kn_insert(ls, li, m, lane, strip[h * 64 + c], sid[h * 64 + c]);
+                    }
+                }
+            }
+            __syncthreads();                               // the list is complete before the next tile reads its threshold
+        }
+    }
+    const size_t o = ((size_t)i * S + sp) * m;
+    for (int e = tid; e < m; e += IPQ_T) { ps[o + e] = ls[e]; pi[o + e] = li[e]; }
+}
+
+template <int VEC>
+static int ipq_launch_scan(const float* lut, int n, const int32_t* probe, int nprobe, const int32_t* off, int nlist, const uint8_t* code,
+                           const uint8_t* bad, const int32_t* rid, int NL, int M, int m, const int32_t* qg, const int32_t* xg, int S,
+                           float* ps, int32_t* pi, hipStream_t s) {
+    static PerDeviceOnce once;
+    if (once.need())
+        HIP_TRY(hipFuncSetAttribute((const void*)ivfpq_scan_kernel<VEC>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    (int)ipq_lds_bytes(PQ_MAX_M, KN_KMAX)));
+    hipLaunchKernelGGL((ivfpq_scan_kernel<VEC>), dim3((unsigned)n, (unsigned)S), dim3(IPQ_T), ipq_lds_bytes(M, m), s, lut, probe, nprobe, off,
+                       nlist, code, bad, rid, NL, M, m, qg, xg, S, ps, pi);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+extern "C" int64_t sylber_ivfpq_workspace_bytes(int32_t n, int32_t nprobe, int32_t m, int32_t splits) {
+    if (n < 1 || nprobe < 1 || nprobe > IPQ_MAX_NPROBE || m < 1 || m > KN_KMAX || splits < 0) return -1;
+    const int64_t S = ipq_splits(n, nprobe, splits), S2 = (S + 1) / 2;
+    // scores [n][S][m] | ids [n][S][m] | scores [n][ceil(S/2)][m] | ids [n][ceil(S/2)][m]
+    return 2 * pq_al((int64_t)n * S * m * 4) + 2 * pq_al((int64_t)n * S2 * m * 4);
+}
+
+extern "C" int sylber_ivfpq_scan(const float* lut_dev, int32_t n, const int32_t* probe_dev, int32_t nprobe, const int32_t* list_offsets_dev,
+                                 int32_t nlist, const uint8_t* code_dev, const uint8_t* bad_dev, const int32_t* row_id_dev, int32_t N_listed,
+                                 int32_t M, int32_t m, const int32_t* q_group_dev, const int32_t* row_group_dev, int32_t splits, float* t_dev,
+                                 int32_t* cand_dev, void* workspace_dev, void* stream) {
+    static const char* what = "sylber_ivfpq_scan";
+    hipStream_t s = (hipStream_t)stream;
+    if (!lut_dev || !probe_dev || !list_offsets_dev || !code_dev || !row_id_dev || !t_dev || !cand_dev || !workspace_dev) {
+        syl_set_error(what, "null argument");
+        return 1;
+    }
+    if (n < 1) { syl_set_error(what, "need n >= 1"); return 1; }
+    if (M < 1 || M > PQ_MAX_M) { syl_set_error(what, "need 1 <= M <= 64"); return 1; }
+    if (m < 1 || m > KN_KMAX) { syl_set_error(what, "need 1 <= m <= 128"); return 1; }
+    if (nprobe < 1 || nprobe > IPQ_MAX_NPROBE) { syl_set_error(what, "need 1 <= nprobe <= 128"); return 1; }
+    if (nlist < 1) { syl_set_error(what, "need nlist >= 1"); return 1; }
+    if (N_listed < 0) { syl_set_error(what, "need N_listed >= 0"); return 1; }
+    if (!q_group_dev != !row_group_dev) { syl_set_error(what, "q_group_dev and row_group_dev go together"); return 1; }
+    if (splits < 0) { syl_set_error(what, "need splits >= 0"); return 1; }
+    const int S = ipq_splits(n, nprobe, splits), S2 = (S + 1) / 2;
+    char* w = (char*)workspace_dev;
+    float* s0 = (float*)w; w += pq_al((int64_t)n * S * m * 4);
+    int32_t* i0 = (int32_t*)w; w += pq_al((int64_t)n * S * m * 4);
+    float* s1 = (float*)w; w += pq_al((int64_t)n * S2 * m * 4);
+    int32_t* i1 = (int32_t*)w;
+    int rc;
+    if (M % 16 == 0)
+        rc = ipq_launch_scan<16>(lut_dev, n, probe_dev, nprobe, list_offsets_dev, nlist, code_dev, bad_dev, row_id_dev, N_listed, M, m,
+                                 q_group_dev, row_group_dev, S, s0, i0, s);
+    else if (M % 4 == 0)
+        rc = ipq_launch_scan<4>(lut_dev, n, probe_dev, nprobe, list_offsets_dev, nlist, code_dev, bad_dev, row_id_dev, N_listed, M, m,
+                                q_group_dev, row_group_dev, S, s0, i0, s);
+    else
+        rc = ipq_launch_scan<1>(lut_dev, n, probe_dev, nprobe, list_offsets_dev, nlist, code_dev, bad_dev, row_id_dev, N_listed, M, m,
+                                q_group_dev, row_group_dev, S, s0, i0, s);
+    if (rc) return rc;
+    float* cs = s0; int32_t* ci = i0;
+    float* os = s1; int32_t* oi = i1;
+    for (int l = S; l > 1; l = (l + 1) / 2) {
+        hipLaunchKernelGGL(knn_merge_kernel, dim3((unsigned)n, (unsigned)((l + 1) / 2)), dim3(64), 0, s, cs, ci, l, m, os, oi);
+        HIP_TRY(hipGetLastError());
+        float* ts = cs; cs = os; os = ts;
+        int32_t* ti = ci; ci = oi; oi = ti;
+    }
+    const int64_t tot = (int64_t)n * m;                    // the finish of sylber_pq_scan: the (+inf, INT_MAX) fillers become (+inf, -1)
     hipLaunchKernelGGL(pq_cand_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, cs, ci, tot, t_dev, cand_dev);
     HIP_TRY(hipGetLastError());
     return 0;

@@ -554,8 +554,14 @@ class IVFSyllableIndex:
         """``source``: a ``SyllableIndex`` (kept as ``ivf.index``, not copied) or ``[N, D]`` features (then ``groups``, ``metric`` and
         ``device`` make the index).  The centroids are ``fit_kmeans(rows, nlist, seed=, max_iter=, tol=, init_rows=train_rows)`` on the
         stored rows, or ``centroids [nlist, D]`` as given (finite).  ``ValueError`` for ``nlist < 1``, ``nlist > N`` or an empty index."""
-        from .kmeans import fit_kmeans
         index = source if isinstance(source, SyllableIndex) else SyllableIndex(source, metric=metric, groups=groups, device=device)
+        C = cls._train_centroids(index, nlist, centroids, seed, max_iter, tol, train_rows)
+        return cls(index, C, cls._assign(index._x, C))
+
+    @staticmethod
+    def _train_centroids(index: SyllableIndex, nlist, centroids, seed: int, max_iter: int, tol: float, train_rows) -> torch.Tensor:
+        """``[nlist, D]`` fp32 on the index's device: ``centroids`` as given (finite), or ``fit_kmeans`` on the stored rows"""
+        from .kmeans import fit_kmeans
         N = len(index)
         if N == 0:
             raise ValueError("the index is empty")
@@ -576,7 +582,7 @@ class IVFSyllableIndex:
             C = c.to(index.device, torch.float32).contiguous().clone()
             if not bool(torch.isfinite(C).all()):
                 raise ValueError("centroids hold non-finite values")
-        return cls(index, C, cls._assign(index._x, C))
+        return C
 
     @staticmethod
     def _assign(x: torch.Tensor, C: torch.Tensor) -> torch.Tensor:
