@@ -232,8 +232,6 @@ __global__ __launch_bounds__(256) void dtw_finish_kernel(const float* __restrict
     cost[e] = ls[e]; seq[e] = j; span[2 * e] = p.x; span[2 * e + 1] = (int64_t)p.y + 1;
 }
 
-static int64_t dt_al(int64_t bytes) { return (bytes + 255) / 256 * 256; }
-
 // Host only.  Packs the phrases, in order, into query blocks of 128 rows and cuts the database at sequence starts.
 extern "C" int32_t sylber_dtw_plan(const int32_t* seq_offsets_host, int32_t n_seq, const int32_t* phrase_len_host, int32_t n_phrases,
                                    int32_t k, int32_t splits, int32_t block_phrases, int32_t* cut_rows_host, int32_t cut_capacity,
@@ -292,7 +290,7 @@ extern "C" int64_t sylber_dtw_workspace_bytes(int32_t n_blocks, int32_t n_phrase
     if (n_blocks < 1 || n_phrases < 1 || k < 1 || k > KN_KMAX || cuts < 1) return -1;
     const int64_t L = (int64_t)n_phrases * cuts * k, L2 = (int64_t)n_phrases * ((cuts + 1) / 2) * k;
     // ||q||^2 [n_blocks * 128] | costs, sequences, spans [P][C][k] | the same [P][ceil(C / 2)][k]
-    return dt_al((int64_t)n_blocks * KN_BM * 4) + 2 * dt_al(L * 4) + dt_al(L * 8) + 2 * dt_al(L2 * 4) + dt_al(L2 * 8);
+    return kn_al((int64_t)n_blocks * KN_BM * 4) + 2 * kn_al(L * 4) + kn_al(L * 8) + 2 * kn_al(L2 * 4) + kn_al(L2 * 8);
 }
 
 extern "C" int sylber_dtw_search(const float* q_dev, int32_t n_blocks, const int32_t* row_meta_dev, const int32_t* slot_phrase_dev,
@@ -314,12 +312,12 @@ extern "C" int sylber_dtw_search(const float* q_dev, int32_t n_blocks, const int
     if ((int64_t)n_phrases * cuts * k > INT32_MAX / 2) { syl_set_error(what, "n_phrases x cuts x k is too large: use smaller phrase chunks"); return 1; }
     const int64_t L = (int64_t)n_phrases * cuts * k, L2 = (int64_t)n_phrases * ((cuts + 1) / 2) * k;
     char* w = (char*)workspace_dev;
-    float* qsq = (float*)w; w += dt_al((int64_t)n_blocks * KN_BM * 4);
-    float* s0 = (float*)w; w += dt_al(L * 4);
-    int32_t* i0 = (int32_t*)w; w += dt_al(L * 4);
-    int2* p0 = (int2*)w; w += dt_al(L * 8);
-    float* s1 = (float*)w; w += dt_al(L2 * 4);
-    int32_t* i1 = (int32_t*)w; w += dt_al(L2 * 4);
+    float* qsq = (float*)w; w += kn_al((int64_t)n_blocks * KN_BM * 4);
+    float* s0 = (float*)w; w += kn_al(L * 4);
+    int32_t* i0 = (int32_t*)w; w += kn_al(L * 4);
+    int2* p0 = (int2*)w; w += kn_al(L * 8);
+    float* s1 = (float*)w; w += kn_al(L2 * 4);
+    int32_t* i1 = (int32_t*)w; w += kn_al(L2 * 4);
     int2* p1 = (int2*)w;
     if (metric == SYLBER_KNN_L2 && launch_km_sqnorm(q_dev, qsq, n_blocks * KN_BM, D, s)) return 1;
     static PerDeviceOnce once;

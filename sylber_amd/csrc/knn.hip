@@ -329,8 +329,6 @@ static int kn_splits(int32_t n, int32_t N, int32_t splits) {
     return (int)(S < 1 ? 1 : S);
 }
 
-static int64_t kn_al(int64_t bytes) { return (bytes + 255) / 256 * 256; }
-
 extern "C" int32_t sylber_knn_splits(int32_t n, int32_t N, int32_t splits) {
     if (n < 1 || N < 1) return -1;
     return kn_splits(n, N, splits);
@@ -338,9 +336,7 @@ extern "C" int32_t sylber_knn_splits(int32_t n, int32_t N, int32_t splits) {
 
 extern "C" int64_t sylber_knn_workspace_bytes(int32_t n, int32_t N, int32_t D, int32_t k, int32_t splits) {
     if (n < 1 || N < 1 || D < 1 || k < 1 || k > KN_KMAX) return -1;
-    const int64_t S = kn_splits(n, N, splits), S2 = (S + 1) / 2;
-    // ||q||^2 [n] | scores [n][S][k] | indices [n][S][k] | scores [n][ceil(S/2)][k] | indices [n][ceil(S/2)][k]
-    return kn_al((int64_t)n * 4) + 2 * kn_al((int64_t)n * S * k * 4) + 2 * kn_al((int64_t)n * S2 * k * 4);
+    return kn_al((int64_t)n * 4) + kn_partials_bytes(n, kn_splits(n, N, splits), k);      // ||q||^2 [n] | the S partial lists (KnPartials)
 }
 
 extern "C" int sylber_knn_row_norms(const float* x_dev, int32_t n, int32_t D, float* out_dev, void* stream) {
@@ -366,32 +362,22 @@ extern "C" int sylber_knn_search(const float* q_dev, int32_t n, const float* db_
     if (metric != SYLBER_KNN_L2 && metric != SYLBER_KNN_IP) { syl_set_error(what, "unknown metric"); return 1; }
     if (metric == SYLBER_KNN_L2 && !db_norm_dev) { syl_set_error(what, "the L2 metric needs db_norm_dev"); return 1; }
     if (!q_group_dev != !db_group_dev) { syl_set_error(what, "q_group_dev and db_group_dev go together"); return 1; }
-    const int S = kn_splits(n, N, splits), S2 = (S + 1) / 2;
+    const int S = kn_splits(n, N, splits);
     char* w = (char*)workspace_dev;
     float* qsq = (float*)w;
     w += kn_al((int64_t)n * 4);
-    float* s0 = (float*)w; w += kn_al((int64_t)n * S * k * 4);
-    int32_t* i0 = (int32_t*)w; w += kn_al((int64_t)n * S * k * 4);
-    float* s1 = (float*)w; w += kn_al((int64_t)n * S2 * k * 4);
-    int32_t* i1 = (int32_t*)w;
+    KnPartials p = kn_partials_carve(w, n, S, k);
     if (metric == SYLBER_KNN_L2 && launch_km_sqnorm(q_dev, qsq, n, D, s)) return 1;
     const size_t lds = kn_lds_bytes(k);
     static PerDeviceOnce once;
     if (once.need()) HIP_TRY(hipFuncSetAttribute((const void*)knn_search_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kn_lds_bytes(KN_KMAX)));
     const unsigned nb = (unsigned)((n + KN_BM - 1) / KN_BM);
     hipLaunchKernelGGL(knn_search_kernel, dim3(nb, (unsigned)S), dim3(256), lds, s, q_dev, n, db_dev, N, D,
-                       metric == SYLBER_KNN_L2 ? db_norm_dev : nullptr, k, q_group_dev, db_group_dev, S, s0, i0);
+                       metric == SYLBER_KNN_L2 ? db_norm_dev : nullptr, k, q_group_dev, db_group_dev, S, p.s0, p.i0);
     HIP_TRY(hipGetLastError());
-    float* cs = s0; int32_t* ci = i0;
-    float* os = s1; int32_t* oi = i1;
-    for (int m = S; m > 1; m = (m + 1) / 2) {
-        hipLaunchKernelGGL(knn_merge_kernel, dim3((unsigned)n, (unsigned)((m + 1) / 2)), dim3(64), 0, s, cs, ci, m, k, os, oi);
-        HIP_TRY(hipGetLastError());
-        float* ts = cs; cs = os; os = ts;
-        int32_t* ti = ci; ci = oi; oi = ti;
-    }
+    if (kn_merge_lists(p, n, S, k, s)) return 1;
     const int64_t tot = (int64_t)n * k;
-    hipLaunchKernelGGL(knn_finish_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, cs, ci, n, k,
+    hipLaunchKernelGGL(knn_finish_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, p.s0, p.i0, n, k,
                        metric == SYLBER_KNN_L2 ? qsq : nullptr, score_dev, idx_dev);
     HIP_TRY(hipGetLastError());
     return 0;
@@ -446,9 +432,7 @@ extern "C" int32_t sylber_ivf_work_items(const int32_t* pair_counts_host, const 
 
 extern "C" int64_t sylber_ivf_workspace_bytes(int32_t n, int32_t nprobe, int32_t k, int32_t cuts) {
     if (n < 1 || nprobe < 1 || nprobe > KN_KMAX || k < 1 || k > KN_KMAX || cuts < 1) return -1;
-    const int64_t M = (int64_t)nprobe * cuts, M2 = (M + 1) / 2;
-    // ||q||^2 [n] | scores [n][M][k] | ids [n][M][k] | scores [n][ceil(M/2)][k] | ids [n][ceil(M/2)][k]
-    return kn_al((int64_t)n * 4) + 2 * kn_al((int64_t)n * M * k * 4) + 2 * kn_al((int64_t)n * M2 * k * 4);
+    return kn_al((int64_t)n * 4) + kn_partials_bytes(n, (int64_t)nprobe * cuts, k);      // ||q||^2 [n] | the nprobe x cuts partial lists (KnPartials)
 }
 
 extern "C" int sylber_ivf_search(const float* q_dev, int32_t n, int32_t D, int32_t nprobe, const int32_t* pair_dev,
@@ -468,30 +452,20 @@ extern "C" int sylber_ivf_search(const float* q_dev, int32_t n, int32_t D, int32
     if (metric != SYLBER_KNN_L2 && metric != SYLBER_KNN_IP) { syl_set_error(what, "unknown metric"); return 1; }
     if (metric == SYLBER_KNN_L2 && !row_norm_dev) { syl_set_error(what, "the L2 metric needs row_norm_dev"); return 1; }
     if (!q_group_dev != !row_group_dev) { syl_set_error(what, "q_group_dev and row_group_dev go together"); return 1; }
-    const int64_t M = (int64_t)nprobe * cuts, M2 = (M + 1) / 2;
+    const int M = nprobe * cuts;
     char* w = (char*)workspace_dev;
     float* qsq = (float*)w;
     w += kn_al((int64_t)n * 4);
-    float* s0 = (float*)w; w += kn_al((int64_t)n * M * k * 4);
-    int32_t* i0 = (int32_t*)w; w += kn_al((int64_t)n * M * k * 4);
-    float* s1 = (float*)w; w += kn_al((int64_t)n * M2 * k * 4);
-    int32_t* i1 = (int32_t*)w;
+    KnPartials p = kn_partials_carve(w, n, M, k);
     if (metric == SYLBER_KNN_L2 && launch_km_sqnorm(q_dev, qsq, n, D, s)) return 1;
     static PerDeviceOnce once;
     if (once.need()) HIP_TRY(hipFuncSetAttribute((const void*)ivf_scan_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)iv_lds_bytes(KN_KMAX)));
     hipLaunchKernelGGL(ivf_scan_kernel, dim3((unsigned)n_items), dim3(256), iv_lds_bytes(k), s, q_dev, items_dev, pair_dev, nprobe, rows_dev, D,
-                       row_id_dev, metric == SYLBER_KNN_L2 ? row_norm_dev : nullptr, k, q_group_dev, row_group_dev, cuts, s0, i0);
+                       row_id_dev, metric == SYLBER_KNN_L2 ? row_norm_dev : nullptr, k, q_group_dev, row_group_dev, cuts, p.s0, p.i0);
     HIP_TRY(hipGetLastError());
-    float* cs = s0; int32_t* ci = i0;
-    float* os = s1; int32_t* oi = i1;
-    for (int m = (int)M; m > 1; m = (m + 1) / 2) {
-        hipLaunchKernelGGL(knn_merge_kernel, dim3((unsigned)n, (unsigned)((m + 1) / 2)), dim3(64), 0, s, cs, ci, m, k, os, oi);
-        HIP_TRY(hipGetLastError());
-        float* ts = cs; cs = os; os = ts;
-        int32_t* ti = ci; ci = oi; oi = ti;
-    }
+    if (kn_merge_lists(p, n, M, k, s)) return 1;
     const int64_t tot = (int64_t)n * k;
-    hipLaunchKernelGGL(knn_finish_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, cs, ci, n, k,
+    hipLaunchKernelGGL(knn_finish_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, p.s0, p.i0, n, k,
                        metric == SYLBER_KNN_L2 ? qsq : nullptr, score_dev, idx_dev);
     HIP_TRY(hipGetLastError());
     return 0;

@@ -282,8 +282,6 @@ __global__ __launch_bounds__(256) void knn_rerank_kernel(const float* __restrict
     }
 }
 
-static int64_t k16_al(int64_t bytes) { return (bytes + 255) / 256 * 256; }
-
 extern "C" int sylber_knn16_pack(const float* x_dev, int32_t n, int32_t D, int32_t storage, void* out16_dev, int32_t* sat_count_dev,
                                  void* stream) {
     static const char* what = "sylber_knn16_pack";
@@ -304,9 +302,7 @@ extern "C" int sylber_knn16_pack(const float* x_dev, int32_t n, int32_t D, int32
 
 extern "C" int64_t sylber_knn16_workspace_bytes(int32_t n, int32_t N, int32_t D, int32_t m, int32_t splits) {
     if (n < 1 || N < 1 || D < 1 || m < 1 || m > KN_KMAX) return -1;
-    const int64_t S = sylber_knn_splits(n, N, splits), S2 = (S + 1) / 2;
-    // coarse scores [n][S][m] | indices [n][S][m] | scores [n][ceil(S/2)][m] | indices [n][ceil(S/2)][m]
-    return 2 * k16_al((int64_t)n * S * m * 4) + 2 * k16_al((int64_t)n * S2 * m * 4);
+    return kn_partials_bytes(n, sylber_knn_splits(n, N, splits), m);      // the S partial lists of coarse scores (KnPartials)
 }
 
 extern "C" int sylber_knn16_scan(const void* q16_dev, int32_t n, const void* db16_dev, int32_t N, int32_t D, const float* db_norm_dev,
@@ -319,12 +315,9 @@ extern "C" int sylber_knn16_scan(const void* q16_dev, int32_t n, const void* db1
     if (m < 1 || m > KN_KMAX) { syl_set_error(what, "need 1 <= m <= 128"); return 1; }
     if (storage != SYLBER_KNN16_FP16 && storage != SYLBER_KNN16_BF16) { syl_set_error(what, "unknown storage"); return 1; }
     if (!q_group_dev != !db_group_dev) { syl_set_error(what, "q_group_dev and db_group_dev go together"); return 1; }
-    const int S = sylber_knn_splits(n, N, splits), S2 = (S + 1) / 2;
+    const int S = sylber_knn_splits(n, N, splits);
     char* w = (char*)workspace_dev;
-    float* s0 = (float*)w; w += k16_al((int64_t)n * S * m * 4);
-    int32_t* i0 = (int32_t*)w; w += k16_al((int64_t)n * S * m * 4);
-    float* s1 = (float*)w; w += k16_al((int64_t)n * S2 * m * 4);
-    int32_t* i1 = (int32_t*)w;
+    KnPartials p = kn_partials_carve(w, n, S, m);
     const size_t lds = k16_lds_bytes(m);
     const unsigned nb = (unsigned)((n + KN_BM - 1) / KN_BM);
     const bf16_t* q16 = (const bf16_t*)q16_dev;
@@ -333,24 +326,17 @@ extern "C" int sylber_knn16_scan(const void* q16_dev, int32_t n, const void* db1
         static PerDeviceOnce once;
         if (once.need()) HIP_TRY(hipFuncSetAttribute((const void*)knn16_scan_kernel<FMT_F16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)k16_lds_bytes(KN_KMAX)));
         hipLaunchKernelGGL(knn16_scan_kernel<FMT_F16>, dim3(nb, (unsigned)S), dim3(256), lds, s, q16, n, x16, N, D, db_norm_dev, m, q_group_dev,
-                           db_group_dev, S, s0, i0);
+                           db_group_dev, S, p.s0, p.i0);
     } else {
         static PerDeviceOnce once;
         if (once.need()) HIP_TRY(hipFuncSetAttribute((const void*)knn16_scan_kernel<FMT_BF16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)k16_lds_bytes(KN_KMAX)));
         hipLaunchKernelGGL(knn16_scan_kernel<FMT_BF16>, dim3(nb, (unsigned)S), dim3(256), lds, s, q16, n, x16, N, D, db_norm_dev, m, q_group_dev,
-                           db_group_dev, S, s0, i0);
+                           db_group_dev, S, p.s0, p.i0);
     }
     HIP_TRY(hipGetLastError());
-    float* cs = s0; int32_t* ci = i0;
-    float* os = s1; int32_t* oi = i1;
-    for (int l = S; l > 1; l = (l + 1) / 2) {
-        hipLaunchKernelGGL(knn_merge_kernel, dim3((unsigned)n, (unsigned)((l + 1) / 2)), dim3(64), 0, s, cs, ci, l, m, os, oi);
-        HIP_TRY(hipGetLastError());
-        float* ts = cs; cs = os; os = ts;
-        int32_t* ti = ci; ci = oi; oi = ti;
-    }
+    if (kn_merge_lists(p, n, S, m, s)) return 1;
     const int64_t tot = (int64_t)n * m;
-    hipLaunchKernelGGL(knn16_cand_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, ci, tot, cand_dev);
+    hipLaunchKernelGGL(knn16_cand_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, p.i0, tot, cand_dev);
     HIP_TRY(hipGetLastError());
     return 0;
 }

@@ -1,5 +1,8 @@
-// The list kernels that knn.hip (sylber_knn_search, sylber_ivf_search) and knn16.hip (sylber_knn16_scan) share: the pairwise merge of
-// sorted partial lists and the reported values.  They are static: each translation unit that launches them carries its own copy.
+// The list kernels that knn.hip (sylber_knn_search, sylber_ivf_search), knn16.hip (sylber_knn16_scan) and pq.hip (sylber_pq_scan,
+// sylber_ivfpq_scan) share: the pairwise merge of sorted partial lists and the reported values.  They are static: each translation
+// unit that launches them carries its own copy.  Below knn_merge_kernel is the host side of the merge, written once for those five
+// entry points: where the partial lists lie in a workspace (KnPartials, kn_partials_bytes, kn_partials_carve) and the merge rounds
+// (kn_merge_lists).  dtw.hip merges lists with a payload and keeps its own.
 #pragma once
 #include "knn_tile.h"
 
@@ -34,6 +37,35 @@ static __global__ __launch_bounds__(64) void knn_merge_kernel(const float* __res
             if (e + lo < k) { os[e + lo] = v; oi[e + lo] = j; }
         }
     }
+}
+
+// The partial lists of a search in its workspace: L sorted lists of k per row from the scan, and room for the ceil(L / 2) of the
+// first merge round; the rounds ping-pong between the two.
+//     scores [n][L][k] | ids [n][L][k] | scores [n][ceil(L/2)][k] | ids [n][ceil(L/2)][k]
+struct KnPartials { float* s0; int32_t* i0; float* s1; int32_t* i1; };
+
+static inline int64_t kn_partials_bytes(int64_t n, int64_t L, int64_t k) {
+    return 2 * kn_al(n * L * k * 4) + 2 * kn_al(n * ((L + 1) / 2) * k * 4);
+}
+
+static inline KnPartials kn_partials_carve(char*& w, int64_t n, int64_t L, int64_t k) {
+    KnPartials p;
+    p.s0 = (float*)w; w += kn_al(n * L * k * 4);
+    p.i0 = (int32_t*)w; w += kn_al(n * L * k * 4);
+    p.s1 = (float*)w; w += kn_al(n * ((L + 1) / 2) * k * 4);
+    p.i1 = (int32_t*)w; w += kn_al(n * ((L + 1) / 2) * k * 4);
+    return p;
+}
+
+// the ceil(log2 L) merge rounds of the L lists per row in (p.s0, p.i0); on return (p.s0, p.i0) is the one merged list per row [n][k]
+static inline int kn_merge_lists(KnPartials& p, int n, int L, int k, hipStream_t s) {
+    for (int m = L; m > 1; m = (m + 1) / 2) {
+        hipLaunchKernelGGL(knn_merge_kernel, dim3((unsigned)n, (unsigned)((m + 1) / 2)), dim3(64), 0, s, p.s0, p.i0, m, k, p.s1, p.i1);
+        HIP_TRY(hipGetLastError());
+        float* ts = p.s0; p.s0 = p.s1; p.s1 = ts;
+        int32_t* ti = p.i0; p.i0 = p.i1; p.i1 = ti;
+    }
+    return 0;
 }
 
 // reported values: L2 max(0, ||q||^2 + s), inner product -s / 2 (as 0 - s / 2, so that s = 0 reports +0); fillers -> (+inf, -1)

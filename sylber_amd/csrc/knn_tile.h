@@ -11,6 +11,8 @@ constexpr int KN_BM = 128, KN_BN = 128, KN_BK = 16, KN_LD = 20;
 constexpr int KN_STAGE = 2 * KN_BM * KN_LD;               // floats of the operand staging
 constexpr int KN_KMAX = 128;
 
+static inline int64_t kn_al(int64_t bytes) { return (bytes + 255) / 256 * 256; }      // every piece of a search workspace starts at a multiple of 256
+
 __device__ __forceinline__ bool kn_better(float v, int i, float bv, int bi) { return v < bv || (v == bv && i < bi); }   // km_better
 
 __device__ __forceinline__ void kn_zero(f32x16_t (&acc)[2][2]) {

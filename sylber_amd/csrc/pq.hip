@@ -273,8 +273,6 @@ template <int QB, typename... A> static int pq_launch_scan_vec(int M, A... a) {
     return pq_launch_scan<QB, 1>(a...);
 }
 
-static int64_t pq_al(int64_t bytes) { return (bytes + 255) / 256 * 256; }
-
 extern "C" int sylber_pq_encode(const float* x_dev, int32_t n, int32_t D, const float* cb_dev, const float* cnorm_dev, int32_t M,
                                 uint8_t* code_dev, uint8_t* bad_dev, void* stream) {
     static const char* what = "sylber_pq_encode";
@@ -316,9 +314,7 @@ extern "C" int sylber_pq_lut(const float* q_dev, int32_t n, int32_t D, const flo
 
 extern "C" int64_t sylber_pq_workspace_bytes(int32_t n, int32_t N, int32_t M, int32_t m, int32_t splits) {
     if (n < 1 || N < 1 || M < 1 || M > PQ_MAX_M || m < 1 || m > KN_KMAX) return -1;
-    const int64_t S = pq_scan_splits(n, N, pq_block_queries(M, m), splits), S2 = (S + 1) / 2;
-    // scores [n][S][m] | rows [n][S][m] | scores [n][ceil(S/2)][m] | rows [n][ceil(S/2)][m]
-    return 2 * pq_al((int64_t)n * S * m * 4) + 2 * pq_al((int64_t)n * S2 * m * 4);
+    return kn_partials_bytes(n, pq_scan_splits(n, N, pq_block_queries(M, m), splits), m);      // the S partial lists (KnPartials)
 }
 
 extern "C" int sylber_pq_scan(const float* lut_dev, int32_t n, const uint8_t* code_dev, const uint8_t* bad_dev, int32_t N, int32_t M, int32_t m,
@@ -332,32 +328,22 @@ extern "C" int sylber_pq_scan(const float* lut_dev, int32_t n, const uint8_t* co
     if (m < 1 || m > KN_KMAX) { syl_set_error(what, "need 1 <= m <= 128"); return 1; }
     if (!q_group_dev != !db_group_dev) { syl_set_error(what, "q_group_dev and db_group_dev go together"); return 1; }
     const int QB = pq_block_queries(M, m);
-    const int S = pq_scan_splits(n, N, QB, splits), S2 = (S + 1) / 2;
+    const int S = pq_scan_splits(n, N, QB, splits);
     char* w = (char*)workspace_dev;
-    float* s0 = (float*)w; w += pq_al((int64_t)n * S * m * 4);
-    int32_t* i0 = (int32_t*)w; w += pq_al((int64_t)n * S * m * 4);
-    float* s1 = (float*)w; w += pq_al((int64_t)n * S2 * m * 4);
-    int32_t* i1 = (int32_t*)w;
+    KnPartials p = kn_partials_carve(w, n, S, m);
     int rc = 1;
     switch (QB) {
-        case 8: rc = pq_launch_scan_vec<8>(M, lut_dev, n, code_dev, bad_dev, N, M, m, q_group_dev, db_group_dev, S, s0, i0, s); break;
-        case 6: rc = pq_launch_scan_vec<6>(M, lut_dev, n, code_dev, bad_dev, N, M, m, q_group_dev, db_group_dev, S, s0, i0, s); break;
-        case 4: rc = pq_launch_scan_vec<4>(M, lut_dev, n, code_dev, bad_dev, N, M, m, q_group_dev, db_group_dev, S, s0, i0, s); break;
-        case 3: rc = pq_launch_scan_vec<3>(M, lut_dev, n, code_dev, bad_dev, N, M, m, q_group_dev, db_group_dev, S, s0, i0, s); break;
-        case 2: rc = pq_launch_scan_vec<2>(M, lut_dev, n, code_dev, bad_dev, N, M, m, q_group_dev, db_group_dev, S, s0, i0, s); break;
-        default: rc = pq_launch_scan_vec<1>(M, lut_dev, n, code_dev, bad_dev, N, M, m, q_group_dev, db_group_dev, S, s0, i0, s); break;
+        case 8: rc = pq_launch_scan_vec<8>(M, lut_dev, n, code_dev, bad_dev, N, M, m, q_group_dev, db_group_dev, S, p.s0, p.i0, s); break;
+        case 6: rc = pq_launch_scan_vec<6>(M, lut_dev, n, code_dev, bad_dev, N, M, m, q_group_dev, db_group_dev, S, p.s0, p.i0, s); break;
+        case 4: rc = pq_launch_scan_vec<4>(M, lut_dev, n, code_dev, bad_dev, N, M, m, q_group_dev, db_group_dev, S, p.s0, p.i0, s); break;
+        case 3: rc = pq_launch_scan_vec<3>(M, lut_dev, n, code_dev, bad_dev, N, M, m, q_group_dev, db_group_dev, S, p.s0, p.i0, s); break;
+        case 2: rc = pq_launch_scan_vec<2>(M, lut_dev, n, code_dev, bad_dev, N, M, m, q_group_dev, db_group_dev, S, p.s0, p.i0, s); break;
+        default: rc = pq_launch_scan_vec<1>(M, lut_dev, n, code_dev, bad_dev, N, M, m, q_group_dev, db_group_dev, S, p.s0, p.i0, s); break;
     }
     if (rc) return rc;
-    float* cs = s0; int32_t* ci = i0;
-    float* os = s1; int32_t* oi = i1;
-    for (int l = S; l > 1; l = (l + 1) / 2) {
-        hipLaunchKernelGGL(knn_merge_kernel, dim3((unsigned)n, (unsigned)((l + 1) / 2)), dim3(64), 0, s, cs, ci, l, m, os, oi);
-        HIP_TRY(hipGetLastError());
-        float* ts = cs; cs = os; os = ts;
-        int32_t* ti = ci; ci = oi; oi = ti;
-    }
+    if (kn_merge_lists(p, n, S, m, s)) return 1;
     const int64_t tot = (int64_t)n * m;
-    hipLaunchKernelGGL(pq_cand_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, cs, ci, tot, t_dev, cand_dev);
+    hipLaunchKernelGGL(pq_cand_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, p.s0, p.i0, tot, t_dev, cand_dev);
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -474,9 +460,7 @@ static int ipq_launch_scan(const float* lut, int n, const int32_t* probe, int np
 
 extern "C" int64_t sylber_ivfpq_workspace_bytes(int32_t n, int32_t nprobe, int32_t m, int32_t splits) {
     if (n < 1 || nprobe < 1 || nprobe > IPQ_MAX_NPROBE || m < 1 || m > KN_KMAX || splits < 0) return -1;
-    const int64_t S = ipq_splits(n, nprobe, splits), S2 = (S + 1) / 2;
-    // scores [n][S][m] | ids [n][S][m] | scores [n][ceil(S/2)][m] | ids [n][ceil(S/2)][m]
-    return 2 * pq_al((int64_t)n * S * m * 4) + 2 * pq_al((int64_t)n * S2 * m * 4);
+    return kn_partials_bytes(n, ipq_splits(n, nprobe, splits), m);      // the S partial lists (KnPartials)
 }
 
 extern "C" int sylber_ivfpq_scan(const float* lut_dev, int32_t n, const int32_t* probe_dev, int32_t nprobe, const int32_t* list_offsets_dev,
@@ -497,33 +481,23 @@ extern "C" int sylber_ivfpq_scan(const float* lut_dev, int32_t n, const int32_t*
     if (N_listed < 0) { syl_set_error(what, "need N_listed >= 0"); return 1; }
     if (!q_group_dev != !row_group_dev) { syl_set_error(what, "q_group_dev and row_group_dev go together"); return 1; }
     if (splits < 0) { syl_set_error(what, "need splits >= 0"); return 1; }
-    const int S = ipq_splits(n, nprobe, splits), S2 = (S + 1) / 2;
+    const int S = ipq_splits(n, nprobe, splits);
     char* w = (char*)workspace_dev;
-    float* s0 = (float*)w; w += pq_al((int64_t)n * S * m * 4);
-    int32_t* i0 = (int32_t*)w; w += pq_al((int64_t)n * S * m * 4);
-    float* s1 = (float*)w; w += pq_al((int64_t)n * S2 * m * 4);
-    int32_t* i1 = (int32_t*)w;
+    KnPartials p = kn_partials_carve(w, n, S, m);
     int rc;
     if (M % 16 == 0)
         rc = ipq_launch_scan<16>(lut_dev, n, probe_dev, nprobe, list_offsets_dev, nlist, code_dev, bad_dev, row_id_dev, N_listed, M, m,
-                                 q_group_dev, row_group_dev, S, s0, i0, s);
+                                 q_group_dev, row_group_dev, S, p.s0, p.i0, s);
     else if (M % 4 == 0)
         rc = ipq_launch_scan<4>(lut_dev, n, probe_dev, nprobe, list_offsets_dev, nlist, code_dev, bad_dev, row_id_dev, N_listed, M, m,
-                                q_group_dev, row_group_dev, S, s0, i0, s);
+                                q_group_dev, row_group_dev, S, p.s0, p.i0, s);
     else
         rc = ipq_launch_scan<1>(lut_dev, n, probe_dev, nprobe, list_offsets_dev, nlist, code_dev, bad_dev, row_id_dev, N_listed, M, m,
-                                q_group_dev, row_group_dev, S, s0, i0, s);
+                                q_group_dev, row_group_dev, S, p.s0, p.i0, s);
     if (rc) return rc;
-    float* cs = s0; int32_t* ci = i0;
-    float* os = s1; int32_t* oi = i1;
-    for (int l = S; l > 1; l = (l + 1) / 2) {
-        hipLaunchKernelGGL(knn_merge_kernel, dim3((unsigned)n, (unsigned)((l + 1) / 2)), dim3(64), 0, s, cs, ci, l, m, os, oi);
-        HIP_TRY(hipGetLastError());
-        float* ts = cs; cs = os; os = ts;
-        int32_t* ti = ci; ci = oi; oi = ti;
-    }
+    if (kn_merge_lists(p, n, S, m, s)) return 1;
     const int64_t tot = (int64_t)n * m;                    // the finish of sylber_pq_scan: the (+inf, INT_MAX) fillers become (+inf, -1)
-    hipLaunchKernelGGL(pq_cand_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, cs, ci, tot, t_dev, cand_dev);
+    hipLaunchKernelGGL(pq_cand_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, p.s0, p.i0, tot, t_dev, cand_dev);
     HIP_TRY(hipGetLastError());
     return 0;
 }

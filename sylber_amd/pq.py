@@ -21,7 +21,10 @@ Codes, candidates, scores and ids do not depend on ``splits``, ``query_chunk``, 
 came in one ``build`` or through later ``add`` calls, or what the workspace held.
 
 ``IVFPQSyllableIndex`` puts the same codes behind ``IVFSyllableIndex``'s lists: a search scans the codes of the ``nprobe`` nearest
-lists only (``sylber_ivfpq_scan``).  tests/ivfpq_ref.py restates that composition."""
+lists only (``sylber_ivfpq_scan``).  tests/ivfpq_ref.py restates that composition.
+
+The two classes differ in where the codes lie and which scan reads them; what they share is written once: the rules of every index in
+_index.py, and here ``_pq_search`` (the search body), ``_decode`` / ``_check_ids`` and ``_saved_codes`` / ``_saved_rows`` (the file)."""
 from __future__ import annotations
 
 from typing import List, Optional, Tuple
@@ -30,9 +33,11 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._index import (DEFAULT_QUERY_CHUNK, METRICS, _added_rows, _base_arrays, _check_k_refine, _check_nprobe, _check_splits_chunk,
+                     _chunked_workspace_bytes, _list_layout, _on_device, _outputs, _prep, _provenance, _query_groups, _result, _row_norms,
+                     _rows, _rows_of_width)
 from .kmeans import _device, _stream, _vp
-from .search import (DEFAULT_QUERY_CHUNK, MAX_CANDIDATES, MAX_K, MAX_NPROBE, METRICS, IVFSyllableIndex, SyllableIndex,
-                     _chunked_workspace_bytes, _groups, _rows)
+from .search import IVFSyllableIndex, SyllableIndex
 
 KSUB = 256                      # centroids per sub-space: one uint8 per code
 MAX_M = 64                      # PQ_MAX_M of csrc/pq.hip: at least two queries' tables (M KiB each) fit beside the top lists in LDS
@@ -69,16 +74,6 @@ def _train_codebooks(index: SyllableIndex, M: int, codebooks, seed: int, max_ite
     return C
 
 
-def _centroid_norms(codebooks: torch.Tensor) -> torch.Tensor:
-    """``[M, 256]``: ``sylber_knn_row_norms`` of the codebooks' centroids"""
-    M, _, dsub = codebooks.shape
-    dev = codebooks.device
-    cnorm = torch.empty((M, KSUB), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(_lib.load().sylber_knn_row_norms(_vp(codebooks), M * KSUB, dsub, _vp(cnorm), _stream(dev)), "sylber_knn_row_norms")
-    return cnorm
-
-
 def _encode(x: torch.Tensor, codebooks: torch.Tensor, cnorm: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
     """stored rows ``[n, D]`` on the device -> ``(codes uint8 [n, M], bad uint8 [n])`` (csrc/pq.hip, ``sylber_pq_encode``)"""
     n, D = x.shape
@@ -94,47 +89,102 @@ def _encode(x: torch.Tensor, codebooks: torch.Tensor, cnorm: torch.Tensor) -> Tu
     return codes, bad
 
 
-def _prep(x: torch.Tensor, metric: str, device: torch.device) -> torch.Tensor:
-    """rows or queries as they are stored / scored: fp32 on the device, unit rows under "cosine" (SyllableIndex._prep)"""
-    lib = _lib.load()
-    x = x.to(device, torch.float32).contiguous()
-    if metric == "cosine" and x.shape[0]:
-        y = torch.empty_like(x)
-        with torch.cuda.device(device):
-            _lib.check(lib.sylber_knn_unit_rows(_vp(x), x.shape[0], x.shape[1], _vp(y), _stream(device)), "sylber_knn_unit_rows")
-        x = y
-    return x
-
-
-def _report_scan(metric: str, qd: torch.Tensor, t: torch.Tensor, cand: torch.Tensor, scores: torch.Tensor, ids: torch.Tensor, st) -> None:
+def _report_scan(metric: str, qd: torch.Tensor, t: torch.Tensor, cand: torch.Tensor, scores: torch.Tensor, ids: torch.Tensor) -> None:
     """the reported values of knn_finish_kernel with the scan's t in place of s (plumbing on [n, k]): each is one fp32 operation"""
-    n, D = qd.shape
     pad = cand < 0
     if metric == "l2":
-        qsq = torch.empty(n, dtype=torch.float32, device=qd.device)
-        _lib.check(_lib.load().sylber_knn_row_norms(_vp(qd), n, D, _vp(qsq), st), "sylber_knn_row_norms")
-        val = torch.fmax(qsq[:, None] + t, torch.zeros_like(t))
+        val = torch.fmax(_row_norms(qd)[:, None] + t, torch.zeros_like(t))
     else:
         val = 0.0 - 0.5 * t
     scores.copy_(torch.where(pad, torch.full_like(t, float("inf")), val))
     ids.copy_(cand)
 
 
-def _check_k_refine(k, refine, rerank: bool, rows_held: bool) -> Tuple[int, int]:
-    """``(k, m_c)`` of a search, or ``ValueError``"""
-    if isinstance(k, bool) or int(k) != k or not 1 <= int(k) <= MAX_K:
-        raise ValueError("k must be an integer in [1, %d], got %r" % (MAX_K, k))
-    k = int(k)
-    if not rerank:
-        return k, k
-    if not rows_held:
-        raise ValueError("rerank=True needs the fp32 rows, which were dropped: search with rerank=False")
-    if isinstance(refine, bool) or int(refine) != refine or int(refine) < 1:
-        raise ValueError("refine must be an integer >= 1, got %r" % (refine,))
-    mc = k * int(refine)
-    if mc > MAX_CANDIDATES:
-        raise ValueError("k * refine = %d candidates per query, more than %d" % (mc, MAX_CANDIDATES))
-    return k, mc
+def _pq_search(ix, name: str, queries, k: int, mc: int, rerank: bool, groups, exclude_same_group: bool, return_candidates: bool, splits,
+               query_chunk, fill, size_fn, scan):
+    """the search of both classes once ``k`` and ``m_c`` are settled -> ``(result, n, scratch bytes)``.  The class supplies
+    ``size_fn(m, splits)``, the workspace of a chunk of ``m`` queries, and ``scan(lib, qc, lut, qg, splits, t, cand, ws, st)``, which
+    scans for one chunk: prepared queries ``qc``, their tables, their groups or ``None``.  Queues work only: no wait for the device."""
+    N = len(ix)
+    if N == 0:
+        raise ValueError("the index is empty")
+    if ix.index is not None and len(ix.index) != N:
+        raise ValueError("%s.index holds %d rows, the codes %d: add rows through %s.add" % (name, len(ix.index), N, name))
+    q = _rows_of_width(queries, ix.dim, "queries")
+    n, D = q.shape
+    dev = ix.device
+    qg = _query_groups(groups, n, exclude_same_group, dev)
+    splits, query_chunk = _check_splits_chunk(splits, query_chunk)
+    scores, ids, cand = _outputs(n, k, dev, mc)
+    if n == 0:
+        return _result(scores, ids, cand, return_candidates), 0, 0
+    lib = _lib.load()
+    qd = _prep(q, ix.metric, dev)
+    M = ix.M
+    step = min(n, query_chunk)
+    nbytes = _chunked_workspace_bytes(size_fn, n, step, splits)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    if fill is not None:
+        ws.fill_(fill)
+    lut = torch.empty((step, M, KSUB), dtype=torch.float32, device=dev)
+    t = torch.empty((n, mc), dtype=torch.float32, device=dev)
+    metric = METRICS[ix.metric]
+    with torch.cuda.device(dev):
+        st = _stream(dev)
+        for r0 in range(0, n, step):
+            r1 = min(n, r0 + step)
+            _lib.check(lib.sylber_pq_lut(_vp(qd[r0:r1]), r1 - r0, D, _vp(ix.codebooks), _vp(ix._cnorm), M, metric, _vp(lut), st), "sylber_pq_lut")
+            scan(lib, qd[r0:r1], lut, qg[r0:r1] if qg is not None else None, splits, t[r0:r1], cand[r0:r1], ws, st)
+            if rerank:
+                i = ix.index
+                _lib.check(lib.sylber_knn_rerank(_vp(qd[r0:r1]), r1 - r0, _vp(i._x), N, D, _vp(i._c), metric, _vp(cand[r0:r1]), mc, k,
+                                                 _vp(scores[r0:r1]), _vp(ids[r0:r1]), st), "sylber_knn_rerank")
+        if not rerank:
+            _report_scan(ix.metric, qd, t, cand, scores, ids)
+    return _result(scores, ids, cand, return_candidates), n, nbytes + lut.numel() * 4
+
+
+def _check_ids(ids, N: int, device) -> torch.Tensor:
+    """a flat sequence of ids in ``[0, N)`` -> int64 on the device"""
+    a = ids if torch.is_tensor(ids) else torch.from_numpy(np.asarray(ids))
+    if a.dim() != 1 or (a.numel() and (a.dtype.is_floating_point or a.dtype == torch.bool)):
+        raise ValueError("ids must be a flat sequence of integers")
+    a = a.to(device, torch.int64)
+    if a.numel() and (int(a.min()) < 0 or int(a.max()) >= N):
+        raise ValueError("ids must lie in [0, %d)" % N)
+    return a
+
+
+def _decode(codes: torch.Tensor, codebooks: torch.Tensor) -> torch.Tensor:
+    """code rows ``[n, M]`` -> their fp32 rows ``[n, D]`` (csrc/pq.hip, ``sylber_pq_decode``)"""
+    M, _, dsub = codebooks.shape
+    out = torch.empty((codes.shape[0], M * dsub), dtype=torch.float32, device=codes.device)
+    if codes.shape[0]:
+        with torch.cuda.device(codes.device):
+            _lib.check(_lib.load().sylber_pq_decode(_vp(codes), codes.shape[0], _vp(codebooks), M, M * dsub, _vp(out), _stream(codes.device)),
+                       "sylber_pq_decode")
+    return out
+
+
+def _saved_codes(z, path: str, dev):
+    """``(codebooks, codes, bad, groups)`` of a saved file on the device, or ``ValueError`` if they do not fit each other"""
+    C, codes, bad, g = (_on_device(z[key], dt, dev) for key, dt in (("codebooks", np.float32), ("codes", np.uint8), ("bad", np.uint8),
+                                                                   ("groups", np.int32)))
+    N = codes.shape[0]
+    if C.dim() != 3 or C.shape[1] != KSUB or codes.dim() != 2 or codes.shape[1] != C.shape[0] or bad.shape != (N,) or g.shape != (N,):
+        raise ValueError("%s: codebooks / codes / mask / groups do not match" % path)
+    _check_geometry(int(C.shape[0] * C.shape[2]), int(C.shape[0]))
+    return C, codes, bad, g
+
+
+def _saved_rows(z, path: str, dev, N: int, D: int):
+    """``(index, {})`` if the file holds the fp32 rows, else ``(None, the constructor's keywords for the state after drop_rows)``"""
+    if not bool(z["rows_held"]):
+        return None, dict(prov=np.asarray(z["provenance"], np.float64).reshape(N, 4), span_int=bool(z["span_int"]))
+    idx = SyllableIndex._from_saved(z, dev)
+    if len(idx) != N or idx.dim != D:
+        raise ValueError("%s: the rows do not match the codes" % path)
+    return idx, {}
 
 
 class PQSyllableIndex:
@@ -153,7 +203,7 @@ class PQSyllableIndex:
         self._g = groups                        # groups / provenance of the rows once the fp32 rows are dropped
         self._prov = prov
         self._span_dtype = np.int64 if span_int else np.float64
-        self._cnorm = _centroid_norms(codebooks)
+        self._cnorm = _row_norms(codebooks)              # [M, 256] ||centroid||^2
 
     # ---- building -------------------------------------------------------------------------------------------------------------------
     @classmethod
@@ -178,10 +228,7 @@ class PQSyllableIndex:
         """``[n, D]`` rows -> ``(codes uint8 [n, M], bad uint8 [n])`` on the device (csrc/pq.hip, ``sylber_pq_encode``: all ``M``
         sub-spaces in one launch per block of rows).  Under ``"cosine"`` the rows are made unit rows first, as ``add`` stores them."""
         x = features if _stored else self._prep(_rows(features, "features"))
-        n, D = x.shape
-        if D != self.dim:
-            raise ValueError("features: expected D = %d, got %d" % (self.dim, D))
-        return _encode(x, self.codebooks, self._cnorm)
+        return _encode(_rows_of_width(x, self.dim, "features"), self.codebooks, self._cnorm)
 
     def _prep(self, x: torch.Tensor) -> torch.Tensor:
         """rows or queries as they are stored / scored"""
@@ -191,27 +238,18 @@ class PQSyllableIndex:
         """append ``[n, D]`` rows, encoded against the existing codebooks (no retraining); while the fp32 rows are held they go to
         ``pq.index`` as well.  The result equals ``build`` from all the rows with ``codebooks=`` these.  A refused ``add`` leaves
         everything unchanged.  Returns the new ids."""
-        start = len(self)
         if self.index is not None:
             ids = self.index.add(features, groups=groups)            # validates before it appends
-            if len(ids):
-                c, b = self.encode(self.index._x[ids.start:ids.stop], _stored=True)
-                self._codes, self._bad = torch.cat([self._codes, c]), torch.cat([self._bad, b])
+            xd = self.index._x[ids.start:ids.stop]
+        else:
+            xd, gd, ids, prov = _added_rows(features, groups, self.dim, len(self), "a PQSyllableIndex", self.metric, self.device)
+        if not len(ids):
             return ids
-        x = _rows(features, "features")
-        n, D = x.shape
-        if D != self.dim:
-            raise ValueError("features: expected D = %d, got %d" % (self.dim, D))
-        g = _groups(groups, n, "groups") if groups is not None else np.full(n, -1, np.int32)
-        if start + n >= 2 ** 31:
-            raise ValueError("a PQSyllableIndex holds fewer than 2^31 rows")
-        if n == 0:
-            return range(start, start)
-        c, b = self.encode(self._prep(x), _stored=True)
+        c, b = _encode(xd, self.codebooks, self._cnorm)
         self._codes, self._bad = torch.cat([self._codes, c]), torch.cat([self._bad, b])
-        self._g = torch.cat([self._g, torch.from_numpy(g).to(self.device)])
-        self._prov = np.concatenate([self._prov, np.full((n, 4), -1.0)])
-        return range(start, start + n)
+        if self.index is None:
+            self._g, self._prov = torch.cat([self._g, gd]), np.concatenate([self._prov, prov])
+        return ids
 
     def drop_rows(self) -> None:
         """free the fp32 rows: the reference to ``pq.index`` goes (the rows live on if somebody else holds that index), the groups
@@ -251,35 +289,13 @@ class PQSyllableIndex:
 
     def decode(self, ids) -> torch.Tensor:
         """``[len(ids), D]`` fp32 on the device: the rows' reconstruction from their codes (for ``"cosine"``, of the unit rows)"""
-        a = ids if torch.is_tensor(ids) else torch.from_numpy(np.asarray(ids))
-        if a.dim() != 1 or (a.numel() and (a.dtype.is_floating_point or a.dtype == torch.bool)):
-            raise ValueError("ids must be a flat sequence of integers")
-        a = a.to(self.device, torch.int64)
-        if a.numel() and (int(a.min()) < 0 or int(a.max()) >= len(self)):
-            raise ValueError("ids must lie in [0, %d)" % len(self))
-        out = torch.empty((a.numel(), self.dim), dtype=torch.float32, device=self.device)
-        if a.numel() == 0:
-            return out
-        c = self._codes.index_select(0, a)
-        lib = _lib.load()
-        with torch.cuda.device(self.device):
-            _lib.check(lib.sylber_pq_decode(_vp(c), c.shape[0], _vp(self.codebooks), self.M, self.dim, _vp(out), _stream(self.device)),
-                       "sylber_pq_decode")
-        return out
+        return _decode(self._codes.index_select(0, _check_ids(ids, len(self), self.device)), self.codebooks)
 
     def provenance(self, ids) -> List[Optional[Tuple[int, int, object, object]]]:
         """as ``SyllableIndex.provenance``"""
         if self.index is not None:
             return self.index.provenance(ids)
-        a = np.asarray(ids.detach().cpu().numpy() if torch.is_tensor(ids) else ids, np.int64).reshape(-1)
-        out = []
-        for i in a.tolist():
-            if i < 0 or i >= len(self) or self._prov[i, 0] < 0:
-                out.append(None)
-                continue
-            r, st = self._prov[i], self._span_dtype
-            out.append((int(r[0]), int(r[1]), st(r[2]).item(), st(r[3]).item()))
-        return out
+        return _provenance(self._prov, self._span_dtype, len(self), ids)
 
     # ---- search ---------------------------------------------------------------------------------------------------------------------
     def search(self, queries, k: int, refine: int = 4, *, rerank: Optional[bool] = None, groups=None, exclude_same_group: bool = False,
@@ -296,69 +312,25 @@ class PQSyllableIndex:
         if rerank is None:
             rerank = self.index is not None
         k, mc = _check_k_refine(k, refine, rerank, self.index is not None)
-        N = len(self)
-        if N == 0:
-            raise ValueError("the index is empty")
-        if self.index is not None and len(self.index) != N:
-            raise ValueError("pq.index holds %d rows, the codes %d: add rows through pq.add" % (len(self.index), N))
-        q = _rows(queries, "queries")
-        n, D = q.shape
-        if D != self.dim:
-            raise ValueError("queries: expected D = %d, got %d" % (self.dim, D))
-        qg = None
-        if exclude_same_group:
-            if groups is None:
-                raise ValueError("exclude_same_group needs the queries' groups")
-            qg = torch.from_numpy(_groups(groups, n, "groups")).to(self.device)
-        elif groups is not None:
-            _groups(groups, n, "groups")
-        query_chunk = DEFAULT_QUERY_CHUNK if query_chunk is None else query_chunk
-        if int(splits) < 0 or int(query_chunk) < 1:
-            raise ValueError("splits must be >= 0 and query_chunk >= 1")
-        dev = self.device
-        scores = torch.empty((n, k), dtype=torch.float32, device=dev)
-        ids = torch.empty((n, k), dtype=torch.int64, device=dev)
-        cand = torch.empty((n, mc), dtype=torch.int32, device=dev)
-        if n == 0:
-            return (scores, ids, cand.to(torch.int64)) if return_candidates else (scores, ids)
-        lib = _lib.load()
-        qd = self._prep(q)
-        M = self.M
-        step = min(n, int(query_chunk))
-        ws = torch.empty(_chunked_workspace_bytes(lib.sylber_pq_workspace_bytes, n, step, N, M, mc, int(splits)), dtype=torch.uint8, device=dev)
-        if _workspace_fill is not None:
-            ws.fill_(_workspace_fill)
-        lut = torch.empty((step, M, KSUB), dtype=torch.float32, device=dev)
-        t = torch.empty((n, mc), dtype=torch.float32, device=dev)
-        metric = METRICS[self.metric]
-        xg = self._db_groups() if qg is not None else None
-        with torch.cuda.device(dev):
-            st = _stream(dev)
-            for r0 in range(0, n, step):
-                r1 = min(n, r0 + step)
-                _lib.check(lib.sylber_pq_lut(_vp(qd[r0:r1]), r1 - r0, D, _vp(self.codebooks), _vp(self._cnorm), M, metric, _vp(lut), st),
-                           "sylber_pq_lut")
-                _lib.check(lib.sylber_pq_scan(_vp(lut), r1 - r0, _vp(self._codes), _vp(self._bad), N, M, mc,
-                                              _vp(qg[r0:r1] if qg is not None else None), _vp(xg), int(splits), _vp(t[r0:r1]), _vp(cand[r0:r1]),
-                                              _vp(ws), st), "sylber_pq_scan")
-                if rerank:
-                    i = self.index
-                    _lib.check(lib.sylber_knn_rerank(_vp(qd[r0:r1]), r1 - r0, _vp(i._x), N, D, _vp(i._c), metric, _vp(cand[r0:r1]), mc, k,
-                                                     _vp(scores[r0:r1]), _vp(ids[r0:r1]), st), "sylber_knn_rerank")
-            if not rerank:
-                _report_scan(self.metric, qd, t, cand, scores, ids, st)
-        return (scores, ids, cand.to(torch.int64)) if return_candidates else (scores, ids)
+        N, M = len(self), self.M
+
+        def scan(lib, qc, lut, qg, splits, t, cand, ws, st):
+            _lib.check(lib.sylber_pq_scan(_vp(lut), qc.shape[0], _vp(self._codes), _vp(self._bad), N, M, mc, _vp(qg),
+                                          _vp(self._db_groups() if qg is not None else None), splits, _vp(t), _vp(cand), _vp(ws), st),
+                       "sylber_pq_scan")
+
+        return _pq_search(self, "pq", queries, k, mc, rerank, groups, exclude_same_group, return_candidates, splits,
+                          DEFAULT_QUERY_CHUNK if query_chunk is None else query_chunk, _workspace_fill,
+                          lambda m, splits: _lib.load().sylber_pq_workspace_bytes(m, N, M, mc, splits), scan)[0]
 
     # ---- persistence ----------------------------------------------------------------------------------------------------------------
     def save(self, path: str) -> None:
         """``.npz`` with the codebooks, codes, row mask, groups, provenance and metric, and the fp32 rows if they are still held.
         Loading neither trains nor encodes, so a round trip searches bit for bit the same."""
-        held = self.index is not None
         i = self.index
-        np.savez(path, metric=np.array(self.metric), codebooks=self.codebooks.cpu().numpy(), codes=self._codes.cpu().numpy(),
-                 bad=self._bad.cpu().numpy(), groups=self._db_groups().cpu().numpy(), provenance=(i._prov if held else self._prov),
-                 span_int=np.array((i._span_dtype if held else self._span_dtype) is np.int64), rows_held=np.array(held),
-                 features=(i._x.cpu().numpy() if held else np.zeros((0, self.dim), np.float32)))
+        base = i._saved() if i is not None else _base_arrays(self.metric, self.dim, None, self._g, self._prov, self._span_dtype)
+        np.savez(path, **base, codebooks=self.codebooks.cpu().numpy(), codes=self._codes.cpu().numpy(), bad=self._bad.cpu().numpy(),
+                 rows_held=np.array(i is not None))
 
     @classmethod
     def load(cls, path: str, device="cuda") -> "PQSyllableIndex":
@@ -366,27 +338,9 @@ class PQSyllableIndex:
         if "codebooks" not in z.files or "codes" not in z.files:
             raise ValueError("%s is not a saved PQSyllableIndex" % path)
         dev = _device(device)
-        metric = str(z["metric"])
-        C = torch.from_numpy(np.ascontiguousarray(z["codebooks"], np.float32)).to(dev)
-        codes = torch.from_numpy(np.ascontiguousarray(z["codes"], np.uint8)).to(dev)
-        bad = torch.from_numpy(np.ascontiguousarray(z["bad"], np.uint8)).to(dev)
-        N = codes.shape[0]
-        if C.dim() != 3 or C.shape[1] != KSUB or codes.dim() != 2 or codes.shape[1] != C.shape[0] or bad.shape != (N,) \
-                or z["groups"].shape != (N,):
-            raise ValueError("%s: codebooks / codes / mask / groups do not match" % path)
-        _check_geometry(int(C.shape[0] * C.shape[2]), int(C.shape[0]))
-        span_int = bool(z["span_int"])
-        if bool(z["rows_held"]):
-            idx = SyllableIndex(metric=metric, device=dev)
-            idx._load_rows(z["features"], z["groups"], z["provenance"])
-            if span_int:
-                idx._span_dtype = np.int64
-            if len(idx) != N or idx.dim != C.shape[0] * C.shape[2]:
-                raise ValueError("%s: the rows do not match the codes" % path)
-            return cls(idx, C, codes, bad, metric=metric, device=idx.device)
-        g = torch.from_numpy(np.ascontiguousarray(z["groups"], np.int32)).to(dev)
-        return cls(None, C, codes, bad, metric=metric, device=dev, groups=g, prov=np.asarray(z["provenance"], np.float64).reshape(N, 4),
-                   span_int=span_int)
+        C, codes, bad, g = _saved_codes(z, path, dev)
+        idx, dropped = _saved_rows(z, path, dev, codes.shape[0], int(C.shape[0] * C.shape[2]))
+        return cls(idx, C, codes, bad, metric=str(z["metric"]), device=dev, groups=(g if idx is None else None), **dropped)
 
 
 class IVFPQSyllableIndex:
@@ -420,7 +374,7 @@ class IVFPQSyllableIndex:
         self.centroids = centroids              # [nlist, D] fp32 on the device
         self.codebooks = codebooks              # [M, 256, dsub] fp32 on the device
         self._coarse = SyllableIndex(centroids, metric="l2", device=device)
-        self._cnorm = _centroid_norms(codebooks)
+        self._cnorm = _row_norms(codebooks)              # [M, 256] ||centroid||^2
         self._prov = prov                       # provenance of the rows once the fp32 rows are dropped
         self._span_dtype = np.int64 if span_int else np.float64
         self._last = None
@@ -440,25 +394,20 @@ class IVFPQSyllableIndex:
         M = _check_geometry(index.dim, M)
         Cl = IVFSyllableIndex._train_centroids(index, nlist, centroids, seed, max_iter, tol, train_rows)
         Cb = _train_codebooks(index, M, codebooks, seed, max_iter, tol, train_rows)
-        codes, bad = _encode(index._x, Cb, _centroid_norms(Cb))
+        codes, bad = _encode(index._x, Cb, _row_norms(Cb))
         return cls(index, Cl, Cb, IVFSyllableIndex._assign(index._x, Cl), codes, bad, index._g, metric=index.metric, device=index.device)
 
     def _layout(self, labels: torch.Tensor, codes: torch.Tensor, bad: torch.Tensor, groups: torch.Tensor) -> None:
-        """IVFSyllableIndex._layout's counting sort (plumbing): list by list, ascending id within a list; the rows in no list come
-        last, so that every row keeps its code"""
-        nlist = self.nlist
-        key = torch.where(labels < 0, torch.full_like(labels, nlist), labels).to(torch.int64)
-        order = torch.sort(key, stable=True).indices
-        sizes = torch.bincount(key, minlength=nlist + 1)[:nlist]
-        off = torch.zeros(nlist + 1, dtype=torch.int64, device=self.device)
-        off[1:] = torch.cumsum(sizes, 0)
-        self.list_sizes = sizes                                         # [nlist] int64 on the device
+        """the rows in list order (plumbing): list by list, ascending id within a list; the rows in no list come last, so that
+        every row keeps its code"""
+        order, self.list_sizes, off = _list_layout(labels, self.nlist)  # list_sizes: [nlist] int64 on the device
         self._off = off.to(torch.int32)                                 # [nlist + 1] positions
-        self._listed = int(off[nlist])                                  # rows in a list: the positions [0, _listed) are scanned
+        self._listed = int(off[-1])                                     # rows in a list: the positions [0, _listed) are scanned
         self._rid = order.to(torch.int32)                               # [N] position -> original id
         self._codes = codes.index_select(0, order)                      # [N, M] uint8 in position order
         self._rbad = bad.index_select(0, order)
         self._rg = groups.index_select(0, order)
+        self._probe_sizes = torch.cat([self.list_sizes, self.list_sizes.new_zeros(1)])      # [-1]: a probe slot without a list
 
     def _by_id(self, t: torch.Tensor) -> torch.Tensor:
         """a per-position tensor in id order"""
@@ -471,25 +420,15 @@ class IVFPQSyllableIndex:
         retraining), and the lists are laid out again; while the fp32 rows are held they go to ``ix.index`` as well.  The result equals
         ``build`` from all the rows with ``centroids=`` and ``codebooks=`` these.  A refused ``add`` leaves everything unchanged.
         Returns the new ids."""
-        start = len(self)
         if self.index is not None:
             ids = self.index.add(features, groups=groups)                # validates before it appends
-            if len(ids) == 0:
-                return ids
             xd, gd = self.index._x[ids.start:ids.stop], self.index._g[ids.start:ids.stop]
         else:
-            x = _rows(features, "features")
-            n, D = x.shape
-            if D != self.dim:
-                raise ValueError("features: expected D = %d, got %d" % (self.dim, D))
-            g = _groups(groups, n, "groups") if groups is not None else np.full(n, -1, np.int32)
-            if start + n >= 2 ** 31:
-                raise ValueError("an IVFPQSyllableIndex holds fewer than 2^31 rows")
-            if n == 0:
-                return range(start, start)
-            xd, gd = _prep(x, self.metric, self.device), torch.from_numpy(g).to(self.device)
-            self._prov = np.concatenate([self._prov, np.full((n, 4), -1.0)])
-            ids = range(start, start + n)
+            xd, gd, ids, prov = _added_rows(features, groups, self.dim, len(self), "an IVFPQSyllableIndex", self.metric, self.device)
+        if not len(ids):
+            return ids
+        if self.index is None:
+            self._prov = np.concatenate([self._prov, prov])
         c, b = _encode(xd, self.codebooks, self._cnorm)
         lab = IVFSyllableIndex._assign(xd, self.centroids)
         self._layout(torch.cat([self._labels32(), lab]), torch.cat([self.codes, c]), torch.cat([self._by_id(self._rbad), b]),
@@ -561,50 +500,21 @@ class IVFPQSyllableIndex:
 
     def decode(self, ids) -> torch.Tensor:
         """``[len(ids), D]`` fp32 on the device: the rows' reconstruction from their codes (for ``"cosine"``, of the unit rows)"""
-        a = ids if torch.is_tensor(ids) else torch.from_numpy(np.asarray(ids))
-        if a.dim() != 1 or (a.numel() and (a.dtype.is_floating_point or a.dtype == torch.bool)):
-            raise ValueError("ids must be a flat sequence of integers")
-        a = a.to(self.device, torch.int64)
-        if a.numel() and (int(a.min()) < 0 or int(a.max()) >= len(self)):
-            raise ValueError("ids must lie in [0, %d)" % len(self))
-        out = torch.empty((a.numel(), self.dim), dtype=torch.float32, device=self.device)
-        if a.numel() == 0:
-            return out
+        a = _check_ids(ids, len(self), self.device)
         pos = self._by_id(torch.arange(len(self), dtype=torch.int64, device=self.device))      # original id -> position
-        c = self._codes.index_select(0, pos.index_select(0, a))
-        with torch.cuda.device(self.device):
-            _lib.check(_lib.load().sylber_pq_decode(_vp(c), c.shape[0], _vp(self.codebooks), self.M, self.dim, _vp(out), _stream(self.device)),
-                       "sylber_pq_decode")
-        return out
+        return _decode(self._codes.index_select(0, pos.index_select(0, a)), self.codebooks)
 
     def provenance(self, ids) -> List[Optional[Tuple[int, int, object, object]]]:
         """as ``SyllableIndex.provenance``"""
         if self.index is not None:
             return self.index.provenance(ids)
-        a = np.asarray(ids.detach().cpu().numpy() if torch.is_tensor(ids) else ids, np.int64).reshape(-1)
-        out = []
-        for i in a.tolist():
-            if i < 0 or i >= len(self) or self._prov[i, 0] < 0:
-                out.append(None)
-                continue
-            r, st = self._prov[i], self._span_dtype
-            out.append((int(r[0]), int(r[1]), st(r[2]).item(), st(r[3]).item()))
-        return out
+        return _provenance(self._prov, self._span_dtype, len(self), ids)
 
     # ---- search ---------------------------------------------------------------------------------------------------------------------
-    def _check_nprobe(self, nprobe) -> int:
-        hi = min(self.nlist, MAX_NPROBE)
-        if isinstance(nprobe, bool) or int(nprobe) != nprobe or not 1 <= int(nprobe) <= hi:
-            raise ValueError("nprobe must be an integer in [1, min(nlist, %d) = %d], got %r" % (MAX_NPROBE, hi, nprobe))
-        return int(nprobe)
-
     def probe(self, queries, nprobe: int) -> torch.Tensor:
         """``[n, nprobe]`` int64: the lists a search of these queries scans, nearest centroid first (-1 where a query is NaN)"""
-        nprobe = self._check_nprobe(nprobe)
-        q = _rows(queries, "queries")
-        if q.shape[1] != self.dim:
-            raise ValueError("queries: expected D = %d, got %d" % (self.dim, q.shape[1]))
-        return self._coarse.search(_prep(q, self.metric, self.device), nprobe)[1]
+        nprobe = _check_nprobe(nprobe, self.nlist)
+        return self._coarse.search(_prep(_rows_of_width(queries, self.dim, "queries"), self.metric, self.device), nprobe)[1]
 
     def search(self, queries, k: int, nprobe: int, refine: int = 4, *, rerank: Optional[bool] = None, groups=None,
                exclude_same_group: bool = False, return_candidates: bool = False, query_chunk: int = DEFAULT_QUERY_CHUNK, splits: int = 0,
@@ -617,79 +527,33 @@ class IVFPQSyllableIndex:
         if rerank is None:
             rerank = self.index is not None
         k, mc = _check_k_refine(k, refine, rerank, self.index is not None)
-        nprobe = self._check_nprobe(nprobe)
-        N = len(self)
-        if N == 0:
-            raise ValueError("the index is empty")
-        if self.index is not None and len(self.index) != N:
-            raise ValueError("ix.index holds %d rows, the codes %d: add rows through ix.add" % (len(self.index), N))
-        q = _rows(queries, "queries")
-        n, D = q.shape
-        if D != self.dim:
-            raise ValueError("queries: expected D = %d, got %d" % (self.dim, D))
-        qg = None
-        if exclude_same_group:
-            if groups is None:
-                raise ValueError("exclude_same_group needs the queries' groups")
-            qg = torch.from_numpy(_groups(groups, n, "groups")).to(self.device)
-        elif groups is not None:
-            _groups(groups, n, "groups")
-        if int(splits) < 0 or int(query_chunk) < 1:
-            raise ValueError("splits must be >= 0 and query_chunk >= 1")
-        dev = self.device
-        scores = torch.empty((n, k), dtype=torch.float32, device=dev)
-        ids = torch.empty((n, k), dtype=torch.int64, device=dev)
-        cand = torch.empty((n, mc), dtype=torch.int32, device=dev)
-        self._last = (0, 0, N, 0)
-        if n == 0:
-            return (scores, ids, cand.to(torch.int64)) if return_candidates else (scores, ids)
-        lib = _lib.load()
-        qd = _prep(q, self.metric, dev)
+        nprobe = _check_nprobe(nprobe, self.nlist)
         M, nlist = self.M, self.nlist
-        step = min(n, int(query_chunk))
-        nbytes = _chunked_workspace_bytes(lib.sylber_ivfpq_workspace_bytes, n, step, nprobe, mc, int(splits))
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        if _workspace_fill is not None:
-            ws.fill_(_workspace_fill)
-        lut = torch.empty((step, M, KSUB), dtype=torch.float32, device=dev)
-        t = torch.empty((n, mc), dtype=torch.float32, device=dev)
-        metric = METRICS[self.metric]
-        sizes = torch.cat([self.list_sizes, torch.zeros(1, dtype=torch.int64, device=dev)])      # [-1]: a probe slot without a list
-        pairs = torch.zeros((), dtype=torch.int64, device=dev)
-        with torch.cuda.device(dev):
-            st = _stream(dev)
-            for r0 in range(0, n, step):
-                r1 = min(n, r0 + step)
-                probe = self._coarse.search(qd[r0:r1], nprobe)[1]                               # the coarse step, on the device
-                pairs += sizes[probe].sum()
-                probe = probe.to(torch.int32)
-                _lib.check(lib.sylber_pq_lut(_vp(qd[r0:r1]), r1 - r0, D, _vp(self.codebooks), _vp(self._cnorm), M, metric, _vp(lut), st),
-                           "sylber_pq_lut")
-                _lib.check(lib.sylber_ivfpq_scan(_vp(lut), r1 - r0, _vp(probe), nprobe, _vp(self._off), nlist, _vp(self._codes), _vp(self._rbad),
-                                                 _vp(self._rid), self._listed, M, mc, _vp(qg[r0:r1] if qg is not None else None),
-                                                 _vp(self._rg if qg is not None else None), int(splits), _vp(t[r0:r1]), _vp(cand[r0:r1]),
-                                                 _vp(ws), st), "sylber_ivfpq_scan")
-                if rerank:
-                    i = self.index
-                    _lib.check(lib.sylber_knn_rerank(_vp(qd[r0:r1]), r1 - r0, _vp(i._x), N, D, _vp(i._c), metric, _vp(cand[r0:r1]), mc, k,
-                                                     _vp(scores[r0:r1]), _vp(ids[r0:r1]), st), "sylber_knn_rerank")
-            if not rerank:
-                _report_scan(self.metric, qd, t, cand, scores, ids, st)
-        self._last = (pairs, n, N, nbytes + lut.numel() * 4)
-        return (scores, ids, cand.to(torch.int64)) if return_candidates else (scores, ids)
+        pairs = [0]                      # the rows scanned: a device tensor once a chunk has run, read only by last_search
+
+        def scan(lib, qc, lut, qg, splits, t, cand, ws, st):
+            probe = self._coarse.search(qc, nprobe)[1]                                          # the coarse step, on the device
+            pairs[0] = pairs[0] + self._probe_sizes[probe].sum()
+            probe = probe.to(torch.int32)
+            _lib.check(lib.sylber_ivfpq_scan(_vp(lut), qc.shape[0], _vp(probe), nprobe, _vp(self._off), nlist, _vp(self._codes), _vp(self._rbad),
+                                             _vp(self._rid), self._listed, M, mc, _vp(qg), _vp(self._rg if qg is not None else None), splits,
+                                             _vp(t), _vp(cand), _vp(ws), st), "sylber_ivfpq_scan")
+
+        out, n, nbytes = _pq_search(self, "ix", queries, k, mc, rerank, groups, exclude_same_group, return_candidates, splits, query_chunk,
+                                    _workspace_fill, lambda m, splits: _lib.load().sylber_ivfpq_workspace_bytes(m, nprobe, mc, splits), scan)
+        self._last = (pairs[0], n, len(self), nbytes)
+        return out
 
     # ---- persistence ----------------------------------------------------------------------------------------------------------------
     def save(self, path: str) -> None:
         """``.npz`` with the centroids, codebooks, every row's list, code, mask and group (in id order), the provenance and metric,
         and the fp32 rows if they are still held.  Loading neither trains, assigns nor encodes, so a round trip searches bit for bit
         the same."""
-        held = self.index is not None
         i = self.index
-        np.savez(path, metric=np.array(self.metric), centroids=self.centroids.cpu().numpy(), codebooks=self.codebooks.cpu().numpy(),
+        base = i._saved() if i is not None else _base_arrays(self.metric, self.dim, None, self._by_id(self._rg), self._prov, self._span_dtype)
+        np.savez(path, **base, centroids=self.centroids.cpu().numpy(), codebooks=self.codebooks.cpu().numpy(),
                  labels=self._labels32().cpu().numpy(), codes=self.codes.cpu().numpy(), bad=self._by_id(self._rbad).cpu().numpy(),
-                 groups=self._by_id(self._rg).cpu().numpy(), provenance=(i._prov if held else self._prov),
-                 span_int=np.array((i._span_dtype if held else self._span_dtype) is np.int64), rows_held=np.array(held),
-                 features=(i._x.cpu().numpy() if held else np.zeros((0, self.dim), np.float32)))
+                 rows_held=np.array(i is not None))
 
     @classmethod
     def load(cls, path: str, device="cuda") -> "IVFPQSyllableIndex":
@@ -697,28 +561,12 @@ class IVFPQSyllableIndex:
         if "codebooks" not in z.files or "codes" not in z.files or "centroids" not in z.files or "labels" not in z.files:
             raise ValueError("%s is not a saved IVFPQSyllableIndex" % path)
         dev = _device(device)
-        metric = str(z["metric"])
-        Cl = torch.from_numpy(np.ascontiguousarray(z["centroids"], np.float32)).to(dev)
-        Cb = torch.from_numpy(np.ascontiguousarray(z["codebooks"], np.float32)).to(dev)
-        codes = torch.from_numpy(np.ascontiguousarray(z["codes"], np.uint8)).to(dev)
-        bad = torch.from_numpy(np.ascontiguousarray(z["bad"], np.uint8)).to(dev)
-        labels = torch.from_numpy(np.ascontiguousarray(z["labels"], np.int32)).to(dev)
-        g = torch.from_numpy(np.ascontiguousarray(z["groups"], np.int32)).to(dev)
-        N = codes.shape[0]
-        if Cb.dim() != 3 or Cb.shape[1] != KSUB or codes.dim() != 2 or codes.shape[1] != Cb.shape[0] or bad.shape != (N,) \
-                or g.shape != (N,) or labels.shape != (N,) or Cl.dim() != 2 or Cl.shape[1] != Cb.shape[0] * Cb.shape[2]:
-            raise ValueError("%s: centroids / codebooks / labels / codes / mask / groups do not match" % path)
-        _check_geometry(int(Cb.shape[0] * Cb.shape[2]), int(Cb.shape[0]))
+        Cb, codes, bad, g = _saved_codes(z, path, dev)
+        Cl, labels = _on_device(z["centroids"], np.float32, dev), _on_device(z["labels"], np.int32, dev)
+        N, D = codes.shape[0], int(Cb.shape[0] * Cb.shape[2])
+        if labels.shape != (N,) or Cl.dim() != 2 or Cl.shape[1] != D:
+            raise ValueError("%s: centroids / labels do not match the codes" % path)
         if N and (int(labels.min()) < -1 or int(labels.max()) >= Cl.shape[0]):
             raise ValueError("%s: labels outside the lists" % path)
-        span_int = bool(z["span_int"])
-        if bool(z["rows_held"]):
-            idx = SyllableIndex(metric=metric, device=dev)
-            idx._load_rows(z["features"], z["groups"], z["provenance"])
-            if span_int:
-                idx._span_dtype = np.int64
-            if len(idx) != N or idx.dim != Cl.shape[1]:
-                raise ValueError("%s: the rows do not match the codes" % path)
-            return cls(idx, Cl, Cb, labels, codes, bad, idx._g, metric=metric, device=idx.device)
-        return cls(None, Cl, Cb, labels, codes, bad, g, metric=metric, device=dev, prov=np.asarray(z["provenance"], np.float64).reshape(N, 4),
-                   span_int=span_int)
+        idx, dropped = _saved_rows(z, path, dev, N, D)
+        return cls(idx, Cl, Cb, labels, codes, bad, g, metric=str(z["metric"]), device=dev, **dropped)

@@ -14,6 +14,9 @@ Contract (tests/knn_ref.py restates it in numpy)::
 ``SyllableIndex.search_phrases`` searches for a *sequence* of syllables: subsequence DTW of each phrase against every sequence (by
 default: clip) of the index, in the epilogue of the same contraction (csrc/dtw.hip, ``sylber_dtw_search``); its contract is in the
 method's docstring, restated in numpy in tests/dtw_ref.py.
+
+The rules that every index shares -- argument checks, row preparation, result buffers, provenance, the list layout, the arrays of a
+saved file -- are in _index.py, each once; this file and pq.py hold what differs between the indexes.
 """
 from __future__ import annotations
 
@@ -24,49 +27,16 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._index import MAX_CANDIDATES, MAX_K, MAX_NPROBE  # noqa: F401  (limits of this module's searches, kept importable from here)
+from ._index import (DEFAULT_QUERY_CHUNK, METRICS, _added_rows, _base_arrays, _check_k_refine, _check_nprobe, _check_splits_chunk,
+                     _chunked_workspace_bytes, _list_layout, _on_device, _outputs, _prep, _provenance, _query_groups, _result, _row_norms,
+                     _rows, _rows_of_width)
 from .kmeans import _device, _stream, _vp
 
-METRICS = {"l2": 0, "cosine": 1}        # SYLBER_KNN_L2, SYLBER_KNN_IP (cosine = inner product on unit rows)
-MAX_K = 128
-DEFAULT_QUERY_CHUNK = 8192
-MAX_NPROBE = 128
 MAX_PHRASE_ROWS = 64            # DT_MAX_M of csrc/dtw.hip: one wave holds a phrase
 MAX_SEQUENCE_ROWS = 65536       # DT_MAX_SEQ: the DP along one sequence is serial
 DEFAULT_PHRASE_CHUNK = 4096
 STORAGES = {"fp16": (0, torch.float16), "bf16": (1, torch.bfloat16)}     # SYLBER_KNN16_FP16 / _BF16: the planes of search_refined
-MAX_CANDIDATES = 128            # k * refine of search_refined: the LDS top-list of the scan beside a 128-row query block
-
-
-def _rows(a, what: str) -> torch.Tensor:
-    """a [n, D] tensor or array -> a 2-D tensor (any device), refusing what cannot become fp32"""
-    t = a if torch.is_tensor(a) else torch.from_numpy(np.asarray(a))
-    if t.dim() != 2:
-        raise ValueError("%s must be [n, D], got %s" % (what, tuple(t.shape)))
-    if not (t.dtype.is_floating_point or t.dtype in (torch.int8, torch.int16, torch.int32, torch.int64, torch.uint8)):
-        raise ValueError("%s: dtype %s cannot be cast to float32" % (what, t.dtype))
-    return t
-
-
-def _groups(g, n: int, what: str) -> np.ndarray:
-    a = np.asarray(g.detach().cpu().numpy() if torch.is_tensor(g) else g)
-    if a.ndim == 0:
-        a = np.full(n, a)
-    if a.shape != (n,):
-        raise ValueError("%s must have one entry per row (%d), got shape %s" % (what, n, a.shape))
-    if a.dtype.kind not in "iub":
-        raise ValueError("%s must be integers, got %s" % (what, a.dtype))
-    if a.size and (a.min() < -2 ** 31 or a.max() >= 2 ** 31):
-        raise ValueError("%s must fit in int32" % what)
-    return a.astype(np.int32)
-
-
-def _chunked_workspace_bytes(size_fn, n: int, step: int, *rest) -> int:
-    """the workspace that serves every chunk of n queries taken ``step`` at a time: with automatic splits a shorter last chunk gets
-    MORE splits than a full one and can need more bytes, so the buffer is the larger of the two sizes"""
-    need = int(size_fn(step, *rest))
-    if n % step:
-        need = max(need, int(size_fn(n % step, *rest)))
-    return need
 
 
 class SyllableIndex:
@@ -103,42 +73,17 @@ class SyllableIndex:
 
     # ---- building -------------------------------------------------------------------------------------------------------------------
     def _prep(self, x: torch.Tensor) -> torch.Tensor:
-        lib = _lib.load()
-        x = x.to(self.device, torch.float32).contiguous()
-        if self.metric == "cosine" and x.shape[0]:
-            y = torch.empty_like(x)
-            with torch.cuda.device(self.device):
-                _lib.check(lib.sylber_knn_unit_rows(_vp(x), x.shape[0], x.shape[1], _vp(y), _stream(self.device)), "sylber_knn_unit_rows")
-            x = y
-        return x
-
-    def _check_width(self, D: int, what: str) -> None:
-        if self.dim is None:
-            if D < 16 or D % 16:
-                raise ValueError("%s: the feature width D must be a multiple of 16, got %d" % (what, D))
-        elif D != self.dim:
-            raise ValueError("%s: expected D = %d, got %d" % (what, self.dim, D))
+        return _prep(x, self.metric, self.device)
 
     def add(self, features, groups=None, *, _prov=None) -> range:
         """append ``[m, D]`` rows (tensor or array, host or device; cast to fp32) with optional ``groups [m]``; returns their ids"""
-        x = _rows(features, "features")
-        m, D = x.shape
-        self._check_width(D, "features")
-        g = _groups(groups, m, "groups") if groups is not None else np.full(m, -1, np.int32)
-        if len(self) + m >= 2 ** 31:
-            raise ValueError("a SyllableIndex holds fewer than 2^31 rows")
-        start = len(self)
-        if m == 0:
-            return range(start, start)
-        lib = _lib.load()
-        xd = self._prep(x)
-        gd = torch.from_numpy(g).to(self.device)
-        c = None
-        if self.metric == "l2":
-            c = torch.empty(m, dtype=torch.float32, device=self.device)
-            with torch.cuda.device(self.device):
-                _lib.check(lib.sylber_knn_row_norms(_vp(xd), m, D, _vp(c), _stream(self.device)), "sylber_knn_row_norms")
-        prov = np.full((m, 4), -1.0) if _prov is None else np.asarray(_prov, np.float64).reshape(m, 4)
+        xd, gd, ids, prov = _added_rows(features, groups, self.dim, len(self), "a SyllableIndex", self.metric, self.device)
+        if not len(ids):
+            return ids
+        m, D = xd.shape
+        c = _row_norms(xd) if self.metric == "l2" else None
+        if _prov is not None:
+            prov = np.asarray(_prov, np.float64).reshape(m, 4)
         more = {st: self._pack16(xd, st, refuse=True) for st in self._planes}      # raises before anything is appended
         for st, h in more.items():
             self._planes[st] = torch.cat([self._planes[st], h])
@@ -149,7 +94,7 @@ class SyllableIndex:
             self._c = torch.cat([self._c, c]) if c is not None else None
             self._g = torch.cat([self._g, gd])
             self._prov = np.concatenate([self._prov, prov])
-        return range(start, start + m)
+        return ids
 
     @classmethod
     def from_outputs(cls, outs: Sequence[dict], *, metric: str = "l2", device="cuda") -> "SyllableIndex":
@@ -173,16 +118,7 @@ class SyllableIndex:
     def provenance(self, ids) -> List[Optional[Tuple[int, int, object, object]]]:
         """``(clip, segment, start, end)`` for each id of a flat sequence or array of ids (``None`` for -1 and for rows added
         without provenance); ``start, end`` in the unit of the outputs' ``segments``"""
-        a = np.asarray(ids.detach().cpu().numpy() if torch.is_tensor(ids) else ids, np.int64).reshape(-1)
-        out = []
-        for i in a.tolist():
-            if i < 0 or i >= len(self) or self._prov[i, 0] < 0:
-                out.append(None)
-                continue
-            r = self._prov[i]
-            st = self._span_dtype
-            out.append((int(r[0]), int(r[1]), st(r[2]).item(), st(r[3]).item()))
-        return out
+        return _provenance(self._prov, self._span_dtype, len(self), ids)
 
     # ---- search ---------------------------------------------------------------------------------------------------------------------
     def search(self, queries, k: int, *, groups=None, exclude_same_group: bool = False, splits: int = 0,
@@ -191,43 +127,28 @@ class SyllableIndex:
         distances, ascending; ``"cosine"``: similarities (queries normalised like the rows), descending.  Ties go to the smaller id;
         missing entries are (+inf, -1).  ``exclude_same_group`` skips rows whose group equals the query's (``groups [n]``).
         ``query_chunk`` bounds the workspace; ``splits`` (0 = automatic) is a test hook.  Neither changes the result."""
-        if isinstance(k, bool) or int(k) != k or not 1 <= int(k) <= MAX_K:
-            raise ValueError("k must be an integer in [1, %d], got %r" % (MAX_K, k))
-        k = int(k)
+        k = _check_k_refine(k)[0]
         if len(self) == 0:
             raise ValueError("the index is empty")
-        q = _rows(queries, "queries")
+        q = _rows_of_width(queries, self.dim, "queries")
         n, D = q.shape
-        if D != self.dim:
-            raise ValueError("queries: expected D = %d, got %d" % (self.dim, D))
-        if exclude_same_group:
-            if groups is None:
-                raise ValueError("exclude_same_group needs the queries' groups")
-            qg = torch.from_numpy(_groups(groups, n, "groups")).to(self.device)
-        elif groups is not None:
-            _groups(groups, n, "groups")
-            qg = None
-        else:
-            qg = None
-        if int(splits) < 0 or int(query_chunk) < 1:
-            raise ValueError("splits must be >= 0 and query_chunk >= 1")
-        scores = torch.empty((n, k), dtype=torch.float32, device=self.device)
-        ids = torch.empty((n, k), dtype=torch.int64, device=self.device)
+        qg = _query_groups(groups, n, exclude_same_group, self.device)
+        splits, query_chunk = _check_splits_chunk(splits, query_chunk)
+        scores, ids = _outputs(n, k, self.device)
         if n == 0:
             return scores, ids
         lib = _lib.load()
         qd = self._prep(q)
         N = len(self)
-        step = min(n, int(query_chunk))
-        ws = torch.empty(_chunked_workspace_bytes(lib.sylber_knn_workspace_bytes, n, step, N, D, k, int(splits)), dtype=torch.uint8,
-                         device=self.device)
+        step = min(n, query_chunk)
+        ws = torch.empty(_chunked_workspace_bytes(lib.sylber_knn_workspace_bytes, n, step, N, D, k, splits), dtype=torch.uint8, device=self.device)
         metric = METRICS[self.metric]
         with torch.cuda.device(self.device):
             for r0 in range(0, n, step):
                 m = min(step, n - r0)
                 _lib.check(lib.sylber_knn_search(_vp(qd[r0:r0 + m]), m, _vp(self._x), N, D, _vp(self._c), metric, k,
                                                  _vp(qg[r0:r0 + m] if qg is not None else None), _vp(self._g if qg is not None else None),
-                                                 int(splits), _vp(scores[r0:r0 + m]), _vp(ids[r0:r0 + m]), _vp(ws), _stream(self.device)),
+                                                 splits, _vp(scores[r0:r0 + m]), _vp(ids[r0:r0 + m]), _vp(ws), _stream(self.device)),
                            "sylber_knn_search")
         return scores, ids
 
@@ -276,44 +197,25 @@ class SyllableIndex:
         ``m >= N`` it *is* ``search``, bit for bit.  The only approximation is which rows get re-ranked; ``refine`` controls it.
         ``cand``, scores and ids do not depend on ``splits``, ``query_chunk``, how the index was built or stale workspace contents.
         ``1 <= k <= 128``, integer ``refine >= 1``, ``k * refine <= 128``."""
-        if isinstance(k, bool) or int(k) != k or not 1 <= int(k) <= MAX_K:
-            raise ValueError("k must be an integer in [1, %d], got %r" % (MAX_K, k))
-        k = int(k)
-        if isinstance(refine, bool) or int(refine) != refine or int(refine) < 1:
-            raise ValueError("refine must be an integer >= 1, got %r" % (refine,))
-        m = k * int(refine)
-        if m > MAX_CANDIDATES:
-            raise ValueError("k * refine = %d candidates per query, more than %d" % (m, MAX_CANDIDATES))
+        k, m = _check_k_refine(k, refine, rerank=True)
         if storage not in STORAGES:
             raise ValueError("storage must be 'fp16' or 'bf16', got %r" % (storage,))
         if len(self) == 0:
             raise ValueError("the index is empty")
-        q = _rows(queries, "queries")
+        q = _rows_of_width(queries, self.dim, "queries")
         n, D = q.shape
-        if D != self.dim:
-            raise ValueError("queries: expected D = %d, got %d" % (self.dim, D))
-        qg = None
-        if exclude_same_group:
-            if groups is None:
-                raise ValueError("exclude_same_group needs the queries' groups")
-            qg = torch.from_numpy(_groups(groups, n, "groups")).to(self.device)
-        elif groups is not None:
-            _groups(groups, n, "groups")
-        if int(splits) < 0 or int(query_chunk) < 1:
-            raise ValueError("splits must be >= 0 and query_chunk >= 1")
-        scores = torch.empty((n, k), dtype=torch.float32, device=self.device)
-        ids = torch.empty((n, k), dtype=torch.int64, device=self.device)
-        cand = torch.empty((n, m), dtype=torch.int32, device=self.device)
+        qg = _query_groups(groups, n, exclude_same_group, self.device)
+        splits, query_chunk = _check_splits_chunk(splits, query_chunk)
+        scores, ids, cand = _outputs(n, k, self.device, m)
         if n == 0:
-            return (scores, ids, cand.to(torch.int64)) if return_candidates else (scores, ids)
+            return _result(scores, ids, cand, return_candidates)
         x16 = self.half_rows(storage)
         lib = _lib.load()
         qd = self._prep(q)
         q16 = self._pack16(qd, storage, refuse=False)
         N = len(self)
-        step = min(n, int(query_chunk))
-        ws = torch.empty(_chunked_workspace_bytes(lib.sylber_knn16_workspace_bytes, n, step, N, D, m, int(splits)), dtype=torch.uint8,
-                         device=self.device)
+        step = min(n, query_chunk)
+        ws = torch.empty(_chunked_workspace_bytes(lib.sylber_knn16_workspace_bytes, n, step, N, D, m, splits), dtype=torch.uint8, device=self.device)
         metric, code = METRICS[self.metric], STORAGES[storage][0]
         xg = self._g if qg is not None else None
         with torch.cuda.device(self.device):
@@ -321,11 +223,11 @@ class SyllableIndex:
             for r0 in range(0, n, step):
                 r1 = min(n, r0 + step)
                 _lib.check(lib.sylber_knn16_scan(_vp(q16[r0:r1]), r1 - r0, _vp(x16), N, D, _vp(self._c), code, m,
-                                                 _vp(qg[r0:r1] if qg is not None else None), _vp(xg), int(splits), _vp(cand[r0:r1]), _vp(ws),
+                                                 _vp(qg[r0:r1] if qg is not None else None), _vp(xg), splits, _vp(cand[r0:r1]), _vp(ws),
                                                  st), "sylber_knn16_scan")
                 _lib.check(lib.sylber_knn_rerank(_vp(qd[r0:r1]), r1 - r0, _vp(self._x), N, D, _vp(self._c), metric, _vp(cand[r0:r1]), m, k,
                                                  _vp(scores[r0:r1]), _vp(ids[r0:r1]), st), "sylber_knn_rerank")
-        return (scores, ids, cand.to(torch.int64)) if return_candidates else (scores, ids)
+        return _result(scores, ids, cand, return_candidates)
 
     # ---- phrase search --------------------------------------------------------------------------------------------------------------
     def sequence_offsets(self) -> np.ndarray:
@@ -395,9 +297,7 @@ class SyllableIndex:
         Test hooks, none of which changes the result: ``splits`` (0 = automatic) asks for that many cuts of the database (cuts fall
         on sequence starts only), ``phrase_chunk`` bounds the phrases per launch (and so the workspace), ``block_phrases`` (0 =
         automatic) the phrases packed into one 128-row query block."""
-        if isinstance(k, bool) or int(k) != k or not 1 <= int(k) <= MAX_K:
-            raise ValueError("k must be an integer in [1, %d], got %r" % (MAX_K, k))
-        k = int(k)
+        k = _check_k_refine(k)[0]
         N = len(self)
         if N == 0:
             raise ValueError("the index is empty")
@@ -407,13 +307,10 @@ class SyllableIndex:
             parts = [_rows(p, "phrases[%d]" % i) for i, p in enumerate(phrases)]
             lens = np.array([p.shape[0] for p in parts], np.int64)
             for p in parts:
-                if p.shape[1] != self.dim:
-                    raise ValueError("phrases: expected D = %d, got %d" % (self.dim, p.shape[1]))
+                _rows_of_width(p, self.dim, "phrases")
             q = torch.cat([p.to(self.device, torch.float32) for p in parts]) if parts else torch.zeros((0, self.dim), device=self.device)
         else:
-            q = _rows(phrases, "phrases")
-            if q.shape[1] != self.dim:
-                raise ValueError("phrases: expected D = %d, got %d" % (self.dim, q.shape[1]))
+            q = _rows_of_width(phrases, self.dim, "phrases")
             lens = np.asarray(lengths.detach().cpu().numpy() if torch.is_tensor(lengths) else lengths)
             if lens.ndim != 1 or (lens.size and lens.dtype.kind not in "iu"):
                 raise ValueError("lengths must be a 1-D sequence of integers")
@@ -423,13 +320,7 @@ class SyllableIndex:
         P = int(lens.size)
         if P and (lens.min() < 1 or lens.max() > MAX_PHRASE_ROWS):
             raise ValueError("a phrase has between 1 and %d rows, got lengths from %d to %d" % (MAX_PHRASE_ROWS, lens.min(), lens.max()))
-        pg = None
-        if exclude_same_group:
-            if groups is None:
-                raise ValueError("exclude_same_group needs the phrases' groups")
-            pg = _groups(groups, P, "groups")
-        elif groups is not None:
-            _groups(groups, P, "groups")
+        pg = _query_groups(groups, P, exclude_same_group, None, "phrases")         # on the host: a chunk's groups go to the device with it
         if int(splits) < 0 or int(phrase_chunk) < 1 or int(block_phrases) < 0:
             raise ValueError("splits and block_phrases must be >= 0 and phrase_chunk >= 1")
         off = self._sequences(sequences)
@@ -484,7 +375,7 @@ class SyllableIndex:
                     ws.fill_(_workspace_fill)
                 meta_d, sp_d, br_d = (torch.from_numpy(a).to(dev) for a in (meta, slot_phrase, block_rows))
                 cut_d = torch.from_numpy(cut_rows).to(dev)
-                pg_d = torch.from_numpy(np.ascontiguousarray(pg[p0:p1])).to(dev) if pg is not None else None
+                pg_d = _on_device(pg[p0:p1], np.int32, dev) if pg is not None else None
                 _lib.check(lib.sylber_dtw_search(_vp(qp), nb, _vp(meta_d), _vp(sp_d), _vp(br_d), Pc, int(slot.max()) + 1, _vp(self._x), N,
                                                  self.dim, _vp(self._c), metric, k, _vp(seq_id), _vp(cut_d), C, _vp(pg_d), _vp(seq_grp),
                                                  _vp(costs[p0:p1]), _vp(seqs[p0:p1]), _vp(spans[p0:p1]), _vp(ws), _stream(dev)),
@@ -495,35 +386,28 @@ class SyllableIndex:
     def save(self, path: str) -> None:
         """``.npz`` with the stored rows, groups, provenance and metric (cosine rows are saved normalised; loading does not
         normalise them again, so a round trip gives the same results bit for bit)"""
-        N = len(self)
-        np.savez(path, metric=np.array(self.metric), features=(self._x.cpu().numpy() if N else np.zeros((0, self.dim or 16), np.float32)),
-                 groups=(self._g.cpu().numpy() if N else np.zeros(0, np.int32)),
-                 provenance=(self._prov if N else np.zeros((0, 4))), span_int=np.array(self._span_dtype is np.int64))
+        np.savez(path, **self._saved())
+
+    def _saved(self) -> dict:
+        return _base_arrays(self.metric, self.dim, self._x, self._g, self._prov, self._span_dtype)
 
     @classmethod
     def load(cls, path: str, device="cuda") -> "SyllableIndex":
-        z = np.load(path, allow_pickle=False)
+        return cls._from_saved(np.load(path, allow_pickle=False), device)
+
+    @classmethod
+    def _from_saved(cls, z, device) -> "SyllableIndex":
+        """the index of a saved file's ``_base_arrays``, rows as saved: cosine rows are not normalised a second time"""
         idx = cls(metric=str(z["metric"]), device=device)
         x = z["features"]
         if x.shape[0]:
-            idx._load_rows(x, z["groups"], z["provenance"])      # rows as saved: cosine rows are not normalised a second time
+            xd = _rows_of_width(_on_device(x, np.float32, idx.device), None, "features")
+            idx.dim, idx._x, idx._c = xd.shape[1], xd, (_row_norms(xd) if idx.metric == "l2" else None)
+            idx._g = _on_device(z["groups"], np.int32, idx.device)
+            idx._prov = np.asarray(z["provenance"], np.float64).reshape(len(idx), 4)
         if bool(z["span_int"]):
             idx._span_dtype = np.int64
         return idx
-
-    def _load_rows(self, x, g, prov) -> None:
-        lib = _lib.load()
-        xd = torch.from_numpy(np.ascontiguousarray(x, np.float32)).to(self.device)
-        m, D = xd.shape
-        self._check_width(D, "features")
-        c = None
-        if self.metric == "l2":
-            c = torch.empty(m, dtype=torch.float32, device=self.device)
-            with torch.cuda.device(self.device):
-                _lib.check(lib.sylber_knn_row_norms(_vp(xd), m, D, _vp(c), _stream(self.device)), "sylber_knn_row_norms")
-        self.dim, self._x, self._c = D, xd, c
-        self._g = torch.from_numpy(np.ascontiguousarray(g, np.int32)).to(self.device)
-        self._prov = np.asarray(prov, np.float64).reshape(m, 4)
 
 
 class IVFSyllableIndex:
@@ -593,14 +477,10 @@ class IVFSyllableIndex:
     def _layout(self) -> None:
         """the counting sort of the rows into lists (plumbing): positions, offsets and the list-ordered copies"""
         idx, nlist = self.index, self.nlist
-        key = torch.where(self._labels < 0, torch.full_like(self._labels, nlist), self._labels).to(torch.int64)
-        order = torch.sort(key, stable=True).indices                    # by list, ascending id within a list; unlisted rows last
-        sizes = torch.bincount(key, minlength=nlist + 1)[:nlist]
-        order = order[:int(sizes.sum())]
-        self.list_sizes = sizes
-        off = np.zeros(nlist + 2, np.int64)
-        off[1:nlist + 1] = np.cumsum(sizes.cpu().numpy())
+        order, self.list_sizes, off = _list_layout(self._labels, nlist)
+        off = np.append(off.cpu().numpy(), 0)
         off[nlist + 1] = off[nlist]                                      # a virtual empty list for probe slots without a list
+        order = order[:int(off[nlist])]                                  # the rows in no list are not laid out
         self._off_host = off.astype(np.int32)
         self._rid = order.to(torch.int32)
         self._rows = idx._x.index_select(0, order)
@@ -644,16 +524,8 @@ class IVFSyllableIndex:
     # ---- search ---------------------------------------------------------------------------------------------------------------------
     def probe(self, queries, nprobe: int) -> torch.Tensor:
         """``[n, nprobe]`` int64: the lists a search of these queries scans, nearest centroid first (-1 where a query is NaN)"""
-        self._check_nprobe(nprobe)
-        q = _rows(queries, "queries")
-        if q.shape[1] != self.index.dim:
-            raise ValueError("queries: expected D = %d, got %d" % (self.index.dim, q.shape[1]))
-        return self._coarse.search(self.index._prep(q), int(nprobe))[1]
-
-    def _check_nprobe(self, nprobe) -> None:
-        hi = min(self.nlist, MAX_NPROBE)
-        if isinstance(nprobe, bool) or int(nprobe) != nprobe or not 1 <= int(nprobe) <= hi:
-            raise ValueError("nprobe must be an integer in [1, min(nlist, %d) = %d], got %r" % (MAX_NPROBE, hi, nprobe))
+        nprobe = _check_nprobe(nprobe, self.nlist)
+        return self._coarse.search(self.index._prep(_rows_of_width(queries, self.index.dim, "queries")), nprobe)[1]
 
     def search(self, queries, k: int, nprobe: int, *, groups=None, exclude_same_group: bool = False,
                query_chunk: int = DEFAULT_QUERY_CHUNK, item_tiles: int = 0, _workspace_fill=None) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -662,36 +534,23 @@ class IVFSyllableIndex:
         ``item_tiles`` (0 = automatic) is a test hook that cuts lists into work items of that many 128-row tiles.  Neither changes
         the result.  ``ivf.last_search`` = ``{"pairs", "fraction", "items", "workspace_bytes"}`` of the call."""
         idx = self.index
-        if isinstance(k, bool) or int(k) != k or not 1 <= int(k) <= MAX_K:
-            raise ValueError("k must be an integer in [1, %d], got %r" % (MAX_K, k))
-        k = int(k)
-        self._check_nprobe(nprobe)
-        nprobe = int(nprobe)
+        k = _check_k_refine(k)[0]
+        nprobe = _check_nprobe(nprobe, self.nlist)
         if len(idx) == 0:
             raise ValueError("the index is empty")
-        q = _rows(queries, "queries")
+        q = _rows_of_width(queries, idx.dim, "queries")
         n, D = q.shape
-        if D != idx.dim:
-            raise ValueError("queries: expected D = %d, got %d" % (idx.dim, D))
-        qg = None
-        if exclude_same_group:
-            if groups is None:
-                raise ValueError("exclude_same_group needs the queries' groups")
-            qg = torch.from_numpy(_groups(groups, n, "groups")).to(idx.device)
-        elif groups is not None:
-            _groups(groups, n, "groups")
-        if int(item_tiles) < 0 or int(query_chunk) < 1:
-            raise ValueError("item_tiles must be >= 0 and query_chunk >= 1")
+        qg = _query_groups(groups, n, exclude_same_group, idx.device)
+        item_tiles, query_chunk = _check_splits_chunk(item_tiles, query_chunk, "item_tiles")
         dev = idx.device
-        scores = torch.empty((n, k), dtype=torch.float32, device=dev)
-        ids = torch.empty((n, k), dtype=torch.int64, device=dev)
+        scores, ids = _outputs(n, k, dev)
         self.last_search = {"pairs": 0, "fraction": 0.0, "items": 0, "workspace_bytes": 0}
         if n == 0:
             return scores, ids
         lib = _lib.load()
         qd = idx._prep(q)
         nlist = self.nlist
-        step = min(n, int(query_chunk), max(1, 2 ** 25 // nprobe))     # n x nprobe x cuts (<= 16) stays below 2^30
+        step = min(n, query_chunk, max(1, 2 ** 25 // nprobe))     # n x nprobe x cuts (<= 16) stays below 2^30
         metric = METRICS[idx.metric]
         i32p = ctypes.POINTER(ctypes.c_int32)
         off_p = self._off_host.ctypes.data_as(i32p)
@@ -707,9 +566,9 @@ class IVFSyllableIndex:
                 counts = np.ascontiguousarray(torch.bincount(key, minlength=nlist + 1).cpu().numpy().astype(np.int32))
                 cnt_p = counts.ctypes.data_as(i32p)
                 cuts = ctypes.c_int32(0)
-                W = int(lib.sylber_ivf_work_items(cnt_p, off_p, nlist + 1, int(item_tiles), None, 0, ctypes.byref(cuts)))
+                W = int(lib.sylber_ivf_work_items(cnt_p, off_p, nlist + 1, item_tiles, None, 0, ctypes.byref(cuts)))
                 items = np.empty((max(W, 1), 8), np.int32)
-                if W < 1 or int(lib.sylber_ivf_work_items(cnt_p, off_p, nlist + 1, int(item_tiles), items.ctypes.data_as(i32p), W,
+                if W < 1 or int(lib.sylber_ivf_work_items(cnt_p, off_p, nlist + 1, item_tiles, items.ctypes.data_as(i32p), W,
                                                           ctypes.byref(cuts))) != W:
                     raise _lib.SylberHipError("sylber_ivf_work_items failed")
                 items_d = torch.from_numpy(items).to(dev)
@@ -732,21 +591,16 @@ class IVFSyllableIndex:
     def save(self, path: str) -> None:
         """``.npz``: the source index's rows, groups, provenance and metric, the centroids and every row's list.  Loading neither
         retrains nor reassigns, so a round trip searches bit for bit the same."""
-        i = self.index
-        np.savez(path, metric=np.array(i.metric), features=i._x.cpu().numpy(), groups=i._g.cpu().numpy(), provenance=i._prov,
-                 span_int=np.array(i._span_dtype is np.int64), centroids=self.centroids.cpu().numpy(), labels=self._labels.cpu().numpy())
+        np.savez(path, **self.index._saved(), centroids=self.centroids.cpu().numpy(), labels=self._labels.cpu().numpy())
 
     @classmethod
     def load(cls, path: str, device="cuda") -> "IVFSyllableIndex":
         z = np.load(path, allow_pickle=False)
         if "centroids" not in z.files or "labels" not in z.files:
             raise ValueError("%s is not a saved IVFSyllableIndex" % path)
-        idx = SyllableIndex(metric=str(z["metric"]), device=device)
-        idx._load_rows(z["features"], z["groups"], z["provenance"])
-        if bool(z["span_int"]):
-            idx._span_dtype = np.int64
-        C = torch.from_numpy(np.ascontiguousarray(z["centroids"], np.float32)).to(idx.device)
-        labels = torch.from_numpy(np.ascontiguousarray(z["labels"], np.int32)).to(idx.device)
+        idx = SyllableIndex._from_saved(z, device)
+        C = _on_device(z["centroids"], np.float32, idx.device)
+        labels = _on_device(z["labels"], np.int32, idx.device)
         if labels.shape != (len(idx),) or C.dim() != 2 or C.shape[1] != idx.dim:
             raise ValueError("%s: centroids / labels do not match the rows" % path)
         return cls(idx, C, labels)
