@@ -333,6 +333,32 @@ int sylber_ivfpq_scan(const float* lut_dev, int32_t n, const int32_t* probe_dev,
                       int32_t m, const int32_t* q_group_dev, const int32_t* row_group_dev, int32_t splits, float* t_dev, int32_t* cand_dev,
                       void* workspace_dev, void* stream);
 
+/* Residual codes (IVFPQSyllableIndex.build(..., residual=True)): a row's code is sylber_pq_encode's of r_j = x_j - centroid[l_j], l_j
+ * its list, so the reconstruction is xhat_j = centroid[l_j] + (the centroids the code names), one fp32 addition per element.  The
+ * table stays one per query: sylber_pq_lut's inner-product table (SYLBER_KNN_IP) for both metrics; what depends on the list and on
+ * the row is added per row.  centroid_dev [nlist, D]; a list id outside [0, nlist) names no list.
+ * sylber_ivfpq_list_terms: list_term_dev [n, nprobe], a[i][s] = -2 (q_i . centroid[probe[i][s]]), the dot product the ascending fmaf
+ *   chain from 0 of sylber_knn_rerank; 0 for a slot that names no list.
+ * sylber_ivfpq_recon_norms: nrm_dev [n] = ||xhat_j||^2 of the rows with codes code_dev [n, M] and lists list_dev [n]: the chain
+ *   nrm = fmaf(xhat[e], xhat[e], nrm) from 0 in ascending e, one thread per row, so the bits are a function of the row alone.  A row
+ *   in no list takes xhat = the centroids its code names.
+ * sylber_ivfpq_decode: out_dev [n, D] = xhat of the same arguments.
+ * sylber_ivfpq_scan_residual: sylber_ivfpq_scan with t(i, j) = (u + a[i][s]) + nrm_j, u sylber_pq_scan's sum, s the probe slot whose
+ *   list holds the row and nrm_j = row_term_dev [N_listed] at the row's position (null: t = u + a[i][s]); both are added before the
+ *   threshold test.  A row is in one list, so t's bits are a function of (query, row) alone.  Everything else, the workspace
+ *   included, is sylber_ivfpq_scan's. */
+int sylber_ivfpq_list_terms(const float* q_dev, int32_t n, int32_t D, const float* centroid_dev, int32_t nlist, const int32_t* probe_dev,
+                            int32_t nprobe, float* list_term_dev, void* stream);
+int sylber_ivfpq_recon_norms(const uint8_t* code_dev, int32_t n, const int32_t* list_dev, const float* centroid_dev, int32_t nlist,
+                             const float* cb_dev, int32_t M, int32_t D, float* nrm_dev, void* stream);
+int sylber_ivfpq_decode(const uint8_t* code_dev, int32_t n, const int32_t* list_dev, const float* centroid_dev, int32_t nlist,
+                        const float* cb_dev, int32_t M, int32_t D, float* out_dev, void* stream);
+int sylber_ivfpq_scan_residual(const float* lut_dev, int32_t n, const int32_t* probe_dev, int32_t nprobe, const int32_t* list_offsets_dev,
+                               int32_t nlist, const uint8_t* code_dev, const uint8_t* bad_dev, const int32_t* row_id_dev, int32_t N_listed,
+                               int32_t M, int32_t m, const int32_t* q_group_dev, const int32_t* row_group_dev, int32_t splits,
+                               const float* list_term_dev, const float* row_term_dev, float* t_dev, int32_t* cand_dev,
+                               void* workspace_dev, void* stream);
+
 /* Phrase search (sylber_amd/search.py: SyllableIndex.search_phrases): query-by-example subsequence DTW of syllable sequences
  * (phrases, 1 <= m <= 64 rows) against every sequence of the database (runs of consecutive rows, at most 65 536 rows each).
  * Local cost of phrase row i against database row j, in fp32, from the score s = fmaf(-2, q_i . x_j, c_j) of sylber_knn_search

@@ -127,6 +127,12 @@ EXPORTS = {
     "sylber_ivfpq_workspace_bytes": (c_int64, [c_int32, c_int32, c_int32, c_int32]),
     "sylber_ivfpq_scan": (c_int, [c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_int32,
                                   c_int32, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "sylber_ivfpq_list_terms": (c_int, [c_void_p, c_int32, c_int32, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p]),
+    "sylber_ivfpq_recon_norms": (c_int, [c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_int32, c_void_p, c_void_p]),
+    "sylber_ivfpq_decode": (c_int, [c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_int32, c_void_p, c_void_p]),
+    "sylber_ivfpq_scan_residual": (c_int, [c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_int32,
+                                           c_int32, c_int32, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                           c_void_p]),
     "sylber_dtw_plan": (c_int32, [POINTER(c_int32), c_int32, POINTER(c_int32), c_int32, c_int32, c_int32, c_int32, POINTER(c_int32), c_int32,
                                   POINTER(c_int32), POINTER(c_int32), POINTER(c_int32)]),
     "sylber_dtw_workspace_bytes": (c_int64, [c_int32, c_int32, c_int32, c_int32]),

@@ -13,7 +13,10 @@
 //     region: bank conflicts of a few ways are part of the algorithm (any layout that avoids them changes the add order).
 //   * pq_decode_kernel: out[j][slice m] = C[m][code[j][m]].
 //   * ivfpq_scan_kernel (IVFPQSyllableIndex): the same t over the codes of the lists a query probes only; a workgroup holds ONE query's
-//     table and walks the lists of one split of the query's probe slots; the order is (t, original id).
+//     table and walks the lists of one split of the query's probe slots; the order is (t, original id).  Its residual variant (the
+//     codes are those of x_j - centroid[list of j]) keeps the one table per query -- the inner products -- and adds what the table
+//     cannot hold: t = (u + a[i][slot]) + nrm_j, a = -2 q . centroid (ivfpq_list_terms_kernel, a block-uniform scalar per list) and
+//     nrm_j = ||centroid + decode(code_j)||^2 (ivfpq_recon_norms_kernel, one coalesced 4-byte load per lane).
 #include "kernels.h"
 #include "../../include/sylber_hip.h"
 #include "knn_tile.h"
@@ -98,15 +101,25 @@ __global__ __launch_bounds__(256) void pq_encode_kernel(const float* __restrict_
 }
 
 // ---- decode ----------------------------------------------------------------------------------------------------------------------
+// list / cent non-null (IVF-PQ residual codes): out[j] = cent[list[j]] + that, one fp32 addition per element; a row in no list gets none.
 __global__ __launch_bounds__(256) void pq_decode_kernel(const uint8_t* __restrict__ code, int64_t quads, const float* __restrict__ cb, int M,
-                                                        int D, float* __restrict__ out) {
+                                                        int D, float* __restrict__ out, const int32_t* __restrict__ list,
+                                                        const float* __restrict__ cent, int nlist) {
     const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;     // one float4 of the output
     if (e >= quads) return;
     const int dsub = D / M, dq = D / 4;
     const int64_t j = e / dq;
     const int col = (int)(e - j * dq) * 4, m = col / dsub;
     const int c = code[j * M + m];
-    *(float4*)(out + j * D + col) = *(const float4*)(cb + ((size_t)m * PQ_KSUB + c) * dsub + (col - m * dsub));
+    float4 v = *(const float4*)(cb + ((size_t)m * PQ_KSUB + c) * dsub + (col - m * dsub));
+    if (list) {
+        const int l = list[j];
+        if (l >= 0 && l < nlist) {
+            const float4 g = *(const float4*)(cent + (size_t)l * D + col);
+            v.x = g.x + v.x; v.y = g.y + v.y; v.z = g.z + v.z; v.w = g.w + v.w;
+        }
+    }
+    *(float4*)(out + j * D + col) = v;
 }
 
 // ---- table -----------------------------------------------------------------------------------------------------------------------
@@ -292,7 +305,8 @@ extern "C" int sylber_pq_decode(const uint8_t* code_dev, int32_t n, const float*
     if (!pq_geometry(D, M)) { syl_set_error(what, "need 1 <= M <= 64, D % M == 0 and (D / M) % 16 == 0"); return 1; }
     const int64_t quads = (int64_t)n * D / 4, blocks = (quads + 255) / 256;
     if (blocks > INT32_MAX) { syl_set_error(what, "n x D is too large: decode in pieces"); return 1; }
-    hipLaunchKernelGGL(pq_decode_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, code_dev, quads, cb_dev, M, D, out_dev);
+    hipLaunchKernelGGL(pq_decode_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, code_dev, quads, cb_dev, M, D, out_dev,
+                       (const int32_t*)nullptr, (const float*)nullptr, 0);
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -369,12 +383,14 @@ static int ipq_splits(int64_t n, int nprobe, int splits) {
 // grid (n, S): split sp of query i walks the lists of its probe slots [sp * nprobe / S, (sp + 1) * nprobe / S), a list at a time in
 // tiles of IPQ_T positions (a slot < 0 or without rows costs nothing).  code / bad / rid / xgrp are in position order (list by list,
 // ascending original id within a list).  Writes the sorted best m (t, original id) of the split to ps / pi [n][S][m]; entries that
-// did not fill stay (+inf, INT_MAX).
-template <int VEC>
+// did not fill stay (+inf, INT_MAX).  RES (residual codes): t = (u + lterm[i][slot]) + rterm[position] (rterm null: t = u + lterm),
+// added before the threshold test; lterm is read once per list, rterm with the lane's own position (clamped like the code row).
+template <int VEC, bool RES>
 __global__ __launch_bounds__(IPQ_T) void ivfpq_scan_kernel(const float* __restrict__ lut, const int32_t* __restrict__ probe, int nprobe,
                                                           const int32_t* __restrict__ off, int nlist, const uint8_t* __restrict__ code,
                                                           const uint8_t* __restrict__ bad, const int32_t* __restrict__ rid, int NL, int M,
                                                           int m, const int32_t* __restrict__ qgrp, const int32_t* __restrict__ xgrp, int S,
+                                                          const float* __restrict__ lterm, const float* __restrict__ rterm,
                                                           float* __restrict__ ps, int32_t* __restrict__ pi) {
     extern __shared__ __attribute__((aligned(16))) float ipq_smem[];
     const int tsz = M * PQ_KSUB;
@@ -399,6 +415,7 @@ __global__ __launch_bounds__(IPQ_T) void ivfpq_scan_kernel(const float* __restri
         if (l < 0 || l >= nlist) continue;
         const int lo = off[l], hi = off[l + 1];
         if (lo < 0 || hi > NL || lo >= hi) continue;
+        const float a = RES ? lterm[(size_t)i * nprobe + slot] : 0.f;      // block-uniform
         for (int base = lo; base < hi; base += IPQ_T, par ^= 1) {
             const int pos = base + tid;
             const int r = pos < hi ? pos : hi - 1;
@@ -409,6 +426,10 @@ __global__ __launch_bounds__(IPQ_T) void ivfpq_scan_kernel(const float* __restri
                 pq_load<VEC>(cr + mb, w);
 #pragma unroll
                 for (int b = 0; b < VEC; ++b) t += tab[(mb + b) * PQ_KSUB + ((w[b >> 2] >> (8 * (b & 3))) & 255u)];
+            }
+            if (RES) {
+                t += a;
+                if (rterm) t += rterm[r];
             }
             // The order is (t, ORIGINAL id): positions ascend with the id inside a list, not across lists.  The id -- with the mask
             // and the group -- is fetched for the rows that pass the threshold only: a superset of the exact (t, id) test (NaN
@@ -444,16 +465,16 @@ __global__ __launch_bounds__(IPQ_T) void ivfpq_scan_kernel(const float* __restri
     for (int e = tid; e < m; e += IPQ_T) { ps[o + e] = ls[e]; pi[o + e] = li[e]; }
 }
 
-template <int VEC>
+template <int VEC, bool RES>
 static int ipq_launch_scan(const float* lut, int n, const int32_t* probe, int nprobe, const int32_t* off, int nlist, const uint8_t* code,
                            const uint8_t* bad, const int32_t* rid, int NL, int M, int m, const int32_t* qg, const int32_t* xg, int S,
-                           float* ps, int32_t* pi, hipStream_t s) {
+                           const float* lterm, const float* rterm, float* ps, int32_t* pi, hipStream_t s) {
     static PerDeviceOnce once;
     if (once.need())
-        HIP_TRY(hipFuncSetAttribute((const void*)ivfpq_scan_kernel<VEC>, hipFuncAttributeMaxDynamicSharedMemorySize,
+        HIP_TRY(hipFuncSetAttribute((const void*)ivfpq_scan_kernel<VEC, RES>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                     (int)ipq_lds_bytes(PQ_MAX_M, KN_KMAX)));
-    hipLaunchKernelGGL((ivfpq_scan_kernel<VEC>), dim3((unsigned)n, (unsigned)S), dim3(IPQ_T), ipq_lds_bytes(M, m), s, lut, probe, nprobe, off,
-                       nlist, code, bad, rid, NL, M, m, qg, xg, S, ps, pi);
+    hipLaunchKernelGGL((ivfpq_scan_kernel<VEC, RES>), dim3((unsigned)n, (unsigned)S), dim3(IPQ_T), ipq_lds_bytes(M, m), s, lut, probe, nprobe,
+                       off, nlist, code, bad, rid, NL, M, m, qg, xg, S, lterm, rterm, ps, pi);
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -463,13 +484,15 @@ extern "C" int64_t sylber_ivfpq_workspace_bytes(int32_t n, int32_t nprobe, int32
     return kn_partials_bytes(n, ipq_splits(n, nprobe, splits), m);      // the S partial lists (KnPartials)
 }
 
-extern "C" int sylber_ivfpq_scan(const float* lut_dev, int32_t n, const int32_t* probe_dev, int32_t nprobe, const int32_t* list_offsets_dev,
-                                 int32_t nlist, const uint8_t* code_dev, const uint8_t* bad_dev, const int32_t* row_id_dev, int32_t N_listed,
-                                 int32_t M, int32_t m, const int32_t* q_group_dev, const int32_t* row_group_dev, int32_t splits, float* t_dev,
-                                 int32_t* cand_dev, void* workspace_dev, void* stream) {
-    static const char* what = "sylber_ivfpq_scan";
+// the body of both scans: list_term_dev null = the codes of the rows themselves
+template <bool RES>
+static int ipq_scan(const char* what, const float* lut_dev, int32_t n, const int32_t* probe_dev, int32_t nprobe, const int32_t* list_offsets_dev,
+                    int32_t nlist, const uint8_t* code_dev, const uint8_t* bad_dev, const int32_t* row_id_dev, int32_t N_listed, int32_t M,
+                    int32_t m, const int32_t* q_group_dev, const int32_t* row_group_dev, int32_t splits, const float* list_term_dev,
+                    const float* row_term_dev, float* t_dev, int32_t* cand_dev, void* workspace_dev, void* stream) {
     hipStream_t s = (hipStream_t)stream;
-    if (!lut_dev || !probe_dev || !list_offsets_dev || !code_dev || !row_id_dev || !t_dev || !cand_dev || !workspace_dev) {
+    if (!lut_dev || !probe_dev || !list_offsets_dev || !code_dev || !row_id_dev || !t_dev || !cand_dev || !workspace_dev ||
+        (RES && !list_term_dev)) {
         syl_set_error(what, "null argument");
         return 1;
     }
@@ -486,18 +509,130 @@ extern "C" int sylber_ivfpq_scan(const float* lut_dev, int32_t n, const int32_t*
     KnPartials p = kn_partials_carve(w, n, S, m);
     int rc;
     if (M % 16 == 0)
-        rc = ipq_launch_scan<16>(lut_dev, n, probe_dev, nprobe, list_offsets_dev, nlist, code_dev, bad_dev, row_id_dev, N_listed, M, m,
-                                 q_group_dev, row_group_dev, S, p.s0, p.i0, s);
+        rc = ipq_launch_scan<16, RES>(lut_dev, n, probe_dev, nprobe, list_offsets_dev, nlist, code_dev, bad_dev, row_id_dev, N_listed, M, m,
+                                      q_group_dev, row_group_dev, S, list_term_dev, row_term_dev, p.s0, p.i0, s);
     else if (M % 4 == 0)
-        rc = ipq_launch_scan<4>(lut_dev, n, probe_dev, nprobe, list_offsets_dev, nlist, code_dev, bad_dev, row_id_dev, N_listed, M, m,
-                                q_group_dev, row_group_dev, S, p.s0, p.i0, s);
+        rc = ipq_launch_scan<4, RES>(lut_dev, n, probe_dev, nprobe, list_offsets_dev, nlist, code_dev, bad_dev, row_id_dev, N_listed, M, m,
+                                     q_group_dev, row_group_dev, S, list_term_dev, row_term_dev, p.s0, p.i0, s);
     else
-        rc = ipq_launch_scan<1>(lut_dev, n, probe_dev, nprobe, list_offsets_dev, nlist, code_dev, bad_dev, row_id_dev, N_listed, M, m,
-                                q_group_dev, row_group_dev, S, p.s0, p.i0, s);
+        rc = ipq_launch_scan<1, RES>(lut_dev, n, probe_dev, nprobe, list_offsets_dev, nlist, code_dev, bad_dev, row_id_dev, N_listed, M, m,
+                                     q_group_dev, row_group_dev, S, list_term_dev, row_term_dev, p.s0, p.i0, s);
     if (rc) return rc;
     if (kn_merge_lists(p, n, S, m, s)) return 1;
     const int64_t tot = (int64_t)n * m;                    // the finish of sylber_pq_scan: the (+inf, INT_MAX) fillers become (+inf, -1)
     hipLaunchKernelGGL(pq_cand_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, p.s0, p.i0, tot, t_dev, cand_dev);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+extern "C" int sylber_ivfpq_scan(const float* lut_dev, int32_t n, const int32_t* probe_dev, int32_t nprobe, const int32_t* list_offsets_dev,
+                                 int32_t nlist, const uint8_t* code_dev, const uint8_t* bad_dev, const int32_t* row_id_dev, int32_t N_listed,
+                                 int32_t M, int32_t m, const int32_t* q_group_dev, const int32_t* row_group_dev, int32_t splits, float* t_dev,
+                                 int32_t* cand_dev, void* workspace_dev, void* stream) {
+    return ipq_scan<false>("sylber_ivfpq_scan", lut_dev, n, probe_dev, nprobe, list_offsets_dev, nlist, code_dev, bad_dev, row_id_dev, N_listed,
+                           M, m, q_group_dev, row_group_dev, splits, nullptr, nullptr, t_dev, cand_dev, workspace_dev, stream);
+}
+
+extern "C" int sylber_ivfpq_scan_residual(const float* lut_dev, int32_t n, const int32_t* probe_dev, int32_t nprobe,
+                                          const int32_t* list_offsets_dev, int32_t nlist, const uint8_t* code_dev, const uint8_t* bad_dev,
+                                          const int32_t* row_id_dev, int32_t N_listed, int32_t M, int32_t m, const int32_t* q_group_dev,
+                                          const int32_t* row_group_dev, int32_t splits, const float* list_term_dev, const float* row_term_dev,
+                                          float* t_dev, int32_t* cand_dev, void* workspace_dev, void* stream) {
+    return ipq_scan<true>("sylber_ivfpq_scan_residual", lut_dev, n, probe_dev, nprobe, list_offsets_dev, nlist, code_dev, bad_dev, row_id_dev,
+                          N_listed, M, m, q_group_dev, row_group_dev, splits, list_term_dev, row_term_dev, t_dev, cand_dev, workspace_dev,
+                          stream);
+}
+
+// ---- residual codes: what the one table per query cannot hold ---------------------------------------------------------------------
+// thread e = pair (i, slot): a = -2 (q_i . cent[probe]), the dot product the ascending fmaf chain from 0 (knn_rerank_kernel's)
+__global__ __launch_bounds__(256) void ivfpq_list_terms_kernel(const float* __restrict__ q, int64_t pairs, int D, const float* __restrict__ cent,
+                                                               int nlist, const int32_t* __restrict__ probe, int nprobe,
+                                                               float* __restrict__ a) {
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= pairs) return;
+    const int l = probe[e];
+    float v = 0.f;
+    if (l >= 0 && l < nlist) {
+        const float* qr = q + (e / nprobe) * D;
+        const float* cr = cent + (size_t)l * D;
+        float dot = 0.f;
+        for (int c = 0; c < D; c += 4) {
+            const float4 x = *(const float4*)(qr + c), y = *(const float4*)(cr + c);
+            dot = __builtin_fmaf(x.x, y.x, dot);
+            dot = __builtin_fmaf(x.y, y.y, dot);
+            dot = __builtin_fmaf(x.z, y.z, dot);
+            dot = __builtin_fmaf(x.w, y.w, dot);
+        }
+        v = -2.0f * dot;
+    }
+    a[e] = v;
+}
+
+// thread j = row j: nrm = fmaf(xhat[e], xhat[e], nrm) from 0 in ascending e, xhat[e] = cent[list[j]][e] + cb[m][code[j][m]][e - m dsub]
+__global__ __launch_bounds__(256) void ivfpq_recon_norms_kernel(const uint8_t* __restrict__ code, int n, const int32_t* __restrict__ list,
+                                                                const float* __restrict__ cent, int nlist, const float* __restrict__ cb,
+                                                                int M, int D, float* __restrict__ nrm) {
+    const int j = blockIdx.x * 256 + threadIdx.x;
+    if (j >= n) return;
+    const int dsub = D / M, l = list[j];
+    const float* gr = l >= 0 && l < nlist ? cent + (size_t)l * D : nullptr;
+    float acc = 0.f;
+    for (int m = 0; m < M; ++m) {
+        const float* cr = cb + ((size_t)m * PQ_KSUB + code[(size_t)j * M + m]) * dsub;
+        for (int k = 0; k < dsub; k += 4) {
+            float4 v = *(const float4*)(cr + k);
+            if (gr) {
+                const float4 g = *(const float4*)(gr + m * dsub + k);
+                v.x = g.x + v.x; v.y = g.y + v.y; v.z = g.z + v.z; v.w = g.w + v.w;
+            }
+            acc = __builtin_fmaf(v.x, v.x, acc);
+            acc = __builtin_fmaf(v.y, v.y, acc);
+            acc = __builtin_fmaf(v.z, v.z, acc);
+            acc = __builtin_fmaf(v.w, v.w, acc);
+        }
+    }
+    nrm[j] = acc;
+}
+
+extern "C" int sylber_ivfpq_list_terms(const float* q_dev, int32_t n, int32_t D, const float* centroid_dev, int32_t nlist,
+                                       const int32_t* probe_dev, int32_t nprobe, float* list_term_dev, void* stream) {
+    static const char* what = "sylber_ivfpq_list_terms";
+    if (!q_dev || !centroid_dev || !probe_dev || !list_term_dev) { syl_set_error(what, "null argument"); return 1; }
+    if (n < 1) { syl_set_error(what, "need n >= 1"); return 1; }
+    if (D < 4 || D % 4) { syl_set_error(what, "need D >= 4, a multiple of 4"); return 1; }
+    if (nlist < 1) { syl_set_error(what, "need nlist >= 1"); return 1; }
+    if (nprobe < 1 || nprobe > IPQ_MAX_NPROBE) { syl_set_error(what, "need 1 <= nprobe <= 128"); return 1; }
+    const int64_t pairs = (int64_t)n * nprobe;
+    hipLaunchKernelGGL(ivfpq_list_terms_kernel, dim3((unsigned)((pairs + 255) / 256)), dim3(256), 0, (hipStream_t)stream, q_dev, pairs, D,
+                       centroid_dev, nlist, probe_dev, nprobe, list_term_dev);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+extern "C" int sylber_ivfpq_recon_norms(const uint8_t* code_dev, int32_t n, const int32_t* list_dev, const float* centroid_dev, int32_t nlist,
+                                        const float* cb_dev, int32_t M, int32_t D, float* nrm_dev, void* stream) {
+    static const char* what = "sylber_ivfpq_recon_norms";
+    if (!code_dev || !list_dev || !centroid_dev || !cb_dev || !nrm_dev) { syl_set_error(what, "null argument"); return 1; }
+    if (n < 1) { syl_set_error(what, "need n >= 1"); return 1; }
+    if (nlist < 1) { syl_set_error(what, "need nlist >= 1"); return 1; }
+    if (!pq_geometry(D, M)) { syl_set_error(what, "need 1 <= M <= 64, D % M == 0 and (D / M) % 16 == 0"); return 1; }
+    hipLaunchKernelGGL(ivfpq_recon_norms_kernel, dim3((unsigned)(((int64_t)n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, code_dev, n,
+                       list_dev, centroid_dev, nlist, cb_dev, M, D, nrm_dev);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+extern "C" int sylber_ivfpq_decode(const uint8_t* code_dev, int32_t n, const int32_t* list_dev, const float* centroid_dev, int32_t nlist,
+                                   const float* cb_dev, int32_t M, int32_t D, float* out_dev, void* stream) {
+    static const char* what = "sylber_ivfpq_decode";
+    if (!code_dev || !list_dev || !centroid_dev || !cb_dev || !out_dev) { syl_set_error(what, "null argument"); return 1; }
+    if (n < 1) { syl_set_error(what, "need n >= 1"); return 1; }
+    if (nlist < 1) { syl_set_error(what, "need nlist >= 1"); return 1; }
+    if (!pq_geometry(D, M)) { syl_set_error(what, "need 1 <= M <= 64, D % M == 0 and (D / M) % 16 == 0"); return 1; }
+    const int64_t quads = (int64_t)n * D / 4, blocks = (quads + 255) / 256;
+    if (blocks > INT32_MAX) { syl_set_error(what, "n x D is too large: decode in pieces"); return 1; }
+    hipLaunchKernelGGL(pq_decode_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, code_dev, quads, cb_dev, M, D, out_dev,
+                       list_dev, centroid_dev, nlist);
     HIP_TRY(hipGetLastError());
     return 0;
 }

@@ -21,7 +21,8 @@ Codes, candidates, scores and ids do not depend on ``splits``, ``query_chunk``, 
 came in one ``build`` or through later ``add`` calls, or what the workspace held.
 
 ``IVFPQSyllableIndex`` puts the same codes behind ``IVFSyllableIndex``'s lists: a search scans the codes of the ``nprobe`` nearest
-lists only (``sylber_ivfpq_scan``).  tests/ivfpq_ref.py restates that composition.
+lists only (``sylber_ivfpq_scan``).  tests/ivfpq_ref.py restates that composition.  With ``residual=True`` the codes are those of
+each row's residual to its list's centroid (``sylber_ivfpq_scan_residual``; tests/ivfpq_residual_ref.py).
 
 The two classes differ in where the codes lie and which scan reads them; what they share is written once: the rules of every index in
 _index.py, and here ``_pq_search`` (the search body), ``_decode`` / ``_check_ids`` and ``_saved_codes`` / ``_saved_rows`` (the file)."""
@@ -42,6 +43,7 @@ from .search import IVFSyllableIndex, SyllableIndex
 KSUB = 256                      # centroids per sub-space: one uint8 per code
 MAX_M = 64                      # PQ_MAX_M of csrc/pq.hip: at least two queries' tables (M KiB each) fit beside the top lists in LDS
 ENCODE_CHUNK = 1 << 20          # rows per encode launch
+RESIDUAL_CHUNK = 1 << 18        # rows whose fp32 residuals exist at a time while residual codes are made
 
 
 def _check_geometry(D: int, M) -> int:
@@ -101,10 +103,11 @@ def _report_scan(metric: str, qd: torch.Tensor, t: torch.Tensor, cand: torch.Ten
 
 
 def _pq_search(ix, name: str, queries, k: int, mc: int, rerank: bool, groups, exclude_same_group: bool, return_candidates: bool, splits,
-               query_chunk, fill, size_fn, scan):
+               query_chunk, fill, size_fn, scan, ip_table: bool = False):
     """the search of both classes once ``k`` and ``m_c`` are settled -> ``(result, n, scratch bytes)``.  The class supplies
     ``size_fn(m, splits)``, the workspace of a chunk of ``m`` queries, and ``scan(lib, qc, lut, qg, splits, t, cand, ws, st)``, which
-    scans for one chunk: prepared queries ``qc``, their tables, their groups or ``None``.  Queues work only: no wait for the device."""
+    scans for one chunk: prepared queries ``qc``, their tables, their groups or ``None``.  ``ip_table``: the inner-product table
+    whatever the metric (residual codes).  Queues work only: no wait for the device."""
     N = len(ix)
     if N == 0:
         raise ValueError("the index is empty")
@@ -133,7 +136,8 @@ def _pq_search(ix, name: str, queries, k: int, mc: int, rerank: bool, groups, ex
         st = _stream(dev)
         for r0 in range(0, n, step):
             r1 = min(n, r0 + step)
-            _lib.check(lib.sylber_pq_lut(_vp(qd[r0:r1]), r1 - r0, D, _vp(ix.codebooks), _vp(ix._cnorm), M, metric, _vp(lut), st), "sylber_pq_lut")
+            _lib.check(lib.sylber_pq_lut(_vp(qd[r0:r1]), r1 - r0, D, _vp(ix.codebooks), _vp(ix._cnorm), M, METRICS["cosine"] if ip_table else metric,
+                                         _vp(lut), st), "sylber_pq_lut")
             scan(lib, qd[r0:r1], lut, qg[r0:r1] if qg is not None else None, splits, t[r0:r1], cand[r0:r1], ws, st)
             if rerank:
                 i = ix.index
@@ -163,6 +167,68 @@ def _decode(codes: torch.Tensor, codebooks: torch.Tensor) -> torch.Tensor:
         with torch.cuda.device(codes.device):
             _lib.check(_lib.load().sylber_pq_decode(_vp(codes), codes.shape[0], _vp(codebooks), M, M * dsub, _vp(out), _stream(codes.device)),
                        "sylber_pq_decode")
+    return out
+
+
+def _check_residual(residual) -> bool:
+    if not isinstance(residual, (bool, np.bool_)):
+        raise ValueError("residual must be a bool, got %r" % (residual,))
+    return bool(residual)
+
+
+def _residuals(x: torch.Tensor, labels: torch.Tensor, centroids: torch.Tensor) -> torch.Tensor:
+    """``x_j - centroids[l_j]``, one fp32 subtraction per element (plumbing); a row in no list becomes a NaN row, which
+    ``sylber_pq_encode`` gives code 0 and masks"""
+    lab = labels.to(torch.int64)
+    r = x - centroids.index_select(0, lab.clamp(min=0))
+    return torch.where((lab < 0)[:, None], torch.full_like(r, float("nan")), r).contiguous()
+
+
+def _encode_residual(x: torch.Tensor, labels: torch.Tensor, centroids: torch.Tensor, codebooks: torch.Tensor,
+                     cnorm: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``_encode`` of the rows' residuals to their lists' centroids, ``RESIDUAL_CHUNK`` rows at a time"""
+    parts = [_encode(_residuals(x[r0:r0 + RESIDUAL_CHUNK], labels[r0:r0 + RESIDUAL_CHUNK], centroids), codebooks, cnorm)
+             for r0 in range(0, x.shape[0], RESIDUAL_CHUNK)]
+    return torch.cat([p[0] for p in parts]), torch.cat([p[1] for p in parts])
+
+
+def _train_residual_codebooks(index: SyllableIndex, labels: torch.Tensor, centroids: torch.Tensor, M: int, seed: int, max_iter: int,
+                              tol: float, train_rows) -> torch.Tensor:
+    """``[M, 256, D / M]``: one ``fit_kmeans`` per sub-space, with ``seed + m``, on the residuals of the rows that are in a list"""
+    from .kmeans import fit_kmeans
+    dsub = index.dim // M
+    keep = torch.nonzero(labels >= 0).flatten()
+    if keep.numel() < KSUB:
+        raise ValueError("training %d centroids per sub-space needs at least %d rows in a list, %d are" % (KSUB, KSUB, keep.numel()))
+    lab = labels.index_select(0, keep).to(torch.int64)
+    out = []
+    for m in range(M):
+        sl = slice(m * dsub, (m + 1) * dsub)
+        r = index._x[:, sl].index_select(0, keep) - centroids[:, sl].index_select(0, lab)      # the slice of _residuals: the same bits
+        out.append(fit_kmeans(r.contiguous(), KSUB, seed=seed + m, max_iter=max_iter, tol=tol, init_rows=train_rows,
+                              device=index.device).centroids)
+    return torch.stack(out).contiguous()
+
+
+def _recon_norms(codes: torch.Tensor, labels: torch.Tensor, centroids: torch.Tensor, codebooks: torch.Tensor) -> torch.Tensor:
+    """``||centroids[l_j] + decode(code_j)||^2`` fp32 ``[n]`` (csrc/pq.hip, ``sylber_ivfpq_recon_norms``); ``labels`` int32"""
+    n, (M, _, dsub) = codes.shape[0], codebooks.shape
+    out = torch.empty(n, dtype=torch.float32, device=codes.device)
+    if n:
+        with torch.cuda.device(codes.device):
+            _lib.check(_lib.load().sylber_ivfpq_recon_norms(_vp(codes), n, _vp(labels), _vp(centroids), centroids.shape[0], _vp(codebooks), M,
+                                                            M * dsub, _vp(out), _stream(codes.device)), "sylber_ivfpq_recon_norms")
+    return out
+
+
+def _decode_residual(codes: torch.Tensor, labels: torch.Tensor, centroids: torch.Tensor, codebooks: torch.Tensor) -> torch.Tensor:
+    """``centroids[l_j] + decode(code_j)`` ``[n, D]`` (csrc/pq.hip, ``sylber_ivfpq_decode``); ``labels`` int32"""
+    n, (M, _, dsub) = codes.shape[0], codebooks.shape
+    out = torch.empty((n, M * dsub), dtype=torch.float32, device=codes.device)
+    if n:
+        with torch.cuda.device(codes.device):
+            _lib.check(_lib.load().sylber_ivfpq_decode(_vp(codes), n, _vp(labels), _vp(centroids), centroids.shape[0], _vp(codebooks), M,
+                                                       M * dsub, _vp(out), _stream(codes.device)), "sylber_ivfpq_decode")
     return out
 
 
@@ -360,15 +426,30 @@ class IVFPQSyllableIndex:
     with "the row is in a probed list" added to admissibility.  Nothing depends on ``splits``, ``query_chunk``, the workspace's
     contents or whether the rows came in one ``build`` or through ``add``.
 
+    ``build(..., residual=True)`` codes each row's residual to its list's centroid instead, so that the codebooks do not spend their
+    256 entries on where the lists lie (tests/ivfpq_residual_ref.py restates it).  Lists, probing, candidates, re-rank and reported
+    values are as above; what changes::
+
+        r_j                = x_j - centroids[l_j] on the stored row, one fp32 subtraction per element (l_j the row's list)
+        codebooks          given, or codebook m = fit_kmeans(r[:, slice m] of the rows in a list, 256, seed=seed + m, ...).centroids
+        code[j, :], bad    = sylber_pq_encode's of r; a row in no list gets code 0 and is masked
+        xhat_j             = centroids[l_j] + decode(code_j), one fp32 addition per element: what ix.decode returns
+        nrm_j              = ||xhat_j||^2, the fmaf chain from 0 in ascending column (sylber_ivfpq_recon_norms); "l2" only
+        lut[i, m, c]       = fmaf(-2, q_i[slice m] . C[m, c], 0) for both metrics: still one table per query
+        a[i, s]            = -2 (q_i . centroids[probe[i, s]]), the ascending fmaf chain from 0 (sylber_ivfpq_list_terms)
+        t(i, j)            = (u + a[i, s]) + nrm_j ("l2") or u + a[i, s] ("cosine"), u the fp32 sum of the table entries as above and
+                             s the slot of the row's list: ||q - xhat||^2 - ||q||^2, respectively -2 q . xhat
+
     Build one with ``IVFPQSyllableIndex.build``.  The device holds ``M + 9`` bytes per row (code, original id, group, mask) in list
-    order plus the centroids and codebooks; ``ix.index`` is the source ``SyllableIndex`` with the fp32 rows (shared, not copied)
-    until ``drop_rows()``."""
+    order -- ``M + 13`` with residual codes under ``"l2"`` (``nrm``) -- plus the centroids and codebooks; ``ix.index`` is the source
+    ``SyllableIndex`` with the fp32 rows (shared, not copied) until ``drop_rows()``."""
 
     def __init__(self, index: Optional[SyllableIndex], centroids: torch.Tensor, codebooks: torch.Tensor, labels: torch.Tensor,
                  codes: torch.Tensor, bad: torch.Tensor, groups: torch.Tensor, *, metric: str, device: torch.device, prov=None,
-                 span_int: bool = False):
+                 span_int: bool = False, residual: bool = False):
         """``labels`` / ``codes`` / ``bad`` / ``groups``: per row in id order; they are kept in list order only"""
         self.index = index
+        self._residual = residual
         self.metric = metric
         self.device = device
         self.centroids = centroids              # [nlist, D] fp32 on the device
@@ -378,26 +459,45 @@ class IVFPQSyllableIndex:
         self._prov = prov                       # provenance of the rows once the fp32 rows are dropped
         self._span_dtype = np.int64 if span_int else np.float64
         self._last = None
-        self._layout(labels, codes, bad, groups)
+        self._layout(labels, codes, bad, groups, self._norms_of(codes, labels))
 
     # ---- building -------------------------------------------------------------------------------------------------------------------
     @classmethod
     def build(cls, source, nlist: Optional[int] = None, M: int = 48, *, centroids=None, codebooks=None, seed: int = 0, max_iter: int = 25,
-              tol: float = 1e-4, train_rows: Optional[int] = None, groups=None, metric: str = "l2", device="cuda") -> "IVFPQSyllableIndex":
+              tol: float = 1e-4, train_rows: Optional[int] = None, groups=None, metric: str = "l2", device="cuda",
+              residual: bool = False) -> "IVFPQSyllableIndex":
         """``source``: a ``SyllableIndex`` (kept as ``ix.index``, not copied) or ``[N, D]`` features (then ``groups``, ``metric`` and
         ``device`` make the index).  The centroids are trained or given as for ``IVFSyllableIndex.build`` (``fit_kmeans`` on the stored
         rows with ``seed``), the codebooks as for ``PQSyllableIndex.build`` (sub-space ``m`` with ``seed + m``; at least 256 rows).
-        ``ValueError`` for whatever either of them refuses."""
+        ``residual=True``: the codes are those of the rows' residuals to their lists' centroids, and codebooks that are not given are
+        trained on the residuals of the rows that are in a list (at least 256).  ``ValueError`` for whatever either of them refuses
+        and for a ``residual`` that is no ``bool``."""
+        residual = _check_residual(residual)
         index = source if isinstance(source, SyllableIndex) else SyllableIndex(source, metric=metric, groups=groups, device=device)
         if len(index) == 0:
             raise ValueError("the index is empty")
         M = _check_geometry(index.dim, M)
         Cl = IVFSyllableIndex._train_centroids(index, nlist, centroids, seed, max_iter, tol, train_rows)
-        Cb = _train_codebooks(index, M, codebooks, seed, max_iter, tol, train_rows)
-        codes, bad = _encode(index._x, Cb, _row_norms(Cb))
-        return cls(index, Cl, Cb, IVFSyllableIndex._assign(index._x, Cl), codes, bad, index._g, metric=index.metric, device=index.device)
+        if not residual:
+            Cb = _train_codebooks(index, M, codebooks, seed, max_iter, tol, train_rows)
+            codes, bad = _encode(index._x, Cb, _row_norms(Cb))
+            return cls(index, Cl, Cb, IVFSyllableIndex._assign(index._x, Cl), codes, bad, index._g, metric=index.metric, device=index.device)
+        if codebooks is not None:
+            Cb = _train_codebooks(index, M, codebooks, seed, max_iter, tol, train_rows)      # validates them
+        labels = IVFSyllableIndex._assign(index._x, Cl)
+        if codebooks is None:
+            Cb = _train_residual_codebooks(index, labels, Cl, M, seed, max_iter, tol, train_rows)
+        codes, bad = _encode_residual(index._x, labels, Cl, Cb, _row_norms(Cb))
+        return cls(index, Cl, Cb, labels, codes, bad, index._g, metric=index.metric, device=index.device, residual=True)
 
-    def _layout(self, labels: torch.Tensor, codes: torch.Tensor, bad: torch.Tensor, groups: torch.Tensor) -> None:
+    def _norms_of(self, codes: torch.Tensor, labels: torch.Tensor) -> Optional[torch.Tensor]:
+        """``nrm`` of these rows (``[n]``, in their order) where the index keeps it: residual codes under ``"l2"``"""
+        if not (self._residual and self.metric == "l2"):
+            return None
+        return _recon_norms(codes.contiguous(), labels.to(torch.int32).contiguous(), self.centroids, self.codebooks)
+
+    def _layout(self, labels: torch.Tensor, codes: torch.Tensor, bad: torch.Tensor, groups: torch.Tensor,
+                nrm: Optional[torch.Tensor] = None) -> None:
         """the rows in list order (plumbing): list by list, ascending id within a list; the rows in no list come last, so that
         every row keeps its code"""
         order, self.list_sizes, off = _list_layout(labels, self.nlist)  # list_sizes: [nlist] int64 on the device
@@ -407,6 +507,7 @@ class IVFPQSyllableIndex:
         self._codes = codes.index_select(0, order)                      # [N, M] uint8 in position order
         self._rbad = bad.index_select(0, order)
         self._rg = groups.index_select(0, order)
+        self._nrm = nrm.index_select(0, order) if nrm is not None else None     # [N] ||xhat||^2 in position order (residual "l2")
         self._probe_sizes = torch.cat([self.list_sizes, self.list_sizes.new_zeros(1)])      # [-1]: a probe slot without a list
 
     def _by_id(self, t: torch.Tensor) -> torch.Tensor:
@@ -417,8 +518,9 @@ class IVFPQSyllableIndex:
 
     def add(self, features, groups=None) -> range:
         """append ``[n, D]`` rows: they are assigned to the existing centroids and encoded with the existing codebooks (no
-        retraining), and the lists are laid out again; while the fp32 rows are held they go to ``ix.index`` as well.  The result equals
-        ``build`` from all the rows with ``centroids=`` and ``codebooks=`` these.  A refused ``add`` leaves everything unchanged.
+        retraining; with residual codes, their residuals are, and ``nrm`` is computed for them), and the lists are laid out again; while
+        the fp32 rows are held they go to ``ix.index`` as well.  The result equals ``build`` from all the rows with ``centroids=`` and
+        ``codebooks=`` these.  A refused ``add`` leaves everything unchanged.
         Returns the new ids."""
         if self.index is not None:
             ids = self.index.add(features, groups=groups)                # validates before it appends
@@ -429,10 +531,14 @@ class IVFPQSyllableIndex:
             return ids
         if self.index is None:
             self._prov = np.concatenate([self._prov, prov])
-        c, b = _encode(xd, self.codebooks, self._cnorm)
         lab = IVFSyllableIndex._assign(xd, self.centroids)
+        if self._residual:
+            c, b = _encode_residual(xd, lab, self.centroids, self.codebooks, self._cnorm)
+        else:
+            c, b = _encode(xd, self.codebooks, self._cnorm)
+        nrm = torch.cat([self._by_id(self._nrm), self._norms_of(c, lab)]) if self._nrm is not None else None
         self._layout(torch.cat([self._labels32(), lab]), torch.cat([self.codes, c]), torch.cat([self._by_id(self._rbad), b]),
-                     torch.cat([self._by_id(self._rg), gd]))
+                     torch.cat([self._by_id(self._rg), gd]), nrm)
         return ids
 
     def drop_rows(self) -> None:
@@ -446,6 +552,11 @@ class IVFPQSyllableIndex:
     # ---- views ----------------------------------------------------------------------------------------------------------------------
     def __len__(self) -> int:
         return int(self._codes.shape[0])
+
+    @property
+    def residual(self) -> bool:
+        """whether the codes are those of the rows' residuals to their lists' centroids (``build(..., residual=True)``)"""
+        return self._residual
 
     @property
     def nlist(self) -> int:
@@ -481,11 +592,11 @@ class IVFPQSyllableIndex:
 
     @property
     def nbytes(self) -> int:
-        """bytes this index holds on the device: ``M + 9`` per row (code, id, group, mask), the list offsets, the centroids and the
-        codebooks with their norms, and ``4 N D`` for the fp32 rows while they are held (the ``4 N`` bytes of an ``"l2"`` source
+        """bytes this index holds on the device: ``M + 9`` per row (code, id, group, mask; ``M + 13`` with the ``nrm`` of residual codes
+        under ``"l2"``), the list offsets, the centroids and the codebooks with their norms, and ``4 N D`` for the fp32 rows while they are held (the ``4 N`` bytes of an ``"l2"`` source
         index's row norms are not counted)"""
         n = self._codes.numel() + 9 * len(self) + 4 * self._off.numel() + 4 * self.centroids.numel() + 4 * self.nlist \
-            + 4 * self.codebooks.numel() + 4 * self._cnorm.numel()
+            + 4 * self.codebooks.numel() + 4 * self._cnorm.numel() + (4 * self._nrm.numel() if self._nrm is not None else 0)
         return int(n + (4 * len(self) * self.dim if self.index is not None else 0))
 
     @property
@@ -499,10 +610,14 @@ class IVFPQSyllableIndex:
         return {"pairs": pairs, "fraction": pairs / (float(n) * N) if n else 0.0, "workspace_bytes": ws}
 
     def decode(self, ids) -> torch.Tensor:
-        """``[len(ids), D]`` fp32 on the device: the rows' reconstruction from their codes (for ``"cosine"``, of the unit rows)"""
+        """``[len(ids), D]`` fp32 on the device: the rows' reconstruction from their codes (for ``"cosine"``, of the unit rows); with
+        residual codes the list's centroid plus the code's centroids (for a row in no list those alone)"""
         a = _check_ids(ids, len(self), self.device)
         pos = self._by_id(torch.arange(len(self), dtype=torch.int64, device=self.device))      # original id -> position
-        return _decode(self._codes.index_select(0, pos.index_select(0, a)), self.codebooks)
+        codes = self._codes.index_select(0, pos.index_select(0, a))
+        if not self._residual:
+            return _decode(codes, self.codebooks)
+        return _decode_residual(codes, self._labels32().index_select(0, a), self.centroids, self.codebooks)
 
     def provenance(self, ids) -> List[Optional[Tuple[int, int, object, object]]]:
         """as ``SyllableIndex.provenance``"""
@@ -535,25 +650,37 @@ class IVFPQSyllableIndex:
             probe = self._coarse.search(qc, nprobe)[1]                                          # the coarse step, on the device
             pairs[0] = pairs[0] + self._probe_sizes[probe].sum()
             probe = probe.to(torch.int32)
+            if self._residual:
+                a = torch.empty(probe.shape, dtype=torch.float32, device=self.device)
+                _lib.check(lib.sylber_ivfpq_list_terms(_vp(qc), qc.shape[0], self.dim, _vp(self.centroids), nlist, _vp(probe), nprobe, _vp(a), st),
+                           "sylber_ivfpq_list_terms")
+                _lib.check(lib.sylber_ivfpq_scan_residual(_vp(lut), qc.shape[0], _vp(probe), nprobe, _vp(self._off), nlist, _vp(self._codes),
+                                                          _vp(self._rbad), _vp(self._rid), self._listed, M, mc, _vp(qg),
+                                                          _vp(self._rg if qg is not None else None), splits, _vp(a), _vp(self._nrm), _vp(t),
+                                                          _vp(cand), _vp(ws), st), "sylber_ivfpq_scan_residual")
+                return
             _lib.check(lib.sylber_ivfpq_scan(_vp(lut), qc.shape[0], _vp(probe), nprobe, _vp(self._off), nlist, _vp(self._codes), _vp(self._rbad),
                                              _vp(self._rid), self._listed, M, mc, _vp(qg), _vp(self._rg if qg is not None else None), splits,
                                              _vp(t), _vp(cand), _vp(ws), st), "sylber_ivfpq_scan")
 
         out, n, nbytes = _pq_search(self, "ix", queries, k, mc, rerank, groups, exclude_same_group, return_candidates, splits, query_chunk,
-                                    _workspace_fill, lambda m, splits: _lib.load().sylber_ivfpq_workspace_bytes(m, nprobe, mc, splits), scan)
+                                    _workspace_fill, lambda m, splits: _lib.load().sylber_ivfpq_workspace_bytes(m, nprobe, mc, splits), scan,
+                                    ip_table=self._residual)
         self._last = (pairs[0], n, len(self), nbytes)
         return out
 
     # ---- persistence ----------------------------------------------------------------------------------------------------------------
     def save(self, path: str) -> None:
         """``.npz`` with the centroids, codebooks, every row's list, code, mask and group (in id order), the provenance and metric,
-        and the fp32 rows if they are still held.  Loading neither trains, assigns nor encodes, so a round trip searches bit for bit
-        the same."""
+        a ``residual`` entry if the codes are residual codes (without them the file is what it always was), and the fp32 rows if they
+        are still held.  Loading neither trains, assigns nor encodes
+        (``nrm`` is computed again from the codes, lists, centroids and codebooks: the same bits), so a round trip searches bit for
+        bit the same."""
         i = self.index
         base = i._saved() if i is not None else _base_arrays(self.metric, self.dim, None, self._by_id(self._rg), self._prov, self._span_dtype)
         np.savez(path, **base, centroids=self.centroids.cpu().numpy(), codebooks=self.codebooks.cpu().numpy(),
                  labels=self._labels32().cpu().numpy(), codes=self.codes.cpu().numpy(), bad=self._by_id(self._rbad).cpu().numpy(),
-                 rows_held=np.array(i is not None))
+                 rows_held=np.array(i is not None), **({"residual": np.array(True)} if self._residual else {}))
 
     @classmethod
     def load(cls, path: str, device="cuda") -> "IVFPQSyllableIndex":
@@ -569,4 +696,5 @@ class IVFPQSyllableIndex:
         if N and (int(labels.min()) < -1 or int(labels.max()) >= Cl.shape[0]):
             raise ValueError("%s: labels outside the lists" % path)
         idx, dropped = _saved_rows(z, path, dev, N, D)
-        return cls(idx, Cl, Cb, labels, codes, bad, g, metric=str(z["metric"]), device=dev, **dropped)
+        residual = bool(z["residual"]) if "residual" in z.files else False     # a file from before residual codes
+        return cls(idx, Cl, Cb, labels, codes, bad, g, metric=str(z["metric"]), device=dev, residual=residual, **dropped)

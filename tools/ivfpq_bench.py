@@ -8,8 +8,13 @@ Prints: the builds (seconds), device bytes of each index, and for every (n, npro
 (query, row) pairs scanned and the workspace; for every n the yardsticks' times and recalls.  One JSON line at the end (rows also go
 to stderr as they finish); ``--md PATH`` writes the tables as markdown (profiles/ivfpq_bench.md).
 
+``--residual`` adds a leg in the same process on the same rows, lists and queries: ``IVFPQSyllableIndex.build(..., residual=True)`` on
+the first index's centroids (its own codebooks, trained on the residuals), its build time beside a non-residual build from the same
+centroids, its bytes per row, and for every (n, nprobe) its times and recalls beside the non-residual figures of that run -- the only
+valid comparison, boxes differ by some per cent.
+
     python tools/ivfpq_bench.py [--N 4194304] [--nlist 4096] [--M 48] [--ns 16,1024,8192] [--nprobes 1,8,32] [--k 10] [--iters 3]
-                                [--max-iter 10] [--train-rows 262144] [--md profiles/ivfpq_bench.md]"""
+                                [--max-iter 10] [--train-rows 262144] [--residual] [--md profiles/ivfpq_bench.md]"""
 import argparse
 import json
 import os
@@ -58,6 +63,18 @@ def markdown(res):
     for r in h["yardsticks"]:
         out.append("| %d | %.2f | %.2f | %.4f | %.2f | %.4f |" % (r["n"], r["search_ms"], r["pq_rerank_ms"], r["pq_rerank_recall"],
                                                                   r["pq_scan_only_ms"], r["pq_scan_only_recall"]))
+    if "residual" in h:
+        r = h["residual"]
+        out += ["", "Residual codes (`build(..., residual=True)`) on the same centroids, rows and queries, same run: codebooks + codes "
+                "%.1f s against %.1f s for the codes of the rows themselves from the same centroids; %.1f device bytes per row without "
+                "the fp32 rows against %.1f." % (r["build_s"], r["plain_build_s"], r["bytes_codes_only"] / h["N"],
+                                                 h["bytes_ivfpq_codes_only"] / h["N"]), "",
+                "| n | nprobe | residual re-ranked ms | today ms | residual recall@%d | today | residual scan only ms | today ms | "
+                "residual recall@%d | today |" % (h["k"], h["k"]), "|---|---|---|---|---|---|---|---|---|---|"]
+        for r in h["rows"]:
+            out.append("| %d | %d | %.2f | %.2f | %.4f | %.4f | %.2f | %.2f | %.4f | %.4f |" % (
+                r["n"], r["nprobe"], r["res_rerank_ms"], r["ivfpq_rerank_ms"], r["res_rerank_recall"], r["ivfpq_rerank_recall"],
+                r["res_scan_only_ms"], r["ivfpq_scan_only_ms"], r["res_scan_only_recall"], r["ivfpq_scan_only_recall"]))
     return "\n".join(out) + "\n"
 
 
@@ -73,6 +90,7 @@ def main():
     ap.add_argument("--max-iter", type=int, default=10)
     ap.add_argument("--train-rows", type=int, default=262144)
     ap.add_argument("--centres", type=int, default=20000)
+    ap.add_argument("--residual", action="store_true")
     ap.add_argument("--md", default=None)
     args = ap.parse_args()
     from sylber_amd import IVFPQSyllableIndex, IVFSyllableIndex, PQSyllableIndex, SyllableIndex
@@ -106,6 +124,12 @@ def main():
             "train_rows": args.train_rows, "bytes_ivfpq_with_rows": ix.nbytes, "bytes_ivfpq_codes_only": ix.nbytes - 4 * N * D,
             "bytes_pq_codes_only": pq.nbytes - 4 * N * D, "list_rows_min_median_max": [int(sizes.min()), int(statistics.median(sizes)), int(sizes.max())],
             "data": "synthetic mixture of %d Gaussians" % args.centres}
+    rx = None
+    if args.residual:
+        kw = dict(centroids=ix.centroids, seed=0, max_iter=args.max_iter, train_rows=args.train_rows)
+        rx, res_s = timed(lambda: IVFPQSyllableIndex.build(index, None, M, residual=True, **kw))
+        plain_s = timed(lambda: IVFPQSyllableIndex.build(index, None, M, **kw))[1]       # built for its time only
+        head["residual"] = {"build_s": round(res_s, 2), "plain_build_s": round(plain_s, 2), "bytes_codes_only": rx.nbytes - 4 * N * D}
     print(json.dumps(head), file=sys.stderr, flush=True)
     rows, yard = [], []
     for n in [int(v) for v in args.ns.split(",")]:
@@ -129,6 +153,11 @@ def main():
             row.update({"fraction": round(ls["fraction"], 5), "workspace_mb": round(ls["workspace_bytes"] / 2 ** 20, 2),
                         "ivf_ms": round(median_ms(lambda: ivf.search(q, k, nprobe), args.iters), 3),
                         "ivf_recall": recall(ivf.search(q, k, nprobe)[1])})
+            if rx is not None:
+                row.update({"res_rerank_ms": round(median_ms(lambda: rx.search(q, k, nprobe, refine), args.iters), 3),
+                            "res_rerank_recall": recall(rx.search(q, k, nprobe, refine)[1]),
+                            "res_scan_only_ms": round(median_ms(lambda: rx.search(q, k, nprobe, rerank=False), args.iters), 3),
+                            "res_scan_only_recall": recall(rx.search(q, k, nprobe, rerank=False)[1])})
             print(json.dumps(row), file=sys.stderr, flush=True)
             rows.append(row)
         del q
