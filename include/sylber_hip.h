@@ -405,6 +405,38 @@ int sylber_dtw_search(const float* q_dev, int32_t n_blocks, const int32_t* row_m
                       int32_t cuts, const int32_t* phrase_group_dev, const int32_t* seq_group_dev, float* cost_dev, int64_t* seq_dev,
                       int64_t* span_dev, void* workspace_dev, void* stream);
 
+/* Two-stage phrase search (sylber_amd/search.py: SyllableIndex.search_phrases_refined): a 16-bit MFMA subsequence-DTW scan picks m
+ * candidate sequences per phrase, the exact subsequence DTW of sylber_dtw_search re-ranks them.  The result is sylber_dtw_search
+ * restricted to the candidate sequences; with m at least the number of admissible sequences of finite cost it is sylber_dtw_search
+ * bit for bit.  sylber_dtw_plan is called with m in place of k, so that a block's phrases fit the scan's lists.
+ * sylber_dtw16_scan: q16_dev [n_blocks * 128, D] the packed phrase rows of sylber_dtw_search as sylber_knn16_pack rounds them,
+ *   db16_dev [N, D] the database's 16-bit plane (both in `storage`); row_meta_dev, slot_phrase_dev, block_rows_dev, block_phrases,
+ *   seq_id_dev, cut_rows_dev, cuts and the two group arrays as for sylber_dtw_search.  Coarse score t(i, j) = fmaf(-2,
+ *   dot16(q16_i, x16_j), c_j) as sylber_knn16_scan's (c_j = db_norm_dev[j] under L2, 0 under IP); local cost in fp32
+ *   L2: max(0, q_norm_dev[i] + t) with q_norm_dev [n_blocks * 128] = sylber_knn_row_norms of the UNROUNDED packed fp32 rows,
+ *   IP: max(0, 1 - (0 - t / 2)); NaN counts as +inf.  Over these the recurrence of sylber_dtw_search; coarse cost of (phrase,
+ *   sequence) = min_j A[m-1][j].  Candidates of a phrase = its m best (1 <= m <= 128) admissible sequences under (coarse cost,
+ *   sequence number); +inf costs and (with both group arrays) sequences of the phrase's group are not admissible.  cand_dev
+ *   [n_phrases, m] int32 padded with -1, coarse_dev [n_phrases, m] fp32 padded with +inf: bitwise independent of the cuts, of the
+ *   packing and chunking of phrases and of what the workspace held.
+ * sylber_dtw_rerank: q_dev [n_blocks * 128, D] the packed fp32 phrase rows, q_norm_dev as above (L2; may be null under IP),
+ *   phrase_row_dev / phrase_len_dev [n_phrases]: first packed row (sylber_dtw_plan's phrase_row_host) and length of each phrase;
+ *   seq_offsets_dev [n_seq + 1].  For every candidate of cand_dev [n_phrases, m] (-1 = none) the cost, start and end of
+ *   sylber_dtw_search for that (phrase, sequence) pair, bit for bit; pairs of cost +inf dropped; ordered by (cost, sequence), the
+ *   best k (1 <= k <= m) reported and padded as sylber_dtw_search reports them.
+ * workspace_dev of either: sylber_dtw16_workspace_bytes(n_phrases, m, cuts) bytes (-1 on a bad argument); the re-rank may reuse
+ *   the scan's on the same stream. */
+int64_t sylber_dtw16_workspace_bytes(int32_t n_phrases, int32_t m, int32_t cuts);
+int sylber_dtw16_scan(const void* q16_dev, int32_t n_blocks, const int32_t* row_meta_dev, const int32_t* slot_phrase_dev,
+                      const int32_t* block_rows_dev, int32_t n_phrases, int32_t block_phrases, const void* db16_dev, int32_t N, int32_t D,
+                      const float* db_norm_dev, const float* q_norm_dev, int32_t metric, int32_t storage, int32_t m,
+                      const int32_t* seq_id_dev, const int32_t* cut_rows_dev, int32_t cuts, const int32_t* phrase_group_dev,
+                      const int32_t* seq_group_dev, int32_t* cand_dev, float* coarse_dev, void* workspace_dev, void* stream);
+int sylber_dtw_rerank(const float* q_dev, int32_t n_blocks, const float* q_norm_dev, const int32_t* phrase_row_dev,
+                      const int32_t* phrase_len_dev, int32_t n_phrases, const float* db_dev, int32_t N, int32_t D, const float* db_norm_dev,
+                      int32_t metric, const int32_t* cand_dev, int32_t m, const int32_t* seq_offsets_dev, int32_t n_seq, int32_t k,
+                      float* cost_dev, int64_t* seq_dev, int64_t* span_dev, void* workspace_dev, void* stream);
+
 /* Learned quantizer (sylber/model/quantizer.py:6-77, 182-257: `load_quantizer` / `Quantizer`), eval, exact fp32.  The host
  * (sylber_amd/quantizer.py) chains: sylber_lq_norm (input norm / padding) -> sylber_ffenc -> sylber_lq_norm (output norm, blank rows)
  * -> sylber_rvq_assign for the art window and the pitch window -> sylber_lq_norm of the quantized rows.  All data pointers are device

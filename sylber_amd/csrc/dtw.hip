@@ -14,24 +14,13 @@
 // Lists are ordered by (cost, sequence): strict and total over the admissible sequences, so the result is unique.
 #include "kernels.h"
 #include "../../include/sylber_hip.h"
-#include "knn_tile.h"
+#include "dtw_tile.h"
 #include <climits>
 
-constexpr int DT_LD = 132;                                // row stride of the cost tile: lane i reads d[i][t - i], bank (3 i + t) % 32
-constexpr int DT_MAX_M = 64;                              // rows of a phrase: one wave
-constexpr int DT_MAX_SEQ = 65536;                         // rows of a sequence (the DP along a sequence is serial)
-constexpr int DT_FIXED = KN_BM * DT_LD + KN_BN + 132 + KN_BN;   // floats: cost tile (aliases the staging) | c_j | sequence ids | groups
-constexpr int DT_LIST_BYTES = 65536;                      // LDS of a workgroup's lists, 16 B per entry: 32 phrases at k = 128
 constexpr int DT_TARGET_BLOCKS = 512;                     // automatic cuts: (query blocks) x C >= 2 workgroups per CU
 constexpr int DT_MIN_TILES = 4;                           // ... of no less than 4 database tiles on average
 
-static_assert(DT_FIXED * 4 % 16 == 0, "the lists start 16-byte aligned");
 static size_t dt_lds_bytes(int ph, int k) { return (size_t)DT_FIXED * 4 + (size_t)ph * k * 16; }
-static int dt_block_phrases(int k, int block_phrases) {
-    int ph = DT_LIST_BYTES / (16 * k);
-    ph = ph < KN_BM ? ph : KN_BM;
-    return block_phrases > 0 && block_phrases < ph ? block_phrases : ph;
-}
 
 // meta[r] of packed query row r: -1 = padding, else (row of its phrase) | (is the phrase's last row) << 7 | (phrase slot in the block) << 8
 __global__ __launch_bounds__(256) void dtw_search_kernel(const float* __restrict__ q, const float* __restrict__ qsq,

@@ -1,0 +1,430 @@
+// Two-stage phrase search (sylber_amd/search.py: SyllableIndex.search_phrases_refined; contract in include/sylber_hip.h, restated in
+// tests/dtw16_ref.py): a 16-bit MFMA subsequence-DTW scan picks m = k * refine candidate sequences per phrase, the exact fp32
+// subsequence DTW of sylber_dtw_search re-ranks only those.
+//   * dtw16_scan_kernel<FMT>: dtw_search_kernel's structure -- grid (query blocks of whole phrases) x C database cuts on sequence
+//     starts, the 128 x 128 cost tile in LDS aliasing the staging, the anti-diagonal wavefront on waves 0 and 1 with the lane state
+//     carried over tile edges -- around knn16_scan_kernel's contraction (knn16_tile.h: 16-bit staging, v_mfma_f32_32x32x16_{f16,bf16},
+//     K steps of 32).  The C layout is the fp32 MFMA's, so the epilogue that writes the local costs is dtw_search_kernel's with the
+//     coarse score t = fmaf(-2, dot16, c_j) in place of s.  dot16 is one MFMA chain over K in ascending 16-wide steps whatever tile,
+//     cut or block row computes it, and the DP adds in a fixed cell order, so a coarse cost's bits are a function of (phrase,
+//     sequence) alone.  No start is tracked and a list entry is (cost, sequence) without a span: 8 B, half of dtw_search_kernel's.
+//     The C partial lists of a phrase are merged by knn_lists.h's merge.
+//   * dtw_rerank_kernel: one wave per (phrase, candidate) pair, lane l owns phrase row l.  The wave walks the candidate sequence in
+//     chunks of DT_RR_CH columns: for a chunk every lane forms its row's dots with the explicit ascending __builtin_fmaf chain from 0
+//     over D (what v_mfma_f32_32x32x2_f32 performs in dtw_search_kernel, as knn_rerank_kernel relies on), the database row being the
+//     same address in every lane; d goes to LDS and the same wavefront advances over the chunk, its state carried across chunks.  The
+//     lane of the last row tracks (best cost, start, end), the smallest end on ties.  Only the chunk loop depends on the length.
+//   * dtw_rank_kernel: one wave per phrase ranks its m pair results by (cost, sequence) and writes the best k with spans as row ids.
+//     A second launch: nothing relies on an order between workgroups.
+// LDS and occupancy (a CU has 160 KiB):
+//   dtw16_scan_kernel   69 136 B fixed (cost tile 67 584 | c_j, sequence ids, groups) + 8 B x (phrases of the block) x m <= 32 KiB
+//                       of lists = at most 101 904 B: one workgroup of 4 waves per CU (dtw_search_kernel: 134 672 B, also one); two
+//                       per CU while the lists take at most 12 784 B, e.g. 128 phrases at m <= 12 or 32 phrases at m <= 49.  Two
+//                       matter: one workgroup's contraction then hides under the other's wavefront (profiles/phrase_bench.md:
+//                       219 ms against 399 ms for the same work).
+//   dtw_rerank_kernel   9 216 B (64 rows x 36 floats), 64 threads: LDS allows 17 workgroups per CU, so the wave slots and registers
+//                       bound it, not LDS.
+#include "kernels.h"
+#include "../../include/sylber_hip.h"
+#include "dtw_tile.h"
+#include "knn16_tile.h"
+#include "knn_lists.h"
+
+constexpr int DT_RR_CH = 32;                              // columns of a re-rank chunk (RERANK_CHUNK of search.py)
+constexpr int DT_RR_LD = 36;                              // row stride of the chunk's costs: lane i reads d[i][t - i], bank (3 i + t) % 32
+
+static size_t d16_lds_bytes(int ph, int m) { return (size_t)DT_FIXED * 4 + (size_t)ph * m * 8; }
+
+// meta / slot_phrase / block_rows / cuts / groups as dtw_search_kernel.  q: the packed phrase blocks' 16-bit rows [n_blocks * 128, D],
+// qsq: the fp32 ||q_i||^2 of the unrounded packed rows (L2) or null (cosine); x: the 16-bit plane; cn: the fp32 ||x_j||^2 (L2) or null.
+// Writes the sorted best m (cost, sequence) of every phrase over the cut to ps / pi [P][C][m]; entries that did not fill stay
+// (+inf, INT_MAX).
+template <int FMT>
+__global__ __launch_bounds__(256) void dtw16_scan_kernel(const bf16_t* __restrict__ q, const float* __restrict__ qsq,
+                                                         const int32_t* __restrict__ meta, const int32_t* __restrict__ slot_phrase,
+                                                         const int32_t* __restrict__ block_rows, int P, int ph,
+                                                         const bf16_t* __restrict__ x, int N, int D, const float* __restrict__ cn, int m,
+                                                         const int32_t* __restrict__ seqid, const int32_t* __restrict__ cuts,
+                                                         const int32_t* __restrict__ pgrp, const int32_t* __restrict__ sgrp, int C,
+                                                         float* __restrict__ ps, int32_t* __restrict__ pi) {
+    extern __shared__ __attribute__((aligned(16))) float dt_smem[];
+    bf16_t* xs = (bf16_t*)dt_smem;                         // staging of the query rows [128][K16_LD]
+    bf16_t* cs = xs + KN_BM * K16_LD;                      // staging of the database rows
+    float* dm = dt_smem;                                   // [128][DT_LD] local costs of the tile, aliasing the staging
+    float* cns = dt_smem + KN_BM * DT_LD;
+    int* sq = (int*)(cns + KN_BN);                         // [130] sequence of columns n0 - 1 .. n0 + 128 (-1 outside the cut)
+    int* sgs = sq + 132;                                   // [128] group of each column's sequence
+    float* ls = (float*)(sgs + KN_BN);                     // [ph][m] sorted coarse costs
+    int* li = (int*)(ls + ph * m);                         // [ph][m] their sequences
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int wm = wave >> 1, wn = wave & 1;
+    const int b = blockIdx.x, cut = blockIdx.y;
+    int rlo = cuts[cut], rhi = cuts[cut + 1];
+    rlo = rlo < 0 ? 0 : rlo; rhi = rhi > N ? N : rhi;
+    const int nrow = block_rows[b];
+    const int tiles = rhi > rlo ? (rhi - rlo + KN_BN - 1) / KN_BN : 0;
+    for (int e = tid; e < ph * m; e += 256) { ls[e] = INFINITY; li[e] = INT_MAX; }
+    // staging: thread -> operand row tid >> 1, halves [16 (tid & 1), 16 (tid & 1) + 16) of the K step, as knn16_scan_kernel
+    const int sr = tid >> 1, sh = (tid & 1) * 16;
+    const bf16_t* qrow = q + ((size_t)b * KN_BM + sr) * D;
+    bf16_t* xdst = xs + sr * K16_LD + sh;
+    bf16_t* cdst = cs + sr * K16_LD + sh;
+    const int frow = lane & 31, fh = lane >> 5;
+    const int ksteps = (D + K16_BK - 1) / K16_BK, T = ksteps * tiles;
+    bool live[2];                                          // wave-uniform: this wave's 32-row half holds phrase rows
+    float qn[2] = {0.f, 0.f};
+#pragma unroll
+    for (int fm = 0; fm < 2; ++fm) {
+        live[fm] = wm * 64 + fm * 32 < nrow;
+        if (qsq) qn[fm] = qsq[(size_t)b * KN_BM + wm * 64 + fm * 32 + frow];
+    }
+    // the DP's lane state: waves 0 and 1 own packed rows wave * 64 + lane
+    const int drow = (wave & 1) * 64 + lane;
+    const int mt = wave < 2 ? meta[(size_t)b * KN_BM + drow] : -1;
+    const int pi_ = mt & 127, lastrow = (mt >> 7) & 1, slot = (mt >> 8) & 255;
+    const bool valid = mt >= 0 && slot < ph;
+    int maxi = valid ? pi_ : -1;
+#pragma unroll
+    for (int o = 32; o; o >>= 1) { const int v = __shfl_xor(maxi, o); maxi = v > maxi ? v : maxi; }
+    int pg = 0;
+    if (pgrp && valid && lastrow) { const int pid = slot_phrase[(size_t)b * KN_BM + slot]; pg = pid >= 0 && pid < P ? pgrp[pid] : 0; }
+    float a_cur = INFINITY, a_prev = INFINITY, bc = INFINITY;      // A[i][last column done], A[i][the one before], best of the sequence
+
+    f32x16_t acc[2][2];
+    uint4 xa, xb, ca, cb;
+    auto fetch = [&](int t) {
+        const int tile = t / ksteps, k0 = (t % ksteps) * K16_BK;
+        int cr = rlo + tile * KN_BN + sr; cr = cr < rhi ? cr : rhi - 1;
+        const bool in = k0 + sh < D;                       // D % 16 == 0: a last K step of 16 is completed with zeros on both sides
+        const int kc = in ? sh + k0 : 0;                   // the loads stay inside the rows either way
+        const bf16_t* crow = x + (size_t)cr * D + kc;
+        const uint4 z = make_uint4(0, 0, 0, 0);
+        xa = *(const uint4*)(qrow + kc); xb = *(const uint4*)(qrow + kc + 8);
+        ca = *(const uint4*)crow; cb = *(const uint4*)(crow + 8);
+        if (!in) { xa = z; xb = z; ca = z; cb = z; }
+    };
+    if (T > 0) fetch(0);
+    for (int t = 0; t < T; ++t) {
+        const int tile = t / ksteps, ks = t % ksteps, n0 = rlo + tile * KN_BN;
+        if (ks == 0) kn_zero(acc);
+        __syncthreads();                                   // previous fragments, the cost tile, cns / sq / sgs are all read
+        *(uint4*)xdst = xa; *(uint4*)(xdst + 8) = xb;
+        *(uint4*)cdst = ca; *(uint4*)(cdst + 8) = cb;
+        if (ks == 0) {
+            if (tid < KN_BN) {
+                const int j = n0 + tid;
+                cns[tid] = (cn && j < rhi) ? cn[j] : 0.f;
+                sgs[tid] = (sgrp && j < rhi) ? sgrp[seqid[j]] : 0;
+            }
+            if (tid < KN_BN + 2) {
+                const int j = n0 - 1 + tid;
+                sq[tid] = (j >= rlo && j < rhi) ? seqid[j] : -1;
+            }
+        }
+        __syncthreads();
+        if (t + 1 < T) fetch(t + 1);
+        k16_mma<FMT>(xs, cs, wm, wn, frow, fh, acc, live[0], live[1]);
+        if (ks != ksteps - 1) continue;
+        // epilogue: lane holds phrase row wm*64 + fm*32 + frow against columns wn*64 + fn*32 + 8g + 4fh + e.  t = fmaf(-2, dot16, c_j);
+        // d~ = max(0, ||q||^2 + t) (L2) or max(0, 1 - (-t / 2)) (cosine), dtw_search_kernel's expressions; a NaN d~ counts as +inf.
+        __syncthreads();                                   // every wave is past its fragment reads: the cost tile aliases the staging
+#pragma unroll
+        for (int fm = 0; fm < 2; ++fm) {
+            if (!live[fm]) continue;
+            const int rl = wm * 64 + fm * 32 + frow;
+#pragma unroll
+            for (int fn = 0; fn < 2; ++fn)
+#pragma unroll
+                for (int g = 0; g < 4; ++g) {
+                    float d[4];
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        const int cl = wn * 64 + fn * 32 + 8 * g + 4 * fh + e;
+                        const float s = fmaf(-2.0f, acc[fm][fn][4 * g + e], cns[cl]);
+                        const float v = qsq ? qn[fm] + s : 1.0f - (0.f - 0.5f * s);
+                        d[e] = v != v ? INFINITY : fmaxf(0.f, v);
+                    }
+                    *(float4*)(dm + rl * DT_LD + wn * 64 + fn * 32 + 8 * g + 4 * fh) = make_float4(d[0], d[1], d[2], d[3]);
+                }
+        }
+        __syncthreads();
+        if (wave >= 2 || maxi < 0) continue;               // wave-uniform
+        const int ncol = rhi - n0 < KN_BN ? rhi - n0 : KN_BN;
+        const float* dr = dm + drow * DT_LD;
+        for (int st = 0; st < ncol + maxi; ++st) {
+            const float u_cur = __shfl_up(a_cur, 1), u_prev = __shfl_up(a_prev, 1);
+            const int j = st - pi_;
+            bool fin = false;
+            int fseq = 0;
+            if (valid && j >= 0 && j < ncol) {
+                const float d = dr[j];
+                const int sj = sq[j + 1];
+                const bool isstart = sq[j] != sj;
+                float A;
+                if (pi_ == 0) A = d;
+                else {
+                    float best = isstart ? INFINITY : u_prev;          // (i-1, j-1), then (i-1, j), then (i, j-1): the first smallest
+                    if (u_cur < best) best = u_cur;
+                    const float left = isstart ? INFINITY : a_cur;
+                    if (left < best) best = left;
+                    A = d + best;
+                }
+                a_prev = a_cur; a_cur = A;
+                if (lastrow) {
+                    if (isstart) bc = INFINITY;
+                    if (A < bc) bc = A;
+                    if (sq[j + 2] != sj && bc < INFINITY && !(sgrp && sgs[j] == pg)) {
+                        fseq = sj;
+                        fin = kn_better(bc, sj, ls[slot * m + m - 1], li[slot * m + m - 1]);
+                    }
+                }
+            }
+            uint64_t fb = __ballot(fin);
+            while (fb) {
+                const int c = __ffsll((unsigned long long)fb) - 1;
+                fb &= fb - 1;
+                const float v = __shfl(bc, c);
+                const int vs = __shfl(fseq, c), sl = __shfl(slot, c);
+                kn_insert(ls + sl * m, li + sl * m, m, lane, v, vs);
+            }
+        }
+    }
+    __syncthreads();
+    for (int sl = wave; sl < ph; sl += 4) {
+        const int pid = slot_phrase[(size_t)b * KN_BM + sl];
+        if (pid < 0 || pid >= P) break;
+        const size_t o = ((size_t)pid * C + cut) * m;
+        for (int e = lane; e < m; e += 64) { ps[o + e] = ls[sl * m + e]; pi[o + e] = li[sl * m + e]; }
+    }
+}
+
+// the merged lists as candidates: the (+inf, INT_MAX) fillers become (+inf, -1)
+__global__ __launch_bounds__(256) void dtw16_cand_kernel(const float* __restrict__ ls, const int32_t* __restrict__ li, int64_t tot,
+                                                         int32_t* __restrict__ cand, float* __restrict__ coarse) {
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= tot) return;
+    const int j = li[e];
+    cand[e] = j == INT_MAX ? -1 : j;
+    coarse[e] = j == INT_MAX ? INFINITY : ls[e];
+}
+
+// Workgroup (one wave) e of phrase p = blockIdx.x / m: the exact subsequence DTW of phrase p (rows prow[p] .. + plen[p] of the packed
+// fp32 blocks q, qsq their ||q_i||^2 (L2) or null) against sequence cand[p][e] (rows soff[s] .. soff[s + 1] of x).  Writes (cost,
+// (start row, end row)) to pc / pspan [P][m]; (+inf, (-1, -1)) for a candidate of -1.
+__global__ __launch_bounds__(64) void dtw_rerank_kernel(const float* __restrict__ q, const float* __restrict__ qsq, int qrows,
+                                                        const int32_t* __restrict__ prow, const int32_t* __restrict__ plen,
+                                                        const float* __restrict__ x, int N, int D, const float* __restrict__ cn,
+                                                        const int32_t* __restrict__ cand, const int32_t* __restrict__ soff, int S,
+                                                        int m, float* __restrict__ pc, int2* __restrict__ pspan) {
+    __shared__ float dsm[DT_MAX_M * DT_RR_LD];
+    const int lane = threadIdx.x;
+    const size_t pair = blockIdx.x;
+    const int p = (int)(pair / m);
+    const int sidx = cand[pair];
+    int j0 = 0, j1 = 0;
+    if (sidx >= 0 && sidx < S) {
+        j0 = soff[sidx]; j1 = soff[sidx + 1];
+        j0 = j0 < 0 ? 0 : j0; j1 = j1 > N ? N : j1;
+    }
+    if (j1 <= j0) {                                        // workgroup-uniform
+        if (lane == 0) { pc[pair] = INFINITY; pspan[pair] = make_int2(-1, -1); }
+        return;
+    }
+    int mp = plen[p];
+    mp = mp < 1 ? 1 : (mp > DT_MAX_M ? DT_MAX_M : mp);
+    int r = prow[p] + (lane < mp ? lane : mp - 1);         // lanes behind the phrase read its last row and keep nothing
+    r = r < 0 ? 0 : (r < qrows ? r : qrows - 1);
+    const float* qr = q + (size_t)r * D;
+    const float qn = qsq ? qsq[r] : 0.f;
+    const bool valid = lane < mp, lastrow = lane == mp - 1;
+    float a_cur = INFINITY, a_prev = INFINITY, bc = INFINITY;
+    int s_cur = 0, s_prev = 0, bst = -1, be = -1;
+    float* dr = dsm + lane * DT_RR_LD;
+    for (int n0 = j0; n0 < j1; n0 += DT_RR_CH) {
+        const int ncol = j1 - n0 < DT_RR_CH ? j1 - n0 : DT_RR_CH;
+        // dot[jj] = the fmaf chain over ascending c from 0 of q_lane . x_(n0 + jj): explicit __builtin_fmaf calls, nothing for the
+        // compiler to contract or reassociate; columns past the sequence repeat its last row and are not read by the DP
+        float dot[DT_RR_CH];
+#pragma unroll
+        for (int jj = 0; jj < DT_RR_CH; ++jj) dot[jj] = 0.f;
+        for (int c = 0; c < D; c += 4) {
+            const float4 a = *(const float4*)(qr + c);
+#pragma unroll
+            for (int jj = 0; jj < DT_RR_CH; ++jj) {
+                const int j = jj < ncol ? n0 + jj : j1 - 1;
+                const float4 bv = *(const float4*)(x + (size_t)j * D + c);
+                dot[jj] = __builtin_fmaf(bv.x, a.x, dot[jj]);
+                dot[jj] = __builtin_fmaf(bv.y, a.y, dot[jj]);
+                dot[jj] = __builtin_fmaf(bv.z, a.z, dot[jj]);
+                dot[jj] = __builtin_fmaf(bv.w, a.w, dot[jj]);
+            }
+        }
+        __syncthreads();                                   // the previous chunk's costs are read
+#pragma unroll
+        for (int jj = 0; jj < DT_RR_CH; ++jj) {
+            const int j = jj < ncol ? n0 + jj : j1 - 1;
+            const float s = __builtin_fmaf(-2.0f, dot[jj], cn ? cn[j] : 0.f);
+            const float v = qsq ? qn + s : 1.0f - (0.f - 0.5f * s);
+            dr[jj] = v != v ? INFINITY : fmaxf(0.f, v);
+        }
+        __syncthreads();
+        for (int st = 0; st < ncol + mp - 1; ++st) {
+            const float u_cur = __shfl_up(a_cur, 1), u_prev = __shfl_up(a_prev, 1);
+            const int us_cur = __shfl_up(s_cur, 1), us_prev = __shfl_up(s_prev, 1);
+            const int j = st - lane;
+            if (valid && j >= 0 && j < ncol) {
+                const float d = dr[j];
+                const bool isstart = n0 + j == j0;
+                float A;
+                int sa;
+                if (lane == 0) { A = d; sa = n0 + j; }
+                else {
+                    float best = isstart ? INFINITY : u_prev;          // (i-1, j-1), then (i-1, j), then (i, j-1): the first smallest
+                    int bs = us_prev;
+                    if (u_cur < best) { best = u_cur; bs = us_cur; }
+                    const float left = isstart ? INFINITY : a_cur;
+                    if (left < best) { best = left; bs = s_cur; }
+                    A = d + best; sa = bs;
+                }
+                a_prev = a_cur; s_prev = s_cur; a_cur = A; s_cur = sa;
+                if (lastrow && A < bc) { bc = A; bst = sa; be = n0 + j; }      // the smallest end column on ties
+            }
+        }
+    }
+    if (lastrow) {
+        pc[pair] = bc;
+        pspan[pair] = bc < INFINITY ? make_int2(bst, be) : make_int2(-1, -1);
+    }
+}
+
+// One wave per phrase i (4 per workgroup).  Lane e (and e + 64) owns pair (i, cand[i][e]); a candidate of -1 or a cost that is not
+// below +inf becomes a (+inf, INT_MAX) filler.  Rank = entries strictly before it under (cost, sequence, position) (the position
+// only orders the fillers); ranks < k are reported as dtw_finish_kernel reports them: spans as (first row, one past the last row),
+// fillers (+inf, -1, (-1, -1)).
+__global__ __launch_bounds__(256) void dtw_rank_kernel(const float* __restrict__ pc, const int2* __restrict__ pspan,
+                                                       const int32_t* __restrict__ cand, int P, int m, int k, float* __restrict__ cost,
+                                                       int64_t* __restrict__ seq, int64_t* __restrict__ span) {
+    __shared__ float ss[4][KN_KMAX];
+    __shared__ int si[4][KN_KMAX];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    int i = blockIdx.x * 4 + wave;
+    const bool live = i < P;
+    i = live ? i : P - 1;
+    float sv[KN_KMAX / 64];
+    int sj[KN_KMAX / 64];
+#pragma unroll
+    for (int h = 0; h < KN_KMAX / 64; ++h) {
+        const int e = lane + 64 * h;
+        sv[h] = INFINITY; sj[h] = INT_MAX;
+        if (e < m) {
+            const float v = pc[(size_t)i * m + e];
+            const int j = cand[(size_t)i * m + e];
+            if (j >= 0 && v < INFINITY) { sv[h] = v; sj[h] = j; }
+            ss[wave][e] = sv[h]; si[wave][e] = sj[h];
+        }
+    }
+    __syncthreads();
+    if (!live) return;
+#pragma unroll
+    for (int h = 0; h < KN_KMAX / 64; ++h) {
+        const int e = lane + 64 * h;
+        if (e >= m) continue;
+        int rank = 0;
+        for (int f = 0; f < m; ++f) {
+            const float ev = ss[wave][f];
+            const int ej = si[wave][f];
+            rank += (kn_better(ev, ej, sv[h], sj[h]) || (ev == sv[h] && ej == sj[h] && f < e)) ? 1 : 0;
+        }
+        if (rank < k) {
+            const size_t o = (size_t)i * k + rank;
+            if (sj[h] == INT_MAX) { cost[o] = INFINITY; seq[o] = -1; span[2 * o] = -1; span[2 * o + 1] = -1; }
+            else {
+                const int2 sp = pspan[(size_t)i * m + e];
+                cost[o] = sv[h]; seq[o] = sj[h]; span[2 * o] = sp.x; span[2 * o + 1] = (int64_t)sp.y + 1;
+            }
+        }
+    }
+}
+
+static int64_t d16_rerank_bytes(int64_t P, int64_t m) { return kn_al(P * m * 4) + kn_al(P * m * 8); }
+
+extern "C" int64_t sylber_dtw16_workspace_bytes(int32_t n_phrases, int32_t m, int32_t cuts) {
+    if (n_phrases < 1 || m < 1 || m > KN_KMAX || cuts < 1) return -1;
+    // the C partial lists of the scan and their merge rounds (KnPartials); then, in the same bytes, the pair results of the re-rank
+    const int64_t scan = kn_partials_bytes(n_phrases, cuts, m), rr = d16_rerank_bytes(n_phrases, m);
+    return scan > rr ? scan : rr;
+}
+
+extern "C" int sylber_dtw16_scan(const void* q16_dev, int32_t n_blocks, const int32_t* row_meta_dev, const int32_t* slot_phrase_dev,
+                                 const int32_t* block_rows_dev, int32_t n_phrases, int32_t block_phrases, const void* db16_dev, int32_t N,
+                                 int32_t D, const float* db_norm_dev, const float* q_norm_dev, int32_t metric, int32_t storage, int32_t m,
+                                 const int32_t* seq_id_dev, const int32_t* cut_rows_dev, int32_t cuts, const int32_t* phrase_group_dev,
+                                 const int32_t* seq_group_dev, int32_t* cand_dev, float* coarse_dev, void* workspace_dev, void* stream) {
+    static const char* what = "sylber_dtw16_scan";
+    hipStream_t s = (hipStream_t)stream;
+    if (!q16_dev || !row_meta_dev || !slot_phrase_dev || !block_rows_dev || !db16_dev || !seq_id_dev || !cut_rows_dev || !cand_dev ||
+        !coarse_dev || !workspace_dev) { syl_set_error(what, "null argument"); return 1; }
+    if (n_blocks < 1 || n_phrases < 1 || N < 1 || D < 16 || D % 16) { syl_set_error(what, "need n_blocks, n_phrases, N >= 1 and D a multiple of 16"); return 1; }
+    if (m < 1 || m > KN_KMAX) { syl_set_error(what, "need 1 <= m <= 128"); return 1; }
+    if (block_phrases < 1 || block_phrases > dt_block_phrases(m, 0)) { syl_set_error(what, "block_phrases exceeds what sylber_dtw_plan allows for this m"); return 1; }
+    if (cuts < 1 || cuts > 65535) { syl_set_error(what, "need 1 <= cuts <= 65535"); return 1; }
+    if (metric != SYLBER_KNN_L2 && metric != SYLBER_KNN_IP) { syl_set_error(what, "unknown metric"); return 1; }
+    if (storage != SYLBER_KNN16_FP16 && storage != SYLBER_KNN16_BF16) { syl_set_error(what, "unknown storage"); return 1; }
+    if (metric == SYLBER_KNN_L2 && (!db_norm_dev || !q_norm_dev)) { syl_set_error(what, "the L2 metric needs db_norm_dev and q_norm_dev"); return 1; }
+    if (!phrase_group_dev != !seq_group_dev) { syl_set_error(what, "phrase_group_dev and seq_group_dev go together"); return 1; }
+    if ((int64_t)n_phrases * cuts * m > INT32_MAX / 2) { syl_set_error(what, "n_phrases x cuts x m is too large: use smaller phrase chunks"); return 1; }
+    char* w = (char*)workspace_dev;
+    KnPartials p = kn_partials_carve(w, n_phrases, cuts, m);
+    const size_t lds = d16_lds_bytes(block_phrases, m);
+    const int max_lds = (int)((size_t)DT_FIXED * 4 + DT_LIST_BYTES / 2);
+    const bf16_t* q16 = (const bf16_t*)q16_dev;
+    const bf16_t* x16 = (const bf16_t*)db16_dev;
+    const float* qn = metric == SYLBER_KNN_L2 ? q_norm_dev : nullptr;
+    const float* cn = metric == SYLBER_KNN_L2 ? db_norm_dev : nullptr;
+    const dim3 grid((unsigned)n_blocks, (unsigned)cuts);
+    if (storage == SYLBER_KNN16_FP16) {
+        static PerDeviceOnce once;
+        if (once.need()) HIP_TRY(hipFuncSetAttribute((const void*)dtw16_scan_kernel<FMT_F16>, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds));
+        hipLaunchKernelGGL(dtw16_scan_kernel<FMT_F16>, grid, dim3(256), lds, s, q16, qn, row_meta_dev, slot_phrase_dev, block_rows_dev, n_phrases,
+                           block_phrases, x16, N, D, cn, m, seq_id_dev, cut_rows_dev, phrase_group_dev, seq_group_dev, cuts, p.s0, p.i0);
+    } else {
+        static PerDeviceOnce once;
+        if (once.need()) HIP_TRY(hipFuncSetAttribute((const void*)dtw16_scan_kernel<FMT_BF16>, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds));
+        hipLaunchKernelGGL(dtw16_scan_kernel<FMT_BF16>, grid, dim3(256), lds, s, q16, qn, row_meta_dev, slot_phrase_dev, block_rows_dev, n_phrases,
+                           block_phrases, x16, N, D, cn, m, seq_id_dev, cut_rows_dev, phrase_group_dev, seq_group_dev, cuts, p.s0, p.i0);
+    }
+    HIP_TRY(hipGetLastError());
+    if (kn_merge_lists(p, n_phrases, cuts, m, s)) return 1;
+    const int64_t tot = (int64_t)n_phrases * m;
+    hipLaunchKernelGGL(dtw16_cand_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, p.s0, p.i0, tot, cand_dev, coarse_dev);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+extern "C" int sylber_dtw_rerank(const float* q_dev, int32_t n_blocks, const float* q_norm_dev, const int32_t* phrase_row_dev,
+                                 const int32_t* phrase_len_dev, int32_t n_phrases, const float* db_dev, int32_t N, int32_t D,
+                                 const float* db_norm_dev, int32_t metric, const int32_t* cand_dev, int32_t m, const int32_t* seq_offsets_dev,
+                                 int32_t n_seq, int32_t k, float* cost_dev, int64_t* seq_dev, int64_t* span_dev, void* workspace_dev,
+                                 void* stream) {
+    static const char* what = "sylber_dtw_rerank";
+    hipStream_t s = (hipStream_t)stream;
+    if (!q_dev || !phrase_row_dev || !phrase_len_dev || !db_dev || !cand_dev || !seq_offsets_dev || !cost_dev || !seq_dev || !span_dev ||
+        !workspace_dev) { syl_set_error(what, "null argument"); return 1; }
+    if (n_blocks < 1 || n_phrases < 1 || N < 1 || n_seq < 1 || D < 16 || D % 16) { syl_set_error(what, "need n_blocks, n_phrases, N, n_seq >= 1 and D a multiple of 16"); return 1; }
+    if (m < 1 || m > KN_KMAX || k < 1 || k > m) { syl_set_error(what, "need 1 <= k <= m <= 128"); return 1; }
+    if (metric != SYLBER_KNN_L2 && metric != SYLBER_KNN_IP) { syl_set_error(what, "unknown metric"); return 1; }
+    if (metric == SYLBER_KNN_L2 && (!db_norm_dev || !q_norm_dev)) { syl_set_error(what, "the L2 metric needs db_norm_dev and q_norm_dev"); return 1; }
+    if ((int64_t)n_blocks * KN_BM > INT32_MAX || (int64_t)n_phrases * m > INT32_MAX) { syl_set_error(what, "n_phrases x m is too large: use smaller phrase chunks"); return 1; }
+    char* w = (char*)workspace_dev;
+    float* pc = (float*)w; w += kn_al((int64_t)n_phrases * m * 4);
+    int2* pspan = (int2*)w;
+    const float* qn = metric == SYLBER_KNN_L2 ? q_norm_dev : nullptr;
+    const float* cn = metric == SYLBER_KNN_L2 ? db_norm_dev : nullptr;
+    hipLaunchKernelGGL(dtw_rerank_kernel, dim3((unsigned)((int64_t)n_phrases * m)), dim3(64), 0, s, q_dev, qn, n_blocks * KN_BM, phrase_row_dev,
+                       phrase_len_dev, db_dev, N, D, cn, cand_dev, seq_offsets_dev, n_seq, m, pc, pspan);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(dtw_rank_kernel, dim3((unsigned)((n_phrases + 3) / 4)), dim3(256), 0, s, pc, pspan, cand_dev, n_phrases, m, k, cost_dev,
+                       seq_dev, span_dev);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}

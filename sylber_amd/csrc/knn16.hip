@@ -14,11 +14,9 @@
 #include "../../include/sylber_hip.h"
 #include "knn_tile.h"
 #include "knn_lists.h"
+#include "knn16_tile.h"
 
-constexpr int K16_BK = 32;                                // halves per K step through LDS: two MFMAs of K = 16 per fragment pair
-constexpr int K16_LD = 40;                                // LDS row stride in halves (80 B: 16-byte aligned, staggered banks)
 constexpr int K16_STRIP = 32, K16_SP = 132;               // epilogue strip: 32 query rows x 128 scores, row stride 132 floats
-static_assert(2 * KN_BM * K16_LD * 2 == KN_STAGE * 4, "the 16-bit staging fills the fp32 kernel's staging exactly (the strip aliases it)");
 
 template <int FMT> __device__ __forceinline__ bf16_t k16_cvt(float f) { return f2bf_dev(f); }
 // IEEE half, saturating: NaN stays NaN, everything else is clamped to +-65504 before the (round to nearest even) conversion.  Not

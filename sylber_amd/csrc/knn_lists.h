@@ -1,6 +1,6 @@
-// The list kernels that knn.hip (sylber_knn_search, sylber_ivf_search), knn16.hip (sylber_knn16_scan) and pq.hip (sylber_pq_scan,
-// sylber_ivfpq_scan) share: the pairwise merge of sorted partial lists and the reported values.  They are static: each translation
-// unit that launches them carries its own copy.  Below knn_merge_kernel is the host side of the merge, written once for those five
+// The list kernels that knn.hip (sylber_knn_search, sylber_ivf_search), knn16.hip (sylber_knn16_scan), pq.hip (sylber_pq_scan,
+// sylber_ivfpq_scan) and dtw16.hip (sylber_dtw16_scan) share: the pairwise merge of sorted partial lists and the reported values.  They are static: each translation
+// unit that launches them carries its own copy.  Below knn_merge_kernel is the host side of the merge, written once for those
 // entry points: where the partial lists lie in a workspace (KnPartials, kn_partials_bytes, kn_partials_carve) and the merge rounds
 // (kn_merge_lists).  dtw.hip merges lists with a payload and keeps its own.
 #pragma once

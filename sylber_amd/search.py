@@ -13,7 +13,8 @@ Contract (tests/knn_ref.py restates it in numpy)::
 
 ``SyllableIndex.search_phrases`` searches for a *sequence* of syllables: subsequence DTW of each phrase against every sequence (by
 default: clip) of the index, in the epilogue of the same contraction (csrc/dtw.hip, ``sylber_dtw_search``); its contract is in the
-method's docstring, restated in numpy in tests/dtw_ref.py.
+method's docstring, restated in numpy in tests/dtw_ref.py.  ``SyllableIndex.search_phrases_refined`` is its two-stage form (csrc/dtw16.hip:
+a 16-bit MFMA scan picks candidate sequences, the exact DTW re-ranks them; tests/dtw16_ref.py).
 
 The rules that every index shares -- argument checks, row preparation, result buffers, provenance, the list layout, the arrays of a
 saved file -- are in _index.py, each once; this file and pq.py hold what differs between the indexes.
@@ -37,6 +38,28 @@ MAX_PHRASE_ROWS = 64            # DT_MAX_M of csrc/dtw.hip: one wave holds a phr
 MAX_SEQUENCE_ROWS = 65536       # DT_MAX_SEQ: the DP along one sequence is serial
 DEFAULT_PHRASE_CHUNK = 4096
 STORAGES = {"fp16": (0, torch.float16), "bf16": (1, torch.bfloat16)}     # SYLBER_KNN16_FP16 / _BF16: the planes of search_refined
+RERANK_CHUNK = 32               # DT_RR_CH of csrc/dtw16.hip: the columns of a sequence that search_phrases_refined re-ranks at a time
+
+
+def _phrase_outputs(P: int, k: int, device):
+    """``(costs fp32 [P, k], seqs int64 [P, k], spans int64 [P, k, 2])`` of a phrase search"""
+    return (torch.empty((P, k), dtype=torch.float32, device=device), torch.empty((P, k), dtype=torch.int64, device=device),
+            torch.empty((P, k, 2), dtype=torch.int64, device=device))
+
+
+class _PhraseBlocks:
+    """one chunk of phrases as ``sylber_dtw_plan`` packs it: ``Pc`` phrases in ``nb`` blocks of 128 rows (``qp``, padding rows zero)
+    against ``C`` cuts; ``slots`` = the most phrases in any block; ``place`` / ``ln``: first packed row and length of each phrase"""
+
+    def __init__(self, dev, Pc, nb, C, slots, place, ln, qp, meta, slot_phrase, block_rows, cut_rows, pg):
+        self.dev, self.Pc, self.nb, self.C, self.slots, self.place, self.ln, self.qp = dev, Pc, nb, C, slots, place, ln, qp
+        self._host = (meta, slot_phrase, block_rows, cut_rows)
+        self._pg = pg
+
+    def tables(self):
+        """``(row meta, slot -> phrase, rows per block, cut rows, the phrases' groups or None)`` on the device"""
+        meta_d, sp_d, br_d, cut_d = (torch.from_numpy(a).to(self.dev) for a in self._host)
+        return meta_d, sp_d, br_d, cut_d, (_on_device(self._pg, np.int32, self.dev) if self._pg is not None else None)
 
 
 class SyllableIndex:
@@ -298,8 +321,100 @@ class SyllableIndex:
         on sequence starts only), ``phrase_chunk`` bounds the phrases per launch (and so the workspace), ``block_phrases`` (0 =
         automatic) the phrases packed into one 128-row query block."""
         k = _check_k_refine(k)[0]
+        q, lens, pg, off = self._phrase_args(phrases, lengths, groups, exclude_same_group, sequences, splits, phrase_chunk, block_phrases)
+        P = int(lens.size)
+        dev = self.device
+        costs, seqs, spans = _phrase_outputs(P, k, dev)
+        if P == 0:
+            return costs, seqs, spans
+        lib = _lib.load()
+        qd = self._prep(q)
         N = len(self)
-        if N == 0:
+        seq_id, seq_grp = self._sequence_tables(off, pg is not None)
+        metric = METRICS[self.metric]
+        with torch.cuda.device(dev):
+            for p0 in range(0, P, int(phrase_chunk)):
+                p1 = min(P, p0 + int(phrase_chunk))
+                b = self._phrase_blocks(lib, qd, lens, p0, p1, off, k, splits, block_phrases, pg)
+                nbytes = int(lib.sylber_dtw_workspace_bytes(b.nb, b.Pc, k, b.C))
+                ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+                if _workspace_fill is not None:
+                    ws.fill_(_workspace_fill)
+                meta_d, sp_d, br_d, cut_d, pg_d = b.tables()
+                _lib.check(lib.sylber_dtw_search(_vp(b.qp), b.nb, _vp(meta_d), _vp(sp_d), _vp(br_d), b.Pc, b.slots, _vp(self._x), N,
+                                                 self.dim, _vp(self._c), metric, k, _vp(seq_id), _vp(cut_d), b.C, _vp(pg_d), _vp(seq_grp),
+                                                 _vp(costs[p0:p1]), _vp(seqs[p0:p1]), _vp(spans[p0:p1]), _vp(ws), _stream(dev)),
+                           "sylber_dtw_search")
+        return costs, seqs, spans
+
+    def search_phrases_refined(self, phrases, k: int, refine: int = 4, storage: str = "fp16", *, lengths=None, groups=None,
+                               exclude_same_group: bool = False, sequences=None, splits: int = 0,
+                               phrase_chunk: int = DEFAULT_PHRASE_CHUNK, block_phrases: int = 0, return_candidates: bool = False,
+                               _workspace_fill=None):
+        """two-stage ``search_phrases``: a 16-bit MFMA subsequence-DTW scan of ``half_rows(storage)`` picks ``m = k * refine`` candidate
+        sequences per phrase, the exact fp32 subsequence DTW re-ranks only those -> ``(costs, seqs, spans)`` shaped, typed, ordered,
+        padded and placed exactly as ``search_phrases``'s; with ``return_candidates=True`` also ``cand`` int64 ``[P, m]`` (the stage-1
+        sequence numbers in stage-1 order, padded with -1) and ``coarse`` fp32 ``[P, m]`` (their stage-1 costs, padded with ``+inf``).
+
+        Stage 1: the phrase rows, prepared as ``search_phrases`` prepares them, and the stored rows are rounded to 16 bits as
+        ``search_refined`` rounds them (round to nearest even, NaN stays NaN, fp16 saturates at +-65504; phrases are never
+        refused); ``t(i, j) = fmaf(-2, dot16(q~_i, x~_j), c_j)`` is ``search_refined``'s coarse score.  Local cost in fp32:
+        ``"l2"``: ``d~ = max(0, ||q_i||^2 + t)`` with the fp32 ``||q_i||^2`` of the *unrounded* phrase row; ``"cosine"``:
+        ``d~ = max(0, 1 - (0 - t / 2))``; a NaN ``d~`` counts as ``+inf``.  Over ``d~`` the recurrence of ``search_phrases``, one
+        fp32 addition per cell; the coarse cost of (phrase, sequence) is ``min_j A[m-1][j]``.  The candidates of a phrase are its m
+        best admissible sequences under (coarse cost, sequence number); a cost of ``+inf`` and, with ``exclude_same_group``, the
+        phrase's own group are not admissible.  Stage 2: for each candidate the exact ``search_phrases`` cost, start and end of that
+        (phrase, sequence) pair, bit for bit; order (cost, sequence), keep k.
+
+        So the result is ``search_phrases`` restricted to the candidate sequences -- every returned cost and span is a real
+        ``search_phrases`` cost and span -- and with m at least the number of admissible sequences of finite cost it *is*
+        ``search_phrases``, bit for bit.  The only approximation is which sequences get re-ranked; ``refine`` controls it.  ``cand``,
+        ``coarse``, costs, seqs and spans do not depend on ``splits``, ``phrase_chunk``, ``block_phrases``, stale workspace contents
+        or how the index was built.  All of ``search_phrases``'s limits, integer ``refine >= 1``, ``k * refine <= 128``,
+        ``storage`` ``"fp16"`` (refuses stored values beyond +-65504, as ``half_rows`` does) or ``"bf16"``."""
+        k, m = _check_k_refine(k, refine, rerank=True)
+        if storage not in STORAGES:
+            raise ValueError("storage must be 'fp16' or 'bf16', got %r" % (storage,))
+        q, lens, pg, off = self._phrase_args(phrases, lengths, groups, exclude_same_group, sequences, splits, phrase_chunk, block_phrases)
+        P = int(lens.size)
+        dev = self.device
+        costs, seqs, spans = _phrase_outputs(P, k, dev)
+        cand = torch.empty((P, m), dtype=torch.int32, device=dev)
+        coarse = torch.empty((P, m), dtype=torch.float32, device=dev)
+        if P == 0:
+            return (costs, seqs, spans, cand.to(torch.int64), coarse) if return_candidates else (costs, seqs, spans)
+        x16 = self.half_rows(storage)
+        lib = _lib.load()
+        qd = self._prep(q)
+        N, S = len(self), off.size - 1
+        seq_id, seq_grp = self._sequence_tables(off, pg is not None)
+        off_d = _on_device(off, np.int32, dev)
+        metric, code = METRICS[self.metric], STORAGES[storage][0]
+        with torch.cuda.device(dev):
+            st = _stream(dev)
+            for p0 in range(0, P, int(phrase_chunk)):
+                p1 = min(P, p0 + int(phrase_chunk))
+                b = self._phrase_blocks(lib, qd, lens, p0, p1, off, m, splits, block_phrases, pg)
+                qn = _row_norms(b.qp) if self.metric == "l2" else None       # the ||q||^2 that sylber_dtw_search adds, same kernel
+                q16 = self._pack16(b.qp, storage, refuse=False)
+                ws = torch.empty(int(lib.sylber_dtw16_workspace_bytes(b.Pc, m, b.C)), dtype=torch.uint8, device=dev)
+                if _workspace_fill is not None:
+                    ws.fill_(_workspace_fill)
+                meta_d, sp_d, br_d, cut_d, pg_d = b.tables()
+                place_d, len_d = _on_device(b.place, np.int32, dev), _on_device(b.ln, np.int32, dev)
+                _lib.check(lib.sylber_dtw16_scan(_vp(q16), b.nb, _vp(meta_d), _vp(sp_d), _vp(br_d), b.Pc, b.slots, _vp(x16), N, self.dim,
+                                                 _vp(self._c), _vp(qn), metric, code, m, _vp(seq_id), _vp(cut_d), b.C, _vp(pg_d),
+                                                 _vp(seq_grp), _vp(cand[p0:p1]), _vp(coarse[p0:p1]), _vp(ws), st), "sylber_dtw16_scan")
+                _lib.check(lib.sylber_dtw_rerank(_vp(b.qp), b.nb, _vp(qn), _vp(place_d), _vp(len_d), b.Pc, _vp(self._x), N, self.dim,
+                                                 _vp(self._c), metric, _vp(cand[p0:p1]), m, _vp(off_d), S, k, _vp(costs[p0:p1]),
+                                                 _vp(seqs[p0:p1]), _vp(spans[p0:p1]), _vp(ws), st), "sylber_dtw_rerank")
+        return (costs, seqs, spans, cand.to(torch.int64), coarse) if return_candidates else (costs, seqs, spans)
+
+    # the arguments and the plumbing that search_phrases and search_phrases_refined share
+    def _phrase_args(self, phrases, lengths, groups, exclude_same_group, sequences, splits, phrase_chunk, block_phrases):
+        """the checks of a phrase search -> ``(phrase rows [sum m, D] as given, lengths int64 [P], the phrases' groups on the host or
+        None, sequence offsets int64 [S + 1])``, or ``ValueError``"""
+        if len(self) == 0:
             raise ValueError("the index is empty")
         if lengths is None:
             if torch.is_tensor(phrases) or isinstance(phrases, np.ndarray):
@@ -323,64 +438,49 @@ class SyllableIndex:
         pg = _query_groups(groups, P, exclude_same_group, None, "phrases")         # on the host: a chunk's groups go to the device with it
         if int(splits) < 0 or int(phrase_chunk) < 1 or int(block_phrases) < 0:
             raise ValueError("splits and block_phrases must be >= 0 and phrase_chunk >= 1")
-        off = self._sequences(sequences)
+        return q, lens, pg, self._sequences(sequences)
+
+    def _sequence_tables(self, off: np.ndarray, with_groups: bool):
+        """plumbing: the sequence of every row and (for the exclusion) the group of every sequence, on the device"""
         dev = self.device
-        costs = torch.empty((P, k), dtype=torch.float32, device=dev)
-        seqs = torch.empty((P, k), dtype=torch.int64, device=dev)
-        spans = torch.empty((P, k, 2), dtype=torch.int64, device=dev)
-        if P == 0:
-            return costs, seqs, spans
-        lib = _lib.load()
-        qd = self._prep(q)
+        off_d = torch.from_numpy(off).to(dev)
+        seq_id = torch.repeat_interleave(torch.arange(off.size - 1, dtype=torch.int32, device=dev), off_d[1:] - off_d[:-1])
+        return seq_id, (self._g.index_select(0, off_d[:-1]) if with_groups else None)
+
+    def _phrase_blocks(self, lib, qd, lens, p0: int, p1: int, off, list_size: int, splits, block_phrases, pg) -> "_PhraseBlocks":
+        """phrases ``p0 : p1`` of the prepared rows ``qd`` packed by ``sylber_dtw_plan`` for lists of ``list_size`` entries: the
+        packed layout of the chunk's rows (where each row goes, what it is, which phrase owns each slot), the rows scattered into
+        zeroed 128-row blocks, and the cut table"""
+        dev = self.device
         S = off.size - 1
         off32 = np.ascontiguousarray(off, np.int32)
-        # plumbing: the sequence of every row and (for the exclusion) the group of every sequence
-        off_d = torch.from_numpy(off).to(dev)
-        seq_id = torch.repeat_interleave(torch.arange(S, dtype=torch.int32, device=dev), off_d[1:] - off_d[:-1])
-        seq_grp = self._g.index_select(0, off_d[:-1]) if pg is not None else None
         i32p = ctypes.POINTER(ctypes.c_int32)
-        metric = METRICS[self.metric]
-        row0 = np.concatenate([[0], np.cumsum(lens)])
-        step = int(phrase_chunk)
-        with torch.cuda.device(dev):
-            for p0 in range(0, P, step):
-                p1 = min(P, p0 + step)
-                Pc = p1 - p0
-                ln = np.ascontiguousarray(lens[p0:p1], np.int32)
-                nb, ph = ctypes.c_int32(0), ctypes.c_int32(0)
-                place = np.empty(Pc, np.int32)
-                args = (off32.ctypes.data_as(i32p), S, ln.ctypes.data_as(i32p), Pc, k, int(splits), int(block_phrases))
-                C = int(lib.sylber_dtw_plan(*args, None, 0, place.ctypes.data_as(i32p), ctypes.byref(nb), ctypes.byref(ph)))
-                cut_rows = np.empty(max(C, 1) + 1, np.int32)
-                if C < 1 or int(lib.sylber_dtw_plan(*args, cut_rows.ctypes.data_as(i32p), C + 1, None, None, None)) != C:
-                    raise _lib.SylberHipError("sylber_dtw_plan failed (%d)" % C)
-                nb = nb.value
-                # the packed layout of the chunk's rows (plumbing): where each row goes, what it is, which phrase owns each slot
-                R = int(ln.sum())
-                first = np.repeat(place.astype(np.int64), ln)
-                local = np.arange(R) - np.repeat(np.cumsum(ln) - ln, ln)
-                blk = place // 128
-                slot = np.arange(Pc) - np.searchsorted(blk, blk, side="left")
-                meta = np.full(nb * 128, -1, np.int32)
-                meta[first + local] = local | ((local == np.repeat(ln, ln) - 1).astype(np.int64) << 7) | (np.repeat(slot, ln) << 8)
-                slot_phrase = np.full(nb * 128, -1, np.int32)
-                slot_phrase[blk.astype(np.int64) * 128 + slot] = np.arange(Pc)
-                block_rows = np.zeros(nb, np.int32)
-                np.maximum.at(block_rows, blk, place % 128 + ln)
-                qp = torch.zeros((nb * 128, self.dim), dtype=torch.float32, device=dev)
-                qp[torch.from_numpy(first + local).to(dev)] = qd[int(row0[p0]):int(row0[p1])]
-                nbytes = int(lib.sylber_dtw_workspace_bytes(nb, Pc, k, C))
-                ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-                if _workspace_fill is not None:
-                    ws.fill_(_workspace_fill)
-                meta_d, sp_d, br_d = (torch.from_numpy(a).to(dev) for a in (meta, slot_phrase, block_rows))
-                cut_d = torch.from_numpy(cut_rows).to(dev)
-                pg_d = _on_device(pg[p0:p1], np.int32, dev) if pg is not None else None
-                _lib.check(lib.sylber_dtw_search(_vp(qp), nb, _vp(meta_d), _vp(sp_d), _vp(br_d), Pc, int(slot.max()) + 1, _vp(self._x), N,
-                                                 self.dim, _vp(self._c), metric, k, _vp(seq_id), _vp(cut_d), C, _vp(pg_d), _vp(seq_grp),
-                                                 _vp(costs[p0:p1]), _vp(seqs[p0:p1]), _vp(spans[p0:p1]), _vp(ws), _stream(dev)),
-                           "sylber_dtw_search")
-        return costs, seqs, spans
+        Pc = p1 - p0
+        ln = np.ascontiguousarray(lens[p0:p1], np.int32)
+        nb, ph = ctypes.c_int32(0), ctypes.c_int32(0)
+        place = np.empty(Pc, np.int32)
+        args = (off32.ctypes.data_as(i32p), S, ln.ctypes.data_as(i32p), Pc, list_size, int(splits), int(block_phrases))
+        C = int(lib.sylber_dtw_plan(*args, None, 0, place.ctypes.data_as(i32p), ctypes.byref(nb), ctypes.byref(ph)))
+        cut_rows = np.empty(max(C, 1) + 1, np.int32)
+        if C < 1 or int(lib.sylber_dtw_plan(*args, cut_rows.ctypes.data_as(i32p), C + 1, None, None, None)) != C:
+            raise _lib.SylberHipError("sylber_dtw_plan failed (%d)" % C)
+        nb = nb.value
+        R = int(ln.sum())
+        first = np.repeat(place.astype(np.int64), ln)
+        local = np.arange(R) - np.repeat(np.cumsum(ln) - ln, ln)
+        blk = place // 128
+        slot = np.arange(Pc) - np.searchsorted(blk, blk, side="left")
+        meta = np.full(nb * 128, -1, np.int32)
+        meta[first + local] = local | ((local == np.repeat(ln, ln) - 1).astype(np.int64) << 7) | (np.repeat(slot, ln) << 8)
+        slot_phrase = np.full(nb * 128, -1, np.int32)
+        slot_phrase[blk.astype(np.int64) * 128 + slot] = np.arange(Pc)
+        block_rows = np.zeros(nb, np.int32)
+        np.maximum.at(block_rows, blk, place % 128 + ln)
+        r0 = int(lens[:p0].sum())
+        qp = torch.zeros((nb * 128, self.dim), dtype=torch.float32, device=dev)
+        qp[torch.from_numpy(first + local).to(dev)] = qd[r0:r0 + R]
+        return _PhraseBlocks(dev, Pc, nb, C, int(slot.max()) + 1, place, ln, qp, meta, slot_phrase, block_rows, cut_rows,
+                             pg[p0:p1] if pg is not None else None)
 
     # ---- persistence ----------------------------------------------------------------------------------------------------------------
     def save(self, path: str) -> None:

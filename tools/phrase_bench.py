@@ -6,7 +6,13 @@ without the dynamic programme.  For every (rows, m): median milliseconds of the 
 device synchronise, after a warm-up call), the spread (min .. max) of the timed calls, TFLOP/s on 2 rows N D, and the ratio
 yardstick time / phrase-search time.  Prints one JSON line (rows also go to stderr as they finish).
 
-    python tools/phrase_bench.py [--iters 5] [--N 4194304] [--rows 128,1024,8192] [--ms 2,8,32] [--k 10]"""
+    python tools/phrase_bench.py [--iters 5] [--N 4194304] [--rows 128,1024,8192] [--ms 2,8,32] [--k 10]
+
+``--refined [--storage fp16|bf16] [--refine 4]`` adds the two-stage leg (csrc/dtw16.hip, ``SyllableIndex.search_phrases_refined``): in
+the same run, on the same phrases and index, the whole-call time of ``search_phrases_refined(k, refine, storage)`` beside
+``search_phrases``'s (``refined_over_phrase`` = two-stage time / ``search_phrases`` time: below 1 is faster), and for refine 1, 2, 4
+and 8 the share of phrases whose exact top-k (``recovered_topk``) and whose exact best sequence (``recovered_top1``) the two-stage
+call returns.  The 16-bit plane is built before anything is timed."""
 import argparse
 import json
 import os
@@ -40,6 +46,9 @@ def main():
     ap.add_argument("--rows", default="128,1024,8192")
     ap.add_argument("--ms", default="2,8,32")
     ap.add_argument("--k", type=int, default=10)
+    ap.add_argument("--refined", action="store_true")
+    ap.add_argument("--storage", default="fp16", choices=["fp16", "bf16"])
+    ap.add_argument("--refine", type=int, default=4)
     args = ap.parse_args()
     from sylber_amd import SyllableIndex
     dev = torch.device("cuda:0")
@@ -54,6 +63,8 @@ def main():
     groups = np.repeat(np.arange(lens.size), lens).astype(np.int32)
     idx = SyllableIndex(torch.randn(N, D, device=dev, generator=g), metric="l2", groups=groups, device=dev)
     idx.sequence_offsets()
+    if args.refined:
+        idx.half_rows(args.storage)
     out = []
     for rows in [int(v) for v in args.rows.split(",")]:
         q = idx.features[torch.randint(0, N - rows, (1,), device=dev, generator=g).item():][:rows] + 0.5 * torch.randn(rows, D, device=dev, generator=g)
@@ -66,6 +77,19 @@ def main():
             t, lo, hi = timed(lambda: idx.search_phrases(q[:P * m], k, lengths=[m] * P), args.iters)
             row = dict(base, m=m, phrases=P, phrase_ms=round(t, 2), phrase_ms_min_max=[round(lo, 2), round(hi, 2)],
                        phrase_tflops=round(2.0 * P * m * N * D / t / 1e9, 1), search_over_phrase=round(t_knn / t, 3))
+            if args.refined:
+                ph, ln = q[:P * m], [m] * P
+                t2, lo, hi = timed(lambda: idx.search_phrases_refined(ph, k, args.refine, args.storage, lengths=ln), args.iters)
+                exact = idx.search_phrases(ph, k, lengths=ln)[1]
+                share = {}
+                for r in (1, 2, 4, 8):
+                    if k * r > 128:
+                        continue
+                    got = idx.search_phrases_refined(ph, k, r, args.storage, lengths=ln)[1]
+                    share[str(r)] = [round(float((got == exact).all(1).float().mean()), 4), round(float((got[:, 0] == exact[:, 0]).float().mean()), 4)]
+                row.update(storage=args.storage, refine=args.refine, refined_ms=round(t2, 2), refined_ms_min_max=[round(lo, 2), round(hi, 2)],
+                           refined_over_phrase=round(t2 / t, 3), recovered_topk={r: v[0] for r, v in share.items()},
+                           recovered_top1={r: v[1] for r, v in share.items()})
             print(json.dumps(row), file=sys.stderr, flush=True)
             out.append(row)
     print(json.dumps({"D": D, "metric": "l2", "iters": args.iters, "rows": out}))
