@@ -437,6 +437,23 @@ int sylber_dtw_rerank(const float* q_dev, int32_t n_blocks, const float* q_norm_
                       int32_t metric, const int32_t* cand_dev, int32_t m, const int32_t* seq_offsets_dev, int32_t n_seq, int32_t k,
                       float* cost_dev, int64_t* seq_dev, int64_t* span_dev, void* workspace_dev, void* stream);
 
+/* Compressed phrase search (sylber_amd/pq.py: PQSyllableIndex.search_phrases): sylber_dtw16_scan with the database given as
+ * product-quantization codes.  codes_dev [N, M] uint8 and bad_dev [N] uint8 (nullable; 1 = a masked row) as sylber_pq_encode writes
+ * them; codebooks16_dev [M, 256, D / M] = sylber_knn16_pack of the fp32 codebooks in `storage`; 1 <= M <= 64, D % M == 0,
+ * (D / M) % 16 == 0.  With x^_j = sylber_pq_decode(code_j), the coarse score is t(i, j) = fmaf(-2, dot16(q16_i, round16(x^_j)), c_j),
+ * c_j = recon_norm_dev[j] under L2 (sylber_knn_row_norms of x^_j; may be null under IP), 0 under IP, and NaN in both metrics for a
+ * masked row, whose local cost is therefore +inf against every phrase row.  round16 is element-wise, so round16(x^_j) is gathered
+ * from codebooks16_dev and no row is ever materialised.  Everything else -- the other arguments, the local cost, the recurrence, the
+ * candidates, cand_dev / coarse_dev, the workspace of sylber_dtw16_workspace_bytes(n_phrases, m, cuts) bytes -- is
+ * sylber_dtw16_scan's: the outputs equal those of sylber_dtw16_scan on db16_dev = sylber_knn16_pack(x^) (a NaN row for a masked
+ * one) with db_norm_dev = recon_norm_dev, bit for bit.  Bad arguments return 1 with sylber_last_error before any device call. */
+int sylber_dtwpq_scan(const void* q16_dev, int32_t n_blocks, const int32_t* row_meta_dev, const int32_t* slot_phrase_dev,
+                      const int32_t* block_rows_dev, int32_t n_phrases, int32_t block_phrases, const uint8_t* codes_dev,
+                      const uint8_t* bad_dev, const void* codebooks16_dev, int32_t N, int32_t D, int32_t M, const float* recon_norm_dev,
+                      const float* q_norm_dev, int32_t metric, int32_t storage, int32_t m, const int32_t* seq_id_dev,
+                      const int32_t* cut_rows_dev, int32_t cuts, const int32_t* phrase_group_dev, const int32_t* seq_group_dev,
+                      int32_t* cand_dev, float* coarse_dev, void* workspace_dev, void* stream);
+
 /* Learned quantizer (sylber/model/quantizer.py:6-77, 182-257: `load_quantizer` / `Quantizer`), eval, exact fp32.  The host
  * (sylber_amd/quantizer.py) chains: sylber_lq_norm (input norm / padding) -> sylber_ffenc -> sylber_lq_norm (output norm, blank rows)
  * -> sylber_rvq_assign for the art window and the pitch window -> sylber_lq_norm of the quantized rows.  All data pointers are device

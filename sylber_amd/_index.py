@@ -1,9 +1,11 @@
 """The host rules that the four syllable indexes share (search.py: ``SyllableIndex``, ``IVFSyllableIndex``; pq.py: ``PQSyllableIndex``,
 ``IVFPQSyllableIndex``), each written once: what a search accepts (``k`` / ``refine``, ``nprobe``, ``splits`` / ``query_chunk``, query
-rows, query groups), how rows are stored (``_prep``, ``_row_norms``), where a search puts its results, what ``provenance`` answers, how
+rows, query groups; the arguments, sequences and packed blocks of a phrase search), how rows are stored (``_prep``, ``_row_norms``,
+``_pack16``), where a search puts its results, what ``provenance`` answers, how
 rows are sorted into lists, and how the common arrays reach an ``.npz`` and come back.  Private: the classes are the public surface."""
 from __future__ import annotations
 
+import ctypes
 from typing import List, Optional, Tuple
 
 import numpy as np
@@ -17,6 +19,10 @@ MAX_K = 128
 DEFAULT_QUERY_CHUNK = 8192
 MAX_NPROBE = 128
 MAX_CANDIDATES = 128            # k * refine of a two-stage search: the LDS top-list of the scan beside a 128-row query block
+MAX_PHRASE_ROWS = 64            # DT_MAX_M of csrc/dtw.hip: one wave holds a phrase
+MAX_SEQUENCE_ROWS = 65536       # DT_MAX_SEQ: the DP along one sequence is serial
+DEFAULT_PHRASE_CHUNK = 4096
+STORAGES = {"fp16": (0, torch.float16), "bf16": (1, torch.bfloat16)}     # SYLBER_KNN16_FP16 / _BF16: the 16-bit planes of the two-stage searches
 
 
 # ---- arguments ---------------------------------------------------------------------------------------------------------------------
@@ -127,6 +133,22 @@ def _row_norms(x: torch.Tensor) -> torch.Tensor:
     return out
 
 
+def _pack16(x: torch.Tensor, storage: str, refuse: bool) -> torch.Tensor:
+    """contiguous fp32 rows on the device -> their 16-bit rows (csrc/knn16.hip, ``sylber_knn16_pack``: round to nearest even, fp16
+    saturates); ``refuse``: a finite value that fp16 cannot hold is a ``ValueError``"""
+    code, dtype = STORAGES[storage]
+    out = torch.empty(x.shape, dtype=dtype, device=x.device)
+    if x.shape[0] == 0:
+        return out
+    sat = torch.zeros(1, dtype=torch.int32, device=x.device) if refuse and storage == "fp16" else None
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.load().sylber_knn16_pack(_vp(x), x.shape[0], x.shape[1], code, _vp(out), _vp(sat), _stream(x.device)),
+                   "sylber_knn16_pack")
+    if sat is not None and int(sat.item()):
+        raise ValueError('%d stored values lie beyond +-65504, the range of storage="fp16": use storage="bf16"' % int(sat.item()))
+    return out
+
+
 def _added_rows(features, groups, dim: Optional[int], start: int, a_class: str, metric: str, device):
     """``[n, D]`` rows for an index that holds ``start`` rows of width ``dim`` -> ``(stored rows, groups on the device, their ids,
     filler provenance)``; with no rows only the (empty) ids are not ``None``.  ``ValueError`` before anything touches the device."""
@@ -150,6 +172,129 @@ def _list_layout(labels: torch.Tensor, nlist: int) -> Tuple[torch.Tensor, torch.
     off = torch.zeros(nlist + 1, dtype=torch.int64, device=labels.device)
     off[1:] = torch.cumsum(sizes, 0)
     return order, sizes, off
+
+
+# ---- phrase searches ----------------------------------------------------------------------------------------------------------------
+# What SyllableIndex.search_phrases / search_phrases_refined and PQSyllableIndex.search_phrases share.  An index enters only as
+# (N rows, width dim, device, the rows' groups on the device).
+def _phrase_outputs(P: int, k: int, device):
+    """``(costs fp32 [P, k], seqs int64 [P, k], spans int64 [P, k, 2])`` of a phrase search"""
+    return (torch.empty((P, k), dtype=torch.float32, device=device), torch.empty((P, k), dtype=torch.int64, device=device),
+            torch.empty((P, k, 2), dtype=torch.int64, device=device))
+
+
+def _group_runs(g: Optional[torch.Tensor], N: int) -> np.ndarray:
+    """int64 ``[S + 1]``: the maximal runs of consecutive rows with equal group, the default sequences of a phrase search"""
+    if N == 0:
+        return np.zeros(1, np.int64)
+    g = g.cpu().numpy()
+    return np.concatenate([[0], np.nonzero(g[1:] != g[:-1])[0] + 1, [N]]).astype(np.int64)
+
+
+def _sequences(sequences, N: int, default) -> np.ndarray:
+    """the sequence offsets int64 ``[S + 1]`` of a phrase search: ``sequences`` validated, or ``default()``"""
+    if sequences is None:
+        off = default()
+    else:
+        a = np.asarray(sequences.detach().cpu().numpy() if torch.is_tensor(sequences) else sequences)
+        if a.ndim != 1 or a.size < 2 or a.dtype.kind not in "iu":
+            raise ValueError("sequences must be integer offsets [S + 1]")
+        off = a.astype(np.int64)
+        if off[0] != 0 or off[-1] != N or np.any(np.diff(off) < 1):
+            raise ValueError("sequences must ascend from 0 to %d rows without an empty sequence" % N)
+    longest = int(np.diff(off).max())
+    if longest > MAX_SEQUENCE_ROWS:
+        raise ValueError("a sequence has %d rows, more than %d: cut it with sequences=" % (longest, MAX_SEQUENCE_ROWS))
+    return off
+
+
+def _phrase_args(N: int, dim: int, device, default_sequences, phrases, lengths, groups, exclude_same_group, sequences, splits,
+                 phrase_chunk, block_phrases):
+    """the checks of a phrase search -> ``(phrase rows [sum m, D] as given, lengths int64 [P], the phrases' groups on the host or
+    None, sequence offsets int64 [S + 1])``, or ``ValueError``"""
+    if N == 0:
+        raise ValueError("the index is empty")
+    if lengths is None:
+        if torch.is_tensor(phrases) or isinstance(phrases, np.ndarray):
+            raise ValueError("phrases given as one [sum m, D] array need lengths=")
+        parts = [_rows(p, "phrases[%d]" % i) for i, p in enumerate(phrases)]
+        lens = np.array([p.shape[0] for p in parts], np.int64)
+        for p in parts:
+            _rows_of_width(p, dim, "phrases")
+        q = torch.cat([p.to(device, torch.float32) for p in parts]) if parts else torch.zeros((0, dim), device=device)
+    else:
+        q = _rows_of_width(phrases, dim, "phrases")
+        lens = np.asarray(lengths.detach().cpu().numpy() if torch.is_tensor(lengths) else lengths)
+        if lens.ndim != 1 or (lens.size and lens.dtype.kind not in "iu"):
+            raise ValueError("lengths must be a 1-D sequence of integers")
+        lens = lens.astype(np.int64)
+        if int(lens.sum()) != q.shape[0]:
+            raise ValueError("lengths sum to %d, phrases has %d rows" % (int(lens.sum()), q.shape[0]))
+    P = int(lens.size)
+    if P and (lens.min() < 1 or lens.max() > MAX_PHRASE_ROWS):
+        raise ValueError("a phrase has between 1 and %d rows, got lengths from %d to %d" % (MAX_PHRASE_ROWS, lens.min(), lens.max()))
+    pg = _query_groups(groups, P, exclude_same_group, None, "phrases")         # on the host: a chunk's groups go to the device with it
+    if int(splits) < 0 or int(phrase_chunk) < 1 or int(block_phrases) < 0:
+        raise ValueError("splits and block_phrases must be >= 0 and phrase_chunk >= 1")
+    return q, lens, pg, _sequences(sequences, N, default_sequences)
+
+
+def _sequence_tables(off: np.ndarray, g: Optional[torch.Tensor], device):
+    """plumbing: the sequence of every row and (with the rows' groups ``g``, for the exclusion) the group of every sequence, on the
+    device"""
+    off_d = torch.from_numpy(off).to(device)
+    seq_id = torch.repeat_interleave(torch.arange(off.size - 1, dtype=torch.int32, device=device), off_d[1:] - off_d[:-1])
+    return seq_id, (g.index_select(0, off_d[:-1]) if g is not None else None)
+
+
+class _PhraseBlocks:
+    """one chunk of phrases as ``sylber_dtw_plan`` packs it: ``Pc`` phrases in ``nb`` blocks of 128 rows (``qp``, padding rows zero)
+    against ``C`` cuts; ``slots`` = the most phrases in any block; ``place`` / ``ln``: first packed row and length of each phrase"""
+
+    def __init__(self, dev, Pc, nb, C, slots, place, ln, qp, meta, slot_phrase, block_rows, cut_rows, pg):
+        self.dev, self.Pc, self.nb, self.C, self.slots, self.place, self.ln, self.qp = dev, Pc, nb, C, slots, place, ln, qp
+        self._host = (meta, slot_phrase, block_rows, cut_rows)
+        self._pg = pg
+
+    def tables(self):
+        """``(row meta, slot -> phrase, rows per block, cut rows, the phrases' groups or None)`` on the device"""
+        meta_d, sp_d, br_d, cut_d = (torch.from_numpy(a).to(self.dev) for a in self._host)
+        return meta_d, sp_d, br_d, cut_d, (_on_device(self._pg, np.int32, self.dev) if self._pg is not None else None)
+
+
+def _phrase_blocks(lib, dev, qd, lens, p0: int, p1: int, off, list_size: int, splits, block_phrases, pg) -> _PhraseBlocks:
+    """phrases ``p0 : p1`` of the prepared rows ``qd`` packed by ``sylber_dtw_plan`` for lists of ``list_size`` entries: the
+    packed layout of the chunk's rows (where each row goes, what it is, which phrase owns each slot), the rows scattered into
+    zeroed 128-row blocks, and the cut table"""
+    S = off.size - 1
+    off32 = np.ascontiguousarray(off, np.int32)
+    i32p = ctypes.POINTER(ctypes.c_int32)
+    Pc = p1 - p0
+    ln = np.ascontiguousarray(lens[p0:p1], np.int32)
+    nb, ph = ctypes.c_int32(0), ctypes.c_int32(0)
+    place = np.empty(Pc, np.int32)
+    args = (off32.ctypes.data_as(i32p), S, ln.ctypes.data_as(i32p), Pc, list_size, int(splits), int(block_phrases))
+    C = int(lib.sylber_dtw_plan(*args, None, 0, place.ctypes.data_as(i32p), ctypes.byref(nb), ctypes.byref(ph)))
+    cut_rows = np.empty(max(C, 1) + 1, np.int32)
+    if C < 1 or int(lib.sylber_dtw_plan(*args, cut_rows.ctypes.data_as(i32p), C + 1, None, None, None)) != C:
+        raise _lib.SylberHipError("sylber_dtw_plan failed (%d)" % C)
+    nb = nb.value
+    R = int(ln.sum())
+    first = np.repeat(place.astype(np.int64), ln)
+    local = np.arange(R) - np.repeat(np.cumsum(ln) - ln, ln)
+    blk = place // 128
+    slot = np.arange(Pc) - np.searchsorted(blk, blk, side="left")
+    meta = np.full(nb * 128, -1, np.int32)
+    meta[first + local] = local | ((local == np.repeat(ln, ln) - 1).astype(np.int64) << 7) | (np.repeat(slot, ln) << 8)
+    slot_phrase = np.full(nb * 128, -1, np.int32)
+    slot_phrase[blk.astype(np.int64) * 128 + slot] = np.arange(Pc)
+    block_rows = np.zeros(nb, np.int32)
+    np.maximum.at(block_rows, blk, place % 128 + ln)
+    r0 = int(lens[:p0].sum())
+    qp = torch.zeros((nb * 128, qd.shape[1]), dtype=torch.float32, device=dev)
+    qp[torch.from_numpy(first + local).to(dev)] = qd[r0:r0 + R]
+    return _PhraseBlocks(dev, Pc, nb, C, int(slot.max()) + 1, place, ln, qp, meta, slot_phrase, block_rows, cut_rows,
+                         pg[p0:p1] if pg is not None else None)
 
 
 # ---- results -----------------------------------------------------------------------------------------------------------------------

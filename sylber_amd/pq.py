@@ -34,9 +34,10 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._index import (DEFAULT_QUERY_CHUNK, METRICS, _added_rows, _base_arrays, _check_k_refine, _check_nprobe, _check_splits_chunk,
-                     _chunked_workspace_bytes, _list_layout, _on_device, _outputs, _prep, _provenance, _query_groups, _result, _row_norms,
-                     _rows, _rows_of_width)
+from ._index import (DEFAULT_PHRASE_CHUNK, DEFAULT_QUERY_CHUNK, METRICS, STORAGES, _added_rows, _base_arrays, _check_k_refine,
+                     _check_nprobe, _check_splits_chunk, _chunked_workspace_bytes, _group_runs, _list_layout, _on_device, _outputs, _pack16,
+                     _phrase_args, _phrase_blocks, _phrase_outputs, _prep, _provenance, _query_groups, _result, _row_norms, _rows,
+                     _rows_of_width, _sequence_tables)
 from .kmeans import _device, _stream, _vp
 from .search import IVFSyllableIndex, SyllableIndex
 
@@ -44,6 +45,8 @@ KSUB = 256                      # centroids per sub-space: one uint8 per code
 MAX_M = 64                      # PQ_MAX_M of csrc/pq.hip: at least two queries' tables (M KiB each) fit beside the top lists in LDS
 ENCODE_CHUNK = 1 << 20          # rows per encode launch
 RESIDUAL_CHUNK = 1 << 18        # rows whose fp32 residuals exist at a time while residual codes are made
+NORM_CHUNK = 1 << 16            # rows decoded at a time while the ||decode(code)||^2 of search_phrases are made
+DEFAULT_SCRATCH_ROWS = 262144   # rows of decoded candidate sequences that search_phrases(rerank=False) holds at a time
 
 
 def _check_geometry(D: int, M) -> int:
@@ -270,6 +273,9 @@ class PQSyllableIndex:
         self._prov = prov
         self._span_dtype = np.int64 if span_int else np.float64
         self._cnorm = _row_norms(codebooks)              # [M, 256] ||centroid||^2
+        self._seq_cache = None                  # (N, default sequence offsets)
+        self._cb16 = {}                         # storage -> [M, 256, dsub] 16-bit codebooks for search_phrases, built on first use
+        self._rnorm = None                      # [N] ||decode(code)||^2, NaN for a masked row ("l2"), built on first use
 
     # ---- building -------------------------------------------------------------------------------------------------------------------
     @classmethod
@@ -313,6 +319,8 @@ class PQSyllableIndex:
             return ids
         c, b = _encode(xd, self.codebooks, self._cnorm)
         self._codes, self._bad = torch.cat([self._codes, c]), torch.cat([self._bad, b])
+        if self._rnorm is not None:
+            self._rnorm = torch.cat([self._rnorm, self._norms_of(c, b)])
         if self.index is None:
             self._g, self._prov = torch.cat([self._g, gd]), np.concatenate([self._prov, prov])
         return ids
@@ -345,9 +353,11 @@ class PQSyllableIndex:
 
     @property
     def nbytes(self) -> int:
-        """bytes this index holds on the device: codes, row mask, groups, codebooks with their norms, and ``4 N D`` for the fp32 rows
-        while they are held (the ``4 N`` bytes of an ``"l2"`` source index's row norms are not counted)"""
+        """bytes this index holds on the device: codes, row mask, groups, codebooks with their norms, what ``search_phrases`` has
+        built so far (a 16-bit copy of the codebooks per storage used, ``4 N`` of reconstruction norms under ``"l2"``), and ``4 N D``
+        for the fp32 rows while they are held (the ``4 N`` bytes of an ``"l2"`` source index's row norms are not counted)"""
         n = self._codes.numel() + self._bad.numel() + 4 * len(self) + 4 * self.codebooks.numel() + 4 * self._cnorm.numel()
+        n += sum(2 * c.numel() for c in self._cb16.values()) + (4 * self._rnorm.numel() if self._rnorm is not None else 0)
         return int(n + (4 * len(self) * self.dim if self.index is not None else 0))
 
     def _db_groups(self) -> torch.Tensor:
@@ -388,6 +398,163 @@ class PQSyllableIndex:
         return _pq_search(self, "pq", queries, k, mc, rerank, groups, exclude_same_group, return_candidates, splits,
                           DEFAULT_QUERY_CHUNK if query_chunk is None else query_chunk, _workspace_fill,
                           lambda m, splits: _lib.load().sylber_pq_workspace_bytes(m, N, M, mc, splits), scan)[0]
+
+    # ---- phrase search --------------------------------------------------------------------------------------------------------------
+    def sequence_offsets(self) -> np.ndarray:
+        """as ``SyllableIndex.sequence_offsets``, from the index's groups: it works after ``drop_rows()``"""
+        N = len(self)
+        if self._seq_cache is None or self._seq_cache[0] != N:
+            self._seq_cache = (N, _group_runs(self._db_groups(), N))
+        return self._seq_cache[1].copy()
+
+    def _codebooks16(self, storage: str) -> torch.Tensor:
+        """``[M, 256, dsub]``: the codebooks as ``sylber_knn16_pack`` rounds them, built on first use.  Rounding is element-wise, so a
+        gather from it is the rounded reconstruction.  ``"fp16"`` raises ``ValueError`` for a finite value beyond +-65504."""
+        if storage not in self._cb16:
+            M, _, dsub = self.codebooks.shape
+            self._cb16[storage] = _pack16(self.codebooks.reshape(M * KSUB, dsub), storage, refuse=True).reshape(M, KSUB, dsub)
+        return self._cb16[storage]
+
+    def _norms_of(self, codes: torch.Tensor, bad: torch.Tensor) -> torch.Tensor:
+        """``||decode(code)||^2`` of these rows as ``_row_norms`` computes it from the decoded row, NaN for a masked row"""
+        parts = [_row_norms(_decode(codes[r0:r0 + NORM_CHUNK], self.codebooks)) for r0 in range(0, codes.shape[0], NORM_CHUNK)]
+        c = torch.cat(parts)
+        return torch.where(bad != 0, torch.full_like(c, float("nan")), c)
+
+    def _recon_norms(self) -> Optional[torch.Tensor]:
+        """the ``c_j`` of ``search_phrases`` under ``"l2"`` (``None`` under ``"cosine"``), built on first use, ``NORM_CHUNK`` rows at a
+        time: the corpus is never materialised"""
+        if self.metric != "l2":
+            return None
+        if self._rnorm is None:
+            self._rnorm = self._norms_of(self._codes, self._bad)
+        return self._rnorm
+
+    def search_phrases(self, phrases, k: int, refine: int = 4, storage: str = "fp16", *, rerank: Optional[bool] = None, lengths=None,
+                       groups=None, exclude_same_group: bool = False, sequences=None, splits: int = 0,
+                       phrase_chunk: int = DEFAULT_PHRASE_CHUNK, block_phrases: int = 0, scratch_rows: int = DEFAULT_SCRATCH_ROWS,
+                       return_candidates: bool = False, _workspace_fill=None):
+        """``SyllableIndex.search_phrases_refined`` on the codes: the same arguments, and ``(costs, seqs, spans)`` (plus ``cand`` and
+        ``coarse`` with ``return_candidates=True``) shaped, typed, ordered, padded and placed exactly as there.  ``m = k * refine <=
+        128`` candidate sequences per phrase in both modes.
+
+        Stage 1 reads the codes alone (csrc/dtwpq.hip, ``sylber_dtwpq_scan``).  With ``x^_j = decode(code_j)`` (under ``"cosine"`` the
+        reconstruction of the unit row, not renormalised) and ``c_j`` the fp32 ``||x^_j||^2`` (``"l2"``) or 0 (``"cosine"``), the coarse
+        score is ``t(i, j) = fmaf(-2, dot16(q~_i, round16(x^_j)), c_j)``; local cost, recurrence, coarse cost and candidates are
+        ``search_phrases_refined``'s word for word.  A masked row behaves as a NaN row: its local cost is ``+inf`` against every
+        phrase row.  So ``cand`` and ``coarse`` are those of ``sylber_dtw16_scan`` on the plane ``pack16(decode(all codes))`` with
+        ``c`` for the norms, bit for bit, and that plane is never built: the kernel gathers ``round16(x^_j)`` from a 16-bit copy of
+        the codebooks.
+
+        Stage 2, ``rerank=True`` (the default while the fp32 rows are held; ``ValueError`` once they are dropped): the exact DTW of
+        ``pq.index.search_phrases`` on the fp32 rows for each candidate, so every returned cost and span is a real
+        ``search_phrases`` cost and span, and with ``m`` at least the number of admissible sequences the result is
+        ``pq.index.search_phrases``'s, bit for bit.  ``rerank=False`` (the only mode after ``drop_rows()``): the same exact DTW on the
+        *decoded* candidate sequences (a masked row is a NaN row), so under ``"l2"`` with no masked row the whole call equals
+        ``SyllableIndex(pq.decode(arange(N)), metric="l2", groups=g).search_phrases_refined(...)``, bit for bit.  The decoded rows
+        of at most ``scratch_rows`` rows' worth of candidate sequences exist at a time (one phrase's candidates at least; the call
+        waits for stage 1 of a chunk to learn them).
+
+        Nothing returned depends on ``splits``, ``phrase_chunk``, ``block_phrases``, ``scratch_rows``, stale workspace contents, how
+        the index was built or whether it was saved and loaded.  ``storage="fp16"`` refuses a finite codebook value beyond
+        +-65504."""
+        if rerank is None:
+            rerank = self.index is not None
+        if rerank and self.index is None:
+            raise ValueError("rerank=True needs the fp32 rows, which were dropped: search with rerank=False")
+        k, m = _check_k_refine(k, refine, rerank=True)
+        if storage not in STORAGES:
+            raise ValueError("storage must be 'fp16' or 'bf16', got %r" % (storage,))
+        if isinstance(scratch_rows, bool) or int(scratch_rows) != scratch_rows or int(scratch_rows) < 1:
+            raise ValueError("scratch_rows must be an integer >= 1, got %r" % (scratch_rows,))
+        N, D, M, dev = len(self), self.dim, self.M, self.device
+        if self.index is not None and len(self.index) != N:
+            raise ValueError("pq.index holds %d rows, the codes %d: add rows through pq.add" % (len(self.index), N))
+        q, lens, pg, off = _phrase_args(N, D, dev, self.sequence_offsets, phrases, lengths, groups, exclude_same_group, sequences, splits,
+                                        phrase_chunk, block_phrases)
+        P = int(lens.size)
+        costs, seqs, spans = _phrase_outputs(P, k, dev)
+        cand = torch.empty((P, m), dtype=torch.int32, device=dev)
+        coarse = torch.empty((P, m), dtype=torch.float32, device=dev)
+        if P == 0:
+            return (costs, seqs, spans, cand.to(torch.int64), coarse) if return_candidates else (costs, seqs, spans)
+        cb16 = self._codebooks16(storage)
+        cn = self._recon_norms()
+        lib = _lib.load()
+        qd = self._prep(q)
+        S = off.size - 1
+        seq_id, seq_grp = _sequence_tables(off, self._db_groups() if pg is not None else None, dev)
+        off_d = _on_device(off, np.int32, dev)
+        metric, code = METRICS[self.metric], STORAGES[storage][0]
+        with torch.cuda.device(dev):
+            st = _stream(dev)
+            for p0 in range(0, P, int(phrase_chunk)):
+                p1 = min(P, p0 + int(phrase_chunk))
+                b = _phrase_blocks(lib, dev, qd, lens, p0, p1, off, m, splits, block_phrases, pg)
+                qn = _row_norms(b.qp) if self.metric == "l2" else None
+                q16 = _pack16(b.qp, storage, refuse=False)
+                ws = torch.empty(int(lib.sylber_dtw16_workspace_bytes(b.Pc, m, b.C)), dtype=torch.uint8, device=dev)
+                if _workspace_fill is not None:
+                    ws.fill_(_workspace_fill)
+                meta_d, sp_d, br_d, cut_d, pg_d = b.tables()
+                place_d, len_d = _on_device(b.place, np.int32, dev), _on_device(b.ln, np.int32, dev)
+                _lib.check(lib.sylber_dtwpq_scan(_vp(q16), b.nb, _vp(meta_d), _vp(sp_d), _vp(br_d), b.Pc, b.slots, _vp(self._codes),
+                                                 _vp(self._bad), _vp(cb16), N, D, M, _vp(cn), _vp(qn), metric, code, m, _vp(seq_id), _vp(cut_d),
+                                                 b.C, _vp(pg_d), _vp(seq_grp), _vp(cand[p0:p1]), _vp(coarse[p0:p1]), _vp(ws), st),
+                           "sylber_dtwpq_scan")
+                if rerank:
+                    i = self.index
+                    _lib.check(lib.sylber_dtw_rerank(_vp(b.qp), b.nb, _vp(qn), _vp(place_d), _vp(len_d), b.Pc, _vp(i._x), N, D, _vp(i._c), metric,
+                                                     _vp(cand[p0:p1]), m, _vp(off_d), S, k, _vp(costs[p0:p1]), _vp(seqs[p0:p1]),
+                                                     _vp(spans[p0:p1]), _vp(ws), st), "sylber_dtw_rerank")
+                    continue
+                self._rerank_decoded(lib, b, qn, place_d, len_d, cand[p0:p1], off, off_d, int(scratch_rows), m, k, costs[p0:p1],
+                                     seqs[p0:p1], spans[p0:p1], ws, st)
+        return (costs, seqs, spans, cand.to(torch.int64), coarse) if return_candidates else (costs, seqs, spans)
+
+    def _rerank_decoded(self, lib, b, qn, place_d, len_d, cand, off, off_d, scratch_rows: int, m: int, k: int, costs, seqs, spans, ws,
+                        st) -> None:
+        """stage 2 of ``search_phrases(rerank=False)`` for one chunk (plumbing around ``sylber_dtw_rerank``): the chunk's phrases in
+        runs whose candidate sequences hold at most ``scratch_rows`` rows together (one phrase at least); per run the unique
+        candidates in ascending sequence number -- so that ties break as on the real numbering -- decoded into a compact scratch
+        with compact offsets, the exact DTW on it, and sequence numbers and row ids mapped back"""
+        dev, metric = self.device, METRICS[self.metric]
+        cand_h = cand.cpu().numpy()                         # waits for stage 1 of the chunk
+        seq_len = np.diff(off)
+        runs, g0, have, rows = [], 0, np.zeros(0, np.int64), 0
+        for p in range(b.Pc):
+            new = np.setdiff1d(cand_h[p][cand_h[p] >= 0], have)
+            more = int(seq_len[new].sum())
+            if p > g0 and rows + more > scratch_rows:
+                runs.append((g0, p, have))
+                g0, have, rows = p, np.zeros(0, np.int64), 0
+                new = np.unique(cand_h[p][cand_h[p] >= 0])
+                more = int(seq_len[new].sum())
+            have, rows = np.union1d(have, new).astype(np.int64), rows + more
+        runs.append((g0, b.Pc, have))
+        for g0, g1, uniq in runs:
+            c_out, s_out, sp_out = costs[g0:g1], seqs[g0:g1], spans[g0:g1]
+            if uniq.size == 0:                              # no candidate at all: the padding of an empty list
+                c_out.fill_(float("inf")); s_out.fill_(-1); sp_out.fill_(-1)
+                continue
+            coff = np.concatenate([[0], np.cumsum(seq_len[uniq])]).astype(np.int64)
+            R = int(coff[-1])
+            uniq_d, coff_d, roff_d = (torch.from_numpy(a).to(dev) for a in (uniq, coff, off[uniq]))
+            srow = torch.repeat_interleave(torch.arange(uniq.size, device=dev), coff_d[1:] - coff_d[:-1])
+            rid = roff_d[srow] + (torch.arange(R, device=dev) - coff_d[srow])                    # the real row of every scratch row
+            x = _decode(self._codes.index_select(0, rid), self.codebooks)
+            x = torch.where((self._bad.index_select(0, rid) != 0)[:, None], torch.full_like(x, float("nan")), x)
+            cn = self._rnorm.index_select(0, rid) if self.metric == "l2" else None
+            cc = torch.searchsorted(uniq_d, cand[g0:g1].to(torch.int64).clamp(min=0))
+            cc = torch.where(cand[g0:g1] < 0, torch.full_like(cc, -1), cc).to(torch.int32).contiguous()
+            coff32 = coff_d.to(torch.int32)
+            _lib.check(lib.sylber_dtw_rerank(_vp(b.qp), b.nb, _vp(qn), _vp(place_d[g0:g1]), _vp(len_d[g0:g1]), g1 - g0, _vp(x), R, self.dim,
+                                             _vp(cn), metric, _vp(cc), m, _vp(coff32), int(uniq.size), k, _vp(c_out),
+                                             _vp(s_out), _vp(sp_out), _vp(ws), st), "sylber_dtw_rerank")
+            hit = s_out >= 0
+            sc = s_out.clamp(min=0)
+            sp_out.copy_(torch.where(hit[:, :, None], sp_out - coff_d[sc][:, :, None] + roff_d[sc][:, :, None], sp_out))
+            s_out.copy_(torch.where(hit, uniq_d[sc], s_out))
 
     # ---- persistence ----------------------------------------------------------------------------------------------------------------
     def save(self, path: str) -> None:

@@ -29,37 +29,14 @@ import torch
 
 from . import _lib
 from ._index import MAX_CANDIDATES, MAX_K, MAX_NPROBE  # noqa: F401  (limits of this module's searches, kept importable from here)
+from ._index import DEFAULT_PHRASE_CHUNK, MAX_PHRASE_ROWS, MAX_SEQUENCE_ROWS, STORAGES  # noqa: F401  (likewise, for the phrase searches)
 from ._index import (DEFAULT_QUERY_CHUNK, METRICS, _added_rows, _base_arrays, _check_k_refine, _check_nprobe, _check_splits_chunk,
-                     _chunked_workspace_bytes, _list_layout, _on_device, _outputs, _prep, _provenance, _query_groups, _result, _row_norms,
-                     _rows, _rows_of_width)
+                     _chunked_workspace_bytes, _group_runs, _list_layout, _on_device, _outputs, _pack16, _phrase_args, _phrase_blocks,
+                     _phrase_outputs, _PhraseBlocks, _prep, _provenance, _query_groups, _result, _row_norms, _rows, _rows_of_width,
+                     _sequence_tables, _sequences)
 from .kmeans import _device, _stream, _vp
 
-MAX_PHRASE_ROWS = 64            # DT_MAX_M of csrc/dtw.hip: one wave holds a phrase
-MAX_SEQUENCE_ROWS = 65536       # DT_MAX_SEQ: the DP along one sequence is serial
-DEFAULT_PHRASE_CHUNK = 4096
-STORAGES = {"fp16": (0, torch.float16), "bf16": (1, torch.bfloat16)}     # SYLBER_KNN16_FP16 / _BF16: the planes of search_refined
 RERANK_CHUNK = 32               # DT_RR_CH of csrc/dtw16.hip: the columns of a sequence that search_phrases_refined re-ranks at a time
-
-
-def _phrase_outputs(P: int, k: int, device):
-    """``(costs fp32 [P, k], seqs int64 [P, k], spans int64 [P, k, 2])`` of a phrase search"""
-    return (torch.empty((P, k), dtype=torch.float32, device=device), torch.empty((P, k), dtype=torch.int64, device=device),
-            torch.empty((P, k, 2), dtype=torch.int64, device=device))
-
-
-class _PhraseBlocks:
-    """one chunk of phrases as ``sylber_dtw_plan`` packs it: ``Pc`` phrases in ``nb`` blocks of 128 rows (``qp``, padding rows zero)
-    against ``C`` cuts; ``slots`` = the most phrases in any block; ``place`` / ``ln``: first packed row and length of each phrase"""
-
-    def __init__(self, dev, Pc, nb, C, slots, place, ln, qp, meta, slot_phrase, block_rows, cut_rows, pg):
-        self.dev, self.Pc, self.nb, self.C, self.slots, self.place, self.ln, self.qp = dev, Pc, nb, C, slots, place, ln, qp
-        self._host = (meta, slot_phrase, block_rows, cut_rows)
-        self._pg = pg
-
-    def tables(self):
-        """``(row meta, slot -> phrase, rows per block, cut rows, the phrases' groups or None)`` on the device"""
-        meta_d, sp_d, br_d, cut_d = (torch.from_numpy(a).to(self.dev) for a in self._host)
-        return meta_d, sp_d, br_d, cut_d, (_on_device(self._pg, np.int32, self.dev) if self._pg is not None else None)
 
 
 class SyllableIndex:
@@ -178,18 +155,7 @@ class SyllableIndex:
     # ---- two-stage search ------------------------------------------------------------------------------------------------------------
     def _pack16(self, x: torch.Tensor, storage: str, refuse: bool) -> torch.Tensor:
         """fp32 rows on the device -> their 16-bit rows (csrc/knn16.hip); ``refuse``: a finite value that fp16 cannot hold is an error"""
-        code, dtype = STORAGES[storage]
-        lib = _lib.load()
-        out = torch.empty(x.shape, dtype=dtype, device=self.device)
-        if x.shape[0] == 0:
-            return out
-        sat = torch.zeros(1, dtype=torch.int32, device=self.device) if refuse and storage == "fp16" else None
-        with torch.cuda.device(self.device):
-            _lib.check(lib.sylber_knn16_pack(_vp(x), x.shape[0], x.shape[1], code, _vp(out), _vp(sat), _stream(self.device)),
-                       "sylber_knn16_pack")
-        if sat is not None and int(sat.item()):
-            raise ValueError('%d stored values lie beyond +-65504, the range of storage="fp16": use storage="bf16"' % int(sat.item()))
-        return out
+        return _pack16(x, storage, refuse)
 
     def half_rows(self, storage: str = "fp16") -> torch.Tensor:
         """the ``[N, D]`` 16-bit plane of the stored rows that ``search_refined(storage=...)`` scans (``torch.float16`` or
@@ -258,29 +224,11 @@ class SyllableIndex:
         maximal runs of consecutive rows with equal group, numbered in row order (``from_outputs``: one per non-empty clip)"""
         N = len(self)
         if self._seq_cache is None or self._seq_cache[0] != N:
-            if N == 0:
-                off = np.zeros(1, np.int64)
-            else:
-                g = self._g.cpu().numpy()
-                off = np.concatenate([[0], np.nonzero(g[1:] != g[:-1])[0] + 1, [N]]).astype(np.int64)
-            self._seq_cache = (N, off)
+            self._seq_cache = (N, _group_runs(self._g, N))
         return self._seq_cache[1].copy()
 
     def _sequences(self, sequences) -> np.ndarray:
-        N = len(self)
-        if sequences is None:
-            off = self.sequence_offsets()
-        else:
-            a = np.asarray(sequences.detach().cpu().numpy() if torch.is_tensor(sequences) else sequences)
-            if a.ndim != 1 or a.size < 2 or a.dtype.kind not in "iu":
-                raise ValueError("sequences must be integer offsets [S + 1]")
-            off = a.astype(np.int64)
-            if off[0] != 0 or off[-1] != N or np.any(np.diff(off) < 1):
-                raise ValueError("sequences must ascend from 0 to %d rows without an empty sequence" % N)
-        longest = int(np.diff(off).max())
-        if longest > MAX_SEQUENCE_ROWS:
-            raise ValueError("a sequence has %d rows, more than %d: cut it with sequences=" % (longest, MAX_SEQUENCE_ROWS))
-        return off
+        return _sequences(sequences, len(self), self.sequence_offsets)
 
     def search_phrases(self, phrases, k: int, *, lengths=None, groups=None, exclude_same_group: bool = False, sequences=None,
                        splits: int = 0, phrase_chunk: int = DEFAULT_PHRASE_CHUNK, block_phrases: int = 0,
@@ -410,77 +358,20 @@ class SyllableIndex:
                                                  _vp(seqs[p0:p1]), _vp(spans[p0:p1]), _vp(ws), st), "sylber_dtw_rerank")
         return (costs, seqs, spans, cand.to(torch.int64), coarse) if return_candidates else (costs, seqs, spans)
 
-    # the arguments and the plumbing that search_phrases and search_phrases_refined share
+    # the arguments and the plumbing that every phrase search shares: _index.py holds them, these keep their names
     def _phrase_args(self, phrases, lengths, groups, exclude_same_group, sequences, splits, phrase_chunk, block_phrases):
         """the checks of a phrase search -> ``(phrase rows [sum m, D] as given, lengths int64 [P], the phrases' groups on the host or
         None, sequence offsets int64 [S + 1])``, or ``ValueError``"""
-        if len(self) == 0:
-            raise ValueError("the index is empty")
-        if lengths is None:
-            if torch.is_tensor(phrases) or isinstance(phrases, np.ndarray):
-                raise ValueError("phrases given as one [sum m, D] array need lengths=")
-            parts = [_rows(p, "phrases[%d]" % i) for i, p in enumerate(phrases)]
-            lens = np.array([p.shape[0] for p in parts], np.int64)
-            for p in parts:
-                _rows_of_width(p, self.dim, "phrases")
-            q = torch.cat([p.to(self.device, torch.float32) for p in parts]) if parts else torch.zeros((0, self.dim), device=self.device)
-        else:
-            q = _rows_of_width(phrases, self.dim, "phrases")
-            lens = np.asarray(lengths.detach().cpu().numpy() if torch.is_tensor(lengths) else lengths)
-            if lens.ndim != 1 or (lens.size and lens.dtype.kind not in "iu"):
-                raise ValueError("lengths must be a 1-D sequence of integers")
-            lens = lens.astype(np.int64)
-            if int(lens.sum()) != q.shape[0]:
-                raise ValueError("lengths sum to %d, phrases has %d rows" % (int(lens.sum()), q.shape[0]))
-        P = int(lens.size)
-        if P and (lens.min() < 1 or lens.max() > MAX_PHRASE_ROWS):
-            raise ValueError("a phrase has between 1 and %d rows, got lengths from %d to %d" % (MAX_PHRASE_ROWS, lens.min(), lens.max()))
-        pg = _query_groups(groups, P, exclude_same_group, None, "phrases")         # on the host: a chunk's groups go to the device with it
-        if int(splits) < 0 or int(phrase_chunk) < 1 or int(block_phrases) < 0:
-            raise ValueError("splits and block_phrases must be >= 0 and phrase_chunk >= 1")
-        return q, lens, pg, self._sequences(sequences)
+        return _phrase_args(len(self), self.dim, self.device, self.sequence_offsets, phrases, lengths, groups, exclude_same_group,
+                            sequences, splits, phrase_chunk, block_phrases)
 
     def _sequence_tables(self, off: np.ndarray, with_groups: bool):
         """plumbing: the sequence of every row and (for the exclusion) the group of every sequence, on the device"""
-        dev = self.device
-        off_d = torch.from_numpy(off).to(dev)
-        seq_id = torch.repeat_interleave(torch.arange(off.size - 1, dtype=torch.int32, device=dev), off_d[1:] - off_d[:-1])
-        return seq_id, (self._g.index_select(0, off_d[:-1]) if with_groups else None)
+        return _sequence_tables(off, self._g if with_groups else None, self.device)
 
     def _phrase_blocks(self, lib, qd, lens, p0: int, p1: int, off, list_size: int, splits, block_phrases, pg) -> "_PhraseBlocks":
-        """phrases ``p0 : p1`` of the prepared rows ``qd`` packed by ``sylber_dtw_plan`` for lists of ``list_size`` entries: the
-        packed layout of the chunk's rows (where each row goes, what it is, which phrase owns each slot), the rows scattered into
-        zeroed 128-row blocks, and the cut table"""
-        dev = self.device
-        S = off.size - 1
-        off32 = np.ascontiguousarray(off, np.int32)
-        i32p = ctypes.POINTER(ctypes.c_int32)
-        Pc = p1 - p0
-        ln = np.ascontiguousarray(lens[p0:p1], np.int32)
-        nb, ph = ctypes.c_int32(0), ctypes.c_int32(0)
-        place = np.empty(Pc, np.int32)
-        args = (off32.ctypes.data_as(i32p), S, ln.ctypes.data_as(i32p), Pc, list_size, int(splits), int(block_phrases))
-        C = int(lib.sylber_dtw_plan(*args, None, 0, place.ctypes.data_as(i32p), ctypes.byref(nb), ctypes.byref(ph)))
-        cut_rows = np.empty(max(C, 1) + 1, np.int32)
-        if C < 1 or int(lib.sylber_dtw_plan(*args, cut_rows.ctypes.data_as(i32p), C + 1, None, None, None)) != C:
-            raise _lib.SylberHipError("sylber_dtw_plan failed (%d)" % C)
-        nb = nb.value
-        R = int(ln.sum())
-        first = np.repeat(place.astype(np.int64), ln)
-        local = np.arange(R) - np.repeat(np.cumsum(ln) - ln, ln)
-        blk = place // 128
-        slot = np.arange(Pc) - np.searchsorted(blk, blk, side="left")
-        meta = np.full(nb * 128, -1, np.int32)
-        meta[first + local] = local | ((local == np.repeat(ln, ln) - 1).astype(np.int64) << 7) | (np.repeat(slot, ln) << 8)
-        slot_phrase = np.full(nb * 128, -1, np.int32)
-        slot_phrase[blk.astype(np.int64) * 128 + slot] = np.arange(Pc)
-        block_rows = np.zeros(nb, np.int32)
-        np.maximum.at(block_rows, blk, place % 128 + ln)
-        r0 = int(lens[:p0].sum())
-        qp = torch.zeros((nb * 128, self.dim), dtype=torch.float32, device=dev)
-        qp[torch.from_numpy(first + local).to(dev)] = qd[r0:r0 + R]
-        return _PhraseBlocks(dev, Pc, nb, C, int(slot.max()) + 1, place, ln, qp, meta, slot_phrase, block_rows, cut_rows,
-                             pg[p0:p1] if pg is not None else None)
+        """phrases ``p0 : p1`` of the prepared rows ``qd`` packed by ``sylber_dtw_plan`` for lists of ``list_size`` entries"""
+        return _phrase_blocks(lib, self.device, qd, lens, p0, p1, off, list_size, splits, block_phrases, pg)
 
     # ---- persistence ----------------------------------------------------------------------------------------------------------------
     def save(self, path: str) -> None:

@@ -12,7 +12,16 @@ yardstick time / phrase-search time.  Prints one JSON line (rows also go to stde
 the same run, on the same phrases and index, the whole-call time of ``search_phrases_refined(k, refine, storage)`` beside
 ``search_phrases``'s (``refined_over_phrase`` = two-stage time / ``search_phrases`` time: below 1 is faster), and for refine 1, 2, 4
 and 8 the share of phrases whose exact top-k (``recovered_topk``) and whose exact best sequence (``recovered_top1``) the two-stage
-call returns.  The 16-bit plane is built before anything is timed."""
+call returns.  The 16-bit plane is built before anything is timed.
+
+``--pq [--M 48] [--storage fp16|bf16] [--refine 4]`` (with ``--refined``) adds the compressed leg (csrc/dtwpq.hip,
+``PQSyllableIndex.search_phrases``) on codes of the same rows: the whole-call time with the fp32 rows held (``pq_held_ms``: exact
+re-rank on the rows) and of the call that runs after ``drop_rows()`` (``pq_dropped_ms``: ``rerank=False``, re-rank on the decoded
+candidates; the two calls are bitwise the same before and after the drop), each over ``search_phrases_refined``'s time in the same
+run; for refine 1, 2, 4 and 8 the share of phrases whose exact top-k comes back (rows held: the same list; rows dropped: the same
+set of sequences); and the device bytes of each index.  The codebooks are the sub-rows of 256 stored rows drawn at random, not
+k-means: the rows are independent gaussian, so training has no structure to find.  Codes, 16-bit codebooks and reconstruction norms
+are built before anything is timed."""
 import argparse
 import json
 import os
@@ -49,6 +58,8 @@ def main():
     ap.add_argument("--refined", action="store_true")
     ap.add_argument("--storage", default="fp16", choices=["fp16", "bf16"])
     ap.add_argument("--refine", type=int, default=4)
+    ap.add_argument("--pq", action="store_true")
+    ap.add_argument("--M", type=int, default=48)
     args = ap.parse_args()
     from sylber_amd import SyllableIndex
     dev = torch.device("cuda:0")
@@ -65,6 +76,15 @@ def main():
     idx.sequence_offsets()
     if args.refined:
         idx.half_rows(args.storage)
+    pq = None
+    if args.pq:
+        if not args.refined:
+            ap.error("--pq is measured beside search_phrases_refined: pass --refined too")
+        from sylber_amd import PQSyllableIndex
+        pick = torch.randperm(N, device=dev, generator=g)[:256]
+        cb = idx.features[pick].reshape(256, args.M, D // args.M).permute(1, 0, 2).contiguous()
+        pq = PQSyllableIndex.build(idx, args.M, codebooks=cb)
+        pq.search_phrases(idx.features[:2], 1, 1, args.storage, lengths=[2])
     out = []
     for rows in [int(v) for v in args.rows.split(",")]:
         q = idx.features[torch.randint(0, N - rows, (1,), device=dev, generator=g).item():][:rows] + 0.5 * torch.randn(rows, D, device=dev, generator=g)
@@ -90,9 +110,30 @@ def main():
                 row.update(storage=args.storage, refine=args.refine, refined_ms=round(t2, 2), refined_ms_min_max=[round(lo, 2), round(hi, 2)],
                            refined_over_phrase=round(t2 / t, 3), recovered_topk={r: v[0] for r, v in share.items()},
                            recovered_top1={r: v[1] for r, v in share.items()})
+            if pq is not None:
+                t3, lo3, hi3 = timed(lambda: pq.search_phrases(ph, k, args.refine, args.storage, lengths=ln, rerank=True), args.iters)
+                t4, lo4, hi4 = timed(lambda: pq.search_phrases(ph, k, args.refine, args.storage, lengths=ln, rerank=False), args.iters)
+                want = exact.sort(1).values
+                held, dropped = {}, {}
+                for r in (1, 2, 4, 8):
+                    if k * r > 128:
+                        continue
+                    got = pq.search_phrases(ph, k, r, args.storage, lengths=ln, rerank=True)[1]
+                    held[str(r)] = round(float((got == exact).all(1).float().mean()), 4)
+                    got = pq.search_phrases(ph, k, r, args.storage, lengths=ln, rerank=False)[1]
+                    dropped[str(r)] = round(float((got.sort(1).values == want).all(1).float().mean()), 4)
+                row.update(M=args.M, pq_held_ms=round(t3, 2), pq_held_ms_min_max=[round(lo3, 2), round(hi3, 2)], pq_dropped_ms=round(t4, 2),
+                           pq_dropped_ms_min_max=[round(lo4, 2), round(hi4, 2)], pq_held_over_refined=round(t3 / t2, 3),
+                           pq_dropped_over_refined=round(t4 / t2, 3), pq_recovered_topk_held=held, pq_recovered_topk_dropped=dropped)
             print(json.dumps(row), file=sys.stderr, flush=True)
             out.append(row)
-    print(json.dumps({"D": D, "metric": "l2", "iters": args.iters, "rows": out}))
+    res = {"D": D, "metric": "l2", "iters": args.iters, "rows": out}
+    if pq is not None:
+        held = pq.nbytes
+        pq.drop_rows()
+        res["device_bytes"] = {"syllable_index_rows_norms_groups_plane": 4 * N * D + 4 * N + 4 * N + 2 * N * D, "pq_rows_held": held,
+                               "pq_rows_dropped": pq.nbytes}
+    print(json.dumps(res))
 
 
 if __name__ == "__main__":
