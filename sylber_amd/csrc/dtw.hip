@@ -10,11 +10,15 @@
 //     The additions are the contract's, one per cell in a fixed order: nothing is re-associated.
 //     A sequence start masks the predecessors of the previous column; at a sequence end the lane of the phrase's last row hands
 //     (cost, sequence, start, end) to the phrase's sorted top-k list in LDS (kn_insert's scheme with a payload).
-//   * dtw_merge_kernel / dtw_finish_kernel: the C partial lists of a phrase merged pairwise, as the k-NN merge does, with the span.
+//     Only the fp32 staging and K loop are written here: the column data, the epilogue, the wavefront and the write-out are
+//     dtw_tile.h's with SPAN = true, the text that the 16-bit scans (dtw16_scan.h) compile with SPAN = false.
+//   * knn_merge_kernel<true> (knn_lists.h) / dtw_finish_kernel: the C partial lists of a phrase merged pairwise, as the k-NN merge
+//     does, with the span.  Sequences of different cuts differ, so only the (+inf, INT_MAX) fillers can be equal.
 // Lists are ordered by (cost, sequence): strict and total over the admissible sequences, so the result is unique.
 #include "kernels.h"
 #include "../../include/sylber_hip.h"
 #include "dtw_tile.h"
+#include "knn_lists.h"
 #include <climits>
 
 constexpr int DT_TARGET_BLOCKS = 512;                     // automatic cuts: (query blocks) x C >= 2 workgroups per CU
@@ -33,13 +37,7 @@ __global__ __launch_bounds__(256) void dtw_search_kernel(const float* __restrict
     extern __shared__ __attribute__((aligned(16))) float dt_smem[];
     float* xs = dt_smem;                                   // staging of the query rows
     float* cs = dt_smem + KN_BM * KN_LD;                   // staging of the database rows
-    float* dm = dt_smem;                                   // [128][DT_LD] local costs of the tile, aliasing the staging
-    float* cns = dt_smem + KN_BM * DT_LD;
-    int* sq = (int*)(cns + KN_BN);                         // [130] sequence of columns n0 - 1 .. n0 + 128 (-1 outside the cut)
-    int* sgs = sq + 132;                                   // [128] group of each column's sequence
-    int2* lp = (int2*)(sgs + KN_BN);                       // [ph][k] (first row, last row) of each entry
-    float* ls = (float*)(lp + ph * k);                     // [ph][k] sorted costs
-    int* li = (int*)(ls + ph * k);                         // [ph][k] their sequences
+    const DtLds<true> L(dt_smem, ph, k);
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const int wm = wave >> 1, wn = wave & 1;
     const int b = blockIdx.x, cut = blockIdx.y;
@@ -47,7 +45,7 @@ __global__ __launch_bounds__(256) void dtw_search_kernel(const float* __restrict
     rlo = rlo < 0 ? 0 : rlo; rhi = rhi > N ? N : rhi;
     const int nrow = block_rows[b];
     const int tiles = rhi > rlo ? (rhi - rlo + KN_BN - 1) / KN_BN : 0;
-    for (int e = tid; e < ph * k; e += 256) { ls[e] = INFINITY; li[e] = INT_MAX; lp[e] = make_int2(-1, -1); }
+    L.clear(tid, ph, k);
     const int sr = tid >> 1, sh = (tid & 1) * 8;
     const float* qrow = q + ((size_t)b * KN_BM + sr) * D + sh;
     float* xdst = xs + sr * KN_LD + (sh >> 1);
@@ -61,18 +59,8 @@ __global__ __launch_bounds__(256) void dtw_search_kernel(const float* __restrict
         live[fm] = wm * 64 + fm * 32 < nrow;
         if (qsq) qn[fm] = qsq[(size_t)b * KN_BM + wm * 64 + fm * 32 + frow];
     }
-    // the DP's lane state: waves 0 and 1 own packed rows wave * 64 + lane
-    const int drow = (wave & 1) * 64 + lane;
-    const int mt = wave < 2 ? meta[(size_t)b * KN_BM + drow] : -1;
-    const int pi_ = mt & 127, lastrow = (mt >> 7) & 1, slot = (mt >> 8) & 255;
-    const bool valid = mt >= 0 && slot < ph;
-    int maxi = valid ? pi_ : -1;
-#pragma unroll
-    for (int o = 32; o; o >>= 1) { const int v = __shfl_xor(maxi, o); maxi = v > maxi ? v : maxi; }
-    int pg = 0;
-    if (pgrp && valid && lastrow) { const int pid = slot_phrase[(size_t)b * KN_BM + slot]; pg = pid >= 0 && pid < P ? pgrp[pid] : 0; }
-    float a_cur = INFINITY, a_prev = INFINITY, bc = INFINITY;      // A[i][last column done], A[i][the one before], best of the sequence
-    int s_cur = 0, s_prev = 0, bst = 0, be = 0;
+    const DtRow row(meta, slot_phrase, pgrp, b, P, ph, wave, lane);
+    DtLane st;
 
     f32x16_t acc[2][2];
     float4 xa, xb, ca, cb;
@@ -89,125 +77,19 @@ __global__ __launch_bounds__(256) void dtw_search_kernel(const float* __restrict
         if (ks == 0) kn_zero(acc);
         __syncthreads();                                   // previous fragments, the cost tile, cns / sq / sgs are all read
         kn_stage(xdst, cdst, xa, xb, ca, cb);
-        if (ks == 0) {
-            if (tid < KN_BN) {
-                const int j = n0 + tid;
-                cns[tid] = (cn && j < rhi) ? cn[j] : 0.f;
-                sgs[tid] = (sgrp && j < rhi) ? sgrp[seqid[j]] : 0;
-            }
-            if (tid < KN_BN + 2) {
-                const int j = n0 - 1 + tid;
-                sq[tid] = (j >= rlo && j < rhi) ? seqid[j] : -1;
-            }
-        }
+        if (ks == 0) dt_tile_meta(L, tid, n0, rlo, rhi, cn, seqid, sgrp, [](int) { return false; });
         __syncthreads();
         if (t + 1 < T) fetch(t + 1);
         kn_mma(xs, cs, wm, wn, frow, fh, acc, live[0], live[1]);
         if (ks != ksteps - 1) continue;
-        // epilogue: lane holds phrase row wm*64 + fm*32 + frow against columns wn*64 + fn*32 + 8g + 4fh + e.  s = fmaf(-2, dot, c_j) as
-        // sylber_knn_search; d = max(0, ||q||^2 + s) (L2) or max(0, 1 - (-s / 2)) (cosine); a NaN d counts as +inf.
         __syncthreads();                                   // every wave is past its fragment reads: the cost tile aliases the staging
-#pragma unroll
-        for (int fm = 0; fm < 2; ++fm) {
-            if (!live[fm]) continue;
-            const int rl = wm * 64 + fm * 32 + frow;
-#pragma unroll
-            for (int fn = 0; fn < 2; ++fn)
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    float d[4];
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        const int cl = wn * 64 + fn * 32 + 8 * g + 4 * fh + e;
-                        const float s = fmaf(-2.0f, acc[fm][fn][4 * g + e], cns[cl]);
-                        const float v = qsq ? qn[fm] + s : 1.0f - (0.f - 0.5f * s);
-                        d[e] = v != v ? INFINITY : fmaxf(0.f, v);
-                    }
-                    *(float4*)(dm + rl * DT_LD + wn * 64 + fn * 32 + 8 * g + 4 * fh) = make_float4(d[0], d[1], d[2], d[3]);
-                }
-        }
+        dt_cost_tile(L.dm, L.cns, acc, qsq != nullptr, qn, live, wm, wn, frow, fh);
         __syncthreads();
-        if (wave >= 2 || maxi < 0) continue;               // wave-uniform
-        const int ncol = rhi - n0 < KN_BN ? rhi - n0 : KN_BN;
-        const float* dr = dm + drow * DT_LD;
-        for (int st = 0; st < ncol + maxi; ++st) {
-            const float u_cur = __shfl_up(a_cur, 1), u_prev = __shfl_up(a_prev, 1);
-            const int us_cur = __shfl_up(s_cur, 1), us_prev = __shfl_up(s_prev, 1);
-            const int j = st - pi_;
-            bool fin = false;
-            int fseq = 0;
-            if (valid && j >= 0 && j < ncol) {
-                const float d = dr[j];
-                const int sj = sq[j + 1];
-                const bool isstart = sq[j] != sj;
-                float A;
-                int sa;
-                if (pi_ == 0) { A = d; sa = n0 + j; }
-                else {
-                    float best = isstart ? INFINITY : u_prev;          // (i-1, j-1), then (i-1, j), then (i, j-1): the first smallest
-                    int bs = us_prev;
-                    if (u_cur < best) { best = u_cur; bs = us_cur; }
-                    const float left = isstart ? INFINITY : a_cur;
-                    if (left < best) { best = left; bs = s_cur; }
-                    A = d + best; sa = bs;
-                }
-                a_prev = a_cur; s_prev = s_cur; a_cur = A; s_cur = sa;
-                if (lastrow) {
-                    if (isstart) bc = INFINITY;
-                    if (A < bc) { bc = A; bst = sa; be = n0 + j; }     // the smallest end column on ties
-                    if (sq[j + 2] != sj && bc < INFINITY && !(sgrp && sgs[j] == pg)) {
-                        fseq = sj;
-                        fin = kn_better(bc, sj, ls[slot * k + k - 1], li[slot * k + k - 1]);
-                    }
-                }
-            }
-            uint64_t fb = __ballot(fin);
-            while (fb) {
-                const int c = __ffsll((unsigned long long)fb) - 1;
-                fb &= fb - 1;
-                const float v = __shfl(bc, c);
-                const int vs = __shfl(fseq, c), v0 = __shfl(bst, c), v1 = __shfl(be, c), sl = __shfl(slot, c);
-                kn_insert_t<true>(ls + sl * k, li + sl * k, lp + sl * k, k, lane, v, vs, make_int2(v0, v1));
-            }
-        }
+        if (wave >= 2 || row.maxi < 0) continue;           // wave-uniform
+        dt_wavefront(L, row, st, lane, n0, rhi - n0 < KN_BN ? rhi - n0 : KN_BN, sgrp != nullptr, k);
     }
     __syncthreads();
-    for (int sl = wave; sl < ph; sl += 4) {
-        const int pid = slot_phrase[(size_t)b * KN_BM + sl];
-        if (pid < 0 || pid >= P) break;
-        const size_t o = ((size_t)pid * C + cut) * k;
-        for (int e = lane; e < k; e += 64) { ps[o + e] = ls[sl * k + e]; pi[o + e] = li[sl * k + e]; pp[o + e] = lp[sl * k + e]; }
-    }
-}
-
-// knn_merge_kernel with a payload: lists 2p and 2p + 1 of phrase r -> list p.  Sequences of different cuts differ, so only the
-// (+inf, INT_MAX) fillers can be equal.
-__global__ __launch_bounds__(64) void dtw_merge_kernel(const float* __restrict__ ss, const int32_t* __restrict__ si, const int2* __restrict__ sp,
-                                                       int m, int k, float* __restrict__ ds, int32_t* __restrict__ di, int2* __restrict__ dp) {
-    const int r = blockIdx.x, p = blockIdx.y, lane = threadIdx.x;
-    const int mo = (m + 1) / 2;
-    const size_t ao = ((size_t)r * m + 2 * p) * k, oo = ((size_t)r * mo + p) * k;
-    const float* as = ss + ao; const int32_t* ai = si + ao; const int2* ap = sp + ao;
-    float* os = ds + oo; int32_t* oi = di + oo; int2* op = dp + oo;
-    if (2 * p + 1 >= m) {
-        for (int e = lane; e < k; e += 64) { os[e] = as[e]; oi[e] = ai[e]; op[e] = ap[e]; }
-        return;
-    }
-    const float* bs = as + k; const int32_t* bi = ai + k; const int2* bp = ap + k;
-    for (int e = lane; e < k; e += 64) {
-        {   // A[e]: + #{B strictly better}
-            const float v = as[e]; const int j = ai[e];
-            int lo = 0, hi = k;
-            while (lo < hi) { const int mid = (lo + hi) >> 1; if (kn_better(bs[mid], bi[mid], v, j)) lo = mid + 1; else hi = mid; }
-            if (e + lo < k) { os[e + lo] = v; oi[e + lo] = j; op[e + lo] = ap[e]; }
-        }
-        {   // B[e]: + #{A not worse}
-            const float v = bs[e]; const int j = bi[e];
-            int lo = 0, hi = k;
-            while (lo < hi) { const int mid = (lo + hi) >> 1; if (!kn_better(v, j, as[mid], ai[mid])) lo = mid + 1; else hi = mid; }
-            if (e + lo < k) { os[e + lo] = v; oi[e + lo] = j; op[e + lo] = bp[e]; }
-        }
-    }
+    dt_write_lists(L, slot_phrase, b, P, ph, C, cut, k, wave, lane, ps, pi, pp);
 }
 
 // fillers -> (+inf, -1, (-1, -1)); spans as (first row, one past the last row)
@@ -321,7 +203,8 @@ extern "C" int sylber_dtw_search(const float* q_dev, int32_t n_blocks, const int
     float* cs = s0; int32_t* ci = i0; int2* cp = p0;
     float* os = s1; int32_t* oi = i1; int2* op = p1;
     for (int m = cuts; m > 1; m = (m + 1) / 2) {
-        hipLaunchKernelGGL(dtw_merge_kernel, dim3((unsigned)n_phrases, (unsigned)((m + 1) / 2)), dim3(64), 0, s, cs, ci, cp, m, k, os, oi, op);
+        hipLaunchKernelGGL(knn_merge_kernel<true>, dim3((unsigned)n_phrases, (unsigned)((m + 1) / 2)), dim3(64), 0, s, cs, ci, (const int2*)cp, m, k,
+                           os, oi, op);
         HIP_TRY(hipGetLastError());
         float* ts = cs; cs = os; os = ts;
         int32_t* ti = ci; ci = oi; oi = ti;

@@ -4,11 +4,16 @@
 //   * dtw16_scan_kernel<FMT>: dtw_search_kernel's structure -- grid (query blocks of whole phrases) x C database cuts on sequence
 //     starts, the 128 x 128 cost tile in LDS aliasing the staging, the anti-diagonal wavefront on waves 0 and 1 with the lane state
 //     carried over tile edges -- around knn16_scan_kernel's contraction (knn16_tile.h: 16-bit staging, v_mfma_f32_32x32x16_{f16,bf16},
-//     K steps of 32).  The C layout is the fp32 MFMA's, so the epilogue that writes the local costs is dtw_search_kernel's with the
-//     coarse score t = fmaf(-2, dot16, c_j) in place of s.  dot16 is one MFMA chain over K in ascending 16-wide steps whatever tile,
-//     cut or block row computes it, and the DP adds in a fixed cell order, so a coarse cost's bits are a function of (phrase,
-//     sequence) alone.  No start is tracked and a list entry is (cost, sequence) without a span: 8 B, half of dtw_search_kernel's.
-//     The C partial lists of a phrase are merged by knn_lists.h's merge.
+//     K steps of 32).  dot16 is one MFMA chain over K in ascending 16-wide steps whatever tile, cut or block row computes it, and
+//     the DP adds in a fixed cell order, so a coarse cost's bits are a function of (phrase, sequence) alone.  No start is tracked
+//     and a list entry is (cost, sequence) without a span: 8 B, half of dtw_search_kernel's.  Of dtw_tile.h's pieces the kernel
+//     uses the column data (dt_tile_meta) and keeps the rest written out, as knn16_scan_kernel keeps its K loop: built from the
+//     shared epilogue and wavefront (as dtwpq_scan_kernel and dtw_search_kernel are) its register allocation around the
+//     accumulators came out different and search_phrases_refined measured 0.5 to 1.4 % slower
+//     (profiles/phrase_scan_refactor_ab.md); as written its instructions are those it had before the pieces existed.  The text is
+//     dtw_tile.h's, SPAN = false: tests/test_gpu_dtwpq.py holds dtwpq_scan_kernel, which is built from the pieces, bitwise to this
+//     kernel on the materialised plane.  The C partial lists of a phrase are merged by knn_lists.h's merge; the host path is
+//     dtw16_scan.h's, shared with sylber_dtwpq_scan.
 //   * dtw_rerank_kernel: one wave per (phrase, candidate) pair, lane l owns phrase row l.  The wave walks the candidate sequence in
 //     chunks of DT_RR_CH columns: for a chunk every lane forms its row's dots with the explicit ascending __builtin_fmaf chain from 0
 //     over D (what v_mfma_f32_32x32x2_f32 performs in dtw_search_kernel, as knn_rerank_kernel relies on), the database row being the
@@ -25,20 +30,15 @@
 //   dtw_rerank_kernel   9 216 B (64 rows x 36 floats), 64 threads: LDS allows 17 workgroups per CU, so the wave slots and registers
 //                       bound it, not LDS.
 #include "kernels.h"
-#include "../../include/sylber_hip.h"
-#include "dtw_tile.h"
-#include "knn16_tile.h"
-#include "knn_lists.h"
+#include "dtw16_scan.h"
 
 constexpr int DT_RR_CH = 32;                              // columns of a re-rank chunk (RERANK_CHUNK of search.py)
 constexpr int DT_RR_LD = 36;                              // row stride of the chunk's costs: lane i reads d[i][t - i], bank (3 i + t) % 32
 
-static size_t d16_lds_bytes(int ph, int m) { return (size_t)DT_FIXED * 4 + (size_t)ph * m * 8; }
-
 // meta / slot_phrase / block_rows / cuts / groups as dtw_search_kernel.  q: the packed phrase blocks' 16-bit rows [n_blocks * 128, D],
 // qsq: the fp32 ||q_i||^2 of the unrounded packed rows (L2) or null (cosine); x: the 16-bit plane; cn: the fp32 ||x_j||^2 (L2) or null.
 // Writes the sorted best m (cost, sequence) of every phrase over the cut to ps / pi [P][C][m]; entries that did not fill stay
-// (+inf, INT_MAX).
+// (+inf, INT_MAX).  Written out: see the file header.
 template <int FMT>
 __global__ __launch_bounds__(256) void dtw16_scan_kernel(const bf16_t* __restrict__ q, const float* __restrict__ qsq,
                                                          const int32_t* __restrict__ meta, const int32_t* __restrict__ slot_phrase,
@@ -56,6 +56,7 @@ __global__ __launch_bounds__(256) void dtw16_scan_kernel(const bf16_t* __restric
     int* sgs = sq + 132;                                   // [128] group of each column's sequence
     float* ls = (float*)(sgs + KN_BN);                     // [ph][m] sorted coarse costs
     int* li = (int*)(ls + ph * m);                         // [ph][m] their sequences
+    const DtLds<false> L(dt_smem, ph, m);
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const int wm = wave >> 1, wn = wave & 1;
     const int b = blockIdx.x, cut = blockIdx.y;
@@ -111,15 +112,7 @@ __global__ __launch_bounds__(256) void dtw16_scan_kernel(const bf16_t* __restric
         *(uint4*)xdst = xa; *(uint4*)(xdst + 8) = xb;
         *(uint4*)cdst = ca; *(uint4*)(cdst + 8) = cb;
         if (ks == 0) {
-            if (tid < KN_BN) {
-                const int j = n0 + tid;
-                cns[tid] = (cn && j < rhi) ? cn[j] : 0.f;
-                sgs[tid] = (sgrp && j < rhi) ? sgrp[seqid[j]] : 0;
-            }
-            if (tid < KN_BN + 2) {
-                const int j = n0 - 1 + tid;
-                sq[tid] = (j >= rlo && j < rhi) ? seqid[j] : -1;
-            }
+            dt_tile_meta(L, tid, n0, rlo, rhi, cn, seqid, sgrp, [](int) { return false; });
         }
         __syncthreads();
         if (t + 1 < T) fetch(t + 1);
@@ -198,16 +191,6 @@ __global__ __launch_bounds__(256) void dtw16_scan_kernel(const bf16_t* __restric
     }
 }
 
-// the merged lists as candidates: the (+inf, INT_MAX) fillers become (+inf, -1)
-__global__ __launch_bounds__(256) void dtw16_cand_kernel(const float* __restrict__ ls, const int32_t* __restrict__ li, int64_t tot,
-                                                         int32_t* __restrict__ cand, float* __restrict__ coarse) {
-    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (e >= tot) return;
-    const int j = li[e];
-    cand[e] = j == INT_MAX ? -1 : j;
-    coarse[e] = j == INT_MAX ? INFINITY : ls[e];
-}
-
 // Workgroup (one wave) e of phrase p = blockIdx.x / m: the exact subsequence DTW of phrase p (rows prow[p] .. + plen[p] of the packed
 // fp32 blocks q, qsq their ||q_i||^2 (L2) or null) against sequence cand[p][e] (rows soff[s] .. soff[s + 1] of x).  Writes (cost,
 // (start row, end row)) to pc / pspan [P][m]; (+inf, (-1, -1)) for a candidate of -1.
@@ -237,8 +220,7 @@ __global__ __launch_bounds__(64) void dtw_rerank_kernel(const float* __restrict_
     const float* qr = q + (size_t)r * D;
     const float qn = qsq ? qsq[r] : 0.f;
     const bool valid = lane < mp, lastrow = lane == mp - 1;
-    float a_cur = INFINITY, a_prev = INFINITY, bc = INFINITY;
-    int s_cur = 0, s_prev = 0, bst = -1, be = -1;
+    DtLane st;
     float* dr = dsm + lane * DT_RR_LD;
     for (int n0 = j0; n0 < j1; n0 += DT_RR_CH) {
         const int ncol = j1 - n0 < DT_RR_CH ? j1 - n0 : DT_RR_CH;
@@ -263,37 +245,18 @@ __global__ __launch_bounds__(64) void dtw_rerank_kernel(const float* __restrict_
 #pragma unroll
         for (int jj = 0; jj < DT_RR_CH; ++jj) {
             const int j = jj < ncol ? n0 + jj : j1 - 1;
-            const float s = __builtin_fmaf(-2.0f, dot[jj], cn ? cn[j] : 0.f);
-            const float v = qsq ? qn + s : 1.0f - (0.f - 0.5f * s);
-            dr[jj] = v != v ? INFINITY : fmaxf(0.f, v);
+            dr[jj] = dt_cost(dot[jj], cn ? cn[j] : 0.f, qsq != nullptr, qn);
         }
         __syncthreads();
-        for (int st = 0; st < ncol + mp - 1; ++st) {
-            const float u_cur = __shfl_up(a_cur, 1), u_prev = __shfl_up(a_prev, 1);
-            const int us_cur = __shfl_up(s_cur, 1), us_prev = __shfl_up(s_prev, 1);
-            const int j = st - lane;
-            if (valid && j >= 0 && j < ncol) {
-                const float d = dr[j];
-                const bool isstart = n0 + j == j0;
-                float A;
-                int sa;
-                if (lane == 0) { A = d; sa = n0 + j; }
-                else {
-                    float best = isstart ? INFINITY : u_prev;          // (i-1, j-1), then (i-1, j), then (i, j-1): the first smallest
-                    int bs = us_prev;
-                    if (u_cur < best) { best = u_cur; bs = us_cur; }
-                    const float left = isstart ? INFINITY : a_cur;
-                    if (left < best) { best = left; bs = s_cur; }
-                    A = d + best; sa = bs;
-                }
-                a_prev = a_cur; s_prev = s_cur; a_cur = A; s_cur = sa;
-                if (lastrow && A < bc) { bc = A; bst = sa; be = n0 + j; }      // the smallest end column on ties
-            }
+        for (int t = 0; t < ncol + mp - 1; ++t) {          // dtw_tile.h's cell: the candidate is one sequence, starting at j0
+            const DtUp u = dt_up<true>(st);
+            const int j = t - lane;
+            if (valid && j >= 0 && j < ncol) dt_cell<true>(st, u, lane == 0, lastrow, n0 + j == j0, dr[j], n0 + j);
         }
     }
     if (lastrow) {
-        pc[pair] = bc;
-        pspan[pair] = bc < INFINITY ? make_int2(bst, be) : make_int2(-1, -1);
+        pc[pair] = st.bc;
+        pspan[pair] = st.bc < INFINITY ? make_int2(st.bst, st.be) : make_int2(-1, -1);
     }
 }
 
@@ -364,41 +327,17 @@ extern "C" int sylber_dtw16_scan(const void* q16_dev, int32_t n_blocks, const in
     hipStream_t s = (hipStream_t)stream;
     if (!q16_dev || !row_meta_dev || !slot_phrase_dev || !block_rows_dev || !db16_dev || !seq_id_dev || !cut_rows_dev || !cand_dev ||
         !coarse_dev || !workspace_dev) { syl_set_error(what, "null argument"); return 1; }
-    if (n_blocks < 1 || n_phrases < 1 || N < 1 || D < 16 || D % 16) { syl_set_error(what, "need n_blocks, n_phrases, N >= 1 and D a multiple of 16"); return 1; }
-    if (m < 1 || m > KN_KMAX) { syl_set_error(what, "need 1 <= m <= 128"); return 1; }
-    if (block_phrases < 1 || block_phrases > dt_block_phrases(m, 0)) { syl_set_error(what, "block_phrases exceeds what sylber_dtw_plan allows for this m"); return 1; }
-    if (cuts < 1 || cuts > 65535) { syl_set_error(what, "need 1 <= cuts <= 65535"); return 1; }
-    if (metric != SYLBER_KNN_L2 && metric != SYLBER_KNN_IP) { syl_set_error(what, "unknown metric"); return 1; }
-    if (storage != SYLBER_KNN16_FP16 && storage != SYLBER_KNN16_BF16) { syl_set_error(what, "unknown storage"); return 1; }
-    if (metric == SYLBER_KNN_L2 && (!db_norm_dev || !q_norm_dev)) { syl_set_error(what, "the L2 metric needs db_norm_dev and q_norm_dev"); return 1; }
-    if (!phrase_group_dev != !seq_group_dev) { syl_set_error(what, "phrase_group_dev and seq_group_dev go together"); return 1; }
-    if ((int64_t)n_phrases * cuts * m > INT32_MAX / 2) { syl_set_error(what, "n_phrases x cuts x m is too large: use smaller phrase chunks"); return 1; }
-    char* w = (char*)workspace_dev;
-    KnPartials p = kn_partials_carve(w, n_phrases, cuts, m);
-    const size_t lds = d16_lds_bytes(block_phrases, m);
-    const int max_lds = (int)((size_t)DT_FIXED * 4 + DT_LIST_BYTES / 2);
-    const bf16_t* q16 = (const bf16_t*)q16_dev;
-    const bf16_t* x16 = (const bf16_t*)db16_dev;
-    const float* qn = metric == SYLBER_KNN_L2 ? q_norm_dev : nullptr;
-    const float* cn = metric == SYLBER_KNN_L2 ? db_norm_dev : nullptr;
-    const dim3 grid((unsigned)n_blocks, (unsigned)cuts);
-    if (storage == SYLBER_KNN16_FP16) {
+    return dt16_scan_host(what, nullptr, "the L2 metric needs db_norm_dev and q_norm_dev", n_blocks, n_phrases, block_phrases, N, D, db_norm_dev,
+                          q_norm_dev, metric, storage, m, cuts, phrase_group_dev, seq_group_dev, cand_dev, coarse_dev, workspace_dev, s,
+                          [&](auto fmt, dim3 grid, size_t lds, int max_lds, const float* qn, const float* cn, float* ps, int32_t* pi) {
+        constexpr int FMT = decltype(fmt)::value;
         static PerDeviceOnce once;
-        if (once.need()) HIP_TRY(hipFuncSetAttribute((const void*)dtw16_scan_kernel<FMT_F16>, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds));
-        hipLaunchKernelGGL(dtw16_scan_kernel<FMT_F16>, grid, dim3(256), lds, s, q16, qn, row_meta_dev, slot_phrase_dev, block_rows_dev, n_phrases,
-                           block_phrases, x16, N, D, cn, m, seq_id_dev, cut_rows_dev, phrase_group_dev, seq_group_dev, cuts, p.s0, p.i0);
-    } else {
-        static PerDeviceOnce once;
-        if (once.need()) HIP_TRY(hipFuncSetAttribute((const void*)dtw16_scan_kernel<FMT_BF16>, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds));
-        hipLaunchKernelGGL(dtw16_scan_kernel<FMT_BF16>, grid, dim3(256), lds, s, q16, qn, row_meta_dev, slot_phrase_dev, block_rows_dev, n_phrases,
-                           block_phrases, x16, N, D, cn, m, seq_id_dev, cut_rows_dev, phrase_group_dev, seq_group_dev, cuts, p.s0, p.i0);
-    }
-    HIP_TRY(hipGetLastError());
-    if (kn_merge_lists(p, n_phrases, cuts, m, s)) return 1;
-    const int64_t tot = (int64_t)n_phrases * m;
-    hipLaunchKernelGGL(dtw16_cand_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, p.s0, p.i0, tot, cand_dev, coarse_dev);
-    HIP_TRY(hipGetLastError());
-    return 0;
+        if (once.need()) HIP_TRY(hipFuncSetAttribute((const void*)dtw16_scan_kernel<FMT>, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds));
+        hipLaunchKernelGGL(dtw16_scan_kernel<FMT>, grid, dim3(256), lds, s, (const bf16_t*)q16_dev, qn, row_meta_dev, slot_phrase_dev,
+                           block_rows_dev, n_phrases, block_phrases, (const bf16_t*)db16_dev, N, D, cn, m, seq_id_dev, cut_rows_dev,
+                           phrase_group_dev, seq_group_dev, cuts, ps, pi);
+        return 0;
+    });
 }
 
 extern "C" int sylber_dtw_rerank(const float* q_dev, int32_t n_blocks, const float* q_norm_dev, const int32_t* phrase_row_dev,

@@ -8,10 +8,11 @@
 //     o = (k0 + sh) % dsub, and the thread loads 32 B from codebooks16 + ((mm * 256 + codes[cr * M + mm]) * dsub + o).  Rounding is
 //     element-wise, so that gather IS round16(decode(code)) and the staged bits are those of the materialised plane
 //     sylber_knn16_pack(sylber_pq_decode(codes)): with db_norm = recon_norm the candidates and coarse costs equal
-//     sylber_dtw16_scan's on that plane bit for bit.  The query side, the `in` test for D % 32 == 16, the row clamp, k16_mma, the
-//     epilogue, the wavefront, the list insertion and the write-out are dtw16_scan_kernel's, duplicated here and not shared:
-//     dtw16_scan_kernel's instruction stream stays exactly what it was (profiles/phrase_bench.md measures it), and a fetch passed in
-//     as a functor would have to carry the LDS code bytes and the mask through that kernel too.
+//     sylber_dtw16_scan's on that plane bit for bit.  The LDS carve, the column data, the epilogue, the lane state, the wavefront with
+//     the list insertion and the write-out are dtw_tile.h's pieces (SPAN = false), the host path dtw16_scan.h's; the query side, the
+//     `in` test for D % 32 == 16, the row clamp and the K loop around k16_mma are dtw16_scan_kernel's, which keeps its own text.
+//     What is particular to the codes (where 16 halves lie, the mask, the bytes staged per tile) is the struct Dt16Codes, which the
+//     body takes as a parameter: written straight into the body the same statements made the compiler spill 36 B per lane.
 //   * the mask: the epilogue reads cns[cl] in both metrics, so a masked row (bad[j] != 0) needs only cns = NaN where the tile's cns
 //     is filled; its local cost is then +inf against every phrase row, as a NaN row's.
 //   * the dependent load (code byte, then gather): the tile's 128 x M code bytes are copied to LDS at ks == 0 beside cns / sq / sgs
@@ -25,40 +26,50 @@
 //                       k16_mma, by which every fetch of the tile has been issued and has returned its byte: the byte feeds an
 //                       address).  Two workgroups per CU where dtw16_scan_kernel has two: lists <= 12 784 B.
 #include "kernels.h"
-#include "../../include/sylber_hip.h"
-#include "dtw_tile.h"
-#include "knn16_tile.h"
-#include "knn_lists.h"
+#include "dtw16_scan.h"
 
 constexpr int DPQ_MAX_M = 64;                             // PQ_MAX_M of pq.hip
 constexpr int DPQ_KSUB = 256;                             // centroids per sub-space
 constexpr int DPQ_CODE_OFF = KN_STAGE * 4;                // byte offset of the tile's code bytes in the cost-tile region
 static_assert(DPQ_CODE_OFF + KN_BN * DPQ_MAX_M <= KN_BM * DT_LD * 4, "the code bytes fit in the cost tile behind the staging");
 
-static size_t dpq_lds_bytes(int ph, int m) { return (size_t)DT_FIXED * 4 + (size_t)ph * m * 8; }
+// codes [N][M] (bad [N] or null: 1 = masked row) and cb16 [M][256][dsub], the 16-bit codebooks; dsub % 16 == 0, so the 16 halves lie
+// in one sub-space mm at offset o, and they are 32 B of codebook row code[cr][mm]: round16(decode(code)), rounding being
+// element-wise.  The load depends on the code byte.  The tile's 128 x M code bytes are copied to LDS at ks == 0 and the fetches of
+// the tile's K steps 1 .. read their byte from there; the one fetch issued for the NEXT tile's first K step, before the current
+// tile's epilogue and DP, reads its byte from global memory: its latency lies under the DP.
+struct Dt16Codes {
+    const uint8_t* codes;
+    const uint8_t* bad;
+    const bf16_t* cb16;
+    int M, dsub;
+    __device__ __forceinline__ const bf16_t* halves(int cr, int kc, int ks, int sr, const uint8_t* cds) const {
+        const int mm = kc / dsub, o = kc - mm * dsub;
+        const int code = ks == 0 ? codes[(size_t)cr * M + mm] : cds[sr * M + mm];
+        return cb16 + ((size_t)(mm * DPQ_KSUB + code) * dsub + o);
+    }
+    __device__ __forceinline__ bool masked(int j) const { return bad && bad[j]; }
+    // the two threads of a staging row copy its bytes; a row past the cut repeats the cut's last row, as the fetch clamps it
+    __device__ __forceinline__ void stage(uint8_t* cds, int n0, int rhi, int tid) const {
+        const int sr = tid >> 1;
+        int cr = n0 + sr; cr = cr < rhi ? cr : rhi - 1;
+        for (int mm = tid & 1; mm < M; mm += 2) cds[sr * M + mm] = codes[(size_t)cr * M + mm];
+    }
+};
 
-// As dtw16_scan_kernel, the database given as codes [N][M] (bad [N] or null: 1 = masked row) and cb16 [M][256][D / M], the 16-bit
-// codebooks; cn: the fp32 ||decode(code_j)||^2 (L2) or null.
-template <int FMT>
-__global__ __launch_bounds__(256) void dtwpq_scan_kernel(const bf16_t* __restrict__ q, const float* __restrict__ qsq,
-                                                         const int32_t* __restrict__ meta, const int32_t* __restrict__ slot_phrase,
-                                                         const int32_t* __restrict__ block_rows, int P, int ph,
-                                                         const uint8_t* __restrict__ codes, const uint8_t* __restrict__ bad,
-                                                         const bf16_t* __restrict__ cb16, int N, int D, int M,
-                                                         const float* __restrict__ cn, int m, const int32_t* __restrict__ seqid,
-                                                         const int32_t* __restrict__ cuts, const int32_t* __restrict__ pgrp,
-                                                         const int32_t* __restrict__ sgrp, int C, float* __restrict__ ps,
-                                                         int32_t* __restrict__ pi) {
+// dtw16_scan_kernel's arguments with the database rows given by db; built from dtw_tile.h's pieces.  256 threads.
+template <int FMT, class Db>
+__device__ __forceinline__ void dt16_scan_body(const bf16_t* __restrict__ q, const float* __restrict__ qsq, const int32_t* __restrict__ meta,
+                                               const int32_t* __restrict__ slot_phrase, const int32_t* __restrict__ block_rows, int P, int ph,
+                                               const Db db, int N, int D, const float* __restrict__ cn, int m,
+                                               const int32_t* __restrict__ seqid, const int32_t* __restrict__ cuts,
+                                               const int32_t* __restrict__ pgrp, const int32_t* __restrict__ sgrp, int C,
+                                               float* __restrict__ ps, int32_t* __restrict__ pi) {
     extern __shared__ __attribute__((aligned(16))) float dt_smem[];
     bf16_t* xs = (bf16_t*)dt_smem;                         // staging of the query rows [128][K16_LD]
-    bf16_t* cs = xs + KN_BM * K16_LD;                      // staging of the decoded database rows
-    uint8_t* cds = (uint8_t*)dt_smem + DPQ_CODE_OFF;       // [128][M] the tile's code bytes, in the cost tile behind the staging
-    float* dm = dt_smem;                                   // [128][DT_LD] local costs of the tile, aliasing the staging and the codes
-    float* cns = dt_smem + KN_BM * DT_LD;
-    int* sq = (int*)(cns + KN_BN);                         // [130] sequence of columns n0 - 1 .. n0 + 128 (-1 outside the cut)
-    int* sgs = sq + 132;                                   // [128] group of each column's sequence
-    float* ls = (float*)(sgs + KN_BN);                     // [ph][m] sorted coarse costs
-    int* li = (int*)(ls + ph * m);                         // [ph][m] their sequences
+    bf16_t* cs = xs + KN_BM * K16_LD;                      // staging of the database rows
+    uint8_t* cds = (uint8_t*)dt_smem + DPQ_CODE_OFF;       // what Db::stage keeps of the tile, in the cost tile behind the staging
+    const DtLds<false> L(dt_smem, ph, m);
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const int wm = wave >> 1, wn = wave & 1;
     const int b = blockIdx.x, cut = blockIdx.y;
@@ -66,10 +77,9 @@ __global__ __launch_bounds__(256) void dtwpq_scan_kernel(const bf16_t* __restric
     rlo = rlo < 0 ? 0 : rlo; rhi = rhi > N ? N : rhi;
     const int nrow = block_rows[b];
     const int tiles = rhi > rlo ? (rhi - rlo + KN_BN - 1) / KN_BN : 0;
-    for (int e = tid; e < ph * m; e += 256) { ls[e] = INFINITY; li[e] = INT_MAX; }
+    L.clear(tid, ph, m);
     // staging: thread -> operand row tid >> 1, halves [16 (tid & 1), 16 (tid & 1) + 16) of the K step, as knn16_scan_kernel
     const int sr = tid >> 1, sh = (tid & 1) * 16;
-    const int dsub = D / M;
     const bf16_t* qrow = q + ((size_t)b * KN_BM + sr) * D;
     bf16_t* xdst = xs + sr * K16_LD + sh;
     bf16_t* cdst = cs + sr * K16_LD + sh;
@@ -82,17 +92,8 @@ __global__ __launch_bounds__(256) void dtwpq_scan_kernel(const bf16_t* __restric
         live[fm] = wm * 64 + fm * 32 < nrow;
         if (qsq) qn[fm] = qsq[(size_t)b * KN_BM + wm * 64 + fm * 32 + frow];
     }
-    // the DP's lane state: waves 0 and 1 own packed rows wave * 64 + lane
-    const int drow = (wave & 1) * 64 + lane;
-    const int mt = wave < 2 ? meta[(size_t)b * KN_BM + drow] : -1;
-    const int pi_ = mt & 127, lastrow = (mt >> 7) & 1, slot = (mt >> 8) & 255;
-    const bool valid = mt >= 0 && slot < ph;
-    int maxi = valid ? pi_ : -1;
-#pragma unroll
-    for (int o = 32; o; o >>= 1) { const int v = __shfl_xor(maxi, o); maxi = v > maxi ? v : maxi; }
-    int pg = 0;
-    if (pgrp && valid && lastrow) { const int pid = slot_phrase[(size_t)b * KN_BM + slot]; pg = pid >= 0 && pid < P ? pgrp[pid] : 0; }
-    float a_cur = INFINITY, a_prev = INFINITY, bc = INFINITY;      // A[i][last column done], A[i][the one before], best of the sequence
+    const DtRow row(meta, slot_phrase, pgrp, b, P, ph, wave, lane);
+    DtLane st;
 
     f32x16_t acc[2][2];
     uint4 xa, xb, ca, cb;
@@ -100,11 +101,8 @@ __global__ __launch_bounds__(256) void dtwpq_scan_kernel(const bf16_t* __restric
         const int tile = t / ksteps, ks = t % ksteps, k0 = ks * K16_BK;
         int cr = rlo + tile * KN_BN + sr; cr = cr < rhi ? cr : rhi - 1;
         const bool in = k0 + sh < D;                       // D % 16 == 0: a last K step of 16 is completed with zeros on both sides
-        const int kc = in ? sh + k0 : 0;                   // the loads stay inside the rows and the codebooks either way
-        const int mm = kc / dsub, o = kc - mm * dsub;      // (D / M) % 16 == 0: the 16 halves lie in one sub-space
-        // a tile's first K step is fetched before its code bytes are in LDS (under the previous tile's DP): from global memory
-        const int code = ks == 0 ? codes[(size_t)cr * M + mm] : cds[sr * M + mm];
-        const bf16_t* crow = cb16 + ((size_t)(mm * DPQ_KSUB + code) * dsub + o);
+        const int kc = in ? sh + k0 : 0;                   // the loads stay inside the rows (and the codebooks) either way
+        const bf16_t* crow = db.halves(cr, kc, ks, sr, cds);
         const uint4 z = make_uint4(0, 0, 0, 0);
         xa = *(const uint4*)(qrow + kc); xb = *(const uint4*)(qrow + kc + 8);
         ca = *(const uint4*)crow; cb = *(const uint4*)(crow + 8);
@@ -118,106 +116,37 @@ __global__ __launch_bounds__(256) void dtwpq_scan_kernel(const bf16_t* __restric
         *(uint4*)xdst = xa; *(uint4*)(xdst + 8) = xb;
         *(uint4*)cdst = ca; *(uint4*)(cdst + 8) = cb;
         if (ks == 0) {
-            if (tid < KN_BN) {
-                const int j = n0 + tid;
-                const float c = (cn && j < rhi) ? cn[j] : 0.f;
-                cns[tid] = (bad && j < rhi && bad[j]) ? NAN : c;
-                sgs[tid] = (sgrp && j < rhi) ? sgrp[seqid[j]] : 0;
-            }
-            if (tid < KN_BN + 2) {
-                const int j = n0 - 1 + tid;
-                sq[tid] = (j >= rlo && j < rhi) ? seqid[j] : -1;
-            }
-            if (ksteps > 1) {                              // the two threads of a staging row copy its bytes; a row past the cut
-                int cr = n0 + sr; cr = cr < rhi ? cr : rhi - 1;            // repeats the cut's last row, as the fetch clamps it
-                for (int mm = tid & 1; mm < M; mm += 2) cds[sr * M + mm] = codes[(size_t)cr * M + mm];
-            }
+            dt_tile_meta(L, tid, n0, rlo, rhi, cn, seqid, sgrp, [&](int j) { return db.masked(j); });
+            if (ksteps > 1) db.stage(cds, n0, rhi, tid);
         }
         __syncthreads();
         if (t + 1 < T) fetch(t + 1);
         k16_mma<FMT>(xs, cs, wm, wn, frow, fh, acc, live[0], live[1]);
         if (ks != ksteps - 1) continue;
-        // epilogue: lane holds phrase row wm*64 + fm*32 + frow against columns wn*64 + fn*32 + 8g + 4fh + e.  t = fmaf(-2, dot16, c_j);
-        // d~ = max(0, ||q||^2 + t) (L2) or max(0, 1 - (-t / 2)) (cosine), dtw16_scan_kernel's expressions; a NaN d~ counts as +inf.
         __syncthreads();                                   // every wave is past its fragment reads: the cost tile aliases the staging
-#pragma unroll
-        for (int fm = 0; fm < 2; ++fm) {
-            if (!live[fm]) continue;
-            const int rl = wm * 64 + fm * 32 + frow;
-#pragma unroll
-            for (int fn = 0; fn < 2; ++fn)
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    float d[4];
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        const int cl = wn * 64 + fn * 32 + 8 * g + 4 * fh + e;
-                        const float s = fmaf(-2.0f, acc[fm][fn][4 * g + e], cns[cl]);
-                        const float v = qsq ? qn[fm] + s : 1.0f - (0.f - 0.5f * s);
-                        d[e] = v != v ? INFINITY : fmaxf(0.f, v);
-                    }
-                    *(float4*)(dm + rl * DT_LD + wn * 64 + fn * 32 + 8 * g + 4 * fh) = make_float4(d[0], d[1], d[2], d[3]);
-                }
-        }
+        dt_cost_tile(L.dm, L.cns, acc, qsq != nullptr, qn, live, wm, wn, frow, fh);
         __syncthreads();
-        if (wave >= 2 || maxi < 0) continue;               // wave-uniform
-        const int ncol = rhi - n0 < KN_BN ? rhi - n0 : KN_BN;
-        const float* dr = dm + drow * DT_LD;
-        for (int st = 0; st < ncol + maxi; ++st) {
-            const float u_cur = __shfl_up(a_cur, 1), u_prev = __shfl_up(a_prev, 1);
-            const int j = st - pi_;
-            bool fin = false;
-            int fseq = 0;
-            if (valid && j >= 0 && j < ncol) {
-                const float d = dr[j];
-                const int sj = sq[j + 1];
-                const bool isstart = sq[j] != sj;
-                float A;
-                if (pi_ == 0) A = d;
-                else {
-                    float best = isstart ? INFINITY : u_prev;          // (i-1, j-1), then (i-1, j), then (i, j-1): the first smallest
-                    if (u_cur < best) best = u_cur;
-                    const float left = isstart ? INFINITY : a_cur;
-                    if (left < best) best = left;
-                    A = d + best;
-                }
-                a_prev = a_cur; a_cur = A;
-                if (lastrow) {
-                    if (isstart) bc = INFINITY;
-                    if (A < bc) bc = A;
-                    if (sq[j + 2] != sj && bc < INFINITY && !(sgrp && sgs[j] == pg)) {
-                        fseq = sj;
-                        fin = kn_better(bc, sj, ls[slot * m + m - 1], li[slot * m + m - 1]);
-                    }
-                }
-            }
-            uint64_t fb = __ballot(fin);
-            while (fb) {
-                const int c = __ffsll((unsigned long long)fb) - 1;
-                fb &= fb - 1;
-                const float v = __shfl(bc, c);
-                const int vs = __shfl(fseq, c), sl = __shfl(slot, c);
-                kn_insert(ls + sl * m, li + sl * m, m, lane, v, vs);
-            }
-        }
+        if (wave >= 2 || row.maxi < 0) continue;           // wave-uniform
+        dt_wavefront(L, row, st, lane, n0, rhi - n0 < KN_BN ? rhi - n0 : KN_BN, sgrp != nullptr, m);
     }
     __syncthreads();
-    for (int sl = wave; sl < ph; sl += 4) {
-        const int pid = slot_phrase[(size_t)b * KN_BM + sl];
-        if (pid < 0 || pid >= P) break;
-        const size_t o = ((size_t)pid * C + cut) * m;
-        for (int e = lane; e < m; e += 64) { ps[o + e] = ls[sl * m + e]; pi[o + e] = li[sl * m + e]; }
-    }
+    dt_write_lists(L, slot_phrase, b, P, ph, C, cut, m, wave, lane, ps, pi, nullptr);
 }
 
-// dtw16_cand_kernel's conversion, restated: the merged lists as candidates, the (+inf, INT_MAX) fillers become (+inf, -1)
-__global__ __launch_bounds__(256) void dtwpq_cand_kernel(const float* __restrict__ ls, const int32_t* __restrict__ li, int64_t tot,
-                                                         int32_t* __restrict__ cand, float* __restrict__ coarse) {
-    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (e >= tot) return;
-    const int j = li[e];
-    cand[e] = j == INT_MAX ? -1 : j;
-    coarse[e] = j == INT_MAX ? INFINITY : ls[e];
+// As dtw16_scan_kernel, the database given as codes [N][M] (bad [N] or null: 1 = masked row) and cb16 [M][256][D / M], the 16-bit
+// codebooks; cn: the fp32 ||decode(code_j)||^2 (L2) or null.
+template <int FMT>
+__global__ __launch_bounds__(256) void dtwpq_scan_kernel(const bf16_t* __restrict__ q, const float* __restrict__ qsq,
+                                                         const int32_t* __restrict__ meta, const int32_t* __restrict__ slot_phrase,
+                                                         const int32_t* __restrict__ block_rows, int P, int ph,
+                                                         const uint8_t* __restrict__ codes, const uint8_t* __restrict__ bad,
+                                                         const bf16_t* __restrict__ cb16, int N, int D, int M,
+                                                         const float* __restrict__ cn, int m, const int32_t* __restrict__ seqid,
+                                                         const int32_t* __restrict__ cuts, const int32_t* __restrict__ pgrp,
+                                                         const int32_t* __restrict__ sgrp, int C, float* __restrict__ ps,
+                                                         int32_t* __restrict__ pi) {
+    dt16_scan_body<FMT>(q, qsq, meta, slot_phrase, block_rows, P, ph, Dt16Codes{codes, bad, cb16, M, D / M}, N, D, cn, m, seqid, cuts, pgrp,
+                        sgrp, C, ps, pi);
 }
 
 extern "C" int sylber_dtwpq_scan(const void* q16_dev, int32_t n_blocks, const int32_t* row_meta_dev, const int32_t* slot_phrase_dev,
@@ -230,42 +159,17 @@ extern "C" int sylber_dtwpq_scan(const void* q16_dev, int32_t n_blocks, const in
     hipStream_t s = (hipStream_t)stream;
     if (!q16_dev || !row_meta_dev || !slot_phrase_dev || !block_rows_dev || !codes_dev || !codebooks16_dev || !seq_id_dev || !cut_rows_dev ||
         !cand_dev || !coarse_dev || !workspace_dev) { syl_set_error(what, "null argument"); return 1; }
-    if (n_blocks < 1 || n_phrases < 1 || N < 1 || D < 16 || D % 16) { syl_set_error(what, "need n_blocks, n_phrases, N >= 1 and D a multiple of 16"); return 1; }
-    if (M < 1 || M > DPQ_MAX_M || D % M || (D / M) % 16) { syl_set_error(what, "need 1 <= M <= 64, D % M == 0 and D / M a multiple of 16"); return 1; }
-    if (m < 1 || m > KN_KMAX) { syl_set_error(what, "need 1 <= m <= 128"); return 1; }
-    if (block_phrases < 1 || block_phrases > dt_block_phrases(m, 0)) { syl_set_error(what, "block_phrases exceeds what sylber_dtw_plan allows for this m"); return 1; }
-    if (cuts < 1 || cuts > 65535) { syl_set_error(what, "need 1 <= cuts <= 65535"); return 1; }
-    if (metric != SYLBER_KNN_L2 && metric != SYLBER_KNN_IP) { syl_set_error(what, "unknown metric"); return 1; }
-    if (storage != SYLBER_KNN16_FP16 && storage != SYLBER_KNN16_BF16) { syl_set_error(what, "unknown storage"); return 1; }
-    if (metric == SYLBER_KNN_L2 && (!recon_norm_dev || !q_norm_dev)) { syl_set_error(what, "the L2 metric needs recon_norm_dev and q_norm_dev"); return 1; }
-    if (!phrase_group_dev != !seq_group_dev) { syl_set_error(what, "phrase_group_dev and seq_group_dev go together"); return 1; }
-    if ((int64_t)n_phrases * cuts * m > INT32_MAX / 2) { syl_set_error(what, "n_phrases x cuts x m is too large: use smaller phrase chunks"); return 1; }
-    char* w = (char*)workspace_dev;
-    KnPartials p = kn_partials_carve(w, n_phrases, cuts, m);
-    const size_t lds = dpq_lds_bytes(block_phrases, m);
-    const int max_lds = (int)((size_t)DT_FIXED * 4 + DT_LIST_BYTES / 2);
-    const bf16_t* q16 = (const bf16_t*)q16_dev;
-    const bf16_t* cb16 = (const bf16_t*)codebooks16_dev;
-    const float* qn = metric == SYLBER_KNN_L2 ? q_norm_dev : nullptr;
-    const float* cn = metric == SYLBER_KNN_L2 ? recon_norm_dev : nullptr;
-    const dim3 grid((unsigned)n_blocks, (unsigned)cuts);
-    if (storage == SYLBER_KNN16_FP16) {
+    const char* db_error = (M < 1 || M > DPQ_MAX_M || D % M || (D / M) % 16) ? "need 1 <= M <= 64, D % M == 0 and D / M a multiple of 16" : nullptr;
+    return dt16_scan_host(what, db_error, "the L2 metric needs recon_norm_dev and q_norm_dev", n_blocks, n_phrases, block_phrases, N, D,
+                          recon_norm_dev, q_norm_dev, metric, storage, m, cuts, phrase_group_dev, seq_group_dev, cand_dev, coarse_dev,
+                          workspace_dev, s,
+                          [&](auto fmt, dim3 grid, size_t lds, int max_lds, const float* qn, const float* cn, float* ps, int32_t* pi) {
+        constexpr int FMT = decltype(fmt)::value;
         static PerDeviceOnce once;
-        if (once.need()) HIP_TRY(hipFuncSetAttribute((const void*)dtwpq_scan_kernel<FMT_F16>, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds));
-        hipLaunchKernelGGL(dtwpq_scan_kernel<FMT_F16>, grid, dim3(256), lds, s, q16, qn, row_meta_dev, slot_phrase_dev, block_rows_dev, n_phrases,
-                           block_phrases, codes_dev, bad_dev, cb16, N, D, M, cn, m, seq_id_dev, cut_rows_dev, phrase_group_dev, seq_group_dev,
-                           cuts, p.s0, p.i0);
-    } else {
-        static PerDeviceOnce once;
-        if (once.need()) HIP_TRY(hipFuncSetAttribute((const void*)dtwpq_scan_kernel<FMT_BF16>, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds));
-        hipLaunchKernelGGL(dtwpq_scan_kernel<FMT_BF16>, grid, dim3(256), lds, s, q16, qn, row_meta_dev, slot_phrase_dev, block_rows_dev, n_phrases,
-                           block_phrases, codes_dev, bad_dev, cb16, N, D, M, cn, m, seq_id_dev, cut_rows_dev, phrase_group_dev, seq_group_dev,
-                           cuts, p.s0, p.i0);
-    }
-    HIP_TRY(hipGetLastError());
-    if (kn_merge_lists(p, n_phrases, cuts, m, s)) return 1;
-    const int64_t tot = (int64_t)n_phrases * m;
-    hipLaunchKernelGGL(dtwpq_cand_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, p.s0, p.i0, tot, cand_dev, coarse_dev);
-    HIP_TRY(hipGetLastError());
-    return 0;
+        if (once.need()) HIP_TRY(hipFuncSetAttribute((const void*)dtwpq_scan_kernel<FMT>, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds));
+        hipLaunchKernelGGL(dtwpq_scan_kernel<FMT>, grid, dim3(256), lds, s, (const bf16_t*)q16_dev, qn, row_meta_dev, slot_phrase_dev,
+                           block_rows_dev, n_phrases, block_phrases, codes_dev, bad_dev, (const bf16_t*)codebooks16_dev, N, D, M, cn, m,
+                           seq_id_dev, cut_rows_dev, phrase_group_dev, seq_group_dev, cuts, ps, pi);
+        return 0;
+    });
 }

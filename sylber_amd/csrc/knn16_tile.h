@@ -1,7 +1,8 @@
-// The 16-bit contraction that knn16.hip (knn16_scan_kernel) and dtw16.hip (dtw16_scan_kernel) share: knn_tile.h's tile (128 query rows
-// x 128 database rows, 2 x 2 waves of 2 x 2 fragments of 32 x 32) on v_mfma_f32_32x32x16_{f16,bf16}, whose C layout is the fp32
-// MFMA's.  One definition of the operand roles and of the K order keeps a coarse score's bits the same wherever it is computed: an
-// output element is one MFMA chain over K in ascending 16-wide steps.
+// The 16-bit contraction that knn16.hip (knn16_scan_kernel), dtw16.hip (dtw16_scan_kernel) and dtwpq.hip (dtwpq_scan_kernel)
+// share: knn_tile.h's tile (128 query rows x 128 database rows, 2 x 2 waves of 2 x 2 fragments of
+// 32 x 32) on v_mfma_f32_32x32x16_{f16,bf16}, whose C layout is the fp32 MFMA's.  One definition of the operand roles and of the
+// K order keeps a coarse score's bits the same wherever it is computed: an output element is one MFMA chain over K in ascending
+// 16-wide steps.
 #pragma once
 #include "knn_tile.h"
 

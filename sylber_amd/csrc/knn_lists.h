@@ -1,40 +1,42 @@
 // The list kernels that knn.hip (sylber_knn_search, sylber_ivf_search), knn16.hip (sylber_knn16_scan), pq.hip (sylber_pq_scan,
-// sylber_ivfpq_scan) and dtw16.hip (sylber_dtw16_scan) share: the pairwise merge of sorted partial lists and the reported values.  They are static: each translation
-// unit that launches them carries its own copy.  Below knn_merge_kernel is the host side of the merge, written once for those
-// entry points: where the partial lists lie in a workspace (KnPartials, kn_partials_bytes, kn_partials_carve) and the merge rounds
-// (kn_merge_lists).  dtw.hip merges lists with a payload and keeps its own.
+// sylber_ivfpq_scan), dtw16_scan.h (sylber_dtw16_scan, sylber_dtwpq_scan) and dtw.hip (sylber_dtw_search) share: the pairwise merge
+// of sorted partial lists and the reported values.  They are static: each translation unit that launches them carries its own
+// copy.  Below knn_merge_kernel is the host side of the merge, written once for the entry points whose lists are (score, id): where
+// the partial lists lie in a workspace (KnPartials, kn_partials_bytes, kn_partials_carve) and the merge rounds (kn_merge_lists).
+// dtw.hip's lists carry a span: it launches knn_merge_kernel<true> from its own rounds and reports with its own dtw_finish_kernel.
 #pragma once
 #include "knn_tile.h"
 
 // one wave per (row, pair): lists 2p and 2p + 1 of row r (m lists of k per row in src) -> list p of row r (ceil(m / 2) per row in
 // dst).  An element's rank in the merged list is its position plus the number of entries of the other list before it (A's elements go
-// before B's equal ones: only the (+inf, INT_MAX) fillers can be equal), so every output slot < k is written exactly once.
-static __global__ __launch_bounds__(64) void knn_merge_kernel(const float* __restrict__ ss, const int32_t* __restrict__ si, int m, int k,
-                                                       float* __restrict__ ds, int32_t* __restrict__ di) {
+// before B's equal ones: only the (+inf, INT_MAX) fillers can be equal), so every output slot < k is written exactly once.  With
+// PAYLOAD every entry carries an int2 (sp -> dp: dtw.hip's spans), as kn_insert_t's lists do; without, sp and dp are null.
+template <bool PAYLOAD>
+static __global__ __launch_bounds__(64) void knn_merge_kernel(const float* __restrict__ ss, const int32_t* __restrict__ si,
+                                                              const int2* __restrict__ sp, int m, int k, float* __restrict__ ds,
+                                                              int32_t* __restrict__ di, int2* __restrict__ dp) {
     const int r = blockIdx.x, p = blockIdx.y, lane = threadIdx.x;
     const int mo = (m + 1) / 2;
-    const float* as = ss + ((size_t)r * m + 2 * p) * k;
-    const int32_t* ai = si + ((size_t)r * m + 2 * p) * k;
-    float* os = ds + ((size_t)r * mo + p) * k;
-    int32_t* oi = di + ((size_t)r * mo + p) * k;
+    const size_t ao = ((size_t)r * m + 2 * p) * k, oo = ((size_t)r * mo + p) * k;
+    const float* as = ss + ao; const int32_t* ai = si + ao; const int2* ap = PAYLOAD ? sp + ao : nullptr;
+    float* os = ds + oo; int32_t* oi = di + oo; int2* op = PAYLOAD ? dp + oo : nullptr;
     if (2 * p + 1 >= m) {
-        for (int e = lane; e < k; e += 64) { os[e] = as[e]; oi[e] = ai[e]; }
+        for (int e = lane; e < k; e += 64) { os[e] = as[e]; oi[e] = ai[e]; if (PAYLOAD) op[e] = ap[e]; }
         return;
     }
-    const float* bs = as + k;
-    const int32_t* bi = ai + k;
+    const float* bs = as + k; const int32_t* bi = ai + k; const int2* bp = PAYLOAD ? ap + k : nullptr;
     for (int e = lane; e < k; e += 64) {
         {   // A[e]: + #{B strictly better}
             const float v = as[e]; const int j = ai[e];
             int lo = 0, hi = k;
             while (lo < hi) { const int mid = (lo + hi) >> 1; if (kn_better(bs[mid], bi[mid], v, j)) lo = mid + 1; else hi = mid; }
-            if (e + lo < k) { os[e + lo] = v; oi[e + lo] = j; }
+            if (e + lo < k) { os[e + lo] = v; oi[e + lo] = j; if (PAYLOAD) op[e + lo] = ap[e]; }
         }
         {   // B[e]: + #{A not worse}
             const float v = bs[e]; const int j = bi[e];
             int lo = 0, hi = k;
             while (lo < hi) { const int mid = (lo + hi) >> 1; if (!kn_better(v, j, as[mid], ai[mid])) lo = mid + 1; else hi = mid; }
-            if (e + lo < k) { os[e + lo] = v; oi[e + lo] = j; }
+            if (e + lo < k) { os[e + lo] = v; oi[e + lo] = j; if (PAYLOAD) op[e + lo] = bp[e]; }
         }
     }
 }
@@ -60,7 +62,8 @@ static inline KnPartials kn_partials_carve(char*& w, int64_t n, int64_t L, int64
 // the ceil(log2 L) merge rounds of the L lists per row in (p.s0, p.i0); on return (p.s0, p.i0) is the one merged list per row [n][k]
 static inline int kn_merge_lists(KnPartials& p, int n, int L, int k, hipStream_t s) {
     for (int m = L; m > 1; m = (m + 1) / 2) {
-        hipLaunchKernelGGL(knn_merge_kernel, dim3((unsigned)n, (unsigned)((m + 1) / 2)), dim3(64), 0, s, p.s0, p.i0, m, k, p.s1, p.i1);
+        hipLaunchKernelGGL(knn_merge_kernel<false>, dim3((unsigned)n, (unsigned)((m + 1) / 2)), dim3(64), 0, s, p.s0, p.i0, (const int2*)nullptr, m, k,
+                           p.s1, p.i1, (int2*)nullptr);
         HIP_TRY(hipGetLastError());
         float* ts = p.s0; p.s0 = p.s1; p.s1 = ts;
         int32_t* ti = p.i0; p.i0 = p.i1; p.i1 = ti;

@@ -1,4 +1,5 @@
-// The pieces that knn.hip (knn_search_kernel, ivf_scan_kernel) and dtw.hip (dtw_search_kernel) share: the geometry and the K step of
+// The pieces that knn.hip (knn_search_kernel, ivf_scan_kernel) and dtw.hip (dtw_search_kernel; the list insertion also through
+// dtw_tile.h's wavefront, which dtwpq_scan_kernel runs too) share: the geometry and the K step of
 // the exact-fp32 contraction of km_fused_assign_kernel (kmeans.hip), the (score, index) order, and the insertion into a sorted
 // top-k list held in LDS.  One definition of the operand roles and the k-pair order is what keeps a score's bits the same wherever
 // it is computed.

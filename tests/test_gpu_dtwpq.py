@@ -301,7 +301,8 @@ def test_lazy_state_counts_in_nbytes():
 EDGE_LENS = [127, 1, 128, 129, 300, 7, 64, 33]                # 127 + 1 and + 128 end on 128-row tile edges; 300 crosses two
 EDGES = [(48, 3, EDGE_LENS),                                  # D % 32 == 16: the last K step is half empty
          (64, 1, EDGE_LENS),                                  # dsub = 64: a sub-space crosses K steps
-         (32, 2, [100, 27]), (32, 2, [100, 28]), (32, 2, [100, 29]), (32, 2, [128, 129])]          # N = 127, 128, 129, 257
+         (32, 2, [100, 27]), (32, 2, [100, 28]), (32, 2, [100, 29]), (32, 2, [128, 129]),          # N = 127, 128, 129, 257
+         (16, 1, [100, 28])]                                  # D = 16: one K step, half empty; every code byte comes from global memory
 
 
 @pytest.mark.parametrize("D,M,lens", EDGES)

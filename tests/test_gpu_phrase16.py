@@ -146,26 +146,37 @@ def test_invariance_is_bitwise():
         _assert_equal(two.search_phrases_refined(ph, k, refine, storage, return_candidates=True), base, "two adds")
 
 
-@pytest.mark.parametrize("metric,storage", COMBOS)
-def test_tile_and_chunk_edges(metric, storage):
+def _check_tile_edges(metric, storage, D, lens, spots):
+    """m >= S: the two-stage call returns search_phrases' results; a lone 1-row phrase's candidates are every sequence"""
     from sylber_amd import SyllableIndex
-    from sylber_amd.search import RERANK_CHUNK
     rng = np.random.default_rng(5)
-    D = 32
-    lens = [127, 1, 128, 129, 300, 7, 64, 33]                # 127 + 1 and + 128 end on 128-row tile edges
     offsets = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
-    assert offsets[2] == 128 and offsets[3] == 256 and max(lens) > RERANK_CHUNK and RERANK_CHUNK + 1 in lens
     N, S = int(offsets[-1]), len(lens)
     x = rng.standard_normal((N, D)).astype(np.float32)
     idx = SyllableIndex(x, metric=metric, groups=_groups_of(offsets), device=DEV)
-    ph = [(x[a:a + m] + 0.2 * rng.standard_normal((m, D))).astype(np.float32)
-          for m, a in ((40, 100), (30, 250), (1, 127), (64, 300), (20, 380), (2, 255), (63, 500))]     # 40 + 30 > 64: both halves of block 0
+    ph = [(x[a:a + m] + 0.2 * rng.standard_normal((m, D))).astype(np.float32) for m, a in spots]
+    what = "D = %d, N = %d" % (D, N)
     for k, refine in ((S, 1), (2, 4)):                       # m = 8 >= S
-        _assert_equal(idx.search_phrases_refined(ph, k, refine, storage), idx.search_phrases(ph, k))
+        _assert_equal(idx.search_phrases_refined(ph, k, refine, storage), idx.search_phrases(ph, k), what)
     one = [ph[2]]                                            # a lone 1-row phrase
     got = idx.search_phrases_refined(one, S, 1, storage, return_candidates=True)
-    _assert_equal(got[:3], idx.search_phrases(one, S))
-    assert sorted(_np(got[3])[0].tolist()) == list(range(S))
+    _assert_equal(got[:3], idx.search_phrases(one, S), what)
+    assert sorted(_np(got[3])[0].tolist()) == list(range(S)), what
+
+
+@pytest.mark.parametrize("metric,storage", COMBOS)
+def test_tile_and_chunk_edges(metric, storage):
+    from sylber_amd.search import RERANK_CHUNK
+    lens = [127, 1, 128, 129, 300, 7, 64, 33]                # 127 + 1 and + 128 end on 128-row tile edges
+    offsets = np.cumsum(lens)
+    assert offsets[1] == 128 and offsets[2] == 256 and max(lens) > RERANK_CHUNK and RERANK_CHUNK + 1 in lens
+    _check_tile_edges(metric, storage, 32, lens,
+                      ((40, 100), (30, 250), (1, 127), (64, 300), (20, 380), (2, 255), (63, 500)))     # 40 + 30 > 64: both halves of block 0
+    # D = 16: one K step whose upper half is zero-filled; D = 48: the last of two is.  N = 127, 128, 129: a tile short of one row,
+    # full, and a second tile of one row
+    for D in (16, 48):
+        for last in (27, 28, 29):
+            _check_tile_edges(metric, storage, D, [100, last], ((40, 60), (30, 10), (1, 126), (64, 20), (20, 3), (2, 90), (63, 0)))
 
 
 def test_admissibility_and_padding():
