@@ -454,6 +454,28 @@ int sylber_dtwpq_scan(const void* q16_dev, int32_t n_blocks, const int32_t* row_
                       const int32_t* cut_rows_dev, int32_t cuts, const int32_t* phrase_group_dev, const int32_t* seq_group_dev,
                       int32_t* cand_dev, float* coarse_dev, void* workspace_dev, void* stream);
 
+/* Phrase search through the inverted file, stage 1b (sylber_amd/search.py: SyllableIndex.search_phrases_seeded): per-row
+ * neighbours ("seeds") vote for candidate sequences, which sylber_dtw_rerank then scores exactly.  seed_score_dev fp32 and
+ * seed_id_dev int64, [R, seeds] each (1 <= seeds <= 128): what a search reports under `metric` for each of the R phrase rows,
+ * concatenated in phrase order (NOT the packed blocks of sylber_dtw_plan); phrase_row_dev / phrase_len_dev [n_phrases]: first row and
+ * length (1 .. 64) of each phrase; seq_offsets_dev [n_seq + 1]; the two group arrays both or neither.
+ *   local cost of a seed: d = score (L2), d = max(0, 1 - score) (IP): the d of sylber_dtw_search, bit for bit.  A seed is ignored
+ *   when its id is -1 (or outside [0, seq_offsets[n_seq])), its score is NaN or its d is +inf.
+ *   Per phrase p with rows i = 0 .. m_p - 1: seq(j) = the sequence holding row j; floor_i = the largest d among row i's valid seeds
+ *   (0 without one); best_i(s) = the smallest d among row i's valid seeds in sequence s (floor_i without one); s is SEEN when some
+ *   row has a valid seed in it, and ADMISSIBLE unless seq_group[s] == phrase_group[p];
+ *   bound(p, s) = (((0 + best_0) + best_1) + ... + best_{m_p - 1}), fp32 additions in ascending i.
+ * cand_dev int32 [n_phrases, m] (1 <= m <= 128): the m smallest admissible seen sequences of finite bound under (bound, sequence
+ * number), padded with -1; bound_dev fp32 [n_phrases, m]: their bounds, padded with +inf.  Every operation is an fp32 min, max or
+ * add in a fixed order, so the outputs are unique: independent of the order of the seeds within a row, of duplicates, of how phrases
+ * are launched and of what the outputs held.  When the seeds of every row are its `seeds` nearest rows (all of them: no exclusion
+ * beyond whole sequences), bound(p, s) <= the sylber_dtw_search cost of (p, s), exactly.  One workgroup per phrase, everything in
+ * LDS; no workspace.  Bad arguments return 1 with sylber_last_error before any device call. */
+int sylber_phrase_vote(const float* seed_score_dev, const int64_t* seed_id_dev, int32_t seeds, const int32_t* phrase_row_dev,
+                       const int32_t* phrase_len_dev, int32_t n_phrases, const int32_t* seq_offsets_dev, int32_t n_seq, int32_t metric,
+                       const int32_t* phrase_group_dev, const int32_t* seq_group_dev, int32_t m, int32_t* cand_dev, float* bound_dev,
+                       void* stream);
+
 /* Learned quantizer (sylber/model/quantizer.py:6-77, 182-257: `load_quantizer` / `Quantizer`), eval, exact fp32.  The host
  * (sylber_amd/quantizer.py) chains: sylber_lq_norm (input norm / padding) -> sylber_ffenc -> sylber_lq_norm (output norm, blank rows)
  * -> sylber_rvq_assign for the art window and the pitch window -> sylber_lq_norm of the quantized rows.  All data pointers are device

@@ -20,6 +20,7 @@ DEFAULT_QUERY_CHUNK = 8192
 MAX_NPROBE = 128
 MAX_CANDIDATES = 128            # k * refine of a two-stage search: the LDS top-list of the scan beside a 128-row query block
 MAX_PHRASE_ROWS = 64            # DT_MAX_M of csrc/dtw.hip: one wave holds a phrase
+MAX_SEEDS = 128                 # PV_MAX_SEEDS of csrc/phrase_vote.hip: the seeds per phrase row of a seeded phrase search
 MAX_SEQUENCE_ROWS = 65536       # DT_MAX_SEQ: the DP along one sequence is serial
 DEFAULT_PHRASE_CHUNK = 4096
 STORAGES = {"fp16": (0, torch.float16), "bf16": (1, torch.bfloat16)}     # SYLBER_KNN16_FP16 / _BF16: the 16-bit planes of the two-stage searches

@@ -148,6 +148,8 @@ EXPORTS = {
     "sylber_dtwpq_scan": (c_int, [c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int32,
                                   c_int32, c_int32, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_int32, c_void_p,
                                   c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "sylber_phrase_vote": (c_int, [c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_int32, c_void_p, c_void_p,
+                                   c_int32, c_void_p, c_void_p, c_void_p]),
     "sylber_lq_norm": (c_int, [c_void_p, c_int64, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int64, c_int32, c_void_p, c_int64,
                                c_int32, c_void_p]),
     "sylber_ffenc_workspace_floats": (c_int64, [c_int32, c_int32, POINTER(c_int32)]),

@@ -14,7 +14,9 @@ Contract (tests/knn_ref.py restates it in numpy)::
 ``SyllableIndex.search_phrases`` searches for a *sequence* of syllables: subsequence DTW of each phrase against every sequence (by
 default: clip) of the index, in the epilogue of the same contraction (csrc/dtw.hip, ``sylber_dtw_search``); its contract is in the
 method's docstring, restated in numpy in tests/dtw_ref.py.  ``SyllableIndex.search_phrases_refined`` is its two-stage form (csrc/dtw16.hip:
-a 16-bit MFMA scan picks candidate sequences, the exact DTW re-ranks them; tests/dtw16_ref.py).
+a 16-bit MFMA scan picks candidate sequences, the exact DTW re-ranks them; tests/dtw16_ref.py).  ``IVFSyllableIndex.search_phrases`` finds the
+candidate sequences without a scan of the corpus: each phrase row's neighbours from the lists vote for them (csrc/phrase_vote.hip;
+``SyllableIndex.search_phrases_seeded`` is the vote and the re-rank on seeds from anywhere; tests/phrase_vote_ref.py).
 
 The rules that every index shares -- argument checks, row preparation, result buffers, provenance, the list layout, the arrays of a
 saved file -- are in _index.py, each once; this file and pq.py hold what differs between the indexes.
@@ -29,7 +31,7 @@ import torch
 
 from . import _lib
 from ._index import MAX_CANDIDATES, MAX_K, MAX_NPROBE  # noqa: F401  (limits of this module's searches, kept importable from here)
-from ._index import DEFAULT_PHRASE_CHUNK, MAX_PHRASE_ROWS, MAX_SEQUENCE_ROWS, STORAGES  # noqa: F401  (likewise, for the phrase searches)
+from ._index import DEFAULT_PHRASE_CHUNK, MAX_PHRASE_ROWS, MAX_SEEDS, MAX_SEQUENCE_ROWS, STORAGES  # noqa: F401  (likewise, for the phrase searches)
 from ._index import (DEFAULT_QUERY_CHUNK, METRICS, _added_rows, _base_arrays, _check_k_refine, _check_nprobe, _check_splits_chunk,
                      _chunked_workspace_bytes, _group_runs, _list_layout, _on_device, _outputs, _pack16, _phrase_args, _phrase_blocks,
                      _phrase_outputs, _PhraseBlocks, _prep, _provenance, _query_groups, _result, _row_norms, _rows, _rows_of_width,
@@ -358,6 +360,79 @@ class SyllableIndex:
                                                  _vp(seqs[p0:p1]), _vp(spans[p0:p1]), _vp(ws), st), "sylber_dtw_rerank")
         return (costs, seqs, spans, cand.to(torch.int64), coarse) if return_candidates else (costs, seqs, spans)
 
+    def search_phrases_seeded(self, phrases, seed_scores, seed_ids, k: int, refine: int = 4, *, lengths=None, groups=None,
+                              exclude_same_group: bool = False, sequences=None, phrase_chunk: int = DEFAULT_PHRASE_CHUNK,
+                              return_candidates: bool = False, _trusted_ids: bool = False):
+        """``search_phrases`` over candidate sequences found from per-row neighbours instead of a scan of the corpus: ``seed_scores``
+        fp32 and ``seed_ids`` int64, ``[R, seeds]`` each (tensors or arrays; ``1 <= seeds <= 128``), are what a ``search`` *reports*
+        for each of the R phrase rows (concatenated in phrase order) under this index's metric -- from ``IVFSyllableIndex.search``,
+        ``search`` itself or anywhere else.  Stage 1 (csrc/phrase_vote.hip, ``sylber_phrase_vote``; tests/phrase_vote_ref.py) lets
+        the seeds vote for ``m = k * refine <= 128`` candidate sequences per phrase; stage 2 is the exact re-rank of
+        ``search_phrases_refined`` -> ``(costs, seqs, spans)`` shaped, typed, ordered, padded and placed exactly as
+        ``search_phrases``'s; with ``return_candidates=True`` also ``cand`` int64 ``[P, m]`` (padded with -1) and ``bound`` fp32
+        ``[P, m]`` (padded with ``+inf``).
+
+        The vote.  Local cost of a seed: ``"l2"``: ``d = score``; ``"cosine"``: ``d = max(0, 1 - score)`` -- bit for bit the ``d`` of
+        ``search_phrases`` for that pair of rows.  A seed is ignored when its id is -1, its score is NaN or its ``d`` is ``+inf``.
+        For phrase p with rows i = 0 .. m_p - 1: ``floor_i`` = the largest ``d`` among row i's valid seeds (0 without one);
+        ``best_i(s)`` = the smallest ``d`` among row i's valid seeds in sequence s (``floor_i`` without one); s is *seen* when some
+        row has a valid seed in it, *admissible* unless, with ``exclude_same_group``, its group is the phrase's;
+        ``bound(p, s) = (((0 + best_0) + best_1) + ... + best_{m_p - 1})`` in fp32, ascending i.  The candidates are the m smallest
+        admissible seen sequences of finite bound under (bound, sequence number).
+
+        So the result is ``search_phrases`` restricted to the candidates: every returned cost and span is a real ``search_phrases``
+        cost and span, bit for bit; the only approximation is which sequences are re-ranked.  When the seeds of every row are its
+        ``seeds`` nearest rows of the whole index, ``bound(p, s) <= cost(p, s)`` exactly (a warping path visits every phrase row; a
+        row that is no seed costs at least the floor; fp32 addition is monotone); when every admissible row is a seed and m is at
+        least the number of admissible sequences, the result *is* ``search_phrases``.  Every operation of the vote is an fp32 min,
+        max or add in a fixed order: nothing returned depends on the order of the seeds within a row, on duplicates or on
+        ``phrase_chunk``.  ``ValueError`` before any launch: ``search_phrases_refined``'s checks, seed tensors of another shape or
+        dtype, an id outside ``[-1, N)``."""
+        k, m = _check_k_refine(k, refine, rerank=True)
+        q, lens, pg, off = self._phrase_args(phrases, lengths, groups, exclude_same_group, sequences, 0, phrase_chunk, 0)
+        P, R = int(lens.size), int(q.shape[0])
+        dev = self.device
+        sc = seed_scores if torch.is_tensor(seed_scores) else torch.from_numpy(np.asarray(seed_scores))
+        si = seed_ids if torch.is_tensor(seed_ids) else torch.from_numpy(np.asarray(seed_ids))
+        if sc.dim() != 2 or si.dim() != 2 or sc.shape != si.shape or sc.shape[0] != R:
+            raise ValueError("seed_scores and seed_ids must both be [%d phrase rows, seeds], got %s and %s" % (R, tuple(sc.shape), tuple(si.shape)))
+        if sc.dtype != torch.float32 or si.dtype != torch.int64:
+            raise ValueError("seed_scores must be float32 and seed_ids int64, got %s and %s" % (sc.dtype, si.dtype))
+        seeds = int(sc.shape[1])
+        if not 1 <= seeds <= MAX_SEEDS:
+            raise ValueError("seeds must be in [1, %d], got %d" % (MAX_SEEDS, seeds))
+        N, S = len(self), off.size - 1
+        sc, si = sc.to(dev).contiguous(), si.to(dev).contiguous()
+        if not _trusted_ids and R and (int(si.min()) < -1 or int(si.max()) >= N):
+            raise ValueError("seed_ids must lie in [-1, %d)" % N)
+        costs, seqs, spans = _phrase_outputs(P, k, dev)
+        cand = torch.empty((P, m), dtype=torch.int32, device=dev)
+        bound = torch.empty((P, m), dtype=torch.float32, device=dev)
+        if P == 0:
+            return (costs, seqs, spans, cand.to(torch.int64), bound) if return_candidates else (costs, seqs, spans)
+        lib = _lib.load()
+        qd = self._prep(q)
+        off_d = _on_device(off, np.int32, dev)
+        seq_grp = self._g.index_select(0, off_d[:-1].to(torch.int64)) if pg is not None else None
+        row_d, len_d = _on_device(np.cumsum(lens) - lens, np.int32, dev), _on_device(lens, np.int32, dev)
+        pg_d = _on_device(pg, np.int32, dev) if pg is not None else None
+        metric = METRICS[self.metric]
+        with torch.cuda.device(dev):
+            st = _stream(dev)
+            for p0 in range(0, P, int(phrase_chunk)):
+                p1 = min(P, p0 + int(phrase_chunk))
+                _lib.check(lib.sylber_phrase_vote(_vp(sc), _vp(si), seeds, _vp(row_d[p0:p1]), _vp(len_d[p0:p1]), p1 - p0, _vp(off_d), S,
+                                                  metric, _vp(pg_d[p0:p1] if pg_d is not None else None), _vp(seq_grp), m,
+                                                  _vp(cand[p0:p1]), _vp(bound[p0:p1]), st), "sylber_phrase_vote")
+                b = self._phrase_blocks(lib, qd, lens, p0, p1, off, m, 0, 0, None)
+                qn = _row_norms(b.qp) if self.metric == "l2" else None
+                ws = torch.empty(int(lib.sylber_dtw16_workspace_bytes(b.Pc, m, 1)), dtype=torch.uint8, device=dev)
+                place_d = _on_device(b.place, np.int32, dev)
+                _lib.check(lib.sylber_dtw_rerank(_vp(b.qp), b.nb, _vp(qn), _vp(place_d), _vp(len_d[p0:p1]), b.Pc, _vp(self._x), N, self.dim,
+                                                 _vp(self._c), metric, _vp(cand[p0:p1]), m, _vp(off_d), S, k, _vp(costs[p0:p1]),
+                                                 _vp(seqs[p0:p1]), _vp(spans[p0:p1]), _vp(ws), st), "sylber_dtw_rerank")
+        return (costs, seqs, spans, cand.to(torch.int64), bound) if return_candidates else (costs, seqs, spans)
+
     # the arguments and the plumbing that every phrase search shares: _index.py holds them, these keep their names
     def _phrase_args(self, phrases, lengths, groups, exclude_same_group, sequences, splits, phrase_chunk, block_phrases):
         """the checks of a phrase search -> ``(phrase rows [sum m, D] as given, lengths int64 [P], the phrases' groups on the host or
@@ -577,6 +652,64 @@ class IVFSyllableIndex:
         self.last_search["pairs"] = pairs_scanned
         self.last_search["fraction"] = pairs_scanned / (float(n) * len(idx))
         return scores, ids
+
+    # ---- phrase search --------------------------------------------------------------------------------------------------------------
+    def sequence_offsets(self) -> np.ndarray:
+        """int64 ``[S + 1]``: the default sequences of ``search_phrases``, those of ``ivf.index`` (rows in id order, not list order)"""
+        return self.index.sequence_offsets()
+
+    def search_phrases(self, phrases, k: int, nprobe: int, seeds: int = 32, refine: int = 4, *, lengths=None, groups=None,
+                       exclude_same_group: bool = False, sequences=None, query_chunk: int = DEFAULT_QUERY_CHUNK,
+                       phrase_chunk: int = DEFAULT_PHRASE_CHUNK, item_tiles: int = 0, return_candidates: bool = False,
+                       _workspace_fill=None):
+        """phrase search without a scan of the corpus: seed, vote, exact re-rank -> ``(costs, seqs, spans)`` as
+        ``SyllableIndex.search_phrases`` returns them (plus ``cand`` int64 ``[P, m]`` and ``bound`` fp32 ``[P, m]`` with
+        ``return_candidates=True``).  The lists are in list order, which breaks a DTW scan over them; they are used only to find
+        candidate sequences, and the DTW runs on ``ivf.index``, whose rows are still in id order.
+
+        Stage 1a: ``ivf.search(all phrase rows, k=seeds, nprobe)``: each row's ``seeds`` nearest rows among its ``nprobe`` nearest
+        lists.  With ``exclude_same_group`` and the default sequences every row carries its phrase's group, so that no seed is spent
+        on the phrase's own clip; with explicit ``sequences=`` stage 1a excludes nothing and the vote drops the excluded sequences.
+        Stages 1b and 2: ``ivf.index.search_phrases_seeded`` on those seeds with ``m = k * refine`` candidates, which has the
+        contract of the vote and of the result: ``search_phrases`` restricted to the candidates, every cost and span bit for bit a
+        ``search_phrases`` cost and span.
+
+        What the parameters trade: ``nprobe`` the share of the lists each row scans (stage 1a's time; a matching row in a list that
+        is not probed cannot be a seed); ``seeds`` how many sequences a row can vote for and how tight its floor is (the vote's LDS
+        and sort grow with it); ``refine`` how many candidates the exact DTW scores per returned sequence (stage 2's time).  Under the
+        default sequences with ``nprobe == nlist``, ``bound[p, r] <= cost(p, cand[p, r])`` exactly; if also ``seeds`` is at least the
+        number of admissible rows and m at least the number of admissible sequences, the result *is* ``search_phrases``, bit for
+        bit.  Nothing returned depends on ``query_chunk``, ``phrase_chunk``, ``item_tiles``, stale workspaces, ``build`` versus
+        ``build`` + ``add`` or a ``save`` / ``load`` round trip.  ``ivf.last_search`` keeps stage 1a's numbers and ``"seen"``: the
+        mean number of seen sequences per phrase.  ``1 <= seeds <= 128``, ``k * refine <= 128``."""
+        idx = self.index
+        k, m = _check_k_refine(k, refine, rerank=True)
+        nprobe = _check_nprobe(nprobe, self.nlist)
+        if isinstance(seeds, bool) or int(seeds) != seeds or not 1 <= int(seeds) <= MAX_SEEDS:
+            raise ValueError("seeds must be an integer in [1, %d], got %r" % (MAX_SEEDS, seeds))
+        seeds = int(seeds)
+        q, lens, pg, off = idx._phrase_args(phrases, lengths, groups, exclude_same_group, sequences, 0, phrase_chunk, 0)
+        _check_splits_chunk(item_tiles, query_chunk, "item_tiles")
+        dev = idx.device
+        P = int(lens.size)
+        if P == 0:
+            self.last_search = {"pairs": 0, "fraction": 0.0, "items": 0, "workspace_bytes": 0, "seen": 0.0}
+            sc = torch.empty((0, seeds), dtype=torch.float32, device=dev)
+            si = torch.empty((0, seeds), dtype=torch.int64, device=dev)
+        else:
+            own = pg is not None and sequences is None         # the rows' groups decide the default sequences: exclude in stage 1a
+            sc, si = self.search(q, seeds, nprobe, groups=np.repeat(pg, lens) if own else None, exclude_same_group=own,
+                                 query_chunk=query_chunk, item_tiles=item_tiles, _workspace_fill=_workspace_fill)
+            # the seen sequences of each phrase, counted as the vote sees them
+            d = sc if idx.metric == "l2" else torch.clamp_min(1.0 - sc, 0.0)
+            valid = (si >= 0) & ~torch.isnan(sc) & ~torch.isposinf(d)
+            seq = torch.bucketize(si, torch.from_numpy(off[1:]).to(dev), right=True)
+            owner = torch.repeat_interleave(torch.arange(P, device=dev), torch.from_numpy(lens).to(dev))
+            pairs = (owner[:, None] * (off.size - 1) + seq)[valid]
+            self.last_search["seen"] = float(torch.unique(pairs).numel()) / P
+        return idx.search_phrases_seeded(q, sc, si, k, refine, lengths=lens, groups=groups, exclude_same_group=exclude_same_group,
+                                         sequences=sequences, phrase_chunk=phrase_chunk, return_candidates=return_candidates,
+                                         _trusted_ids=True)
 
     # ---- persistence ----------------------------------------------------------------------------------------------------------------
     def save(self, path: str) -> None:

@@ -21,7 +21,17 @@ candidates; the two calls are bitwise the same before and after the drop), each 
 run; for refine 1, 2, 4 and 8 the share of phrases whose exact top-k comes back (rows held: the same list; rows dropped: the same
 set of sequences); and the device bytes of each index.  The codebooks are the sub-rows of 256 stored rows drawn at random, not
 k-means: the rows are independent gaussian, so training has no structure to find.  Codes, 16-bit codebooks and reconstruction norms
-are built before anything is timed."""
+are built before anything is timed.
+
+``--ivf [--nlist 4096] [--centres 20000] [--noise 0.3] [--configs 1:8:4,8:32:4,8:32:12,32:32:4,32:64:8]`` runs the leg of the phrase search
+through the inverted file (csrc/phrase_vote.hip, ``IVFSyllableIndex.search_phrases``) INSTEAD of the legs above, on data of its own:
+on independent gaussian rows recall of an inverted file means nothing, so the rows are the clustered mixture of tools/ivf_bench.py
+(sequences of 20 to 60 rows) and each phrase is m consecutive rows of one sequence plus ``noise`` x gaussian noise.  Per (rows, m),
+all from one run: the whole-call time of ``search_phrases`` and ``search_phrases_refined`` (the parent's entry points, the
+yardstick), and per ``nprobe:seeds:refine`` the whole-call time of ``ivf.search_phrases``, of ``ivf.search`` alone on the same rows
+with ``k = seeds``, of the re-rank alone (``sylber_dtw_rerank`` on the call's candidates, packed before the clock starts), the
+remainder (the vote and the host work: packing, tables, the seen count), ``last_search``'s fraction and seen, recall@k against the
+exact sequences, the share of phrases whose exact top-k / best sequence comes back and the share whose planted sequence is first."""
 import argparse
 import json
 import os
@@ -48,6 +58,102 @@ def timed(fn, iters):
     return statistics.median(out), min(out), max(out)
 
 
+def rerank_alone(idx, phrases, lens, cand, k):
+    """a closure that runs stage 2 alone (``sylber_dtw_rerank``) on the candidates ``cand [P, m]`` of one call; the packing of the
+    phrases, the tables and the buffers are made here, before the clock starts"""
+    from sylber_amd import _lib
+    from sylber_amd._index import _on_device, _phrase_outputs, _row_norms
+    from sylber_amd.kmeans import _stream, _vp
+    lib, dev = _lib.load(), idx.device
+    lens = np.asarray(lens, np.int64)
+    P, m = cand.shape
+    off = idx.sequence_offsets()
+    off_d = _on_device(off, np.int32, dev)
+    b = idx._phrase_blocks(lib, idx._prep(phrases), lens, 0, P, off, m, 0, 0, None)
+    qn = _row_norms(b.qp)
+    ws = torch.empty(int(lib.sylber_dtw16_workspace_bytes(P, m, 1)), dtype=torch.uint8, device=dev)
+    place_d, len_d = _on_device(b.place, np.int32, dev), _on_device(lens, np.int32, dev)
+    c32 = cand.to(torch.int32).contiguous()
+    costs, seqs, spans = _phrase_outputs(P, k, dev)
+
+    def run():
+        with torch.cuda.device(dev):
+            _lib.check(lib.sylber_dtw_rerank(_vp(b.qp), b.nb, _vp(qn), _vp(place_d), _vp(len_d), P, _vp(idx._x), len(idx), idx.dim, _vp(idx._c),
+                                             0, _vp(c32), m, _vp(off_d), off.size - 1, k, _vp(costs), _vp(seqs), _vp(spans), _vp(ws),
+                                             _stream(dev)), "sylber_dtw_rerank")
+    return run
+
+
+def ivf_leg(args, dev):
+    from sylber_amd import IVFSyllableIndex, SyllableIndex
+    g = torch.Generator(device=dev).manual_seed(0)
+    rng = np.random.default_rng(0)
+    D, N, k = 768, args.N, args.k
+    lens = rng.integers(20, 61, N // 20 + 1)
+    lens = lens[:int(np.searchsorted(np.cumsum(lens), N)) + 1]
+    lens[-1] -= int(lens.sum()) - N
+    lens = lens[lens > 0]
+    off = np.concatenate([[0], np.cumsum(lens)])
+    groups = np.repeat(np.arange(lens.size), lens).astype(np.int32)
+    cent = 2.0 * torch.randn(args.centres, D, device=dev, generator=g)
+    w = torch.rand(args.centres, device=dev, generator=g) ** 3
+    x = torch.empty(N, D, device=dev)
+    for r0 in range(0, N, 1 << 19):
+        n = min(1 << 19, N - r0)
+        x[r0:r0 + n] = cent[torch.multinomial(w, n, replacement=True, generator=g)] + torch.randn(n, D, device=dev, generator=g)
+    idx = SyllableIndex(x, metric="l2", groups=groups, device=dev)
+    del x
+    idx.sequence_offsets()
+    idx.half_rows(args.storage)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    ivf = IVFSyllableIndex.build(idx, nlist=args.nlist, seed=0, max_iter=args.max_iter, train_rows=args.train_rows)
+    torch.cuda.synchronize()
+    head = {"D": D, "metric": "l2", "N": N, "sequences": int(lens.size), "nlist": args.nlist, "k": k, "iters": args.iters, "noise": args.noise,
+            "storage": args.storage, "build_s": round(time.perf_counter() - t0, 2),
+            "data": "synthetic mixture of %d Gaussians, sequences of 20 to 60 rows, planted noisy phrases" % args.centres}
+    print(json.dumps(head), file=sys.stderr, flush=True)
+    configs = [tuple(int(v) for v in c.split(":")) for c in args.configs.split(",")]
+    out = []
+    for rows in [int(v) for v in args.rows.split(",")]:
+        for m in [int(v) for v in args.ms.split(",")]:
+            P = rows // m
+            ok = np.nonzero(lens >= m)[0]
+            truth = ok[rng.integers(0, ok.size, P)]
+            start = off[truth] + (rng.random(P) * (lens[truth] - m + 1)).astype(np.int64)
+            pick = torch.from_numpy((start[:, None] + np.arange(m)[None, :]).reshape(-1)).to(dev)
+            ph = idx.features[pick] + args.noise * torch.randn(P * m, D, device=dev, generator=g)
+            ln = [m] * P
+            truth_d = torch.from_numpy(truth).to(dev)
+            t_exact, lo, hi = timed(lambda: idx.search_phrases(ph, k, lengths=ln), min(args.iters, 2))
+            exact = idx.search_phrases(ph, k, lengths=ln)[1]
+            t_ref, lo2, hi2 = timed(lambda: idx.search_phrases_refined(ph, k, args.refine, args.storage, lengths=ln), args.iters)
+            base = {"rows": P * m, "m": m, "phrases": P, "phrase_ms": round(t_exact, 2), "phrase_ms_min_max": [round(lo, 2), round(hi, 2)],
+                    "refined_ms": round(t_ref, 2), "refined_ms_min_max": [round(lo2, 2), round(hi2, 2)], "refined_refine": args.refine,
+                    "exact_planted_top1": round(float((exact[:, 0] == truth_d).float().mean()), 4)}
+            for nprobe, seeds, refine in configs:
+                if nprobe > min(args.nlist, 128) or k * refine > 128:
+                    continue
+                call = lambda: ivf.search_phrases(ph, k, nprobe, seeds=seeds, refine=refine, lengths=ln, return_candidates=True)
+                t, lo, hi = timed(call, args.iters)
+                got = call()
+                ls = dict(ivf.last_search)
+                t_seed, _, _ = timed(lambda: ivf.search(ph, seeds, nprobe), args.iters)
+                t_rr, _, _ = timed(rerank_alone(idx, ph, ln, got[3], k), args.iters)
+                row = dict(base, nprobe=nprobe, seeds=seeds, refine=refine, ivf_phrase_ms=round(t, 2), ivf_phrase_ms_min_max=[round(lo, 2), round(hi, 2)],
+                           seed_search_ms=round(t_seed, 2), rerank_ms=round(t_rr, 2), remainder_ms=round(t - t_seed - t_rr, 2),
+                           over_refined=round(t / t_ref, 3), over_phrase=round(t / t_exact, 3), fraction=round(ls["fraction"], 6),
+                           seen=round(ls["seen"], 1),
+                           recall_at_k=round(float(((got[1][:, :, None] == exact[:, None, :]) & (exact[:, None, :] >= 0)).any(1).sum())
+                                             / max(1, int((exact >= 0).sum())), 4), recovered_topk=round(float((got[1] == exact).all(1).float().mean()), 4),
+                           recovered_top1=round(float((got[1][:, 0] == exact[:, 0]).float().mean()), 4),
+                           planted_top1=round(float((got[1][:, 0] == truth_d).float().mean()), 4))
+                print(json.dumps(row), file=sys.stderr, flush=True)
+                out.append(row)
+    head["rows"] = out
+    print(json.dumps(head))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=5)
@@ -60,10 +166,19 @@ def main():
     ap.add_argument("--refine", type=int, default=4)
     ap.add_argument("--pq", action="store_true")
     ap.add_argument("--M", type=int, default=48)
+    ap.add_argument("--ivf", action="store_true")
+    ap.add_argument("--nlist", type=int, default=4096)
+    ap.add_argument("--centres", type=int, default=20000)
+    ap.add_argument("--noise", type=float, default=0.3)
+    ap.add_argument("--configs", default="1:8:4,8:32:4,8:32:12,32:32:4,32:64:8")
+    ap.add_argument("--max-iter", type=int, default=10)
+    ap.add_argument("--train-rows", type=int, default=524288)
     args = ap.parse_args()
     from sylber_amd import SyllableIndex
     dev = torch.device("cuda:0")
     torch.cuda.set_device(dev)
+    if args.ivf:
+        return ivf_leg(args, dev)
     g = torch.Generator(device=dev).manual_seed(0)
     rng = np.random.default_rng(0)
     D, N, k = 768, args.N, args.k
