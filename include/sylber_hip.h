@@ -437,6 +437,49 @@ int sylber_dtw_rerank(const float* q_dev, int32_t n_blocks, const float* q_norm_
                       int32_t metric, const int32_t* cand_dev, int32_t m, const int32_t* seq_offsets_dev, int32_t n_seq, int32_t k,
                       float* cost_dev, int64_t* seq_dev, int64_t* span_dev, void* workspace_dev, void* stream);
 
+/* Every occurrence of a phrase (sylber_amd/search.py: SyllableIndex.search_occurrences / search_occurrences_refined; restated in
+ * tests/occ_ref.py): every non-overlapping occurrence of a phrase in a sequence instead of the sequence's best one.  Local costs d,
+ * the recurrence, the predecessor order on ties, start[i][j] and the NaN -> +inf rule are sylber_dtw_search's, word for word.  For
+ * one phrase (m rows) and one sequence (columns 0 .. L - 1) let E[j] = A[m-1][j] and st[j] = start[m-1][j].
+ *   1. Families.  Only columns with E[j] < +inf count (the start of an infinite cell carries no meaning and is not looked at).
+ *      Columns with equal st[j] form a family: start = st[j], cost = min E[j], end = the smallest such j.  Over the finite columns
+ *      st[j] does not decrease as j grows (two paths that would cross share a cell, and a cell has one predecessor chain), so a
+ *      family is a run of neighbouring finite columns and families arrive in ascending start and ascending end.
+ *   2. One left-to-right pass keeps non-overlapping families.  The first family becomes pending.  For each later family F: if
+ *      F.start <= pending.end (the spans share a row) the cheaper of the two stays pending, the pending one on equal cost;
+ *      otherwise the pending family is emitted and F becomes pending.  At the sequence end the pending family is emitted.  Emitted
+ *      occurrences of one sequence are pairwise disjoint, and each is a real warping path with the cost, start and end the
+ *      recurrence gives it.
+ *   3. Per phrase the k best emitted occurrences over all admissible sequences (the group arrays mean what they mean for
+ *      sylber_dtw_search), ordered strictly by (cost, first row of the span) ascending -- row ids ascend with sequence numbers, so
+ *      this refines sylber_dtw_search's (cost, sequence) -- and padded with (+inf, -1, (-1, -1)).
+ *   So: the best occurrence of a sequence under (cost, start) is bit for bit sylber_dtw_search's (cost, span) of that pair; for
+ *   one-row phrases every finite row is an occurrence (sylber_knn_search with ids = span starts); nothing depends on the cuts, the
+ *   packing or chunking of phrases or what the workspace held.
+ *   The pass is NOT global greedy suppression by cost: of a chain A - B - C with A and C disjoint, both overlapping B, and costs
+ *   A > B > C it emits only C (B beats A, C beats B), where greedy suppression would keep C and A.  The one-pass rule is what runs
+ *   inside the scan with constant state per lane.
+ * sylber_dtw_occurrences: sylber_dtw_search's arguments, sylber_dtw_plan's packing and cuts, a workspace of
+ *   sylber_dtw_workspace_bytes(n_blocks, n_phrases, k, cuts) bytes.  cost_dev [n_phrases, k] fp32, seq_dev [n_phrases, k] int64
+ *   (the sequence of each occurrence), span_dev [n_phrases, k, 2] int64 (first row, one past the last row).
+ * sylber_dtw_rerank_occurrences: sylber_dtw_rerank's arguments; for the candidate sequences of cand_dev [n_phrases, m] (-1 = none;
+ *   the candidates of one phrase must be distinct, as sylber_dtw16_scan's are) the occurrences of sylber_dtw_occurrences restricted
+ *   to those sequences, bit for bit, the best k (1 <= k <= 128, not bounded by m) per phrase.  It excludes nothing: the stage that
+ *   chose the candidates did.  workspace_dev: sylber_dtw_occ_workspace_bytes(n_phrases, m, k) bytes (-1 on a bad argument),
+ *   O(P m k): m lists of k per phrase and their merge rounds.
+ * Both refuse n_phrases x lists x k beyond 2^30 entries (status 1, sylber_last_error): use smaller phrase chunks. */
+int sylber_dtw_occurrences(const float* q_dev, int32_t n_blocks, const int32_t* row_meta_dev, const int32_t* slot_phrase_dev,
+                           const int32_t* block_rows_dev, int32_t n_phrases, int32_t block_phrases, const float* db_dev, int32_t N,
+                           int32_t D, const float* db_norm_dev, int32_t metric, int32_t k, const int32_t* seq_id_dev,
+                           const int32_t* cut_rows_dev, int32_t cuts, const int32_t* phrase_group_dev, const int32_t* seq_group_dev,
+                           float* cost_dev, int64_t* seq_dev, int64_t* span_dev, void* workspace_dev, void* stream);
+int64_t sylber_dtw_occ_workspace_bytes(int32_t n_phrases, int32_t m, int32_t k);
+int sylber_dtw_rerank_occurrences(const float* q_dev, int32_t n_blocks, const float* q_norm_dev, const int32_t* phrase_row_dev,
+                                  const int32_t* phrase_len_dev, int32_t n_phrases, const float* db_dev, int32_t N, int32_t D,
+                                  const float* db_norm_dev, int32_t metric, const int32_t* cand_dev, int32_t m,
+                                  const int32_t* seq_offsets_dev, int32_t n_seq, int32_t k, float* cost_dev, int64_t* seq_dev,
+                                  int64_t* span_dev, void* workspace_dev, void* stream);
+
 /* Compressed phrase search (sylber_amd/pq.py: PQSyllableIndex.search_phrases): sylber_dtw16_scan with the database given as
  * product-quantization codes.  codes_dev [N, M] uint8 and bad_dev [N] uint8 (nullable; 1 = a masked row) as sylber_pq_encode writes
  * them; codebooks16_dev [M, 256, D / M] = sylber_knn16_pack of the fp32 codebooks in `storage`; 1 <= M <= 64, D % M == 0,

@@ -21,6 +21,8 @@
 //     lane of the last row tracks (best cost, start, end), the smallest end on ties.  Only the chunk loop depends on the length.
 //   * dtw_rank_kernel: one wave per phrase ranks its m pair results by (cost, sequence) and writes the best k with spans as row ids.
 //     A second launch: nothing relies on an order between workgroups.
+//   * dtw_occ_rerank_kernel (at the end of the file; SyllableIndex.search_occurrences_refined, tests/occ_ref.py): dtw_rerank_kernel's
+//     walk with every non-overlapping occurrence of the candidate kept, k per pair in LDS; merged and reported by dtw_occ.h.
 // LDS and occupancy (a CU has 160 KiB):
 //   dtw16_scan_kernel   69 136 B fixed (cost tile 67 584 | c_j, sequence ids, groups) + 8 B x (phrases of the block) x m <= 32 KiB
 //                       of lists = at most 101 904 B: one workgroup of 4 waves per CU (dtw_search_kernel: 134 672 B, also one); two
@@ -28,9 +30,10 @@
 //                       matter: one workgroup's contraction then hides under the other's wavefront (profiles/phrase_bench.md:
 //                       219 ms against 399 ms for the same work).
 //   dtw_rerank_kernel   9 216 B (64 rows x 36 floats), 64 threads: LDS allows 17 workgroups per CU, so the wave slots and registers
-//                       bound it, not LDS.
+//                       bound it, not LDS.  dtw_occ_rerank_kernel adds its list: 9 216 + 16 k <= 11 264 B.
 #include "kernels.h"
 #include "dtw16_scan.h"
+#include "dtw_occ.h"
 
 constexpr int DT_RR_CH = 32;                              // columns of a re-rank chunk (RERANK_CHUNK of search.py)
 constexpr int DT_RR_LD = 36;                              // row stride of the chunk's costs: lane i reads d[i][t - i], bank (3 i + t) % 32
@@ -366,4 +369,118 @@ extern "C" int sylber_dtw_rerank(const float* q_dev, int32_t n_blocks, const flo
                        seq_dev, span_dev);
     HIP_TRY(hipGetLastError());
     return 0;
+}
+
+// ---- every occurrence of a phrase among candidate sequences (SyllableIndex.search_occurrences_refined) ----------------------------
+// dtw_rerank_kernel's sibling: the same wave per (phrase, candidate) pair, the same chunk loop and explicit fmaf chain, so every
+// A[m-1][j] and start has the bits of dtw_occ_kernel's.  The lane of the last row runs dt_occ_cell's one-pass rule and the wave
+// keeps the pair's k best occurrences as a sorted list of (cost, start row, (start row, end row)) in LDS (16 B x k <= 2 KiB);
+// it goes to ps / pi / pp [P][m][k], a list of fillers for a candidate of -1.  Candidate sequences of a phrase are distinct (stage
+// 1's are), so the start rows of its m lists are: knn_merge_kernel<true> reduces them and dtw_occ_finish_kernel reports.
+__global__ __launch_bounds__(64) void dtw_occ_rerank_kernel(const float* __restrict__ q, const float* __restrict__ qsq, int qrows,
+                                                            const int32_t* __restrict__ prow, const int32_t* __restrict__ plen,
+                                                            const float* __restrict__ x, int N, int D, const float* __restrict__ cn,
+                                                            const int32_t* __restrict__ cand, const int32_t* __restrict__ soff, int S,
+                                                            int m, int k, float* __restrict__ ps, int32_t* __restrict__ pi,
+                                                            int2* __restrict__ pp) {
+    __shared__ float dsm[DT_MAX_M * DT_RR_LD];
+    __shared__ float ols[KN_KMAX];
+    __shared__ int oli[KN_KMAX];
+    __shared__ int2 olp[KN_KMAX];
+    const int lane = threadIdx.x;
+    const size_t pair = blockIdx.x;
+    const int p = (int)(pair / m);
+    const int sidx = cand[pair];
+    int j0 = 0, j1 = 0;
+    if (sidx >= 0 && sidx < S) {
+        j0 = soff[sidx]; j1 = soff[sidx + 1];
+        j0 = j0 < 0 ? 0 : j0; j1 = j1 > N ? N : j1;
+    }
+    for (int e = lane; e < k; e += 64) { ols[e] = INFINITY; oli[e] = INT_MAX; olp[e] = make_int2(-1, -1); }
+    int mp = plen[p];
+    mp = mp < 1 ? 1 : (mp > DT_MAX_M ? DT_MAX_M : mp);
+    int r = prow[p] + (lane < mp ? lane : mp - 1);         // lanes behind the phrase read its last row and keep nothing
+    r = r < 0 ? 0 : (r < qrows ? r : qrows - 1);
+    const float* qr = q + (size_t)r * D;
+    const float qn = qsq ? qsq[r] : 0.f;
+    const bool valid = lane < mp, lastrow = lane == mp - 1;
+    DtLane st;
+    DtOcc oc;
+    float* dr = dsm + lane * DT_RR_LD;
+    for (int n0 = j0; n0 < j1; n0 += DT_RR_CH) {           // no chunk for a candidate of -1: its list stays fillers
+        const int ncol = j1 - n0 < DT_RR_CH ? j1 - n0 : DT_RR_CH;
+        // dtw_rerank_kernel's dots: the fmaf chain over ascending c from 0, explicit __builtin_fmaf calls
+        float dot[DT_RR_CH];
+#pragma unroll
+        for (int jj = 0; jj < DT_RR_CH; ++jj) dot[jj] = 0.f;
+        for (int c = 0; c < D; c += 4) {
+            const float4 a = *(const float4*)(qr + c);
+#pragma unroll
+            for (int jj = 0; jj < DT_RR_CH; ++jj) {
+                const int j = jj < ncol ? n0 + jj : j1 - 1;
+                const float4 bv = *(const float4*)(x + (size_t)j * D + c);
+                dot[jj] = __builtin_fmaf(bv.x, a.x, dot[jj]);
+                dot[jj] = __builtin_fmaf(bv.y, a.y, dot[jj]);
+                dot[jj] = __builtin_fmaf(bv.z, a.z, dot[jj]);
+                dot[jj] = __builtin_fmaf(bv.w, a.w, dot[jj]);
+            }
+        }
+        __syncthreads();                                   // the previous chunk's costs are read; the first time: the list is cleared
+#pragma unroll
+        for (int jj = 0; jj < DT_RR_CH; ++jj) {
+            const int j = jj < ncol ? n0 + jj : j1 - 1;
+            dr[jj] = dt_cost(dot[jj], cn ? cn[j] : 0.f, qsq != nullptr, qn);
+        }
+        __syncthreads();
+        for (int t = 0; t < ncol + mp - 1; ++t) {
+            const DtUp u = dt_up<true>(st);
+            const int j = t - lane;
+            bool out = false, end = false;
+            float ec = INFINITY;
+            int es = 0, ee = 0;
+            if (valid && j >= 0 && j < ncol) {
+                out = dt_occ_cell(st, oc, u, lane == 0, lastrow, n0 + j == j0, dr[j], n0 + j, ec, es, ee);
+                end = lastrow && n0 + j == j1 - 1 && oc.pc < INFINITY;
+            }
+            // only lane mp - 1 can owe a hand-off; at the sequence's last column it may owe both
+            if (__ballot(out)) {
+                const int vs = __shfl(es, mp - 1);
+                kn_insert_t<true>(ols, oli, olp, k, lane, __shfl(ec, mp - 1), vs, make_int2(vs, __shfl(ee, mp - 1)));
+            }
+            if (__ballot(end)) {
+                const int vs = __shfl(oc.ps, mp - 1);
+                kn_insert_t<true>(ols, oli, olp, k, lane, __shfl(oc.pc, mp - 1), vs, make_int2(vs, __shfl(oc.pe, mp - 1)));
+            }
+        }
+    }
+    __syncthreads();
+    for (int e = lane; e < k; e += 64) { ps[pair * k + e] = ols[e]; pi[pair * k + e] = oli[e]; pp[pair * k + e] = olp[e]; }
+}
+
+extern "C" int64_t sylber_dtw_occ_workspace_bytes(int32_t n_phrases, int32_t m, int32_t k) {
+    if (n_phrases < 1 || m < 1 || m > KN_KMAX || k < 1 || k > KN_KMAX) return -1;
+    return dt_occ_lists_bytes(n_phrases, m, k);
+}
+
+extern "C" int sylber_dtw_rerank_occurrences(const float* q_dev, int32_t n_blocks, const float* q_norm_dev, const int32_t* phrase_row_dev,
+                                             const int32_t* phrase_len_dev, int32_t n_phrases, const float* db_dev, int32_t N, int32_t D,
+                                             const float* db_norm_dev, int32_t metric, const int32_t* cand_dev, int32_t m,
+                                             const int32_t* seq_offsets_dev, int32_t n_seq, int32_t k, float* cost_dev, int64_t* seq_dev,
+                                             int64_t* span_dev, void* workspace_dev, void* stream) {
+    static const char* what = "sylber_dtw_rerank_occurrences";
+    hipStream_t s = (hipStream_t)stream;
+    if (!q_dev || !phrase_row_dev || !phrase_len_dev || !db_dev || !cand_dev || !seq_offsets_dev || !cost_dev || !seq_dev || !span_dev ||
+        !workspace_dev) { syl_set_error(what, "null argument"); return 1; }
+    if (n_blocks < 1 || n_phrases < 1 || N < 1 || n_seq < 1 || D < 16 || D % 16) { syl_set_error(what, "need n_blocks, n_phrases, N, n_seq >= 1 and D a multiple of 16"); return 1; }
+    if (m < 1 || m > KN_KMAX || k < 1 || k > KN_KMAX) { syl_set_error(what, "need 1 <= m <= 128 and 1 <= k <= 128"); return 1; }
+    if (metric != SYLBER_KNN_L2 && metric != SYLBER_KNN_IP) { syl_set_error(what, "unknown metric"); return 1; }
+    if (metric == SYLBER_KNN_L2 && (!db_norm_dev || !q_norm_dev)) { syl_set_error(what, "the L2 metric needs db_norm_dev and q_norm_dev"); return 1; }
+    if ((int64_t)n_blocks * KN_BM > INT32_MAX || (int64_t)n_phrases * m * k > INT32_MAX / 2) { syl_set_error(what, "n_phrases x m x k is too large: use smaller phrase chunks"); return 1; }
+    const DtOccLists lists = dt_occ_lists_carve((char*)workspace_dev, n_phrases, m, k);
+    const float* qn = metric == SYLBER_KNN_L2 ? q_norm_dev : nullptr;
+    const float* cn = metric == SYLBER_KNN_L2 ? db_norm_dev : nullptr;
+    hipLaunchKernelGGL(dtw_occ_rerank_kernel, dim3((unsigned)((int64_t)n_phrases * m)), dim3(64), 0, s, q_dev, qn, n_blocks * KN_BM, phrase_row_dev,
+                       phrase_len_dev, db_dev, N, D, cn, cand_dev, seq_offsets_dev, n_seq, m, k, lists.s0, lists.i0, lists.p0);
+    HIP_TRY(hipGetLastError());
+    return dt_occ_merge_finish(lists, n_phrases, m, k, nullptr, seq_offsets_dev, n_seq, cost_dev, seq_dev, span_dev, s);
 }

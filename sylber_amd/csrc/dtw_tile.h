@@ -4,7 +4,9 @@
 // the write-out of a block's lists.  dtw.hip's dtw_search_kernel (fp32, spans tracked: SPAN = true) and dtwpq.hip's
 // dtwpq_scan_kernel (SPAN = false) are built from all of them; dtw16.hip's dtw16_scan_kernel uses the column data and keeps the
 // rest written out (its header says why), its dtw_rerank_kernel uses the local cost, the lane state and the cell (dt_cost, dt_up,
-// dt_cell).  The order of the predecessor comparisons and the NaN -> +inf rule are the contract's (include/sylber_hip.h).  Every
+// dt_cell).  The occurrence scans (dtw.hip's dtw_occ_kernel, dtw16.hip's dtw_occ_rerank_kernel) add a pending occurrence to the lane
+// state and hand over at any column: DtOcc, dt_occ_cell, dt_occ_wavefront below, siblings that leave the pieces above as they
+// were.  The order of the predecessor comparisons and the NaN -> +inf rule are the contract's (include/sylber_hip.h).  Every
 // piece is forced inline; the contraction (fp32: knn_tile.h, 16-bit: knn16_tile.h) and the K loop around it stay with the kernels.
 #pragma once
 #include "knn_tile.h"
@@ -191,6 +193,76 @@ __device__ __forceinline__ void dt_wavefront(const DtLds<SPAN>& L, const DtRow& 
             if constexpr (SPAN) span = make_int2(__shfl(s.bst, c), __shfl(s.be, c));
             kn_insert_t<SPAN>(L.ls + sl * m, L.li + sl * m, L.lp + sl * m, m, lane, v, vs, span);
         }
+    }
+}
+
+// ---- every occurrence (sylber_dtw_occurrences, sylber_dtw_rerank_occurrences; "Every occurrence of a phrase" in
+// include/sylber_hip.h).  Siblings of dt_cell / dt_wavefront: those two and DtLane are untouched, the kernels built from them
+// compile from the text they had.
+// What the lane of a phrase's last row keeps of the current sequence beside its DtLane: the pending occurrence (cost, start row,
+// end row); pc = +inf: none, and then (ps, pe) mean nothing.  The contract's one-pass rule is stated over families (the finite
+// columns of the last row with one start); here every finite column is taken by itself as (E[j], st[j], j).  That is the same
+// pass: a family's columns are neighbours and all of them overlap the pending occurrence or none does, so offering them one by
+// one against "the cheaper stays, the pending one on ties" leaves what offering their (min, smallest such j) once leaves; a
+// column that finds its own family pending overlaps it (start <= end).  tests/test_occ_ref.py holds the two forms equal.
+struct DtOcc { float pc = INFINITY; int ps = 0, pe = 0; };
+
+// One cell of the occurrence scan: dt_cell's recurrence (taken with lastrow = false: the best-of-sequence fields of DtLane stay
+// unused), then on a phrase's last row the one-pass rule on column `col`.  Returns true when the pending occurrence is pushed out
+// by a disjoint one: the caller hands over (ec, es, ee).
+__device__ __forceinline__ bool dt_occ_cell(DtLane& s, DtOcc& o, const DtUp& u, bool first, bool lastrow, bool isstart, float d, int col,
+                                            float& ec, int& es, int& ee) {
+    dt_cell<true>(s, u, first, false, isstart, d, col);
+    if (!lastrow) return false;
+    if (isstart) o.pc = INFINITY;                          // a new sequence: nothing is pending
+    const float A = s.a_cur;
+    if (!(A < INFINITY)) return false;                     // the start of an infinite cell carries no meaning
+    const int sa = s.s_cur;
+    if (o.pc < INFINITY && sa > o.pe) {                    // disjoint from the pending one: that one is an occurrence
+        ec = o.pc; es = o.ps; ee = o.pe;
+        o.pc = A; o.ps = sa; o.pe = col;
+        return true;
+    }
+    if (A < o.pc) { o.pc = A; o.ps = sa; o.pe = col; }     // the spans share a row: the cheaper stays, the pending one on ties
+    return false;
+}
+
+// one hand-off per set bit of fb: lane c's (v, start row, (start row, end row)) into the list of its phrase.  Distinct occurrences
+// have distinct start rows, so the lists stay strictly ordered by (cost, start row).
+__device__ __forceinline__ void dt_occ_hand(const DtLds<true>& L, uint64_t fb, int lane, int m, float v, int vs, int ve, int slot) {
+    while (fb) {
+        const int c = __ffsll((unsigned long long)fb) - 1;
+        fb &= fb - 1;
+        const float cv = __shfl(v, c);
+        const int cs = __shfl(vs, c), ce = __shfl(ve, c), sl = __shfl(slot, c);
+        kn_insert_t<true>(L.ls + sl * m, L.li + sl * m, L.lp + sl * m, m, lane, cv, cs, make_int2(cs, ce));
+    }
+}
+
+// dt_wavefront for occurrences.  A hand-off can happen at any column, gated by the list's tail exactly as dt_wavefront's; at a
+// sequence's last column a lane may owe two: the pending occurrence that a disjoint column has just pushed out, and that column
+// itself, pending at the sequence end.  The pending state survives tile edges with DtLane and is cleared at a sequence start;
+// cuts fall on sequence starts, so none crosses workgroups.
+__device__ __forceinline__ void dt_occ_wavefront(const DtLds<true>& L, const DtRow& r, DtLane& s, DtOcc& o, int lane, int n0, int ncol,
+                                                 bool grouped, int m) {
+    const float* dr = L.dm + r.drow * DT_LD;
+    for (int st = 0; st < ncol + r.maxi; ++st) {
+        const DtUp u = dt_up<true>(s);
+        const int j = st - r.pi;
+        bool fin = false, fin2 = false;
+        float ec = INFINITY;
+        int es = 0, ee = 0;
+        if (r.valid && j >= 0 && j < ncol) {
+            const int sj = L.sq[j + 1];
+            const bool out = dt_occ_cell(s, o, u, r.pi == 0, r.lastrow, L.sq[j] != sj, dr[j], n0 + j, ec, es, ee);
+            const bool adm = r.lastrow && !(grouped && L.sgs[j] == r.pg);
+            const float tv = L.ls[r.slot * m + m - 1];
+            const int ti = L.li[r.slot * m + m - 1];
+            fin = out && adm && kn_better(ec, es, tv, ti);
+            fin2 = adm && L.sq[j + 2] != sj && o.pc < INFINITY && kn_better(o.pc, o.ps, tv, ti);
+        }
+        dt_occ_hand(L, __ballot(fin), lane, m, ec, es, ee, r.slot);
+        dt_occ_hand(L, __ballot(fin2), lane, m, o.pc, o.ps, o.pe, r.slot);       // kn_insert_t tests the tail again: the first hand-off may have moved it
     }
 }
 

@@ -17,6 +17,8 @@ method's docstring, restated in numpy in tests/dtw_ref.py.  ``SyllableIndex.sear
 a 16-bit MFMA scan picks candidate sequences, the exact DTW re-ranks them; tests/dtw16_ref.py).  ``IVFSyllableIndex.search_phrases`` finds the
 candidate sequences without a scan of the corpus: each phrase row's neighbours from the lists vote for them (csrc/phrase_vote.hip;
 ``SyllableIndex.search_phrases_seeded`` is the vote and the re-rank on seeds from anywhere; tests/phrase_vote_ref.py).
+``SyllableIndex.search_occurrences`` / ``search_occurrences_refined`` return every non-overlapping occurrence of a phrase instead of one
+match per sequence (``sylber_dtw_occurrences``, ``sylber_dtw_rerank_occurrences``; tests/occ_ref.py).
 
 The rules that every index shares -- argument checks, row preparation, result buffers, provenance, the list layout, the arrays of a
 saved file -- are in _index.py, each once; this file and pq.py hold what differs between the indexes.
@@ -39,6 +41,7 @@ from ._index import (DEFAULT_QUERY_CHUNK, METRICS, _added_rows, _base_arrays, _c
 from .kmeans import _device, _stream, _vp
 
 RERANK_CHUNK = 32               # DT_RR_CH of csrc/dtw16.hip: the columns of a sequence that search_phrases_refined re-ranks at a time
+OCC_RERANK_ENTRIES = 1 << 24    # list entries (24 B each with the merge rounds' half) of one sylber_dtw_rerank_occurrences launch
 
 
 class SyllableIndex:
@@ -358,6 +361,124 @@ class SyllableIndex:
                 _lib.check(lib.sylber_dtw_rerank(_vp(b.qp), b.nb, _vp(qn), _vp(place_d), _vp(len_d), b.Pc, _vp(self._x), N, self.dim,
                                                  _vp(self._c), metric, _vp(cand[p0:p1]), m, _vp(off_d), S, k, _vp(costs[p0:p1]),
                                                  _vp(seqs[p0:p1]), _vp(spans[p0:p1]), _vp(ws), st), "sylber_dtw_rerank")
+        return (costs, seqs, spans, cand.to(torch.int64), coarse) if return_candidates else (costs, seqs, spans)
+
+    def search_occurrences(self, phrases, k: int, *, lengths=None, groups=None, exclude_same_group: bool = False, sequences=None,
+                           splits: int = 0, phrase_chunk: int = DEFAULT_PHRASE_CHUNK, block_phrases: int = 0,
+                           _workspace_fill=None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """every non-overlapping occurrence of each phrase, not one match per sequence: the k best occurrences over the whole index
+        -> ``(costs fp32 [P, k], seqs int64 [P, k], spans int64 [P, k, 2])`` on the device, as ``search_phrases`` shapes them; a
+        keyword said five times in one long recording comes back five times, with one sequence number.  Arguments, sequences,
+        local costs ``d``, the recurrence, the predecessor order on ties, ``start[i][j]`` and the NaN -> ``+inf`` rule are
+        ``search_phrases``'s, word for word (csrc/dtw.hip, ``sylber_dtw_occurrences``; restated in tests/occ_ref.py).
+
+        For one phrase (m rows) and one sequence (columns ``0 .. L - 1``) let ``E[j] = A[m-1][j]``, ``st[j] = start[m-1][j]``:
+
+        1. Families.  Only columns with ``E[j] < +inf`` count.  Columns with equal ``st[j]`` form a family: ``start = st[j]``,
+           ``cost = min E[j]``, ``end`` = the smallest such j.  Over the finite columns ``st[j]`` does not decrease with j, so a
+           family is a run of neighbouring finite columns and families arrive in ascending start and ascending end.
+        2. One left-to-right pass keeps non-overlapping families.  The first becomes *pending*.  For each later family ``F``: if
+           ``F.start <= pending.end`` (the spans share a row) the cheaper of the two stays pending, the pending one on equal cost;
+           otherwise the pending family is *emitted* and ``F`` becomes pending.  At the sequence end the pending family is emitted.
+           Emitted occurrences of one sequence are pairwise disjoint; each is a real warping path with the cost, start and end the
+           recurrence gives it.
+        3. Per phrase the k best emitted occurrences over all admissible sequences (``exclude_same_group`` as in
+           ``search_phrases``), ordered strictly by (cost, first row id of the span) ascending, which refines ``search_phrases``'s
+           (cost, sequence); padding ``(+inf, -1, (-1, -1))``.
+
+        So the best occurrence of a sequence under (cost, start) is bit for bit ``search_phrases``'s (cost, span) of that pair, and
+        keeping each sequence's first entry gives ``search_phrases`` when nothing was cut off at k; for one-row phrases every
+        finite row is an occurrence, so the call is ``search`` (ids = span starts); nothing depends on ``splits``,
+        ``phrase_chunk``, ``block_phrases``, stale workspace contents or one ``add`` against many.
+
+        The pass is **not** global greedy suppression by cost: of a chain A - B - C with A and C disjoint, both overlapping B, and
+        costs A > B > C it emits only C, where greedy suppression would also keep A.  The one-pass rule is what runs inside the
+        scan with constant state per lane.  No cost threshold, no cap per sequence: filter the result."""
+        k = _check_k_refine(k)[0]
+        q, lens, pg, off = self._phrase_args(phrases, lengths, groups, exclude_same_group, sequences, splits, phrase_chunk, block_phrases)
+        P = int(lens.size)
+        dev = self.device
+        costs, seqs, spans = _phrase_outputs(P, k, dev)
+        if P == 0:
+            return costs, seqs, spans
+        lib = _lib.load()
+        qd = self._prep(q)
+        N = len(self)
+        seq_id, seq_grp = self._sequence_tables(off, pg is not None)
+        metric = METRICS[self.metric]
+        with torch.cuda.device(dev):
+            for p0 in range(0, P, int(phrase_chunk)):
+                p1 = min(P, p0 + int(phrase_chunk))
+                b = self._phrase_blocks(lib, qd, lens, p0, p1, off, k, splits, block_phrases, pg)
+                ws = torch.empty(int(lib.sylber_dtw_workspace_bytes(b.nb, b.Pc, k, b.C)), dtype=torch.uint8, device=dev)
+                if _workspace_fill is not None:
+                    ws.fill_(_workspace_fill)
+                meta_d, sp_d, br_d, cut_d, pg_d = b.tables()
+                _lib.check(lib.sylber_dtw_occurrences(_vp(b.qp), b.nb, _vp(meta_d), _vp(sp_d), _vp(br_d), b.Pc, b.slots, _vp(self._x), N,
+                                                      self.dim, _vp(self._c), metric, k, _vp(seq_id), _vp(cut_d), b.C, _vp(pg_d),
+                                                      _vp(seq_grp), _vp(costs[p0:p1]), _vp(seqs[p0:p1]), _vp(spans[p0:p1]), _vp(ws),
+                                                      _stream(dev)), "sylber_dtw_occurrences")
+        return costs, seqs, spans
+
+    def search_occurrences_refined(self, phrases, k: int, refine: int = 4, storage: str = "fp16", *, lengths=None, groups=None,
+                                   exclude_same_group: bool = False, sequences=None, splits: int = 0,
+                                   phrase_chunk: int = DEFAULT_PHRASE_CHUNK, block_phrases: int = 0, return_candidates: bool = False,
+                                   _workspace_fill=None):
+        """two-stage ``search_occurrences``: stage 1 is ``search_phrases_refined``'s, unchanged -- the 16-bit MFMA scan picks
+        ``m = k * refine`` candidate *sequences* per phrase -- and stage 2 finds every occurrence in those sequences with the exact
+        fp32 recurrence (csrc/dtw16.hip, ``sylber_dtw_rerank_occurrences``) -> ``(costs, seqs, spans)`` as ``search_occurrences``
+        returns them; with ``return_candidates=True`` also ``cand`` int64 ``[P, m]`` and ``coarse`` fp32 ``[P, m]``, which are
+        ``search_phrases_refined``'s.
+
+        The result is ``search_occurrences`` restricted to the sequences of ``cand``, bit for bit, and with m at least the number
+        of admissible sequences of finite cost it *is* ``search_occurrences``.  The only approximation is which sequences are
+        searched: stage 1 ranks a sequence by its best match, so a sequence whose many occurrences are all mediocre can be left
+        out.  Nothing returned depends on ``splits``, ``phrase_chunk``, ``block_phrases``, stale workspace contents or how the
+        index was built.  Limits and refusals are ``search_phrases_refined``'s."""
+        k, m = _check_k_refine(k, refine, rerank=True)
+        if storage not in STORAGES:
+            raise ValueError("storage must be 'fp16' or 'bf16', got %r" % (storage,))
+        q, lens, pg, off = self._phrase_args(phrases, lengths, groups, exclude_same_group, sequences, splits, phrase_chunk, block_phrases)
+        P = int(lens.size)
+        dev = self.device
+        costs, seqs, spans = _phrase_outputs(P, k, dev)
+        cand = torch.empty((P, m), dtype=torch.int32, device=dev)
+        coarse = torch.empty((P, m), dtype=torch.float32, device=dev)
+        if P == 0:
+            return (costs, seqs, spans, cand.to(torch.int64), coarse) if return_candidates else (costs, seqs, spans)
+        x16 = self.half_rows(storage)
+        lib = _lib.load()
+        qd = self._prep(q)
+        N, S = len(self), off.size - 1
+        seq_id, seq_grp = self._sequence_tables(off, pg is not None)
+        off_d = _on_device(off, np.int32, dev)
+        metric, code = METRICS[self.metric], STORAGES[storage][0]
+        step = max(1, OCC_RERANK_ENTRIES // (m * k))                   # phrases per re-rank launch: bounds its m lists of k per phrase
+        with torch.cuda.device(dev):
+            st = _stream(dev)
+            for p0 in range(0, P, int(phrase_chunk)):
+                p1 = min(P, p0 + int(phrase_chunk))
+                b = self._phrase_blocks(lib, qd, lens, p0, p1, off, m, splits, block_phrases, pg)
+                qn = _row_norms(b.qp) if self.metric == "l2" else None
+                q16 = self._pack16(b.qp, storage, refuse=False)
+                ws = torch.empty(int(lib.sylber_dtw16_workspace_bytes(b.Pc, m, b.C)), dtype=torch.uint8, device=dev)
+                wo = torch.empty(int(lib.sylber_dtw_occ_workspace_bytes(min(step, b.Pc), m, k)), dtype=torch.uint8, device=dev)
+                if _workspace_fill is not None:
+                    ws.fill_(_workspace_fill)
+                    wo.fill_(_workspace_fill)
+                meta_d, sp_d, br_d, cut_d, pg_d = b.tables()
+                place_d, len_d = _on_device(b.place, np.int32, dev), _on_device(b.ln, np.int32, dev)
+                _lib.check(lib.sylber_dtw16_scan(_vp(q16), b.nb, _vp(meta_d), _vp(sp_d), _vp(br_d), b.Pc, b.slots, _vp(x16), N, self.dim,
+                                                 _vp(self._c), _vp(qn), metric, code, m, _vp(seq_id), _vp(cut_d), b.C, _vp(pg_d),
+                                                 _vp(seq_grp), _vp(cand[p0:p1]), _vp(coarse[p0:p1]), _vp(ws), st), "sylber_dtw16_scan")
+                for r0 in range(0, b.Pc, step):
+                    r1 = min(b.Pc, r0 + step)
+                    _lib.check(lib.sylber_dtw_rerank_occurrences(_vp(b.qp), b.nb, _vp(qn), _vp(place_d[r0:r1]), _vp(len_d[r0:r1]), r1 - r0,
+                                                                 _vp(self._x), N, self.dim, _vp(self._c), metric,
+                                                                 _vp(cand[p0 + r0:p0 + r1]), m, _vp(off_d), S, k,
+                                                                 _vp(costs[p0 + r0:p0 + r1]), _vp(seqs[p0 + r0:p0 + r1]),
+                                                                 _vp(spans[p0 + r0:p0 + r1]), _vp(wo), st),
+                               "sylber_dtw_rerank_occurrences")
         return (costs, seqs, spans, cand.to(torch.int64), coarse) if return_candidates else (costs, seqs, spans)
 
     def search_phrases_seeded(self, phrases, seed_scores, seed_ids, k: int, refine: int = 4, *, lengths=None, groups=None,

@@ -23,6 +23,12 @@ set of sequences); and the device bytes of each index.  The codebooks are the su
 k-means: the rows are independent gaussian, so training has no structure to find.  Codes, 16-bit codebooks and reconstruction norms
 are built before anything is timed.
 
+``--occurrences [--storage fp16|bf16] [--refine 4]`` adds the leg of "every occurrence" (``SyllableIndex.search_occurrences`` and
+``search_occurrences_refined``): in the same run, on the same phrases and index, the whole-call time of each beside its
+per-sequence sibling's (``occ_over_phrase`` = ``search_occurrences`` / ``search_phrases``, ``occ_refined_over_refined`` =
+``search_occurrences_refined`` / ``search_phrases_refined``: above 1 is slower), and the mean number of distinct sequences among a
+phrase's k occurrences.  It times ``search_phrases_refined`` itself when ``--refined`` is not given.
+
 ``--ivf [--nlist 4096] [--centres 20000] [--noise 0.3] [--configs 1:8:4,8:32:4,8:32:12,32:32:4,32:64:8]`` runs the leg of the phrase search
 through the inverted file (csrc/phrase_vote.hip, ``IVFSyllableIndex.search_phrases``) INSTEAD of the legs above, on data of its own:
 on independent gaussian rows recall of an inverted file means nothing, so the rows are the clustered mixture of tools/ivf_bench.py
@@ -164,6 +170,7 @@ def main():
     ap.add_argument("--refined", action="store_true")
     ap.add_argument("--storage", default="fp16", choices=["fp16", "bf16"])
     ap.add_argument("--refine", type=int, default=4)
+    ap.add_argument("--occurrences", action="store_true")
     ap.add_argument("--pq", action="store_true")
     ap.add_argument("--M", type=int, default=48)
     ap.add_argument("--ivf", action="store_true")
@@ -189,7 +196,7 @@ def main():
     groups = np.repeat(np.arange(lens.size), lens).astype(np.int32)
     idx = SyllableIndex(torch.randn(N, D, device=dev, generator=g), metric="l2", groups=groups, device=dev)
     idx.sequence_offsets()
-    if args.refined:
+    if args.refined or args.occurrences:
         idx.half_rows(args.storage)
     pq = None
     if args.pq:
@@ -225,6 +232,18 @@ def main():
                 row.update(storage=args.storage, refine=args.refine, refined_ms=round(t2, 2), refined_ms_min_max=[round(lo, 2), round(hi, 2)],
                            refined_over_phrase=round(t2 / t, 3), recovered_topk={r: v[0] for r, v in share.items()},
                            recovered_top1={r: v[1] for r, v in share.items()})
+            if args.occurrences:
+                ph, ln = q[:P * m], [m] * P
+                if not args.refined:
+                    t2, lo, hi = timed(lambda: idx.search_phrases_refined(ph, k, args.refine, args.storage, lengths=ln), args.iters)
+                    row.update(storage=args.storage, refine=args.refine, refined_ms=round(t2, 2), refined_ms_min_max=[round(lo, 2), round(hi, 2)])
+                t5, lo5, hi5 = timed(lambda: idx.search_occurrences(ph, k, lengths=ln), args.iters)
+                t6, lo6, hi6 = timed(lambda: idx.search_occurrences_refined(ph, k, args.refine, args.storage, lengths=ln), args.iters)
+                sq = idx.search_occurrences(ph, k, lengths=ln)[1].sort(1).values
+                distinct = 1 + (sq[:, 1:] != sq[:, :-1]).sum(1)
+                row.update(occ_ms=round(t5, 2), occ_ms_min_max=[round(lo5, 2), round(hi5, 2)], occ_over_phrase=round(t5 / t, 3),
+                           occ_refined_ms=round(t6, 2), occ_refined_ms_min_max=[round(lo6, 2), round(hi6, 2)],
+                           occ_refined_over_refined=round(t6 / t2, 3), occ_distinct_sequences=round(float(distinct.float().mean()), 2))
             if pq is not None:
                 t3, lo3, hi3 = timed(lambda: pq.search_phrases(ph, k, args.refine, args.storage, lengths=ln, rerank=True), args.iters)
                 t4, lo4, hi4 = timed(lambda: pq.search_phrases(ph, k, args.refine, args.storage, lengths=ln, rerank=False), args.iters)
