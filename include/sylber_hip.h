@@ -480,6 +480,42 @@ int sylber_dtw_rerank_occurrences(const float* q_dev, int32_t n_blocks, const fl
                                   const int32_t* seq_offsets_dev, int32_t n_seq, int32_t k, float* cost_dev, int64_t* seq_dev,
                                   int64_t* span_dev, void* workspace_dev, void* stream);
 
+/* Warping paths (sylber_amd/search.py: SyllableIndex.align_phrases; restated in tests/align_ref.py): HOW a phrase matches a
+ * window of rows -- which stored rows each phrase row is warped onto -- where the searches above report only where.  For one pair
+ * (phrase of m rows, window [a, b) of row ids, W = b - a):
+ *   Window DP.  The local costs d[i][j] are sylber_dtw_search's, bit for bit (the ascending fmaf chain from 0 over D of
+ *   sylber_dtw_rerank, then the same d).  The window is taken as ONE sequence whose first column is a: a free start (A[0][j] =
+ *   d[0][j] for every column of the window) and a forced end: the path ends in cell (m-1, b-1).  The recurrence and the predecessor
+ *   order on ties are sylber_dtw_search's, unchanged: diagonal, then (i-1, j), then (i, j-1).
+ *   Path and outputs.  The path is the chain of predecessors taken from (m-1, b-1) back to the row-0 cell it reaches.  cost =
+ *   A[m-1][b-1]; steps = the number of cells on the path; rows[i] = (first row id, one past the last row id) of the run of columns
+ *   the path visits in phrase row i.  A monotone path visits one contiguous run per row and lo[i+1] is hi[i] or hi[i] + 1, so the
+ *   runs ARE the path.  If A[m-1][b-1] is not below +inf the pair is padding on output: rows (-1, -1), steps 0, cost +inf.
+ *   The theorem.  If [a, b) is a span that a phrase search of this library returned for that phrase under the same metric and rows,
+ *   then (1) the path starts in column a, (2) cost has the bits of the reported cost, (3) the path is the full scan's own path.
+ *   Why: every window cell's A is at least the full DP's (it is a minimum over fewer paths and fp32 + is monotone), and on the
+ *   optimal path the two are equal, so at every cell of that path the first smallest predecessor is the same one.
+ *   tests/test_align_ref.py holds it on random, tied and +inf-holed matrices.  So no scan had to keep its path.
+ *   Any other window is legal and gets what the definition gives; its path may start inside the window.  steps is the divisor of
+ *   a length-normalised DTW cost: cost / steps.
+ *   Nothing returned depends on how pairs are chunked or on what the workspace held.
+ * sylber_dtw_align: q_dev, n_blocks, q_norm_dev, phrase_row_dev, phrase_len_dev, n_phrases, db_dev, N, D, db_norm_dev, metric as
+ *   for sylber_dtw_rerank.  pair_phrase_dev [n_pairs] int32: the phrase of each pair; pair_window_dev [n_pairs, 2] int32: (a, b),
+ *   (-1, -1) = none; max_cols: no window is longer (1 .. 65 536); max_rows: the row pitch Mx of rows_dev, at least the longest
+ *   phrase (1 .. 64).  rows_dev [n_pairs, max_rows, 2] int32, (-1, -1) for i >= m and for padding; steps_dev [n_pairs] int32;
+ *   cost_dev [n_pairs] fp32; start_dev [n_pairs] int32, may be null: the start row that the walk itself tracked for (m-1, b-1),
+ *   as sylber_dtw_rerank tracks it (-1 for padding) -- always rows_dev[pair][0][0]; a check of the codes, not a result.  workspace_dev: sylber_dtw_align_workspace_bytes(n_pairs, max_cols) = 16 B x (max_cols + 63) per pair
+ *   (-1 on a bad argument): 2 bits per cell for the predecessor taken.  Bad arguments and max_cols > 65 536 return 1 with
+ *   sylber_last_error before any device call.  The windows are device data that the entry cannot see: the caller validates them
+ *   (align_phrases does, with one reduction, before any launch), and a pair whose window lies outside [0, N], is empty or is longer
+ *   than max_cols reads and writes nothing beyond its outputs, which are padding. */
+int64_t sylber_dtw_align_workspace_bytes(int32_t n_pairs, int32_t max_cols);
+int sylber_dtw_align(const float* q_dev, int32_t n_blocks, const float* q_norm_dev, const int32_t* phrase_row_dev,
+                     const int32_t* phrase_len_dev, int32_t n_phrases, const float* db_dev, int32_t N, int32_t D, const float* db_norm_dev,
+                     int32_t metric, const int32_t* pair_phrase_dev, const int32_t* pair_window_dev, int32_t n_pairs, int32_t max_cols,
+                     int32_t max_rows, int32_t* rows_dev, int32_t* steps_dev, float* cost_dev, int32_t* start_dev, void* workspace_dev,
+                     void* stream);
+
 /* Compressed phrase search (sylber_amd/pq.py: PQSyllableIndex.search_phrases): sylber_dtw16_scan with the database given as
  * product-quantization codes.  codes_dev [N, M] uint8 and bad_dev [N] uint8 (nullable; 1 = a masked row) as sylber_pq_encode writes
  * them; codebooks16_dev [M, 256, D / M] = sylber_knn16_pack of the fp32 codebooks in `storage`; 1 <= M <= 64, D % M == 0,

@@ -39,7 +39,7 @@ from ._index import (DEFAULT_PHRASE_CHUNK, DEFAULT_QUERY_CHUNK, METRICS, STORAGE
                      _phrase_args, _phrase_blocks, _phrase_outputs, _prep, _provenance, _query_groups, _result, _row_norms, _rows,
                      _rows_of_width, _sequence_tables)
 from .kmeans import _device, _stream, _vp
-from .search import IVFSyllableIndex, SyllableIndex
+from .search import IVFSyllableIndex, SyllableIndex, _align_launch, _align_phrases
 
 KSUB = 256                      # centroids per sub-space: one uint8 per code
 MAX_M = 64                      # PQ_MAX_M of csrc/pq.hip: at least two queries' tables (M KiB each) fit beside the top lists in LDS
@@ -555,6 +555,66 @@ class PQSyllableIndex:
             sc = s_out.clamp(min=0)
             sp_out.copy_(torch.where(hit[:, :, None], sp_out - coff_d[sc][:, :, None] + roff_d[sc][:, :, None], sp_out))
             s_out.copy_(torch.where(hit, uniq_d[sc], s_out))
+
+    def align_phrases(self, phrases, spans, lengths=None, pair_chunk: Optional[int] = None, *, rerank: Optional[bool] = None,
+                      scratch_rows: int = DEFAULT_SCRATCH_ROWS, _tracked_start: bool = False):
+        """the warping paths behind the spans of ``search_phrases`` -> ``(rows, steps, costs)`` as ``SyllableIndex.align_phrases``
+        returns them; ``rerank`` is what that search was given.  ``rerank=True`` (the default while the fp32 rows are held;
+        ``ValueError`` once they are dropped): ``pq.index.align_phrases``, on the rows the exact re-rank ran on.  ``rerank=False``
+        (the only mode after ``drop_rows()``): the same alignment (csrc/dtw_align.hip) on the *decoded* rows of the windows, a
+        masked row being a NaN row, as ``search_phrases(rerank=False)`` re-ranks -- so on spans from that search ``costs`` has the
+        bits of its costs, and the result is ``SyllableIndex(pq.decode(arange(N)), ...).align_phrases``'s.  Per chunk of pairs the
+        windows are decoded into a compact scratch of at most ``scratch_rows`` rows (one window at least; the call waits to learn
+        the widths) and the row ids are mapped back on the device.  Nothing returned depends on ``pair_chunk``, ``scratch_rows``
+        or, with ``rerank=False``, on whether the rows are still held."""
+        if rerank is None:
+            rerank = self.index is not None
+        if rerank and self.index is None:
+            raise ValueError("rerank=True needs the fp32 rows, which were dropped: align with rerank=False")
+        if isinstance(scratch_rows, bool) or int(scratch_rows) != scratch_rows or int(scratch_rows) < 1:
+            raise ValueError("scratch_rows must be an integer >= 1, got %r" % (scratch_rows,))
+        N, D, dev = len(self), self.dim, self.device
+        if rerank:
+            if len(self.index) != N:
+                raise ValueError("pq.index holds %d rows, the codes %d: add rows through pq.add" % (len(self.index), N))
+            return self.index.align_phrases(phrases, spans, lengths=lengths, pair_chunk=pair_chunk, _tracked_start=_tracked_start)
+        metric = METRICS[self.metric]
+
+        def run(lib, b, qn, place_d, len_d, pair_phrase, win, max_cols, rows, steps, costs, start, ws, st):
+            w64 = win.to(torch.int64)
+            width = w64[:, 1] - w64[:, 0]                       # 0 for padding
+            width_h = width.cpu().numpy()
+            cuts, have = [0], 0                                 # runs of pairs whose windows hold at most scratch_rows rows together
+            for i, w in enumerate(width_h.tolist()):
+                if i > cuts[-1] and have + w > int(scratch_rows):
+                    cuts.append(i)
+                    have = 0
+                have += w
+            cuts.append(len(width_h))
+            rnorm = self._recon_norms()
+            for g0, g1 in zip(cuts[:-1], cuts[1:]):
+                R = int(width_h[g0:g1].sum())
+                if R == 0:                                      # nothing but padding: the outputs hold it already
+                    continue
+                wd, a = width[g0:g1], w64[g0:g1, 0]
+                coff = torch.zeros(g1 - g0 + 1, dtype=torch.int64, device=dev)
+                coff[1:] = torch.cumsum(wd, 0)
+                owner = torch.repeat_interleave(torch.arange(g1 - g0, device=dev), wd)
+                rid = a[owner] + (torch.arange(R, device=dev) - coff[owner])                   # the real row of every scratch row
+                x = _decode(self._codes.index_select(0, rid), self.codebooks)
+                x = torch.where((self._bad.index_select(0, rid) != 0)[:, None], torch.full_like(x, float("nan")), x)
+                cn = rnorm.index_select(0, rid) if rnorm is not None else None
+                cwin = torch.stack([coff[:-1], coff[1:]], 1)
+                cwin = torch.where((wd == 0)[:, None], torch.full_like(cwin, -1), cwin).to(torch.int32).contiguous()
+                r, s0 = rows[g0:g1], (start[g0:g1] if start is not None else None)
+                _align_launch(lib, b, qn, place_d, len_d, x, R, D, cn, metric, pair_phrase[g0:g1], cwin, max_cols, r, steps[g0:g1],
+                              costs[g0:g1], s0, ws, st)
+                shift = (a - coff[:-1]).to(torch.int32)
+                r.copy_(torch.where(r >= 0, r + shift[:, None, None], r))
+                if s0 is not None:
+                    s0.copy_(torch.where(s0 >= 0, s0 + shift, s0))
+
+        return _align_phrases(N, D, dev, self.metric, phrases, spans, lengths, pair_chunk, run, _tracked_start)
 
     # ---- persistence ----------------------------------------------------------------------------------------------------------------
     def save(self, path: str) -> None:

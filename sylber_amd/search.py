@@ -19,6 +19,8 @@ candidate sequences without a scan of the corpus: each phrase row's neighbours f
 ``SyllableIndex.search_phrases_seeded`` is the vote and the re-rank on seeds from anywhere; tests/phrase_vote_ref.py).
 ``SyllableIndex.search_occurrences`` / ``search_occurrences_refined`` return every non-overlapping occurrence of a phrase instead of one
 match per sequence (``sylber_dtw_occurrences``, ``sylber_dtw_rerank_occurrences``; tests/occ_ref.py).
+``align_phrases`` takes the spans of any of them and returns the warping path of each match: the stored rows every phrase row was
+aligned to (csrc/dtw_align.hip, ``sylber_dtw_align``; tests/align_ref.py).
 
 The rules that every index shares -- argument checks, row preparation, result buffers, provenance, the list layout, the arrays of a
 saved file -- are in _index.py, each once; this file and pq.py hold what differs between the indexes.
@@ -42,6 +44,78 @@ from .kmeans import _device, _stream, _vp
 
 RERANK_CHUNK = 32               # DT_RR_CH of csrc/dtw16.hip: the columns of a sequence that search_phrases_refined re-ranks at a time
 OCC_RERANK_ENTRIES = 1 << 24    # list entries (24 B each with the merge rounds' half) of one sylber_dtw_rerank_occurrences launch
+MAX_WINDOW_ROWS = 65536         # DA_MAX_COLS of csrc/dtw_align.hip: the rows of a window that align_phrases walks (= MAX_SEQUENCE_ROWS)
+ALIGN_WORKSPACE_BYTES = 256 << 20       # the default pair_chunk of align_phrases keeps its workspace below this
+
+
+# ---- warping paths: what SyllableIndex.align_phrases and PQSyllableIndex.align_phrases share ---------------------------------------
+def _align_spans(spans, P: int, N: int, device) -> Tuple[torch.Tensor, int]:
+    """the checks of ``align_phrases`` on ``spans`` -> ``(spans int64 [P, k, 2] on the device, the widest window)``, or ``ValueError``;
+    one reduction on the device and one copy of two numbers to the host"""
+    sp = spans if torch.is_tensor(spans) else torch.from_numpy(np.asarray(spans))
+    if sp.dtype != torch.int64 or sp.dim() != 3 or sp.shape[0] != P or sp.shape[2] != 2:
+        raise ValueError("spans must be int64 [%d phrases, k, 2], got %s %s" % (P, sp.dtype, tuple(sp.shape)))
+    sp = sp.to(device).contiguous()
+    if sp.numel() == 0:
+        return sp, 0
+    a, b = sp[..., 0], sp[..., 1]
+    pad = (a == -1) & (b == -1)
+    ok = pad | ((a >= 0) & (a < b) & (b <= N))
+    width = torch.where(ok & ~pad, b - a, torch.zeros_like(a))
+    bad, widest = torch.stack([(~ok).sum(), width.max()]).cpu().tolist()
+    if bad:
+        raise ValueError("%d spans are neither (-1, -1) nor 0 <= first < one past the last <= %d rows" % (bad, N))
+    if widest > MAX_WINDOW_ROWS:
+        raise ValueError("a window has %d rows, more than %d" % (widest, MAX_WINDOW_ROWS))
+    return sp, int(widest)
+
+
+def _align_launch(lib, b: "_PhraseBlocks", qn, place_d, len_d, x, N: int, D: int, cn, metric: int, pair_phrase, win, max_cols: int,
+                  rows, steps, costs, start, ws, st) -> None:
+    """``sylber_dtw_align`` for the pairs ``(pair_phrase [n] int32, win [n, 2] int32)`` against the rows ``x [N, D]`` with norms ``cn``
+    into ``rows [n, Mx, 2]`` int32, ``steps [n]``, ``costs [n]`` and, unless it is None, ``start [n]`` int32"""
+    _lib.check(lib.sylber_dtw_align(_vp(b.qp), b.nb, _vp(qn), _vp(place_d), _vp(len_d), b.Pc, _vp(x), N, D, _vp(cn), metric, _vp(pair_phrase),
+                                    _vp(win), int(pair_phrase.shape[0]), max_cols, int(rows.shape[1]), _vp(rows), _vp(steps), _vp(costs),
+                                    _vp(start), _vp(ws), st), "sylber_dtw_align")
+
+
+def _align_phrases(N: int, dim: int, dev, metric: str, phrases, spans, lengths, pair_chunk, run, tracked: bool = False):
+    """``align_phrases`` of an index of N rows of width ``dim``: the checks, the phrase rows prepared and packed as ``search_phrases``
+    packs them, the pairs taken ``pair_chunk`` at a time.  ``run(lib, b, qn, place_d, len_d, pair_phrase, win, max_cols, rows,
+    steps, costs, start, ws, st)`` aligns one chunk against the index's rows, however it holds them.  ``tracked`` (a test hook):
+    also return ``start`` int64 ``[P, k]``, the start row that the kernel's walk tracked as the re-rank tracks it (-1 for padding),
+    which must equal ``rows[:, :, 0, 0]``."""
+    # a window is its own sequence: the sequences of the search do not enter, so neither do their checks (one dummy sequence)
+    q, lens, _, _ = _phrase_args(N, dim, dev, lambda: np.zeros(2, np.int64), phrases, lengths, None, False, None, 0, 1, 0)
+    if pair_chunk is not None and (isinstance(pair_chunk, bool) or int(pair_chunk) != pair_chunk or int(pair_chunk) < 1):
+        raise ValueError("pair_chunk must be an integer >= 1, got %r" % (pair_chunk,))
+    P = int(lens.size)
+    sp, widest = _align_spans(spans, P, N, dev)
+    k, Mx = int(sp.shape[1]), (int(lens.max()) if P else 0)
+    n = P * k
+    rows = torch.full((n, Mx, 2), -1, dtype=torch.int32, device=dev)
+    steps = torch.zeros(n, dtype=torch.int32, device=dev)
+    costs = torch.full((n,), float("inf"), dtype=torch.float32, device=dev)
+    start = torch.full((n,), -1, dtype=torch.int32, device=dev) if tracked else None
+    if n and widest:                                        # else: nothing but padding, and no launch
+        lib = _lib.load()
+        qd = _prep(q, metric, dev)
+        b = _phrase_blocks(lib, dev, qd, lens, 0, P, np.array([0, 1], np.int64), 1, 0, 0, None)      # the packing alone: no cut is used
+        qn = _row_norms(b.qp) if metric == "l2" else None   # the ||q||^2 that sylber_dtw_search adds, same kernel
+        place_d, len_d = _on_device(b.place, np.int32, dev), _on_device(b.ln, np.int32, dev)
+        pair_phrase = torch.arange(P, dtype=torch.int32, device=dev).repeat_interleave(k)
+        win = sp.reshape(n, 2).to(torch.int32)
+        step = int(pair_chunk) if pair_chunk is not None else max(1, ALIGN_WORKSPACE_BYTES // (16 * (widest + 63)))
+        step = min(step, n)
+        with torch.cuda.device(dev):
+            st = _stream(dev)
+            ws = torch.empty(int(lib.sylber_dtw_align_workspace_bytes(step, widest)), dtype=torch.uint8, device=dev)
+            for r0 in range(0, n, step):
+                r1 = min(n, r0 + step)
+                run(lib, b, qn, place_d, len_d, pair_phrase[r0:r1], win[r0:r1], widest, rows[r0:r1], steps[r0:r1], costs[r0:r1],
+                    start[r0:r1] if tracked else None, ws, st)
+    out = (rows.to(torch.int64).reshape(P, k, Mx, 2), steps.reshape(P, k), costs.reshape(P, k))
+    return out + (start.to(torch.int64).reshape(P, k),) if tracked else out
 
 
 class SyllableIndex:
@@ -554,8 +628,46 @@ class SyllableIndex:
                                                  _vp(seqs[p0:p1]), _vp(spans[p0:p1]), _vp(ws), st), "sylber_dtw_rerank")
         return (costs, seqs, spans, cand.to(torch.int64), bound) if return_candidates else (costs, seqs, spans)
 
+    # ---- warping paths -------------------------------------------------------------------------------------------------------------
+    def align_phrases(self, phrases, spans, lengths=None, pair_chunk: Optional[int] = None, *, _tracked_start: bool = False):
+        """*how* each phrase matches each of its spans: the stored rows every phrase row was warped onto ->
+        ``(rows int64 [P, k, Mx, 2], steps int32 [P, k], costs fp32 [P, k])`` on the device, ``Mx = max_p m_p``.  ``phrases`` and
+        ``lengths=`` are exactly what the search that produced ``spans`` was given; ``spans`` int64 ``[P, k, 2]`` (host or device):
+        (first row id, one past the last), ``(-1, -1)`` = padding -- the spans of ``search_phrases``, ``search_phrases_refined``,
+        ``search_phrases_seeded``, ``search_occurrences`` or ``search_occurrences_refined``, or any windows of your own.
+        ``rows[p, r, i]`` = (first row id, one past the last row id) of the stored rows that phrase row i is aligned to, so
+        ``provenance`` works on it; ``(-1, -1)`` for ``i >= m_p``, for padding spans and for pairs of cost ``+inf``.  ``steps``: the
+        cells on the path, 0 where ``rows`` is all padding; ``costs``: the DP's cost of that path, ``+inf`` there
+        (csrc/dtw_align.hip, ``sylber_dtw_align``; restated in tests/align_ref.py).
+
+        Window DP, for one pair (phrase of m rows, window ``[a, b)``): the local costs ``d[i][j]`` are ``search_phrases``'s, bit for
+        bit (phrase rows prepared as there: unit rows under ``"cosine"``); the window is taken as **one** sequence whose first
+        column is ``a``, with a free start (``A[0][j] = d[0][j]`` for every column of the window) and a forced end: the path ends in
+        cell ``(m-1, b-1)``; recurrence and predecessor order on ties are ``search_phrases``'s: diagonal, then ``(i-1, j)``, then
+        ``(i, j-1)``.  The path is the chain of predecessors from ``(m-1, b-1)`` back to the row-0 cell it reaches; ``costs =
+        A[m-1][b-1]``; ``rows[i]`` is the run of columns the path visits in phrase row i (a monotone path visits one contiguous run
+        per row and ``lo[i+1]`` is ``hi[i]`` or ``hi[i] + 1``, so the runs *are* the path).
+
+        The theorem: if ``[a, b)`` is a span a phrase search of this index returned for that phrase, the path starts in column
+        ``a``, ``costs`` has the bits of the reported cost, and the path is the full scan's own path (every window cell's ``A`` is
+        at least the full DP's -- fewer paths, monotone fp32 ``+`` -- and equal on the optimal path, so the first smallest
+        predecessor is the same one).  Any other window is legal and gets what the definition gives; its path may start inside it.
+
+        ``costs / steps`` is the length-normalised DTW cost: ``steps`` is the divisor that belongs under a DTW sum.  Nothing
+        returned depends on ``pair_chunk`` (the pairs per launch; by default the workspace, 16 B per window column and pair, stays
+        below 256 MiB), on stale workspace contents, on one ``add`` against many or on a ``save`` / ``load`` round trip.
+        ``ValueError`` before any launch: what ``search_phrases`` refuses of the phrases; ``spans`` of another shape or dtype; a
+        span that is neither ``(-1, -1)`` nor ``0 <= a < b <= N``; a window of more than 65 536 rows."""
+        N = len(self)
+
+        def run(lib, b, qn, place_d, len_d, pair_phrase, win, max_cols, rows, steps, costs, start, ws, st):
+            _align_launch(lib, b, qn, place_d, len_d, self._x, N, self.dim, self._c, METRICS[self.metric], pair_phrase, win, max_cols,
+                          rows, steps, costs, start, ws, st)
+
+        return _align_phrases(N, self.dim, self.device, self.metric, phrases, spans, lengths, pair_chunk, run, _tracked_start)
+
     # the arguments and the plumbing that every phrase search shares: _index.py holds them, these keep their names
-    def _phrase_args(self, phrases, lengths, groups, exclude_same_group, sequences, splits, phrase_chunk, block_phrases):
+    def _phrase_args(self,phrases, lengths, groups, exclude_same_group, sequences, splits, phrase_chunk, block_phrases):
         """the checks of a phrase search -> ``(phrase rows [sum m, D] as given, lengths int64 [P], the phrases' groups on the host or
         None, sequence offsets int64 [S + 1])``, or ``ValueError``"""
         return _phrase_args(len(self), self.dim, self.device, self.sequence_offsets, phrases, lengths, groups, exclude_same_group,
@@ -831,6 +943,11 @@ class IVFSyllableIndex:
         return idx.search_phrases_seeded(q, sc, si, k, refine, lengths=lens, groups=groups, exclude_same_group=exclude_same_group,
                                          sequences=sequences, phrase_chunk=phrase_chunk, return_candidates=return_candidates,
                                          _trusted_ids=True)
+
+    def align_phrases(self, phrases, spans, lengths=None, pair_chunk: Optional[int] = None):
+        """the warping paths behind the spans of ``search_phrases``: ``ivf.index.align_phrases``, whose rows (in id order) are the
+        ones the exact re-rank ran on -> ``(rows, steps, costs)`` as there"""
+        return self.index.align_phrases(phrases, spans, lengths=lengths, pair_chunk=pair_chunk)
 
     # ---- persistence ----------------------------------------------------------------------------------------------------------------
     def save(self, path: str) -> None:

@@ -29,6 +29,12 @@ per-sequence sibling's (``occ_over_phrase`` = ``search_occurrences`` / ``search_
 ``search_occurrences_refined`` / ``search_phrases_refined``: above 1 is slower), and the mean number of distinct sequences among a
 phrase's k occurrences.  It times ``search_phrases_refined`` itself when ``--refined`` is not given.
 
+``--align [--storage fp16|bf16] [--refine 4]`` adds the leg of the warping paths (csrc/dtw_align.hip, ``SyllableIndex.align_phrases``):
+in the same run, on the same phrases and index, the whole-call time of ``align_phrases`` on the spans that the timed
+``search_phrases_refined`` call returns, beside that call's time (``align_over_refined`` = ``align_phrases`` / ``search_phrases_refined``),
+with the number of pairs aligned, the spans' mean width and the paths' mean number of cells.  It times ``search_phrases_refined``
+itself when neither ``--refined`` nor ``--occurrences`` is given.
+
 ``--ivf [--nlist 4096] [--centres 20000] [--noise 0.3] [--configs 1:8:4,8:32:4,8:32:12,32:32:4,32:64:8]`` runs the leg of the phrase search
 through the inverted file (csrc/phrase_vote.hip, ``IVFSyllableIndex.search_phrases``) INSTEAD of the legs above, on data of its own:
 on independent gaussian rows recall of an inverted file means nothing, so the rows are the clustered mixture of tools/ivf_bench.py
@@ -171,6 +177,7 @@ def main():
     ap.add_argument("--storage", default="fp16", choices=["fp16", "bf16"])
     ap.add_argument("--refine", type=int, default=4)
     ap.add_argument("--occurrences", action="store_true")
+    ap.add_argument("--align", action="store_true")
     ap.add_argument("--pq", action="store_true")
     ap.add_argument("--M", type=int, default=48)
     ap.add_argument("--ivf", action="store_true")
@@ -196,7 +203,7 @@ def main():
     groups = np.repeat(np.arange(lens.size), lens).astype(np.int32)
     idx = SyllableIndex(torch.randn(N, D, device=dev, generator=g), metric="l2", groups=groups, device=dev)
     idx.sequence_offsets()
-    if args.refined or args.occurrences:
+    if args.refined or args.occurrences or args.align:
         idx.half_rows(args.storage)
     pq = None
     if args.pq:
@@ -244,6 +251,18 @@ def main():
                 row.update(occ_ms=round(t5, 2), occ_ms_min_max=[round(lo5, 2), round(hi5, 2)], occ_over_phrase=round(t5 / t, 3),
                            occ_refined_ms=round(t6, 2), occ_refined_ms_min_max=[round(lo6, 2), round(hi6, 2)],
                            occ_refined_over_refined=round(t6 / t2, 3), occ_distinct_sequences=round(float(distinct.float().mean()), 2))
+            if args.align:
+                ph, ln = q[:P * m], [m] * P
+                if not (args.refined or args.occurrences):
+                    t2, lo, hi = timed(lambda: idx.search_phrases_refined(ph, k, args.refine, args.storage, lengths=ln), args.iters)
+                    row.update(storage=args.storage, refine=args.refine, refined_ms=round(t2, 2), refined_ms_min_max=[round(lo, 2), round(hi, 2)])
+                spans = idx.search_phrases_refined(ph, k, args.refine, args.storage, lengths=ln)[2]
+                t7, lo7, hi7 = timed(lambda: idx.align_phrases(ph, spans, lengths=ln), args.iters)
+                steps = idx.align_phrases(ph, spans, lengths=ln)[1]
+                hit = spans[:, :, 0] >= 0
+                row.update(align_ms=round(t7, 2), align_ms_min_max=[round(lo7, 2), round(hi7, 2)], align_over_refined=round(t7 / t2, 3),
+                           align_pairs=int(hit.sum()), span_mean_width=round(float((spans[:, :, 1] - spans[:, :, 0])[hit].float().mean()), 2),
+                           path_mean_steps=round(float(steps[hit].float().mean()), 2))
             if pq is not None:
                 t3, lo3, hi3 = timed(lambda: pq.search_phrases(ph, k, args.refine, args.storage, lengths=ln, rerank=True), args.iters)
                 t4, lo4, hi4 = timed(lambda: pq.search_phrases(ph, k, args.refine, args.storage, lengths=ln, rerank=False), args.iters)
