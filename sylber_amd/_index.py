@@ -1,7 +1,7 @@
 """The host rules that the four syllable indexes share (search.py: ``SyllableIndex``, ``IVFSyllableIndex``; pq.py: ``PQSyllableIndex``,
 ``IVFPQSyllableIndex``), each written once: what a search accepts (``k`` / ``refine``, ``nprobe``, ``splits`` / ``query_chunk``, query
-rows, query groups; the arguments, sequences and packed blocks of a phrase search), how rows are stored (``_prep``, ``_row_norms``,
-``_pack16``), where a search puts its results, what ``provenance`` answers, how
+rows, query groups; the arguments, sequences and packed blocks of a phrase search and the host loop of the ones that scan the corpus,
+``_scan_phrases``), how rows are stored (``_prep``, ``_row_norms``, ``_pack16``), where a search puts its results, what ``provenance`` answers, how
 rows are sorted into lists, and how the common arrays reach an ``.npz`` and come back.  Private: the classes are the public surface."""
 from __future__ import annotations
 
@@ -176,8 +176,9 @@ def _list_layout(labels: torch.Tensor, nlist: int) -> Tuple[torch.Tensor, torch.
 
 
 # ---- phrase searches ----------------------------------------------------------------------------------------------------------------
-# What SyllableIndex.search_phrases / search_phrases_refined and PQSyllableIndex.search_phrases share.  An index enters only as
-# (N rows, width dim, device, the rows' groups on the device).
+# What the phrase searches share: SyllableIndex.search_phrases, search_phrases_refined, search_occurrences,
+# search_occurrences_refined and PQSyllableIndex.search_phrases (all five through _scan_phrases below), search_phrases_seeded and the
+# two align_phrases.  An index enters only as (N rows, width dim, device, metric, the rows' groups on the device).
 def _phrase_outputs(P: int, k: int, device):
     """``(costs fp32 [P, k], seqs int64 [P, k], spans int64 [P, k, 2])`` of a phrase search"""
     return (torch.empty((P, k), dtype=torch.float32, device=device), torch.empty((P, k), dtype=torch.int64, device=device),
@@ -296,6 +297,77 @@ def _phrase_blocks(lib, dev, qd, lens, p0: int, p1: int, off, list_size: int, sp
     qp[torch.from_numpy(first + local).to(dev)] = qd[r0:r0 + R]
     return _PhraseBlocks(dev, Pc, nb, C, int(slot.max()) + 1, place, ln, qp, meta, slot_phrase, block_rows, cut_rows,
                          pg[p0:p1] if pg is not None else None)
+
+
+class _PhraseChunk:
+    """what ``_scan_phrases`` hands to the stages of a search.  For the whole call: ``lib, dev, st`` (the stream), ``N, dim, metric``
+    (its code), ``k``, ``m`` (entries per list in stage 1: ``k``, or ``k * refine``), ``off, off_d`` (``off_d``: two-stage only),
+    ``S, seq_id, seq_grp``.  For the chunk: ``b`` (its ``_PhraseBlocks``), ``meta_d, sp_d, br_d, cut_d, pg_d`` (``b.tables()``) and
+    the chunk's slices ``costs, seqs, spans``; two-stage searches also get ``place_d, len_d, qn`` (the ``||q||^2`` that
+    ``sylber_dtw_search`` adds, same kernel; ``None`` under "cosine"), ``q16`` (the packed rows in 16 bits), ``cand, coarse`` and
+    ``ws``: stage 1 leaves its workspace there for stage 2."""
+
+    def __init__(self, fill, **whole_call):
+        self._fill = fill
+        self.__dict__.update(whole_call)
+
+    def part(self, **changed) -> "_PhraseChunk":
+        """a copy with these attributes replaced: some of the chunk's phrases, or other rows to re-rank on"""
+        c = _PhraseChunk(self._fill, **self.__dict__)
+        c.__dict__.update(changed)
+        return c
+
+    def workspace(self, nbytes) -> torch.Tensor:
+        """``nbytes`` of workspace; a test's ``_workspace_fill`` reaches every workspace of the call through here"""
+        ws = torch.empty(int(nbytes), dtype=torch.uint8, device=self.dev)
+        if self._fill is not None:
+            ws.fill_(self._fill)
+        return ws
+
+
+def _scan_phrases(N: int, dim: int, dev, metric: str, db_groups, default_sequences, stages, phrases, k, refine, storage, lengths, groups,
+                  exclude_same_group, sequences, splits, phrase_chunk, block_phrases, return_candidates, workspace_fill):
+    """the host loop of every phrase search that scans the corpus: the checks in their order (``k`` / ``refine`` / ``storage``, then
+    ``_phrase_args``), the outputs, the return for no phrase, the prepared rows, the sequence tables and, ``phrase_chunk`` phrases
+    at a time, the packed blocks with their tables -> ``(costs, seqs, spans)``, and ``cand`` int64, ``coarse`` with
+    ``return_candidates``.  ``refine=None``: one stage with lists of ``k`` (``storage`` and ``return_candidates`` unused); else two
+    with ``m = k * refine`` candidates.  ``stages()`` is called once, behind every check and before anything is launched (it may
+    still refuse, e.g. values that fp16 cannot hold) -> ``(scan, rerank)``: ``scan(c)`` launches stage 1 of the chunk ``c`` (a
+    ``_PhraseChunk``) -- into ``c.costs, c.seqs, c.spans`` when it is the only stage, else into ``c.cand, c.coarse`` -- and
+    ``rerank(c)`` (``None`` with one stage) stage 2, inside the loop: it may read the chunk's ``cand`` on the host."""
+    two = refine is not None
+    k, m = _check_k_refine(k, refine, rerank=True) if two else _check_k_refine(k)
+    if two and storage not in STORAGES:
+        raise ValueError("storage must be 'fp16' or 'bf16', got %r" % (storage,))
+    q, lens, pg, off = _phrase_args(N, dim, dev, default_sequences, phrases, lengths, groups, exclude_same_group, sequences, splits,
+                                    phrase_chunk, block_phrases)
+    P = int(lens.size)
+    costs, seqs, spans = _phrase_outputs(P, k, dev)
+    cand = torch.empty((P, m), dtype=torch.int32, device=dev) if two else None
+    coarse = torch.empty((P, m), dtype=torch.float32, device=dev) if two else None
+    if P:
+        scan, rerank = stages()
+        lib = _lib.load()
+        qd = _prep(q, metric, dev)
+        seq_id, seq_grp = _sequence_tables(off, db_groups if pg is not None else None, dev)
+        c = _PhraseChunk(workspace_fill, lib=lib, dev=dev, N=N, dim=dim, metric=METRICS[metric], k=k, m=m, off=off, S=off.size - 1,
+                         off_d=_on_device(off, np.int32, dev) if two else None, seq_id=seq_id, seq_grp=seq_grp)
+        with torch.cuda.device(dev):
+            c.st = _stream(dev)
+            for p0 in range(0, P, int(phrase_chunk)):
+                p1 = min(P, p0 + int(phrase_chunk))
+                c.b = b = _phrase_blocks(lib, dev, qd, lens, p0, p1, off, m, splits, block_phrases, pg)
+                c.meta_d, c.sp_d, c.br_d, c.cut_d, c.pg_d = b.tables()
+                c.costs, c.seqs, c.spans = costs[p0:p1], seqs[p0:p1], spans[p0:p1]
+                if two:
+                    c.place_d, c.len_d = _on_device(b.place, np.int32, dev), _on_device(b.ln, np.int32, dev)
+                    c.qn = _row_norms(b.qp) if metric == "l2" else None
+                    c.q16 = _pack16(b.qp, storage, refuse=False)
+                    c.cand, c.coarse = cand[p0:p1], coarse[p0:p1]
+                scan(c)
+                if two:
+                    rerank(c)
+    return (costs, seqs, spans, cand.to(torch.int64), coarse) if two and return_candidates else (costs, seqs, spans)
 
 
 # ---- results -----------------------------------------------------------------------------------------------------------------------

@@ -15,14 +15,15 @@
 //     kernel on the materialised plane.  The C partial lists of a phrase are merged by knn_lists.h's merge; the host path is
 //     dtw16_scan.h's, shared with sylber_dtwpq_scan.
 //   * dtw_rerank_kernel: one wave per (phrase, candidate) pair, lane l owns phrase row l.  The wave walks the candidate sequence in
-//     chunks of DT_RR_CH columns: for a chunk every lane forms its row's dots with the explicit ascending __builtin_fmaf chain from 0
-//     over D (what v_mfma_f32_32x32x2_f32 performs in dtw_search_kernel, as knn_rerank_kernel relies on), the database row being the
-//     same address in every lane; d goes to LDS and the same wavefront advances over the chunk, its state carried across chunks.  The
-//     lane of the last row tracks (best cost, start, end), the smallest end on ties.  Only the chunk loop depends on the length.
+//     chunks; the lane's set-up, a chunk's local costs (the explicit ascending __builtin_fmaf chain that gives every A[i][j] the
+//     bits of dtw_search_kernel's) and the wavefront over a chunk are dtw_pair.h's, shared with dtw_occ_rerank_kernel below and
+//     dtw_align.hip's dtw_align_kernel; the cell is dtw_tile.h's dt_cell.  The lane of the last row tracks (best cost, start, end),
+//     the smallest end on ties.  Only the chunk loop depends on the length.
 //   * dtw_rank_kernel: one wave per phrase ranks its m pair results by (cost, sequence) and writes the best k with spans as row ids.
 //     A second launch: nothing relies on an order between workgroups.
 //   * dtw_occ_rerank_kernel (at the end of the file; SyllableIndex.search_occurrences_refined, tests/occ_ref.py): dtw_rerank_kernel's
-//     walk with every non-overlapping occurrence of the candidate kept, k per pair in LDS; merged and reported by dtw_occ.h.
+//     walk (the same pieces of dtw_pair.h, dt_occ_cell for the cell and two ballots after it) with every non-overlapping occurrence
+//     of the candidate kept, k per pair in LDS; merged and reported by dtw_occ.h.
 // LDS and occupancy (a CU has 160 KiB):
 //   dtw16_scan_kernel   69 136 B fixed (cost tile 67 584 | c_j, sequence ids, groups) + 8 B x (phrases of the block) x m <= 32 KiB
 //                       of lists = at most 101 904 B: one workgroup of 4 waves per CU (dtw_search_kernel: 134 672 B, also one); two
@@ -33,10 +34,8 @@
 //                       bound it, not LDS.  dtw_occ_rerank_kernel adds its list: 9 216 + 16 k <= 11 264 B.
 #include "kernels.h"
 #include "dtw16_scan.h"
+#include "dtw_pair.h"
 #include "dtw_occ.h"
-
-constexpr int DT_RR_CH = 32;                              // columns of a re-rank chunk (RERANK_CHUNK of search.py)
-constexpr int DT_RR_LD = 36;                              // row stride of the chunk's costs: lane i reads d[i][t - i], bank (3 i + t) % 32
 
 // meta / slot_phrase / block_rows / cuts / groups as dtw_search_kernel.  q: the packed phrase blocks' 16-bit rows [n_blocks * 128, D],
 // qsq: the fp32 ||q_i||^2 of the unrounded packed rows (L2) or null (cosine); x: the 16-bit plane; cn: the fp32 ||x_j||^2 (L2) or null.
@@ -202,7 +201,7 @@ __global__ __launch_bounds__(64) void dtw_rerank_kernel(const float* __restrict_
                                                         const float* __restrict__ x, int N, int D, const float* __restrict__ cn,
                                                         const int32_t* __restrict__ cand, const int32_t* __restrict__ soff, int S,
                                                         int m, float* __restrict__ pc, int2* __restrict__ pspan) {
-    __shared__ float dsm[DT_MAX_M * DT_RR_LD];
+    __shared__ float dsm[DT_MAX_M * DP_LD];
     const int lane = threadIdx.x;
     const size_t pair = blockIdx.x;
     const int p = (int)(pair / m);
@@ -216,48 +215,17 @@ __global__ __launch_bounds__(64) void dtw_rerank_kernel(const float* __restrict_
         if (lane == 0) { pc[pair] = INFINITY; pspan[pair] = make_int2(-1, -1); }
         return;
     }
-    int mp = plen[p];
-    mp = mp < 1 ? 1 : (mp > DT_MAX_M ? DT_MAX_M : mp);
-    int r = prow[p] + (lane < mp ? lane : mp - 1);         // lanes behind the phrase read its last row and keep nothing
-    r = r < 0 ? 0 : (r < qrows ? r : qrows - 1);
-    const float* qr = q + (size_t)r * D;
-    const float qn = qsq ? qsq[r] : 0.f;
-    const bool valid = lane < mp, lastrow = lane == mp - 1;
+    const DpLane L(q, qsq, qrows, prow, plen, p, D, lane, DT_MAX_M);
     DtLane st;
-    float* dr = dsm + lane * DT_RR_LD;
-    for (int n0 = j0; n0 < j1; n0 += DT_RR_CH) {
-        const int ncol = j1 - n0 < DT_RR_CH ? j1 - n0 : DT_RR_CH;
-        // dot[jj] = the fmaf chain over ascending c from 0 of q_lane . x_(n0 + jj): explicit __builtin_fmaf calls, nothing for the
-        // compiler to contract or reassociate; columns past the sequence repeat its last row and are not read by the DP
-        float dot[DT_RR_CH];
-#pragma unroll
-        for (int jj = 0; jj < DT_RR_CH; ++jj) dot[jj] = 0.f;
-        for (int c = 0; c < D; c += 4) {
-            const float4 a = *(const float4*)(qr + c);
-#pragma unroll
-            for (int jj = 0; jj < DT_RR_CH; ++jj) {
-                const int j = jj < ncol ? n0 + jj : j1 - 1;
-                const float4 bv = *(const float4*)(x + (size_t)j * D + c);
-                dot[jj] = __builtin_fmaf(bv.x, a.x, dot[jj]);
-                dot[jj] = __builtin_fmaf(bv.y, a.y, dot[jj]);
-                dot[jj] = __builtin_fmaf(bv.z, a.z, dot[jj]);
-                dot[jj] = __builtin_fmaf(bv.w, a.w, dot[jj]);
-            }
-        }
-        __syncthreads();                                   // the previous chunk's costs are read
-#pragma unroll
-        for (int jj = 0; jj < DT_RR_CH; ++jj) {
-            const int j = jj < ncol ? n0 + jj : j1 - 1;
-            dr[jj] = dt_cost(dot[jj], cn ? cn[j] : 0.f, qsq != nullptr, qn);
-        }
-        __syncthreads();
-        for (int t = 0; t < ncol + mp - 1; ++t) {          // dtw_tile.h's cell: the candidate is one sequence, starting at j0
-            const DtUp u = dt_up<true>(st);
-            const int j = t - lane;
-            if (valid && j >= 0 && j < ncol) dt_cell<true>(st, u, lane == 0, lastrow, n0 + j == j0, dr[j], n0 + j);
-        }
+    float* dr = dsm + lane * DP_LD;
+    for (int n0 = j0; n0 < j1; n0 += DP_CH) {
+        const int ncol = j1 - n0 < DP_CH ? j1 - n0 : DP_CH;
+        dp_chunk_costs(dr, L, x, D, cn, qsq != nullptr, n0, ncol, j1);
+        dp_walk(st, L, lane, n0, ncol, j0, [&](int j, int col, bool isstart, const DtUp& u) {
+            dt_cell<true>(st, u, lane == 0, L.lastrow, isstart, dr[j], col);
+        });
     }
-    if (lastrow) {
+    if (L.lastrow) {
         pc[pair] = st.bc;
         pspan[pair] = st.bc < INFINITY ? make_int2(st.bst, st.be) : make_int2(-1, -1);
     }
@@ -352,16 +320,14 @@ extern "C" int sylber_dtw_rerank(const float* q_dev, int32_t n_blocks, const flo
     hipStream_t s = (hipStream_t)stream;
     if (!q_dev || !phrase_row_dev || !phrase_len_dev || !db_dev || !cand_dev || !seq_offsets_dev || !cost_dev || !seq_dev || !span_dev ||
         !workspace_dev) { syl_set_error(what, "null argument"); return 1; }
-    if (n_blocks < 1 || n_phrases < 1 || N < 1 || n_seq < 1 || D < 16 || D % 16) { syl_set_error(what, "need n_blocks, n_phrases, N, n_seq >= 1 and D a multiple of 16"); return 1; }
-    if (m < 1 || m > KN_KMAX || k < 1 || k > m) { syl_set_error(what, "need 1 <= k <= m <= 128"); return 1; }
-    if (metric != SYLBER_KNN_L2 && metric != SYLBER_KNN_IP) { syl_set_error(what, "unknown metric"); return 1; }
-    if (metric == SYLBER_KNN_L2 && (!db_norm_dev || !q_norm_dev)) { syl_set_error(what, "the L2 metric needs db_norm_dev and q_norm_dev"); return 1; }
-    if ((int64_t)n_blocks * KN_BM > INT32_MAX || (int64_t)n_phrases * m > INT32_MAX) { syl_set_error(what, "n_phrases x m is too large: use smaller phrase chunks"); return 1; }
+    const float *qn, *cn;
+    if (dt_pair_check(what, "need n_blocks, n_phrases, N, n_seq >= 1 and D a multiple of 16",
+                      m < 1 || m > KN_KMAX || k < 1 || k > m ? "need 1 <= k <= m <= 128" : nullptr,
+                      "n_phrases x m is too large: use smaller phrase chunks", n_blocks, n_phrases, n_seq, N, D, q_norm_dev, db_norm_dev, metric,
+                      (int64_t)n_phrases * m > INT32_MAX, qn, cn)) return 1;
     char* w = (char*)workspace_dev;
     float* pc = (float*)w; w += kn_al((int64_t)n_phrases * m * 4);
     int2* pspan = (int2*)w;
-    const float* qn = metric == SYLBER_KNN_L2 ? q_norm_dev : nullptr;
-    const float* cn = metric == SYLBER_KNN_L2 ? db_norm_dev : nullptr;
     hipLaunchKernelGGL(dtw_rerank_kernel, dim3((unsigned)((int64_t)n_phrases * m)), dim3(64), 0, s, q_dev, qn, n_blocks * KN_BM, phrase_row_dev,
                        phrase_len_dev, db_dev, N, D, cn, cand_dev, seq_offsets_dev, n_seq, m, pc, pspan);
     HIP_TRY(hipGetLastError());
@@ -372,8 +338,8 @@ extern "C" int sylber_dtw_rerank(const float* q_dev, int32_t n_blocks, const flo
 }
 
 // ---- every occurrence of a phrase among candidate sequences (SyllableIndex.search_occurrences_refined) ----------------------------
-// dtw_rerank_kernel's sibling: the same wave per (phrase, candidate) pair, the same chunk loop and explicit fmaf chain, so every
-// A[m-1][j] and start has the bits of dtw_occ_kernel's.  The lane of the last row runs dt_occ_cell's one-pass rule and the wave
+// dtw_rerank_kernel's sibling: the same wave per (phrase, candidate) pair on the same pieces of dtw_pair.h, so every A[m-1][j] and
+// start has the bits of dtw_occ_kernel's.  The lane of the last row runs dt_occ_cell's one-pass rule and the wave
 // keeps the pair's k best occurrences as a sorted list of (cost, start row, (start row, end row)) in LDS (16 B x k <= 2 KiB);
 // it goes to ps / pi / pp [P][m][k], a list of fillers for a candidate of -1.  Candidate sequences of a phrase are distinct (stage
 // 1's are), so the start rows of its m lists are: knn_merge_kernel<true> reduces them and dtw_occ_finish_kernel reports.
@@ -383,7 +349,7 @@ __global__ __launch_bounds__(64) void dtw_occ_rerank_kernel(const float* __restr
                                                             const int32_t* __restrict__ cand, const int32_t* __restrict__ soff, int S,
                                                             int m, int k, float* __restrict__ ps, int32_t* __restrict__ pi,
                                                             int2* __restrict__ pp) {
-    __shared__ float dsm[DT_MAX_M * DT_RR_LD];
+    __shared__ float dsm[DT_MAX_M * DP_LD];
     __shared__ float ols[KN_KMAX];
     __shared__ int oli[KN_KMAX];
     __shared__ int2 olp[KN_KMAX];
@@ -397,61 +363,31 @@ __global__ __launch_bounds__(64) void dtw_occ_rerank_kernel(const float* __restr
         j0 = j0 < 0 ? 0 : j0; j1 = j1 > N ? N : j1;
     }
     for (int e = lane; e < k; e += 64) { ols[e] = INFINITY; oli[e] = INT_MAX; olp[e] = make_int2(-1, -1); }
-    int mp = plen[p];
-    mp = mp < 1 ? 1 : (mp > DT_MAX_M ? DT_MAX_M : mp);
-    int r = prow[p] + (lane < mp ? lane : mp - 1);         // lanes behind the phrase read its last row and keep nothing
-    r = r < 0 ? 0 : (r < qrows ? r : qrows - 1);
-    const float* qr = q + (size_t)r * D;
-    const float qn = qsq ? qsq[r] : 0.f;
-    const bool valid = lane < mp, lastrow = lane == mp - 1;
+    const DpLane L(q, qsq, qrows, prow, plen, p, D, lane, DT_MAX_M);
     DtLane st;
     DtOcc oc;
-    float* dr = dsm + lane * DT_RR_LD;
-    for (int n0 = j0; n0 < j1; n0 += DT_RR_CH) {           // no chunk for a candidate of -1: its list stays fillers
-        const int ncol = j1 - n0 < DT_RR_CH ? j1 - n0 : DT_RR_CH;
-        // dtw_rerank_kernel's dots: the fmaf chain over ascending c from 0, explicit __builtin_fmaf calls
-        float dot[DT_RR_CH];
-#pragma unroll
-        for (int jj = 0; jj < DT_RR_CH; ++jj) dot[jj] = 0.f;
-        for (int c = 0; c < D; c += 4) {
-            const float4 a = *(const float4*)(qr + c);
-#pragma unroll
-            for (int jj = 0; jj < DT_RR_CH; ++jj) {
-                const int j = jj < ncol ? n0 + jj : j1 - 1;
-                const float4 bv = *(const float4*)(x + (size_t)j * D + c);
-                dot[jj] = __builtin_fmaf(bv.x, a.x, dot[jj]);
-                dot[jj] = __builtin_fmaf(bv.y, a.y, dot[jj]);
-                dot[jj] = __builtin_fmaf(bv.z, a.z, dot[jj]);
-                dot[jj] = __builtin_fmaf(bv.w, a.w, dot[jj]);
-            }
-        }
-        __syncthreads();                                   // the previous chunk's costs are read; the first time: the list is cleared
-#pragma unroll
-        for (int jj = 0; jj < DT_RR_CH; ++jj) {
-            const int j = jj < ncol ? n0 + jj : j1 - 1;
-            dr[jj] = dt_cost(dot[jj], cn ? cn[j] : 0.f, qsq != nullptr, qn);
-        }
-        __syncthreads();
-        for (int t = 0; t < ncol + mp - 1; ++t) {
-            const DtUp u = dt_up<true>(st);
-            const int j = t - lane;
-            bool out = false, end = false;
-            float ec = INFINITY;
-            int es = 0, ee = 0;
-            if (valid && j >= 0 && j < ncol) {
-                out = dt_occ_cell(st, oc, u, lane == 0, lastrow, n0 + j == j0, dr[j], n0 + j, ec, es, ee);
-                end = lastrow && n0 + j == j1 - 1 && oc.pc < INFINITY;
-            }
+    float* dr = dsm + lane * DP_LD;
+    for (int n0 = j0; n0 < j1; n0 += DP_CH) {              // no chunk for a candidate of -1: its list stays fillers
+        const int ncol = j1 - n0 < DP_CH ? j1 - n0 : DP_CH;
+        dp_chunk_costs(dr, L, x, D, cn, qsq != nullptr, n0, ncol, j1);       // its first barrier, the first time: the list is cleared
+        bool out = false, end = false;                     // what the lane's cell of this step owes the list
+        float ec = INFINITY;
+        int es = 0, ee = 0;
+        dp_walk(st, L, lane, n0, ncol, j0, [&](int j, int col, bool isstart, const DtUp& u) {
+            out = dt_occ_cell(st, oc, u, lane == 0, L.lastrow, isstart, dr[j], col, ec, es, ee);
+            end = L.lastrow && col == j1 - 1 && oc.pc < INFINITY;
+        }, [&] {
             // only lane mp - 1 can owe a hand-off; at the sequence's last column it may owe both
             if (__ballot(out)) {
-                const int vs = __shfl(es, mp - 1);
-                kn_insert_t<true>(ols, oli, olp, k, lane, __shfl(ec, mp - 1), vs, make_int2(vs, __shfl(ee, mp - 1)));
+                const int vs = __shfl(es, L.mp - 1);
+                kn_insert_t<true>(ols, oli, olp, k, lane, __shfl(ec, L.mp - 1), vs, make_int2(vs, __shfl(ee, L.mp - 1)));
             }
             if (__ballot(end)) {
-                const int vs = __shfl(oc.ps, mp - 1);
-                kn_insert_t<true>(ols, oli, olp, k, lane, __shfl(oc.pc, mp - 1), vs, make_int2(vs, __shfl(oc.pe, mp - 1)));
+                const int vs = __shfl(oc.ps, L.mp - 1);
+                kn_insert_t<true>(ols, oli, olp, k, lane, __shfl(oc.pc, L.mp - 1), vs, make_int2(vs, __shfl(oc.pe, L.mp - 1)));
             }
-        }
+            out = false; end = false;
+        });
     }
     __syncthreads();
     for (int e = lane; e < k; e += 64) { ps[pair * k + e] = ols[e]; pi[pair * k + e] = oli[e]; pp[pair * k + e] = olp[e]; }
@@ -471,14 +407,12 @@ extern "C" int sylber_dtw_rerank_occurrences(const float* q_dev, int32_t n_block
     hipStream_t s = (hipStream_t)stream;
     if (!q_dev || !phrase_row_dev || !phrase_len_dev || !db_dev || !cand_dev || !seq_offsets_dev || !cost_dev || !seq_dev || !span_dev ||
         !workspace_dev) { syl_set_error(what, "null argument"); return 1; }
-    if (n_blocks < 1 || n_phrases < 1 || N < 1 || n_seq < 1 || D < 16 || D % 16) { syl_set_error(what, "need n_blocks, n_phrases, N, n_seq >= 1 and D a multiple of 16"); return 1; }
-    if (m < 1 || m > KN_KMAX || k < 1 || k > KN_KMAX) { syl_set_error(what, "need 1 <= m <= 128 and 1 <= k <= 128"); return 1; }
-    if (metric != SYLBER_KNN_L2 && metric != SYLBER_KNN_IP) { syl_set_error(what, "unknown metric"); return 1; }
-    if (metric == SYLBER_KNN_L2 && (!db_norm_dev || !q_norm_dev)) { syl_set_error(what, "the L2 metric needs db_norm_dev and q_norm_dev"); return 1; }
-    if ((int64_t)n_blocks * KN_BM > INT32_MAX || (int64_t)n_phrases * m * k > INT32_MAX / 2) { syl_set_error(what, "n_phrases x m x k is too large: use smaller phrase chunks"); return 1; }
+    const float *qn, *cn;
+    if (dt_pair_check(what, "need n_blocks, n_phrases, N, n_seq >= 1 and D a multiple of 16",
+                      m < 1 || m > KN_KMAX || k < 1 || k > KN_KMAX ? "need 1 <= m <= 128 and 1 <= k <= 128" : nullptr,
+                      "n_phrases x m x k is too large: use smaller phrase chunks", n_blocks, n_phrases, n_seq, N, D, q_norm_dev, db_norm_dev, metric,
+                      (int64_t)n_phrases * m * k > INT32_MAX / 2, qn, cn)) return 1;
     const DtOccLists lists = dt_occ_lists_carve((char*)workspace_dev, n_phrases, m, k);
-    const float* qn = metric == SYLBER_KNN_L2 ? q_norm_dev : nullptr;
-    const float* cn = metric == SYLBER_KNN_L2 ? db_norm_dev : nullptr;
     hipLaunchKernelGGL(dtw_occ_rerank_kernel, dim3((unsigned)((int64_t)n_phrases * m)), dim3(64), 0, s, q_dev, qn, n_blocks * KN_BM, phrase_row_dev,
                        phrase_len_dev, db_dev, N, D, cn, cand_dev, seq_offsets_dev, n_seq, m, k, lists.s0, lists.i0, lists.p0);
     HIP_TRY(hipGetLastError());

@@ -1,8 +1,9 @@
 // Warping paths (sylber_amd/search.py: SyllableIndex.align_phrases; contract in include/sylber_hip.h, restated in
 // tests/align_ref.py): for a (phrase, window of rows) pair, which stored rows each phrase row was warped onto.
-//   * dtw_align_kernel: dtw_rerank_kernel's sibling -- one wave per pair, lane l owns phrase row l, the window walked in chunks of
-//     DA_CH columns with the explicit ascending __builtin_fmaf chain from 0 over D, dt_cost, dt_up and dt_cell (dtw_tile.h), so
-//     every A[i][j] has the bits dtw_search_kernel gives it on that window taken as one sequence.  Beside the cell each lane takes
+//   * dtw_align_kernel: dtw_rerank_kernel's sibling -- one wave per pair, lane l owns phrase row l, the window walked in chunks.
+//     The lane's set-up, a chunk's local costs (the explicit ascending __builtin_fmaf chain) and the wavefront over a chunk are
+//     dtw_pair.h's, the cell is dtw_tile.h's dt_cell, so every A[i][j] has the bits dtw_search_kernel gives it on that window
+//     taken as one sequence.  Beside the cell each lane takes
 //     down a 2-bit code of the predecessor the cell took (DA_NONE for row 0, DA_DIAG, DA_UP, DA_LEFT), from the comparisons
 //     dt_cell makes, in dt_cell's order.  A lane's 32 codes of a chunk are one 64-bit word; the wave stores the chunk's words as
 //     one coalesced row of 64 x 8 B, so the pair's slice of the workspace is [chunks][64] words = 16 B per column: cell (i, j) is
@@ -15,15 +16,13 @@
 //     it: tests hold it against the backtracked one, i.e. the codes against the cell that formed them.
 // LDS: 9 216 B of costs (64 rows x 36 floats) + 512 B of runs, 64 threads: wave slots and registers bound the occupancy.
 #include "kernels.h"
-#include "../../include/sylber_hip.h"
-#include "dtw_tile.h"
+#include "dtw_pair.h"
 
-constexpr int DA_CH = 32;                                 // columns of a chunk: the 2-bit codes of a lane's chunk fill one 64-bit word
-constexpr int DA_LD = 36;                                 // row stride of the chunk's costs: lane i reads d[i][t - i], bank (3 i + t) % 32
 constexpr int DA_MAX_COLS = 65536;                        // rows of a window: the DP along it is serial, as along a sequence
 constexpr unsigned DA_NONE = 0, DA_DIAG = 1, DA_UP = 2, DA_LEFT = 3;
 
 static_assert(DA_MAX_COLS == DT_MAX_SEQ, "a returned span lies inside one sequence");
+static_assert(2 * DP_CH == 64, "the 2-bit codes of a lane's chunk fill one 64-bit word");
 
 // the predecessor dt_cell takes for this cell: its comparisons on its operands, in its order -- (i-1, j-1), then (i-1, j), then
 // (i, j-1), the first smallest.  Called before dt_cell moves the lane's state on.
@@ -55,7 +54,7 @@ __global__ __launch_bounds__(64) void dtw_align_kernel(const float* __restrict__
                                                        const int32_t* __restrict__ pp, const int2* __restrict__ win, int max_cols, int Mx,
                                                        int2* __restrict__ rows, int32_t* __restrict__ steps, float* __restrict__ cost,
                                                        int32_t* __restrict__ tstart, uint64_t* ws) {
-    __shared__ float dsm[DT_MAX_M * DA_LD];
+    __shared__ float dsm[DT_MAX_M * DP_LD];
     __shared__ int rlo[DT_MAX_M], rhi[DT_MAX_M];
     __shared__ int nstep;
     const int lane = threadIdx.x;
@@ -67,55 +66,21 @@ __global__ __launch_bounds__(64) void dtw_align_kernel(const float* __restrict__
         da_padding(lane, pair, Mx, rows, steps, cost, tstart);
         return;
     }
-    int mp = plen[p];
-    mp = mp < 1 ? 1 : (mp > DT_MAX_M ? DT_MAX_M : mp);
-    mp = mp > Mx ? Mx : mp;
-    int r = prow[p] + (lane < mp ? lane : mp - 1);         // lanes behind the phrase read its last row and keep nothing
-    r = r < 0 ? 0 : (r < qrows ? r : qrows - 1);
-    const float* qr = q + (size_t)r * D;
-    const float qn = qsq ? qsq[r] : 0.f;
-    const bool valid = lane < mp;
+    const DpLane L(q, qsq, qrows, prow, plen, p, D, lane, Mx);
+    const int mp = L.mp;
     const int W = j1 - j0;
-    uint64_t* wp = ws + pair * ((size_t)((max_cols + DA_CH - 1) / DA_CH) * 64);
+    uint64_t* wp = ws + pair * ((size_t)((max_cols + DP_CH - 1) / DP_CH) * 64);
     DtLane st;
-    float* dr = dsm + lane * DA_LD;
-    for (int n0 = j0; n0 < j1; n0 += DA_CH) {
-        const int ncol = j1 - n0 < DA_CH ? j1 - n0 : DA_CH;
-        // dtw_rerank_kernel's dots: the fmaf chain over ascending c from 0, explicit __builtin_fmaf calls; columns past the window
-        // repeat its last row and are not read by the DP
-        float dot[DA_CH];
-#pragma unroll
-        for (int jj = 0; jj < DA_CH; ++jj) dot[jj] = 0.f;
-        for (int c = 0; c < D; c += 4) {
-            const float4 a = *(const float4*)(qr + c);
-#pragma unroll
-            for (int jj = 0; jj < DA_CH; ++jj) {
-                const int j = jj < ncol ? n0 + jj : j1 - 1;
-                const float4 bv = *(const float4*)(x + (size_t)j * D + c);
-                dot[jj] = __builtin_fmaf(bv.x, a.x, dot[jj]);
-                dot[jj] = __builtin_fmaf(bv.y, a.y, dot[jj]);
-                dot[jj] = __builtin_fmaf(bv.z, a.z, dot[jj]);
-                dot[jj] = __builtin_fmaf(bv.w, a.w, dot[jj]);
-            }
-        }
-        __syncthreads();                                   // the previous chunk's costs are read
-#pragma unroll
-        for (int jj = 0; jj < DA_CH; ++jj) {
-            const int j = jj < ncol ? n0 + jj : j1 - 1;
-            dr[jj] = dt_cost(dot[jj], cn ? cn[j] : 0.f, qsq != nullptr, qn);
-        }
-        __syncthreads();
+    float* dr = dsm + lane * DP_LD;
+    for (int n0 = j0; n0 < j1; n0 += DP_CH) {
+        const int ncol = j1 - n0 < DP_CH ? j1 - n0 : DP_CH;
+        dp_chunk_costs(dr, L, x, D, cn, qsq != nullptr, n0, ncol, j1);
         uint64_t codes = 0;
-        for (int t = 0; t < ncol + mp - 1; ++t) {          // dtw_tile.h's cell: the window is one sequence, starting at j0
-            const DtUp u = dt_up<true>(st);
-            const int j = t - lane;
-            if (valid && j >= 0 && j < ncol) {
-                const bool isstart = n0 + j == j0;
-                codes |= (uint64_t)da_code(st, u, lane == 0, isstart) << (2 * j);
-                dt_cell<true>(st, u, lane == 0, false, isstart, dr[j], n0 + j);
-            }
-        }
-        wp[(size_t)((n0 - j0) / DA_CH) * 64 + lane] = codes;
+        dp_walk(st, L, lane, n0, ncol, j0, [&](int j, int col, bool isstart, const DtUp& u) {
+            codes |= (uint64_t)da_code(st, u, lane == 0, isstart) << (2 * j);
+            dt_cell<true>(st, u, lane == 0, false, isstart, dr[j], col);
+        });
+        wp[(size_t)((n0 - j0) / DP_CH) * 64 + lane] = codes;
     }
     const float A = __shfl(st.a_cur, mp - 1);              // A[m-1][b-1]: the last cell of the last row
     const int ts = __shfl(st.s_cur, mp - 1);               // and the start its path was tracked to
@@ -131,7 +96,7 @@ __global__ __launch_bounds__(64) void dtw_align_kernel(const float* __restrict__
         // a finite cell's predecessor is finite and inside the window (what lies outside is +inf), so the chain reaches row 0 in
         // at most W + m - 1 cells; the bound and the j >= 0 test only keep a corrupted workspace from leading anywhere else
         for (int guard = W + mp; i > 0 && guard > 0; --guard) {
-            const unsigned code = (unsigned)(wp[(size_t)(j / DA_CH) * 64 + i] >> (2 * (j % DA_CH))) & 3u;
+            const unsigned code = (unsigned)(wp[(size_t)(j / DP_CH) * 64 + i] >> (2 * (j % DP_CH))) & 3u;
             if (code != DA_LEFT) { rlo[i] = j; --i; }
             if (code != DA_UP) --j;
             if (j < 0) break;
@@ -164,14 +129,12 @@ extern "C" int sylber_dtw_align(const float* q_dev, int32_t n_blocks, const floa
     hipStream_t s = (hipStream_t)stream;
     if (!q_dev || !phrase_row_dev || !phrase_len_dev || !db_dev || !pair_phrase_dev || !pair_window_dev || !rows_dev || !steps_dev ||
         !cost_dev || !workspace_dev) { syl_set_error(what, "null argument"); return 1; }
-    if (n_blocks < 1 || n_phrases < 1 || n_pairs < 1 || N < 1 || D < 16 || D % 16) { syl_set_error(what, "need n_blocks, n_phrases, n_pairs, N >= 1 and D a multiple of 16"); return 1; }
-    if (max_cols < 1 || max_cols > DA_MAX_COLS) { syl_set_error(what, "need 1 <= max_cols <= 65536: a window has at most 65536 rows"); return 1; }
-    if (max_rows < 1 || max_rows > DT_MAX_M) { syl_set_error(what, "need 1 <= max_rows <= 64"); return 1; }
-    if (metric != SYLBER_KNN_L2 && metric != SYLBER_KNN_IP) { syl_set_error(what, "unknown metric"); return 1; }
-    if (metric == SYLBER_KNN_L2 && (!db_norm_dev || !q_norm_dev)) { syl_set_error(what, "the L2 metric needs db_norm_dev and q_norm_dev"); return 1; }
-    if ((int64_t)n_blocks * KN_BM > INT32_MAX) { syl_set_error(what, "too many phrase blocks: use smaller phrase chunks"); return 1; }
-    const float* qn = metric == SYLBER_KNN_L2 ? q_norm_dev : nullptr;
-    const float* cn = metric == SYLBER_KNN_L2 ? db_norm_dev : nullptr;
+    const float *qn, *cn;
+    if (dt_pair_check(what, "need n_blocks, n_phrases, n_pairs, N >= 1 and D a multiple of 16",
+                      max_cols < 1 || max_cols > DA_MAX_COLS ? "need 1 <= max_cols <= 65536: a window has at most 65536 rows"
+                      : max_rows < 1 || max_rows > DT_MAX_M  ? "need 1 <= max_rows <= 64" : nullptr,
+                      "too many phrase blocks: use smaller phrase chunks", n_blocks, n_phrases, n_pairs, N, D, q_norm_dev, db_norm_dev, metric, false,
+                      qn, cn)) return 1;
     hipLaunchKernelGGL(dtw_align_kernel, dim3((unsigned)n_pairs), dim3(64), 0, s, q_dev, qn, n_blocks * KN_BM, phrase_row_dev, phrase_len_dev,
                        n_phrases, db_dev, N, D, cn, pair_phrase_dev, (const int2*)pair_window_dev, max_cols, max_rows, (int2*)rows_dev,
                        steps_dev, cost_dev, start_dev, (uint64_t*)workspace_dev);

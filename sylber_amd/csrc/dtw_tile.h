@@ -1,13 +1,16 @@
 // What the subsequence-DTW kernels share: the geometry (the cost tile that the dynamic programme reads, the limits of a phrase and
 // of a sequence, how many phrases sylber_dtw_plan packs into a query block) and the device pieces -- a workgroup's LDS carve, the
 // per-tile column data, the epilogue that turns the contraction into local costs, the lane state with the wavefront over a tile,
-// the write-out of a block's lists.  dtw.hip's dtw_search_kernel (fp32, spans tracked: SPAN = true) and dtwpq.hip's
-// dtwpq_scan_kernel (SPAN = false) are built from all of them; dtw16.hip's dtw16_scan_kernel uses the column data and keeps the
-// rest written out (its header says why), its dtw_rerank_kernel uses the local cost, the lane state and the cell (dt_cost, dt_up,
-// dt_cell).  The occurrence scans (dtw.hip's dtw_occ_kernel, dtw16.hip's dtw_occ_rerank_kernel) add a pending occurrence to the lane
-// state and hand over at any column: DtOcc, dt_occ_cell, dt_occ_wavefront below, siblings that leave the pieces above as they
-// were.  The order of the predecessor comparisons and the NaN -> +inf rule are the contract's (include/sylber_hip.h).  Every
-// piece is forced inline; the contraction (fp32: knn_tile.h, 16-bit: knn16_tile.h) and the K loop around it stay with the kernels.
+// the write-out of a block's lists.  Who uses what:
+//   * dtw.hip's dtw_scan_body<OCC> (dtw_search_kernel and dtw_occ_kernel; fp32, spans tracked: SPAN = true) and dtwpq.hip's
+//     dtwpq_scan_kernel (SPAN = false) are built from all of them;
+//   * dtw16.hip's dtw16_scan_kernel uses the column data and keeps the rest written out (its header says why);
+//   * the wave-per-pair kernels (dtw16.hip's dtw_rerank_kernel and dtw_occ_rerank_kernel, dtw_align.hip's dtw_align_kernel) use the
+//     local cost, the lane state and the cell (dt_cost, dt_up, dt_cell) through dtw_pair.h, which holds their chunk walk.
+// The occurrence scans (dtw_occ_kernel, dtw_occ_rerank_kernel) add a pending occurrence to the lane state and hand over at any
+// column: DtOcc, dt_occ_cell, dt_occ_wavefront below, siblings that leave the pieces above as they were.  The order of the
+// predecessor comparisons and the NaN -> +inf rule are the contract's (include/sylber_hip.h).  Every piece is forced inline; the
+// contraction (fp32: knn_tile.h, 16-bit: knn16_tile.h) and the K loop around it stay with the kernels.
 #pragma once
 #include "knn_tile.h"
 

@@ -36,10 +36,9 @@ import torch
 from . import _lib
 from ._index import (DEFAULT_PHRASE_CHUNK, DEFAULT_QUERY_CHUNK, METRICS, STORAGES, _added_rows, _base_arrays, _check_k_refine,
                      _check_nprobe, _check_splits_chunk, _chunked_workspace_bytes, _group_runs, _list_layout, _on_device, _outputs, _pack16,
-                     _phrase_args, _phrase_blocks, _phrase_outputs, _prep, _provenance, _query_groups, _result, _row_norms, _rows,
-                     _rows_of_width, _sequence_tables)
+                     _prep, _provenance, _query_groups, _result, _row_norms, _rows, _rows_of_width, _scan_phrases)
 from .kmeans import _device, _stream, _vp
-from .search import IVFSyllableIndex, SyllableIndex, _align_launch, _align_phrases
+from .search import IVFSyllableIndex, SyllableIndex, _align_launch, _align_phrases, _rerank_launch
 
 KSUB = 256                      # centroids per sub-space: one uint8 per code
 MAX_M = 64                      # PQ_MAX_M of csrc/pq.hip: at least two queries' tables (M KiB each) fit beside the top lists in LDS
@@ -462,67 +461,54 @@ class PQSyllableIndex:
             rerank = self.index is not None
         if rerank and self.index is None:
             raise ValueError("rerank=True needs the fp32 rows, which were dropped: search with rerank=False")
-        k, m = _check_k_refine(k, refine, rerank=True)
-        if storage not in STORAGES:
-            raise ValueError("storage must be 'fp16' or 'bf16', got %r" % (storage,))
         if isinstance(scratch_rows, bool) or int(scratch_rows) != scratch_rows or int(scratch_rows) < 1:
             raise ValueError("scratch_rows must be an integer >= 1, got %r" % (scratch_rows,))
-        N, D, M, dev = len(self), self.dim, self.M, self.device
+        N = len(self)
         if self.index is not None and len(self.index) != N:
             raise ValueError("pq.index holds %d rows, the codes %d: add rows through pq.add" % (len(self.index), N))
-        q, lens, pg, off = _phrase_args(N, D, dev, self.sequence_offsets, phrases, lengths, groups, exclude_same_group, sequences, splits,
-                                        phrase_chunk, block_phrases)
-        P = int(lens.size)
-        costs, seqs, spans = _phrase_outputs(P, k, dev)
-        cand = torch.empty((P, m), dtype=torch.int32, device=dev)
-        coarse = torch.empty((P, m), dtype=torch.float32, device=dev)
-        if P == 0:
-            return (costs, seqs, spans, cand.to(torch.int64), coarse) if return_candidates else (costs, seqs, spans)
-        cb16 = self._codebooks16(storage)
-        cn = self._recon_norms()
-        lib = _lib.load()
-        qd = self._prep(q)
-        S = off.size - 1
-        seq_id, seq_grp = _sequence_tables(off, self._db_groups() if pg is not None else None, dev)
-        off_d = _on_device(off, np.int32, dev)
-        metric, code = METRICS[self.metric], STORAGES[storage][0]
-        with torch.cuda.device(dev):
-            st = _stream(dev)
-            for p0 in range(0, P, int(phrase_chunk)):
-                p1 = min(P, p0 + int(phrase_chunk))
-                b = _phrase_blocks(lib, dev, qd, lens, p0, p1, off, m, splits, block_phrases, pg)
-                qn = _row_norms(b.qp) if self.metric == "l2" else None
-                q16 = _pack16(b.qp, storage, refuse=False)
-                ws = torch.empty(int(lib.sylber_dtw16_workspace_bytes(b.Pc, m, b.C)), dtype=torch.uint8, device=dev)
-                if _workspace_fill is not None:
-                    ws.fill_(_workspace_fill)
-                meta_d, sp_d, br_d, cut_d, pg_d = b.tables()
-                place_d, len_d = _on_device(b.place, np.int32, dev), _on_device(b.ln, np.int32, dev)
-                _lib.check(lib.sylber_dtwpq_scan(_vp(q16), b.nb, _vp(meta_d), _vp(sp_d), _vp(br_d), b.Pc, b.slots, _vp(self._codes),
-                                                 _vp(self._bad), _vp(cb16), N, D, M, _vp(cn), _vp(qn), metric, code, m, _vp(seq_id), _vp(cut_d),
-                                                 b.C, _vp(pg_d), _vp(seq_grp), _vp(cand[p0:p1]), _vp(coarse[p0:p1]), _vp(ws), st),
-                           "sylber_dtwpq_scan")
-                if rerank:
-                    i = self.index
-                    _lib.check(lib.sylber_dtw_rerank(_vp(b.qp), b.nb, _vp(qn), _vp(place_d), _vp(len_d), b.Pc, _vp(i._x), N, D, _vp(i._c), metric,
-                                                     _vp(cand[p0:p1]), m, _vp(off_d), S, k, _vp(costs[p0:p1]), _vp(seqs[p0:p1]),
-                                                     _vp(spans[p0:p1]), _vp(ws), st), "sylber_dtw_rerank")
-                    continue
-                self._rerank_decoded(lib, b, qn, place_d, len_d, cand[p0:p1], off, off_d, int(scratch_rows), m, k, costs[p0:p1],
-                                     seqs[p0:p1], spans[p0:p1], ws, st)
-        return (costs, seqs, spans, cand.to(torch.int64), coarse) if return_candidates else (costs, seqs, spans)
 
-    def _rerank_decoded(self, lib, b, qn, place_d, len_d, cand, off, off_d, scratch_rows: int, m: int, k: int, costs, seqs, spans, ws,
-                        st) -> None:
+        def stages():
+            cb16, cn, code = self._codebooks16(storage), self._recon_norms(), STORAGES[storage][0]
+
+            def scan(c):
+                b = c.b
+                c.ws = c.workspace(c.lib.sylber_dtw16_workspace_bytes(b.Pc, c.m, b.C))
+                _lib.check(c.lib.sylber_dtwpq_scan(_vp(c.q16), b.nb, _vp(c.meta_d), _vp(c.sp_d), _vp(c.br_d), b.Pc, b.slots, _vp(self._codes),
+                                                   _vp(self._bad), _vp(cb16), N, c.dim, self.M, _vp(cn), _vp(c.qn), c.metric, code, c.m,
+                                                   _vp(c.seq_id), _vp(c.cut_d), b.C, _vp(c.pg_d), _vp(c.seq_grp), _vp(c.cand), _vp(c.coarse),
+                                                   _vp(c.ws), c.st), "sylber_dtwpq_scan")
+
+            if rerank:
+                return scan, lambda c: _rerank_launch(c, self.index._x, self.index._c)
+            return scan, lambda c: self._rerank_decoded(c, int(scratch_rows))
+
+        return _scan_phrases(N, self.dim, self.device, self.metric, self._db_groups(), self.sequence_offsets, stages, phrases, k, refine, storage,
+                             lengths, groups, exclude_same_group, sequences, splits, phrase_chunk, block_phrases, return_candidates,
+                             _workspace_fill)
+
+    def _decode_windows(self, first: torch.Tensor, width: np.ndarray):
+        """the decoded rows of the windows ``first[i] : first[i] + width[i]`` (``first`` int64 on the device, ``width`` on the host) laid
+        end to end in a compact scratch -> ``(x fp32 [R, D] with masked rows NaN, their ||x^||^2 under "l2" or None, coff int64
+        [n + 1] on the device: window i is scratch rows coff[i] : coff[i + 1])``"""
+        dev = self.device
+        coff = torch.from_numpy(np.concatenate([[0], np.cumsum(width)]).astype(np.int64)).to(dev)
+        owner = torch.repeat_interleave(torch.arange(len(width), device=dev), coff[1:] - coff[:-1])
+        rid = first[owner] + (torch.arange(int(width.sum()), device=dev) - coff[owner])         # the real row of every scratch row
+        x = _decode(self._codes.index_select(0, rid), self.codebooks)
+        x = torch.where((self._bad.index_select(0, rid) != 0)[:, None], torch.full_like(x, float("nan")), x)
+        rnorm = self._recon_norms()
+        return x, (rnorm.index_select(0, rid) if rnorm is not None else None), coff
+
+    def _rerank_decoded(self, c, scratch_rows: int) -> None:
         """stage 2 of ``search_phrases(rerank=False)`` for one chunk (plumbing around ``sylber_dtw_rerank``): the chunk's phrases in
         runs whose candidate sequences hold at most ``scratch_rows`` rows together (one phrase at least); per run the unique
         candidates in ascending sequence number -- so that ties break as on the real numbering -- decoded into a compact scratch
         with compact offsets, the exact DTW on it, and sequence numbers and row ids mapped back"""
-        dev, metric = self.device, METRICS[self.metric]
-        cand_h = cand.cpu().numpy()                         # waits for stage 1 of the chunk
+        dev, off = self.device, c.off
+        cand_h = c.cand.cpu().numpy()                       # waits for stage 1 of the chunk
         seq_len = np.diff(off)
         runs, g0, have, rows = [], 0, np.zeros(0, np.int64), 0
-        for p in range(b.Pc):
+        for p in range(c.b.Pc):
             new = np.setdiff1d(cand_h[p][cand_h[p] >= 0], have)
             more = int(seq_len[new].sum())
             if p > g0 and rows + more > scratch_rows:
@@ -531,26 +517,18 @@ class PQSyllableIndex:
                 new = np.unique(cand_h[p][cand_h[p] >= 0])
                 more = int(seq_len[new].sum())
             have, rows = np.union1d(have, new).astype(np.int64), rows + more
-        runs.append((g0, b.Pc, have))
+        runs.append((g0, c.b.Pc, have))
         for g0, g1, uniq in runs:
-            c_out, s_out, sp_out = costs[g0:g1], seqs[g0:g1], spans[g0:g1]
+            cand, c_out, s_out, sp_out = c.cand[g0:g1], c.costs[g0:g1], c.seqs[g0:g1], c.spans[g0:g1]
             if uniq.size == 0:                              # no candidate at all: the padding of an empty list
                 c_out.fill_(float("inf")); s_out.fill_(-1); sp_out.fill_(-1)
                 continue
-            coff = np.concatenate([[0], np.cumsum(seq_len[uniq])]).astype(np.int64)
-            R = int(coff[-1])
-            uniq_d, coff_d, roff_d = (torch.from_numpy(a).to(dev) for a in (uniq, coff, off[uniq]))
-            srow = torch.repeat_interleave(torch.arange(uniq.size, device=dev), coff_d[1:] - coff_d[:-1])
-            rid = roff_d[srow] + (torch.arange(R, device=dev) - coff_d[srow])                    # the real row of every scratch row
-            x = _decode(self._codes.index_select(0, rid), self.codebooks)
-            x = torch.where((self._bad.index_select(0, rid) != 0)[:, None], torch.full_like(x, float("nan")), x)
-            cn = self._rnorm.index_select(0, rid) if self.metric == "l2" else None
-            cc = torch.searchsorted(uniq_d, cand[g0:g1].to(torch.int64).clamp(min=0))
-            cc = torch.where(cand[g0:g1] < 0, torch.full_like(cc, -1), cc).to(torch.int32).contiguous()
-            coff32 = coff_d.to(torch.int32)
-            _lib.check(lib.sylber_dtw_rerank(_vp(b.qp), b.nb, _vp(qn), _vp(place_d[g0:g1]), _vp(len_d[g0:g1]), g1 - g0, _vp(x), R, self.dim,
-                                             _vp(cn), metric, _vp(cc), m, _vp(coff32), int(uniq.size), k, _vp(c_out),
-                                             _vp(s_out), _vp(sp_out), _vp(ws), st), "sylber_dtw_rerank")
+            uniq_d, roff_d = (torch.from_numpy(a).to(dev) for a in (uniq, off[uniq]))
+            x, cn, coff_d = self._decode_windows(roff_d, seq_len[uniq])
+            cc = torch.searchsorted(uniq_d, cand.to(torch.int64).clamp(min=0))
+            cc = torch.where(cand < 0, torch.full_like(cc, -1), cc).to(torch.int32).contiguous()
+            _rerank_launch(c.part(place_d=c.place_d[g0:g1], len_d=c.len_d[g0:g1], N=int(x.shape[0]), cand=cc, off_d=coff_d.to(torch.int32),
+                                  S=int(uniq.size), costs=c_out, seqs=s_out, spans=sp_out), x, cn)
             hit = s_out >= 0
             sc = s_out.clamp(min=0)
             sp_out.copy_(torch.where(hit[:, :, None], sp_out - coff_d[sc][:, :, None] + roff_d[sc][:, :, None], sp_out))
@@ -591,19 +569,12 @@ class PQSyllableIndex:
                     have = 0
                 have += w
             cuts.append(len(width_h))
-            rnorm = self._recon_norms()
             for g0, g1 in zip(cuts[:-1], cuts[1:]):
                 R = int(width_h[g0:g1].sum())
                 if R == 0:                                      # nothing but padding: the outputs hold it already
                     continue
                 wd, a = width[g0:g1], w64[g0:g1, 0]
-                coff = torch.zeros(g1 - g0 + 1, dtype=torch.int64, device=dev)
-                coff[1:] = torch.cumsum(wd, 0)
-                owner = torch.repeat_interleave(torch.arange(g1 - g0, device=dev), wd)
-                rid = a[owner] + (torch.arange(R, device=dev) - coff[owner])                   # the real row of every scratch row
-                x = _decode(self._codes.index_select(0, rid), self.codebooks)
-                x = torch.where((self._bad.index_select(0, rid) != 0)[:, None], torch.full_like(x, float("nan")), x)
-                cn = rnorm.index_select(0, rid) if rnorm is not None else None
+                x, cn, coff = self._decode_windows(a, width_h[g0:g1])
                 cwin = torch.stack([coff[:-1], coff[1:]], 1)
                 cwin = torch.where((wd == 0)[:, None], torch.full_like(cwin, -1), cwin).to(torch.int32).contiguous()
                 r, s0 = rows[g0:g1], (start[g0:g1] if start is not None else None)

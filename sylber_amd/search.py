@@ -38,11 +38,11 @@ from ._index import MAX_CANDIDATES, MAX_K, MAX_NPROBE  # noqa: F401  (limits of 
 from ._index import DEFAULT_PHRASE_CHUNK, MAX_PHRASE_ROWS, MAX_SEEDS, MAX_SEQUENCE_ROWS, STORAGES  # noqa: F401  (likewise, for the phrase searches)
 from ._index import (DEFAULT_QUERY_CHUNK, METRICS, _added_rows, _base_arrays, _check_k_refine, _check_nprobe, _check_splits_chunk,
                      _chunked_workspace_bytes, _group_runs, _list_layout, _on_device, _outputs, _pack16, _phrase_args, _phrase_blocks,
-                     _phrase_outputs, _PhraseBlocks, _prep, _provenance, _query_groups, _result, _row_norms, _rows, _rows_of_width,
-                     _sequence_tables, _sequences)
+                     _phrase_outputs, _PhraseBlocks, _PhraseChunk, _prep, _provenance, _query_groups, _result, _row_norms, _rows, _rows_of_width,
+                     _scan_phrases)
 from .kmeans import _device, _stream, _vp
 
-RERANK_CHUNK = 32               # DT_RR_CH of csrc/dtw16.hip: the columns of a sequence that search_phrases_refined re-ranks at a time
+RERANK_CHUNK = 32               # DP_CH of csrc/dtw_pair.h: the columns of a sequence that search_phrases_refined re-ranks at a time
 OCC_RERANK_ENTRIES = 1 << 24    # list entries (24 B each with the merge rounds' half) of one sylber_dtw_rerank_occurrences launch
 MAX_WINDOW_ROWS = 65536         # DA_MAX_COLS of csrc/dtw_align.hip: the rows of a window that align_phrases walks (= MAX_SEQUENCE_ROWS)
 ALIGN_WORKSPACE_BYTES = 256 << 20       # the default pair_chunk of align_phrases keeps its workspace below this
@@ -77,6 +77,15 @@ def _align_launch(lib, b: "_PhraseBlocks", qn, place_d, len_d, x, N: int, D: int
     _lib.check(lib.sylber_dtw_align(_vp(b.qp), b.nb, _vp(qn), _vp(place_d), _vp(len_d), b.Pc, _vp(x), N, D, _vp(cn), metric, _vp(pair_phrase),
                                     _vp(win), int(pair_phrase.shape[0]), max_cols, int(rows.shape[1]), _vp(rows), _vp(steps), _vp(costs),
                                     _vp(start), _vp(ws), st), "sylber_dtw_align")
+
+
+def _rerank_launch(c: "_PhraseChunk", x, cn) -> None:
+    """the exact re-rank, ``sylber_dtw_rerank``, of the chunk's phrases on their candidates ``c.cand`` among the ``c.S`` sequences
+    ``c.off_d`` of the ``c.N`` rows ``x`` with norms ``cn`` -> ``c.costs, c.seqs, c.spans``; ``c.ws`` is its workspace"""
+    b = c.b
+    _lib.check(c.lib.sylber_dtw_rerank(_vp(b.qp), b.nb, _vp(c.qn), _vp(c.place_d), _vp(c.len_d), int(c.cand.shape[0]), _vp(x), c.N, c.dim,
+                                       _vp(cn), c.metric, _vp(c.cand), c.m, _vp(c.off_d), c.S, c.k, _vp(c.costs), _vp(c.seqs), _vp(c.spans),
+                                       _vp(c.ws), c.st), "sylber_dtw_rerank")
 
 
 def _align_phrases(N: int, dim: int, dev, metric: str, phrases, spans, lengths, pair_chunk, run, tracked: bool = False):
@@ -163,7 +172,7 @@ class SyllableIndex:
         c = _row_norms(xd) if self.metric == "l2" else None
         if _prov is not None:
             prov = np.asarray(_prov, np.float64).reshape(m, 4)
-        more = {st: self._pack16(xd, st, refuse=True) for st in self._planes}      # raises before anything is appended
+        more = {st: _pack16(xd, st, refuse=True) for st in self._planes}      # raises before anything is appended
         for st, h in more.items():
             self._planes[st] = torch.cat([self._planes[st], h])
         if self._x is None:
@@ -232,10 +241,6 @@ class SyllableIndex:
         return scores, ids
 
     # ---- two-stage search ------------------------------------------------------------------------------------------------------------
-    def _pack16(self, x: torch.Tensor, storage: str, refuse: bool) -> torch.Tensor:
-        """fp32 rows on the device -> their 16-bit rows (csrc/knn16.hip); ``refuse``: a finite value that fp16 cannot hold is an error"""
-        return _pack16(x, storage, refuse)
-
     def half_rows(self, storage: str = "fp16") -> torch.Tensor:
         """the ``[N, D]`` 16-bit plane of the stored rows that ``search_refined(storage=...)`` scans (``torch.float16`` or
         ``torch.bfloat16``, round to nearest even), built on first use and extended by ``add``; ``2 N D`` bytes.  ``"fp16"`` raises
@@ -245,7 +250,7 @@ class SyllableIndex:
         if len(self) == 0:
             raise ValueError("the index is empty")
         if storage not in self._planes:
-            self._planes[storage] = self._pack16(self._x, storage, refuse=True)
+            self._planes[storage] = _pack16(self._x, storage, refuse=True)
         return self._planes[storage]
 
     def search_refined(self, queries, k: int, refine: int = 4, storage: str = "fp16", groups=None, exclude_same_group: bool = False,
@@ -280,7 +285,7 @@ class SyllableIndex:
         x16 = self.half_rows(storage)
         lib = _lib.load()
         qd = self._prep(q)
-        q16 = self._pack16(qd, storage, refuse=False)
+        q16 = _pack16(qd, storage, refuse=False)
         N = len(self)
         step = min(n, query_chunk)
         ws = torch.empty(_chunked_workspace_bytes(lib.sylber_knn16_workspace_bytes, n, step, N, D, m, splits), dtype=torch.uint8, device=self.device)
@@ -305,9 +310,6 @@ class SyllableIndex:
         if self._seq_cache is None or self._seq_cache[0] != N:
             self._seq_cache = (N, _group_runs(self._g, N))
         return self._seq_cache[1].copy()
-
-    def _sequences(self, sequences) -> np.ndarray:
-        return _sequences(sequences, len(self), self.sequence_offsets)
 
     def search_phrases(self, phrases, k: int, *, lengths=None, groups=None, exclude_same_group: bool = False, sequences=None,
                        splits: int = 0, phrase_chunk: int = DEFAULT_PHRASE_CHUNK, block_phrases: int = 0,
@@ -347,32 +349,8 @@ class SyllableIndex:
         Test hooks, none of which changes the result: ``splits`` (0 = automatic) asks for that many cuts of the database (cuts fall
         on sequence starts only), ``phrase_chunk`` bounds the phrases per launch (and so the workspace), ``block_phrases`` (0 =
         automatic) the phrases packed into one 128-row query block."""
-        k = _check_k_refine(k)[0]
-        q, lens, pg, off = self._phrase_args(phrases, lengths, groups, exclude_same_group, sequences, splits, phrase_chunk, block_phrases)
-        P = int(lens.size)
-        dev = self.device
-        costs, seqs, spans = _phrase_outputs(P, k, dev)
-        if P == 0:
-            return costs, seqs, spans
-        lib = _lib.load()
-        qd = self._prep(q)
-        N = len(self)
-        seq_id, seq_grp = self._sequence_tables(off, pg is not None)
-        metric = METRICS[self.metric]
-        with torch.cuda.device(dev):
-            for p0 in range(0, P, int(phrase_chunk)):
-                p1 = min(P, p0 + int(phrase_chunk))
-                b = self._phrase_blocks(lib, qd, lens, p0, p1, off, k, splits, block_phrases, pg)
-                nbytes = int(lib.sylber_dtw_workspace_bytes(b.nb, b.Pc, k, b.C))
-                ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-                if _workspace_fill is not None:
-                    ws.fill_(_workspace_fill)
-                meta_d, sp_d, br_d, cut_d, pg_d = b.tables()
-                _lib.check(lib.sylber_dtw_search(_vp(b.qp), b.nb, _vp(meta_d), _vp(sp_d), _vp(br_d), b.Pc, b.slots, _vp(self._x), N,
-                                                 self.dim, _vp(self._c), metric, k, _vp(seq_id), _vp(cut_d), b.C, _vp(pg_d), _vp(seq_grp),
-                                                 _vp(costs[p0:p1]), _vp(seqs[p0:p1]), _vp(spans[p0:p1]), _vp(ws), _stream(dev)),
-                           "sylber_dtw_search")
-        return costs, seqs, spans
+        return self._scan_phrases(lambda: (self._scan32("sylber_dtw_search"), None), phrases, k, None, None, lengths, groups, exclude_same_group,
+                                  sequences, splits, phrase_chunk, block_phrases, False, _workspace_fill)
 
     def search_phrases_refined(self, phrases, k: int, refine: int = 4, storage: str = "fp16", *, lengths=None, groups=None,
                                exclude_same_group: bool = False, sequences=None, splits: int = 0,
@@ -399,43 +377,9 @@ class SyllableIndex:
         ``coarse``, costs, seqs and spans do not depend on ``splits``, ``phrase_chunk``, ``block_phrases``, stale workspace contents
         or how the index was built.  All of ``search_phrases``'s limits, integer ``refine >= 1``, ``k * refine <= 128``,
         ``storage`` ``"fp16"`` (refuses stored values beyond +-65504, as ``half_rows`` does) or ``"bf16"``."""
-        k, m = _check_k_refine(k, refine, rerank=True)
-        if storage not in STORAGES:
-            raise ValueError("storage must be 'fp16' or 'bf16', got %r" % (storage,))
-        q, lens, pg, off = self._phrase_args(phrases, lengths, groups, exclude_same_group, sequences, splits, phrase_chunk, block_phrases)
-        P = int(lens.size)
-        dev = self.device
-        costs, seqs, spans = _phrase_outputs(P, k, dev)
-        cand = torch.empty((P, m), dtype=torch.int32, device=dev)
-        coarse = torch.empty((P, m), dtype=torch.float32, device=dev)
-        if P == 0:
-            return (costs, seqs, spans, cand.to(torch.int64), coarse) if return_candidates else (costs, seqs, spans)
-        x16 = self.half_rows(storage)
-        lib = _lib.load()
-        qd = self._prep(q)
-        N, S = len(self), off.size - 1
-        seq_id, seq_grp = self._sequence_tables(off, pg is not None)
-        off_d = _on_device(off, np.int32, dev)
-        metric, code = METRICS[self.metric], STORAGES[storage][0]
-        with torch.cuda.device(dev):
-            st = _stream(dev)
-            for p0 in range(0, P, int(phrase_chunk)):
-                p1 = min(P, p0 + int(phrase_chunk))
-                b = self._phrase_blocks(lib, qd, lens, p0, p1, off, m, splits, block_phrases, pg)
-                qn = _row_norms(b.qp) if self.metric == "l2" else None       # the ||q||^2 that sylber_dtw_search adds, same kernel
-                q16 = self._pack16(b.qp, storage, refuse=False)
-                ws = torch.empty(int(lib.sylber_dtw16_workspace_bytes(b.Pc, m, b.C)), dtype=torch.uint8, device=dev)
-                if _workspace_fill is not None:
-                    ws.fill_(_workspace_fill)
-                meta_d, sp_d, br_d, cut_d, pg_d = b.tables()
-                place_d, len_d = _on_device(b.place, np.int32, dev), _on_device(b.ln, np.int32, dev)
-                _lib.check(lib.sylber_dtw16_scan(_vp(q16), b.nb, _vp(meta_d), _vp(sp_d), _vp(br_d), b.Pc, b.slots, _vp(x16), N, self.dim,
-                                                 _vp(self._c), _vp(qn), metric, code, m, _vp(seq_id), _vp(cut_d), b.C, _vp(pg_d),
-                                                 _vp(seq_grp), _vp(cand[p0:p1]), _vp(coarse[p0:p1]), _vp(ws), st), "sylber_dtw16_scan")
-                _lib.check(lib.sylber_dtw_rerank(_vp(b.qp), b.nb, _vp(qn), _vp(place_d), _vp(len_d), b.Pc, _vp(self._x), N, self.dim,
-                                                 _vp(self._c), metric, _vp(cand[p0:p1]), m, _vp(off_d), S, k, _vp(costs[p0:p1]),
-                                                 _vp(seqs[p0:p1]), _vp(spans[p0:p1]), _vp(ws), st), "sylber_dtw_rerank")
-        return (costs, seqs, spans, cand.to(torch.int64), coarse) if return_candidates else (costs, seqs, spans)
+        return self._scan_phrases(lambda: (self._scan16(storage), lambda c: _rerank_launch(c, self._x, self._c)), phrases, k, refine, storage,
+                                  lengths, groups, exclude_same_group, sequences, splits, phrase_chunk, block_phrases, return_candidates,
+                                  _workspace_fill)
 
     def search_occurrences(self, phrases, k: int, *, lengths=None, groups=None, exclude_same_group: bool = False, sequences=None,
                            splits: int = 0, phrase_chunk: int = DEFAULT_PHRASE_CHUNK, block_phrases: int = 0,
@@ -468,31 +412,8 @@ class SyllableIndex:
         The pass is **not** global greedy suppression by cost: of a chain A - B - C with A and C disjoint, both overlapping B, and
         costs A > B > C it emits only C, where greedy suppression would also keep A.  The one-pass rule is what runs inside the
         scan with constant state per lane.  No cost threshold, no cap per sequence: filter the result."""
-        k = _check_k_refine(k)[0]
-        q, lens, pg, off = self._phrase_args(phrases, lengths, groups, exclude_same_group, sequences, splits, phrase_chunk, block_phrases)
-        P = int(lens.size)
-        dev = self.device
-        costs, seqs, spans = _phrase_outputs(P, k, dev)
-        if P == 0:
-            return costs, seqs, spans
-        lib = _lib.load()
-        qd = self._prep(q)
-        N = len(self)
-        seq_id, seq_grp = self._sequence_tables(off, pg is not None)
-        metric = METRICS[self.metric]
-        with torch.cuda.device(dev):
-            for p0 in range(0, P, int(phrase_chunk)):
-                p1 = min(P, p0 + int(phrase_chunk))
-                b = self._phrase_blocks(lib, qd, lens, p0, p1, off, k, splits, block_phrases, pg)
-                ws = torch.empty(int(lib.sylber_dtw_workspace_bytes(b.nb, b.Pc, k, b.C)), dtype=torch.uint8, device=dev)
-                if _workspace_fill is not None:
-                    ws.fill_(_workspace_fill)
-                meta_d, sp_d, br_d, cut_d, pg_d = b.tables()
-                _lib.check(lib.sylber_dtw_occurrences(_vp(b.qp), b.nb, _vp(meta_d), _vp(sp_d), _vp(br_d), b.Pc, b.slots, _vp(self._x), N,
-                                                      self.dim, _vp(self._c), metric, k, _vp(seq_id), _vp(cut_d), b.C, _vp(pg_d),
-                                                      _vp(seq_grp), _vp(costs[p0:p1]), _vp(seqs[p0:p1]), _vp(spans[p0:p1]), _vp(ws),
-                                                      _stream(dev)), "sylber_dtw_occurrences")
-        return costs, seqs, spans
+        return self._scan_phrases(lambda: (self._scan32("sylber_dtw_occurrences"), None), phrases, k, None, None, lengths, groups,
+                                  exclude_same_group, sequences, splits, phrase_chunk, block_phrases, False, _workspace_fill)
 
     def search_occurrences_refined(self, phrases, k: int, refine: int = 4, storage: str = "fp16", *, lengths=None, groups=None,
                                    exclude_same_group: bool = False, sequences=None, splits: int = 0,
@@ -509,51 +430,18 @@ class SyllableIndex:
         searched: stage 1 ranks a sequence by its best match, so a sequence whose many occurrences are all mediocre can be left
         out.  Nothing returned depends on ``splits``, ``phrase_chunk``, ``block_phrases``, stale workspace contents or how the
         index was built.  Limits and refusals are ``search_phrases_refined``'s."""
-        k, m = _check_k_refine(k, refine, rerank=True)
-        if storage not in STORAGES:
-            raise ValueError("storage must be 'fp16' or 'bf16', got %r" % (storage,))
-        q, lens, pg, off = self._phrase_args(phrases, lengths, groups, exclude_same_group, sequences, splits, phrase_chunk, block_phrases)
-        P = int(lens.size)
-        dev = self.device
-        costs, seqs, spans = _phrase_outputs(P, k, dev)
-        cand = torch.empty((P, m), dtype=torch.int32, device=dev)
-        coarse = torch.empty((P, m), dtype=torch.float32, device=dev)
-        if P == 0:
-            return (costs, seqs, spans, cand.to(torch.int64), coarse) if return_candidates else (costs, seqs, spans)
-        x16 = self.half_rows(storage)
-        lib = _lib.load()
-        qd = self._prep(q)
-        N, S = len(self), off.size - 1
-        seq_id, seq_grp = self._sequence_tables(off, pg is not None)
-        off_d = _on_device(off, np.int32, dev)
-        metric, code = METRICS[self.metric], STORAGES[storage][0]
-        step = max(1, OCC_RERANK_ENTRIES // (m * k))                   # phrases per re-rank launch: bounds its m lists of k per phrase
-        with torch.cuda.device(dev):
-            st = _stream(dev)
-            for p0 in range(0, P, int(phrase_chunk)):
-                p1 = min(P, p0 + int(phrase_chunk))
-                b = self._phrase_blocks(lib, qd, lens, p0, p1, off, m, splits, block_phrases, pg)
-                qn = _row_norms(b.qp) if self.metric == "l2" else None
-                q16 = self._pack16(b.qp, storage, refuse=False)
-                ws = torch.empty(int(lib.sylber_dtw16_workspace_bytes(b.Pc, m, b.C)), dtype=torch.uint8, device=dev)
-                wo = torch.empty(int(lib.sylber_dtw_occ_workspace_bytes(min(step, b.Pc), m, k)), dtype=torch.uint8, device=dev)
-                if _workspace_fill is not None:
-                    ws.fill_(_workspace_fill)
-                    wo.fill_(_workspace_fill)
-                meta_d, sp_d, br_d, cut_d, pg_d = b.tables()
-                place_d, len_d = _on_device(b.place, np.int32, dev), _on_device(b.ln, np.int32, dev)
-                _lib.check(lib.sylber_dtw16_scan(_vp(q16), b.nb, _vp(meta_d), _vp(sp_d), _vp(br_d), b.Pc, b.slots, _vp(x16), N, self.dim,
-                                                 _vp(self._c), _vp(qn), metric, code, m, _vp(seq_id), _vp(cut_d), b.C, _vp(pg_d),
-                                                 _vp(seq_grp), _vp(cand[p0:p1]), _vp(coarse[p0:p1]), _vp(ws), st), "sylber_dtw16_scan")
-                for r0 in range(0, b.Pc, step):
-                    r1 = min(b.Pc, r0 + step)
-                    _lib.check(lib.sylber_dtw_rerank_occurrences(_vp(b.qp), b.nb, _vp(qn), _vp(place_d[r0:r1]), _vp(len_d[r0:r1]), r1 - r0,
-                                                                 _vp(self._x), N, self.dim, _vp(self._c), metric,
-                                                                 _vp(cand[p0 + r0:p0 + r1]), m, _vp(off_d), S, k,
-                                                                 _vp(costs[p0 + r0:p0 + r1]), _vp(seqs[p0 + r0:p0 + r1]),
-                                                                 _vp(spans[p0 + r0:p0 + r1]), _vp(wo), st),
-                               "sylber_dtw_rerank_occurrences")
-        return (costs, seqs, spans, cand.to(torch.int64), coarse) if return_candidates else (costs, seqs, spans)
+        def rerank(c):
+            step = max(1, OCC_RERANK_ENTRIES // (c.m * c.k))           # phrases per re-rank launch: bounds its m lists of k per phrase
+            wo = c.workspace(c.lib.sylber_dtw_occ_workspace_bytes(min(step, c.b.Pc), c.m, c.k))
+            for r0 in range(0, c.b.Pc, step):
+                r1 = min(c.b.Pc, r0 + step)
+                _lib.check(c.lib.sylber_dtw_rerank_occurrences(_vp(c.b.qp), c.b.nb, _vp(c.qn), _vp(c.place_d[r0:r1]), _vp(c.len_d[r0:r1]),
+                                                               r1 - r0, _vp(self._x), c.N, c.dim, _vp(self._c), c.metric, _vp(c.cand[r0:r1]),
+                                                               c.m, _vp(c.off_d), c.S, c.k, _vp(c.costs[r0:r1]), _vp(c.seqs[r0:r1]),
+                                                               _vp(c.spans[r0:r1]), _vp(wo), c.st), "sylber_dtw_rerank_occurrences")
+
+        return self._scan_phrases(lambda: (self._scan16(storage), rerank), phrases, k, refine, storage, lengths, groups, exclude_same_group,
+                                  sequences, splits, phrase_chunk, block_phrases, return_candidates, _workspace_fill)
 
     def search_phrases_seeded(self, phrases, seed_scores, seed_ids, k: int, refine: int = 4, *, lengths=None, groups=None,
                               exclude_same_group: bool = False, sequences=None, phrase_chunk: int = DEFAULT_PHRASE_CHUNK,
@@ -584,7 +472,8 @@ class SyllableIndex:
         ``phrase_chunk``.  ``ValueError`` before any launch: ``search_phrases_refined``'s checks, seed tensors of another shape or
         dtype, an id outside ``[-1, N)``."""
         k, m = _check_k_refine(k, refine, rerank=True)
-        q, lens, pg, off = self._phrase_args(phrases, lengths, groups, exclude_same_group, sequences, 0, phrase_chunk, 0)
+        q, lens, pg, off = _phrase_args(len(self), self.dim, self.device, self.sequence_offsets, phrases, lengths, groups, exclude_same_group,
+                                        sequences, 0, phrase_chunk, 0)
         P, R = int(lens.size), int(q.shape[0])
         dev = self.device
         sc = seed_scores if torch.is_tensor(seed_scores) else torch.from_numpy(np.asarray(seed_scores))
@@ -619,13 +508,12 @@ class SyllableIndex:
                 _lib.check(lib.sylber_phrase_vote(_vp(sc), _vp(si), seeds, _vp(row_d[p0:p1]), _vp(len_d[p0:p1]), p1 - p0, _vp(off_d), S,
                                                   metric, _vp(pg_d[p0:p1] if pg_d is not None else None), _vp(seq_grp), m,
                                                   _vp(cand[p0:p1]), _vp(bound[p0:p1]), st), "sylber_phrase_vote")
-                b = self._phrase_blocks(lib, qd, lens, p0, p1, off, m, 0, 0, None)
-                qn = _row_norms(b.qp) if self.metric == "l2" else None
-                ws = torch.empty(int(lib.sylber_dtw16_workspace_bytes(b.Pc, m, 1)), dtype=torch.uint8, device=dev)
-                place_d = _on_device(b.place, np.int32, dev)
-                _lib.check(lib.sylber_dtw_rerank(_vp(b.qp), b.nb, _vp(qn), _vp(place_d), _vp(len_d[p0:p1]), b.Pc, _vp(self._x), N, self.dim,
-                                                 _vp(self._c), metric, _vp(cand[p0:p1]), m, _vp(off_d), S, k, _vp(costs[p0:p1]),
-                                                 _vp(seqs[p0:p1]), _vp(spans[p0:p1]), _vp(ws), st), "sylber_dtw_rerank")
+                b = _phrase_blocks(lib, dev, qd, lens, p0, p1, off, m, 0, 0, None)
+                c = _PhraseChunk(None, lib=lib, dev=dev, st=st, N=N, dim=self.dim, metric=metric, k=k, m=m, S=S, off_d=off_d, b=b,
+                                 qn=_row_norms(b.qp) if self.metric == "l2" else None, place_d=_on_device(b.place, np.int32, dev),
+                                 len_d=len_d[p0:p1], cand=cand[p0:p1], costs=costs[p0:p1], seqs=seqs[p0:p1], spans=spans[p0:p1])
+                c.ws = c.workspace(lib.sylber_dtw16_workspace_bytes(b.Pc, m, 1))
+                _rerank_launch(c, self._x, self._c)
         return (costs, seqs, spans, cand.to(torch.int64), bound) if return_candidates else (costs, seqs, spans)
 
     # ---- warping paths -------------------------------------------------------------------------------------------------------------
@@ -666,20 +554,31 @@ class SyllableIndex:
 
         return _align_phrases(N, self.dim, self.device, self.metric, phrases, spans, lengths, pair_chunk, run, _tracked_start)
 
-    # the arguments and the plumbing that every phrase search shares: _index.py holds them, these keep their names
-    def _phrase_args(self,phrases, lengths, groups, exclude_same_group, sequences, splits, phrase_chunk, block_phrases):
-        """the checks of a phrase search -> ``(phrase rows [sum m, D] as given, lengths int64 [P], the phrases' groups on the host or
-        None, sequence offsets int64 [S + 1])``, or ``ValueError``"""
-        return _phrase_args(len(self), self.dim, self.device, self.sequence_offsets, phrases, lengths, groups, exclude_same_group,
-                            sequences, splits, phrase_chunk, block_phrases)
+    # ---- the stages that the scanning phrase searches hand to _index.py's _scan_phrases ------------------------------------------------
+    def _scan_phrases(self, stages, *args):
+        return _scan_phrases(len(self), self.dim, self.device, self.metric, self._g, self.sequence_offsets, stages, *args)
 
-    def _sequence_tables(self, off: np.ndarray, with_groups: bool):
-        """plumbing: the sequence of every row and (for the exclusion) the group of every sequence, on the device"""
-        return _sequence_tables(off, self._g if with_groups else None, self.device)
+    def _scan32(self, entry: str):
+        """stage 1 on the fp32 rows, the only stage: ``sylber_dtw_search`` or ``sylber_dtw_occurrences``, which take the same arguments"""
+        def scan(c):
+            b = c.b
+            ws = c.workspace(c.lib.sylber_dtw_workspace_bytes(b.nb, b.Pc, c.k, b.C))
+            _lib.check(getattr(c.lib, entry)(_vp(b.qp), b.nb, _vp(c.meta_d), _vp(c.sp_d), _vp(c.br_d), b.Pc, b.slots, _vp(self._x), c.N, c.dim,
+                                             _vp(self._c), c.metric, c.k, _vp(c.seq_id), _vp(c.cut_d), b.C, _vp(c.pg_d), _vp(c.seq_grp),
+                                             _vp(c.costs), _vp(c.seqs), _vp(c.spans), _vp(ws), c.st), entry)
+        return scan
 
-    def _phrase_blocks(self, lib, qd, lens, p0: int, p1: int, off, list_size: int, splits, block_phrases, pg) -> "_PhraseBlocks":
-        """phrases ``p0 : p1`` of the prepared rows ``qd`` packed by ``sylber_dtw_plan`` for lists of ``list_size`` entries"""
-        return _phrase_blocks(lib, self.device, qd, lens, p0, p1, off, list_size, splits, block_phrases, pg)
+    def _scan16(self, storage: str):
+        """stage 1 of the two-stage searches: ``sylber_dtw16_scan`` on ``half_rows(storage)``, which may refuse"""
+        x16, code = self.half_rows(storage), STORAGES[storage][0]
+
+        def scan(c):
+            b = c.b
+            c.ws = c.workspace(c.lib.sylber_dtw16_workspace_bytes(b.Pc, c.m, b.C))
+            _lib.check(c.lib.sylber_dtw16_scan(_vp(c.q16), b.nb, _vp(c.meta_d), _vp(c.sp_d), _vp(c.br_d), b.Pc, b.slots, _vp(x16), c.N, c.dim,
+                                               _vp(self._c), _vp(c.qn), c.metric, code, c.m, _vp(c.seq_id), _vp(c.cut_d), b.C, _vp(c.pg_d),
+                                               _vp(c.seq_grp), _vp(c.cand), _vp(c.coarse), _vp(c.ws), c.st), "sylber_dtw16_scan")
+        return scan
 
     # ---- persistence ----------------------------------------------------------------------------------------------------------------
     def save(self, path: str) -> None:
@@ -921,7 +820,8 @@ class IVFSyllableIndex:
         if isinstance(seeds, bool) or int(seeds) != seeds or not 1 <= int(seeds) <= MAX_SEEDS:
             raise ValueError("seeds must be an integer in [1, %d], got %r" % (MAX_SEEDS, seeds))
         seeds = int(seeds)
-        q, lens, pg, off = idx._phrase_args(phrases, lengths, groups, exclude_same_group, sequences, 0, phrase_chunk, 0)
+        q, lens, pg, off = _phrase_args(len(idx), idx.dim, idx.device, idx.sequence_offsets, phrases, lengths, groups, exclude_same_group,
+                                        sequences, 0, phrase_chunk, 0)
         _check_splits_chunk(item_tiles, query_chunk, "item_tiles")
         dev = idx.device
         P = int(lens.size)

@@ -171,6 +171,7 @@ def test_equals_search_where_the_bound_decides(storage):
 @pytest.mark.parametrize("metric", ["l2", "cosine"])
 def test_bitwise_independent_of_splits_chunks_adds_and_workspace(metric, storage):
     from sylber_amd import SyllableIndex, _lib
+    from sylber_amd._index import _pack16
     from sylber_amd.kmeans import _stream, _vp
     from sylber_amd.search import METRICS, STORAGES as ST
     rng = np.random.default_rng(11)
@@ -195,7 +196,7 @@ def test_bitwise_independent_of_splits_chunks_adds_and_workspace(metric, storage
     lib = _lib.load()
     m = k * refine
     qd = one._prep(_t(q))
-    q16 = one._pack16(qd, storage, refuse=False)
+    q16 = _pack16(qd, storage, refuse=False)
     for splits in (0, 3):
         ws = torch.full((int(lib.sylber_knn16_workspace_bytes(n, N, D, m, splits)) // 4,), float("nan"), device=DEV)
         cand = torch.empty((n, m), dtype=torch.int32, device=DEV)

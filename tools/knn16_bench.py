@@ -69,6 +69,7 @@ def main():
     ap.add_argument("--no-torch", action="store_true")
     args = ap.parse_args()
     from sylber_amd import SyllableIndex, _lib
+    from sylber_amd._index import _pack16
     from sylber_amd.search import STORAGES
     lib = _lib.load()
     dev = torch.device("cuda:0")
@@ -108,7 +109,7 @@ def main():
                 rows.append(row)
             for st in args.storages.split(","):
                 code = STORAGES[st][0]
-                q16 = idx._pack16(q, st, refuse=False)
+                q16 = _pack16(q, st, refuse=False)
                 for k, refine in shapes:
                     m = k * refine
                     ts, tr = alternating_ms(lambda: idx.search(q, k), lambda: idx.search_refined(q, k, refine, st), args.iters)

@@ -74,14 +74,14 @@ def rerank_alone(idx, phrases, lens, cand, k):
     """a closure that runs stage 2 alone (``sylber_dtw_rerank``) on the candidates ``cand [P, m]`` of one call; the packing of the
     phrases, the tables and the buffers are made here, before the clock starts"""
     from sylber_amd import _lib
-    from sylber_amd._index import _on_device, _phrase_outputs, _row_norms
+    from sylber_amd._index import _on_device, _phrase_blocks, _phrase_outputs, _row_norms
     from sylber_amd.kmeans import _stream, _vp
     lib, dev = _lib.load(), idx.device
     lens = np.asarray(lens, np.int64)
     P, m = cand.shape
     off = idx.sequence_offsets()
     off_d = _on_device(off, np.int32, dev)
-    b = idx._phrase_blocks(lib, idx._prep(phrases), lens, 0, P, off, m, 0, 0, None)
+    b = _phrase_blocks(lib, dev, idx._prep(phrases), lens, 0, P, off, m, 0, 0, None)
     qn = _row_norms(b.qp)
     ws = torch.empty(int(lib.sylber_dtw16_workspace_bytes(P, m, 1)), dtype=torch.uint8, device=dev)
     place_d, len_d = _on_device(b.place, np.int32, dev), _on_device(lens, np.int32, dev)
