@@ -19,8 +19,9 @@
 //     bits of dtw_search_kernel's) and the wavefront over a chunk are dtw_pair.h's, shared with dtw_occ_rerank_kernel below and
 //     dtw_align.hip's dtw_align_kernel; the cell is dtw_tile.h's dt_cell.  The lane of the last row tracks (best cost, start, end),
 //     the smallest end on ties.  Only the chunk loop depends on the length.
-//   * dtw_rank_kernel: one wave per phrase ranks its m pair results by (cost, sequence) and writes the best k with spans as row ids.
-//     A second launch: nothing relies on an order between workgroups.
+//     The body is dtw_pair.h's dp_rerank_pair, which dtw_codes.hip runs on a coded database.
+//   * dtw_rank_kernel (dtw_pair.h): one wave per phrase ranks its m pair results by (cost, sequence) and writes the best k with
+//     spans as row ids.  A second launch: nothing relies on an order between workgroups.
 //   * dtw_occ_rerank_kernel (at the end of the file; SyllableIndex.search_occurrences_refined, tests/occ_ref.py): dtw_rerank_kernel's
 //     walk (the same pieces of dtw_pair.h, dt_occ_cell for the cell and two ballots after it) with every non-overlapping occurrence
 //     of the candidate kept, k per pair in LDS; merged and reported by dtw_occ.h.
@@ -202,90 +203,13 @@ __global__ __launch_bounds__(64) void dtw_rerank_kernel(const float* __restrict_
                                                         const int32_t* __restrict__ cand, const int32_t* __restrict__ soff, int S,
                                                         int m, float* __restrict__ pc, int2* __restrict__ pspan) {
     __shared__ float dsm[DT_MAX_M * DP_LD];
-    const int lane = threadIdx.x;
-    const size_t pair = blockIdx.x;
-    const int p = (int)(pair / m);
-    const int sidx = cand[pair];
-    int j0 = 0, j1 = 0;
-    if (sidx >= 0 && sidx < S) {
-        j0 = soff[sidx]; j1 = soff[sidx + 1];
-        j0 = j0 < 0 ? 0 : j0; j1 = j1 > N ? N : j1;
-    }
-    if (j1 <= j0) {                                        // workgroup-uniform
-        if (lane == 0) { pc[pair] = INFINITY; pspan[pair] = make_int2(-1, -1); }
-        return;
-    }
-    const DpLane L(q, qsq, qrows, prow, plen, p, D, lane, DT_MAX_M);
-    DtLane st;
-    float* dr = dsm + lane * DP_LD;
-    for (int n0 = j0; n0 < j1; n0 += DP_CH) {
-        const int ncol = j1 - n0 < DP_CH ? j1 - n0 : DP_CH;
-        dp_chunk_costs(dr, L, x, D, cn, qsq != nullptr, n0, ncol, j1);
-        dp_walk(st, L, lane, n0, ncol, j0, [&](int j, int col, bool isstart, const DtUp& u) {
-            dt_cell<true>(st, u, lane == 0, L.lastrow, isstart, dr[j], col);
-        });
-    }
-    if (L.lastrow) {
-        pc[pair] = st.bc;
-        pspan[pair] = st.bc < INFINITY ? make_int2(st.bst, st.be) : make_int2(-1, -1);
-    }
+    dp_rerank_pair(dsm, DpRowsSrc{x, D}, q, qsq, qrows, prow, plen, N, D, cn, cand, soff, S, m, pc, pspan);
 }
-
-// One wave per phrase i (4 per workgroup).  Lane e (and e + 64) owns pair (i, cand[i][e]); a candidate of -1 or a cost that is not
-// below +inf becomes a (+inf, INT_MAX) filler.  Rank = entries strictly before it under (cost, sequence, position) (the position
-// only orders the fillers); ranks < k are reported as dtw_finish_kernel reports them: spans as (first row, one past the last row),
-// fillers (+inf, -1, (-1, -1)).
-__global__ __launch_bounds__(256) void dtw_rank_kernel(const float* __restrict__ pc, const int2* __restrict__ pspan,
-                                                       const int32_t* __restrict__ cand, int P, int m, int k, float* __restrict__ cost,
-                                                       int64_t* __restrict__ seq, int64_t* __restrict__ span) {
-    __shared__ float ss[4][KN_KMAX];
-    __shared__ int si[4][KN_KMAX];
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    int i = blockIdx.x * 4 + wave;
-    const bool live = i < P;
-    i = live ? i : P - 1;
-    float sv[KN_KMAX / 64];
-    int sj[KN_KMAX / 64];
-#pragma unroll
-    for (int h = 0; h < KN_KMAX / 64; ++h) {
-        const int e = lane + 64 * h;
-        sv[h] = INFINITY; sj[h] = INT_MAX;
-        if (e < m) {
-            const float v = pc[(size_t)i * m + e];
-            const int j = cand[(size_t)i * m + e];
-            if (j >= 0 && v < INFINITY) { sv[h] = v; sj[h] = j; }
-            ss[wave][e] = sv[h]; si[wave][e] = sj[h];
-        }
-    }
-    __syncthreads();
-    if (!live) return;
-#pragma unroll
-    for (int h = 0; h < KN_KMAX / 64; ++h) {
-        const int e = lane + 64 * h;
-        if (e >= m) continue;
-        int rank = 0;
-        for (int f = 0; f < m; ++f) {
-            const float ev = ss[wave][f];
-            const int ej = si[wave][f];
-            rank += (kn_better(ev, ej, sv[h], sj[h]) || (ev == sv[h] && ej == sj[h] && f < e)) ? 1 : 0;
-        }
-        if (rank < k) {
-            const size_t o = (size_t)i * k + rank;
-            if (sj[h] == INT_MAX) { cost[o] = INFINITY; seq[o] = -1; span[2 * o] = -1; span[2 * o + 1] = -1; }
-            else {
-                const int2 sp = pspan[(size_t)i * m + e];
-                cost[o] = sv[h]; seq[o] = sj[h]; span[2 * o] = sp.x; span[2 * o + 1] = (int64_t)sp.y + 1;
-            }
-        }
-    }
-}
-
-static int64_t d16_rerank_bytes(int64_t P, int64_t m) { return kn_al(P * m * 4) + kn_al(P * m * 8); }
 
 extern "C" int64_t sylber_dtw16_workspace_bytes(int32_t n_phrases, int32_t m, int32_t cuts) {
     if (n_phrases < 1 || m < 1 || m > KN_KMAX || cuts < 1) return -1;
     // the C partial lists of the scan and their merge rounds (KnPartials); then, in the same bytes, the pair results of the re-rank
-    const int64_t scan = kn_partials_bytes(n_phrases, cuts, m), rr = d16_rerank_bytes(n_phrases, m);
+    const int64_t scan = kn_partials_bytes(n_phrases, cuts, m), rr = dp_rerank_bytes(n_phrases, m);
     return scan > rr ? scan : rr;
 }
 
@@ -325,16 +249,11 @@ extern "C" int sylber_dtw_rerank(const float* q_dev, int32_t n_blocks, const flo
                       m < 1 || m > KN_KMAX || k < 1 || k > m ? "need 1 <= k <= m <= 128" : nullptr,
                       "n_phrases x m is too large: use smaller phrase chunks", n_blocks, n_phrases, n_seq, N, D, q_norm_dev, db_norm_dev, metric,
                       (int64_t)n_phrases * m > INT32_MAX, qn, cn)) return 1;
-    char* w = (char*)workspace_dev;
-    float* pc = (float*)w; w += kn_al((int64_t)n_phrases * m * 4);
-    int2* pspan = (int2*)w;
+    const DpPairResults r(workspace_dev, n_phrases, m);
     hipLaunchKernelGGL(dtw_rerank_kernel, dim3((unsigned)((int64_t)n_phrases * m)), dim3(64), 0, s, q_dev, qn, n_blocks * KN_BM, phrase_row_dev,
-                       phrase_len_dev, db_dev, N, D, cn, cand_dev, seq_offsets_dev, n_seq, m, pc, pspan);
+                       phrase_len_dev, db_dev, N, D, cn, cand_dev, seq_offsets_dev, n_seq, m, r.pc, r.pspan);
     HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(dtw_rank_kernel, dim3((unsigned)((n_phrases + 3) / 4)), dim3(256), 0, s, pc, pspan, cand_dev, n_phrases, m, k, cost_dev,
-                       seq_dev, span_dev);
-    HIP_TRY(hipGetLastError());
-    return 0;
+    return dp_rank_launch(r, cand_dev, n_phrases, m, k, cost_dev, seq_dev, span_dev, s);
 }
 
 // ---- every occurrence of a phrase among candidate sequences (SyllableIndex.search_occurrences_refined) ----------------------------
@@ -369,7 +288,7 @@ __global__ __launch_bounds__(64) void dtw_occ_rerank_kernel(const float* __restr
     float* dr = dsm + lane * DP_LD;
     for (int n0 = j0; n0 < j1; n0 += DP_CH) {              // no chunk for a candidate of -1: its list stays fillers
         const int ncol = j1 - n0 < DP_CH ? j1 - n0 : DP_CH;
-        dp_chunk_costs(dr, L, x, D, cn, qsq != nullptr, n0, ncol, j1);       // its first barrier, the first time: the list is cleared
+        dp_chunk_costs(dr, L, DpRows{x, D}, D, cn, qsq != nullptr, n0, ncol, j1);       // its first barrier, the first time: the list is cleared
         bool out = false, end = false;                     // what the lane's cell of this step owes the list
         float ec = INFINITY;
         int es = 0, ee = 0;

@@ -22,7 +22,9 @@ came in one ``build`` or through later ``add`` calls, or what the workspace held
 
 ``IVFPQSyllableIndex`` puts the same codes behind ``IVFSyllableIndex``'s lists: a search scans the codes of the ``nprobe`` nearest
 lists only (``sylber_ivfpq_scan``).  tests/ivfpq_ref.py restates that composition.  With ``residual=True`` the codes are those of
-each row's residual to its list's centroid (``sylber_ivfpq_scan_residual``; tests/ivfpq_residual_ref.py).
+each row's residual to its list's centroid (``sylber_ivfpq_scan_residual``; tests/ivfpq_residual_ref.py).  Its ``search_phrases`` is
+``IVFSyllableIndex``'s seed, vote and exact re-rank on those lists; once the fp32 rows are dropped the exact DTW and ``align_phrases``
+run on the codes themselves (csrc/dtw_codes.hip; tests/ivfpq_phrase_ref.py).
 
 The two classes differ in where the codes lie and which scan reads them; what they share is written once: the rules of every index in
 _index.py, and here ``_pq_search`` (the search body), ``_decode`` / ``_check_ids`` and ``_saved_codes`` / ``_saved_rows`` (the file)."""
@@ -34,11 +36,11 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._index import (DEFAULT_PHRASE_CHUNK, DEFAULT_QUERY_CHUNK, METRICS, STORAGES, _added_rows, _base_arrays, _check_k_refine,
+from ._index import (DEFAULT_PHRASE_CHUNK, DEFAULT_QUERY_CHUNK, MAX_SEEDS, METRICS, STORAGES, _added_rows, _base_arrays, _check_k_refine,
                      _check_nprobe, _check_splits_chunk, _chunked_workspace_bytes, _group_runs, _list_layout, _on_device, _outputs, _pack16,
-                     _prep, _provenance, _query_groups, _result, _row_norms, _rows, _rows_of_width, _scan_phrases)
+                     _phrase_args, _prep, _provenance, _query_groups, _result, _row_norms, _rows, _rows_of_width, _scan_phrases)
 from .kmeans import _device, _stream, _vp
-from .search import IVFSyllableIndex, SyllableIndex, _align_launch, _align_phrases, _rerank_launch
+from .search import IVFSyllableIndex, SyllableIndex, _align_launch, _align_phrases, _rerank_launch, _seeded_phrases
 
 KSUB = 256                      # centroids per sub-space: one uint8 per code
 MAX_M = 64                      # PQ_MAX_M of csrc/pq.hip: at least two queries' tables (M KiB each) fit beside the top lists in LDS
@@ -639,8 +641,9 @@ class IVFPQSyllableIndex:
                              s the slot of the row's list: ||q - xhat||^2 - ||q||^2, respectively -2 q . xhat
 
     Build one with ``IVFPQSyllableIndex.build``.  The device holds ``M + 9`` bytes per row (code, original id, group, mask) in list
-    order -- ``M + 13`` with residual codes under ``"l2"`` (``nrm``) -- plus the centroids and codebooks; ``ix.index`` is the source
-    ``SyllableIndex`` with the fp32 rows (shared, not copied) until ``drop_rows()``."""
+    order -- ``M + 13`` with residual codes under ``"l2"`` (``nrm``) -- plus the centroids and codebooks, and 4 more (8 under ``"l2"``)
+    once ``search_phrases`` or ``align_phrases`` has run with ``rerank=False``; ``ix.index`` is the source ``SyllableIndex`` with the
+    fp32 rows (shared, not copied) until ``drop_rows()``."""
 
     def __init__(self, index: Optional[SyllableIndex], centroids: torch.Tensor, codebooks: torch.Tensor, labels: torch.Tensor,
                  codes: torch.Tensor, bad: torch.Tensor, groups: torch.Tensor, *, metric: str, device: torch.device, prov=None,
@@ -657,6 +660,8 @@ class IVFPQSyllableIndex:
         self._prov = prov                       # provenance of the rows once the fp32 rows are dropped
         self._span_dtype = np.int64 if span_int else np.float64
         self._last = None
+        self._seeds = None                      # what the last search_phrases keeps for last_search's "seen"
+        self._seq_cache = None                  # (N, default sequence offsets)
         self._layout(labels, codes, bad, groups, self._norms_of(codes, labels))
 
     # ---- building -------------------------------------------------------------------------------------------------------------------
@@ -707,6 +712,7 @@ class IVFPQSyllableIndex:
         self._rg = groups.index_select(0, order)
         self._nrm = nrm.index_select(0, order) if nrm is not None else None     # [N] ||xhat||^2 in position order (residual "l2")
         self._probe_sizes = torch.cat([self.list_sizes, self.list_sizes.new_zeros(1)])      # [-1]: a probe slot without a list
+        self._pos = self._pc = None             # what the phrase search on the codes adds, built on first use (_phrase_state)
 
     def _by_id(self, t: torch.Tensor) -> torch.Tensor:
         """a per-position tensor in id order"""
@@ -791,21 +797,35 @@ class IVFPQSyllableIndex:
     @property
     def nbytes(self) -> int:
         """bytes this index holds on the device: ``M + 9`` per row (code, id, group, mask; ``M + 13`` with the ``nrm`` of residual codes
-        under ``"l2"``), the list offsets, the centroids and the codebooks with their norms, and ``4 N D`` for the fp32 rows while they are held (the ``4 N`` bytes of an ``"l2"`` source
-        index's row norms are not counted)"""
+        under ``"l2"``), the list offsets, the centroids and the codebooks with their norms, what ``search_phrases(rerank=False)`` has
+        built so far (``4 N`` of positions, and ``4 N`` of reconstruction norms under ``"l2"``), and ``4 N D`` for the fp32 rows while
+        they are held (the ``4 N`` bytes of an ``"l2"`` source index's row norms are not counted)"""
         n = self._codes.numel() + 9 * len(self) + 4 * self._off.numel() + 4 * self.centroids.numel() + 4 * self.nlist \
-            + 4 * self.codebooks.numel() + 4 * self._cnorm.numel() + (4 * self._nrm.numel() if self._nrm is not None else 0)
+            + 4 * self.codebooks.numel() + 4 * self._cnorm.numel() + (4 * self._nrm.numel() if self._nrm is not None else 0) \
+            + sum(4 * t.numel() for t in (self._pos, self._pc) if t is not None)
         return int(n + (4 * len(self) * self.dim if self.index is not None else 0))
 
     @property
     def last_search(self) -> Optional[dict]:
         """``{"pairs", "fraction", "workspace_bytes"}`` of the last ``search``: the (query, row) pairs it scanned, their share of
-        ``n N`` and the workspace it took.  Reading it waits for the device; ``search`` does not."""
+        ``n N`` and the workspace it took; after a ``search_phrases`` those of its stage 1a and ``"seen"``, the mean number of seen
+        sequences per phrase.  Reading it waits for the device; the searches do not."""
         if self._last is None:
             return None
         pairs, n, N, ws = self._last
         pairs = int(pairs)
-        return {"pairs": pairs, "fraction": pairs / (float(n) * N) if n else 0.0, "workspace_bytes": ws}
+        out = {"pairs": pairs, "fraction": pairs / (float(n) * N) if n else 0.0, "workspace_bytes": ws}
+        if self._seeds is not None:
+            sc, si, off, lens = self._seeds                 # the seen sequences of each phrase, counted as the vote sees them
+            P, dev = int(lens.size), self.device
+            out["seen"] = 0.0
+            if P:
+                d = sc if self.metric == "l2" else torch.clamp_min(1.0 - sc, 0.0)
+                valid = (si >= 0) & ~torch.isnan(sc) & ~torch.isposinf(d)
+                seq = torch.bucketize(si, torch.from_numpy(off[1:]).to(dev), right=True)
+                owner = torch.repeat_interleave(torch.arange(P, device=dev), torch.from_numpy(lens).to(dev))
+                out["seen"] = float(torch.unique((owner[:, None] * (off.size - 1) + seq)[valid]).numel()) / P
+        return out
 
     def decode(self, ids) -> torch.Tensor:
         """``[len(ids), D]`` fp32 on the device: the rows' reconstruction from their codes (for ``"cosine"``, of the unit rows); with
@@ -864,8 +884,139 @@ class IVFPQSyllableIndex:
         out, n, nbytes = _pq_search(self, "ix", queries, k, mc, rerank, groups, exclude_same_group, return_candidates, splits, query_chunk,
                                     _workspace_fill, lambda m, splits: _lib.load().sylber_ivfpq_workspace_bytes(m, nprobe, mc, splits), scan,
                                     ip_table=self._residual)
-        self._last = (pairs[0], n, len(self), nbytes)
+        self._last, self._seeds = (pairs[0], n, len(self), nbytes), None
         return out
+
+    # ---- phrase search --------------------------------------------------------------------------------------------------------------
+    def sequence_offsets(self) -> np.ndarray:
+        """as ``SyllableIndex.sequence_offsets``, from the index's groups: it works after ``drop_rows()``"""
+        N = len(self)
+        if self._seq_cache is None or self._seq_cache[0] != N:
+            self._seq_cache = (N, _group_runs(self._by_id(self._rg), N))
+        return self._seq_cache[1].copy()
+
+    def _phrase_state(self) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+        """what the exact DTW on the codes needs beside the lists, built on first use and dropped when ``add`` lays the lists out
+        again: ``pos [N]`` int32, row id -> position, and under ``"l2"`` ``c [N]`` fp32 in id order: ``_row_norms`` of the rows that
+        ``decode`` returns (``NORM_CHUNK`` at a time), NaN for a masked row -- what a ``SyllableIndex`` built from the decoded rows
+        holds, and not ``_nrm``, whose chain is the scan's"""
+        if self._pos is None:
+            N, dev = len(self), self.device
+            pos = torch.empty(N, dtype=torch.int32, device=dev)
+            pos[self._rid.to(torch.int64)] = torch.arange(N, dtype=torch.int32, device=dev)
+            if self.metric == "l2":
+                lab = torch.full((N,), -1, dtype=torch.int32, device=dev)       # by position
+                lab[:self._listed] = torch.repeat_interleave(torch.arange(self.nlist, dtype=torch.int32, device=dev), self.list_sizes)
+                parts = []
+                for r0 in range(0, N, NORM_CHUNK):
+                    c = self._codes[r0:r0 + NORM_CHUNK]
+                    parts.append(_row_norms(_decode_residual(c, lab[r0:r0 + NORM_CHUNK].contiguous(), self.centroids, self.codebooks)
+                                            if self._residual else _decode(c, self.codebooks)))
+                c = torch.cat(parts)
+                self._pc = self._by_id(torch.where(self._rbad != 0, torch.full_like(c, float("nan")), c))
+            self._pos = pos
+        return self._pos, self._pc
+
+    def _coded_db(self):
+        """the coded-database argument group of ``sylber_dtw_rerank_codes`` / ``sylber_dtw_align_codes`` up to ``nlist``, and ``c``"""
+        pos, pc = self._phrase_state()
+        lists = (_vp(self._off), _vp(self.centroids), self.nlist) if self._residual else (None, None, 0)
+        return (_vp(self._codes), _vp(self._rbad), _vp(pos), _vp(self.codebooks), self.M) + lists, pc
+
+    def _check_rerank(self, rerank: Optional[bool], verb: str) -> bool:
+        if rerank is None:
+            rerank = self.index is not None
+        if rerank and self.index is None:
+            raise ValueError("rerank=True needs the fp32 rows, which were dropped: %s with rerank=False" % verb)
+        if self.index is not None and len(self.index) != len(self):
+            raise ValueError("ix.index holds %d rows, the codes %d: add rows through ix.add" % (len(self.index), len(self)))
+        return bool(rerank)
+
+    def search_phrases(self, phrases, k: int, nprobe: int, seeds: int = 32, refine: int = 4, *, rerank: Optional[bool] = None, lengths=None,
+                       groups=None, exclude_same_group: bool = False, sequences=None, query_chunk: int = DEFAULT_QUERY_CHUNK,
+                       phrase_chunk: int = DEFAULT_PHRASE_CHUNK, splits: int = 0, return_candidates: bool = False, _workspace_fill=None):
+        """``IVFSyllableIndex.search_phrases`` on the compressed lists: seed, vote, exact re-rank -> ``(costs, seqs, spans)`` as
+        ``SyllableIndex.search_phrases`` returns them (plus ``cand`` int64 ``[P, m]`` and ``bound`` fp32 ``[P, m]`` with
+        ``return_candidates=True``).  The arguments are those of ``IVFSyllableIndex.search_phrases`` with ``rerank=`` added and
+        ``splits=`` (``search``'s test hook) in place of ``item_tiles=``; ``1 <= seeds <= 128``, ``m = k * refine <= 128``.
+
+        Stage 1a: ``ix.search(all phrase rows, k=seeds, nprobe, refine=1, rerank=rerank)``; with ``exclude_same_group`` and the
+        default sequences every row carries its phrase's group, with explicit ``sequences=`` stage 1a excludes nothing and the vote
+        drops the excluded sequences.  Stage 1b: ``sylber_phrase_vote`` on what stage 1a reported (the contract of
+        ``SyllableIndex.search_phrases_seeded``).
+
+        Stage 2, ``rerank=True`` (the default while the fp32 rows are held; ``ValueError`` once they are dropped):
+        ``ix.index.search_phrases_seeded``, so every returned cost and span is a real ``search_phrases`` cost and span, bit for bit.
+        ``rerank=False`` (the only mode after ``drop_rows()``): the same exact DTW on the rows that ``ix.decode`` returns, a masked row
+        being a NaN row (``+inf`` against every phrase row).  The rows are rebuilt from the code bytes, the codebooks and, for residual
+        codes, the list centroids inside the kernel's dot products (csrc/dtw_codes.hip, ``sylber_dtw_rerank_codes``): there is no
+        decoded scratch and no copy to the host.  Under ``"l2"`` with no masked row the whole call equals
+        ``SyllableIndex(ix.decode(arange(N)), metric="l2", groups=g).search_phrases_seeded(phrases, *ix.search(rows, seeds, nprobe,
+        rerank=False), k, refine)``, bit for bit.
+
+        ``bound`` ranks the candidates and certifies nothing, in either mode: with ``rerank=False`` the seeds' scores are sums of
+        table entries, not the ``d`` of the DTW's chain; with ``rerank=True`` the seeds are the best of the scan's candidates, not
+        each row's nearest rows.  So ``bound <= cost`` does not hold in general.
+
+        ``rerank=False`` needs ``pos`` (4 bytes per row) and under ``"l2"`` the norms of the reconstructions (4 more), built on the
+        first call, rebuilt after ``add``, counted in ``nbytes`` and not saved.  Once they and ``sequence_offsets()`` exist, a
+        ``rerank=False`` call only queues work: it never waits for the device.  ``ix.last_search`` keeps stage 1a's numbers and adds
+        ``"seen"``, both computed when it is read.  Nothing returned depends on ``query_chunk``, ``phrase_chunk``, ``splits``, stale
+        workspaces, ``build`` versus ``build`` + ``add``, a ``save`` / ``load`` round trip or, with ``rerank=False``, on whether the
+        rows are still held.  ``ValueError`` before any launch: what ``IVFSyllableIndex.search_phrases`` and ``ix.search`` refuse,
+        ``rerank=True`` without the rows, an ``ix.index`` of another length."""
+        rerank = self._check_rerank(rerank, "search")
+        N, dev = len(self), self.device
+        k, m = _check_k_refine(k, refine, rerank=True)
+        nprobe = _check_nprobe(nprobe, self.nlist)
+        if isinstance(seeds, bool) or int(seeds) != seeds or not 1 <= int(seeds) <= MAX_SEEDS:
+            raise ValueError("seeds must be an integer in [1, %d], got %r" % (MAX_SEEDS, seeds))
+        seeds = int(seeds)
+        q, lens, pg, off = _phrase_args(N, self.dim, dev, self.sequence_offsets, phrases, lengths, groups, exclude_same_group, sequences, 0,
+                                        phrase_chunk, 0)
+        _check_splits_chunk(splits, query_chunk)
+        own = pg is not None and sequences is None             # the rows' groups decide the default sequences: exclude in stage 1a
+        sc, si = self.search(q, seeds, nprobe, 1, rerank=rerank, groups=np.repeat(pg, lens) if own else None, exclude_same_group=own,
+                             query_chunk=query_chunk, splits=splits, _workspace_fill=_workspace_fill)
+        self._seeds = (sc, si, off, lens)
+        if rerank:
+            return self.index.search_phrases_seeded(q, sc, si, k, refine, lengths=lens, groups=groups, exclude_same_group=exclude_same_group,
+                                                    sequences=sequences, phrase_chunk=phrase_chunk, return_candidates=return_candidates,
+                                                    _trusted_ids=True)
+        db, pc = self._coded_db()
+
+        def rerank_codes(c):
+            b = c.b
+            _lib.check(c.lib.sylber_dtw_rerank_codes(_vp(b.qp), b.nb, _vp(c.qn), _vp(c.place_d), _vp(c.len_d), int(c.cand.shape[0]), *db, N,
+                                                     c.dim, _vp(pc), c.metric, _vp(c.cand), c.m, _vp(c.off_d), c.S, c.k, _vp(c.costs),
+                                                     _vp(c.seqs), _vp(c.spans), _vp(c.ws), c.st), "sylber_dtw_rerank_codes")
+
+        return _seeded_phrases(N, self.dim, dev, self.metric, self._by_id(self._rg), q, lens, pg, off, sc, si, k, m, phrase_chunk,
+                               return_candidates, rerank_codes, _workspace_fill)
+
+    def align_phrases(self, phrases, spans, lengths=None, pair_chunk: Optional[int] = None, *, rerank: Optional[bool] = None,
+                      _tracked_start: bool = False):
+        """the warping paths behind the spans of ``search_phrases`` -> ``(rows, steps, costs)`` as ``SyllableIndex.align_phrases``
+        returns them; ``rerank`` is what that search was given.  ``rerank=True`` (the default while the fp32 rows are held;
+        ``ValueError`` once they are dropped): ``ix.index.align_phrases``, on the rows the exact re-rank ran on.  ``rerank=False``:
+        the same alignment on the rows that ``ix.decode`` returns, rebuilt from the codes inside the kernel (csrc/dtw_codes.hip,
+        ``sylber_dtw_align_codes``; no scratch) -- so on spans from ``search_phrases(rerank=False)`` ``costs`` has the bits of its
+        costs, before and after ``drop_rows()``.  Nothing returned depends on ``pair_chunk``."""
+        rerank = self._check_rerank(rerank, "align")
+        if rerank:
+            return self.index.align_phrases(phrases, spans, lengths=lengths, pair_chunk=pair_chunk, _tracked_start=_tracked_start)
+        N, D, metric = len(self), self.dim, METRICS[self.metric]
+        state = []                                              # the lazy state, built behind align_phrases' checks
+
+        def run(lib, b, qn, place_d, len_d, pair_phrase, win, max_cols, rows, steps, costs, start, ws, st):
+            if not state:
+                state.extend(self._coded_db())
+            db, pc = state
+            _lib.check(lib.sylber_dtw_align_codes(_vp(b.qp), b.nb, _vp(qn), _vp(place_d), _vp(len_d), b.Pc, *db, N, D, _vp(pc), metric,
+                                                  _vp(pair_phrase), _vp(win), int(pair_phrase.shape[0]), max_cols, int(rows.shape[1]),
+                                                  _vp(rows), _vp(steps), _vp(costs), _vp(start), _vp(ws), st), "sylber_dtw_align_codes")
+
+        return _align_phrases(N, D, self.device, self.metric, phrases, spans, lengths, pair_chunk, run, _tracked_start)
 
     # ---- persistence ----------------------------------------------------------------------------------------------------------------
     def save(self, path: str) -> None:

@@ -88,6 +88,41 @@ def _rerank_launch(c: "_PhraseChunk", x, cn) -> None:
                                        _vp(c.ws), c.st), "sylber_dtw_rerank")
 
 
+def _seeded_phrases(N: int, dim: int, dev, metric: str, db_groups, q, lens, pg, off, sc, si, k: int, m: int, phrase_chunk,
+                    return_candidates: bool, rerank, fill=None):
+    """``search_phrases_seeded`` behind its checks, for an index of N rows of width ``dim`` with the rows' groups ``db_groups`` (in id
+    order, on the device): ``phrase_chunk`` phrases at a time, ``sylber_phrase_vote`` on the seeds ``sc, si`` (on the device), the
+    phrases packed as ``search_phrases`` packs them and ``rerank(c)``, which scores the chunk's candidates ``c.cand`` exactly into
+    ``c.costs, c.seqs, c.spans`` on the index's rows, however it holds them.  ``fill``: a test's workspace fill.  Queues work only."""
+    P, seeds, S = int(lens.size), int(sc.shape[1]), off.size - 1
+    costs, seqs, spans = _phrase_outputs(P, k, dev)
+    cand = torch.empty((P, m), dtype=torch.int32, device=dev)
+    bound = torch.empty((P, m), dtype=torch.float32, device=dev)
+    if P == 0:
+        return (costs, seqs, spans, cand.to(torch.int64), bound) if return_candidates else (costs, seqs, spans)
+    lib = _lib.load()
+    qd = _prep(q, metric, dev)
+    off_d = _on_device(off, np.int32, dev)
+    seq_grp = db_groups.index_select(0, off_d[:-1].to(torch.int64)) if pg is not None else None
+    row_d, len_d = _on_device(np.cumsum(lens) - lens, np.int32, dev), _on_device(lens, np.int32, dev)
+    pg_d = _on_device(pg, np.int32, dev) if pg is not None else None
+    code = METRICS[metric]
+    with torch.cuda.device(dev):
+        st = _stream(dev)
+        for p0 in range(0, P, int(phrase_chunk)):
+            p1 = min(P, p0 + int(phrase_chunk))
+            _lib.check(lib.sylber_phrase_vote(_vp(sc), _vp(si), seeds, _vp(row_d[p0:p1]), _vp(len_d[p0:p1]), p1 - p0, _vp(off_d), S,
+                                              code, _vp(pg_d[p0:p1] if pg_d is not None else None), _vp(seq_grp), m,
+                                              _vp(cand[p0:p1]), _vp(bound[p0:p1]), st), "sylber_phrase_vote")
+            b = _phrase_blocks(lib, dev, qd, lens, p0, p1, off, m, 0, 0, None)
+            c = _PhraseChunk(fill, lib=lib, dev=dev, st=st, N=N, dim=dim, metric=code, k=k, m=m, S=S, off_d=off_d, b=b,
+                             qn=_row_norms(b.qp) if metric == "l2" else None, place_d=_on_device(b.place, np.int32, dev),
+                             len_d=len_d[p0:p1], cand=cand[p0:p1], costs=costs[p0:p1], seqs=seqs[p0:p1], spans=spans[p0:p1])
+            c.ws = c.workspace(lib.sylber_dtw16_workspace_bytes(b.Pc, m, 1))
+            rerank(c)
+    return (costs, seqs, spans, cand.to(torch.int64), bound) if return_candidates else (costs, seqs, spans)
+
+
 def _align_phrases(N: int, dim: int, dev, metric: str, phrases, spans, lengths, pair_chunk, run, tracked: bool = False):
     """``align_phrases`` of an index of N rows of width ``dim``: the checks, the phrase rows prepared and packed as ``search_phrases``
     packs them, the pairs taken ``pair_chunk`` at a time.  ``run(lib, b, qn, place_d, len_d, pair_phrase, win, max_cols, rows,
@@ -474,8 +509,7 @@ class SyllableIndex:
         k, m = _check_k_refine(k, refine, rerank=True)
         q, lens, pg, off = _phrase_args(len(self), self.dim, self.device, self.sequence_offsets, phrases, lengths, groups, exclude_same_group,
                                         sequences, 0, phrase_chunk, 0)
-        P, R = int(lens.size), int(q.shape[0])
-        dev = self.device
+        R, N, dev = int(q.shape[0]), len(self), self.device
         sc = seed_scores if torch.is_tensor(seed_scores) else torch.from_numpy(np.asarray(seed_scores))
         si = seed_ids if torch.is_tensor(seed_ids) else torch.from_numpy(np.asarray(seed_ids))
         if sc.dim() != 2 or si.dim() != 2 or sc.shape != si.shape or sc.shape[0] != R:
@@ -485,36 +519,11 @@ class SyllableIndex:
         seeds = int(sc.shape[1])
         if not 1 <= seeds <= MAX_SEEDS:
             raise ValueError("seeds must be in [1, %d], got %d" % (MAX_SEEDS, seeds))
-        N, S = len(self), off.size - 1
         sc, si = sc.to(dev).contiguous(), si.to(dev).contiguous()
         if not _trusted_ids and R and (int(si.min()) < -1 or int(si.max()) >= N):
             raise ValueError("seed_ids must lie in [-1, %d)" % N)
-        costs, seqs, spans = _phrase_outputs(P, k, dev)
-        cand = torch.empty((P, m), dtype=torch.int32, device=dev)
-        bound = torch.empty((P, m), dtype=torch.float32, device=dev)
-        if P == 0:
-            return (costs, seqs, spans, cand.to(torch.int64), bound) if return_candidates else (costs, seqs, spans)
-        lib = _lib.load()
-        qd = self._prep(q)
-        off_d = _on_device(off, np.int32, dev)
-        seq_grp = self._g.index_select(0, off_d[:-1].to(torch.int64)) if pg is not None else None
-        row_d, len_d = _on_device(np.cumsum(lens) - lens, np.int32, dev), _on_device(lens, np.int32, dev)
-        pg_d = _on_device(pg, np.int32, dev) if pg is not None else None
-        metric = METRICS[self.metric]
-        with torch.cuda.device(dev):
-            st = _stream(dev)
-            for p0 in range(0, P, int(phrase_chunk)):
-                p1 = min(P, p0 + int(phrase_chunk))
-                _lib.check(lib.sylber_phrase_vote(_vp(sc), _vp(si), seeds, _vp(row_d[p0:p1]), _vp(len_d[p0:p1]), p1 - p0, _vp(off_d), S,
-                                                  metric, _vp(pg_d[p0:p1] if pg_d is not None else None), _vp(seq_grp), m,
-                                                  _vp(cand[p0:p1]), _vp(bound[p0:p1]), st), "sylber_phrase_vote")
-                b = _phrase_blocks(lib, dev, qd, lens, p0, p1, off, m, 0, 0, None)
-                c = _PhraseChunk(None, lib=lib, dev=dev, st=st, N=N, dim=self.dim, metric=metric, k=k, m=m, S=S, off_d=off_d, b=b,
-                                 qn=_row_norms(b.qp) if self.metric == "l2" else None, place_d=_on_device(b.place, np.int32, dev),
-                                 len_d=len_d[p0:p1], cand=cand[p0:p1], costs=costs[p0:p1], seqs=seqs[p0:p1], spans=spans[p0:p1])
-                c.ws = c.workspace(lib.sylber_dtw16_workspace_bytes(b.Pc, m, 1))
-                _rerank_launch(c, self._x, self._c)
-        return (costs, seqs, spans, cand.to(torch.int64), bound) if return_candidates else (costs, seqs, spans)
+        return _seeded_phrases(N, self.dim, dev, self.metric, self._g, q, lens, pg, off, sc, si, k, m, phrase_chunk, return_candidates,
+                               lambda c: _rerank_launch(c, self._x, self._c))
 
     # ---- warping paths -------------------------------------------------------------------------------------------------------------
     def align_phrases(self, phrases, spans, lengths=None, pair_chunk: Optional[int] = None, *, _tracked_start: bool = False):

@@ -43,7 +43,17 @@ all from one run: the whole-call time of ``search_phrases`` and ``search_phrases
 yardstick), and per ``nprobe:seeds:refine`` the whole-call time of ``ivf.search_phrases``, of ``ivf.search`` alone on the same rows
 with ``k = seeds``, of the re-rank alone (``sylber_dtw_rerank`` on the call's candidates, packed before the clock starts), the
 remainder (the vote and the host work: packing, tables, the seen count), ``last_search``'s fraction and seen, recall@k against the
-exact sequences, the share of phrases whose exact top-k / best sequence comes back and the share whose planted sequence is first."""
+exact sequences, the share of phrases whose exact top-k / best sequence comes back and the share whose planted sequence is first.
+
+``--ivfpq [--M 48] [--nlist 4096] [--configs 1:8:4,8:32:4]`` runs the leg of the phrase search on the compressed inverted file
+(csrc/dtw_codes.hip, ``IVFPQSyllableIndex.search_phrases``) INSTEAD of the legs above, on the data of ``--ivf``.  The codebooks are the
+sub-rows of 256 stored rows (of 256 residuals for ``residual=True``) drawn at random.  Per (rows, m) and ``nprobe:seeds:refine``, all
+from one run: the whole-call time of ``ix.search_phrases`` with the rows held (``rerank=True``), after ``drop_rows()`` and with
+residual codes after ``drop_rows()``; ``IVFSyllableIndex.search_phrases`` at the same setting and ``PQSyllableIndex.search_phrases``
+(rows dropped, ``refine``) beside them; the dropped call's stage 1a (``ix.search`` alone), stage 2 alone and remainder (the vote and
+the host work); and stage 2 alone two ways on the same candidates: ``sylber_dtw_rerank_codes``, and ``ix.decode`` of the candidate
+sequences' rows into a scratch followed by ``sylber_dtw_rerank`` on it (the candidate copy to the host that sizes the scratch
+included, as in ``PQSyllableIndex``), with the scratch's rows.  Lazy state is built before anything is timed."""
 import argparse
 import json
 import os
@@ -96,11 +106,10 @@ def rerank_alone(idx, phrases, lens, cand, k):
     return run
 
 
-def ivf_leg(args, dev):
-    from sylber_amd import IVFSyllableIndex, SyllableIndex
-    g = torch.Generator(device=dev).manual_seed(0)
-    rng = np.random.default_rng(0)
-    D, N, k = 768, args.N, args.k
+def clustered_index(args, dev, g, rng):
+    """the data of the --ivf and --ivfpq legs -> (SyllableIndex, sequence lengths, offsets)"""
+    from sylber_amd import SyllableIndex
+    D, N = 768, args.N
     lens = rng.integers(20, 61, N // 20 + 1)
     lens = lens[:int(np.searchsorted(np.cumsum(lens), N)) + 1]
     lens[-1] -= int(lens.sum()) - N
@@ -113,8 +122,173 @@ def ivf_leg(args, dev):
     for r0 in range(0, N, 1 << 19):
         n = min(1 << 19, N - r0)
         x[r0:r0 + n] = cent[torch.multinomial(w, n, replacement=True, generator=g)] + torch.randn(n, D, device=dev, generator=g)
-    idx = SyllableIndex(x, metric="l2", groups=groups, device=dev)
-    del x
+    return SyllableIndex(x, metric="l2", groups=groups, device=dev), lens, off
+
+
+def codes_rerank_alone(ix, phrases, lens, cand, k):
+    """``rerank_alone`` for ``sylber_dtw_rerank_codes`` on ``ix``'s own codes"""
+    from sylber_amd import _lib
+    from sylber_amd._index import _on_device, _phrase_blocks, _phrase_outputs, _prep, _row_norms
+    from sylber_amd.kmeans import _stream, _vp
+    lib, dev = _lib.load(), ix.device
+    lens = np.asarray(lens, np.int64)
+    P, m = cand.shape
+    off = ix.sequence_offsets()
+    off_d = _on_device(off, np.int32, dev)
+    b = _phrase_blocks(lib, dev, _prep(phrases, "l2", dev), lens, 0, P, off, m, 0, 0, None)
+    qn = _row_norms(b.qp)
+    ws = torch.empty(int(lib.sylber_dtw16_workspace_bytes(P, m, 1)), dtype=torch.uint8, device=dev)
+    place_d, len_d = _on_device(b.place, np.int32, dev), _on_device(lens, np.int32, dev)
+    c32 = cand.to(torch.int32).contiguous()
+    costs, seqs, spans = _phrase_outputs(P, k, dev)
+    db, pc = ix._coded_db()
+
+    def run():
+        with torch.cuda.device(dev):
+            _lib.check(lib.sylber_dtw_rerank_codes(_vp(b.qp), b.nb, _vp(qn), _vp(place_d), _vp(len_d), P, *db, len(ix), ix.dim, _vp(pc), 0,
+                                                   _vp(c32), m, _vp(off_d), off.size - 1, k, _vp(costs), _vp(seqs), _vp(spans), _vp(ws),
+                                                   _stream(dev)), "sylber_dtw_rerank_codes")
+        return costs, seqs, spans
+    return run
+
+
+def decode_rerank_alone(ix, phrases, lens, cand, k):
+    """stage 2 the other way: the candidates to the host, ``ix.decode`` of the rows of the distinct candidate sequences into a
+    compact scratch, ``sylber_dtw_rerank`` on it, sequence numbers and rows mapped back -> a closure, and a dict that it fills with
+    the scratch's rows"""
+    from sylber_amd import _lib
+    from sylber_amd._index import _on_device, _phrase_blocks, _phrase_outputs, _prep, _row_norms
+    from sylber_amd.kmeans import _stream, _vp
+    lib, dev = _lib.load(), ix.device
+    lens = np.asarray(lens, np.int64)
+    P, m = cand.shape
+    off = ix.sequence_offsets()
+    seq_len = np.diff(off)
+    b = _phrase_blocks(lib, dev, _prep(phrases, "l2", dev), lens, 0, P, off, m, 0, 0, None)
+    qn = _row_norms(b.qp)
+    ws = torch.empty(int(lib.sylber_dtw16_workspace_bytes(P, m, 1)), dtype=torch.uint8, device=dev)
+    place_d, len_d = _on_device(b.place, np.int32, dev), _on_device(lens, np.int32, dev)
+    costs, seqs, spans = _phrase_outputs(P, k, dev)
+    info = {}
+
+    def run():
+        cand_h = cand.cpu().numpy()
+        uniq = np.unique(cand_h[cand_h >= 0])
+        coff = np.concatenate([[0], np.cumsum(seq_len[uniq])]).astype(np.int64)
+        rid = np.repeat(off[uniq] - coff[:-1], seq_len[uniq]) + np.arange(coff[-1])
+        x = ix.decode(torch.from_numpy(rid).to(dev))
+        cn = _row_norms(x)
+        uniq_d, coff_d, roff_d = (torch.from_numpy(a).to(dev) for a in (uniq, coff, off[uniq]))
+        cc = torch.searchsorted(uniq_d, cand.clamp(min=0))
+        cc = torch.where(cand < 0, torch.full_like(cc, -1), cc).to(torch.int32).contiguous()
+        with torch.cuda.device(dev):
+            _lib.check(lib.sylber_dtw_rerank(_vp(b.qp), b.nb, _vp(qn), _vp(place_d), _vp(len_d), P, _vp(x), int(coff[-1]), ix.dim, _vp(cn), 0,
+                                             _vp(cc), m, _vp(coff_d.to(torch.int32)), int(uniq.size), k, _vp(costs), _vp(seqs), _vp(spans),
+                                             _vp(ws), _stream(dev)), "sylber_dtw_rerank")
+        hit = seqs >= 0
+        sc = seqs.clamp(min=0)
+        spans.copy_(torch.where(hit[:, :, None], spans - coff_d[sc][:, :, None] + roff_d[sc][:, :, None], spans))
+        seqs.copy_(torch.where(hit, uniq_d[sc], seqs))
+        info["scratch_rows"] = int(coff[-1])
+        return costs, seqs, spans
+    return run, info
+
+
+def sampled_codebooks(rows, M, g):
+    """[M, 256, D / M]: the sub-rows of 256 of ``rows`` drawn at random"""
+    pick = torch.randperm(rows.shape[0], device=rows.device, generator=g)[:256]
+    return rows[pick].reshape(256, M, rows.shape[1] // M).permute(1, 0, 2).contiguous()
+
+
+def ivfpq_leg(args, dev):
+    from sylber_amd import IVFPQSyllableIndex, IVFSyllableIndex, PQSyllableIndex
+    g = torch.Generator(device=dev).manual_seed(0)
+    rng = np.random.default_rng(0)
+    D, N, k, M = 768, args.N, args.k, args.M
+    idx, lens, off = clustered_index(args, dev, g, rng)
+    idx.sequence_offsets()
+    ivf = IVFSyllableIndex.build(idx, nlist=args.nlist, seed=0, max_iter=args.max_iter, train_rows=args.train_rows)
+    cb = sampled_codebooks(idx.features, M, g)
+    t0 = time.perf_counter()
+    ix = IVFPQSyllableIndex.build(idx, M=M, centroids=ivf.centroids, codebooks=cb)
+    torch.cuda.synchronize()
+    build_s = time.perf_counter() - t0
+    lab = ix.labels
+    keep = torch.nonzero(lab >= 0).flatten()[:1 << 16]
+    rcb = sampled_codebooks(idx.features[keep] - ivf.centroids[lab[keep]], M, g)
+    ixr = IVFPQSyllableIndex.build(idx, M=M, centroids=ivf.centroids, codebooks=rcb, residual=True)
+    pq = PQSyllableIndex.build(idx, M, codebooks=cb)
+    warm = idx.features[:2]
+    for i in (ix, ixr):
+        i.search_phrases(warm, 1, 1, lengths=[2], rerank=False)              # the lazy state
+    pq.search_phrases(warm, 1, 1, args.storage, lengths=[2], rerank=False)
+    torch.cuda.synchronize()
+    held_bytes = {"ivfpq": ix.nbytes, "ivfpq_residual": ixr.nbytes, "pq": pq.nbytes}
+    head = {"D": D, "metric": "l2", "N": N, "sequences": int(lens.size), "nlist": args.nlist, "M": M, "k": k, "iters": args.iters,
+            "noise": args.noise, "storage": args.storage, "ivfpq_build_s": round(build_s, 2),
+            "data": "synthetic mixture of %d Gaussians, sequences of 20 to 60 rows, planted noisy phrases" % args.centres}
+    print(json.dumps(head), file=sys.stderr, flush=True)
+    configs = [tuple(int(v) for v in c.split(":")) for c in args.configs.split(",")]
+    shapes = []
+    for rows in [int(v) for v in args.rows.split(",")]:
+        for m in [int(v) for v in args.ms.split(",")]:
+            P = rows // m
+            ok = np.nonzero(lens >= m)[0]
+            truth = ok[rng.integers(0, ok.size, P)]
+            start = off[truth] + (rng.random(P) * (lens[truth] - m + 1)).astype(np.int64)
+            pick = torch.from_numpy((start[:, None] + np.arange(m)[None, :]).reshape(-1)).to(dev)
+            shapes.append((m, P, idx.features[pick] + args.noise * torch.randn(P * m, D, device=dev, generator=g), torch.from_numpy(truth).to(dev)))
+    out = []
+    planted = lambda got, truth_d: round(float((got[1][:, 0] == truth_d).float().mean()), 4)
+    for dropped in (False, True):                                             # every rows-held figure first: drop_rows() cannot be undone
+        if dropped:
+            for i in (ix, ixr, pq):
+                i.drop_rows()
+        for m, P, ph, truth_d in shapes:
+            ln = [m] * P
+            for nprobe, seeds, refine in configs:
+                row = {"rows": P * m, "m": m, "phrases": P, "nprobe": nprobe, "seeds": seeds, "refine": refine}
+                if not dropped:
+                    call = lambda: ix.search_phrases(ph, k, nprobe, seeds=seeds, refine=refine, lengths=ln, rerank=True)
+                    t, lo, hi = timed(call, args.iters)
+                    t_ivf, _, _ = timed(lambda: ivf.search_phrases(ph, k, nprobe, seeds=seeds, refine=refine, lengths=ln), args.iters)
+                    row.update(held_ms=round(t, 2), held_ms_min_max=[round(lo, 2), round(hi, 2)], held_planted_top1=planted(call(), truth_d),
+                               ivf_phrase_ms=round(t_ivf, 2))
+                else:
+                    call = lambda: ix.search_phrases(ph, k, nprobe, seeds=seeds, refine=refine, lengths=ln, return_candidates=True)
+                    t, lo, hi = timed(call, args.iters)
+                    got = call()
+                    ls = ix.last_search
+                    callr = lambda: ixr.search_phrases(ph, k, nprobe, seeds=seeds, refine=refine, lengths=ln)
+                    t_r, lo_r, hi_r = timed(callr, args.iters)
+                    t_pq, _, _ = timed(lambda: pq.search_phrases(ph, k, refine, args.storage, lengths=ln), args.iters)
+                    t_seed, _, _ = timed(lambda: ix.search(ph, seeds, nprobe), args.iters)
+                    codes_run = codes_rerank_alone(ix, ph, ln, got[3], k)
+                    decode_run, info = decode_rerank_alone(ix, ph, ln, got[3], k)
+                    t_codes, _, _ = timed(codes_run, args.iters)
+                    t_dec, _, _ = timed(decode_run, args.iters)
+                    a, b = codes_run(), decode_run()
+                    same = all(torch.equal(u, v) for u, v in zip(a, b)) and all(torch.equal(u, v) for u, v in zip(a, got[:3]))
+                    cols = int((torch.from_numpy(np.diff(off)).to(dev)[got[3].clamp(min=0)] * (got[3] >= 0)).sum())
+                    row.update(dropped_ms=round(t, 2), dropped_ms_min_max=[round(lo, 2), round(hi, 2)], dropped_planted_top1=planted(got, truth_d),
+                               residual_dropped_ms=round(t_r, 2), residual_dropped_ms_min_max=[round(lo_r, 2), round(hi_r, 2)],
+                               residual_planted_top1=planted(callr(), truth_d), pq_dropped_ms=round(t_pq, 2), seed_search_ms=round(t_seed, 2),
+                               rerank_codes_ms=round(t_codes, 2), remainder_ms=round(t - t_seed - t_codes, 2), decode_then_rerank_ms=round(t_dec, 2),
+                               codes_over_decode=round(t_codes / t_dec, 3), two_ways_same_bits=same, scratch_rows=info["scratch_rows"],
+                               pair_columns=cols, fraction=round(ls["fraction"], 6), seen=round(ls["seen"], 1))
+                print(json.dumps(row), file=sys.stderr, flush=True)
+                out.append(row)
+    head.update(rows=out, device_bytes={"syllable_index_rows_norms_groups": 4 * N * D + 8 * N, "rows_held": held_bytes,
+                                        "rows_dropped": {"ivfpq": ix.nbytes, "ivfpq_residual": ixr.nbytes, "pq": pq.nbytes}})
+    print(json.dumps(head))
+
+
+def ivf_leg(args, dev):
+    from sylber_amd import IVFSyllableIndex
+    g = torch.Generator(device=dev).manual_seed(0)
+    rng = np.random.default_rng(0)
+    D, N, k = 768, args.N, args.k
+    idx, lens, off = clustered_index(args, dev, g, rng)
     idx.sequence_offsets()
     idx.half_rows(args.storage)
     torch.cuda.synchronize()
@@ -181,6 +355,7 @@ def main():
     ap.add_argument("--pq", action="store_true")
     ap.add_argument("--M", type=int, default=48)
     ap.add_argument("--ivf", action="store_true")
+    ap.add_argument("--ivfpq", action="store_true")
     ap.add_argument("--nlist", type=int, default=4096)
     ap.add_argument("--centres", type=int, default=20000)
     ap.add_argument("--noise", type=float, default=0.3)
@@ -193,6 +368,8 @@ def main():
     torch.cuda.set_device(dev)
     if args.ivf:
         return ivf_leg(args, dev)
+    if args.ivfpq:
+        return ivfpq_leg(args, dev)
     g = torch.Generator(device=dev).manual_seed(0)
     rng = np.random.default_rng(0)
     D, N, k = 768, args.N, args.k
