@@ -516,10 +516,10 @@ int sylber_dtw_align(const float* q_dev, int32_t n_blocks, const float* q_norm_d
                      int32_t max_rows, int32_t* rows_dev, int32_t* steps_dev, float* cost_dev, int32_t* start_dev, void* workspace_dev,
                      void* stream);
 
-/* The exact DTW on a coded database (sylber_amd/pq.py: IVFPQSyllableIndex.search_phrases / align_phrases with rerank=False; restated
- * in tests/ivfpq_phrase_ref.py): sylber_dtw_rerank and sylber_dtw_align with db_dev replaced by product-quantization codes that may
- * lie in another order than the row ids and may be codes of residuals to a list centroid.  No row is materialised: the kernels rebuild
- * each row inside the dot-product chain.  The coded database is one argument group, the same in both entries:
+/* The exact DTW on a coded database (sylber_amd/pq.py: IVFPQSyllableIndex.search_phrases / search_occurrences / align_phrases with
+ * rerank=False; restated in tests/ivfpq_phrase_ref.py): sylber_dtw_rerank and sylber_dtw_align with db_dev replaced by
+ * product-quantization codes that may lie in another order than the row ids and may be codes of residuals to a list centroid.  No row is materialised: the kernels rebuild
+ * each row inside the dot-product chain.  The coded database is one argument group, the same in every entry:
  *   code_dev [N, M] uint8 and bad_dev [N] uint8 (nullable; 1 = a masked row), both in POSITION order; pos_dev [N] int32: row id ->
  *   position (null = identity); cb_dev [M, 256, D / M] fp32, 1 <= M <= 64, D % M == 0, (D / M) % 16 == 0;
  *   list_offsets_dev [nlist + 1] int32, centroid_dev [nlist, D] fp32, nlist >= 1: all three or none (null, null, 0).  None: the codes
@@ -533,6 +533,12 @@ int sylber_dtw_align(const float* q_dev, int32_t n_blocks, const float* q_norm_d
  * other arguments and the workspaces (sylber_dtw16_workspace_bytes(n_phrases, m, 1), sylber_dtw_align_workspace_bytes) -- is
  * sylber_dtw_rerank's and sylber_dtw_align's, word for word.  So the outputs of either equal those of the fp32 entry on the
  * materialised plane db_dev[j] = xhat_j (NaN rows as above) with the same db_norm_dev, BIT FOR BIT.
+ * sylber_dtw_rerank_occurrences_codes: sylber_dtw_rerank_occurrences on the same coded database (PQSyllableIndex.search_occurrences and
+ *   IVFPQSyllableIndex.search_occurrences with rerank=False): the arguments of sylber_dtw_rerank_codes, the coded-database group
+ *   unchanged and in the same order; k as in sylber_dtw_rerank_occurrences (1 <= k <= 128, not bounded by m); workspace_dev:
+ *   sylber_dtw_occ_workspace_bytes(n_phrases, m, k) bytes.  The outputs equal those of sylber_dtw_rerank_occurrences on the
+ *   materialised plane db_dev[j] = xhat_j with the same db_norm_dev, BIT FOR BIT; NaN rows are a masked row, an out-of-range
+ *   position and a residual-coded row in no list.  It also refuses n_phrases x m x k beyond 2^30 list entries.
  * Every index read from device memory is clamped before it is an address: stale pos_dev, offsets or windows give NaN rows or padding,
  * never an access outside the arrays.  Bad arguments (those of the fp32 entry, the geometry of M, a partial list group, a null
  * code_dev or cb_dev) return 1 with sylber_last_error before any device call. */
@@ -542,6 +548,12 @@ int sylber_dtw_rerank_codes(const float* q_dev, int32_t n_blocks, const float* q
                             const float* centroid_dev, int32_t nlist, int32_t N, int32_t D, const float* db_norm_dev, int32_t metric,
                             const int32_t* cand_dev, int32_t m, const int32_t* seq_offsets_dev, int32_t n_seq, int32_t k, float* cost_dev,
                             int64_t* seq_dev, int64_t* span_dev, void* workspace_dev, void* stream);
+int sylber_dtw_rerank_occurrences_codes(const float* q_dev, int32_t n_blocks, const float* q_norm_dev, const int32_t* phrase_row_dev,
+                                        const int32_t* phrase_len_dev, int32_t n_phrases, const uint8_t* code_dev, const uint8_t* bad_dev,
+                                        const int32_t* pos_dev, const float* cb_dev, int32_t M, const int32_t* list_offsets_dev,
+                                        const float* centroid_dev, int32_t nlist, int32_t N, int32_t D, const float* db_norm_dev,
+                                        int32_t metric, const int32_t* cand_dev, int32_t m, const int32_t* seq_offsets_dev, int32_t n_seq,
+                                        int32_t k, float* cost_dev, int64_t* seq_dev, int64_t* span_dev, void* workspace_dev, void* stream);
 int sylber_dtw_align_codes(const float* q_dev, int32_t n_blocks, const float* q_norm_dev, const int32_t* phrase_row_dev,
                            const int32_t* phrase_len_dev, int32_t n_phrases, const uint8_t* code_dev, const uint8_t* bad_dev,
                            const int32_t* pos_dev, const float* cb_dev, int32_t M, const int32_t* list_offsets_dev,

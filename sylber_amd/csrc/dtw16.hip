@@ -24,7 +24,7 @@
 //     spans as row ids.  A second launch: nothing relies on an order between workgroups.
 //   * dtw_occ_rerank_kernel (at the end of the file; SyllableIndex.search_occurrences_refined, tests/occ_ref.py): dtw_rerank_kernel's
 //     walk (the same pieces of dtw_pair.h, dt_occ_cell for the cell and two ballots after it) with every non-overlapping occurrence
-//     of the candidate kept, k per pair in LDS; merged and reported by dtw_occ.h.
+//     of the candidate kept, k per pair in LDS; merged and reported by dtw_occ.h.  The body is dtw_pair.h's dp_occ_rerank_pair.
 // LDS and occupancy (a CU has 160 KiB):
 //   dtw16_scan_kernel   69 136 B fixed (cost tile 67 584 | c_j, sequence ids, groups) + 8 B x (phrases of the block) x m <= 32 KiB
 //                       of lists = at most 101 904 B: one workgroup of 4 waves per CU (dtw_search_kernel: 134 672 B, also one); two
@@ -32,7 +32,7 @@
 //                       matter: one workgroup's contraction then hides under the other's wavefront (profiles/phrase_bench.md:
 //                       219 ms against 399 ms for the same work).
 //   dtw_rerank_kernel   9 216 B (64 rows x 36 floats), 64 threads: LDS allows 17 workgroups per CU, so the wave slots and registers
-//                       bound it, not LDS.  dtw_occ_rerank_kernel adds its list: 9 216 + 16 k <= 11 264 B.
+//                       bound it, not LDS.  dtw_occ_rerank_kernel adds its list (16 B x k, held for k = 128): 11 264 B.
 #include "kernels.h"
 #include "dtw16_scan.h"
 #include "dtw_pair.h"
@@ -257,11 +257,8 @@ extern "C" int sylber_dtw_rerank(const float* q_dev, int32_t n_blocks, const flo
 }
 
 // ---- every occurrence of a phrase among candidate sequences (SyllableIndex.search_occurrences_refined) ----------------------------
-// dtw_rerank_kernel's sibling: the same wave per (phrase, candidate) pair on the same pieces of dtw_pair.h, so every A[m-1][j] and
-// start has the bits of dtw_occ_kernel's.  The lane of the last row runs dt_occ_cell's one-pass rule and the wave
-// keeps the pair's k best occurrences as a sorted list of (cost, start row, (start row, end row)) in LDS (16 B x k <= 2 KiB);
-// it goes to ps / pi / pp [P][m][k], a list of fillers for a candidate of -1.  Candidate sequences of a phrase are distinct (stage
-// 1's are), so the start rows of its m lists are: knn_merge_kernel<true> reduces them and dtw_occ_finish_kernel reports.
+// dtw_rerank_kernel's sibling: the same wave per (phrase, candidate) pair, with every non-overlapping occurrence of the candidate
+// kept.  The body is dtw_pair.h's dp_occ_rerank_pair, which dtw_codes.hip runs on a coded database.
 __global__ __launch_bounds__(64) void dtw_occ_rerank_kernel(const float* __restrict__ q, const float* __restrict__ qsq, int qrows,
                                                             const int32_t* __restrict__ prow, const int32_t* __restrict__ plen,
                                                             const float* __restrict__ x, int N, int D, const float* __restrict__ cn,
@@ -272,44 +269,7 @@ __global__ __launch_bounds__(64) void dtw_occ_rerank_kernel(const float* __restr
     __shared__ float ols[KN_KMAX];
     __shared__ int oli[KN_KMAX];
     __shared__ int2 olp[KN_KMAX];
-    const int lane = threadIdx.x;
-    const size_t pair = blockIdx.x;
-    const int p = (int)(pair / m);
-    const int sidx = cand[pair];
-    int j0 = 0, j1 = 0;
-    if (sidx >= 0 && sidx < S) {
-        j0 = soff[sidx]; j1 = soff[sidx + 1];
-        j0 = j0 < 0 ? 0 : j0; j1 = j1 > N ? N : j1;
-    }
-    for (int e = lane; e < k; e += 64) { ols[e] = INFINITY; oli[e] = INT_MAX; olp[e] = make_int2(-1, -1); }
-    const DpLane L(q, qsq, qrows, prow, plen, p, D, lane, DT_MAX_M);
-    DtLane st;
-    DtOcc oc;
-    float* dr = dsm + lane * DP_LD;
-    for (int n0 = j0; n0 < j1; n0 += DP_CH) {              // no chunk for a candidate of -1: its list stays fillers
-        const int ncol = j1 - n0 < DP_CH ? j1 - n0 : DP_CH;
-        dp_chunk_costs(dr, L, DpRows{x, D}, D, cn, qsq != nullptr, n0, ncol, j1);       // its first barrier, the first time: the list is cleared
-        bool out = false, end = false;                     // what the lane's cell of this step owes the list
-        float ec = INFINITY;
-        int es = 0, ee = 0;
-        dp_walk(st, L, lane, n0, ncol, j0, [&](int j, int col, bool isstart, const DtUp& u) {
-            out = dt_occ_cell(st, oc, u, lane == 0, L.lastrow, isstart, dr[j], col, ec, es, ee);
-            end = L.lastrow && col == j1 - 1 && oc.pc < INFINITY;
-        }, [&] {
-            // only lane mp - 1 can owe a hand-off; at the sequence's last column it may owe both
-            if (__ballot(out)) {
-                const int vs = __shfl(es, L.mp - 1);
-                kn_insert_t<true>(ols, oli, olp, k, lane, __shfl(ec, L.mp - 1), vs, make_int2(vs, __shfl(ee, L.mp - 1)));
-            }
-            if (__ballot(end)) {
-                const int vs = __shfl(oc.ps, L.mp - 1);
-                kn_insert_t<true>(ols, oli, olp, k, lane, __shfl(oc.pc, L.mp - 1), vs, make_int2(vs, __shfl(oc.pe, L.mp - 1)));
-            }
-            out = false; end = false;
-        });
-    }
-    __syncthreads();
-    for (int e = lane; e < k; e += 64) { ps[pair * k + e] = ols[e]; pi[pair * k + e] = oli[e]; pp[pair * k + e] = olp[e]; }
+    dp_occ_rerank_pair(dsm, ols, oli, olp, DpRowsSrc{x, D}, q, qsq, qrows, prow, plen, N, D, cn, cand, soff, S, m, k, ps, pi, pp);
 }
 
 extern "C" int64_t sylber_dtw_occ_workspace_bytes(int32_t n_phrases, int32_t m, int32_t k) {

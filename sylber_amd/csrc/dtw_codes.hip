@@ -1,10 +1,13 @@
-// The exact DTW on a coded database (sylber_amd/pq.py: IVFPQSyllableIndex.search_phrases / align_phrases with rerank=False; contract
-// in include/sylber_hip.h, restated in tests/ivfpq_phrase_ref.py): sylber_dtw_rerank and sylber_dtw_align on rows that exist only as
+// The exact DTW on a coded database (sylber_amd/pq.py: IVFPQSyllableIndex.search_phrases / search_occurrences / align_phrases and
+// PQSyllableIndex.search_occurrences with rerank=False; contract in include/sylber_hip.h, restated in tests/ivfpq_phrase_ref.py and
+// tests/occ_ref.py): sylber_dtw_rerank, sylber_dtw_rerank_occurrences and sylber_dtw_align on rows that exist only as
 // product-quantization codes, in list order, possibly as residuals to a list centroid.  No row is written anywhere: each float4 of
 // the dot-product chain is rebuilt from a code byte and the fp32 codebooks (plus the list centroid) where the chain consumes it.
-//   * dtw_rerank_codes_kernel / dtw_align_codes_kernel: dtw_pair.h's dp_rerank_pair and dtw_align.h's da_align_pair, the bodies of
-//     dtw_rerank_kernel and dtw_align_kernel, on DcSrc below in place of a plain pointer.  Lane state, chain, cell, predecessor
-//     bits, walk back and ranking (dtw_rank_kernel) are those files'; only where a row's elements come from is here.
+//   * dtw_rerank_codes_kernel / dtw_occ_rerank_codes_kernel / dtw_align_codes_kernel: dtw_pair.h's dp_rerank_pair and
+//     dp_occ_rerank_pair and dtw_align.h's da_align_pair, the bodies of dtw_rerank_kernel, dtw_occ_rerank_kernel and
+//     dtw_align_kernel, on DcSrc below in place of a plain pointer.  Lane state, chain, cell, the occurrence rule and its hand-off
+//     ballots, predecessor bits, walk back, ranking (dtw_rank_kernel) and the merge of the occurrence lists (dtw_occ.h) are those
+//     files'; only where a row's elements come from is here.
 //   * DcSrc::chunk, once per chunk of DP_CH = 32 columns: lane jj < 32 resolves column jj -- row id -> position (pos, or the id
 //     itself), its mask byte, and for residual codes its list, a binary search of the position in list_offsets (uniform trip count:
 //     the bits of nlist) -- and the wave stages the chunk's 32 M code bytes in LDS (2 KiB at M = 64, beside the walk's 9 216 B).
@@ -15,10 +18,15 @@
 //     element: one fp32 addition that is rounded before the chain's fmaf and cannot be contracted into it.
 //   * A NaN row (mask byte set, position out of range, or residual-coded and in no list) gets a NaN in element x of every float4:
 //     its dot is NaN, and dt_cost turns any NaN into +inf, as it does for the NaN row of the materialised plane.
+// LDS: dtw_rerank_codes_kernel 9 216 B (the walk's 64 rows x 36 floats) + 2 048 B of code bytes = 11 264 B;
+// dtw_occ_rerank_codes_kernel adds the pair's list, 16 B x k, held for k = 128: 9 216 + 2 048 + 2 048 = 13 312 B;
+// dtw_align_codes_kernel the walk, dtw_align.h's DaLds and the code bytes.  64 threads each: the wave slots and registers bound the
+// occupancy, not LDS (a CU has 160 KiB).
 // Every index that comes from device memory is clamped before it is an address: the position into [0, N), the list into
 // [0, nlist) by the search's own bounds; a code byte is below 256 by its type, m below M by the loop.
 #include "kernels.h"
 #include "dtw_align.h"
+#include "dtw_occ.h"
 
 constexpr int DC_MAX_M = 64;                              // PQ_MAX_M of pq.hip
 
@@ -130,6 +138,21 @@ __global__ __launch_bounds__(64) void dtw_align_codes_kernel(const float* __rest
     da_align_pair(dsm, lds, DcSrc<RES>{db, sc}, q, qsq, qrows, prow, plen, P, db.N, db.D, cn, pp, win, max_cols, Mx, rows, steps, cost, tstart, ws);
 }
 
+template <bool RES>
+__global__ __launch_bounds__(64) void dtw_occ_rerank_codes_kernel(const float* __restrict__ q, const float* __restrict__ qsq, int qrows,
+                                                                  const int32_t* __restrict__ prow, const int32_t* __restrict__ plen,
+                                                                  DC_DB_PARAMS, const float* __restrict__ cn, const int32_t* __restrict__ cand,
+                                                                  const int32_t* __restrict__ soff, int S, int m, int k, float* __restrict__ ps,
+                                                                  int32_t* __restrict__ pi, int2* __restrict__ pp) {
+    __shared__ float dsm[DT_MAX_M * DP_LD];
+    __shared__ float ols[KN_KMAX];
+    __shared__ int oli[KN_KMAX];
+    __shared__ int2 olp[KN_KMAX];
+    __shared__ uint8_t sc[DP_CH * DC_MAX_M];
+    const DcDb db{code, bad, pos, cb, off, cent, N, D, M, D / M, nlist};
+    dp_occ_rerank_pair(dsm, ols, oli, olp, DcSrc<RES>{db, sc}, q, qsq, qrows, prow, plen, db.N, db.D, cn, cand, soff, S, m, k, ps, pi, pp);
+}
+
 // the entries' verdict on the coded database, reported behind dt_pair_check's count checks
 static const char* dc_db_error(int32_t D, int32_t M, const int32_t* list_offsets_dev, const float* centroid_dev, int32_t nlist) {
     if (M < 1 || M > DC_MAX_M || D % M || (D / M) % 16) return "need 1 <= M <= 64, D % M == 0 and (D / M) % 16 == 0";
@@ -161,6 +184,32 @@ extern "C" int sylber_dtw_rerank_codes(const float* q_dev, int32_t n_blocks, con
                        r.pc, r.pspan);
     HIP_TRY(hipGetLastError());
     return dp_rank_launch(r, cand_dev, n_phrases, m, k, cost_dev, seq_dev, span_dev, s);
+}
+
+extern "C" int sylber_dtw_rerank_occurrences_codes(const float* q_dev, int32_t n_blocks, const float* q_norm_dev, const int32_t* phrase_row_dev,
+                                                   const int32_t* phrase_len_dev, int32_t n_phrases, const uint8_t* code_dev,
+                                                   const uint8_t* bad_dev, const int32_t* pos_dev, const float* cb_dev, int32_t M,
+                                                   const int32_t* list_offsets_dev, const float* centroid_dev, int32_t nlist, int32_t N,
+                                                   int32_t D, const float* db_norm_dev, int32_t metric, const int32_t* cand_dev, int32_t m,
+                                                   const int32_t* seq_offsets_dev, int32_t n_seq, int32_t k, float* cost_dev, int64_t* seq_dev,
+                                                   int64_t* span_dev, void* workspace_dev, void* stream) {
+    static const char* what = "sylber_dtw_rerank_occurrences_codes";
+    hipStream_t s = (hipStream_t)stream;
+    if (!q_dev || !phrase_row_dev || !phrase_len_dev || !code_dev || !cb_dev || !cand_dev || !seq_offsets_dev || !cost_dev || !seq_dev ||
+        !span_dev || !workspace_dev) { syl_set_error(what, "null argument"); return 1; }
+    const float *qn, *cn;
+    const char* own = m < 1 || m > KN_KMAX || k < 1 || k > KN_KMAX ? "need 1 <= m <= 128 and 1 <= k <= 128" : nullptr;
+    if (dt_pair_check(what, "need n_blocks, n_phrases, N, n_seq >= 1 and D a multiple of 16",
+                      own ? own : dc_db_error(D, M, list_offsets_dev, centroid_dev, nlist),
+                      "n_phrases x m x k is too large: use smaller phrase chunks", n_blocks, n_phrases, n_seq, N, D, q_norm_dev, db_norm_dev, metric,
+                      (int64_t)n_phrases * m * k > INT32_MAX / 2, qn, cn)) return 1;
+    const DcDb db{code_dev, bad_dev, pos_dev, cb_dev, list_offsets_dev, centroid_dev, N, D, M, D / M, nlist};
+    const DtOccLists lists = dt_occ_lists_carve((char*)workspace_dev, n_phrases, m, k);
+    hipLaunchKernelGGL(list_offsets_dev ? dtw_occ_rerank_codes_kernel<true> : dtw_occ_rerank_codes_kernel<false>,
+                       dim3((unsigned)((int64_t)n_phrases * m)), dim3(64), 0, s, q_dev, qn, n_blocks * KN_BM, phrase_row_dev, phrase_len_dev,
+                       DC_DB_ARGS(db), cn, cand_dev, seq_offsets_dev, n_seq, m, k, lists.s0, lists.i0, lists.p0);
+    HIP_TRY(hipGetLastError());
+    return dt_occ_merge_finish(lists, n_phrases, m, k, nullptr, seq_offsets_dev, n_seq, cost_dev, seq_dev, span_dev, s);
 }
 
 extern "C" int sylber_dtw_align_codes(const float* q_dev, int32_t n_blocks, const float* q_norm_dev, const int32_t* phrase_row_dev,

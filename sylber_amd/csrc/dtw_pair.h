@@ -1,5 +1,5 @@
 // What the wave-per-pair DTW kernels share: dtw16.hip's dtw_rerank_kernel and dtw_occ_rerank_kernel, dtw_align.hip's dtw_align_kernel
-// and dtw_codes.hip's two kernels on a coded database.  One wave owns a (phrase, run of rows) pair, lane l owns phrase row l, and the
+// and dtw_codes.hip's three kernels on a coded database.  One wave owns a (phrase, run of rows) pair, lane l owns phrase row l, and the
 // run is walked in chunks of DP_CH columns.  Each piece is here once and forced inline:
 //   * the chunk geometry (DP_CH, DP_LD);
 //   * DpLane: what a lane knows of its phrase row;
@@ -16,8 +16,10 @@
 //     that have a cell at this step, step() in every lane after it (the occurrence re-rank's ballots);
 //   * dp_rerank_pair and dtw_rank_kernel: the body of a re-rank kernel over any source of rows, and the ranking launch behind it
 //     (sylber_dtw_rerank, sylber_dtw_rerank_codes);
-//   * dt_pair_check: the host checks of sylber_dtw_rerank, sylber_dtw_rerank_occurrences, sylber_dtw_align and the two _codes entries,
-//     and the norms by metric.
+//   * dp_occ_rerank_pair: the body of an occurrence re-rank kernel over any source of rows: dt_occ_cell for the cell, the two
+//     hand-off ballots after it and the pair's list in LDS (sylber_dtw_rerank_occurrences, sylber_dtw_rerank_occurrences_codes);
+//   * dt_pair_check: the host checks of sylber_dtw_rerank, sylber_dtw_rerank_occurrences, sylber_dtw_align and the three _codes
+//     entries, and the norms by metric.
 #pragma once
 #include "../../include/sylber_hip.h"
 #include "dtw_tile.h"
@@ -145,6 +147,59 @@ __device__ __forceinline__ void dp_rerank_pair(float* dsm, const Src& src, const
         pc[pair] = st.bc;
         pspan[pair] = st.bc < INFINITY ? make_int2(st.bst, st.be) : make_int2(-1, -1);
     }
+}
+
+// The body of an occurrence re-rank kernel (sylber_dtw_rerank_occurrences, sylber_dtw_rerank_occurrences_codes): dp_rerank_pair's
+// pair, walk and pieces, so every A[m-1][j] and start has the bits of dtw_occ_kernel's, with every non-overlapping occurrence of
+// the candidate kept.  The lane of the last row runs dt_occ_cell's one-pass rule and the wave keeps the pair's k best occurrences
+// as a sorted list of (cost, start row, (start row, end row)) in LDS (ols / oli / olp [KN_KMAX]: 16 B x 128 = 2 KiB, k of them
+// used); it goes to ps / pi / pp [P][m][k], a list of fillers for a candidate of -1.  Candidate sequences of a phrase are distinct (stage 1's are),
+// so the start rows of its m lists are: knn_merge_kernel<true> reduces them and dtw_occ_finish_kernel reports (dtw_occ.h).
+template <class Src>
+__device__ __forceinline__ void dp_occ_rerank_pair(float* dsm, float* ols, int* oli, int2* olp, const Src& src, const float* __restrict__ q,
+                                                   const float* __restrict__ qsq, int qrows, const int32_t* __restrict__ prow,
+                                                   const int32_t* __restrict__ plen, int N, int D, const float* __restrict__ cn,
+                                                   const int32_t* __restrict__ cand, const int32_t* __restrict__ soff, int S, int m, int k,
+                                                   float* __restrict__ ps, int32_t* __restrict__ pi, int2* __restrict__ pp) {
+    const int lane = threadIdx.x;
+    const size_t pair = blockIdx.x;
+    const int p = (int)(pair / m);
+    const int sidx = cand[pair];
+    int j0 = 0, j1 = 0;
+    if (sidx >= 0 && sidx < S) {
+        j0 = soff[sidx]; j1 = soff[sidx + 1];
+        j0 = j0 < 0 ? 0 : j0; j1 = j1 > N ? N : j1;
+    }
+    for (int e = lane; e < k; e += 64) { ols[e] = INFINITY; oli[e] = INT_MAX; olp[e] = make_int2(-1, -1); }
+    const DpLane L(q, qsq, qrows, prow, plen, p, D, lane, DT_MAX_M);
+    DtLane st;
+    DtOcc oc;
+    float* dr = dsm + lane * DP_LD;
+    for (int n0 = j0; n0 < j1; n0 += DP_CH) {              // no chunk for a candidate of -1: its list stays fillers
+        const int ncol = j1 - n0 < DP_CH ? j1 - n0 : DP_CH;
+        // a barrier of the source or dp_chunk_costs' first, the first time: the list is cleared
+        dp_chunk_costs(dr, L, src.chunk(lane, n0, ncol, j1), D, cn, qsq != nullptr, n0, ncol, j1);
+        bool out = false, end = false;                     // what the lane's cell of this step owes the list
+        float ec = INFINITY;
+        int es = 0, ee = 0;
+        dp_walk(st, L, lane, n0, ncol, j0, [&](int j, int col, bool isstart, const DtUp& u) {
+            out = dt_occ_cell(st, oc, u, lane == 0, L.lastrow, isstart, dr[j], col, ec, es, ee);
+            end = L.lastrow && col == j1 - 1 && oc.pc < INFINITY;
+        }, [&] {
+            // only lane mp - 1 can owe a hand-off; at the sequence's last column it may owe both
+            if (__ballot(out)) {
+                const int vs = __shfl(es, L.mp - 1);
+                kn_insert_t<true>(ols, oli, olp, k, lane, __shfl(ec, L.mp - 1), vs, make_int2(vs, __shfl(ee, L.mp - 1)));
+            }
+            if (__ballot(end)) {
+                const int vs = __shfl(oc.ps, L.mp - 1);
+                kn_insert_t<true>(ols, oli, olp, k, lane, __shfl(oc.pc, L.mp - 1), vs, make_int2(vs, __shfl(oc.pe, L.mp - 1)));
+            }
+            out = false; end = false;
+        });
+    }
+    __syncthreads();
+    for (int e = lane; e < k; e += 64) { ps[pair * k + e] = ols[e]; pi[pair * k + e] = oli[e]; pp[pair * k + e] = olp[e]; }
 }
 
 // One wave per phrase i (4 per workgroup).  Lane e (and e + 64) owns pair (i, cand[i][e]); a candidate of -1 or a cost that is not

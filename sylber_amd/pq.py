@@ -40,7 +40,7 @@ from ._index import (DEFAULT_PHRASE_CHUNK, DEFAULT_QUERY_CHUNK, MAX_SEEDS, METRI
                      _check_nprobe, _check_splits_chunk, _chunked_workspace_bytes, _group_runs, _list_layout, _on_device, _outputs, _pack16,
                      _phrase_args, _prep, _provenance, _query_groups, _result, _row_norms, _rows, _rows_of_width, _scan_phrases)
 from .kmeans import _device, _stream, _vp
-from .search import IVFSyllableIndex, SyllableIndex, _align_launch, _align_phrases, _rerank_launch, _seeded_phrases
+from .search import IVFSyllableIndex, SyllableIndex, _align_launch, _align_phrases, _occ_rerank_launch, _rerank_launch, _seeded_phrases
 
 KSUB = 256                      # centroids per sub-space: one uint8 per code
 MAX_M = 64                      # PQ_MAX_M of csrc/pq.hip: at least two queries' tables (M KiB each) fit beside the top lists in LDS
@@ -459,15 +459,57 @@ class PQSyllableIndex:
         Nothing returned depends on ``splits``, ``phrase_chunk``, ``block_phrases``, ``scratch_rows``, stale workspace contents, how
         the index was built or whether it was saved and loaded.  ``storage="fp16"`` refuses a finite codebook value beyond
         +-65504."""
+        rerank = self._check_rerank(rerank)
+        if isinstance(scratch_rows, bool) or int(scratch_rows) != scratch_rows or int(scratch_rows) < 1:
+            raise ValueError("scratch_rows must be an integer >= 1, got %r" % (scratch_rows,))
+        stage2 = (lambda c: _rerank_launch(c, self.index._x, self.index._c)) if rerank else (lambda c: self._rerank_decoded(c, int(scratch_rows)))
+        return self._scan_codes(stage2, phrases, k, refine, storage, lengths, groups, exclude_same_group, sequences, splits, phrase_chunk,
+                                block_phrases, return_candidates, _workspace_fill)
+
+    def search_occurrences(self, phrases, k: int, refine: int = 4, storage: str = "fp16", *, rerank: Optional[bool] = None, lengths=None,
+                           groups=None, exclude_same_group: bool = False, sequences=None, splits: int = 0,
+                           phrase_chunk: int = DEFAULT_PHRASE_CHUNK, block_phrases: int = 0, return_candidates: bool = False,
+                           _workspace_fill=None):
+        """``SyllableIndex.search_occurrences_refined`` on the codes: every non-overlapping occurrence of each phrase in ``m = k *
+        refine <= 128`` candidate sequences -> ``(costs, seqs, spans)`` as ``SyllableIndex.search_occurrences`` returns them (plus
+        ``cand`` and ``coarse`` with ``return_candidates=True``).  The arguments are ``search_phrases``'s without ``scratch_rows``.
+
+        Stage 1 is ``search_phrases``'s, unchanged (``sylber_dtwpq_scan``): ``cand`` and ``coarse`` are its, bit for bit.  Stage 2,
+        ``rerank=True`` (the default while the fp32 rows are held; ``ValueError`` once they are dropped):
+        ``sylber_dtw_rerank_occurrences`` on the fp32 rows, so the result is ``pq.index.search_occurrences`` restricted to ``cand``.
+        ``rerank=False`` (the only mode after ``drop_rows()``): the same occurrences on the rows that ``pq.decode`` returns, a masked
+        row being a NaN row, rebuilt from the code bytes inside the kernel's dot products (csrc/dtw_codes.hip,
+        ``sylber_dtw_rerank_occurrences_codes``): no decoded scratch, no wait for the device.  Under ``"l2"`` with no masked row the
+        whole call equals ``SyllableIndex(pq.decode(arange(N)), metric="l2", groups=g).search_occurrences_refined(...)``, bit for
+        bit.  Stage 1 ranks a sequence by its best match: a sequence whose many occurrences are all mediocre can be left out.
+
+        Nothing returned depends on ``splits``, ``phrase_chunk``, ``block_phrases``, stale workspace contents, how the index was
+        built, whether it was saved and loaded or, with ``rerank=False``, whether the rows are still held."""
+        rerank = self._check_rerank(rerank)
+        N = len(self)
+        if rerank:
+            def stage2(c):
+                _occ_rerank_launch(c, "sylber_dtw_rerank_occurrences", (_vp(self.index._x), N, c.dim, _vp(self.index._c)))
+        else:
+            def stage2(c):
+                db = (_vp(self._codes), _vp(self._bad), None, _vp(self.codebooks), self.M, None, None, 0, N, c.dim, _vp(self._recon_norms()))
+                _occ_rerank_launch(c, "sylber_dtw_rerank_occurrences_codes", db)
+        return self._scan_codes(stage2, phrases, k, refine, storage, lengths, groups, exclude_same_group, sequences, splits, phrase_chunk,
+                                block_phrases, return_candidates, _workspace_fill)
+
+    def _check_rerank(self, rerank: Optional[bool]) -> bool:
         if rerank is None:
             rerank = self.index is not None
         if rerank and self.index is None:
             raise ValueError("rerank=True needs the fp32 rows, which were dropped: search with rerank=False")
-        if isinstance(scratch_rows, bool) or int(scratch_rows) != scratch_rows or int(scratch_rows) < 1:
-            raise ValueError("scratch_rows must be an integer >= 1, got %r" % (scratch_rows,))
+        if self.index is not None and len(self.index) != len(self):
+            raise ValueError("pq.index holds %d rows, the codes %d: add rows through pq.add" % (len(self.index), len(self)))
+        return bool(rerank)
+
+    def _scan_codes(self, stage2, phrases, k, refine, storage, lengths, groups, exclude_same_group, sequences, splits, phrase_chunk,
+                    block_phrases, return_candidates, fill):
+        """``_scan_phrases`` with stage 1 = ``sylber_dtwpq_scan`` on the codes and ``stage2(c)`` behind it"""
         N = len(self)
-        if self.index is not None and len(self.index) != N:
-            raise ValueError("pq.index holds %d rows, the codes %d: add rows through pq.add" % (len(self.index), N))
 
         def stages():
             cb16, cn, code = self._codebooks16(storage), self._recon_norms(), STORAGES[storage][0]
@@ -480,13 +522,10 @@ class PQSyllableIndex:
                                                    _vp(c.seq_id), _vp(c.cut_d), b.C, _vp(c.pg_d), _vp(c.seq_grp), _vp(c.cand), _vp(c.coarse),
                                                    _vp(c.ws), c.st), "sylber_dtwpq_scan")
 
-            if rerank:
-                return scan, lambda c: _rerank_launch(c, self.index._x, self.index._c)
-            return scan, lambda c: self._rerank_decoded(c, int(scratch_rows))
+            return scan, stage2
 
         return _scan_phrases(N, self.dim, self.device, self.metric, self._db_groups(), self.sequence_offsets, stages, phrases, k, refine, storage,
-                             lengths, groups, exclude_same_group, sequences, splits, phrase_chunk, block_phrases, return_candidates,
-                             _workspace_fill)
+                             lengths, groups, exclude_same_group, sequences, splits, phrase_chunk, block_phrases, return_candidates, fill)
 
     def _decode_windows(self, first: torch.Tensor, width: np.ndarray):
         """the decoded rows of the windows ``first[i] : first[i] + width[i]`` (``first`` int64 on the device, ``width`` on the host) laid
@@ -538,11 +577,11 @@ class PQSyllableIndex:
 
     def align_phrases(self, phrases, spans, lengths=None, pair_chunk: Optional[int] = None, *, rerank: Optional[bool] = None,
                       scratch_rows: int = DEFAULT_SCRATCH_ROWS, _tracked_start: bool = False):
-        """the warping paths behind the spans of ``search_phrases`` -> ``(rows, steps, costs)`` as ``SyllableIndex.align_phrases``
-        returns them; ``rerank`` is what that search was given.  ``rerank=True`` (the default while the fp32 rows are held;
-        ``ValueError`` once they are dropped): ``pq.index.align_phrases``, on the rows the exact re-rank ran on.  ``rerank=False``
-        (the only mode after ``drop_rows()``): the same alignment (csrc/dtw_align.hip) on the *decoded* rows of the windows, a
-        masked row being a NaN row, as ``search_phrases(rerank=False)`` re-ranks -- so on spans from that search ``costs`` has the
+        """the warping paths behind the spans of ``search_phrases`` or ``search_occurrences`` -> ``(rows, steps, costs)`` as
+        ``SyllableIndex.align_phrases`` returns them; ``rerank`` is what that search was given.  ``rerank=True`` (the default while the
+        fp32 rows are held; ``ValueError`` once they are dropped): ``pq.index.align_phrases``, on the rows the exact re-rank ran on.
+        ``rerank=False`` (the only mode after ``drop_rows()``): the same alignment (csrc/dtw_align.hip) on the *decoded* rows of the
+        windows, a masked row being a NaN row, as both searches score them with ``rerank=False`` -- so on their spans ``costs`` has the
         bits of its costs, and the result is ``SyllableIndex(pq.decode(arange(N)), ...).align_phrases``'s.  Per chunk of pairs the
         windows are decoded into a compact scratch of at most ``scratch_rows`` rows (one window at least; the call waits to learn
         the widths) and the row ids are mapped back on the device.  Nothing returned depends on ``pair_chunk``, ``scratch_rows``
@@ -965,6 +1004,36 @@ class IVFPQSyllableIndex:
         workspaces, ``build`` versus ``build`` + ``add``, a ``save`` / ``load`` round trip or, with ``rerank=False``, on whether the
         rows are still held.  ``ValueError`` before any launch: what ``IVFSyllableIndex.search_phrases`` and ``ix.search`` refuse,
         ``rerank=True`` without the rows, an ``ix.index`` of another length."""
+        return self._seeded_codes(False, phrases, k, nprobe, seeds, refine, rerank, lengths, groups, exclude_same_group, sequences, query_chunk,
+                                  phrase_chunk, splits, return_candidates, _workspace_fill)
+
+    def search_occurrences(self, phrases, k: int, nprobe: int, seeds: int = 32, refine: int = 4, *, rerank: Optional[bool] = None,
+                           lengths=None, groups=None, exclude_same_group: bool = False, sequences=None,
+                           query_chunk: int = DEFAULT_QUERY_CHUNK, phrase_chunk: int = DEFAULT_PHRASE_CHUNK, splits: int = 0,
+                           return_candidates: bool = False, _workspace_fill=None):
+        """every non-overlapping occurrence of each phrase on the compressed lists -> ``(costs, seqs, spans)`` as
+        ``SyllableIndex.search_occurrences`` returns them (plus ``cand`` and ``bound`` with ``return_candidates=True``).  The
+        arguments are ``search_phrases``'s.  Stages 1a and 1b are ``search_phrases``'s, unchanged: ``cand`` and ``bound`` are its, bit
+        for bit, for the same ``rerank``.
+
+        Stage 2, ``rerank=True`` (the default while the fp32 rows are held; ``ValueError`` once they are dropped):
+        ``ix.index.search_occurrences_seeded`` on ``ix.search``'s seeds, so the result is ``ix.index.search_occurrences`` restricted
+        to ``cand``.  ``rerank=False`` (the only mode after ``drop_rows()``): the same occurrences on the rows that ``ix.decode``
+        returns, a masked row being a NaN row, rebuilt inside the kernel's dot products (csrc/dtw_codes.hip,
+        ``sylber_dtw_rerank_occurrences_codes``): no decoded scratch, and once the lazy state of ``search_phrases(rerank=False)``
+        exists the call only queues work.  Stage 1 ranks a sequence by a bound on its best match: a sequence whose many occurrences
+        are all mediocre can be left out.
+
+        Nothing returned depends on ``query_chunk``, ``phrase_chunk``, ``splits``, stale workspaces, ``build`` versus ``build`` +
+        ``add``, a ``save`` / ``load`` round trip or, with ``rerank=False``, on whether the rows are still held.  Refusals are
+        ``search_phrases``'s."""
+        return self._seeded_codes(True, phrases, k, nprobe, seeds, refine, rerank, lengths, groups, exclude_same_group, sequences, query_chunk,
+                                  phrase_chunk, splits, return_candidates, _workspace_fill)
+
+    def _seeded_codes(self, occurrences: bool, phrases, k, nprobe, seeds, refine, rerank, lengths, groups, exclude_same_group, sequences,
+                      query_chunk, phrase_chunk, splits, return_candidates, _workspace_fill):
+        """``search_phrases`` (one match per candidate sequence) or ``search_occurrences`` (every occurrence in it): the checks, stage 1a
+        and, by ``rerank``, the seeded search of ``ix.index`` or the vote and the DTW on the codes"""
         rerank = self._check_rerank(rerank, "search")
         N, dev = len(self), self.device
         k, m = _check_k_refine(k, refine, rerank=True)
@@ -980,10 +1049,15 @@ class IVFPQSyllableIndex:
                              query_chunk=query_chunk, splits=splits, _workspace_fill=_workspace_fill)
         self._seeds = (sc, si, off, lens)
         if rerank:
-            return self.index.search_phrases_seeded(q, sc, si, k, refine, lengths=lens, groups=groups, exclude_same_group=exclude_same_group,
-                                                    sequences=sequences, phrase_chunk=phrase_chunk, return_candidates=return_candidates,
-                                                    _trusted_ids=True)
+            kw = dict(lengths=lens, groups=groups, exclude_same_group=exclude_same_group, sequences=sequences, phrase_chunk=phrase_chunk,
+                      return_candidates=return_candidates, _trusted_ids=True)
+            if occurrences:
+                return self.index.search_occurrences_seeded(q, sc, si, k, refine, _workspace_fill=_workspace_fill, **kw)
+            return self.index.search_phrases_seeded(q, sc, si, k, refine, **kw)
         db, pc = self._coded_db()
+
+        def occ_codes(c):
+            _occ_rerank_launch(c, "sylber_dtw_rerank_occurrences_codes", db + (N, c.dim, _vp(pc)))
 
         def rerank_codes(c):
             b = c.b
@@ -992,16 +1066,16 @@ class IVFPQSyllableIndex:
                                                      _vp(c.seqs), _vp(c.spans), _vp(c.ws), c.st), "sylber_dtw_rerank_codes")
 
         return _seeded_phrases(N, self.dim, dev, self.metric, self._by_id(self._rg), q, lens, pg, off, sc, si, k, m, phrase_chunk,
-                               return_candidates, rerank_codes, _workspace_fill)
+                               return_candidates, occ_codes if occurrences else rerank_codes, _workspace_fill)
 
     def align_phrases(self, phrases, spans, lengths=None, pair_chunk: Optional[int] = None, *, rerank: Optional[bool] = None,
                       _tracked_start: bool = False):
-        """the warping paths behind the spans of ``search_phrases`` -> ``(rows, steps, costs)`` as ``SyllableIndex.align_phrases``
-        returns them; ``rerank`` is what that search was given.  ``rerank=True`` (the default while the fp32 rows are held;
-        ``ValueError`` once they are dropped): ``ix.index.align_phrases``, on the rows the exact re-rank ran on.  ``rerank=False``:
-        the same alignment on the rows that ``ix.decode`` returns, rebuilt from the codes inside the kernel (csrc/dtw_codes.hip,
-        ``sylber_dtw_align_codes``; no scratch) -- so on spans from ``search_phrases(rerank=False)`` ``costs`` has the bits of its
-        costs, before and after ``drop_rows()``.  Nothing returned depends on ``pair_chunk``."""
+        """the warping paths behind the spans of ``search_phrases`` or ``search_occurrences`` -> ``(rows, steps, costs)`` as
+        ``SyllableIndex.align_phrases`` returns them; ``rerank`` is what that search was given.  ``rerank=True`` (the default while the
+        fp32 rows are held; ``ValueError`` once they are dropped): ``ix.index.align_phrases``, on the rows the exact re-rank ran on.
+        ``rerank=False``: the same alignment on the rows that ``ix.decode`` returns, rebuilt from the codes inside the kernel
+        (csrc/dtw_codes.hip, ``sylber_dtw_align_codes``; no scratch) -- so on spans from ``search_phrases(rerank=False)`` or
+        ``search_occurrences(rerank=False)`` ``costs`` has the bits of that search's costs, before and after ``drop_rows()``.  Nothing returned depends on ``pair_chunk``."""
         rerank = self._check_rerank(rerank, "align")
         if rerank:
             return self.index.align_phrases(phrases, spans, lengths=lengths, pair_chunk=pair_chunk, _tracked_start=_tracked_start)

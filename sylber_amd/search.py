@@ -18,7 +18,8 @@ a 16-bit MFMA scan picks candidate sequences, the exact DTW re-ranks them; tests
 candidate sequences without a scan of the corpus: each phrase row's neighbours from the lists vote for them (csrc/phrase_vote.hip;
 ``SyllableIndex.search_phrases_seeded`` is the vote and the re-rank on seeds from anywhere; tests/phrase_vote_ref.py).
 ``SyllableIndex.search_occurrences`` / ``search_occurrences_refined`` return every non-overlapping occurrence of a phrase instead of one
-match per sequence (``sylber_dtw_occurrences``, ``sylber_dtw_rerank_occurrences``; tests/occ_ref.py).
+match per sequence (``sylber_dtw_occurrences``, ``sylber_dtw_rerank_occurrences``; tests/occ_ref.py);
+``SyllableIndex.search_occurrences_seeded`` and ``IVFSyllableIndex.search_occurrences`` do so among the candidate sequences of the vote.
 ``align_phrases`` takes the spans of any of them and returns the warping path of each match: the stored rows every phrase row was
 aligned to (csrc/dtw_align.hip, ``sylber_dtw_align``; tests/align_ref.py).
 
@@ -86,6 +87,22 @@ def _rerank_launch(c: "_PhraseChunk", x, cn) -> None:
     _lib.check(c.lib.sylber_dtw_rerank(_vp(b.qp), b.nb, _vp(c.qn), _vp(c.place_d), _vp(c.len_d), int(c.cand.shape[0]), _vp(x), c.N, c.dim,
                                        _vp(cn), c.metric, _vp(c.cand), c.m, _vp(c.off_d), c.S, c.k, _vp(c.costs), _vp(c.seqs), _vp(c.spans),
                                        _vp(c.ws), c.st), "sylber_dtw_rerank")
+
+
+def _occ_rerank_launch(c: "_PhraseChunk", entry: str, db: tuple) -> None:
+    """every occurrence of the chunk's phrases in their candidate sequences ``c.cand`` -> ``c.costs, c.seqs, c.spans``: ``entry`` is
+    ``sylber_dtw_rerank_occurrences`` with ``db = (rows, N, D, norms)`` or ``sylber_dtw_rerank_occurrences_codes`` with ``db`` = the
+    coded-database group, ``N, D`` and the norms.  At most ``OCC_RERANK_ENTRIES`` list entries per launch: that bounds the workspace
+    (m lists of k per phrase and their merge rounds), and the phrases of a launch do not meet, so nothing depends on it."""
+    step = max(1, OCC_RERANK_ENTRIES // (c.m * c.k))
+    Pc = int(c.cand.shape[0])
+    wo = c.workspace(c.lib.sylber_dtw_occ_workspace_bytes(min(step, Pc), c.m, c.k))
+    fn = getattr(c.lib, entry)
+    for r0 in range(0, Pc, step):
+        r1 = min(Pc, r0 + step)
+        _lib.check(fn(_vp(c.b.qp), c.b.nb, _vp(c.qn), _vp(c.place_d[r0:r1]), _vp(c.len_d[r0:r1]), r1 - r0, *db, c.metric,
+                      _vp(c.cand[r0:r1]), c.m, _vp(c.off_d), c.S, c.k, _vp(c.costs[r0:r1]), _vp(c.seqs[r0:r1]), _vp(c.spans[r0:r1]), _vp(wo),
+                      c.st), entry)
 
 
 def _seeded_phrases(N: int, dim: int, dev, metric: str, db_groups, q, lens, pg, off, sc, si, k: int, m: int, phrase_chunk,
@@ -466,14 +483,7 @@ class SyllableIndex:
         out.  Nothing returned depends on ``splits``, ``phrase_chunk``, ``block_phrases``, stale workspace contents or how the
         index was built.  Limits and refusals are ``search_phrases_refined``'s."""
         def rerank(c):
-            step = max(1, OCC_RERANK_ENTRIES // (c.m * c.k))           # phrases per re-rank launch: bounds its m lists of k per phrase
-            wo = c.workspace(c.lib.sylber_dtw_occ_workspace_bytes(min(step, c.b.Pc), c.m, c.k))
-            for r0 in range(0, c.b.Pc, step):
-                r1 = min(c.b.Pc, r0 + step)
-                _lib.check(c.lib.sylber_dtw_rerank_occurrences(_vp(c.b.qp), c.b.nb, _vp(c.qn), _vp(c.place_d[r0:r1]), _vp(c.len_d[r0:r1]),
-                                                               r1 - r0, _vp(self._x), c.N, c.dim, _vp(self._c), c.metric, _vp(c.cand[r0:r1]),
-                                                               c.m, _vp(c.off_d), c.S, c.k, _vp(c.costs[r0:r1]), _vp(c.seqs[r0:r1]),
-                                                               _vp(c.spans[r0:r1]), _vp(wo), c.st), "sylber_dtw_rerank_occurrences")
+            _occ_rerank_launch(c, "sylber_dtw_rerank_occurrences", (_vp(self._x), c.N, c.dim, _vp(self._c)))
 
         return self._scan_phrases(lambda: (self._scan16(storage), rerank), phrases, k, refine, storage, lengths, groups, exclude_same_group,
                                   sequences, splits, phrase_chunk, block_phrases, return_candidates, _workspace_fill)
@@ -506,6 +516,31 @@ class SyllableIndex:
         max or add in a fixed order: nothing returned depends on the order of the seeds within a row, on duplicates or on
         ``phrase_chunk``.  ``ValueError`` before any launch: ``search_phrases_refined``'s checks, seed tensors of another shape or
         dtype, an id outside ``[-1, N)``."""
+        return self._seeded(lambda c: _rerank_launch(c, self._x, self._c), phrases, seed_scores, seed_ids, k, refine, lengths, groups,
+                            exclude_same_group, sequences, phrase_chunk, return_candidates, _trusted_ids)
+
+    def search_occurrences_seeded(self, phrases, seed_scores, seed_ids, k: int, refine: int = 4, *, lengths=None, groups=None,
+                                  exclude_same_group: bool = False, sequences=None, phrase_chunk: int = DEFAULT_PHRASE_CHUNK,
+                                  return_candidates: bool = False, _trusted_ids: bool = False, _workspace_fill=None):
+        """``search_occurrences`` over candidate sequences found from per-row neighbours: stage 1 is ``search_phrases_seeded``'s,
+        unchanged -- the seeds vote for ``m = k * refine <= 128`` candidate *sequences* per phrase -- and stage 2 finds every
+        occurrence in those sequences with the exact fp32 recurrence (``sylber_dtw_rerank_occurrences``) -> ``(costs, seqs,
+        spans)`` as ``search_occurrences`` returns them; with ``return_candidates=True`` also ``cand`` int64 ``[P, m]`` and ``bound``
+        fp32 ``[P, m]``, which are ``search_phrases_seeded``'s, bit for bit.
+
+        The result is ``search_occurrences`` restricted to the sequences of ``cand``, bit for bit.  The only approximation is which
+        sequences are searched: the vote ranks a sequence by a bound on its best match, so a sequence whose many occurrences are
+        all mediocre can be left out.  Nothing returned depends on ``phrase_chunk``, on stale workspace contents or on how the
+        index was built.  Arguments, checks and refusals are ``search_phrases_seeded``'s."""
+        def rerank(c):
+            _occ_rerank_launch(c, "sylber_dtw_rerank_occurrences", (_vp(self._x), c.N, c.dim, _vp(self._c)))
+
+        return self._seeded(rerank, phrases, seed_scores, seed_ids, k, refine, lengths, groups, exclude_same_group, sequences, phrase_chunk,
+                            return_candidates, _trusted_ids, _workspace_fill)
+
+    def _seeded(self, rerank, phrases, seed_scores, seed_ids, k, refine, lengths, groups, exclude_same_group, sequences, phrase_chunk,
+                return_candidates, trusted_ids, fill=None):
+        """the checks of ``search_phrases_seeded`` in their order, then ``_seeded_phrases`` with this stage 2"""
         k, m = _check_k_refine(k, refine, rerank=True)
         q, lens, pg, off = _phrase_args(len(self), self.dim, self.device, self.sequence_offsets, phrases, lengths, groups, exclude_same_group,
                                         sequences, 0, phrase_chunk, 0)
@@ -520,10 +555,10 @@ class SyllableIndex:
         if not 1 <= seeds <= MAX_SEEDS:
             raise ValueError("seeds must be in [1, %d], got %d" % (MAX_SEEDS, seeds))
         sc, si = sc.to(dev).contiguous(), si.to(dev).contiguous()
-        if not _trusted_ids and R and (int(si.min()) < -1 or int(si.max()) >= N):
+        if not trusted_ids and R and (int(si.min()) < -1 or int(si.max()) >= N):
             raise ValueError("seed_ids must lie in [-1, %d)" % N)
         return _seeded_phrases(N, self.dim, dev, self.metric, self._g, q, lens, pg, off, sc, si, k, m, phrase_chunk, return_candidates,
-                               lambda c: _rerank_launch(c, self._x, self._c))
+                               rerank, fill)
 
     # ---- warping paths -------------------------------------------------------------------------------------------------------------
     def align_phrases(self, phrases, spans, lengths=None, pair_chunk: Optional[int] = None, *, _tracked_start: bool = False):
@@ -531,7 +566,8 @@ class SyllableIndex:
         ``(rows int64 [P, k, Mx, 2], steps int32 [P, k], costs fp32 [P, k])`` on the device, ``Mx = max_p m_p``.  ``phrases`` and
         ``lengths=`` are exactly what the search that produced ``spans`` was given; ``spans`` int64 ``[P, k, 2]`` (host or device):
         (first row id, one past the last), ``(-1, -1)`` = padding -- the spans of ``search_phrases``, ``search_phrases_refined``,
-        ``search_phrases_seeded``, ``search_occurrences`` or ``search_occurrences_refined``, or any windows of your own.
+        ``search_phrases_seeded``, ``search_occurrences``, ``search_occurrences_refined`` or ``search_occurrences_seeded``, or any windows
+        of your own.
         ``rows[p, r, i]`` = (first row id, one past the last row id) of the stored rows that phrase row i is aligned to, so
         ``provenance`` works on it; ``(-1, -1)`` for ``i >= m_p``, for padding spans and for pairs of cost ``+inf``.  ``steps``: the
         cells on the path, 0 where ``rows`` is all padding; ``costs``: the DP's cost of that path, ``+inf`` there
@@ -823,6 +859,37 @@ class IVFSyllableIndex:
         bit.  Nothing returned depends on ``query_chunk``, ``phrase_chunk``, ``item_tiles``, stale workspaces, ``build`` versus
         ``build`` + ``add`` or a ``save`` / ``load`` round trip.  ``ivf.last_search`` keeps stage 1a's numbers and ``"seen"``: the
         mean number of seen sequences per phrase.  ``1 <= seeds <= 128``, ``k * refine <= 128``."""
+        q, lens, sc, si = self._phrase_seeds(phrases, k, nprobe, seeds, refine, lengths, groups, exclude_same_group, sequences, query_chunk,
+                                             phrase_chunk, item_tiles, _workspace_fill)
+        return self.index.search_phrases_seeded(q, sc, si, k, refine, lengths=lens, groups=groups, exclude_same_group=exclude_same_group,
+                                                sequences=sequences, phrase_chunk=phrase_chunk, return_candidates=return_candidates,
+                                                _trusted_ids=True)
+
+    def search_occurrences(self, phrases, k: int, nprobe: int, seeds: int = 32, refine: int = 4, *, lengths=None, groups=None,
+                           exclude_same_group: bool = False, sequences=None, query_chunk: int = DEFAULT_QUERY_CHUNK,
+                           phrase_chunk: int = DEFAULT_PHRASE_CHUNK, item_tiles: int = 0, return_candidates: bool = False,
+                           _workspace_fill=None):
+        """every non-overlapping occurrence of each phrase without a scan of the corpus -> ``(costs, seqs, spans)`` as
+        ``SyllableIndex.search_occurrences`` returns them (plus ``cand`` and ``bound`` with ``return_candidates=True``).  The
+        arguments are ``search_phrases``'s.  Stage 1a is ``search_phrases``'s, unchanged (``ivf.search`` on all phrase rows; it sets
+        ``ivf.last_search`` and its ``"seen"`` as there); stages 1b and 2 are ``ivf.index.search_occurrences_seeded``: the vote
+        for ``m = k * refine`` candidate sequences, then every occurrence in them by the exact fp32 recurrence.
+
+        So ``cand`` and ``bound`` are ``search_phrases``'s, bit for bit, and the result is ``ivf.index.search_occurrences`` restricted
+        to the sequences of ``cand``; with ``nprobe == nlist``, ``seeds`` at least the number of admissible rows and m at least the
+        number of admissible sequences it *is* ``ivf.index.search_occurrences``.  Stage 1 ranks a sequence by its best match: a
+        sequence whose many occurrences are all mediocre can be left out.  Nothing returned depends on ``query_chunk``,
+        ``phrase_chunk``, ``item_tiles``, stale workspaces, ``build`` versus ``build`` + ``add`` or a ``save`` / ``load`` round trip."""
+        q, lens, sc, si = self._phrase_seeds(phrases, k, nprobe, seeds, refine, lengths, groups, exclude_same_group, sequences, query_chunk,
+                                             phrase_chunk, item_tiles, _workspace_fill)
+        return self.index.search_occurrences_seeded(q, sc, si, k, refine, lengths=lens, groups=groups, exclude_same_group=exclude_same_group,
+                                                    sequences=sequences, phrase_chunk=phrase_chunk, return_candidates=return_candidates,
+                                                    _trusted_ids=True, _workspace_fill=_workspace_fill)
+
+    def _phrase_seeds(self, phrases, k, nprobe, seeds, refine, lengths, groups, exclude_same_group, sequences, query_chunk, phrase_chunk,
+                      item_tiles, fill):
+        """the checks and stage 1a of ``search_phrases`` / ``search_occurrences`` -> ``(phrase rows, lengths, seed scores, seed ids)``;
+        sets ``last_search``"""
         idx = self.index
         k, m = _check_k_refine(k, refine, rerank=True)
         nprobe = _check_nprobe(nprobe, self.nlist)
@@ -841,7 +908,7 @@ class IVFSyllableIndex:
         else:
             own = pg is not None and sequences is None         # the rows' groups decide the default sequences: exclude in stage 1a
             sc, si = self.search(q, seeds, nprobe, groups=np.repeat(pg, lens) if own else None, exclude_same_group=own,
-                                 query_chunk=query_chunk, item_tiles=item_tiles, _workspace_fill=_workspace_fill)
+                                 query_chunk=query_chunk, item_tiles=item_tiles, _workspace_fill=fill)
             # the seen sequences of each phrase, counted as the vote sees them
             d = sc if idx.metric == "l2" else torch.clamp_min(1.0 - sc, 0.0)
             valid = (si >= 0) & ~torch.isnan(sc) & ~torch.isposinf(d)
@@ -849,13 +916,11 @@ class IVFSyllableIndex:
             owner = torch.repeat_interleave(torch.arange(P, device=dev), torch.from_numpy(lens).to(dev))
             pairs = (owner[:, None] * (off.size - 1) + seq)[valid]
             self.last_search["seen"] = float(torch.unique(pairs).numel()) / P
-        return idx.search_phrases_seeded(q, sc, si, k, refine, lengths=lens, groups=groups, exclude_same_group=exclude_same_group,
-                                         sequences=sequences, phrase_chunk=phrase_chunk, return_candidates=return_candidates,
-                                         _trusted_ids=True)
+        return q, lens, sc, si
 
     def align_phrases(self, phrases, spans, lengths=None, pair_chunk: Optional[int] = None):
-        """the warping paths behind the spans of ``search_phrases``: ``ivf.index.align_phrases``, whose rows (in id order) are the
-        ones the exact re-rank ran on -> ``(rows, steps, costs)`` as there"""
+        """the warping paths behind the spans of ``search_phrases`` or ``search_occurrences``: ``ivf.index.align_phrases``, whose rows
+        (in id order) are the ones the exact re-rank ran on -> ``(rows, steps, costs)`` as there"""
         return self.index.align_phrases(phrases, spans, lengths=lengths, pair_chunk=pair_chunk)
 
     # ---- persistence ----------------------------------------------------------------------------------------------------------------

@@ -53,7 +53,21 @@ residual codes after ``drop_rows()``; ``IVFSyllableIndex.search_phrases`` at the
 (rows dropped, ``refine``) beside them; the dropped call's stage 1a (``ix.search`` alone), stage 2 alone and remainder (the vote and
 the host work); and stage 2 alone two ways on the same candidates: ``sylber_dtw_rerank_codes``, and ``ix.decode`` of the candidate
 sequences' rows into a scratch followed by ``sylber_dtw_rerank`` on it (the candidate copy to the host that sizes the scratch
-included, as in ``PQSyllableIndex``), with the scratch's rows.  Lazy state is built before anything is timed."""
+included, as in ``PQSyllableIndex``), with the scratch's rows.  Lazy state is built before anything is timed.
+
+``--occurrences`` combines with ``--ivf``, ``--ivfpq`` and ``--pq``: each new ``search_occurrences`` is timed beside its per-sequence
+sibling in the same process (``ivf_occ_ms`` beside ``ivf_phrase_ms``; ``occ_held_ms`` / ``occ_dropped_ms`` /
+``occ_residual_dropped_ms`` / ``pq_occ_dropped_ms`` beside ``held_ms`` / ``dropped_ms`` / ``residual_dropped_ms`` / ``pq_dropped_ms``;
+``pq_occ_held_ms`` / ``pq_occ_dropped_ms`` beside ``pq_held_ms`` / ``pq_dropped_ms``).  With ``--ivfpq`` the dropped half then reports the
+occurrence calls in place of its stage break-down, and stage 2 alone two ways on the dropped call's candidates:
+``sylber_dtw_rerank_occurrences_codes`` on the codes and ``sylber_dtw_rerank_occurrences`` on the decoded plane of the whole index
+(``two_entries_same_bits``).  Without ``--ivf`` / ``--ivfpq`` it also times ``sylber_dtw_rerank_occurrences`` alone on
+``search_occurrences_refined``'s candidates (``occ_rerank_alone_ms``).
+
+``--repeats R`` (``--ivf`` / ``--ivfpq``) plants each query phrase R times in one sequence -- the phrase is the noisy copy of the
+sequence's first m rows, and R - 1 further noisy copies of the phrase are written behind it -- so that occurrences exist;
+``*_planted_found`` is the mean number of a phrase's R planted spans that come back among its k (a returned span that shares half of
+a planted span's rows counts).  Shapes whose R m exceeds the sequences are left out."""
 import argparse
 import json
 import os
@@ -107,7 +121,7 @@ def rerank_alone(idx, phrases, lens, cand, k):
 
 
 def clustered_index(args, dev, g, rng):
-    """the data of the --ivf and --ivfpq legs -> (SyllableIndex, sequence lengths, offsets)"""
+    """the data of the --ivf and --ivfpq legs -> (SyllableIndex, sequence lengths, offsets, the shapes of ``planted_shapes``)"""
     from sylber_amd import SyllableIndex
     D, N = 768, args.N
     lens = rng.integers(20, 61, N // 20 + 1)
@@ -122,7 +136,78 @@ def clustered_index(args, dev, g, rng):
     for r0 in range(0, N, 1 << 19):
         n = min(1 << 19, N - r0)
         x[r0:r0 + n] = cent[torch.multinomial(w, n, replacement=True, generator=g)] + torch.randn(n, D, device=dev, generator=g)
-    return SyllableIndex(x, metric="l2", groups=groups, device=dev), lens, off
+    shapes = planted_shapes(args, x, lens, off, dev, g, rng)                # --repeats > 1 writes into x: before the index exists
+    return SyllableIndex(x, metric="l2", groups=groups, device=dev), lens, off, shapes
+
+
+def planted_shapes(args, x, lens, off, dev, g, rng):
+    """per (rows, m) of --rows x --ms: ``(m, P, phrases [P m, D], truth [P] on the device, planted [P, R, 2] on the device)``.  A phrase
+    is m consecutive rows of its truth sequence plus ``noise`` x gaussian noise (the planted noisy copy).  With ``--repeats R`` > 1 the
+    truth sequences are distinct and hold R m rows or more; the phrase comes from the sequence's first m rows and R - 1 further noisy
+    copies OF THE PHRASE are written into the next slots of m rows, so that the sequence holds R occurrences: ``planted`` are their spans.
+    A shape whose R m exceeds every sequence, or that needs more sequences than there are, is left out."""
+    D, R = x.shape[1], args.repeats
+    used = np.zeros(lens.size, bool)
+    shapes = []
+    for rows in [int(v) for v in args.rows.split(",")]:
+        for m in [int(v) for v in args.ms.split(",")]:
+            P = rows // m
+            ok = np.nonzero((lens >= R * m) & ~used)[0]
+            if R > 1:
+                if ok.size < P:
+                    print(json.dumps({"rows": rows, "m": m, "skipped": "fewer than %d free sequences of %d rows" % (P, R * m)}), file=sys.stderr)
+                    continue
+                truth = rng.choice(ok, P, replace=False)
+                used[truth] = True
+                start = off[truth]
+            else:
+                truth = ok[rng.integers(0, ok.size, P)]
+                start = off[truth] + (rng.random(P) * (lens[truth] - m + 1)).astype(np.int64)
+            pick = torch.from_numpy((start[:, None] + np.arange(m)[None, :]).reshape(-1)).to(dev)
+            ph = x[pick] + args.noise * torch.randn(P * m, D, device=dev, generator=g)
+            for r in range(1, R):
+                x[pick + r * m] = ph + args.noise * torch.randn(P * m, D, device=dev, generator=g)
+            first = start[:, None] + m * np.arange(R)[None, :]
+            planted = torch.from_numpy(np.stack([first, first + m], 2)).to(dev)
+            shapes.append((m, P, ph, torch.from_numpy(truth).to(dev), planted))
+    return shapes
+
+
+def planted_found(spans, planted):
+    """the mean number of a phrase's planted spans [P, R, 2] that come back among its k spans [P, k, 2]: a planted span counts when a
+    returned one shares at least half of its rows"""
+    lo = torch.maximum(spans[:, :, None, 0], planted[:, None, :, 0])
+    hi = torch.minimum(spans[:, :, None, 1], planted[:, None, :, 1])
+    need = (planted[:, None, :, 1] - planted[:, None, :, 0] + 1) // 2
+    return round(float(((hi - lo >= need) & (spans[:, :, None, 0] >= 0)).any(1).sum(1).float().mean()), 3)
+
+
+def occ_stage2_alone(dev, phrases, lens, cand, k, off, entry, db):
+    """a closure that runs stage 2 of an occurrence search alone on the candidates ``cand [P, m]`` of one call: ``entry`` is
+    ``sylber_dtw_rerank_occurrences`` with ``db = (rows, N, D, norms)`` or ``sylber_dtw_rerank_occurrences_codes`` with ``db`` = the
+    coded-database group, N, D and the norms (L2, the phrases as given).  Packing, tables, buffers and the workspace are made here,
+    before the clock starts; one launch, so P m k must stay below 2^30."""
+    from sylber_amd import _lib
+    from sylber_amd._index import _on_device, _phrase_blocks, _phrase_outputs, _prep, _row_norms
+    from sylber_amd.kmeans import _stream, _vp
+    lib = _lib.load()
+    lens = np.asarray(lens, np.int64)
+    P, m = cand.shape
+    off_d = _on_device(off, np.int32, dev)
+    b = _phrase_blocks(lib, dev, _prep(phrases, "l2", dev), lens, 0, P, off, m, 0, 0, None)
+    qn = _row_norms(b.qp)
+    ws = torch.empty(int(lib.sylber_dtw_occ_workspace_bytes(P, m, k)), dtype=torch.uint8, device=dev)
+    place_d, len_d = _on_device(b.place, np.int32, dev), _on_device(lens, np.int32, dev)
+    c32 = cand.to(torch.int32).contiguous()
+    costs, seqs, spans = _phrase_outputs(P, k, dev)
+    fn = getattr(lib, entry)
+
+    def run():
+        with torch.cuda.device(dev):
+            _lib.check(fn(_vp(b.qp), b.nb, _vp(qn), _vp(place_d), _vp(len_d), P, *db, 0, _vp(c32), m, _vp(off_d), off.size - 1, k, _vp(costs),
+                          _vp(seqs), _vp(spans), _vp(ws), _stream(dev)), entry)
+        return costs, seqs, spans
+    return run
 
 
 def codes_rerank_alone(ix, phrases, lens, cand, k):
@@ -202,10 +287,11 @@ def sampled_codebooks(rows, M, g):
 
 def ivfpq_leg(args, dev):
     from sylber_amd import IVFPQSyllableIndex, IVFSyllableIndex, PQSyllableIndex
+    from sylber_amd.kmeans import _vp
     g = torch.Generator(device=dev).manual_seed(0)
     rng = np.random.default_rng(0)
     D, N, k, M = 768, args.N, args.k, args.M
-    idx, lens, off = clustered_index(args, dev, g, rng)
+    idx, lens, off, shapes = clustered_index(args, dev, g, rng)
     idx.sequence_offsets()
     ivf = IVFSyllableIndex.build(idx, nlist=args.nlist, seed=0, max_iter=args.max_iter, train_rows=args.train_rows)
     cb = sampled_codebooks(idx.features, M, g)
@@ -229,31 +315,69 @@ def ivfpq_leg(args, dev):
             "data": "synthetic mixture of %d Gaussians, sequences of 20 to 60 rows, planted noisy phrases" % args.centres}
     print(json.dumps(head), file=sys.stderr, flush=True)
     configs = [tuple(int(v) for v in c.split(":")) for c in args.configs.split(",")]
-    shapes = []
-    for rows in [int(v) for v in args.rows.split(",")]:
-        for m in [int(v) for v in args.ms.split(",")]:
-            P = rows // m
-            ok = np.nonzero(lens >= m)[0]
-            truth = ok[rng.integers(0, ok.size, P)]
-            start = off[truth] + (rng.random(P) * (lens[truth] - m + 1)).astype(np.int64)
-            pick = torch.from_numpy((start[:, None] + np.arange(m)[None, :]).reshape(-1)).to(dev)
-            shapes.append((m, P, idx.features[pick] + args.noise * torch.randn(P * m, D, device=dev, generator=g), torch.from_numpy(truth).to(dev)))
+    head["repeats"] = args.repeats
+    if args.occurrences:
+        for i in (ix, ixr):
+            i.search_occurrences(warm, 1, 1, lengths=[2], rerank=False)
+        pq.search_occurrences(warm, 1, 1, args.storage, lengths=[2], rerank=False)
+        torch.cuda.synchronize()
     out = []
     planted = lambda got, truth_d: round(float((got[1][:, 0] == truth_d).float().mean()), 4)
     for dropped in (False, True):                                             # every rows-held figure first: drop_rows() cannot be undone
         if dropped:
             for i in (ix, ixr, pq):
                 i.drop_rows()
-        for m, P, ph, truth_d in shapes:
+        for m, P, ph, truth_d, planted_d in shapes:
             ln = [m] * P
             for nprobe, seeds, refine in configs:
                 row = {"rows": P * m, "m": m, "phrases": P, "nprobe": nprobe, "seeds": seeds, "refine": refine}
+                kw = dict(seeds=seeds, refine=refine, lengths=ln)
                 if not dropped:
                     call = lambda: ix.search_phrases(ph, k, nprobe, seeds=seeds, refine=refine, lengths=ln, rerank=True)
                     t, lo, hi = timed(call, args.iters)
                     t_ivf, _, _ = timed(lambda: ivf.search_phrases(ph, k, nprobe, seeds=seeds, refine=refine, lengths=ln), args.iters)
                     row.update(held_ms=round(t, 2), held_ms_min_max=[round(lo, 2), round(hi, 2)], held_planted_top1=planted(call(), truth_d),
                                ivf_phrase_ms=round(t_ivf, 2))
+                    if args.occurrences:
+                        occ = lambda: ix.search_occurrences(ph, k, nprobe, rerank=True, **kw)
+                        to, lo, hi = timed(occ, args.iters)
+                        t_io, lo2, hi2 = timed(lambda: ivf.search_occurrences(ph, k, nprobe, **kw), args.iters)
+                        row.update(occ_held_ms=round(to, 2), occ_held_ms_min_max=[round(lo, 2), round(hi, 2)], occ_held_over_held=round(to / t, 3),
+                                   occ_held_planted_found=planted_found(occ()[2], planted_d), ivf_occ_ms=round(t_io, 2),
+                                   ivf_occ_ms_min_max=[round(lo2, 2), round(hi2, 2)], ivf_occ_over_ivf_phrase=round(t_io / t_ivf, 3),
+                                   ivf_occ_planted_found=planted_found(ivf.search_occurrences(ph, k, nprobe, **kw)[2], planted_d))
+                elif args.occurrences:                                      # every occurrence from the codes, beside the per-sequence siblings
+                    t, lo, hi = timed(lambda: ix.search_phrases(ph, k, nprobe, **kw), args.iters)
+                    occ = lambda: ix.search_occurrences(ph, k, nprobe, return_candidates=True, **kw)
+                    to, lo_o, hi_o = timed(occ, args.iters)
+                    got = occ()
+                    t_r, _, _ = timed(lambda: ixr.search_phrases(ph, k, nprobe, **kw), args.iters)
+                    occr = lambda: ixr.search_occurrences(ph, k, nprobe, **kw)
+                    to_r, lo_r, hi_r = timed(occr, args.iters)
+                    t_pq, _, _ = timed(lambda: pq.search_phrases(ph, k, refine, args.storage, lengths=ln), args.iters)
+                    occp = lambda: pq.search_occurrences(ph, k, refine, args.storage, lengths=ln)
+                    to_pq, lo_p, hi_p = timed(occp, args.iters)
+                    db, pc = ix._coded_db()
+                    if "plane" not in head:                                  # the decoded plane of the whole index, once: 4 N D bytes
+                        head["plane"] = torch.cat([ix.decode(torch.arange(r0, min(N, r0 + (1 << 18)), device=dev)) for r0 in range(0, N, 1 << 18)])
+                    codes_run = occ_stage2_alone(dev, ph, ln, got[3], k, off, "sylber_dtw_rerank_occurrences_codes", db + (N, D, _vp(pc)))
+                    plane_run = occ_stage2_alone(dev, ph, ln, got[3], k, off, "sylber_dtw_rerank_occurrences", (_vp(head["plane"]), N, D, _vp(pc)))
+                    t_codes, lo_c, hi_c = timed(codes_run, args.iters)
+                    t_plane, lo_f, hi_f = timed(plane_run, args.iters)
+                    a, b = codes_run(), plane_run()
+                    same = all(torch.equal(u, v) for u, v in zip(a, b)) and all(torch.equal(u, v) for u, v in zip(a, got[:3]))
+                    sq = got[1].sort(1).values
+                    row.update(dropped_ms=round(t, 2), dropped_ms_min_max=[round(lo, 2), round(hi, 2)], occ_dropped_ms=round(to, 2),
+                               occ_dropped_ms_min_max=[round(lo_o, 2), round(hi_o, 2)], occ_dropped_over_dropped=round(to / t, 3),
+                               occ_dropped_planted_found=planted_found(got[2], planted_d), residual_dropped_ms=round(t_r, 2),
+                               occ_residual_dropped_ms=round(to_r, 2), occ_residual_dropped_ms_min_max=[round(lo_r, 2), round(hi_r, 2)],
+                               occ_residual_over_residual=round(to_r / t_r, 3), occ_residual_planted_found=planted_found(occr()[2], planted_d),
+                               pq_dropped_ms=round(t_pq, 2), pq_occ_dropped_ms=round(to_pq, 2), pq_occ_dropped_ms_min_max=[round(lo_p, 2), round(hi_p, 2)],
+                               pq_occ_over_pq=round(to_pq / t_pq, 3), pq_occ_planted_found=planted_found(occp()[2], planted_d),
+                               occ_codes_entry_ms=round(t_codes, 2), occ_codes_entry_ms_min_max=[round(lo_c, 2), round(hi_c, 2)],
+                               occ_fp32_entry_on_decoded_plane_ms=round(t_plane, 2), occ_fp32_entry_ms_min_max=[round(lo_f, 2), round(hi_f, 2)],
+                               occ_codes_over_fp32=round(t_codes / t_plane, 3), two_entries_same_bits=same,
+                               occ_distinct_sequences=round(float((1 + (sq[:, 1:] != sq[:, :-1]).sum(1)).float().mean()), 2))
                 else:
                     call = lambda: ix.search_phrases(ph, k, nprobe, seeds=seeds, refine=refine, lengths=ln, return_candidates=True)
                     t, lo, hi = timed(call, args.iters)
@@ -278,6 +402,7 @@ def ivfpq_leg(args, dev):
                                pair_columns=cols, fraction=round(ls["fraction"], 6), seen=round(ls["seen"], 1))
                 print(json.dumps(row), file=sys.stderr, flush=True)
                 out.append(row)
+    head.pop("plane", None)
     head.update(rows=out, device_bytes={"syllable_index_rows_norms_groups": 4 * N * D + 8 * N, "rows_held": held_bytes,
                                         "rows_dropped": {"ivfpq": ix.nbytes, "ivfpq_residual": ixr.nbytes, "pq": pq.nbytes}})
     print(json.dumps(head))
@@ -288,7 +413,7 @@ def ivf_leg(args, dev):
     g = torch.Generator(device=dev).manual_seed(0)
     rng = np.random.default_rng(0)
     D, N, k = 768, args.N, args.k
-    idx, lens, off = clustered_index(args, dev, g, rng)
+    idx, lens, off, shapes = clustered_index(args, dev, g, rng)
     idx.sequence_offsets()
     idx.half_rows(args.storage)
     torch.cuda.synchronize()
@@ -301,41 +426,39 @@ def ivf_leg(args, dev):
     print(json.dumps(head), file=sys.stderr, flush=True)
     configs = [tuple(int(v) for v in c.split(":")) for c in args.configs.split(",")]
     out = []
-    for rows in [int(v) for v in args.rows.split(",")]:
-        for m in [int(v) for v in args.ms.split(",")]:
-            P = rows // m
-            ok = np.nonzero(lens >= m)[0]
-            truth = ok[rng.integers(0, ok.size, P)]
-            start = off[truth] + (rng.random(P) * (lens[truth] - m + 1)).astype(np.int64)
-            pick = torch.from_numpy((start[:, None] + np.arange(m)[None, :]).reshape(-1)).to(dev)
-            ph = idx.features[pick] + args.noise * torch.randn(P * m, D, device=dev, generator=g)
-            ln = [m] * P
-            truth_d = torch.from_numpy(truth).to(dev)
-            t_exact, lo, hi = timed(lambda: idx.search_phrases(ph, k, lengths=ln), min(args.iters, 2))
-            exact = idx.search_phrases(ph, k, lengths=ln)[1]
-            t_ref, lo2, hi2 = timed(lambda: idx.search_phrases_refined(ph, k, args.refine, args.storage, lengths=ln), args.iters)
-            base = {"rows": P * m, "m": m, "phrases": P, "phrase_ms": round(t_exact, 2), "phrase_ms_min_max": [round(lo, 2), round(hi, 2)],
-                    "refined_ms": round(t_ref, 2), "refined_ms_min_max": [round(lo2, 2), round(hi2, 2)], "refined_refine": args.refine,
-                    "exact_planted_top1": round(float((exact[:, 0] == truth_d).float().mean()), 4)}
-            for nprobe, seeds, refine in configs:
-                if nprobe > min(args.nlist, 128) or k * refine > 128:
-                    continue
-                call = lambda: ivf.search_phrases(ph, k, nprobe, seeds=seeds, refine=refine, lengths=ln, return_candidates=True)
-                t, lo, hi = timed(call, args.iters)
-                got = call()
-                ls = dict(ivf.last_search)
-                t_seed, _, _ = timed(lambda: ivf.search(ph, seeds, nprobe), args.iters)
-                t_rr, _, _ = timed(rerank_alone(idx, ph, ln, got[3], k), args.iters)
-                row = dict(base, nprobe=nprobe, seeds=seeds, refine=refine, ivf_phrase_ms=round(t, 2), ivf_phrase_ms_min_max=[round(lo, 2), round(hi, 2)],
-                           seed_search_ms=round(t_seed, 2), rerank_ms=round(t_rr, 2), remainder_ms=round(t - t_seed - t_rr, 2),
-                           over_refined=round(t / t_ref, 3), over_phrase=round(t / t_exact, 3), fraction=round(ls["fraction"], 6),
-                           seen=round(ls["seen"], 1),
-                           recall_at_k=round(float(((got[1][:, :, None] == exact[:, None, :]) & (exact[:, None, :] >= 0)).any(1).sum())
-                                             / max(1, int((exact >= 0).sum())), 4), recovered_topk=round(float((got[1] == exact).all(1).float().mean()), 4),
-                           recovered_top1=round(float((got[1][:, 0] == exact[:, 0]).float().mean()), 4),
-                           planted_top1=round(float((got[1][:, 0] == truth_d).float().mean()), 4))
-                print(json.dumps(row), file=sys.stderr, flush=True)
-                out.append(row)
+    head["repeats"] = args.repeats
+    for m, P, ph, truth_d, planted_d in shapes:
+        ln = [m] * P
+        t_exact, lo, hi = timed(lambda: idx.search_phrases(ph, k, lengths=ln), min(args.iters, 2))
+        exact = idx.search_phrases(ph, k, lengths=ln)[1]
+        t_ref, lo2, hi2 = timed(lambda: idx.search_phrases_refined(ph, k, args.refine, args.storage, lengths=ln), args.iters)
+        base = {"rows": P * m, "m": m, "phrases": P, "phrase_ms": round(t_exact, 2), "phrase_ms_min_max": [round(lo, 2), round(hi, 2)],
+                "refined_ms": round(t_ref, 2), "refined_ms_min_max": [round(lo2, 2), round(hi2, 2)], "refined_refine": args.refine,
+                "exact_planted_top1": round(float((exact[:, 0] == truth_d).float().mean()), 4)}
+        for nprobe, seeds, refine in configs:
+            if nprobe > min(args.nlist, 128) or k * refine > 128:
+                continue
+            call = lambda: ivf.search_phrases(ph, k, nprobe, seeds=seeds, refine=refine, lengths=ln, return_candidates=True)
+            t, lo, hi = timed(call, args.iters)
+            got = call()
+            ls = dict(ivf.last_search)
+            t_seed, _, _ = timed(lambda: ivf.search(ph, seeds, nprobe), args.iters)
+            t_rr, _, _ = timed(rerank_alone(idx, ph, ln, got[3], k), args.iters)
+            row = dict(base, nprobe=nprobe, seeds=seeds, refine=refine, ivf_phrase_ms=round(t, 2), ivf_phrase_ms_min_max=[round(lo, 2), round(hi, 2)],
+                       seed_search_ms=round(t_seed, 2), rerank_ms=round(t_rr, 2), remainder_ms=round(t - t_seed - t_rr, 2),
+                       over_refined=round(t / t_ref, 3), over_phrase=round(t / t_exact, 3), fraction=round(ls["fraction"], 6),
+                       seen=round(ls["seen"], 1),
+                       recall_at_k=round(float(((got[1][:, :, None] == exact[:, None, :]) & (exact[:, None, :] >= 0)).any(1).sum())
+                                         / max(1, int((exact >= 0).sum())), 4), recovered_topk=round(float((got[1] == exact).all(1).float().mean()), 4),
+                       recovered_top1=round(float((got[1][:, 0] == exact[:, 0]).float().mean()), 4),
+                       planted_top1=round(float((got[1][:, 0] == truth_d).float().mean()), 4))
+            if args.occurrences:
+                occ = lambda: ivf.search_occurrences(ph, k, nprobe, seeds=seeds, refine=refine, lengths=ln)
+                to, lo, hi = timed(occ, args.iters)
+                row.update(ivf_occ_ms=round(to, 2), ivf_occ_ms_min_max=[round(lo, 2), round(hi, 2)], ivf_occ_over_ivf_phrase=round(to / t, 3),
+                           ivf_occ_planted_found=planted_found(occ()[2], planted_d))
+            print(json.dumps(row), file=sys.stderr, flush=True)
+            out.append(row)
     head["rows"] = out
     print(json.dumps(head))
 
@@ -351,6 +474,7 @@ def main():
     ap.add_argument("--storage", default="fp16", choices=["fp16", "bf16"])
     ap.add_argument("--refine", type=int, default=4)
     ap.add_argument("--occurrences", action="store_true")
+    ap.add_argument("--repeats", type=int, default=1)
     ap.add_argument("--align", action="store_true")
     ap.add_argument("--pq", action="store_true")
     ap.add_argument("--M", type=int, default=48)
@@ -423,6 +547,11 @@ def main():
                     row.update(storage=args.storage, refine=args.refine, refined_ms=round(t2, 2), refined_ms_min_max=[round(lo, 2), round(hi, 2)])
                 t5, lo5, hi5 = timed(lambda: idx.search_occurrences(ph, k, lengths=ln), args.iters)
                 t6, lo6, hi6 = timed(lambda: idx.search_occurrences_refined(ph, k, args.refine, args.storage, lengths=ln), args.iters)
+                cand = idx.search_occurrences_refined(ph, k, args.refine, args.storage, lengths=ln, return_candidates=True)[3]
+                from sylber_amd.kmeans import _vp
+                t8, lo8, hi8 = timed(occ_stage2_alone(dev, ph, ln, cand, k, idx.sequence_offsets(), "sylber_dtw_rerank_occurrences",
+                                                      (_vp(idx._x), N, D, _vp(idx._c))), args.iters)
+                row.update(occ_rerank_alone_ms=round(t8, 3), occ_rerank_alone_ms_min_max=[round(lo8, 3), round(hi8, 3)])
                 sq = idx.search_occurrences(ph, k, lengths=ln)[1].sort(1).values
                 distinct = 1 + (sq[:, 1:] != sq[:, :-1]).sum(1)
                 row.update(occ_ms=round(t5, 2), occ_ms_min_max=[round(lo5, 2), round(hi5, 2)], occ_over_phrase=round(t5 / t, 3),
@@ -452,6 +581,12 @@ def main():
                     held[str(r)] = round(float((got == exact).all(1).float().mean()), 4)
                     got = pq.search_phrases(ph, k, r, args.storage, lengths=ln, rerank=False)[1]
                     dropped[str(r)] = round(float((got.sort(1).values == want).all(1).float().mean()), 4)
+                if args.occurrences:
+                    t9, lo9, hi9 = timed(lambda: pq.search_occurrences(ph, k, args.refine, args.storage, lengths=ln, rerank=True), args.iters)
+                    t10, lo10, hi10 = timed(lambda: pq.search_occurrences(ph, k, args.refine, args.storage, lengths=ln, rerank=False), args.iters)
+                    row.update(pq_occ_held_ms=round(t9, 2), pq_occ_held_ms_min_max=[round(lo9, 2), round(hi9, 2)], pq_occ_held_over_pq_held=round(t9 / t3, 3),
+                               pq_occ_dropped_ms=round(t10, 2), pq_occ_dropped_ms_min_max=[round(lo10, 2), round(hi10, 2)],
+                               pq_occ_dropped_over_pq_dropped=round(t10 / t4, 3))
                 row.update(M=args.M, pq_held_ms=round(t3, 2), pq_held_ms_min_max=[round(lo3, 2), round(hi3, 2)], pq_dropped_ms=round(t4, 2),
                            pq_dropped_ms_min_max=[round(lo4, 2), round(hi4, 2)], pq_held_over_refined=round(t3 / t2, 3),
                            pq_dropped_over_refined=round(t4 / t2, 3), pq_recovered_topk_held=held, pq_recovered_topk_dropped=dropped)
