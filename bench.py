@@ -1,7 +1,14 @@
 #!/usr/bin/env python
 """Throughput benchmark of the Segmenter hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full]
+
+A plain run does what its headline figure needs and nothing else: it sets up, runs the W warm-up steps, times the K steps, writes
+its outputs if ``--dump-outputs`` is given and prints the result line.  ``--full`` adds, after the timed steps and outside them, every
+other measurement of this script: the per-kernel pass behind ``roofline`` / ``kernel_ms_per_forward``, the API-level (PCIe-inclusive)
+timings, the CPU baseline, ``--agreement-clips``, the ``other_configs`` block (long-form, fp8, fp16, split16, the one-rank rehearsal of
+the N > 1 step), ``box_speed``, ``segments_per_clip`` and, for N > 1, the ``results_left_sharded`` pass.  In a plain line those entries
+are null or absent; ``metric``, ``value``, ``unit``, ``higher_is_better``, ``dtype`` and ``ms_per_step`` are the same in both.
 
 N > 1 with no WORLD_SIZE in the environment re-executes itself under ``python -m torch.distributed.run``
 (one rank per GPU, rendezvous on 127.0.0.1) and fails loudly when fewer than N GPUs are visible; launched
@@ -50,7 +57,12 @@ def parse_args():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=BATCH_PER_GPU, help="clips per GPU")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every other measurement (per-kernel roofline pass, API-level timings, CPU baseline, "
+                         "--agreement-clips, `other_configs`, `box_speed`, `segments_per_clip`, N>1: `results_left_sharded`); without it the run "
+                         "ends with the headline figure.  --no-cpu-baseline / --no-api / --no-other-configs / --no-exchange-rehearsal take "
+                         "single parts out of a --full run")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--no-exchange", action="store_true",
                     help="N>1: time resident shards (no data-path collective) as `value`; the exchange figure moves to `exchange`")
     ap.add_argument("--no-overlap", action="store_true", help="one batch in flight, segmenter on the forward stream")
@@ -91,9 +103,9 @@ def parse_args():
     ap.add_argument("--plain-streams", action="store_true", help="A/B switch: take the pipeline's streams from the pool without the hardware-queue probe")
     ap.add_argument("--skip-segment", action="store_true",
                     help="A/B switch: leave boundary detection out of the timed steps (the line is marked `invalid`)")
-    ap.add_argument("--no-api", action="store_true", help="skip the API-level (PCIe-inclusive) Segmenter.__call__ timing")
+    ap.add_argument("--no-api", action="store_true", help="--full: skip the API-level (PCIe-inclusive) Segmenter.__call__ timing")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="skip the `other_configs` block (BASELINE configs[3] long-form, configs[4] fp8 and the split16 parity mode, "
+                    help="--full: skip the `other_configs` block (BASELINE configs[3] long-form, configs[4] fp8 and the split16 parity mode, "
                          "10 steps each in this same process after the headline run; N = 1, default workload only)")
     ap.add_argument("--exchange-root-copies", action="store_true", help="A/B: root's own share goes through the collectives' device-to-device copies as in rounds 2-6a "
                     "(default since round 6: root computes on a view of its chunk and writes its results straight into the gathered tensors; ShardedSegmenter.inplace_root)")
@@ -113,7 +125,7 @@ def parse_args():
     ap.add_argument("--no-exchange-rehearsal", action="store_true",
                     help="skip the one-rank RCCL self-test child of `other_configs` (the N > 1 code path on this one GPU)")
     ap.add_argument("--agreement-clips", type=int, default=0,
-                    help="also report bf16-vs-fp32 segment agreement on this many synthetic clips (fp32 parity mode as truth)")
+                    help="--full: also report bf16-vs-fp32 segment agreement on this many synthetic clips (fp32 parity mode as truth)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the timed path computed in its last step (rank 0) as DIR/<name>.npy: "
                          "hidden_states, segments, segment_counts, segment_features (float32 / float64, all finite: table slots past an "
@@ -122,6 +134,8 @@ def parse_args():
     args = ap.parse_args()
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.agreement_clips > 0 and not args.full:
+        ap.error("--agreement-clips is a measurement of its own: it needs --full")
     return args
 
 
@@ -323,7 +337,7 @@ def exchange_rehearsal(timeout_s: int = 150) -> dict:
     resident one of the same child -- what the collectives cost the persistent GEMM workgroups they share the chip with, with zero
     remote bytes.  A child, not this process: a communicator that hangs must not take the headline line with it."""
     import subprocess
-    cmd = [sys.executable, os.path.abspath(__file__), "--exchange-selftest", "--no-api", "--no-cpu-baseline", "--no-other-configs", "--steps", "10",
+    cmd = [sys.executable, os.path.abspath(__file__), "--exchange-selftest", "--full", "--no-api", "--no-cpu-baseline", "--no-other-configs", "--steps", "10",
            "--warmup", "3", "--exchange-timeout", str(max(30, timeout_s - 60))]
     t0 = time.perf_counter()
     try:
@@ -744,7 +758,7 @@ def main():
             "value": round(value_, 1), "unit": "audio-sec/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": round(1e3 * elapsed_ / args.steps, 3),
             "ms_per_step_median": None if med_ is None else round(med_, 3),
-            "higher_is_better": True, "scaling": "weak",
+            "higher_is_better": True, "scaling": "weak", "full": args.full,
             "vs_baseline": None, "dtype": dtype, "data": "synthetic",
             "config": {"workload": "Segmenter forward (conv frontend + HuBERT-9L encoder + boundary detection + "
                                    "segment mean-pool), batch %d x %g s 16 kHz random waveforms per GPU, random-init "
@@ -857,7 +871,7 @@ def main():
                 exchange_first = True
                 secondary = ("resident_shards", r_elapsed, r_med)
             xdone["exchange"] = (x_elapsed, x_med)
-            if args.gather == "root":
+            if args.gather == "root" and args.full:
                 # the same step with the results left on their ranks: what the root gather costs, and the realistic corpus deployment.
                 # OPTIONAL: a failure (or a hang: the watchdog below) here must not cost the exchange figure measured above
                 try:
@@ -886,7 +900,7 @@ def main():
     roofline = None
     kernels = {}
     frontend = None
-    if rank == 0 and args.precision == "fp32":
+    if args.full and rank == 0 and args.precision == "fp32":
         # the exact mode: every contraction on v_mfma_f32_32x32x2_f32 (157.3 TFLOP/s dense, MI355X_MICROARCH.md)
         enc.set_profiling(True)
         nprof = 3
@@ -904,7 +918,7 @@ def main():
                         "achieved": round(tf, 1), "peak": 157.3, "unit": "TFLOP/s", "frac": round(tf / 157.3, 4), "traffic": None,
                         "traffic_note": "no PMC pass for the parity mode", "flops_per_forward": gemm_fl,
                         "ms_per_forward": kernels["gemm_f32"]}
-    if rank == 0 and args.precision != "fp32":
+    if args.full and rank == 0 and args.precision != "fp32":
         # the per-kernel pass runs ONE handle with nothing else on the chip: it tells the library so (SYLBER_OPT_GEMM_MODEL: the tiles a
         # synchronous caller gets), where the timed steps above declared NPIPE batches in flight; `roofline.tile_selection` says which
         if not any(kv.startswith("12=") for kv in args.opt):
@@ -992,7 +1006,7 @@ def main():
 
     # ---- API level, PCIe inclusive (never `value`): Segmenter.__call__ on host tensors -> numpy dicts
     api = None
-    if rank == 0 and world == 1 and not args.no_api:
+    if args.full and rank == 0 and world == 1 and not args.no_api:
         from sylber_amd import Segmenter
         seg_api = Segmenter(model_ckpt=sd, device=str(dev), precision=args.precision)
         host_wavs = [w[None, :].clone() for w in noise_batch(B, clip_samples, seed=0)]
@@ -1063,11 +1077,11 @@ def main():
         del seg_api
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(sd)
 
     agreement = None
-    if rank == 0 and world == 1 and args.agreement_clips > 0 and args.precision != "fp32":
+    if args.full and rank == 0 and world == 1 and args.agreement_clips > 0 and args.precision != "fp32":
         from sylber_amd.agreement import segment_agreement
         agreement = segment_agreement(sd, enc, args.agreement_clips, device=str(dev))
 
@@ -1075,7 +1089,7 @@ def main():
     # command, so configs[3] (long-form), configs[4] (fp8) and the mode that meets north_star's "boundaries bit-identical"
     # (split16) are measured here, each with its own roofline -- fp8 launches against the fp8 peak
     other = None
-    if (rank == 0 and world == 1 and not args.no_other_configs and args.precision == "bf16" and B == BATCH_PER_GPU
+    if (args.full and rank == 0 and world == 1 and not args.no_other_configs and args.precision == "bf16" and B == BATCH_PER_GPU
             and clip_samples == CLIP_SAMPLES and not args.ragged and not args.opt and args.gemm_tile < 0):
         other = {}
         for name, (prec, b_, secs, agree) in {"configs[3] long-form 8 x 60 s, bf16": ("bf16", 8, 60.0, 0),
@@ -1095,7 +1109,7 @@ def main():
     # One fixed, shape-independent launch series of the same library -- the 4096^3 bf16 GEMM loop, hot operands -- lets a reader
     # normalise a slow box: value / box_speed is comparable across runs
     box_speed = None
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         try:
             import ctypes as _ct
             from sylber_amd import _lib as _l
@@ -1114,7 +1128,7 @@ def main():
             box_speed = {"error": "%s: %s" % (type(e).__name__, e)}
 
     seg_stats = None
-    if rank == 0:
+    if args.full and rank == 0:
         h = enc.forward(my_batch, None)
         _, nseg_t, _ = enc.segment(h, 2.6, 0.8)
         nn_ = nseg_t.float()

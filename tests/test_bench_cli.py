@@ -91,6 +91,21 @@ def test_steps_must_be_at_least_one():
     assert "{" not in r.stdout
 
 
+def test_full_is_an_option_and_off_by_default(monkeypatch):
+    """a plain command line asks for the headline figure alone; --full turns every other measurement on, and a measurement asked for
+    by name without it is an error, not something silently left out"""
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "5", "--warmup", "2"])
+    a = bench.parse_args()
+    assert a.full is False and (a.gpus, a.steps, a.warmup) == (1, 5, 2)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--agreement-clips", "8"])
+    a = bench.parse_args()
+    assert a.full is True and a.agreement_clips == 8
+    r = run("--agreement-clips", "8")
+    assert r.returncode == 2 and "--full" in r.stderr and "{" not in r.stdout
+
+
 def test_dump_outputs_fits_the_budget_with_a_fixed_sample(tmp_path):
     """--dump-outputs on the default workload's four arrays (98 MB): at most 64 MB in all, small arrays whole, the large ones a
     seeded sample of rows that depends on the shapes alone, so that two runs write the same rows"""

@@ -5,7 +5,7 @@ ROOT=$(pwd)
 OUT=$ROOT/gpurun_out/final
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-F="--no-cpu-baseline --no-api --no-other-configs"
+F="--full --no-cpu-baseline --no-api --no-other-configs"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_pipelined -- python $ROOT/bench.py --steps 10 --warmup 3 $F > $OUT/trace_pipelined.log 2>&1
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_sequential -- python $ROOT/bench.py --steps 10 --warmup 3 $F --no-overlap > $OUT/trace_sequential.log 2>&1
 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_fetch -- python $ROOT/bench.py --steps 3 --warmup 1 $F --no-overlap > $OUT/pmc_fetch.log 2>&1

@@ -8,7 +8,7 @@ echo "| NCCL_MIN/MAX_NCHANNELS | exchange ms/step | resident ms/step (same proce
 echo "|---|---:|---:|---:|---:|"
 for ch in default 1 2 4 8 16 32; do
   if [ "$ch" = default ]; then unset NCCL_MIN_NCHANNELS NCCL_MAX_NCHANNELS; else export NCCL_MIN_NCHANNELS=$ch NCCL_MAX_NCHANNELS=$ch; fi
-  python bench.py --exchange-selftest --no-api --no-cpu-baseline --no-other-configs --steps 20 --warmup 5 2>/dev/null | tail -1 | python -c "
+  python bench.py --exchange-selftest --full --no-api --no-cpu-baseline --no-other-configs --steps 20 --warmup 5 2>/dev/null | tail -1 | python -c "
 import json, sys
 d = json.loads(sys.stdin.read())
 r = d.get('resident_shards') or {}

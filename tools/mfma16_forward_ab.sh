@@ -3,7 +3,7 @@
 # the 32 x 10 s headline, 8 x 60 s, and the small batches the hipcc-scheduled small tiles serve (1 x 10 s, 4 x 10 s).
 # usage: tools/mfma16_forward_ab.sh [reps]   -> one line per run: batch, seconds, option, ms/step, encoder / dominant fractions
 REPS=${1:-2}
-Q="--no-api --no-other-configs --no-exchange-rehearsal --no-cpu-baseline --agreement-clips 0"
+Q="--full --no-api --no-other-configs --no-exchange-rehearsal --no-cpu-baseline --agreement-clips 0"
 for r in $(seq $REPS); do
   for opt in "" "--opt 13=-1"; do
     for shape in "32 10" "8 60" "1 10" "4 10"; do

@@ -25,7 +25,7 @@ def main(src, dst):
             wall[k].append(float(r["End_Timestamp"]) - float(r["Start_Timestamp"]))
     out = ["# Matrix-pipe utilisation per kernel (rocprofv3 PMC, gfx950)", "",
            "`rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_BUSY_CYCLES SQ_INSTS_VALU_MFMA_MOPS_BF16 -- python bench.py "
-           "--steps 3 --warmup 1 --no-cpu-baseline --no-overlap` (own pass, no tracing; tools/collect_profiles.sh).", "",
+           "--full --steps 3 --warmup 1 --no-cpu-baseline --no-overlap` (own pass, no tracing; tools/collect_profiles.sh).", "",
            "MfmaUtil = MFMA_BUSY / (GUI_ACTIVE / 8 XCDs x 1024 SIMDs); effective clock = (GUI_ACTIVE / 8) / dispatch wall time "
            "(profiled passes clock a little lower than un-profiled ones).", "",
            "| kernel | launches | avg wall us | MfmaUtil | effective clock GHz | implied bf16 TFLOP/s |", "|---|---:|---:|---:|---:|---:|"]
