@@ -480,6 +480,51 @@ int sylber_dtw_rerank_occurrences(const float* q_dev, int32_t n_blocks, const fl
                                   const int32_t* seq_offsets_dev, int32_t n_seq, int32_t k, float* cost_dev, int64_t* seq_dev,
                                   int64_t* span_dev, void* workspace_dev, void* stream);
 
+/* Unit search (sylber_amd/units.py: UnitIndex.search_phrases / search_occurrences; csrc/unit_search.hip; restated in
+ * tests/unit_search_ref.py): where is a phrase of syllable UNIT IDS said, by semi-global edit distance (Sellers' approximate
+ * string matching).  The corpus holds tokens only: no embedding is needed.  A unit is a row of W non-negative int32 ids
+ * (1 <= W <= 8: 1 for k-means units, 2 for residual units, Qa + Qp for the learned quantizer).  For phrase unit p_i
+ * (i = 0 .. m-1, 1 <= m <= 64) and sequence unit t_j (j = 0 .. L-1, 1 <= L <= 65536), all in int32:
+ *     sub(i, j) = number of columns c with p_i[c] != t_j[c]   (0 .. W);   an insertion or a deletion costs W
+ *     E[-1][j] = 0,            start[-1][j] = j + 1           (j = -1 .. L-1: the phrase may begin anywhere)
+ *     E[i][-1] = (i + 1) W,    start[i][-1] = 0
+ *     E[i][j]  = min(E[i-1][j-1] + sub(i, j), E[i-1][j] + W, E[i][j-1] + W)
+ *                on equal values the predecessor is taken in that order (diagonal, then (i-1, j), then (i, j-1)), the order of
+ *                sylber_dtw_search; start[i][j] = start of the predecessor taken
+ *   A column j of the last row is admissible when E[m-1][j] <= thr, thr = min(thr_host[p], m W - 1).  An admissible column has a
+ *   path with a diagonal step, so start <= j and its span is never empty.
+ * sylber_unit_search: per (phrase, sequence) cost = min E[m-1][j] over the admissible columns, end = the smallest such j, start =
+ *   start[m-1][end]; a sequence without an admissible column is not returned.  Per phrase the k best sequences by
+ *   (cost, sequence) ascending.
+ * sylber_unit_occurrences: the three steps of "Every occurrence of a phrase" above, word for word, with "admissible" in place of
+ *   "finite": families of admissible columns with equal start (cost = their minimum, end = the smallest such j; starts do not
+ *   decrease with j, so they arrive in order), the one-pass left-to-right rule (on overlap the cheaper family stays pending, the
+ *   pending one on equal cost), per phrase the k best emitted occurrences by (cost, first row).
+ * Both: phrase_units_dev [R, W] holds the phrases' units, phrase p in rows phrase_row_host[p] .. + phrase_len_host[p]; units_dev
+ *   [N, W] the corpus; seq_offsets_host [n_seq + 1] ascends from 0 to N without an empty sequence; seq_id_dev [N] is the sequence of
+ *   every row; phrase_group_host [n_phrases] and seq_group_dev [n_seq] go together (both null: nothing excluded) and exclude the
+ *   sequences of the phrase's own group; splits: 0 = automatic, else the cuts of the corpus asked for (cuts fall on sequence
+ *   starts).  Out: cost_dev [n_phrases, k] int32, seq_dev [n_phrases, k] int64, span_dev [n_phrases, k, 2] int64 (first row, one
+ *   past the last row), padded with (2^31 - 1, -1, (-1, -1)).  Costs are small integers: every result is exact and unique, and
+ *   nothing depends on splits, the chunking of phrases or what the workspace held.  The host arrays are read before the call
+ *   returns; everything else is enqueued on `stream`.  workspace_dev: sylber_unit_workspace_bytes of the same phrase lengths,
+ *   offsets, k and splits (-1 on a bad argument).
+ *   Every argument is checked on the host before any device call: a null pointer, W outside 1..8, k outside 1..128, a phrase of
+ *   fewer than 1 or more than 64 units or outside its R rows, a sequence over 65536 rows, offsets that do not ascend from 0 to N,
+ *   thr < 0, one group array without the other, n_phrases x cuts x k beyond 2^30 return status 1 with sylber_last_error set. */
+int64_t sylber_unit_workspace_bytes(const int32_t* phrase_len_host, int32_t n_phrases, const int32_t* seq_offsets_host, int32_t n_seq,
+                                    int32_t k, int32_t splits);
+int sylber_unit_search(const int32_t* phrase_units_dev, int32_t R, int32_t W, const int32_t* phrase_row_host,
+                       const int32_t* phrase_len_host, const int32_t* thr_host, int32_t n_phrases, const int32_t* units_dev, int32_t N,
+                       const int32_t* seq_offsets_host, int32_t n_seq, const int32_t* seq_id_dev, const int32_t* phrase_group_host,
+                       const int32_t* seq_group_dev, int32_t splits, int32_t k, int32_t* cost_dev, int64_t* seq_dev, int64_t* span_dev,
+                       void* workspace_dev, void* stream);
+int sylber_unit_occurrences(const int32_t* phrase_units_dev, int32_t R, int32_t W, const int32_t* phrase_row_host,
+                            const int32_t* phrase_len_host, const int32_t* thr_host, int32_t n_phrases, const int32_t* units_dev, int32_t N,
+                            const int32_t* seq_offsets_host, int32_t n_seq, const int32_t* seq_id_dev, const int32_t* phrase_group_host,
+                            const int32_t* seq_group_dev, int32_t splits, int32_t k, int32_t* cost_dev, int64_t* seq_dev,
+                            int64_t* span_dev, void* workspace_dev, void* stream);
+
 /* Warping paths (sylber_amd/search.py: SyllableIndex.align_phrases; restated in tests/align_ref.py): HOW a phrase matches a
  * window of rows -- which stored rows each phrase row is warped onto -- where the searches above report only where.  For one pair
  * (phrase of m rows, window [a, b) of row ids, W = b - a):

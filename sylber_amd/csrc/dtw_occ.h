@@ -50,9 +50,9 @@ static __global__ __launch_bounds__(256) void dtw_occ_finish_kernel(const float*
     cost[e] = ls[e]; seq[e] = s; span[2 * e] = p.x; span[2 * e + 1] = (int64_t)p.y + 1;
 }
 
-// the ceil(log2 L) merge rounds of the L lists per phrase in (p.s0, p.i0, p.p0), then the report of the one list left
-static inline int dt_occ_merge_finish(DtOccLists p, int n, int L, int k, const int32_t* seqid, const int32_t* soff, int S, float* cost_dev,
-                                      int64_t* seq_dev, int64_t* span_dev, hipStream_t s) {
+// the ceil(log2 L) merge rounds of the L lists per phrase in (p.s0, p.i0, p.p0); on return those three are the one merged list
+// per phrase [n][k] (unit_search.hip reports it itself: its costs are int32)
+static inline int dt_occ_merge(DtOccLists& p, int n, int L, int k, hipStream_t s) {
     for (int m = L; m > 1; m = (m + 1) / 2) {
         hipLaunchKernelGGL(knn_merge_kernel<true>, dim3((unsigned)n, (unsigned)((m + 1) / 2)), dim3(64), 0, s, p.s0, p.i0, (const int2*)p.p0, m, k,
                            p.s1, p.i1, p.p1);
@@ -61,6 +61,13 @@ static inline int dt_occ_merge_finish(DtOccLists p, int n, int L, int k, const i
         int32_t* ti = p.i0; p.i0 = p.i1; p.i1 = ti;
         int2* tp = p.p0; p.p0 = p.p1; p.p1 = tp;
     }
+    return 0;
+}
+
+// the merge rounds, then the report of the one list left
+static inline int dt_occ_merge_finish(DtOccLists p, int n, int L, int k, const int32_t* seqid, const int32_t* soff, int S, float* cost_dev,
+                                      int64_t* seq_dev, int64_t* span_dev, hipStream_t s) {
+    if (dt_occ_merge(p, n, L, k, s)) return 1;
     const int64_t tot = (int64_t)n * k;
     hipLaunchKernelGGL(dtw_occ_finish_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, p.s0, p.i0, p.p0, tot, seqid, soff, S, cost_dev,
                        seq_dev, span_dev);

@@ -1,0 +1,291 @@
+"""``UnitIndex``: a device-resident corpus of syllable *unit ids* -- what ``SegmentSynthesis.tokenize`` returns -- searched by
+semi-global edit distance (csrc/unit_search.hip; contract in include/sylber_hip.h "Unit search", restated in
+tests/unit_search_ref.py).  The four syllable indexes (search.py, pq.py) need every syllable's embedding; this one needs ``4 W``
+bytes per syllable (``W`` codebooks) and answers "where is this word said?" for a corpus kept as tokens, for a unit language
+model's output and for a lexicon written as unit strings.  The argument rules it shares with the syllable indexes are
+``_index.py``'s."""
+from __future__ import annotations
+
+import ctypes
+from typing import List, Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from . import _lib
+from ._index import (DEFAULT_PHRASE_CHUNK, MAX_PHRASE_ROWS, _check_k_refine, _group_runs, _groups, _provenance, _query_groups,
+                     _sequence_tables, _sequences)
+from .kmeans import _device, _stream, _vp
+
+TILE_COLS = 256                 # US_TILE of csrc/unit_search.hip: the columns a workgroup stages at a time
+MAX_WIDTH = 8                   # US_MAX_W: ids per unit
+FORMAT = "sylber_amd.UnitIndex/1"
+_i32p = ctypes.POINTER(ctypes.c_int32)
+
+
+def _unit_rows(a, width: Optional[int], what: str) -> torch.Tensor:
+    """``[n]`` (one id per unit) or ``[n, W]`` integers, tensor or array on any device -> int64 ``[n, W]`` as given, refusing
+    what is not a row of ``width`` ids (``None``: any width in 1 .. 8) in ``0 .. 2**31 - 1``"""
+    t = a if torch.is_tensor(a) else torch.from_numpy(np.asarray(a))
+    if t.dtype.is_floating_point or t.dtype.is_complex or t.dtype == torch.bool:
+        raise ValueError("%s must be integers, got %s" % (what, t.dtype))
+    if t.dim() == 1:
+        t = t[:, None]
+    if t.dim() != 2:
+        raise ValueError("%s must be [n] or [n, W], got %s" % (what, tuple(t.shape)))
+    W = t.shape[1]
+    if width is None:
+        if not 1 <= W <= MAX_WIDTH:
+            raise ValueError("%s: the width W must be in [1, %d], got %d" % (what, MAX_WIDTH, W))
+    elif W != width:
+        raise ValueError("%s: expected W = %d, got %d" % (what, width, W))
+    if t.numel():
+        lo, hi = int(t.min()), int(t.max())
+        if lo < 0 or hi > 2 ** 31 - 1:
+            raise ValueError("%s: unit ids lie in [0, 2**31 - 1], got %d .. %d" % (what, lo, hi))
+    return t
+
+
+class UnitIndex:
+    """A device-resident corpus of syllable unit strings with exact phrase search by edit distance.
+
+    ``UnitIndex(units=None, *, width=None, groups=None, device="cuda")``.  A *unit* is a row of ``W`` non-negative ids (``W`` =
+    ``width``, ``1 <= W <= 8``: 1 for k-means units, 2 for residual units, ``Qa + Qp`` for the learned quantizer), stored int32:
+    ``4 W`` bytes per syllable.  ``groups`` (one integer per row, e.g. the clip id) cut the corpus into sequences and drive
+    ``exclude_same_group``; rows added without groups get group -1."""
+
+    def __init__(self, units=None, *, width: Optional[int] = None, groups=None, device="cuda"):
+        if width is not None and (isinstance(width, bool) or int(width) != width or not 1 <= int(width) <= MAX_WIDTH):
+            raise ValueError("width must be an integer in [1, %d], got %r" % (MAX_WIDTH, width))
+        self.device = _device(device)
+        self.width: Optional[int] = None if width is None else int(width)
+        self._u = None              # [N, W] int32 on the device
+        self._g = None              # [N] int32 groups on the device
+        self._prov = None           # [N, 4] provenance (clip, segment, start, end)
+        self._span_dtype = np.float64
+        self._seq_cache = None      # (N, default sequence offsets)
+        if units is not None:
+            self.add(units, groups=groups)
+
+    def __len__(self) -> int:
+        return 0 if self._u is None else int(self._u.shape[0])
+
+    @property
+    def units(self) -> torch.Tensor:
+        """the stored ``[N, W]`` int32 ids"""
+        return self._u
+
+    @property
+    def nbytes(self) -> int:
+        """device bytes of the corpus: ``4 W`` per syllable of ids and 4 of group"""
+        return 0 if self._u is None else int(self._u.numel() * 4 + self._g.numel() * 4)
+
+    # ---- building -------------------------------------------------------------------------------------------------------------------
+    def add(self, units, groups=None, *, _prov=None) -> range:
+        """append ``[n]`` or ``[n, W]`` integer ids (tensor or array, host or device) with optional ``groups [n]``; returns their
+        row ids.  ``ValueError`` before anything is stored for an id outside ``0 .. 2**31 - 1`` or another width."""
+        t = _unit_rows(units, self.width, "units")
+        n, start = t.shape[0], len(self)
+        g = _groups(groups, n, "groups") if groups is not None else np.full(n, -1, np.int32)
+        if start + n >= 2 ** 31:
+            raise ValueError("a UnitIndex holds fewer than 2^31 rows")
+        if self.width is None:
+            self.width = int(t.shape[1])
+        if n == 0:
+            return range(start, start)
+        ud = t.to(self.device, torch.int32).contiguous()
+        gd = torch.from_numpy(g).to(self.device)
+        prov = np.full((n, 4), -1.0) if _prov is None else np.asarray(_prov, np.float64).reshape(n, 4)
+        if self._u is None:
+            self._u, self._g, self._prov = ud, gd, prov
+        else:
+            self._u, self._g, self._prov = torch.cat([self._u, ud]), torch.cat([self._g, gd]), np.concatenate([self._prov, prov])
+        return range(start, start + n)
+
+    @classmethod
+    def from_tokens(cls, toks: Sequence[dict], *, device="cuda") -> "UnitIndex":
+        """an index over the list ``SegmentSynthesis.tokenize`` returns: each clip's ``units``, one group per clip (its position in
+        ``toks``), with provenance ``(clip, segment, start frame, end frame)`` from the clip's ``segments``"""
+        idx = cls(device=device)
+        for ci, o in enumerate(toks):
+            u, segs = np.asarray(o["units"]), np.asarray(o["segments"])
+            if u.size == 0:
+                continue
+            if u.ndim == 1:
+                u = u[:, None]
+            if u.ndim != 2 or segs.shape != (u.shape[0], 2):
+                raise ValueError("clip %d: units %s and segments %s do not match" % (ci, u.shape, segs.shape))
+            n = u.shape[0]
+            prov = np.column_stack([np.full(n, ci), np.arange(n), segs[:, 0], segs[:, 1]]).astype(np.float64)
+            idx.add(u, groups=np.full(n, ci, np.int32), _prov=prov)
+            if np.issubdtype(segs.dtype, np.integer):
+                idx._span_dtype = np.int64
+        return idx
+
+    def provenance(self, ids) -> List[Optional[Tuple[int, int, object, object]]]:
+        """``(clip, segment, start, end)`` for each id of a flat sequence or array of row ids (``None`` for -1 and for rows added
+        without provenance); a span ``(a, b)`` of a search covers ``provenance(range(a, b))``"""
+        return _provenance(self._prov, self._span_dtype, len(self), ids)
+
+    def sequence_offsets(self) -> np.ndarray:
+        """int64 ``[S + 1]``: the default sequences of the searches, sequence ``s`` = rows ``offsets[s] : offsets[s + 1]``: the
+        maximal runs of consecutive rows with equal group, numbered in row order (``from_tokens``: one per non-empty clip)"""
+        N = len(self)
+        if self._seq_cache is None or self._seq_cache[0] != N:
+            self._seq_cache = (N, _group_runs(self._g, N))
+        return self._seq_cache[1].copy()
+
+    # ---- search ---------------------------------------------------------------------------------------------------------------------
+    def search_phrases(self, phrases, k: int, *, lengths=None, groups=None, exclude_same_group: bool = False, sequences=None,
+                       max_cost=None, splits: int = 0, phrase_chunk: int = DEFAULT_PHRASE_CHUNK,
+                       _workspace_fill=None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """the k best sequences of the index for each phrase of units, by semi-global edit distance (Sellers' approximate string
+        matching) -> ``(costs int32 [P, k], seqs int64 [P, k], spans int64 [P, k, 2])`` on the device; a span is (first row id, one
+        past the last row id) of the match, so ``provenance`` works on it.  At most one match per sequence: its best one.
+        ``phrases``: a list of ``[m_p]`` / ``[m_p, W]`` integer arrays or tensors, or one packed ``[sum m_p]`` / ``[sum m_p, W]``
+        array with ``lengths=[m_0, m_1, ...]``; ``1 <= m_p <= 64``.
+
+        Sequences, ``groups [P]`` / ``exclude_same_group`` (a sequence's group is its first row's) and ``sequences=`` follow
+        ``SyllableIndex.search_phrases``; a sequence has at most 65 536 rows.
+
+        For phrase unit ``p_i`` and sequence unit ``t_j`` (columns ``0 .. L - 1``), all in int32::
+
+            sub(i, j) = number of columns c with p_i[c] != t_j[c]  (0 .. W);   an insertion or a deletion costs W
+            E[-1][j] = 0,           start[-1][j] = j + 1           (j = -1 .. L - 1: the phrase may begin anywhere)
+            E[i][-1] = (i + 1) W,   start[i][-1] = 0
+            E[i][j]  = min(E[i-1][j-1] + sub(i, j), E[i-1][j] + W, E[i][j-1] + W)
+                       on equal values the predecessor is taken in that order: diagonal, then (i-1, j), then (i, j-1);
+                       start[i][j] = start of the predecessor taken
+
+        A column of the last row is *admissible* when ``E[m-1][j] <= thr``, ``thr = min(max_cost, m W - 1)``; ``max_cost`` is
+        ``None`` (``m W - 1``: anything cheaper than deleting the whole phrase), an int, or ``[P]``; 0 keeps exact matches only.
+        An admissible column has a path with a diagonal step, so its span is never empty.  Per (phrase, sequence):
+        ``cost = min_j E[m-1][j]`` over the admissible columns, ``end`` = the smallest such j, ``start = start[m-1][end]``; a
+        sequence without an admissible column is not returned.  Each phrase's list is ordered by (cost, sequence number)
+        ascending; lists with fewer than k sequences end in cost ``2**31 - 1``, sequence -1, span (-1, -1).
+
+        Costs are small integers, so the result is exact and unique: it does not depend on ``splits`` (0 = automatic: the cuts of
+        the corpus, on sequence starts only), ``phrase_chunk`` (the phrases per launch), stale workspace contents or one ``add``
+        against many.  ``m > L`` is legal.  The scan evaluates every cell; a bit-parallel (Myers) pre-scan that skips sequences
+        without an admissible column is the known next step."""
+        return self._search("sylber_unit_search", phrases, k, lengths, groups, exclude_same_group, sequences, max_cost, splits,
+                            phrase_chunk, _workspace_fill)
+
+    def search_occurrences(self, phrases, k: int, *, lengths=None, groups=None, exclude_same_group: bool = False, sequences=None,
+                           max_cost=None, splits: int = 0, phrase_chunk: int = DEFAULT_PHRASE_CHUNK,
+                           _workspace_fill=None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """every non-overlapping occurrence of each phrase, not one match per sequence: the k best occurrences over the whole
+        index, shaped and padded as ``search_phrases``'s; a keyword said five times in one recording comes back five times with
+        one sequence number.  Arguments, the recurrence, the order on ties, ``start`` and "admissible" are ``search_phrases``'s;
+        the three steps are ``SyllableIndex.search_occurrences``' word for word, with "admissible" in place of "finite":
+
+        1. Families: admissible columns of the last row with equal ``start``; ``cost`` = their minimum, ``end`` = the smallest
+           such j.  Starts do not decrease with j, so families arrive in order.
+        2. One left-to-right pass: the first family becomes pending; a later family that shares a row with the pending one
+           competes with it (the cheaper stays, the pending one on equal cost), otherwise the pending one is emitted and the
+           later one becomes pending; at the sequence end the pending family is emitted.
+        3. Per phrase the k best emitted occurrences by (cost, first row id of the span).
+
+        The best occurrence of a sequence under (cost, start) is ``search_phrases``' (cost, span) of that pair.  Not global
+        greedy suppression: of a chain A - B - C with A and C disjoint, both overlapping B, and costs A > B > C only C is
+        emitted."""
+        return self._search("sylber_unit_occurrences", phrases, k, lengths, groups, exclude_same_group, sequences, max_cost, splits,
+                            phrase_chunk, _workspace_fill)
+
+    def _phrases(self, phrases, lengths) -> Tuple[torch.Tensor, np.ndarray]:
+        """``(the phrases' units int64 [sum m, W] as given, lengths int64 [P])`` or ``ValueError``"""
+        W = self.width
+        if lengths is None:
+            if torch.is_tensor(phrases) or isinstance(phrases, np.ndarray):
+                raise ValueError("phrases given as one packed array need lengths=")
+            parts = [_unit_rows(p, W, "phrases[%d]" % i) for i, p in enumerate(phrases)]
+            lens = np.array([p.shape[0] for p in parts], np.int64)
+            q = torch.cat([p.to(self.device, torch.int64) for p in parts]) if parts else torch.zeros((0, W), dtype=torch.int64)
+        else:
+            q = _unit_rows(phrases, W, "phrases")
+            lens = np.asarray(lengths.detach().cpu().numpy() if torch.is_tensor(lengths) else lengths)
+            if lens.ndim != 1 or (lens.size and lens.dtype.kind not in "iu"):
+                raise ValueError("lengths must be a 1-D sequence of integers")
+            lens = lens.astype(np.int64)
+            if int(lens.sum()) != q.shape[0]:
+                raise ValueError("lengths sum to %d, phrases has %d units" % (int(lens.sum()), q.shape[0]))
+        if lens.size and (lens.min() < 1 or lens.max() > MAX_PHRASE_ROWS):
+            raise ValueError("a phrase has between 1 and %d units, got lengths from %d to %d" % (MAX_PHRASE_ROWS, lens.min(), lens.max()))
+        return q, lens
+
+    def _thresholds(self, max_cost, lens: np.ndarray) -> np.ndarray:
+        """int32 ``[P]``: ``min(max_cost, m W - 1)``"""
+        cap = lens * self.width - 1
+        if max_cost is None:
+            return cap.astype(np.int32)
+        a = np.asarray(max_cost.detach().cpu().numpy() if torch.is_tensor(max_cost) else max_cost)
+        if a.dtype.kind not in "iu" or a.shape not in ((), (lens.size,)):
+            raise ValueError("max_cost must be None, an integer or %d integers, got %r" % (lens.size, max_cost))
+        a = np.broadcast_to(a.astype(np.int64), (lens.size,))
+        if a.size and a.min() < 0:
+            raise ValueError("max_cost must be >= 0, got %d" % a.min())
+        return np.minimum(a, cap).astype(np.int32)
+
+    def _search(self, entry: str, phrases, k, lengths, groups, exclude_same_group, sequences, max_cost, splits, phrase_chunk, fill):
+        k, _ = _check_k_refine(k)
+        N, dev = len(self), self.device
+        if N == 0:
+            raise ValueError("the index is empty")
+        q, lens = self._phrases(phrases, lengths)
+        P = int(lens.size)
+        pg = _query_groups(groups, P, exclude_same_group, None, "phrases")
+        if int(splits) < 0 or int(phrase_chunk) < 1:
+            raise ValueError("splits must be >= 0 and phrase_chunk >= 1")
+        thr = self._thresholds(max_cost, lens)
+        off = _sequences(sequences, N, self.sequence_offsets)
+        costs = torch.empty((P, k), dtype=torch.int32, device=dev)
+        seqs = torch.empty((P, k), dtype=torch.int64, device=dev)
+        spans = torch.empty((P, k, 2), dtype=torch.int64, device=dev)
+        if P == 0:
+            return costs, seqs, spans
+        lib = _lib.load()
+        qd = q.to(dev, torch.int32).contiguous()
+        seq_id, seq_grp = _sequence_tables(off, self._g if pg is not None else None, dev)
+        off32, S = np.ascontiguousarray(off, np.int32), off.size - 1
+        rows = np.ascontiguousarray(np.cumsum(lens) - lens, np.int32)
+        ln = np.ascontiguousarray(lens, np.int32)
+        offp = off32.ctypes.data_as(_i32p)
+        with torch.cuda.device(dev):
+            st = _stream(dev)
+            for p0 in range(0, P, int(phrase_chunk)):
+                p1 = min(P, p0 + int(phrase_chunk))
+                lp, rp, tp = (np.ascontiguousarray(a[p0:p1]) for a in (ln, rows, thr))
+                gp = np.ascontiguousarray(pg[p0:p1], np.int32) if pg is not None else None
+                need = int(lib.sylber_unit_workspace_bytes(lp.ctypes.data_as(_i32p), p1 - p0, offp, S, k, int(splits)))
+                if need < 0:
+                    raise _lib.SylberHipError("sylber_unit_workspace_bytes refused the call")
+                ws = torch.empty(need, dtype=torch.uint8, device=dev)
+                if fill is not None:
+                    ws.fill_(fill)
+                _lib.check(getattr(lib, entry)(_vp(qd), qd.shape[0], self.width, rp.ctypes.data_as(_i32p), lp.ctypes.data_as(_i32p),
+                                               tp.ctypes.data_as(_i32p), p1 - p0, _vp(self._u), N, offp, S, _vp(seq_id),
+                                               gp.ctypes.data_as(_i32p) if gp is not None else None, _vp(seq_grp), int(splits), k,
+                                               _vp(costs[p0:p1]), _vp(seqs[p0:p1]), _vp(spans[p0:p1]), _vp(ws), st), entry)
+        return costs, seqs, spans
+
+    # ---- persistence ----------------------------------------------------------------------------------------------------------------
+    def save(self, path: str) -> None:
+        """``.npz`` with the units, groups, provenance and a format tag; a round trip gives the same results bit for bit"""
+        N, W = len(self), self.width or 1
+        np.savez(path, format=np.array(FORMAT), width=np.array(-1 if self.width is None else self.width),
+                 units=(self._u.cpu().numpy() if N else np.zeros((0, W), np.int32)),
+                 groups=(self._g.cpu().numpy() if N else np.zeros(0, np.int32)), provenance=(self._prov if N else np.zeros((0, 4))),
+                 span_int=np.array(self._span_dtype is np.int64))
+
+    @classmethod
+    def load(cls, path: str, device="cuda") -> "UnitIndex":
+        z = np.load(path, allow_pickle=False)
+        if "format" not in z.files or str(z["format"]) != FORMAT:
+            raise ValueError("%s is not a saved UnitIndex (%s)" % (path, FORMAT))
+        W = int(z["width"])
+        idx = cls(width=None if W < 0 else W, device=device)
+        if z["units"].shape[0]:
+            idx.add(z["units"], groups=z["groups"], _prov=z["provenance"])
+        if bool(z["span_int"]):
+            idx._span_dtype = np.int64
+        return idx
