@@ -525,6 +525,55 @@ int sylber_unit_occurrences(const int32_t* phrase_units_dev, int32_t R, int32_t 
                             const int32_t* seq_group_dev, int32_t splits, int32_t k, int32_t* cost_dev, int64_t* seq_dev,
                             int64_t* span_dev, void* workspace_dev, void* stream);
 
+/* Edit scripts (sylber_amd/units.py: UnitIndex.align_phrases; csrc/unit_align.hip; restated in tests/unit_align_ref.py): HOW a
+ * phrase of units matches a window of rows -- which stored row each phrase unit is paired with and what was substituted, deleted
+ * and inserted -- where the unit searches above report only where.  For one pair (phrase of m units, window [a, b) of row ids,
+ * L = b - a columns):
+ *   Window DP.  sub(i, j), the recurrence, the predecessor order on ties (diagonal, then (i-1, j), then (i, j-1): the first
+ *   smallest) and the int32 arithmetic are unit search's.  The window is taken as ONE sequence whose column 0 is row a, even if it
+ *   crosses a sequence boundary of the index.  The boundary column is E[i][-1] = (i + 1) W.  The boundary row depends on free_start:
+ *     free_start = 1: E[-1][j] = 0: the phrase may begin anywhere in the window; this is the searches' DP.
+ *     free_start = 0 (global): E[-1][j] = (j + 1) W with predecessor "left": the whole window is consumed, so cost is the weighted
+ *       Levenshtein distance of phrase and window.
+ *   The end is forced: the path ends in cell (m-1, L-1).
+ *   Path.  The chain of predecessors taken from (m-1, L-1) back to the boundary.  Under free_start = 1 it stops at row -1 in some
+ *   column j (the first row of the path is a + j + 1) or at column -1 in some row i (phrase units 0 .. i are deletions, the first
+ *   row is a).  Under free_start = 0 it runs on along row -1 to the corner: those steps are leading insertions and the first row is a.
+ *   Outputs.  cols[i] = the row id that phrase unit i is paired with by a diagonal step, -1 if unit i is deleted or i >= m;
+ *   subs[i] = sub(i, j) of that pairing (0 .. W), W for a deleted unit, -1 for i >= m; ops = (equal, substituted, deleted,
+ *   inserted): diagonal steps with sub = 0, diagonal steps with sub > 0, phrase units without a row, rows of the path without a
+ *   phrase unit; cost = E[m-1][L-1].  By construction equal + substituted + deleted = m, the first row of the path =
+ *   b - (equal + substituted + inserted), cost = sum(subs[:m]) + W * inserted, and the sum of ops is the number of edit operations,
+ *   the divisor of a length-normalised cost.  Every legal window has a finite cost.
+ *   The theorem.  If [a, b) is a span that sylber_unit_search or sylber_unit_occurrences returned for that phrase on those rows,
+ *   then in either mode (1) the path's first row is a, (2) cost is the reported cost, (3) the path is the scan's own path.  Why, as
+ *   for "Warping paths" below and simpler in int32: a window cell is a minimum over fewer paths, so it is never below the full
+ *   DP's cell; the window boundary (i + 1) W is what a run of deletions from row -1 costs in the full DP; on the scan's path the
+ *   two DPs are equal; a predecessor that lost in the full DP was strictly larger there and still is, so the same one wins.
+ *   tests/test_unit_align_ref.py holds it on more than 20 000 returned spans.  So no scan had to keep its path.
+ *   Any other window is legal and gets what the definition gives; under free_start = 1 its path may begin inside the window.
+ *   Nothing returned depends on how pairs are chunked or on what the workspace held.
+ * sylber_unit_align: phrase_units_dev [R, W] and units_dev [N, W] as for sylber_unit_search; phrase_row_dev, phrase_len_dev
+ *   [n_phrases] int32 on the DEVICE: phrase p is rows phrase_row[p] .. + phrase_len[p].  pair_phrase_dev [n_pairs] int32: the
+ *   phrase of each pair; pair_window_dev [n_pairs, 2] int32: (a, b), (-1, -1) = none; max_cols: no window is longer (1 .. 65 536);
+ *   max_rows: the pitch Mx of cols_dev and subs_dev, at least the longest phrase (1 .. 64); free_start: 0 or 1.  Out: cols_dev,
+ *   subs_dev [n_pairs, max_rows] int32, ops_dev [n_pairs, 4] int32, cost_dev [n_pairs] int32; start_dev [n_pairs] int32, may be
+ *   null: the first row as the forward walk itself tracked it through the cells, as the scans track theirs (free_start = 0: a) --
+ *   always b - (equal + substituted + inserted); a check of the codes, not a result.  workspace_dev:
+ *   sylber_unit_align_workspace_bytes(n_pairs, max_cols) = 16 B per column of max_cols + 63 steps, rounded up to chunks of 32, per
+ *   pair (-1 on a bad argument): 2 bits per cell for the predecessor taken.
+ *   A null pointer other than start_dev, W outside 1..8, R, N, n_phrases or n_pairs below 1, max_cols outside 1..65 536, max_rows
+ *   outside 1..64 and free_start outside {0, 1} return 1 with sylber_last_error before any device call.  The windows and the
+ *   phrase tables are device data that the entry cannot see: the caller validates them (align_phrases does, with one reduction,
+ *   before any launch), and a pair whose phrase number lies outside [0, n_phrases), whose phrase has fewer than 1 or more than
+ *   min(64, max_rows) units or rows outside R, or whose window lies outside [0, N], is empty or is longer than max_cols is padding
+ *   on output -- cols and subs -1, ops 0, cost 2^31 - 1, start -1 -- having read and written nothing but that. */
+int64_t sylber_unit_align_workspace_bytes(int32_t n_pairs, int32_t max_cols);
+int sylber_unit_align(const int32_t* phrase_units_dev, int32_t R, int32_t W, const int32_t* phrase_row_dev, const int32_t* phrase_len_dev,
+                      int32_t n_phrases, const int32_t* units_dev, int32_t N, const int32_t* pair_phrase_dev, const int32_t* pair_window_dev,
+                      int32_t n_pairs, int32_t max_cols, int32_t max_rows, int32_t free_start, int32_t* cols_dev, int32_t* subs_dev,
+                      int32_t* ops_dev, int32_t* cost_dev, int32_t* start_dev /* nullable */, void* workspace_dev, void* stream);
+
 /* Warping paths (sylber_amd/search.py: SyllableIndex.align_phrases; restated in tests/align_ref.py): HOW a phrase matches a
  * window of rows -- which stored rows each phrase row is warped onto -- where the searches above report only where.  For one pair
  * (phrase of m rows, window [a, b) of row ids, W = b - a):

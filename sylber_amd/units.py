@@ -2,8 +2,11 @@
 semi-global edit distance (csrc/unit_search.hip; contract in include/sylber_hip.h "Unit search", restated in
 tests/unit_search_ref.py).  The four syllable indexes (search.py, pq.py) need every syllable's embedding; this one needs ``4 W``
 bytes per syllable (``W`` codebooks) and answers "where is this word said?" for a corpus kept as tokens, for a unit language
-model's output and for a lexicon written as unit strings.  The argument rules it shares with the syllable indexes are
-``_index.py``'s."""
+model's output and for a lexicon written as unit strings.  ``align_phrases`` takes the spans of either search, or any windows,
+and returns the edit script of each match: the stored row every phrase unit is paired with and the equal / substituted / deleted /
+inserted counts (csrc/unit_align.hip, "Edit scripts", tests/unit_align_ref.py); in global mode that is the weighted Levenshtein
+distance of two unit strings.  The argument rules it shares with the syllable indexes are ``_index.py``'s, the span checks of
+``align_phrases`` are search.py's."""
 from __future__ import annotations
 
 import ctypes
@@ -16,8 +19,10 @@ from . import _lib
 from ._index import (DEFAULT_PHRASE_CHUNK, MAX_PHRASE_ROWS, _check_k_refine, _group_runs, _groups, _provenance, _query_groups,
                      _sequence_tables, _sequences)
 from .kmeans import _device, _stream, _vp
+from .search import ALIGN_WORKSPACE_BYTES, _align_spans       # the span checks and the workspace bound of every align_phrases
 
 TILE_COLS = 256                 # US_TILE of csrc/unit_search.hip: the columns a workgroup stages at a time
+ALIGN_CHUNK_COLS = 32           # UA_CH of csrc/unit_align.hip: the anti-diagonal steps whose 2-bit codes fill one 64-bit word
 MAX_WIDTH = 8                   # US_MAX_W: ids per unit
 FORMAT = "sylber_amd.UnitIndex/1"
 _i32p = ctypes.POINTER(ctypes.c_int32)
@@ -267,6 +272,83 @@ class UnitIndex:
                                                gp.ctypes.data_as(_i32p) if gp is not None else None, _vp(seq_grp), int(splits), k,
                                                _vp(costs[p0:p1]), _vp(seqs[p0:p1]), _vp(spans[p0:p1]), _vp(ws), st), entry)
         return costs, seqs, spans
+
+    # ---- edit scripts ---------------------------------------------------------------------------------------------------------------
+    def align_phrases(self, phrases, spans, *, lengths=None, free_start: bool = True, pair_chunk: Optional[int] = None,
+                      _workspace_fill=None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+        """*how* each phrase matches each of its spans: the edit script -> ``(cols int64 [P, k, Mx], subs int32 [P, k, Mx],
+        ops int32 [P, k, 4], costs int32 [P, k])`` on the device, ``Mx = max_p m_p`` (csrc/unit_align.hip, ``sylber_unit_align``;
+        contract in include/sylber_hip.h "Edit scripts", restated in tests/unit_align_ref.py).  ``phrases`` and ``lengths=`` are
+        exactly as the search took them; ``spans`` int64 ``[P, k, 2]`` (host or device): (first row id, one past the last),
+        ``(-1, -1)`` = padding -- the spans of ``search_phrases`` or ``search_occurrences``, or any windows of your own.
+
+        ``cols[p, r, i]``: the row id that phrase unit i is paired with by a diagonal step, so ``provenance`` works on it; -1 if
+        the unit is deleted or ``i >= m_p``.  ``subs``: ``sub(i, j)`` of that pairing (0 .. W), W for a deleted unit, -1 for
+        ``i >= m_p``.  ``ops``: (equal, substituted, deleted, inserted) = diagonal steps with ``sub = 0``, diagonal steps with
+        ``sub > 0``, phrase units without a row, rows of the path without a phrase unit.  ``costs``: ``E[m-1][L-1]``.  A padding
+        span gives ``cols`` and ``subs`` -1, ``ops`` 0 and cost ``2**31 - 1``; every legal window has a finite cost.
+
+        Window DP, for one pair (phrase of m units, window ``[a, b)``, ``L = b - a``): ``sub``, the recurrence, the predecessor
+        order on ties and the int32 arithmetic are ``search_phrases``'s; the window is taken as **one** sequence whose column 0 is
+        row ``a``, even across a sequence boundary of the index; ``E[i][-1] = (i + 1) W``; the end is forced: the path ends in
+        cell ``(m-1, L-1)``.  ``free_start=True``: ``E[-1][j] = 0``, the searches' DP -- the phrase may begin anywhere in the
+        window.  ``free_start=False`` (global): ``E[-1][j] = (j + 1) W`` with predecessor "left", so the whole window is consumed
+        and ``costs`` is the weighted Levenshtein distance of phrase and window: with ``ops`` the unit error rate between two
+        tokenisations.  The path is the chain of predecessors from ``(m-1, L-1)`` back to the boundary: to row -1 in column j
+        (first row ``a + j + 1``; global: on to the corner, leading insertions, first row ``a``) or to column -1 in row i
+        (units ``0 .. i`` are deletions, first row ``a``).
+
+        By construction ``equal + substituted + deleted = m``, the path's first row is ``b - (equal + substituted + inserted)``,
+        ``costs = subs[:m].sum() + W * inserted``, and ``ops.sum(-1)`` is the number of edit operations: ``costs / ops.sum(-1)``
+        is the length-normalised cost.
+
+        The theorem: if ``[a, b)`` is a span a search of this index returned for that phrase, then in either mode the path's
+        first row is ``a``, ``costs`` is the reported cost and the path is the scan's own path (a window cell is a minimum over
+        fewer paths, so never below the full DP's; the boundary ``(i + 1) W`` is what deletions from row -1 cost there; on the
+        scan's path the two are equal, and a predecessor that lost in the full DP was strictly larger and still is).  Any other
+        window is legal and gets what the definition gives.
+
+        Nothing returned depends on ``pair_chunk`` (the pairs per launch; by default the workspace, 16 B per window column and
+        pair, stays below 256 MiB), on stale workspace contents, on one ``add`` against many or on a ``save`` / ``load`` round
+        trip.  ``ValueError`` before any launch: what ``search_phrases`` refuses of the phrases; ``spans`` of another shape or
+        dtype; a span that is neither ``(-1, -1)`` nor ``0 <= a < b <= N`` (one reduction on the device); a window of more than
+        65 536 rows; ``pair_chunk < 1``; an empty index."""
+        N, dev = len(self), self.device
+        if N == 0:
+            raise ValueError("the index is empty")
+        q, lens = self._phrases(phrases, lengths)
+        if pair_chunk is not None and (isinstance(pair_chunk, bool) or int(pair_chunk) != pair_chunk or int(pair_chunk) < 1):
+            raise ValueError("pair_chunk must be an integer >= 1, got %r" % (pair_chunk,))
+        P = int(lens.size)
+        sp, widest = _align_spans(spans, P, N, dev)
+        k, Mx = int(sp.shape[1]), (int(lens.max()) if P else 0)
+        n = P * k
+        cols = torch.full((n, Mx), -1, dtype=torch.int32, device=dev)
+        subs = torch.full((n, Mx), -1, dtype=torch.int32, device=dev)
+        ops = torch.zeros((n, 4), dtype=torch.int32, device=dev)
+        costs = torch.full((n,), 2 ** 31 - 1, dtype=torch.int32, device=dev)
+        if n and widest:                                    # else: nothing but padding, and no launch
+            lib = _lib.load()
+            qd = q.to(dev, torch.int32).contiguous()
+            row_d = torch.from_numpy(np.ascontiguousarray(np.cumsum(lens) - lens, np.int32)).to(dev)
+            len_d = torch.from_numpy(np.ascontiguousarray(lens, np.int32)).to(dev)
+            pair_phrase = torch.arange(P, dtype=torch.int32, device=dev).repeat_interleave(k)
+            win = sp.reshape(n, 2).to(torch.int32)
+            step = int(pair_chunk) if pair_chunk is not None else \
+                max(1, ALIGN_WORKSPACE_BYTES // int(lib.sylber_unit_align_workspace_bytes(1, widest)))
+            step = min(step, n)
+            with torch.cuda.device(dev):
+                st = _stream(dev)
+                ws = torch.empty(int(lib.sylber_unit_align_workspace_bytes(step, widest)), dtype=torch.uint8, device=dev)
+                if _workspace_fill is not None:
+                    ws.fill_(_workspace_fill)
+                for r0 in range(0, n, step):
+                    r1 = min(n, r0 + step)
+                    _lib.check(lib.sylber_unit_align(_vp(qd), qd.shape[0], self.width, _vp(row_d), _vp(len_d), P, _vp(self._u), N,
+                                                     _vp(pair_phrase[r0:r1]), _vp(win[r0:r1]), r1 - r0, widest, Mx, 1 if free_start else 0,
+                                                     _vp(cols[r0:r1]), _vp(subs[r0:r1]), _vp(ops[r0:r1]), _vp(costs[r0:r1]), None,
+                                                     _vp(ws), st), "sylber_unit_align")
+        return cols.to(torch.int64).reshape(P, k, Mx), subs.reshape(P, k, Mx), ops.reshape(P, k, 4), costs.reshape(P, k)
 
     # ---- persistence ----------------------------------------------------------------------------------------------------------------
     def save(self, path: str) -> None:

@@ -9,7 +9,11 @@ and DP cells per second, ``P m N / t``.
 Yardstick, in the same process on the same box: ``PQSyllableIndex.search_phrases`` after ``drop_rows()`` (M = 48 codes of D = 768
 gaussian rows, ``rerank=False``, refine 4, fp16) at the same N, P and m -- the cheapest phrase search the embedding indexes offer.
 The two answer different questions (edit distance over tokens against DTW over embeddings), so the ratio is context, not a gate.
-``--no-yardstick`` leaves it out."""
+``--no-yardstick`` leaves it out.
+
+``--align`` measures something else and writes profiles/unit_align_bench.md instead: on the same corpus and shapes it times
+``UnitIndex.search_phrases`` and, beside it in the same run, ``UnitIndex.align_phrases`` (csrc/unit_align.hip) on the spans that this
+search returned -- P k pairs of a phrase and a window of at most 2 m rows -- under the same timing rule.  No yardstick is run."""
 import argparse
 import os
 import statistics
@@ -56,8 +60,13 @@ def main():
     ap.add_argument("--alphabet", type=int, default=10000)
     ap.add_argument("--widths", default="1,2")
     ap.add_argument("--no-yardstick", action="store_true")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "unit_search_bench.md"))
+    ap.add_argument("--align", action="store_true", help="time align_phrases on the spans of search_phrases; writes unit_align_bench.md")
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "unit_align_bench.md" if args.align else "unit_search_bench.md")
+    if args.align:
+        return align_main(args)
     from sylber_amd import PQSyllableIndex, SyllableIndex, UnitIndex
     dev = torch.device("cuda:0")
     torch.cuda.set_device(dev)
@@ -119,6 +128,50 @@ def main():
         del idx
     lines += ["", "Device bytes (`nbytes`, ids and groups): " + ", ".join("%.1f MB at W = %d" % (b / 1e6, W) for W, b in nbytes.items()) +
               ("; the yardstick's `PQSyllableIndex` after `drop_rows()`: %.1f MB." % (yard_bytes / 1e6) if yard else "."), ""]
+    with open(args.out, "w") as f:
+        f.write("\n".join(lines))
+    print("\n".join(lines))
+
+
+def align_main(args):
+    from sylber_amd import UnitIndex
+    dev = torch.device("cuda:0")
+    torch.cuda.set_device(dev)
+    rng = np.random.default_rng(0)
+    N, k, A = args.N, args.k, args.alphabet
+    lens = sequence_lengths(N, rng)
+    groups = np.repeat(np.arange(lens.size), lens).astype(np.int32)
+    lines = ["# Edit scripts beside the search that found them: one MI355X, one run", "",
+             "`python tools/unit_search_bench.py --align --iters %d`: the corpus, phrases and timing rule of profiles/unit_search_bench.md "
+             "(N = %s units in %s sequences of 20 to 60, k = %d, ids uniform over %s symbols per column; one warm-up call, then the median of "
+             "%d whole calls with their min .. max).  `align_phrases` is given the spans that the `search_phrases` call timed beside it "
+             "returned: `pairs` of them are not padding, and a window has at most 2 m rows.  `ratio` = `align_phrases` time / "
+             "`search_phrases` time." %
+             (args.iters, "{:,}".format(N).replace(",", " "), "{:,}".format(lens.size).replace(",", " "), k, "{:,}".format(A).replace(",", " "),
+              args.iters), "",
+             "| W | phrases P | units m | pairs | widest window | search_phrases ms (min .. max) | align_phrases ms (min .. max) | "
+             "align_phrases global ms (min .. max) | ratio |",
+             "|---:|---:|---:|---:|---:|---:|---:|---:|---:|"]
+    for W in [int(v) for v in args.widths.split(",")]:
+        corpus = torch.from_numpy(rng.integers(0, A, (N, W)).astype(np.int32))
+        idx = UnitIndex(corpus, groups=groups, device=dev)
+        idx.sequence_offsets()
+        for P, m in SHAPES:
+            at = rng.integers(0, N - m, P)
+            ph = torch.stack([corpus[a:a + m] for a in at]).reshape(P * m, W).clone()
+            swap = torch.from_numpy(rng.random(P * m) < 0.25)
+            ph[swap] = torch.from_numpy(rng.integers(0, A, (int(swap.sum()), W)).astype(np.int32))
+            ph, ln = ph.to(dev), [m] * P
+            tp = timed(lambda: idx.search_phrases(ph, k, lengths=ln), args.iters)
+            spans = idx.search_phrases(ph, k, lengths=ln)[2]
+            ta = timed(lambda: idx.align_phrases(ph, spans, lengths=ln), args.iters)
+            tg = timed(lambda: idx.align_phrases(ph, spans, lengths=ln, free_start=False), args.iters)
+            pairs, widest = int((spans[..., 0] >= 0).sum()), int((spans[..., 1] - spans[..., 0]).max())
+            row = "| %d | %d | %d | %d | %d | %s | %s | %s | %.3f |" % (W, P, m, pairs, widest, fmt(tp), fmt(ta), fmt(tg), ta[0] / tp[0])
+            print(row, file=sys.stderr, flush=True)
+            lines.append(row)
+        del idx
+    lines.append("")
     with open(args.out, "w") as f:
         f.write("\n".join(lines))
     print("\n".join(lines))
