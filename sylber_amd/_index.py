@@ -301,7 +301,7 @@ def _phrase_blocks(lib, dev, qd, lens, p0: int, p1: int, off, list_size: int, sp
 
 class _PhraseChunk:
     """what ``_scan_phrases`` hands to the stages of a search.  For the whole call: ``lib, dev, st`` (the stream), ``N, dim, metric``
-    (its code), ``k``, ``m`` (entries per list in stage 1: ``k``, or ``k * refine``), ``off, off_d`` (``off_d``: two-stage only),
+    (its code), ``k``, ``m`` (entries per list in stage 1: ``k``, or ``k * refine``), ``off_d`` (two-stage only),
     ``S, seq_id, seq_grp``.  For the chunk: ``b`` (its ``_PhraseBlocks``), ``meta_d, sp_d, br_d, cut_d, pg_d`` (``b.tables()``) and
     the chunk's slices ``costs, seqs, spans``; two-stage searches also get ``place_d, len_d, qn`` (the ``||q||^2`` that
     ``sylber_dtw_search`` adds, same kernel; ``None`` under "cosine"), ``q16`` (the packed rows in 16 bits), ``cand, coarse`` and
@@ -310,12 +310,6 @@ class _PhraseChunk:
     def __init__(self, fill, **whole_call):
         self._fill = fill
         self.__dict__.update(whole_call)
-
-    def part(self, **changed) -> "_PhraseChunk":
-        """a copy with these attributes replaced: some of the chunk's phrases, or other rows to re-rank on"""
-        c = _PhraseChunk(self._fill, **self.__dict__)
-        c.__dict__.update(changed)
-        return c
 
     def workspace(self, nbytes) -> torch.Tensor:
         """``nbytes`` of workspace; a test's ``_workspace_fill`` reaches every workspace of the call through here"""
@@ -334,7 +328,7 @@ def _scan_phrases(N: int, dim: int, dev, metric: str, db_groups, default_sequenc
     with ``m = k * refine`` candidates.  ``stages()`` is called once, behind every check and before anything is launched (it may
     still refuse, e.g. values that fp16 cannot hold) -> ``(scan, rerank)``: ``scan(c)`` launches stage 1 of the chunk ``c`` (a
     ``_PhraseChunk``) -- into ``c.costs, c.seqs, c.spans`` when it is the only stage, else into ``c.cand, c.coarse`` -- and
-    ``rerank(c)`` (``None`` with one stage) stage 2, inside the loop: it may read the chunk's ``cand`` on the host."""
+    ``rerank(c)`` (``None`` with one stage) stage 2, inside the loop."""
     two = refine is not None
     k, m = _check_k_refine(k, refine, rerank=True) if two else _check_k_refine(k)
     if two and storage not in STORAGES:
@@ -350,7 +344,7 @@ def _scan_phrases(N: int, dim: int, dev, metric: str, db_groups, default_sequenc
         lib = _lib.load()
         qd = _prep(q, metric, dev)
         seq_id, seq_grp = _sequence_tables(off, db_groups if pg is not None else None, dev)
-        c = _PhraseChunk(workspace_fill, lib=lib, dev=dev, N=N, dim=dim, metric=METRICS[metric], k=k, m=m, off=off, S=off.size - 1,
+        c = _PhraseChunk(workspace_fill, lib=lib, dev=dev, N=N, dim=dim, metric=METRICS[metric], k=k, m=m, S=off.size - 1,
                          off_d=_on_device(off, np.int32, dev) if two else None, seq_id=seq_id, seq_grp=seq_grp)
         with torch.cuda.device(dev):
             c.st = _stream(dev)

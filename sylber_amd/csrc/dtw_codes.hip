@@ -1,5 +1,5 @@
-// The exact DTW on a coded database (sylber_amd/pq.py: IVFPQSyllableIndex.search_phrases / search_occurrences / align_phrases and
-// PQSyllableIndex.search_occurrences with rerank=False; contract in include/sylber_hip.h, restated in tests/ivfpq_phrase_ref.py and
+// The exact DTW on a coded database (sylber_amd/pq.py: search_phrases / search_occurrences / align_phrases of IVFPQSyllableIndex and of
+// PQSyllableIndex with rerank=False; contract in include/sylber_hip.h, restated in tests/ivfpq_phrase_ref.py and
 // tests/occ_ref.py): sylber_dtw_rerank, sylber_dtw_rerank_occurrences and sylber_dtw_align on rows that exist only as
 // product-quantization codes, in list order, possibly as residuals to a list centroid.  No row is written anywhere: each float4 of
 // the dot-product chain is rebuilt from a code byte and the fp32 codebooks (plus the list centroid) where the chain consumes it.

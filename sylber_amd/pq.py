@@ -27,7 +27,10 @@ each row's residual to its list's centroid (``sylber_ivfpq_scan_residual``; test
 run on the codes themselves (csrc/dtw_codes.hip; tests/ivfpq_phrase_ref.py).
 
 The two classes differ in where the codes lie and which scan reads them; what they share is written once: the rules of every index in
-_index.py, and here ``_pq_search`` (the search body), ``_decode`` / ``_check_ids`` and ``_saved_codes`` / ``_saved_rows`` (the file)."""
+_index.py, and here ``_pq_search`` (the search body), ``_decode`` / ``_check_ids``, ``_saved_codes`` / ``_saved_rows`` (the file) and
+the ``rerank=False`` phrase paths (``_check_rerank``, ``_rerank_codes_launch``, ``_align_codes``): with ``rerank=False`` both classes run
+the exact DTW of ``search_phrases``, ``search_occurrences`` and ``align_phrases`` on the codes themselves (csrc/dtw_codes.hip) and
+differ there by their ``_coded_db()`` alone."""
 from __future__ import annotations
 
 from typing import List, Optional, Tuple
@@ -40,14 +43,13 @@ from ._index import (DEFAULT_PHRASE_CHUNK, DEFAULT_QUERY_CHUNK, MAX_SEEDS, METRI
                      _check_nprobe, _check_splits_chunk, _chunked_workspace_bytes, _group_runs, _list_layout, _on_device, _outputs, _pack16,
                      _phrase_args, _prep, _provenance, _query_groups, _result, _row_norms, _rows, _rows_of_width, _scan_phrases)
 from .kmeans import _device, _stream, _vp
-from .search import IVFSyllableIndex, SyllableIndex, _align_launch, _align_phrases, _occ_rerank_launch, _rerank_launch, _seeded_phrases
+from .search import IVFSyllableIndex, SyllableIndex, _align_phrases, _occ_rerank_launch, _rerank_launch, _seeded_phrases
 
 KSUB = 256                      # centroids per sub-space: one uint8 per code
 MAX_M = 64                      # PQ_MAX_M of csrc/pq.hip: at least two queries' tables (M KiB each) fit beside the top lists in LDS
 ENCODE_CHUNK = 1 << 20          # rows per encode launch
 RESIDUAL_CHUNK = 1 << 18        # rows whose fp32 residuals exist at a time while residual codes are made
 NORM_CHUNK = 1 << 16            # rows decoded at a time while the ||decode(code)||^2 of search_phrases are made
-DEFAULT_SCRATCH_ROWS = 262144   # rows of decoded candidate sequences that search_phrases(rerank=False) holds at a time
 
 
 def _check_geometry(D: int, M) -> int:
@@ -172,6 +174,42 @@ def _decode(codes: torch.Tensor, codebooks: torch.Tensor) -> torch.Tensor:
             _lib.check(_lib.load().sylber_pq_decode(_vp(codes), codes.shape[0], _vp(codebooks), M, M * dsub, _vp(out), _stream(codes.device)),
                        "sylber_pq_decode")
     return out
+
+
+# ---- the exact DTW on the codes: what the rerank=False phrase paths of both classes share -------------------------------------------
+def _check_rerank(index: Optional[SyllableIndex], n_codes: int, rerank: Optional[bool], verb: str, name: str) -> bool:
+    """``rerank`` settled (``None``: whether the fp32 rows ``index`` are held), or ``ValueError``; ``name`` is ``"pq"`` or ``"ix"``"""
+    if rerank is None:
+        rerank = index is not None
+    if rerank and index is None:
+        raise ValueError("rerank=True needs the fp32 rows, which were dropped: %s with rerank=False" % verb)
+    if index is not None and len(index) != n_codes:
+        raise ValueError("%s.index holds %d rows, the codes %d: add rows through %s.add" % (name, len(index), n_codes, name))
+    return bool(rerank)
+
+
+def _rerank_codes_launch(c, db: tuple, cn) -> None:
+    """``_rerank_launch`` on a coded database, ``sylber_dtw_rerank_codes``: ``db, cn`` are what the index's ``_coded_db()`` returns"""
+    b = c.b
+    _lib.check(c.lib.sylber_dtw_rerank_codes(_vp(b.qp), b.nb, _vp(c.qn), _vp(c.place_d), _vp(c.len_d), int(c.cand.shape[0]), *db, c.N, c.dim,
+                                             _vp(cn), c.metric, _vp(c.cand), c.m, _vp(c.off_d), c.S, c.k, _vp(c.costs), _vp(c.seqs),
+                                             _vp(c.spans), _vp(c.ws), c.st), "sylber_dtw_rerank_codes")
+
+
+def _align_codes(N: int, dim: int, dev, metric: str, coded_db, phrases, spans, lengths, pair_chunk, tracked: bool):
+    """``align_phrases(rerank=False)`` of both classes: ``_align_phrases`` with ``sylber_dtw_align_codes`` on the real windows, so the
+    row ids are the real ones.  ``coded_db()`` is called once, behind the checks: it may build the index's lazy state."""
+    state = []
+
+    def run(lib, b, qn, place_d, len_d, pair_phrase, win, max_cols, rows, steps, costs, start, ws, st):
+        if not state:
+            state.extend(coded_db())
+        db, cn = state
+        _lib.check(lib.sylber_dtw_align_codes(_vp(b.qp), b.nb, _vp(qn), _vp(place_d), _vp(len_d), b.Pc, *db, N, dim, _vp(cn), METRICS[metric],
+                                              _vp(pair_phrase), _vp(win), int(pair_phrase.shape[0]), max_cols, int(rows.shape[1]),
+                                              _vp(rows), _vp(steps), _vp(costs), _vp(start), _vp(ws), st), "sylber_dtw_align_codes")
+
+    return _align_phrases(N, dim, dev, metric, phrases, spans, lengths, pair_chunk, run, tracked)
 
 
 def _check_residual(residual) -> bool:
@@ -433,8 +471,8 @@ class PQSyllableIndex:
 
     def search_phrases(self, phrases, k: int, refine: int = 4, storage: str = "fp16", *, rerank: Optional[bool] = None, lengths=None,
                        groups=None, exclude_same_group: bool = False, sequences=None, splits: int = 0,
-                       phrase_chunk: int = DEFAULT_PHRASE_CHUNK, block_phrases: int = 0, scratch_rows: int = DEFAULT_SCRATCH_ROWS,
-                       return_candidates: bool = False, _workspace_fill=None):
+                       phrase_chunk: int = DEFAULT_PHRASE_CHUNK, block_phrases: int = 0, return_candidates: bool = False,
+                       _workspace_fill=None):
         """``SyllableIndex.search_phrases_refined`` on the codes: the same arguments, and ``(costs, seqs, spans)`` (plus ``cand`` and
         ``coarse`` with ``return_candidates=True``) shaped, typed, ordered, padded and placed exactly as there.  ``m = k * refine <=
         128`` candidate sequences per phrase in both modes.
@@ -451,18 +489,21 @@ class PQSyllableIndex:
         ``pq.index.search_phrases`` on the fp32 rows for each candidate, so every returned cost and span is a real
         ``search_phrases`` cost and span, and with ``m`` at least the number of admissible sequences the result is
         ``pq.index.search_phrases``'s, bit for bit.  ``rerank=False`` (the only mode after ``drop_rows()``): the same exact DTW on the
-        *decoded* candidate sequences (a masked row is a NaN row), so under ``"l2"`` with no masked row the whole call equals
-        ``SyllableIndex(pq.decode(arange(N)), metric="l2", groups=g).search_phrases_refined(...)``, bit for bit.  The decoded rows
-        of at most ``scratch_rows`` rows' worth of candidate sequences exist at a time (one phrase's candidates at least; the call
-        waits for stage 1 of a chunk to learn them).
+        rows that ``pq.decode`` returns, a masked row being a NaN row, rebuilt from the code bytes inside the kernel's dot products
+        (csrc/dtw_codes.hip, ``sylber_dtw_rerank_codes``): no decoded scratch and no copy to the host.  Under ``"l2"`` with no
+        masked row the whole call equals ``SyllableIndex(pq.decode(arange(N)), metric="l2", groups=g).search_phrases_refined(...)``,
+        bit for bit.  Once ``sequence_offsets()`` and the lazy state (the 16-bit codebooks, the reconstruction norms) exist, a
+        ``rerank=False`` call only queues work: it never waits for the device.
 
-        Nothing returned depends on ``splits``, ``phrase_chunk``, ``block_phrases``, ``scratch_rows``, stale workspace contents, how
-        the index was built or whether it was saved and loaded.  ``storage="fp16"`` refuses a finite codebook value beyond
-        +-65504."""
-        rerank = self._check_rerank(rerank)
-        if isinstance(scratch_rows, bool) or int(scratch_rows) != scratch_rows or int(scratch_rows) < 1:
-            raise ValueError("scratch_rows must be an integer >= 1, got %r" % (scratch_rows,))
-        stage2 = (lambda c: _rerank_launch(c, self.index._x, self.index._c)) if rerank else (lambda c: self._rerank_decoded(c, int(scratch_rows)))
+        Nothing returned depends on ``splits``, ``phrase_chunk``, ``block_phrases``, stale workspace contents, how the index was
+        built, whether it was saved and loaded or, with ``rerank=False``, whether the rows are still held.  ``storage="fp16"``
+        refuses a finite codebook value beyond +-65504."""
+        if _check_rerank(self.index, len(self), rerank, "search", "pq"):
+            def stage2(c):
+                _rerank_launch(c, self.index._x, self.index._c)
+        else:
+            def stage2(c):
+                _rerank_codes_launch(c, *self._coded_db())
         return self._scan_codes(stage2, phrases, k, refine, storage, lengths, groups, exclude_same_group, sequences, splits, phrase_chunk,
                                 block_phrases, return_candidates, _workspace_fill)
 
@@ -472,7 +513,7 @@ class PQSyllableIndex:
                            _workspace_fill=None):
         """``SyllableIndex.search_occurrences_refined`` on the codes: every non-overlapping occurrence of each phrase in ``m = k *
         refine <= 128`` candidate sequences -> ``(costs, seqs, spans)`` as ``SyllableIndex.search_occurrences`` returns them (plus
-        ``cand`` and ``coarse`` with ``return_candidates=True``).  The arguments are ``search_phrases``'s without ``scratch_rows``.
+        ``cand`` and ``coarse`` with ``return_candidates=True``).  The arguments are ``search_phrases``'s.
 
         Stage 1 is ``search_phrases``'s, unchanged (``sylber_dtwpq_scan``): ``cand`` and ``coarse`` are its, bit for bit.  Stage 2,
         ``rerank=True`` (the default while the fp32 rows are held; ``ValueError`` once they are dropped):
@@ -485,26 +526,20 @@ class PQSyllableIndex:
 
         Nothing returned depends on ``splits``, ``phrase_chunk``, ``block_phrases``, stale workspace contents, how the index was
         built, whether it was saved and loaded or, with ``rerank=False``, whether the rows are still held."""
-        rerank = self._check_rerank(rerank)
-        N = len(self)
-        if rerank:
+        if _check_rerank(self.index, len(self), rerank, "search", "pq"):
             def stage2(c):
-                _occ_rerank_launch(c, "sylber_dtw_rerank_occurrences", (_vp(self.index._x), N, c.dim, _vp(self.index._c)))
+                _occ_rerank_launch(c, "sylber_dtw_rerank_occurrences", (_vp(self.index._x), c.N, c.dim, _vp(self.index._c)))
         else:
             def stage2(c):
-                db = (_vp(self._codes), _vp(self._bad), None, _vp(self.codebooks), self.M, None, None, 0, N, c.dim, _vp(self._recon_norms()))
-                _occ_rerank_launch(c, "sylber_dtw_rerank_occurrences_codes", db)
+                db, cn = self._coded_db()
+                _occ_rerank_launch(c, "sylber_dtw_rerank_occurrences_codes", db + (c.N, c.dim, _vp(cn)))
         return self._scan_codes(stage2, phrases, k, refine, storage, lengths, groups, exclude_same_group, sequences, splits, phrase_chunk,
                                 block_phrases, return_candidates, _workspace_fill)
 
-    def _check_rerank(self, rerank: Optional[bool]) -> bool:
-        if rerank is None:
-            rerank = self.index is not None
-        if rerank and self.index is None:
-            raise ValueError("rerank=True needs the fp32 rows, which were dropped: search with rerank=False")
-        if self.index is not None and len(self.index) != len(self):
-            raise ValueError("pq.index holds %d rows, the codes %d: add rows through pq.add" % (len(self.index), len(self)))
-        return bool(rerank)
+    def _coded_db(self):
+        """the coded-database argument group of ``sylber_dtw_rerank_codes`` / ``sylber_dtw_align_codes`` up to ``nlist``, and ``c``:
+        the codes lie in id order (no ``pos``) and are codes of the rows themselves (no lists)"""
+        return (_vp(self._codes), _vp(self._bad), None, _vp(self.codebooks), self.M, None, None, 0), self._recon_norms()
 
     def _scan_codes(self, stage2, phrases, k, refine, storage, lengths, groups, exclude_same_group, sequences, splits, phrase_chunk,
                     block_phrases, return_candidates, fill):
@@ -527,106 +562,19 @@ class PQSyllableIndex:
         return _scan_phrases(N, self.dim, self.device, self.metric, self._db_groups(), self.sequence_offsets, stages, phrases, k, refine, storage,
                              lengths, groups, exclude_same_group, sequences, splits, phrase_chunk, block_phrases, return_candidates, fill)
 
-    def _decode_windows(self, first: torch.Tensor, width: np.ndarray):
-        """the decoded rows of the windows ``first[i] : first[i] + width[i]`` (``first`` int64 on the device, ``width`` on the host) laid
-        end to end in a compact scratch -> ``(x fp32 [R, D] with masked rows NaN, their ||x^||^2 under "l2" or None, coff int64
-        [n + 1] on the device: window i is scratch rows coff[i] : coff[i + 1])``"""
-        dev = self.device
-        coff = torch.from_numpy(np.concatenate([[0], np.cumsum(width)]).astype(np.int64)).to(dev)
-        owner = torch.repeat_interleave(torch.arange(len(width), device=dev), coff[1:] - coff[:-1])
-        rid = first[owner] + (torch.arange(int(width.sum()), device=dev) - coff[owner])         # the real row of every scratch row
-        x = _decode(self._codes.index_select(0, rid), self.codebooks)
-        x = torch.where((self._bad.index_select(0, rid) != 0)[:, None], torch.full_like(x, float("nan")), x)
-        rnorm = self._recon_norms()
-        return x, (rnorm.index_select(0, rid) if rnorm is not None else None), coff
-
-    def _rerank_decoded(self, c, scratch_rows: int) -> None:
-        """stage 2 of ``search_phrases(rerank=False)`` for one chunk (plumbing around ``sylber_dtw_rerank``): the chunk's phrases in
-        runs whose candidate sequences hold at most ``scratch_rows`` rows together (one phrase at least); per run the unique
-        candidates in ascending sequence number -- so that ties break as on the real numbering -- decoded into a compact scratch
-        with compact offsets, the exact DTW on it, and sequence numbers and row ids mapped back"""
-        dev, off = self.device, c.off
-        cand_h = c.cand.cpu().numpy()                       # waits for stage 1 of the chunk
-        seq_len = np.diff(off)
-        runs, g0, have, rows = [], 0, np.zeros(0, np.int64), 0
-        for p in range(c.b.Pc):
-            new = np.setdiff1d(cand_h[p][cand_h[p] >= 0], have)
-            more = int(seq_len[new].sum())
-            if p > g0 and rows + more > scratch_rows:
-                runs.append((g0, p, have))
-                g0, have, rows = p, np.zeros(0, np.int64), 0
-                new = np.unique(cand_h[p][cand_h[p] >= 0])
-                more = int(seq_len[new].sum())
-            have, rows = np.union1d(have, new).astype(np.int64), rows + more
-        runs.append((g0, c.b.Pc, have))
-        for g0, g1, uniq in runs:
-            cand, c_out, s_out, sp_out = c.cand[g0:g1], c.costs[g0:g1], c.seqs[g0:g1], c.spans[g0:g1]
-            if uniq.size == 0:                              # no candidate at all: the padding of an empty list
-                c_out.fill_(float("inf")); s_out.fill_(-1); sp_out.fill_(-1)
-                continue
-            uniq_d, roff_d = (torch.from_numpy(a).to(dev) for a in (uniq, off[uniq]))
-            x, cn, coff_d = self._decode_windows(roff_d, seq_len[uniq])
-            cc = torch.searchsorted(uniq_d, cand.to(torch.int64).clamp(min=0))
-            cc = torch.where(cand < 0, torch.full_like(cc, -1), cc).to(torch.int32).contiguous()
-            _rerank_launch(c.part(place_d=c.place_d[g0:g1], len_d=c.len_d[g0:g1], N=int(x.shape[0]), cand=cc, off_d=coff_d.to(torch.int32),
-                                  S=int(uniq.size), costs=c_out, seqs=s_out, spans=sp_out), x, cn)
-            hit = s_out >= 0
-            sc = s_out.clamp(min=0)
-            sp_out.copy_(torch.where(hit[:, :, None], sp_out - coff_d[sc][:, :, None] + roff_d[sc][:, :, None], sp_out))
-            s_out.copy_(torch.where(hit, uniq_d[sc], s_out))
-
     def align_phrases(self, phrases, spans, lengths=None, pair_chunk: Optional[int] = None, *, rerank: Optional[bool] = None,
-                      scratch_rows: int = DEFAULT_SCRATCH_ROWS, _tracked_start: bool = False):
+                      _tracked_start: bool = False):
         """the warping paths behind the spans of ``search_phrases`` or ``search_occurrences`` -> ``(rows, steps, costs)`` as
         ``SyllableIndex.align_phrases`` returns them; ``rerank`` is what that search was given.  ``rerank=True`` (the default while the
         fp32 rows are held; ``ValueError`` once they are dropped): ``pq.index.align_phrases``, on the rows the exact re-rank ran on.
-        ``rerank=False`` (the only mode after ``drop_rows()``): the same alignment (csrc/dtw_align.hip) on the *decoded* rows of the
-        windows, a masked row being a NaN row, as both searches score them with ``rerank=False`` -- so on their spans ``costs`` has the
-        bits of its costs, and the result is ``SyllableIndex(pq.decode(arange(N)), ...).align_phrases``'s.  Per chunk of pairs the
-        windows are decoded into a compact scratch of at most ``scratch_rows`` rows (one window at least; the call waits to learn
-        the widths) and the row ids are mapped back on the device.  Nothing returned depends on ``pair_chunk``, ``scratch_rows``
-        or, with ``rerank=False``, on whether the rows are still held."""
-        if rerank is None:
-            rerank = self.index is not None
-        if rerank and self.index is None:
-            raise ValueError("rerank=True needs the fp32 rows, which were dropped: align with rerank=False")
-        if isinstance(scratch_rows, bool) or int(scratch_rows) != scratch_rows or int(scratch_rows) < 1:
-            raise ValueError("scratch_rows must be an integer >= 1, got %r" % (scratch_rows,))
-        N, D, dev = len(self), self.dim, self.device
-        if rerank:
-            if len(self.index) != N:
-                raise ValueError("pq.index holds %d rows, the codes %d: add rows through pq.add" % (len(self.index), N))
+        ``rerank=False`` (the only mode after ``drop_rows()``): the same alignment on the rows that ``pq.decode`` returns, a masked
+        row being a NaN row, rebuilt from the codes inside the kernel (csrc/dtw_codes.hip, ``sylber_dtw_align_codes``; no scratch,
+        no wait for the device beyond the one check of the spans) -- as both searches score them with ``rerank=False``, so on their
+        spans ``costs`` has the bits of its costs, and the result is ``SyllableIndex(pq.decode(arange(N)), ...).align_phrases``'s.
+        Nothing returned depends on ``pair_chunk`` or, with ``rerank=False``, on whether the rows are still held."""
+        if _check_rerank(self.index, len(self), rerank, "align", "pq"):
             return self.index.align_phrases(phrases, spans, lengths=lengths, pair_chunk=pair_chunk, _tracked_start=_tracked_start)
-        metric = METRICS[self.metric]
-
-        def run(lib, b, qn, place_d, len_d, pair_phrase, win, max_cols, rows, steps, costs, start, ws, st):
-            w64 = win.to(torch.int64)
-            width = w64[:, 1] - w64[:, 0]                       # 0 for padding
-            width_h = width.cpu().numpy()
-            cuts, have = [0], 0                                 # runs of pairs whose windows hold at most scratch_rows rows together
-            for i, w in enumerate(width_h.tolist()):
-                if i > cuts[-1] and have + w > int(scratch_rows):
-                    cuts.append(i)
-                    have = 0
-                have += w
-            cuts.append(len(width_h))
-            for g0, g1 in zip(cuts[:-1], cuts[1:]):
-                R = int(width_h[g0:g1].sum())
-                if R == 0:                                      # nothing but padding: the outputs hold it already
-                    continue
-                wd, a = width[g0:g1], w64[g0:g1, 0]
-                x, cn, coff = self._decode_windows(a, width_h[g0:g1])
-                cwin = torch.stack([coff[:-1], coff[1:]], 1)
-                cwin = torch.where((wd == 0)[:, None], torch.full_like(cwin, -1), cwin).to(torch.int32).contiguous()
-                r, s0 = rows[g0:g1], (start[g0:g1] if start is not None else None)
-                _align_launch(lib, b, qn, place_d, len_d, x, R, D, cn, metric, pair_phrase[g0:g1], cwin, max_cols, r, steps[g0:g1],
-                              costs[g0:g1], s0, ws, st)
-                shift = (a - coff[:-1]).to(torch.int32)
-                r.copy_(torch.where(r >= 0, r + shift[:, None, None], r))
-                if s0 is not None:
-                    s0.copy_(torch.where(s0 >= 0, s0 + shift, s0))
-
-        return _align_phrases(N, D, dev, self.metric, phrases, spans, lengths, pair_chunk, run, _tracked_start)
+        return _align_codes(len(self), self.dim, self.device, self.metric, self._coded_db, phrases, spans, lengths, pair_chunk, _tracked_start)
 
     # ---- persistence ----------------------------------------------------------------------------------------------------------------
     def save(self, path: str) -> None:
@@ -962,15 +910,6 @@ class IVFPQSyllableIndex:
         lists = (_vp(self._off), _vp(self.centroids), self.nlist) if self._residual else (None, None, 0)
         return (_vp(self._codes), _vp(self._rbad), _vp(pos), _vp(self.codebooks), self.M) + lists, pc
 
-    def _check_rerank(self, rerank: Optional[bool], verb: str) -> bool:
-        if rerank is None:
-            rerank = self.index is not None
-        if rerank and self.index is None:
-            raise ValueError("rerank=True needs the fp32 rows, which were dropped: %s with rerank=False" % verb)
-        if self.index is not None and len(self.index) != len(self):
-            raise ValueError("ix.index holds %d rows, the codes %d: add rows through ix.add" % (len(self.index), len(self)))
-        return bool(rerank)
-
     def search_phrases(self, phrases, k: int, nprobe: int, seeds: int = 32, refine: int = 4, *, rerank: Optional[bool] = None, lengths=None,
                        groups=None, exclude_same_group: bool = False, sequences=None, query_chunk: int = DEFAULT_QUERY_CHUNK,
                        phrase_chunk: int = DEFAULT_PHRASE_CHUNK, splits: int = 0, return_candidates: bool = False, _workspace_fill=None):
@@ -1034,7 +973,7 @@ class IVFPQSyllableIndex:
                       query_chunk, phrase_chunk, splits, return_candidates, _workspace_fill):
         """``search_phrases`` (one match per candidate sequence) or ``search_occurrences`` (every occurrence in it): the checks, stage 1a
         and, by ``rerank``, the seeded search of ``ix.index`` or the vote and the DTW on the codes"""
-        rerank = self._check_rerank(rerank, "search")
+        rerank = _check_rerank(self.index, len(self), rerank, "search", "ix")
         N, dev = len(self), self.device
         k, m = _check_k_refine(k, refine, rerank=True)
         nprobe = _check_nprobe(nprobe, self.nlist)
@@ -1059,14 +998,8 @@ class IVFPQSyllableIndex:
         def occ_codes(c):
             _occ_rerank_launch(c, "sylber_dtw_rerank_occurrences_codes", db + (N, c.dim, _vp(pc)))
 
-        def rerank_codes(c):
-            b = c.b
-            _lib.check(c.lib.sylber_dtw_rerank_codes(_vp(b.qp), b.nb, _vp(c.qn), _vp(c.place_d), _vp(c.len_d), int(c.cand.shape[0]), *db, N,
-                                                     c.dim, _vp(pc), c.metric, _vp(c.cand), c.m, _vp(c.off_d), c.S, c.k, _vp(c.costs),
-                                                     _vp(c.seqs), _vp(c.spans), _vp(c.ws), c.st), "sylber_dtw_rerank_codes")
-
         return _seeded_phrases(N, self.dim, dev, self.metric, self._by_id(self._rg), q, lens, pg, off, sc, si, k, m, phrase_chunk,
-                               return_candidates, occ_codes if occurrences else rerank_codes, _workspace_fill)
+                               return_candidates, occ_codes if occurrences else (lambda c: _rerank_codes_launch(c, db, pc)), _workspace_fill)
 
     def align_phrases(self, phrases, spans, lengths=None, pair_chunk: Optional[int] = None, *, rerank: Optional[bool] = None,
                       _tracked_start: bool = False):
@@ -1076,21 +1009,9 @@ class IVFPQSyllableIndex:
         ``rerank=False``: the same alignment on the rows that ``ix.decode`` returns, rebuilt from the codes inside the kernel
         (csrc/dtw_codes.hip, ``sylber_dtw_align_codes``; no scratch) -- so on spans from ``search_phrases(rerank=False)`` or
         ``search_occurrences(rerank=False)`` ``costs`` has the bits of that search's costs, before and after ``drop_rows()``.  Nothing returned depends on ``pair_chunk``."""
-        rerank = self._check_rerank(rerank, "align")
-        if rerank:
+        if _check_rerank(self.index, len(self), rerank, "align", "ix"):
             return self.index.align_phrases(phrases, spans, lengths=lengths, pair_chunk=pair_chunk, _tracked_start=_tracked_start)
-        N, D, metric = len(self), self.dim, METRICS[self.metric]
-        state = []                                              # the lazy state, built behind align_phrases' checks
-
-        def run(lib, b, qn, place_d, len_d, pair_phrase, win, max_cols, rows, steps, costs, start, ws, st):
-            if not state:
-                state.extend(self._coded_db())
-            db, pc = state
-            _lib.check(lib.sylber_dtw_align_codes(_vp(b.qp), b.nb, _vp(qn), _vp(place_d), _vp(len_d), b.Pc, *db, N, D, _vp(pc), metric,
-                                                  _vp(pair_phrase), _vp(win), int(pair_phrase.shape[0]), max_cols, int(rows.shape[1]),
-                                                  _vp(rows), _vp(steps), _vp(costs), _vp(start), _vp(ws), st), "sylber_dtw_align_codes")
-
-        return _align_phrases(N, D, self.device, self.metric, phrases, spans, lengths, pair_chunk, run, _tracked_start)
+        return _align_codes(len(self), self.dim, self.device, self.metric, self._coded_db, phrases, spans, lengths, pair_chunk, _tracked_start)
 
     # ---- persistence ----------------------------------------------------------------------------------------------------------------
     def save(self, path: str) -> None:

@@ -39,7 +39,7 @@ from ._index import MAX_CANDIDATES, MAX_K, MAX_NPROBE  # noqa: F401  (limits of 
 from ._index import DEFAULT_PHRASE_CHUNK, MAX_PHRASE_ROWS, MAX_SEEDS, MAX_SEQUENCE_ROWS, STORAGES  # noqa: F401  (likewise, for the phrase searches)
 from ._index import (DEFAULT_QUERY_CHUNK, METRICS, _added_rows, _base_arrays, _check_k_refine, _check_nprobe, _check_splits_chunk,
                      _chunked_workspace_bytes, _group_runs, _list_layout, _on_device, _outputs, _pack16, _phrase_args, _phrase_blocks,
-                     _phrase_outputs, _PhraseBlocks, _PhraseChunk, _prep, _provenance, _query_groups, _result, _row_norms, _rows, _rows_of_width,
+                     _phrase_outputs, _PhraseChunk, _prep, _provenance, _query_groups, _result, _row_norms, _rows, _rows_of_width,
                      _scan_phrases)
 from .kmeans import _device, _stream, _vp
 
@@ -49,7 +49,7 @@ MAX_WINDOW_ROWS = 65536         # DA_MAX_COLS of csrc/dtw_align.hip: the rows of
 ALIGN_WORKSPACE_BYTES = 256 << 20       # the default pair_chunk of align_phrases keeps its workspace below this
 
 
-# ---- warping paths: what SyllableIndex.align_phrases and PQSyllableIndex.align_phrases share ---------------------------------------
+# ---- warping paths: what the align_phrases of SyllableIndex and of the compressed indexes share -------------------------------
 def _align_spans(spans, P: int, N: int, device) -> Tuple[torch.Tensor, int]:
     """the checks of ``align_phrases`` on ``spans`` -> ``(spans int64 [P, k, 2] on the device, the widest window)``, or ``ValueError``;
     one reduction on the device and one copy of two numbers to the host"""
@@ -69,15 +69,6 @@ def _align_spans(spans, P: int, N: int, device) -> Tuple[torch.Tensor, int]:
     if widest > MAX_WINDOW_ROWS:
         raise ValueError("a window has %d rows, more than %d" % (widest, MAX_WINDOW_ROWS))
     return sp, int(widest)
-
-
-def _align_launch(lib, b: "_PhraseBlocks", qn, place_d, len_d, x, N: int, D: int, cn, metric: int, pair_phrase, win, max_cols: int,
-                  rows, steps, costs, start, ws, st) -> None:
-    """``sylber_dtw_align`` for the pairs ``(pair_phrase [n] int32, win [n, 2] int32)`` against the rows ``x [N, D]`` with norms ``cn``
-    into ``rows [n, Mx, 2]`` int32, ``steps [n]``, ``costs [n]`` and, unless it is None, ``start [n]`` int32"""
-    _lib.check(lib.sylber_dtw_align(_vp(b.qp), b.nb, _vp(qn), _vp(place_d), _vp(len_d), b.Pc, _vp(x), N, D, _vp(cn), metric, _vp(pair_phrase),
-                                    _vp(win), int(pair_phrase.shape[0]), max_cols, int(rows.shape[1]), _vp(rows), _vp(steps), _vp(costs),
-                                    _vp(start), _vp(ws), st), "sylber_dtw_align")
 
 
 def _rerank_launch(c: "_PhraseChunk", x, cn) -> None:
@@ -594,8 +585,9 @@ class SyllableIndex:
         N = len(self)
 
         def run(lib, b, qn, place_d, len_d, pair_phrase, win, max_cols, rows, steps, costs, start, ws, st):
-            _align_launch(lib, b, qn, place_d, len_d, self._x, N, self.dim, self._c, METRICS[self.metric], pair_phrase, win, max_cols,
-                          rows, steps, costs, start, ws, st)
+            _lib.check(lib.sylber_dtw_align(_vp(b.qp), b.nb, _vp(qn), _vp(place_d), _vp(len_d), b.Pc, _vp(self._x), N, self.dim, _vp(self._c),
+                                            METRICS[self.metric], _vp(pair_phrase), _vp(win), int(pair_phrase.shape[0]), max_cols,
+                                            int(rows.shape[1]), _vp(rows), _vp(steps), _vp(costs), _vp(start), _vp(ws), st), "sylber_dtw_align")
 
         return _align_phrases(N, self.dim, self.device, self.metric, phrases, spans, lengths, pair_chunk, run, _tracked_start)
 

@@ -3,11 +3,14 @@ against tests/align_ref.py: the local costs are taken from the library itself (`
 rows, as tests/test_gpu_phrase.py takes them), the fp32 window DP and the backtrack of align_ref run over them, and the call must
 return exactly those rows, steps and cost bits.  On the spans of every phrase search the path must start and end where the span does
 and carry the search's cost bits (the theorem of include/sylber_hip.h)."""
+import functools
+
 import numpy as np
 import pytest
 import torch
 
 import align_ref as A
+from test_gpu_dtwpq import _decoded_index
 from test_gpu_phrase import _groups_of, _local_costs, _np
 
 pytestmark = pytest.mark.gpu
@@ -193,8 +196,8 @@ def test_the_inverted_file_delegates():
     assert torch.equal(got[2].view(torch.int32), costs.view(torch.int32)) and torch.equal(got[0][:, :, 0, 0], spans[:, :, 0])
 
 
-def test_the_compressed_index_with_and_without_its_rows():
-    from sylber_amd import PQSyllableIndex, SyllableIndex
+def _compressed_corpus():
+    """rows in sequences of 1, 33 and 65 rows around the 32-column chunk of csrc/dtw_pair.h, random codebooks (M = 2), four phrases"""
     rng = np.random.default_rng(6)
     lens = [40, 7, 90, 1, 33, 65, 20]
     offsets = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
@@ -202,6 +205,13 @@ def test_the_compressed_index_with_and_without_its_rows():
     x = rng.standard_normal((N, D)).astype(np.float32)
     books = rng.standard_normal((M, 256, D // M)).astype(np.float32)
     phrases = [x[a:a + m] + 0.1 * rng.standard_normal((m, D)).astype(np.float32) for m, a in ((1, 3), (4, 60), (9, 150), (30, 200))]
+    return x, offsets, books, phrases
+
+
+def test_the_compressed_index_with_and_without_its_rows():
+    from sylber_amd import PQSyllableIndex, SyllableIndex
+    x, offsets, books, phrases = _compressed_corpus()
+    N, M = len(x), len(books)
     idx = SyllableIndex(x, metric="l2", groups=_groups_of(offsets), device=DEV)
     pq = PQSyllableIndex.build(idx, M, codebooks=books)
     k = 8
@@ -212,7 +222,7 @@ def test_the_compressed_index_with_and_without_its_rows():
     pq.drop_rows()
     with pytest.raises(ValueError, match="rerank"):
         pq.align_phrases(phrases, spans, rerank=True)
-    got = pq.align_phrases(phrases, spans, scratch_rows=40, _tracked_start=True)
+    got = pq.align_phrases(phrases, spans, _tracked_start=True)
     assert torch.equal(got[3], got[0][:, :, 0, 0])
     got = got[:3]
     _equal(held, got, "drop_rows")
@@ -222,8 +232,57 @@ def test_the_compressed_index_with_and_without_its_rows():
     assert torch.equal(got[0][:, :, 0, 0][hit], spans[:, :, 0][hit])
     xhat = _np(pq.decode(np.arange(N)))
     _assert_same(got, _reference(xhat, phrases, spans, "l2", offsets))
-    for kw in ({"scratch_rows": 1}, {"scratch_rows": 50}, {"scratch_rows": 50, "pair_chunk": 3}, {"pair_chunk": 1}):
+    for kw in ({"pair_chunk": 3}, {"pair_chunk": 1}):
         _equal(got, pq.align_phrases(phrases, spans, **kw), kw)
+
+
+MASKED = 100                                                # a row inside the 90-row sequence, rows 47 .. 136
+CODED_WINDOWS = ((90, 110), (80, MASKED + 1), (3, 4), (40, 55), (-1, -1), (MASKED, MASKED + 1), (137, 236))
+#                 holds the masked row | ends on it | one row | crosses the sequence edges 40 and 47 | padding | the masked row alone |
+#                 the sequences of 1, 33 and 65 rows: 99 columns, four chunks
+
+
+@functools.lru_cache(maxsize=None)
+def _coded_alignment():
+    """the corpus with one masked row, the windows, and what ``SyllableIndex.align_phrases`` returns for them on the decoded rows with
+    the masked row as a NaN row: the oracle of ``PQSyllableIndex.align_phrases(rerank=False)``, computed once"""
+    from sylber_amd import PQSyllableIndex
+    x, offsets, books, phrases = _compressed_corpus()
+    x = x.copy()
+    x[MASKED, 5] = np.nan
+    grp = _groups_of(offsets)
+    pq = PQSyllableIndex.build(x, len(books), codebooks=books, groups=grp, metric="l2", device=DEV)
+    assert _np(pq._bad).nonzero()[0].tolist() == [MASKED]
+    windows = np.array([CODED_WINDOWS] * len(phrases), np.int64)
+    windows[1:, 2] = ((50, 51), (136, 137), (len(x) - 1, len(x)))   # other 1-row windows: inside, the last row of the 90, the last of all
+    want = _decoded_index(pq, grp, nan_masked=True).align_phrases(phrases, windows, _tracked_start=True)
+    return x, grp, books, phrases, windows, want
+
+
+@pytest.mark.parametrize("dropped", [False, True])
+def test_the_compressed_index_aligns_straight_from_its_codes(dropped):
+    """``PQSyllableIndex.align_phrases(rerank=False)`` (``sylber_dtw_align_codes`` on plain codes: identity positions, no lists)
+    against the fp32 alignment on the materialised rows, bit for bit, with the rows held and after ``drop_rows()``"""
+    from sylber_amd import PQSyllableIndex
+    x, grp, books, phrases, windows, want = _coded_alignment()
+    pq = PQSyllableIndex.build(x, len(books), codebooks=books, groups=grp, metric="l2", device=DEV)
+    if dropped:
+        pq.drop_rows()
+    got = pq.align_phrases(phrases, windows, rerank=False, _tracked_start=True)
+    assert len(got) == 4
+    for g, w in zip(got, want):
+        assert g.dtype == w.dtype and g.shape == w.shape
+    _equal(got[:2] + got[3:], want[:2] + want[3:])
+    assert torch.equal(got[2].view(torch.int32), want[2].view(torch.int32))
+    rows, steps, costs, start = got
+    assert torch.equal(start, rows[:, :, 0, 0])
+    pad = torch.zeros(costs.shape, dtype=torch.bool, device=DEV)
+    pad[:, [1, 4, 5]] = True                                  # a window that ends on the masked row has no path, nor has the padding
+    assert _is_padding(rows, steps, costs, pad) and torch.isfinite(costs[~pad]).all() and (steps[~pad] > 0).all()
+    assert (rows[:, 0, 0, 0] > MASKED).all()                  # the path starts behind the masked row
+    assert int(steps[3, 2]) == 30                             # 30 phrase rows on one column
+    for pair_chunk in (1, 3, None):
+        _equal(got, pq.align_phrases(phrases, windows, pair_chunk=pair_chunk, rerank=False, _tracked_start=True), pair_chunk)
 
 
 def test_every_refusal_comes_before_a_launch(monkeypatch):
@@ -238,7 +297,8 @@ def test_every_refusal_comes_before_a_launch(monkeypatch):
 
     def fail(*a):
         raise AssertionError("launched")
-    monkeypatch.setattr(_lib, "_LIB", type("L", (), {"__getattr__": lambda self, n: fail if n == "sylber_dtw_align" else getattr(lib, n)})())
+    entries = {"sylber_dtw_align", "sylber_dtw_align_codes"}
+    monkeypatch.setattr(_lib, "_LIB", type("L", (), {"__getattr__": lambda self, n: fail if n in entries else getattr(lib, n)})())
     p = [x[:3]]
     ok = np.array([[[0, 5], [-1, -1]]], np.int64)
     bad = [dict(spans=[[[0, 41]]]), dict(spans=[[[-2, 5]]]), dict(spans=[[[-1, 5]]]), dict(spans=[[[5, 5]]]), dict(spans=[[[7, 3]]]),
@@ -253,8 +313,8 @@ def test_every_refusal_comes_before_a_launch(monkeypatch):
             kw = dict(kw)
             with pytest.raises(ValueError):
                 call(kw.pop("phrases", p), kw.pop("spans"), **kw)
-    with pytest.raises(ValueError):
-        pq.align_phrases(p, ok, scratch_rows=0)
+    with pytest.raises(TypeError):
+        pq.align_phrases(p, ok, scratch_rows=0)             # there is no scratch to bound
     with pytest.raises(ValueError):
         SyllableIndex(device=DEV).align_phrases(p, ok)
     with pytest.raises(ValueError, match="65536"):

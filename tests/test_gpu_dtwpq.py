@@ -5,7 +5,7 @@
   bit, both metrics, masked rows included;
 * rows held: ``pq.index.search_phrases`` restricted to the candidates, and that search itself once m covers the sequences or the bound
   of tests/dtwpq_ref.py decides the candidate set;
-* bitwise invariance under the split / chunk / packing / scratch hooks, stale workspace contents, how the index was built, a save /
+* bitwise invariance under the split / chunk / packing hooks, stale workspace contents, how the index was built, a save /
   load round trip and ``drop_rows()``;
 * tile, K-step and sub-space edges; admissibility and padding; the fp16 range, the refusals (the C entry's too) and ``P = 0``;
 * stage 1 within ``coarse_cost_error_bound`` of the float64 restatement on the decoded rows."""
@@ -240,8 +240,8 @@ def test_invariance_is_bitwise(tmp_path):
     x, offsets, phrases, k, refine = R16.checkable_inputs()
     ph = list(phrases)
     grp = _groups_of(offsets)
-    hooks = ({"splits": 1}, {"splits": 2}, {"splits": 5}, {"phrase_chunk": 1}, {"block_phrases": 1}, {"scratch_rows": 1},
-             {"_workspace_fill": 0xFF}, {"_workspace_fill": 0xFF, "splits": 5, "phrase_chunk": 7, "block_phrases": 3, "scratch_rows": 100})
+    hooks = ({"splits": 1}, {"splits": 2}, {"splits": 5}, {"phrase_chunk": 1}, {"block_phrases": 1}, {"_workspace_fill": 0xFF},
+             {"_workspace_fill": 0xFF, "splits": 5, "phrase_chunk": 7, "block_phrases": 3})
     for metric, storage in (("l2", "fp16"), ("cosine", "bf16")):
         pq = _pq(metric)
         for rerank in (False, True):
@@ -448,7 +448,7 @@ def test_every_refusal_comes_before_a_launch(monkeypatch):
     big = PQSyllableIndex.build(np.zeros((65537, 16), np.float32), 1, codebooks=C, device=DEV)
     lib = _lib.load()
     launched = []
-    spied = ("sylber_dtwpq_scan", "sylber_dtw16_scan", "sylber_dtw_rerank", "sylber_dtw_search")
+    spied = ("sylber_dtwpq_scan", "sylber_dtw16_scan", "sylber_dtw_rerank", "sylber_dtw_rerank_codes", "sylber_dtw_search")
 
     def spy(name):
         real = getattr(lib, name)
@@ -470,10 +470,7 @@ def test_every_refusal_comes_before_a_launch(monkeypatch):
            # the two-stage call's own limits: they hold in both modes, m = k * refine
            dict(phrases=p, k=1, refine=0), dict(phrases=p, k=1, refine=-2), dict(phrases=p, k=1, refine=1.5), dict(phrases=p, k=1, refine=True),
            dict(phrases=p, k=True), dict(phrases=p, k=33, refine=4), dict(phrases=p, k=128, refine=2), dict(phrases=p, k=1, refine=129),
-           dict(phrases=p, k=1, storage="fp32"), dict(phrases=p, k=1, storage="fp8"), dict(phrases=p, k=1, storage=None),
-           # this call's own
-           dict(phrases=p, k=1, scratch_rows=0), dict(phrases=p, k=1, scratch_rows=-5), dict(phrases=p, k=1, scratch_rows=1.5),
-           dict(phrases=p, k=1, scratch_rows=True)]
+           dict(phrases=p, k=1, storage="fp32"), dict(phrases=p, k=1, storage="fp8"), dict(phrases=p, k=1, storage=None)]
     for kw in bad:
         for ix, rerank in ((pq, True), (pq, False), (dropped, False)):
             kw2 = dict(kw)
@@ -481,6 +478,9 @@ def test_every_refusal_comes_before_a_launch(monkeypatch):
                 ix.search_phrases(kw2.pop("phrases"), kw2.pop("k"), rerank=rerank, **kw2)
     with pytest.raises(ValueError, match="rerank=True"):
         dropped.search_phrases(p, 1, rerank=True)
+    for ix in (pq, dropped):
+        with pytest.raises(TypeError):
+            ix.search_phrases(p, 1, scratch_rows=1)          # there is no scratch to bound
     for rerank in (True, False):
         with pytest.raises(ValueError, match="sequences="):
             big.search_phrases(p, 1, rerank=rerank)
@@ -496,8 +496,8 @@ def test_every_refusal_comes_before_a_launch(monkeypatch):
     _assert_equal(got[:3], big.index.search_phrases(p, 1, sequences=[0, 65536, 65537]))
     assert _np(got[3]).tolist() == [[0, 1]]
     launched.clear()
-    dropped.search_phrases(p, 2, 2, scratch_rows=1)          # a run per phrase at least
-    assert launched == ["sylber_dtwpq_scan", "sylber_dtw_rerank"]
+    dropped.search_phrases(p, 2, 2)                          # the exact DTW straight from the codes
+    assert launched == ["sylber_dtwpq_scan", "sylber_dtw_rerank_codes"]
     launched.clear()
     assert len(dropped.search_phrases([], 4, 3)) == 3 and not launched
 

@@ -16,12 +16,14 @@ call returns.  The 16-bit plane is built before anything is timed.
 
 ``--pq [--M 48] [--storage fp16|bf16] [--refine 4]`` (with ``--refined``) adds the compressed leg (csrc/dtwpq.hip,
 ``PQSyllableIndex.search_phrases``) on codes of the same rows: the whole-call time with the fp32 rows held (``pq_held_ms``: exact
-re-rank on the rows) and of the call that runs after ``drop_rows()`` (``pq_dropped_ms``: ``rerank=False``, re-rank on the decoded
-candidates; the two calls are bitwise the same before and after the drop), each over ``search_phrases_refined``'s time in the same
+re-rank on the rows) and of the call that runs after ``drop_rows()`` (``pq_dropped_ms``: ``rerank=False``, the exact DTW straight
+from the codes; the call is bitwise the same before and after the drop), each over ``search_phrases_refined``'s time in the same
 run; for refine 1, 2, 4 and 8 the share of phrases whose exact top-k comes back (rows held: the same list; rows dropped: the same
 set of sequences); and the device bytes of each index.  The codebooks are the sub-rows of 256 stored rows drawn at random, not
 k-means: the rows are independent gaussian, so training has no structure to find.  Codes, 16-bit codebooks and reconstruction norms
-are built before anything is timed.
+are built before anything is timed.  With ``--align`` also ``pq_align_dropped_ms``: the whole call of
+``pq.align_phrases(..., rerank=False)`` on the spans of that ``rerank=False`` search, with the number of pairs aligned
+(``pq_align_pairs``).
 
 ``--occurrences [--storage fp16|bf16] [--refine 4]`` adds the leg of "every occurrence" (``SyllableIndex.search_occurrences`` and
 ``search_occurrences_refined``): in the same run, on the same phrases and index, the whole-call time of each beside its
@@ -53,7 +55,7 @@ residual codes after ``drop_rows()``; ``IVFSyllableIndex.search_phrases`` at the
 (rows dropped, ``refine``) beside them; the dropped call's stage 1a (``ix.search`` alone), stage 2 alone and remainder (the vote and
 the host work); and stage 2 alone two ways on the same candidates: ``sylber_dtw_rerank_codes``, and ``ix.decode`` of the candidate
 sequences' rows into a scratch followed by ``sylber_dtw_rerank`` on it (the candidate copy to the host that sizes the scratch
-included, as in ``PQSyllableIndex``), with the scratch's rows.  Lazy state is built before anything is timed.
+included), with the scratch's rows.  Lazy state is built before anything is timed.
 
 ``--occurrences`` combines with ``--ivf``, ``--ivfpq`` and ``--pq``: each new ``search_occurrences`` is timed beside its per-sequence
 sibling in the same process (``ivf_occ_ms`` beside ``ivf_phrase_ms``; ``occ_held_ms`` / ``occ_dropped_ms`` /
@@ -587,6 +589,11 @@ def main():
                     row.update(pq_occ_held_ms=round(t9, 2), pq_occ_held_ms_min_max=[round(lo9, 2), round(hi9, 2)], pq_occ_held_over_pq_held=round(t9 / t3, 3),
                                pq_occ_dropped_ms=round(t10, 2), pq_occ_dropped_ms_min_max=[round(lo10, 2), round(hi10, 2)],
                                pq_occ_dropped_over_pq_dropped=round(t10 / t4, 3))
+                if args.align:
+                    pspans = pq.search_phrases(ph, k, args.refine, args.storage, lengths=ln, rerank=False)[2]
+                    t11, lo11, hi11 = timed(lambda: pq.align_phrases(ph, pspans, lengths=ln, rerank=False), args.iters)
+                    row.update(pq_align_dropped_ms=round(t11, 2), pq_align_dropped_ms_min_max=[round(lo11, 2), round(hi11, 2)],
+                               pq_align_pairs=int((pspans[:, :, 0] >= 0).sum()))
                 row.update(M=args.M, pq_held_ms=round(t3, 2), pq_held_ms_min_max=[round(lo3, 2), round(hi3, 2)], pq_dropped_ms=round(t4, 2),
                            pq_dropped_ms_min_max=[round(lo4, 2), round(hi4, 2)], pq_held_over_refined=round(t3 / t2, 3),
                            pq_dropped_over_refined=round(t4 / t2, 3), pq_recovered_topk_held=held, pq_recovered_topk_dropped=dropped)
