@@ -889,7 +889,13 @@ int sylber_condition_features(sylber_mlp_t m, const float* features_dev, int32_t
  *       SYLBER_LTAP_LN1       after LayerNorm 1: the FFN's operand                                                       W = 768
  *       SYLBER_LTAP_FFN1      after FFN1 (GELU applied)                                                                  W = 3072
  *       SYLBER_LTAP_FFN2_SUM  after FFN2: bias + residual added, the input of LayerNorm 2 (whose output is stage 3 + l)  W = 768
- *   Refused for l >= num_layers, for the SYLBER_FP8 precision and (like every stop stage) by sylber_forward_packed.
+ *   SYLBER_FP8: the MXFP8 buffers (q / k / v with SYLBER_OPT_FP8_ATTENTION on, the context, LayerNorm 1's output, FFN1's output) are
+ *   dequantised exactly -- e4m3 x 2^(s - 127) is an fp32 value -- and returned as [B, T, 2 W]: the W values, then W floats that hold
+ *   each element's own block exponent s - 127 (constant over 32 features; for v over 32 keys of a feature), so that the scale bytes
+ *   are observable as well.  q is as stored: pre-scaled by 1 / 8 (the fp8 attention core applies log2(e) itself).  The fp32 sums
+ *   (ATTN_SUM, FFN2_SUM) keep W = 768, and so does QKV with SYLBER_OPT_FP8_ATTENTION at -1 (bf16 buffers, W = 2304, q pre-scaled
+ *   by log2(e) / 8).
+ *   Refused for l >= num_layers and (like every stop stage) by sylber_forward_packed.
  * Any other negative stage (-4 .. -7, k = 6, 7) is refused. */
 enum { SYLBER_TAP_CONV0 = -1, SYLBER_TAP_PROJ = -2, SYLBER_TAP_POSCONV = -3 };
 enum { SYLBER_LTAP_QKV = 0, SYLBER_LTAP_CTX = 1, SYLBER_LTAP_ATTN_SUM = 2, SYLBER_LTAP_LN1 = 3, SYLBER_LTAP_FFN1 = 4, SYLBER_LTAP_FFN2_SUM = 5 };

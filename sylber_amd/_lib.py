@@ -242,6 +242,15 @@ LTAP_QKV, LTAP_CTX, LTAP_ATTN_SUM, LTAP_LN1, LTAP_FFN1, LTAP_FFN2_SUM = 0, 1, 2,
 LTAP_WIDTH = {LTAP_QKV: 2304, LTAP_CTX: 768, LTAP_ATTN_SUM: 768, LTAP_LN1: 768, LTAP_FFN1: 3072, LTAP_FFN2_SUM: 768}
 
 
+def ltap_width(k: int, precision: str = "bf16", fp8_attention: bool = True) -> int:
+    """floats per frame that tap k returns.  The fp8 precision returns its MXFP8 buffers as W dequantised values followed by W block
+    exponents (2 W); its fp32 sums, and q | k | v where the attention core runs on bf16 operands (OPT_FP8_ATTENTION < 0), keep W"""
+    w = LTAP_WIDTH.get(int(k), 768)
+    if precision != "fp8" or k in (LTAP_ATTN_SUM, LTAP_FFN2_SUM) or (k == LTAP_QKV and not fp8_attention):
+        return w
+    return 2 * w
+
+
 def TAP_LAYER(l: int, k: int) -> int:
     """the stop stage of tap k (LTAP_*) of encoder layer l"""
     return -(8 * (int(l) + 1) + int(k))

@@ -195,7 +195,6 @@ extern "C" int sylber_set_stop_stage(sylber_t c, int32_t stage) {
             syl_set_error("sylber_set_stop_stage", "unknown tap (negative stages: -1 conv0, -2 projection, -3 pos-conv, -(8 (l + 1) + k) tap k = 0..5 of layer l)"); return 1;
         }
         if (l >= c->num_layers) { syl_set_error("sylber_set_stop_stage", "layer tap: the handle has no such layer"); return 1; }
-        if (c->precision == SYLBER_FP8) { syl_set_error("sylber_set_stop_stage", "layer taps are not available in the fp8 precision"); return 1; }
     }
     c->stop_stage = stage;
     return 0;

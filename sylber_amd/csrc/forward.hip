@@ -352,7 +352,7 @@ struct Forward {
     // the residual of every block is the previous LayerNorm's output; it is re-derived in the GEMM epilogue from
     // the pre-LN sum still sitting in `pre` (updated in place) + that LayerNorm's row statistics and affine
     const float *res_g = nullptr, *res_b = nullptr;
-    const LayerTap tap;                                 // a tap inside a layer: layer16 sets `tapped` once it has copied it out
+    const LayerTap tap;                                 // a tap inside a layer: layer16 / layer8 set `tapped` once they have copied it out
     bool tapped = false;
 
     Forward(sylber_ctx* c_, const Plan& p_, const float* wav, float* hidden, hipStream_t s_, const PackedCall* pk_)
@@ -507,9 +507,17 @@ struct Forward {
         return 0;
     }
 
+    // a layer tap of SYLBER_FP8: frames [0, T) of an MXFP8 workspace buffer [B][Tp][W] (K-pair-major scales, pitch w8.Mp) dequantised
+    // exactly, as [B][T][2 W]: W values, then W floats holding each element's block exponent s - 127
+    int tap_rows8(const uint8_t* buf, const uint8_t* scale, int W) {
+        tapped = true;
+        RUN("copy_out", launch_mxfp8_to_f32_rows(buf, scale, MXTAP_ROWS, w8.Mp, hidden_dev, 2L * W, 0, W, B, p.Tp, p.T, W, s));
+        return 0;
+    }
+
     // one post-LN encoder layer on MXFP8 operands (SYLBER_FP8): every GEMM reads e4m3 + block scales; FFN1 leaves its GELU output as
-    // MXFP8 for FFN2
-    int layer8(const LayerDev& d, bool last) {
+    // MXFP8 for FFN2; tk: the layer tap to stop behind (-1: none)
+    int layer8(const LayerDev& d, bool last, int tk) {
         GemmF8Args g = linear8(w8.h, w8.hs, d.wqkvq, d.wqkvs, d.bqkv, 2304, 768);
         g.g.out0 = w.q; g.g.out1 = w.k; g.g.out2 = w.vt; g.g.Tp = p.Tp; g.g.Tpv = p.Tpv; g.g.T = p.T;
         // the attention core of the mode must not depend on the batch shape (one utterance, same hidden states alone or in a
@@ -520,21 +528,38 @@ struct Forward {
         if (c->opt_attn8 >= 0 && gemm_asm_f8_tile(EPI_QK8, gq) != 0) {     // attention core on MXFP8 operands
             gq.g.out0 = w8.q; gq.g.out1 = w8.k; gq.g.out2 = w8.v; gq.qs = w8.qs; gq.ks = w8.ks; gq.vs = w8.vs;
             RUN("gemm_qkv", launch_gemm_mxfp8(EPI_QK8, gq, s));
+            if (tk == SYLBER_LTAP_QKV) {                // q | k | v values [0, 2304), their block exponents [2304, 4608)
+                tapped = true;
+                RUN("copy_out", launch_mxfp8_to_f32_rows(w8.q, w8.qs, MXTAP_HEADS, 0, hidden_dev, 4608, 0, 2304, B, p.Tp, p.T, 768, s));
+                RUN("copy_out", launch_mxfp8_to_f32_rows(w8.k, w8.ks, MXTAP_HEADS, 0, hidden_dev, 4608, 768, 3072, B, p.Tp, p.T, 768, s));
+                RUN("copy_out", launch_mxfp8_to_f32_rows(w8.v, w8.vs, MXTAP_VT, p.Tpv, hidden_dev, 4608, 1536, 3840, B, p.Tp, p.T, 768, s));
+                return 0;
+            }
             RUN("attention", launch_attention_f8(w8.q, w8.qs, w8.k, w8.ks, w8.v, w8.vs, w.valid, w8.ctx, w8.ctxs, w8.Mp, B, p.T, p.Tp, p.Tpv, s));
         } else {
             RUN("gemm_qkv", launch_gemm_mxfp8(EPI_QK, g, s));
+            if (tk == SYLBER_LTAP_QKV) {                // the 16-bit buffers of EPI_QK: [B][T][2304] as in layer16
+                tapped = true;
+                RUN("copy_out", launch_tap_qkv(w.q, w.k, w.vt, hidden_dev, B, p.T, p.Tp, p.Tpv, s, c->fmt, p.lo_qk, p.lo_vt));
+                return 0;
+            }
             RUN("attention", launch_attention_f8out(w.q, w.k, w.vt, w.valid, w8.ctx, w8.ctxs, w8.Mp, B, p.T, p.Tp, p.Tpv, c->opt_attn_qw, s));
         }
+        if (tk == SYLBER_LTAP_CTX) return tap_rows8(w8.ctx, w8.ctxs, 768);
         GemmF8Args o = linear8(w8.ctx, w8.ctxs, d.woq, d.wos, d.bo, 768, 768);
         residual(o.g, res_g, res_b);
         RUN("gemm_out", launch_gemm_mxfp8(EPI_F32_RESLN, o, s));
+        if (tk == SYLBER_LTAP_ATTN_SUM) return tap_pre();
         RUN("layernorm", layernorm(d.ln1w, d.ln1b, false));
+        if (tk == SYLBER_LTAP_LN1) return tap_rows8(w8.h, w8.hs, 768);
         GemmF8Args f1 = linear8(w8.h, w8.hs, d.w1q, d.w1s, d.b1, 3072, 768);
         f1.g.act = 1; f1.g.out0 = w8.ffn; f1.g.ld0 = 3072; f1.out_scale = w8.ffns; f1.os_rows = w8.Mp;
         RUN("gemm_ffn1", launch_gemm_mxfp8(EPI_MXFP8, f1, s));
+        if (tk == SYLBER_LTAP_FFN1) return tap_rows8(w8.ffn, w8.ffns, 3072);
         GemmF8Args f2 = linear8(w8.ffn, w8.ffns, d.w2q, d.w2s, d.b2, 768, 3072);
         residual(f2.g, d.ln1w, d.ln1b);
         RUN("gemm_ffn2", launch_gemm_mxfp8(EPI_F32_RESLN, f2, s));
+        if (tk == SYLBER_LTAP_FFN2_SUM) return tap_pre();
         RUN("layernorm", layernorm(d.ln2w, d.ln2b, last));
         return 0;
     }
@@ -560,7 +585,8 @@ struct Forward {
         for (int l = 0; l < c->num_layers; ++l) {
             const LayerDev& d = c->L[l];
             const bool last = (l == c->num_layers - 1) || (c->stop_stage == 3 + l);
-            if (f8 ? layer8(d, last) : layer16(d, last, l == tap.l ? tap.k : -1)) return 1;
+            const int tk = l == tap.l ? tap.k : -1;         // the layer tap to stop behind (-1: none)
+            if (f8 ? layer8(d, last, tk) : layer16(d, last, tk)) return 1;
             if (last || tapped) break;
             res_g = d.ln2w; res_b = d.ln2b;
         }

@@ -579,3 +579,51 @@ int launch_bf16_to_f32_rows(const bf16_t* in, long ld_in, float* out, int B, int
     HIP_TRY(hipGetLastError());
     return 0;
 }
+
+// the same for an MXFP8 buffer (the layer taps of SYLBER_FP8): frames [0, T) of every utterance, W features each, dequantised exactly
+// -- e4m3 x 2^(s - 127) is an fp32 value -- into out[(b T + t) ld_out + val_col + c], and the element's own block exponent s - 127 as
+// a float into out[(b T + t) ld_out + exp_col + c], so that the scale bytes can be looked at as well as the values.  Layouts:
+//   MXTAP_ROWS  data [B Tp][W], one scale per (row, 32 features), K-pair-major with row pitch `pitch` (mx_scale_index)
+//   MXTAP_HEADS data [B][12][Tp][64] head-major (W = 768), one scale per (token, 32 features): [B][12][Tp][2]
+//   MXTAP_VT    data [B][768][pitch] with pitch = Tpv keys per feature row, natural key order (W = 768), one scale per (feature, 32 KEYS):
+//               [B 768][Tpv / 32]
+// An e4m3 NaN code or a scale byte of 255 comes out as NaN.
+__device__ __forceinline__ float e4m3_to_f32(unsigned b) {
+    const unsigned e = (b >> 3) & 15u, m = b & 7u;
+    if ((b & 0x7fu) == 0x7fu) return __uint_as_float(0x7fc00000u);
+    const float mag = e == 0u ? (float)m * 0x1p-9f : ldexpf((float)(8u + m), (int)e - 10);
+    return (b & 0x80u) ? -mag : mag;
+}
+__global__ __launch_bounds__(256) void mxfp8_rows_to_f32_kernel(const uint8_t* __restrict__ data, const uint8_t* __restrict__ scale, int layout,
+                                                                long pitch, float* __restrict__ out, long ld_out, int val_col, int exp_col,
+                                                                int Tp, int T, int W) {
+    const int b = blockIdx.y, t = blockIdx.x;
+    float* dst = out + ((size_t)b * T + t) * ld_out;
+    for (int c = threadIdx.x; c < W; c += 256) {
+        size_t di, si;
+        if (layout == MXTAP_ROWS) {
+            const size_t row = (size_t)b * Tp + t;
+            di = row * W + c; si = mx_scale_index((long)row, c >> 5, pitch);
+        } else if (layout == MXTAP_HEADS) {
+            const size_t row = ((size_t)b * SYL_HEADS + (c >> 6)) * Tp + t;
+            di = row * 64 + (c & 63); si = row * 2 + ((c & 63) >> 5);
+        } else {
+            const size_t row = (size_t)b * SYL_HIDDEN + c;
+            di = row * pitch + t; si = row * (pitch / 32) + (t >> 5);
+        }
+        const unsigned sb = scale[si];
+        dst[val_col + c] = sb == 255u ? __uint_as_float(0x7fc00000u) : ldexpf(e4m3_to_f32(data[di]), (int)sb - 127);
+        dst[exp_col + c] = (float)((int)sb - 127);
+    }
+}
+int launch_mxfp8_to_f32_rows(const uint8_t* data, const uint8_t* scale, int layout, long pitch, float* out, long ld_out, int val_col, int exp_col,
+                             int B, int Tp, int T, int W, hipStream_t s) {
+    if (T < 1 || T > Tp || Tp % 32 != 0 || W % 32 != 0 || (layout != MXTAP_ROWS && W != SYL_HIDDEN) || (layout == MXTAP_VT && (pitch < Tp || pitch % 32 != 0)) ||
+        val_col + W > ld_out || exp_col + W > ld_out) {
+        syl_set_error("launch_mxfp8_to_f32_rows", "need 1 <= T <= Tp, Tp % 32 == 0, W % 32 == 0 (768 for the head-major and V^T layouts), columns inside the row");
+        return 1;
+    }
+    hipLaunchKernelGGL(mxfp8_rows_to_f32_kernel, dim3(T, B), dim3(256), 0, s, data, scale, layout, pitch, out, ld_out, val_col, exp_col, Tp, T, W);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}

@@ -210,5 +210,9 @@ int launch_upload_ints(int* dst, const int32_t* vals_host, int n, int add, hipSt
 int launch_f32_to_bf16(const float* in, bf16_t* out, size_t n, hipStream_t s);
 int launch_f32_to_split16(const float* in, bf16_t* out, long lo_off, size_t n, hipStream_t s);   // hi plane at out, lo plane at out + lo_off
 int launch_bf16_to_f32_rows(const bf16_t* in, long ld_in, float* out, int B, int Tp, int T, int D, hipStream_t s, int fmt = 0, long in_lo = 0);
+// the layer taps of SYLBER_FP8 (frontend.hip): an MXFP8 buffer dequantised exactly, plus every element's block exponent s - 127
+enum { MXTAP_ROWS = 0, MXTAP_HEADS = 1, MXTAP_VT = 2 };
+int launch_mxfp8_to_f32_rows(const uint8_t* data, const uint8_t* scale, int layout, long pitch, float* out, long ld_out, int val_col, int exp_col,
+                             int B, int Tp, int T, int W, hipStream_t s);
 // SYLBER_LTAP_QKV (ops.hip): head-major q / k [B][12][Tp][64] and key-permuted V^T [B][12][64][Tpv] -> f32 [B][T][2304] = q | k | v in natural order
 int launch_tap_qkv(const bf16_t* q, const bf16_t* k, const bf16_t* vt, float* out, int B, int T, int Tp, int Tpv, hipStream_t s, int fmt, long lo_qk, long lo_vt);

@@ -354,14 +354,17 @@ class HubertEncoderHIP:
         the encoder LayerNorm / layer l.  Negative values are the taps of the front half: ``_lib.TAP_CONV0`` conv layer 0 alone,
         [B, 64 * padded_frames(Lmax), 512] (every row of its buffer); ``_lib.TAP_PROJ`` the projected residual stream and
         ``_lib.TAP_POSCONV`` the encoder LayerNorm's input, both [B, T, 768].  ``_lib.TAP_LAYER(l, k)`` is tap k (``_lib.LTAP_*``)
-        inside encoder layer l: [B, T, _lib.LTAP_WIDTH[k]] (2304 = q | k | v, 3072 for FFN1, else 768)."""
+        inside encoder layer l: [B, T, _lib.LTAP_WIDTH[k]] (2304 = q | k | v, 3072 for FFN1, else 768).  In the fp8 precision the MXFP8
+        buffers (QKV, CTX, LN1, FFN1) come back as [B, T, 2 W]: W values dequantised exactly, then W floats holding each element's block
+        exponent s - 127 (``_lib.ltap_width``); the fp32 sums keep W, and so does QKV with ``_lib.OPT_FP8_ATTENTION`` at -1."""
         assert wav.is_cuda and wav.dtype == torch.float32 and wav.dim() == 2 and wav.is_contiguous()
         B, Lmax = wav.shape
         T = self.num_frames(Lmax)
         if stop_stage == _lib.TAP_CONV0:
             shape = (B, 64 * self.padded_frames(Lmax), 512)
         elif stop_stage <= -8:
-            shape = (B, T, _lib.LTAP_WIDTH.get(-stop_stage % 8, 768))       # (an unknown k is refused by the library below)
+            # (an unknown k is refused by the library below)
+            shape = (B, T, _lib.ltap_width(-stop_stage % 8, self.precision, self._opts.get(_lib.OPT_FP8_ATTENTION, 0) >= 0))
         else:
             shape = (B, T, 512 if stop_stage == 1 else 768)
         if out is None:

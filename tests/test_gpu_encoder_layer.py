@@ -204,9 +204,12 @@ def test_layer_taps_are_refused_where_they_do_not_apply(encoders, sds):
         with pytest.raises(_lib.SylberHipError):
             enc.forward(wav, lens, stop_stage=stage)
     assert enc.forward(wav, lens).shape == (1, 1, 768)                # (a refused stage left the handle at stage 0)
+    # (the fp8 precision has layer taps of its own, values + block exponents: tests/test_gpu_fp8_layer.py; the same refusals apply)
     e8 = HubertEncoderHIP(sds["base"], num_layers=2, precision="fp8")
-    with pytest.raises(_lib.SylberHipError):
-        e8.forward(wav, lens, stop_stage=_lib.TAP_LAYER(0, _lib.LTAP_CTX))
+    assert e8.forward(wav, lens, stop_stage=_lib.TAP_LAYER(0, _lib.LTAP_CTX)).shape == (1, 1, 2 * 768)
+    for stage in (-4, _lib.TAP_LAYER(0, 6), _lib.TAP_LAYER(2, 0)):
+        with pytest.raises(_lib.SylberHipError):
+            e8.forward(wav, lens, stop_stage=stage)
     # the packed forward refuses every stop stage
     _lib.check(enc.lib.sylber_set_stop_stage(enc.handle, _lib.TAP_LAYER(0, _lib.LTAP_CTX)), "sylber_set_stop_stage")
     try:
