@@ -790,7 +790,7 @@ int sylber_expand_units(const float* feats_dev, const int32_t* durations_dev, in
 /* ---- per-handle options ------------------------------------------------------------------------ */
 /* Tuning / test overrides, scoped to ONE handle (nothing process-global).  SYLBER_OPT_GEMM_TILE: value < 0 restores the
  * automatic choice (0 is a tile id); the other keys: 0 = automatic.
- *   SYLBER_OPT_GEMM_TILE               tile configuration id of the bf16 GEMM launches (csrc/gemm_bf16.hip launch_t:
+ *   SYLBER_OPT_GEMM_TILE               tile configuration id of the bf16 GEMM launches (csrc/gemm_tiles.h:
  *                                      0 = 256x128, 3 = 128x128, 4 = 128x192, 10 = 256x256 8-wave, 11 = 256x192 8-wave;
  *                                      hand-scheduled K loops (csrc/gemm_asm.hip; a launch whose epilogue / K has no such
  *                                      instantiation falls back to 128x192): 80 = 256x256 4-wave, 90 = 256x192, 95 = 256x256
@@ -822,7 +822,7 @@ int sylber_expand_units(const float* feats_dev, const int32_t* durations_dev, in
  *   SYLBER_OPT_GEMM_TAIL               k > 0: a GEMM launch whose tile count is not a whole number of rounds of 256 persistent workgroups is split BY ROWS --
  *                                      the rows of the full rounds on the chosen tile, the remaining rows as a second launch on tile id k (bit-identical
  *                                      outputs: every element is one fp32 chain over K whatever tile computes it).  0 / -1 (default): one launch.  Measured
- *                                      not to pay (a small tile alone on a CU is no faster than a big one; csrc/gemm_bf16.hip launch_f): the partial
+ *                                      not to pay (a small tile alone on a CU is no faster than a big one; csrc/gemm_bf16.hip gemm_plan): the partial
  *                                      rounds are handled by the 192-row tiles below; this stays as a test vehicle
  *   SYLBER_OPT_GEMM_H192               0 (default): the cost model may pick the 192-row siblings of the hand-scheduled tiles (ids 51 = 192x192, 57 = 192x256:
  *                                      a second tile HEIGHT, for launches whose 256-row tile count leaves a partial last round); -1: 256-row tiles only (A/B)
@@ -832,7 +832,7 @@ int sylber_expand_units(const float* feats_dev, const int32_t* durations_dev, in
  *                                      launches.  -1: those launches on the 32x32x16 kernels of the earlier rounds (A/B switch).  The two families group an output
  *                                      element's fp32 sum over K differently (32-k against 16-k blocks): results agree to fp32 rounding of the accumulator, not bit
  *                                      for bit -- WITHIN either setting results do not depend on the batch shape or the tile.
- *   SYLBER_OPT_GEMM_MODEL              which tiles the GEMM launches of this handle get (csrc/gemm_bf16.hip launch_f).  0 (default): the handle OWNS the chip -- one batch in
+ *   SYLBER_OPT_GEMM_MODEL              which tiles the GEMM launches of this handle get (csrc/gemm_bf16.hip gemm_plan).  0 (default): the handle OWNS the chip -- one batch in
  *                                      flight, as in a synchronous Segmenter.__call__: a launch is charged its partial last round (measured per kernel
  *                                      family) and may use the 192-row tiles; 5: the handle SHARES the chip with another in-flight batch (bench.py's
  *                                      pipeline, ShardedSegmenter's two engines): the CUs a partial round leaves idle go to the other stream's

@@ -20,6 +20,13 @@ int sylber_debug_gemm_bench(int32_t M, int32_t N, int32_t K, int32_t ldx, int32_
  * epi / act as the forward passes them (0 = 16-bit out, 3 = q,k,v, 6 = fp32 residual + LayerNorm; act 1 = GELU), fmt 0 bf16 / 1 fp16,
  * model = SYLBER_OPT_GEMM_MODEL, kpat = 1 for the 3-tap conv K order.  tests/test_abi.py pins the choices of the headline shapes. */
 int sylber_debug_gemm_pick(int32_t M, int32_t N, int32_t K, int32_t epi, int32_t act, int32_t fmt, int32_t model, int32_t kpat);
+/* the kernel instantiation(s) the launcher resolves that launch to (host arithmetic only): `tile` as sylber_op_linear takes it (-1 = the cost
+ * model's pick; + 1000 x workgroups per CU, 9000 + id = one workgroup per tile, + 1000000 = the 16-bit-output role on the 32x32x16 kernels), fmt 2 =
+ * split16, h192 / pre / tail = SYLBER_OPT_GEMM_H192 / the residual prefetch columns / the forced tail tile id + 1.  buf receives one line per launch,
+ * "<first row> <end row> <kernel template>[<template arguments>]"; returns the number of launches (2 = a forced row split), 0 = refused,
+ * -1 = buf too small.  tests/test_abi.py pins a grid of these against tests/golden/gemm_dispatch.txt. */
+int sylber_debug_gemm_resolve(int32_t M, int32_t N, int32_t K, int32_t epi, int32_t act, int32_t fmt, int32_t kpat, int32_t tile, int32_t model,
+                              int32_t h192, int32_t pre, int32_t tail, char* buf, int32_t cap);
 /* the same launch through the TRACE instantiation of the 8-wave 256x256 kernel (s_memtime stamps around the phases of its K
  * loop): out20 = 2 x 10 shader-cycle counters of workgroup 0's waves 0 and 4 (csrc/api.hip sylber_debug_gemm_trace) */
 int sylber_debug_gemm_trace(int32_t M, int32_t N, int32_t K, int32_t ldx, int32_t epi, int32_t act, unsigned long long* out20,

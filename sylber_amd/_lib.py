@@ -227,6 +227,7 @@ EXPORTS = {
 DEV_EXPORTS = {
     "sylber_debug_gemm_bench": (c_int, [c_int32] * 8 + [POINTER(c_float)]),
     "sylber_debug_gemm_pick": (c_int, [c_int32] * 8),
+    "sylber_debug_gemm_resolve": (c_int, [c_int32] * 12 + [ctypes.c_char_p, c_int32]),
     "sylber_debug_gemm_trace": (c_int, [c_int32] * 6 + [POINTER(ctypes.c_uint64), POINTER(c_float)]),
     "sylber_debug_attention_bench": (c_int, [c_int32] * 4 + [POINTER(c_float)]),
     "sylber_debug_poison_workspace": (c_int, [c_void_p, c_int32]),

@@ -1,6 +1,6 @@
 // Tile 47: tile 97's geometry (256x256 on eight waves, X3 ring, persistent) with the K loop on v_mfma_f32_16x16x32 (round 6).
 //
-// Same contract and same operands as launch_gemm_asm's tile 97 (y = act(x W^T + b) as 16-bit rows: the GELU GEMMs of the path -- conv1-5
+// Same contract and same operands as gemm_asm.hip's tile 97 (y = act(x W^T + b) as 16-bit rows: the GELU GEMMs of the path -- conv1-5
 // TP:154-213, FFN1 TP:347-368 reached from sylber.py:122), same LDS image (128-byte rows, source-side chunk swizzle), same LDS-DMA pieces,
 // same ring and tile walk as gemmb_bf16_kernel<.., 2, 8, true>.  What differs is the MFMA shape of the loop (tools/gen_gemm_asm.py "Y3"):
 // the vendor library's kernels on this part issue 16x16x32, and profiles/r06_mfma_shape.md measured that shape 8.5 % cheaper per FLOP
@@ -462,35 +462,40 @@ static int launch_s(const GemmArgs& a, hipStream_t s) {
 }
 
 // ---- the family's dispatch ------------------------------------------------------------------------------------------------------
-bool gemm_asm16_has_tile(int epi, const GemmArgs& a, int tile) {
-    if (tile != 13 && tile != 14 && tile != 15 && tile != 16 && tile != 17 && tile != 46 && tile != 47) return false;
-    if ((epi != EPI_BF16 && epi != EPI_F32) || (a.act != 0 && a.act != 1)) return false;
-    if (a.fmt != FMT_BF16 && a.fmt != FMT_F16) return false;
-    if (epi == EPI_F32 && (a.fmt != FMT_BF16 || a.kpat)) return false;
-    if (a.K % 64 != 0 || a.K < 64) return false;
-    if (a.kpat && a.K != 1536) return false;
-    if (tile == 13 || tile == 14 || tile == 15 || tile == 16 || tile == 17) return true;
-    if (a.K % 128 != 0 || a.K < 256) return false;         // the generated loops: pairs of K steps, at least four
-    if (tile == 46 && a.kpat) return false;
-    return true;
+// One GemmKernel per instantiation: the launch wrapper, and as its static name the __global__ template with every template argument
+namespace kern {
+template <int EPI, int ACT, int FMT, bool TAP, int FMV = 4>
+static GemmKernel gemmc_bf16_kernel() { return {launch_c<EPI, ACT, FMT, TAP, FMV>, __PRETTY_FUNCTION__}; }
+template <int FM, int FN, int EPI, int ACT, int FMT, int NW = 4, int NSTAGE = 2>
+static GemmKernel gemm16_bf16_kernel() { return {launch_s<FM, FN, EPI, ACT, FMT, NW, NSTAGE>, __PRETTY_FUNCTION__}; }
 }
 
 template <int EPI, int ACT, int FMT>
-static int launch_family(int tile, const GemmArgs& a, hipStream_t s) {
-    if (tile == 13) return launch_s<2, 2, EPI, ACT, FMT>(a, s);
-    if (tile == 14) return launch_s<2, 3, EPI, ACT, FMT>(a, s);
-    if (tile == 15) return launch_s<2, 2, EPI, ACT, FMT, 8>(a, s);
-    if (tile == 16) return launch_s<2, 3, EPI, ACT, FMT, 8>(a, s);
-    if (tile == 17) return launch_s<1, 1, EPI, ACT, FMT, 4, 3>(a, s);      // 64x64, three-slot ring: the launches of one or two clips (gemm_bf16.hip tile 1)
-    if (tile == 46) return launch_c<EPI, ACT, FMT, false, 3>(a, s);
-    if constexpr (EPI == EPI_BF16) { if (a.kpat) return launch_c<EPI, ACT, FMT, true>(a, s); }
-    return launch_c<EPI, ACT, FMT, false>(a, s);
+static GemmKernel resolve_asm16(int tile, const GemmArgs& a) {
+    using namespace kern;
+    if (a.K % 64 != 0 || a.K < 64) return {};
+    if (a.kpat && (EPI != EPI_BF16 || a.K != 1536)) return {};             // the conv K order: 16-bit outputs, K = 1536
+    switch (tile) {
+        case 13: return gemm16_bf16_kernel<2, 2, EPI, ACT, FMT>();
+        case 14: return gemm16_bf16_kernel<2, 3, EPI, ACT, FMT>();
+        case 15: return gemm16_bf16_kernel<2, 2, EPI, ACT, FMT, 8>();
+        case 16: return gemm16_bf16_kernel<2, 3, EPI, ACT, FMT, 8>();
+        case 17: return gemm16_bf16_kernel<1, 1, EPI, ACT, FMT, 4, 3>();   // 64x64, three-slot ring: the launches of one or two clips (gemm_bf16.hip tile 1)
+    }
+    if (a.K % 128 != 0 || a.K < 256) return {};                            // the generated loops: pairs of K steps, at least four
+    if (tile == 46 && !a.kpat) return gemmc_bf16_kernel<EPI, ACT, FMT, false, 3>();
+    if (tile == 47) {
+        if constexpr (EPI == EPI_BF16) { if (a.kpat) return gemmc_bf16_kernel<EPI, ACT, FMT, true>(); }
+        return gemmc_bf16_kernel<EPI, ACT, FMT, false>();
+    }
+    return {};
 }
 
-int launch_gemm_asm16(int epi, const GemmArgs& a, hipStream_t s) {
-    const int tile = a.tune_cfg - 1;
-    if (!gemm_asm16_has_tile(epi, a, tile)) { syl_set_error("launch_gemm_asm16", "no 16x16x32 instantiation for this tile / epilogue / K"); return 1; }
-    if (epi == EPI_F32) return a.act == 1 ? launch_family<EPI_F32, 1, FMT_BF16>(tile, a, s) : launch_family<EPI_F32, 0, FMT_BF16>(tile, a, s);
-    if (a.fmt == FMT_F16) return a.act == 1 ? launch_family<EPI_BF16, 1, FMT_F16>(tile, a, s) : launch_family<EPI_BF16, 0, FMT_F16>(tile, a, s);
-    return a.act == 1 ? launch_family<EPI_BF16, 1, FMT_BF16>(tile, a, s) : launch_family<EPI_BF16, 0, FMT_BF16>(tile, a, s);
+// the (epilogue, activation, format) launches the family is instantiated for: 16-bit outputs in bf16 and fp16, the plain fp32 output in bf16
+GemmKernel gemm_asm16_resolve(int tile, int epi, const GemmArgs& a) {
+    if ((a.act != 0 && a.act != 1) || (a.fmt != FMT_BF16 && a.fmt != FMT_F16)) return {};
+    if (epi == EPI_F32 && a.fmt == FMT_BF16) return a.act == 1 ? resolve_asm16<EPI_F32, 1, FMT_BF16>(tile, a) : resolve_asm16<EPI_F32, 0, FMT_BF16>(tile, a);
+    if (epi != EPI_BF16) return {};
+    if (a.fmt == FMT_F16) return a.act == 1 ? resolve_asm16<EPI_BF16, 1, FMT_F16>(tile, a) : resolve_asm16<EPI_BF16, 0, FMT_F16>(tile, a);
+    return a.act == 1 ? resolve_asm16<EPI_BF16, 1, FMT_BF16>(tile, a) : resolve_asm16<EPI_BF16, 0, FMT_BF16>(tile, a);
 }

@@ -21,6 +21,7 @@
 // remapped so that each XCD owns a contiguous run of tiles (shared X panel in L2; same row ownership as the
 // LayerNorm / attention launches between the GEMMs).
 #include "kernels.h"
+#include "gemm_tiles.h"
 #include <type_traits>
 
 typedef __attribute__((address_space(3))) void* lds_vptr;
@@ -882,71 +883,102 @@ static int launch_cfg8p(const GemmArgs& a, hipStream_t s) {
                                     // there are (B = 1: FFN1 as 36 tiles of 192x256 = 19.5-21 us against 10.3 us on 96 tiles of 128x128; profiles/r06_small_tiles.md) -- the
                                     // partial-round rule below (fitted to launches of one round and more) priced it at 0.48 and sent every GEMM of a single-clip call to the big tiles
 #endif
-#ifndef GEMM_SPLIT_US
-#define GEMM_SPLIT_US 4.0           // what the second launch of a split costs (dispatch gap + a second prologue)
-#endif
 #ifndef GEMM_H192_EFF
 #define GEMM_H192_EFF 0.90          // the 192-row tiles' efficiency relative to their 256-row siblings (in-forward: full rounds at 0.845 instead of 0.75 of the time)
 #endif
 #ifndef GEMM_PR0_ASM
 #define GEMM_PR0_ASM 0.4            // cost of an (almost) empty partial round of the persistent hand-scheduled tiles, relative to a full round
 #endif
-#define GEMM_CU_MACS_PER_US 1.8e6   // one CU's rate on these loops (256 x 256 x 768 MACs in ~28 us)
 
-// launch one tile configuration (by id) over rows [a.m_begin, a.M)
+// One GemmKernel per instantiation: the launch wrapper, and as its static name the __global__ template with every template argument
+// (the compiler spells them, defaults included)
+namespace kern {
+template <int FM, int FN, int BK, int NSTAGE, int MINB, bool PRIO, int EPI, int ACT, int FMT, int WM = 2, int WN = 2>
+static GemmKernel gemm_bf16_kernel() { return {launch_cfg<FM, FN, BK, NSTAGE, MINB, PRIO, EPI, ACT, FMT, WM, WN>, __PRETTY_FUNCTION__}; }
+template <int FM, int FN, int WM, int WN, int EPI, int ACT, int FMT, int VAR = 0>
+static GemmKernel gemm8_bf16_kernel() { return {launch_cfg8<FM, FN, WM, WN, EPI, ACT, FMT, VAR>, __PRETTY_FUNCTION__}; }
+template <int EPI, int ACT, int FMT, bool TRACE = false>
+static GemmKernel gemm8u_bf16_kernel() { return {launch_cfg8u<EPI, ACT, FMT, TRACE>, __PRETTY_FUNCTION__}; }
+template <int ACT, int FMT>
+static GemmKernel gemm8p_bf16_kernel() { return {launch_cfg8p<ACT, FMT>, __PRETTY_FUNCTION__}; }
+}
+
+// the hipcc kernels' instantiation for tile id `tile` over rows [a.m_begin, a.M)
 template <int EPI, int ACT, int FMT>
-static int launch_tile(int cfg, const GemmArgs& a, hipStream_t s) {
-    if constexpr (FMT == FMT_SPLIT) {
-        // the split-operand mode instantiates the three tile shapes the cost model picks (and nothing else)
-        if (cfg == 3) return launch_cfg<2, 2, 64, 2, 2, false, EPI, ACT, FMT>(a, s);
-        if (cfg == 10) {
-            if constexpr (EPI == EPI_BF16) {
-                if (a.tune_persist >= 0 && (a.M - a.m_begin) % 256 == 0 && a.N % 256 == 0 && a.K >= 96 && (long)((a.M - a.m_begin) / 256) * (a.N / 256) > 256)
-                    return launch_cfg8p<ACT, FMT>(a, s);
-            }
-            return launch_cfg8<4, 2, 2, 4, EPI, ACT, FMT>(a, s);
-        }
-        return launch_cfg<2, 3, 64, 2, 2, false, EPI, ACT, FMT>(a, s);
-    } else
-    switch (cfg) {
-        case 0: return launch_cfg<4, 2, 64, 3, 1, false, EPI, ACT, FMT>(a, s);   // 256x128, 3-slot ring, 1 WG/CU
-        // round 6: the launches of a call on one or two clips are chains of K steps on a few LONE workgroups (fewer tiles than CUs), each step waiting for LDS-DMA pieces
-        // issued half a step earlier.  64-row tiles put four times the workgroups on the idle CUs, and a THREE-slot ring lets a step's pieces be one and a half steps old:
-        // out-proj of one clip 12.5 -> 7.0 us, FFN2 25.5 -> 18.5, q,k,v 9.4 -> 7.9 (profiles/r06_small_tiles.md).  Same chain per output element: bit-identical.
-        case 1: return launch_cfg<1, 1, 64, 3, 2, false, EPI, ACT, FMT>(a, s);   // 64x64, three-slot ring, 2+ WG/CU
-        case 2: return launch_cfg<1, 2, 64, 2, 2, false, EPI, ACT, FMT>(a, s);   // 64x128, two-slot ring
-        case 3: return launch_cfg<2, 2, 64, 2, 2, false, EPI, ACT, FMT>(a, s);   // 128x128, 2 WG/CU
-        // (the projection's dual-output fp32 staging does not fit eight private regions into the two-slot ring: it keeps the four-wave forms)
-        case 5:
-            if constexpr (EPI == EPI_PROJ) return launch_cfg<2, 2, 64, 2, 2, false, EPI, ACT, FMT>(a, s);
-            else return launch_cfg<1, 2, 64, 2, 2, false, EPI, ACT, FMT, 4, 2>(a, s);   // 128x128 on EIGHT waves (4 x 2, wave tile 32x64), 2 WG/CU
-        case 6:
-            if constexpr (EPI == EPI_PROJ) return launch_cfg<2, 3, 64, 2, 2, false, EPI, ACT, FMT>(a, s);
-            else return launch_cfg<1, 3, 64, 2, 2, false, EPI, ACT, FMT, 4, 2>(a, s);   // 128x192 on eight waves (wave tile 32x96), 2 WG/CU
+static GemmKernel resolve_hip(int tile, const GemmArgs& a) {
+    using namespace kern;
+    switch (tile) {
+        case 3: return gemm_bf16_kernel<2, 2, 64, 2, 2, false, EPI, ACT, FMT>();   // 128x128, 2 WG/CU
+        case 4: return gemm_bf16_kernel<2, 3, 64, 2, 2, false, EPI, ACT, FMT>();   // 128x192, 2 WG/CU
         case 10:
             if constexpr (EPI == EPI_BF16) {
                 // whole tiles, more than one round, at least 3 K steps: the persistent kernel with cross-tile prefetch
                 if (a.tune_persist >= 0 && (a.M - a.m_begin) % 256 == 0 && a.N % 256 == 0 && a.K >= 96 && (long)((a.M - a.m_begin) / 256) * (a.N / 256) > 256)
-                    return launch_cfg8p<ACT, FMT>(a, s);
+                    return gemm8p_bf16_kernel<ACT, FMT>();
             }
-            return launch_cfg8<4, 2, 2, 4, EPI, ACT, FMT>(a, s);                 // 256x256, 8 waves staggered
-        case 11: return launch_cfg8<2, 3, 4, 2, EPI, ACT, FMT>(a, s);            // 256x192, 8 waves staggered
-        case 13: case 14: case 15: case 16: case 17: case 46: case 47:
-            // the v_mfma_f32_16x16x32 family (gemm_asm16.hip): the 16-bit-output launches by default (launch_f), any instantiated epilogue when forced
-            if (gemm_asm16_has_tile(EPI, a, cfg)) { GemmArgs b = a; b.tune_cfg = cfg + 1; return launch_gemm_asm16(EPI, b, s); }
-            break;
-        case 51: case 57: case 60: case 61: case 62: case 63: case 64: case 65: case 66: case 67: case 68: case 69: case 70: case 71: case 72: case 73: case 74: case 75: case 76: case 77: case 78: case 80: case 81: case 82: case 83: case 85: case 86: case 87: case 88: case 89: case 90: case 91: case 92: case 93: case 94: case 95: case 96: case 97: case 98:
-            // hand-scheduled K loop; a forced tile without an instantiation for this epilogue falls back to 128x192 (sylber_hip.h)
-            if (gemm_asm_has_tile(EPI, a, cfg) || (cfg != 51 && cfg != 57 && cfg != 60 && cfg != 80 && cfg != 85 && cfg != 86 && cfg != 90 && cfg != 91 && cfg != 95 && cfg != 96 && cfg != 97 && gemm_asm_applicable(EPI, a))) {
-                GemmArgs b = a; b.tune_cfg = cfg + 1; return launch_gemm_asm(EPI, b, s);
-            }
-            break;
-        case 40: if constexpr (FMT == FMT_BF16) return launch_cfg8u<EPI, ACT, FMT>(a, s); break;                     // unstaggered 8-wave 256x256
-        case 41: if constexpr (FMT == FMT_BF16 && EPI == EPI_BF16 && ACT == 0) return launch_cfg8u<EPI, ACT, FMT, true>(a, s); break;   // its trace
-        case 30: if constexpr (FMT == FMT_BF16 && (EPI == EPI_BF16 || EPI == EPI_F32_RESLN)) return launch_cfg8<4, 2, 2, 4, EPI, ACT, FMT, 10>(a, s); break;   // trace
-        default: break;
+            return gemm8_bf16_kernel<4, 2, 2, 4, EPI, ACT, FMT>();                 // 256x256, 8 waves staggered
     }
-    return launch_cfg<2, 3, 64, 2, 2, false, EPI, ACT, FMT>(a, s);              // 128x192, 2 WG/CU
+    // (the split-operand mode instantiates the three tile shapes above -- what its cost model picks -- and nothing else)
+    if constexpr (FMT != FMT_SPLIT) switch (tile) {
+        case 0: return gemm_bf16_kernel<4, 2, 64, 3, 1, false, EPI, ACT, FMT>();   // 256x128, 3-slot ring, 1 WG/CU
+        // round 6: the launches of a call on one or two clips are chains of K steps on a few LONE workgroups (fewer tiles than CUs), each step waiting for LDS-DMA pieces
+        // issued half a step earlier.  64-row tiles put four times the workgroups on the idle CUs, and a THREE-slot ring lets a step's pieces be one and a half steps old:
+        // out-proj of one clip 12.5 -> 7.0 us, FFN2 25.5 -> 18.5, q,k,v 9.4 -> 7.9 (profiles/r06_small_tiles.md).  Same chain per output element: bit-identical.
+        case 1: return gemm_bf16_kernel<1, 1, 64, 3, 2, false, EPI, ACT, FMT>();   // 64x64, three-slot ring, 2+ WG/CU
+        case 2: return gemm_bf16_kernel<1, 2, 64, 2, 2, false, EPI, ACT, FMT>();   // 64x128, two-slot ring
+        // (the projection's dual-output fp32 staging does not fit eight private regions into the two-slot ring: it keeps the four-wave forms)
+        case 5:
+            if constexpr (EPI == EPI_PROJ) return gemm_bf16_kernel<2, 2, 64, 2, 2, false, EPI, ACT, FMT>();
+            else return gemm_bf16_kernel<1, 2, 64, 2, 2, false, EPI, ACT, FMT, 4, 2>();   // 128x128 on EIGHT waves (4 x 2, wave tile 32x64), 2 WG/CU
+        case 6:
+            if constexpr (EPI == EPI_PROJ) return gemm_bf16_kernel<2, 3, 64, 2, 2, false, EPI, ACT, FMT>();
+            else return gemm_bf16_kernel<1, 3, 64, 2, 2, false, EPI, ACT, FMT, 4, 2>();   // 128x192 on eight waves (wave tile 32x96), 2 WG/CU
+        case 11: return gemm8_bf16_kernel<2, 3, 4, 2, EPI, ACT, FMT>();            // 256x192, 8 waves staggered
+        case 40: if constexpr (FMT == FMT_BF16) return gemm8u_bf16_kernel<EPI, ACT, FMT>(); break;                     // unstaggered 8-wave 256x256
+        case 41: if constexpr (FMT == FMT_BF16 && EPI == EPI_BF16 && ACT == 0) return gemm8u_bf16_kernel<EPI, ACT, FMT, true>(); break;   // its trace
+        case 30: if constexpr (FMT == FMT_BF16 && (EPI == EPI_BF16 || EPI == EPI_F32_RESLN)) return gemm8_bf16_kernel<4, 2, 2, 4, EPI, ACT, FMT, 10>(); break;   // trace
+    }
+    return {};
+}
+
+// operand format (GemmArgs::fmt): the fp16 instantiations exist for every epilogue, the split16 ones for what the split16 forward launches: erf-GELU
+// 16-bit outputs (convs, FFN1), the projection, q/k/v, the residual GEMMs, and the plain fp32 output of the op-level test entry point
+template <int EPI, int ACT>
+static GemmKernel resolve_hip_fmt(int tile, const GemmArgs& a) {
+    if (a.fmt == FMT_SPLIT) {
+        if constexpr ((EPI == EPI_BF16 && ACT == ACT_GELU_ERF7) || (EPI == EPI_F32 && ACT == ACT_NONE) || EPI == EPI_F32_RESLN ||
+                      EPI == EPI_QK || EPI == EPI_PROJ)
+            return resolve_hip<EPI, ACT, FMT_SPLIT>(tile, a);
+        else return {};
+    }
+    if constexpr (ACT == ACT_GELU_ERF7) return {};          // activation 3 exists for the split16 format only
+    else return a.fmt == FMT_F16 ? resolve_hip<EPI, ACT, FMT_F16>(tile, a) : resolve_hip<EPI, ACT, FMT_BF16>(tile, a);
+}
+
+GemmKernel gemm_hip_resolve(int tile, int epi, const GemmArgs& a) {
+    switch (epi) {
+        case EPI_BF16:
+            if (a.act == 1) return resolve_hip_fmt<EPI_BF16, 1>(tile, a);
+            if (a.act == 2) return resolve_hip_fmt<EPI_BF16, 2>(tile, a);
+            if (a.act == 3) return resolve_hip_fmt<EPI_BF16, 3>(tile, a);
+            return resolve_hip_fmt<EPI_BF16, 0>(tile, a);
+        case EPI_F32:
+            if (a.act == 1) return resolve_hip_fmt<EPI_F32, 1>(tile, a);
+            if (a.act == 2) return resolve_hip_fmt<EPI_F32, 2>(tile, a);
+            return resolve_hip_fmt<EPI_F32, 0>(tile, a);
+        case EPI_F32_RES: return resolve_hip_fmt<EPI_F32_RES, 0>(tile, a);
+        case EPI_F32_RESLN: return resolve_hip_fmt<EPI_F32_RESLN, 0>(tile, a);
+        case EPI_QK: return resolve_hip_fmt<EPI_QK, 0>(tile, a);
+        case EPI_PROJ: return resolve_hip_fmt<EPI_PROJ, 0>(tile, a);
+    }
+    return {};
+}
+
+// the instantiation behind tile id `id`, from the family that owns it (gemm_tiles.h); none: the caller takes the 128x192 fallback (sylber_hip.h)
+static GemmKernel tile_kernel(int id, int epi, const GemmArgs& a) {
+    const GemmTile* t = gemm_tile(id);
+    if (!t) return {};
+    return t->family == FAM_ASM ? gemm_asm_resolve(id, epi, a) : (t->family == FAM_ASM16 ? gemm_asm16_resolve(id, epi, a) : gemm_hip_resolve(id, epi, a));
 }
 
 // Tile-shape choice, measured on MI355X with tools/gemm_bench.py (random operands):
@@ -965,13 +997,19 @@ static int launch_tile(int cfg, const GemmArgs& a, hipStream_t s) {
 //     3/4-size tiles at 192 rows)
 //   * a row split: rows of the full rounds on the chosen tile, rows [M1, M) as a second launch on another tile (GemmArgs::m_begin).
 //     Measured not to pay with the tiles that exist (see below): kept as a forced option and as the test vehicle of m_begin.
-// The tile cost model (shared by launch_f and the CPU-tier regression test through sylber_debug_gemm_pick): configuration table and cost of
-// configuration i over `rows` rows of launch `a`, for epilogue EPI and operand format FMT.
-struct TileCfg { int id, bm, bn, per_cu; double eff, pr0; };
+// The tile cost model (shared by gemm_plan and the CPU-tier regression test through sylber_debug_gemm_pick): configuration table and cost of
+// configuration i over `rows` rows of launch `a`, for epilogue EPI and operand format FMT.  A candidate = a tile id with its measured ratings;
+// its geometry is the tile table's.
+struct TileCfg {
+    int id, bm, bn, per_cu; double eff, pr0;
+    TileCfg() : id(-1), bm(256), bn(256), per_cu(1), eff(1.0), pr0(1.0) {}
+    TileCfg(int id_, double eff_, double pr0_) : TileCfg(*gemm_tile(id_), eff_, pr0_) {}
+    TileCfg(const GemmTile& t, double eff_, double pr0_) : id(t.id), bm(t.bm), bn(t.bn), per_cu(t.per_cu), eff(eff_), pr0(pr0_) {}
+};
 struct TileModel {
     static constexpr int NCFG = 11;
     TileCfg cfgs[NCFG];
-    bool asm_ok, r5, m16, split;
+    bool r5, m16;
     int EPI;
     const GemmArgs* a;
     TileModel(int EPI_, int FMT, const GemmArgs& a_) : EPI(EPI_), a(&a_) {
@@ -979,8 +1017,6 @@ struct TileModel {
         // 80 / 90: the hand-scheduled 4-wave kernels (gemm_asm.hip).  Their K loop runs ~25 % above the 8-wave kernel's, but one
         // wave per SIMD leaves a tile's prologue and epilogue uncovered (~9 us + ~5 us of GELU against a 17 us K = 768 loop), so
         // they are rated for long K only (same-box tools/gemm_bench.py: conv1-4 +3-10 %, FFN2 +7 %, K = 768 shapes -5-20 %).
-        split = FMT == FMT_SPLIT;
-        asm_ok = FMT != FMT_SPLIT && gemm_asm_applicable(EPI, a) && a.K >= 256;
         const bool long_k = a.K >= 1024;
         // 95: the same loop on eight waves (two per SIMD share the epilogue's VALU work): the GELU GEMMs, K = 768 included.
         // 85 / 91 / 97 = 80 / 90 / 95 with three ring slots for X (bf16 only): never slower hot, 5-15 % faster on cold activations
@@ -1009,56 +1045,45 @@ struct TileModel {
         // (two-per-CU kernels: q,k,v's 4.4 rounds cost 4.4 round-times, but FFN2's 0.75 of a round costs 0.90 of one and 1.47 rounds cost 1.6: the same
         //  pr0 as the persistent tiles fits all three within 5 %; charging them proportionally made the model take 128x192 for FFN2 where tile 51 is 10-15 % faster)
         const double pa = r5 ? 1.0 : (thr ? 0.0 : GEMM_PR0_ASM), p2 = r5 ? 1.0 : (thr ? 0.0 : GEMM_PR0_ASM), p10 = thr ? 0.0 : 1.0;
-        const TileCfg init[NCFG] = {{3, 128, 128, 2, r5 ? 0.93 : 0.95, p2}, {4, 128, 192, 2, e4, p2}, {10, 256, 256, 1, e10, p10},
-                                {x3 ? 85 : 80, 256, 256, 1, long_k ? (r5 ? 1.28 : 1.20) : (!r5 && EPI == EPI_QK ? 1.00 : 1.10), pa},   // (q,k,v on 85: 0.795 vs 0.691 ms on 128x192 at 24 x 15 s)
-                                {91, 256, 192, 1, long_k ? 1.10 : 1.04, pa},
-                                {x3 ? 97 : 95, 256, 256, 1, long_k ? 1.32 : 1.27, pa}, {86, 256, 128, 1, 1.10, pa},
-                                {51, 192, 192, 1, (long_k ? 1.10 : 1.04) * GEMM_H192_EFF, pa}, {57, 192, 256, 1, (long_k ? 1.32 : 1.27) * GEMM_H192_EFF, pa},
+        const TileCfg init[NCFG] = {{3, r5 ? 0.93 : 0.95, p2}, {4, e4, p2}, {10, e10, p10},
+                                {x3 ? 85 : 80, long_k ? (r5 ? 1.28 : 1.20) : (!r5 && EPI == EPI_QK ? 1.00 : 1.10), pa},   // (q,k,v on 85: 0.795 vs 0.691 ms on 128x192 at 24 x 15 s)
+                                {91, long_k ? 1.10 : 1.04, pa},
+                                {x3 ? 97 : 95, long_k ? 1.32 : 1.27, pa}, {86, 1.10, pa},
+                                {51, (long_k ? 1.10 : 1.04) * GEMM_H192_EFF, pa}, {57, (long_k ? 1.32 : 1.27) * GEMM_H192_EFF, pa},
                                 // 64-row tiles (round 6): a quarter / half of the 128x128 tile per workgroup at 0.34 / 0.50 of its per-output efficiency -- they only ever win where a
                                 // launch has fewer tiles than the chip has workgroup slots (one to four clips), which is what they exist for (fitted: profiles/r06_small_tiles.md §3)
-                                {1, 64, 64, 2, 0.34, p2}, {2, 64, 128, 2, 0.50, p2}};
+                                {1, 0.34, p2}, {2, 0.50, p2}};
         for (int i = 0; i < NCFG; ++i) cfgs[i] = init[i];
         // The 16-bit-output GEMMs (EPI_BF16, plain or GELU: conv1-5 and FFN1, 46 % of the 32 x 10 s forward) run on the v_mfma_f32_16x16x32 FAMILY
         // (gemm_asm16.hip; same-box +2.7 ... +7.2 % per launch, profiles/r06_mfma16_loop.md): 13 / 14 = the two-per-CU 128x128 / 128x192 kernels, 47 =
         // tile 97's geometry, 46 = its 192-row sibling.  The family adds 32-k blocks to an element's fp32 chain where the 32x32x16 kernels add 16-k
         // blocks, so the ROLE moves as a whole: every tile a batch shape can pick for these launches is a member, and results stay independent of
         // the batch shape.  tune_mfma16 = -1 (SYLBER_OPT_GEMM_MFMA16) puts the role back on the 32x32x16 kernels.
-        m16 = EPI == EPI_BF16 && FMT != FMT_SPLIT && (a.act == 0 || a.act == 1) && a.tune_mfma16 >= 0 && gemm_asm16_has_tile(EPI, a, 15);
+        m16 = EPI == EPI_BF16 && a.tune_mfma16 >= 0 && gemm_asm16_resolve(GEMM_M16_DEFAULT, EPI, a).launch;
         if (m16) {
             // small tiles: 15 = the 128x128 tile on EIGHT waves (+3 ... +21 % over its four-wave form 13 on every shape of the role: a 16-cycle-MFMA loop is bound by
             // what one wave has to issue, profiles/r06_small_tiles.md); 14 = 128x192 on four waves, rated below it (it wins only where 512 of its tiles are exactly
             // one round: 8 clips).  13 and 16 (128x192 on eight waves: 136 VGPRs, one workgroup per CU) stay forced-only members.
             // 17 = 64x64 on a three-slot ring: the launches of one or two clips (the family's form of tile 1 below)
-            const TileCfg fam[5] = {{15, 128, 128, 2, 1.00, p2}, {14, 128, 192, 2, 0.88, p2}, {47, 256, 256, 1, long_k ? 1.32 : 1.27, pa},
-                                    {46, 192, 256, 1, (long_k ? 1.32 : 1.27) * GEMM_H192_EFF, pa}, {17, 64, 64, 2, 0.36, p2}};
-            for (int i = 0; i < NCFG; ++i) cfgs[i] = i < 5 ? fam[i] : TileCfg{-1, 256, 256, 1, 1.0, 1.0};
+            const TileCfg fam[5] = {{15, 1.00, p2}, {14, 0.88, p2}, {47, long_k ? 1.32 : 1.27, pa},
+                                    {46, (long_k ? 1.32 : 1.27) * GEMM_H192_EFF, pa}, {17, 0.36, p2}};
+            for (int i = 0; i < NCFG; ++i) cfgs[i] = i < 5 ? fam[i] : TileCfg();
         }
     }
     // the member of the 16x16x32 family that stands in for a FORCED tile id (SYLBER_OPT_GEMM_TILE is per handle: the parity tests force one id on
     // every launch of a forward and expect the same bits from each; on the role's launches every id maps to a member of the same shape class)
     int family_member(int cfg) const {
-        const GemmArgs& a = *this->a;
-        int m;
-        switch (cfg) {
-            case 13: case 14: case 15: case 16: case 17: case 46: case 47: m = cfg; break;
-            case 1: m = 17; break;
-            case 2: case 3: case 5: m = 15; break;
-            case 6: m = 16; break;
-            case 51: case 57: m = 46; break;
-            case 10: case 30: case 40: case 41: case 60: case 80: case 85: case 95: case 97: case 98: m = 47; break;
-            case 4: case 11: case 90: case 91: case 96: case 0: case 86: m = 14; break;
-            default: m = 15; break;
-        }
-        return gemm_asm16_has_tile(EPI, a, m) ? m : 15;
+        const GemmTile* t = gemm_tile(cfg);
+        const int m = t ? t->m16 : GEMM_M16_DEFAULT;
+        return gemm_asm16_resolve(m, EPI, *a).launch ? m : GEMM_M16_DEFAULT;
     }
     double cost_of(int i, long rows) const {
         const GemmArgs& a = *this->a;
         const TileCfg& c = cfgs[i];
         if (c.id < 0) return 1e300;
-        if (m16) { if (!gemm_asm16_has_tile(EPI, a, c.id) || (c.id == 17 && a.tune_model == 6)) return 1e300; }
-        else if (c.id == 1 || c.id == 2) { if (split || a.tune_model == 6) return 1e300; }    // (the split16 mode instantiates three tile shapes; model 6 = the round-6a choice, A/B)
-        else if (i >= 3 && (!asm_ok || !gemm_asm_has_tile(EPI, a, c.id))) return 1e300;   // only tiles that exist for this epilogue / format
-        if ((c.id == 51 || c.id == 57 || c.id == 46) && (a.tune_h192 < 0 || r5)) return 1e300;
+        if (c.bm == 64 && a.tune_model == 6) return 1e300;                              // (model 6 = the round-6a choice, before the 64-row tiles: A/B)
+        if (c.bm == 192 && (a.tune_h192 < 0 || r5)) return 1e300;
+        if (!tile_kernel(c.id, EPI, a).launch) return 1e300;                            // only tiles that exist for this epilogue / format / K
         const long tm = (rows + c.bm - 1) / c.bm, tn = (a.N + c.bn - 1) / c.bn;
         if (c.id == 86 && tm * tn < 192) return 1e300;      // (measured for launches that fill the chip; small batches keep their tiles)
         const long slots = 256L * c.per_cu, tiles = tm * tn;
@@ -1085,80 +1110,60 @@ struct TileModel {
         return best;
     }
 };
-int gemm_pick_tile(int epi, const GemmArgs& a) {
-    TileModel m(epi, a.fmt, a);
-    double c;
-    return m.cfgs[m.pick(a.M - a.m_begin, &c)].id;
+// What a launch runs.  The tile is the cost model's, or the forced one (on the 16x16x32 family's launches: its stand-in member).
+// Row split: rows of the full rounds on that tile, rows [M1, M) as a second launch on another tile (GemmArgs::m_begin).  FORCED ONLY
+// (tune_tail > 0): measured (profiles/r06_tail_policy.md), a smaller tile alone on its CU runs its K loop at the same wall time per step as a
+// big one (a lone 128x192x3072 tile: 66 us; two co-resident: 80 us), so re-tiling the tail buys nothing and the second launch costs 3-5 us;
+// with two batches in flight it is a loss (8 x 60 s: 8.76 -> 9.15 ms).  What does fill a partial round at full CU efficiency is a second tile
+// HEIGHT: tiles 51 / 57 above.
+static bool plan_add(GemmPlan& p, int id, int epi, const GemmArgs& g) {
+    GemmKernel k = tile_kernel(id, epi, g);
+    if (!k.launch) k = gemm_hip_resolve(GEMM_TILE_FALLBACK, epi, g);
+    if (!k.launch) { syl_set_error("launch_gemm_bf16", "no kernel instantiation for this epilogue / activation / operand format"); p.n = 0; return false; }
+    p.tile[p.n] = id; p.k[p.n] = k; p.a[p.n] = g;
+    ++p.n;
+    return true;
 }
 
-template <int EPI, int ACT, int FMT>
-static int launch_f(const GemmArgs& a, hipStream_t s) {
-    const TileModel tm_(EPI, FMT, a);
-    const TileCfg* cfgs = tm_.cfgs;
-    constexpr int NCFG = TileModel::NCFG;
-    auto cost_of = [&](int i, long rows) -> double { return tm_.cost_of(i, rows); };
-    auto pick = [&](long rows, double* cost) -> int { return tm_.pick(rows, cost); };
+GemmPlan gemm_plan(int epi, const GemmArgs& a) {
+    GemmPlan p = {};
+    if (a.K % 64 != 0 || a.K <= 0 || a.M <= 0 || a.N <= 0) { syl_set_error("launch_gemm_bf16", "K must be a positive multiple of 64"); return p; }
+    if (a.N % 4 != 0) { syl_set_error("launch_gemm_bf16", "N must be a multiple of 4"); return p; }
+    const TileModel tm(epi, a.fmt, a);
     const long rows = a.M - a.m_begin;
-    double whole_cost;
-    const int best = pick(rows, &whole_cost);
-    int cfg = cfgs[best].id;
-    if (a.tune_cfg > 0) cfg = tm_.m16 ? tm_.family_member(a.tune_cfg - 1) : a.tune_cfg - 1;   // per-call override (sylber_set_option / parity tests)
-    // ---- row split: rows of the full rounds on the chosen tile, the rest re-tiled.  FORCED ONLY (tune_tail > 0): measured (profiles/r06_tail_policy.md),
-    // a smaller tile alone on its CU runs its K loop at the same wall time per step as a big one (a lone 128x192x3072 tile: 66 us; two
-    // co-resident: 80 us), so re-tiling the tail buys nothing and the second launch costs 3-5 us; with two batches in flight it is a loss
-    // (8 x 60 s: 8.76 -> 9.15 ms).  What does fill a partial round at full CU efficiency is a second tile HEIGHT: tiles 51 / 57 above.
+    double cost;
+    int cfg = tm.cfgs[tm.pick(rows, &cost)].id;
+    if (a.tune_cfg > 0) cfg = tm.m16 ? tm.family_member(a.tune_cfg - 1) : a.tune_cfg - 1;   // per-call override (sylber_set_option / parity tests)
     if (a.tune_tail > 0 && a.m_begin == 0) {
-        int bi = -1;
-        for (int i = 0; i < NCFG; ++i) if (cfgs[i].id == cfg) bi = i;
-        if (bi >= 0 && cost_of(bi, rows) < 1e299) {
-            const TileCfg& c = cfgs[bi];
-            const long tm = (rows + c.bm - 1) / c.bm, tn = (a.N + c.bn - 1) / c.bn, slots = 256L * c.per_cu;
-            const long full = (tm * tn) / slots, rem = tm * tn - full * slots;
-            const long main_tiles_m = full * slots / tn;        // whole row tiles inside the full rounds
-            const long M1 = main_tiles_m * c.bm;
-            if (full >= 1 && rem > 0 && M1 > 0 && M1 < a.M) {
-                double tail_cost = 1e300;
-                int ti = -1;
-                if (a.tune_tail > 0) { for (int i = 0; i < NCFG; ++i) if (cfgs[i].id == a.tune_tail - 1) ti = i; if (ti >= 0) tail_cost = cost_of(ti, a.M - M1); }
-                else ti = pick(a.M - M1, &tail_cost);
-                // a second launch costs ~GEMM_SPLIT_US of an idle chip: in the model's units (output elements per CU at K) that is
-                // GEMM_SPLIT_US x (MACs a CU retires per us) / K
-                const double split_cost = (double)full * c.per_cu * c.bm * c.bn / c.eff + tail_cost + GEMM_SPLIT_US * GEMM_CU_MACS_PER_US / a.K;
-                const double unsplit = a.tune_cfg > 0 ? cost_of(bi, rows) : whole_cost;
-                if (ti >= 0 && tail_cost < 1e299 && (a.tune_tail > 0 || split_cost < 0.95 * unsplit)) {
-                    GemmArgs head = a, tail = a;
-                    head.M = (int)M1; head.tune_tail = -1;
-                    tail.m_begin = (int)M1; tail.tune_tail = -1; tail.tune_cfg = 0;
-                    if (launch_tile<EPI, ACT, FMT>(cfg, head, s) != 0) return 1;
-                    return launch_tile<EPI, ACT, FMT>(cfgs[ti].id, tail, s);
-                }
+        int bi = -1, ti = -1;
+        for (int i = 0; i < TileModel::NCFG; ++i) {
+            if (tm.cfgs[i].id == cfg) bi = i;
+            if (tm.cfgs[i].id == a.tune_tail - 1) ti = i;
+        }
+        if (bi >= 0 && ti >= 0 && tm.cost_of(bi, rows) < 1e299) {
+            const TileCfg& c = tm.cfgs[bi];
+            const long tiles_m = (rows + c.bm - 1) / c.bm, tn = (a.N + c.bn - 1) / c.bn, slots = 256L * c.per_cu;
+            const long full = (tiles_m * tn) / slots, rem = tiles_m * tn - full * slots;
+            const long M1 = full * slots / tn * c.bm;           // whole row tiles inside the full rounds
+            if (full >= 1 && rem > 0 && M1 > 0 && M1 < a.M && tm.cost_of(ti, a.M - M1) < 1e299) {
+                GemmArgs head = a, tail = a;
+                head.M = (int)M1; head.tune_tail = -1;
+                tail.m_begin = (int)M1; tail.tune_tail = -1; tail.tune_cfg = 0;
+                if (plan_add(p, cfg, epi, head)) plan_add(p, tm.cfgs[ti].id, epi, tail);
+                return p;
             }
         }
     }
-    return launch_tile<EPI, ACT, FMT>(cfg, a, s);
+    plan_add(p, cfg, epi, a);
+    return p;
 }
 
-// operand format (GemmArgs::fmt): the fp16 instantiations exist for the epilogues the fp16 forward uses
-template <int EPI, int ACT>
-static int launch_t(const GemmArgs& a, hipStream_t s) {
-    if (a.fmt == FMT_SPLIT) {
-        // what the split16 forward launches: erf-GELU 16-bit outputs (convs, FFN1), the projection, q/k/v, the residual
-        // GEMMs, and the plain fp32 output of the op-level test entry point
-        if constexpr ((EPI == EPI_BF16 && ACT == ACT_GELU_ERF7) || (EPI == EPI_F32 && ACT == ACT_NONE) || EPI == EPI_F32_RESLN ||
-                      EPI == EPI_QK || EPI == EPI_PROJ)
-            return launch_f<EPI, ACT, FMT_SPLIT>(a, s);
-        else { syl_set_error("launch_gemm_bf16", "this epilogue has no split16 instantiation"); return 1; }
-    }
-    if constexpr (ACT == ACT_GELU_ERF7) { syl_set_error("launch_gemm_bf16", "activation 3 exists for the split16 format only"); return 1; }
-    else {
-        if (a.fmt == FMT_F16) return launch_f<EPI, ACT, FMT_F16>(a, s);
-        return launch_f<EPI, ACT, FMT_BF16>(a, s);
-    }
+int gemm_pick_tile(int epi, const GemmArgs& a) {
+    const GemmPlan p = gemm_plan(epi, a);
+    return p.n ? p.tile[0] : -1;
 }
 
 int launch_gemm_bf16(int epi, const GemmArgs& a, hipStream_t s) {
-    if (a.K % 64 != 0 || a.K <= 0 || a.M <= 0 || a.N <= 0) { syl_set_error("launch_gemm_bf16", "K must be a positive multiple of 64"); return 1; }
-    if (a.N % 4 != 0) { syl_set_error("launch_gemm_bf16", "N must be a multiple of 4"); return 1; }
     if (a.fmt == FMT_SPLIT) {
         // the lo planes are reached through the 32-bit scalar offset of the tile's buffer descriptor (unsigned, range-checked
         // against 2^32 - 1 records): plane offset + the largest in-tile offset must stay below 2^32 or the X.lo / W.lo passes
@@ -1170,21 +1175,9 @@ int launch_gemm_bf16(int epi, const GemmArgs& a, hipStream_t s) {
             return 1;
         }
     }
-    switch (epi) {
-        case EPI_BF16:
-            if (a.act == 1) return launch_t<EPI_BF16, 1>(a, s);
-            if (a.act == 2) return launch_t<EPI_BF16, 2>(a, s);
-            if (a.act == 3) return launch_t<EPI_BF16, 3>(a, s);
-            return launch_t<EPI_BF16, 0>(a, s);
-        case EPI_F32:
-            if (a.act == 1) return launch_t<EPI_F32, 1>(a, s);
-            if (a.act == 2) return launch_t<EPI_F32, 2>(a, s);
-            return launch_t<EPI_F32, 0>(a, s);
-        case EPI_F32_RES: return launch_t<EPI_F32_RES, 0>(a, s);
-        case EPI_F32_RESLN: return launch_t<EPI_F32_RESLN, 0>(a, s);
-        case EPI_QK: return launch_t<EPI_QK, 0>(a, s);
-        case EPI_PROJ: return launch_t<EPI_PROJ, 0>(a, s);
-    }
-    syl_set_error("launch_gemm_bf16", "unknown epilogue");
-    return 1;
+    const GemmPlan p = gemm_plan(epi, a);
+    if (p.n == 0) return 1;
+    for (int i = 0; i < p.n; ++i)
+        if (p.k[i].launch(p.a[i], s) != 0) return 1;
+    return 0;
 }

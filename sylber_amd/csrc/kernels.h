@@ -51,9 +51,9 @@ struct GemmArgs {
     int kpat;                     // 1: the 3-tap stride-2 conv layers' chunk-major K order (K = 1536, 512 channels): W is packed
                                   // [out][64-channel chunk][tap 0, 2, 1][64] and the X byte offset of K position o follows tap3_offset(o)
     int tune_pre;                 // residual GEMMs on tile 91: -1 no residual prefetch in the K loop, 1..3 fragment columns prefetched, 0 default
-    int m_begin;                  // the launch covers rows [m_begin, M) (0 = all): the tail launch of a row-split GEMM (launch_f, "tail policy");
+    int m_begin;                  // the launch covers rows [m_begin, M) (0 = all): the tail launch of a row-split GEMM (gemm_plan, "tail policy");
                                   // row indices stay absolute everywhere (operands, epilogues, the row -> (utterance, frame) maps)
-    int tune_model;               // 5: the round-5 cost model of launch_f (A/B switch); 0: the current one
+    int tune_model;               // 5: the round-5 cost model of gemm_plan (A/B switch); 0: the current one
     int tune_h192;                // -1: the cost model leaves the 192-row tiles (51 / 57) out (A/B switch)
     int tune_mfma16;              // 0 (default): the 16-bit-output GEMMs (EPI_BF16: conv1-5, FFN1) run on the v_mfma_f32_16x16x32 family (tiles 13 / 14 / 46 / 47,
                                   // gemm_asm16.hip); -1: on the 32x32x16 kernels of rounds 1-6a (A/B switch; the two families group an element's fp32 chain differently)
@@ -61,18 +61,22 @@ struct GemmArgs {
 };
 
 int launch_gemm_bf16(int epi, const GemmArgs& a, hipStream_t s);
+// One kernel instantiation: its launch wrapper and a static name that spells the __global__ template with every template argument.
+// Each kernel family states ONCE which instantiation serves (tile id, epilogue, launch) -- every run-time condition included -- in its
+// resolver; {nullptr, nullptr} = the family has none.  Host arithmetic only.
+struct GemmKernel { int (*launch)(const GemmArgs&, hipStream_t); const char* name; };
+GemmKernel gemm_hip_resolve(int tile, int epi, const GemmArgs& a);     // the hipcc kernels (gemm_bf16.hip)
+GemmKernel gemm_asm_resolve(int tile, int epi, const GemmArgs& a);     // the hand-scheduled 32x32x16 loops (gemm_asm.hip)
+GemmKernel gemm_asm16_resolve(int tile, int epi, const GemmArgs& a);   // the v_mfma_f32_16x16x32 family (gemm_asm16.hip)
+// what launch_gemm_bf16 does with a launch: one kernel over rows [a[0].m_begin, a[0].M), or two when GemmArgs::tune_tail forces a row
+// split; tile[] = the ids the kernels were resolved from (tile[0] with tune_cfg = 0: the cost model's pick).  n = 0: refused (syl_set_error)
+struct GemmPlan { int n; int tile[2]; GemmKernel k[2]; GemmArgs a[2]; };
+GemmPlan gemm_plan(int epi, const GemmArgs& a);
 // the tile id launch_gemm_bf16's cost model picks for this launch (host arithmetic only: no GPU needed; tests/test_abi.py pins the headline shapes)
 int gemm_pick_tile(int epi, const GemmArgs& a);
 // residual GEMM + the LayerNorm that follows it in one launch (gemm_rowln.hip): N = 768, full rows per workgroup
 bool gemm_rowln_applicable(const GemmArgs& a);
 int launch_gemm_rowln(const GemmArgs& a, hipStream_t s);
-// 256x256 tile, four waves x 128x128, K loop scheduled by hand (gemm_asm.hip, tile id 60)
-bool gemm_asm_applicable(int epi, const GemmArgs& a);
-bool gemm_asm_has_tile(int epi, const GemmArgs& a, int tile);
-int launch_gemm_asm(int epi, const GemmArgs& a, hipStream_t s);
-// tile 47 (gemm_asm16.hip): tile 97's geometry on v_mfma_f32_16x16x32; forced only (its own fp32 grouping over K)
-bool gemm_asm16_has_tile(int epi, const GemmArgs& a, int tile);
-int launch_gemm_asm16(int epi, const GemmArgs& a, hipStream_t s);
 
 // MXFP8 GEMM (gemm_mxfp8.hip): e4m3 operands [rows][K] with one E8M0 scale per 32 elements along K stored
 // K-pair-major [K/64][rows_pitch][2] (common.h mx_scale_index; pitches are multiples of 8, and the scale arrays of

@@ -520,6 +520,30 @@ extern "C" int sylber_debug_gemm_pick(int32_t M, int32_t N, int32_t K, int32_t e
     return gemm_pick_tile(epi, g);
 }
 
+// which kernel instantiation(s) launch_gemm_bf16 resolves a launch to (gemm_plan; host arithmetic only, no device is touched): the launch as
+// sylber_debug_gemm_pick describes it (fmt 2 = split16), `tile` in the encoding of the op-level entry points (decode_tile), h192 / pre / tail =
+// GemmArgs::tune_h192 / tune_pre / tune_tail (tail 0: what `tile` encodes).  One line per launch of the plan goes to buf: "<first row> <end row>
+// <kernel template>[<its template arguments>]".  Returns the number of launches; 0 = refused (sylber_last_error), -1 = buf too small
+extern "C" int sylber_debug_gemm_resolve(int32_t M, int32_t N, int32_t K, int32_t epi, int32_t act, int32_t fmt, int32_t kpat, int32_t tile,
+                                         int32_t model, int32_t h192, int32_t pre, int32_t tail, char* buf, int32_t cap) {
+    GemmArgs g = {};
+    g.M = M; g.N = N; g.K = K; g.act = act; g.fmt = fmt; g.kpat = kpat; g.tune_model = model; g.tune_h192 = h192; g.tune_pre = pre;
+    decode_tile(tile, g);
+    if (tail) g.tune_tail = tail;
+    const GemmPlan p = gemm_plan(epi, g);
+    int used = 0;
+    for (int i = 0; i < p.n; ++i) {
+        // "GemmKernel kern::<template>() [<arguments>]" (__PRETTY_FUNCTION__) -> "<template>[<arguments>]"
+        const char* nm = strstr(p.k[i].name, "kern::");
+        nm = nm ? nm + 6 : p.k[i].name;
+        const char* par = strstr(nm, "() ");
+        const int w = snprintf(buf + used, (size_t)(cap - used), "%d %d %.*s%s\n", p.a[i].m_begin, p.a[i].M, par ? (int)(par - nm) : (int)strlen(nm), nm, par ? par + 3 : "");
+        if (w < 0 || w >= cap - used) return -1;
+        used += w;
+    }
+    return p.n;
+}
+
 extern "C" int sylber_debug_gemm_bench(int32_t M, int32_t N, int32_t K, int32_t ldx, int32_t epi, int32_t act, int32_t cfg,
                                        int32_t iters, float* ms_out) {
     return gemm_bench_impl(M, N, K, ldx, epi, act, cfg, iters, ms_out, nullptr);

@@ -162,3 +162,84 @@ def test_gemm_tile_cost_model_picks():
             for model in (0, 5, 100, 105):
                 ids = (14, 15, 17, 46, 47) if (e == BF16 and model < 100) else (1, 2, 3, 4, 10, 85, 91, 97, 86, 51, 57, 80, 90, 95)
                 assert pick(m, n, k, e, a, 0, model, 0) in ids, (m, n, k, e, model)
+
+
+# ---- which kernel instantiation every launch of the 16-bit GEMM launcher resolves to (sylber_debug_gemm_resolve; host arithmetic only) ----
+GEMM_DISPATCH_FIXTURE = os.path.join(ROOT, "tests", "golden", "gemm_dispatch.txt")
+_FORCED_IDS = list(range(-1, 100)) + [9010]                 # 9010 = tile 10 with one workgroup per tile (never its persistent form)
+_EPI_ACTS = ((0, 0), (0, 1), (0, 2), (0, 3), (1, 0), (1, 1), (1, 2), (2, 0), (6, 0), (3, 0), (4, 0))   # every epilogue of launch_gemm_bf16 with its activations
+
+
+def _gemm_dispatch_grid():
+    """the grid as (line key, [arguments of sylber_debug_gemm_resolve without the buffer]): M N K epi act fmt kpat tile model h192 pre tail.
+    Forced cross: a line = one launch under every forced id (N = 1536: whole 192- and 256-column tiles and more than one round at M = 16384, so
+    that tile 91's residual prefetch and tile 10's persistent form are reachable).  Automatic pick: a line = one launch."""
+    for epi, act in _EPI_ACTS:
+        for fmt in (0, 1, 2):
+            for K, N, kpat in [(k, 1536, 0) for k in (64, 128, 192, 256, 768, 1536, 3072)] + [(1536, 512, 1)]:
+                for mfma16 in (0, 1000000):
+                    for M in (1000, 16384):
+                        key = "forced %d %d %d %d %d %d %d %d" % (M, N, K, epi, act, fmt, kpat, mfma16)
+                        yield key, [(M, N, K, epi, act, fmt, kpat, (mfma16 + t) if t >= 0 else (mfma16 + 999 if mfma16 else -1), 0, 0, 0, 0) for t in _FORCED_IDS]
+    QK, RESLN, BF16, GELU = 3, 6, 0, 1
+    rows = ((2304, 768, QK, 0, 0), (768, 768, RESLN, 0, 0), (3072, 768, BF16, GELU, 0), (768, 3072, RESLN, 0, 0), (512, 1024, BF16, GELU, 0), (512, 1536, BF16, GELU, 1))
+    for M in (256, 512, 1000, 1024, 2048, 6144, 8192, 12288, 16384, 24064, 49152):
+        for N, K, epi, act, kpat in rows:
+            for model in (0, 2, 5, 6):
+                for h192 in (0, -1):
+                    for pre in ((-1, 0, 1, 2, 3) if epi == RESLN else (0,)):
+                        for tile in ((-1, 1000999) if epi == BF16 else (-1,)):
+                            yield "auto %d %d %d %d %d %d %d %d %d %d" % (M, N, K, epi, act, kpat, tile, model, h192, pre), [(M, N, K, epi, act, 0, kpat, tile, model, h192, pre, 0)]
+    # forced row splits (8 x 60 s, 1.47 rounds of tile 91: its full round on 91, the rest on 128x128 / 128x192), and one the model refuses
+    for tile, tail in ((91, 4), (91, 5), (-1, 4), (3, 4)):
+        yield "tail %d %d" % (tile, tail), [(24064, 768, 3072, RESLN, 0, 0, 0, tile, 0, 0, 0, tail)]
+
+
+def _gemm_dispatch_results(lib, intern):
+    """[(key, [result per case])]: a result = the interned kernel name of the launch, `first-end:name` per launch of a row split, `x` = refused"""
+    import ctypes
+    buf = ctypes.create_string_buffer(4096)
+    out = []
+    for key, cases in _gemm_dispatch_grid():
+        res = []
+        for c in cases:
+            n = lib.sylber_debug_gemm_resolve(*c, buf, len(buf))
+            assert n >= 0, (key, c)
+            launches = [ln.split(" ", 2) for ln in buf.value.decode().splitlines()] if n else []
+            assert len(launches) == n
+            if n == 1 and (int(launches[0][0]), int(launches[0][1])) == (0, c[0]):
+                res.append(intern(launches[0][2]))
+            else:
+                res.append("+".join("%s-%s:%s" % (m0, m1, intern(nm)) for m0, m1, nm in launches) or "x")
+        out.append((key, res))
+    return out
+
+
+def _rle(res):
+    runs = []
+    for r in res:
+        if runs and runs[-1][0] == r:
+            runs[-1][1] += 1
+        else:
+            runs.append([r, 1])
+    return " ".join(r if n == 1 else "%s*%d" % (r, n) for r, n in runs)
+
+
+def test_gemm_dispatch_resolves_to_the_recorded_kernels(lib):
+    """Every tile of a family returns the same bits by design, so a launch routed to the wrong member passes every parity test and only runs slower:
+    the routing is pinned here.  tests/golden/gemm_dispatch.txt holds, for a grid of launches (_gemm_dispatch_grid), the kernel instantiation(s)
+    launch_gemm_bf16 resolved each to BEFORE the dispatch became one resolver per kernel family (recorded from the launch wrappers of that tree run
+    dry), except forced ids without an instantiation, which since then take the documented 128x192 fallback uniformly.
+    File: `name <index> <kernel>` lines, then `<key> | <results, run-length encoded>` lines."""
+    names, want = {}, {}
+    for ln in open(GEMM_DISPATCH_FIXTURE).read().splitlines():
+        if ln.startswith("name "):
+            _, idx, nm = ln.split(" ", 2)
+            names[nm] = idx
+        elif ln and not ln.startswith("#"):
+            key, res = ln.split(" | ")
+            want[key] = res
+    got = _gemm_dispatch_results(lib, lambda nm: names.get(nm, "<" + nm + ">"))
+    assert [k for k, _ in got] == list(want), "the grid and the fixture list different launches"
+    bad = [(k, _rle(r), want[k]) for k, r in got if _rle(r) != want[k]]
+    assert not bad, "%d launches resolve to other kernels than recorded, e.g. %s: got %s, recorded %s" % ((len(bad),) + bad[0])

@@ -361,7 +361,7 @@ NOSPLIT, TAIL = 100000, lambda t: 100000 * (t + 2)      # `tile` argument: + 100
 
 @pytest.mark.parametrize("tail", [3, 4, 0, 91, 97, 86, 51, 57])
 def test_tail_split_is_bitwise(lib, tail):
-    """round 6 tail policy (gemm_bf16.hip launch_f): a launch whose tile count is not a whole number of rounds of 256 persistent workgroups
+    """round 6 tail policy (gemm_bf16.hip gemm_plan): a launch whose tile count is not a whole number of rounds of 256 persistent workgroups
     runs the rows of its full rounds on the chosen tile and the remaining rows, as a second launch over rows [M1, M), on another tile.  Every
     output element is one fp32 chain over K in the same order whatever tile computes it, so the split changes no bit: 16-bit GELU epilogue
     (FFN1 / conv shape), the in-place fp32 residual epilogue (out-proj / FFN2, incl. the loop that prefetches the residual rows), the plain

@@ -1,4 +1,4 @@
-"""Tail policy of the persistent GEMM tiles (gemm_bf16.hip launch_f): us per launch of the encoder GEMM shapes over a range of row counts,
+"""Tail policy of the persistent GEMM tiles (gemm_bf16.hip gemm_plan): us per launch of the encoder GEMM shapes over a range of row counts,
 the round-5 launcher against the 192-row tiles and the row split -- the data the cost model's constants (GEMM_H192_EFF, GEMM_SOLO_EFF, GEMM_SPLIT_US) are fitted to.
 
     python tools/tail_sweep.py [row_tiles,...] > profiles/r06_tail_policy.md       (on the GPU box)

@@ -1,5 +1,5 @@
 """In-forward time of each GEMM launch group (sequential profile, cold activations) with ONE tile id forced on every launch that has it, over a few batch
-shapes: the ground truth the cost model of gemm_bf16.hip::launch_f is checked against (its hot micro-benchmark, tools/tail_sweep.py, flatters
+shapes: the ground truth the cost model of gemm_bf16.hip::gemm_plan is checked against (its hot micro-benchmark, tools/tail_sweep.py, flatters
 the hipcc-scheduled tiles).  `auto` = the cost model's own choice.
 
     python tools/tile_pick_sweep.py [--shapes 8x60,24x10,...] [--tiles 91,51,...] > profiles/r06_tile_pick.md
