@@ -878,6 +878,12 @@ int sylber_condition_features(sylber_mlp_t m, const float* features_dev, int32_t
  * not available to sylber_forward_packed), all fp32:
  *   SYLBER_TAP_CONV0    conv layer 0 alone (GroupNorm + GELU applied): [B, R0, 512] with R0 = 64 * sylber_padded_frames(Lmax), every
  *                       row of the 16-bit buffer widened exactly (hi + lo for SYLBER_SPLIT16); rows at or past (Lmax - 10) / 5 + 1 are +0
+ *   SYLBER_TAP_CONV(i)  = -(1024 + i), i = 1..6: conv layer i alone (GELU applied), the forward ends right behind its launch: [B, R_i, 512] with
+ *                       R_i = sylber_padded_frames(Lmax) << (6 - i), every row of the layer's output buffer (16-bit buffers widened exactly, hi +
+ *                       lo for SYLBER_SPLIT16; a device-to-device copy for SYLBER_FP32).  Utterance b's valid rows are [0, L_i) of its R_i rows,
+ *                       L_i = (L_(i-1) - k_i) / 2 + 1 from L_0 = (Lmax - 10) / 5 + 1 (k_i = 3 for i <= 4, else 2); rows [L_i, R_i) hold whatever
+ *                       the launch computes from the rows behind the previous layer's valid ones.  Rows [0, T) of SYLBER_TAP_CONV(6) are stage 1.
+ *                       i = 0 and i >= 7 are refused
  *   SYLBER_TAP_PROJ     the projected residual stream x, frames at or past an utterance's valid count zeroed: [B, T, 768]
  *   SYLBER_TAP_POSCONV  x + GELU(pos-conv(x)), the input of the encoder LayerNorm: [B, T, 768]
  * Taps inside encoder layer l: stage SYLBER_TAP_LAYER(l, k) = -(8 (l + 1) + k) ends the forward after one launch of the layer and returns
@@ -900,6 +906,7 @@ int sylber_condition_features(sylber_mlp_t m, const float* features_dev, int32_t
 enum { SYLBER_TAP_CONV0 = -1, SYLBER_TAP_PROJ = -2, SYLBER_TAP_POSCONV = -3 };
 enum { SYLBER_LTAP_QKV = 0, SYLBER_LTAP_CTX = 1, SYLBER_LTAP_ATTN_SUM = 2, SYLBER_LTAP_LN1 = 3, SYLBER_LTAP_FFN1 = 4, SYLBER_LTAP_FFN2_SUM = 5 };
 #define SYLBER_TAP_LAYER(l, k) (-(8 * ((l) + 1) + (k)))
+#define SYLBER_TAP_CONV(i) (-(1024 + (i)))
 int sylber_set_stop_stage(sylber_t h, int32_t stage);
 /* per-kernel device time of the last forward, measured with HIP events on the launch stream.
  * names/ms arrays of capacity cap; returns the number of entries (<=cap) or <0 on error. */

@@ -38,6 +38,10 @@ int sylber_debug_poison_workspace(sylber_t h, int32_t byte);
  * out_host [B][512][2]: (a, b) per channel with a = gamma / sqrt(var + 1e-5), b = beta - mean * a; synchronises the device
  * (tests/test_gpu_frontend.py checks it against float64) */
 int sylber_debug_conv0_scale_shift(sylber_t h, int32_t B, float* out_host);
+/* test aid (host arithmetic only, no device touched): the forward's plan for n_samples >= 400 samples per utterance -- L[i] = valid rows of
+ * conv layer i = 0..6 and R[i] = rows per utterance of its output buffer (sylber_padded_frames << (6 - i)); tests/test_conv_stack_ref.py
+ * checks L[i] <= R[i] and both against their restatement */
+int sylber_debug_conv_rows(int32_t n_samples, int32_t* L, int32_t* R);
 /* average ms of one launch of the attention core (12 heads x 64, B utterances of T frames, no key mask) on pseudo-random packed
  * operands; precision: SYLBER_BF16 (bf16 operands) or SYLBER_FP8 (MXFP8 q / k / V^T, e4m3 P) */
 int sylber_debug_attention_bench(int32_t B, int32_t T, int32_t precision, int32_t iters, float* ms_out);

@@ -232,10 +232,12 @@ DEV_EXPORTS = {
     "sylber_debug_attention_bench": (c_int, [c_int32] * 4 + [POINTER(c_float)]),
     "sylber_debug_poison_workspace": (c_int, [c_void_p, c_int32]),
     "sylber_debug_conv0_scale_shift": (c_int, [c_void_p, c_int32, c_void_p]),
+    "sylber_debug_conv_rows": (c_int, [c_int32, POINTER(c_int32), POINTER(c_int32)]),
 }
 OPT_GEMM_TILE, OPT_ATTN_QUERIES_PER_WAVE, OPT_GEMM_PERSISTENT = 1, 2, 3
 OPT_FUSE_OUTPROJ_LN, OPT_CONV0_VALU = 4, 5
 OPT_FP8_ATTENTION, OPT_SEGMENT, OPT_PER_UTTERANCE = 7, 9, 14
+OPT_GEMM_MODEL, OPT_GEMM_MFMA16 = 12, 13
 # negative stop stages of sylber_set_stop_stage: taps inside the front half (include/sylber_hip.h SYLBER_TAP_*)
 TAP_CONV0, TAP_PROJ, TAP_POSCONV = -1, -2, -3
 # taps inside encoder layer l (SYLBER_TAP_LAYER / SYLBER_LTAP_*): the forward ends after launch k of the layer
@@ -255,6 +257,11 @@ def ltap_width(k: int, precision: str = "bf16", fp8_attention: bool = True) -> i
 def TAP_LAYER(l: int, k: int) -> int:
     """the stop stage of tap k (LTAP_*) of encoder layer l"""
     return -(8 * (int(l) + 1) + int(k))
+
+
+def TAP_CONV(i: int) -> int:
+    """the stop stage of the tap behind conv layer i = 1..6 (SYLBER_TAP_CONV): every row of its output buffer, [B, padded_frames << (6 - i), 512]"""
+    return -(1024 + int(i))
 
 
 _LIB = None

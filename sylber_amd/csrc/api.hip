@@ -188,7 +188,12 @@ extern "C" void sylber_destroy(sylber_t c) {
 
 extern "C" int sylber_set_stop_stage(sylber_t c, int32_t stage) {
     if (!c) return 1;
-    if (stage < SYLBER_TAP_POSCONV) {
+    if (stage <= SYLBER_TAP_CONV(0)) {
+        // SYLBER_TAP_CONV(i) = -(1024 + i)
+        if (stage == SYLBER_TAP_CONV(0) || stage < SYLBER_TAP_CONV(6)) {
+            syl_set_error("sylber_set_stop_stage", "unknown tap (conv-layer taps: -(1024 + i) behind conv layer i = 1..6; conv layer 0 is stage -1)"); return 1;
+        }
+    } else if (stage < SYLBER_TAP_POSCONV) {
         // SYLBER_TAP_LAYER(l, k) = -(8 (l + 1) + k)
         const int n = -stage, l = n / 8 - 1, k = n % 8;
         if (l < 0 || k > SYLBER_LTAP_FFN2_SUM) {

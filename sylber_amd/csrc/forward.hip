@@ -77,6 +77,14 @@ static void plan_padded(Plan& p, int B, int Lmax) {
     p.Tpv = (p.Tp + 63) & ~63;
     for (int i = 0; i < 7; ++i) p.R[i] = p.Tp << (6 - i);
 }
+// test aid (host arithmetic only): the plan's valid rows L[7] and rows per utterance R[7] of every conv layer's output buffer
+extern "C" int sylber_debug_conv_rows(int32_t n_samples, int32_t* L, int32_t* R) {
+    if (!L || !R || n_samples < 400) { syl_set_error("sylber_debug_conv_rows", "need at least 400 samples and non-null arrays"); return 1; }
+    Plan p = {};
+    plan_padded(p, 1, n_samples);
+    for (int i = 0; i < 7; ++i) { L[i] = p.L[i]; R[i] = p.R[i]; }
+    return 0;
+}
 
 // the workspace offsets of a plan whose geometry is set: nb = utterances of the per-utterance tables (GroupNorm
 // partials, scale / shift, valid, rows), ntab = ints of a packed batch's slot tables (0: none)
@@ -333,8 +341,10 @@ static int copy_frames_f32(const float* src, float* dst, int B, int Tp, int T, h
 // the taps inside an encoder layer (SYLBER_TAP_LAYER(l, k) = -(8 (l + 1) + k)): the layer and the launch a call stops behind
 struct LayerTap {
     int l = -1, k = -1;
-    explicit LayerTap(int stop_stage) { if (stop_stage <= -8) { l = -stop_stage / 8 - 1; k = -stop_stage % 8; } }
+    explicit LayerTap(int stop_stage) { if (stop_stage <= -8 && stop_stage > -1024) { l = -stop_stage / 8 - 1; k = -stop_stage % 8; } }
 };
+// the taps behind conv layer i = 1..6 (SYLBER_TAP_CONV(i) = -(1024 + i)): the layer a call stops behind, 0 for every other stage
+static int conv_tap_layer(int stop_stage) { return (stop_stage <= SYLBER_TAP_CONV(1) && stop_stage >= SYLBER_TAP_CONV(6)) ? -stop_stage - 1024 : 0; }
 
 // every kernel launch of the bf16 / fp16 / mixed16 / split16 / fp8 forward, in stream order; nothing else (no allocation, copy or
 // synchronisation), so the sequence can be replayed from a captured hipGraph.  pk: a packed batch (bf16 / fp16), nullptr for the padded
@@ -353,12 +363,14 @@ struct Forward {
     // the pre-LN sum still sitting in `pre` (updated in place) + that LayerNorm's row statistics and affine
     const float *res_g = nullptr, *res_b = nullptr;
     const LayerTap tap;                                 // a tap inside a layer: layer16 / layer8 set `tapped` once they have copied it out
+    const int ctap;                                     // a tap behind conv layer ctap (0: none): conv_stack sets `tapped` once it has copied it out
     bool tapped = false;
 
     Forward(sylber_ctx* c_, const Plan& p_, const float* wav, float* hidden, hipStream_t s_, const PackedCall* pk_)
         : c(c_), p(p_), wav_dev(wav), hidden_dev(hidden), s(s_), pk(pk_), w(c_->ws, p_), w8(w, p_), B(p_.B), M(p_.B * p_.Tp),
           split(c_->precision == SYLBER_SPLIT16), f8(c_->precision == SYLBER_FP8),
-          aud_c(c_->opt_audit16 && c_->fmt_conv == FMT_F16), aud_e(c_->opt_audit16 && c_->fmt == FMT_F16), tap(c_->stop_stage) {}
+          aud_c(c_->opt_audit16 && c_->fmt_conv == FMT_F16), aud_e(c_->opt_audit16 && c_->fmt == FMT_F16), tap(c_->stop_stage),
+          ctap(conv_tap_layer(c_->stop_stage)) {}
 
     // conv layer 0 + GroupNorm + GELU
     int conv0() {
@@ -390,6 +402,11 @@ struct Forward {
             tune_from_options(c, a);
             RUN(nm[i], launch_gemm_bf16(EPI_BF16, a, s));
             AUDIT(aud_c, AUD_CONV0 + i, dst, (long)B * p.R[i], 512, 512);
+            if (i == ctap) {                            // every row of the layer's output buffer, rows [L_i, R_i) included, widened exactly
+                tapped = true;
+                RUN("copy_out", launch_bf16_to_f32_rows(dst, 512, hidden_dev, B, p.R[i], p.R[i], 512, s, c->fmt_conv, dst_lo));
+                return 0;
+            }
             std::swap(src, dst); std::swap(src_lo, dst_lo);
         }
         feats = src; feats_lo = src_lo;
@@ -571,6 +588,7 @@ struct Forward {
             return 0;
         }
         if (conv_stack()) return 1;
+        if (tapped) return 0;
         if (c->stop_stage == 1) {
             RUN("copy_out", launch_bf16_to_f32_rows(feats, 512, hidden_dev, B, p.Tp, p.T, 512, s, c->fmt_conv, feats_lo));
             return 0;
@@ -601,10 +619,12 @@ struct ForwardF32 {
     const int B, M;
     const float* feats = nullptr;                       // the conv stack's output [B*Tp][512]
     const LayerTap tap;                                 // a tap inside a layer: layer() sets `tapped` once it has copied it out
+    const int ctap;                                     // a tap behind conv layer ctap (0: none)
     bool tapped = false;
 
     ForwardF32(sylber_ctx* c_, const Plan& p_, const float* wav, float* hidden, hipStream_t s_)
-        : c(c_), p(p_), wav_dev(wav), hidden_dev(hidden), s(s_), w(c_->ws, p_), B(p_.B), M(p_.B * p_.Tp), tap(c_->stop_stage) {}
+        : c(c_), p(p_), wav_dev(wav), hidden_dev(hidden), s(s_), w(c_->ws, p_), B(p_.B), M(p_.B * p_.Tp), tap(c_->stop_stage),
+          ctap(conv_tap_layer(c_->stop_stage)) {}
 
     int conv0() {
         const int* rows0 = c->opt_per_utt ? w.rows : nullptr;
@@ -621,6 +641,11 @@ struct ForwardF32 {
             a.X = src; a.ldx = (long)CS[i] * 512; a.W = c->conv_w32[i]; a.M = B * p.R[i]; a.N = 512; a.K = CK[i] * 512; a.act = 1;
             a.out0 = dst; a.ld0 = 512; a.tiled = 1;
             RUN("gemm_f32", launch_gemm_f32(a, s));
+            if (i == ctap) {
+                tapped = true;
+                HIP_TRY(hipMemcpyAsync(hidden_dev, dst, (size_t)B * p.R[i] * 512 * 4, hipMemcpyDeviceToDevice, s));
+                return 0;
+            }
             std::swap(src, dst);
         }
         feats = src;
@@ -688,6 +713,7 @@ struct ForwardF32 {
             return 0;
         }
         if (conv_stack()) return 1;
+        if (tapped) return 0;
         if (c->stop_stage == 1) {
             for (int b = 0; b < B; ++b)
                 HIP_TRY(hipMemcpyAsync(hidden_dev + (size_t)b * p.T * 512, feats + (size_t)b * p.Tp * 512, (size_t)p.T * 512 * 4,

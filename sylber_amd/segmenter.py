@@ -353,7 +353,8 @@ class HubertEncoderHIP:
         ``stop_stage`` (include/sylber_hip.h sylber_set_stop_stage): 1 returns the conv features [B, T, 512], 2 / 3 + l the stream after
         the encoder LayerNorm / layer l.  Negative values are the taps of the front half: ``_lib.TAP_CONV0`` conv layer 0 alone,
         [B, 64 * padded_frames(Lmax), 512] (every row of its buffer); ``_lib.TAP_PROJ`` the projected residual stream and
-        ``_lib.TAP_POSCONV`` the encoder LayerNorm's input, both [B, T, 768].  ``_lib.TAP_LAYER(l, k)`` is tap k (``_lib.LTAP_*``)
+        ``_lib.TAP_POSCONV`` the encoder LayerNorm's input, both [B, T, 768]; ``_lib.TAP_CONV(i)`` conv layer i = 1..6 alone,
+        [B, padded_frames(Lmax) << (6 - i), 512] (every row of its buffer).  ``_lib.TAP_LAYER(l, k)`` is tap k (``_lib.LTAP_*``)
         inside encoder layer l: [B, T, _lib.LTAP_WIDTH[k]] (2304 = q | k | v, 3072 for FFN1, else 768).  In the fp8 precision the MXFP8
         buffers (QKV, CTX, LN1, FFN1) come back as [B, T, 2 W]: W values dequantised exactly, then W floats holding each element's block
         exponent s - 127 (``_lib.ltap_width``); the fp32 sums keep W, and so does QKV with ``_lib.OPT_FP8_ATTENTION`` at -1."""
@@ -362,6 +363,9 @@ class HubertEncoderHIP:
         T = self.num_frames(Lmax)
         if stop_stage == _lib.TAP_CONV0:
             shape = (B, 64 * self.padded_frames(Lmax), 512)
+        elif _lib.TAP_CONV(7) <= stop_stage <= _lib.TAP_CONV(0):
+            # (i = 0 and i = 7 are refused by the library below)
+            shape = (B, self.padded_frames(Lmax) << max(6 + 1024 + stop_stage, 0), 512)
         elif stop_stage <= -8:
             # (an unknown k is refused by the library below)
             shape = (B, T, _lib.ltap_width(-stop_stage % 8, self.precision, self._opts.get(_lib.OPT_FP8_ATTENTION, 0) >= 0))
