@@ -574,6 +574,50 @@ int sylber_unit_align(const int32_t* phrase_units_dev, int32_t R, int32_t W, con
                       int32_t n_pairs, int32_t max_cols, int32_t max_rows, int32_t free_start, int32_t* cols_dev, int32_t* subs_dev,
                       int32_t* ops_dev, int32_t* cost_dev, int32_t* start_dev /* nullable */, void* workspace_dev, void* stream);
 
+/* Unit strings (sylber_amd/units.py: align_unit_strings / unit_error_rate; csrc/unit_strings.hip; restated in
+ * tests/unit_strings_ref.py): how far two tokenisations of the same audio are from each other -- the global alignment of WHOLE
+ * unit strings, without the 64-unit limit of "Edit scripts", many pairs per call.  A pair is a reference string r of m units and a
+ * hypothesis string h of L units, 0 <= m, L <= 65 536; a unit is a row of W ids, 1 <= W <= 8, ids in 0 .. 2^31 - 1;
+ * sub(i, j) = the number of columns in which r[i] and h[j] differ.  The DP, all int32:
+ *     E[i][-1] = (i + 1) W        E[-1][j] = (j + 1) W  (predecessor "left")        E[-1][-1] = 0
+ *     E[i][j]  = min(E[i-1][j-1] + sub(i, j), E[i-1][j] + W, E[i][j-1] + W)   the first smallest in that order
+ *   The path is the chain of predecessors from (m-1, L-1) to the corner.
+ *   Outputs per pair.  cost = E[m-1][L-1].  ops = (equal, substituted, deleted, inserted): diagonal steps with sub = 0, diagonal
+ *   steps with sub > 0, reference units without a partner, hypothesis units without one.  With pairing, cols[i] = the position
+ *   INSIDE h (0-based) that reference unit i met on a diagonal step, -1 if the unit is deleted, and subs[i] = that sub, W for a
+ *   deleted unit.
+ *   Empty sides.  m = 0: cost L W, ops (0, 0, 0, L).  L = 0: cost m W, ops (0, 0, m, 0), every cols -1 and every subs W.
+ *   Identities.  equal + substituted + deleted = m; equal + substituted + inserted = L; cost = sum(subs) + W * inserted.
+ *   For 1 <= m <= 64 and L >= 1 this is sylber_unit_align with free_start = 0 on the window [0, L) of h: cost, ops, cols and subs,
+ *   bit for bit.  Only cost is symmetric under exchanging r and h; the counts are not, since ties resolve differently.
+ *   Counts without a path.  A cell carries (cost, d, sb): d = the diagonal steps on the path that the chosen predecessor tracked,
+ *   sb = those of them with sub > 0, both 0 on row -1 and column -1; then equal = d - sb, substituted = sb, deleted = m - d,
+ *   inserted = L - d.  ops_dev is written from these counters in both modes; with pairing the walk back over the predecessor codes
+ *   counts its own four and writes them to ops_walk_dev where that is not null -- always equal to ops_dev; a check of the codes,
+ *   not a result.
+ *   Nothing returned depends on what the workspace held, on which pairs share a call or on their order: a pair touches only its
+ *   own slice of the workspace and its own outputs.
+ * sylber_unit_strings_align: ref_units_dev [ref_offsets_host[n_pairs], W] and hyp_units_dev [hyp_offsets_host[n_pairs], W] int32 on
+ *   the device; pair p is reference rows ref_offsets_host[p] .. ref_offsets_host[p + 1] against hypothesis rows
+ *   hyp_offsets_host[p] .. hyp_offsets_host[p + 1].  The offsets [n_pairs + 1] ascend from 0 and may repeat (empty strings); they
+ *   are read before the call returns, everything else is enqueued on `stream`.  pairing: 0 = counts only, 1 = cols_dev and
+ *   subs_dev [ref_offsets_host[n_pairs]] int32 too (required iff pairing).  ops_dev [n_pairs, 4], cost_dev [n_pairs] int32;
+ *   ops_walk_dev [n_pairs, 4] may be null and is written with pairing only.
+ *   workspace_dev: sylber_unit_strings_workspace_bytes of the same offsets and pairing, host arithmetic on the lengths (-1 on a bad
+ *   argument), every term rounded up to 256 B:
+ *       48 B per pair of table
+ *     + 24 L per pair with m > 64 and L > 0: two rows of (cost, d, sb) between strips of 64 reference rows, at most 1.5 MiB
+ *     + with pairing, ceil(m / 64) * ceil((L + 63) / 32) * 512 B per pair with m, L > 0: 2 bits per cell, about m L / 4.
+ *   A null pointer other than ops_walk_dev (and cols_dev, subs_dev without pairing), W outside 1..8, n_pairs < 1, pairing outside
+ *   {0, 1}, offsets that do not start at 0 or that descend, and a string of more than 65 536 units return 1 with
+ *   sylber_last_error before any device call. */
+int64_t sylber_unit_strings_workspace_bytes(const int32_t* ref_offsets_host, const int32_t* hyp_offsets_host, int32_t n_pairs,
+                                            int32_t pairing);
+int sylber_unit_strings_align(const int32_t* ref_units_dev, const int32_t* ref_offsets_host, const int32_t* hyp_units_dev,
+                              const int32_t* hyp_offsets_host, int32_t W, int32_t n_pairs, int32_t pairing, int32_t* cols_dev,
+                              int32_t* subs_dev, int32_t* ops_dev, int32_t* cost_dev, int32_t* ops_walk_dev /* nullable */,
+                              void* workspace_dev, void* stream);
+
 /* Warping paths (sylber_amd/search.py: SyllableIndex.align_phrases; restated in tests/align_ref.py): HOW a phrase matches a
  * window of rows -- which stored rows each phrase row is warped onto -- where the searches above report only where.  For one pair
  * (phrase of m rows, window [a, b) of row ids, W = b - a):

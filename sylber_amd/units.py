@@ -5,8 +5,10 @@ bytes per syllable (``W`` codebooks) and answers "where is this word said?" for 
 model's output and for a lexicon written as unit strings.  ``align_phrases`` takes the spans of either search, or any windows,
 and returns the edit script of each match: the stored row every phrase unit is paired with and the equal / substituted / deleted /
 inserted counts (csrc/unit_align.hip, "Edit scripts", tests/unit_align_ref.py); in global mode that is the weighted Levenshtein
-distance of two unit strings.  The argument rules it shares with the syllable indexes are ``_index.py``'s, the span checks of
-``align_phrases`` are search.py's."""
+distance of two unit strings, for a phrase of at most 64 units.  ``align_unit_strings`` and ``unit_error_rate`` align WHOLE unit
+strings of any length up to 65 536 units, pair by pair, without an index (csrc/unit_strings.hip, "Unit strings",
+tests/unit_strings_ref.py): how far two tokenisations of the same audio are from each other.  The argument rules ``UnitIndex``
+shares with the syllable indexes are ``_index.py``'s, the span checks of ``align_phrases`` are search.py's."""
 from __future__ import annotations
 
 import ctypes
@@ -24,6 +26,8 @@ from .search import ALIGN_WORKSPACE_BYTES, _align_spans       # the span checks 
 TILE_COLS = 256                 # US_TILE of csrc/unit_search.hip: the columns a workgroup stages at a time
 ALIGN_CHUNK_COLS = 32           # UA_CH of csrc/unit_align.hip: the anti-diagonal steps whose 2-bit codes fill one 64-bit word
 MAX_WIDTH = 8                   # US_MAX_W: ids per unit
+STRING_ROWS = 64                # UT_ROWS of csrc/unit_strings.hip: the reference rows of a strip
+MAX_STRING_UNITS = 65536        # UT_MAX_LEN: the units of one string of align_unit_strings
 FORMAT = "sylber_amd.UnitIndex/1"
 _i32p = ctypes.POINTER(ctypes.c_int32)
 
@@ -371,3 +375,213 @@ class UnitIndex:
         if bool(z["span_int"]):
             idx._span_dtype = np.int64
         return idx
+
+
+# ---- unit strings -------------------------------------------------------------------------------------------------------------------
+def _strings(seq, what: str) -> Tuple[list, np.ndarray, Optional[int]]:
+    """a sequence of unit strings (``[n]`` or ``[n, W]`` integer arrays or tensors, or ``tokenize``'s dicts through their
+    ``"units"``) -> (the strings as 2-D arrays or tensors where they are, lengths int64 ``[S]``, the width of the non-empty ones or
+    ``None``); ids are checked by the caller, once, on the concatenation"""
+    if torch.is_tensor(seq) or isinstance(seq, (np.ndarray, dict)):
+        raise ValueError("%s must be a sequence of unit strings, got one %s" % (what, type(seq).__name__))
+    parts, lens, W = [], [], None
+    for i, a in enumerate(seq):
+        if isinstance(a, dict):
+            a = a["units"]
+        if torch.is_tensor(a):
+            if a.dtype.is_floating_point or a.dtype.is_complex or a.dtype == torch.bool:
+                raise ValueError("%s[%d] must be integers, got %s" % (what, i, a.dtype))
+        else:
+            a = np.asarray(a)
+            kind = a.dtype.kind
+            if kind == "u":                                # torch has no wide unsigned types
+                if a.size and int(a.max()) > 2 ** 31 - 1:
+                    raise ValueError("%s[%d]: unit ids lie in [0, 2**31 - 1], got %d" % (what, i, int(a.max())))
+                a = a.astype(np.int64)
+            elif kind == "f" and a.size == 0 and a.ndim == 1:      # np.asarray([]) is float64
+                a = a.astype(np.int64)
+            elif kind != "i":
+                raise ValueError("%s[%d] must be integers, got %s" % (what, i, a.dtype))
+        shape = tuple(a.shape)
+        if len(shape) == 1:
+            a, shape = a[:, None], (shape[0], 1)
+        elif len(shape) != 2:
+            raise ValueError("%s[%d] must be [n] or [n, W], got %s" % (what, i, shape))
+        n, w = shape
+        if n > MAX_STRING_UNITS:
+            raise ValueError("%s[%d] has %d units, more than %d" % (what, i, n, MAX_STRING_UNITS))
+        if n:
+            if not 1 <= w <= MAX_WIDTH:
+                raise ValueError("%s[%d]: the width W must be in [1, %d], got %d" % (what, i, MAX_WIDTH, w))
+            if W is not None and w != W:
+                raise ValueError("%s[%d]: expected W = %d, got %d" % (what, i, W, w))
+            W = w
+        parts.append(a)
+        lens.append(n)
+    return parts, np.array(lens, np.int64), W
+
+
+def _flat_strings(parts: list, W: int, dev: torch.device, what: str) -> torch.Tensor:
+    """the non-empty strings one after another, int32 ``[max(sum n, 1), W]`` on ``dev``; ``ValueError`` for an id outside
+    ``0 .. 2**31 - 1`` (one reduction)"""
+    parts = [p for p in parts if p.shape[0]]
+    if not parts:
+        return torch.zeros((1, W), dtype=torch.int32, device=dev)
+    if not any(torch.is_tensor(p) for p in parts):
+        flat = torch.from_numpy(np.concatenate(parts))     # host arrays, as tokenize returns them: one copy to the device
+    else:
+        parts = [p if torch.is_tensor(p) else torch.from_numpy(p) for p in parts]
+        host = all(p.device.type == "cpu" for p in parts)
+        flat = torch.cat([p.to(torch.device("cpu") if host else dev, torch.int64) for p in parts])
+    lo, hi = int(flat.min()), int(flat.max())
+    if lo < 0 or hi > 2 ** 31 - 1:
+        raise ValueError("%s: unit ids lie in [0, 2**31 - 1], got %d .. %d" % (what, lo, hi))
+    return flat.to(dev, torch.int32).contiguous()
+
+
+def unit_strings_workspace_bytes(m, L, pairing: bool) -> np.ndarray:
+    """int64: the bytes of workspace that each pair (``m`` reference units, ``L`` hypothesis units; arrays) adds to a launch of
+    ``sylber_unit_strings_align`` beyond its 48 B of table: two rows of 12 B per column between strips where ``m > 64``, and with
+    ``pairing`` 2 bits per cell of ``ceil(m / 64)`` strips of ``L + 63`` steps, in chunks of 32 steps"""
+    m, L = np.asarray(m, np.int64), np.asarray(L, np.int64)
+    rows = np.where((m > STRING_ROWS) & (L > 0), (24 * L + 255) // 256 * 256, 0)
+    if not pairing:
+        return rows
+    strips, chunks = (m + STRING_ROWS - 1) // STRING_ROWS, (L + STRING_ROWS - 1 + ALIGN_CHUNK_COLS - 1) // ALIGN_CHUNK_COLS
+    return rows + np.where((m > 0) & (L > 0), strips * chunks * 512, 0)
+
+
+def _align_strings(refs, hyps, pairing, device, pair_chunk, fill, need_ref_units=False):
+    """``align_unit_strings`` -> (cols, subs, ops, costs, ref offsets int64 on the host, hyp lengths, W); cols and subs ``None``
+    without pairing; ``need_ref_units``: refuse references without a single unit, as everything before any launch"""
+    rp, rl, Wr = _strings(refs, "refs")
+    hp, hl, Wh = _strings(hyps, "hyps")
+    S = int(rl.size)
+    if S != int(hl.size):
+        raise ValueError("refs and hyps must be equally long, got %d and %d strings" % (S, int(hl.size)))
+    if Wr is not None and Wh is not None and Wr != Wh:
+        raise ValueError("refs have W = %d, hyps have W = %d" % (Wr, Wh))
+    if pair_chunk is not None and (isinstance(pair_chunk, bool) or int(pair_chunk) != pair_chunk or int(pair_chunk) < 1):
+        raise ValueError("pair_chunk must be an integer >= 1, got %r" % (pair_chunk,))
+    W = Wr or Wh or 1
+    pairing = bool(pairing)
+    ro, ho = (np.concatenate([[0], np.cumsum(x)]).astype(np.int64) for x in (rl, hl))
+    if ro[-1] >= 2 ** 31 or ho[-1] >= 2 ** 31:
+        raise ValueError("one call takes fewer than 2^31 units on each side")
+    need = unit_strings_workspace_bytes(rl, hl, pairing) + 48
+    if S and int(need.max()) + 256 > ALIGN_WORKSPACE_BYTES:
+        s = int(need.argmax())
+        raise ValueError("pair %d (%d x %d units) needs %d bytes of predecessor codes for its pairing, more than %d; pairing=False "
+                         "(counts only) never needs more than 1.5 MiB per pair" % (s, rl[s], hl[s], need[s], ALIGN_WORKSPACE_BYTES))
+    if need_ref_units and ro[-1] == 0:
+        raise ValueError("the unit error rate needs at least one reference unit")
+    dev = _device(device)
+    ops = torch.empty((S, 4), dtype=torch.int32, device=dev)
+    costs = torch.empty((S,), dtype=torch.int32, device=dev)
+    cols = subs = None
+    if pairing:
+        cols = torch.empty(max(int(ro[-1]), 1), dtype=torch.int32, device=dev)
+        subs = torch.empty(max(int(ro[-1]), 1), dtype=torch.int32, device=dev)
+    if S:
+        # the launches: pair_chunk pairs each, or as many as keep the workspace below ALIGN_WORKSPACE_BYTES
+        if pair_chunk is not None:
+            cuts = list(range(0, S, int(pair_chunk))) + [S]
+        else:
+            cuts, acc = [0], np.concatenate([[0], np.cumsum(need)])
+            while cuts[-1] < S:
+                cuts.append(max(cuts[-1] + 1, int(np.searchsorted(acc, acc[cuts[-1]] + ALIGN_WORKSPACE_BYTES - 256, side="right")) - 1))
+        lib = _lib.load()
+        rd, hd = _flat_strings(rp, W, dev, "refs"), _flat_strings(hp, W, dev, "hyps")
+        groups = []
+        for g0, g1 in zip(cuts[:-1], cuts[1:]):
+            r32, h32 = (np.ascontiguousarray(o[g0:g1 + 1] - o[g0], np.int32) for o in (ro, ho))
+            size = int(lib.sylber_unit_strings_workspace_bytes(r32.ctypes.data_as(_i32p), h32.ctypes.data_as(_i32p), g1 - g0, int(pairing)))
+            if size < 0:
+                raise _lib.SylberHipError("sylber_unit_strings_workspace_bytes refused the call")
+            groups.append((g0, g1, r32, h32, size))
+
+        def at(t, row, width=1):                           # the address of row `row` of a non-empty tensor, also where the slice is empty
+            return ctypes.c_void_p(t.data_ptr() + int(row) * width * 4)
+
+        with torch.cuda.device(dev):
+            st = _stream(dev)
+            ws = torch.empty(max(g[4] for g in groups), dtype=torch.uint8, device=dev)
+            if fill is not None:
+                ws.fill_(fill)
+            for g0, g1, r32, h32, _ in groups:
+                _lib.check(lib.sylber_unit_strings_align(at(rd, ro[g0], W), r32.ctypes.data_as(_i32p), at(hd, ho[g0], W),
+                                                         h32.ctypes.data_as(_i32p), W, g1 - g0, int(pairing),
+                                                         at(cols, ro[g0]) if pairing else None, at(subs, ro[g0]) if pairing else None,
+                                                         at(ops, 4 * g0), at(costs, g0), None, _vp(ws), st), "sylber_unit_strings_align")
+    if pairing:
+        cols, subs = cols[:int(ro[-1])].to(torch.int64), subs[:int(ro[-1])]
+    return cols, subs, ops, costs, ro, hl, W
+
+
+def align_unit_strings(refs, hyps, *, pairing: bool = False, device="cuda", pair_chunk: Optional[int] = None, _workspace_fill=None):
+    """how far two tokenisations are from each other: the global alignment of whole unit strings of any length, pair by pair
+    (csrc/unit_strings.hip, ``sylber_unit_strings_align``; contract in include/sylber_hip.h "Unit strings", restated in
+    tests/unit_strings_ref.py).  ``refs`` and ``hyps``: equally long sequences of ``[m]`` / ``[m, W]`` integer arrays or tensors
+    (host or device, empty ones allowed), or the lists of dicts that ``SegmentSynthesis.tokenize`` returns, through their
+    ``"units"``.  ``1 <= W <= 8``, ids in ``0 .. 2**31 - 1``, at most 65 536 units per string.
+
+    Without ``pairing``: ``(ops int32 [S, 4], costs int32 [S])`` on the device.  With it: ``(cols int64 [sum m], subs int32 [sum m],
+    ops, costs, ref_offsets int64 [S + 1])``, reference ``s`` in rows ``ref_offsets[s] : ref_offsets[s + 1]``.
+
+    For a reference ``r`` of ``m`` units and a hypothesis ``h`` of ``L`` units, ``sub(i, j)`` = the columns in which ``r[i]`` and
+    ``h[j]`` differ, all int32::
+
+        E[i][-1] = (i + 1) W        E[-1][j] = (j + 1) W  (predecessor "left")        E[-1][-1] = 0
+        E[i][j]  = min(E[i-1][j-1] + sub(i, j), E[i-1][j] + W, E[i][j-1] + W)   the first smallest in that order
+
+    The path is the chain of predecessors from ``(m-1, L-1)`` to the corner.  ``costs = E[m-1][L-1]``, the weighted Levenshtein
+    distance; ``ops = (equal, substituted, deleted, inserted)``: diagonal steps with ``sub = 0``, diagonal steps with ``sub > 0``,
+    reference units without a partner, hypothesis units without one; ``cols[i]``: the position inside ``h`` (0-based) that
+    reference unit ``i`` met on a diagonal step, -1 if it is deleted; ``subs[i]``: that ``sub``, ``W`` for a deleted unit.
+    ``m = 0``: cost ``L W``, ops ``(0, 0, 0, L)``; ``L = 0``: cost ``m W``, ops ``(0, 0, m, 0)``, ``cols`` -1, ``subs`` ``W``.
+    ``equal + substituted + deleted = m``, ``equal + substituted + inserted = L``, ``costs = subs.sum() + W * inserted``.  For
+    ``1 <= m <= 64`` and ``L >= 1`` this is ``UnitIndex(h).align_phrases([r], [[[0, L]]], free_start=False)`` bit for bit.  Only
+    the cost is symmetric under exchanging ``r`` and ``h``: ties resolve differently, so the counts need not be.
+
+    Exact (small integers), and nothing depends on ``pair_chunk`` (the pairs per launch; by default as many as keep a launch's
+    workspace below ``search.ALIGN_WORKSPACE_BYTES``), on which pairs share a call, on their order or on stale workspace
+    contents.  Counts only, a pair needs at most 1.5 MiB of workspace; the pairing keeps 2 bits per cell, about ``m L / 4``
+    bytes.  ``ValueError`` before any launch: lists of different length, differing widths, a width outside 1 .. 8, non-integer
+    or negative ids, a string of more than 65 536 units, ``pair_chunk < 1``, and with ``pairing`` a single pair whose codes exceed
+    ``ALIGN_WORKSPACE_BYTES`` (before anything is allocated).  ``S = 0`` returns empty tensors without a launch."""
+    cols, subs, ops, costs, ro, _, _ = _align_strings(refs, hyps, pairing, device, pair_chunk, _workspace_fill)
+    if not pairing:
+        return ops, costs
+    return cols, subs, ops, costs, torch.from_numpy(ro).to(ops.device)
+
+
+class UnitErrorRate:
+    """what ``unit_error_rate`` returns: ``uer`` = (substituted + deleted + inserted) / reference units over all pairs;
+    ``weighted`` = the summed costs / (W x reference units), where a substitution counts by the share of its ids that differ; the
+    four totals ``equal``, ``substituted``, ``deleted``, ``inserted``; ``ref_units``, ``hyp_units``; the per-pair ``ops`` int32
+    ``[S, 4]`` and ``costs`` int32 ``[S]`` on the device"""
+    __slots__ = ("uer", "weighted", "equal", "substituted", "deleted", "inserted", "ref_units", "hyp_units", "ops", "costs")
+
+    def __init__(self, ops: torch.Tensor, costs: torch.Tensor, ref_units: int, hyp_units: int, W: int):
+        tot = ops.to(torch.int64).sum(0).tolist()
+        self.equal, self.substituted, self.deleted, self.inserted = (int(v) for v in tot)
+        self.ref_units, self.hyp_units, self.ops, self.costs = int(ref_units), int(hyp_units), ops, costs
+        self.uer = (self.substituted + self.deleted + self.inserted) / self.ref_units
+        self.weighted = int(costs.to(torch.int64).sum()) / (W * self.ref_units)
+
+    def __repr__(self) -> str:
+        return "UnitErrorRate(uer=%.4f, weighted=%.4f, equal=%d, substituted=%d, deleted=%d, inserted=%d, ref_units=%d, hyp_units=%d)" % (
+            self.uer, self.weighted, self.equal, self.substituted, self.deleted, self.inserted, self.ref_units, self.hyp_units)
+
+
+def unit_error_rate(refs, hyps, **kw) -> UnitErrorRate:
+    """the corpus-level unit error rate of hypothesis tokenisations against reference ones (clean against noisy, bf16 against
+    fp32, one codebook against another): ``align_unit_strings(refs, hyps, **kw)`` summed over the pairs -> ``UnitErrorRate``.
+    ``ValueError`` for what ``align_unit_strings`` refuses and for zero reference units in total."""
+    kw = dict(kw)
+    kw.pop("pairing", None)                                # the counts need no path
+    device, pair_chunk, fill = kw.pop("device", "cuda"), kw.pop("pair_chunk", None), kw.pop("_workspace_fill", None)
+    if kw:
+        raise TypeError("unit_error_rate: unexpected arguments %s" % sorted(kw))
+    _, _, ops, costs, ro, hl, W = _align_strings(refs, hyps, False, device, pair_chunk, fill, need_ref_units=True)
+    return UnitErrorRate(ops, costs, int(ro[-1]), int(hl.sum()), W)
