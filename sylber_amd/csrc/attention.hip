@@ -15,23 +15,13 @@
 // K and V^T tiles (64 keys) are staged with global_load_lds_dwordx4 into a double buffer, XOR-swizzled
 // through the source address so the ds_read_b128 fragment reads are bank-conflict free.
 #include "kernels.h"
+#include "lds_dma.h"
 #include <type_traits>
 
 #define AT_QBLK 128      // queries per workgroup (4 waves x 32)
 #define AT_KV 64         // keys per tile
 #define AT_TILE 8192     // bytes of one K or V^T tile
 #define AT_LDS (4 * AT_TILE)
-
-typedef __attribute__((address_space(3))) void* lds_vptr;
-typedef const __attribute__((address_space(1))) void* glb_vptr;
-// LDS-DMA through a buffer descriptor (constant per-lane byte offset, the tile's first key in the scalar offset): no 64-bit
-// per-lane address arithmetic per tile (profiles/r03_lds_dma_cost.md)
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc_a(const void* base) {
-    return __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, (int)0xffffffffu, 0x00020000);
-}
-__device__ __forceinline__ void glds16a(__amdgpu_buffer_rsrc_t rs, int voff, int soff, void* l) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_vptr)l, 16, voff, soff, 0, 0);
-}
 
 // 1/l and the store of one 32-query sub-tile: ctx[b*Tp + q][head*64 + d] (or its MXFP8 form)
 template <bool F8, int FMT>
@@ -160,8 +150,8 @@ __global__ __launch_bounds__(256, FMT == FMT_SPLIT ? 2 : (QW == 2 ? 3 : 4)) void
     // K rows beyond Tp (a last tile of 64 keys when Tp % 64 == 32) are read from whatever follows -- the next head's rows or
     // the next workspace buffer, finite or not: their scores are REPLACED by -inf through the key mask (a select, no
     // arithmetic), and V^T's key tail is kept zero by its producer
-    const __amdgpu_buffer_rsrc_t rk = make_rsrc_a(Kb), rv = make_rsrc_a(Vb);
-    const __amdgpu_buffer_rsrc_t rkl = make_rsrc_a(Kb + lo_qk), rvl = make_rsrc_a(Vb + lo_vt);
+    const __amdgpu_buffer_rsrc_t rk = make_rsrc(Kb), rv = make_rsrc(Vb);
+    const __amdgpu_buffer_rsrc_t rkl = make_rsrc(Kb + lo_qk), rvl = make_rsrc(Vb + lo_vt);
     int kvoff[2], vvoff[2];
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
@@ -191,11 +181,11 @@ __global__ __launch_bounds__(256, FMT == FMT_SPLIT ? 2 : (QW == 2 ? 3 : 4)) void
     {
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
-            glds16a(rk, kvoff[i], 0, smem + lds_piece + i * 1024);
-            glds16a(rv, vvoff[i], 0, smem + AT_TILE + lds_piece + i * 1024);
+            glds16b(rk, kvoff[i], 0, smem + lds_piece + i * 1024);
+            glds16b(rv, vvoff[i], 0, smem + AT_TILE + lds_piece + i * 1024);
             if constexpr (SP) {
-                glds16a(rkl, kvoff[i], 0, smem + 2 * AT_TILE + lds_piece + i * 1024);
-                glds16a(rvl, vvoff[i], 0, smem + 3 * AT_TILE + lds_piece + i * 1024);
+                glds16b(rkl, kvoff[i], 0, smem + 2 * AT_TILE + lds_piece + i * 1024);
+                glds16b(rvl, vvoff[i], 0, smem + 3 * AT_TILE + lds_piece + i * 1024);
             }
         }
     }
@@ -317,11 +307,11 @@ __global__ __launch_bounds__(256, FMT == FMT_SPLIT ? 2 : (QW == 2 ? 3 : 4)) void
             const int kv1 = (t + 1) * AT_KV;
 #pragma unroll
             for (int i = 0; i < 2; ++i) {
-                glds16a(rk, kvoff[i], kv1 * 128, nb + lds_piece + i * 1024);
-                glds16a(rv, vvoff[i], kv1 * 2, nb + AT_TILE + lds_piece + i * 1024);
+                glds16b(rk, kvoff[i], kv1 * 128, nb + lds_piece + i * 1024);
+                glds16b(rv, vvoff[i], kv1 * 2, nb + AT_TILE + lds_piece + i * 1024);
                 if constexpr (SP) {
-                    glds16a(rkl, kvoff[i], kv1 * 128, nb + 2 * AT_TILE + lds_piece + i * 1024);
-                    glds16a(rvl, vvoff[i], kv1 * 2, nb + 3 * AT_TILE + lds_piece + i * 1024);
+                    glds16b(rkl, kvoff[i], kv1 * 128, nb + 2 * AT_TILE + lds_piece + i * 1024);
+                    glds16b(rvl, vvoff[i], kv1 * 2, nb + 3 * AT_TILE + lds_piece + i * 1024);
                 }
             }
         }
@@ -384,7 +374,7 @@ __global__ __launch_bounds__(256, 4) void attention_f8_kernel(const uint8_t* __r
     }
     // staging: wave w fills rows [16 w, 16 w + 16) of the K tile and of the V^T tile, ONE 16-byte piece per lane and operand;
     // chunk c of row r lands at position c ^ ((r >> 1) & 3) (bank swizzle of the 64-byte rows)
-    const __amdgpu_buffer_rsrc_t rk = make_rsrc_a(Kb), rv = make_rsrc_a(Vb);
+    const __amdgpu_buffer_rsrc_t rk = make_rsrc(Kb), rv = make_rsrc(Vb);
     int kvoff, vvoff;
     {
         const int r = wave * 16 + (lane >> 2);
@@ -420,8 +410,8 @@ __global__ __launch_bounds__(256, 4) void attention_f8_kernel(const uint8_t* __r
     int ksc[2], vsc[2];                               // scales of the tile about to be used (requested one tile ahead)
     auto request = [&](int t, char* stage) {
         const int kv = t * AT_KV;
-        glds16a(rk, kvoff, kv * 64, stage + lds_piece);
-        glds16a(rv, vvoff, kv, stage + AT8_TILE + lds_piece);
+        glds16b(rk, kvoff, kv * 64, stage + lds_piece);
+        glds16b(rv, vvoff, kv, stage + AT8_TILE + lds_piece);
     };
     auto scales = [&](int t, int (&ks)[2], int (&vs)[2]) {
         const int kv = t * AT_KV;
@@ -517,17 +507,6 @@ __global__ __launch_bounds__(256, 4) void attention_f8_kernel(const uint8_t* __r
 // as the compiler-scheduled reference (SYLBER_OPT_ATTN_QUERIES_PER_WAVE = 32 / 64).  156 fixed registers: three waves per SIMD.
 // The schedule is executed on the CPU by tools/attn_asm_emu.py (tests/test_attn_asm_gen.py) and checked for the issue hazards the
 // compiler cannot see inside an asm statement.
-typedef int i32x4a_t __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ i32x4a_t rsrc_words_a(const void* base) {
-    const unsigned long long p = (unsigned long long)base;
-    i32x4a_t r;
-    r.x = __builtin_amdgcn_readfirstlane((int)(unsigned)p);
-    r.y = __builtin_amdgcn_readfirstlane((int)((unsigned)(p >> 32) & 0xffffu));
-    r.z = (int)0xffffffffu;
-    r.w = 0x00020000;
-    return r;
-}
-
 #define ATA_SLOT 16384
 // PK (packed layout, launch_attention_packed): q / k [H][Tp][64] and V^T [H][64][Tpv] of ONE pseudo-utterance of Tp = Tpv frames that
 // holds `nclip` utterances in slots; pk = [slot offsets (nclip + 1) | frames (nclip) | prefix of 128-query blocks (nclip + 1)].  Workgroup
@@ -600,7 +579,7 @@ __global__ __launch_bounds__(256, 3) void attention_asm_kernel(const bf16_t* __r
             kvoff[i] = (r * 64 + c * 8) * 2;
             vvoff[i] = (r * Tpv + c * 8) * 2;
         }
-        const i32x4a_t rsk = rsrc_words_a(Kb), rsv = rsrc_words_a(Vb);
+        const i32x4_t rsk = rsrc_words(Kb), rsv = rsrc_words(Vb);
         const int ldsw = __builtin_amdgcn_readfirstlane(lds0 + wave * 2048);
         const int limbase = nvalid - 4 * h;
         const int kvl0 = __builtin_amdgcn_readfirstlane(64 * (nt - 1)), kvl1 = __builtin_amdgcn_readfirstlane(64 * (nt - 1) + 32);

@@ -4,6 +4,7 @@
 // compared bit for bit against the reference's goldens (in bf16 a frame within 4e-3 of a threshold may
 // flip).  Correctness first: these kernels are simple, LDS-tiled, and not tuned.
 #include "kernels.h"
+#include "lds_dma.h"
 
 // ---------------------------------------------------------------------------------------------------
 // out[m][n] = act(sum_k X[m][k] W[n][k] + bias[n]) (+ res[m][n]);  64x64 tile, 4 waves (one 32x32 fragment
@@ -74,14 +75,11 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(const GemmArgsF32 a) {
 // {8j + e, 8j + 4 + e}: every output visits k in the fixed order 0 4 1 5 2 6 3 7 | 8 12 ... (exact fp32 FMAs, the same
 // order for every tile shape and batch size).  At 64 cycles per MFMA the matrix pipe is the only bound: staging and
 // fragment reads are ~5 % of its time, so a plain "wait, barrier, compute" loop suffices.
-typedef __attribute__((address_space(3))) void* lds_vptr32;
-typedef const __attribute__((address_space(1))) void* glb_vptr32;
-__device__ __forceinline__ void glds16f(const void* g, void* l) { __builtin_amdgcn_global_load_lds((glb_vptr32)g, (lds_vptr32)l, 16, 0, 0); }
 
 __global__ __launch_bounds__(256, 2) void gemm_f32_tiled_kernel(const GemmArgsF32 a) {
     constexpr int BM = 128, BN = 128, RB = 128;          // rows of 32 floats
     constexpr int XT = BM * RB, STAGE = (BM + BN) * RB;  // 32 KB per stage
-    constexpr int NPW = (BM + BN) / 8 / 4;               // 1-KiB pieces (8 rows) per wave and stage: 8
+    constexpr int NPW = LdsPieces<BM, BN, RB, 4>::NPW;   // 1-KiB pieces (8 rows) per wave and stage: 8
     extern __shared__ __attribute__((aligned(256))) char smem[];
     const int tid = threadIdx.x;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
@@ -97,16 +95,16 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_tiled_kernel(const GemmArgsF3
         const int p = wave + 4 * i;
         const bool isx = p < BM / 8;
         const int r = (isx ? p : p - BM / 8) * 8 + srow;
-        const int c = spos ^ ((r >> 1) & 7);
+        const int c = lds_src_chunk<RB>(r, spos);
         if (isx) { int xm = m0 + r; xm = xm < a.M ? xm : a.M - 1; gp[i] = a.X + (size_t)xm * a.ldx + c * 4; }
         else { int wr = n0 + r; wr = wr < a.N ? wr : a.N - 1; gp[i] = a.W + (size_t)wr * a.K + c * 4; }
         lds_off[i] = (isx ? 0 : XT) + (isx ? p : p - BM / 8) * 1024;
     }
     auto stage = [&](int kt, int slot) {
 #pragma unroll
-        for (int i = 0; i < NPW; ++i) glds16f(gp[i] + kt * 32, smem + slot * STAGE + lds_off[i]);
+        for (int i = 0; i < NPW; ++i) glds16(gp[i] + kt * 32, smem + slot * STAGE + lds_off[i]);
     };
-    const int frow = lane & 31, fh = lane >> 5, swz = (lane >> 1) & 7;
+    const int frow = lane & 31, fh = lane >> 5, swz = frag32_key<RB>(lane);
     const int xrow_off = (wm * 64 + frow) * RB, wrow_off = XT + (wn * 64 + frow) * RB;
     f32x16_t acc[2][2];
 #pragma unroll
@@ -124,7 +122,7 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_tiled_kernel(const GemmArgsF3
         const char* sb = smem + (t & 1) * STAGE;
 #pragma unroll
         for (int kk = 0; kk < 4; ++kk) {
-            const int ko = (((2 * kk + fh) ^ swz) << 4);
+            const int ko = lds_koff(2 * kk + fh, swz);
             f32x4_t xf[2], wf[2];
 #pragma unroll
             for (int f = 0; f < 2; ++f) {
@@ -241,8 +239,8 @@ __global__ __launch_bounds__(256, 2) void attention_f32_kernel(const float* __re
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             int kr = kv0 + krow[i]; kr = kr < Tp ? kr : Tp - 1;
-            glds16f(gk[i] + (size_t)kr * ld, dst + lds_piece + i * 1024);
-            glds16f(gv[i] + (size_t)kr * ld, dst + AF_TILE + lds_piece + i * 1024);
+            glds16(gk[i] + (size_t)kr * ld, dst + lds_piece + i * 1024);
+            glds16(gv[i] + (size_t)kr * ld, dst + AF_TILE + lds_piece + i * 1024);
         }
     };
     f32x16_t oacc[2];
@@ -378,7 +376,7 @@ __global__ __launch_bounds__(256) void posconv_f32_kernel(const float* __restric
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int piece = wave + 4 * i;
-            if (piece < 13) glds16f(src + piece * 1024 + lane * 16, dst + piece * 1024);
+            if (piece < 13) glds16(src + piece * 1024 + lane * 16, dst + piece * 1024);
         }
     };
     f32x16_t acc[2];

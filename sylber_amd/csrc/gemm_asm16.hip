@@ -1,7 +1,7 @@
 // Tile 47: tile 97's geometry (256x256 on eight waves, X3 ring, persistent) with the K loop on v_mfma_f32_16x16x32 (round 6).
 //
 // Same contract and same operands as gemm_asm.hip's tile 97 (y = act(x W^T + b) as 16-bit rows: the GELU GEMMs of the path -- conv1-5
-// TP:154-213, FFN1 TP:347-368 reached from sylber.py:122), same LDS image (128-byte rows, source-side chunk swizzle), same LDS-DMA pieces,
+// TP:154-213, FFN1 TP:347-368 reached from sylber.py:122), the LDS image and LDS-DMA pieces of lds_dma.h on 128-byte rows,
 // same ring and tile walk as gemmb_bf16_kernel<.., 2, 8, true>.  What differs is the MFMA shape of the loop (tools/gen_gemm_asm.py "Y3"):
 // the vendor library's kernels on this part issue 16x16x32, and profiles/r06_mfma_shape.md measured that shape 8.5 % cheaper per FLOP
 // under the package power cap as a register-only stream.  This kernel is the same question asked of the real loop.
@@ -14,23 +14,8 @@
 // output columns 4 q + e (e < 4) of the W fragment.  A wave's 128 x 64 tile = 8 X fragments x 4 W fragments = 32 accumulator quads.
 #include "kernels.h"
 #include "gemm_epilogue.h"
+#include "lds_dma.h"
 #include <type_traits>
-
-typedef __attribute__((address_space(3))) void* lds_vptr_c;
-typedef int i32x4c_t __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ void glds16_c(__amdgpu_buffer_rsrc_t rs, int voff, int soff, void* l) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_vptr_c)l, 16, voff, soff, 0, 0);
-}
-__device__ __forceinline__ i32x4c_t rsrc_words_c(const void* base) {
-    const unsigned long long p = (unsigned long long)base;
-    i32x4c_t r;
-    r.x = __builtin_amdgcn_readfirstlane((int)(unsigned)p);
-    r.y = __builtin_amdgcn_readfirstlane((int)((unsigned)(p >> 32) & 0xffffu));
-    r.z = (int)0xffffffffu;
-    r.w = 0x00020000;
-    return r;
-}
 
 // one 32-row block of a wave's tile through the wave's private LDS region (as epilogue_rows32, EPI_BF16): blk[th][j] = the accumulator quad of
 // X fragment (16 th + t) x W fragment j; bias[j] = a.bias[ncol0 + 16 j + 4 q .. + 3]
@@ -85,7 +70,8 @@ __global__ __launch_bounds__(512, 2) void gemmc_bf16_kernel(const GemmArgs a) {
     constexpr int GX = 2 * FM, GW = 2 * FN;                  // 16-row X fragments / 16-column W fragments per wave
     constexpr int XT = BM * RB, WS = BN * RB;
     constexpr int XRING = 3 * XT;
-    constexpr int NPW = (BM + BN) / 8 / NW, NXW = BM / 8 / NW;
+    using P = LdsPieces<BM, BN, RB, NW>;
+    constexpr int NPW = P::NPW, NXW = P::XPW;
     constexpr int EPB = 32 * (16 * GW * 2 + 16);              // staging bytes per wave (one 32-row block)
     extern __shared__ __attribute__((aligned(256))) char smem[];
     const int tid = threadIdx.x;
@@ -95,7 +81,7 @@ __global__ __launch_bounds__(512, 2) void gemmc_bf16_kernel(const GemmArgs a) {
     const int ntiles = tiles_m * tiles_n;
 
     const int srow = lane >> 3, spos = lane & 7;
-    struct Tile { int m0, n0; int voff[NPW]; i32x4c_t rx, rw; };
+    struct Tile { int m0, n0; int voff[NPW]; i32x4_t rx, rw; };
     auto setup = [&](int tile_id, Tile& t) {
         const int wg = xcd_remap(tile_id, ntiles);
         t.m0 = a.m_begin + (wg / tiles_n) * BM;
@@ -105,35 +91,35 @@ __global__ __launch_bounds__(512, 2) void gemmc_bf16_kernel(const GemmArgs a) {
             const int p = wave + NW * i;
             const bool isx = i < NXW;
             const int r = (isx ? p : p - BM / 8) * 8 + srow;
-            const int c = spos ^ ((r >> 1) & 7);
+            const int c = lds_src_chunk<RB>(r, spos);
             if (isx) { int xm = t.m0 + r; xm = xm < a.M ? xm : a.M - 1; t.voff[i] = (int)(((long)(xm - t.m0) * a.ldx + c * 8) * 2); }
             else { int wr = t.n0 + r; wr = wr < a.N ? wr : a.N - 1; t.voff[i] = ((wr - t.n0) * a.K + c * 8) * 2; }
         }
-        t.rx = rsrc_words_c(a.X + (size_t)t.m0 * a.ldx);
-        t.rw = rsrc_words_c(a.W + (size_t)t.n0 * a.K);
+        t.rx = rsrc_words(a.X + (size_t)t.m0 * a.ldx);
+        t.rw = rsrc_words(a.W + (size_t)t.n0 * a.K);
     };
     auto stage_x = [&](const Tile& t, int s, int slot) {
-        const __amdgpu_buffer_rsrc_t bx = __builtin_amdgcn_make_buffer_rsrc((void*)(a.X + (size_t)t.m0 * a.ldx), 0, (int)0xffffffffu, 0x00020000);
+        const __amdgpu_buffer_rsrc_t bx = make_rsrc(a.X + (size_t)t.m0 * a.ldx);
 #pragma unroll
         for (int i = 0; i < NXW; ++i)
-            glds16_c(bx, t.voff[i], TAP ? tap3_offset(s * 128) : s * 128, smem + slot * XT + (wave + NW * i) * 1024);
+            glds16b(bx, t.voff[i], TAP ? tap3_offset(s * 128) : s * 128, smem + slot * XT + (wave + NW * i) * 1024);
     };
     auto stage_w = [&](const Tile& t, int s, int slot) {
-        const __amdgpu_buffer_rsrc_t bw = __builtin_amdgcn_make_buffer_rsrc((void*)(a.W + (size_t)t.n0 * a.K), 0, (int)0xffffffffu, 0x00020000);
+        const __amdgpu_buffer_rsrc_t bw = make_rsrc(a.W + (size_t)t.n0 * a.K);
 #pragma unroll
         for (int i = NXW; i < NPW; ++i)
-            glds16_c(bw, t.voff[i], s * 128, smem + XRING + slot * WS + (wave + NW * (i - NXW)) * 1024);
+            glds16b(bw, t.voff[i], s * 128, smem + XRING + slot * WS + (wave + NW * (i - NXW)) * 1024);
     };
     auto stage = [&](const Tile& t, int s) { stage_x(t, s, s); stage_w(t, s, s); };
-    const int lds0 = (int)(unsigned)(unsigned long long)(lds_vptr_c)smem;
+    const int lds0 = (int)(unsigned)(unsigned long long)(lds_vptr)smem;
     const int lbase = __builtin_amdgcn_readfirstlane(lds0 + wave * 1024);
 
     // ---- fragment addresses: lane (t, q) reads row t of a 16-row fragment, 16-byte chunk (4 h + q) ^ swizzle(row) of slice h
-    const int frow = lane & 15, fq = lane >> 4, swz = (frow >> 1) & 7;
+    const int frow = lane & 15, fq = lane >> 4;
     int ax[2], aw[2], awh[2];
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
-        const int ko = ((4 * h + fq) ^ swz) << 4;
+        const int ko = frag16_chunk_off<RB>(lane, 4 * h + fq);
         ax[h] = lds0 + (wm * 32 * FM + frow) * RB + ko;
         aw[h] = lds0 + XRING + (wn * 32 * FN + frow) * RB + ko;
         awh[h] = aw[h] + WS;
@@ -147,7 +133,7 @@ __global__ __launch_bounds__(512, 2) void gemmc_bf16_kernel(const GemmArgs a) {
     stage(cur, 0);
     stage(cur, 1);
     stage_x(cur, 2, 2);
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NPW + NXW) : "memory");      // my pieces of step 0 (K >= 256 and K % 128 == 0: launcher)
+    wait_vmcnt<NPW + NXW>();      // my pieces of step 0 (K >= 256 and K % 128 == 0: launcher)
     for (;;) {
         __builtin_amdgcn_s_barrier();
         f32x4_t acc[GX][GW];
@@ -156,7 +142,7 @@ __global__ __launch_bounds__(512, 2) void gemmc_bf16_kernel(const GemmArgs a) {
         bf16x8_t fx[GX], fw[2][GW];
         {
             const int (&voff)[NPW] = cur.voff;
-            i32x4c_t rx, rw;
+            i32x4_t rx, rw;
             rx.x = __builtin_amdgcn_readfirstlane(cur.rx.x); rx.y = __builtin_amdgcn_readfirstlane(cur.rx.y); rx.z = (int)0xffffffffu; rx.w = 0x00020000;
             rw.x = __builtin_amdgcn_readfirstlane(cur.rw.x); rw.y = __builtin_amdgcn_readfirstlane(cur.rw.y); rw.z = (int)0xffffffffu; rw.w = 0x00020000;
             int axc[2] = {ax[0], ax[1]};
@@ -216,7 +202,7 @@ __global__ __launch_bounds__(512, 2) void gemmc_bf16_kernel(const GemmArgs a) {
                     }
             if constexpr (EPI == EPI_BF16) epilogue_rows32_m16<GW, ACT, FMT>(a, blk, bias, mw + fm * 32, nw, my, lane);
             else epilogue_rows32_m16_f32<GW, ACT>(a, blk, bias, mw + fm * 32, nw, lane);
-            __builtin_amdgcn_sched_barrier(0);
+            SCHED_FENCE();
         }
         if (!more) break;
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -226,8 +212,8 @@ __global__ __launch_bounds__(512, 2) void gemmc_bf16_kernel(const GemmArgs a) {
         constexpr int NYOUNG = NPW + NXW;
         constexpr int NST = FM * ((16 * GW * 2 / 16) / 2);
         static_assert(NYOUNG + NST < 64, "vmcnt is a 6-bit counter");
-        if (EPI == EPI_BF16 && whole_tiles) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NYOUNG + NST) : "memory");
-        else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NYOUNG) : "memory");
+        if (EPI == EPI_BF16 && whole_tiles) wait_vmcnt<NYOUNG + NST>();
+        else wait_vmcnt<NYOUNG>();
         cur = nxt;
         tile = next;
     }
@@ -264,8 +250,6 @@ template <> struct MF16<FMT_F16> {
         return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8_t, a), __builtin_bit_cast(f16x8_t, b), c, 0, 0, 0);
     }
 };
-template <int N> __device__ __forceinline__ void wait_vmcnt_c() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-#define SCHED_FENCE_C() __builtin_amdgcn_sched_barrier(0)
 
 // register -> global epilogue of a wave tile of GX x GW accumulator quads (EPI_BF16: 16-bit rows, EPI_F32: fp32 rows)
 template <int GX, int GW, int EPI, int ACT, int FMT>
@@ -310,8 +294,9 @@ __device__ __forceinline__ void gemm16_tile(const GemmArgs& a, const int tile_id
     constexpr int WNN = NW / 2;                              // waves along n
     constexpr int GX = 2 * FM, GW = 4 * FN / WNN;            // 16-row fragments per wave (wave tile 32 FM x (64 FN / WNN))
     constexpr int XT = BM * RB, WT = BN * RB, STAGE = XT + WT;
-    constexpr int NP = (BM + BN) / 8, NPW = NP / NW, XPW = BM / 8 / NW;
-    static_assert(NP % NW == 0 && (BM / 8) % NW == 0 && (4 * FN) % WNN == 0, "pieces / fragments must split evenly over the waves");
+    using P = LdsPieces<BM, BN, RB, NW>;
+    constexpr int NP = P::NP, NPW = P::NPW, XPW = P::XPW;
+    static_assert(NP % NW == 0 && (4 * FN) % WNN == 0, "pieces / fragments must split evenly over the waves");
     const int tid = threadIdx.x;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
     const int wm = wave / WNN, wn = wave % WNN;
@@ -320,15 +305,15 @@ __device__ __forceinline__ void gemm16_tile(const GemmArgs& a, const int tile_id
     const int m0 = a.m_begin + (wg / tiles_n) * BM, n0 = (wg % tiles_n) * BN;
 
     const int srow = lane >> 3, spos = lane & 7;
-    const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc((void*)(a.X + (size_t)m0 * a.ldx), 0, (int)0xffffffffu, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc((void*)(a.W + (size_t)n0 * a.K), 0, (int)0xffffffffu, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rx = make_rsrc(a.X + (size_t)m0 * a.ldx);
+    const __amdgpu_buffer_rsrc_t rw = make_rsrc(a.W + (size_t)n0 * a.K);
     int voff[NPW], lds_off[NPW];
 #pragma unroll
     for (int i = 0; i < NPW; ++i) {
         const int p = wave + NW * i;
         const bool isx = i < XPW;
         const int r = (isx ? p : p - BM / 8) * 8 + srow;
-        const int c = spos ^ ((r >> 1) & 7);
+        const int c = lds_src_chunk<RB>(r, spos);
         if (isx) { int xm = m0 + r; xm = xm < a.M ? xm : a.M - 1; voff[i] = (int)(((long)(xm - m0) * a.ldx + c * 8) * 2); }
         else { int wr = n0 + r; wr = wr < a.N ? wr : a.N - 1; voff[i] = ((wr - n0) * a.K + c * 8) * 2; }
         lds_off[i] = (isx ? 0 : XT) + (isx ? p : p - BM / 8) * 1024;
@@ -336,16 +321,16 @@ __device__ __forceinline__ void gemm16_tile(const GemmArgs& a, const int tile_id
     const int nt = a.K / 64;
     auto dma = [&](int kt, int i, char* base) {
         const bool isx = i < XPW;
-        glds16_c(isx ? rx : rw, voff[i], (a.kpat && isx) ? tap3_offset(kt * 128) : kt * 128, base + lds_off[i]);
+        glds16b(isx ? rx : rw, voff[i], (a.kpat && isx) ? tap3_offset(kt * 128) : kt * 128, base + lds_off[i]);
     };
     auto stage = [&](int kt, int slot) {
 #pragma unroll
         for (int i = 0; i < NPW; ++i) dma(kt, i, smem + slot * STAGE);
     };
-    const int frow = lane & 15, fq = lane >> 4, swz = (frow >> 1) & 7;
+    const int frow = lane & 15, fq = lane >> 4;
     int koff[2];
 #pragma unroll
-    for (int h = 0; h < 2; ++h) koff[h] = ((4 * h + fq) ^ swz) << 4;
+    for (int h = 0; h < 2; ++h) koff[h] = frag16_chunk_off<RB>(lane, 4 * h + fq);
     const int xrow_off = (wm * 32 * FM + frow) * RB, wrow_off = XT + (wn * 16 * GW + frow) * RB;
 
     f32x4_t acc[GX][GW];
@@ -374,9 +359,9 @@ __device__ __forceinline__ void gemm16_tile(const GemmArgs& a, const int tile_id
 #pragma unroll
                 for (int p = 0; p < NPW; ++p) {
                     if (np > 0 && p >= p0 && p < p1 && ((p - p0 + 1) * NM + np - 1) / np - 1 == n) {
-                        SCHED_FENCE_C();
+                        SCHED_FENCE();
                         if (on) dma(kt, p, base);
-                        SCHED_FENCE_C();
+                        SCHED_FENCE();
                     }
                 }
             }
@@ -386,9 +371,9 @@ __device__ __forceinline__ void gemm16_tile(const GemmArgs& a, const int tile_id
     stage(0, 0);
     if (nt > 1) stage(1, 1);
     if constexpr (NSTAGE == 3) { if (nt > 2) stage(2, 2); }
-    if (NSTAGE == 3 && nt > 2) wait_vmcnt_c<2 * NPW>();
-    else if (nt > 1) wait_vmcnt_c<NPW>();
-    else wait_vmcnt_c<0>();
+    if (NSTAGE == 3 && nt > 2) wait_vmcnt<2 * NPW>();
+    else if (nt > 1) wait_vmcnt<NPW>();
+    else wait_vmcnt<0>();
     __builtin_amdgcn_s_barrier();
     read_frags(smem, 0, 0);
     int slot = 0;
@@ -405,20 +390,20 @@ __device__ __forceinline__ void gemm16_tile(const GemmArgs& a, const int tile_id
         const int nslot = slot == NSTAGE - 1 ? 0 : slot + 1;
         const int rslot = NSTAGE == 2 ? nslot : (nslot == NSTAGE - 1 ? 0 : nslot + 1);      // slot of tile t + A while tile t is consumed
         const bool has_next = STEADY || t + 1 < nt, cont = STEADY || (t >= 1 && t + A < nt), dma2 = STEADY || t + A + 1 < nt;
-        SCHED_FENCE_C();
+        SCHED_FENCE();
         read_frags(sb, 1, 1);
-        SCHED_FENCE_C();
+        SCHED_FENCE();
         mfmas_dma(0, 0, GX, t + A, rslot, D0, NPW, cont);
         mfmas_dma(1, 0, GX / 2, 0, 0, 0, 0, false);
-        SCHED_FENCE_C();
+        SCHED_FENCE();
         if (has_next) {
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            if (NSTAGE == 3 && (STEADY || t + 2 < nt)) wait_vmcnt_c<NPW>();      // tile t+2 (all of it requested by now) may stay in flight
-            else wait_vmcnt_c<0>();
+            if (NSTAGE == 3 && (STEADY || t + 2 < nt)) wait_vmcnt<NPW>();      // tile t+2 (all of it requested by now) may stay in flight
+            else wait_vmcnt<0>();
             __builtin_amdgcn_s_barrier();
-            SCHED_FENCE_C();
+            SCHED_FENCE();
             read_frags(smem + nslot * STAGE, 0, 0);
-            SCHED_FENCE_C();
+            SCHED_FENCE();
         }
         mfmas_dma(1, GX / 2, GX, t + A + 1, slot, 0, D0, dma2);
         slot = nslot;

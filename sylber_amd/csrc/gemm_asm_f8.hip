@@ -11,22 +11,7 @@
 #include "kernels.h"
 #include "gemm_epilogue.h"
 #include "gemm_epilogue_f8.h"
-
-typedef __attribute__((address_space(3))) void* lds_vptr_f;
-typedef int i32x4f_t __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ void glds16_f(__amdgpu_buffer_rsrc_t rs, int voff, int soff, void* l) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_vptr_f)l, 16, voff, soff, 0, 0);
-}
-__device__ __forceinline__ i32x4f_t rsrc_words_f(const void* base) {
-    const unsigned long long p = (unsigned long long)base;
-    i32x4f_t r;
-    r.x = __builtin_amdgcn_readfirstlane((int)(unsigned)p);
-    r.y = __builtin_amdgcn_readfirstlane((int)((unsigned)(p >> 32) & 0xffffu));
-    r.z = (int)0xffffffffu;
-    r.w = 0x00020000;
-    return r;
-}
+#include "lds_dma.h"
 
 // FN = 4: 256x256 tile, FN = 3: 256x192.  Whole tiles only (M % 256 == 0, N % (64 FN) == 0; the launcher checks), K % 256 == 0, K >= 512.
 // SCL (256x192 only): the block scales reach the lanes through LDS (one 1-KiB LDS-DMA piece per wave and step + ds_read_u8) instead
@@ -38,7 +23,8 @@ __global__ __launch_bounds__(256, 1) void gemmf8_kernel(const GemmF8Args a) {
     constexpr int FM = 4, BM = 256, BN = 64 * FN, RB = 128;
     constexpr int XT = BM * RB, WS_ = BN * RB;
     constexpr int XRING = 3 * XT;
-    constexpr int NPW = (BM + BN) / 8 / 4, NXW = 8;
+    using P = LdsPieces<BM, BN, RB, 4>;
+    constexpr int NPW = P::NPW, NXW = P::XPW;
     constexpr bool STAGED = (EPI == EPI_QK || EPI == EPI_MXFP8 || EPI == EPI_QK8);
     extern __shared__ __attribute__((aligned(256))) char smem[];
     const int tid = threadIdx.x;
@@ -64,16 +50,16 @@ __global__ __launch_bounds__(256, 1) void gemmf8_kernel(const GemmF8Args a) {
         }
     };
     auto stage_x = [&](const Tile& t, int s, int slot) {
-        const __amdgpu_buffer_rsrc_t bx = __builtin_amdgcn_make_buffer_rsrc((void*)(a.X8 + (size_t)t.m0 * a.ldx8), 0, (int)0xffffffffu, 0x00020000);
+        const __amdgpu_buffer_rsrc_t bx = make_rsrc(a.X8 + (size_t)t.m0 * a.ldx8);
 #pragma unroll
-        for (int i = 0; i < NXW; ++i) glds16_f(bx, t.voff[i], s * 128, smem + slot * XT + (wave + 4 * i) * 1024);
+        for (int i = 0; i < NXW; ++i) glds16b(bx, t.voff[i], s * 128, smem + slot * XT + (wave + 4 * i) * 1024);
     };
     auto stage_w = [&](const Tile& t, int s, int slot) {
-        const __amdgpu_buffer_rsrc_t bw = __builtin_amdgcn_make_buffer_rsrc((void*)(a.W8 + (size_t)t.n0 * K), 0, (int)0xffffffffu, 0x00020000);
+        const __amdgpu_buffer_rsrc_t bw = make_rsrc(a.W8 + (size_t)t.n0 * K);
 #pragma unroll
-        for (int i = NXW; i < NPW; ++i) glds16_f(bw, t.voff[i], s * 128, smem + XRING + slot * WS_ + (wave + 4 * (i - NXW)) * 1024);
+        for (int i = NXW; i < NPW; ++i) glds16b(bw, t.voff[i], s * 128, smem + XRING + slot * WS_ + (wave + 4 * (i - NXW)) * 1024);
     };
-    const int lds0 = (int)(unsigned)(unsigned long long)(lds_vptr_f)smem;
+    const int lds0 = (int)(unsigned)(unsigned long long)(lds_vptr)smem;
     const int lbase = __builtin_amdgcn_readfirstlane(lds0 + wave * 1024);
 
     // fragment addresses: the bf16 loop's (slice kk of a row = 16-byte chunks 2 kk + half, XORed with the row's swizzle); an fp8
@@ -110,7 +96,7 @@ __global__ __launch_bounds__(256, 1) void gemmf8_kernel(const GemmF8Args a) {
     stage_x(cur, 0, 0); stage_w(cur, 0, 0);
     stage_x(cur, 1, 1); stage_w(cur, 1, 1);
     stage_x(cur, 2, 2);
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NPW + NXW) : "memory");
+    wait_vmcnt<NPW + NXW>();
     for (;;) {
         __builtin_amdgcn_s_barrier();
         f32x16_t acc[FM][FN];
@@ -118,8 +104,8 @@ __global__ __launch_bounds__(256, 1) void gemmf8_kernel(const GemmF8Args a) {
         int nloop = (K / 128 - 4) / 2;
         {
             const int (&voff)[NPW] = cur.voff;
-            i32x4f_t rx = rsrc_words_f(a.X8 + (size_t)cur.m0 * a.ldx8), rw = rsrc_words_f(a.W8 + (size_t)cur.n0 * K);
-            i32x4f_t rxs = rsrc_words_f(a.XS + (size_t)cur.m0 * 2), rws = rsrc_words_f(a.WS + (size_t)cur.n0 * 2);
+            i32x4_t rx = rsrc_words(a.X8 + (size_t)cur.m0 * a.ldx8), rw = rsrc_words(a.W8 + (size_t)cur.n0 * K);
+            i32x4_t rxs = rsrc_words(a.XS + (size_t)cur.m0 * 2), rws = rsrc_words(a.WS + (size_t)cur.n0 * 2);
             int axc[4] = {ax[0], ax[1], ax[2], ax[3]};
             int xr = 0, xwl, dlt, kofx;
             const int cneg = -2 * XT;
@@ -131,7 +117,7 @@ __global__ __launch_bounds__(256, 1) void gemmf8_kernel(const GemmF8Args a) {
                 const int rows8 = wsc ? BN / 8 : BM / 8;
                 const int l31 = (lane & 31) < rows8 ? (lane & 31) : rows8 - 1;
                 const int vsc = (int)((long)(lane >> 5) * (wsc ? a.ws_rows : a.xs_rows) * 2 + l31 * 16);
-                const i32x4f_t rsc = wsc ? rws : rxs;
+                const i32x4_t rsc = wsc ? rws : rxs;
                 int ksc = 2 * (wsc ? wstep : xstep);            // step 1's first slice
                 const int scstep = 2 * (wsc ? wstep : xstep);
                 const int lsc = __builtin_amdgcn_readfirstlane(lds0 + XRING + 2 * WS_ + (wsc ? 1024 : 0));
@@ -174,7 +160,7 @@ __global__ __launch_bounds__(256, 1) void gemmf8_kernel(const GemmF8Args a) {
                 if constexpr (EPI == EPI_MXFP8) epilogue_mxfp8_rows32<FN, ACT>(a, blk, bias, mw + fm * 32, nw, my, lane);
                 else if constexpr (EPI == EPI_QK8) epilogue_qk8_rows32<FN>(a, blk, bias, mw + fm * 32, nw, my, lane);
                 else epilogue_rows32<FN, EPI, ACT, FMT_BF16>(a.g, blk, bias, mw + fm * 32, nw, my, lane);
-                __builtin_amdgcn_sched_barrier(0);
+                SCHED_FENCE();
             }
         } else {
             epilogue_direct<FM, FN, EPI, ACT>(a.g, acc, mw, nw, lane);
@@ -185,7 +171,7 @@ __global__ __launch_bounds__(256, 1) void gemmf8_kernel(const GemmF8Args a) {
         __builtin_amdgcn_s_barrier();                        // the staging area (X slots 1, 2) is free again
         stage_x(nxt, 1, 1); stage_w(nxt, 1, 1);
         stage_x(nxt, 2, 2);
-        asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NPW + NXW) : "memory");
+        wait_vmcnt<NPW + NXW>();
         cur = nxt;
         tile = next;
     }

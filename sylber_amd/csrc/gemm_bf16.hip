@@ -11,42 +11,19 @@
 //     barrier and LDS-DMA issue time.  Used for the N = 768 / 1536 launches (500 / 1000 tiles = 1 / 2 rounds).
 //   * gemm8_bf16_kernel (below): 512 threads, tile 256x256, K step 32, 4-slot ring, one workgroup per CU, the two
 //     wave groups staggered by one barrier.  Used for the big GEMMs (convs, FFN1).
-// Both operands are staged HBM -> LDS with global_load_lds_dwordx4 (no VGPR round trip); the loads of the next tile(s)
-// are issued between the MFMAs of the current one and stay in flight ACROSS the per-tile barrier (raw s_barrier +
-// counted s_waitcnt vmcnt(N), never vmcnt(0) in the steady state).  The LDS image is lane-linear per wave
-// instruction (8 rows x 128 B), so the bank-conflict swizzle (16-B chunk ^= (row>>1)&7, conflict-free for
-// ds_read_b128's 16-lane groups on 128-B rows; (row>>2)&3 on 64-B rows) is applied to the per-lane SOURCE address
-// and again on the fragment read.  Fragments of k-substep kk+1 are read while the MFMAs of kk issue.  Tile shape is
-// picked per launch by a measured cost model (rounds over 256 CUs x tile area / efficiency).  Workgroup ids are
-// remapped so that each XCD owns a contiguous run of tiles (shared X panel in L2; same row ownership as the
-// LayerNorm / attention launches between the GEMMs).
+// Both operands are staged HBM -> LDS by LDS-DMA; the LDS image, its bank swizzle, the piece geometry and the rule for retiring
+// the loads before a barrier are lds_dma.h's.  The loads of the next tile(s) are issued between the MFMAs of the current one and
+// stay in flight ACROSS the per-tile barrier (raw s_barrier + counted wait_vmcnt<N>, never 0 in the steady state).  Fragments
+// of k-substep kk+1 are read while the MFMAs of kk issue.  Tile shape is picked per launch by a measured cost model (rounds
+// over 256 CUs x tile area / efficiency).  Workgroup ids are remapped so that each XCD owns a contiguous run of tiles (shared
+// X panel in L2; same row ownership as the LayerNorm / attention launches between the GEMMs).
 #include "kernels.h"
 #include "gemm_tiles.h"
 #include <type_traits>
 
-typedef __attribute__((address_space(3))) void* lds_vptr;
-typedef const __attribute__((address_space(1))) void* glb_vptr;
-
-__device__ __forceinline__ void glds16(const void* g, void* l) {
-    __builtin_amdgcn_global_load_lds((glb_vptr)g, (lds_vptr)l, 16, 0, 0);
-}
-
-// LDS-DMA through a buffer descriptor: the per-lane part of the source address is a 32-bit byte offset that stays
-// CONSTANT over the K loop (and, in the persistent kernels, over the tiles), the K step / operand plane travel in the scalar
-// offset, the tile's first row in the descriptor base.  Against global_load_lds with a 64-bit per-lane address (two VALU
-// adds per piece and step, twice the address registers) tools/ubench/mfma_mix2.hip measures the DMA's cost beside the
-// MFMAs at +16 instead of +200 issue cycles per two pieces (profiles/r03_lds_dma_cost.md).
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* base) {
-    return __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, (int)0xffffffffu, 0x00020000);
-}
-__device__ __forceinline__ void glds16b(__amdgpu_buffer_rsrc_t rs, int voff, int soff, void* l) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_vptr)l, 16, voff, soff, 0, 0);
-}
-
+#include "lds_dma.h"
 #include "gemm_epilogue.h"
 
-template <int N> __device__ __forceinline__ void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-#define SCHED_FENCE() __builtin_amdgcn_sched_barrier(0)
 // shader-clock timestamp (development, trace instantiation only): s_memtime shares lgkmcnt with the LDS reads, so a stamp
 // sits only where the kernel waits lgkmcnt(0) anyway or has no LDS read in flight
 #define TSTAMP(v) asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(v)::"memory")
@@ -64,8 +41,9 @@ __device__ __forceinline__ void gemm_bf16_tile(const GemmArgs& a, const int tile
     constexpr int RPP = 1024 / RB;           // rows per 1-KiB staging piece (one wave instruction)
     constexpr int KK = BK / 16;              // MFMA k-substeps per stage
     constexpr int XT = BM * RB, WT = BN * RB, STAGE = XT + WT;
-    constexpr int NP = (BM + BN) / RPP;      // 1-KiB pieces per stage
-    constexpr int NPW = NP / NWV;            // pieces per wave
+    using P = LdsPieces<BM, BN, RB, NWV>;
+    constexpr int NP = P::NP;                // 1-KiB pieces per stage
+    constexpr int NPW = P::NPW;              // pieces per wave
     static_assert(NP % NWV == 0, "tile must split evenly over the waves");
     const int tid = threadIdx.x;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
@@ -84,8 +62,7 @@ __device__ __forceinline__ void gemm_bf16_tile(const GemmArgs& a, const int tile
     int lds_off[NPW];
     // pieces wave + 4 i with i < XPW are X rows for EVERY wave (the X pieces split evenly over the waves): which operand
     // a piece belongs to is a compile-time property of i, so its descriptor is too
-    static_assert((BM / RPP) % NWV == 0, "X pieces must split evenly over the waves");
-    constexpr int XPW = BM / RPP / NWV;
+    constexpr int XPW = P::XPW;
     const int pl_x = (int)(unsigned)(a.x_lo * 2), pl_w = (int)(unsigned)(a.w_lo * 2);   // FMT_SPLIT: lo-plane byte offsets
 #pragma unroll
     for (int i = 0; i < NPW; ++i) {
@@ -98,9 +75,9 @@ __device__ __forceinline__ void gemm_bf16_tile(const GemmArgs& a, const int tile
         else { int wr = n0 + r; wr = wr < a.N ? wr : a.N - 1; voff[i] = ((wr - n0) * a.K + c * 8) * 2; }
         lds_off[i] = (isx_i ? 0 : XT) + (isx_i ? p : p - BM / RPP) * 1024;
     }
+    const int ntk = a.K / BK;
     // FMT_SPLIT: the K loop runs three segments over the same K range -- X.hi W.hi, X.lo W.hi, X.hi W.lo -- into one
     // accumulator; a k-tile index beyond K / BK selects the plane through the scalar offset only
-    const int ntk = a.K / BK;
     auto ksoff = [&](int kt, bool isx_i) -> int {
         if constexpr (FMT != FMT_SPLIT) return (a.kpat && isx_i) ? tap3_offset(kt * (BK * 2)) : kt * (BK * 2);
         else {
@@ -120,7 +97,7 @@ __device__ __forceinline__ void gemm_bf16_tile(const GemmArgs& a, const int tile
 
     // ---- fragment read addresses (bytes within a stage)
     const int frow = lane & 31;
-    const int swz = BK == 64 ? ((lane >> 1) & 7) : ((lane >> 2) & 3);   // swizzle key of row 32*j + (lane & 31)
+    const int swz = BK == 64 ? ((lane >> 1) & 7) : ((lane >> 2) & 3);   // swizzle key of row 32*j + (lane & 31): lds_key<RB>
     const int fhalf = lane >> 5;
     int koff[KK];
 #pragma unroll
@@ -313,8 +290,8 @@ __device__ __forceinline__ void gemm8_bf16_tile(const GemmArgs& a, const int til
     constexpr int BM = 32 * FM * WM, BN = 32 * FN * WN;
     constexpr int RB = 64;
     constexpr int XT = BM * RB, WT = BN * RB, STAGE = XT + WT;
-    constexpr int NP = (BM + BN) / 16;               // 1-KiB pieces (16 rows x 64 B) per step
-    constexpr int NPW_HI = (NP + 7) / 8, NPW_LO = NP / 8;
+    using P = LdsPieces<BM, BN, RB, 8>;              // 1-KiB pieces (16 rows x 64 B)
+    constexpr int NP = P::NP, NPW_HI = P::NPW_HI, NPW_LO = P::NPW_LO;
     static_assert(WM * WN == 8, "8 waves");
     unsigned long long tk_start = 0;
     if constexpr (VAR == 10) TSTAMP(tk_start);
@@ -322,7 +299,7 @@ __device__ __forceinline__ void gemm8_bf16_tile(const GemmArgs& a, const int til
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
     const int group = wave >> 2;                     // waves w and w+4 share a SIMD
     const int wm = wave / WN, wn = wave % WN;
-    const bool hi = wave < (NP % 8 == 0 ? 8 : NP % 8);   // this wave issues NPW_HI pieces per step
+    const bool hi = P::is_hi(wave);                  // this wave issues NPW_HI pieces per step
 
     const int tiles_n = (a.N + BN - 1) / BN;
     const int tiles_m = (a.M - a.m_begin + BM - 1) / BM;
@@ -335,8 +312,7 @@ __device__ __forceinline__ void gemm8_bf16_tile(const GemmArgs& a, const int til
     int voff[NPW_HI];
     int lds_off[NPW_HI];
     // pieces wave + 8 i with i < XPW are X rows for every wave: the operand (and its descriptor) of piece i is static
-    static_assert((BM / 16) % 8 == 0, "X pieces must split evenly over the 8 waves");
-    constexpr int XPW = BM / 16 / 8;
+    constexpr int XPW = P::XPW;
     const int pl_x = (int)(unsigned)(a.x_lo * 2), pl_w = (int)(unsigned)(a.w_lo * 2);   // FMT_SPLIT: lo-plane byte offsets
 #pragma unroll
     for (int i = 0; i < NPW_HI; ++i) {
@@ -504,7 +480,8 @@ __device__ __forceinline__ void gemm8u_bf16_tile(const GemmArgs& a, const int ti
     if constexpr (TRACE) TSTAMP(tk0);
     constexpr int BM = 256, BN = 256, RB = 64;
     constexpr int XT = BM * RB, STAGE = (BM + BN) * RB;
-    constexpr int NPW = 4;
+    using P = LdsPieces<BM, BN, RB, 8>;
+    constexpr int NPW = P::NPW;
     const int tid = threadIdx.x;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
     const int wm = wave / WN, wn = wave % WN;
@@ -515,7 +492,7 @@ __device__ __forceinline__ void gemm8u_bf16_tile(const GemmArgs& a, const int ti
     const __amdgpu_buffer_rsrc_t rx = make_rsrc(a.X + (size_t)m0 * a.ldx), rw = make_rsrc(a.W + (size_t)n0 * a.K);
     int voff[NPW];
     int lds_off[NPW];
-    constexpr int XPW = BM / 16 / 8;                 // pieces wave + 8 i with i < XPW are X rows for every wave
+    constexpr int XPW = P::XPW;                      // pieces wave + 8 i with i < XPW are X rows for every wave
     const int pl_x = (int)(unsigned)(a.x_lo * 2), pl_w = (int)(unsigned)(a.w_lo * 2);
 #pragma unroll
     for (int i = 0; i < NPW; ++i) {
@@ -694,7 +671,8 @@ __global__ __launch_bounds__(512, 2) void gemm8p_bf16_kernel(const GemmArgs a) {
     constexpr int FM = 4, FN = 2, WM = 2, WN = 4, EPI = EPI_BF16;
     constexpr int BM = 256, BN = 256, RB = 64;
     constexpr int XT = BM * RB, WT = BN * RB, STAGE = XT + WT;
-    constexpr int NPW = (BM + BN) / 16 / 8;          // 4 one-KiB pieces per wave and step
+    using P = LdsPieces<BM, BN, RB, 8>;
+    constexpr int NPW = P::NPW;                      // 4 one-KiB pieces per wave and step
     constexpr int NST = FM * (StagedEpi<FN, EPI>::CH / 2) * (FMT == FMT_SPLIT ? 2 : 1);   // global stores per wave in the staged epilogue: 16 (two planes: 32)
     static_assert(8 * StagedEpi<FN, EPI>::BYTES <= 2 * STAGE, "staging must stay inside ring slots 0 and 1");
     extern __shared__ __attribute__((aligned(256))) char smem[];
@@ -716,7 +694,7 @@ __global__ __launch_bounds__(512, 2) void gemm8p_bf16_kernel(const GemmArgs a) {
 
     int lds_off[NPW];
     int voff[NPW];                                   // this lane's byte offset inside its operand's tile rows: the SAME for every tile
-    constexpr int XPW = BM / 16 / 8;                 // pieces wave + 8 i with i < XPW (= 2) are X rows for every wave
+    constexpr int XPW = P::XPW;                      // pieces wave + 8 i with i < XPW (= 2) are X rows for every wave
 #pragma unroll
     for (int i = 0; i < NPW; ++i) {
         const int p = wave + 8 * i;

@@ -10,9 +10,9 @@
 //   * the scale of (row r, K block h) is taken from lane (r, h): byte OPSEL of that lane's scale register;
 //   * C/D layout as for every 32x32 MFMA: col = l & 31, row = (reg & 3) + 8 (reg >> 2) + 4 h.
 //
-// Structure (4 waves as 2x2, two workgroups per CU): tile (64 FM) x (64 FN), K step 128 BYTES — the same 128-byte
-// LDS rows, global_load_lds_dwordx4 staging and source-side XOR swizzle as the bf16 kernel (gemm_bf16.hip), so a
-// stage moves the same bytes but feeds twice the FLOPs.  2-slot ring with ONE barrier per K step: all fragments of
+// Structure (4 waves as 2x2, two workgroups per CU): tile (64 FM) x (64 FN), K step 128 BYTES — the LDS image of
+// lds_dma.h on 128-byte rows, as the bf16 kernel (gemm_bf16.hip), so a stage moves the same bytes but feeds twice
+// the FLOPs.  2-slot ring with ONE barrier per K step: all fragments of
 // tile t are read into registers, then (barrier) the slot is refilled with tile t+2 while the MFMAs of tile t issue,
 // the LDS-DMA instructions interleaved between them.  Scale words (4 bytes = the 4 K blocks of a stage per row) go
 // global -> VGPR one stage ahead (they are 3 % of the operand bytes and every lane needs exactly its own rows').
@@ -20,22 +20,9 @@
 #include "kernels.h"
 #include "gemm_epilogue.h"
 #include "gemm_epilogue_f8.h"
+#include "lds_dma.h"
 
-typedef __attribute__((address_space(3))) void* lds_vptr8;
-typedef const __attribute__((address_space(1))) void* glb_vptr8;
 typedef int v8i_t __attribute__((ext_vector_type(8)));
-
-__device__ __forceinline__ void glds16g(const void* g, void* l) {
-    __builtin_amdgcn_global_load_lds((glb_vptr8)g, (lds_vptr8)l, 16, 0, 0);
-}
-// the buffer-descriptor form (see gemm_bf16.hip): constant per-lane offset, the K step in the scalar offset
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t f8_make_rsrc(const void* base) {
-    return __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, (int)0xffffffffu, 0x00020000);
-}
-__device__ __forceinline__ void f8_glds16b(__amdgpu_buffer_rsrc_t rs, int voff, int soff, void* l) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_vptr8)l, 16, voff, soff, 0, 0);
-}
-#define F8_FENCE() __builtin_amdgcn_sched_barrier(0)
 
 // ---- quantiser: f32 rows -> MXFP8 (used for the weights at create time and by the op-level entry point) -------
 __global__ __launch_bounds__(256) void mx_quant_rows_kernel(const float* __restrict__ in, long ld_in, uint8_t* __restrict__ out,
@@ -72,8 +59,9 @@ __global__ __launch_bounds__(256, 2) void gemm_mxfp8_kernel(const GemmF8Args a) 
     constexpr int BM = 64 * FM, BN = 64 * FN;
     constexpr int RB = 128;                  // bytes (= fp8 elements) per LDS row = K step
     constexpr int XT = BM * RB, WT = BN * RB, STAGE = XT + WT;
-    constexpr int NP = (BM + BN) / 8;        // 1-KiB pieces per stage (8 rows each)
-    constexpr int NPW = NP / 4;
+    using P = LdsPieces<BM, BN, RB, 4>;
+    constexpr int NP = P::NP;                // 1-KiB pieces per stage (8 rows each)
+    constexpr int NPW = P::NPW;
     constexpr int NMT = 2 * FM * FN;         // MFMAs per stage per wave
     static_assert(NP % 4 == 0, "tile must split evenly over 4 waves");
     const int tid = threadIdx.x;
@@ -84,11 +72,10 @@ __global__ __launch_bounds__(256, 2) void gemm_mxfp8_kernel(const GemmF8Args a) 
     const int wg = xcd_remap(blockIdx.x, tiles_m * tiles_n);
     const int m0 = (wg / tiles_n) * BM, n0 = (wg % tiles_n) * BN;
 
-    // ---- staging (identical byte geometry to the bf16 kernel's 128-byte rows)
+    // ---- staging (lds_dma.h, 128-byte rows)
     const int srow = lane >> 3, spos = lane & 7;
-    static_assert((BM / 8) % 4 == 0, "X pieces must split evenly over the 4 waves");
-    constexpr int XPW = BM / 8 / 4;
-    const __amdgpu_buffer_rsrc_t rx = f8_make_rsrc(a.X8 + (size_t)m0 * a.ldx8), rw = f8_make_rsrc(a.W8 + (size_t)n0 * K);
+    constexpr int XPW = P::XPW;
+    const __amdgpu_buffer_rsrc_t rx = make_rsrc(a.X8 + (size_t)m0 * a.ldx8), rw = make_rsrc(a.W8 + (size_t)n0 * K);
     int voff[NPW];
     int lds_off[NPW];
 #pragma unroll
@@ -96,12 +83,12 @@ __global__ __launch_bounds__(256, 2) void gemm_mxfp8_kernel(const GemmF8Args a) 
         const int p = wave + 4 * i;
         const bool isx = i < XPW;
         const int r = (isx ? p : p - BM / 8) * 8 + srow;
-        const int c = spos ^ ((r >> 1) & 7);
+        const int c = lds_src_chunk<RB>(r, spos);
         if (isx) { int xm = m0 + r; xm = xm < M ? xm : M - 1; voff[i] = (int)((long)(xm - m0) * a.ldx8 + c * 16); }
         else { int wr = n0 + r; wr = wr < N ? wr : N - 1; voff[i] = (wr - n0) * K + c * 16; }
         lds_off[i] = (isx ? 0 : XT) + (isx ? p : p - BM / 8) * 1024;
     }
-    auto dma1 = [&](int kt, int i, char* base) { f8_glds16b(i < XPW ? rx : rw, voff[i], kt * RB, base + lds_off[i]); };
+    auto dma1 = [&](int kt, int i, char* base) { glds16b(i < XPW ? rx : rw, voff[i], kt * RB, base + lds_off[i]); };
     auto stage = [&](int kt, int slot) {
         char* base = smem + slot * STAGE;
 #pragma unroll
@@ -110,10 +97,10 @@ __global__ __launch_bounds__(256, 2) void gemm_mxfp8_kernel(const GemmF8Args a) 
 
     // ---- fragment addresses: MFMA j of a stage reads 16-byte chunks 4j + h and 4j + 2 + h of its row
     const int frow = lane & 31, fhalf = lane >> 5;
-    const int swz = (lane >> 1) & 7;
+    const int swz = frag32_key<RB>(lane);
     int koff[2][2];
 #pragma unroll
-    for (int j = 0; j < 2; ++j) { koff[j][0] = ((4 * j + fhalf) ^ swz) << 4; koff[j][1] = ((4 * j + 2 + fhalf) ^ swz) << 4; }
+    for (int j = 0; j < 2; ++j) { koff[j][0] = lds_koff(4 * j + fhalf, swz); koff[j][1] = lds_koff(4 * j + 2 + fhalf, swz); }
     const int xrow_off = (wm * 32 * FM + frow) * RB;
     const int wrow_off = XT + (wn * 32 * FN + frow) * RB;
 
@@ -179,7 +166,7 @@ __global__ __launch_bounds__(256, 2) void gemm_mxfp8_kernel(const GemmF8Args a) 
         // have landed, so the next iteration may read the other slot
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
-        F8_FENCE();
+        SCHED_FENCE();
         if (t + 1 < nt) load_scales(t + 1, xs_n, ws_n);
         const bool refill = t + 2 < nt;
         char* dbase = smem + slot * STAGE;
@@ -194,9 +181,9 @@ __global__ __launch_bounds__(256, 2) void gemm_mxfp8_kernel(const GemmF8Args a) 
 #pragma unroll
             for (int p = 0; p < NPW; ++p) {
                 if (((p + 1) * NMT + NPW - 1) / NPW - 1 == i) {
-                    F8_FENCE();
+                    SCHED_FENCE();
                     if (refill) dma1(t + 2, p, dbase);
-                    F8_FENCE();
+                    SCHED_FENCE();
                 }
             }
         }
@@ -225,16 +212,15 @@ __global__ __launch_bounds__(256, 2) void gemm_mxfp8_kernel(const GemmF8Args a) 
 // MFMA cycles as the bf16 kernel's 32-wide step but contracts twice the K.  The scales ride along as ONE extra
 // 1-KiB LDS-DMA piece per step: lanes 0-31 fetch the X scales of 8 rows each (16 contiguous bytes in the
 // K-pair-major layout), lanes 32-63 the W scales; a lane then reads its (row, half) byte with ds_read_u8.
-template <int N> __device__ __forceinline__ void f8_wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 
 template <int FM, int FN, int WM, int WN, int EPI, int ACT>
 __global__ __launch_bounds__(512, 2) void gemm8_mxfp8_kernel(const GemmF8Args a) {
     constexpr int BM = 32 * FM * WM, BN = 32 * FN * WN;
     constexpr int RB = 64;
     constexpr int XT = BM * RB, WT = BN * RB, SC = 1024, STAGE = XT + WT + SC;
-    constexpr int NPT = (BM + BN) / 16;              // operand pieces (16 rows x 64 B) per step
-    constexpr int NP = NPT + 1;                      // + the scale piece
-    constexpr int NPW_HI = (NP + 7) / 8, NPW_LO = NP / 8;
+    using P = LdsPieces<BM, BN, RB, 8, 1>;           // + the scale piece
+    constexpr int NPT = P::NPT;                      // operand pieces (16 rows x 64 B) per step
+    constexpr int NP = P::NP, NPW_HI = P::NPW_HI, NPW_LO = P::NPW_LO;
     constexpr int NMF = FM * FN;
     static_assert(WM * WN == 8, "8 waves");
     static_assert(BM <= 256 && BN <= 256, "one scale piece covers 256 + 256 rows");
@@ -243,7 +229,7 @@ __global__ __launch_bounds__(512, 2) void gemm8_mxfp8_kernel(const GemmF8Args a)
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
     const int group = wave >> 2;
     const int wm = wave / WN, wn = wave % WN;
-    const bool hi = wave < (NP % 8 == 0 ? 8 : NP % 8);
+    const bool hi = P::is_hi(wave);
     const int M = a.g.M, N = a.g.N, K = a.g.K;
     const int tiles_n = (N + BN - 1) / BN, tiles_m = (M + BM - 1) / BM;
     const int wg = xcd_remap(blockIdx.x, tiles_m * tiles_n);
@@ -253,9 +239,8 @@ __global__ __launch_bounds__(512, 2) void gemm8_mxfp8_kernel(const GemmF8Args a)
     // operand pieces go through buffer descriptors (one per operand, based at the tile's first row): the per-lane
     // offset is a constant 32-bit VGPR and the K step rides in the scalar offset, so a step costs no address VALU.
     // The scale piece keeps the flat form: its two lane halves read two different arrays.
-    static_assert((BM / 16) % 8 == 0, "X pieces must split evenly over the 8 waves");
-    constexpr int XPW = BM / 16 / 8;                 // pieces wave + 8 i with i < XPW are X rows for every wave
-    const __amdgpu_buffer_rsrc_t rx = f8_make_rsrc(a.X8 + (size_t)m0 * a.ldx8), rw = f8_make_rsrc(a.W8 + (size_t)n0 * K);
+    constexpr int XPW = P::XPW;                      // pieces wave + 8 i with i < XPW are X rows for every wave
+    const __amdgpu_buffer_rsrc_t rx = make_rsrc(a.X8 + (size_t)m0 * a.ldx8), rw = make_rsrc(a.W8 + (size_t)n0 * K);
     int voff[NPW_HI];
     int lds_off[NPW_HI];
     const uint8_t* gsc;                              // scale piece source of this lane and its bytes per K step
@@ -280,8 +265,8 @@ __global__ __launch_bounds__(512, 2) void gemm8_mxfp8_kernel(const GemmF8Args a)
     }
     auto dma1 = [&](int ks, int i, char* base) {
         // only the last piece slot of a wave can be the scale piece (wave-uniform)
-        if (i == NPW_HI - 1 && is_sc[i]) glds16g(gsc + (size_t)ks * gsc_step, base + lds_off[i]);
-        else f8_glds16b(i < XPW ? rx : rw, voff[i], ks * RB, base + lds_off[i]);
+        if (i == NPW_HI - 1 && is_sc[i]) glds16(gsc + (size_t)ks * gsc_step, base + lds_off[i]);
+        else glds16b(i < XPW ? rx : rw, voff[i], ks * RB, base + lds_off[i]);
     };
     auto stage = [&](int ks, int slot) {
         char* base = smem + slot * STAGE;
@@ -291,9 +276,9 @@ __global__ __launch_bounds__(512, 2) void gemm8_mxfp8_kernel(const GemmF8Args a)
     };
     auto wait_steps = [&](int nsteps_in_flight) {
         if (hi) {
-            if (nsteps_in_flight >= 2) f8_wait_vmcnt<2 * NPW_HI>(); else if (nsteps_in_flight == 1) f8_wait_vmcnt<NPW_HI>(); else f8_wait_vmcnt<0>();
+            if (nsteps_in_flight >= 2) wait_vmcnt<2 * NPW_HI>(); else if (nsteps_in_flight == 1) wait_vmcnt<NPW_HI>(); else wait_vmcnt<0>();
         } else {
-            if (nsteps_in_flight >= 2) f8_wait_vmcnt<2 * NPW_LO>(); else if (nsteps_in_flight == 1) f8_wait_vmcnt<NPW_LO>(); else f8_wait_vmcnt<0>();
+            if (nsteps_in_flight >= 2) wait_vmcnt<2 * NPW_LO>(); else if (nsteps_in_flight == 1) wait_vmcnt<NPW_LO>(); else wait_vmcnt<0>();
         }
     };
 
@@ -326,7 +311,7 @@ __global__ __launch_bounds__(512, 2) void gemm8_mxfp8_kernel(const GemmF8Args a)
     for (int s = 0; s < nt; ++s) {
         const char* sb = smem + slot * STAGE;
         // ---- A: fragments + scales of step s; retire step s+1
-        F8_FENCE();
+        SCHED_FENCE();
         v8i_t xf[FM], wf[FN];
         int xsc[FM], wsc[FN];
 #pragma unroll
@@ -348,9 +333,9 @@ __global__ __launch_bounds__(512, 2) void gemm8_mxfp8_kernel(const GemmF8Args a)
             wait_steps(after >= 1 ? 1 : 0);
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        F8_FENCE();
+        SCHED_FENCE();
         __builtin_amdgcn_s_barrier();
-        F8_FENCE();
+        SCHED_FENCE();
         // ---- B: MFMAs of step s with the LDS-DMA of step s+3 spread between them (slot of step s-1)
         const bool dma = s + 3 < nt;
         char* dbase = smem + ((slot + 3) & 3) * STAGE;
@@ -362,14 +347,14 @@ __global__ __launch_bounds__(512, 2) void gemm8_mxfp8_kernel(const GemmF8Args a)
 #pragma unroll
             for (int q = 0; q < NPW_HI; ++q) {
                 if (((q + 1) * NMF + NPW_HI - 1) / NPW_HI - 1 == i) {
-                    F8_FENCE();
+                    SCHED_FENCE();
                     if (dma && (q < NPW_LO || hi)) dma1(s + 3, q, dbase);
-                    F8_FENCE();
+                    SCHED_FENCE();
                 }
             }
         }
         __builtin_amdgcn_s_setprio(0);
-        F8_FENCE();
+        SCHED_FENCE();
         __builtin_amdgcn_s_barrier();
         slot = (slot + 1) & 3;
     }

@@ -17,16 +17,7 @@
 // so its K loop is DMA-bound (52 one-KiB pieces per step against 768 MFMA cycles per SIMD), which is why it is used only
 // where the fused LayerNorm pays for it: K = 768 (out-proj).  Measured same-box against GEMM + LayerNorm: DESIGN.md §6.
 #include "kernels.h"
-
-typedef __attribute__((address_space(3))) void* lds_vptr_r;
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc_r(const void* base) {
-    return __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, (int)0xffffffffu, 0x00020000);
-}
-__device__ __forceinline__ void glds16r(__amdgpu_buffer_rsrc_t rs, int voff, int soff, void* l) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_vptr_r)l, 16, voff, soff, 0, 0);
-}
-template <int N> __device__ __forceinline__ void wait_vmcnt_r() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-#define RL_FENCE() __builtin_amdgcn_sched_barrier(0)
+#include "lds_dma.h"
 
 #define RL_BM 64
 #define RL_N 768
@@ -46,7 +37,7 @@ __global__ __launch_bounds__(512, 2) void gemm_rowln_kernel(const GemmArgs a) {
     // ---- staging.  Pieces (16 rows x 64 B) 0..47 are W rows, 48..51 the X rows: piece wave + 8 i is a W piece for every
     // wave when i < 6; i == 6 is the X piece of waves 0..3 (waves 4..7 have none)
     const int srow = lane >> 2, spos = lane & 3;
-    const __amdgpu_buffer_rsrc_t rx = make_rsrc_r(a.X + (size_t)m0 * a.ldx), rw = make_rsrc_r(a.W);
+    const __amdgpu_buffer_rsrc_t rx = make_rsrc(a.X + (size_t)m0 * a.ldx), rw = make_rsrc(a.W);
     int voff[7], lds_off[7];
 #pragma unroll
     for (int i = 0; i < 7; ++i) {
@@ -60,15 +51,15 @@ __global__ __launch_bounds__(512, 2) void gemm_rowln_kernel(const GemmArgs a) {
     }
     const bool has_x = wave < 4;
     auto dma1 = [&](int ks, int i, char* base) {
-        if (i == 6) { if (has_x) glds16r(rx, voff[6], ks * 64, base + lds_off[6]); }
-        else glds16r(rw, voff[i], ks * 64, base + lds_off[i]);
+        if (i == 6) { if (has_x) glds16b(rx, voff[6], ks * 64, base + lds_off[6]); }
+        else glds16b(rw, voff[i], ks * 64, base + lds_off[i]);
     };
     auto stage = [&](int ks, int slot) {
 #pragma unroll
         for (int i = 0; i < 7; ++i) dma1(ks, i, smem + slot * RL_STAGE);
     };
     // my pieces per step: 7 (waves 0..3) or 6; "first half" = pieces 0..2, issued before the step's barrier
-    auto wait_keep3 = [&]() { wait_vmcnt_r<3>(); };
+    auto wait_keep3 = [&]() { wait_vmcnt<3>(); };
 
     const int frow = lane & 31, swz = (lane >> 2) & 3, fhalf = lane >> 5;
     const int koff0 = (((0 + fhalf) ^ swz) << 4), koff1 = (((2 + fhalf) ^ swz) << 4);
@@ -96,9 +87,9 @@ __global__ __launch_bounds__(512, 2) void gemm_rowln_kernel(const GemmArgs a) {
             acc[fm][fn] = H16<FMT>::mfma(wf[buf][fn], xf[buf][fm], acc[fm][fn]);
             const int q = p0 + i - 1;
             if (i >= 1 && q < p1) {
-                RL_FENCE();
+                SCHED_FENCE();
                 if (on) dma1(ks, q, dbase);
-                RL_FENCE();
+                SCHED_FENCE();
             }
         }
     };
@@ -106,7 +97,7 @@ __global__ __launch_bounds__(512, 2) void gemm_rowln_kernel(const GemmArgs a) {
     stage(0, 0);
     if (nt > 1) stage(1, 1);
     // step 0 landed; younger: step 1 (7 or 6 pieces)
-    if (nt > 1) { if (has_x) wait_vmcnt_r<7>(); else wait_vmcnt_r<6>(); } else wait_vmcnt_r<0>();
+    if (nt > 1) { if (has_x) wait_vmcnt<7>(); else wait_vmcnt<6>(); } else wait_vmcnt<0>();
     __builtin_amdgcn_s_barrier();
     read_frags(smem, koff0, 0);
     int slot = 0;
@@ -115,19 +106,19 @@ __global__ __launch_bounds__(512, 2) void gemm_rowln_kernel(const GemmArgs a) {
         const int nslot = slot == 2 ? 0 : slot + 1;
         char* dbase = smem + (slot == 0 ? 2 : slot - 1) * RL_STAGE;     // slot of step s-1 = slot of step s+2
         const bool dma = s + 2 < nt;
-        RL_FENCE();
+        SCHED_FENCE();
         read_frags(sb, koff1, 1);
-        RL_FENCE();
+        SCHED_FENCE();
         mfmas_dma(0, s + 2, dbase, 0, 3, dma);
-        RL_FENCE();
+        SCHED_FENCE();
         if (s + 1 < nt) {
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             // my pieces of step s+1 have landed; younger: pieces 0..2 of step s+2
-            if (dma) wait_keep3(); else wait_vmcnt_r<0>();
+            if (dma) wait_keep3(); else wait_vmcnt<0>();
             __builtin_amdgcn_s_barrier();
-            RL_FENCE();
+            SCHED_FENCE();
             read_frags(smem + nslot * RL_STAGE, koff0, 0);
-            RL_FENCE();
+            SCHED_FENCE();
         }
         mfmas_dma(1, s + 2, dbase, 3, 7, dma);
         slot = nslot;

@@ -14,6 +14,7 @@
 // Orientation is "lane = frame" (A = weights, B = activations) so the epilogue adds the fp32 residual
 // and stores 16-byte runs.
 #include "kernels.h"
+#include "lds_dma.h"
 
 #define PC_BM 256                 // frames per workgroup (8 waves x 32): a weight slab read from L2 serves 256 frames
 #define PC_XROW 112               // bytes per staged x row (48 bf16 + 16 B pad)
@@ -22,13 +23,6 @@
 #define PC_TAPS_PER_STEP 2
 #define PC_STEP (PC_TAPS_PER_STEP * PC_SLAB)   // 14336
 #define PC_LDS (PC_XWIN + 2 * PC_STEP)         // 71680: two workgroups per CU
-
-typedef __attribute__((address_space(3))) void* lds_vptr;
-typedef const __attribute__((address_space(1))) void* glb_vptr;
-// LDS-DMA through a buffer descriptor: constant per-lane offset, the weight step in the scalar offset
-__device__ __forceinline__ void glds16p(__amdgpu_buffer_rsrc_t rs, int voff, int soff, void* l) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_vptr)l, 16, voff, soff, 0, 0);
-}
 
 template <int ACT, int FMT>
 __global__ __launch_bounds__(512, 4) void posconv_bf16_kernel(const bf16_t* __restrict__ xpad, const bf16_t* __restrict__ wpk,
@@ -83,13 +77,13 @@ __global__ __launch_bounds__(512, 4) void posconv_bf16_kernel(const bf16_t* __re
     }
     // ---- weight ring: a step = 2 taps = 14 KiB = 14 wave-instructions; wave w issues pieces w and w + 8
     const char* wg_base = (const char*)(wpk + (pass == 2 ? w_lo : 0L)) + (size_t)g * SYL_POSK * PC_SLAB;
-    const __amdgpu_buffer_rsrc_t rwg = __builtin_amdgcn_make_buffer_rsrc((void*)wg_base, 0, (int)0xffffffffu, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rwg = make_rsrc(wg_base);
     auto stage = [&](int step, int buf) {
         char* dst = wring + buf * PC_STEP;
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
             const int piece = wave + 8 * i;
-            if (piece < 14) glds16p(rwg, piece * 1024 + lane * 16, step * PC_STEP, dst + piece * 1024);
+            if (piece < 14) glds16b(rwg, piece * 1024 + lane * 16, step * PC_STEP, dst + piece * 1024);
         }
     };
 
