@@ -618,6 +618,46 @@ int sylber_unit_strings_align(const int32_t* ref_units_dev, const int32_t* ref_o
                               int32_t* subs_dev, int32_t* ops_dev, int32_t* cost_dev, int32_t* ops_walk_dev /* nullable */,
                               void* workspace_dev, void* stream);
 
+/* Unit repeats (sylber_amd/units.py: local_align_unit_strings / UnitIndex.find_repeats; csrc/unit_repeats.hip; restated in
+ * tests/unit_repeats_ref.py): what is said in BOTH of two recordings, found without a query -- the local alignment
+ * (Smith-Waterman) of two unit strings, the best-scoring pair of sub-spans, many pairs per call.  A pair is a string x of m units
+ * and a string y of L units, 0 <= m, L <= 65 536; a unit is a row of W ids, 1 <= W <= 8, ids in 0 .. 2^31 - 1; sub(i, j) = the
+ * number of columns in which x[i] and y[j] differ.  Parameters: 1 <= match <= 64 (2), 0 <= mismatch <= 64 (3), 1 <= gap <= 64
+ * (4).  The DP, all int32 (scores stay below 64 * 8 * 65 536):
+ *     s(i, j)  = match * (W - sub(i, j)) - mismatch * sub(i, j)
+ *     H[i][-1] = H[-1][j] = 0
+ *     c_diag   = H[i-1][j-1] + s(i, j)     start: start[i-1][j-1] if H[i-1][j-1] > 0, else (i, j)
+ *     c_up     = H[i-1][j]   - gap * W     start: start[i-1][j]
+ *     c_left   = H[i][j-1]   - gap * W     start: start[i][j-1]
+ *     v        = the first largest of (c_diag, c_up, c_left), in that order
+ *     H[i][j]  = v if v > 0 else 0         start[i][j] = that candidate's start (unused where H = 0)
+ *   x is the rows and y the columns: the ties depend on it, so the two are not exchanged.
+ *   Outputs per pair: its best cell (i, j) = the largest H[i][j], on equal values the smallest i, then the smallest j.
+ *   score = H[i][j]; with (si, sj) = start[i][j] the spans are x[si : i + 1] and y[sj : j + 1], written as
+ *   span = (a0, a1, b0, b1) = (si, i + 1, sj, j + 1), positions INSIDE the two windows.  A pair without a positive cell -- an empty
+ *   side included -- has score 0 and span (-1, -1, -1, -1).
+ *   Consequences.  Both spans are non-empty: the first and the last step of the path are diagonal steps with s > 0.  When
+ *   gap = mismatch + match / 2 with match even, score = match * W * ((a1 - a0) + (b1 - b0)) / 2 - (match + mismatch) * cost, cost =
+ *   the weighted Levenshtein distance of the two spans ("Unit strings"); under the defaults score = W * (len_x + len_y) - 5 cost.
+ *   Nothing returned depends on what the workspace held, on which pairs share a call or on their order: a pair touches only its
+ *   own slice of the workspace and its own outputs.
+ * sylber_unit_local_align: x_units_dev [x_rows, W] and y_units_dev [y_rows, W] int32 on the device; x_win_host and y_win_host
+ *   [n_pairs, 2] int32 = (first row, number of rows) of each pair's window into its buffer.  The two buffers may be the same
+ *   buffer, windows may overlap and may repeat: that is how one corpus is aligned against itself.  The windows are read before the
+ *   call returns, everything else is enqueued on `stream`.  score_dev [n_pairs], span_dev [n_pairs, 4] int32.
+ *   workspace_dev: sylber_unit_local_workspace_bytes of the same windows, host arithmetic on the lengths (-1 on a bad argument),
+ *   every term rounded up to 256 B:
+ *       40 B per pair of table
+ *     + 24 L per pair with m > 64 and L > 0: two rows of (H, si, sj), 12 B per column, between strips of 64 rows of x, at most
+ *       1.5 MiB.
+ *   A null pointer, W outside 1..8, n_pairs < 1, match, mismatch or gap outside its range, a window with a negative length or of
+ *   more than 65 536 rows and a window outside its buffer return 1 with sylber_last_error before any device call. */
+int64_t sylber_unit_local_workspace_bytes(const int32_t* x_win_host, const int32_t* y_win_host, int32_t n_pairs);
+int sylber_unit_local_align(const int32_t* x_units_dev, int32_t x_rows, const int32_t* y_units_dev, int32_t y_rows, int32_t W,
+                            const int32_t* x_win_host, const int32_t* y_win_host, int32_t n_pairs, int32_t match, int32_t mismatch,
+                            int32_t gap, int32_t* score_dev /* [n_pairs] */, int32_t* span_dev /* [n_pairs, 4] */,
+                            void* workspace_dev, void* stream);
+
 /* Warping paths (sylber_amd/search.py: SyllableIndex.align_phrases; restated in tests/align_ref.py): HOW a phrase matches a
  * window of rows -- which stored rows each phrase row is warped onto -- where the searches above report only where.  For one pair
  * (phrase of m rows, window [a, b) of row ids, W = b - a):

@@ -7,7 +7,9 @@ and returns the edit script of each match: the stored row every phrase unit is p
 inserted counts (csrc/unit_align.hip, "Edit scripts", tests/unit_align_ref.py); in global mode that is the weighted Levenshtein
 distance of two unit strings, for a phrase of at most 64 units.  ``align_unit_strings`` and ``unit_error_rate`` align WHOLE unit
 strings of any length up to 65 536 units, pair by pair, without an index (csrc/unit_strings.hip, "Unit strings",
-tests/unit_strings_ref.py): how far two tokenisations of the same audio are from each other.  The argument rules ``UnitIndex``
+tests/unit_strings_ref.py): how far two tokenisations of the same audio are from each other.  ``local_align_unit_strings`` and
+``UnitIndex.find_repeats`` need no query: the local alignment of two unit strings, i.e. the phrase that both recordings hold, pair
+by pair or over every pair of sequences of an index (csrc/unit_repeats.hip, "Unit repeats", tests/unit_repeats_ref.py).  The argument rules ``UnitIndex``
 shares with the syllable indexes are ``_index.py``'s, the span checks of ``align_phrases`` are search.py's."""
 from __future__ import annotations
 
@@ -28,6 +30,8 @@ ALIGN_CHUNK_COLS = 32           # UA_CH of csrc/unit_align.hip: the anti-diagona
 MAX_WIDTH = 8                   # US_MAX_W: ids per unit
 STRING_ROWS = 64                # UT_ROWS of csrc/unit_strings.hip: the reference rows of a strip
 MAX_STRING_UNITS = 65536        # UT_MAX_LEN: the units of one string of align_unit_strings
+MAX_LOCAL_PARAM = 64            # UL_MAX_PARAM of csrc/unit_repeats.hip: match, mismatch and gap of a local alignment
+REPEAT_PAIRS = 1 << 16          # the pairs of sequences that find_repeats enumerates on the host at a time
 FORMAT = "sylber_amd.UnitIndex/1"
 _i32p = ctypes.POINTER(ctypes.c_int32)
 
@@ -354,6 +358,90 @@ class UnitIndex:
                                                      _vp(ws), st), "sylber_unit_align")
         return cols.to(torch.int64).reshape(P, k, Mx), subs.reshape(P, k, Mx), ops.reshape(P, k, 4), costs.reshape(P, k)
 
+    # ---- repeats --------------------------------------------------------------------------------------------------------------------
+    def find_repeats(self, k: int, *, min_score=None, match: int = 2, mismatch: int = 3, gap: int = 4, sequences=None,
+                     exclude_same_group: bool = False, pair_chunk: Optional[int] = None,
+                     _workspace_fill=None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """what is said more than once, found without a query: the k best repeats between two sequences of the index ->
+        ``(scores int32 [k], pairs int64 [k, 2], spans int64 [k, 2, 2])`` on the device.  Every pair of sequences ``(s, t)`` with
+        ``s < t`` is aligned locally (``local_align_unit_strings``: Smith-Waterman with ``match``, ``mismatch``, ``gap``; contract
+        in include/sylber_hip.h "Unit repeats") with x = sequence ``s`` and y = sequence ``t``; a pair is kept when ``score >=
+        min_score`` (``None``: ``3 * match * W``, three exactly repeated units; else an integer >= 1), and the k best kept pairs
+        are returned ordered by (score descending, s, t).  ``pairs[r] = (s, t)``; ``spans[r] = ((a0, a1), (b0, b1))`` are ROW IDS
+        of the index (first, one past the last) in sequence ``s`` and in sequence ``t``, so ``provenance`` and
+        ``align_phrases(..., free_start=False)`` work on them.  Shorter lists end in score 0, pairs ``(-1, -1)`` and spans -1.
+
+        Sequences are the index's or those of ``sequences=``, as the searches take them; with ``exclude_same_group`` pairs whose
+        two sequences share a group (a sequence's group is its first row's) are skipped.  Pairs are enumerated on the host in
+        chunks and both windows of a pair point into the one stored ``units`` buffer.
+
+        Exact (small integers): nothing returned depends on ``pair_chunk`` (the pairs per launch; by default as many as keep a
+        launch's workspace below ``search.ALIGN_WORKSPACE_BYTES``), on stale workspace contents, on one ``add`` against many or on
+        a ``save`` / ``load`` round trip.  ``ValueError`` before any launch: an empty index, ``k < 1``, ``min_score < 1``, a
+        parameter outside its range, ``pair_chunk < 1``, a sequence of more than 65 536 rows.  Fewer than two sequences: padding
+        only, without a launch.
+
+        Out of scope: repeats inside one sequence (cut the recording with ``sequences=``); more than one repeat per pair of
+        sequences (Waterman-Eggert suppression is the known next step); the same on embeddings (``SyllableIndex``)."""
+        N, dev, W = len(self), self.device, self.width
+        if N == 0:
+            raise ValueError("the index is empty")
+        if isinstance(k, bool) or int(k) != k or int(k) < 1:
+            raise ValueError("k must be an integer >= 1, got %r" % (k,))
+        k = int(k)
+        params = _local_params(match, mismatch, gap)
+        pair_chunk = _check_pair_chunk(pair_chunk)
+        if min_score is None:
+            floor = 3 * params[0] * W
+        elif isinstance(min_score, bool) or not isinstance(min_score, (int, np.integer)) or int(min_score) < 1:
+            raise ValueError("min_score must be None or an integer >= 1, got %r" % (min_score,))
+        else:
+            floor = int(min_score)
+        off = _sequences(sequences, N, self.sequence_offsets)
+        S = int(off.size - 1)
+        scores = torch.zeros((k,), dtype=torch.int32, device=dev)
+        pairs = torch.full((k, 2), -1, dtype=torch.int64, device=dev)
+        spans = torch.full((k, 4), -1, dtype=torch.int64, device=dev)
+        if S < 2:
+            return scores, pairs, spans.reshape(k, 2, 2)
+        lib = _lib.load()
+        lens = np.diff(off)
+        grp = self._g.index_select(0, torch.from_numpy(off[:-1]).to(dev)).cpu().numpy() if exclude_same_group else None
+        # pair (s, t), s < t, is number first[s] + t - s - 1 of the enumeration by (s, t)
+        idx = np.arange(S, dtype=np.int64)
+        first, total = idx * S - idx * (idx + 1) // 2, S * (S - 1) // 2
+        step = pair_chunk if pair_chunk is not None else REPEAT_PAIRS
+        best = None                                         # the kept pairs so far: (scores, s, t, spans), in the contract's order
+        for p0 in range(0, total, step):
+            p = np.arange(p0, min(total, p0 + step), dtype=np.int64)
+            s = np.searchsorted(first, p, side="right") - 1
+            t = p - first[s] + s + 1
+            if grp is not None:
+                other = grp[s] != grp[t]
+                s, t = s[other], t[other]
+            n = int(s.size)
+            if n == 0:
+                continue
+            xw, yw = (np.ascontiguousarray(np.stack([off[q], lens[q]], 1), np.int32) for q in (s, t))
+            sc = torch.empty((n,), dtype=torch.int32, device=dev)
+            sp = torch.empty((n, 4), dtype=torch.int32, device=dev)
+            _local_launch(lib, self._u, self._u, W, xw, yw, params, sc, sp, 0, pair_chunk, _workspace_fill, dev)
+            keep = (sc >= floor).nonzero().flatten()
+            if keep.numel() == 0:
+                continue
+            st = torch.from_numpy(np.stack([s, t], 1)).to(dev).index_select(0, keep)
+            base = torch.from_numpy(np.stack([off[s], off[s], off[t], off[t]], 1)).to(dev).index_select(0, keep)
+            new = (sc.index_select(0, keep), st, sp.index_select(0, keep).to(torch.int64) + base)
+            if best is not None:
+                new = tuple(torch.cat([a, b]) for a, b in zip(best, new))
+            # what was kept before comes from earlier pairs and is in order: a stable sort by score alone keeps (s, t) ascending
+            order = torch.sort(-new[0].to(torch.int64), stable=True).indices[:k]
+            best = tuple(a.index_select(0, order) for a in new)
+        if best is not None:
+            n = int(best[0].shape[0])
+            scores[:n], pairs[:n], spans[:n] = best
+        return scores, pairs, spans.reshape(k, 2, 2)
+
     # ---- persistence ----------------------------------------------------------------------------------------------------------------
     def save(self, path: str) -> None:
         """``.npz`` with the units, groups, provenance and a format tag; a round trip gives the same results bit for bit"""
@@ -585,3 +673,119 @@ def unit_error_rate(refs, hyps, **kw) -> UnitErrorRate:
         raise TypeError("unit_error_rate: unexpected arguments %s" % sorted(kw))
     _, _, ops, costs, ro, hl, W = _align_strings(refs, hyps, False, device, pair_chunk, fill, need_ref_units=True)
     return UnitErrorRate(ops, costs, int(ro[-1]), int(hl.sum()), W)
+
+
+# ---- unit repeats -------------------------------------------------------------------------------------------------------------------
+def unit_local_workspace_bytes(m, L) -> np.ndarray:
+    """int64: the bytes of workspace that each pair (``m`` units of x, ``L`` units of y; arrays) adds to a launch of
+    ``sylber_unit_local_align`` beyond its 40 B of table: two rows of 12 B per column between strips where ``m > 64``"""
+    m, L = np.asarray(m, np.int64), np.asarray(L, np.int64)
+    return np.where((m > STRING_ROWS) & (L > 0), (24 * L + 255) // 256 * 256, 0)
+
+
+def _local_params(match, mismatch, gap) -> Tuple[int, int, int]:
+    """the three scores of a local alignment as ints, or ``ValueError``"""
+    out = []
+    for name, v, lo in (("match", match, 1), ("mismatch", mismatch, 0), ("gap", gap, 1)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= int(v) <= MAX_LOCAL_PARAM:
+            raise ValueError("%s must be an integer in [%d, %d], got %r" % (name, lo, MAX_LOCAL_PARAM, v))
+        out.append(int(v))
+    return tuple(out)
+
+
+def _check_pair_chunk(pair_chunk) -> Optional[int]:
+    if pair_chunk is None:
+        return None
+    if isinstance(pair_chunk, bool) or int(pair_chunk) != pair_chunk or int(pair_chunk) < 1:
+        raise ValueError("pair_chunk must be an integer >= 1, got %r" % (pair_chunk,))
+    return int(pair_chunk)
+
+
+def _local_launch(lib, xd, yd, W, xw, yw, params, scores, spans, at, pair_chunk, fill, dev) -> None:
+    """``sylber_unit_local_align`` on the pairs of the windows ``xw`` / ``yw`` (int32 ``[n, 2]`` on the host, ``n >= 1``) into
+    ``scores[at : at + n]`` and ``spans[at : at + n]``: ``pair_chunk`` pairs per launch, or as many as keep a launch's workspace
+    below ``ALIGN_WORKSPACE_BYTES``"""
+    n = int(xw.shape[0])
+    if pair_chunk is not None:
+        cuts = list(range(0, n, pair_chunk)) + [n]
+    else:
+        need = unit_local_workspace_bytes(xw[:, 1], yw[:, 1]) + 40
+        cuts, acc = [0], np.concatenate([[0], np.cumsum(need)])
+        while cuts[-1] < n:
+            cuts.append(max(cuts[-1] + 1, int(np.searchsorted(acc, acc[cuts[-1]] + ALIGN_WORKSPACE_BYTES - 256, side="right")) - 1))
+    groups = []
+    for g0, g1 in zip(cuts[:-1], cuts[1:]):
+        a, b = np.ascontiguousarray(xw[g0:g1]), np.ascontiguousarray(yw[g0:g1])
+        size = int(lib.sylber_unit_local_workspace_bytes(a.ctypes.data_as(_i32p), b.ctypes.data_as(_i32p), g1 - g0))
+        if size < 0:
+            raise _lib.SylberHipError("sylber_unit_local_workspace_bytes refused the call")
+        groups.append((g0, g1, a, b, size))
+    with torch.cuda.device(dev):
+        st = _stream(dev)
+        ws = None
+        for g0, g1, a, b, size in groups:
+            if ws is None or ws.numel() != size:           # exactly what the size function said, launch by launch
+                ws = torch.empty(size, dtype=torch.uint8, device=dev)
+                if fill is not None:
+                    ws.fill_(fill)
+            _lib.check(lib.sylber_unit_local_align(_vp(xd), xd.shape[0], _vp(yd), yd.shape[0], W, a.ctypes.data_as(_i32p),
+                                                   b.ctypes.data_as(_i32p), g1 - g0, params[0], params[1], params[2],
+                                                   _vp(scores[at + g0:at + g1]), _vp(spans[at + g0:at + g1]), _vp(ws), st),
+                       "sylber_unit_local_align")
+
+
+def local_align_unit_strings(xs, ys, *, match: int = 2, mismatch: int = 3, gap: int = 4, device="cuda",
+                             pair_chunk: Optional[int] = None, _workspace_fill=None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """what two unit strings have in common: their local alignment (Smith-Waterman), pair by pair -> ``(scores int32 [S], spans
+    int64 [S, 2, 2])`` on the device, ``spans[s] = ((a0, a1), (b0, b1))``: the best-scoring pair of sub-spans is ``xs[s][a0:a1]``
+    and ``ys[s][b0:b1]`` (csrc/unit_repeats.hip, ``sylber_unit_local_align``; contract in include/sylber_hip.h "Unit repeats",
+    restated in tests/unit_repeats_ref.py).  ``xs`` and ``ys`` are what ``align_unit_strings`` takes: equally long sequences of
+    ``[n]`` / ``[n, W]`` integer arrays or tensors (host or device, empty ones allowed), or ``tokenize``'s lists of dicts.
+    ``1 <= W <= 8``, ids in ``0 .. 2**31 - 1``, at most 65 536 units per string; ``1 <= match <= 64``, ``0 <= mismatch <= 64``,
+    ``1 <= gap <= 64``.
+
+    With ``sub(i, j)`` = the columns in which ``x[i]`` and ``y[j]`` differ, all int32::
+
+        s(i, j)  = match * (W - sub(i, j)) - mismatch * sub(i, j)
+        H[i][-1] = H[-1][j] = 0
+        c_diag   = H[i-1][j-1] + s(i, j)     start: start[i-1][j-1] if H[i-1][j-1] > 0, else (i, j)
+        c_up     = H[i-1][j]   - gap * W     start: start[i-1][j]
+        c_left   = H[i][j-1]   - gap * W     start: start[i][j-1]
+        v        = the first largest of (c_diag, c_up, c_left), in that order
+        H[i][j]  = v if v > 0 else 0         start[i][j] = that candidate's start
+
+    The result is the best cell ``(i, j)``: the largest ``H``, then the smallest ``i``, then the smallest ``j``; ``score = H[i][j]``,
+    ``(a0, a1, b0, b1) = (si, i + 1, sj, j + 1)`` with ``(si, sj) = start[i][j]``.  ``x`` is the rows: ties depend on it, so
+    exchanging ``xs`` and ``ys`` may move the spans.  A pair without a positive cell -- an empty string included -- has score 0 and
+    spans -1.  Both spans of a positive score are non-empty.  When ``gap == mismatch + match / 2`` with ``match`` even, as under
+    the defaults, ``score = match * W * ((a1 - a0) + (b1 - b0)) / 2 - (match + mismatch) * cost`` with ``cost`` what
+    ``align_unit_strings`` gives for the two spans: under the defaults ``W * (len_x + len_y) - 5 * cost``.
+
+    Exact (small integers), and nothing depends on ``pair_chunk`` (the pairs per launch; by default as many as keep a launch's
+    workspace below ``search.ALIGN_WORKSPACE_BYTES``; a pair needs at most 1.5 MiB), on which pairs share a call, on their order
+    or on stale workspace contents.  ``ValueError`` before any launch: what ``align_unit_strings`` refuses, and a parameter outside
+    its range.  ``S = 0`` returns empty tensors without a launch.
+
+    Out of scope: more than one repeat per pair (Waterman-Eggert suppression is the known next step), repeats inside one string
+    (cut it), and the same on embeddings."""
+    xp, xl, Wx = _strings(xs, "xs")
+    yp, yl, Wy = _strings(ys, "ys")
+    S = int(xl.size)
+    if S != int(yl.size):
+        raise ValueError("xs and ys must be equally long, got %d and %d strings" % (S, int(yl.size)))
+    if Wx is not None and Wy is not None and Wx != Wy:
+        raise ValueError("xs have W = %d, ys have W = %d" % (Wx, Wy))
+    pair_chunk = _check_pair_chunk(pair_chunk)
+    params = _local_params(match, mismatch, gap)
+    W = Wx or Wy or 1
+    xo, yo = (np.concatenate([[0], np.cumsum(v)]).astype(np.int64) for v in (xl, yl))
+    if xo[-1] >= 2 ** 31 or yo[-1] >= 2 ** 31:
+        raise ValueError("one call takes fewer than 2^31 units on each side")
+    dev = _device(device)
+    scores = torch.empty((S,), dtype=torch.int32, device=dev)
+    spans = torch.empty((S, 4), dtype=torch.int32, device=dev)
+    if S:
+        xd, yd = _flat_strings(xp, W, dev, "xs"), _flat_strings(yp, W, dev, "ys")
+        xw, yw = (np.ascontiguousarray(np.stack([o[:-1], np.diff(o)], 1), np.int32) for o in (xo, yo))
+        _local_launch(_lib.load(), xd, yd, W, xw, yw, params, scores, spans, 0, pair_chunk, _workspace_fill, dev)
+    return scores, spans.to(torch.int64).reshape(S, 2, 2)
