@@ -480,6 +480,44 @@ int sylber_dtw_rerank_occurrences(const float* q_dev, int32_t n_blocks, const fl
                                   const int32_t* seq_offsets_dev, int32_t n_seq, int32_t k, float* cost_dev, int64_t* seq_dev,
                                   int64_t* span_dev, void* workspace_dev, void* stream);
 
+/* Embedding repeats (sylber_amd/search.py: SyllableIndex.search_repeats / find_repeats; csrc/dtw_local.hip; restated in
+ * tests/repeats_ref.py): LOCAL alignment of a probe (m rows, 1 <= m <= 64, prepared exactly as a phrase of sylber_dtw_search) against
+ * every sequence (at most 65 536 rows) -- which part of the probe is said where in the sequence; both ends of both spans are free.
+ * The local cost d[i][j] is sylber_dtw_search's, word for word (s0 = fmaf(-2, q_i . x_j, c_j) from the same contraction with the same
+ * bits, then the L2 / IP forms; a NaN d counts as +inf).  radius > 0 and gap >= 0 are finite fp32.  Everything below is fp32 with one
+ * rounding per operation, exactly as written:
+ *   s  = radius - d[i][j]            (-inf where d = +inf)
+ *   sg = s - gap
+ *   H[i][-1] = H[-1][j] = 0
+ *   c_diag = H[i-1][j-1] + s     start: start[i-1][j-1] if H[i-1][j-1] > 0 else (i, j)
+ *   c_up   = H[i-1][j]   + sg    start: start[i-1][j]
+ *   c_left = H[i][j-1]   + sg    start: start[i][j-1]
+ *   v = the first largest of (c_diag, c_up, c_left) in that order; H[i][j] = v if v > 0 else 0
+ * Every step lands on a cell and earns that cell's s; a non-diagonal step (one syllable said as two, a syllable without a partner)
+ * also pays gap.  gap = 0 is a local DTW with free warping, a large gap is Smith-Waterman without gaps.
+ * Result of (probe, sequence): the best cell -- the largest H, then the smallest i, then the smallest j; score = H[i][j];
+ * (si, sj) = start[i][j]; the probe span is [si, i + 1), the sequence span [sj, j + 1) as row ids.  No positive cell: no result.
+ *   Facts (held in tests/test_repeats_ref.py).  A predecessor with H = 0 is never strictly better through c_up / c_left than c_diag
+ *   (gap >= 0), so start is only ever read from a positive cell, both spans are non-empty and the first cell of a path has s > 0.
+ *   fp32 addition is monotone, so H[i][j] is the maximum over paths of the path's left-to-right fp32 sum: restricting the probe to a
+ *   sub-range of its rows never raises a score, and a path that lies inside the sub-range keeps its bits.
+ * Per probe an admissible result has score >= min_score (finite, > 0), a sequence numbered > after_seq[p] (where given) and, with
+ * both group arrays, a sequence whose group differs from the probe's.  The k best admissible sequences are ordered strictly by
+ * (score descending, sequence ascending); padding is score 0, sequence -1, spans -1.  Nothing depends on the cuts, the packing or
+ * chunking of probes or what the workspace held.
+ * sylber_dtw_local: sylber_dtw_search's arguments with sylber_dtw_plan's packing and cuts; radius, gap, min_score as above;
+ *   after_seq_dev [n_phrases] int32 or null.  score_dev [n_phrases, k] fp32, seq_dev [n_phrases, k] int64, span_dev
+ *   [n_phrases, k, 2, 2] int64: span[p][r][0] = (si, i + 1) positions inside the probe, span[p][r][1] = (sj, j + 1) row ids.
+ *   workspace_dev: sylber_dtw_workspace_bytes(n_blocks, n_phrases, k, cuts) bytes (the lists keep their 16-byte entries:
+ *   (-score, sequence, (sj row, (j - sj) | i << 16 | si << 22))).  Every argument is checked on the host before any device call:
+ *   status 1 with sylber_last_error set. */
+int sylber_dtw_local(const float* q_dev, int32_t n_blocks, const int32_t* row_meta_dev, const int32_t* slot_phrase_dev,
+                     const int32_t* block_rows_dev, int32_t n_phrases, int32_t block_phrases, const float* db_dev, int32_t N, int32_t D,
+                     const float* db_norm_dev, int32_t metric, int32_t k, float radius, float gap, float min_score,
+                     const int32_t* seq_id_dev, const int32_t* cut_rows_dev, int32_t cuts, const int32_t* phrase_group_dev,
+                     const int32_t* seq_group_dev, const int32_t* after_seq_dev, float* score_dev, int64_t* seq_dev, int64_t* span_dev,
+                     void* workspace_dev, void* stream);
+
 /* Unit search (sylber_amd/units.py: UnitIndex.search_phrases / search_occurrences; csrc/unit_search.hip; restated in
  * tests/unit_search_ref.py): where is a phrase of syllable UNIT IDS said, by semi-global edit distance (Sellers' approximate
  * string matching).  The corpus holds tokens only: no embedding is needed.  A unit is a row of W non-negative int32 ids

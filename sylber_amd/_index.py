@@ -179,10 +179,11 @@ def _list_layout(labels: torch.Tensor, nlist: int) -> Tuple[torch.Tensor, torch.
 # What the phrase searches share: SyllableIndex.search_phrases, search_phrases_refined, search_occurrences,
 # search_occurrences_refined and PQSyllableIndex.search_phrases (all five through _scan_phrases below), search_phrases_seeded and the
 # two align_phrases.  An index enters only as (N rows, width dim, device, metric, the rows' groups on the device).
-def _phrase_outputs(P: int, k: int, device):
-    """``(costs fp32 [P, k], seqs int64 [P, k], spans int64 [P, k, 2])`` of a phrase search"""
+def _phrase_outputs(P: int, k: int, device, span=(2,)):
+    """``(costs fp32 [P, k], seqs int64 [P, k], spans int64 [P, k, 2])`` of a phrase search; ``span=(2, 2)``: the two spans of
+    ``search_repeats``"""
     return (torch.empty((P, k), dtype=torch.float32, device=device), torch.empty((P, k), dtype=torch.int64, device=device),
-            torch.empty((P, k, 2), dtype=torch.int64, device=device))
+            torch.empty((P, k) + tuple(span), dtype=torch.int64, device=device))
 
 
 def _group_runs(g: Optional[torch.Tensor], N: int) -> np.ndarray:
@@ -320,7 +321,7 @@ class _PhraseChunk:
 
 
 def _scan_phrases(N: int, dim: int, dev, metric: str, db_groups, default_sequences, stages, phrases, k, refine, storage, lengths, groups,
-                  exclude_same_group, sequences, splits, phrase_chunk, block_phrases, return_candidates, workspace_fill):
+                  exclude_same_group, sequences, splits, phrase_chunk, block_phrases, return_candidates, workspace_fill, local=None):
     """the host loop of every phrase search that scans the corpus: the checks in their order (``k`` / ``refine`` / ``storage``, then
     ``_phrase_args``), the outputs, the return for no phrase, the prepared rows, the sequence tables and, ``phrase_chunk`` phrases
     at a time, the packed blocks with their tables -> ``(costs, seqs, spans)``, and ``cand`` int64, ``coarse`` with
@@ -328,7 +329,9 @@ def _scan_phrases(N: int, dim: int, dev, metric: str, db_groups, default_sequenc
     with ``m = k * refine`` candidates.  ``stages()`` is called once, behind every check and before anything is launched (it may
     still refuse, e.g. values that fp16 cannot hold) -> ``(scan, rerank)``: ``scan(c)`` launches stage 1 of the chunk ``c`` (a
     ``_PhraseChunk``) -- into ``c.costs, c.seqs, c.spans`` when it is the only stage, else into ``c.cand, c.coarse`` -- and
-    ``rerank(c)`` (``None`` with one stage) stage 2, inside the loop."""
+    ``rerank(c)`` (``None`` with one stage) stage 2, inside the loop.  ``local`` (``search_repeats``): ``(radius, gap, min_score)`` as
+    fp32 and ``after`` (int32 ``[P]`` on the host, or ``None``); the spans are then ``[P, k, 2, 2]``, the chunk carries ``c.local``
+    (the three scalars) and ``c.after_d`` (its slice of ``after`` on the device, or ``None``)."""
     two = refine is not None
     k, m = _check_k_refine(k, refine, rerank=True) if two else _check_k_refine(k)
     if two and storage not in STORAGES:
@@ -336,7 +339,9 @@ def _scan_phrases(N: int, dim: int, dev, metric: str, db_groups, default_sequenc
     q, lens, pg, off = _phrase_args(N, dim, dev, default_sequences, phrases, lengths, groups, exclude_same_group, sequences, splits,
                                     phrase_chunk, block_phrases)
     P = int(lens.size)
-    costs, seqs, spans = _phrase_outputs(P, k, dev)
+    if local is not None and local[3] is not None and len(local[3]) != P:
+        raise ValueError("after_seq must have one entry per probe (%d), got %d" % (P, len(local[3])))
+    costs, seqs, spans = _phrase_outputs(P, k, dev, (2,) if local is None else (2, 2))
     cand = torch.empty((P, m), dtype=torch.int32, device=dev) if two else None
     coarse = torch.empty((P, m), dtype=torch.float32, device=dev) if two else None
     if P:
@@ -353,6 +358,8 @@ def _scan_phrases(N: int, dim: int, dev, metric: str, db_groups, default_sequenc
                 c.b = b = _phrase_blocks(lib, dev, qd, lens, p0, p1, off, m, splits, block_phrases, pg)
                 c.meta_d, c.sp_d, c.br_d, c.cut_d, c.pg_d = b.tables()
                 c.costs, c.seqs, c.spans = costs[p0:p1], seqs[p0:p1], spans[p0:p1]
+                if local is not None:
+                    c.local, c.after_d = local[:3], (_on_device(local[3][p0:p1], np.int32, dev) if local[3] is not None else None)
                 if two:
                     c.place_d, c.len_d = _on_device(b.place, np.int32, dev), _on_device(b.ln, np.int32, dev)
                     c.qn = _row_norms(b.qp) if metric == "l2" else None

@@ -149,6 +149,9 @@ EXPORTS = {
                                        c_int32, c_int32, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                        c_void_p, c_void_p]),
     "sylber_dtw_occ_workspace_bytes": (c_int64, [c_int32, c_int32, c_int32]),
+    "sylber_dtw_local": (c_int, [c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_int32, c_int32, c_void_p,
+                                 c_int32, c_int32, c_float, c_float, c_float, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p,
+                                 c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "sylber_dtw_rerank_occurrences": (c_int, [c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_int32, c_void_p,
                                               c_int32, c_void_p, c_int32, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p,
                                               c_void_p]),

@@ -22,6 +22,9 @@ match per sequence (``sylber_dtw_occurrences``, ``sylber_dtw_rerank_occurrences`
 ``SyllableIndex.search_occurrences_seeded`` and ``IVFSyllableIndex.search_occurrences`` do so among the candidate sequences of the vote.
 ``align_phrases`` takes the spans of any of them and returns the warping path of each match: the stored rows every phrase row was
 aligned to (csrc/dtw_align.hip, ``sylber_dtw_align``; tests/align_ref.py).
+``SyllableIndex.search_repeats`` / ``find_repeats`` need no whole-phrase match and no query: the LOCAL alignment of probes -- or of
+windows of the index's own sequences -- against every sequence, in the same epilogue (csrc/dtw_local.hip, ``sylber_dtw_local``;
+tests/repeats_ref.py).
 
 The rules that every index shares -- argument checks, row preparation, result buffers, provenance, the list layout, the arrays of a
 saved file -- are in _index.py, each once; this file and pq.py hold what differs between the indexes.
@@ -40,13 +43,34 @@ from ._index import DEFAULT_PHRASE_CHUNK, MAX_PHRASE_ROWS, MAX_SEEDS, MAX_SEQUEN
 from ._index import (DEFAULT_QUERY_CHUNK, METRICS, _added_rows, _base_arrays, _check_k_refine, _check_nprobe, _check_splits_chunk,
                      _chunked_workspace_bytes, _group_runs, _list_layout, _on_device, _outputs, _pack16, _phrase_args, _phrase_blocks,
                      _phrase_outputs, _PhraseChunk, _prep, _provenance, _query_groups, _result, _row_norms, _rows, _rows_of_width,
-                     _scan_phrases)
+                     _scan_phrases, _sequences)
 from .kmeans import _device, _stream, _vp
 
 RERANK_CHUNK = 32               # DP_CH of csrc/dtw_pair.h: the columns of a sequence that search_phrases_refined re-ranks at a time
 OCC_RERANK_ENTRIES = 1 << 24    # list entries (24 B each with the merge rounds' half) of one sylber_dtw_rerank_occurrences launch
 MAX_WINDOW_ROWS = 65536         # DA_MAX_COLS of csrc/dtw_align.hip: the rows of a window that align_phrases walks (= MAX_SEQUENCE_ROWS)
 ALIGN_WORKSPACE_BYTES = 256 << 20       # the default pair_chunk of align_phrases keeps its workspace below this
+
+
+# ---- repeated phrases: the three fp32 scalars of search_repeats / find_repeats ---------------------------------------------------
+def _local_scalars(radius, gap, min_score) -> Tuple[np.float32, np.float32, np.float32]:
+    """``(radius, gap, min_score)`` as fp32 with the defaults ``gap = 2 radius``, ``min_score = 3 radius``, or ``ValueError``"""
+    def f32(v, what):
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
+            raise ValueError("%s must be a number, got %r" % (what, v))
+        with np.errstate(over="ignore"):
+            return np.float32(v)
+    radius = f32(radius, "radius")
+    if not (np.isfinite(radius) and radius > 0):
+        raise ValueError("radius must be finite and > 0 as float32, got %r" % (radius,))
+    with np.errstate(over="ignore"):
+        gap = np.float32(2) * radius if gap is None else f32(gap, "gap")
+        min_score = np.float32(3) * radius if min_score is None else f32(min_score, "min_score")
+    if not (np.isfinite(gap) and gap >= 0):
+        raise ValueError("gap must be finite and >= 0 as float32, got %r" % (gap,))
+    if not (np.isfinite(min_score) and min_score > 0):
+        raise ValueError("min_score must be finite and > 0 as float32, got %r" % (min_score,))
+    return radius, gap, min_score
 
 
 # ---- warping paths: what the align_phrases of SyllableIndex and of the compressed indexes share -------------------------------
@@ -591,9 +615,156 @@ class SyllableIndex:
 
         return _align_phrases(N, self.dim, self.device, self.metric, phrases, spans, lengths, pair_chunk, run, _tracked_start)
 
+    # ---- repeated phrases ---------------------------------------------------------------------------------------------------------------
+    def search_repeats(self, probes, k: int, radius, *, gap=None, min_score=None, lengths=None, groups=None,
+                       exclude_same_group: bool = False, sequences=None, splits: int = 0, phrase_chunk: int = DEFAULT_PHRASE_CHUNK,
+                       block_phrases: int = 0, _workspace_fill=None, _after_seq=None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """which part of each probe is said anywhere in the index: LOCAL alignment of each probe against every sequence, the k best
+        sequences per probe -> ``(scores fp32 [P, k], seqs int64 [P, k], spans int64 [P, k, 2, 2])`` on the device.
+        ``spans[p, r, 0]`` = (first, one past the last) position inside the probe, ``spans[p, r, 1]`` = (first, one past the last)
+        row id of the index, so ``provenance`` works on it.  ``probes``, ``lengths``, ``groups``, ``sequences`` and the test hooks
+        are ``search_phrases``'s, and so are the limits (``1 <= m <= 64`` rows, sequences of at most 65 536 rows, ``k <= 128``).
+
+        Contract ("Embedding repeats" in include/sylber_hip.h, restated in tests/repeats_ref.py; csrc/dtw_local.hip).  The local
+        cost ``d[i][j]`` is ``search_phrases``'s, word for word.  ``radius > 0`` and ``gap >= 0`` are taken as fp32; everything is
+        fp32 with one rounding per operation, exactly as written::
+
+            s  = radius - d[i][j]            (-inf where d = +inf)
+            sg = s - gap
+            H[i][-1] = H[-1][j] = 0
+            c_diag = H[i-1][j-1] + s     start: start[i-1][j-1] if H[i-1][j-1] > 0 else (i, j)
+            c_up   = H[i-1][j]   + sg    start: start[i-1][j]
+            c_left = H[i][j-1]   + sg    start: start[i][j-1]
+            v = the first largest of (c_diag, c_up, c_left) in that order; H[i][j] = v if v > 0 else 0
+
+        Every step lands on a cell and earns that cell's ``s``: a pair of syllables closer than ``radius`` earns, a farther one
+        costs.  A non-diagonal step (one syllable said as two, a syllable without a partner) also pays ``gap``.  ``gap = 0`` is a
+        local DTW with free warping, a large ``gap`` is Smith-Waterman without gaps.  The result of (probe, sequence) is the best
+        cell -- the largest ``H``, then the smallest ``i``, then the smallest ``j`` -- with ``score = H[i][j]`` and the spans
+        ``[si, i + 1)``, ``[sj, j + 1)`` from ``(si, sj) = start[i][j]``; no positive cell, no result.  Both spans are non-empty.
+
+        Per probe a sequence is admissible with ``score >= min_score`` (and a group other than the probe's under
+        ``exclude_same_group``); the k best are ordered strictly by (score descending, sequence ascending); padding is score 0,
+        sequence -1, spans -1.  Nothing depends on ``splits``, ``phrase_chunk``, ``block_phrases``, stale workspace contents or one
+        ``add`` against many.
+
+        ``radius`` is required: it is in the unit of ``d`` (squared L2 distance, or ``1 - cosine``), and what radius suits real
+        speech has not been measured here -- look at the ``search`` scores of syllables you know to be the same.  ``gap=None``
+        means ``2 * radius``, ``min_score=None`` means ``3 * radius`` (three perfect matches), both exact products in fp32.
+        ``ValueError`` before any launch: whatever ``search_phrases`` refuses, a ``radius`` that is not finite and ``> 0``, a ``gap``
+        that is not finite and ``>= 0``, a ``min_score`` that is not finite and ``> 0`` (all three as fp32)."""
+        local = _local_scalars(radius, gap, min_score)
+        after = None if _after_seq is None else np.ascontiguousarray(_after_seq, np.int32)
+        return self._scan_phrases(lambda: (self._scan_local(), None), probes, k, None, None, lengths, groups, exclude_same_group, sequences,
+                                  splits, phrase_chunk, block_phrases, False, _workspace_fill, local + (after,))
+
+    def find_repeats(self, k: int, radius, *, gap=None, min_score=None, window: int = 64, hop: int = 32, sequences=None,
+                     exclude_same_group: bool = False, splits: int = 0, phrase_chunk: int = DEFAULT_PHRASE_CHUNK,
+                     _workspace_fill=None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """what is said more than once, found without a query and without a codebook: the k best repeats between two sequences of
+        the index -> ``(scores fp32 [k], pairs int64 [k, 2], spans int64 [k, 2, 2])`` on the device, shaped and padded like
+        ``UnitIndex.find_repeats``'s: ``pairs[r] = (s, t)`` with ``s < t``, ``spans[r] = ((a0, a1), (b0, b1))`` ROW IDS (first,
+        one past the last) in sequence ``s`` and in sequence ``t``; shorter lists end in score 0, pairs ``(-1, -1)``, spans -1.
+
+        The probes are windows of the index's own sequences -- the rows as the index holds them, prepared like any probe (under
+        ``"cosine"`` the stored unit rows are normalised once more) -- searched with ``search_repeats`` (same ``radius``, ``gap``,
+        ``min_score``, same contract).  A sequence of ``L`` rows gives one window if ``L <= window``, else
+        ``ceil((L - window) / hop) + 1``; window ``r`` = rows ``min(r * hop, L - window)`` onwards, ``min(window, L)`` of them
+        (``1 <= hop <= window <= 64``).  A window of sequence ``s`` is aligned against the sequences ``t > s`` only (with
+        ``exclude_same_group``: of another group than ``s``'s first row) and asks for its k best (``k <= 128``).  Per pair
+        ``(s, t)`` the best window counts, by score descending and then the smallest window; the k best pairs are ordered by
+        (score descending, ``s``, ``t``).  This is exact: a pair among the k best has fewer than k better sequences in its best
+        window's list, so it is in that list.
+
+        Window theorem (held in tests/test_repeats_ref.py).  If the best local alignment of the WHOLE sequence ``s`` against
+        ``t`` covers at most ``window - hop + 1`` rows of ``s``, some window contains it and ``find_repeats`` returns it bit for
+        bit, score and both spans; otherwise it returns a score that is never larger (fp32 addition is monotone: restricting the
+        probe to a sub-range of its rows never raises a score, and a path inside the sub-range keeps its bits).
+
+        Nothing depends on ``splits``, ``phrase_chunk`` (the windows per launch), stale workspace contents, one ``add`` against
+        many or a ``save`` / ``load`` round trip.  ``ValueError`` before any launch: an empty index, what ``search_repeats``
+        refuses, ``window`` / ``hop`` outside ``1 <= hop <= window <= 64``.  Fewer than two sequences: padding only, no launch.
+
+        Not here: more than one repeat per pair of sequences, repeats inside one sequence (cut it with ``sequences=``), the
+        16-bit / PQ / IVF forms, scores normalised by length."""
+        N, dev = len(self), self.device
+        if N == 0:
+            raise ValueError("the index is empty")
+        k = _check_k_refine(k)[0]
+        local = _local_scalars(radius, gap, min_score)
+        for name, v in (("window", window), ("hop", hop)):
+            if isinstance(v, bool) or int(v) != v:
+                raise ValueError("%s must be an integer, got %r" % (name, v))
+        window, hop = int(window), int(hop)
+        if not 1 <= hop <= window <= MAX_PHRASE_ROWS:
+            raise ValueError("need 1 <= hop <= window <= %d, got hop = %d, window = %d" % (MAX_PHRASE_ROWS, hop, window))
+        if int(splits) < 0 or int(phrase_chunk) < 1:
+            raise ValueError("splits must be >= 0 and phrase_chunk >= 1")
+        off = _sequences(sequences, N, self.sequence_offsets)
+        S = int(off.size - 1)
+        scores = torch.zeros((k,), dtype=torch.float32, device=dev)
+        pairs = torch.full((k, 2), -1, dtype=torch.int64, device=dev)
+        spans = torch.full((k, 2, 2), -1, dtype=torch.int64, device=dev)
+        if S < 2:
+            return scores, pairs, spans
+        # the windows, in (sequence, window) order; the last sequence has no t > s and gives none
+        lens = np.diff(off)[:-1]
+        n_w = np.where(lens <= window, 1, -(-(lens - window) // hop) + 1)
+        ws = np.repeat(np.arange(S - 1, dtype=np.int64), n_w)                      # the sequence of every window
+        r = np.arange(ws.size, dtype=np.int64) - np.repeat(np.cumsum(n_w) - n_w, n_w)
+        wlen = np.minimum(window, lens)[ws]
+        wrow = off[ws] + np.minimum(r * hop, np.maximum(lens[ws] - window, 0))     # the first row of every window
+        grp = self._g.index_select(0, torch.from_numpy(off[:-1]).to(dev)).cpu().numpy()[ws] if exclude_same_group else None
+        found = []
+        step = int(phrase_chunk)
+        for w0 in range(0, ws.size, step):
+            w1 = min(ws.size, w0 + step)
+            wl = wlen[w0:w1]
+            rows = np.repeat(wrow[w0:w1], wl) + np.arange(int(wl.sum())) - np.repeat(np.cumsum(wl) - wl, wl)
+            probes = self._x.index_select(0, torch.from_numpy(rows).to(dev))
+            sc, sq, sp = self.search_repeats(probes, k, local[0], gap=local[1], min_score=local[2], lengths=wl,
+                                             groups=None if grp is None else grp[w0:w1], exclude_same_group=exclude_same_group,
+                                             sequences=off, splits=splits, phrase_chunk=step, _workspace_fill=_workspace_fill,
+                                             _after_seq=ws[w0:w1])
+            hit = (sq >= 0).nonzero()                                              # [n, 2]: (window of the chunk, rank), windows ascending
+            if hit.shape[0] == 0:
+                continue
+            wi, ri = hit[:, 0], hit[:, 1]
+            s_d = torch.from_numpy(ws[w0:w1]).to(dev).index_select(0, wi)
+            sp = sp[wi, ri]
+            sp[:, 0] += torch.from_numpy(wrow[w0:w1]).to(dev).index_select(0, wi)[:, None]
+            found.append((sc[wi, ri], s_d, sq[wi, ri], sp))
+        if not found:
+            return scores, pairs, spans
+        sc, s_d, t_d, sp = (torch.cat(a) for a in zip(*found))
+        # entries are in window order: a stable sort by score, then by pair, leaves each pair's best window (the smallest on ties) first
+        o = torch.sort(sc, descending=True, stable=True).indices
+        o = o.index_select(0, torch.sort((s_d * S + t_d).index_select(0, o), stable=True).indices)
+        key = (s_d * S + t_d).index_select(0, o)
+        first = torch.ones_like(key, dtype=torch.bool)
+        first[1:] = key[1:] != key[:-1]
+        o = o[first]                                                               # one entry per pair, pairs ascending by (s, t)
+        o = o.index_select(0, torch.sort(sc.index_select(0, o), descending=True, stable=True).indices[:k])
+        n = int(o.shape[0])
+        scores[:n], spans[:n] = sc.index_select(0, o), sp.index_select(0, o)
+        pairs[:n, 0], pairs[:n, 1] = s_d.index_select(0, o), t_d.index_select(0, o)
+        return scores, pairs, spans
+
     # ---- the stages that the scanning phrase searches hand to _index.py's _scan_phrases ------------------------------------------------
     def _scan_phrases(self, stages, *args):
         return _scan_phrases(len(self), self.dim, self.device, self.metric, self._g, self.sequence_offsets, stages, *args)
+
+    def _scan_local(self):
+        """the only stage of ``search_repeats``: ``sylber_dtw_local``, whose lists are laid out as ``sylber_dtw_search``'s"""
+        def scan(c):
+            b = c.b
+            ws = c.workspace(c.lib.sylber_dtw_workspace_bytes(b.nb, b.Pc, c.k, b.C))
+            radius, gap, min_score = (float(v) for v in c.local)
+            _lib.check(c.lib.sylber_dtw_local(_vp(b.qp), b.nb, _vp(c.meta_d), _vp(c.sp_d), _vp(c.br_d), b.Pc, b.slots, _vp(self._x), c.N, c.dim,
+                                              _vp(self._c), c.metric, c.k, radius, gap, min_score, _vp(c.seq_id), _vp(c.cut_d), b.C,
+                                              _vp(c.pg_d), _vp(c.seq_grp), _vp(c.after_d), _vp(c.costs), _vp(c.seqs), _vp(c.spans), _vp(ws),
+                                              c.st), "sylber_dtw_local")
+        return scan
 
     def _scan32(self, entry: str):
         """stage 1 on the fp32 rows, the only stage: ``sylber_dtw_search`` or ``sylber_dtw_occurrences``, which take the same arguments"""

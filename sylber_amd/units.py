@@ -382,7 +382,7 @@ class UnitIndex:
         only, without a launch.
 
         Out of scope: repeats inside one sequence (cut the recording with ``sequences=``); more than one repeat per pair of
-        sequences (Waterman-Eggert suppression is the known next step); the same on embeddings (``SyllableIndex``)."""
+        sequences (Waterman-Eggert suppression is the known next step).  ``SyllableIndex.find_repeats`` is the same on embeddings."""
         N, dev, W = len(self), self.device, self.width
         if N == 0:
             raise ValueError("the index is empty")
