@@ -732,6 +732,65 @@ int sylber_dtw_align(const float* q_dev, int32_t n_blocks, const float* q_norm_d
                      int32_t max_rows, int32_t* rows_dev, int32_t* steps_dev, float* cost_dev, int32_t* start_dev, void* workspace_dev,
                      void* stream);
 
+/* Embedding strings (sylber_amd/search.py: align_sequences / SyllableIndex.align_sequences; csrc/dtw_strings.hip; restated in
+ * tests/dtw_strings_ref.py): how two WHOLE embedding sequences line up, row by row -- the global DTW of two recordings, without
+ * the 64-row limit of a phrase, many pairs per call.  What "Unit strings" is to unit ids.  A pair is a sequence x of m rows and a
+ * sequence y of L rows, 0 <= m, L <= 65 536; D is a multiple of 16 and at least 16.
+ *   Local cost.  d[i][j] is sylber_dtw_search's, word for word, with x in the role of the phrase and y in the role of the
+ *   database: dot = the ascending fmaf chain from 0 over D; s = fmaf(-2, dot, c_j); L2: c_j = ||y_j||^2 as sylber_knn_row_norms
+ *   gives it and d = max(0, ||x_i||^2 + s); IP / cosine: both sides made unit rows by sylber_knn_unit_rows, c_j = 0 and
+ *   d = max(0, 1 - (0 - s / 2)); a NaN d counts as +inf.  The kernel contracts on v_mfma_f32_32x32x2_f32 in sylber_dtw_search's
+ *   k-pair order, which produces the bits of that chain.
+ *   Global DTW, all additions in fp32, one per cell:
+ *     A[0][0] = d[0][0]                                     n[0][0] = 1
+ *     A[i][j] = d[i][j] + min(A[i-1][j-1], A[i-1][j], A[i][j-1])      terms outside the matrix are +inf
+ *               the first smallest in that order (diagonal, up, left): the order of every DTW in this library
+ *     n[i][j] = n[the predecessor taken] + 1
+ *   Outputs per pair.  cost = A[m-1][L-1].  steps = n[m-1][L-1], the cells on the path: the divisor of the length-normalised
+ *   distance cost / steps.  With path, rows[i] = (lo, hi) for every row i of x: the run of y positions the path visits in row i,
+ *   0-based INSIDE y's window, hi exclusive, written at x's flat row rows_offset_host[pair] + i.  A monotone path visits one run
+ *   per row; lo[0] = 0, hi[m-1] = L, and lo[i+1] is hi[i] - 1 or hi[i], so the runs ARE the path.
+ *   Padding.  A pair whose cost is not below +inf is padding: cost +inf, steps 0, rows (-1, -1).  An empty side (m = 0 or L = 0)
+ *   is padding too.
+ *   Counts without a path.  A cell carries (A, n), the way "Unit strings" carries (cost, d, sb); the counts-only kernel writes no
+ *   predecessor codes.  With path the walk back over the 2-bit codes counts its own cells and writes them to steps_walk_dev
+ *   where that is not null -- always equal to steps_dev; a check of the codes, not a result.
+ *   Nothing returned depends on what the workspace held, on which pairs share a call or on their order: a pair touches only its
+ *   own slice of the workspace and its own outputs.
+ *   The theorem.  Take a phrase x of at most 64 rows and a window [a, b) of rows.  If sylber_dtw_align's path for that pair
+ *   starts in column a -- it does for every span that a phrase search returned -- then the global alignment of x against rows
+ *   [a, b) has that cost, bit for bit, that steps, and those runs shifted by a.  Why: the window DP has a free start and a forced
+ *   end, and the global DP minimises over a subset of its paths; fp32 + is monotone, so every global cell is at least the
+ *   window cell, and on that path the two are equal; a predecessor that lost in the window DP was strictly larger there and
+ *   still is; on an exact tie the global cell is not smaller, so the first-smallest order names the same winner whenever the
+ *   winner lies on the common path.  Always: the global cost >= sylber_dtw_align's cost on the same window.
+ *   tests/test_dtw_strings_ref.py holds both on random, tied and +inf-holed matrices.
+ * sylber_dtw_strings_align: x_dev [x_rows, D] and y_dev [y_rows, D] fp32 on the device (unit rows under IP); x_norm_dev [x_rows]
+ *   and y_norm_dev [y_rows] fp32: required under L2, may be null under IP; metric as for sylber_knn_search.  x_win_host and
+ *   y_win_host [n_pairs, 2] int32 = (first row, number of rows) of each pair's window into its buffer.  The two buffers may be
+ *   the same buffer, windows may overlap and may repeat.  The host arrays are read before the call returns, everything else is
+ *   enqueued on `stream`.  path: 0 = cost and steps only, 1 = rows_dev [*, 2] int32 too, pair p at rows rows_offset_host[p] .. + m
+ *   (rows_offset_host [n_pairs] int64 and rows_dev are required iff path).  steps_dev [n_pairs] int32, cost_dev [n_pairs] fp32;
+ *   steps_walk_dev [n_pairs] may be null and is written with path only.
+ *   workspace_dev: sylber_dtw_strings_workspace_bytes of the same windows and path, host arithmetic on the lengths (-1 on a bad
+ *   argument), every term rounded up to 256 B:
+ *       64 B per pair of table
+ *     + 16 L per pair with m > 128 and L > 0: two alternating rows of (A, n), 8 B per column, between super-strips of 128 rows
+ *       of x, at most 1 MiB
+ *     + with path, ceil(m / 64) * ceil(L / 128) * 2048 B per pair with m, L > 0: 2 bits per cell, about m L / 4; one lane's 128
+ *       cells of one tile are four 64-bit words.
+ *   A null pointer other than the nullable ones (the norms under IP, steps_walk_dev, and rows_offset_host and rows_dev without
+ *   path), D below 16 or no multiple of 16, an unknown metric, L2 without norms, n_pairs < 1, a window with a negative length or
+ *   of more than 65 536 rows, a window outside its buffer, a negative rows_offset_host and path outside {0, 1} return 1 with
+ *   sylber_last_error before any device call.  The windows are host data, so no stale table can reach the kernel; what it reads
+ *   from the table is what this entry checked and wrote. */
+int64_t sylber_dtw_strings_workspace_bytes(const int32_t* x_win_host, const int32_t* y_win_host, int32_t n_pairs, int32_t path);
+int sylber_dtw_strings_align(const float* x_dev, int32_t x_rows, const float* x_norm_dev, const float* y_dev, int32_t y_rows,
+                             const float* y_norm_dev, int32_t D, int32_t metric, const int32_t* x_win_host, const int32_t* y_win_host,
+                             int32_t n_pairs, int32_t path, const int64_t* rows_offset_host /* [n_pairs], with path: x's flat row in rows_dev */,
+                             int32_t* rows_dev /* [*, 2], with path */, int32_t* steps_dev, float* cost_dev,
+                             int32_t* steps_walk_dev /* nullable */, void* workspace_dev, void* stream);
+
 /* The exact DTW on a coded database (sylber_amd/pq.py: IVFPQSyllableIndex.search_phrases / search_occurrences / align_phrases with
  * rerank=False; restated in tests/ivfpq_phrase_ref.py): sylber_dtw_rerank and sylber_dtw_align with db_dev replaced by
  * product-quantization codes that may lie in another order than the row ids and may be codes of residuals to a list centroid.  No row is materialised: the kernels rebuild

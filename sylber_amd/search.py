@@ -25,6 +25,8 @@ aligned to (csrc/dtw_align.hip, ``sylber_dtw_align``; tests/align_ref.py).
 ``SyllableIndex.search_repeats`` / ``find_repeats`` need no whole-phrase match and no query: the LOCAL alignment of probes -- or of
 windows of the index's own sequences -- against every sequence, in the same epilogue (csrc/dtw_local.hip, ``sylber_dtw_local``;
 tests/repeats_ref.py).
+``align_sequences`` / ``SyllableIndex.align_sequences`` align two WHOLE sequences of any length, the global DTW with its path
+(csrc/dtw_strings.hip, ``sylber_dtw_strings_align``; tests/dtw_strings_ref.py).
 
 The rules that every index shares -- argument checks, row preparation, result buffers, provenance, the list layout, the arrays of a
 saved file -- are in _index.py, each once; this file and pq.py hold what differs between the indexes.
@@ -50,6 +52,7 @@ RERANK_CHUNK = 32               # DP_CH of csrc/dtw_pair.h: the columns of a seq
 OCC_RERANK_ENTRIES = 1 << 24    # list entries (24 B each with the merge rounds' half) of one sylber_dtw_rerank_occurrences launch
 MAX_WINDOW_ROWS = 65536         # DA_MAX_COLS of csrc/dtw_align.hip: the rows of a window that align_phrases walks (= MAX_SEQUENCE_ROWS)
 ALIGN_WORKSPACE_BYTES = 256 << 20       # the default pair_chunk of align_phrases keeps its workspace below this
+SEQUENCE_SUPER_ROWS = 128       # KN_BM of csrc/dtw_strings.hip: the rows of x that align_sequences takes between two carried rows
 
 
 # ---- repeated phrases: the three fp32 scalars of search_repeats / find_repeats ---------------------------------------------------
@@ -192,6 +195,172 @@ def _align_phrases(N: int, dim: int, dev, metric: str, phrases, spans, lengths, 
                     start[r0:r1] if tracked else None, ws, st)
     out = (rows.to(torch.int64).reshape(P, k, Mx, 2), steps.reshape(P, k), costs.reshape(P, k))
     return out + (start.to(torch.int64).reshape(P, k),) if tracked else out
+
+
+# ---- whole sequences: what align_sequences and SyllableIndex.align_sequences share --------------------------------------------------
+_i32p, _i64p = ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int64)
+
+
+def dtw_strings_workspace_bytes(m, L, path: bool) -> np.ndarray:
+    """int64: the bytes of workspace that each pair (``m`` rows of x, ``L`` rows of y; arrays) adds to a launch of
+    ``sylber_dtw_strings_align`` beyond its 64 B of table: two rows of (A, n), 8 B per column, between super-strips of 128 rows where
+    ``m > 128``, and with ``path`` 2 bits per cell of ``ceil(m / 64)`` strips of ``ceil(L / 128)`` tiles, 2048 B each"""
+    m, L = np.asarray(m, np.int64), np.asarray(L, np.int64)
+    rows = np.where((m > SEQUENCE_SUPER_ROWS) & (L > 0), (16 * L + 255) // 256 * 256, 0)
+    if not path:
+        return rows
+    return rows + np.where((m > 0) & (L > 0), ((m + 63) // 64) * ((L + 127) // 128) * 2048, 0)
+
+
+def _check_sequence_pairs(ml: np.ndarray, Ll: np.ndarray, path: bool, pair_chunk) -> np.ndarray:
+    """the checks of ``align_sequences`` on the lengths of its pairs -> the workspace bytes of each pair, or ``ValueError``"""
+    if pair_chunk is not None and (isinstance(pair_chunk, bool) or int(pair_chunk) != pair_chunk or int(pair_chunk) < 1):
+        raise ValueError("pair_chunk must be an integer >= 1, got %r" % (pair_chunk,))
+    for what, ln in (("xs", ml), ("ys", Ll)):
+        if ln.size and int(ln.max()) > MAX_SEQUENCE_ROWS:
+            raise ValueError("%s[%d] has %d rows, more than %d" % (what, int(ln.argmax()), int(ln.max()), MAX_SEQUENCE_ROWS))
+        if int(ln.sum()) >= 2 ** 31:
+            raise ValueError("one call takes fewer than 2^31 rows on each side")
+    need = dtw_strings_workspace_bytes(ml, Ll, path) + 64
+    if need.size and int(need.max()) + 256 > ALIGN_WORKSPACE_BYTES:
+        s = int(need.argmax())
+        raise ValueError("pair %d (%d x %d rows) needs %d bytes of predecessor codes for its path, more than %d; path=False never "
+                         "needs more than 1 MiB per pair" % (s, ml[s], Ll[s], need[s], ALIGN_WORKSPACE_BYTES))
+    return need
+
+
+def _align_windows(xd, xn, yd, yn, D: int, metric: str, xw: np.ndarray, yw: np.ndarray, need: np.ndarray, path: bool, pair_chunk, fill,
+                   dev, _steps_walk: bool = False):
+    """``sylber_dtw_strings_align`` on the pairs of windows ``xw, yw`` int32 ``[S, 2]`` = (first row, rows) into the prepared rows
+    ``xd, yd`` with norms ``xn, yn`` (``None`` under cosine), behind every check -> ``(rows int32 [sum m, 2] or None, costs, steps,
+    x offsets int64 on the host)``; the launches are grouped as ``_align_strings`` groups them"""
+    S = int(xw.shape[0])
+    xo = np.concatenate([[0], np.cumsum(xw[:, 1], dtype=np.int64)]).astype(np.int64)
+    costs = torch.empty((S,), dtype=torch.float32, device=dev)
+    steps = torch.empty((S,), dtype=torch.int32, device=dev)
+    walk = torch.empty((S,), dtype=torch.int32, device=dev) if _steps_walk and path else None
+    rows = torch.empty((max(int(xo[-1]), 1), 2), dtype=torch.int32, device=dev) if path else None
+    if S:
+        # the launches: pair_chunk pairs each, or as many as keep the workspace below ALIGN_WORKSPACE_BYTES
+        if pair_chunk is not None:
+            cuts = list(range(0, S, int(pair_chunk))) + [S]
+        else:
+            cuts, acc = [0], np.concatenate([[0], np.cumsum(need)])
+            while cuts[-1] < S:
+                cuts.append(max(cuts[-1] + 1, int(np.searchsorted(acc, acc[cuts[-1]] + ALIGN_WORKSPACE_BYTES - 256, side="right")) - 1))
+        lib = _lib.load()
+        groups = []
+        for g0, g1 in zip(cuts[:-1], cuts[1:]):
+            x32, y32 = np.ascontiguousarray(xw[g0:g1], np.int32), np.ascontiguousarray(yw[g0:g1], np.int32)
+            size = int(lib.sylber_dtw_strings_workspace_bytes(x32.ctypes.data_as(_i32p), y32.ctypes.data_as(_i32p), g1 - g0, int(path)))
+            if size < 0:
+                raise _lib.SylberHipError("sylber_dtw_strings_workspace_bytes refused the call")
+            groups.append((g0, g1, x32, y32, np.ascontiguousarray(xo[g0:g1], np.int64), size))
+
+        def at(t, row):                                    # the address of element `row` of a non-empty 4-byte tensor
+            return ctypes.c_void_p(t.data_ptr() + int(row) * 4)
+
+        with torch.cuda.device(dev):
+            st = _stream(dev)
+            ws = None
+            for g0, g1, x32, y32, ro, size in groups:
+                if ws is None or ws.numel() != size:       # every launch gets exactly what its size function asked for
+                    ws = torch.empty(size, dtype=torch.uint8, device=dev)
+                    if fill is not None:
+                        ws.fill_(fill)
+                _lib.check(lib.sylber_dtw_strings_align(_vp(xd), int(xd.shape[0]), _vp(xn), _vp(yd), int(yd.shape[0]), _vp(yn), D, METRICS[metric],
+                                                        x32.ctypes.data_as(_i32p), y32.ctypes.data_as(_i32p), g1 - g0, int(path),
+                                                        ro.ctypes.data_as(_i64p) if path else None, _vp(rows), at(steps, g0), at(costs, g0),
+                                                        at(walk, g0) if walk is not None else None, _vp(ws), st), "sylber_dtw_strings_align")
+    if path:
+        rows = rows[:int(xo[-1])]
+    return (rows, costs, steps, xo) + ((walk,) if _steps_walk else ())
+
+
+def _sequence_rows(seqs, what: str):
+    """a list of ``[m, D]`` float arrays / tensors -> ``(the parts as tensors, their lengths int64, D or None)``, or ``ValueError``"""
+    if torch.is_tensor(seqs) or isinstance(seqs, np.ndarray):
+        raise ValueError("%s must be a list of [m, D] arrays, got one array" % what)
+    parts = [_rows(p, "%s[%d]" % (what, i)) for i, p in enumerate(seqs)]
+    D = None
+    for i, p in enumerate(parts):
+        if not p.dtype.is_floating_point:
+            raise ValueError("%s[%d]: embeddings are floating point, got %s" % (what, i, p.dtype))
+        if D is not None and p.shape[1] != D:
+            raise ValueError("%s[%d]: expected D = %d, got %d" % (what, i, D, p.shape[1]))
+        D = int(p.shape[1])
+    return parts, np.array([p.shape[0] for p in parts], np.int64), D
+
+
+def _flat_rows(parts, D: int, metric: str, dev):
+    """the parts as one prepared ``[max(sum m, 1), D]`` buffer on the device with its norms (``None`` under cosine): a buffer without
+    a row gets one zero row, which no window reaches"""
+    if sum(int(p.shape[0]) for p in parts) == 0:
+        flat = torch.zeros((1, D), dtype=torch.float32, device=dev)
+    else:
+        flat = _prep(torch.cat([p.to(dev, torch.float32) for p in parts]), metric, dev)
+    return flat, (_row_norms(flat) if metric == "l2" else None)
+
+
+def align_sequences(xs, ys, *, metric: str = "l2", path: bool = False, device="cuda", pair_chunk: Optional[int] = None,
+                    _workspace_fill=None, _steps_walk: bool = False):
+    """how two whole recordings line up, syllable by syllable or frame by frame: the global DTW of whole embedding sequences of any
+    length up to 65 536 rows, pair by pair (csrc/dtw_strings.hip, ``sylber_dtw_strings_align``; contract in include/sylber_hip.h
+    "Embedding strings", restated in tests/dtw_strings_ref.py).  ``xs`` and ``ys``: equally long lists of ``[m, D]`` float arrays or
+    tensors (host or device, empty ones allowed) -- the ``segment_features`` or ``hidden_states`` of two ``Segmenter`` calls;
+    ``D`` a multiple of 16.
+
+    Without ``path``: ``(costs fp32 [S], steps int32 [S])`` on the device.  With it: ``(rows int64 [sum m, 2], costs, steps,
+    x_offsets int64 [S + 1])``, sequence ``xs[s]`` in rows ``x_offsets[s] : x_offsets[s + 1]``.
+
+    The local cost ``d[i][j]`` of row i of x against row j of y is ``search_phrases``'s, word for word, with x in the role of the
+    phrase (``"cosine"``: both sides made unit rows).  Global DTW, all additions in fp32, one per cell::
+
+        A[0][0] = d[0][0]                                     n[0][0] = 1
+        A[i][j] = d[i][j] + min(A[i-1][j-1], A[i-1][j], A[i][j-1])      (terms outside the matrix are +inf)
+                  the first smallest in that order: diagonal, then (i-1, j), then (i, j-1)
+        n[i][j] = n[the predecessor taken] + 1
+
+    ``costs = A[m-1][L-1]``; ``steps = n[m-1][L-1]``, the cells on the path, so ``costs / steps`` is the length-normalised DTW
+    distance; ``rows[i] = (lo, hi)``: the run of positions inside y (0-based, ``hi`` exclusive) that the path visits in row i of x:
+    ``lo[0] = 0``, ``hi[m-1] = L`` and ``lo[i+1]`` is ``hi[i] - 1`` or ``hi[i]``, so the runs are the path.  A pair whose cost is
+    not below ``+inf`` (a NaN row on either side) and a pair with an empty side are padding: cost ``+inf``, steps 0, rows
+    ``(-1, -1)``.  (Under ``"cosine"`` the rows are made unit rows first, exactly as the index makes them: that keeps a row with a
+    NaN in it as the zero row, as it keeps a zero row, and turns a row of ``inf`` into a NaN row.)  For a phrase of at most 64 rows and a span ``[a, b)`` that a phrase search returned,
+    ``align_sequences([phrase], [rows[a:b]], path=True)`` is ``align_phrases`` on that span: costs bit for bit, the same steps, the
+    runs shifted by ``a``; for any other window the global cost is at least ``align_phrases``'s.
+
+    Nothing depends on ``pair_chunk`` (the pairs per launch; by default as many as keep a launch's workspace below
+    ``ALIGN_WORKSPACE_BYTES``), on which pairs share a call, on their order or on stale workspace contents.  It costs ``m L D``
+    multiply-adds per pair, on the fp32 MFMA; without ``path`` a pair needs at most 1 MiB of workspace, the path keeps 2 bits per
+    cell, about ``m L / 4`` bytes.  ``ValueError`` before any allocation or launch: lists of different length, differing widths or
+    a width that is no multiple of 16, a non-float input, a side of more than 65 536 rows, 2^31 or more rows in total on a side,
+    ``pair_chunk < 1``, and with ``path`` a single pair whose codes exceed ``ALIGN_WORKSPACE_BYTES``.  ``S = 0`` returns empty
+    tensors without a launch."""
+    if metric not in METRICS:
+        raise ValueError("metric must be 'l2' or 'cosine', got %r" % (metric,))
+    xp, ml, Dx = _sequence_rows(xs, "xs")
+    yp, Ll, Dy = _sequence_rows(ys, "ys")
+    S, path = int(ml.size), bool(path)
+    if S != int(Ll.size):
+        raise ValueError("xs and ys must be equally long, got %d and %d sequences" % (S, int(Ll.size)))
+    if Dx is not None and Dy is not None and Dx != Dy:
+        raise ValueError("xs have D = %d, ys have D = %d" % (Dx, Dy))
+    D = Dx or Dy
+    if D is not None and (D < 16 or D % 16):
+        raise ValueError("the feature width D must be a multiple of 16, got %d" % D)
+    need = _check_sequence_pairs(ml, Ll, path, pair_chunk)
+    dev = _device(device)
+    xw = np.stack([np.cumsum(ml) - ml, ml], 1).astype(np.int32).reshape(S, 2)
+    yw = np.stack([np.cumsum(Ll) - Ll, Ll], 1).astype(np.int32).reshape(S, 2)
+    if S == 0:
+        xd = xn = yd = yn = None
+    else:
+        (xd, xn), (yd, yn) = _flat_rows(xp, D, metric, dev), _flat_rows(yp, D, metric, dev)
+    out = _align_windows(xd, xn, yd, yn, D or 16, metric, xw, yw, need, path, pair_chunk, _workspace_fill, dev, _steps_walk)
+    rows, costs, steps, xo = out[:4]
+    res = (rows.to(torch.int64), costs, steps, torch.from_numpy(xo).to(dev)) if path else (costs, steps)
+    return res + tuple(out[4:])
 
 
 class SyllableIndex:
@@ -614,6 +783,42 @@ class SyllableIndex:
                                             int(rows.shape[1]), _vp(rows), _vp(steps), _vp(costs), _vp(start), _vp(ws), st), "sylber_dtw_align")
 
         return _align_phrases(N, self.dim, self.device, self.metric, phrases, spans, lengths, pair_chunk, run, _tracked_start)
+
+    def align_sequences(self, pairs, *, path: bool = False, pair_chunk: Optional[int] = None, sequences=None, _workspace_fill=None):
+        """``align_sequences`` between stored sequences, with no copy: ``pairs`` int ``[S, 2]`` (host or device) are sequence numbers
+        of the index, x then y -- by default of ``sequence_offsets()``, or of ``sequences=`` as ``search_phrases`` takes them.  The
+        windows go into the index's own rows with its stored norms (unit rows under ``"cosine"``), so the result is the free
+        function's on those rows under the index's metric, bit for bit.  Without ``path``: ``(costs fp32 [S], steps int32 [S])``.
+        With it: ``(rows int64 [sum m, 2], costs, steps, x_offsets int64 [S + 1])`` where ``rows`` are row ids of the index (``lo``
+        and ``hi`` shifted by y's first row, padding stays ``(-1, -1)``): ``align_phrases`` and ``provenance`` take them.
+        ``ValueError`` before any launch: an empty index, ``pairs`` of another shape or dtype, a sequence number outside
+        ``[0, number of sequences)``, and what ``align_sequences`` refuses of ``pair_chunk`` and of a pair's codes."""
+        N = len(self)
+        if N == 0:
+            raise ValueError("the index is empty")
+        pr = np.asarray(pairs.detach().cpu().numpy() if torch.is_tensor(pairs) else pairs)
+        if pr.size == 0:
+            pr = pr.reshape(0, 2).astype(np.int64)
+        if pr.ndim != 2 or pr.shape[1] != 2 or pr.dtype.kind not in "iu":
+            raise ValueError("pairs must be integer [S, 2] sequence numbers, got %s %s" % (pr.dtype, pr.shape))
+        off = _sequences(sequences, N, self.sequence_offsets)
+        nseq = off.size - 1
+        pr = pr.astype(np.int64)
+        if pr.size and (pr.min() < 0 or pr.max() >= nseq):
+            raise ValueError("pairs must name sequences in [0, %d)" % nseq)
+        path = bool(path)
+        first, length = off[:-1][pr], np.diff(off)[pr]      # [S, 2] each
+        need = _check_sequence_pairs(length[:, 0], length[:, 1], path, pair_chunk)
+        xw = np.stack([first[:, 0], length[:, 0]], 1).astype(np.int32)
+        yw = np.stack([first[:, 1], length[:, 1]], 1).astype(np.int32)
+        rows, costs, steps, xo = _align_windows(self._x, self._c, self._x, self._c, self.dim, self.metric, xw, yw, need, path, pair_chunk,
+                                                _workspace_fill, self.device)
+        if not path:
+            return costs, steps
+        rows = rows.to(torch.int64)
+        shift = torch.from_numpy(np.repeat(first[:, 1], length[:, 0])).to(self.device)
+        rows = torch.where(rows >= 0, rows + shift[:, None], rows)
+        return rows, costs, steps, torch.from_numpy(xo).to(self.device)
 
     # ---- repeated phrases ---------------------------------------------------------------------------------------------------------------
     def search_repeats(self, probes, k: int, radius, *, gap=None, min_score=None, lengths=None, groups=None,
@@ -1085,6 +1290,10 @@ class IVFSyllableIndex:
         """the warping paths behind the spans of ``search_phrases`` or ``search_occurrences``: ``ivf.index.align_phrases``, whose rows
         (in id order) are the ones the exact re-rank ran on -> ``(rows, steps, costs)`` as there"""
         return self.index.align_phrases(phrases, spans, lengths=lengths, pair_chunk=pair_chunk)
+
+    def align_sequences(self, pairs, *, path: bool = False, pair_chunk: Optional[int] = None, sequences=None):
+        """the global DTW of whole stored sequences: ``ivf.index.align_sequences`` on the rows in id order"""
+        return self.index.align_sequences(pairs, path=path, pair_chunk=pair_chunk, sequences=sequences)
 
     # ---- persistence ----------------------------------------------------------------------------------------------------------------
     def save(self, path: str) -> None:
