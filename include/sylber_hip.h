@@ -696,7 +696,50 @@ int sylber_unit_local_align(const int32_t* x_units_dev, int32_t x_rows, const in
                             int32_t gap, int32_t* score_dev /* [n_pairs] */, int32_t* span_dev /* [n_pairs, 4] */,
                             void* workspace_dev, void* stream);
 
-/* Warping paths (sylber_amd/search.py: SyllableIndex.align_phrases; restated in tests/align_ref.py): HOW a phrase matches a
+/* Unit repeats, every one (sylber_amd/units.py: local_align_unit_strings_all / UnitIndex.find_repeats with per_pair or within;
+ * csrc/unit_repeats_all.hip; restated in tests/unit_repeats_all_ref.py): EVERY phrase two unit strings share, and the phrases one
+ * string says more than once -- up to n_best repeats per pair, found round by round without a traceback.  A pair is x (m units)
+ * and y (L units); widths, the id range, match / mismatch / gap and the limit of 65 536 units are those of "Unit repeats".  Three
+ * more parameters: n_best = R, 1 <= R <= 32; min_score >= 1; per pair sep >= 0.
+ *   The rounds r = 0 .. R - 1 run in order.  Round r computes the recurrence of "Unit repeats" word for word with one change: a
+ *   BLOCKED cell has H = 0, carries no start and is never the best cell.  Cell (i, j) is blocked in round r when
+ *     * sep > 0 and j - i < sep: the band on and below the diagonal, for x and y the same string (sep = 1 leaves only j > i, so
+ *       every repeat is found once and no unit is matched with itself), or
+ *     * a0 <= i < a1 and b0 <= j < b1 for the span (a0, a1, b0, b1) that an earlier round of this pair returned: the rectangle
+ *       of an earlier repeat.
+ *   The result of round r is the best unblocked cell in the order of "Unit repeats": the largest H, then the smallest i, then the
+ *   smallest j; score = H[i][j], span = (si, i + 1, sj, j + 1).  If a round's score is below min_score, that round and every
+ *   later one return score 0 and span (-1, -1, -1, -1), and the pair does no further DP work; so does every round of a pair with
+ *   an empty side.
+ *   Why rectangles.  The kernel keeps no traceback and a rectangle needs none: every cell of a round's path lies inside the
+ *   round's rectangle, and a path never contains a blocked cell -- a diagonal step out of H = 0 starts anew and an up or left
+ *   step out of it is negative.  The rectangle also removes the shadow alignments that hug a found path.
+ *   Consequences (tests/test_unit_repeats_all_ref.py).  Round 0 with sep = 0 and min_score = 1 is "Unit repeats" bit for bit.
+ *   Blocking only lowers H, so scores never increase from round to round.  A phrase said once in x and twice in y comes back as
+ *   two rounds with the same x span; three occurrences p1 < p2 < p3 inside one string with sep = 1 come back as the three repeats
+ *   (p1, p2), (p1, p3), (p2, p3).  Rectangles of different rounds may intersect as rectangles; no cell of a round's path lies in
+ *   an earlier rectangle.  With sep > 0 the two spans of a repeat may overlap, as in tandem repetition: [1, 2, 3] * 10 against
+ *   itself with sep = 1 gives one repeat, x[0:27] against y[3:30].  a1 <= b0 is the caller's filter; the DP does not enforce it.
+ *   Nothing returned depends on what the workspace held, on which pairs share a call or on their order.
+ * sylber_unit_local_align_all: buffers and windows as for sylber_unit_local_align.  sep_host [n_pairs] int32 may be null: all 0.
+ *   The windows and sep_host are read before the call returns, everything else is enqueued on `stream`: ONE launch runs all the
+ *   rounds of every pair, one 64-thread workgroup per pair, the pair's rectangles in LDS.  score_dev [n_pairs, n_best],
+ *   span_dev [n_pairs, n_best, 4] int32.
+ *   workspace_dev: sylber_unit_local_all_workspace_bytes of the same windows, host arithmetic on the lengths (-1 on a bad
+ *   argument), every term rounded up to 256 B:
+ *       48 B per pair of table
+ *     + 24 L per pair with m > 64 and L > 0: the two rows between strips, as for sylber_unit_local_align; every round uses them
+ *       again.
+ *   What sylber_unit_local_align refuses, n_best outside 1..32, min_score < 1 and a negative sep return 1 with sylber_last_error
+ *   before any device call. */
+int64_t sylber_unit_local_all_workspace_bytes(const int32_t* x_win_host, const int32_t* y_win_host, int32_t n_pairs);
+int sylber_unit_local_align_all(const int32_t* x_units_dev, int32_t x_rows, const int32_t* y_units_dev, int32_t y_rows, int32_t W,
+                                const int32_t* x_win_host, const int32_t* y_win_host, const int32_t* sep_host /* nullable: all 0 */,
+                                int32_t n_pairs, int32_t match, int32_t mismatch, int32_t gap, int32_t n_best, int32_t min_score,
+                                int32_t* score_dev /* [n_pairs, n_best] */, int32_t* span_dev /* [n_pairs, n_best, 4] */,
+                                void* workspace_dev, void* stream);
+
+/* Warping paths(sylber_amd/search.py: SyllableIndex.align_phrases; restated in tests/align_ref.py): HOW a phrase matches a
  * window of rows -- which stored rows each phrase row is warped onto -- where the searches above report only where.  For one pair
  * (phrase of m rows, window [a, b) of row ids, W = b - a):
  *   Window DP.  The local costs d[i][j] are sylber_dtw_search's, bit for bit (the ascending fmaf chain from 0 over D of

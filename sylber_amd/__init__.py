@@ -8,10 +8,10 @@ from .quantizer import Quantizer, load_quantizer  # noqa: F401
 from .kmeans import KMeansFit, fit_kmeans, fit_km_quantizer, fit_residual_km_quantizer  # noqa: F401
 from .search import IVFSyllableIndex, SyllableIndex, align_sequences  # noqa: F401
 from .pq import IVFPQSyllableIndex, PQSyllableIndex  # noqa: F401
-from .units import UnitErrorRate, UnitIndex, align_unit_strings, local_align_unit_strings, unit_error_rate  # noqa: F401
+from .units import UnitErrorRate, UnitIndex, align_unit_strings, local_align_unit_strings, local_align_unit_strings_all, unit_error_rate  # noqa: F401
 
 __all__ = ["Segmenter", "HubertEncoderHIP", "SegmentSynthesis", "KMQuantizer", "ResidualKMQuantizer", "expand_feature",
            "load_km_quantizer", "load_residualkm_quantizer", "Quantizer", "load_quantizer",
            "KMeansFit", "fit_kmeans", "fit_km_quantizer", "fit_residual_km_quantizer", "SyllableIndex", "IVFSyllableIndex",
            "PQSyllableIndex", "IVFPQSyllableIndex", "UnitIndex", "UnitErrorRate", "align_unit_strings", "unit_error_rate",
-           "local_align_unit_strings", "align_sequences"]
+           "local_align_unit_strings", "local_align_unit_strings_all", "align_sequences"]

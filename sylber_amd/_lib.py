@@ -193,6 +193,9 @@ EXPORTS = {
     "sylber_unit_local_workspace_bytes": (c_int64, [POINTER(c_int32), POINTER(c_int32), c_int32]),
     "sylber_unit_local_align": (c_int, [c_void_p, c_int32, c_void_p, c_int32, c_int32, POINTER(c_int32), POINTER(c_int32), c_int32, c_int32,
                                         c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "sylber_unit_local_all_workspace_bytes": (c_int64, [POINTER(c_int32), POINTER(c_int32), c_int32]),
+    "sylber_unit_local_align_all": (c_int, [c_void_p, c_int32, c_void_p, c_int32, c_int32, POINTER(c_int32), POINTER(c_int32), POINTER(c_int32),
+                                            c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
     "sylber_lq_norm": (c_int, [c_void_p, c_int64, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int64, c_int32, c_void_p, c_int64,
                                c_int32, c_void_p]),
     "sylber_ffenc_workspace_floats": (c_int64, [c_int32, c_int32, POINTER(c_int32)]),

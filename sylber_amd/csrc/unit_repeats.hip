@@ -25,21 +25,10 @@
 // LDS: 4 KiB of ring at WP = 8, 64 threads: wave slots bound the occupancy.
 #include "kernels.h"
 #include "../../include/sylber_hip.h"
+#include "unit_local.h"                                   // the strip's shape, the limits, the DPP exchange, the host's length checks
 #include <vector>
 
-constexpr int UL_CH = 32;                                 // steps of a chunk: lanes 0 .. 31 stage its columns
-constexpr int UL_RING = 128;                              // columns of the ring: a step reads back 63 columns, a chunk is staged 32 ahead
-constexpr int UL_ROWS = 64;                               // rows of x in a strip: one per lane
-constexpr int UL_MAX_LEN = 65536, UL_MAX_W = 8, UL_MAX_PARAM = 64;
 constexpr int UL_TAB = 5;                                 // int64 per pair: x row, m, y row, L, byte offset of the two rows
-
-static_assert(UL_RING >= UL_ROWS - 1 + 2 * UL_CH && (UL_RING & (UL_RING - 1)) == 0, "the ring holds a chunk's columns, the 63 behind them and the next chunk");
-
-// lane l: v of lane l - 1 (lane 0: its own), DPP wave_shr:1
-__device__ __forceinline__ int ul_lane_above(int v) { return __builtin_amdgcn_update_dpp(v, v, 0x138, 0xf, 0xf, false); }
-static inline int64_t ul_al(int64_t bytes) { return (bytes + 255) & ~(int64_t)255; }
-// the two rows between strips: (H, si, sj) per column, only where there is a second strip
-static inline int64_t ul_rows_bytes(int64_t m, int64_t L) { return m > UL_ROWS && L > 0 ? ul_al(2 * 12 * L) : 0; }
 
 // Workgroup (one wave) `pair`: rows tab[0] .. + tab[1] of x [*, W] against rows tab[2] .. + tab[3] of y [*, W]; tab[4]: where in ws
 // its two rows lie.  sw = match * W, pen = match + mismatch, gw = gap * W: s(i, j) = sw - pen * sub(i, j).  Writes score [pairs] and
@@ -157,18 +146,6 @@ __global__ __launch_bounds__(64) void unit_local_kernel(const int32_t* __restric
         if (bh > 0) { sp[0] = bsi; sp[1] = bi + 1; sp[2] = bsj; sp[3] = bj + 1; }
         else { sp[0] = -1; sp[1] = -1; sp[2] = -1; sp[3] = -1; }
     }
-}
-
-// the host's checks of the windows' lengths -> nullptr or what is wrong
-static const char* ul_check(const int32_t* x_win, const int32_t* y_win, int32_t n_pairs) {
-    if (!x_win || !y_win) return "null argument";
-    if (n_pairs < 1) return "need n_pairs >= 1";
-    for (int32_t p = 0; p < n_pairs; ++p) {
-        const int64_t m = x_win[2 * (size_t)p + 1], L = y_win[2 * (size_t)p + 1];
-        if (m < 0 || L < 0) return "a window has a negative number of rows";
-        if (m > UL_MAX_LEN || L > UL_MAX_LEN) return "a string has at most 65536 units";
-    }
-    return nullptr;
 }
 
 static inline int64_t ul_table_bytes(int32_t n_pairs) { return ul_al((int64_t)n_pairs * UL_TAB * 8); }

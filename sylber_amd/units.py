@@ -9,7 +9,9 @@ distance of two unit strings, for a phrase of at most 64 units.  ``align_unit_st
 strings of any length up to 65 536 units, pair by pair, without an index (csrc/unit_strings.hip, "Unit strings",
 tests/unit_strings_ref.py): how far two tokenisations of the same audio are from each other.  ``local_align_unit_strings`` and
 ``UnitIndex.find_repeats`` need no query: the local alignment of two unit strings, i.e. the phrase that both recordings hold, pair
-by pair or over every pair of sequences of an index (csrc/unit_repeats.hip, "Unit repeats", tests/unit_repeats_ref.py).  The argument rules ``UnitIndex``
+by pair or over every pair of sequences of an index (csrc/unit_repeats.hip, "Unit repeats", tests/unit_repeats_ref.py);
+``local_align_unit_strings_all`` and ``find_repeats(per_pair=, within=)`` return every repeat of a pair and the repeats inside one
+string (csrc/unit_repeats_all.hip, "Unit repeats, every one", tests/unit_repeats_all_ref.py).  The argument rules ``UnitIndex``
 shares with the syllable indexes are ``_index.py``'s, the span checks of ``align_phrases`` are search.py's."""
 from __future__ import annotations
 
@@ -30,7 +32,8 @@ ALIGN_CHUNK_COLS = 32           # UA_CH of csrc/unit_align.hip: the anti-diagona
 MAX_WIDTH = 8                   # US_MAX_W: ids per unit
 STRING_ROWS = 64                # UT_ROWS of csrc/unit_strings.hip: the reference rows of a strip
 MAX_STRING_UNITS = 65536        # UT_MAX_LEN: the units of one string of align_unit_strings
-MAX_LOCAL_PARAM = 64            # UL_MAX_PARAM of csrc/unit_repeats.hip: match, mismatch and gap of a local alignment
+MAX_LOCAL_PARAM = 64            # UL_MAX_PARAM of csrc/unit_local.h: match, mismatch and gap of a local alignment
+MAX_BEST = 32                   # ULA_MAX_BEST of csrc/unit_repeats_all.hip: the repeats of one pair
 REPEAT_PAIRS = 1 << 16          # the pairs of sequences that find_repeats enumerates on the host at a time
 FORMAT = "sylber_amd.UnitIndex/1"
 _i32p = ctypes.POINTER(ctypes.c_int32)
@@ -360,8 +363,8 @@ class UnitIndex:
 
     # ---- repeats --------------------------------------------------------------------------------------------------------------------
     def find_repeats(self, k: int, *, min_score=None, match: int = 2, mismatch: int = 3, gap: int = 4, sequences=None,
-                     exclude_same_group: bool = False, pair_chunk: Optional[int] = None,
-                     _workspace_fill=None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+                     exclude_same_group: bool = False, pair_chunk: Optional[int] = None, per_pair: int = 1, within: bool = False,
+                     min_sep: int = 1, _workspace_fill=None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
         """what is said more than once, found without a query: the k best repeats between two sequences of the index ->
         ``(scores int32 [k], pairs int64 [k, 2], spans int64 [k, 2, 2])`` on the device.  Every pair of sequences ``(s, t)`` with
         ``s < t`` is aligned locally (``local_align_unit_strings``: Smith-Waterman with ``match``, ``mismatch``, ``gap``; contract
@@ -378,11 +381,19 @@ class UnitIndex:
         Exact (small integers): nothing returned depends on ``pair_chunk`` (the pairs per launch; by default as many as keep a
         launch's workspace below ``search.ALIGN_WORKSPACE_BYTES``), on stale workspace contents, on one ``add`` against many or on
         a ``save`` / ``load`` round trip.  ``ValueError`` before any launch: an empty index, ``k < 1``, ``min_score < 1``, a
-        parameter outside its range, ``pair_chunk < 1``, a sequence of more than 65 536 rows.  Fewer than two sequences: padding
-        only, without a launch.
+        parameter outside its range, ``pair_chunk < 1``, a sequence of more than 65 536 rows, ``per_pair`` outside 1 .. 32,
+        ``min_sep < 1``.  Fewer than two sequences (one with ``within``): padding only, without a launch.
 
-        Out of scope: repeats inside one sequence (cut the recording with ``sequences=``); more than one repeat per pair of
-        sequences (Waterman-Eggert suppression is the known next step).  ``SyllableIndex.find_repeats`` is the same on embeddings."""
+        Every repeat.  ``per_pair = R > 1`` takes up to R repeats from each pair of sequences, and ``within=True`` adds the pairs
+        ``(s, s)``: the repeats INSIDE one sequence, its cells with ``j - i < min_sep`` held at 0 (``local_align_unit_strings_all``,
+        "Unit repeats, every one": the rectangle of each found repeat is taken out before the next round of its pair).  Every
+        round with ``score >= min_score`` is a candidate, and the k best come back ordered by (score descending, s, t, round), so
+        ``pairs[r] = (s, t)`` may repeat and may have ``s == t``; ``exclude_same_group`` never skips ``(s, s)``.  The two spans of a
+        repeat inside one sequence may overlap (tandem repetition): ``a1 <= b0`` is the caller's filter.  With ``per_pair=1,
+        within=False`` the call is the one-repeat search above, launch for launch.
+
+        Out of scope: path-exact (Waterman-Eggert) blocking, which needs a traceback; non-overlapping spans inside one sequence.
+        ``SyllableIndex.find_repeats`` is the one-repeat search on embeddings and still returns one repeat per pair."""
         N, dev, W = len(self), self.device, self.width
         if N == 0:
             raise ValueError("the index is empty")
@@ -391,50 +402,56 @@ class UnitIndex:
         k = int(k)
         params = _local_params(match, mismatch, gap)
         pair_chunk = _check_pair_chunk(pair_chunk)
-        if min_score is None:
-            floor = 3 * params[0] * W
-        elif isinstance(min_score, bool) or not isinstance(min_score, (int, np.integer)) or int(min_score) < 1:
-            raise ValueError("min_score must be None or an integer >= 1, got %r" % (min_score,))
-        else:
-            floor = int(min_score)
+        floor = _min_score(min_score, params[0], W)
+        R, min_sep = _check_best(per_pair, "per_pair"), _check_min_sep(min_sep)
+        if not isinstance(within, (bool, np.bool_)):
+            raise ValueError("within must be a bool, got %r" % (within,))
+        every = R > 1 or bool(within)                       # else the one-repeat entry, as before these arguments
         off = _sequences(sequences, N, self.sequence_offsets)
         S = int(off.size - 1)
         scores = torch.zeros((k,), dtype=torch.int32, device=dev)
         pairs = torch.full((k, 2), -1, dtype=torch.int64, device=dev)
         spans = torch.full((k, 4), -1, dtype=torch.int64, device=dev)
-        if S < 2:
+        if S < (1 if within else 2):
             return scores, pairs, spans.reshape(k, 2, 2)
         lib = _lib.load()
         lens = np.diff(off)
         grp = self._g.index_select(0, torch.from_numpy(off[:-1]).to(dev)).cpu().numpy() if exclude_same_group else None
-        # pair (s, t), s < t, is number first[s] + t - s - 1 of the enumeration by (s, t)
+        # pair (s, t), s < t, is number first[s] + t - s - 1 of the enumeration by (s, t); with `within`, s <= t, first[s] + t - s
         idx = np.arange(S, dtype=np.int64)
-        first, total = idx * S - idx * (idx + 1) // 2, S * (S - 1) // 2
+        d = 0 if within else 1                              # the first t of row s is s + d
+        first, total = idx * S - idx * (idx + 2 * d - 1) // 2, S * (S + 1 - 2 * d) // 2
         step = pair_chunk if pair_chunk is not None else REPEAT_PAIRS
-        best = None                                         # the kept pairs so far: (scores, s, t, spans), in the contract's order
+        best = None                                         # the kept repeats so far: (scores, (s, t), spans), in the contract's order
         for p0 in range(0, total, step):
             p = np.arange(p0, min(total, p0 + step), dtype=np.int64)
             s = np.searchsorted(first, p, side="right") - 1
-            t = p - first[s] + s + 1
+            t = p - first[s] + s + d
             if grp is not None:
-                other = grp[s] != grp[t]
+                other = (grp[s] != grp[t]) | (s == t)
                 s, t = s[other], t[other]
             n = int(s.size)
             if n == 0:
                 continue
             xw, yw = (np.ascontiguousarray(np.stack([off[q], lens[q]], 1), np.int32) for q in (s, t))
-            sc = torch.empty((n,), dtype=torch.int32, device=dev)
-            sp = torch.empty((n, 4), dtype=torch.int32, device=dev)
-            _local_launch(lib, self._u, self._u, W, xw, yw, params, sc, sp, 0, pair_chunk, _workspace_fill, dev)
+            sc = torch.empty((n, R), dtype=torch.int32, device=dev)
+            sp = torch.empty((n, R, 4), dtype=torch.int32, device=dev)
+            if every:
+                sep = np.where(s == t, min_sep, 0).astype(np.int32)
+                _local_all_launch(lib, self._u, self._u, W, xw, yw, sep, params, R, floor, sc, sp, pair_chunk, _workspace_fill, dev)
+            else:
+                _local_launch(lib, self._u, self._u, W, xw, yw, params, sc, sp, 0, pair_chunk, _workspace_fill, dev)
+            sc, sp = sc.reshape(n * R), sp.reshape(n * R, 4)      # candidate c: round c % R of pair c // R
             keep = (sc >= floor).nonzero().flatten()
             if keep.numel() == 0:
                 continue
-            st = torch.from_numpy(np.stack([s, t], 1)).to(dev).index_select(0, keep)
-            base = torch.from_numpy(np.stack([off[s], off[s], off[t], off[t]], 1)).to(dev).index_select(0, keep)
+            of = keep // R
+            st = torch.from_numpy(np.stack([s, t], 1)).to(dev).index_select(0, of)
+            base = torch.from_numpy(np.stack([off[s], off[s], off[t], off[t]], 1)).to(dev).index_select(0, of)
             new = (sc.index_select(0, keep), st, sp.index_select(0, keep).to(torch.int64) + base)
             if best is not None:
                 new = tuple(torch.cat([a, b]) for a, b in zip(best, new))
-            # what was kept before comes from earlier pairs and is in order: a stable sort by score alone keeps (s, t) ascending
+            # what was kept before comes from earlier pairs and is in order: a stable sort by score alone keeps (s, t, round) ascending
             order = torch.sort(-new[0].to(torch.int64), stable=True).indices[:k]
             best = tuple(a.index_select(0, order) for a in new)
         if best is not None:
@@ -701,25 +718,33 @@ def _check_pair_chunk(pair_chunk) -> Optional[int]:
     return int(pair_chunk)
 
 
-def _local_launch(lib, xd, yd, W, xw, yw, params, scores, spans, at, pair_chunk, fill, dev) -> None:
-    """``sylber_unit_local_align`` on the pairs of the windows ``xw`` / ``yw`` (int32 ``[n, 2]`` on the host, ``n >= 1``) into
-    ``scores[at : at + n]`` and ``spans[at : at + n]``: ``pair_chunk`` pairs per launch, or as many as keep a launch's workspace
-    below ``ALIGN_WORKSPACE_BYTES``"""
+def _local_groups(size_fn, name: str, table: int, xw, yw, pair_chunk) -> list:
+    """the launches of a local alignment over the pairs of ``xw`` / ``yw``: ``pair_chunk`` pairs each, or as many as keep a launch's
+    workspace (``table`` bytes of table per pair and its two rows) below ``ALIGN_WORKSPACE_BYTES`` -> ``[(g0, g1, xw[g0:g1],
+    yw[g0:g1], bytes)]`` with ``bytes`` what ``size_fn`` (the entry's size function, ``name``) says of that launch"""
     n = int(xw.shape[0])
     if pair_chunk is not None:
         cuts = list(range(0, n, pair_chunk)) + [n]
     else:
-        need = unit_local_workspace_bytes(xw[:, 1], yw[:, 1]) + 40
+        need = unit_local_workspace_bytes(xw[:, 1], yw[:, 1]) + table
         cuts, acc = [0], np.concatenate([[0], np.cumsum(need)])
         while cuts[-1] < n:
             cuts.append(max(cuts[-1] + 1, int(np.searchsorted(acc, acc[cuts[-1]] + ALIGN_WORKSPACE_BYTES - 256, side="right")) - 1))
     groups = []
     for g0, g1 in zip(cuts[:-1], cuts[1:]):
         a, b = np.ascontiguousarray(xw[g0:g1]), np.ascontiguousarray(yw[g0:g1])
-        size = int(lib.sylber_unit_local_workspace_bytes(a.ctypes.data_as(_i32p), b.ctypes.data_as(_i32p), g1 - g0))
+        size = int(size_fn(a.ctypes.data_as(_i32p), b.ctypes.data_as(_i32p), g1 - g0))
         if size < 0:
-            raise _lib.SylberHipError("sylber_unit_local_workspace_bytes refused the call")
+            raise _lib.SylberHipError("%s refused the call" % name)
         groups.append((g0, g1, a, b, size))
+    return groups
+
+
+def _local_launch(lib, xd, yd, W, xw, yw, params, scores, spans, at, pair_chunk, fill, dev) -> None:
+    """``sylber_unit_local_align`` on the pairs of the windows ``xw`` / ``yw`` (int32 ``[n, 2]`` on the host, ``n >= 1``) into
+    ``scores[at : at + n]`` and ``spans[at : at + n]``: ``pair_chunk`` pairs per launch, or as many as keep a launch's workspace
+    below ``ALIGN_WORKSPACE_BYTES``"""
+    groups = _local_groups(lib.sylber_unit_local_workspace_bytes, "sylber_unit_local_workspace_bytes", 40, xw, yw, pair_chunk)
     with torch.cuda.device(dev):
         st = _stream(dev)
         ws = None
@@ -732,6 +757,47 @@ def _local_launch(lib, xd, yd, W, xw, yw, params, scores, spans, at, pair_chunk,
                                                    b.ctypes.data_as(_i32p), g1 - g0, params[0], params[1], params[2],
                                                    _vp(scores[at + g0:at + g1]), _vp(spans[at + g0:at + g1]), _vp(ws), st),
                        "sylber_unit_local_align")
+
+
+def _local_all_launch(lib, xd, yd, W, xw, yw, sep, params, n_best, floor, scores, spans, pair_chunk, fill, dev) -> None:
+    """``sylber_unit_local_align_all`` on the pairs of the windows ``xw`` / ``yw`` with ``sep`` (int32 ``[n]`` on the host) into
+    ``scores [n, n_best]`` and ``spans [n, n_best, 4]``, grouped into launches as ``_local_launch`` groups them"""
+    groups = _local_groups(lib.sylber_unit_local_all_workspace_bytes, "sylber_unit_local_all_workspace_bytes", 48, xw, yw, pair_chunk)
+    floor = min(floor, 2 ** 31 - 1)                        # an int32 argument; no score reaches 64 * 8 * 65 536
+    with torch.cuda.device(dev):
+        st = _stream(dev)
+        ws = None
+        for g0, g1, a, b, size in groups:
+            if ws is None or ws.numel() != size:           # exactly what the size function said, launch by launch
+                ws = torch.empty(size, dtype=torch.uint8, device=dev)
+                if fill is not None:
+                    ws.fill_(fill)
+            c = np.ascontiguousarray(sep[g0:g1], np.int32)
+            _lib.check(lib.sylber_unit_local_align_all(_vp(xd), xd.shape[0], _vp(yd), yd.shape[0], W, a.ctypes.data_as(_i32p),
+                                                       b.ctypes.data_as(_i32p), c.ctypes.data_as(_i32p), g1 - g0, params[0], params[1],
+                                                       params[2], n_best, floor, _vp(scores[g0:g1]), _vp(spans[g0:g1]), _vp(ws), st),
+                       "sylber_unit_local_align_all")
+
+
+def _check_best(n, what: str) -> int:
+    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not 1 <= int(n) <= MAX_BEST:
+        raise ValueError("%s must be an integer in [1, %d], got %r" % (what, MAX_BEST, n))
+    return int(n)
+
+
+def _check_min_sep(min_sep) -> int:
+    if isinstance(min_sep, bool) or not isinstance(min_sep, (int, np.integer)) or not 1 <= int(min_sep) <= MAX_STRING_UNITS:
+        raise ValueError("min_sep must be an integer in [1, %d], got %r" % (MAX_STRING_UNITS, min_sep))
+    return int(min_sep)
+
+
+def _min_score(min_score, match: int, W: int) -> int:
+    """the floor of a repeat's score: ``None`` = ``3 * match * W``, three exactly repeated units"""
+    if min_score is None:
+        return 3 * match * W
+    if isinstance(min_score, bool) or not isinstance(min_score, (int, np.integer)) or int(min_score) < 1:
+        raise ValueError("min_score must be None or an integer >= 1, got %r" % (min_score,))
+    return int(min_score)
 
 
 def local_align_unit_strings(xs, ys, *, match: int = 2, mismatch: int = 3, gap: int = 4, device="cuda",
@@ -766,8 +832,8 @@ def local_align_unit_strings(xs, ys, *, match: int = 2, mismatch: int = 3, gap: 
     or on stale workspace contents.  ``ValueError`` before any launch: what ``align_unit_strings`` refuses, and a parameter outside
     its range.  ``S = 0`` returns empty tensors without a launch.
 
-    Out of scope: more than one repeat per pair (Waterman-Eggert suppression is the known next step), repeats inside one string
-    (cut it), and the same on embeddings."""
+    More than one repeat per pair and the repeats inside one string: ``local_align_unit_strings_all``.  Out of scope: the same on
+    embeddings."""
     xp, xl, Wx = _strings(xs, "xs")
     yp, yl, Wy = _strings(ys, "ys")
     S = int(xl.size)
@@ -789,3 +855,60 @@ def local_align_unit_strings(xs, ys, *, match: int = 2, mismatch: int = 3, gap: 
         xw, yw = (np.ascontiguousarray(np.stack([o[:-1], np.diff(o)], 1), np.int32) for o in (xo, yo))
         _local_launch(_lib.load(), xd, yd, W, xw, yw, params, scores, spans, 0, pair_chunk, _workspace_fill, dev)
     return scores, spans.to(torch.int64).reshape(S, 2, 2)
+
+
+def local_align_unit_strings_all(xs, ys=None, *, n_best: int, min_score=None, min_sep: int = 1, match: int = 2, mismatch: int = 3,
+                                 gap: int = 4, device="cuda", pair_chunk: Optional[int] = None,
+                                 _workspace_fill=None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """EVERY phrase two unit strings share, and the phrases one string says more than once: up to ``n_best`` local alignments per
+    pair -> ``(scores int32 [S, n_best], spans int64 [S, n_best, 2, 2])`` on the device (csrc/unit_repeats_all.hip,
+    ``sylber_unit_local_align_all``; contract in include/sylber_hip.h "Unit repeats, every one", restated in
+    tests/unit_repeats_all_ref.py).  Strings and parameters are ``local_align_unit_strings``'s; ``1 <= n_best <= 32``.
+
+    The rounds ``r = 0 .. n_best - 1`` of a pair run in order, all in one launch.  Round ``r`` is the recurrence of
+    ``local_align_unit_strings`` with the cells ``(i, j)``, ``a0 <= i < a1`` and ``b0 <= j < b1``, of every earlier round's
+    ``spans[s, q] = ((a0, a1), (b0, b1))`` held at ``H = 0``: the rectangle of a found repeat is taken out, and with it the shadow
+    alignments that hug its path.  A round whose score is below ``min_score`` (``None``: ``3 * match * W``, three exactly repeated
+    units; else an integer >= 1) ends the pair: it and the later rounds are score 0 and spans -1.  Scores never increase along
+    ``n_best``.  Rectangles of different rounds may intersect as rectangles, so two repeats of a pair may share units of ``x`` or
+    of ``y``, not both at once: a phrase said once in ``x`` and twice in ``y`` comes back twice with the same ``x`` span.
+
+    ``ys=None`` aligns every string against ITSELF: the cells with ``j - i < min_sep`` (``min_sep >= 1``) are held at 0 as well,
+    so only ``j > i`` is left, every repeat is found once and ``spans[s, r]`` has its earlier occurrence first.  Three occurrences
+    come back as three repeats, (p1, p2), (p1, p3), (p2, p3).  The two spans of such a repeat may overlap, as in tandem
+    repetition: ``[1, 2, 3] * 10`` gives one repeat, ``0:27`` against ``3:30``.  ``a1 <= b0`` is the caller's filter.  With ``ys``
+    given ``min_sep`` is ignored.
+
+    With ``ys``, ``min_score=1`` and any ``n_best``, ``scores[:, 0]`` and ``spans[:, 0]`` are ``local_align_unit_strings``'s, bit
+    for bit.  Exact (small integers), and nothing depends on ``pair_chunk``, on which pairs share a call, on their order or on stale
+    workspace contents.  ``ValueError`` before any launch: what ``local_align_unit_strings`` refuses, ``n_best`` outside 1 .. 32,
+    ``min_score < 1``, ``min_sep < 1``.  ``S = 0`` returns empty tensors without a launch.
+
+    Out of scope: path-exact (Waterman-Eggert) blocking, which needs a traceback; non-overlapping spans inside one string; the
+    same on embeddings."""
+    xp, xl, Wx = _strings(xs, "xs")
+    yp, yl, Wy = (xp, xl, Wx) if ys is None else _strings(ys, "ys")
+    S = int(xl.size)
+    if S != int(yl.size):
+        raise ValueError("xs and ys must be equally long, got %d and %d strings" % (S, int(yl.size)))
+    if Wx is not None and Wy is not None and Wx != Wy:
+        raise ValueError("xs have W = %d, ys have W = %d" % (Wx, Wy))
+    pair_chunk = _check_pair_chunk(pair_chunk)
+    params = _local_params(match, mismatch, gap)
+    n_best = _check_best(n_best, "n_best")
+    min_sep = _check_min_sep(min_sep)
+    W = Wx or Wy or 1
+    floor = _min_score(min_score, params[0], W)
+    xo, yo = (np.concatenate([[0], np.cumsum(v)]).astype(np.int64) for v in (xl, yl))
+    if xo[-1] >= 2 ** 31 or yo[-1] >= 2 ** 31:
+        raise ValueError("one call takes fewer than 2^31 units on each side")
+    dev = _device(device)
+    scores = torch.empty((S, n_best), dtype=torch.int32, device=dev)
+    spans = torch.empty((S, n_best, 4), dtype=torch.int32, device=dev)
+    if S:
+        xd = _flat_strings(xp, W, dev, "xs")
+        yd = xd if ys is None else _flat_strings(yp, W, dev, "ys")
+        xw, yw = (np.ascontiguousarray(np.stack([o[:-1], np.diff(o)], 1), np.int32) for o in (xo, yo))
+        sep = np.full(S, min_sep if ys is None else 0, np.int32)
+        _local_all_launch(_lib.load(), xd, yd, W, xw, yw, sep, params, n_best, floor, scores, spans, pair_chunk, _workspace_fill, dev)
+    return scores, spans.to(torch.int64).reshape(S, n_best, 2, 2)
