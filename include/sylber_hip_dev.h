@@ -1,7 +1,7 @@
 /*
  * sylber_hip_dev.h -- development aids exported by libsylber_hip.so that are NOT part of the drop-in C-ABI
  * (include/sylber_hip.h): micro-benchmarks used by tools/.  Nothing on the product path or in the parity tests
- * needs them (one GPU test uses the workspace-poisoning aid), and they keep no process-global state.
+ * needs them (GPU tests use the workspace-poisoning aid and the taps), and they keep no process-global state.
  */
 #ifndef SYLBER_HIP_DEV_H
 #define SYLBER_HIP_DEV_H
@@ -45,6 +45,26 @@ int sylber_debug_conv_rows(int32_t n_samples, int32_t* L, int32_t* R);
 /* average ms of one launch of the attention core (12 heads x 64, B utterances of T frames, no key mask) on pseudo-random packed
  * operands; precision: SYLBER_BF16 (bf16 operands) or SYLBER_FP8 (MXFP8 q / k / V^T, e4m3 P) */
 int sylber_debug_attention_bench(int32_t B, int32_t T, int32_t precision, int32_t iters, float* ms_out);
+/* test aid: a tap inside the resynthesis decoder (csrc/cfm.hip), per handle, off by default and without effect when off.  With a stage set,
+ * the next eval / sample / sample_frames / sample_packed call (steps >= 2) runs its preparation and its first evaluation (time index 0; a
+ * sample call: t = 0, state y0) through the launches it always issues, up to the launch that writes the stage's buffer, copies that buffer to
+ * tap_dev and returns 0; the call's own output is not written.  The copy is every row of the buffer (M = B x Tp rows, or the packed
+ * call's slot rows; frame rows B x T or sum Tb for CONDX / XE) without the slack rows, in STORAGE order (no permutation undone), 16-bit
+ * words widened to fp32 exactly.  The setting persists until changed; stage 0 switches it off.  Refused with an error text and no launch: an
+ * unknown stage (Q / K / VT exist in the 16-bit precisions only, QKVF in fp32 only), a call whose stage needs more than tap_floats
+ * floats, a sample call with steps = 1 (no evaluation).  tests/test_gpu_cfm_block.py holds every stage to float64.
+ *   front stages: CONDX [NF, 512]; GB [16 norms][gamma, beta][512] of time index 0; XE [NF, 512]; X0 [M, 512] (behind cfm_conv)
+ *   block li = 0..7, SYLBER_CFM_TAP(li, k): H_ATTN [M, 512]; QKV [M, 1536] fp32; Q, K [B, 12, Tp, 64]; VT [B, 12, 64, Tpv]; QKVF [M, 2304];
+ *   CTX [M, 768]; X_ATTN [M, 512]; H_FF [M, 512]; FF [M, 2816] (value 1408 | gate 1408); G [M, 1408]; X_FF [M, 512] */
+enum { SYLBER_CFM_TAP_CONDX = 1, SYLBER_CFM_TAP_GB = 2, SYLBER_CFM_TAP_XE = 3, SYLBER_CFM_TAP_X0 = 4 };
+enum { SYLBER_CFM_BTAP_H_ATTN = 0, SYLBER_CFM_BTAP_QKV = 1, SYLBER_CFM_BTAP_Q = 2, SYLBER_CFM_BTAP_K = 3, SYLBER_CFM_BTAP_VT = 4,
+       SYLBER_CFM_BTAP_QKVF = 5, SYLBER_CFM_BTAP_CTX = 6, SYLBER_CFM_BTAP_X_ATTN = 7, SYLBER_CFM_BTAP_H_FF = 8, SYLBER_CFM_BTAP_FF = 9,
+       SYLBER_CFM_BTAP_G = 10, SYLBER_CFM_BTAP_X_FF = 11 };
+#define SYLBER_CFM_TAP(block, k) (16 * ((block) + 1) + (k))
+int sylber_cfm_set_tap(sylber_cfm_t h, int32_t stage, float* tap_dev, int64_t tap_floats);
+/* floats the tap of `stage` writes for a padded [B, T] call / a packed call of B clips; -1 for an unknown stage or a bad shape */
+int64_t sylber_cfm_tap_floats(sylber_cfm_t h, int32_t stage, int32_t B, int32_t T);
+int64_t sylber_cfm_tap_floats_packed(sylber_cfm_t h, int32_t stage, const int32_t* frames_host, int32_t B);
 #ifdef __cplusplus
 }
 #endif

@@ -249,7 +249,19 @@ DEV_EXPORTS = {
     "sylber_debug_poison_workspace": (c_int, [c_void_p, c_int32]),
     "sylber_debug_conv0_scale_shift": (c_int, [c_void_p, c_int32, c_void_p]),
     "sylber_debug_conv_rows": (c_int, [c_int32, POINTER(c_int32), POINTER(c_int32)]),
+    "sylber_cfm_set_tap": (c_int, [c_void_p, c_int32, c_void_p, c_int64]),
+    "sylber_cfm_tap_floats": (c_int64, [c_void_p, c_int32, c_int32, c_int32]),
+    "sylber_cfm_tap_floats_packed": (c_int64, [c_void_p, c_int32, POINTER(c_int32), c_int32]),
 }
+# taps inside the resynthesis decoder (include/sylber_hip_dev.h SYLBER_CFM_TAP_* / SYLBER_CFM_BTAP_*): the front stages, and launch k of block li
+CFM_TAP_CONDX, CFM_TAP_GB, CFM_TAP_XE, CFM_TAP_X0 = 1, 2, 3, 4
+(CFM_BTAP_H_ATTN, CFM_BTAP_QKV, CFM_BTAP_Q, CFM_BTAP_K, CFM_BTAP_VT, CFM_BTAP_QKVF, CFM_BTAP_CTX, CFM_BTAP_X_ATTN, CFM_BTAP_H_FF, CFM_BTAP_FF,
+ CFM_BTAP_G, CFM_BTAP_X_FF) = range(12)
+
+
+def CFM_TAP(block: int, k: int) -> int:
+    """the tap stage behind launch k (CFM_BTAP_*) of decoder block ``block``"""
+    return 16 * (int(block) + 1) + int(k)
 OPT_GEMM_TILE, OPT_ATTN_QUERIES_PER_WAVE, OPT_GEMM_PERSISTENT = 1, 2, 3
 OPT_FUSE_OUTPROJ_LN, OPT_CONV0_VALU = 4, 5
 OPT_FP8_ATTENTION, OPT_SEGMENT, OPT_PER_UTTERANCE = 7, 9, 14

@@ -30,6 +30,7 @@
 // [1, Tb] call computes.
 #include "kernels.h"
 #include "../../include/sylber_hip.h"
+#include "../../include/sylber_hip_dev.h"
 #include <cmath>
 #include <vector>
 
@@ -68,6 +69,8 @@ struct sylber_cfm {
     float *fin_g = nullptr, *pred_w = nullptr;                       // [512], [14][512]
     // GEMM operands: fp32 in the parity mode, else 16-bit copies (same packing, CFM_SLACK zero rows behind each)
     const void *wc = nullptr, *wqkv[SYLBER_CFM_DEPTH] = {}, *wo[SYLBER_CFM_DEPTH] = {}, *w1[SYLBER_CFM_DEPTH] = {}, *w2[SYLBER_CFM_DEPTH] = {};
+    // development tap (sylber_cfm_set_tap, include/sylber_hip_dev.h): 0 = off
+    int tap_stage = 0; float* tap_dev = nullptr; int64_t tap_floats = 0;
 };
 
 // ---- workspace layout ----------------------------------------------------------------------------------------------
@@ -151,6 +154,36 @@ static CfmLayout cfm_layout_packed(int precision, int nclip, int Ptot, long NF) 
     return l;
 }
 
+// ---- development tap ---------------------------------------------------------------------------------------------------
+// the buffer behind stage `stage` of a call with layout l: its bytes in the workspace, its floats (every row, no slack rows) and
+// whether it holds 16-bit words.  false: no such stage in this precision
+struct CfmTapBuf { size_t off; int64_t n; bool half; };
+static bool cfm_tap_buf(int precision, const CfmLayout& l, int stage, CfmTapBuf& t) {
+    const bool f32 = precision == SYLBER_FP32;
+    const int64_t M = l.M, NF = l.NF;
+    switch (stage) {
+    case SYLBER_CFM_TAP_CONDX: t = {l.o_condx, NF * CFM_D, false}; return true;
+    case SYLBER_CFM_TAP_GB: t = {l.o_gb, (int64_t)CFM_NORMS * 2 * CFM_D, false}; return true;
+    case SYLBER_CFM_TAP_XE: t = {l.o_xe, NF * CFM_D, false}; return true;
+    case SYLBER_CFM_TAP_X0: t = {l.o_x, M * CFM_D, false}; return true;
+    }
+    if (stage < SYLBER_CFM_TAP(0, 0) || stage >= SYLBER_CFM_TAP(SYLBER_CFM_DEPTH, 0)) return false;
+    const int64_t nq = (int64_t)l.B * SYL_HEADS * l.Tp * 64;
+    switch (stage & 15) {
+    case SYLBER_CFM_BTAP_H_ATTN: case SYLBER_CFM_BTAP_H_FF: t = {l.o_h, M * CFM_D, !f32}; return true;
+    case SYLBER_CFM_BTAP_QKV: t = {l.o_qkv, M * 3 * CFM_D, false}; return true;
+    case SYLBER_CFM_BTAP_Q: t = {l.o_q, nq, true}; return !f32;
+    case SYLBER_CFM_BTAP_K: t = {l.o_k, nq, true}; return !f32;
+    case SYLBER_CFM_BTAP_VT: t = {l.o_vt, (int64_t)l.B * SYL_HEADS * 64 * l.Tpv, true}; return !f32;
+    case SYLBER_CFM_BTAP_QKVF: t = {l.o_qkvf, M * 3 * SYL_HIDDEN, false}; return f32;
+    case SYLBER_CFM_BTAP_CTX: t = {l.o_ctx, M * SYL_HIDDEN, !f32}; return true;
+    case SYLBER_CFM_BTAP_X_ATTN: case SYLBER_CFM_BTAP_X_FF: t = {l.o_x, M * CFM_D, false}; return true;
+    case SYLBER_CFM_BTAP_FF: t = {l.o_ff, M * 2 * CFM_FIP, false}; return true;
+    case SYLBER_CFM_BTAP_G: t = {l.o_g, M * CFM_FIP, !f32}; return true;
+    }
+    return false;
+}
+
 // ---- kernels ---------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ float cfm_gelu(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752f)); }
 
@@ -200,6 +233,12 @@ __global__ __launch_bounds__(256) void cfm_time_gb(const float* __restrict__ tem
 template <int FMT>
 __global__ void cfm_convert(const float* __restrict__ in, bf16_t* __restrict__ out, size_t n) {
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) out[i] = H16<FMT>::cvt(in[i]);
+}
+
+// the tap's copy of a 16-bit buffer: every word widened to fp32 (exact)
+template <int FMT>
+__global__ void cfm_widen(const bf16_t* __restrict__ in, float* __restrict__ out, size_t n) {
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) out[i] = H16<FMT>::up(in[i]);
 }
 
 // xe[b, t] = condx[b, t] + Wy y[b, t]   (condx holds to_embed's cond block plus every bias)
@@ -421,6 +460,31 @@ static int cfm_gemm(const sylber_cfm* h, const void* X, long ldx, const void* W,
 
 #define CFM_RUN(what, expr) do { if (expr) return 1; HIP_TRY(hipGetLastError()); } while (0)
 
+// a tap is set and `stage` is it: copy the buffer behind the launch just issued to the caller's tap buffer (storage order, 16-bit words
+// widened) and end the call.  CFM_TAPPED is cfm_evaluate's third result: no error, nothing further launched
+enum { CFM_TAPPED = 2 };
+static int cfm_tap_copy(const sylber_cfm* h, const CfmLayout& l, char* ws, int stage, int ti, hipStream_t s) {
+    CfmTapBuf t;
+    if (!cfm_tap_buf(h->precision, l, stage, t) || t.n > h->tap_floats) { syl_set_error("sylber_cfm tap", "tap buffer does not fit the stage"); return 1; }
+    const char* src = ws + t.off + (stage == SYLBER_CFM_TAP_GB ? (size_t)ti * CFM_NORMS * 2 * CFM_D * 4 : 0);
+    if (!t.half) HIP_TRY(hipMemcpyAsync(h->tap_dev, src, (size_t)t.n * 4, hipMemcpyDeviceToDevice, s));
+    else if (h->fmt == FMT_F16) hipLaunchKernelGGL(cfm_widen<FMT_F16>, dim3(1024), dim3(256), 0, s, (const bf16_t*)src, h->tap_dev, (size_t)t.n);
+    else hipLaunchKernelGGL(cfm_widen<FMT_BF16>, dim3(1024), dim3(256), 0, s, (const bf16_t*)src, h->tap_dev, (size_t)t.n);
+    HIP_TRY(hipGetLastError());
+    return CFM_TAPPED;
+}
+#define CFM_TAP(stage) do { if (h->tap_stage == (stage)) return cfm_tap_copy(h, l, ws, (stage), ti, s); } while (0)
+
+// what every entry point asks before it launches anything while a tap is set
+static int cfm_tap_check(const char* what, const sylber_cfm* h, const CfmLayout& l, int steps) {
+    if (!h->tap_stage) return 0;
+    CfmTapBuf t;
+    if (!cfm_tap_buf(h->precision, l, h->tap_stage, t)) { syl_set_error(what, "the tap's stage does not exist in this precision"); return 1; }
+    if (t.n > h->tap_floats) { syl_set_error(what, "the tap buffer is too small for this call (sylber_cfm_tap_floats)"); return 1; }
+    if (steps < 2) { syl_set_error(what, "a tap needs an evaluation: steps >= 2"); return 1; }
+    return 0;
+}
+
 // torch.linspace(0, 1, steps) on the CPU in float32: the first half counts up from 0, the second half down from 1
 static void cfm_linspace(int steps, std::vector<float>& t) {
     t.resize(steps);
@@ -443,10 +507,14 @@ static int cfm_evaluate(const sylber_cfm* h, const CfmLayout& l, char* ws, int t
     const float* gb = (const float*)(ws + l.o_gb) + (size_t)ti * CFM_NORMS * 2 * CFM_D;
     const int M = (int)l.M;
     const dim3 rows4((unsigned)((l.M + 3) / 4));
+    CFM_TAP(SYLBER_CFM_TAP_CONDX);
+    CFM_TAP(SYLBER_CFM_TAP_GB);
     hipLaunchKernelGGL(cfm_embed, dim3((unsigned)l.NF), dim3(256), 0, s, (const float*)(ws + l.o_condx), yin, h->wy, xe);
     CFM_RUN("embed", 0);
+    CFM_TAP(SYLBER_CFM_TAP_XE);
     hipLaunchKernelGGL(cfm_conv, dim3(l.Tp, B), dim3(256), 0, s, xe, h->conv_w, h->conv_b, h->reg, x, T, l.Tp, valid, pk, nclip);
     CFM_RUN("conv", 0);
+    CFM_TAP(SYLBER_CFM_TAP_X0);
     auto norm = [&](int n) {
         const float* ga = gb + (size_t)n * 2 * CFM_D;
         if (f32) hipLaunchKernelGGL((cfm_adanorm<FMT_BF16, true>), rows4, dim3(256), 0, s, x, ga, ga + CFM_D, hb, l.M);
@@ -456,7 +524,9 @@ static int cfm_evaluate(const sylber_cfm* h, const CfmLayout& l, char* ws, int t
     for (int li = 0; li < SYLBER_CFM_DEPTH; ++li) {
         norm(2 * li);
         CFM_RUN("adanorm", 0);
+        CFM_TAP(SYLBER_CFM_TAP(li, SYLBER_CFM_BTAP_H_ATTN));
         CFM_RUN("qkv", cfm_gemm(h, hb, CFM_D, h->wqkv[li], M, 3 * CFM_D, CFM_D, nullptr, qkv, 3 * CFM_D, false, s));
+        CFM_TAP(SYLBER_CFM_TAP(li, SYLBER_CFM_BTAP_QKV));
         const float* qg = h->qg + li * CFM_H * 64; const float* kg = h->kg + li * CFM_H * 64;
         const dim3 gq(l.L, B, 2);
         if (f32) {
@@ -464,6 +534,7 @@ static int cfm_evaluate(const sylber_cfm* h, const CfmLayout& l, char* ws, int t
             hipLaunchKernelGGL((cfm_qkprep<FMT_BF16, true>), gq, dim3(256), 0, s, qkv, qg, kg, h->inv_freq, nullptr, nullptr, nullptr, qkvf, l.L, l.Tp, l.Tpv,
                                nullptr, 0);
             CFM_RUN("qkprep", 0);
+            CFM_TAP(SYLBER_CFM_TAP(li, SYLBER_CFM_BTAP_QKVF));
             CFM_RUN("attention", launch_attention_f32(qkvf, qkvf + SYL_HIDDEN, qkvf + 2 * SYL_HIDDEN, valid, (float*)ctx, B, l.L, l.Tp, s));
         } else {
             bf16_t* q = (bf16_t*)(ws + l.o_q); bf16_t* k = (bf16_t*)(ws + l.o_k); bf16_t* vt = (bf16_t*)(ws + l.o_vt);
@@ -471,18 +542,27 @@ static int cfm_evaluate(const sylber_cfm* h, const CfmLayout& l, char* ws, int t
                                                       pk, nclip);
             else hipLaunchKernelGGL((cfm_qkprep<FMT_BF16, false>), gq, dim3(256), 0, s, qkv, qg, kg, h->inv_freq, q, k, vt, nullptr, l.L, l.Tp, l.Tpv, pk, nclip);
             CFM_RUN("qkprep", 0);
+            CFM_TAP(SYLBER_CFM_TAP(li, SYLBER_CFM_BTAP_Q));
+            CFM_TAP(SYLBER_CFM_TAP(li, SYLBER_CFM_BTAP_K));
+            CFM_TAP(SYLBER_CFM_TAP(li, SYLBER_CFM_BTAP_VT));
             if (pk) CFM_RUN("attention", launch_attention_packed(q, k, vt, pk, nclip, l.total_qb, (bf16_t*)ctx, l.Tp, s, h->fmt));
             else CFM_RUN("attention", launch_attention(q, k, vt, valid, (bf16_t*)ctx, B, l.L, l.Tp, l.Tpv, 0, s, h->fmt));
         }
+        CFM_TAP(SYLBER_CFM_TAP(li, SYLBER_CFM_BTAP_CTX));
         CFM_RUN("out", cfm_gemm(h, ctx, SYL_HIDDEN, h->wo[li], M, CFM_D, CFM_D, nullptr, x, CFM_D, true, s));
+        CFM_TAP(SYLBER_CFM_TAP(li, SYLBER_CFM_BTAP_X_ATTN));
         norm(2 * li + 1);
         CFM_RUN("adanorm", 0);
+        CFM_TAP(SYLBER_CFM_TAP(li, SYLBER_CFM_BTAP_H_FF));
         CFM_RUN("ff1", cfm_gemm(h, hb, CFM_D, h->w1[li], M, 2 * CFM_FIP, CFM_D, h->b1 + (size_t)li * 2 * CFM_FIP, ff, 2 * CFM_FIP, false, s));
+        CFM_TAP(SYLBER_CFM_TAP(li, SYLBER_CFM_BTAP_FF));
         if (f32) hipLaunchKernelGGL((cfm_geglu<FMT_BF16, true>), dim3(M), dim3(256), 0, s, ff, g, l.M);
         else if (h->fmt == FMT_F16) hipLaunchKernelGGL((cfm_geglu<FMT_F16, false>), dim3(M), dim3(256), 0, s, ff, g, l.M);
         else hipLaunchKernelGGL((cfm_geglu<FMT_BF16, false>), dim3(M), dim3(256), 0, s, ff, g, l.M);
         CFM_RUN("geglu", 0);
+        CFM_TAP(SYLBER_CFM_TAP(li, SYLBER_CFM_BTAP_G));
         CFM_RUN("ff2", cfm_gemm(h, g, CFM_FIP, h->w2[li], M, CFM_D, CFM_FIP, h->b2 + (size_t)li * CFM_D, x, CFM_D, true, s));
+        CFM_TAP(SYLBER_CFM_TAP(li, SYLBER_CFM_BTAP_X_FF));
     }
     hipLaunchKernelGGL(cfm_final, dim3((unsigned)((l.NF + 3) / 4)), dim3(256), 0, s, x, h->fin_g, h->pred_w, ybase, out, l.NF, nclip ? nclip : B, T,
                        l.Tp, mode, dt, last, pitch_amp, valid, pk);
@@ -655,6 +735,7 @@ static int cfm_sample(const char* what, sylber_cfm_t h, const float* cond_emb_de
     hipStream_t s = (hipStream_t)stream;
     const size_t n = (size_t)B * T * CFM_OUT;
     const CfmLayout l = cfm_layout(h->precision, B, T);
+    if (cfm_tap_check(what, h, l, steps)) return 1;
     char* ws = (char*)workspace_dev;
     int* valid = nullptr;
     if (frames_host) {
@@ -668,8 +749,16 @@ static int cfm_sample(const char* what, sylber_cfm_t h, const float* cond_emb_de
 static int cfm_steps(const sylber_cfm* h, const CfmLayout& l, char* ws, const float* cond_emb_dev, int steps, const float* y0_dev, float pitch_amp,
                      float* art_dev, size_t n, int T, const int* valid, hipStream_t s) {
     // art is the sampler state; steps == 1 is a one-point grid (the state is y0) and scales channel 12 right away
-    hipLaunchKernelGGL(cfm_init_state, dim3(256), dim3(256), 0, s, y0_dev, art_dev, n, steps == 1 ? 1 : 0, pitch_amp, valid, T);
-    HIP_TRY(hipGetLastError());
+    // (a tap leaves art alone: the state of its one evaluation lives in the workspace's midpoint buffer, written after cfm_prepare's clear)
+    const bool tap = h->tap_stage != 0;
+    float* ymid = (float*)(ws + l.o_y);
+    float* state = tap ? ymid : art_dev;
+    auto init = [&]() {
+        hipLaunchKernelGGL(cfm_init_state, dim3(256), dim3(256), 0, s, y0_dev, state, n, steps == 1 ? 1 : 0, pitch_amp, valid, T);
+        HIP_TRY(hipGetLastError());
+        return 0;
+    };
+    if (!tap && init()) return 1;
     if (steps == 1) return 0;
     std::vector<float> t;
     cfm_linspace(steps, t);
@@ -680,7 +769,12 @@ static int cfm_steps(const sylber_cfm* h, const CfmLayout& l, char* ws, const fl
         times.push_back(t[i]); times.push_back(t[i] + half); dts.push_back(dt);
     }
     if (cfm_prepare(h, l, ws, cond_emb_dev, times.data(), (int)times.size(), s)) return 1;
-    float* ymid = (float*)(ws + l.o_y);
+    if (tap) {
+        if (init()) return 1;
+        const int r = cfm_evaluate(h, l, ws, 0, state, state, state, 1, 0.5f * dts[0], 0, pitch_amp, s, valid);
+        if (r == 0) syl_set_error("sylber_cfm tap", "the evaluation ended without reaching the tap's stage");   // (cfm_tap_check rules it out)
+        return r == CFM_TAPPED ? 0 : 1;
+    }
     for (int i = 0; i + 1 < steps; ++i) {
         const float dt = dts[i], half = 0.5f * dt;
         if (cfm_evaluate(h, l, ws, 2 * i, art_dev, art_dev, ymid, 1, half, 0, pitch_amp, s, valid)) return 1;
@@ -745,6 +839,7 @@ extern "C" int sylber_cfm_sample_packed(sylber_cfm_t h, const float* cond_dev, c
     hipStream_t s = (hipStream_t)stream;
     CfmLayout l = cfm_layout_packed(h->precision, B, slot[B], nf);
     l.total_qb = tab[3 * (size_t)B + 1];
+    if (cfm_tap_check(what, h, l, steps)) return 1;
     char* ws = (char*)workspace_dev;
     if (launch_upload_ints((int*)(ws + l.o_valid), tab.data(), (int)tab.size(), 0, s)) return 1;
     return cfm_steps(h, l, ws, cond_dev, steps, y0_dev, pitch_amp, art_dev, (size_t)nf * CFM_OUT, 1, nullptr, s);
@@ -757,7 +852,36 @@ extern "C" int sylber_cfm_eval(sylber_cfm_t h, const float* x_dev, float t, cons
     DevGuardC dg(h->device);
     hipStream_t s = (hipStream_t)stream;
     const CfmLayout l = cfm_layout(h->precision, B, T);
+    if (cfm_tap_check("sylber_cfm_eval", h, l, 2)) return 1;
     char* ws = (char*)workspace_dev;
     if (cfm_prepare(h, l, ws, cond_emb_dev, &t, 1, s)) return 1;
-    return cfm_evaluate(h, l, ws, 0, x_dev, x_dev, v_dev, 0, 0.f, 0, 1.f, s);
+    const int r = cfm_evaluate(h, l, ws, 0, x_dev, x_dev, v_dev, 0, 0.f, 0, 1.f, s);
+    return r == CFM_TAPPED ? 0 : r;
+}
+
+// ---- development tap (include/sylber_hip_dev.h) -------------------------------------------------------------------------------
+extern "C" int sylber_cfm_set_tap(sylber_cfm_t h, int32_t stage, float* tap_dev, int64_t tap_floats) {
+    if (!h) { syl_set_error("sylber_cfm_set_tap", "null handle"); return 1; }
+    if (stage == 0) { h->tap_stage = 0; h->tap_dev = nullptr; h->tap_floats = 0; return 0; }
+    CfmTapBuf t;
+    if (!cfm_tap_buf(h->precision, cfm_layout(h->precision, 1, 1), stage, t)) {
+        syl_set_error("sylber_cfm_set_tap", "unknown stage (or one this precision does not have)"); return 1;
+    }
+    if (!tap_dev || tap_floats < 1) { syl_set_error("sylber_cfm_set_tap", "need a tap buffer"); return 1; }
+    h->tap_stage = stage; h->tap_dev = tap_dev; h->tap_floats = tap_floats;
+    return 0;
+}
+
+extern "C" int64_t sylber_cfm_tap_floats(sylber_cfm_t h, int32_t stage, int32_t B, int32_t T) {
+    CfmTapBuf t;
+    if (!h || B < 1 || T < 1 || (long)B * (CFM_REG + T + 31) > (1l << 24)) return -1;
+    return cfm_tap_buf(h->precision, cfm_layout(h->precision, B, T), stage, t) ? t.n : -1;
+}
+
+extern "C" int64_t sylber_cfm_tap_floats_packed(sylber_cfm_t h, int32_t stage, const int32_t* frames_host, int32_t B) {
+    std::vector<int32_t> slot;
+    long nf = 0;
+    CfmTapBuf t;
+    if (!cfm_packed_check("sylber_cfm_tap_floats_packed", h, frames_host, B, slot, nf)) return -1;
+    return cfm_tap_buf(h->precision, cfm_layout_packed(h->precision, B, slot[B], nf), stage, t) ? t.n : -1;
 }

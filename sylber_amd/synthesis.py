@@ -235,12 +235,30 @@ class CfmDecoder:
             _lib.check(1, "sylber_cfm_workspace_bytes")
         return torch.empty(n, dtype=torch.uint8, device=self.device)
 
+    def _call(self, what: str, fn, args, out, tap: Optional[int], tap_floats):
+        """one library call -> ``out``.  ``tap`` (development aid, ``_lib.CFM_TAP_*`` / ``_lib.CFM_TAP(block, k)``, see
+        include/sylber_hip_dev.h): set around this one call, which then stops behind the tapped launch of its first evaluation and
+        returns that buffer instead -- flat fp32, ``tap_floats()`` values in storage order -- leaving ``out`` unwritten."""
+        if tap is None:
+            _lib.check(fn(*args), what)
+            return out
+        n = int(tap_floats())
+        if n < 0:
+            raise ValueError("%s: no tap stage %r in precision %r" % (what, tap, self.precision))
+        buf = torch.empty(n, dtype=torch.float32, device=self.device)
+        _lib.check(self.lib.sylber_cfm_set_tap(self.handle, int(tap), ctypes.c_void_p(buf.data_ptr()), n), "sylber_cfm_set_tap")
+        try:
+            _lib.check(fn(*args), what)
+        finally:
+            self.lib.sylber_cfm_set_tap(self.handle, 0, None, 0)
+        return buf
+
     def sample(self, cond_emb: torch.Tensor, steps: int = 5, y0: Optional[torch.Tensor] = None, pitch_amp: float = 1.0,
-               frames: Optional[Sequence[int]] = None) -> torch.Tensor:
+               frames: Optional[Sequence[int]] = None, tap: Optional[int] = None) -> torch.Tensor:
         """``cfm_wrapper.sample(cond_emb=..., steps=...)`` from ``y0`` (None: zeros, i.e. ``rand_scale = 0``), then channel 12
-        divided by ``pitch_amp`` -> ``[B, T, 14]`` fp32 on the device.  Enqueued on the current stream.
+        divided by ``pitch_amp`` -> ``[B, T, 14]`` fp32 on the device (with ``tap``: the tap's flat fp32 buffer instead).  Enqueued on the current stream.
         ``frames``: each row's own frame count (``sylber_cfm_sample_frames``): row b is sampled as ``cond_emb[b:b+1, :frames[b]]``
-        alone would be, and ``art[b, frames[b]:]`` is 0.  Counts outside ``[1, T]`` raise ValueError."""
+        alone would be, and ``art[b, frames[b]:]`` is 0.  Counts outside ``[1, T]`` raise ValueError.  ``tap``: see ``_call``."""
         if isinstance(steps, bool) or int(steps) != steps or not 1 <= int(steps) <= 65:
             raise ValueError("steps must be an integer in 1..65, got %r" % (steps,))
         cond = self._cond(cond_emb)
@@ -259,18 +277,18 @@ class CfmDecoder:
                 ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream))
         with torch.cuda.device(self.device):
             if farr is None:
-                _lib.check(self.lib.sylber_cfm_sample(self.handle, ctypes.c_void_p(cond.data_ptr()), B, T, *tail), "sylber_cfm_sample")
-            else:
-                _lib.check(self.lib.sylber_cfm_sample_frames(self.handle, ctypes.c_void_p(cond.data_ptr()), farr, B, T, *tail),
-                           "sylber_cfm_sample_frames")
-        return art
+                return self._call("sylber_cfm_sample", self.lib.sylber_cfm_sample, (self.handle, ctypes.c_void_p(cond.data_ptr()), B, T) + tail,
+                                  art, tap, lambda: self.lib.sylber_cfm_tap_floats(self.handle, int(tap), B, T))
+            return self._call("sylber_cfm_sample_frames", self.lib.sylber_cfm_sample_frames,
+                              (self.handle, ctypes.c_void_p(cond.data_ptr()), farr, B, T) + tail, art, tap,
+                              lambda: self.lib.sylber_cfm_tap_floats(self.handle, int(tap), B, T))
 
-    def sample_packed(self, conds, steps: int = 5, y0: Optional[torch.Tensor] = None, pitch_amp: float = 1.0):
+    def sample_packed(self, conds, steps: int = 5, y0: Optional[torch.Tensor] = None, pitch_amp: float = 1.0, tap: Optional[int] = None):
         """A ragged batch without padding to its longest clip (``sylber_cfm_sample_packed``, bf16 / fp16).  ``conds``: a list of
         ``[T_b, 256]`` tensors, or ``(packed [sum T_b, 256], frames)``.  ``y0``: ``[sum T_b, 14]`` in the same order, or None (zeros).
         Returns ``(art [sum T_b, 14] fp32 on the device, starts)``: clip b is ``art[starts[b]:starts[b + 1]]``, bit-identical to
         ``sample(cond, frames=...)``'s row b and to the clip sampled alone.  ValueError before any launch for an fp32 decoder, bad counts
-        or shapes."""
+        or shapes.  ``tap`` (see ``_call``): returns ``(the tap's buffer, starts)``."""
         if self.precision not in PACKED_PRECISIONS:
             raise ValueError("sample_packed: packed batches run in precision %s only (this decoder: %r)"
                              % (" / ".join(map(repr, PACKED_PRECISIONS)), self.precision))
@@ -305,28 +323,28 @@ class CfmDecoder:
         ws = torch.empty(n, dtype=torch.uint8, device=self.device)
         art = torch.empty(NF, CFM_DIM_OUT, dtype=torch.float32, device=self.device)
         with torch.cuda.device(self.device):
-            _lib.check(self.lib.sylber_cfm_sample_packed(self.handle, ctypes.c_void_p(cond.data_ptr()), farr, B, int(steps),
-                                                         ctypes.c_void_p(y0.data_ptr()) if y0 is not None else None,
-                                                         ctypes.c_float(float(pitch_amp)), ctypes.c_void_p(art.data_ptr()),
-                                                         ctypes.c_void_p(ws.data_ptr()),
-                                                         ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)),
-                       "sylber_cfm_sample_packed")
+            art = self._call("sylber_cfm_sample_packed", self.lib.sylber_cfm_sample_packed,
+                             (self.handle, ctypes.c_void_p(cond.data_ptr()), farr, B, int(steps),
+                              ctypes.c_void_p(y0.data_ptr()) if y0 is not None else None, ctypes.c_float(float(pitch_amp)),
+                              ctypes.c_void_p(art.data_ptr()), ctypes.c_void_p(ws.data_ptr()),
+                              ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)),
+                             art, tap, lambda: self.lib.sylber_cfm_tap_floats_packed(self.handle, int(tap), farr, B))
         return art, _frame_starts(fl)
 
-    def eval(self, x: torch.Tensor, t: float, cond_emb: torch.Tensor) -> torch.Tensor:
-        """one velocity evaluation of the ``Regressor`` at state ``x [B, T, 14]`` and time ``t``"""
+    def eval(self, x: torch.Tensor, t: float, cond_emb: torch.Tensor, tap: Optional[int] = None) -> torch.Tensor:
+        """one velocity evaluation of the ``Regressor`` at state ``x [B, T, 14]`` and time ``t`` -> ``[B, T, 14]`` fp32 on the device
+        (with ``tap``, see ``_call``: the tap's flat fp32 buffer instead)."""
         cond = self._cond(cond_emb)
         x = self._state(x, cond, "x")
         B, T, _ = cond.shape
         v = torch.empty(B, T, CFM_DIM_OUT, dtype=torch.float32, device=self.device)
         ws = self._workspace(B, T)
         with torch.cuda.device(self.device):
-            _lib.check(self.lib.sylber_cfm_eval(self.handle, ctypes.c_void_p(x.data_ptr()), ctypes.c_float(float(t)),
-                                                ctypes.c_void_p(cond.data_ptr()), B, T, ctypes.c_void_p(v.data_ptr()),
-                                                ctypes.c_void_p(ws.data_ptr()),
-                                                ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)),
-                       "sylber_cfm_eval")
-        return v
+            return self._call("sylber_cfm_eval", self.lib.sylber_cfm_eval,
+                              (self.handle, ctypes.c_void_p(x.data_ptr()), ctypes.c_float(float(t)), ctypes.c_void_p(cond.data_ptr()), B, T,
+                               ctypes.c_void_p(v.data_ptr()), ctypes.c_void_p(ws.data_ptr()),
+                               ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)), v, tap,
+                              lambda: self.lib.sylber_cfm_tap_floats(self.handle, int(tap), B, T))
 
 
 class SegmentSynthesis:

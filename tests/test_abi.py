@@ -54,6 +54,26 @@ def test_front_half_taps_are_declared_on_both_sides(lib):
     assert lib.sylber_set_stop_stage(None, -1) != 0 and lib.sylber_debug_conv0_scale_shift(None, 1, None) != 0
 
 
+def test_decoder_taps_are_declared_on_both_sides(lib):
+    """the resynthesis decoder's tap stages (include/sylber_hip_dev.h SYLBER_CFM_TAP_* / SYLBER_CFM_BTAP_* / SYLBER_CFM_TAP) carry the same ids
+    in the header and in the ctypes binding; the entry points are development aids, and refuse a null handle without touching a device"""
+    from sylber_amd import _lib
+    dev = open(os.path.join(ROOT, "include", "sylber_hip_dev.h")).read()
+    front = {k: int(v) for k, v in re.findall(r"\b(SYLBER_CFM_TAP_[A-Z0-9]+)\s*=\s*(\d+)", dev)}
+    assert front == {"SYLBER_CFM_TAP_CONDX": _lib.CFM_TAP_CONDX, "SYLBER_CFM_TAP_GB": _lib.CFM_TAP_GB, "SYLBER_CFM_TAP_XE": _lib.CFM_TAP_XE,
+                     "SYLBER_CFM_TAP_X0": _lib.CFM_TAP_X0}
+    btap = {k: int(v) for k, v in re.findall(r"\b(SYLBER_CFM_BTAP_[A-Z0-9_]+)\s*=\s*(\d+)", dev)}
+    assert btap == {"SYLBER_CFM_BTAP_" + n: getattr(_lib, "CFM_BTAP_" + n)
+                    for n in ("H_ATTN", "QKV", "Q", "K", "VT", "QKVF", "CTX", "X_ATTN", "H_FF", "FF", "G", "X_FF")}
+    assert sorted(btap.values()) == list(range(12)) and sorted(front.values()) == [1, 2, 3, 4]
+    assert re.search(r"#define\s+SYLBER_CFM_TAP\(block,\s*k\)\s+\(16\s*\*\s*\(\(block\)\s*\+\s*1\)\s*\+\s*\(k\)\)", dev)
+    assert _lib.CFM_TAP(0, 0) == 16 and _lib.CFM_TAP(7, 11) == 139
+    for name in ("sylber_cfm_set_tap", "sylber_cfm_tap_floats", "sylber_cfm_tap_floats_packed"):
+        assert name in _lib.DEV_EXPORTS and name not in _lib.EXPORTS
+    assert lib.sylber_cfm_set_tap(None, 1, None, 0) != 0
+    assert lib.sylber_cfm_tap_floats(None, 1, 1, 1) == -1 and lib.sylber_cfm_tap_floats_packed(None, 1, None, 1) == -1
+
+
 def test_no_process_global_tuning_state():
     """tuning overrides are per handle (sylber_set_option) or per call: the old process-global force switches are gone"""
     for f in ("gemm_bf16.hip", "gemm_mxfp8.hip", "attention.hip", "api.hip", "forward.hip", "ops.hip", "ctx.h"):
