@@ -65,6 +65,15 @@ int sylber_cfm_set_tap(sylber_cfm_t h, int32_t stage, float* tap_dev, int64_t ta
 /* floats the tap of `stage` writes for a padded [B, T] call / a packed call of B clips; -1 for an unknown stage or a bad shape */
 int64_t sylber_cfm_tap_floats(sylber_cfm_t h, int32_t stage, int32_t B, int32_t T);
 int64_t sylber_cfm_tap_floats_packed(sylber_cfm_t h, int32_t stage, const int32_t* frames_host, int32_t B);
+/* test aid: the scalar chain behind the segmenter's threshold comparisons, as csrc/segment.hip compiles it (device pointers, launched on
+ * `stream`, not synchronised).  For i < n: pow_dev[i] = the device restatement of glibc powf(x[i], .5f), sqrt_dev[i] = sqrtf(x[i]),
+ * div_dev[i] = x[i] / d[i].  For wave w < nwaves and j < 768: quot_dev[768 w + j] = (c[768 w + j] * cnt[w] + m[768 w + j]) / (cnt[w] + 1),
+ * the greedy scan's merge update through the scan's own function, one wave per group of 768 with its wave-wide choice between the
+ * one-division form and the plain division.  Either part may be empty (n = 0 / nwaves = 0).  tests/test_gpu_segment_edges.py holds
+ * all four to the host bit for bit. */
+int sylber_debug_segment_scalars(const float* x_dev, const float* d_dev, int64_t n, float* pow_dev, float* sqrt_dev, float* div_dev,
+                                 const float* c_dev, const float* m_dev, const int32_t* cnt_dev, int64_t nwaves, float* quot_dev,
+                                 void* stream);
 #ifdef __cplusplus
 }
 #endif

@@ -36,6 +36,11 @@ def _lib():
         lib.sylber_oracle_np_sum.argtypes = [ctypes.c_void_p, ctypes.c_long]
         lib.sylber_oracle_powf_half.restype = ctypes.c_float
         lib.sylber_oracle_powf_half.argtypes = [ctypes.c_float]
+        lib.sylber_oracle_get_segment_trace.restype = ctypes.c_long
+        lib.sylber_oracle_get_segment_trace.argtypes = lib.sylber_oracle_get_segment.argtypes + [
+            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_long, ctypes.POINTER(ctypes.c_long)]
+        lib.sylber_oracle_powf_half_array.restype = None
+        lib.sylber_oracle_powf_half_array.argtypes = [ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p]
         _LIB = lib
     return _LIB
 
@@ -57,6 +62,24 @@ def get_segment(states: np.ndarray, normthreshold: float, mergethreshold: float,
     return out[:n].copy()
 
 
+def get_segment_trace(states: np.ndarray, normthreshold: float, mergethreshold: float):
+    """``get_segment`` and every value it compared with ``mergethreshold``, in order: returns ``(segments, val float32 [n],
+    phase int32 [n], frame int64 [n])`` -- phase 1 = the greedy scan's similarity at ``frame``, phase 2 = the re-merge's centroid
+    similarity at the mid boundary ``frame``."""
+    states = np.ascontiguousarray(states, dtype=np.float32)
+    T, d = states.shape
+    out = np.zeros((max(T, 1), 2), dtype=np.int64)
+    cap = 2 * T + 2
+    val, phase, frame = np.zeros(cap, np.float32), np.zeros(cap, np.int32), np.zeros(cap, np.int64)
+    nt = ctypes.c_long(0)
+    n = _lib().sylber_oracle_get_segment_trace(states.ctypes.data, T, d, np.float32(normthreshold), np.float32(mergethreshold), None,
+                                               out.ctypes.data, val.ctypes.data, phase.ctypes.data, frame.ctypes.data, cap,
+                                               ctypes.byref(nt))
+    assert nt.value <= cap
+    k = nt.value
+    return (out[:n].copy() if n else np.array([])), val[:k].copy(), phase[:k].copy(), frame[:k].copy()
+
+
 def mean_pool(states: np.ndarray, segments: np.ndarray) -> np.ndarray:
     states = np.ascontiguousarray(states, dtype=np.float32)
     if len(segments) == 0:
@@ -71,6 +94,14 @@ def mean_pool(states: np.ndarray, segments: np.ndarray) -> np.ndarray:
 def np_sum(a: np.ndarray) -> np.float32:
     a = np.ascontiguousarray(a, dtype=np.float32)
     return np.float32(_lib().sylber_oracle_np_sum(a.ctypes.data, a.size))
+
+
+def powf_half_array(v: np.ndarray) -> np.ndarray:
+    """libm ``powf(x, .5f)`` of every element (float32 in, float32 out)"""
+    v = np.ascontiguousarray(v, dtype=np.float32)
+    out = np.empty_like(v)
+    _lib().sylber_oracle_powf_half_array(v.ctypes.data, v.size, out.ctypes.data)
+    return out
 
 
 def powf_half(v: float) -> np.float32:

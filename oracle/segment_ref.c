@@ -83,12 +83,24 @@ static void mean_rows(const float *states, long d, long s, long e, float *out)
     for (long j = 0; j < d; j++) out[j] = out[j] / n;
 }
 
-/*
- * segments_out: capacity T rows of [start,end); returns the number of segments.
- * norms_in may be NULL (computed as sqrt(sum(states**2)+1e-8), segment_utils.py:74-75).
- */
-long sylber_oracle_get_segment(const float *states, long T, long d, float norm_thr, float merge_thr,
-                               const float *norms_in, int64_t *segments_out)
+/* every value compared with merge_thr, in the order the comparisons happen (sylber_oracle_get_segment_trace); NULL = not recorded */
+typedef struct {
+    float *val;      /* the similarity */
+    int32_t *phase;  /* 1 = greedy scan (frame vs running centroid), 2 = re-merge (centroid vs centroid) */
+    int64_t *frame;  /* phase 1: the frame; phase 2: the mid boundary between the two segments */
+    long cap, n;     /* n counts every decision, also those beyond cap */
+} seg_trace;
+
+static void trace_put(seg_trace *tr, float v, int phase, long frame)
+{
+    if (!tr) return;
+    if (tr->n < tr->cap) { tr->val[tr->n] = v; tr->phase[tr->n] = phase; tr->frame[tr->n] = frame; }
+    tr->n++;
+}
+
+/* the one body behind sylber_oracle_get_segment and sylber_oracle_get_segment_trace */
+static long get_segment_impl(const float *states, long T, long d, float norm_thr, float merge_thr,
+                             const float *norms_in, int64_t *segments_out, seg_trace *tr)
 {
     float *tmp = (float *)malloc(sizeof(float) * (size_t)(d > T ? d : T + 1));
     float *curr = (float *)malloc(sizeof(float) * (size_t)d);
@@ -118,6 +130,7 @@ long sylber_oracle_get_segment(const float *states, long T, long d, float norm_t
             s = i;
         } else {
             float sim = cossim_scalar(curr, st, d, tmp);
+            trace_put(tr, sim, 1, i);
             if (sim >= merge_thr) {
                 float c = (float)seg_cnt, c1 = (float)(seg_cnt + 1);
                 for (long j = 0; j < d; j++) curr[j] = (curr[j] * c + st[j]) / c1;
@@ -141,7 +154,9 @@ long sylber_oracle_get_segment(const float *states, long T, long d, float norm_t
         long b0 = seg[2 * (si + 1)], b1 = seg[2 * (si + 1) + 1];
         mean_rows(states, d, a0, a1, ca);
         mean_rows(states, d, b0, b1, cb);
-        if (cossim_scalar(ca, cb, d, tmp) >= merge_thr) {
+        float sim_ab = cossim_scalar(ca, cb, d, tmp);
+        trace_put(tr, sim_ab, 2, bd);
+        if (sim_ab >= merge_thr) {
             seg[2 * (si + 1)] = a0;
             merged[si] = 1;
             continue;
@@ -179,6 +194,28 @@ long sylber_oracle_get_segment(const float *states, long T, long d, float norm_t
     return n;
 }
 
+/*
+ * segments_out: capacity T rows of [start,end); returns the number of segments.
+ * norms_in may be NULL (computed as sqrt(sum(states**2)+1e-8), segment_utils.py:74-75).
+ */
+long sylber_oracle_get_segment(const float *states, long T, long d, float norm_thr, float merge_thr,
+                               const float *norms_in, int64_t *segments_out)
+{
+    return get_segment_impl(states, T, d, norm_thr, merge_thr, norms_in, segments_out, NULL);
+}
+
+/* the same call, and every value it compared with merge_thr: val / phase / frame hold the first trace_cap decisions in order
+ * (a call makes fewer than 2 T), *ntrace = how many there were */
+long sylber_oracle_get_segment_trace(const float *states, long T, long d, float norm_thr, float merge_thr,
+                                     const float *norms_in, int64_t *segments_out, float *val, int32_t *phase,
+                                     int64_t *frame, long trace_cap, long *ntrace)
+{
+    seg_trace tr = { val, phase, frame, trace_cap, 0 };
+    long n = get_segment_impl(states, T, d, norm_thr, merge_thr, norms_in, segments_out, &tr);
+    *ntrace = tr.n;
+    return n;
+}
+
 /* segment mean-pool, sylber/model/sylber.py:133 */
 void sylber_oracle_mean_pool(const float *states, long d, const int64_t *segments, long nseg, float *out)
 {
@@ -188,3 +225,7 @@ void sylber_oracle_mean_pool(const float *states, long d, const int64_t *segment
 /* exposed for unit tests of the summation order */
 float sylber_oracle_np_sum(const float *a, long n) { return np_sum(a, n); }
 float sylber_oracle_powf_half(float v) { return powf(v, 0.5f); }
+void sylber_oracle_powf_half_array(const float *v, long n, float *out)
+{
+    for (long i = 0; i < n; i++) out[i] = powf(v[i], 0.5f);
+}

@@ -252,6 +252,8 @@ DEV_EXPORTS = {
     "sylber_cfm_set_tap": (c_int, [c_void_p, c_int32, c_void_p, c_int64]),
     "sylber_cfm_tap_floats": (c_int64, [c_void_p, c_int32, c_int32, c_int32]),
     "sylber_cfm_tap_floats_packed": (c_int64, [c_void_p, c_int32, POINTER(c_int32), c_int32]),
+    "sylber_debug_segment_scalars": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64,
+                                             c_void_p, c_void_p]),
 }
 # taps inside the resynthesis decoder (include/sylber_hip_dev.h SYLBER_CFM_TAP_* / SYLBER_CFM_BTAP_*): the front stages, and launch k of block li
 CFM_TAP_CONDX, CFM_TAP_GB, CFM_TAP_XE, CFM_TAP_X0 = 1, 2, 3, 4

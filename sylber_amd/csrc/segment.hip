@@ -113,6 +113,37 @@ __device__ __forceinline__ void mean_rows(const float* __restrict__ states, int 
     for (int j = 0; j < ND; ++j) dst[id + NT * j] = a[j] / n;
 }
 
+// The greedy scan's merge update, per lane over its twelve elements: c <- (c * n + x) / (n + 1), n = seg_cnt frames merged so far
+// (segment_utils.py:99).  Twelve IEEE divisions by the same small integer per frame are ~140 of the ~250 instructions of a merge step.
+// Same quotients, bit for bit, from ONE division: r = RN(1 / c1) (IEEE), q0 = a r, then two residual corrections
+// q <- fma(fma(-q, c1, a), r, q) (Markstein: with r correctly rounded and q faithful, the corrected quotient is RN(a / c1)).
+// The identity is checked on the CPU by tests/merge_quotient_check.c (tests/test_powf_replica.py: every divisor 2..8192 and every 7th
+// up to 20000, dividends across all binades of [2^-100, 2^126]) and on the device, through this function, by tests/test_gpu_segment_edges.py
+// (sylber_debug_segment_scalars).  Dividends that are zero, below 2^-100 (inexact residuals) or non-finite take the division; the
+// choice is made by a WAVE-WIDE ballot, so all 64 lanes (all 768 dimensions) of a frame go the same way.  Must be called by whole waves.
+__device__ __forceinline__ void merge_update(float (&c)[12], const float (&x)[12], int seg_cnt) {
+    const float cf = (float)seg_cnt, c1 = (float)(seg_cnt + 1);
+    const float r = 1.0f / c1;
+    float a[12];
+    float amin = INFINITY, amax = 0.f;
+#pragma unroll
+    for (int k = 0; k < 12; ++k) {
+        a[k] = c[k] * cf + x[k];
+        amin = fminf(amin, fabsf(a[k])); amax = fmaxf(amax, fabsf(a[k]));
+    }
+    if (__builtin_amdgcn_ballot_w64(!(amin >= 0x1p-100f) || !(amax <= 0x1p126f))) {
+#pragma unroll
+        for (int k = 0; k < 12; ++k) c[k] = a[k] / c1;
+    } else {
+#pragma unroll
+        for (int k = 0; k < 12; ++k) {
+            const float q0 = a[k] * r;
+            const float q1 = fmaf(fmaf(-q0, c1, a[k]), r, q0);
+            c[k] = fmaf(fmaf(-q1, c1, a[k]), r, q1);
+        }
+    }
+}
+
 // GS = false: all bookkeeping lives in LDS (dynamic, sized by T): the refinement loop is a chain of dependent reads of
 // the segment table, which from global memory cost an L2 round trip per step.  That fits T <= 3940 frames (78.8 s of
 // audio) in the 160 KiB of a CU.  GS = true (longer utterances; the reference's get_segment has no length limit): the
@@ -202,32 +233,7 @@ __global__ __launch_bounds__(256) void segment_kernel(const float* __restrict__ 
                     else if (est < merge_thr - 1e-4f) merge = false;
                     else merge = (dot / powf_half_glibc(cc) / npw[i]) >= merge_thr;   // also taken for NaN
                     if (merge) {
-                        // c = (c * n + x) / (n + 1), twelve IEEE divisions by the same small integer per frame: ~140 of
-                        // the ~250 instructions of a merge step.  Same quotients, bit for bit, from ONE division:
-                        // r = RN(1 / c1) (IEEE), q0 = a r, then two residual corrections q <- fma(fma(-q, c1, a), r, q)
-                        // (Markstein: with r correctly rounded and q faithful, the corrected quotient is RN(a / c1);
-                        // checked against a / c1 for every divisor <= 8192 x 3.2e8 dividends on the CPU, 0 mismatches).
-                        // Dividends that are zero, below 2^-100 (inexact residuals) or non-finite take the division.
-                        const float cf = (float)seg_cnt, c1 = (float)(seg_cnt + 1);
-                        const float r = 1.0f / c1;
-                        float a[12];
-                        float amin = INFINITY, amax = 0.f;
-#pragma unroll
-                        for (int k = 0; k < 12; ++k) {
-                            a[k] = c[k] * cf + x[k];
-                            amin = fminf(amin, fabsf(a[k])); amax = fmaxf(amax, fabsf(a[k]));
-                        }
-                        if (__builtin_amdgcn_ballot_w64(!(amin >= 0x1p-100f) || !(amax <= 0x1p126f))) {
-#pragma unroll
-                            for (int k = 0; k < 12; ++k) c[k] = a[k] / c1;
-                        } else {
-#pragma unroll
-                            for (int k = 0; k < 12; ++k) {
-                                const float q0 = a[k] * r;
-                                const float q1 = fmaf(fmaf(-q0, c1, a[k]), r, q0);
-                                c[k] = fmaf(fmaf(-q1, c1, a[k]), r, q1);
-                            }
-                        }
+                        merge_update(c, x, seg_cnt);           // c = (c * n + x) / (n + 1): one division + two FMA corrections per element
                         seg_cnt += 1;
                     } else {
 #pragma unroll
@@ -509,26 +515,7 @@ __global__ __launch_bounds__(256) void segment_runs_kernel(const float* __restri
                         else if (est < merge_thr - 1e-4f) merge = false;
                         else merge = (dot / powf_half_glibc(cc) / npw[i - base]) >= merge_thr;   // also taken for NaN
                         if (merge) {
-                            const float cf = (float)seg_cnt, c1 = (float)(seg_cnt + 1);
-                            const float r = 1.0f / c1;
-                            float a[12];
-                            float amin = INFINITY, amax = 0.f;
-#pragma unroll
-                            for (int k = 0; k < 12; ++k) {
-                                a[k] = c[k] * cf + x[k];
-                                amin = fminf(amin, fabsf(a[k])); amax = fmaxf(amax, fabsf(a[k]));
-                            }
-                            if (__builtin_amdgcn_ballot_w64(!(amin >= 0x1p-100f) || !(amax <= 0x1p126f))) {
-#pragma unroll
-                                for (int k = 0; k < 12; ++k) c[k] = a[k] / c1;
-                            } else {
-#pragma unroll
-                                for (int k = 0; k < 12; ++k) {
-                                    const float q0 = a[k] * r;
-                                    const float q1 = fmaf(fmaf(-q0, c1, a[k]), r, q0);
-                                    c[k] = fmaf(fmaf(-q1, c1, a[k]), r, q1);
-                                }
-                            }
+                            merge_update(c, x, seg_cnt);
                             seg_cnt += 1;
                         } else {
 #pragma unroll
@@ -711,6 +698,56 @@ int launch_segment(const float* hidden, int B, int T, int D, float norm_thr, flo
         if (!scratch) { syl_set_error("launch_segment", "utterances beyond 3940 frames need the global scratch slab"); return 1; }
         hipLaunchKernelGGL(segment_kernel<true>, dim3(B), dim3(256), (2 * SEG_D + 8) * 4, s, hidden, T, norm_thr, merge_thr, seg, nseg, feat,
                            scratch, segment_slab_floats(T));
+    }
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// ================================================================================================================================
+// Development aid (include/sylber_hip_dev.h sylber_debug_segment_scalars): the scalar chain behind every `>=` of this file, evaluated by
+// the code THIS translation unit compiles (its flags: no contraction, IEEE divide and square root), for arrays of inputs.
+// tests/test_gpu_segment_edges.py compares each bit for bit with the host (libm powf, numpy float32).
+__global__ __launch_bounds__(256) void segment_scalars_kernel(const float* __restrict__ x, const float* __restrict__ d, long n,
+                                                              float* __restrict__ pow_out, float* __restrict__ sqrt_out, float* __restrict__ div_out) {
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
+        const float v = x[i];
+        pow_out[i] = powf_half_glibc(v);
+        sqrt_out[i] = sqrtf(v);
+        div_out[i] = v / d[i];
+    }
+}
+// one wave per group of 768 (c, x) pairs with one count, laid out as the scan holds a frame: lane l owns elements l + 64 k, k = 0..11, of its
+// group.  Whole waves only (merge_update ballots); nwaves need not fill the last workgroup: a wave past the end leaves as a whole.
+__global__ __launch_bounds__(256) void segment_merge_quot_kernel(const float* __restrict__ c_in, const float* __restrict__ x_in,
+                                                                 const int* __restrict__ cnt, long nwaves, float* __restrict__ out) {
+    const int lane = threadIdx.x & 63;
+    for (long w = (long)blockIdx.x * 4 + (threadIdx.x >> 6); w < nwaves; w += (long)gridDim.x * 4) {
+        float c[12], x[12];
+        const size_t base = (size_t)w * SEG_D + lane;
+#pragma unroll
+        for (int k = 0; k < 12; ++k) { c[k] = c_in[base + 64 * k]; x[k] = x_in[base + 64 * k]; }
+        merge_update(c, x, __builtin_amdgcn_readfirstlane(cnt[w]));
+#pragma unroll
+        for (int k = 0; k < 12; ++k) out[base + 64 * k] = c[k];
+    }
+}
+
+extern "C" int sylber_debug_segment_scalars(const float* x_dev, const float* d_dev, int64_t n, float* pow_dev, float* sqrt_dev, float* div_dev,
+                                            const float* c_dev, const float* m_dev, const int32_t* cnt_dev, int64_t nwaves, float* quot_dev,
+                                            void* stream) {
+    if (n < 0 || nwaves < 0) { syl_set_error("sylber_debug_segment_scalars", "negative count"); return 1; }
+    if (n > 0 && (!x_dev || !d_dev || !pow_dev || !sqrt_dev || !div_dev)) { syl_set_error("sylber_debug_segment_scalars", "null array (n > 0)"); return 1; }
+    if (nwaves > 0 && (!c_dev || !m_dev || !cnt_dev || !quot_dev)) { syl_set_error("sylber_debug_segment_scalars", "null array (nwaves > 0)"); return 1; }
+    hipStream_t s = (hipStream_t)stream;
+    if (n > 0) {
+        const long blocks = (n + 255) / 256;
+        hipLaunchKernelGGL(segment_scalars_kernel, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, s, x_dev, d_dev, (long)n, pow_dev,
+                           sqrt_dev, div_dev);
+    }
+    if (nwaves > 0) {
+        const long blocks = (nwaves + 3) / 4;
+        hipLaunchKernelGGL(segment_merge_quot_kernel, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, s, c_dev, m_dev, cnt_dev,
+                           (long)nwaves, quot_dev);
     }
     HIP_TRY(hipGetLastError());
     return 0;

@@ -74,6 +74,28 @@ def test_decoder_taps_are_declared_on_both_sides(lib):
     assert lib.sylber_cfm_tap_floats(None, 1, 1, 1) == -1 and lib.sylber_cfm_tap_floats_packed(None, 1, None, 1) == -1
 
 
+def test_segment_scalars_aid_is_declared_on_both_sides(lib):
+    """sylber_debug_segment_scalars (the segmenter's scalar chain for arrays of inputs, tests/test_gpu_segment_edges.py) is a development
+    aid: declared in include/sylber_hip_dev.h with the signature the ctypes binding uses, exported, not part of the drop-in ABI, and its
+    kernels live in segment.hip, the one source built without FMA contraction.  Host-only behaviour: bad counts and null arrays are refused
+    before any launch."""
+    from sylber_amd import _lib, build
+    dev = open(os.path.join(ROOT, "include", "sylber_hip_dev.h")).read()
+    m = re.search(r"int\s+sylber_debug_segment_scalars\s*\(([^)]*)\)", dev)
+    assert m and [re.sub(r"\s+", " ", a.strip()) for a in m.group(1).split(",")] == [
+        "const float* x_dev", "const float* d_dev", "int64_t n", "float* pow_dev", "float* sqrt_dev", "float* div_dev", "const float* c_dev",
+        "const float* m_dev", "const int32_t* cnt_dev", "int64_t nwaves", "float* quot_dev", "void* stream"]
+    assert "sylber_debug_segment_scalars" in _lib.DEV_EXPORTS and "sylber_debug_segment_scalars" not in _lib.EXPORTS
+    assert len(_lib.DEV_EXPORTS["sylber_debug_segment_scalars"][1]) == 12 and hasattr(lib, "sylber_debug_segment_scalars")
+    seg = open(os.path.join(ROOT, "sylber_amd", "csrc", "segment.hip")).read()
+    assert 'extern "C" int sylber_debug_segment_scalars' in seg and build.EXTRA["segment.hip"] == ["-ffp-contract=off"]
+    assert seg.count("merge_update(c, x, ") == 3              # the two scans and the aid run ONE merge update
+    none = [None] * 3
+    assert lib.sylber_debug_segment_scalars(None, None, -1, *none, *none, 0, None, None) != 0
+    assert lib.sylber_debug_segment_scalars(None, None, 5, *none, *none, 0, None, None) != 0
+    assert lib.sylber_debug_segment_scalars(None, None, 0, *none, *none, 3, None, None) != 0
+
+
 def test_no_process_global_tuning_state():
     """tuning overrides are per handle (sylber_set_option) or per call: the old process-global force switches are gone"""
     for f in ("gemm_bf16.hip", "gemm_mxfp8.hip", "attention.hip", "api.hip", "forward.hip", "ops.hip", "ctx.h"):
