@@ -21,15 +21,15 @@
 // LDS: 4 KiB of ring at WP = 8 and 0.5 KiB of pairing, 64 threads: wave slots bound the occupancy.
 #include "kernels.h"
 #include "../../include/sylber_hip.h"
+#include "unit_strip.h"                                   // the ring and the mismatch count
 #include <climits>
 
 constexpr int UA_CH = 32;                                 // steps of a chunk: their 2-bit codes fill one 64-bit word (units.py: ALIGN_CHUNK_COLS)
-constexpr int UA_RING = 128;                              // columns of the ring: a step reads back 63 columns, a chunk is staged 32 ahead
 constexpr int UA_MAX_COLS = 65536, UA_MAX_M = 64, UA_MAX_W = 8;
 constexpr unsigned UA_DIAG = 0, UA_UP = 1, UA_LEFT = 2;
 
 static_assert(2 * UA_CH == 64, "the 2-bit codes of a lane's chunk fill one 64-bit word");
-static_assert(UA_RING >= UA_MAX_M - 1 + 2 * UA_CH && (UA_RING & (UA_RING - 1)) == 0, "the ring holds a chunk's columns, the 63 behind them and the next chunk");
+static_assert(UST_RING >= UA_MAX_M - 1 + 2 * UA_CH, "the ring holds a chunk's columns, the 63 behind them and the next chunk");
 
 // the chunks of a window of `cols` columns against a phrase of up to 64 units: L + m - 1 <= cols + 63 steps
 __host__ __device__ static inline int64_t ua_chunks(int64_t cols) { return (cols + UA_MAX_M - 1 + UA_CH - 1) / UA_CH; }
@@ -53,7 +53,7 @@ __global__ __launch_bounds__(64) void unit_align_kernel(const int32_t* __restric
                                                         int free_start, int32_t* __restrict__ cols, int32_t* __restrict__ subs,
                                                         int32_t* __restrict__ ops, int32_t* __restrict__ cost, int32_t* __restrict__ tstart,
                                                         uint64_t* ws) {
-    __shared__ __attribute__((aligned(16))) int ring[UA_RING * WP];      // [column % 128][WP] ids of the window's columns
+    __shared__ __attribute__((aligned(16))) int ring[UST_RING * WP];      // [column % 128][WP] ids of the window's columns
     __shared__ int ocol[UA_MAX_M], osub[UA_MAX_M], oops[4];
     const int lane = threadIdx.x;
     const size_t pair = blockIdx.x;
@@ -87,15 +87,7 @@ __global__ __launch_bounds__(64) void unit_align_kernel(const int32_t* __restric
     int se = (lane + 1) * W, ss = 0, de = lane * W, ds = 0;
     fetch(0);
     for (int chunk = 0; chunk < nchunks; ++chunk) {
-        if (lane < UA_CH) {
-            int* dst = ring + ((chunk * UA_CH + lane) & (UA_RING - 1)) * WP;
-            if constexpr (WP == 1) dst[0] = xr[0];
-            else if constexpr (WP == 2) *(int2*)dst = make_int2(xr[0], xr[1]);
-            else {
-#pragma unroll
-                for (int c = 0; c < WP; c += 4) *(int4*)(dst + c) = make_int4(xr[c], xr[c + 1], xr[c + 2], xr[c + 3]);
-            }
-        }
+        if (lane < UA_CH) ust_ring_store<WP>(ring, chunk * UA_CH + lane, xr);
         __syncthreads();                                   // one wave: its LDS accesses stay in order, the barrier makes the writes visible
         fetch(chunk + 1);
         uint64_t codes = 0;
@@ -104,20 +96,9 @@ __global__ __launch_bounds__(64) void unit_align_kernel(const int32_t* __restric
             int ue = __shfl_up(se, 1), us = __shfl_up(ss, 1);      // the cell [i-1][j] where this lane works on column j
             const int j = st0 + s - lane;
             if (valid && (unsigned)j < (unsigned)L) {
-                const int* src = ring + (j & (UA_RING - 1)) * WP;
                 int t[WP];
-                if constexpr (WP == 1) t[0] = src[0];
-                else if constexpr (WP == 2) { const int2 v = *(const int2*)src; t[0] = v.x; t[1] = v.y; }
-                else {
-#pragma unroll
-                    for (int c = 0; c < WP; c += 4) {
-                        const int4 v = *(const int4*)(src + c);
-                        t[c] = v.x; t[c + 1] = v.y; t[c + 2] = v.z; t[c + 3] = v.w;
-                    }
-                }
-                int sub = 0;
-#pragma unroll
-                for (int c = 0; c < WP; ++c) sub += pu[c] != t[c] ? 1 : 0;
+                ust_ring_load<WP>(ring, j, t);
+                const int sub = ust_mismatches<WP>(pu, t);
                 if (first) { ue = fs ? 0 : (j + 1) * W; us = fs ? j + 1 : 0; }      // row -1
                 int best = de + sub, bs = ds;
                 unsigned code = UA_DIAG;

@@ -30,9 +30,9 @@ from .search import ALIGN_WORKSPACE_BYTES, _align_spans       # the span checks 
 TILE_COLS = 256                 # US_TILE of csrc/unit_search.hip: the columns a workgroup stages at a time
 ALIGN_CHUNK_COLS = 32           # UA_CH of csrc/unit_align.hip: the anti-diagonal steps whose 2-bit codes fill one 64-bit word
 MAX_WIDTH = 8                   # US_MAX_W: ids per unit
-STRING_ROWS = 64                # UT_ROWS of csrc/unit_strings.hip: the reference rows of a strip
-MAX_STRING_UNITS = 65536        # UT_MAX_LEN: the units of one string of align_unit_strings
-MAX_LOCAL_PARAM = 64            # UL_MAX_PARAM of csrc/unit_local.h: match, mismatch and gap of a local alignment
+STRING_ROWS = 64                # UST_ROWS of csrc/unit_strip.h: the reference rows of a strip
+MAX_STRING_UNITS = 65536        # UST_MAX_LEN: the units of one string of align_unit_strings
+MAX_LOCAL_PARAM = 64            # UST_MAX_PARAM: match, mismatch and gap of a local alignment
 MAX_BEST = 32                   # ULA_MAX_BEST of csrc/unit_repeats_all.hip: the repeats of one pair
 REPEAT_PAIRS = 1 << 16          # the pairs of sequences that find_repeats enumerates on the host at a time
 FORMAT = "sylber_amd.UnitIndex/1"
