@@ -834,6 +834,51 @@ int sylber_dtw_strings_align(const float* x_dev, int32_t x_rows, const float* x_
                              int32_t* rows_dev /* [*, 2], with path */, int32_t* steps_dev, float* cost_dev,
                              int32_t* steps_walk_dev /* nullable */, void* workspace_dev, void* stream);
 
+/* Embedding strings, local (sylber_amd/search.py: local_align_sequences / SyllableIndex.local_align_sequences;
+ * csrc/dtw_strings_local.hip; restated in tests/dtw_strings_local_ref.py): every repeat between two WHOLE embedding sequences --
+ * the best sub-span of x against the best sub-span of y, up to n_best of them per pair, and with a band below the diagonal the
+ * repeats inside ONE sequence.  "Embedding repeats" without the 64-row limit of a probe; what "Unit repeats, every one" is to
+ * unit ids.  A pair is x of m rows and y of L rows, 0 <= m, L <= 65 536; D is a multiple of 16 and at least 16; d[i][j] is the
+ * local cost of "Embedding strings" (sylber_dtw_search's, word for word; a NaN d counts as +inf).  radius > 0, gap >= 0 and
+ * min_score > 0 are finite fp32; n_best = R, 1 <= R <= 32; per pair sep >= 0.
+ *   Rounds r = 0 .. R-1 run in order; round r is the "Embedding repeats" recurrence unchanged, everything in fp32 with one rounding
+ *   per operation:
+ *     s = radius - d[i][j], sg = s - gap, H[i][-1] = H[-1][j] = 0
+ *     c_diag = H[i-1][j-1] + s     start: start[i-1][j-1] if H[i-1][j-1] > 0 else (i, j)
+ *     c_up   = H[i-1][j]   + sg    start: start[i-1][j]
+ *     c_left = H[i][j-1]   + sg    start: start[i][j-1]
+ *     v = the first largest of (c_diag, c_up, c_left) in that order; H[i][j] = v if v > 0 else 0
+ *   Blocked cells, the one addition, from "Unit repeats, every one".  A blocked cell has H = 0, carries no start and is never the
+ *   best cell.  (i, j) is blocked when sep > 0 and j - i < sep, or when a0 <= i < a1 and b0 <= j < b1 for the spans of an earlier
+ *   round.  Rectangles of different rounds may intersect as rectangles; no cell of a round's path lies in an earlier rectangle.
+ *   Result of a round: the best unblocked cell -- the largest H, then the smallest i, then the smallest j -- with score = H[i][j]
+ *   and the spans [si, i + 1) of x and [sj, j + 1) of y, (si, sj) = start[i][j], positions INSIDE the two windows.  A round
+ *   without a positive cell or with score < min_score ends the pair: it and every later round are score 0, spans -1.  An empty
+ *   side gives padding only.  So: round 0 with sep = 0 is the "Embedding repeats" result of x as a probe of any length against y
+ *   as one sequence, bit for bit, wherever its score reaches min_score; scores never increase from round to round.
+ *   With sep > 0 the two spans of a repeat may overlap, as in tandem repetition; a1 <= b0 is the caller's filter.
+ *   Nothing returned depends on what the workspace held, on which pairs share a call or on their order.
+ *   Not built: blocking the cells of a path instead of its rectangle; one pair split across workgroups; the 16-bit and PQ forms.
+ * sylber_dtw_strings_local: buffers, norms, metric and windows as for sylber_dtw_strings_align; x and y may be one buffer and the
+ *   windows of a pair the same window (a sequence against itself, with sep >= 1).  sep_host [n_pairs] int32 may be null: all 0.
+ *   The windows and sep_host are read before the call returns, everything else is enqueued on `stream`: ONE launch runs all the
+ *   rounds of every pair, one 256-thread workgroup per pair; each round repeats the contraction, the costs are not kept.
+ *   scores_dev fp32 [n_pairs, n_best]; spans_dev int32 [n_pairs, n_best, 4] = (a0, a1, b0, b1).
+ *   workspace_dev: sylber_dtw_strings_local_workspace_bytes of the same windows, host arithmetic on the lengths (-1 on a bad
+ *   argument), every term rounded up to 256 B; it does not grow with n_best:
+ *       64 B per pair of table
+ *     + 16 L per pair with m > 128 and L > 0: two alternating rows of (H, start), 8 B per column, between super-strips of 128 rows
+ *       of x, at most 1 MiB; every round uses them again.
+ *   What sylber_dtw_strings_align refuses of its buffers, norms, D, metric, n_pairs and windows, a radius, gap or min_score that
+ *   is not finite or not > 0 (gap: >= 0), n_best outside 1..32 and a negative sep return 1 with sylber_last_error before any
+ *   device call. */
+int64_t sylber_dtw_strings_local_workspace_bytes(const int32_t* x_win_host, const int32_t* y_win_host, int32_t n_pairs);
+int sylber_dtw_strings_local(const float* x_dev, int32_t x_rows, const float* x_norm_dev, const float* y_dev, int32_t y_rows,
+                             const float* y_norm_dev, int32_t D, int32_t metric, const int32_t* x_win_host, const int32_t* y_win_host,
+                             const int32_t* sep_host /* nullable: all 0 */, int32_t n_pairs, float radius, float gap, float min_score,
+                             int32_t n_best, float* scores_dev /* [n_pairs, n_best] */, int32_t* spans_dev /* [n_pairs, n_best, 4] */,
+                             void* workspace_dev, void* stream);
+
 /* The exact DTW on a coded database (sylber_amd/pq.py: IVFPQSyllableIndex.search_phrases / search_occurrences / align_phrases with
  * rerank=False; restated in tests/ivfpq_phrase_ref.py): sylber_dtw_rerank and sylber_dtw_align with db_dev replaced by
  * product-quantization codes that may lie in another order than the row ids and may be codes of residuals to a list centroid.  No row is materialised: the kernels rebuild

@@ -27,6 +27,8 @@ windows of the index's own sequences -- against every sequence, in the same epil
 tests/repeats_ref.py).
 ``align_sequences`` / ``SyllableIndex.align_sequences`` align two WHOLE sequences of any length, the global DTW with its path
 (csrc/dtw_strings.hip, ``sylber_dtw_strings_align``; tests/dtw_strings_ref.py).
+``local_align_sequences`` / ``SyllableIndex.local_align_sequences`` are its LOCAL form: every repeat between two whole sequences,
+or inside one (csrc/dtw_strings_local.hip, ``sylber_dtw_strings_local``; tests/dtw_strings_local_ref.py).
 
 The rules that every index shares -- argument checks, row preparation, result buffers, provenance, the list layout, the arrays of a
 saved file -- are in _index.py, each once; this file and pq.py hold what differs between the indexes.
@@ -229,6 +231,18 @@ def _check_sequence_pairs(ml: np.ndarray, Ll: np.ndarray, path: bool, pair_chunk
     return need
 
 
+def _launch_cuts(S: int, need: np.ndarray, pair_chunk) -> List[Tuple[int, int]]:
+    """the launches of S > 0 pairs as ``(first pair, one past the last)``: ``pair_chunk`` pairs each, or as many as keep the workspace
+    (``need`` bytes per pair) below ``ALIGN_WORKSPACE_BYTES``"""
+    if pair_chunk is not None:
+        cuts = list(range(0, S, int(pair_chunk))) + [S]
+    else:
+        cuts, acc = [0], np.concatenate([[0], np.cumsum(need)])
+        while cuts[-1] < S:
+            cuts.append(max(cuts[-1] + 1, int(np.searchsorted(acc, acc[cuts[-1]] + ALIGN_WORKSPACE_BYTES - 256, side="right")) - 1))
+    return list(zip(cuts[:-1], cuts[1:]))
+
+
 def _align_windows(xd, xn, yd, yn, D: int, metric: str, xw: np.ndarray, yw: np.ndarray, need: np.ndarray, path: bool, pair_chunk, fill,
                    dev, _steps_walk: bool = False):
     """``sylber_dtw_strings_align`` on the pairs of windows ``xw, yw`` int32 ``[S, 2]`` = (first row, rows) into the prepared rows
@@ -241,16 +255,9 @@ def _align_windows(xd, xn, yd, yn, D: int, metric: str, xw: np.ndarray, yw: np.n
     walk = torch.empty((S,), dtype=torch.int32, device=dev) if _steps_walk and path else None
     rows = torch.empty((max(int(xo[-1]), 1), 2), dtype=torch.int32, device=dev) if path else None
     if S:
-        # the launches: pair_chunk pairs each, or as many as keep the workspace below ALIGN_WORKSPACE_BYTES
-        if pair_chunk is not None:
-            cuts = list(range(0, S, int(pair_chunk))) + [S]
-        else:
-            cuts, acc = [0], np.concatenate([[0], np.cumsum(need)])
-            while cuts[-1] < S:
-                cuts.append(max(cuts[-1] + 1, int(np.searchsorted(acc, acc[cuts[-1]] + ALIGN_WORKSPACE_BYTES - 256, side="right")) - 1))
         lib = _lib.load()
         groups = []
-        for g0, g1 in zip(cuts[:-1], cuts[1:]):
+        for g0, g1 in _launch_cuts(S, need, pair_chunk):
             x32, y32 = np.ascontiguousarray(xw[g0:g1], np.int32), np.ascontiguousarray(yw[g0:g1], np.int32)
             size = int(lib.sylber_dtw_strings_workspace_bytes(x32.ctypes.data_as(_i32p), y32.ctypes.data_as(_i32p), g1 - g0, int(path)))
             if size < 0:
@@ -361,6 +368,116 @@ def align_sequences(xs, ys, *, metric: str = "l2", path: bool = False, device="c
     rows, costs, steps, xo = out[:4]
     res = (rows.to(torch.int64), costs, steps, torch.from_numpy(xo).to(dev)) if path else (costs, steps)
     return res + tuple(out[4:])
+
+
+# ---- whole sequences, local: what local_align_sequences and SyllableIndex.local_align_sequences share -----------------------------
+MAX_LOCAL_BEST = 32             # DSL_MAX_BEST of csrc/dtw_strings_local.hip: the rounds of a pair
+
+
+def _local_rounds(n_best, min_sep) -> Tuple[int, int]:
+    """``(n_best, min_sep)`` as ints, or ``ValueError``"""
+    for name, v in (("n_best", n_best), ("min_sep", min_sep)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise ValueError("%s must be an integer, got %r" % (name, v))
+    if not 1 <= int(n_best) <= MAX_LOCAL_BEST:
+        raise ValueError("need 1 <= n_best <= %d, got %d" % (MAX_LOCAL_BEST, int(n_best)))
+    if not 1 <= int(min_sep) < 2 ** 31:
+        raise ValueError("need min_sep >= 1, got %d" % int(min_sep))
+    return int(n_best), int(min_sep)
+
+
+def _local_align_windows(xd, xn, yd, yn, D: int, metric: str, xw: np.ndarray, yw: np.ndarray, sep: np.ndarray, need: np.ndarray, local,
+                         n_best: int, pair_chunk, fill, dev):
+    """``sylber_dtw_strings_local`` on the pairs of windows ``xw, yw`` int32 ``[S, 2]`` = (first row, rows) with ``sep`` int32 ``[S]``
+    into the prepared rows ``xd, yd`` with norms ``xn, yn`` (``None`` under cosine), behind every check -> ``(scores fp32 [S, n_best],
+    spans int32 [S, n_best, 4])``; the launches are grouped as ``_align_windows`` groups them"""
+    S = int(xw.shape[0])
+    scores = torch.empty((S, n_best), dtype=torch.float32, device=dev)
+    spans = torch.empty((S, n_best, 4), dtype=torch.int32, device=dev)
+    if S:
+        lib = _lib.load()
+        groups = []
+        for g0, g1 in _launch_cuts(S, need, pair_chunk):
+            x32, y32 = np.ascontiguousarray(xw[g0:g1], np.int32), np.ascontiguousarray(yw[g0:g1], np.int32)
+            size = int(lib.sylber_dtw_strings_local_workspace_bytes(x32.ctypes.data_as(_i32p), y32.ctypes.data_as(_i32p), g1 - g0))
+            if size < 0:
+                raise _lib.SylberHipError("sylber_dtw_strings_local_workspace_bytes refused the call")
+            groups.append((g0, g1, x32, y32, np.ascontiguousarray(sep[g0:g1], np.int32), size))
+        radius, gap, min_score = (float(v) for v in local)
+        with torch.cuda.device(dev):
+            st = _stream(dev)
+            ws = None
+            for g0, g1, x32, y32, s32, size in groups:
+                if ws is None or ws.numel() != size:       # every launch gets exactly what its size function asked for
+                    ws = torch.empty(size, dtype=torch.uint8, device=dev)
+                    if fill is not None:
+                        ws.fill_(fill)
+                _lib.check(lib.sylber_dtw_strings_local(_vp(xd), int(xd.shape[0]), _vp(xn), _vp(yd), int(yd.shape[0]), _vp(yn), D, METRICS[metric],
+                                                        x32.ctypes.data_as(_i32p), y32.ctypes.data_as(_i32p), s32.ctypes.data_as(_i32p), g1 - g0,
+                                                        radius, gap, min_score, n_best, _vp(scores[g0:g1]), _vp(spans[g0:g1]), _vp(ws), st),
+                           "sylber_dtw_strings_local")
+    return scores, spans
+
+
+def local_align_sequences(xs, ys=None, *, radius, gap=None, min_score=None, n_best: int = 1, min_sep: int = 1, metric: str = "l2",
+                          device="cuda", pair_chunk: Optional[int] = None, _workspace_fill=None):
+    """what two whole recordings share, and what one recording says more than once: the LOCAL alignment of whole embedding sequences
+    of any length up to 65 536 rows, pair by pair, up to ``n_best`` repeats per pair (csrc/dtw_strings_local.hip,
+    ``sylber_dtw_strings_local``; contract in include/sylber_hip.h "Embedding strings, local", restated in
+    tests/dtw_strings_local_ref.py).  ``xs`` and ``ys`` are ``align_sequences``'s: equally long lists of ``[m, D]`` float arrays or
+    tensors, prepared exactly as there.  ``ys=None`` aligns every sequence of ``xs`` against ITSELF: cells with ``j - i < min_sep``
+    are blocked, so with ``min_sep >= 1`` a repeat is reported once, above the diagonal, and never as the sequence against itself.
+
+    -> ``(scores fp32 [S, n_best], spans int64 [S, n_best, 2, 2])`` on the device: ``spans[s, r, 0]`` = (first, one past the last)
+    position inside ``xs[s]``, ``spans[s, r, 1]`` the same inside ``ys[s]`` (inside ``xs[s]`` with ``ys=None``).
+
+    The local cost ``d[i][j]`` is ``search_phrases``'s, word for word.  Round ``r = 0 .. n_best - 1`` is ``search_repeats``'s
+    recurrence (``radius``, ``gap``, ``min_score`` and their defaults ``2 * radius`` and ``3 * radius`` as there) with the cells of
+    the band and of the rectangles ``spans[s, :r]`` of the earlier rounds held at ``H = 0``; its result is the best cell left -- the
+    largest ``H``, then the smallest ``i``, then the smallest ``j``.  A round without a positive cell or below ``min_score`` ends
+    the pair: it and the later rounds are score 0 and spans -1, as is every round of a pair with an empty side.  Scores never
+    increase along ``r``; no path cell of a round lies in an earlier rectangle.  Round 0 between two sequences equals
+    ``SyllableIndex.search_repeats`` of ``xs[s]`` as a probe against ``ys[s]`` as the one sequence of an index, bit for bit, where
+    that applies (at most 64 rows); here a side may have 65 536.  With ``ys=None`` the two spans of a repeat may overlap (tandem
+    repetition); ``spans[..., 0, 1] <= spans[..., 1, 0]`` is the caller's filter.
+
+    Nothing depends on ``pair_chunk``, on which pairs share a call, on their order or on stale workspace contents.  A round costs
+    ``m L D`` multiply-adds (about half with ``ys=None``), on the fp32 MFMA, and every round repeats them; a pair needs at most
+    1 MiB of workspace whatever ``n_best`` is.  ``ValueError`` before any allocation or launch: what ``align_sequences`` refuses,
+    what ``search_repeats`` refuses of ``radius``, ``gap`` and ``min_score``, ``n_best`` outside 1 .. 32, ``min_sep < 1``.
+    ``S = 0`` returns empty tensors without a launch.
+
+    Not here: blocking the cells of a path rather than its rectangle; one pair split across workgroups; 16-bit and PQ forms; a
+    scan of all pairs of whole sequences without a query (``find_repeats`` proposes pairs); what radius suits real speech."""
+    if metric not in METRICS:
+        raise ValueError("metric must be 'l2' or 'cosine', got %r" % (metric,))
+    local = _local_scalars(radius, gap, min_score)
+    n_best, min_sep = _local_rounds(n_best, min_sep)
+    xp, ml, Dx = _sequence_rows(xs, "xs")
+    S = int(ml.size)
+    if ys is None:
+        yp, Ll, Dy = xp, ml, Dx
+    else:
+        yp, Ll, Dy = _sequence_rows(ys, "ys")
+        if S != int(Ll.size):
+            raise ValueError("xs and ys must be equally long, got %d and %d sequences" % (S, int(Ll.size)))
+    if Dx is not None and Dy is not None and Dx != Dy:
+        raise ValueError("xs have D = %d, ys have D = %d" % (Dx, Dy))
+    D = Dx or Dy
+    if D is not None and (D < 16 or D % 16):
+        raise ValueError("the feature width D must be a multiple of 16, got %d" % D)
+    need = _check_sequence_pairs(ml, Ll, False, pair_chunk)
+    dev = _device(device)
+    xw = np.stack([np.cumsum(ml) - ml, ml], 1).astype(np.int32).reshape(S, 2)
+    yw = np.stack([np.cumsum(Ll) - Ll, Ll], 1).astype(np.int32).reshape(S, 2)
+    sep = np.full(S, min_sep if ys is None else 0, np.int32)
+    if S == 0:
+        xd = xn = yd = yn = None
+    else:
+        xd, xn = _flat_rows(xp, D, metric, dev)
+        yd, yn = (xd, xn) if ys is None else _flat_rows(yp, D, metric, dev)        # a sequence against itself: both windows in one buffer
+    scores, spans = _local_align_windows(xd, xn, yd, yn, D or 16, metric, xw, yw, sep, need, local, n_best, pair_chunk, _workspace_fill, dev)
+    return scores, spans.to(torch.int64).reshape(S, n_best, 2, 2)
 
 
 class SyllableIndex:
@@ -820,6 +937,44 @@ class SyllableIndex:
         rows = torch.where(rows >= 0, rows + shift[:, None], rows)
         return rows, costs, steps, torch.from_numpy(xo).to(self.device)
 
+    def local_align_sequences(self, pairs, radius, *, gap=None, min_score=None, n_best: int = 1, min_sep: int = 1,
+                              pair_chunk: Optional[int] = None, sequences=None, _workspace_fill=None):
+        """``local_align_sequences`` between stored sequences, with no copy: every repeat between two whole sequences of the index,
+        or inside one.  ``pairs`` int ``[S, 2]`` are sequence numbers as ``align_sequences`` takes them; a pair ``(s, s)`` is the
+        repeats inside ``s``, with the cells ``j - i < min_sep`` blocked, every other pair has no band.  The windows go into the
+        index's own rows with its stored norms, so the result is the free function's on those rows under the index's metric, bit
+        for bit -> ``(scores fp32 [S, n_best], spans int64 [S, n_best, 2, 2])`` where ``spans`` are ROW IDS of the index (first,
+        one past the last; padding stays -1): ``provenance`` and ``align_phrases`` take them.  The pairs that ``find_repeats``
+        returns are pairs for this call: it gives the full extent of a repeat whose window ``find_repeats`` found, with a score
+        that is never smaller.  ``ValueError`` before any launch: an empty index, what ``align_sequences`` refuses of ``pairs``,
+        ``sequences`` and ``pair_chunk``, and what the free function refuses of its scalars."""
+        N = len(self)
+        if N == 0:
+            raise ValueError("the index is empty")
+        local = _local_scalars(radius, gap, min_score)
+        n_best, min_sep = _local_rounds(n_best, min_sep)
+        pr = np.asarray(pairs.detach().cpu().numpy() if torch.is_tensor(pairs) else pairs)
+        if pr.size == 0:
+            pr = pr.reshape(0, 2).astype(np.int64)
+        if pr.ndim != 2 or pr.shape[1] != 2 or pr.dtype.kind not in "iu":
+            raise ValueError("pairs must be integer [S, 2] sequence numbers, got %s %s" % (pr.dtype, pr.shape))
+        off = _sequences(sequences, N, self.sequence_offsets)
+        nseq = off.size - 1
+        pr = pr.astype(np.int64)
+        if pr.size and (pr.min() < 0 or pr.max() >= nseq):
+            raise ValueError("pairs must name sequences in [0, %d)" % nseq)
+        first, length = off[:-1][pr], np.diff(off)[pr]      # [S, 2] each
+        need = _check_sequence_pairs(length[:, 0], length[:, 1], False, pair_chunk)
+        xw = np.stack([first[:, 0], length[:, 0]], 1).astype(np.int32)
+        yw = np.stack([first[:, 1], length[:, 1]], 1).astype(np.int32)
+        sep = np.where(pr[:, 0] == pr[:, 1], min_sep, 0).astype(np.int32)
+        scores, spans = _local_align_windows(self._x, self._c, self._x, self._c, self.dim, self.metric, xw, yw, sep, need, local, n_best,
+                                             pair_chunk, _workspace_fill, self.device)
+        S = int(pr.shape[0])
+        spans = spans.to(torch.int64).reshape(S, n_best, 2, 2)
+        shift = torch.from_numpy(np.ascontiguousarray(first)).to(self.device)[:, None, :, None]
+        return scores, torch.where(spans >= 0, spans + shift, spans)
+
     # ---- repeated phrases ---------------------------------------------------------------------------------------------------------------
     def search_repeats(self, probes, k: int, radius, *, gap=None, min_score=None, lengths=None, groups=None,
                        exclude_same_group: bool = False, sequences=None, splits: int = 0, phrase_chunk: int = DEFAULT_PHRASE_CHUNK,
@@ -890,8 +1045,8 @@ class SyllableIndex:
         many or a ``save`` / ``load`` round trip.  ``ValueError`` before any launch: an empty index, what ``search_repeats``
         refuses, ``window`` / ``hop`` outside ``1 <= hop <= window <= 64``.  Fewer than two sequences: padding only, no launch.
 
-        Not here: more than one repeat per pair of sequences, repeats inside one sequence (cut it with ``sequences=``), the
-        16-bit / PQ / IVF forms, scores normalised by length."""
+        Not here: more than one repeat per pair of sequences and repeats inside one sequence (both: ``local_align_sequences`` on
+        the pairs this returns), the 16-bit / PQ / IVF forms, scores normalised by length."""
         N, dev = len(self), self.device
         if N == 0:
             raise ValueError("the index is empty")
@@ -1294,6 +1449,12 @@ class IVFSyllableIndex:
     def align_sequences(self, pairs, *, path: bool = False, pair_chunk: Optional[int] = None, sequences=None):
         """the global DTW of whole stored sequences: ``ivf.index.align_sequences`` on the rows in id order"""
         return self.index.align_sequences(pairs, path=path, pair_chunk=pair_chunk, sequences=sequences)
+
+    def local_align_sequences(self, pairs, radius, *, gap=None, min_score=None, n_best: int = 1, min_sep: int = 1,
+                              pair_chunk: Optional[int] = None, sequences=None):
+        """every repeat between whole stored sequences: ``ivf.index.local_align_sequences`` on the rows in id order"""
+        return self.index.local_align_sequences(pairs, radius, gap=gap, min_score=min_score, n_best=n_best, min_sep=min_sep,
+                                                pair_chunk=pair_chunk, sequences=sequences)
 
     # ---- persistence ----------------------------------------------------------------------------------------------------------------
     def save(self, path: str) -> None:
