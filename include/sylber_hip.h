@@ -833,8 +833,43 @@ int sylber_dtw_strings_align(const float* x_dev, int32_t x_rows, const float* x_
                              int32_t n_pairs, int32_t path, const int64_t* rows_offset_host /* [n_pairs], with path: x's flat row in rows_dev */,
                              int32_t* rows_dev /* [*, 2], with path */, int32_t* steps_dev, float* cost_dev,
                              int32_t* steps_walk_dev /* nullable */, void* workspace_dev, void* stream);
+/* sylber_dtw_strings_align_split (csrc/dtw_strings_split.hip; the blocked recurrence restated in tests/dtw_strings_split_ref.py):
+ *   sylber_dtw_strings_align with the work of ONE pair spread over many workgroups, for calls that bring few long pairs.  Every
+ *   argument of sylber_dtw_strings_align means what it means there; block_rows and block_cols are the rows of x and the columns
+ *   of y of a block, multiples of 128 up to 65 536, 0 = the library's choice (128 x 128, profiles/dtw_strings_split_bench.md).
+ *   The block recurrence.  With BR = block_rows and BC = block_cols a pair has nbr = ceil(m / BR) bands of rows and
+ *   nbc = ceil(L / BC) chunks of columns; block (b, c) holds the cells of rows [b BR, (b+1) BR) and columns [c BC, (c+1) BC)
+ *   that lie in the matrix.  It computes them by the recurrence above from three inputs: the last row of block (b-1, c), the
+ *   last column of block (b, c-1) and the corner cell (A, n)[b BR - 1][c BC - 1]; outside the matrix they are +inf.  Launch d
+ *   runs every block with b + c = d of every pair of the call, one workgroup per block; a pair needs nbr + nbc - 1 launches and
+ *   one more that writes its outputs, all on `stream`, and stream order is the only order between blocks: no workgroup waits
+ *   for another.  Inside a block the cells are computed by the code of sylber_dtw_strings_align on the same global grid of
+ *   128-column tiles and 64-row strips, the same operations in the same order, so cost, steps, rows and steps_walk are
+ *   BIT FOR BIT sylber_dtw_strings_align's.  Nothing returned depends on the block sizes, on which pairs share a call, on
+ *   their order or on what the workspace held: a block reads only cells that an earlier launch of the same call wrote.
+ *   workspace_dev: sylber_dtw_strings_split_workspace_bytes of the same windows, path and block sizes, host arithmetic on the
+ *   lengths (-1 on a bad argument), every term rounded up to 256 B:
+ *       64 B per pair of table
+ *     + per pair with m, L > 0:
+ *         256 B: the last cell, from the block that holds it to the launch that writes the outputs
+ *       + 16 L where nbr > 1: two boundary rows of (A, n), 8 B per column, alternating by the parity of b
+ *       + 16 L where BR > 128 and m > 128: two rows between a block's own super-strips of 128 rows
+ *       + 16 (m + nbr) where nbc > 1: two boundary columns of (A, n), 8 B per row, alternating by the parity of c, each band's
+ *         cells led by one more: the corner of the block to the right, which travels with the column because the boundary
+ *         row that holds it is rewritten in the launch that would read it
+ *     + with path, the codes of sylber_dtw_strings_align, at the same places.
+ *   Refused with status 1 and sylber_last_error before any device call: everything sylber_dtw_strings_align refuses, and a
+ *   block_rows or block_cols that is negative, no multiple of 128 or above 65 536. */
+int64_t sylber_dtw_strings_split_workspace_bytes(const int32_t* x_win_host, const int32_t* y_win_host, int32_t n_pairs, int32_t path,
+                                                 int32_t block_rows, int32_t block_cols);
+int sylber_dtw_strings_align_split(const float* x_dev, int32_t x_rows, const float* x_norm_dev, const float* y_dev, int32_t y_rows,
+                                   const float* y_norm_dev, int32_t D, int32_t metric, const int32_t* x_win_host, const int32_t* y_win_host,
+                                   int32_t n_pairs, int32_t path, const int64_t* rows_offset_host /* [n_pairs], with path */,
+                                   int32_t* rows_dev /* [*, 2], with path */, int32_t* steps_dev, float* cost_dev,
+                                   int32_t* steps_walk_dev /* nullable */, int32_t block_rows, int32_t block_cols, void* workspace_dev,
+                                   void* stream);
 
-/* Embedding strings, local (sylber_amd/search.py: local_align_sequences / SyllableIndex.local_align_sequences;
+/* Embedding strings, local(sylber_amd/search.py: local_align_sequences / SyllableIndex.local_align_sequences;
  * csrc/dtw_strings_local.hip; restated in tests/dtw_strings_local_ref.py): every repeat between two WHOLE embedding sequences --
  * the best sub-span of x against the best sub-span of y, up to n_best of them per pair, and with a band below the diagonal the
  * repeats inside ONE sequence.  "Embedding repeats" without the 64-row limit of a probe; what "Unit repeats, every one" is to

@@ -162,7 +162,11 @@ EXPORTS = {
     "sylber_dtw_strings_align": (c_int, [c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_int32, POINTER(c_int32),
                                          POINTER(c_int32), c_int32, c_int32, POINTER(c_int64), c_void_p, c_void_p, c_void_p, c_void_p,
                                          c_void_p, c_void_p]),
-    "sylber_dtw_strings_local_workspace_bytes": (c_int64, [POINTER(c_int32), POINTER(c_int32), c_int32]),
+    "sylber_dtw_strings_split_workspace_bytes": (c_int64, [POINTER(c_int32), POINTER(c_int32), c_int32, c_int32, c_int32, c_int32]),
+    "sylber_dtw_strings_align_split": (c_int, [c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_int32, POINTER(c_int32),
+                                               POINTER(c_int32), c_int32, c_int32, POINTER(c_int64), c_void_p, c_void_p, c_void_p, c_void_p,
+                                               c_int32, c_int32, c_void_p, c_void_p]),
+    "sylber_dtw_strings_local_workspace_bytes": (c_int64,[POINTER(c_int32), POINTER(c_int32), c_int32]),
     "sylber_dtw_strings_local": (c_int, [c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_int32, POINTER(c_int32),
                                          POINTER(c_int32), POINTER(c_int32), c_int32, c_float, c_float, c_float, c_int32, c_void_p, c_void_p,
                                          c_void_p, c_void_p]),

@@ -25,7 +25,7 @@ GEN_DIR = os.path.join(HERE, "build", "gen")           # generated inline-asm lo
 GEN_EXP_DIR = os.path.join(HERE, "build", "gen_exp")   # the knock-out / timing variants of the experiments build: their own directory, so that
                                                        # they neither ship with the product snapshot nor age the product's objects
 GENERATORS = [os.path.join(os.path.dirname(HERE), "tools", g) for g in ("gen_gemm_asm.py", "gen_attn_asm.py")]
-SOURCES = ["api.hip", "forward.hip", "ops.hip", "gemm_bf16.hip", "frontend.hip", "attention.hip", "posconv.hip", "segment.hip", "fp32_path.hip", "ingest.hip", "gemm_mxfp8.hip", "downstream.hip", "cfm.hip", "gemm_rowln.hip", "gemm_asm.hip", "gemm_asm_f8.hip", "gemm_asm16.hip", "flac_host.hip", "kmeans.hip", "knn.hip", "dtw.hip", "knn16.hip", "pq.hip", "dtw16.hip", "dtwpq.hip", "phrase_vote.hip", "dtw_align.hip", "dtw_codes.hip", "unit_search.hip", "unit_align.hip", "unit_strings.hip", "unit_repeats.hip", "unit_repeats_all.hip", "dtw_local.hip", "dtw_strings.hip", "dtw_strings_local.hip"]
+SOURCES = ["api.hip", "forward.hip", "ops.hip", "gemm_bf16.hip", "frontend.hip", "attention.hip", "posconv.hip", "segment.hip", "fp32_path.hip", "ingest.hip", "gemm_mxfp8.hip", "downstream.hip", "cfm.hip", "gemm_rowln.hip", "gemm_asm.hip", "gemm_asm_f8.hip", "gemm_asm16.hip", "flac_host.hip", "kmeans.hip", "knn.hip", "dtw.hip", "knn16.hip", "pq.hip", "dtw16.hip", "dtwpq.hip", "phrase_vote.hip", "dtw_align.hip", "dtw_codes.hip", "unit_search.hip", "unit_align.hip", "unit_strings.hip", "unit_repeats.hip", "unit_repeats_all.hip", "dtw_local.hip", "dtw_strings.hip", "dtw_strings_local.hip", "dtw_strings_split.hip"]
 EXTRA = {"segment.hip": ["-ffp-contract=off"]}
 # -fno-slp-vectorize: NO packed-fp32 VALU (v_pk_fma_f32 / v_pk_mul_f32 / v_pk_add_f32) anywhere in the library.  Measured on
 # MI355X / ROCm 7.2 (profiles/r02_packed_f32_hazard.md): a wave running dependent packed-fp32 chains returns wrong values

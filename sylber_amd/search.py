@@ -26,7 +26,8 @@ aligned to (csrc/dtw_align.hip, ``sylber_dtw_align``; tests/align_ref.py).
 windows of the index's own sequences -- against every sequence, in the same epilogue (csrc/dtw_local.hip, ``sylber_dtw_local``;
 tests/repeats_ref.py).
 ``align_sequences`` / ``SyllableIndex.align_sequences`` align two WHOLE sequences of any length, the global DTW with its path
-(csrc/dtw_strings.hip, ``sylber_dtw_strings_align``; tests/dtw_strings_ref.py).
+(csrc/dtw_strings.hip, ``sylber_dtw_strings_align``; tests/dtw_strings_ref.py); a call of few long pairs spreads each pair over the
+chip in blocks, with the same bits (``split=``; csrc/dtw_strings_split.hip, ``sylber_dtw_strings_align_split``).
 ``local_align_sequences`` / ``SyllableIndex.local_align_sequences`` are its LOCAL form: every repeat between two whole sequences,
 or inside one (csrc/dtw_strings_local.hip, ``sylber_dtw_strings_local``; tests/dtw_strings_local_ref.py).
 
@@ -55,6 +56,8 @@ OCC_RERANK_ENTRIES = 1 << 24    # list entries (24 B each with the merge rounds'
 MAX_WINDOW_ROWS = 65536         # DA_MAX_COLS of csrc/dtw_align.hip: the rows of a window that align_phrases walks (= MAX_SEQUENCE_ROWS)
 ALIGN_WORKSPACE_BYTES = 256 << 20       # the default pair_chunk of align_phrases keeps its workspace below this
 SEQUENCE_SUPER_ROWS = 128       # KN_BM of csrc/dtw_strings.hip: the rows of x that align_sequences takes between two carried rows
+SPLIT_BLOCK = (128, 128)        # DSS_BLOCK_ROWS, DSS_BLOCK_COLS of csrc/dtw_strings_split.hip: the blocks of a split pair by default
+SPLIT_MIN_CELLS = 256 * 256     # split=None: the smallest m L that is split (profiles/dtw_strings_split_bench.md, "The automatic threshold")
 
 
 # ---- repeated phrases: the three fp32 scalars of search_repeats / find_repeats ---------------------------------------------------
@@ -214,16 +217,91 @@ def dtw_strings_workspace_bytes(m, L, path: bool) -> np.ndarray:
     return rows + np.where((m > 0) & (L > 0), ((m + 63) // 64) * ((L + 127) // 128) * 2048, 0)
 
 
-def _check_sequence_pairs(ml: np.ndarray, Ll: np.ndarray, path: bool, pair_chunk) -> np.ndarray:
-    """the checks of ``align_sequences`` on the lengths of its pairs -> the workspace bytes of each pair, or ``ValueError``"""
+def _check_pair_chunk(pair_chunk) -> None:
     if pair_chunk is not None and (isinstance(pair_chunk, bool) or int(pair_chunk) != pair_chunk or int(pair_chunk) < 1):
         raise ValueError("pair_chunk must be an integer >= 1, got %r" % (pair_chunk,))
+
+
+def dtw_strings_split_workspace_bytes(m, L, path: bool, block_rows: int = 0, block_cols: int = 0) -> np.ndarray:
+    """int64: the bytes of workspace that each pair adds to a call of ``sylber_dtw_strings_align_split`` with these block sizes (0:
+    ``SPLIT_BLOCK``) beyond its 64 B of table, every term rounded up to 256 B: for a pair with two non-empty sides 256 B for its last
+    cell, two boundary rows of (A, n), ``16 L``, where it has more than one band of ``block_rows`` rows, two rows between a block's
+    own super-strips, ``16 L``, where ``block_rows > 128`` and ``m > 128``, two boundary columns with one corner per band,
+    ``16 (m + bands)``, where it has more than one chunk of ``block_cols`` columns, and with ``path`` the codes of
+    ``dtw_strings_workspace_bytes``"""
+    m, L = np.asarray(m, np.int64), np.asarray(L, np.int64)
+    BR, BC = int(block_rows) or SPLIT_BLOCK[0], int(block_cols) or SPLIT_BLOCK[1]
+    al = lambda b: (b + 255) // 256 * 256
+    nbr, nbc = (m + BR - 1) // BR, (L + BC - 1) // BC
+    some = (m > 0) & (L > 0)
+    state = 256 + np.where(nbr > 1, al(16 * L), 0) + np.where((m > SEQUENCE_SUPER_ROWS) & (BR > SEQUENCE_SUPER_ROWS), al(16 * L), 0) \
+        + np.where(nbc > 1, al(16 * (m + nbr)), 0)
+    out = np.where(some, state, 0)
+    if path:
+        out = out + np.where(some, ((m + 63) // 64) * ((L + 127) // 128) * 2048, 0)
+    return out
+
+
+def split_schedule(nbr: int, nbc: int) -> List[List[Tuple[int, int]]]:
+    """the launches of one split pair of ``nbr`` bands by ``nbc`` chunks, by the arithmetic of ``sylber_dtw_strings_align_split``
+    (dss_run and dtw_strings_split_kernel, restated for the tests and for whoever schedules blocks next): launch d has
+    ``min(d + 1, nbr, nbc, launches - d)`` workgroups, workgroup k takes block ``b = max(0, d - nbc + 1) + k``, ``c = d - b`` and
+    returns at once unless ``b < nbr`` and ``c >= 0``.  A block's inputs -- blocks ``(b-1, c)`` and ``(b, c-1)`` -- are then always of
+    the launch before.  Nothing in it knows the recurrence."""
+    launches = nbr + nbc - 1 if nbr > 0 and nbc > 0 else 0
+    out = []
+    for d in range(launches):
+        blocks = []
+        for k in range(min(d + 1, nbr, nbc, launches - d)):
+            b = max(0, d - nbc + 1) + k
+            if b < nbr and d - b >= 0:
+                blocks.append((b, d - b))
+        out.append(blocks)
+    return out
+
+
+def _split_plan(ml: np.ndarray, Ll: np.ndarray, split, pair_chunk, dev=None):
+    """what ``split`` asks for -> ``None`` (no pair is split) or ``(mask bool [S], block_rows, block_cols)``, or ``ValueError``.
+    ``None``: automatic, ``False``: never, ``True``: every pair larger than one block of ``SPLIT_BLOCK``, ``(block_rows, block_cols)``
+    (a test hook): every pair with two non-empty sides, in blocks of that size."""
+    if split is False:
+        return None
+    some = (ml > 0) & (Ll > 0)
+    if split is None or split is True:
+        BR, BC = SPLIT_BLOCK
+        mask = some & ((ml > BR) | (Ll > BC))
+        if split is None:
+            # the workgroups of a launch of today's entry are its pairs: split only where they would leave CUs idle
+            launch = int(ml.size) if pair_chunk is None else min(int(ml.size), int(pair_chunk))
+            if not mask.any() or launch >= torch.cuda.get_device_properties(dev).multi_processor_count:
+                return None
+            # at least two bands AND two chunks: a pair of one band or one chunk has one block per anti-diagonal, so its blocks
+            # would run one after the other, with a launch between them
+            mask = mask & (ml > BR) & (Ll > BC) & (ml * Ll >= SPLIT_MIN_CELLS)
+    else:
+        try:
+            BR, BC = split
+        except (TypeError, ValueError):
+            raise ValueError("split must be None, a bool or (block_rows, block_cols), got %r" % (split,)) from None
+        for v in (BR, BC):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 128 or v % 128 or v > MAX_SEQUENCE_ROWS:
+                raise ValueError("split = (block_rows, block_cols) must be multiples of 128 from 128 to %d, got %r" % (MAX_SEQUENCE_ROWS, split))
+        BR, BC, mask = int(BR), int(BC), some
+    return (mask, BR, BC) if mask.any() else None
+
+
+def _check_sequence_pairs(ml: np.ndarray, Ll: np.ndarray, path: bool, pair_chunk, plan=None) -> np.ndarray:
+    """the checks of ``align_sequences`` on the lengths of its pairs -> the workspace bytes of each pair (``plan``: ``_split_plan``'s,
+    the split pairs with the hand-over state of their blocks), or ``ValueError``"""
+    _check_pair_chunk(pair_chunk)
     for what, ln in (("xs", ml), ("ys", Ll)):
         if ln.size and int(ln.max()) > MAX_SEQUENCE_ROWS:
             raise ValueError("%s[%d] has %d rows, more than %d" % (what, int(ln.argmax()), int(ln.max()), MAX_SEQUENCE_ROWS))
         if int(ln.sum()) >= 2 ** 31:
             raise ValueError("one call takes fewer than 2^31 rows on each side")
     need = dtw_strings_workspace_bytes(ml, Ll, path) + 64
+    if plan is not None:
+        need = np.where(plan[0], dtw_strings_split_workspace_bytes(ml, Ll, path, plan[1], plan[2]) + 64, need)
     if need.size and int(need.max()) + 256 > ALIGN_WORKSPACE_BYTES:
         s = int(need.argmax())
         raise ValueError("pair %d (%d x %d rows) needs %d bytes of predecessor codes for its path, more than %d; path=False never "
@@ -244,10 +322,12 @@ def _launch_cuts(S: int, need: np.ndarray, pair_chunk) -> List[Tuple[int, int]]:
 
 
 def _align_windows(xd, xn, yd, yn, D: int, metric: str, xw: np.ndarray, yw: np.ndarray, need: np.ndarray, path: bool, pair_chunk, fill,
-                   dev, _steps_walk: bool = False):
+                   dev, _steps_walk: bool = False, plan=None):
     """``sylber_dtw_strings_align`` on the pairs of windows ``xw, yw`` int32 ``[S, 2]`` = (first row, rows) into the prepared rows
     ``xd, yd`` with norms ``xn, yn`` (``None`` under cosine), behind every check -> ``(rows int32 [sum m, 2] or None, costs, steps,
-    x offsets int64 on the host)``; the launches are grouped as ``_align_strings`` groups them"""
+    x offsets int64 on the host)``; the launches are grouped as ``_align_strings`` groups them.  ``plan``: ``_split_plan``'s; its
+    pairs go to ``sylber_dtw_strings_align_split`` in calls of their own, grouped the same way, and every output lands in the caller's
+    order."""
     S = int(xw.shape[0])
     xo = np.concatenate([[0], np.cumsum(xw[:, 1], dtype=np.int64)]).astype(np.int64)
     costs = torch.empty((S,), dtype=torch.float32, device=dev)
@@ -256,32 +336,56 @@ def _align_windows(xd, xn, yd, yn, D: int, metric: str, xw: np.ndarray, yw: np.n
     rows = torch.empty((max(int(xo[-1]), 1), 2), dtype=torch.int32, device=dev) if path else None
     if S:
         lib = _lib.load()
-        groups = []
-        for g0, g1 in _launch_cuts(S, need, pair_chunk):
-            x32, y32 = np.ascontiguousarray(xw[g0:g1], np.int32), np.ascontiguousarray(yw[g0:g1], np.int32)
-            size = int(lib.sylber_dtw_strings_workspace_bytes(x32.ctypes.data_as(_i32p), y32.ctypes.data_as(_i32p), g1 - g0, int(path)))
-            if size < 0:
-                raise _lib.SylberHipError("sylber_dtw_strings_workspace_bytes refused the call")
-            groups.append((g0, g1, x32, y32, np.ascontiguousarray(xo[g0:g1], np.int64), size))
-
-        def at(t, row):                                    # the address of element `row` of a non-empty 4-byte tensor
-            return ctypes.c_void_p(t.data_ptr() + int(row) * 4)
-
+        parts = [(None, None)] if plan is None else [(np.flatnonzero(~plan[0]), None), (np.flatnonzero(plan[0]), (plan[1], plan[2]))]
         with torch.cuda.device(dev):
             st = _stream(dev)
-            ws = None
-            for g0, g1, x32, y32, ro, size in groups:
-                if ws is None or ws.numel() != size:       # every launch gets exactly what its size function asked for
-                    ws = torch.empty(size, dtype=torch.uint8, device=dev)
-                    if fill is not None:
-                        ws.fill_(fill)
-                _lib.check(lib.sylber_dtw_strings_align(_vp(xd), int(xd.shape[0]), _vp(xn), _vp(yd), int(yd.shape[0]), _vp(yn), D, METRICS[metric],
-                                                        x32.ctypes.data_as(_i32p), y32.ctypes.data_as(_i32p), g1 - g0, int(path),
-                                                        ro.ctypes.data_as(_i64p) if path else None, _vp(rows), at(steps, g0), at(costs, g0),
-                                                        at(walk, g0) if walk is not None else None, _vp(ws), st), "sylber_dtw_strings_align")
+            for sel, blocks in parts:
+                if sel is None or sel.size == S:           # the whole call: straight into the outputs
+                    _align_launches(lib, xd, xn, yd, yn, D, metric, xw, yw, need, xo[:-1], path, pair_chunk, fill, dev, st, blocks,
+                                    rows, costs, steps, walk)
+                elif sel.size:                             # a part: its pairs side by side, then to their places
+                    n = int(sel.size)
+                    c, s = torch.empty((n,), dtype=torch.float32, device=dev), torch.empty((n,), dtype=torch.int32, device=dev)
+                    w = torch.empty((n,), dtype=torch.int32, device=dev) if walk is not None else None
+                    _align_launches(lib, xd, xn, yd, yn, D, metric, xw[sel], yw[sel], need[sel], xo[:-1][sel], path, pair_chunk, fill, dev,
+                                    st, blocks, rows, c, s, w)
+                    at = torch.from_numpy(sel).to(dev)
+                    costs[at], steps[at] = c, s
+                    if walk is not None:
+                        walk[at] = w
     if path:
         rows = rows[:int(xo[-1])]
     return (rows, costs, steps, xo) + ((walk,) if _steps_walk else ())
+
+
+def _align_launches(lib, xd, xn, yd, yn, D: int, metric: str, xw, yw, need, ro_all, path: bool, pair_chunk, fill, dev, st, blocks,
+                    rows, costs, steps, walk) -> None:
+    """the calls of ``sylber_dtw_strings_align`` (``blocks`` None) or ``sylber_dtw_strings_align_split`` (``blocks`` = its block sizes)
+    on these pairs, ``_launch_cuts`` pairs each: pair p writes ``costs[p]``, ``steps[p]`` and its runs at ``rows[ro_all[p]:]``"""
+    name = "sylber_dtw_strings_align" if blocks is None else "sylber_dtw_strings_align_split"
+    size_of = lib.sylber_dtw_strings_workspace_bytes if blocks is None else lib.sylber_dtw_strings_split_workspace_bytes
+    more = () if blocks is None else (int(blocks[0]), int(blocks[1]))
+    groups = []
+    for g0, g1 in _launch_cuts(int(xw.shape[0]), need, pair_chunk):
+        x32, y32 = np.ascontiguousarray(xw[g0:g1], np.int32), np.ascontiguousarray(yw[g0:g1], np.int32)
+        size = int(size_of(x32.ctypes.data_as(_i32p), y32.ctypes.data_as(_i32p), g1 - g0, int(path), *more))
+        if size < 0:
+            raise _lib.SylberHipError("sylber_dtw_strings_%sworkspace_bytes refused the call" % ("" if blocks is None else "split_"))
+        groups.append((g0, g1, x32, y32, np.ascontiguousarray(ro_all[g0:g1], np.int64), size))
+
+    def at(t, row):                                        # the address of element `row` of a non-empty 4-byte tensor
+        return ctypes.c_void_p(t.data_ptr() + int(row) * 4)
+
+    ws = None
+    for g0, g1, x32, y32, ro, size in groups:
+        if ws is None or ws.numel() != size:               # every launch gets exactly what its size function asked for
+            ws = torch.empty(size, dtype=torch.uint8, device=dev)
+            if fill is not None:
+                ws.fill_(fill)
+        _lib.check(getattr(lib, name)(_vp(xd), int(xd.shape[0]), _vp(xn), _vp(yd), int(yd.shape[0]), _vp(yn), D, METRICS[metric],
+                                      x32.ctypes.data_as(_i32p), y32.ctypes.data_as(_i32p), g1 - g0, int(path),
+                                      ro.ctypes.data_as(_i64p) if path else None, _vp(rows), at(steps, g0), at(costs, g0),
+                                      at(walk, g0) if walk is not None else None, *more, _vp(ws), st), name)
 
 
 def _sequence_rows(seqs, what: str):
@@ -310,7 +414,7 @@ def _flat_rows(parts, D: int, metric: str, dev):
 
 
 def align_sequences(xs, ys, *, metric: str = "l2", path: bool = False, device="cuda", pair_chunk: Optional[int] = None,
-                    _workspace_fill=None, _steps_walk: bool = False):
+                    split=None, _workspace_fill=None, _steps_walk: bool = False):
     """how two whole recordings line up, syllable by syllable or frame by frame: the global DTW of whole embedding sequences of any
     length up to 65 536 rows, pair by pair (csrc/dtw_strings.hip, ``sylber_dtw_strings_align``; contract in include/sylber_hip.h
     "Embedding strings", restated in tests/dtw_strings_ref.py).  ``xs`` and ``ys``: equally long lists of ``[m, D]`` float arrays or
@@ -343,7 +447,18 @@ def align_sequences(xs, ys, *, metric: str = "l2", path: bool = False, device="c
     cell, about ``m L / 4`` bytes.  ``ValueError`` before any allocation or launch: lists of different length, differing widths or
     a width that is no multiple of 16, a non-float input, a side of more than 65 536 rows, 2^31 or more rows in total on a side,
     ``pair_chunk < 1``, and with ``path`` a single pair whose codes exceed ``ALIGN_WORKSPACE_BYTES``.  ``S = 0`` returns empty
-    tensors without a launch."""
+    tensors without a launch.
+
+    ``split``: one pair in one workgroup takes ``m L`` time on one CU of 256 (0.64 s for 8192 x 8192 at D = 768).  A split pair is
+    cut into blocks of ``SPLIT_BLOCK`` rows by columns; the blocks of one anti-diagonal run side by side, one launch per
+    anti-diagonal (csrc/dtw_strings_split.hip, ``sylber_dtw_strings_align_split``), and every cell is computed by the same code in
+    the same order, so the results are the unsplit ones bit for bit.  ``None`` (default): a pair is split when the call's launch
+    has fewer pairs than the chip has CUs, the pair has at least two blocks each way (with one band or one chunk no two blocks
+    ever run side by side) and ``m L >= SPLIT_MIN_CELLS`` (profiles/dtw_strings_split_bench.md); ``False``: never; ``True``: every pair larger than one block; ``(block_rows,
+    block_cols)``, multiples of 128: a test hook, every pair with two non-empty sides in blocks of that size.  The split pairs of a
+    call share one workspace and one loop over anti-diagonals per ``pair_chunk`` of them, the others go through the one-workgroup
+    kernel as before, and the outputs come back in the caller's order.  A split pair adds to its workspace what
+    ``dtw_strings_split_workspace_bytes`` says: about ``32 L + 16 m`` bytes of boundary rows and columns in place of ``16 L``."""
     if metric not in METRICS:
         raise ValueError("metric must be 'l2' or 'cosine', got %r" % (metric,))
     xp, ml, Dx = _sequence_rows(xs, "xs")
@@ -356,15 +471,19 @@ def align_sequences(xs, ys, *, metric: str = "l2", path: bool = False, device="c
     D = Dx or Dy
     if D is not None and (D < 16 or D % 16):
         raise ValueError("the feature width D must be a multiple of 16, got %d" % D)
+    _split_plan(ml, Ll, False if split is None else split, None)       # what is wrong with `split` itself
     need = _check_sequence_pairs(ml, Ll, path, pair_chunk)
     dev = _device(device)
+    plan = _split_plan(ml, Ll, split, pair_chunk, dev)
+    if plan is not None:
+        need = _check_sequence_pairs(ml, Ll, path, pair_chunk, plan)
     xw = np.stack([np.cumsum(ml) - ml, ml], 1).astype(np.int32).reshape(S, 2)
     yw = np.stack([np.cumsum(Ll) - Ll, Ll], 1).astype(np.int32).reshape(S, 2)
     if S == 0:
         xd = xn = yd = yn = None
     else:
         (xd, xn), (yd, yn) = _flat_rows(xp, D, metric, dev), _flat_rows(yp, D, metric, dev)
-    out = _align_windows(xd, xn, yd, yn, D or 16, metric, xw, yw, need, path, pair_chunk, _workspace_fill, dev, _steps_walk)
+    out = _align_windows(xd, xn, yd, yn, D or 16, metric, xw, yw, need, path, pair_chunk, _workspace_fill, dev, _steps_walk, plan)
     rows, costs, steps, xo = out[:4]
     res = (rows.to(torch.int64), costs, steps, torch.from_numpy(xo).to(dev)) if path else (costs, steps)
     return res + tuple(out[4:])
@@ -901,7 +1020,8 @@ class SyllableIndex:
 
         return _align_phrases(N, self.dim, self.device, self.metric, phrases, spans, lengths, pair_chunk, run, _tracked_start)
 
-    def align_sequences(self, pairs, *, path: bool = False, pair_chunk: Optional[int] = None, sequences=None, _workspace_fill=None):
+    def align_sequences(self, pairs, *, path: bool = False, pair_chunk: Optional[int] = None, sequences=None, split=None,
+                        _workspace_fill=None):
         """``align_sequences`` between stored sequences, with no copy: ``pairs`` int ``[S, 2]`` (host or device) are sequence numbers
         of the index, x then y -- by default of ``sequence_offsets()``, or of ``sequences=`` as ``search_phrases`` takes them.  The
         windows go into the index's own rows with its stored norms (unit rows under ``"cosine"``), so the result is the free
@@ -909,7 +1029,8 @@ class SyllableIndex:
         With it: ``(rows int64 [sum m, 2], costs, steps, x_offsets int64 [S + 1])`` where ``rows`` are row ids of the index (``lo``
         and ``hi`` shifted by y's first row, padding stays ``(-1, -1)``): ``align_phrases`` and ``provenance`` take them.
         ``ValueError`` before any launch: an empty index, ``pairs`` of another shape or dtype, a sequence number outside
-        ``[0, number of sequences)``, and what ``align_sequences`` refuses of ``pair_chunk`` and of a pair's codes."""
+        ``[0, number of sequences)``, and what ``align_sequences`` refuses of ``pair_chunk``, of ``split`` and of a pair's codes.
+        ``split`` is ``align_sequences``'s: by default a call of few long pairs spreads each over the chip, with the same bits."""
         N = len(self)
         if N == 0:
             raise ValueError("the index is empty")
@@ -925,11 +1046,13 @@ class SyllableIndex:
             raise ValueError("pairs must name sequences in [0, %d)" % nseq)
         path = bool(path)
         first, length = off[:-1][pr], np.diff(off)[pr]      # [S, 2] each
-        need = _check_sequence_pairs(length[:, 0], length[:, 1], path, pair_chunk)
+        _check_pair_chunk(pair_chunk)
+        plan = _split_plan(length[:, 0], length[:, 1], split, pair_chunk, self.device)
+        need = _check_sequence_pairs(length[:, 0], length[:, 1], path, pair_chunk, plan)
         xw = np.stack([first[:, 0], length[:, 0]], 1).astype(np.int32)
         yw = np.stack([first[:, 1], length[:, 1]], 1).astype(np.int32)
         rows, costs, steps, xo = _align_windows(self._x, self._c, self._x, self._c, self.dim, self.metric, xw, yw, need, path, pair_chunk,
-                                                _workspace_fill, self.device)
+                                                _workspace_fill, self.device, plan=plan)
         if not path:
             return costs, steps
         rows = rows.to(torch.int64)
@@ -1446,9 +1569,9 @@ class IVFSyllableIndex:
         (in id order) are the ones the exact re-rank ran on -> ``(rows, steps, costs)`` as there"""
         return self.index.align_phrases(phrases, spans, lengths=lengths, pair_chunk=pair_chunk)
 
-    def align_sequences(self, pairs, *, path: bool = False, pair_chunk: Optional[int] = None, sequences=None):
+    def align_sequences(self, pairs, *, path: bool = False, pair_chunk: Optional[int] = None, sequences=None, split=None):
         """the global DTW of whole stored sequences: ``ivf.index.align_sequences`` on the rows in id order"""
-        return self.index.align_sequences(pairs, path=path, pair_chunk=pair_chunk, sequences=sequences)
+        return self.index.align_sequences(pairs, path=path, pair_chunk=pair_chunk, sequences=sequences, split=split)
 
     def local_align_sequences(self, pairs, radius, *, gap=None, min_score=None, n_best: int = 1, min_sep: int = 1,
                               pair_chunk: Optional[int] = None, sequences=None):
