@@ -172,7 +172,11 @@ int sylber_flac_decode(const uint8_t* data_host, int64_t size, int32_t* out_host
 /* N4: k-means tokenisation, KMQuantizer.get_indices (sylber/model/quantizer.py:86-111; codebook look-up of
  * vector_quantize_pytorch's EuclideanCodebook: argmin_c ||x - c||, first index on ties).
  *   feats_dev [n, D] fp32 (D % 16 == 0), centroids_dev [K, D] fp32, normalize != 0: x / sqrt(sum x^2 + 1e-8) * 6 first
- *   idx_dev [n] int32; workspace_dev: sylber_km_workspace_floats(n, K, D) floats.  Exact-fp32 contraction. */
+ *   idx_dev [n] int32; workspace_dev: sylber_km_workspace_floats(n, K, D) floats.  Exact-fp32 contraction.
+ *   Ids are always in [0, K): a NaN score is never chosen, and a row whose scores are all NaN (a NaN or inf - inf token) gets id 0,
+ *   upstream's argmax of an all-NaN row.  The same holds for sylber_km_assign_residual and sylber_rvq_assign.  (sylber_kmeans_assign
+ *   differs on purpose: such a row gets 2147483647 there, "no nearest centroid", which the inverted-file indexes read as "in no list".)
+ *   K < 4 with K % 4 != 0 is refused. */
 int64_t sylber_km_workspace_floats(int32_t n, int32_t K, int32_t D);
 int sylber_km_assign(const float* feats_dev, int32_t n, const float* centroids_dev, int32_t K, int32_t D, int32_t normalize,
                      int32_t* idx_dev, float* workspace_dev, void* stream);

@@ -36,7 +36,8 @@ __global__ __launch_bounds__(256) void km_sqnorm_kernel(const float* __restrict_
     if (lane == 0) out[r] = s;
 }
 // idx[r] = argmin_c (||c||^2 - 2 x.c)  (the ||x||^2 term and the square root of cdist are monotone / constant per
-// row); ties -> the smallest index, like argmax over -cdist returns the first maximum
+// row); ties -> the smallest index, like argmax over -cdist returns the first maximum.  A NaN score compares false and is never
+// taken; a row whose scores are all NaN (a NaN or inf - inf token) gets index 0, which is what that argmax returns for it
 __global__ __launch_bounds__(256) void km_argmin_kernel(const float* __restrict__ dots, long ld, const float* __restrict__ cn,
                                                         int32_t* __restrict__ idx, int istride, int n, int K) {
     __shared__ float bv[4]; __shared__ int bi[4];
@@ -56,7 +57,7 @@ __global__ __launch_bounds__(256) void km_argmin_kernel(const float* __restrict_
     __syncthreads();
     if (threadIdx.x == 0) {
         for (int w = 1; w < 4; ++w) if (bv[w] < best || (bv[w] == best && bi[w] < besti)) { best = bv[w]; besti = bi[w]; }
-        idx[(size_t)r * istride] = besti;
+        idx[(size_t)r * istride] = besti < K ? besti : 0;
     }
 }
 

@@ -81,7 +81,9 @@ def assign(x: torch.Tensor, centroids: torch.Tensor, prev: Optional[torch.Tensor
     """the fused assign (``sylber_kmeans_assign``) of contiguous fp32 rows ``x [n, D]`` against ``centroids [K, D]`` on one device ->
     ``(labels int32 [n], d_min fp32 [n], inertia float, changed int or None)``; ``d_min[r] = ||c||^2 - 2 x.c`` of the chosen centroid.
     ``row_chunk`` runs the rows in chunks of that many (labels and d_min do not depend on it; the inertia is summed per chunk, then
-    over the chunks in order)."""
+    over the chunks in order).  A row without a comparable score (it holds a NaN, or its dot products are inf - inf) has no nearest
+    centroid: its label is 2147483647, never one in ``[0, K)``, and its ``d_min`` is +inf.  The fits refuse non-finite features before
+    they get here; the inverted-file indexes put such a row in no list.  (``KMQuantizer.get_indices`` gives such a token id 0.)"""
     lib = _lib.load()
     dev = x.device
     n, D = x.shape

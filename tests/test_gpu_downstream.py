@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 import torch
 
+import tokenizer_ref as T
 from oracle import downstream_ref as R
 from sylber_amd.synth_states import syllable_states
 from sylber_amd.weights import synthetic_mlp_state_dict, synthetic_state_dict
@@ -30,6 +31,8 @@ def test_km_assign_matches_oracle(n, K, normalize):
     for r in np.nonzero(~same)[0]:
         assert abs(d2[r, got[r]] - d2[r, exp[r]]) <= 1e-4 * abs(d2[r, exp[r]]) + 1e-4
     assert same.mean() > 0.99
+    s, bnd = T.km_bounds(x, c, normalize)                        # and every row under the id rule of tests/tokenizer_ref.py
+    assert T.judge_ids(s, bnd, got) == []
     if not normalize:
         assert got[0] == K - 1
     dec = q.decode(torch.from_numpy(idx)).cpu().numpy()

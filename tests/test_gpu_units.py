@@ -83,7 +83,12 @@ def test_residual_ids_match_restatement(gold):
             ties += 1
     print("residual ids: %d of %d rows on a numerical tie" % (ties, len(x)))
     assert ties <= 3
-    dec = q.decode(torch.from_numpy(idx)).cpu().numpy()
+    # and every row under the id rule of tests/tokenizer_ref.py, stage 2 on the residual of the device's own stage-1 id
+    import tokenizer_ref as T
+    s1, b1 = T.km_bounds(x, c1, False)
+    s2, b2 = T.km_bounds((x - c1[got[:, 0]]).astype(np.float32), c2, False)
+    assert T.judge_ids(s1, b1, got[:, 0]) == [] and T.judge_ids(s2, b2, got[:, 1]) == []
+    dec =q.decode(torch.from_numpy(idx)).cpu().numpy()
     assert np.array_equal(dec[0], c1[got[:, 0]] + c2[got[:, 1]])
     out = q(torch.from_numpy(x[:4]).cuda())
     assert torch.equal(out["indices"].cpu(), torch.from_numpy(got[:4]))
